@@ -7,7 +7,10 @@ through HybridIndex's search (IVF coarse + list scan + top-k and the whole HNSW 
 stable merge on the host).  Query batches are resident in HBM before the timed region starts; every step's results are
 complete, in host memory, inside it (the reference API returns them to the caller).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+--dump-outputs writes the results of the last of the K timed steps to DIR/{ids,distances,counts}.npy.  Data and queries
+are functions of the arguments alone; the operating point is too once --nprobe and --ef are given (left at 0 it is chosen
+by the recall the build under test reaches), so pin both when the dumps of two builds are to be compared.
 N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank per
 GPU.  IVF lists are sharded over the ranks, the graph is replicated; both exchange steps of a search run over RCCL
 inside the engine's C ABI (fvdb_comm_*, fvdb_ivf_search_sharded_begin/_end).  torch.distributed (gloo, CPU) only
@@ -115,6 +118,31 @@ def recall_at_k(found_ids, found_cnt, exact_ids, k):
     return hits / (k * max(found_ids.shape[0], 1))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, distances, counts, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller, as out_dir/{ids,distances,counts}.npy (ids and
+    counts widened to float64, distances as the f32 they are), so that two builds run with the same arguments can be
+    compared array for array.  The API pads a row past the query's hit count with FVDB_NO_ID (UINT64_MAX) / +inf
+    (include/fvdb.h); neither survives a comparison by difference (UINT64_MAX is not a float64, inf - inf is NaN), so
+    those slots are written as -1.  Should the arrays of all ranks together exceed DUMP_LIMIT_BYTES, a fixed seeded
+    sample of the queries is kept."""
+    row_bytes = ids.shape[1] * (8 + 4) + 8
+    room = DUMP_LIMIT_BYTES // world - 4096  # the three .npy headers
+    if ids.shape[0] * row_bytes > room:
+        keep = np.sort(np.random.Generator(np.random.Philox(key=4321)).choice(ids.shape[0], room // row_bytes, replace=False))
+        ids, distances, counts = ids[keep], distances[keep], counts[keep]
+    live = np.arange(ids.shape[1])[None, :] < counts[:, None]
+    assert not live.any() or int(ids[live].max()) < 2 ** 53, "ids are not exact in float64"
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""  # every rank returns rows of its own
+    np.save(os.path.join(out_dir, f"ids{suffix}.npy"), np.where(live, ids.astype(np.float64), -1.0))
+    np.save(os.path.join(out_dir, f"distances{suffix}.npy"), np.where(live, distances, np.float32(-1.0)))
+    np.save(os.path.join(out_dir, f"counts{suffix}.npy"), counts.astype(np.float64))
+    log(f"dumped the last timed step's results ({ids.shape[0]} queries) to {out_dir}")
+
+
 def exact_ground_truth(fv, ctx, x, ids, queries, k):
     """Flat f32 scan on the GPU (exact k-NN)."""
     N, d = x.shape
@@ -132,6 +160,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of the last timed step to DIR/{ids,distances,counts}.npy (see dump_outputs)")
     ap.add_argument("--n-vectors", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=384)
     ap.add_argument("--batch", type=int, default=1024)
@@ -398,6 +428,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.ids, last.distances, last.counts, rank, world)
     # host share of a step: collect + translate + merge of batches whose GPU work is already complete
     host_collect_ms = None
     if depth > 1:
@@ -687,6 +719,8 @@ def run_ivf_config(args):
     qps = B * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     log(f"{args.steps} steps: {ms_per_step:.3f} ms/step, {qps:.0f} QPS, recall@{k}={recall:.4f}, rescans {ivf.scan_fallbacks() - f0}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *result((args.steps - 1) % depth))
     # per-stage / per-kernel durations, one batch at a time (HIP events on the launch stream)
     ctx.set_profiling(1)
     ivf.stage_times()

@@ -1,21 +1,25 @@
 """The driver-facing contract of bench.py, on a small workload: stdout carries exactly ONE JSON line with the agreed
 keys, `roofline` and `cpu_baseline` objects included, the roofline fraction is a fraction, and the GPU answers of the
-sample equal the oracle's."""
+sample equal the oracle's; --dump-outputs leaves the results of the last timed step, whichever way the steps ran."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+import bench
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_prints_one_json_line_with_the_contract_fields():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n-vectors", "60000", "--nlist", "64", "--steps", "6",
-           "--warmup", "1", "--query-batches", "4", "--select-batches", "2", "--cpu-sample", "64", "--compare-host-walk", "1",
-           "--train-sample", "20000", "--batch", "256", "--insert-sample", "256"]
+def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
+    shape = [sys.executable, os.path.join(ROOT, "bench.py"), "--n-vectors", "60000", "--nlist", "64", "--steps", "6",
+             "--warmup", "1", "--query-batches", "4", "--train-sample", "20000", "--batch", "256"]
+    cmd = shape + ["--select-batches", "2", "--cpu-sample", "64", "--compare-host-walk", "1", "--insert-sample", "256",
+                   "--dump-outputs", str(tmp_path / "pipelined")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -45,3 +49,46 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
         assert key in ins, key
     assert ins["unit"] == "inserts/s" and ins["value"] > 0 and ins["cpu_value"] > 0 and ins["cpu_cores"] == 1
     assert ins["graph_matches_oracle_on_sample"] is True and ins["device_insert"]["host_path_inserts"] == 0
+    # --dump-outputs: what search_dev_end returned for the last of the 6 timed steps
+    ids, dist, cnt = (np.load(tmp_path / "pipelined" / f"{n}.npy") for n in ("ids", "distances", "counts"))
+    assert ids.dtype == np.float64 and dist.dtype == np.float32 and cnt.dtype == np.float64
+    assert ids.shape == dist.shape == (256, 10) and cnt.shape == (256,)
+    assert cnt.min() >= 1 and cnt.max() <= 10
+    live = np.arange(10)[None, :] < cnt[:, None]
+    assert (ids[live] >= 0).all() and (ids[live] < 60000).all() and (dist[live] >= 0).all()
+    assert (ids[~live] == -1).all() and (dist[~live] == -1).all()
+    # ... of THAT step: step 5 of 6 over 4 query batches searched batch 1 (the warm-up ends on batches 0 and 3, step 0
+    # searched batch 0), so every returned row lies at the returned distance from its query of batch 1, and the rows are
+    # the batch's nearest ones
+    gen = bench.Generator()
+    x = np.concatenate([gen.rows(10_000, stream=c) for c in range(6)]).astype(np.float64)
+    q = gen.rows(256, stream=10_000_000 + 1).astype(np.float64)
+    qi, slot = np.nonzero(live)
+    assert np.allclose(np.linalg.norm(x[ids[live].astype(np.int64)] - q[qi], axis=1), dist[live], rtol=1e-4)
+    d2 = (q * q).sum(1)[:, None] - 2.0 * q @ x.T + (x * x).sum(1)[None, :]
+    exact = np.argsort(d2, axis=1)[:, :10]
+    assert bench.recall_at_k(ids.astype(np.int64), cnt.astype(np.int64), exact, 10) >= 0.9
+    # the same step collected one batch at a time (search_dev instead of search_dev_begin / _end), at the operating
+    # point the first run chose: the same arrays
+    one = shape + ["--in-flight", "1", "--nprobe", str(j["config"]["nprobe"]), "--ef", str(j["config"]["hnsw_ef"]),
+                   "--no-cpu-baseline", "--compare-host-walk", "0", "--insert-sample", "0", "--dump-outputs", str(tmp_path / "one")]
+    p = subprocess.run(one, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    for n, a in (("ids", ids), ("distances", dist), ("counts", cnt)):
+        assert np.array_equal(np.load(tmp_path / "one" / f"{n}.npy"), a), n
+
+
+def test_dump_outputs_takes_rows_with_fewer_than_k_hits(tmp_path):
+    # c2 with ONE probed list (about 100 rows each) and k = 100: many queries get fewer than k hits, the search pads
+    # their rows with FVDB_NO_ID / +inf, and the dump writes that padding as -1
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--nprobe", "1", "--k", "100", "--steps", "3",
+           "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len([ln for ln in p.stdout.splitlines() if ln.strip()]) == 1, p.stdout[:2000]
+    ids, dist, cnt = (np.load(tmp_path / f"{n}.npy") for n in ("ids", "distances", "counts"))
+    assert ids.shape == dist.shape == (256, 100) and cnt.shape == (256,)
+    assert cnt.min() < 100 and cnt.max() <= 100
+    live = np.arange(100)[None, :] < cnt[:, None]
+    assert (ids[live] >= 0).all() and (ids[live] < 100_000).all() and np.isfinite(dist[live]).all() and (dist[live] >= 0).all()
+    assert (ids[~live] == -1).all() and (dist[~live] == -1).all()
