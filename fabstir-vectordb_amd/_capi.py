@@ -102,6 +102,8 @@ SIGNATURES = {
     "fvdb_graph_entry": (i32, [vp, u32p, u32p]),
     "fvdb_graph_download": (i32, [vp, u32p, u32p, u64, u64p]),
     "fvdb_graph_upload_bytes": (u64, [vp]),
+    "fvdb_graph_set_insert_visited": (i32, [vp, i32, u32]),
+    "fvdb_graph_insert_info": (i32, [vp, u32, vp]),
     "fvdb_graph_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_graph_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ctx_device": (i32, [vp]),

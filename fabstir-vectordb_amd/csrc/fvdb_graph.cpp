@@ -37,6 +37,11 @@ struct fvdb_graph {
   std::vector<uint32_t> h_level, h_ubase;
   uint64_t upload_bytes = 0;        // host -> device bytes of graph STRUCTURE (not vectors) since creation
   fvdb_graph_insert_stats last{};
+  // form of the device insert's `visited` (fvdb_graph_set_insert_visited) and what the hashed form has seen since creation
+  int ins_vis_mode = 0;
+  uint32_t ins_vis_slots = 0;
+  uint64_t ins_hashed = 0, ins_vis_over = 0, ins_vis_searches = 0, ins_vis_entries = 0;
+  uint32_t ins_vis_peak = 0;
   DBuf s_q, d_counters;
   uint64_t tot_queries = 0, tot_again = 0;  // traversal counters [3], [2] folded in at every fvdb_graph_kernel_times
   static constexpr uint32_t kSlots = 16;  // batches that may be in flight at once, each on its own stream
@@ -180,6 +185,71 @@ BuildView build_view(fvdb_graph* g, uint32_t ef, uint32_t cand_cap) {
     else if (nb128_ <= 6) FVDB_BUILD_DISPATCH(6, false, __VA_ARGS__);          \
     else FVDB_BUILD_DISPATCH(8, false, __VA_ARGS__);                           \
   } while (0)
+
+// ... and per form of the insert's `visited` (HASH_: kernels_graph_build.h, Visited<>)
+#define FVDB_BUILD_SWITCH_V(dpad, hashed, ...)      \
+  do {                                              \
+    if (hashed) {                                   \
+      constexpr bool HASH_ = true;                  \
+      FVDB_BUILD_SWITCH(dpad, __VA_ARGS__);         \
+    } else {                                        \
+      constexpr bool HASH_ = false;                 \
+      FVDB_BUILD_SWITCH(dpad, __VA_ARGS__);         \
+    }                                               \
+  } while (0)
+
+// What fvdb_graph_insert_linked would put in LDS for this graph now.  The fixed tables come first; `visited` and the
+// restated `candidates` heap (512 .. 4096 slots) share what is left of the budget.
+//   bitmap: one bit per node index — serves the graph while that still leaves the heap its minimum;
+//   hashed: a table of node indices whose size does not depend on the graph — by default the largest power of two
+//           that leaves the heap 2048 slots (8192 at ef_construction 200).
+// FVDB_BUILD_LDS_LIMIT (the LDS budget, default 160 KiB) and FVDB_BUILD_BITMAP_MAX_NODES (a cap on the node count the
+// bitmap serves) are test hooks, read at every call: they bring a small graph to the limits.
+struct InsertPlan {
+  uint32_t repr = 0;  // 0: nothing fits, 1 bitmap, 2 hashed
+  uint32_t words = 0, slots = 0, cand_cap = 0, lds_bytes = 0, bitmap_max_nodes = 0;
+  const char* why = "";
+};
+InsertPlan insert_plan(const fvdb_graph* g, uint32_t ef) {
+  InsertPlan p;
+  const uint32_t lds_max = getenv("FVDB_BUILD_LDS_LIMIT") ? (uint32_t)atoi(getenv("FVDB_BUILD_LDS_LIMIT")) : 160u * 1024u;
+  const uint32_t fixed0 = build_lds_layout(0, ef, 0).total;
+  const uint32_t kMinCand = 512 * 8;
+  const uint32_t room = lds_max > fixed0 ? lds_max - fixed0 : 0;  // bytes for `visited` + `candidates`
+  uint64_t bmax = room > kMinCand ? (uint64_t)((room - kMinCand) / 16) * 128 : 0;  // (the carve is padded to 16 bytes)
+  if (getenv("FVDB_BUILD_BITMAP_MAX_NODES")) bmax = std::min<uint64_t>(bmax, (uint64_t)atoll(getenv("FVDB_BUILD_BITMAP_MAX_NODES")));
+  p.bitmap_max_nodes = (uint32_t)std::min<uint64_t>(bmax, 0x7FFFFFFFu);
+  auto cand_for = [&](uint32_t visited_bytes) -> uint32_t {
+    return room >= visited_bytes ? std::min<uint32_t>(4096, ((room - visited_bytes) / 8) & ~1u) : 0u;
+  };
+  const bool bitmap_ok = g->n <= p.bitmap_max_nodes;
+  uint32_t slots = 0;
+  if (g->ins_vis_slots) {
+    if (cand_for(g->ins_vis_slots * 4) >= 512) slots = g->ins_vis_slots;
+  } else {
+    for (uint32_t need : {2048u, 512u}) {
+      for (uint32_t s2 = 32768; s2 >= 256 && !slots; s2 >>= 1)
+        if (cand_for(s2 * 4) >= need) slots = s2;
+      if (slots) break;
+    }
+  }
+  if (g->ins_vis_mode != 2 && bitmap_ok) {
+    p.repr = 1;
+    p.words = (g->n + 31) / 32;
+    p.cand_cap = cand_for((p.words * 4 + 15u) & ~15u);
+  } else if (g->ins_vis_mode != 1 && slots) {
+    p.repr = 2;
+    p.words = p.slots = slots;
+    p.cand_cap = cand_for(slots * 4);
+  } else {
+    p.why = g->ins_vis_mode == 2 ? "device insert: the LDS budget does not hold the hashed visited set"
+            : g->ins_vis_mode == 1 || !bitmap_ok ? "device insert: graph too large for the on-chip visited bitmap"
+                                                 : "device insert: the LDS budget holds neither form of the visited set";
+    return p;
+  }
+  p.lds_bytes = build_lds_layout(p.words, ef, p.cand_cap).total;
+  return p;
+}
 
 // distances of the stored edges: all rows (codes == nullptr) or the listed ones
 int edge_dist(fvdb_graph* g, const uint32_t* codes_dev, const uint32_t* owner_dev, uint32_t n_rows, bool upper_all) {
@@ -507,14 +577,13 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   if (s->dpad > 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: at most 1024 dimensions");
   if (g->n >= 0x80000000u) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: node index needs 31 bits");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // LDS: visited bitmap over all nodes + fixed tables; the restated candidates heap gets what is left (<= 4096 slots)
-  const uint32_t words = (g->n + 31) / 32;
-  const uint32_t fixed = build_lds_layout(words, ef_construction, 0).total;
-  // FVDB_BUILD_LDS_LIMIT: test hook (a small value makes the graph "too large" for the on-chip bitmap)
-  const uint32_t lds_max = getenv("FVDB_BUILD_LDS_LIMIT") ? (uint32_t)atoi(getenv("FVDB_BUILD_LDS_LIMIT")) : 160u * 1024u;
-  if (fixed + 512 * 8 > lds_max) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: graph too large for the on-chip visited bitmap");
-  const uint32_t cand_cap = std::min<uint32_t>(4096, (lds_max - fixed) / 8 & ~1u);
-  const BuildLds L = build_lds_layout(words, ef_construction, cand_cap);
+  // LDS: `visited` (a bitmap over all nodes while that fits, a hashed set beyond) + fixed tables; the restated candidates
+  // heap gets what is left (<= 4096 slots)
+  const InsertPlan plan = insert_plan(g, ef_construction);
+  if (plan.repr == 0) FAIL(ctx, FVDB_E_UNSUPPORTED, plan.why);
+  const bool hashed = plan.repr == 2;
+  const uint32_t cand_cap = plan.cand_cap;
+  const BuildLds L = build_lds_layout(plan.words, ef_construction, cand_cap);
   int rc = ensure_edge_dist(g);
   if (rc) return rc;
   BuildState st{};
@@ -525,6 +594,8 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   st.status = 0;
   st.n_valid = st.n_rerun = st.n_stopped = st.rounds = st.consumed = st.scored = st.ties = st.spec_ties = 0;
   std::memset(st.why, 0, sizeof(st.why));
+  st.vis_host = st.vis_peak = st.vis_searches = 0;
+  st.vis_sum = 0;
   rc = push_state(g, st);
   if (rc) return rc;
   // speculation pays once an insert touches a small part of the graph (mode 0 = choose; 1 = never; 2 = always)
@@ -550,11 +621,12 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   HIPCHK(ctx, g->d_chg.ensure((size_t)kChgCap * 4 * 4));
   if (n >= 8)  // (a call that cannot speculate skips this)
     HIPCHK(ctx, hipMemsetAsync(g->d_spec.p, 0, (size_t)Kmax * kSpecWords * 4, ctx->stream));  // no stale "usable" flags
-  FVDB_BUILD_SWITCH(s->dpad, {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_commit_kernel<NB_, FULL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_search_kernel<NB_, FULL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
+  FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_commit_kernel<NB_, FULL_, HASH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_search_kernel<NB_, FULL_, HASH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
   });
   BuildView v = build_view(g, ef_construction, cand_cap);
+  v.bitmap_words = plan.words;
 #ifdef FVDB_BUILD_STAMPS
   static unsigned long long* d_dbg = nullptr;
   if (!d_dbg) (void)hipMalloc(&d_dbg, 64 * 8);
@@ -579,8 +651,8 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
       if (mode == 0 && (uint64_t)first + done < seq_below) chunk = std::min<uint32_t>(chunk, seq_below - (first + done));
       g->tag += 1;
       const uint32_t tag = g->tag;
-      FVDB_BUILD_SWITCH(s->dpad, {
-        hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n,
+      FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
+        hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_, HASH_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n,
                            chunk, tag, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 1u);
       });
       launches = 1;
@@ -589,10 +661,10 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
       for (uint32_t p = 0; p < pairs; ++p) {
         g->tag += 1;
         const uint32_t tag = g->tag;
-        FVDB_BUILD_SWITCH(s->dpad, {
-          hipLaunchKernelGGL((hnsw_insert_search_kernel<NB_, FULL_>), dim3(K, kBuildLayers), dim3(kBuildThreads), L.total, ctx->stream, v,
+        FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
+          hipLaunchKernelGGL((hnsw_insert_search_kernel<NB_, FULL_, HASH_>), dim3(K, kBuildLayers), dim3(kBuildThreads), L.total, ctx->stream, v,
                              first, n, exact_positions, tag, g->d_spec.as<uint32_t>(), g->d_elog.as<uint32_t>());
-          hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n, K,
+          hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_, HASH_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n, K,
                              tag, max_rerun, (const uint32_t*)g->d_spec.p, (const uint32_t*)g->d_elog.p, g->d_chg.as<uint32_t>(), strict);
         });
       }
@@ -642,6 +714,17 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
             st.why[11], st.why[12], st.why[13], st.why[14], st.spec_ties);
   if (getenv("FVDB_BUILD_DEBUG"))
     fprintf(stderr, "[device insert] second looks: overlapping %u, nodes the popped newcomer would bring in %u, later pop is the maximum %u\n", st.why[15], st.why[16], st.why[17]);
+  if (hashed && getenv("FVDB_BUILD_DEBUG"))
+    fprintf(stderr, "[device insert] hashed visited set, %u slots: %u searches gave up on a full set (%u of them inserts handed to the host), "
+            "entries after a search: largest %u, mean %.0f over %u searches\n", plan.slots, st.why[18], st.vis_host, st.vis_peak,
+            (double)st.vis_sum / std::max(1u, st.vis_searches), st.vis_searches);
+  if (hashed) {
+    g->ins_hashed += done;
+    g->ins_vis_over += st.vis_host;
+    g->ins_vis_searches += st.vis_searches;
+    g->ins_vis_entries += st.vis_sum;
+    g->ins_vis_peak = std::max(g->ins_vis_peak, st.vis_peak);
+  }
   g->entry = st.entry;
   g->top_level = st.entry_level;
   g->has_entry = st.has_entry != 0;
@@ -657,6 +740,36 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   g->last = acc;
   if (stats) *stats = acc;
   if (n_done) *n_done = done;
+  return FVDB_OK;
+}
+
+int fvdb_graph_set_insert_visited(fvdb_graph* g, int mode, uint32_t table_slots) {
+  fvdb_ctx* ctx = g->store->ctx;
+  if (mode < 0 || mode > 2) FAIL(ctx, FVDB_E_INVALID, "insert visited mode: 0 auto, 1 bitmap, 2 hashed");
+  if (table_slots != 0 && (table_slots < 256 || table_slots > 32768 || (table_slots & (table_slots - 1)) != 0))
+    FAIL(ctx, FVDB_E_INVALID, "insert visited table: a power of two in 256..32768 slots (0 = default)");
+  g->ins_vis_mode = mode;
+  g->ins_vis_slots = table_slots;
+  return FVDB_OK;
+}
+
+int fvdb_graph_insert_info(fvdb_graph* g, uint32_t ef_construction, fvdb_graph_insert_info_t* out) {
+  fvdb_ctx* ctx = g->store->ctx;
+  if (!out) FAIL(ctx, FVDB_E_INVALID, "insert info: no output");
+  if (ef_construction == 0 || ef_construction > 512) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: ef_construction in 1..512");
+  const InsertPlan p = insert_plan(g, ef_construction);
+  std::memset(out, 0, sizeof(*out));
+  out->mode = (uint32_t)g->ins_vis_mode;
+  out->representation = p.repr;
+  out->table_slots = p.slots;
+  out->cand_cap = p.cand_cap;
+  out->lds_bytes = p.lds_bytes;
+  out->bitmap_max_nodes = p.bitmap_max_nodes;
+  out->visited_peak = g->ins_vis_peak;
+  out->hashed_inserts = g->ins_hashed;
+  out->visited_overflows = g->ins_vis_over;
+  out->visited_searches = g->ins_vis_searches;
+  out->visited_entries = g->ins_vis_entries;
   return FVDB_OK;
 }
 

@@ -70,17 +70,22 @@ constexpr uint32_t kChkCap = 512;                // distances one validation may
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kTileRows = 16;               // rows of a wave's product tile
 
-// device-resident state of a graph under construction (one 64-byte record)
+// device-resident state of a graph under construction (one small record, copied whole in both directions)
 struct BuildState {
   uint32_t has_entry, entry, entry_level, n_linked;  // n_linked: nodes whose insert has completed
   uint32_t cursor;                                   // next node of the current fvdb_graph_insert_linked call
-  uint32_t status;                                   // 0 ok; 1: node `cursor` needs the host path (on-chip heap overflow)
+  uint32_t status;                                   // 0 ok; 1: node `cursor` needs the host path (an on-chip heap or the hashed visited set outgrown)
   uint32_t n_valid, n_rerun, n_stopped;              // speculation statistics
   uint32_t rounds, consumed, scored, ties;           // search statistics (sums)
   uint32_t spec_ties;                                // speculated searches that met equal distances
-  uint32_t why[18];  // commit stops by cause: [1] another entry point, [2] a search of the batch gave up (tie / overflow),
+  uint32_t why[20];  // commit stops by cause: [1] another entry point, [2] a search of the batch gave up (tie / overflow),
                      // [3] changed row + order-dependent search (or strict), [4] caps, [5] a changed node within the
-                     // bound, [6] ... and that bound was +inf (set never filled); [7] checks made, [8] rows touched
+                     // bound, [6] ... and that bound was +inf (set never filled); [7] checks made, [8] rows touched;
+                     // [18] searches (speculated ones included) that gave up because the hashed visited set filled
+  // hashed visited set (Visited<true>): inserts the commit workgroup handed to the host because the set filled; entries
+  // in the set at the end of a search_layer(ef) — largest, number of searches, sum
+  uint32_t vis_host, vis_peak, vis_searches, vis_pad;
+  unsigned long long vis_sum;
 };
 
 struct BuildView {
@@ -98,7 +103,8 @@ struct BuildView {
   uint32_t* stamp0;  // [n]  tag of the batch that last changed the node's layer-0 row
   uint32_t* stampU;  // [upper rows]
   uint32_t M, M0, ef;
-  uint32_t bitmap_words;  // visited bitmap (LDS) words: covers every node index of the graph
+  uint32_t bitmap_words;  // `visited` in LDS, words: a bitmap over every node index of the graph (Visited<false>), or the
+                          // slots of the hashed set (Visited<true>: a power of two >= 256, whatever the graph's size)
   uint32_t cand_cap;      // restated `candidates` heap slots in LDS
   uint32_t exact_first;   // 1: skip the register-set attempt (data on which nearly every search has to start again)
   BuildState* state;
@@ -144,7 +150,9 @@ __host__ __device__ inline BuildLds build_lds_layout(uint32_t bitmap_words, uint
 
 // misc words
 enum { MS_NSPEC = 0, MS_NSCORE = 1, MS_DONE = 2, MS_TIE = 3, MS_OVER = 4, MS_CUR = 5, MS_CURD = 6, MS_CONFLICT = 7,
-       MS_NLOG = 8, MS_NC = 9, MS_NN = 10, MS_ORDER = 11, MS_NT = 12, MS_NCHK = 13, MS_NCHG = 14, MS_CHGOVER = 15, MS_SEG0 = 16, MS_FNODE = 64, MS_FSLOT = 64 + kSpec, MS_CNT = 64 + 2 * kSpec };
+       MS_NLOG = 8, MS_NC = 9, MS_NN = 10, MS_ORDER = 11, MS_NT = 12, MS_NCHK = 13, MS_NCHG = 14, MS_CHGOVER = 15, MS_SEG0 = 16,
+       MS_VCNT = 17, MS_VFULL = 18,  // hashed visited set: entries (where several waves or the descent insert), "filled up"
+       MS_FNODE = 64, MS_FSLOT = 64 + kSpec, MS_CNT = 64 + 2 * kSpec };
 
 // ---------------------------------------------------------------------------------------------
 // scoring: RC rows by one wave, one product tile (see score_fixed, kernels_graph_fast.h, for the derivation)
@@ -286,15 +294,95 @@ __device__ __forceinline__ const uint32_t* adj_row(const BuildView& g, uint32_t 
   return layer == 0 ? g.adj0 + (size_t)node * g.stride0 : g.adjU + (size_t)(g.ubase[node] + layer - 1) * g.strideU;
 }
 
-__device__ __forceinline__ void clear_bitmap(const BuildView& g, BuildCtx& c) {
-  uint4* b4 = (uint4*)c.bitmap;
-  const uint32_t n4 = (g.bitmap_words + 3) >> 2;  // the carve is padded to 16 bytes
-  for (uint32_t i = threadIdx.x; i < n4; i += kBuildThreads) b4[i] = make_uint4(0, 0, 0, 0);
-}
+// ---------------------------------------------------------------------------------------------
+// `visited` (src/hnsw/core.rs:469-554, a HashSet<VectorId>) on chip, in one of two forms chosen at compile time:
+//
+//  Visited<false>  one bit per node index of the graph.  A test is one LDS read; the set costs n / 8 bytes, which is what
+//                  bounds the graphs this form serves (fvdb_graph_insert_info names the node count).
+//  Visited<true>   the node indices themselves in an open-addressed table of g.bitmap_words slots (a power of two): empty =
+//                  kNone (indices are < 2^31), multiplicative hash, linear probing, nothing is ever removed.  Full keys: no
+//                  false "visited" (a neighbour dropped unscored would be a wrong graph) and no false "fresh" (a double
+//                  admission).  Size independent of the graph.  A search whose set grows past 3/4 of the slots gives up
+//                  (MS_OVER = 2, the route a `candidates` heap overflow takes): callers check the count after every list
+//                  (<= 64 entries: slots >= 256 keeps one list's overshoot below the table's size), and every probe loop
+//                  ends after `slots` steps whatever the table holds.
+//
+//  absent        the read-only test; phases in which nobody inserts (fetch_lists, validate_speculation (c))
+//  test_and_set  (and `mark`, the same without a branch on the answer) lane = node; true = the node was not in the set and now is.  Hashed: atomicCAS(slot, kNone, id) — the
+//                same id arriving from two waves walks the same probe sequence, one of them wins the slot
+//  clear         all threads, 16-byte stores
+// ---------------------------------------------------------------------------------------------
+template <bool HASH>
+struct Visited;
+
+template <>
+struct Visited<false> {
+  static __device__ __forceinline__ void clear(const BuildView& g, BuildCtx& c) {
+    uint4* b4 = (uint4*)c.bitmap;
+    const uint32_t n4 = (g.bitmap_words + 3) >> 2;  // the carve is padded to 16 bytes
+    for (uint32_t i = threadIdx.x; i < n4; i += kBuildThreads) b4[i] = make_uint4(0, 0, 0, 0);
+  }
+  static __device__ __forceinline__ bool absent(const BuildView&, const BuildCtx& c, uint32_t id) {
+    return ((c.bitmap[id >> 5] >> (id & 31)) & 1u) == 0;
+  }
+  static __device__ __forceinline__ bool test_and_set(const BuildView&, BuildCtx& c, uint32_t id) {
+    const uint32_t bit = 1u << (id & 31);
+    const bool fresh = (c.bitmap[id >> 5] & bit) == 0;
+    if (fresh) atomicOr(&c.bitmap[id >> 5], bit);  // visited.insert (:506-507)
+    return fresh;
+  }
+  // unconditional form, for callers that do not branch on the answer
+  static __device__ __forceinline__ bool mark(const BuildView&, BuildCtx& c, uint32_t id) {
+    const uint32_t bit = 1u << (id & 31);
+    return (atomicOr(&c.bitmap[id >> 5], bit) & bit) == 0;
+  }
+  static __device__ __forceinline__ uint32_t limit(const BuildView&) { return 0xFFFFFFFFu; }
+};
+
+template <>
+struct Visited<true> {
+  static __device__ __forceinline__ void clear(const BuildView& g, BuildCtx& c) {
+    uint4* b4 = (uint4*)c.bitmap;
+    const uint32_t n4 = g.bitmap_words >> 2;
+    for (uint32_t i = threadIdx.x; i < n4; i += kBuildThreads) b4[i] = make_uint4(kNone, kNone, kNone, kNone);
+    if (threadIdx.x == 0) {
+      c.misc[MS_VCNT] = 0;
+      c.misc[MS_VFULL] = 0;
+    }
+  }
+  // slots = 2^k: the top k bits of id * 2^32 / golden ratio
+  static __device__ __forceinline__ uint32_t home(uint32_t slots, uint32_t id) { return (id * 2654435761u) >> (__clz((int)slots) + 1); }
+  static __device__ __forceinline__ bool absent(const BuildView& g, const BuildCtx& c, uint32_t id) {
+    const uint32_t slots = g.bitmap_words;
+    uint32_t s = home(slots, id);
+    for (uint32_t i = 0; i < slots; ++i) {
+      const uint32_t v = c.bitmap[s];
+      if (v == id) return false;
+      if (v == kNone) return true;
+      s = (s + 1) & (slots - 1);
+    }
+    return true;  // (a table without an empty slot: the load limit keeps it from existing)
+  }
+  static __device__ __forceinline__ bool test_and_set(const BuildView& g, BuildCtx& c, uint32_t id) {
+    const uint32_t slots = g.bitmap_words;
+    uint32_t s = home(slots, id);
+    for (uint32_t i = 0; i < slots; ++i) {
+      const uint32_t v = atomicCAS(&c.bitmap[s], kNone, id);  // visited.insert (:506-507)
+      if (v == kNone) return true;
+      if (v == id) return false;
+      s = (s + 1) & (slots - 1);
+    }
+    c.misc[MS_VFULL] = 1;  // every slot taken by another node: the caller gives up
+    return false;
+  }
+  static __device__ __forceinline__ bool mark(const BuildView& g, BuildCtx& c, uint32_t id) { return test_and_set(g, c, id); }
+  static __device__ __forceinline__ uint32_t limit(const BuildView& g) { return g.bitmap_words - (g.bitmap_words >> 2); }
+};
 
 // Fetch the adjacency rows of the round's new candidates — misc[MS_FNODE + i] into table slot misc[MS_FSLOT + i],
 // i < nf — drop what is visited already, list the rest for scoring.  Wave w takes entries w, w + 8, ...
 // A candidate below the layer is not expanded (:503).
+template <bool HASH>
 __device__ __forceinline__ void fetch_lists(const BuildView& g, BuildCtx& c, uint32_t nf, uint32_t layer) {
   const int lane = c.lane;
   for (uint32_t i = c.wave; i < nf; i += kBuildWaves) {
@@ -307,7 +395,7 @@ __device__ __forceinline__ void fetch_lists(const BuildView& g, BuildCtx& c, uin
     }
     bool fresh = false;
     if ((uint32_t)lane < cnt) {
-      fresh = ((c.bitmap[nb >> 5] >> (nb & 31)) & 1u) == 0;
+      fresh = Visited<HASH>::absent(g, c, nb);
       if (g.any_deleted && g.deleted[nb]) {
         nb |= 0x80000000u;  // visited like any other neighbour, never scored (:511-513)
         fresh = false;
@@ -346,21 +434,26 @@ __device__ __forceinline__ void score_lists(const BuildView& g, BuildCtx& c, con
 // returns it, and the loop ends at the first hop that admits nobody — a greedy walk.  In a hop the neighbours are
 // tested in list order against the running minimum with `<`, so the hop's winner is the FIRST neighbour holding the
 // smallest distance below the current one.  Returns (node, distance) in every thread.
+// false (hashed visited set only): the walk met more nodes than the set holds (MS_OVER = 2).
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL>
-__device__ __forceinline__ void greedy_layer(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t& cur,
+template <int NB, bool FULL, bool HASH>
+__device__ __forceinline__ bool greedy_layer(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t& cur,
                                              float& cur_d, uint32_t* elog) {
-  clear_bitmap(g, c);
+  Visited<HASH>::clear(g, c);
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicOr(&c.bitmap[cur >> 5], 1u << (cur & 31));
+    (void)Visited<HASH>::mark(g, c, cur);
+    if (HASH) {
+      c.misc[MS_VCNT] = 1;
+      c.misc[MS_OVER] = 0;
+    }
     c.misc[MS_FNODE] = cur;
     c.misc[MS_FSLOT] = 0;
     c.misc[MS_NSCORE] = 0;
   }
   __syncthreads();
   for (;;) {
-    fetch_lists(g, c, 1, layer);
+    fetch_lists<HASH>(g, c, 1, layer);
     __syncthreads();
     const uint32_t U = c.misc[MS_NSCORE];
     score_lists<NB, FULL>(g, c, q2, U);
@@ -371,14 +464,18 @@ __device__ __forceinline__ void greedy_layer(const BuildView& g, BuildCtx& c, co
       uint32_t nb = 0;
       bool keep = false;
       float d = __uint_as_float(0x7F800000u);
+      bool fresh = false;
       if ((uint32_t)lane < cnt) {
         nb = c.nbr[lane];
-        const uint32_t id = nb & 0x7FFFFFFFu;
-        const uint32_t bit = 1u << (id & 31);
-        const bool fresh = (c.bitmap[id >> 5] & bit) == 0;
-        if (fresh) atomicOr(&c.bitmap[id >> 5], bit);  // visited.insert (:506-507)
+        fresh = Visited<HASH>::test_and_set(g, c, nb & 0x7FFFFFFFu);
         keep = fresh && (nb >> 31) == 0;
         if (keep) d = c.dist[lane];
+      }
+      bool full = false;
+      if (HASH) {  // the set after this list: past the load limit the walk gives up
+        const uint32_t vc = c.misc[MS_VCNT] + (uint32_t)__popcll(__ballot(fresh));
+        full = vc > Visited<HASH>::limit(g);
+        if (lane == 0) c.misc[MS_VCNT] = vc;
       }
       // first lane holding the minimum
       const float m = wave_min_f(d);
@@ -407,15 +504,23 @@ __device__ __forceinline__ void greedy_layer(const BuildView& g, BuildCtx& c, co
         c.misc[MS_DONE] = moved ? 0u : 1u;
         c.misc[MS_FNODE] = nxt;
         c.misc[MS_NSCORE] = 0;
+        if (HASH && full) {
+          c.misc[MS_DONE] = 1;
+          c.misc[MS_OVER] = 2;
+          atomicAdd(&g.state->why[18], 1u);
+        }
       }
     }
     __syncthreads();
     cur = c.misc[MS_CUR];
     cur_d = __uint_as_float(c.misc[MS_CURD]);
     const uint32_t done = c.misc[MS_DONE];
+    const bool over = HASH && c.misc[MS_OVER] != 0;
     __syncthreads();
+    if (over) return false;
     if (done) break;
   }
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -465,12 +570,12 @@ __device__ __forceinline__ void near_reg_max(const NearSet& h, int r, uint32_t e
 // goes on.  A list is fetched once: it stays in the table until its candidate is expanded or falls out of the kSpec
 // nearest.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL, bool EXACT>
+template <int NB, bool FULL, bool EXACT, bool HASH>
 __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t start,
                                                 float start_d, uint32_t* elog, uint32_t* stat) {
   const int lane = c.lane;
   const uint32_t ef = g.ef;
-  clear_bitmap(g, c);
+  Visited<HASH>::clear(g, c);
   __syncthreads();
   NearSet h;
 #pragma unroll
@@ -479,6 +584,7 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
     h.d[r] = 0x7F800000u;
   }
   uint32_t nN = 0, nC = 0;          // wave 0's copies are the live ones
+  uint32_t vcount = 1;              // hashed visited set: its entries (wave 0 alone inserts during a search)
   uint32_t slot_node = 0xFFFFFFFFu;  // wave 0, lane l < kSlots: the node whose list table slot l holds
   // non-EXACT: the maximum of the set.  While it fills: a running maximum.  Once full: per-register maxima (rm, lane
   // rl), the set's maximum is the largest of them (register wr) — an admission then re-reduces ONE register.
@@ -499,7 +605,7 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
   if (c.wave == 0) {
     if (lane == 0) {
       c.misc[MS_SEG0] = c.misc[MS_NLOG];
-      atomicOr(&c.bitmap[start >> 5], 1u << (start & 31));
+      (void)Visited<HASH>::mark(g, c, start);
       c.misc[MS_NSCORE] = 0;
       c.misc[MS_TIE] = 0;
       c.misc[MS_OVER] = 0;
@@ -531,7 +637,7 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
     BSTAMP(t0);
     if (c.wave == 0) {
       bool tie = false, over = false, finished = false;
-      uint32_t tie_why = 0;
+      uint32_t tie_why = 0, over_why = 1;  // over_why 2: the hashed visited set filled, not the `candidates` heap
       // ---- the reference's loop, out of the table ----
       for (;;) {
         uint32_t node, slot = 0, popd = 0;
@@ -599,18 +705,23 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
         consumed += 1;
         const uint32_t cnt = c.misc[MS_CNT + p];
         uint32_t nb = 0;
-        bool keep = false;
+        bool keep = false, fresh = false;
         uint32_t db = 0x7F800000u;
         if ((uint32_t)lane < cnt) {
           nb = c.nbr[p * 64 + lane];
-          const uint32_t id = nb & 0x7FFFFFFFu;
-          const uint32_t bit = 1u << (id & 31);
-          const bool fresh = (c.bitmap[id >> 5] & bit) == 0;
-          if (fresh) atomicOr(&c.bitmap[id >> 5], bit);  // visited.insert (:506-507)
+          fresh = Visited<HASH>::test_and_set(g, c, nb & 0x7FFFFFFFu);
           keep = fresh && (nb >> 31) == 0;                // deleted: visited, skipped (:511-513)
           if (keep) db = __float_as_uint(c.dist[p * 64 + lane]);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (HASH) {  // the set after this list: past the load limit the search gives up
+          vcount += (uint32_t)__popcll(__ballot(fresh));
+          if (vcount > Visited<HASH>::limit(g)) {
+            over = true;
+            over_why = 2;
+            break;
+          }
+        }
         const uint64_t seen = __ballot(keep);
         // admission (:517-531) in list order; `worst` only shrinks while they are applied
         if (EXACT) worst = __float_as_uint(-c.near[0].d);
@@ -782,14 +893,14 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
         c.misc[MS_NSPEC] = nf;
         c.misc[MS_NSCORE] = 0;
         if (tie) c.misc[MS_TIE] = tie_why;
-        if (over) c.misc[MS_OVER] = 1;
+        if (over) c.misc[MS_OVER] = HASH ? over_why : 1u;
       }
     }
     BSTAMP(t1);
     __syncthreads();
     const uint32_t nf = c.misc[MS_NSPEC];
     if (nf == 0) break;  // search finished, or a tie / overflow was met
-    fetch_lists(g, c, nf, layer);
+    fetch_lists<HASH>(g, c, nf, layer);
     __syncthreads();
     BSTAMP(t2);
     const uint32_t U = c.misc[MS_NSCORE];
@@ -803,12 +914,18 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
     scored += U;
   }
   const bool failed = (c.misc[MS_TIE] | c.misc[MS_OVER]) != 0;
-  if (failed && threadIdx.x == 0) atomicAdd(&g.state->why[c.misc[MS_OVER] ? 14 : 10 + min(c.misc[MS_TIE], 2u)], 1u);
+  if (failed && threadIdx.x == 0)
+    atomicAdd(&g.state->why[HASH && c.misc[MS_OVER] == 2 ? 18 : (c.misc[MS_OVER] ? 14 : 10 + min(c.misc[MS_TIE], 2u))], 1u);
   __syncthreads();
   if (threadIdx.x == 0 && stat) {
     stat[0] += rounds;
     stat[1] += consumed;
     stat[2] += scored;
+  }
+  if (HASH && threadIdx.x == 0) {  // how full the set gets: the table's size rests on this distribution
+    atomicMax(&g.state->vis_peak, vcount);
+    atomicAdd(&g.state->vis_searches, 1u);
+    atomicAdd(&g.state->vis_sum, (unsigned long long)vcount);
   }
   if (failed) return false;
   // ---- result: `nearest` in heap order, stable-sorted by distance (:541-553); the first 64 are enough ----
@@ -854,20 +971,21 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
 }
 
 // search_layer(ef) with the tie rule: sorted registers first, the restated heaps when two members tie.
-// false: the restated `candidates` heap outgrew its LDS slots (host path for this node).
-template <int NB, bool FULL>
+// false: the restated `candidates` heap outgrew its LDS slots, or the hashed visited set filled (host path for this node).
+template <int NB, bool FULL, bool HASH>
 __device__ __forceinline__ bool ef_search(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t start,
                                           float start_d, uint32_t* elog, uint32_t* stat, bool exact_on_tie) {
   const uint32_t log0 = c.misc[MS_NLOG];
   if (g.ef <= (uint32_t)kNearRegs * 64u && !g.exact_first) {
-    if (ef_search_layer<NB, FULL, false>(g, c, q2, layer, start, start_d, elog, stat)) return true;
+    if (ef_search_layer<NB, FULL, false, HASH>(g, c, q2, layer, start, start_d, elog, stat)) return true;
+    if (HASH && c.misc[MS_OVER] == 2) return false;  // the restated heaps would meet the same nodes
     if (threadIdx.x == 0 && stat) stat[3] += 1;
     if (!exact_on_tie) return false;  // a speculation far down the batch: not worth twice the time of the others
     if (threadIdx.x == 0) c.misc[MS_NLOG] = log0;  // the aborted attempt expanded a prefix of what the exact run expands
     __syncthreads();
   }
   if (threadIdx.x == 0) c.misc[MS_ORDER] = 1;  // heaps with equal keys: the outcome depends on the order of the lists
-  return ef_search_layer<NB, FULL, true>(g, c, q2, layer, start, start_d, elog, stat);
+  return ef_search_layer<NB, FULL, true, HASH>(g, c, q2, layer, start, start_d, elog, stat);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -877,7 +995,7 @@ __device__ __forceinline__ bool ef_search(const BuildView& g, BuildCtx& c, const
 // l + 1 rows only, so all of an insert's searches can run before any of its links are made.
 // Results -> res[layer]; false = host path needed.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL>
+template <int NB, bool FULL, bool HASH>
 __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c, uint32_t node, uint32_t level, uint32_t entry,
                                                 uint32_t entry_level, uint32_t* elog, uint32_t* stat, bool exact_on_tie = true,
                                                 int only_layer = -1 /* >= 0: the descent + that layer's search only */) {
@@ -906,13 +1024,14 @@ __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c,
   BSTAMP(tg0);
   // the descent's expansions are logged once per insert: by the whole-insert call, or by the layer-0 call
   if (only_layer < 0 || (uint32_t)only_layer <= search_level)
-    for (uint32_t lc = search_level + 1; lc-- > 0;) greedy_layer<NB, FULL>(g, c, q2, lc, cur, cur_d, only_layer <= 0 ? elog : nullptr);
+    for (uint32_t lc = search_level + 1; lc-- > 0;)
+      if (!greedy_layer<NB, FULL, HASH>(g, c, q2, lc, cur, cur_d, only_layer <= 0 ? elog : nullptr)) return false;
   BSTAMP(tg1);
   BSTAMP_ADD(g, 3, tg0, tg1);
   for (uint32_t lc = 0; lc <= level; ++lc) {
     if (only_layer >= 0 && lc != (uint32_t)only_layer) continue;
     const bool low = lc <= search_level;
-    if (!ef_search<NB, FULL>(g, c, q2, lc, low ? cur : entry, low ? cur_d : entry_d, elog, stat, exact_on_tie)) return false;
+    if (!ef_search<NB, FULL, HASH>(g, c, q2, lc, low ? cur : entry, low ? cur_d : entry_d, elog, stat, exact_on_tie)) return false;
   }
   return true;
 }
@@ -1076,10 +1195,12 @@ __device__ __forceinline__ void insert_links(const BuildView& g, BuildCtx& c, ui
 //    node of x's row is one the search has met by then (rows of the expansions so far, marked in the visited bitmap),
 //    is soft-deleted, or is not nearer than the maximum of the moment — and no later pop is the set's maximum (the
 //    element x displaces must not be the one the logged run expands) until W drops below d(q, x).
+//    (With the hashed visited set those rows may hold more nodes than the set does: the look is then abandoned — cause 4,
+//    the search runs again — rather than answered from a partial set.)
 //
 // Returns 0 (adopt) or the cause.  Uses the searches' scratch (dist / nbr / slist / cand), idle between two inserts.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL>
+template <int NB, bool FULL, bool HASH>
 __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, BuildCtx& c, uint32_t node, uint32_t level, uint32_t tag,
                                                          const uint32_t* __restrict__ sp, const uint32_t* __restrict__ elog, const uint32_t* chg,
                                                              uint32_t strict /* A/B and bisecting: 1 any change is a conflict, 2 no second
@@ -1272,19 +1393,33 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
       if (c.misc[MS_DONE] == 0 && threadIdx.x == 0) c.misc[MS_CONFLICT] = 9;
     } else {
       // (b) everything the search has met before it pops x: the rows of the expansions seg0 .. ta-1 and their nodes
-      clear_bitmap(g, c);
+      Visited<HASH>::clear(g, c);
       __syncthreads();
       for (uint32_t t = seg0 + (uint32_t)c.wave; t < ta; t += kBuildWaves) {
         const uint32_t e = el[t];
         const uint32_t* row = g.adj0 + (size_t)e * g.stride0;
         const uint32_t cnt = __builtin_amdgcn_readfirstlane(row[0]);
-        if ((uint32_t)c.lane < cnt) {
-          const uint32_t y = row[1 + c.lane];
-          atomicOr(&c.bitmap[y >> 5], 1u << (y & 31));
+        bool fresh = false;
+        if ((uint32_t)c.lane < cnt) fresh = Visited<HASH>::mark(g, c, row[1 + c.lane]);
+        const bool fresh_e = c.lane == 0 && Visited<HASH>::mark(g, c, e);
+        if (HASH) {
+          // eight waves insert at once: each adds what it put in; past the load limit (or with a probe that found every
+          // slot taken, which a small table allows between two looks at the count) all of them stop
+          const uint32_t add = (uint32_t)__popcll(__ballot(fresh || fresh_e));
+          uint32_t stop = 0;
+          if (c.lane == 0) {
+            if (atomicAdd(&c.misc[MS_VCNT], add) + add > Visited<HASH>::limit(g)) c.misc[MS_VFULL] = 1;
+            stop = __hip_atomic_load(&c.misc[MS_VFULL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          if (__builtin_amdgcn_readfirstlane(stop)) break;
         }
-        if (c.lane == 0) atomicOr(&c.bitmap[e >> 5], 1u << (e & 31));
       }
       __syncthreads();
+      if (HASH && c.misc[MS_VFULL]) {
+        if (threadIdx.x == 0) c.misc[MS_CONFLICT] = 4;
+        __syncthreads();
+        break;
+      }
       // (c) x's own row: whoever is new to the search and alive must be turned away (not nearer than the maximum then)
       if (c.wave == 0) {
         const uint32_t* row = g.adj0 + (size_t)x * g.stride0;
@@ -1293,7 +1428,7 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
         uint32_t y = 0;
         if ((uint32_t)c.lane < cnt) {
           y = row[1 + c.lane];
-          fresh = ((c.bitmap[y >> 5] >> (y & 31)) & 1u) == 0 && !(g.any_deleted && g.deleted[y]);
+          fresh = Visited<HASH>::absent(g, c, y) && !(g.any_deleted && g.deleted[y]);
         }
         const uint64_t fm = __ballot(fresh);
         if (fresh) {
@@ -1331,7 +1466,7 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
 // Speculation: workgroup (b, l) runs the layer-l search of node first + cursor + b against the graph as it stands (the
 // searches of an insert's layers only share the greedy descent, which every one of them repeats: a node with levels
 // would otherwise take several times as long as its batch mates, and the slowest workgroup sets the launch's duration).
-template <int NB, bool FULL>
+template <int NB, bool FULL, bool HASH>
 __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(const BuildView g, uint32_t first, uint32_t n, uint32_t exact_positions,
                                                                               uint32_t tag, uint32_t* __restrict__ spec /* [grid.x][kSpecWords] */,
                                                                               uint32_t* __restrict__ elogs /* [grid.x][kBuildLayers][kLogWords] */) {
@@ -1351,7 +1486,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(co
   // speculations of a batch, the ones most likely to be adopted, do that; the others are left to the next batch
   // (`exact_positions`: the host raises it to the whole batch on data where ties are the rule, e.g. duplicate vectors)
   uint32_t tstat[4] = {0, 0, 0, 0};
-  const bool ok = insert_searches<NB, FULL>(g, c, node, level, st.entry, st.entry_level, elog, tstat, blockIdx.x < exact_positions, (int)layer);
+  const bool ok = insert_searches<NB, FULL, HASH>(g, c, node, level, st.entry, st.entry_level, elog, tstat, blockIdx.x < exact_positions, (int)layer);
   __syncthreads();
   const uint32_t nlog = c.misc[MS_NLOG];
   if (threadIdx.x == 0) {
@@ -1371,7 +1506,8 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(co
 // expanded is untouched by this batch and the entry point is the one it started from; otherwise the search runs here
 // (at most max_rerun times per launch, then the kernel stops and leaves the rest to the next speculation).
 // spec == nullptr: no speculation, every search runs here (small graphs, where every insert touches what the next reads).
-template <int NB, bool FULL>
+// HASH: the form of `visited` (Visited<HASH>), chosen by the host for the whole call.
+template <int NB, bool FULL, bool HASH>
 __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(const BuildView g, uint32_t first, uint32_t n, uint32_t count,
                                                                               uint32_t tag, uint32_t max_rerun,
                                                                               const uint32_t* __restrict__ spec,
@@ -1390,7 +1526,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
   uint32_t reruns = 0;
   uint32_t stat[4] = {0, 0, 0, 0};
   uint32_t n_valid = 0, n_rerun = 0, stopped = 0, why_stop = 0, n_chk = 0, n_touch = 0;
-  uint32_t done = 0;
+  uint32_t done = 0, vis_host = 0;
   for (uint32_t b = 0; b < count; ++b) {
     const uint32_t idx = st.cursor + b;
     if (idx >= n) break;
@@ -1420,7 +1556,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
       for (uint32_t l = 0; l <= level; ++l) usable = usable && sp[8 + l] == tag;
       uint32_t why = sp[1] == node && sp[2] == st.entry ? 2u : 1u;
       if (usable) {
-        why = validate_speculation<NB, FULL>(g, c, node, level, tag, sp, elogs + (size_t)b * kBuildLayers * kLogWords, chg, strict);
+        why = validate_speculation<NB, FULL, HASH>(g, c, node, level, tag, sp, elogs + (size_t)b * kBuildLayers * kLogWords, chg, strict);
         have = why == 0;
         n_chk += c.misc[MS_NCHK];
         n_touch += c.misc[MS_NT];
@@ -1442,7 +1578,8 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
       reruns += 1;
       n_rerun += 1;
       BSTAMP(ts0);
-      if (!insert_searches<NB, FULL>(g, c, node, level, st.entry, st.entry_level, nullptr, stat)) {
+      if (!insert_searches<NB, FULL, HASH>(g, c, node, level, st.entry, st.entry_level, nullptr, stat)) {
+        if (HASH && c.misc[MS_OVER] == 2) vis_host = 1;  // the hashed visited set filled: this node is the host's
         st.status = 1;
         break;
       }
@@ -1480,6 +1617,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
     o->consumed += stat[1];
     o->scored += stat[2];
     o->ties += stat[3];
+    if (HASH) o->vis_host += vis_host;
   }
 }
 

@@ -70,6 +70,8 @@ int fvh_hnsw_batch_insert(void* p, const uint64_t* ids, const float* v, uint64_t
 }
 void fvh_hnsw_set_device_insert(void* p, int on, int mode) { ((HNSWIndex*)p)->set_device_insert(on != 0, mode); }
 int fvh_hnsw_device_insert(void* p) { return ((HNSWIndex*)p)->device_insert(); }
+int fvh_hnsw_set_insert_visited(void* p, int mode, uint32_t table_slots) { return ((HNSWIndex*)p)->set_insert_visited(mode, table_slots); }
+int fvh_hnsw_insert_info(void* p, fvdb_graph_insert_info_t* out) { return ((HNSWIndex*)p)->insert_info(out); }
 void fvh_hnsw_insert_stats(void* p, fvdb_graph_insert_stats* out, uint64_t* host_path_inserts, uint64_t* upload_bytes) {
   HNSWIndex* h = (HNSWIndex*)p;
   if (out) *out = h->insert_stats();

@@ -155,6 +155,12 @@ class HNSWIndex {
     insert_mode_ = mode;
   }
   bool device_insert() const { return device_insert_; }
+  // `visited` of the device insert's searches (src/hnsw/core.rs:469-554): fvdb_graph_set_insert_visited's mode (0 = a
+  // bitmap over all nodes while the graph fits it, a hashed set beyond; 1 = bitmap only; 2 = hashed always) and table size.
+  // Same graph whichever form.  insert_info: fvdb_graph_insert_info for this index's ef_construction (FVDB_E_NOT_FOUND
+  // before the device graph exists, i.e. before the first insert or search).
+  int set_insert_visited(int mode, uint32_t table_slots = 0);
+  int insert_info(fvdb_graph_insert_info_t* out);
   const fvdb_graph_insert_stats& insert_stats() const { return insert_stats_; }  // sums since construction
   uint64_t host_path_inserts() const { return n_host_inserts_; }
   uint64_t graph_upload_bytes() const { return graph_ ? fvdb_graph_upload_bytes(graph_) : 0; }
@@ -271,6 +277,9 @@ class HNSWIndex {
   fvdb_graph* graph_ = nullptr;
   bool host_ahead_ = true, dev_ahead_ = false, device_traversal_ = true, device_insert_ = true;
   int insert_mode_ = 0;
+  int visited_mode_ = 0;
+  uint32_t visited_slots_ = 0;
+  bool host_link_reported_ = false;  // the stderr line "device insert refused, linking on the host" was written
   fvdb_graph_insert_stats insert_stats_{};
   uint64_t n_host_inserts_ = 0;
   int ensure_graph_handle();

@@ -519,7 +519,22 @@ int HNSWIndex::ensure_graph_handle() {
   if (graph_) return FVDB_OK;
   int rc = fvdb_graph_create(store_, &graph_);
   if (rc) return rc;
+  rc = fvdb_graph_set_insert_visited(graph_, visited_mode_, visited_slots_);
+  if (rc) return rc;
   return fvdb_graph_configure(graph_, cfg_.max_connections, cfg_.max_connections_layer_0);
+}
+
+int HNSWIndex::set_insert_visited(int mode, uint32_t table_slots) {
+  if (mode < 0 || mode > 2) return FVDB_E_INVALID;
+  if (table_slots != 0 && (table_slots < 256 || table_slots > 32768 || (table_slots & (table_slots - 1)) != 0)) return FVDB_E_INVALID;
+  visited_mode_ = mode;
+  visited_slots_ = table_slots;
+  return graph_ ? fvdb_graph_set_insert_visited(graph_, mode, table_slots) : FVDB_OK;
+}
+
+int HNSWIndex::insert_info(fvdb_graph_insert_info_t* out) {
+  if (!graph_) return FVDB_E_NOT_FOUND;
+  return fvdb_graph_insert_info(graph_, cfg_.ef_construction, out);
 }
 
 // host -> device: install the whole graph, once, when nbrs_ holds changes the device has not seen
@@ -929,10 +944,15 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
       uint32_t nd = 0;
       fvdb_graph_insert_stats st{};
       rc = fvdb_graph_insert_linked(graph_, first + done, m - done, cfg_.ef_construction, insert_mode_, &nd, &st);
-      if (rc == FVDB_E_UNSUPPORTED) {  // e.g. a graph too large for the on-chip visited bitmap: the host algorithm links
+      if (rc == FVDB_E_UNSUPPORTED) {  // e.g. an LDS budget that holds neither form of `visited`: the host algorithm links
         rc = FVDB_OK;                  // this node (rows patched into HBM), and the question is asked again for the next
         nd = 0;
         st.needs_host = 1;
+        if (!host_link_reported_) {    // a few hundred inserts/s instead of thousands: said once per index, not per node
+          fprintf(stderr, "[fvdb] HNSWIndex: the device insert refused the graph (%s); nodes are linked by the host algorithm\n",
+                  fvdb_last_error(ctx_));
+          host_link_reported_ = true;
+        }
       }
       if (rc) return finish(rc);
       insert_stats_.n_done += st.n_done;

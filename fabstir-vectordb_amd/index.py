@@ -68,6 +68,8 @@ HOST_SIGNATURES = {
     "fvh_hnsw_set_device_insert": (None, [vp, i32, i32]),
     "fvh_hnsw_device_insert": (i32, [vp]),
     "fvh_hnsw_insert_stats": (None, [vp, vp, u64p, u64p]),
+    "fvh_hnsw_set_insert_visited": (i32, [vp, i32, u32]),
+    "fvh_hnsw_insert_info": (i32, [vp, vp]),
     "fvh_hnsw_device_traversal": (i32, [vp]),
     "fvh_hnsw_device_fallbacks": (u64, [vp]),
     "fvh_hnsw_graph_kernel_times": (i32, [vp, f32p, u32p, u64p, u64p]),
@@ -305,6 +307,13 @@ class IVFIndex(_Base):
         return dict(rows_scanned=st.rows_scanned, work_items=st.work_items, list_rows_touched=st.list_rows_touched)
 
 
+class _InsertInfo(C.Structure):
+    """fvdb_graph_insert_info_t (include/fvdb.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "representation", "table_slots", "cand_cap", "lds_bytes",
+                                          "bitmap_max_nodes", "visited_peak", "reserved")] + \
+               [(n, C.c_uint64) for n in ("hashed_inserts", "visited_overflows", "visited_searches", "visited_entries")]
+
+
 class HNSWIndex(_Base):
     """src/hnsw/core.rs HNSWIndex (HNSWConfig::default :37-46)."""
 
@@ -459,7 +468,43 @@ class HNSWIndex(_Base):
         out = {k: int(v) for k, v in zip(names, st)}
         out["host_path_inserts"] = host.value
         out["graph_upload_bytes"] = up.value
+        info = self._insert_info()
+        out["hashed_inserts"] = info.hashed_inserts if info else 0
+        out["visited_overflows"] = info.visited_overflows if info else 0
+        out["visited_peak"] = info.visited_peak if info else 0
         return out
+
+    def set_insert_visited(self, mode, slots=0):
+        """The device insert keeps `visited` on chip.  mode 0 (default) or "auto": a bitmap over all nodes while the
+        graph fits it, a hashed set of node indices beyond; 1 / "bitmap": bitmap only (larger graphs are linked by the
+        host algorithm); 2 / "hashed": hashed always.  slots: size of the hashed table, a power of two in 256..32768
+        (0 = default).  An insert whose search fills the table takes the host algorithm.  The graph is identical."""
+        mode = {"auto": 0, "bitmap": 1, "hashed": 2}.get(mode, mode)
+        rc = self.lib.fvh_hnsw_set_insert_visited(self.h, int(mode), int(slots))
+        if rc:
+            raise ValueError(f"set_insert_visited({mode}, {slots}): mode 0..2, slots 0 or a power of two in 256..32768")
+
+    def _insert_info(self):
+        info = _InsertInfo()
+        rc = self.lib.fvh_hnsw_insert_info(self.h, C.cast(C.pointer(info), C.c_void_p))
+        return None if rc else info
+
+    def insert_info(self):
+        """What the next device insert would use for the graph as it stands: representation ("bitmap" / "hashed" /
+        None when neither fits and the host algorithm links), the hashed table's slots, the `candidates` heap's slots,
+        LDS bytes per workgroup, the largest node count the bitmap serves — and what the hashed set has seen so far
+        (inserts, overflows, largest and mean number of entries after a search)."""
+        info = self._insert_info()
+        if info is None:
+            raise RuntimeError("insert_info: the index has no device graph yet (insert or search first)")
+        return {
+            "mode": ("auto", "bitmap", "hashed")[info.mode],
+            "representation": (None, "bitmap", "hashed")[info.representation],
+            "table_slots": int(info.table_slots), "cand_cap": int(info.cand_cap), "lds_bytes": int(info.lds_bytes),
+            "bitmap_max_nodes": int(info.bitmap_max_nodes), "hashed_inserts": int(info.hashed_inserts),
+            "visited_overflows": int(info.visited_overflows), "visited_peak": int(info.visited_peak),
+            "visited_mean": info.visited_entries / info.visited_searches if info.visited_searches else 0.0,
+        }
 
     def device_fallbacks(self):
         return int(self.lib.fvh_hnsw_device_fallbacks(self.h))

@@ -367,8 +367,8 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
  *   cannot alter its pops, its expansions or its result — DESIGN.md section 6a).  The result never depends on the
  *   mode.  Environment knobs for A/B runs only: FVDB_BUILD_MODE, FVDB_BUILD_K / FVDB_BUILD_KMAX (batch size),
  *   FVDB_BUILD_STRICT (1 = adopt only when no expanded row changed), FVDB_BUILD_SEQ_BELOW, FVDB_BUILD_EXACT_FIRST,
- *   FVDB_BUILD_DEBUG (per-call diagnostics on stderr).  *n_done < n with stats->needs_host = 1: node first + *n_done needs the host path (level >= 16 or an
- *   on-chip heap overflow); link it through fvdb_graph_set_lists / fvdb_graph_set_entry and call again.
+ *   FVDB_BUILD_DEBUG (per-call diagnostics on stderr).  *n_done < n with stats->needs_host = 1: node first + *n_done needs the host path (level >= 16, an
+ *   on-chip heap overflow or a hashed visited set that filled); link it through fvdb_graph_set_lists / fvdb_graph_set_entry and call again.
  * set_lists: overwrite the lists of n_lists (node, layer) rows: offsets[n_lists + 1] into nbrs[].
  * set_entry: entry point + the number of nodes whose links are complete.
  * download: the adjacency in CSR form over (node, layer) slots in node order (slot_start[slots + 1], adj[adj_cap];
@@ -389,6 +389,34 @@ int fvdb_graph_set_entry(fvdb_graph* g, uint32_t entry_node, uint32_t n_linked);
 int fvdb_graph_entry(fvdb_graph* g, uint32_t* entry_node, uint32_t* n_nodes);
 int fvdb_graph_download(fvdb_graph* g, uint32_t* slot_start, uint32_t* adj, uint64_t adj_cap, uint64_t* n_edges);
 uint64_t fvdb_graph_upload_bytes(fvdb_graph* g);
+/* `visited` of the insert's searches (src/hnsw/core.rs:469-554, visited: HashSet<VectorId>) lives in LDS in one of two
+ * forms.  A bitmap over every node index of the graph: one LDS read per test, n / 8 bytes — it fits beside the
+ * search's other tables up to bitmap_max_nodes nodes (appended, not yet linked nodes count).  Or a hashed set of node
+ * indices (open addressing, full keys: exact like the bitmap) whose size does not depend on the graph; a search that
+ * meets more nodes than 3/4 of its slots gives up and that one insert takes the host path (needs_host), like an
+ * insert whose `candidates` heap outgrows LDS.  The graph never depends on the form.
+ * set_insert_visited: mode 0 = bitmap while the graph fits it, hashed beyond (default); 1 = bitmap only
+ *   (insert_linked returns FVDB_E_UNSUPPORTED beyond its reach); 2 = hashed always.  table_slots: 0 = default (the
+ *   largest power of two that leaves the `candidates` heap 2048 slots: 8192 at ef_construction 200), else a power of two
+ *   in 256..32768.  Test hooks, read at every call: FVDB_BUILD_LDS_LIMIT (LDS budget in bytes),
+ *   FVDB_BUILD_BITMAP_MAX_NODES (lowers the node count the bitmap serves).
+ * insert_info: what insert_linked(ef_construction) would use for the graph as it stands — representation 1 bitmap,
+ *   2 hashed, 0 neither fits (the call would return FVDB_E_UNSUPPORTED) — and, since the graph was created: inserts
+ *   linked with the hashed set, inserts it handed to the host because it filled, and the number of entries it held at
+ *   the end of a search_layer(ef_construction) (largest; count and sum for the mean). */
+typedef struct fvdb_graph_insert_info_t {
+  uint32_t mode;              /* the setting */
+  uint32_t representation;
+  uint32_t table_slots;       /* hashed: slots of the table; bitmap: 0 */
+  uint32_t cand_cap;          /* slots of the restated `candidates` heap */
+  uint32_t lds_bytes;         /* LDS of one insert workgroup */
+  uint32_t bitmap_max_nodes;  /* the largest node count the bitmap serves at this ef_construction */
+  uint32_t visited_peak;
+  uint32_t reserved;
+  uint64_t hashed_inserts, visited_overflows, visited_searches, visited_entries;
+} fvdb_graph_insert_info_t;
+int fvdb_graph_set_insert_visited(fvdb_graph* g, int mode, uint32_t table_slots);
+int fvdb_graph_insert_info(fvdb_graph* g, uint32_t ef_construction, fvdb_graph_insert_info_t* out);
 
 /* With profiling on (fvdb_ctx_set_profiling): summed duration (HIP events on the launch stream) of the last
  * <= 64 launches of the traversal kernel since the previous call, and how many were summed; and (always) the

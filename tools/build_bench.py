@@ -1,5 +1,10 @@
 """Sequential HNSW build (HNSWIndex::insert, src/hnsw/core.rs:226-378): the device-resident insert against the CPU
-oracle.  python tools/build_bench.py --n 10000 --d 384 [--mode 0|1|2] [--check] [--gen mixture|refbench|latent]"""
+oracle.  python tools/build_bench.py --n 10000 --d 384 [--mode 0|1|2] [--check] [--gen mixture|refbench|latent]
+[--visited auto|bitmap|hashed]
+
+Large graphs (the oracle links 200-300 nodes/s: it cannot build them itself):
+python tools/build_bench.py --n 1000000 --sample 2048 builds n nodes on the device, installs the exported graph into the
+oracle, inserts the next `sample` rows on both and compares every list either of them touched."""
 import argparse
 import os
 import sys
@@ -33,6 +38,65 @@ def gen(name, n, d, seed):
     return rng.standard_normal((n, d)).astype(np.float32)
 
 
+def slot_sums(off, nb):
+    """One number per (node, layer) list: its length and an order-sensitive sum of its members."""
+    ln = np.diff(off).astype(np.int64)
+    pos = np.arange(nb.size, dtype=np.int64) - np.repeat(off[:-1].astype(np.int64), ln)
+    w = (nb.astype(np.int64) + 1) * (pos + 1)
+    cs = np.concatenate([[0], np.cumsum(w)])
+    return ln, cs[off[1:].astype(np.int64)] - cs[off[:-1].astype(np.int64)]
+
+
+def sample_check(gh, orc, a, x, xs, levels):
+    """The graph as the device built it goes into the oracle; `sample` more inserts on both; every list the device
+    changed, every list of a new node and every list of a node the oracle linked a new node to must be the same."""
+    n, k = a.n, xs.shape[0]
+    gi, lv, off, nb = gh.export_graph()
+    oh = orc.HNSWIndex(a.m, a.m0, a.efc, seed=42)
+    t0 = time.time()
+    oh.restore(gi, x, lv, off, nb, gh.entry_point())
+    print(f"[sample] graph of {n} nodes installed into the oracle ({time.time() - t0:.1f}s)", flush=True)
+    ids = np.arange(n, n + k, dtype=np.uint64)
+    slv = orc.rng_levels(43, k)
+    b = gh.insert_stats()
+    t0 = time.time()
+    assert gh.batch_insert(ids, xs, slv) == (k, 0)
+    t_dev = time.time() - t0
+    e = gh.insert_stats()
+    t0 = time.time()
+    oh.batch_insert(ids, xs, slv)
+    t_orc = time.time() - t0
+    info = gh.insert_info()
+    print(f"[sample] {k} inserts at {n} nodes: device {k / t_dev:.0f} inserts/s ({t_dev / k * 1e3:.3f} ms each), oracle {k / t_orc:.0f} inserts/s; "
+          f"representation {info['representation']}, host-path inserts {e['host_path_inserts'] - b['host_path_inserts']}, hashed "
+          f"{e['hashed_inserts'] - b['hashed_inserts']}, visited overflows {e['visited_overflows'] - b['visited_overflows']}", flush=True)
+    gi2, lv2, off2, nb2 = gh.export_graph()
+    slots = off.size - 1
+    l0, s0 = slot_sums(off, nb)
+    l1, s1 = slot_sums(off2, nb2)
+    changed = np.nonzero((l0 != l1[:slots]) | (s0 != s1[:slots]))[0]
+    first_slot = np.concatenate([[0], np.cumsum(lv2.astype(np.int64) + 1)])
+    node_of = np.searchsorted(first_slot, changed, side="right") - 1
+    todo = {(int(nd), int(sl - first_slot[nd])) for nd, sl in zip(node_of, changed)}
+    for r in range(n, n + k):
+        for layer in range(int(lv2[r]) + 1):
+            todo.add((r, layer))
+            for o in oh.neighbors(int(gi2[r]), layer):
+                if int(lv2[o]) >= layer:  # (a search may start from a node that does not reach this layer, :323)
+                    todo.add((int(o), layer))
+    bad = 0
+    for r, layer in sorted(todo):
+        at = int(first_slot[r]) + layer
+        if nb2[int(off2[at]):int(off2[at + 1])].tolist() != oh.neighbors(int(gi2[r]), layer):
+            if bad < 5:
+                print("MISMATCH node", r, "layer", layer)
+            bad += 1
+    same_entry = gh.entry_point() == oh.entry_point()
+    print(f"[sample] lists compared {len(todo)} (changed on the device: {changed.size}), differing from the oracle: {bad}, entry point "
+          f"{'same' if same_entry else 'DIFFERENT'}", flush=True)
+    assert bad == 0 and same_entry
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=10000)
@@ -47,17 +111,25 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="insert in chunks of this many (0 = one batch_insert call)")
     ap.add_argument("--tail", type=int, default=0, help="after the build: this many more inserts, timed on their own")
     ap.add_argument("--tail-mode", type=int, default=1)
+    ap.add_argument("--visited", choices=["auto", "bitmap", "hashed"], default="auto",
+                    help="form of the device insert's visited set (HNSWIndex.set_insert_visited)")
+    ap.add_argument("--slots", type=int, default=0, help="slots of the hashed visited table (0 = default)")
+    ap.add_argument("--sample", type=int, default=0,
+                    help="large-graph mode: after the build, this many more inserts on the device and on the oracle "
+                         "(which is handed the device's graph), every touched list compared")
     a = ap.parse_args()
     fv = fvdb_import.load()
     import oracle as orc
     orc.build()
-    x = gen(a.gen, a.n + a.tail, a.d, 1234)
+    x = gen(a.gen, a.n + a.tail + a.sample, a.d, 1234)
+    xs, x = x[a.n + a.tail:], x[:a.n + a.tail]
     xt, x = x[a.n:], x[:a.n]
     ids = np.arange(a.n, dtype=np.uint64)
     levels = orc.rng_levels(42, a.n)
     ctx = fv.Context(0)
     gh = fv.HNSWIndex(ctx, a.m, a.m0, a.efc, seed=42)
     gh.set_device_insert(not a.host, a.mode)
+    gh.set_insert_visited(a.visited, a.slots)
     t0 = time.time()
     if a.chunk:
         for o in range(0, a.n, a.chunk):
@@ -67,7 +139,8 @@ def main():
         gh.batch_insert(ids, x, levels)
     t1 = time.time()
     st = gh.insert_stats()
-    print(f"[build] n {a.n} d {a.d} gen {a.gen} mode {a.mode} host {a.host}: {t1 - t0:.2f}s = {a.n / (t1 - t0):.0f} inserts/s "
+    print(f"[visited] {gh.insert_info()}", flush=True)
+    print(f"[build] n {a.n} d {a.d} gen {a.gen} mode {a.mode} visited {a.visited} host {a.host}: {t1 - t0:.2f}s = {a.n / (t1 - t0):.0f} inserts/s "
           f"({(t1 - t0) / a.n * 1e3:.3f} ms each)  stats {st}", flush=True)
     if a.tail:
         gh.set_device_insert(not a.host, a.tail_mode)
@@ -78,6 +151,9 @@ def main():
         e = gh.insert_stats()
         print(f"[tail] {a.tail} inserts at {a.n} nodes, mode {a.tail_mode}: {(t1 - t0) / a.tail * 1e3:.3f} ms each; "
               f"{ {k: e[k] - b[k] for k in e} }", flush=True)
+    if a.sample:
+        assert not a.tail, "--sample compares against a graph exported before the sample: not with --tail"
+        sample_check(gh, orc, a, x, xs, levels)
     if a.check:
         t0 = time.time()
         oh = orc.HNSWIndex(a.m, a.m0, a.efc, seed=42)

@@ -23,7 +23,7 @@ def same_results(got, want, k):
                            np.ascontiguousarray(want[1]).view(np.uint32)[valid]))
 
 
-def one_case(fv, orc, ctx, rng, case, only=-1, log=print):
+def one_case(fv, orc, ctx, rng, case, only=-1, log=print, visited="auto"):
     d = int(rng.choice([8, 24, 100, 384]))
     M = int(rng.choice([4, 8, 16]))
     M0 = int(min(63, 2 * M))
@@ -45,6 +45,7 @@ def one_case(fv, orc, ctx, rng, case, only=-1, log=print):
     ids = (np.arange(total, dtype=np.uint64) * 7 + 3)
     levels = orc.rng_levels(seed, total)
     gh, oh = fv.HNSWIndex(ctx, M, M0, efc, seed=seed), orc.HNSWIndex(M, M0, efc, seed=seed)
+    gh.set_insert_visited(visited)
     at, bad, trail = 0, 0, []
     alive = []
     for s in range(steps):
@@ -137,6 +138,8 @@ def main():
     ap.add_argument("--cases", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1)
+    ap.add_argument("--visited", choices=["auto", "bitmap", "hashed"], default="auto",
+                    help="form of the device insert's visited set (HNSWIndex.set_insert_visited)")
     a = ap.parse_args()
     fv = fvdb_import.load()
     import oracle as orc
@@ -145,7 +148,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     t0, bad = time.time(), 0
     for c in range(a.cases):
-        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only) else 0
+        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only, visited=a.visited) else 0
     print(f"[ops fuzz] {a.cases} cases, {bad} with mismatches, {time.time() - t0:.0f}s", flush=True)
     sys.exit(1 if bad else 0)
 

@@ -25,7 +25,7 @@ def same_results(got, want, k):
                            np.ascontiguousarray(want[1]).view(np.uint32)[valid]))
 
 
-def one_case(fv, orc, ctx, rng, case, only=-1, log=print):
+def one_case(fv, orc, ctx, rng, case, only=-1, log=print, visited="auto"):
     d = int(rng.choice([8, 32, 128]))
     nlist = int(rng.choice([4, 8, 24]))
     n_comp = int(rng.choice([2, 8, 64]))
@@ -46,6 +46,7 @@ def one_case(fv, orc, ctx, rng, case, only=-1, log=print):
     kw = dict(max_connections=8, max_connections_layer_0=16, ef_construction=int(g.choice([24, 60])), n_clusters=nlist,
               n_probe=int(g.integers(1, nlist + 1)))
     gi, oi = fv.HybridIndex(ctx, **kw), orc.HybridIndex(**kw)
+    gi.hnsw().set_insert_visited(visited)
     cents = np.ascontiguousarray(x[g.choice(total, nlist, replace=False)])
     gi.set_ivf_centroids(cents)
     oi.set_ivf_centroids(cents)
@@ -113,6 +114,8 @@ def main():
     ap.add_argument("--cases", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1)
+    ap.add_argument("--visited", choices=["auto", "bitmap", "hashed"], default="auto",
+                    help="form of the device insert's visited set (HNSWIndex.set_insert_visited)")
     a = ap.parse_args()
     fv = fvdb_import.load()
     import oracle as orc
@@ -121,7 +124,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     t0, bad = time.time(), 0
     for c in range(a.cases):
-        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only) else 0
+        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only, visited=a.visited) else 0
     print(f"[hybrid ops fuzz] {a.cases} cases, {bad} with mismatches, {time.time() - t0:.0f}s", flush=True)
     sys.exit(1 if bad else 0)
 

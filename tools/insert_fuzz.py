@@ -1,6 +1,6 @@
 """Randomised parity sweep of the device-resident insert: many small graphs of varied shape — dimension, degree,
 ef_construction, cluster structure, exact duplicates, soft deletes between batches, forced speculation with long batches —
-each compared list by list with the CPU oracle.  python tools/insert_fuzz.py [--cases 40] [--seed 1]"""
+each compared list by list with the CPU oracle.  python tools/insert_fuzz.py [--cases 40] [--seed 1] [--visited hashed]"""
 import argparse
 import os
 import sys
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fvdb_import  # noqa: E402
 
 
-def one_case(fv, orc, ctx, rng, case, only=-1):
+def one_case(fv, orc, ctx, rng, case, only=-1, visited="auto"):
     n = int(rng.integers(600, 5000))
     d = int(rng.choice([3, 8, 16, 24, 48, 100, 128, 384]))
     M = int(rng.choice([4, 6, 8, 12, 16]))
@@ -41,6 +41,7 @@ def one_case(fv, orc, ctx, rng, case, only=-1):
     levels = orc.rng_levels(seed, n)
     gh, oh = fv.HNSWIndex(ctx, M, M0, efc, seed=seed), orc.HNSWIndex(M, M0, efc, seed=seed)
     gh.set_device_insert(True, mode)
+    gh.set_insert_visited(visited)
     cuts = sorted(set([0, n] + [int(c) for c in g.integers(1, n, int(g.integers(0, 4)))]))
     for a, b in zip(cuts[:-1], cuts[1:]):
         gh.batch_insert(ids[a:b], x[a:b], levels[a:b])
@@ -83,7 +84,7 @@ def one_case(fv, orc, ctx, rng, case, only=-1):
     bad += sbad
     print(f"case {case:3d}: n {n:5d} d {d:3d} M {M:2d}/{M0:2d} ef {efc:3d} comps {n_comp:4d} sigma {sigma:.2f} dup {dup_frac:.2f} grid {int(quant)} "
           f"mode {mode} batches {len(cuts) - 1}: adopted {st['speculated_ok']:5d} stops {st['commit_stops']:5d} restarts {st['tie_restarts']:4d} "
-          f"host {st['host_path_inserts']:3d} dev-fallbacks {gh.device_fallbacks():3d}  -> "
+          f"host {st['host_path_inserts']:3d} hashed {st['hashed_inserts']:5d} dev-fallbacks {gh.device_fallbacks():3d}  -> "
           f"{'OK' if bad == 0 else 'MISMATCH in %d lists / search settings (%d of them searches)' % (bad, sbad)}", flush=True)
     return bad
 
@@ -93,6 +94,8 @@ def main():
     ap.add_argument("--cases", type=int, default=40)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1, help="run this case of the sequence only")
+    ap.add_argument("--visited", choices=["auto", "bitmap", "hashed"], default="auto",
+                    help="form of the device insert's visited set (HNSWIndex.set_insert_visited)")
     a = ap.parse_args()
     fv = fvdb_import.load()
     import oracle as orc
@@ -101,7 +104,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     t0, bad = time.time(), 0
     for c in range(a.cases):
-        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only) else 0
+        bad += 1 if one_case(fv, orc, ctx, rng, c, a.only, a.visited) else 0
     print(f"[fuzz] {a.cases} cases, {bad} with mismatches, {time.time() - t0:.0f}s")
     sys.exit(1 if bad else 0)
 
