@@ -43,6 +43,7 @@ struct fvdb_graph {
   uint64_t ins_hashed = 0, ins_vis_over = 0, ins_vis_searches = 0, ins_vis_entries = 0;
   uint32_t ins_vis_peak = 0;
   DBuf s_q, d_counters;
+  DBuf d_stamps, d_build_stamps;  // diagnostic builds only (-DFVDB_GRAPH_STAMPS, -DFVDB_BUILD_STAMPS)
   uint64_t tot_queries = 0, tot_again = 0;  // traversal counters [3], [2] folded in at every fvdb_graph_kernel_times
   static constexpr uint32_t kSlots = 16;  // batches that may be in flight at once, each on its own stream
   DBuf s_visited[kSlots], s_touched[kSlots], s_spill[kSlots];
@@ -139,64 +140,30 @@ int pull_state(fvdb_graph* g, BuildState* st) {
   return FVDB_OK;
 }
 
-BuildView build_view(fvdb_graph* g, uint32_t ef, uint32_t cand_cap) {
-  fvdb_store* s = g->store;
-  BuildView v{};
-  v.rows = s->data;
-  v.dpad = s->dpad;
-  v.level = g->d_level.as<uint32_t>();
-  v.deleted = g->d_deleted.as<uint32_t>();
-  v.any_deleted = g->n_deleted ? 1u : 0u;
-  v.ubase = g->d_ubase.as<uint32_t>();
-  v.adj0 = g->d_adj0.as<uint32_t>();
-  v.dist0 = g->d_dist0.as<float>();
-  v.adjU = g->d_adjU.as<uint32_t>();
-  v.distU = g->d_distU.as<float>();
-  v.stride0 = g->stride0;
-  v.strideU = g->strideU;
-  v.stamp0 = g->d_stamp0.as<uint32_t>();
-  v.stampU = g->d_stampU.as<uint32_t>();
-  v.M = g->M;
-  v.M0 = g->M0;
-  v.ef = ef;
-  v.bitmap_words = (g->n + 31) / 32;
-  v.cand_cap = cand_cap;
-  v.state = (BuildState*)g->d_state.p;
-  v.dbg = nullptr;
-  return v;
+// The construction kernels are instantiated per 128-dim block count NB, FULL (no bounds checks) for the BASELINE
+// dimensions 384 and 768, and, the insert pair, per form of the insert's `visited` (HASH: kernels_graph_build.h,
+// Visited<>).  Every instantiation of one template has the same signature, so choosing one is a lookup.
+struct BuildKernels {
+  decltype(&hnsw_insert_search_kernel<3, true, false>) search;
+  decltype(&hnsw_insert_commit_kernel<3, true, false>) commit;
+  decltype(&graph_edge_dist_kernel<3, true>) edge_dist;
+};
+template <int NB, bool FULL>
+BuildKernels build_kernels_of(bool hashed) {
+  if (hashed) return {hnsw_insert_search_kernel<NB, FULL, true>, hnsw_insert_commit_kernel<NB, FULL, true>, graph_edge_dist_kernel<NB, FULL>};
+  return {hnsw_insert_search_kernel<NB, FULL, false>, hnsw_insert_commit_kernel<NB, FULL, false>, graph_edge_dist_kernel<NB, FULL>};
 }
-
-// kernels are instantiated per 128-dim block count; FULL (no bounds checks) for the BASELINE dimensions 384 and 768
-#define FVDB_BUILD_DISPATCH(NBV, FULLV, ...) \
-  do {                                       \
-    constexpr int NB_ = NBV;                 \
-    constexpr bool FULL_ = FULLV;            \
-    __VA_ARGS__;                             \
-  } while (0)
-#define FVDB_BUILD_SWITCH(dpad, ...)                                           \
-  do {                                                                         \
-    const uint32_t nb128_ = ((dpad) + 127) / 128;                              \
-    if ((dpad) == 384) FVDB_BUILD_DISPATCH(3, true, __VA_ARGS__);              \
-    else if ((dpad) == 768) FVDB_BUILD_DISPATCH(6, true, __VA_ARGS__);         \
-    else if (nb128_ == 1) FVDB_BUILD_DISPATCH(1, false, __VA_ARGS__);          \
-    else if (nb128_ == 2) FVDB_BUILD_DISPATCH(2, false, __VA_ARGS__);          \
-    else if (nb128_ == 3) FVDB_BUILD_DISPATCH(3, false, __VA_ARGS__);          \
-    else if (nb128_ == 4) FVDB_BUILD_DISPATCH(4, false, __VA_ARGS__);          \
-    else if (nb128_ <= 6) FVDB_BUILD_DISPATCH(6, false, __VA_ARGS__);          \
-    else FVDB_BUILD_DISPATCH(8, false, __VA_ARGS__);                           \
-  } while (0)
-
-// ... and per form of the insert's `visited` (HASH_: kernels_graph_build.h, Visited<>)
-#define FVDB_BUILD_SWITCH_V(dpad, hashed, ...)      \
-  do {                                              \
-    if (hashed) {                                   \
-      constexpr bool HASH_ = true;                  \
-      FVDB_BUILD_SWITCH(dpad, __VA_ARGS__);         \
-    } else {                                        \
-      constexpr bool HASH_ = false;                 \
-      FVDB_BUILD_SWITCH(dpad, __VA_ARGS__);         \
-    }                                               \
-  } while (0)
+BuildKernels build_kernels(uint32_t dpad, bool hashed) {
+  const uint32_t nb128 = (dpad + 127) / 128;
+  if (dpad == 384) return build_kernels_of<3, true>(hashed);
+  if (dpad == 768) return build_kernels_of<6, true>(hashed);
+  if (nb128 == 1) return build_kernels_of<1, false>(hashed);
+  if (nb128 == 2) return build_kernels_of<2, false>(hashed);
+  if (nb128 == 3) return build_kernels_of<3, false>(hashed);
+  if (nb128 == 4) return build_kernels_of<4, false>(hashed);
+  if (nb128 <= 6) return build_kernels_of<6, false>(hashed);
+  return build_kernels_of<8, false>(hashed);
+}
 
 // What fvdb_graph_insert_linked would put in LDS for this graph now.  The fixed tables come first; `visited` and the
 // restated `candidates` heap (512 .. 4096 slots) share what is left of the budget.
@@ -251,16 +218,23 @@ InsertPlan insert_plan(const fvdb_graph* g, uint32_t ef) {
   return p;
 }
 
+// the graph as the construction kernels see it; an insert adds ef and its LDS plan, the edge distances need neither
+BuildView build_view(fvdb_graph* g, uint32_t ef = 0, const InsertPlan& plan = InsertPlan{}) {
+  const fvdb_store* s = g->store;
+  BuildView v{s->data, s->dpad, g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(), g->n_deleted ? 1u : 0u, g->d_ubase.as<uint32_t>(),
+              g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->stride0, g->strideU,
+              g->d_stamp0.as<uint32_t>(), g->d_stampU.as<uint32_t>(), g->M, g->M0, ef, plan.words, plan.cand_cap};
+  v.state = (BuildState*)g->d_state.p;
+  return v;
+}
+
 // distances of the stored edges: all rows (codes == nullptr) or the listed ones
 int edge_dist(fvdb_graph* g, const uint32_t* codes_dev, const uint32_t* owner_dev, uint32_t n_rows, bool upper_all) {
   fvdb_ctx* ctx = g->store->ctx;
   if (n_rows == 0) return FVDB_OK;
-  const BuildView v = build_view(g, 1, 1);
   const size_t lds = 4 * (size_t)kTileRows * kFastStride * 4;
-  FVDB_BUILD_SWITCH(g->store->dpad, {
-    hipLaunchKernelGGL((graph_edge_dist_kernel<NB_, FULL_>), dim3((n_rows + 3) / 4), dim3(256), lds, ctx->stream, v, codes_dev,
-                       owner_dev, n_rows, upper_all ? 1u : 0u);
-  });
+  hipLaunchKernelGGL(build_kernels(g->store->dpad, false).edge_dist, dim3((n_rows + 3) / 4), dim3(256), lds, ctx->stream, build_view(g), codes_dev,
+                     owner_dev, n_rows, upper_all ? 1u : 0u);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
@@ -284,6 +258,329 @@ int ensure_edge_dist(fvdb_graph* g) {
   g->dist_valid = true;
   return FVDB_OK;
 }
+
+// Environment knobs of the schedule and its launches: tuning aids for A/B runs (include/fvdb.h), read once per process.
+struct BuildKnobs {
+  static int num(const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; }
+  int mode = num("FVDB_BUILD_MODE", 0);  // not 0: replaces the caller's mode
+  int k = num("FVDB_BUILD_K", 0);        // > 0: the batch size, fixed
+  int kmax = num("FVDB_BUILD_KMAX", 0);  // > 0: the largest batch size the schedule adapts to
+  // 0: the commit workgroup adopts speculated searches up to the first one an earlier insert of the batch invalidated,
+  // searches that ONE itself (so every launch pair makes progress) and stops; the rest of the batch is speculated again,
+  // in parallel, against the graph as it then stands
+  uint32_t max_rerun = (uint32_t)std::max(0, num("FVDB_BUILD_RERUN", -1));
+  // FVDB_BUILD_STRICT=1: a speculation is dropped when ANY row it expanded changed (round-3 first form; A/B runs)
+  uint32_t strict = (uint32_t)num("FVDB_BUILD_STRICT", 0);
+  // below this many nodes every insert lands in every other's neighbourhood: one at a time, no speculation
+  uint32_t seq_below = (uint32_t)num("FVDB_BUILD_SEQ_BELOW", 256);
+  bool exact_first = num("FVDB_BUILD_EXACT_FIRST", 1) != 0;  // A/B
+};
+
+// One launch group: what runs between two reads of the device's BuildState.
+struct BuildGroup {
+  bool speculate;        // true: `count` pairs of launches, the schedule's K speculated searches and then one commit;
+  uint32_t count;        // false: one commit launch that searches and links `count` nodes itself, one after the other
+  uint32_t exact_first;  // 1: the group's searches go straight to the restated heaps
+};
+
+// The schedule of one fvdb_graph_insert_linked call: host arithmetic between launch groups.
+struct BuildSchedule {
+  const BuildKnobs& knobs;
+  const int mode;  // speculation pays once an insert touches a small part of the graph (mode 0 = choose; 1 = never; 2 = always)
+  const uint32_t first, n;
+  // (a call never speculates further than it has nodes to link: the logs of a batch are 160 KB per (insert, layer) slot)
+  const uint32_t Kmax = std::min<uint32_t>((uint32_t)std::max(1, std::min(knobs.k > 0 ? knobs.k : (knobs.kmax > 0 ? knobs.kmax : 128), 256)),
+                                           std::max<uint32_t>(8, n));
+  uint32_t K = knobs.k > 0 ? Kmax : std::min<uint32_t>(16, Kmax);  // adapts to the run length of adopted speculations
+  uint32_t exact_positions = 4;  // speculated searches of a batch that may start again with the restated heaps on a tie
+  uint32_t ties_seen = 0;
+  // where ties are the rule (duplicate vectors) the register-set attempt is wasted work: the next `exact_left` groups go
+  // straight to the restated heaps, then the question is asked again
+  uint32_t exact_left = 0, commit_ties_seen = 0;
+
+  // the group to launch when `done` nodes of the call are linked
+  BuildGroup next(uint32_t done) {
+    BuildGroup grp{};
+    grp.speculate = mode == 2 || (mode == 0 && (uint64_t)first + done >= knobs.seq_below && n - done >= 8);
+    grp.exact_first = exact_left > 0 ? 1u : 0u;
+    if (exact_left) exact_left -= 1;
+    if (grp.speculate) {
+      grp.count = std::min<uint32_t>(16, (n - done + K - 1) / K);  // the cursor lives on the device: no sync in between
+    } else {
+      grp.count = std::min<uint32_t>(n - done, 2048);  // bounds one launch to a fraction of a second
+      if (mode == 0 && (uint64_t)first + done < knobs.seq_below) grp.count = std::min<uint32_t>(grp.count, knobs.seq_below - (first + done));
+    }
+    return grp;
+  }
+
+  // `st`: the state read back after `grp`, which started with `done` nodes linked
+  void update(const BuildGroup& grp, uint32_t done, const BuildState& st) {
+    const uint32_t linked = st.cursor - done;
+    if (grp.speculate && knobs.k <= 0) {
+      // a batch is adopted up to its first conflict: speculating much further than the usual run only adds stragglers
+      // (the slowest of the batch's searches sets the launch's duration)
+      const uint32_t run = linked / grp.count;
+      K = std::min<uint32_t>(Kmax, std::max<uint32_t>(8, 2 * run + 4));
+    }
+    if (grp.speculate) {  // where ties are the rule (duplicate vectors) every speculation takes the exact search
+      const uint32_t searched = grp.count * K, tied = st.spec_ties - ties_seen;  // (K as just adapted, not the group's)
+      if (!grp.exact_first) exact_positions = 4 * tied > searched ? Kmax : 4;
+      if (knobs.exact_first && !grp.exact_first && 2 * tied > searched) exact_left = 8;
+      ties_seen = st.spec_ties;
+    }
+    if (!grp.speculate && knobs.exact_first && !grp.exact_first && 2 * (st.ties - commit_ties_seen) > linked) exact_left = 8;
+    commit_ties_seen = st.ties;
+  }
+};
+
+// the device's record of construction at the start of a call: entry point and n_linked stay, the cursor, the status and
+// every counter start at zero
+int reset_build_state(fvdb_graph* g, uint32_t first, BuildState* st) {
+  int rc;
+  if ((rc = pull_state(g, st))) return rc;
+  if (st->n_linked != first) FAIL(g->store->ctx, FVDB_E_INVALID, "nodes are linked in store-row order");
+  *st = BuildState{st->has_entry, st->entry, st->entry_level, st->n_linked};
+  return push_state(g, *st);
+}
+
+// the launches of one group on the graph's stream, each with its own row-stamp tag
+void launch_group(fvdb_graph* g, const BuildKernels& kernels, const BuildView& v, uint32_t lds, const BuildSchedule& sched, const BuildGroup& grp) {
+  const uint32_t first = sched.first, n = sched.n;
+  hipStream_t stream = g->store->ctx->stream;
+  if (!grp.speculate) {
+    g->tag += 1;
+    hipLaunchKernelGGL(kernels.commit, dim3(1), dim3(kBuildThreads), lds, stream, v, first, n, grp.count, g->tag, 0u, nullptr, nullptr, nullptr, 1u);
+    return;
+  }
+  for (uint32_t p = 0; p < grp.count; ++p) {
+    g->tag += 1;
+    hipLaunchKernelGGL(kernels.search, dim3(sched.K, kBuildLayers), dim3(kBuildThreads), lds, stream, v, first, n, sched.exact_positions,
+                       g->tag, g->d_spec.as<uint32_t>(), g->d_elog.as<uint32_t>());
+    hipLaunchKernelGGL(kernels.commit, dim3(1), dim3(kBuildThreads), lds, stream, v, first, n, sched.K, g->tag, sched.knobs.max_rerun,
+                       g->d_spec.as<uint32_t>(), g->d_elog.as<uint32_t>(), g->d_chg.as<uint32_t>(), sched.knobs.strict);
+  }
+}
+
+#ifdef FVDB_BUILD_STAMPS
+// diagnostic build: the insert kernels add their phase times (10 ns ticks) into 64 words that this call owns
+void build_stamps_begin(fvdb_graph* g, BuildView* v) {
+  (void)g->d_build_stamps.ensure(64 * 8);
+  (void)hipMemset(g->d_build_stamps.p, 0, 64 * 8);
+  v->dbg = g->d_build_stamps.as<unsigned long long>();
+}
+void build_stamps_print(fvdb_graph* g, const BuildState& st, uint32_t done) {
+  unsigned long long h[16] = {};
+  (void)hipMemcpy(h, g->d_build_stamps.p, sizeof(h), hipMemcpyDeviceToHost);
+  fprintf(stderr, "[build stamps] of replay+select (us): replay %.1f  select %.1f  (table = the rest) | admissions %.1f\n", h[6] * 0.01 / std::max(1u, st.n_rerun),
+          h[7] * 0.01 / std::max(1u, st.n_rerun), (double)h[8] / std::max(1u, st.n_rerun));
+  const double us = 0.01, nn = std::max(1u, st.n_rerun);
+  fprintf(stderr, "[build stamps] per searched insert (us): replay+select %.1f  fetch %.1f  score %.1f | greedy %.1f  all searches %.1f  links %.1f"
+          " | rounds %.1f expanded %.1f scored %.0f\n", h[0] * us / nn, h[1] * us / nn, h[2] * us / nn, h[3] * us / nn, h[4] * us / nn,
+          h[5] * us / std::max(1u, done), st.rounds / nn, st.consumed / nn, st.scored / nn);
+}
+#else
+inline void build_stamps_begin(fvdb_graph*, BuildView*) {}
+inline void build_stamps_print(fvdb_graph*, const BuildState&, uint32_t) {}
+#endif
+
+// FVDB_BUILD_DEBUG: per-call diagnostics on stderr
+void report_insert(const InsertPlan& plan, const BuildState& st) {
+  if (!getenv("FVDB_BUILD_DEBUG")) return;
+  fprintf(stderr, "[device insert] %u linked, %u adopted, stops %u: entry %u, gave-up %u, order/strict %u, caps %u, added node nearer than a later pop %u, added node inside the final set %u, dropped node matters %u | "
+          "checks %u, touched rows %u\n", st.cursor, st.n_valid, st.n_stopped, st.why[1], st.why[2], st.why[3], st.why[4], st.why[5], st.why[6],
+          st.why[9], st.why[7], st.why[8]);
+  fprintf(stderr, "[device insert] searches that left the register set: pops tied %u, evictions tied %u, result tied %u, heap overflow %u | speculations given up or restarted %u\n",
+          st.why[11], st.why[12], st.why[13], st.why[14], st.spec_ties);
+  fprintf(stderr, "[device insert] second looks: overlapping %u, nodes the popped newcomer would bring in %u, later pop is the maximum %u\n", st.why[15], st.why[16], st.why[17]);
+  if (plan.repr == 2)
+    fprintf(stderr, "[device insert] hashed visited set, %u slots: %u searches gave up on a full set (%u of them inserts handed to the host), "
+            "entries after a search: largest %u, mean %.0f over %u searches\n", plan.slots, st.why[18], st.vis_host, st.vis_peak,
+            (double)st.vis_sum / std::max(1u, st.vis_searches), st.vis_searches);
+}
+
+// what a finished call leaves on the graph (entry point, the hashed set's totals, `last`) and hands to its caller
+void fold_insert(fvdb_graph* g, const InsertPlan& plan, const BuildState& st, uint32_t launches, uint32_t* n_done,
+                 fvdb_graph_insert_stats* stats) {
+  if (plan.repr == 2) {
+    g->ins_hashed += st.cursor;
+    g->ins_vis_over += st.vis_host;
+    g->ins_vis_searches += st.vis_searches;
+    g->ins_vis_entries += st.vis_sum;
+    g->ins_vis_peak = std::max(g->ins_vis_peak, st.vis_peak);
+  }
+  g->entry = st.entry;
+  g->top_level = st.entry_level;
+  g->has_entry = st.has_entry != 0;
+  // n_done, needs_host | speculated_ok, searched_in_commit, commit_stops | rounds, expanded, rows_scored, tie_restarts | launches
+  const fvdb_graph_insert_stats acc{st.cursor, st.status, st.n_valid, st.n_rerun, st.n_stopped, st.rounds, st.consumed, st.scored, st.ties, launches};
+  g->last = acc;
+  if (stats) *stats = acc;
+  if (n_done) *n_done = st.cursor;
+}
+
+// The traversal kernels: the sorted-register kernel per (128-dim blocks NB, rows per scoring round R, byte map or bitmap
+// as `visited`), the exact-heap kernel per place of its `nearest` heap.
+using FastKernel = decltype(&hnsw_search_fast_kernel<3, 16, true>);
+template <int NB, int R>
+FastKernel fast_kernel_of(bool bytemap) {
+  return bytemap ? hnsw_search_fast_kernel<NB, R, true> : hnsw_search_fast_kernel<NB, R, false>;
+}
+FastKernel fast_kernel(uint32_t nb128, int R, bool bytemap) {
+  switch (nb128) {
+    case 1: return fast_kernel_of<1, 16>(bytemap);
+    case 2: return fast_kernel_of<2, 16>(bytemap);
+    case 3: return R == 8 ? fast_kernel_of<3, 8>(bytemap) : R == 12 ? fast_kernel_of<3, 12>(bytemap) : fast_kernel_of<3, 16>(bytemap);
+    case 4: return fast_kernel_of<4, 12>(bytemap);
+    case 5:
+    case 6: return fast_kernel_of<6, 8>(bytemap);
+    default: return fast_kernel_of<8, 6>(bytemap);
+  }
+}
+
+// What one traversal launch works with: the slot's scratch and its numbers (search_scratch), the kernel (search_kernel).
+struct SearchPlan {
+  bool bytemap;  // `visited` of a query: one byte per node, else one bit
+  uint32_t words, vstride, tcap, spill_cap, cand_cap;
+  size_t lds;         // dynamic LDS of a workgroup: of the exact-heap search first, then of the kernel chosen
+  uint32_t wave_lds;  // the sorted-register kernel's share of it per query (4 queries to a workgroup)
+  FastKernel fast;    // the sorted-register kernel, or
+  decltype(&hnsw_search_kernel<true>) exact;  // the exact-heap kernel, one query per workgroup;
+  bool rh;            // its `nearest` in registers (ef <= 63): the candidates heap may continue in the HBM spill
+};
+
+// sizes and (re)zeroes the slot's visited maps, touched log and spill for (B, n)
+int search_scratch(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, uint32_t B, uint32_t ef, SearchPlan* sp) {
+  // visited-log capacity per query: a query that outgrows it clears its whole map at the end of the layer instead of
+  // entry by entry (FVDB_GRAPH_TCAP: test hook that forces that)
+  sp->words = (g->n + 31) / 32;
+  sp->tcap = getenv("FVDB_GRAPH_TCAP") ? std::max(1, atoi(getenv("FVDB_GRAPH_TCAP"))) : 8192;
+  // visited set per query: one byte per node while a batch's maps stay under 1 GiB (no atomics, see
+  // kernels_graph_fast.h), else one bit per node; the row stride is the same for both views
+  static const bool no_bytes = getenv("FVDB_GRAPH_BITMAP") != nullptr;  // tuning aid / A-B (byte map: ~2.5 % faster, 8x the memory)
+  const uint32_t vbytes = ((g->n + 63) / 64) * 64;
+  sp->bytemap = !no_bytes && (uint64_t)vbytes * std::max<uint32_t>(B, 1024) <= (1ull << 30);
+  sp->vstride = sp->bytemap ? vbytes : sp->words * 4;
+  if (sp->words != g->vis_words || sp->tcap != g->vis_tcap || sp->vstride != g->vis_stride) {
+    for (auto& v : g->vis_B) v = 0;
+    g->vis_words = sp->words;
+    g->vis_tcap = sp->tcap;
+    g->vis_stride = sp->vstride;
+  }
+  if (B > g->vis_B[slot]) {  // the maps are left all-zero by every search: zero once
+    HIPCHK(ctx, g->s_visited[slot].ensure((size_t)B * sp->vstride));
+    HIPCHK(ctx, hipMemsetAsync(g->s_visited[slot].p, 0, g->s_visited[slot].cap, ctx->stream));
+    HIPCHK(ctx, g->s_touched[slot].ensure((size_t)B * sp->tcap * 4));
+    g->vis_B[slot] = B;
+  }
+  // where the restated candidates heap continues when it outgrows its LDS slots (duplicate-heavy data): no node is
+  // admitted twice, so a query never needs more than n slots
+  sp->spill_cap = std::min<uint32_t>(((g->n + 63) / 64) * 64, 8192);
+  HIPCHK(ctx, g->s_spill[slot].ensure((size_t)B * sp->spill_cap * 8));
+  // candidate-heap slots of the exact-heap search: it holds every admitted node not yet expanded; a query that
+  // overflows it goes to the host walk (data with many duplicate vectors fills it quickly, so it stays generous:
+  // at the default tile size the sorted-register kernel's LDS need is larger anyway)
+  const int cand_env = getenv("FVDB_GRAPH_CAND_CAP") ? atoi(getenv("FVDB_GRAPH_CAND_CAP")) : 0;  // test hook: forces the host-walk fallback
+  sp->cand_cap = cand_env > 0 ? (uint32_t)cand_env : std::max<uint32_t>(1024, 8 * ef);
+  sp->lds = graph_lds_bytes(g->store->dpad, ef, sp->cand_cap);
+  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
+  return FVDB_OK;
+}
+
+int search_kernel(fvdb_graph* g, fvdb_ctx* ctx, uint32_t ef, SearchPlan* sp) {
+  static const bool lds_heaps = getenv("FVDB_GRAPH_LDS_HEAPS") != nullptr;  // tuning aid: lane-0 heaps for any ef
+  sp->rh = ef <= 63 && !lds_heaps;
+  // ef <= 63: the sorted-register kernel; a query in which two heap members meet with equal distances is re-run by
+  // the same wave with the reference's heaps restated (exact on ties)
+  static const bool no_fast = getenv("FVDB_GRAPH_NO_FAST") != nullptr;  // tuning aid / A-B
+  static const int fast_r = getenv("FVDB_GRAPH_FAST_R") ? atoi(getenv("FVDB_GRAPH_FAST_R")) : 0;
+  const uint32_t nb128 = (g->store->dpad + 127) / 128;
+  if (no_fast || !sp->rh || nb128 > 8 || g->n >= 0x80000000u) {
+    sp->exact = sp->rh ? hnsw_search_kernel<true> : hnsw_search_kernel<false>;
+    return FVDB_OK;
+  }
+  int R = nb128 <= 3 ? 16 : (nb128 == 4 ? 12 : (nb128 <= 6 ? 8 : 6));  // rows per scoring round: registers R*NB*2
+  if (nb128 == 3 && (fast_r == 8 || fast_r == 12)) R = fast_r;
+  sp->wave_lds = (uint32_t)((std::max(graph_fast_lds_bytes((uint32_t)R), sp->lds) + 15) & ~(size_t)15);
+  sp->lds = 4 * (size_t)sp->wave_lds;
+  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
+  sp->fast = fast_kernel(nb128, R, sp->bytemap);
+  return FVDB_OK;
+}
+
+#ifdef FVDB_GRAPH_STAMPS
+// diagnostic build: prints what the traversal launches since the last call stamped (sums, and per query of the last
+// launch: cycles, placement, start and lifetime), clears it and returns the words for the next launch to write
+unsigned long long* graph_stamps_report(fvdb_graph* g) {
+  constexpr size_t kStampWords = 8 + 3 * 16384 + 4;  // 8 sums, then per query (cycles, hops, start tick) of the last launch
+  if (!g->d_stamps.p) {
+    (void)g->d_stamps.ensure(kStampWords * 8);
+    (void)hipMemset(g->d_stamps.p, 0, kStampWords * 8);
+  }
+  unsigned long long* d_stamps = g->d_stamps.as<unsigned long long>();
+  (void)hipDeviceSynchronize();
+  std::vector<unsigned long long> h(kStampWords);
+  (void)hipMemcpy(h.data(), d_stamps, kStampWords * 8, hipMemcpyDeviceToHost);
+  fprintf(stderr, "[graph stamps, cumulative] s0 %llu s1 %llu s2 %llu s3 %llu | rows %llu rounds %llu hops %llu total %llu | score: issue %llu "
+          "first-block wait+products %llu other-block products %llu adds %llu\n",
+          h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8 + 3 * 16384], h[8 + 3 * 16384 + 1], h[8 + 3 * 16384 + 2], h[8 + 3 * 16384 + 3]);
+  std::vector<unsigned long long> cyc, hp, rt;
+  {
+    // placement: HW_ID bits [3:0] wave, [5:4] simd, [11:8] cu, [12] sh, [15:13] se; top nibble = XCC
+    std::map<unsigned, unsigned> per_cu, per_simd;
+    unsigned late = 0;
+    unsigned long long first = ~0ull;
+    for (uint32_t q = 0; q < 16384; ++q)
+      if (h[8 + 3 * q]) first = std::min(first, h[8 + 3 * q + 1]);
+    for (uint32_t q = 0; q < 16384; ++q)
+      if (h[8 + 3 * q]) {
+        const unsigned hw = (unsigned)((h[8 + 3 * q] >> 32) & 0x0FFFFFFFu), xcc = (unsigned)(h[8 + 3 * q] >> 60);
+        const unsigned cu = (xcc << 16) | (hw & 0xFF00u);
+        per_cu[cu]++;
+        per_simd[(cu << 2) | ((hw >> 4) & 3)]++;
+        if (h[8 + 3 * q + 1] - first > 10000) late++;
+        h[8 + 3 * q] &= 0xFFFFFFFFull;
+      }
+    unsigned mx_cu = 0, mx_simd = 0;
+    for (auto& kv : per_cu) mx_cu = std::max(mx_cu, kv.second);
+    for (auto& kv : per_simd) mx_simd = std::max(mx_simd, kv.second);
+    fprintf(stderr, "[graph stamps, placement] CUs used %zu (max waves on one CU %u), SIMDs used %zu (max on one %u), waves starting > 100 us late: %u\n",
+            per_cu.size(), mx_cu, per_simd.size(), mx_simd, late);
+  }
+  for (uint32_t q = 0; q < 16384; ++q)
+    if (h[8 + 3 * q]) {
+      cyc.push_back(h[8 + 3 * q]);
+      hp.push_back(h[8 + 3 * q + 1]);
+      rt.push_back(h[8 + 3 * q + 2]);
+    }
+  if (!cyc.empty()) {
+    double csum = 0, rsum = 0;
+    for (size_t i = 0; i < cyc.size(); ++i) {
+      csum += (double)cyc[i];
+      rsum += (double)rt[i];
+    }
+    // hp = start tick (100 MHz), rt = lifetime ticks
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (size_t i = 0; i < cyc.size(); ++i) {
+      t0 = std::min(t0, hp[i]);
+      t1 = std::max(t1, hp[i] + rt[i]);
+    }
+    std::vector<unsigned long long> st;
+    for (size_t i = 0; i < cyc.size(); ++i) st.push_back(hp[i] - t0);
+    std::sort(cyc.begin(), cyc.end());
+    std::sort(st.begin(), st.end());
+    std::sort(rt.begin(), rt.end());
+    const size_t n = cyc.size();
+    fprintf(stderr, "[graph stamps, last launch] queries %zu  cycles p50 %llu max %llu | wave lifetime us p50 %.1f p99 %.1f max %.1f | clock %.2f GHz | "
+            "first start .. last end %.1f us; starts us: p25 %.1f p50 %.1f p75 %.1f p90 %.1f max %.1f\n", n, cyc[n / 2], cyc[n - 1],
+            rt[n / 2] / 100.0, rt[n * 99 / 100] / 100.0, rt[n - 1] / 100.0, csum / rsum / 10.0, (t1 - t0) / 100.0, st[n / 4] / 100.0,
+            st[n / 2] / 100.0, st[n * 3 / 4] / 100.0, st[n * 9 / 10] / 100.0, st[n - 1] / 100.0);
+  }
+  (void)hipMemset(d_stamps, 0, kStampWords * 8);
+  return d_stamps;
+}
+#else
+inline unsigned long long* graph_stamps_report(fvdb_graph*) { return nullptr; }
+#endif
 
 }  // namespace
 
@@ -310,7 +607,7 @@ void fvdb_graph_destroy(fvdb_graph* g) {
   (void)hipSetDevice(g->store->ctx->device);
   (void)hipStreamSynchronize(g->store->ctx->stream);
   DBuf* bufs[] = {&g->d_level, &g->d_deleted, &g->d_ubase, &g->d_adj0, &g->d_adjU, &g->d_dist0, &g->d_distU, &g->d_stamp0,
-                  &g->d_stampU, &g->d_state, &g->d_spec, &g->d_elog, &g->d_chg, &g->s_patch, &g->s_codes, &g->s_q, &g->d_counters};
+                  &g->d_stampU, &g->d_state, &g->d_spec, &g->d_elog, &g->d_chg, &g->s_patch, &g->s_codes, &g->s_q, &g->d_counters, &g->d_stamps, &g->d_build_stamps};
   for (auto& b : g->s_visited) b.release();
   for (auto& b : g->s_touched) b.release();
   for (auto& b : g->s_spill) b.release();
@@ -577,169 +874,42 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   if (s->dpad > 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: at most 1024 dimensions");
   if (g->n >= 0x80000000u) FAIL(ctx, FVDB_E_UNSUPPORTED, "device insert: node index needs 31 bits");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // LDS: `visited` (a bitmap over all nodes while that fits, a hashed set beyond) + fixed tables; the restated candidates
-  // heap gets what is left (<= 4096 slots)
+  // plan — LDS: `visited` (a bitmap over all nodes while that fits, a hashed set beyond) + fixed tables; the restated
+  // candidates heap gets what is left (<= 4096 slots)
   const InsertPlan plan = insert_plan(g, ef_construction);
   if (plan.repr == 0) FAIL(ctx, FVDB_E_UNSUPPORTED, plan.why);
-  const bool hashed = plan.repr == 2;
-  const uint32_t cand_cap = plan.cand_cap;
-  const BuildLds L = build_lds_layout(plan.words, ef_construction, cand_cap);
-  int rc = ensure_edge_dist(g);
-  if (rc) return rc;
+  int rc;
   BuildState st{};
-  rc = pull_state(g, &st);
-  if (rc) return rc;
-  if (st.n_linked != first) FAIL(ctx, FVDB_E_INVALID, "nodes are linked in store-row order");
-  st.cursor = 0;
-  st.status = 0;
-  st.n_valid = st.n_rerun = st.n_stopped = st.rounds = st.consumed = st.scored = st.ties = st.spec_ties = 0;
-  std::memset(st.why, 0, sizeof(st.why));
-  st.vis_host = st.vis_peak = st.vis_searches = 0;
-  st.vis_sum = 0;
-  rc = push_state(g, st);
-  if (rc) return rc;
-  // speculation pays once an insert touches a small part of the graph (mode 0 = choose; 1 = never; 2 = always)
-  static const int env_mode = getenv("FVDB_BUILD_MODE") ? atoi(getenv("FVDB_BUILD_MODE")) : 0;  // tuning aid / A-B
-  static const int env_k = getenv("FVDB_BUILD_K") ? atoi(getenv("FVDB_BUILD_K")) : 0;
-  static const int env_rerun = getenv("FVDB_BUILD_RERUN") ? atoi(getenv("FVDB_BUILD_RERUN")) : -1;
-  if (env_mode) mode = env_mode;
-  // FVDB_BUILD_STRICT=1: a speculation is dropped when ANY row it expanded changed (round-3 first form; A/B runs)
-  static const uint32_t strict = getenv("FVDB_BUILD_STRICT") ? (uint32_t)atoi(getenv("FVDB_BUILD_STRICT")) : 0u;
-  static const int env_kmax = getenv("FVDB_BUILD_KMAX") ? atoi(getenv("FVDB_BUILD_KMAX")) : 0;
-  // below this many nodes every insert lands in every other's neighbourhood: one at a time, no speculation
-  static const uint32_t seq_below = getenv("FVDB_BUILD_SEQ_BELOW") ? (uint32_t)atoi(getenv("FVDB_BUILD_SEQ_BELOW")) : 256u;
-  // (a call never speculates further than it has nodes to link: the logs of a batch are 160 KB per (insert, layer) slot)
-  const uint32_t Kmax = std::min<uint32_t>((uint32_t)std::max(1, std::min(env_k > 0 ? env_k : (env_kmax > 0 ? env_kmax : 128), 256)),
-                                           std::max<uint32_t>(8, n));
-  uint32_t K = env_k > 0 ? Kmax : std::min<uint32_t>(16, Kmax);  // adapts to the run length of adopted speculations
-  // 0: the commit workgroup adopts speculated searches up to the first one an earlier insert of the batch invalidated,
-  // searches that ONE itself (so every launch pair makes progress) and stops; the rest of the batch is speculated again,
-  // in parallel, against the graph as it then stands
-  const uint32_t max_rerun = env_rerun >= 0 ? (uint32_t)env_rerun : 0u;
-  HIPCHK(ctx, g->d_spec.ensure((size_t)Kmax * kSpecWords * 4));
-  HIPCHK(ctx, g->d_elog.ensure((size_t)Kmax * kBuildLayers * kLogWords * 4));
+  if ((rc = ensure_edge_dist(g)) || (rc = reset_build_state(g, first, &st))) return rc;
+  static const BuildKnobs knobs{};
+  BuildSchedule sched{knobs, knobs.mode ? knobs.mode : mode, first, n};
+  // launch: the batch logs, the kernels for this dimension and form of `visited`, then group after group
+  HIPCHK(ctx, g->d_spec.ensure((size_t)sched.Kmax * kSpecWords * 4));
+  HIPCHK(ctx, g->d_elog.ensure((size_t)sched.Kmax * kBuildLayers * kLogWords * 4));
   HIPCHK(ctx, g->d_chg.ensure((size_t)kChgCap * 4 * 4));
   if (n >= 8)  // (a call that cannot speculate skips this)
-    HIPCHK(ctx, hipMemsetAsync(g->d_spec.p, 0, (size_t)Kmax * kSpecWords * 4, ctx->stream));  // no stale "usable" flags
-  FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_commit_kernel<NB_, FULL_, HASH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_insert_search_kernel<NB_, FULL_, HASH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
-  });
-  BuildView v = build_view(g, ef_construction, cand_cap);
-  v.bitmap_words = plan.words;
-#ifdef FVDB_BUILD_STAMPS
-  static unsigned long long* d_dbg = nullptr;
-  if (!d_dbg) (void)hipMalloc(&d_dbg, 64 * 8);
-  (void)hipMemset(d_dbg, 0, 64 * 8);
-  v.dbg = d_dbg;
-#endif
-  fvdb_graph_insert_stats acc{};
-  uint32_t done = 0;
-  uint32_t exact_positions = 4;  // speculated searches of a batch that may start again with the restated heaps on a tie
-  uint32_t ties_seen = 0;
-  static const int env_xf = getenv("FVDB_BUILD_EXACT_FIRST") ? atoi(getenv("FVDB_BUILD_EXACT_FIRST")) : 1;    // A/B
-  // where ties are the rule (duplicate vectors) the register-set attempt is wasted work: the next `exact_left` rounds of
-  // this loop go straight to the restated heaps, then the question is asked again
-  uint32_t exact_left = 0, commit_ties_seen = 0;
+    HIPCHK(ctx, hipMemsetAsync(g->d_spec.p, 0, (size_t)sched.Kmax * kSpecWords * 4, ctx->stream));  // no stale "usable" flags
+  const BuildKernels kernels = build_kernels(s->dpad, plan.repr == 2);
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)kernels.commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)kernels.search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+  BuildView v = build_view(g, ef_construction, plan);
+  build_stamps_begin(g, &v);
+  uint32_t done = 0, launches = 0;
   while (done < n) {
-    const bool speculate = mode == 2 || (mode == 0 && (uint64_t)first + done >= seq_below && n - done >= 8);
-    uint32_t launches = 0;
-    v.exact_first = exact_left > 0 ? 1u : 0u;
-    if (exact_left) exact_left -= 1;
-    if (!speculate) {
-      uint32_t chunk = std::min<uint32_t>(n - done, 2048);  // bounds one launch to a fraction of a second
-      if (mode == 0 && (uint64_t)first + done < seq_below) chunk = std::min<uint32_t>(chunk, seq_below - (first + done));
-      g->tag += 1;
-      const uint32_t tag = g->tag;
-      FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
-        hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_, HASH_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n,
-                           chunk, tag, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 1u);
-      });
-      launches = 1;
-    } else {
-      const uint32_t pairs = std::min<uint32_t>(16, (n - done + K - 1) / K);  // the cursor lives on the device: no sync in between
-      for (uint32_t p = 0; p < pairs; ++p) {
-        g->tag += 1;
-        const uint32_t tag = g->tag;
-        FVDB_BUILD_SWITCH_V(s->dpad, hashed, {
-          hipLaunchKernelGGL((hnsw_insert_search_kernel<NB_, FULL_, HASH_>), dim3(K, kBuildLayers), dim3(kBuildThreads), L.total, ctx->stream, v,
-                             first, n, exact_positions, tag, g->d_spec.as<uint32_t>(), g->d_elog.as<uint32_t>());
-          hipLaunchKernelGGL((hnsw_insert_commit_kernel<NB_, FULL_, HASH_>), dim3(1), dim3(kBuildThreads), L.total, ctx->stream, v, first, n, K,
-                             tag, max_rerun, (const uint32_t*)g->d_spec.p, (const uint32_t*)g->d_elog.p, g->d_chg.as<uint32_t>(), strict);
-        });
-      }
-      launches = 2 * pairs;
-    }
+    const BuildGroup grp = sched.next(done);
+    v.exact_first = grp.exact_first;
+    launch_group(g, kernels, v, plan.lds_bytes, sched, grp);
     HIPCHK(ctx, hipGetLastError());
-    const uint32_t before = st.cursor;
-    rc = pull_state(g, &st);
-    if (rc) return rc;
-    acc.launches += launches;
-    if (speculate && env_k <= 0 && launches >= 2) {
-      // a batch is adopted up to its first conflict: speculating much further than the usual run only adds stragglers
-      // (the slowest of the batch's searches sets the launch's duration)
-      const uint32_t run = (st.cursor - before) / (launches / 2);
-      K = std::min<uint32_t>(Kmax, std::max<uint32_t>(8, 2 * run + 4));
-    }
-    if (speculate && launches >= 2) {  // where ties are the rule (duplicate vectors) every speculation takes the exact search
-      const uint32_t searched = (launches / 2) * K, tied = st.spec_ties - ties_seen;
-      if (!v.exact_first) exact_positions = 4 * tied > searched ? Kmax : 4;
-      if (env_xf && !v.exact_first && 2 * tied > searched) exact_left = 8;
-      ties_seen = st.spec_ties;
-    }
-    if (!speculate && env_xf && !v.exact_first && 2 * (st.ties - commit_ties_seen) > st.cursor - before) exact_left = 8;
-    commit_ties_seen = st.ties;
+    if ((rc = pull_state(g, &st))) return rc;
+    launches += grp.speculate ? 2 * grp.count : 1;
+    sched.update(grp, done, st);
     if (st.cursor == done && st.status == 0) FAIL(ctx, FVDB_E_HIP, "device insert made no progress");
     done = st.cursor;
     if (st.status) break;
   }
-#ifdef FVDB_BUILD_STAMPS
-  {
-    unsigned long long h[16];
-    (void)hipMemcpy(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[build stamps] of replay+select (us): replay %.1f  select %.1f  (table = the rest) | admissions %.1f\n", h[6] * 0.01 / std::max(1u, st.n_rerun),
-            h[7] * 0.01 / std::max(1u, st.n_rerun), (double)h[8] / std::max(1u, st.n_rerun));
-    const double us = 0.01, nn = std::max(1u, st.n_rerun);
-    fprintf(stderr, "[build stamps] per searched insert (us): replay+select %.1f  fetch %.1f  score %.1f | greedy %.1f  all searches %.1f  links %.1f"
-            " | rounds %.1f expanded %.1f scored %.0f\n", h[0] * us / nn, h[1] * us / nn, h[2] * us / nn, h[3] * us / nn, h[4] * us / nn,
-            h[5] * us / std::max(1u, done), st.rounds / nn, st.consumed / nn, st.scored / nn);
-  }
-#endif
-  if (getenv("FVDB_BUILD_DEBUG"))
-    fprintf(stderr, "[device insert] %u linked, %u adopted, stops %u: entry %u, gave-up %u, order/strict %u, caps %u, added node nearer than a later pop %u, added node inside the final set %u, dropped node matters %u | "
-            "checks %u, touched rows %u\n", done, st.n_valid, st.n_stopped, st.why[1], st.why[2], st.why[3], st.why[4], st.why[5], st.why[6],
-            st.why[9], st.why[7], st.why[8]);
-  if (getenv("FVDB_BUILD_DEBUG"))
-    fprintf(stderr, "[device insert] searches that left the register set: pops tied %u, evictions tied %u, result tied %u, heap overflow %u | speculations given up or restarted %u\n",
-            st.why[11], st.why[12], st.why[13], st.why[14], st.spec_ties);
-  if (getenv("FVDB_BUILD_DEBUG"))
-    fprintf(stderr, "[device insert] second looks: overlapping %u, nodes the popped newcomer would bring in %u, later pop is the maximum %u\n", st.why[15], st.why[16], st.why[17]);
-  if (hashed && getenv("FVDB_BUILD_DEBUG"))
-    fprintf(stderr, "[device insert] hashed visited set, %u slots: %u searches gave up on a full set (%u of them inserts handed to the host), "
-            "entries after a search: largest %u, mean %.0f over %u searches\n", plan.slots, st.why[18], st.vis_host, st.vis_peak,
-            (double)st.vis_sum / std::max(1u, st.vis_searches), st.vis_searches);
-  if (hashed) {
-    g->ins_hashed += done;
-    g->ins_vis_over += st.vis_host;
-    g->ins_vis_searches += st.vis_searches;
-    g->ins_vis_entries += st.vis_sum;
-    g->ins_vis_peak = std::max(g->ins_vis_peak, st.vis_peak);
-  }
-  g->entry = st.entry;
-  g->top_level = st.entry_level;
-  g->has_entry = st.has_entry != 0;
-  acc.n_done = done;
-  acc.needs_host = st.status;
-  acc.speculated_ok = st.n_valid;
-  acc.searched_in_commit = st.n_rerun;
-  acc.commit_stops = st.n_stopped;
-  acc.rounds = st.rounds;
-  acc.expanded = st.consumed;
-  acc.rows_scored = st.scored;
-  acc.tie_restarts = st.ties;
-  g->last = acc;
-  if (stats) *stats = acc;
-  if (n_done) *n_done = done;
+  build_stamps_print(g, st, done);
+  report_insert(plan, st);
+  fold_insert(g, plan, st, launches, n_done, stats);
   return FVDB_OK;
 }
 
@@ -803,123 +973,18 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
                        s->dpad, (uint64_t)B, g->s_q.as<float>());
     qd = g->s_q.as<float>();
   }
-  // visited-log capacity per query: a query that outgrows it clears its whole map at the end of the layer instead of
-  // entry by entry (FVDB_GRAPH_TCAP: test hook that forces that)
-  const uint32_t words = (g->n + 31) / 32;
-  const uint32_t tcap = getenv("FVDB_GRAPH_TCAP") ? std::max(1, atoi(getenv("FVDB_GRAPH_TCAP"))) : 8192;
-  // visited set per query: one byte per node while a batch's maps stay under 1 GiB (no atomics, see
-  // kernels_graph_fast.h), else one bit per node; the row stride is the same for both views
-  static const bool no_bytes = getenv("FVDB_GRAPH_BITMAP") != nullptr;  // tuning aid / A-B (byte map: ~2.5 % faster, 8x the memory)
-  const uint32_t vbytes = ((g->n + 63) / 64) * 64;
-  const bool bytemap = !no_bytes && (uint64_t)vbytes * std::max<uint32_t>(B, 1024) <= (1ull << 30);
-  const uint32_t vstride = bytemap ? vbytes : words * 4;
-  if (words != g->vis_words || tcap != g->vis_tcap || vstride != g->vis_stride) {
-    for (auto& v : g->vis_B) v = 0;
-    g->vis_words = words;
-    g->vis_tcap = tcap;
-    g->vis_stride = vstride;
-  }
-  if (B > g->vis_B[slot]) {  // the maps are left all-zero by every search: zero once
-    HIPCHK(ctx, g->s_visited[slot].ensure((size_t)B * vstride));
-    HIPCHK(ctx, hipMemsetAsync(g->s_visited[slot].p, 0, g->s_visited[slot].cap, ctx->stream));
-    HIPCHK(ctx, g->s_touched[slot].ensure((size_t)B * tcap * 4));
-    g->vis_B[slot] = B;
-  }
-  // where the restated candidates heap continues when it outgrows its LDS slots (duplicate-heavy data): no node is
-  // admitted twice, so a query never needs more than n slots
-  const uint32_t spill_cap = std::min<uint32_t>(((g->n + 63) / 64) * 64, 8192);
-  HIPCHK(ctx, g->s_spill[slot].ensure((size_t)B * spill_cap * 8));
-  // candidate-heap slots of the exact-heap search: it holds every admitted node not yet expanded; a query that
-  // overflows it goes to the host walk (data with many duplicate vectors fills it quickly, so it stays generous:
-  // at the default tile size the sorted-register kernel's LDS need is larger anyway)
-  const int cand_env = getenv("FVDB_GRAPH_CAND_CAP") ? atoi(getenv("FVDB_GRAPH_CAND_CAP")) : 0;  // test hook: forces the host-walk fallback
-  const uint32_t cand_cap = cand_env > 0 ? (uint32_t)cand_env : std::max<uint32_t>(1024, 8 * ef);
-  const size_t lds = graph_lds_bytes(s->dpad, ef, cand_cap);
-  if (lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
-  static const bool lds_heaps = getenv("FVDB_GRAPH_LDS_HEAPS") != nullptr;  // tuning aid: lane-0 heaps for any ef
-  const bool rh = ef <= 63 && !lds_heaps;
-  if (lds > 48 * 1024) {
-    if (rh) HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_search_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    else HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_search_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  GraphView gv{s->data, g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(), g->d_adj0.as<uint32_t>(), g->d_ubase.as<uint32_t>(),
-               g->d_adjU.as<uint32_t>(), g->stride0, g->strideU, g->n, s->dpad, g->entry, g->top_level, g->n_deleted ? 1u : 0u,
-               nullptr, nullptr};
+  SearchPlan sp{};
+  int rc;
+  if ((rc = search_scratch(g, ctx, slot, B, ef, &sp)) || (rc = search_kernel(g, ctx, ef, &sp))) return rc;
+  if (sp.lds > 48 * 1024)
+    HIPCHK(ctx, hipFuncSetAttribute(sp.fast ? (const void*)sp.fast : (const void*)sp.exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
   if (!g->d_counters.p) {
     HIPCHK(ctx, g->d_counters.ensure(32));
     HIPCHK(ctx, hipMemsetAsync(g->d_counters.p, 0, 32, ctx->stream));
   }
-  gv.counters = (unsigned long long*)g->d_counters.p;
-#ifdef FVDB_GRAPH_STAMPS
-  static unsigned long long* d_stamps = nullptr;
-  constexpr size_t kStampWords = 8 + 3 * 16384 + 4;  // 8 sums, then per query (cycles, hops, start tick) of the last launch
-  if (!d_stamps) {
-    (void)hipMalloc(&d_stamps, kStampWords * 8);
-    (void)hipMemset(d_stamps, 0, kStampWords * 8);
-  }
-  gv.stamps = d_stamps;
-  {
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(kStampWords);
-    (void)hipMemcpy(h.data(), d_stamps, kStampWords * 8, hipMemcpyDeviceToHost);
-    fprintf(stderr, "[graph stamps, cumulative] s0 %llu s1 %llu s2 %llu s3 %llu | rows %llu rounds %llu hops %llu total %llu | score: issue %llu "
-            "first-block wait+products %llu other-block products %llu adds %llu\n",
-            h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8 + 3 * 16384], h[8 + 3 * 16384 + 1], h[8 + 3 * 16384 + 2], h[8 + 3 * 16384 + 3]);
-    std::vector<unsigned long long> cyc, hp, rt;
-    {
-      // placement: HW_ID bits [3:0] wave, [5:4] simd, [11:8] cu, [12] sh, [15:13] se; top nibble = XCC
-      std::map<unsigned, unsigned> per_cu, per_simd;
-      unsigned late = 0;
-      unsigned long long first = ~0ull;
-      for (uint32_t q = 0; q < 16384; ++q)
-        if (h[8 + 3 * q]) first = std::min(first, h[8 + 3 * q + 1]);
-      for (uint32_t q = 0; q < 16384; ++q)
-        if (h[8 + 3 * q]) {
-          const unsigned hw = (unsigned)((h[8 + 3 * q] >> 32) & 0x0FFFFFFFu), xcc = (unsigned)(h[8 + 3 * q] >> 60);
-          const unsigned cu = (xcc << 16) | (hw & 0xFF00u);
-          per_cu[cu]++;
-          per_simd[(cu << 2) | ((hw >> 4) & 3)]++;
-          if (h[8 + 3 * q + 1] - first > 10000) late++;
-          h[8 + 3 * q] &= 0xFFFFFFFFull;
-        }
-      unsigned mx_cu = 0, mx_simd = 0;
-      for (auto& kv : per_cu) mx_cu = std::max(mx_cu, kv.second);
-      for (auto& kv : per_simd) mx_simd = std::max(mx_simd, kv.second);
-      fprintf(stderr, "[graph stamps, placement] CUs used %zu (max waves on one CU %u), SIMDs used %zu (max on one %u), waves starting > 100 us late: %u\n",
-              per_cu.size(), mx_cu, per_simd.size(), mx_simd, late);
-    }
-    for (uint32_t q = 0; q < 16384; ++q)
-      if (h[8 + 3 * q]) {
-        cyc.push_back(h[8 + 3 * q]);
-        hp.push_back(h[8 + 3 * q + 1]);
-        rt.push_back(h[8 + 3 * q + 2]);
-      }
-    if (!cyc.empty()) {
-      double csum = 0, rsum = 0;
-      for (size_t i = 0; i < cyc.size(); ++i) {
-        csum += (double)cyc[i];
-        rsum += (double)rt[i];
-      }
-      // hp = start tick (100 MHz), rt = lifetime ticks
-      unsigned long long t0 = ~0ull, t1 = 0;
-      for (size_t i = 0; i < cyc.size(); ++i) {
-        t0 = std::min(t0, hp[i]);
-        t1 = std::max(t1, hp[i] + rt[i]);
-      }
-      std::vector<unsigned long long> st;
-      for (size_t i = 0; i < cyc.size(); ++i) st.push_back(hp[i] - t0);
-      std::sort(cyc.begin(), cyc.end());
-      std::sort(st.begin(), st.end());
-      std::sort(rt.begin(), rt.end());
-      const size_t n = cyc.size();
-      fprintf(stderr, "[graph stamps, last launch] queries %zu  cycles p50 %llu max %llu | wave lifetime us p50 %.1f p99 %.1f max %.1f | clock %.2f GHz | "
-              "first start .. last end %.1f us; starts us: p25 %.1f p50 %.1f p75 %.1f p90 %.1f max %.1f\n", n, cyc[n / 2], cyc[n - 1],
-              rt[n / 2] / 100.0, rt[n * 99 / 100] / 100.0, rt[n - 1] / 100.0, csum / rsum / 10.0, (t1 - t0) / 100.0, st[n / 4] / 100.0,
-              st[n / 2] / 100.0, st[n * 3 / 4] / 100.0, st[n * 9 / 10] / 100.0, st[n - 1] / 100.0);
-    }
-    (void)hipMemset(d_stamps, 0, kStampWords * 8);
-  }
-#endif
+  const GraphView gv{s->data, g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(), g->d_adj0.as<uint32_t>(), g->d_ubase.as<uint32_t>(),
+                     g->d_adjU.as<uint32_t>(), g->stride0, g->strideU, g->n, s->dpad, g->entry, g->top_level, g->n_deleted ? 1u : 0u,
+                     g->d_counters.as<unsigned long long>(), graph_stamps_report(g)};
   hipEvent_t* ev = nullptr;
   if (s->ctx->profiling) {  // the store's context carries the switch, whichever stream the launch goes to
     ev = g->kev[g->kev_n & 63];
@@ -929,56 +994,14 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
     }
     (void)hipEventRecord(ev[0], ctx->stream);
   }
-  // ef <= 63: the sorted-register kernel; a query in which two heap members meet with equal distances is re-run by
-  // the same wave with the reference's heaps restated (exact on ties)
-  static const bool no_fast = getenv("FVDB_GRAPH_NO_FAST") != nullptr;  // tuning aid / A-B
-  static const int fast_r = getenv("FVDB_GRAPH_FAST_R") ? atoi(getenv("FVDB_GRAPH_FAST_R")) : 0;
-  const uint32_t nb128 = (s->dpad + 127) / 128;
-  const bool fast = !no_fast && rh && nb128 <= 8 && g->n < 0x80000000u;
-  if (fast) {
-    int R = nb128 <= 3 ? 16 : (nb128 == 4 ? 12 : (nb128 <= 6 ? 8 : 6));  // rows per scoring round: registers R*NB*2
-    if (nb128 == 3 && (fast_r == 8 || fast_r == 12)) R = fast_r;
-    const uint32_t wave_lds = (uint32_t)((std::max(graph_fast_lds_bytes((uint32_t)R), lds) + 15) & ~(size_t)15);
-#define FVDB_FAST_LAUNCH_V(NB_, R_, BY_)                                                                                   \
-  do {                                                                                                                    \
-    if (4 * wave_lds > 48 * 1024)                                                                                         \
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)hnsw_search_fast_kernel<NB_, R_, BY_>,                                 \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * wave_lds)));                  \
-    hipLaunchKernelGGL((hnsw_search_fast_kernel<NB_, R_, BY_>), dim3(cdiv(B, 4)), dim3(256), 4 * wave_lds, ctx->stream,   \
-                       gv, qd, B, k, ef, cand_cap, wave_lds, g->s_visited[slot].as<uint8_t>(), vstride, words,            \
-                       g->s_touched[slot].as<uint32_t>(), tcap, out_nodes_dev, out_dist_dev, out_counts_dev,              \
-                       out_status_dev, (HItem*)g->s_spill[slot].p, spill_cap);                                            \
-  } while (0)
-#define FVDB_FAST_LAUNCH(NB_, R_)                  \
-  do {                                             \
-    if (bytemap) FVDB_FAST_LAUNCH_V(NB_, R_, true); \
-    else FVDB_FAST_LAUNCH_V(NB_, R_, false);       \
-  } while (0)
-    if (4 * (size_t)wave_lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
-    switch (nb128) {
-      case 1: FVDB_FAST_LAUNCH(1, 16); break;
-      case 2: FVDB_FAST_LAUNCH(2, 16); break;
-      case 3:
-        if (R == 8) FVDB_FAST_LAUNCH(3, 8);
-        else if (R == 12) FVDB_FAST_LAUNCH(3, 12);
-        else FVDB_FAST_LAUNCH(3, 16);
-        break;
-      case 4: FVDB_FAST_LAUNCH(4, 12); break;
-      case 5:
-      case 6: FVDB_FAST_LAUNCH(6, 8); break;
-      default: FVDB_FAST_LAUNCH(8, 6); break;
-    }
-#undef FVDB_FAST_LAUNCH_V
-#undef FVDB_FAST_LAUNCH
-  } else if (rh) {
-    hipLaunchKernelGGL(hnsw_search_kernel<true>, dim3(B), dim3(64), lds, ctx->stream, gv, qd, B, k, ef, cand_cap,
-                       g->s_visited[slot].as<uint32_t>(), vstride / 4, g->s_touched[slot].as<uint32_t>(), tcap, out_nodes_dev, out_dist_dev,
-                       out_counts_dev, out_status_dev, (HItem*)g->s_spill[slot].p, spill_cap);
-  } else {
-    hipLaunchKernelGGL(hnsw_search_kernel<false>, dim3(B), dim3(64), lds, ctx->stream, gv, qd, B, k, ef, cand_cap,
-                       g->s_visited[slot].as<uint32_t>(), vstride / 4, g->s_touched[slot].as<uint32_t>(), tcap, out_nodes_dev, out_dist_dev,
-                       out_counts_dev, out_status_dev, (HItem*)nullptr, 0u);
-  }
+  if (sp.fast)
+    hipLaunchKernelGGL(sp.fast, dim3(cdiv(B, 4)), dim3(256), sp.lds, ctx->stream, gv, qd, B, k, ef, sp.cand_cap, sp.wave_lds,
+                       g->s_visited[slot].as<uint8_t>(), sp.vstride, sp.words, g->s_touched[slot].as<uint32_t>(), sp.tcap, out_nodes_dev,
+                       out_dist_dev, out_counts_dev, out_status_dev, (HItem*)g->s_spill[slot].p, sp.spill_cap);
+  else  // (lane-0 heaps stay in LDS: no spill)
+    hipLaunchKernelGGL(sp.exact, dim3(B), dim3(64), sp.lds, ctx->stream, gv, qd, B, k, ef, sp.cand_cap, g->s_visited[slot].as<uint32_t>(),
+                       sp.vstride / 4, g->s_touched[slot].as<uint32_t>(), sp.tcap, out_nodes_dev, out_dist_dev, out_counts_dev,
+                       out_status_dev, sp.rh ? (HItem*)g->s_spill[slot].p : nullptr, sp.rh ? sp.spill_cap : 0u);
   if (ev) {
     (void)hipEventRecord(ev[1], ctx->stream);
     g->kev_n += 1;

@@ -282,6 +282,7 @@ class HNSWIndex {
   bool host_link_reported_ = false;  // the stderr line "device insert refused, linking on the host" was written
   fvdb_graph_insert_stats insert_stats_{};
   uint64_t n_host_inserts_ = 0;
+  void add_insert_stats(const fvdb_graph_insert_stats& st);  // one fvdb_graph_insert_linked call into the sums
   int ensure_graph_handle();
   int ensure_host_graph();
   bool device_insert_ok() const;

@@ -860,6 +860,20 @@ void HNSWIndex::finalize_insert(uint32_t row) {  // "nodes.insert(id, node)" (:3
   n_registered_ += 1;
 }
 
+void HNSWIndex::add_insert_stats(const fvdb_graph_insert_stats& st) {
+  insert_stats_.n_done += st.n_done;
+  insert_stats_.speculated_ok += st.speculated_ok;
+  insert_stats_.searched_in_commit += st.searched_in_commit;
+  insert_stats_.commit_stops += st.commit_stops;
+  insert_stats_.rounds += st.rounds;
+  insert_stats_.expanded += st.expanded;
+  insert_stats_.rows_scored += st.rows_scored;
+  insert_stats_.tie_restarts += st.tie_restarts;
+  insert_stats_.launches += st.launches;
+  n_dist_ += st.rows_scored;  // of the searches the commit workgroup ran (speculated ones are not counted)
+  n_hops_ += st.rounds;
+}
+
 int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const int64_t* levels, uint64_t* n_ok,
                             int* first_error) {
   if (n_ok) *n_ok = 0;
@@ -955,17 +969,7 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
         }
       }
       if (rc) return finish(rc);
-      insert_stats_.n_done += st.n_done;
-      insert_stats_.speculated_ok += st.speculated_ok;
-      insert_stats_.searched_in_commit += st.searched_in_commit;
-      insert_stats_.commit_stops += st.commit_stops;
-      insert_stats_.rounds += st.rounds;
-      insert_stats_.expanded += st.expanded;
-      insert_stats_.rows_scored += st.rows_scored;
-      insert_stats_.tie_restarts += st.tie_restarts;
-      insert_stats_.launches += st.launches;
-      n_dist_ += st.rows_scored;  // of the searches the commit workgroup ran (speculated ones are not counted)
-      n_hops_ += st.rounds;
+      add_insert_stats(st);
       for (uint32_t j = 0; j < nd; ++j) finalize_insert(first + done + j);
       done += nd;
       dev_ahead_ = dev_ahead_ || nd > 0;
