@@ -120,6 +120,44 @@ struct Pool {
   }
 };
 
+// Words of the counter block of an index (fvdb_ivf::s_fallbacks, 32 bytes, and its pinned copy h_fb): running totals
+// since the centroids were installed, added to by the kernels named.
+enum FbWord : uint32_t {
+  FB_COARSE = 0,    // coarse_select_kernel: queries whose 64 proposals did not prove the ranking (exact ranking instead)
+  FB_SCAN = 1,      // select_kernel: queries not proven, rescanned exactly (VerifyArgs::fallbacks)
+  FB_REASONS = 2,   // [2..5] why, one word per reason (VerifyArgs::reasons): [2] the survivor buffer overflowed,
+                    // [3] more candidates than the select stage scores, [4] the k-th kept distance not strictly below
+                    // the bound, [5] no usable threshold
+  FB_OVERFLOW = 2,  // the first of them, watched by AUTO's refine decision
+  FB_REFINED = 6,   // refine_threshold_kernel: queries given a tighter threshold and a second filter pass
+  FB_WORDS = 8,     // [7] unused
+};
+constexpr size_t kFbBytes = FB_WORDS * 4;
+constexpr uint32_t kFbReasonWords = 5;  // fvdb_ivf_scan_fallback_reasons: words 2..6, the four reasons and the refine counter
+
+// Stage events of a search, recorded while profiling is on; finish_profile turns pairs of them into stage times.
+enum StageEvent {
+  EV_COARSE_BEGIN = 0,
+  EV_COARSE_SCANNED,  // centroid distances (or partial lists) done, selection / merge follows
+  EV_COARSE_DONE,
+  EV_SCAN_BEGIN,      // exact path: after the plan kernels; matrix-core path: before query prep
+  EV_SCAN_DONE,       // partial lists / survivors done, merge / select follows
+  EV_FINE_DONE,
+  EV_FILTER_BEGIN,    // the matrix-core filter kernel alone (inside the scan interval)
+  EV_FILTER_DONE,
+  EV_COUNT
+};
+
+// Words of IvfScratch::s_scalars (64 bytes).
+enum ScalWord : uint32_t {
+  SC_COARSE_ITEMS = 0,  // coarse scan: work items, queue head
+  SC_COARSE_HEAD = 1,
+  SC_FINE_ITEMS = 2,    // list scan: the same
+  SC_FINE_HEAD = 3,
+  SC_STATS = 4,         // [4..9] 3 x u64: rows scanned, work items, list rows touched (fvdb_ivf_last_stats)
+};
+constexpr size_t kScalarsBytes = 64;
+
 // Per-search scratch of an IVF index.  Set 0 lives in the index itself (also used by the mutating entry points);
 // sets 1..7 serve the other explicit slots of the *_slot entry points; a further pool of leased sets, each with a
 // stream of its own, serves the blocking host-pointer searches, so any number of host threads may search one index
@@ -129,15 +167,20 @@ struct IvfScratch {
   std::mutex enq;  // held while one search's launches are enqueued: searches sharing a set are ordered by the stream
   bool pend_filter = false;
   bool pending_profile = false, pend_coarse = false, pend_fine = false, collecting = false;
-  DBuf s_qnorm, s_A;
-  DBuf s_qh, s_qn2, s_thr, s_tA, s_pa, s_surv, s_scnt, s_fail, s_mslots, s_sdist, s_probes2;
-  DBuf s_q, s_cpart, s_probes, s_cnt, s_fill, s_eoff, s_ioff, s_entries, s_part, s_scalars, s_ceoff, s_cioff;
-  DBuf s_in, s_slots, s_ids, s_clusters, s_out_ids, s_out_dist, s_out_cnt, s_cdist;
-  hipEvent_t sev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // a buffer of the set enrols itself on construction, so that release_all cannot miss one
+  std::vector<DBuf*> bufs;
+  struct Buf : DBuf {
+    explicit Buf(IvfScratch* set) { set->bufs.push_back(this); }
+  };
+  Buf s_qnorm{this}, s_A{this};
+  Buf s_qh{this}, s_qn2{this}, s_thr{this}, s_tA{this}, s_pa{this}, s_surv{this}, s_scnt{this}, s_fail{this}, s_mslots{this};
+  Buf s_sdist{this}, s_probes2{this};
+  Buf s_q{this}, s_cpart{this}, s_probes{this}, s_cnt{this}, s_fill{this}, s_eoff{this}, s_ioff{this}, s_entries{this};
+  Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
+  Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
+  hipEvent_t sev[EV_COUNT] = {};
+  uint32_t* scalar(ScalWord w) const { return s_scalars.as<uint32_t>() + w; }
   void release_all() {
-    DBuf* bufs[] = {&s_qnorm, &s_A, &s_qh, &s_qn2, &s_thr, &s_tA, &s_pa, &s_surv, &s_scnt, &s_fail, &s_mslots, &s_sdist, &s_probes2,
-                    &s_q, &s_cpart, &s_probes, &s_cnt, &s_fill, &s_eoff, &s_ioff, &s_entries, &s_part, &s_scalars,
-                    &s_ceoff, &s_cioff, &s_in, &s_slots, &s_ids, &s_clusters, &s_out_ids, &s_out_dist, &s_out_cnt, &s_cdist};
     for (DBuf* b : bufs) b->release();
     for (auto& e : sev) {
       if (e) (void)hipEventDestroy(e);
@@ -168,21 +211,25 @@ struct fvdb_ivf : IvfScratch {
   DBuf d_centroids_rm;   // [nlist][d]
   DBuf d_cent_pad;       // [nlist][dpad] zero padded (only when d != dpad)
   DBuf d_cnorm, d_cnmax; // |c|^2 per centroid, max |c|^2 (matrix-core coarse stage)
-  DBuf s_fallbacks;
+  DBuf s_fallbacks;      // counter block (FbWord)
+  uint32_t* fb_word(FbWord w) const { return s_fallbacks.as<uint32_t>() + w; }
   int coarse_mode = 0;   // 0 = matrix cores + exact verification when applicable, 1 = exact scan only
   int scan_mode = 0;     // same choice for the inverted-list scan
   // AUTO scan mode watches its own hit rate: the rescan counter is copied to pinned host memory behind every
   // matrix-core batch (no sync); when too many queries of the recent batches needed the exact rescan (data the
   // filter cannot separate, e.g. no cluster structure), the next batches go straight to the exact scan
-  HBuf h_fb;                 // pinned copy of s_fallbacks[0..7]
+  HBuf h_fb;                 // pinned copy of s_fallbacks
   uint64_t mfma_q = 0;       // queries sent down the matrix-core path
   uint64_t fb_seen = 0, q_seen = 0;  // counter / queries at the last decision
   uint32_t exact_batches_left = 0;   // > 0: AUTO is backing off to the exact scan
   uint32_t backoff_len = 0;
   // the second filter pass for queries whose survivors outgrew the buffer (refine_threshold_kernel) costs five small
-  // launches per batch: AUTO enqueues them only while such queries have been seen recently (counters [2] and [6])
+  // launches per batch: AUTO enqueues them only while such queries have been seen recently (FB_OVERFLOW + FB_REFINED)
   uint64_t overflow_seen = 0, overflow_q = 0;
   uint32_t refine_batches_left = 0;
+  // diagnostic build only (-DFVDB_MFMA_STAMPS_BUILD): the filter's per-item timeline and the launches counted so far
+  DBuf d_mfma_stamps;
+  int mfma_stamps_launch = 0;
   DBuf d_xmax;           // max |x|^2 over the rows ever added (float bits)
   Pool cpool;
   DBuf c_off, c_blocks, c_glob;  // single-list table for the centroid pool
@@ -200,7 +247,7 @@ struct fvdb_ivf : IvfScratch {
 
   // per-search scratch
   fvdb_search_stats last_stats{};
-  // coarse scan, coarse merge, plan, fine scan, fine merge, [5] the matrix-core filter kernel alone (inside fine scan)
+  // coarse scan, coarse merge, plan, fine scan, fine merge, [5] the matrix-core filter kernel alone (kStageSpan)
   float stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t stage_calls = 0;
 };
@@ -217,9 +264,46 @@ inline IvfScratch& slot_scratch(fvdb_ivf* ivf, uint32_t slot) { return slot == 0
 
 
 // ---------------------------------------------------------------------------------------------
-// launch helpers
+// knobs and launch helpers
 // ---------------------------------------------------------------------------------------------
 namespace {
+
+// Environment knobs of the IVF search path: tuning aids for A/B runs, read once per process when the
+// first search asks for them, clamped here to values the code below can use as they are.
+struct IvfKnobs {
+  static int num(const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; }
+  static bool has(const char* name) { return getenv(name) != nullptr; }
+  static int tiles(int m) { return m >= 4 ? 4 : (m >= 2 ? 2 : 1); }
+  bool coarse_exact = has("FVDB_COARSE_EXACT");  // centroid ranking by the exact scan only
+  bool scan_exact = has("FVDB_SCAN_EXACT");      // list scan by the exact scan only
+  uint32_t scan_wgs_per_cu = (uint32_t)num("FVDB_SCAN_WGS_PER_CU", 8);  // exact scan: workgroups per CU
+  int segb = num("FVDB_SEGB", 0);                                       // > 0: its blocks per segment, fixed
+  bool no_shared_thr = has("FVDB_NO_SHARED_THR");  // sharded search: every rank computes every threshold itself
+  // the matrix-core list scan (run_fine_mfma), wave form
+  int mfma_m = tiles(num("FVDB_MFMA_M", 2));  // 16-query tiles per group: 1, 2 or 4
+  int mfma_segb = num("FVDB_MFMA_SEGB", 0);   // > 0: blocks per segment, fixed
+  uint32_t mfma_wgs_per_cu = (uint32_t)std::max(1, num("FVDB_MFMA_WGS_PER_CU", 2));
+  bool mfma_groups_in_item = num("FVDB_MFMA_GROUPS_IN_ITEM", 0) != 0;  // MfmaScanArgs::groups_in_item (A/B)
+  // its workgroup form (kernels_mfma_wg.h); 0 = always the wave form
+  bool mfma_wg = num("FVDB_MFMA_WG", 1) != 0;
+  int mfma_wg_m = num("FVDB_MFMA_WG_M", 4) >= 4 ? 4 : 2;
+  uint32_t mfma_wg_segb = (uint32_t)std::max(4, num("FVDB_MFMA_WG_SEGB", 16));
+  uint32_t mfma_wg_per_cu = (uint32_t)std::max(1, num("FVDB_MFMA_WG_PER_CU", 2));
+  int mfma_wg_tail_pct = num("FVDB_MFMA_WG_TAIL_PCT", 25);    // the last quarter of the lists ...
+  int mfma_wg_segb_tail = num("FVDB_MFMA_WG_SEGB_TAIL", 4);   // ... in small segments (MfmaScanArgs::lsplit)
+  // the threshold: blocks sampled; the earlier matrix-core pass instead of the direct kernel (A/B), and its segments
+  uint32_t mfma_cap_a = (uint32_t)std::max(1, num("FVDB_MFMA_CAP_A", 4));
+  bool mfma_threshold_pass = has("FVDB_MFMA_THRESHOLD_PASS");
+  uint32_t mfma_segb_a = (uint32_t)std::max(1, num("FVDB_MFMA_SEGB_A", 1));
+  bool mfma_no_refine = has("FVDB_MFMA_NO_REFINE");  // no second filter pass (A/B)
+#ifdef FVDB_MFMA_STAMPS_BUILD
+  int mfma_stamps = num("FVDB_MFMA_STAMPS", 0);  // first launch whose per-item timeline is printed (and the two after)
+#endif
+};
+const IvfKnobs& ivf_knobs() {
+  static const IvfKnobs knobs{};
+  return knobs;
+}
 
 struct ScanLaunch {
   PoolView pool;
@@ -243,8 +327,7 @@ inline uint32_t q_for(uint32_t k) { return k <= 64 ? 16u : (k <= 128 ? 8u : 4u);
 
 template <int Q, int KR, int ROLE, int ST>
 void launch_scan_t(fvdb_ctx* ctx, const ScanLaunch& s) {
-  static const uint32_t wgs_per_cu = getenv("FVDB_SCAN_WGS_PER_CU") ? (uint32_t)atoi(getenv("FVDB_SCAN_WGS_PER_CU")) : 8u;
-  uint32_t grid = (uint32_t)ctx->num_cus * wgs_per_cu;  // more than fit: surplus workgroups find the queue empty
+  uint32_t grid = (uint32_t)ctx->num_cus * ivf_knobs().scan_wgs_per_cu;  // more than fit: surplus workgroups find the queue empty
   if (s.max_items) grid = std::min(grid, std::max<uint32_t>(1u, (s.max_items + 3) / 4));  // 4 waves per workgroup
   hipLaunchKernelGGL((scan_topk_kernel<Q, KR, ROLE, ST>), dim3(grid), dim3(256), 0, ctx->stream, s.pool.data, s.pool.valid,
                      s.pool.d4, s.list_off, s.list_blocks, s.nlist, s.entry_off, s.item_off, (const u32x2*)s.entries,
@@ -278,10 +361,6 @@ void launch_merge(fvdb_ctx* ctx, const MergeArgs& m) {
     default: hipLaunchKernelGGL((merge_topk_kernel<4>), dim3(grid), dim3(256), 0, ctx->stream, m); break;
   }
 }
-
-// scalars block layout (uint32): [0]=coarse n_items [1]=coarse head [2]=fine n_items [3]=fine head
-//                                 [4..9] = stats (3 x u64)
-constexpr size_t kScalarsBytes = 64;
 
 int upload_table(fvdb_ivf* ivf) {
   fvdb_ctx* ctx = ivf->ctx;
@@ -329,31 +408,71 @@ int padded_queries(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32_t B, 
   return FVDB_OK;
 }
 
+inline void mark(const fvdb_ivf* ivf, const Env& E, StageEvent e) {
+  if (ivf->ctx->profiling) (void)hipEventRecord(E.S->sev[e], E.ctx->stream);
+}
+
+// One batch of a scan stage: B queries ([B][dpad], padded) with their probes[B][np] in HBM (nullptr: the single list of
+// the centroid pool), and where the k results per query go (any of them may be null).
+struct Batch {
+  const float* qpad;
+  const uint32_t* probes;
+  uint32_t B, k, np;
+  uint64_t* out_ids;
+  float* out_dist;
+  uint32_t* out_counts;
+  uint64_t* out_keys;
+};
+
+inline ListTable list_table(const fvdb_ivf* ivf) {
+  return ListTable{ivf->t_off.as<uint32_t>(), ivf->t_blocks.as<uint32_t>(), ivf->nlist};
+}
+
+// merge of the partial lists a scan of `pool` left in `part`; the caller adds what only it has (out_probes, qlist)
+MergeArgs merge_args(const PoolView& pool, const ListTable& lists, const uint32_t* glob_blocks, const DBuf& part,
+                     uint32_t maxsegs, uint32_t segb, const Batch& b) {
+  MergeArgs m{};
+  m.pool = pool;
+  m.lists = lists;
+  m.probes = b.probes;
+  m.glob_blocks = glob_blocks;
+  m.part = part.as<uint2>();
+  m.B = b.B;
+  m.k = b.k;
+  m.nprobe = b.np;
+  m.maxsegs = maxsegs;
+  m.segb = segb;
+  m.out_ids = b.out_ids;
+  m.out_dist = b.out_dist;
+  m.out_counts = b.out_counts;
+  m.out_keys = b.out_keys;
+  return m;
+}
+
 // Coarse stage: rank the centroid table for B queries, keep kc nearest per query.
 // Writes u32 cluster ids to out_probes[B][kc] (probe order) and, optionally, their distances.
 int run_coarse(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t kc, uint32_t* out_probes,
                float* out_dist) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
-  static const bool env_exact = getenv("FVDB_COARSE_EXACT") != nullptr;  // tuning aid
-  if (ivf->coarse_mode == 0 && !env_exact && ivf->dpad % 16 == 0 && kc <= 48 && ivf->nlist >= 64 && B > 0 &&
+  if (ivf->coarse_mode == 0 && !ivf_knobs().coarse_exact && ivf->dpad % 16 == 0 && kc <= 48 && ivf->nlist >= 64 && B > 0 &&
       (uint64_t)B * ivf->nlist < (1ull << 31)) {
     // matrix cores propose 64 candidates per query; the reference's arithmetic decides (kernels_coarse.h)
     const uint32_t nlist = ivf->nlist;
     const float* cpad = ivf->d == ivf->dpad ? ivf->d_centroids_rm.as<float>() : ivf->d_cent_pad.as<float>();
     HIPCHK(ctx, S.s_qnorm.ensure((size_t)B * 4));
     HIPCHK(ctx, S.s_A.ensure((size_t)B * nlist * 4));
-    if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[0], ctx->stream);
+    mark(ivf, E, EV_COARSE_BEGIN);
     hipLaunchKernelGGL(row_sqnorm_wave_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, qpad, ivf->dpad, ivf->dpad, B,
                        S.s_qnorm.as<float>());
     const uint32_t waves = cdiv(B, 32) * cdiv(nlist, 64);
     hipLaunchKernelGGL(coarse_gemm_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, ctx->stream, qpad, cpad,
                        S.s_qnorm.as<float>(), ivf->d_cnorm.as<float>(), B, nlist, ivf->dpad, S.s_A.as<float>());
-    if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[1], ctx->stream);
+    mark(ivf, E, EV_COARSE_SCANNED);
     hipLaunchKernelGGL(coarse_select_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, S.s_A.as<float>(), qpad, cpad,
                        S.s_qnorm.as<float>(), ivf->d_cnmax.as<float>(), B, nlist, ivf->d, ivf->dpad, 64u, kc,
-                       out_probes, out_dist, ivf->s_fallbacks.as<uint32_t>());
-    if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[2], ctx->stream);
+                       out_probes, out_dist, ivf->fb_word(FB_COARSE));
+    mark(ivf, E, EV_COARSE_DONE);
     HIPCHK(ctx, hipGetLastError());
     return FVDB_OK;
   }
@@ -365,376 +484,448 @@ int run_coarse(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint3
   HIPCHK(ctx, S.s_ceoff.ensure(16));
   HIPCHK(ctx, S.s_cioff.ensure(16));
   HIPCHK(ctx, S.s_scalars.ensure(kScalarsBytes));
-  uint32_t* scal = S.s_scalars.as<uint32_t>();
   hipLaunchKernelGGL(plan_all_kernel, dim3(cdiv(std::max<uint32_t>(B, 1), 256)), dim3(256), 0, ctx->stream, B, cblocks,
                      segb, Q, S.s_ceoff.as<uint32_t>(), S.s_cioff.as<uint32_t>(), S.s_entries.as<uint2>(),
-                     scal + 0, scal + 1);
-  ScanLaunch s{ivf->cpool.view(), ivf->c_off.as<uint32_t>(), ivf->c_blocks.as<uint32_t>(), 1,
-               S.s_ceoff.as<uint32_t>(), S.s_cioff.as<uint32_t>(), S.s_entries.as<uint2>(), scal + 0,
-               scal + 1, qpad, ivf->dpad, segb, kc, 1, maxsegs, S.s_cpart.as<uint2>(),
-               cdiv(cblocks, segb) * cdiv(B, Q)};
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[0], ctx->stream);
+                     S.scalar(SC_COARSE_ITEMS), S.scalar(SC_COARSE_HEAD));
+  const ListTable clist{ivf->c_off.as<uint32_t>(), ivf->c_blocks.as<uint32_t>(), 1};
+  ScanLaunch s{ivf->cpool.view(), clist.off, clist.blocks, 1, S.s_ceoff.as<uint32_t>(), S.s_cioff.as<uint32_t>(),
+               S.s_entries.as<uint2>(), S.scalar(SC_COARSE_ITEMS), S.scalar(SC_COARSE_HEAD), qpad, ivf->dpad, segb, kc, 1,
+               maxsegs, S.s_cpart.as<uint2>(), cdiv(cblocks, segb) * cdiv(B, Q)};
+  mark(ivf, E, EV_COARSE_BEGIN);
   launch_scan(ctx, s, ROLE_COARSE);
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[1], ctx->stream);
-  MergeArgs m{};
-  m.pool = ivf->cpool.view();
-  m.lists = ListTable{ivf->c_off.as<uint32_t>(), ivf->c_blocks.as<uint32_t>(), 1};
-  m.probes = nullptr;
-  m.glob_blocks = ivf->c_glob.as<uint32_t>();
-  m.part = S.s_cpart.as<uint2>();
-  m.B = B;
-  m.k = kc;
-  m.nprobe = 1;
-  m.maxsegs = maxsegs;
-  m.segb = segb;
+  mark(ivf, E, EV_COARSE_SCANNED);
+  MergeArgs m = merge_args(ivf->cpool.view(), clist, ivf->c_glob.as<uint32_t>(), S.s_cpart, maxsegs, segb,
+                           Batch{qpad, nullptr, B, kc, 1, nullptr, out_dist, nullptr, nullptr});
   m.out_probes = out_probes;
-  m.out_dist = out_dist;
   launch_merge(ctx, m);
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[2], ctx->stream);
+  mark(ivf, E, EV_COARSE_DONE);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
 
-uint32_t pick_segb(fvdb_ivf* ivf, uint32_t B, uint32_t nprobe) {
-  static const int forced = getenv("FVDB_SEGB") ? atoi(getenv("FVDB_SEGB")) : 0;  // tuning aid
-  if (forced > 0) return (uint32_t)forced;
-  // enough (segment, group) items to fill 256 CUs x 32 waves, without shredding long lists
+// Blocks per segment of the exact scan over lists of at most max_blocks blocks: enough (segment, group) items to fill
+// 256 CUs x 32 waves, without shredding long lists.
+uint32_t segb_for(uint32_t max_blocks, uint32_t B, uint32_t nprobe) {
   const uint64_t pairs = (uint64_t)B * nprobe;
-  if (ivf->max_list_blocks >= 4096) return 16;
+  if (max_blocks >= 4096) return 16;
   if (pairs >= 4096) return 4;
   if (pairs >= 512) return 2;
   return 1;
 }
+uint32_t pick_segb(fvdb_ivf* ivf, uint32_t B, uint32_t nprobe) {
+  const int forced = ivf_knobs().segb;
+  return forced > 0 ? (uint32_t)forced : segb_for(ivf->max_list_blocks, B, nprobe);
+}
+// queries whose fine-stage partial buffer stays under ~1 GiB
+uint64_t queries_per_gib(uint32_t max_blocks, uint32_t segb, uint32_t k, uint32_t np) {
+  const uint64_t per_q = (uint64_t)np * std::max<uint32_t>(1, cdiv(max_blocks, segb)) * k * 8;
+  return (1ull << 30) / std::max<uint64_t>(per_q, 1);
+}
 
-// Fine stage for B queries whose probes[B][np] are already in HBM: every row scored with the reference's fold.
-int run_fine_exact(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t k, uint32_t np,
-                   const uint32_t* probes, uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys,
-                   int role, bool events = true) {
+// The plan kernels (kernels_scan.h): n = B * np (query, probe) pairs -> per-list entries and the scan's work items.
+// cnt[] must be zero on entry; with rezero_cnt the scan kernel leaves it zero again for the next plan of the batch.
+void launch_plan(fvdb_ivf* ivf, const Env& E, const uint32_t* probes, uint32_t n, uint32_t np, uint32_t segb, uint32_t Q,
+                 unsigned long long* stats, uint32_t* rezero_cnt, uint32_t lsplit = 0xFFFFFFFFu, uint32_t segb_tail = 0) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  const uint32_t* list_off = ivf->t_off.as<uint32_t>();
+  hipLaunchKernelGGL(plan_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, probes, n, S.s_cnt.as<uint32_t>(),
+                     list_off);
+  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, S.s_cnt.as<uint32_t>(), list_off,
+                     ivf->t_len.as<uint32_t>(), ivf->nlist, segb, Q, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(),
+                     S.s_fill.as<uint32_t>(), S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), stats, rezero_cnt, lsplit,
+                     segb_tail);
+  hipLaunchKernelGGL(plan_fill_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, probes, n, np,
+                     S.s_eoff.as<uint32_t>(), S.s_fill.as<uint32_t>(), S.s_entries.as<uint2>(), list_off);
+}
+inline unsigned long long* scan_stats(const IvfScratch& S) { return (unsigned long long*)S.scalar(SC_STATS); }
+
+// what the plan kernels write (s_cnt is also cleared by prep_queries_kernel, s_part sized by the caller)
+int plan_scratch(fvdb_ivf* ivf, const Env& E, uint32_t B, uint32_t np) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
   const uint32_t nlist = ivf->nlist;
-  const uint32_t segb = pick_segb(ivf, B, np), Q = q_for(k);
-  const uint32_t maxsegs = std::max<uint32_t>(1, cdiv(ivf->max_list_blocks, segb));
-  const uint64_t part_elems = (uint64_t)B * np * maxsegs * k;
-  if (part_elems >= (1ull << 32)) FAIL(ctx, FVDB_E_UNSUPPORTED, "batch too large for one launch (sub-batch it)");
   HIPCHK(ctx, S.s_cnt.ensure((size_t)nlist * 4));
   HIPCHK(ctx, S.s_fill.ensure((size_t)nlist * 4));
   HIPCHK(ctx, S.s_eoff.ensure((size_t)(nlist + 1) * 4));
   HIPCHK(ctx, S.s_ioff.ensure((size_t)(nlist + 1) * 4));
   HIPCHK(ctx, S.s_entries.ensure((size_t)B * np * 8));
+  return FVDB_OK;
+}
+
+// Fine stage for B queries whose probes[B][np] are already in HBM: every row scored with the reference's fold.
+int run_fine_exact(fvdb_ivf* ivf, const Env& E, const Batch& b, int role) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  const uint32_t nlist = ivf->nlist;
+  const uint32_t segb = pick_segb(ivf, b.B, b.np), Q = q_for(b.k);
+  const uint32_t maxsegs = std::max<uint32_t>(1, cdiv(ivf->max_list_blocks, segb));
+  const uint64_t part_elems = (uint64_t)b.B * b.np * maxsegs * b.k;
+  if (part_elems >= (1ull << 32)) FAIL(ctx, FVDB_E_UNSUPPORTED, "batch too large for one launch (sub-batch it)");
+  int rc = plan_scratch(ivf, E, b.B, b.np);
+  if (rc) return rc;
   HIPCHK(ctx, S.s_part.ensure((size_t)part_elems * 8));
   HIPCHK(ctx, S.s_scalars.ensure(kScalarsBytes));
-  uint32_t* scal = S.s_scalars.as<uint32_t>();
-  const uint32_t n = B * np;
+  // nobody cleared cnt[] for this path, and no later plan of the batch needs it cleared again
   HIPCHK(ctx, hipMemsetAsync(S.s_cnt.p, 0, (size_t)nlist * 4, ctx->stream));
-  hipLaunchKernelGGL(plan_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, probes, n,
-                     S.s_cnt.as<uint32_t>(), ivf->t_off.as<uint32_t>());
-  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, S.s_cnt.as<uint32_t>(),
-                     ivf->t_off.as<uint32_t>(), ivf->t_len.as<uint32_t>(), nlist, segb, Q, S.s_eoff.as<uint32_t>(),
-                     S.s_ioff.as<uint32_t>(), S.s_fill.as<uint32_t>(), scal + 2, scal + 3,
-                     (unsigned long long*)(scal + 4));
-  hipLaunchKernelGGL(plan_fill_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, probes, n, np,
-                     S.s_eoff.as<uint32_t>(), S.s_fill.as<uint32_t>(), S.s_entries.as<uint2>(), ivf->t_off.as<uint32_t>());
-  if (ivf->ctx->profiling && events) (void)hipEventRecord(S.sev[3], ctx->stream);
-  ScanLaunch s{ivf->pool.view(), ivf->t_off.as<uint32_t>(), ivf->t_blocks.as<uint32_t>(), nlist,
-               S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(), S.s_entries.as<uint2>(), scal + 2,
-               scal + 3, qpad, ivf->dpad, segb, k, np, maxsegs, S.s_part.as<uint2>()};
+  launch_plan(ivf, E, b.probes, b.B * b.np, b.np, segb, Q, scan_stats(S), /*rezero_cnt=*/nullptr);
+  mark(ivf, E, EV_SCAN_BEGIN);
+  const ListTable lists = list_table(ivf);
+  ScanLaunch s{ivf->pool.view(), lists.off, lists.blocks, nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(),
+               S.s_entries.as<uint2>(), S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.k, b.np,
+               maxsegs, S.s_part.as<uint2>()};
   s.f16 = ivf->f16;
   launch_scan(ctx, s, role);
-  if (ivf->ctx->profiling && events) (void)hipEventRecord(S.sev[4], ctx->stream);
-  MergeArgs m{};
-  m.pool = ivf->pool.view();
-  m.lists = ListTable{ivf->t_off.as<uint32_t>(), ivf->t_blocks.as<uint32_t>(), nlist};
-  m.probes = probes;
-  m.glob_blocks = ivf->t_glob.as<uint32_t>();
-  m.part = S.s_part.as<uint2>();
-  m.B = B;
-  m.k = k;
-  m.nprobe = np;
-  m.maxsegs = maxsegs;
-  m.segb = segb;
-  m.out_ids = out_ids;
-  m.out_dist = out_dist;
-  m.out_counts = out_counts;
-  m.out_keys = out_keys;
-  launch_merge(ctx, m);
-  if (ivf->ctx->profiling && events) (void)hipEventRecord(S.sev[5], ctx->stream);
+  mark(ivf, E, EV_SCAN_DONE);
+  launch_merge(ctx, merge_args(ivf->pool.view(), lists, ivf->t_glob.as<uint32_t>(), S.s_part, maxsegs, segb, b));
+  mark(ivf, E, EV_FINE_DONE);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
 
-// Fine stage on the matrix cores (kernels_mfma.h): threshold from the nearest list, fp16 MFMA filter over all
-// probed lists, exact verification of the survivors, exact rescan of unproven queries.  Same outputs as
-// run_fine_exact.
+// ---- fine stage on the matrix cores (kernels_mfma.h): threshold from the nearest list, fp16 MFMA filter over all
+// probed lists, exact verification of the survivors, exact rescan of unproven queries.  Same outputs as run_fine_exact.
 constexpr uint32_t kMfmaSlack = 6;     // phase A scores k + 6 rows
 constexpr uint32_t kMfmaCmax = 4096;   // survivor slots per query
-namespace {
-int env_u(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
 
-template <int MODE>
-void launch_mfma(fvdb_ctx* ctx, const MfmaScanArgs& a, int M, bool f16, uint32_t grid) {
-#define FVDB_MFMA_CASE(MM)                                                                                      \
-  if (f16) hipLaunchKernelGGL((scan_mfma_kernel<MM, 1, MODE>), dim3(grid), dim3(256), 0, ctx->stream, a);       \
-  else hipLaunchKernelGGL((scan_mfma_kernel<MM, 0, MODE>), dim3(grid), dim3(256), 0, ctx->stream, a)
-  if (M == 1) { FVDB_MFMA_CASE(1); }
-  else if (M == 2) { FVDB_MFMA_CASE(2); }
-  else { FVDB_MFMA_CASE(4); }
-#undef FVDB_MFMA_CASE
+// Shapes the matrix-core filter serves.  thr_share_ok asks this too, and there every rank of a sharded search must
+// answer alike: nothing that differs between the ranks may enter.
+bool mfma_shape_ok(const fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
+  return ivf->dpad % 16 == 0 && k + kMfmaSlack <= 32 && np <= 256 && B >= 32 && B <= 16384;
 }
-}  // namespace
+// the filter reads fp16 rows (stored or mirrored)
+inline bool half_rows(const fvdb_ivf* ivf) { return ivf->f16 || ivf->pool.half != nullptr; }
+// those rows against the rows the reference sees (mfma_error_bound): 0 the same, 1 rounded to nearest, 2 truncated
+inline int x_rounded(const fvdb_ivf* ivf) { return ivf->f16 ? 0 : (ivf->pool.half ? 1 : 2); }
 
-int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t k, uint32_t np,
-                  const uint32_t* probes, uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys) {
+// What one matrix-core batch runs with, derived once from the index, the knobs and the batch shape.
+struct MfmaPlan {
+  bool wg;            // the workgroup form of the filter (kernels_mfma_wg.h), else the wave form
+  int M;              // 16-query tiles per group
+  uint32_t Q, ka, cmax;
+  uint32_t segb, segbA;              // blocks per segment: the filter, the threshold pass
+  uint32_t lsplit, segb_tail;        // workgroup form: lists >= lsplit in segments of segb_tail (MfmaScanArgs::lsplit)
+  uint32_t fsegb, fmaxsegs;          // partial lists of the exact rescan: same geometry as the exact scan's
+  uint64_t fpart;
+  uint32_t grid, wg_grid, wg_lds;    // wave form (and the rescan); workgroup form and its LDS bytes
+  bool half_rows;
+  int x_rounded;
+};
+
+int mfma_plan(fvdb_ivf* ivf, fvdb_ctx* ctx, const IvfKnobs& kn, uint32_t B, uint32_t k, uint32_t np, MfmaPlan* out) {
+  MfmaPlan P{};
+  P.half_rows = half_rows(ivf);
+  P.x_rounded = x_rounded(ivf);
+  // workgroup form: fp16 rows, dpad a multiple of 128, 32 or 64 queries per group
+  int wgM = kn.mfma_wg_m;
+  if (mfma_wg_lds_bytes(ivf->dpad, 16u * wgM) > 64u * 1024u) wgM = 2;  // wide rows: the 32-query tile still fits
+  P.wg = kn.mfma_wg && kn.mfma_m == 2 && P.half_rows && ivf->dpad % 128 == 0 &&
+         mfma_wg_lds_bytes(ivf->dpad, 16u * wgM) <= 64u * 1024u;
+  P.M = P.wg ? wgM : kn.mfma_m;
+  P.Q = 16u * P.M;
+  P.ka = k + kMfmaSlack;
+  P.cmax = kMfmaCmax;
+  P.segbA = kn.mfma_segb_a;
+  P.segb = P.wg ? kn.mfma_wg_segb : (kn.mfma_segb > 0 ? (uint32_t)kn.mfma_segb : pick_segb(ivf, B, np));
+  P.lsplit = 0xFFFFFFFFu;
+  P.segb_tail = P.segb;
+  if (P.wg && kn.mfma_wg_tail_pct > 0 && kn.mfma_wg_segb_tail > 0 && (uint32_t)kn.mfma_wg_segb_tail < P.segb) {
+    P.lsplit = (uint32_t)((uint64_t)ivf->nlist * (uint32_t)(100 - std::min(kn.mfma_wg_tail_pct, 100)) / 100);
+    P.segb_tail = (uint32_t)kn.mfma_wg_segb_tail;
+  }
+  P.fsegb = pick_segb(ivf, B, np);
+  P.fmaxsegs = std::max<uint32_t>(1, cdiv(ivf->max_list_blocks, P.fsegb));
+  P.fpart = (uint64_t)B * np * P.fmaxsegs * k;
+  if (P.fpart >= (1ull << 32)) FAIL(ctx, FVDB_E_UNSUPPORTED, "batch too large for one launch (sub-batch it)");
+  P.grid = (uint32_t)ctx->num_cus * kn.mfma_wgs_per_cu;
+  P.wg_grid = (uint32_t)ctx->num_cus * kn.mfma_wg_per_cu;
+  P.wg_lds = mfma_wg_lds_bytes(ivf->dpad, P.Q);
+  *out = P;
+  return FVDB_OK;
+}
+
+int mfma_scratch(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, uint32_t B, uint32_t np) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
-  // tuning aids
-  static const int M_env = env_u("FVDB_MFMA_M", 2), segb_env = env_u("FVDB_MFMA_SEGB", 0),
-                   segbA_env = env_u("FVDB_MFMA_SEGB_A", 1), capA_env = env_u("FVDB_MFMA_CAP_A", 4), wgs_env = env_u("FVDB_MFMA_WGS_PER_CU", 2);
-  static const int wg_m_env = env_u("FVDB_MFMA_WG_M", 4);
-  int M = M_env >= 4 ? 4 : (M_env >= 2 ? 2 : 1);
-  // the workgroup form of the filter (kernels_mfma_wg.h): fp16 rows, dpad a multiple of 128, 32 or 64 queries per group
-  static const int wg_env = env_u("FVDB_MFMA_WG", 1), wg_segb_env = env_u("FVDB_MFMA_WG_SEGB", 16),
-                   wg_wgs_env = env_u("FVDB_MFMA_WG_PER_CU", 2);
-  int wgM = wg_m_env >= 4 ? 4 : 2;
-  if (mfma_wg_lds_bytes(ivf->dpad, 16u * wgM) > 64u * 1024u) wgM = 2;  // wide rows: the 32-query tile still fits
-  const bool use_wg = wg_env && M == 2 && (ivf->f16 || ivf->pool.half != nullptr) && ivf->dpad % 128 == 0 &&
-                      mfma_wg_lds_bytes(ivf->dpad, 16u * wgM) <= 64u * 1024u;
-  if (use_wg) M = wgM;
-  const uint32_t Q = 16u * M;
-  const uint32_t nlist = ivf->nlist, ka = k + kMfmaSlack, cmax = kMfmaCmax;
-  const uint32_t segbA = std::max(1, segbA_env);
-  const uint32_t segb = use_wg ? (uint32_t)std::max(4, wg_segb_env)
-                               : (segb_env > 0 ? (uint32_t)segb_env : pick_segb(ivf, B, np));
-  // partial lists of the exact rescan: same geometry as the exact scan's
-  const uint32_t fsegb = pick_segb(ivf, B, np), fmaxsegs = std::max<uint32_t>(1, cdiv(ivf->max_list_blocks, fsegb));
-  const uint64_t fpart = (uint64_t)B * np * fmaxsegs * k;
-  if (fpart >= (1ull << 32)) FAIL(ctx, FVDB_E_UNSUPPORTED, "batch too large for one launch (sub-batch it)");
   HIPCHK(ctx, S.s_qh.ensure((size_t)(B + 1) * ivf->dpad * 2));
   HIPCHK(ctx, S.s_qn2.ensure((size_t)B * 4));
   HIPCHK(ctx, S.s_thr.ensure((size_t)B * 4));
   HIPCHK(ctx, S.s_tA.ensure((size_t)B * 4));
   HIPCHK(ctx, S.s_pa.ensure((size_t)B * 4));
   HIPCHK(ctx, S.s_mslots.ensure((size_t)B * 64 * 4));
-  HIPCHK(ctx, S.s_surv.ensure((size_t)B * cmax * 8));
-  HIPCHK(ctx, S.s_sdist.ensure((size_t)B * cmax * 4));
+  HIPCHK(ctx, S.s_surv.ensure((size_t)B * P.cmax * 8));
+  HIPCHK(ctx, S.s_sdist.ensure((size_t)B * P.cmax * 4));
   HIPCHK(ctx, S.s_scnt.ensure((size_t)(B + 2) * 4));  // [B] survivor counts, then nfail and the rescan queue head
   HIPCHK(ctx, S.s_fail.ensure((size_t)B * 4));
-  HIPCHK(ctx, S.s_part.ensure((size_t)fpart * 8));
-  HIPCHK(ctx, S.s_cnt.ensure((size_t)nlist * 4));
-  HIPCHK(ctx, S.s_fill.ensure((size_t)nlist * 4));
-  HIPCHK(ctx, S.s_eoff.ensure((size_t)(nlist + 1) * 4));
-  HIPCHK(ctx, S.s_ioff.ensure((size_t)(nlist + 1) * 4));
-  HIPCHK(ctx, S.s_entries.ensure((size_t)B * np * 8));
+  HIPCHK(ctx, S.s_part.ensure((size_t)P.fpart * 8));
+  int rc = plan_scratch(ivf, E, B, np);
+  if (rc) return rc;
   HIPCHK(ctx, S.s_scalars.ensure(kScalarsBytes));
-  uint32_t* scal = S.s_scalars.as<uint32_t>();
-  const uint32_t grid = (uint32_t)ctx->num_cus * (uint32_t)std::max(1, wgs_env);
-  const ListTable lists{ivf->t_off.as<uint32_t>(), ivf->t_blocks.as<uint32_t>(), nlist};
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[3], ctx->stream);
+  return FVDB_OK;
+}
 
-  hipLaunchKernelGGL(prep_queries_kernel, dim3(cdiv(B + 1, 4)), dim3(256), 0, ctx->stream, qpad, B, ivf->dpad,
-                     (_Float16*)S.s_qh.p, S.s_qn2.as<float>(), S.s_cnt.as<uint32_t>(), nlist,
+// fp16 queries (+ the zero row), |q|^2; clears cnt[], the survivor counts with nfail and the queue head, the row slots
+void launch_prep_queries(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B) {
+  IvfScratch& S = *E.S;
+  hipLaunchKernelGGL(prep_queries_kernel, dim3(cdiv(B + 1, 4)), dim3(256), 0, E.ctx->stream, qpad, B, ivf->dpad,
+                     (_Float16*)S.s_qh.p, S.s_qn2.as<float>(), S.s_cnt.as<uint32_t>(), ivf->nlist,
                      S.s_scnt.as<uint32_t>(), S.s_mslots.as<uint32_t>());
-  auto plan = [&](const uint32_t* pr, uint32_t n, uint32_t npp, uint32_t sb, unsigned long long* stats,
-                  uint32_t lsplit = 0xFFFFFFFFu, uint32_t sb_tail = 0) {
-    // cnt[] is zero on entry: cleared by prep_queries_kernel for the first plan, by plan_scan_kernel for the second
-    hipLaunchKernelGGL(plan_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, pr, n, S.s_cnt.as<uint32_t>(),
-                       lists.off);
-    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, S.s_cnt.as<uint32_t>(), lists.off,
-                       ivf->t_len.as<uint32_t>(), nlist, sb, Q, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(),
-                       S.s_fill.as<uint32_t>(), scal + 2, scal + 3, stats, S.s_cnt.as<uint32_t>(), lsplit, sb_tail);
-    hipLaunchKernelGGL(plan_fill_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, pr, n, npp,
-                       S.s_eoff.as<uint32_t>(), S.s_fill.as<uint32_t>(), S.s_entries.as<uint2>(), lists.off);
-  };
+}
+
+ThresholdArgs threshold_args(fvdb_ivf* ivf, const IvfScratch& S, const float* qpad, const uint32_t* probes, uint32_t B,
+                             uint32_t k, uint32_t np, float* thr_out) {
+  ThresholdArgs t{};
+  t.rows = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
+  t.pool_valid = ivf->pool.valid;
+  t.pool_norms = ivf->pool.norms;
+  t.d4 = ivf->d4;
+  t.lists = list_table(ivf);
+  t.list_len = ivf->t_len.as<uint32_t>();
+  t.probes = probes;
+  t.qh = (const _Float16*)S.s_qh.p;
+  t.queries = qpad;
+  t.qn = S.s_qn2.as<float>();
+  t.xmax_bits = ivf->d_xmax.as<uint32_t>();
+  t.B = B;
+  t.np = np;
+  t.ka = k + kMfmaSlack;
+  t.dpad = ivf->dpad;
+  t.capA = ivf_knobs().mfma_cap_a;
+  t.min_rows = 256u;
+  t.rows_f16 = x_rounded(ivf);
+  t.thr = thr_out;
+  return t;
+}
+void launch_threshold_direct(fvdb_ivf* ivf, fvdb_ctx* ctx, const ThresholdArgs& t) {
+  if (half_rows(ivf)) hipLaunchKernelGGL((threshold_direct_kernel<true>), dim3(cdiv(t.B, 4)), dim3(256), 0, ctx->stream, t);
+  else hipLaunchKernelGGL((threshold_direct_kernel<false>), dim3(cdiv(t.B, 4)), dim3(256), 0, ctx->stream, t);
+}
+
+MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, uint32_t B) {
+  const IvfScratch& S = *E.S;
   MfmaScanArgs a{};
-  const bool half_rows = ivf->f16 || ivf->pool.half != nullptr;  // the filter reads fp16 rows (stored or mirrored)
-  const int x_rounded = ivf->f16 ? 0 : (ivf->pool.half ? 1 : 2);  // vs the rows the reference sees: exact, RNE, RTZ
   a.pool_data = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
   a.pool_valid = ivf->pool.valid;
   a.pool_norms = ivf->pool.norms;
   a.d4 = ivf->d4;
-  a.list_off = lists.off;
-  a.list_blocks = lists.blocks;
-  a.nlist = nlist;
+  a.list_off = ivf->t_off.as<uint32_t>();
+  a.list_blocks = ivf->t_blocks.as<uint32_t>();
+  a.nlist = ivf->nlist;
   a.entry_off = S.s_eoff.as<uint32_t>();
   a.item_off = S.s_ioff.as<uint32_t>();
   a.entries = (const u32x2*)S.s_entries.p;
-  a.n_items = scal + 2;
-  a.head = scal + 3;
+  a.n_items = S.scalar(SC_FINE_ITEMS);
+  a.head = S.scalar(SC_FINE_HEAD);
   a.qh = (const _Float16*)S.s_qh.p;
   a.zero_row = B;
   a.dpad = ivf->dpad;
-  a.thr = S.s_thr.as<float>();
-  a.cmax = cmax;
+  a.segb = P.segb;
+  // sharded search: the thresholds were computed once per query by the rank owning the list and combined across the
+  // ranks before this call (ivf_shared_thresholds + the exchange in comm_sharded.h)
+  a.thr = E.given_thr ? E.given_thr : S.s_thr.as<float>();
+  a.cmax = P.cmax;
   a.surv = (u32x2*)S.s_surv.p;
   a.sval = S.s_sdist.as<float>();
   a.scnt = S.s_scnt.as<uint32_t>();
   a.slots = S.s_mslots.as<uint32_t>();
-  a.capA = (uint32_t)std::max(1, capA_env);
-  static const int gii_env = env_u("FVDB_MFMA_GROUPS_IN_ITEM", 0);  // tuning aid / A-B
-  a.groups_in_item = gii_env ? 1u : 0u;
+  a.capA = ivf_knobs().mfma_cap_a;
+  a.groups_in_item = ivf_knobs().mfma_groups_in_item ? 1u : 0u;
+  a.lsplit = P.lsplit;
+  a.segb_tail = P.segb_tail;
+  return a;
+}
 
-  // A. threshold: the smallest v per row slot over the head of a near, well-filled list -> (k+6)-th smallest -> thr.
-  //    Direct form: one wave per query, one launch (kernels_mfma.h).  FVDB_MFMA_THRESHOLD_PASS=1 keeps the earlier
-  //    form (first_probe + plan + matrix-core MODE 1 pass + threshold_kernel) for A/B runs.
-  static const bool thr_pass = getenv("FVDB_MFMA_THRESHOLD_PASS") != nullptr;
-  if (E.given_thr) {
-    // sharded search: the thresholds were computed once per query by the rank owning the list and combined across the
-    // ranks before this call (ivf_shared_thresholds + the exchange in comm_sharded.h)
-    a.thr = E.given_thr;
-  } else if (!thr_pass) {
-    ThresholdArgs t{};
-    t.rows = a.pool_data;
-    t.pool_valid = a.pool_valid;
-    t.pool_norms = a.pool_norms;
-    t.d4 = ivf->d4;
-    t.lists = lists;
-    t.list_len = ivf->t_len.as<uint32_t>();
-    t.probes = probes;
-    t.qh = (const _Float16*)S.s_qh.p;
-    t.queries = qpad;
-    t.qn = S.s_qn2.as<float>();
-    t.xmax_bits = ivf->d_xmax.as<uint32_t>();
-    t.B = B;
-    t.np = np;
-    t.ka = ka;
-    t.dpad = ivf->dpad;
-    t.capA = a.capA;
-    t.min_rows = 256u;
-    t.rows_f16 = x_rounded;
-    t.thr = S.s_thr.as<float>();
-    if (half_rows) hipLaunchKernelGGL((threshold_direct_kernel<true>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, t);
-    else hipLaunchKernelGGL((threshold_direct_kernel<false>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, t);
+// the wave form of the matrix-core scan: MODE 0 filters, MODE 1 collects the smallest v per row slot
+using MfmaKernel = decltype(&scan_mfma_kernel<2, 1, 0>);
+template <int M, int MODE>
+MfmaKernel mfma_kernel_of(bool f16) {
+  return f16 ? scan_mfma_kernel<M, 1, MODE> : scan_mfma_kernel<M, 0, MODE>;
+}
+template <int MODE>
+void launch_mfma(fvdb_ctx* ctx, const MfmaScanArgs& a, const MfmaPlan& P) {
+  const MfmaKernel kernel = P.M == 1   ? mfma_kernel_of<1, MODE>(P.half_rows)
+                            : P.M == 2 ? mfma_kernel_of<2, MODE>(P.half_rows)
+                                       : mfma_kernel_of<4, MODE>(P.half_rows);
+  hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(256), 0, ctx->stream, a);
+}
+
+// A. threshold: the smallest v per row slot over the head of a near, well-filled list -> (k+6)-th smallest -> thr.
+//    Direct form: one wave per query, one launch (kernels_mfma.h).  FVDB_MFMA_THRESHOLD_PASS=1 keeps the earlier
+//    form (first_probe + plan + matrix-core MODE 1 pass + threshold_kernel) for A/B runs.
+void mfma_threshold(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const MfmaScanArgs& a) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  if (E.given_thr) return;
+  if (!ivf_knobs().mfma_threshold_pass) {
+    launch_threshold_direct(ivf, ctx, threshold_args(ivf, S, b.qpad, b.probes, b.B, b.k, b.np, S.s_thr.as<float>()));
+    return;
+  }
+  hipLaunchKernelGGL(first_probe_kernel, dim3(cdiv(b.B, 256)), dim3(256), 0, ctx->stream, b.probes, b.B, b.np,
+                     ivf->t_len.as<uint32_t>(), 256u, S.s_pa.as<uint32_t>());
+  // cnt[] is zero on entry: cleared by prep_queries_kernel for this plan, by plan_scan_kernel for the filter's
+  launch_plan(ivf, E, S.s_pa.as<uint32_t>(), b.B, 1, P.segbA, P.Q, nullptr, S.s_cnt.as<uint32_t>());
+  MfmaScanArgs head = a;
+  head.segb = P.segbA;
+  launch_mfma<1>(ctx, head, P);
+  hipLaunchKernelGGL(threshold_kernel, dim3(cdiv(b.B, 4)), dim3(256), 0, ctx->stream, S.s_mslots.as<uint32_t>(),
+                     S.s_pa.as<uint32_t>(), S.s_qn2.as<float>(), ivf->d_xmax.as<uint32_t>(), b.B, P.ka, ivf->dpad,
+                     P.x_rounded, S.s_thr.as<float>());
+}
+
+// the filter over the planned items, in the form the plan chose
+void launch_filter(fvdb_ctx* ctx, const MfmaScanArgs& a, const MfmaPlan& P) {
+  if (P.wg) {
+    const MfmaKernel kernel = P.M == 4 ? scan_mfma_wg_kernel<4> : scan_mfma_wg_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3(P.wg_grid), dim3(256), P.wg_lds, ctx->stream, a);
   } else {
-    hipLaunchKernelGGL(first_probe_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, probes, B, np,
-                       ivf->t_len.as<uint32_t>(), 256u, S.s_pa.as<uint32_t>());
-    plan(S.s_pa.as<uint32_t>(), B, 1, segbA, nullptr);
-    a.segb = segbA;
-    launch_mfma<1>(ctx, a, M, half_rows, grid);
-    hipLaunchKernelGGL(threshold_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, S.s_mslots.as<uint32_t>(),
-                       S.s_pa.as<uint32_t>(), S.s_qn2.as<float>(), ivf->d_xmax.as<uint32_t>(), B, ka, ivf->dpad,
-                       x_rounded, S.s_thr.as<float>());
+    launch_mfma<0>(ctx, a, P);
   }
+}
 
-  // B. filter over all probed lists
-  // workgroup form: the last quarter of the lists in small segments (see MfmaScanArgs::lsplit)
-  static const int wg_tail_pct = env_u("FVDB_MFMA_WG_TAIL_PCT", 25), wg_tail_segb = env_u("FVDB_MFMA_WG_SEGB_TAIL", 4);
-  a.lsplit = 0xFFFFFFFFu;
-  a.segb_tail = segb;
-  if (use_wg && wg_tail_pct > 0 && wg_tail_segb > 0 && (uint32_t)wg_tail_segb < segb) {
-    a.lsplit = (uint32_t)((uint64_t)nlist * (uint32_t)(100 - std::min(wg_tail_pct, 100)) / 100);
-    a.segb_tail = (uint32_t)wg_tail_segb;
-  }
-  plan(probes, B * np, np, segb, (unsigned long long*)(scal + 4), a.lsplit, a.segb_tail);
-  a.segb = segb;
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[6], ctx->stream);
-  static const int stamps_env = env_u("FVDB_MFMA_STAMPS", 0);  // dev aid: per-item timeline of the workgroup filter
-  static void* stamps_buf = nullptr;
-  static int stamps_launch = 0;
-  constexpr uint32_t kStampsCap = 32768;
-  const bool stamp_now = use_wg && stamps_env && ++stamps_launch >= stamps_env && stamps_launch < stamps_env + 3;
-  if (stamp_now) {
-    if (!stamps_buf) HIPCHK(ctx, hipMalloc(&stamps_buf, (size_t)kStampsCap * 64));
-    HIPCHK(ctx, hipMemsetAsync(stamps_buf, 0, (size_t)kStampsCap * 64, ctx->stream));
-    a.stamps = (unsigned long long*)stamps_buf;
-    a.stamps_cap = kStampsCap;
-  }
-  if (use_wg) {
-    const dim3 wg_grid((uint32_t)ctx->num_cus * (uint32_t)std::max(1, wg_wgs_env));
-    if (M == 4)
-      hipLaunchKernelGGL(scan_mfma_wg_kernel<4>, wg_grid, dim3(256), mfma_wg_lds_bytes(ivf->dpad, 64), ctx->stream, a);
-    else
-      hipLaunchKernelGGL(scan_mfma_wg_kernel<2>, wg_grid, dim3(256), mfma_wg_lds_bytes(ivf->dpad, 32), ctx->stream, a);
-  } else
-    launch_mfma<0>(ctx, a, M, half_rows, grid);
-  if (stamp_now) {
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<unsigned long long> h((size_t)kStampsCap * 8);
-    HIPCHK(ctx, hipMemcpy(h.data(), stamps_buf, h.size() * 8, hipMemcpyDeviceToHost));
-    unsigned long long t_min = ~0ull, t_max = 0;
-    size_t n = 0;
-    for (size_t i = 0; i < kStampsCap; ++i)
-      if (h[i * 8 + 3]) {
-        t_min = std::min(t_min, h[i * 8]);
-        t_max = std::max(t_max, h[i * 8 + 3]);
-        ++n;
-      }
-    double s_loc = 0, s_tile = 0, s_comp = 0, s_steps = 0, s_blocks = 0;
-    size_t per_xcd[16] = {0};
-    std::vector<double> per_step;
-    for (size_t i = 0; i < kStampsCap; ++i) {
-      const unsigned long long* r = &h[i * 8];
-      if (!r[3]) continue;
-      const double steps = (double)((r[5] + 3) / 4) * (double)(ivf->dpad / 16);
-      s_loc += (double)(r[1] - r[0]);
-      s_tile += (double)(r[2] - r[1]);
-      s_comp += (double)(r[3] - r[2]);
-      s_steps += steps;
-      s_blocks += (double)r[5];
-      per_xcd[r[7] & 15]++;
-      per_step.push_back((double)(r[3] - r[2]) / steps);
+#ifdef FVDB_MFMA_STAMPS_BUILD
+// diagnostic build (FVDB_MFMA_STAMPS=<first launch to print>): per-item timeline of the workgroup filter, written by
+// the kernel into a buffer the index owns, read back and summarised on stderr for three launches
+constexpr uint32_t kStampsCap = 32768;
+int mfma_stamps_begin(fvdb_ivf* ivf, fvdb_ctx* ctx, const MfmaPlan& P, MfmaScanArgs* a) {
+  const int stamps_env = ivf_knobs().mfma_stamps;
+  const bool stamp_now = P.wg && stamps_env && ++ivf->mfma_stamps_launch >= stamps_env && ivf->mfma_stamps_launch < stamps_env + 3;
+  if (!stamp_now) return FVDB_OK;
+  HIPCHK(ctx, ivf->d_mfma_stamps.ensure((size_t)kStampsCap * 64));
+  HIPCHK(ctx, hipMemsetAsync(ivf->d_mfma_stamps.p, 0, (size_t)kStampsCap * 64, ctx->stream));
+  a->stamps = ivf->d_mfma_stamps.as<unsigned long long>();
+  a->stamps_cap = kStampsCap;
+  return FVDB_OK;
+}
+int mfma_stamps_report(fvdb_ivf* ivf, fvdb_ctx* ctx, MfmaScanArgs* a) {
+  if (!a->stamps) return FVDB_OK;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<unsigned long long> h((size_t)kStampsCap * 8);
+  HIPCHK(ctx, hipMemcpy(h.data(), a->stamps, h.size() * 8, hipMemcpyDeviceToHost));
+  unsigned long long t_min = ~0ull, t_max = 0;
+  size_t n = 0;
+  for (size_t i = 0; i < kStampsCap; ++i)
+    if (h[i * 8 + 3]) {
+      t_min = std::min(t_min, h[i * 8]);
+      t_max = std::max(t_max, h[i * 8 + 3]);
+      ++n;
     }
-    std::sort(per_step.begin(), per_step.end());
-    const double tick = 0.01;  // us per tick of the 100 MHz wall clock
-    fprintf(stderr,
-            "[mfma stamps] launch %d: %zu items, %0.f blocks, span %.1f us | per item (wave 0): locate %.2f us, tile %.2f us, "
-            "compute %.2f us | per 16-dim step: mean %.3f us, p10 %.3f, p50 %.3f, p90 %.3f | items per XCD",
-            stamps_launch, n, s_blocks, (double)(t_max - t_min) * tick, s_loc / n * tick, s_tile / n * tick, s_comp / n * tick,
-            s_comp / s_steps * tick, per_step.empty() ? 0.0 : per_step[per_step.size() / 10] * tick,
-            per_step.empty() ? 0.0 : per_step[per_step.size() / 2] * tick,
-            per_step.empty() ? 0.0 : per_step[per_step.size() * 9 / 10] * tick);
-    for (int x = 0; x < 8; ++x) fprintf(stderr, " %zu", per_xcd[x]);
-    // when did the last item START, and how long were the items that finished last
-    unsigned long long last_start = 0;
-    for (size_t i = 0; i < kStampsCap; ++i)
-      if (h[i * 8 + 3]) last_start = std::max(last_start, h[i * 8]);
-    fprintf(stderr, " | last item drawn at %.1f us\n", (double)(last_start - t_min) * tick);
-    a.stamps = nullptr;
+  double s_loc = 0, s_tile = 0, s_comp = 0, s_steps = 0, s_blocks = 0;
+  size_t per_xcd[16] = {0};
+  std::vector<double> per_step;
+  for (size_t i = 0; i < kStampsCap; ++i) {
+    const unsigned long long* r = &h[i * 8];
+    if (!r[3]) continue;
+    const double steps = (double)((r[5] + 3) / 4) * (double)(ivf->dpad / 16);
+    s_loc += (double)(r[1] - r[0]);
+    s_tile += (double)(r[2] - r[1]);
+    s_comp += (double)(r[3] - r[2]);
+    s_steps += steps;
+    s_blocks += (double)r[5];
+    per_xcd[r[7] & 15]++;
+    per_step.push_back((double)(r[3] - r[2]) / steps);
   }
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[7], ctx->stream);
-  // B'. queries whose survivors outgrew the buffer get a threshold from those survivors and a second filter pass over
-  //     their probes alone (normally nobody: the three plan kernels and the filter find nothing to do)
-  static const bool no_refine = getenv("FVDB_MFMA_NO_REFINE") != nullptr;  // tuning aid / A-B
-  bool refine = !E.given_thr && !no_refine;
-  if (refine && ivf->scan_mode == FVDB_SCAN_AUTO) {
-    std::lock_guard<std::mutex> lk(ivf->mu);
-    if (ivf->h_fb.p && ivf->mfma_q - ivf->overflow_q >= 2048) {
-      // worth five more launches per batch once more than one query in a thousand overflows (a stray one is cheaper to
-      // rescan exactly); looked at every 2048 queries, the counters lag by the batches in flight
-      const volatile uint32_t* c = (const volatile uint32_t*)ivf->h_fb.p;
-      const uint64_t now = (uint64_t)c[2] + c[6], dq = ivf->mfma_q - ivf->overflow_q;
-      if ((now - ivf->overflow_seen) * 1000 > dq) ivf->refine_batches_left = 1024;
-      ivf->overflow_seen = now;
-      ivf->overflow_q = ivf->mfma_q;
-    }
-    if (ivf->refine_batches_left > 0) ivf->refine_batches_left -= 1;
-    else refine = false;
-  }
-  if (refine) {
-    HIPCHK(ctx, S.s_probes2.ensure((size_t)B * np * 4));
-    hipLaunchKernelGGL(refine_threshold_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, S.s_sdist.as<float>(),
-                       S.s_scnt.as<uint32_t>(), probes, S.s_qn2.as<float>(), ivf->d_xmax.as<uint32_t>(), B, np, ka, cmax, ivf->dpad,
-                       x_rounded, S.s_thr.as<float>(), S.s_probes2.as<uint32_t>(), ivf->s_fallbacks.as<uint32_t>() + 6);
-    plan(S.s_probes2.as<uint32_t>(), B * np, np, segb, nullptr, a.lsplit, a.segb_tail);
-    if (use_wg) {
-      const dim3 wg_grid((uint32_t)ctx->num_cus * (uint32_t)std::max(1, wg_wgs_env));
-      if (M == 4)
-        hipLaunchKernelGGL(scan_mfma_wg_kernel<4>, wg_grid, dim3(256), mfma_wg_lds_bytes(ivf->dpad, 64), ctx->stream, a);
-      else
-        hipLaunchKernelGGL(scan_mfma_wg_kernel<2>, wg_grid, dim3(256), mfma_wg_lds_bytes(ivf->dpad, 32), ctx->stream, a);
-    } else {
-      launch_mfma<0>(ctx, a, M, half_rows, grid);
-    }
-  }
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[4], ctx->stream);
-  S.pend_filter = true;
+  std::sort(per_step.begin(), per_step.end());
+  const double tick = 0.01;  // us per tick of the 100 MHz wall clock
+  fprintf(stderr,
+          "[mfma stamps] launch %d: %zu items, %0.f blocks, span %.1f us | per item (wave 0): locate %.2f us, tile %.2f us, "
+          "compute %.2f us | per 16-dim step: mean %.3f us, p10 %.3f, p50 %.3f, p90 %.3f | items per XCD",
+          ivf->mfma_stamps_launch, n, s_blocks, (double)(t_max - t_min) * tick, s_loc / n * tick, s_tile / n * tick, s_comp / n * tick,
+          s_comp / s_steps * tick, per_step.empty() ? 0.0 : per_step[per_step.size() / 10] * tick,
+          per_step.empty() ? 0.0 : per_step[per_step.size() / 2] * tick,
+          per_step.empty() ? 0.0 : per_step[per_step.size() * 9 / 10] * tick);
+  for (int x = 0; x < 8; ++x) fprintf(stderr, " %zu", per_xcd[x]);
+  // when did the last item START, and how long were the items that finished last
+  unsigned long long last_start = 0;
+  for (size_t i = 0; i < kStampsCap; ++i)
+    if (h[i * 8 + 3]) last_start = std::max(last_start, h[i * 8]);
+  fprintf(stderr, " | last item drawn at %.1f us\n", (double)(last_start - t_min) * tick);
+  a->stamps = nullptr;  // the refine pass is not stamped
+  return FVDB_OK;
+}
+#else
+inline int mfma_stamps_begin(fvdb_ivf*, fvdb_ctx*, const MfmaPlan&, MfmaScanArgs*) { return FVDB_OK; }
+inline int mfma_stamps_report(fvdb_ivf*, fvdb_ctx*, MfmaScanArgs*) { return FVDB_OK; }
+#endif
 
-  // C. select
+// B. filter over all probed lists
+int mfma_filter(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, MfmaScanArgs* a) {
+  fvdb_ctx* ctx = E.ctx;
+  launch_plan(ivf, E, b.probes, b.B * b.np, b.np, P.segb, P.Q, scan_stats(*E.S), E.S->s_cnt.as<uint32_t>(), P.lsplit,
+              P.segb_tail);
+  mark(ivf, E, EV_FILTER_BEGIN);
+  int rc = mfma_stamps_begin(ivf, ctx, P, a);
+  if (rc) return rc;
+  launch_filter(ctx, *a, P);
+  rc = mfma_stamps_report(ivf, ctx, a);
+  if (rc) return rc;
+  mark(ivf, E, EV_FILTER_DONE);
+  return FVDB_OK;
+}
+
+// AUTO scan mode steers itself by two counters of the pinned copy of the counter block, each looked at every 2048
+// matrix-core queries under ivf->mu (the watch is shared by every search on the index; the counters lag by the batches
+// in flight).  First watch: does this batch go to the exact scan instead?
+bool auto_backs_off(fvdb_ivf* ivf) {
+  std::lock_guard<std::mutex> lk(ivf->mu);
+  if (ivf->exact_batches_left > 0) {
+    ivf->exact_batches_left -= 1;
+    return true;
+  }
+  if (!(ivf->h_fb.p && ivf->mfma_q - ivf->q_seen >= 2048)) return false;
+  // rescans among the matrix-core queries since the last look
+  const uint64_t fb_now = ((volatile uint32_t*)ivf->h_fb.p)[FB_SCAN];
+  const uint64_t dq = ivf->mfma_q - ivf->q_seen, dfb = fb_now - ivf->fb_seen;
+  ivf->q_seen = ivf->mfma_q;
+  ivf->fb_seen = fb_now;
+  if (dfb * 8 > dq) {  // more than 1 in 8: the exact scan is cheaper here; look again after a while, ever more rarely
+    ivf->backoff_len = std::min<uint32_t>(ivf->backoff_len ? ivf->backoff_len * 2 : 64, 4096);
+    ivf->exact_batches_left = ivf->backoff_len;
+    return true;
+  }
+  ivf->backoff_len = 0;
+  return false;
+}
+// Second watch: does this batch get the refine pass?
+bool auto_refines(fvdb_ivf* ivf) {
+  std::lock_guard<std::mutex> lk(ivf->mu);
+  if (ivf->h_fb.p && ivf->mfma_q - ivf->overflow_q >= 2048) {
+    // worth five more launches per batch once more than one query in a thousand overflows (a stray one is cheaper to
+    // rescan exactly)
+    const volatile uint32_t* c = (const volatile uint32_t*)ivf->h_fb.p;
+    const uint64_t now = (uint64_t)c[FB_OVERFLOW] + c[FB_REFINED], dq = ivf->mfma_q - ivf->overflow_q;
+    if ((now - ivf->overflow_seen) * 1000 > dq) ivf->refine_batches_left = 1024;
+    ivf->overflow_seen = now;
+    ivf->overflow_q = ivf->mfma_q;
+  }
+  if (ivf->refine_batches_left == 0) return false;
+  ivf->refine_batches_left -= 1;
+  return true;
+}
+
+// B'. queries whose survivors outgrew the buffer get a threshold from those survivors and a second filter pass over
+//     their probes alone (normally nobody: the three plan kernels and the filter find nothing to do)
+int mfma_refine(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const MfmaScanArgs& a) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  HIPCHK(ctx, S.s_probes2.ensure((size_t)b.B * b.np * 4));
+  hipLaunchKernelGGL(refine_threshold_kernel, dim3(cdiv(b.B, 4)), dim3(256), 0, ctx->stream, S.s_sdist.as<float>(),
+                     S.s_scnt.as<uint32_t>(), b.probes, S.s_qn2.as<float>(), ivf->d_xmax.as<uint32_t>(), b.B, b.np, P.ka, P.cmax,
+                     ivf->dpad, P.x_rounded, S.s_thr.as<float>(), S.s_probes2.as<uint32_t>(), ivf->fb_word(FB_REFINED));
+  launch_plan(ivf, E, S.s_probes2.as<uint32_t>(), b.B * b.np, b.np, P.segb, P.Q, nullptr, S.s_cnt.as<uint32_t>(), P.lsplit,
+              P.segb_tail);
+  launch_filter(ctx, a, P);
+  return FVDB_OK;
+}
+
+// C. select
+VerifyArgs verify_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b) {
+  const IvfScratch& S = *E.S;
   VerifyArgs v{};
   v.pool = ivf->pool.view();
-  v.lists = lists;
-  v.probes = probes;
+  v.lists = list_table(ivf);
+  v.probes = b.probes;
   v.glob_blocks = ivf->t_glob.as<uint32_t>();
-  v.queries = qpad;
+  v.queries = b.qpad;
   v.qn = S.s_qn2.as<float>();
   v.xmax_bits = ivf->d_xmax.as<uint32_t>();
   v.thr = E.given_thr ? E.given_thr : S.s_thr.as<float>();
@@ -742,63 +933,63 @@ int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, ui
   v.surv = (const u32x2*)S.s_surv.p;
   v.sval = S.s_sdist.as<float>();
   v.scnt = S.s_scnt.as<uint32_t>();
-  v.B = B;
-  v.k = k;
-  v.ka = ka;
-  v.nprobe = np;
+  v.B = b.B;
+  v.k = b.k;
+  v.ka = P.ka;
+  v.nprobe = b.np;
   v.d = ivf->dpad;
   v.dpad = ivf->dpad;
-  v.cmax = cmax;
-  v.rows_f16 = x_rounded;
+  v.cmax = P.cmax;
+  v.rows_f16 = P.x_rounded;
   v.rows_rm = ivf->pool.rm;
-  v.out_ids = out_ids;
-  v.out_dist = out_dist;
-  v.out_counts = out_counts;
-  v.out_keys = out_keys;
-  v.fallbacks = ivf->s_fallbacks.as<uint32_t>() + 1;
-  v.reasons = ivf->s_fallbacks.as<uint32_t>() + 2;
+  v.out_ids = b.out_ids;
+  v.out_dist = b.out_dist;
+  v.out_counts = b.out_counts;
+  v.out_keys = b.out_keys;
+  v.fallbacks = ivf->fb_word(FB_SCAN);
+  v.reasons = ivf->fb_word(FB_REASONS);
   v.fail_list = S.s_fail.as<uint32_t>();
-  v.nfail = S.s_scnt.as<uint32_t>() + B;
-  if (ivf->f16) hipLaunchKernelGGL((select_kernel<1>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, v);
-  else hipLaunchKernelGGL((select_kernel<0>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, v);
+  v.nfail = S.s_scnt.as<uint32_t>() + b.B;
+  return v;
+}
+void launch_select(fvdb_ivf* ivf, fvdb_ctx* ctx, const VerifyArgs& v) {
+  if (ivf->f16) hipLaunchKernelGGL((select_kernel<1>), dim3(cdiv(v.B, 4)), dim3(256), 0, ctx->stream, v);
+  else hipLaunchKernelGGL((select_kernel<0>), dim3(cdiv(v.B, 4)), dim3(256), 0, ctx->stream, v);
+}
 
-  // exact rescan of the queries that were not proven (normally none: both kernels return at once)
+FallbackArgs fallback_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const VerifyArgs& v) {
+  const IvfScratch& S = *E.S;
   FallbackArgs fa{};
   fa.pool = ivf->pool.view();
-  fa.lists = lists;
-  fa.probes = probes;
-  fa.queries = qpad;
+  fa.lists = v.lists;
+  fa.probes = b.probes;
+  fa.queries = b.qpad;
   fa.fail_list = v.fail_list;
   fa.nfail = v.nfail;
-  fa.head = S.s_scnt.as<uint32_t>() + B + 1;
-  fa.k = k;
-  fa.nprobe = np;
+  fa.head = S.s_scnt.as<uint32_t>() + b.B + 1;
+  fa.k = b.k;
+  fa.nprobe = b.np;
   fa.dpad = ivf->dpad;
-  fa.segb = fsegb;
-  fa.maxsegs = fmaxsegs;
+  fa.segb = P.fsegb;
+  fa.maxsegs = P.fmaxsegs;
   fa.part = (u32x2*)S.s_part.p;
-  if (ivf->f16) hipLaunchKernelGGL((fallback_scan_kernel<1>), dim3(grid), dim3(256), 0, ctx->stream, fa);
-  else hipLaunchKernelGGL((fallback_scan_kernel<0>), dim3(grid), dim3(256), 0, ctx->stream, fa);
-  MergeArgs fm{};
-  fm.pool = ivf->pool.view();
-  fm.lists = lists;
-  fm.probes = probes;
-  fm.glob_blocks = ivf->t_glob.as<uint32_t>();
-  fm.part = S.s_part.as<uint2>();
-  fm.B = B;
-  fm.k = k;
-  fm.nprobe = np;
-  fm.maxsegs = fmaxsegs;
-  fm.segb = fsegb;
-  fm.out_ids = out_ids;
-  fm.out_dist = out_dist;
-  fm.out_counts = out_counts;
-  fm.out_keys = out_keys;
+  return fa;
+}
+
+// exact rescan of the queries the select stage did not prove (normally none: both kernels return at once)
+void mfma_rescan(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const VerifyArgs& v) {
+  fvdb_ctx* ctx = E.ctx;
+  const FallbackArgs fa = fallback_args(ivf, E, P, b, v);
+  if (ivf->f16) hipLaunchKernelGGL((fallback_scan_kernel<1>), dim3(P.grid), dim3(256), 0, ctx->stream, fa);
+  else hipLaunchKernelGGL((fallback_scan_kernel<0>), dim3(P.grid), dim3(256), 0, ctx->stream, fa);
+  MergeArgs fm = merge_args(fa.pool, fa.lists, v.glob_blocks, E.S->s_part, P.fmaxsegs, P.fsegb, b);
   fm.qlist = v.fail_list;
   fm.nq = v.nfail;
   launch_merge(ctx, fm);
-  if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[5], ctx->stream);
-  // the rescan counter, for AUTO's hit-rate watch (run_fine): a 4-byte copy into pinned memory, nobody waits for it
+}
+
+// the counter block, for AUTO's watches: a 32-byte copy into pinned memory, nobody waits for it
+int mfma_watch_counters(fvdb_ivf* ivf, fvdb_ctx* ctx, uint32_t B) {
   {
     std::lock_guard<std::mutex> lk(ivf->mu);
     const bool fresh = ivf->h_fb.p == nullptr;
@@ -806,41 +997,62 @@ int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, ui
     if (fresh) std::memset(ivf->h_fb.p, 0, 64);
     ivf->mfma_q += B;
   }
-  HIPCHK(ctx, hipMemcpyAsync(ivf->h_fb.p, ivf->s_fallbacks.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ivf->h_fb.p, ivf->s_fallbacks.p, kFbBytes, hipMemcpyDeviceToHost, ctx->stream));
+  return FVDB_OK;
+}
+
+int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const Batch& b) {
+  fvdb_ctx* ctx = E.ctx;
+  const IvfKnobs& kn = ivf_knobs();
+  MfmaPlan P;
+  int rc = mfma_plan(ivf, ctx, kn, b.B, b.k, b.np, &P);
+  if (rc) return rc;
+  rc = mfma_scratch(ivf, E, P, b.B, b.np);
+  if (rc) return rc;
+  mark(ivf, E, EV_SCAN_BEGIN);
+  launch_prep_queries(ivf, E, b.qpad, b.B);
+  MfmaScanArgs a = mfma_scan_args(ivf, E, P, b.B);
+  mfma_threshold(ivf, E, P, b, a);
+  rc = mfma_filter(ivf, E, P, b, &a);
+  if (rc) return rc;
+  // thresholds agreed between the ranks are not refined; AUTO refines only while it has seen the need
+  if (!E.given_thr && !kn.mfma_no_refine && (ivf->scan_mode != FVDB_SCAN_AUTO || auto_refines(ivf))) {
+    rc = mfma_refine(ivf, E, P, b, a);
+    if (rc) return rc;
+  }
+  mark(ivf, E, EV_SCAN_DONE);
+  E.S->pend_filter = true;
+  const VerifyArgs v = verify_args(ivf, E, P, b);
+  launch_select(ivf, ctx, v);
+  mfma_rescan(ivf, E, P, b, v);
+  mark(ivf, E, EV_FINE_DONE);
+  rc = mfma_watch_counters(ivf, ctx, b.B);
+  if (rc) return rc;
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
 
 int run_fine(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t k, uint32_t np, const uint32_t* probes,
              uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys, int role) {
-  IvfScratch& S = *E.S;
-  static const bool env_exact = getenv("FVDB_SCAN_EXACT") != nullptr;  // tuning aid
-  S.pend_filter = false;
-  bool mfma = (ivf->scan_mode == FVDB_SCAN_AUTO || ivf->scan_mode == FVDB_SCAN_FILTER) && !env_exact && role == ROLE_LIST && ivf->dpad % 16 == 0 &&
-              k + kMfmaSlack <= 32 && np <= 256 && B >= 32 && B <= 16384 && ivf->pool.norms != nullptr;
-  if (mfma && ivf->scan_mode == FVDB_SCAN_AUTO) {
-    std::lock_guard<std::mutex> lk(ivf->mu);  // the hit-rate watch is shared by every search on the index
-    if (ivf->exact_batches_left > 0) {
-      ivf->exact_batches_left -= 1;
-      mfma = false;
-    } else if (ivf->h_fb.p && ivf->mfma_q - ivf->q_seen >= 2048) {
-      // rescans among the matrix-core queries since the last look (the counter lags by the batches in flight)
-      const uint64_t fb_now = ((volatile uint32_t*)ivf->h_fb.p)[1];
-      const uint64_t dq = ivf->mfma_q - ivf->q_seen, dfb = fb_now - ivf->fb_seen;
-      ivf->q_seen = ivf->mfma_q;
-      ivf->fb_seen = fb_now;
-      if (dfb * 8 > dq) {  // more than 1 in 8: the exact scan is cheaper here; look again after a while, ever more rarely
-        ivf->backoff_len = std::min<uint32_t>(ivf->backoff_len ? ivf->backoff_len * 2 : 64, 4096);
-        ivf->exact_batches_left = ivf->backoff_len;
-        mfma = false;
-      } else {
-        ivf->backoff_len = 0;
-      }
-    }
-  }
-  if (mfma) return run_fine_mfma(ivf, E, qpad, B, k, np, probes, out_ids, out_dist, out_counts, out_keys);
-  return run_fine_exact(ivf, E, qpad, B, k, np, probes, out_ids, out_dist, out_counts, out_keys, role);
+  const Batch b{qpad, probes, B, k, np, out_ids, out_dist, out_counts, out_keys};
+  E.S->pend_filter = false;
+  // beyond the shape: this index's own state (norms, lists rather than the one flat list), which thr_share_ok must not ask
+  bool mfma = (ivf->scan_mode == FVDB_SCAN_AUTO || ivf->scan_mode == FVDB_SCAN_FILTER) && !ivf_knobs().scan_exact &&
+              mfma_shape_ok(ivf, B, k, np) && role == ROLE_LIST && ivf->pool.norms != nullptr;
+  if (mfma && ivf->scan_mode == FVDB_SCAN_AUTO && auto_backs_off(ivf)) mfma = false;
+  if (mfma) return run_fine_mfma(ivf, E, b);
+  return run_fine_exact(ivf, E, b, role);
 }
+
+// stage_ms[i]: the time between two stage events
+struct StageSpan {
+  StageEvent from, to;
+};
+constexpr StageSpan kStageSpan[6] = {
+    {EV_COARSE_BEGIN, EV_COARSE_SCANNED}, {EV_COARSE_SCANNED, EV_COARSE_DONE},  // coarse scan, coarse merge
+    {EV_COARSE_DONE, EV_SCAN_BEGIN},                                            // plan
+    {EV_SCAN_BEGIN, EV_SCAN_DONE},        {EV_SCAN_DONE, EV_FINE_DONE},         // fine scan, fine merge
+    {EV_FILTER_BEGIN, EV_FILTER_DONE}};                                         // the filter kernel alone
 
 int finish_profile(fvdb_ivf* ivf, const Env& E, bool coarse, bool fine) {
   fvdb_ctx* ctx = E.ctx;
@@ -854,25 +1066,19 @@ int finish_profile(fvdb_ivf* ivf, const Env& E, bool coarse, bool fine) {
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   float ms = 0;
+  auto add = [&](int stage) {
+    (void)hipEventElapsedTime(&ms, S.sev[kStageSpan[stage].from], S.sev[kStageSpan[stage].to]);
+    ivf->stage_ms[stage] += ms;
+  };
   if (coarse) {
-    (void)hipEventElapsedTime(&ms, S.sev[0], S.sev[1]);
-    ivf->stage_ms[0] += ms;
-    (void)hipEventElapsedTime(&ms, S.sev[1], S.sev[2]);
-    ivf->stage_ms[1] += ms;
+    add(0);
+    add(1);
   }
   if (fine) {
-    if (coarse) {
-      (void)hipEventElapsedTime(&ms, S.sev[2], S.sev[3]);
-      ivf->stage_ms[2] += ms;
-    }
-    (void)hipEventElapsedTime(&ms, S.sev[3], S.sev[4]);
-    ivf->stage_ms[3] += ms;
-    (void)hipEventElapsedTime(&ms, S.sev[4], S.sev[5]);
-    ivf->stage_ms[4] += ms;
-    if (S.pend_filter) {
-      (void)hipEventElapsedTime(&ms, S.sev[6], S.sev[7]);
-      ivf->stage_ms[5] += ms;
-    }
+    if (coarse) add(2);
+    add(3);
+    add(4);
+    if (S.pend_filter) add(5);
   }
   ivf->stage_calls += 1;
   return FVDB_OK;
@@ -880,9 +1086,7 @@ int finish_profile(fvdb_ivf* ivf, const Env& E, bool coarse, bool fine) {
 
 // largest sub-batch whose fine-stage partial buffer stays under ~1 GiB
 uint32_t sub_batch(fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
-  const uint32_t segb = pick_segb(ivf, B, np);
-  const uint64_t per_q = (uint64_t)np * std::max<uint32_t>(1, cdiv(ivf->max_list_blocks, segb)) * k * 8;
-  uint64_t fit = (1ull << 30) / std::max<uint64_t>(per_q, 1);
+  uint64_t fit = queries_per_gib(ivf->max_list_blocks, pick_segb(ivf, B, np), k, np);
   fit = std::max<uint64_t>(fit, 1);
   fit = std::min<uint64_t>(fit, 16384);
   return (uint32_t)std::min<uint64_t>(fit, B);
@@ -891,21 +1095,20 @@ uint32_t sub_batch(fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
 // ---- sharded search: filter thresholds computed once per query across the ranks (comm_sharded.h) ----
 // Whether a sharded step of B scanned queries uses the shared thresholds.  Every rank must answer alike (the answer
 // decides whether a collective is issued), so only quantities that are the same on every rank enter: shapes, and the
-// LOGICAL index's longest list.
+// LOGICAL index's longest list.  Unlike run_fine it therefore does not ask whether this rank has rows (pool.norms).
 bool thr_share_ok(fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
-  static const bool env_exact = getenv("FVDB_SCAN_EXACT") != nullptr, env_off = getenv("FVDB_NO_SHARED_THR") != nullptr;
-  if (env_exact || env_off || ivf->scan_mode != 0) return false;
-  if (!(ivf->dpad % 16 == 0 && k + kMfmaSlack <= 32 && np <= 256 && B >= 32 && B <= 16384)) return false;
+  const IvfKnobs& kn = ivf_knobs();
+  if (kn.scan_exact || kn.no_shared_thr || ivf->scan_mode != FVDB_SCAN_AUTO) return false;
+  if (!mfma_shape_ok(ivf, B, k, np)) return false;
   uint32_t gmax = 0;
   if (ivf->glob_set) {
     for (uint32_t b : ivf->glob_blocks_host) gmax = std::max(gmax, b);
   } else {
     gmax = ivf->max_list_blocks;
   }
-  // one sub-batch on every rank (sub_batch() with the logical index's longest list: local lists are no longer)
-  const uint32_t segb = gmax >= 4096 ? 16 : ((uint64_t)B * np >= 4096 ? 4 : ((uint64_t)B * np >= 512 ? 2 : 1));
-  const uint64_t per_q = (uint64_t)np * std::max<uint32_t>(1, cdiv(gmax, segb)) * k * 8;
-  return (1ull << 30) / std::max<uint64_t>(per_q, 1) >= B;
+  // one sub-batch on every rank: sub_batch() with the logical index's longest list (local lists are no longer) and
+  // with segb_for rather than pick_segb, that is, without a forced FVDB_SEGB
+  return queries_per_gib(gmax, segb_for(gmax, B, np), k, np) >= B;
 }
 
 // U_q (kernels_mfma.h, ThresholdArgs::glob_blocks) for the B queries of a sharded step, +inf where this rank does
@@ -932,34 +1135,10 @@ int ivf_shared_thresholds(fvdb_ivf* ivf, const Env& E, const float* q_dev, const
   HIPCHK(ctx, S.s_cnt.ensure((size_t)ivf->nlist * 4));
   HIPCHK(ctx, S.s_scnt.ensure((size_t)(B + 2) * 4));
   HIPCHK(ctx, S.s_mslots.ensure((size_t)B * 64 * 4));
-  hipLaunchKernelGGL(prep_queries_kernel, dim3(cdiv(B + 1, 4)), dim3(256), 0, ctx->stream, qpad, B, ivf->dpad,
-                     (_Float16*)S.s_qh.p, S.s_qn2.as<float>(), S.s_cnt.as<uint32_t>(), ivf->nlist,
-                     S.s_scnt.as<uint32_t>(), S.s_mslots.as<uint32_t>());
-  static const int capA_env = env_u("FVDB_MFMA_CAP_A", 4);
-  const bool half_rows = ivf->f16 || ivf->pool.half != nullptr;
-  ThresholdArgs t{};
-  t.rows = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
-  t.pool_valid = ivf->pool.valid;
-  t.pool_norms = ivf->pool.norms;
-  t.d4 = ivf->d4;
-  t.lists = ListTable{ivf->t_off.as<uint32_t>(), ivf->t_blocks.as<uint32_t>(), ivf->nlist};
-  t.list_len = ivf->t_len.as<uint32_t>();
-  t.probes = probes;
-  t.qh = (const _Float16*)S.s_qh.p;
-  t.queries = qpad;
-  t.qn = S.s_qn2.as<float>();
-  t.xmax_bits = ivf->d_xmax.as<uint32_t>();
-  t.B = B;
-  t.np = np;
-  t.ka = k + kMfmaSlack;
-  t.dpad = ivf->dpad;
-  t.capA = (uint32_t)std::max(1, capA_env);
-  t.min_rows = 256u;
-  t.rows_f16 = ivf->f16 ? 0 : (ivf->pool.half ? 1 : 2);
-  t.thr = u_out;
+  launch_prep_queries(ivf, E, qpad, B);
+  ThresholdArgs t = threshold_args(ivf, S, qpad, probes, B, k, np, u_out);
   t.glob_blocks = ivf->t_glob.as<uint32_t>();
-  if (half_rows) hipLaunchKernelGGL((threshold_direct_kernel<true>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, t);
-  else hipLaunchKernelGGL((threshold_direct_kernel<false>), dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, t);
+  launch_threshold_direct(ivf, ctx, t);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
@@ -974,7 +1153,7 @@ int ivf_thr_combine(fvdb_ivf* ivf, const Env& E, const float* u_all, uint32_t W,
     HIPCHK(ctx, hipMemsetAsync(ivf->d_xmax.p, 0, 4, ctx->stream));
   }
   hipLaunchKernelGGL(thr_combine_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, u_all, W, B, S.s_qn2.as<float>(),
-                     ivf->d_xmax.as<uint32_t>(), (float)ivf->dpad, ivf->f16 ? 0 : (ivf->pool.half ? 1 : 2), thr_out);
+                     ivf->d_xmax.as<uint32_t>(), (float)ivf->dpad, x_rounded(ivf), thr_out);
 #ifdef FVDB_DEV_TOOLS
   if (loopback_fill)
     hipLaunchKernelGGL(thr_loopback_fill_kernel, dim3(1), dim3(1024), 0, ctx->stream, thr_out, S.s_qn2.as<float>(), B);
@@ -1261,7 +1440,7 @@ void fvdb_ivf_destroy(fvdb_ivf* ivf) {
   (void)hipStreamSynchronize(ivf->ctx->stream);
   ivf->pool.release();
   ivf->cpool.release();
-  DBuf* bufs[] = {&ivf->d_xmax, &ivf->d_cent_pad, &ivf->d_cnorm, &ivf->d_cnmax, &ivf->s_fallbacks, &ivf->d_centroids_rm,
+  DBuf* bufs[] = {&ivf->d_xmax, &ivf->d_cent_pad, &ivf->d_cnorm, &ivf->d_cnmax, &ivf->s_fallbacks, &ivf->d_mfma_stamps, &ivf->d_centroids_rm,
                   &ivf->c_off, &ivf->c_blocks, &ivf->c_glob, &ivf->t_off, &ivf->t_blocks, &ivf->t_glob, &ivf->t_len};
   for (DBuf* b : bufs) b->release();
   ivf->release_all();
@@ -1307,12 +1486,12 @@ static int install_centroids(fvdb_ivf* ivf, const float* d_rowmajor /* device [n
   }
   HIPCHK(ctx, ivf->d_cnorm.ensure((size_t)nlist * 4));
   HIPCHK(ctx, ivf->d_cnmax.ensure(4));
-  HIPCHK(ctx, ivf->s_fallbacks.ensure(32));  // [0] coarse, [1] list scan, [2..5] why a query was not proven (VerifyArgs::reasons)
+  HIPCHK(ctx, ivf->s_fallbacks.ensure(kFbBytes));
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(nlist, 256)), dim3(256), 0, ctx->stream, cpad, ivf->dpad, ivf->dpad,
                      nlist, ivf->d_cnorm.as<float>());
   hipLaunchKernelGGL(max_f32_kernel, dim3(1), dim3(64), 0, ctx->stream, ivf->d_cnorm.as<float>(), nlist,
                      ivf->d_cnmax.as<float>());
-  HIPCHK(ctx, hipMemsetAsync(ivf->s_fallbacks.p, 0, 32, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ivf->s_fallbacks.p, 0, kFbBytes, ctx->stream));
   if (ivf->h_fb.p) *(volatile uint32_t*)ivf->h_fb.p = 0;
   ivf->mfma_q = ivf->fb_seen = ivf->q_seen = 0;
   ivf->exact_batches_left = ivf->backoff_len = 0;
@@ -1593,14 +1772,13 @@ static int search_common(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32
     if (all) {
       hipLaunchKernelGGL(probes_all_kernel, dim3(cdiv((uint64_t)b * np, 256)), dim3(256), 0, ctx->stream, b, np,
                          S.s_probes.as<uint32_t>());
-      if (ivf->ctx->profiling) (void)hipEventRecord(S.sev[2], ctx->stream);
+      mark(ivf, E, EV_COARSE_DONE);
     } else if (given_probes) {
       probes = given_probes + (size_t)o * np;
-      if (ivf->ctx->profiling) {  // no coarse stage in this call: zero-length stage intervals
-        (void)hipEventRecord(S.sev[0], ctx->stream);
-        (void)hipEventRecord(S.sev[1], ctx->stream);
-        (void)hipEventRecord(S.sev[2], ctx->stream);
-      }
+      // no coarse stage in this call: zero-length stage intervals
+      mark(ivf, E, EV_COARSE_BEGIN);
+      mark(ivf, E, EV_COARSE_SCANNED);
+      mark(ivf, E, EV_COARSE_DONE);
     } else {
       rc = run_coarse(ivf, E, qpad, b, np, probes_only ? probes_only + (size_t)o * np : S.s_probes.as<uint32_t>(), nullptr);
       if (rc) return rc;
@@ -1889,41 +2067,21 @@ int fvdb_ivf_scan_survivor_dump(fvdb_ivf* ivf, uint32_t query, uint32_t max_n, u
   return FVDB_OK;
 }
 
-int fvdb_ivf_scan_fallbacks(fvdb_ivf* ivf, uint64_t* out) {
+// n words of the counter block from `first` on (zeros while there is no block yet)
+static int read_counters(fvdb_ivf* ivf, FbWord first, uint32_t n, uint64_t* out) {
   fvdb_ctx* ctx = ivf->ctx;
-  *out = 0;
+  for (uint32_t i = 0; i < n; ++i) out[i] = 0;
   if (!ivf->s_fallbacks.p) return FVDB_OK;
-  uint32_t v = 0;
+  uint32_t v[FB_WORDS] = {};
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpyAsync(&v, ivf->s_fallbacks.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(v, ivf->fb_word(first), n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *out = v;
+  for (uint32_t i = 0; i < n; ++i) out[i] = v[i];
   return FVDB_OK;
 }
-
-int fvdb_ivf_scan_fallback_reasons(fvdb_ivf* ivf, uint64_t* out5) {
-  fvdb_ctx* ctx = ivf->ctx;
-  for (int i = 0; i < 5; ++i) out5[i] = 0;
-  if (!ivf->s_fallbacks.p) return FVDB_OK;
-  uint32_t v[5] = {0, 0, 0, 0, 0};
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpyAsync(v, ivf->s_fallbacks.as<uint32_t>() + 2, 20, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < 5; ++i) out5[i] = v[i];
-  return FVDB_OK;
-}
-
-int fvdb_ivf_coarse_fallbacks(fvdb_ivf* ivf, uint64_t* out) {
-  fvdb_ctx* ctx = ivf->ctx;
-  *out = 0;
-  if (!ivf->s_fallbacks.p) return FVDB_OK;
-  uint32_t v = 0;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpyAsync(&v, ivf->s_fallbacks.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *out = v;
-  return FVDB_OK;
-}
+int fvdb_ivf_scan_fallbacks(fvdb_ivf* ivf, uint64_t* out) { return read_counters(ivf, FB_SCAN, 1, out); }
+int fvdb_ivf_scan_fallback_reasons(fvdb_ivf* ivf, uint64_t* out5) { return read_counters(ivf, FB_REASONS, kFbReasonWords, out5); }
+int fvdb_ivf_coarse_fallbacks(fvdb_ivf* ivf, uint64_t* out) { return read_counters(ivf, FB_COARSE, 1, out); }
 
 int fvdb_ivf_last_stats(fvdb_ivf* ivf, fvdb_search_stats* out) {
   fvdb_ctx* ctx = ivf->ctx;
@@ -1934,7 +2092,7 @@ int fvdb_ivf_last_stats(fvdb_ivf* ivf, fvdb_search_stats* out) {
   }
   unsigned long long st[3];
   HIPCHK(ctx, hipDeviceSynchronize());
-  HIPCHK(ctx, hipMemcpyAsync(st, S.s_scalars.as<uint32_t>() + 4, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(st, S.scalar(SC_STATS), sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   out->rows_scanned = st[0];
   out->work_items = st[1];
