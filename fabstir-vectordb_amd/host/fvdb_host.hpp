@@ -63,6 +63,45 @@ struct Visited {
   void grow();
 };
 
+// "no result" rows of a batch: counts 0, ids FVDB_NO_ID, distances +inf
+inline void fill_empty(uint64_t* ids, float* dist, uint32_t* counts, uint32_t B, uint32_t k) {
+  for (uint32_t b = 0; b < B; ++b) counts[b] = 0;
+  for (size_t i = 0; i < (size_t)B * k; ++i) {
+    ids[i] = FVDB_NO_ID;
+    dist[i] = __builtin_huge_valf();
+  }
+}
+
+// Grow-only device block and, where the owner asks for one, its pinned host twin of the same size.  reserve() frees and
+// reallocates when the block is too small (contents are not kept); the owner's destructor calls release().
+struct DevBuf {
+  fvdb_ctx* ctx = nullptr;  // the context of the last allocation
+  void *dev = nullptr, *host = nullptr;
+  uint64_t cap = 0;  // bytes
+  int reserve(fvdb_ctx* c, uint64_t bytes, bool pinned) {
+    if (bytes <= cap) return FVDB_OK;
+    release();
+    ctx = c;
+    if (fvdb_dev_alloc(c, bytes, &dev) || (pinned && fvdb_host_alloc(c, bytes, &host))) return FVDB_E_OOM;
+    cap = bytes;
+    return FVDB_OK;
+  }
+  void release() {
+    if (dev) fvdb_dev_free(ctx, dev);
+    if (host) fvdb_host_free(ctx, host);
+    dev = host = nullptr;
+    cap = 0;
+  }
+};
+
+// The context (stream) of one in-flight slot, made on first use: borrowed from the index (slot 0) or created.
+inline int slot_ctx(fvdb_ctx* base, bool borrow, fvdb_ctx** ctx) {
+  if (*ctx) return FVDB_OK;
+  if (!borrow) return fvdb_ctx_create(fvdb_ctx_device(base), ctx);
+  *ctx = base;
+  return FVDB_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
@@ -222,43 +261,29 @@ class HNSWIndex {
     RustHeap candidates, nearest;
     Visited visited;
     std::vector<uint32_t> pending;  // candidates sent to the GPU this hop
+    std::vector<Cand> cur;          // search_layer: [0] = the layer's entry going in; the layer's nearest, ascending, coming out
     bool active = false;
   };
-  uint32_t cap(uint32_t layer) const { return layer == 0 ? cfg_.max_connections_layer_0 : cfg_.max_connections; }
-  std::vector<uint32_t>& nb(uint32_t node, uint32_t layer) { return nbrs_[node][layer]; }
-  int ensure_store(uint32_t dim);
-  int ensure_scorer(uint32_t B, uint32_t C);
-  int append_row(const float* v, uint32_t* row);
-  // lock-step search_layer (:469-554) for B queries already loaded into the scorer
-  int search_layer_batch(uint32_t B, const std::vector<Cand>& entries, const std::vector<uint8_t>& has_entry,
-                         uint32_t ef, uint32_t layer, std::vector<std::vector<Cand>>& results);
-  int score_pairs_from_row(uint32_t base_row, const std::vector<uint32_t>& cands, std::vector<float>& out);
-  int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                  float* dist, uint32_t* counts);
-  // Pipelined batch search: queries are split into a few lanes (one scorer = one HIP stream each) driven
-  // round-robin, so that while the GPU scores one lane's hop the host applies and prepares another's.
-  // Per query the operation sequence is still search_layer's.
-  struct Lane {
+  // Working state of one lock-step walk: the scorer (one HIP stream; candidate and distance rows in pinned memory) and
+  // the per-query heaps.  There are two, never used by the same caller: search_walk_ serves the host walk of the
+  // searches (under walk_mu_ — finish_failed runs it from search threads that hold the index only for reading),
+  // insert_walk_ the host algorithm of an insert (B = 1, under the caller's write exclusion).
+  struct Walk {
     fvdb_scorer* sc = nullptr;
     uint32_t cap_B = 0, cap_C = 0;
     std::vector<Query> qs;
-    std::vector<uint32_t> prev_cnt;
-    std::vector<std::vector<Cand>> cur;
-    uint32_t lo = 0, n = 0, layer = 0, ef = 0, k = 0;
-    int stage = 0;  // 0 start, 1 entry scored, 2 hop in flight
-    int threads = 1;  // OpenMP threads for this lane's host phases
-    bool done = true;
-    int rc = 0;
-    uint64_t dists = 0, hops = 0;
+    std::vector<uint32_t> prev_cnt;  // candidates each scorer row holds from the hop before: what the next hop blanks
   };
-  int lane_ensure(Lane& ln, uint32_t B, uint32_t C);
-  void lane_layer_init(Lane& ln);
-  uint32_t lane_hop_prepare(Lane& ln);
-  void lane_hop_apply(Lane& ln);
-  void lane_layer_collect(Lane& ln);
-  void lane_advance(Lane& ln, const float* q, bool q_on_device, uint32_t ef_final, uint64_t* ids, float* dist,
-                    uint32_t* counts);
-  std::vector<Lane> lanes_;
+  Walk search_walk_, insert_walk_;
+  uint32_t cap(uint32_t layer) const { return layer == 0 ? cfg_.max_connections_layer_0 : cfg_.max_connections; }
+  int ensure_store(uint32_t dim);
+  // a walk of B queries with up to C candidates per hop: scorer large enough, every candidate row counted as dirty
+  int walk_begin(Walk& w, uint32_t B, uint32_t C);
+  // search_layer (:469-554) for the B queries loaded into w's scorer, in lock step; entries and results in Query::cur
+  int search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer);
+  int score_pairs_from_row(uint32_t base_row, const std::vector<uint32_t>& cands, std::vector<float>& out);
+  int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
+                  float* dist, uint32_t* counts);
   int sync_graph();
   bool device_path_ok(uint32_t ef) const;
   int device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot);
@@ -288,20 +313,26 @@ class HNSWIndex {
   bool device_insert_ok() const;
   int check_insert(uint64_t id, const float* v, uint32_t dim) const;
   int insert_host(uint64_t id, const float* v, uint32_t dim, int64_t forced_level);
+  // m inserts in progress: vectors into the store and host_vecs_, bookkeeping with registered = 0 ("not yet in the nodes
+  // map" while the links are being made, :370); *first = the first of their rows
+  int append_nodes(const uint64_t* ids, const uint32_t* levels, const float* v, uint32_t m, uint32_t* first);
+  // a whole pre-built graph's nodes into the empty index, registered (restore, bulk_build); levels == nullptr: drawn
+  template <class L>
+  int adopt_nodes(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const L* levels);
+  // Links the appended row by the host algorithm, registers it and brings the device graph up to date by the rules
+  // above: rows patched while the two copies agree, host_ahead_ otherwise.  on_device: the device graph holds the node
+  // already (fvdb_graph_append_nodes).  The caller has pulled nbrs_ (ensure_host_graph).
+  int link_and_publish(uint32_t row, bool on_device);
   // the host algorithm's links for node `row` (bookkeeping and vector already in place); the (node, layer) lists it
   // changed are appended to `touched`
   int link_host(uint32_t row, std::vector<std::pair<uint32_t, uint32_t>>* touched);
-  int push_lists(const std::vector<std::pair<uint32_t, uint32_t>>& touched);
   void finalize_insert(uint32_t row);
-  struct DevSlot {  // per in-flight batch: stream (context), device result buffers, pinned host copies
+  struct DevSlot {  // per in-flight batch: stream (context), device result block and its pinned host copy
     fvdb_ctx* ctx = nullptr;  // slot 0 borrows ctx_, the others own theirs
-    void *d_nodes = nullptr, *d_dist = nullptr, *d_cnt = nullptr, *d_status = nullptr;
-    void *h_nodes = nullptr, *h_dist = nullptr, *h_cnt = nullptr, *h_status = nullptr;
-    uint64_t cap = 0;
+    DevBuf buf;               // WalkBlock layout
   };
   DevSlot slots_[kSlots];
-  void* d_q_ = nullptr;
-  uint64_t d_q_cap_ = 0;
+  DevBuf d_q_;  // staging for host-resident query batches of search()
   std::atomic<uint64_t> n_fallback_{0};
   // Searches may come from several host threads (HybridIndex leases a slot per call): the graph mirror is synced by
   // one of them, the rare host-walk fallback and the standalone search()/search_dev() entry points are serialised.
@@ -311,8 +342,6 @@ class HNSWIndex {
   HNSWConfig cfg_;
   SplitMix64 rng_;
   fvdb_store* store_ = nullptr;
-  fvdb_scorer* scorer_ = nullptr;
-  uint32_t scorer_B_ = 0, scorer_C_ = 0;
   uint32_t dim_ = 0;
   bool has_dim_ = false, has_entry_ = false, entry_lost_ = false;
   uint32_t entry_ = 0;
@@ -323,9 +352,7 @@ class HNSWIndex {
   std::vector<std::vector<std::vector<uint32_t>>> nbrs_;  // [node][layer] insertion-ordered sets
   std::unordered_map<uint64_t, uint32_t> index_of_;
   std::vector<float> host_vecs_;
-  std::vector<Query> qs_;
   uint64_t n_dist_ = 0, n_hops_ = 0;
-  double t_prepare_us_ = 0, t_gpu_us_ = 0, t_apply_us_ = 0;
   int threads_ = 0;
 };
 
@@ -456,9 +483,24 @@ class HybridIndex {
   static double age_of(double now, double ts) { return now - ts < 0 ? 0.0 : now - ts; }
   int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                   double now, uint64_t* ids, float* dist, uint32_t* counts);
+  // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl
+  int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
+                     int shard_mode, double now);
   int begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                  int shard_mode = -1);
+  // The per-search auto-migration (src/hybrid/core.rs:437-439).  A due migration moves rows between the two indexes (and
+  // may grow the list pool), so it is refused with FVDB_E_INVALID while batches begun with search_dev_begin are
+  // uncollected — now, or (`in_flight_before`) when the caller looked before it came here.
+  int migrate_if_due(double now, bool in_flight_before);
+  struct Slice {  // FVDB_SHARD_STRONG: this rank's rows [lo, hi) of a global batch, `per` rows to every rank
+    uint32_t per, lo, hi;
+  };
+  Slice strong_slice(uint32_t B) const;
   int build_recent(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim);
+  // first half of both bulk loaders: timestamps, routing by age like insert_with_timestamp, the graph of the recent rows
+  // and their migration queue; the historical rows come back in hid / hv
+  int bulk_route(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts, double now,
+                 std::vector<uint64_t>& hid, std::vector<float>& hv);
   bool sequential_graph_ = true;
   std::atomic<bool> writers_wait_{false};
   // exclusive access for a mutation: with no batch in flight, or FVDB_E_INVALID / after waiting (set_blocking_writers)
@@ -481,18 +523,30 @@ class HybridIndex {
   std::condition_variable slot_cv_;
   fvdb_ctx* ctx_ivf_;
   struct Slot {  // one batch in flight
-    void *d_hid = nullptr, *d_hd = nullptr, *d_hc = nullptr;  // device result buffers of the IVF part
-    void *h_hid = nullptr, *h_hd = nullptr, *h_hc = nullptr;  // pinned host copies
-    uint64_t cap = 0;
+    DevBuf ivf;             // results of the IVF part (IvfBlock layout): device block and its pinned host copy
+    uint32_t ivf_rows = 0;  // rows the IVF part writes into it for this batch
     fvdb_event* ivf_done = nullptr;
     fvdb_ctx* ivf_ctx = nullptr;  // slot 0 borrows ctx_ivf_, the others own a context (stream) each
     bool active = false, ivf_in_flight = false, hnsw_in_flight = false, recent = false;
-    void* d_q = nullptr;      // staging for host-resident query batches of the blocking entry points
-    uint64_t d_q_cap = 0;
+    DevBuf d_q;  // staging for host-resident query batches of the blocking entry points
     const float* q = nullptr;
     uint32_t B = 0, dim = 0, k = 0, rk = 0, hk = 0, ef = 0;
   };
   Slot slots_[kSlots];
+  // Slot::active held for a scope: set under slot_mu_, cleared on release with the waiting writers and searches woken.
+  // hand_over() leaves the mark in place for the search_dev_end that collects the batch, which adopts it.
+  struct Lease {
+    static constexpr uint32_t kAnyFree = ~0u;  // wait for a free slot and take the highest
+    enum How { kTake, kAdopt };                // mark a slot that is not active / take over the mark of one that is
+    Lease(HybridIndex* h, uint32_t slot, How how);
+    ~Lease();
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    void hand_over() { sl = nullptr; }
+    uint32_t index() const { return (uint32_t)(sl - h->slots_); }
+    HybridIndex* h;
+    Slot* sl = nullptr;  // nullptr: nothing held (the slot was not in the state asked for, or handed over)
+  };
   HybridConfig cfg_;
   HNSWIndex* recent_;
   IVFIndex* historical_;

@@ -2,7 +2,9 @@
 // Ids, levels, flags and a copy of the adjacency live here.  Inserts and batch searches normally run whole on the
 // device against the adjacency in HBM (fvdb_graph_insert_linked / fvdb_graph_search_dev*); the host algorithm below —
 // heaps and visited sets here, every distance batch scored on the GPU through fvdb_scorer_* — is the other mode of
-// both (same results), and what takes over for shapes the device kernels do not serve.
+// both (same results), and what takes over for shapes the device kernels do not serve.  The reference's search_layer
+// is restated once (HNSWIndex::search_layer, B queries in lock step): search_host_walk runs it for a batch of queries,
+// link_host for the one vector being inserted, each on its own Walk (scorer and heaps).
 #include <omp.h>
 
 #include <algorithm>
@@ -139,16 +141,12 @@ HNSWIndex::HNSWIndex(fvdb_ctx* ctx, const HNSWConfig& cfg) : ctx_(ctx), cfg_(cfg
 HNSWIndex::~HNSWIndex() {
   if (graph_) fvdb_graph_destroy(graph_);
   for (uint32_t i = 0; i < kSlots; ++i) {
-    DevSlot& sl = slots_[i];
-    fvdb_ctx* c = sl.ctx ? sl.ctx : ctx_;
-    if (sl.d_nodes) fvdb_dev_free(c, sl.d_nodes);  // the other pointers are carved out of these two blocks
-    if (sl.h_nodes) fvdb_host_free(c, sl.h_nodes);
-    if (i > 0 && sl.ctx) fvdb_ctx_destroy(sl.ctx);
+    slots_[i].buf.release();
+    if (i > 0 && slots_[i].ctx) fvdb_ctx_destroy(slots_[i].ctx);
   }
-  if (d_q_) fvdb_dev_free(ctx_, d_q_);
-  for (auto& ln : lanes_)
-    if (ln.sc) fvdb_scorer_destroy(ln.sc);
-  if (scorer_) fvdb_scorer_destroy(scorer_);
+  d_q_.release();
+  for (Walk* w : {&search_walk_, &insert_walk_})
+    if (w->sc) fvdb_scorer_destroy(w->sc);
   if (store_) fvdb_store_destroy(store_);
 }
 
@@ -170,21 +168,17 @@ int HNSWIndex::ensure_store(uint32_t dim) {
   return fvdb_store_create(ctx_, dim, 1024, &store_);
 }
 
-int HNSWIndex::ensure_scorer(uint32_t B, uint32_t C) {
-  if (scorer_ && scorer_B_ >= B && scorer_C_ >= C) return FVDB_OK;
-  if (scorer_) fvdb_scorer_destroy(scorer_);
-  scorer_ = nullptr;
-  scorer_B_ = std::max(B, scorer_B_);
-  scorer_C_ = std::max(C, scorer_C_);
-  return fvdb_scorer_create(store_, scorer_B_, scorer_C_, &scorer_);
-}
-
-int HNSWIndex::append_row(const float* v, uint32_t* row) {
-  uint64_t first = 0;
-  int rc = fvdb_store_append(store_, v, 1, &first);
-  if (rc) return rc;
-  *row = (uint32_t)first;
-  host_vecs_.insert(host_vecs_.end(), v, v + dim_);
+int HNSWIndex::walk_begin(Walk& w, uint32_t B, uint32_t C) {
+  if (!w.sc || w.cap_B < B || w.cap_C < C) {
+    if (w.sc) fvdb_scorer_destroy(w.sc);
+    w.sc = nullptr;
+    w.cap_B = std::max(B, w.cap_B);
+    w.cap_C = std::max(C, w.cap_C);
+    int rc = fvdb_scorer_create(store_, w.cap_B, w.cap_C, &w.sc);
+    if (rc) return rc;
+  }
+  if (w.qs.size() < B) w.qs.resize(B);
+  w.prev_cnt.assign(w.cap_B, w.cap_C);  // rows start dirty: blanked on first use, so no stale candidate is ever scored
   return FVDB_OK;
 }
 
@@ -228,48 +222,39 @@ uint64_t HNSWIndex::active_count() const {
 
 // --------------------------------------------------------------------------------------------
 // search_layer (src/hnsw/core.rs:469-554) for B queries in lock-step.  The queries are already
-// in the scorer.  Per hop every active query pops candidates until one of them has unvisited,
-// live neighbours; those go to the GPU in one launch; the admission rule (:517-531) is then
-// applied in neighbour order with the returned distances.
+// in the scorer, each query's entry is cur[0].  Per hop every active query pops candidates until
+// one of them has unvisited, live neighbours; those go to the GPU in one launch; the admission
+// rule (:517-531) is then applied in neighbour order with the returned distances.  cur becomes
+// the layer's result — and stays what it was if the layer returned nothing (:445-447).
 // --------------------------------------------------------------------------------------------
-int HNSWIndex::search_layer_batch(uint32_t B, const std::vector<Cand>& entries, const std::vector<uint8_t>& has_entry,
-                                  uint32_t ef, uint32_t layer, std::vector<std::vector<Cand>>& results) {
-  if (qs_.size() < B) qs_.resize(B);
-  results.resize(B);
-  const uint32_t maxC = scorer_C_;
-  uint32_t* cand = fvdb_scorer_cand_buffer(scorer_);
-  const float* dist = fvdb_scorer_dist_buffer(scorer_);
+int HNSWIndex::search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer) {
+  const uint32_t maxC = w.cap_C;
+  uint32_t* cand = fvdb_scorer_cand_buffer(w.sc);
+  const float* dist = fvdb_scorer_dist_buffer(w.sc);
   static const int auto_threads = usable_cpus();
-  const int nt = threads_ > 0 ? threads_ : auto_threads;
-  const bool par = B >= 32 && nt > 1;
-  std::vector<uint32_t> prev_cnt(B, maxC);  // rows start dirty: clear them on first use
+  const int nt = B >= 32 ? std::max(1, threads_ > 0 ? threads_ : auto_threads) : 1;  // OpenMP threads of the host phases
 
-#pragma omp parallel for schedule(static) num_threads(nt) if (par)
+#pragma omp parallel for schedule(static) num_threads(nt) if (nt > 1)
   for (uint32_t b = 0; b < B; ++b) {
-    Query& s = qs_[b];
+    Query& s = w.qs[b];
     s.candidates.clear();
     s.nearest.clear();
     s.pending.clear();
-    s.active = false;
-    results[b].clear();
-    if (!has_entry[b]) continue;
     s.visited.reset((size_t)ef * 8 + 64);
-    const Cand e = entries[b];
+    const Cand e = s.cur[0];
     s.candidates.push({e.node, e.distance});
     s.nearest.push({e.node, -e.distance});
     s.visited.insert(e.node);
     s.active = true;
   }
 
-  using clk = std::chrono::steady_clock;
-  auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
   for (;;) {
-    const auto t_a = clk::now();
+    // prepare: the hop's candidates into the scorer's rows, what the previous hop left there blanked
     uint32_t hopC = 0;
     uint64_t hop_dists = 0;
-#pragma omp parallel for schedule(static) num_threads(nt) reduction(max : hopC) reduction(+ : hop_dists) if (par)
+#pragma omp parallel for schedule(static) num_threads(nt) reduction(max : hopC) reduction(+ : hop_dists) if (nt > 1)
     for (uint32_t b = 0; b < B; ++b) {
-      Query& s = qs_[b];
+      Query& s = w.qs[b];
       s.pending.clear();
       if (s.active) {
         for (;;) {
@@ -297,22 +282,20 @@ int HNSWIndex::search_layer_batch(uint32_t B, const std::vector<Cand>& entries, 
       uint32_t* row = cand + (size_t)b * maxC;
       const uint32_t n = (uint32_t)s.pending.size();
       for (uint32_t i = 0; i < n; ++i) row[i] = s.pending[i];
-      for (uint32_t i = n; i < prev_cnt[b]; ++i) row[i] = FVDB_NO_ROW;
-      prev_cnt[b] = n;
+      for (uint32_t i = n; i < w.prev_cnt[b]; ++i) row[i] = FVDB_NO_ROW;
+      w.prev_cnt[b] = n;
       hopC = std::max(hopC, n);
       hop_dists += n;
     }
     if (hopC == 0) break;
-    static const bool dbg = getenv("FVDB_DEBUG") != nullptr;
-    const auto t_b = clk::now();
-    int rc = fvdb_scorer_run(scorer_, B, hopC);
+    int rc = fvdb_scorer_run(w.sc, B, hopC);  // score: one launch for the whole batch
     if (rc) return rc;
-    const auto t_c = clk::now();
     n_hops_ += 1;
     n_dist_ += hop_dists;
-#pragma omp parallel for schedule(static) num_threads(nt) if (par)
+    // apply
+#pragma omp parallel for schedule(static) num_threads(nt) if (nt > 1)
     for (uint32_t b = 0; b < B; ++b) {
-      Query& s = qs_[b];
+      Query& s = w.qs[b];
       const float* drow = dist + (size_t)b * maxC;
       for (size_t i = 0; i < s.pending.size(); ++i) {
         const float d = drow[i];
@@ -323,18 +306,14 @@ int HNSWIndex::search_layer_batch(uint32_t B, const std::vector<Cand>& entries, 
         }
       }
     }
-    const auto t_d = clk::now();
-    t_prepare_us_ += us(t_a, t_b);
-    t_gpu_us_ += us(t_b, t_c);
-    t_apply_us_ += us(t_c, t_d);
-    (void)dbg;
   }
 
-#pragma omp parallel for schedule(static) num_threads(nt) if (par)
+#pragma omp parallel for schedule(static) num_threads(nt) if (nt > 1)
   for (uint32_t b = 0; b < B; ++b) {
-    if (!has_entry[b]) continue;
-    Query& s = qs_[b];
-    auto& r = results[b];
+    Query& s = w.qs[b];
+    if (s.nearest.empty()) continue;  // search_layer returned nothing: keep the previous nearest (:445-447)
+    auto& r = s.cur;
+    r.clear();
     r.reserve(s.nearest.len());
     for (const Cand& c : s.nearest.data) r.push_back({c.node, -c.distance});  // :541-547 (heap order)
     std::stable_sort(r.begin(), r.end(), [](const Cand& a, const Cand& c) { return a.distance < c.distance; });
@@ -352,167 +331,6 @@ int HNSWIndex::search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint
 int HNSWIndex::search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
                           float* dist, uint32_t* counts) {
   return search_impl(q_dev, true, B, dim, k, ef, ids, dist, counts);
-}
-
-// ---- lane primitives: search_layer (:469-554) split into init / prepare-hop / apply-hop / collect ----
-int HNSWIndex::lane_ensure(Lane& ln, uint32_t B, uint32_t C) {
-  if (ln.sc && ln.cap_B >= B && ln.cap_C >= C) return FVDB_OK;
-  if (ln.sc) fvdb_scorer_destroy(ln.sc);
-  ln.sc = nullptr;
-  ln.cap_B = std::max(B, ln.cap_B);
-  ln.cap_C = std::max(C, ln.cap_C);
-  return fvdb_scorer_create(store_, ln.cap_B, ln.cap_C, &ln.sc);
-}
-
-void HNSWIndex::lane_layer_init(Lane& ln) {
-#pragma omp parallel for schedule(static) num_threads(ln.threads) if (ln.threads > 1)
-  for (uint32_t b = 0; b < ln.n; ++b) {
-    Query& s = ln.qs[b];
-    s.candidates.clear();
-    s.nearest.clear();
-    s.pending.clear();
-    s.visited.reset((size_t)ln.ef * 8 + 64);
-    const Cand e = ln.cur[b][0];
-    s.candidates.push({e.node, e.distance});
-    s.nearest.push({e.node, -e.distance});
-    s.visited.insert(e.node);
-    s.active = true;
-  }
-}
-
-uint32_t HNSWIndex::lane_hop_prepare(Lane& ln) {
-  uint32_t* cand = fvdb_scorer_cand_buffer(ln.sc);
-  const uint32_t maxC = ln.cap_C, layer = ln.layer;
-  uint32_t hopC = 0;
-  uint64_t nd = 0;
-#pragma omp parallel for schedule(static) num_threads(ln.threads) reduction(max : hopC) reduction(+ : nd) if (ln.threads > 1)
-  for (uint32_t b = 0; b < ln.n; ++b) {
-    Query& s = ln.qs[b];
-    s.pending.clear();
-    if (s.active) {
-      for (;;) {
-        if (s.candidates.empty()) {
-          s.active = false;
-          break;
-        }
-        const Cand cur = s.candidates.pop();
-        if (cur.distance > -s.nearest.peek().distance) {  // :499-501
-          s.active = false;
-          break;
-        }
-        const uint32_t node = cur.node;
-        if (registered_[node] && level_[node] >= layer) {
-          for (uint32_t nbv : nbrs_[node][layer]) {
-            if (!s.visited.insert(nbv)) continue;  // :506-507
-            if (!registered_[nbv]) continue;       // :509
-            if (deleted_[nbv]) continue;           // :511-513
-            s.pending.push_back(nbv);
-          }
-        }
-        if (!s.pending.empty()) break;
-      }
-    }
-    uint32_t* row = cand + (size_t)b * maxC;
-    const uint32_t n = (uint32_t)s.pending.size();
-    for (uint32_t i = 0; i < n; ++i) row[i] = s.pending[i];
-    for (uint32_t i = n; i < ln.prev_cnt[b]; ++i) row[i] = FVDB_NO_ROW;
-    ln.prev_cnt[b] = n;
-    hopC = std::max(hopC, n);
-    nd += n;
-  }
-  ln.dists += nd;
-  return hopC;
-}
-
-void HNSWIndex::lane_hop_apply(Lane& ln) {
-  const float* dist = fvdb_scorer_dist_buffer(ln.sc);
-  const uint32_t maxC = ln.cap_C, ef = ln.ef;
-#pragma omp parallel for schedule(static) num_threads(ln.threads) if (ln.threads > 1)
-  for (uint32_t b = 0; b < ln.n; ++b) {
-    Query& s = ln.qs[b];
-    const float* drow = dist + (size_t)b * maxC;
-    for (size_t i = 0; i < s.pending.size(); ++i) {
-      const float d = drow[i];
-      if (d < -s.nearest.peek().distance || s.nearest.len() < ef) {  // :517-519
-        s.candidates.push({s.pending[i], d});
-        s.nearest.push({s.pending[i], -d});
-        if (s.nearest.len() > ef) s.nearest.pop();
-      }
-    }
-  }
-}
-
-void HNSWIndex::lane_layer_collect(Lane& ln) {
-#pragma omp parallel for schedule(static) num_threads(ln.threads) if (ln.threads > 1)
-  for (uint32_t b = 0; b < ln.n; ++b) {
-    Query& s = ln.qs[b];
-    if (s.nearest.empty()) continue;  // search_layer returned nothing: keep the previous nearest (:445-447)
-    auto& r = ln.cur[b];
-    r.clear();
-    r.reserve(s.nearest.len());
-    for (const Cand& c : s.nearest.data) r.push_back({c.node, -c.distance});  // :541-547
-    std::stable_sort(r.begin(), r.end(), [](const Cand& a, const Cand& c) { return a.distance < c.distance; });
-  }
-}
-
-// One step of a lane's state machine: consume the GPU results that just arrived, do host work until
-// the next GPU launch is issued (or the lane's queries are finished).
-void HNSWIndex::lane_advance(Lane& ln, const float* q, bool q_on_device, uint32_t ef_final, uint64_t* ids,
-                             float* dist, uint32_t* counts) {
-  if (ln.done) return;
-  if (ln.stage == 0) {  // load this lane's queries, score the entry point (:432-435)
-    ln.rc = q_on_device ? fvdb_scorer_set_queries_dev(ln.sc, q + (size_t)ln.lo * dim_, ln.n)
-                        : fvdb_scorer_set_queries(ln.sc, q + (size_t)ln.lo * dim_, ln.n);
-    if (ln.rc) { ln.done = true; return; }
-    uint32_t* cand = fvdb_scorer_cand_buffer(ln.sc);
-    for (uint32_t b = 0; b < ln.n; ++b) {
-      cand[(size_t)b * ln.cap_C] = entry_;
-      ln.prev_cnt[b] = std::max<uint32_t>(ln.prev_cnt[b], 1);
-    }
-    ln.rc = fvdb_scorer_launch(ln.sc, ln.n, 1);
-    if (ln.rc) { ln.done = true; return; }
-    ln.dists += ln.n;
-    ln.hops += 1;
-    ln.stage = 1;
-    return;
-  }
-  if (ln.stage == 1) {
-    const float* dbuf = fvdb_scorer_dist_buffer(ln.sc);
-    for (uint32_t b = 0; b < ln.n; ++b) ln.cur[b].assign(1, Cand{entry_, dbuf[(size_t)b * ln.cap_C]});
-    ln.layer = level_[entry_];
-    ln.ef = ln.layer == 0 ? ef_final : 1;
-    lane_layer_init(ln);
-    ln.stage = 2;
-  } else {
-    lane_hop_apply(ln);
-  }
-  for (;;) {
-    const uint32_t C = lane_hop_prepare(ln);
-    if (C > 0) {
-      ln.rc = fvdb_scorer_launch(ln.sc, ln.n, C);
-      if (ln.rc) ln.done = true;
-      ln.hops += 1;
-      return;
-    }
-    lane_layer_collect(ln);
-    if (ln.layer == 0) break;
-    ln.layer -= 1;
-    ln.ef = ln.layer == 0 ? ef_final : 1;
-    lane_layer_init(ln);
-  }
-  for (uint32_t b = 0; b < ln.n; ++b) {  // :451-466 filter deleted, take k
-    uint32_t w = 0;
-    const size_t o = (size_t)(ln.lo + b) * ln.k;
-    for (const Cand& c : ln.cur[b]) {
-      if (!registered_[c.node] || deleted_[c.node]) continue;
-      if (w >= ln.k) break;
-      ids[o + w] = ids_[c.node];
-      dist[o + w] = c.distance;
-      ++w;
-    }
-    counts[ln.lo + b] = w;
-  }
-  ln.done = true;
 }
 
 int HNSWIndex::ensure_graph_handle() {
@@ -596,41 +414,39 @@ bool HNSWIndex::device_path_ok(uint32_t ef) const {
   return device_traversal_ && !env_off && maxdeg <= 64 && ef <= 4096;  // one lane per neighbour
 }
 
+// one device block and one pinned block per slot, [nodes B*k | dist B*k | counts B | status B] -> a single copy
+namespace {
+struct WalkBlock {
+  uint32_t* nodes;
+  float* dist;
+  uint32_t *counts, *status;
+  uint64_t bytes;
+  WalkBlock(void* base, uint32_t B, uint32_t k) {
+    const uint64_t need = (uint64_t)B * std::max<uint32_t>(k, 1);
+    nodes = (uint32_t*)base;
+    dist = (float*)base + need;
+    counts = (uint32_t*)base + 2 * need;
+    status = counts + B;
+    bytes = (2 * need + 2 * (uint64_t)B) * 4;
+  }
+};
+}  // namespace
+
 // whole batch in one launch, results copied to pinned host memory — all asynchronous on the slot's stream
 int HNSWIndex::device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot) {
   if (slot >= kSlots) return FVDB_E_INVALID;
   int rc = sync_graph();
   if (rc) return rc;
   DevSlot& sl = slots_[slot];
-  if (!sl.ctx) {
-    if (slot == 0) {
-      sl.ctx = ctx_;
-    } else {
-      rc = fvdb_ctx_create(fvdb_ctx_device(ctx_), &sl.ctx);
-      if (rc) return rc;
-    }
-  }
-  // one device block and one pinned block per slot: [nodes B*k | dist B*k | counts B | status B] -> a single copy
-  const uint64_t need = (uint64_t)B * std::max<uint32_t>(k, 1);
-  const uint64_t words = 2 * need + 2 * (uint64_t)B;
-  if (words > sl.cap) {
-    if (sl.d_nodes) fvdb_dev_free(sl.ctx, sl.d_nodes);
-    if (sl.h_nodes) fvdb_host_free(sl.ctx, sl.h_nodes);
-    sl.d_nodes = sl.h_nodes = nullptr;
-    sl.cap = 0;
-    if (fvdb_dev_alloc(sl.ctx, words * 4, &sl.d_nodes) || fvdb_host_alloc(sl.ctx, words * 4, &sl.h_nodes)) return FVDB_E_OOM;
-    sl.cap = words;
-  }
-  auto carve = [&](void* base, void*& dist, void*& cnt, void*& status) {
-    dist = (uint32_t*)base + need;
-    cnt = (uint32_t*)base + 2 * need;
-    status = (uint32_t*)base + 2 * need + B;
-  };
-  carve(sl.d_nodes, sl.d_dist, sl.d_cnt, sl.d_status);
-  carve(sl.h_nodes, sl.h_dist, sl.h_cnt, sl.h_status);
-  rc = fvdb_graph_search_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, q_dev, B, k, ef, (uint32_t*)sl.d_nodes,
-                                  (float*)sl.d_dist, (uint32_t*)sl.d_cnt, (uint32_t*)sl.d_status);
-  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.h_nodes, sl.d_nodes, (size_t)words * 4);
+  rc = slot_ctx(ctx_, slot == 0, &sl.ctx);
+  if (rc) return rc;
+  const uint64_t bytes = WalkBlock(nullptr, B, k).bytes;
+  rc = sl.buf.reserve(sl.ctx, bytes, true);
+  if (rc) return rc;
+  const WalkBlock d(sl.buf.dev, B, k);
+  rc = fvdb_graph_search_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, q_dev, B, k, ef, d.nodes, d.dist, d.counts,
+                                  d.status);
+  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
   return rc;
 }
 
@@ -640,18 +456,17 @@ int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist
   DevSlot& sl = slots_[slot];
   int rc = fvdb_ctx_synchronize(sl.ctx);
   if (rc) return rc;
-  const uint32_t* nodes = (const uint32_t*)sl.h_nodes;
-  const uint32_t* status = (const uint32_t*)sl.h_status;
-  std::memcpy(dist, sl.h_dist, (size_t)B * k * 4);
-  std::memcpy(counts, sl.h_cnt, (size_t)B * 4);
+  const WalkBlock h(sl.buf.host, B, k);
+  std::memcpy(dist, h.dist, (size_t)B * k * 4);
+  std::memcpy(counts, h.counts, (size_t)B * 4);
   for (uint32_t b = 0; b < B; ++b) {
-    if (status[b]) {
+    if (h.status[b]) {
       failed.push_back(b);
       counts[b] = 0;
       continue;
     }
     for (uint32_t i = 0; i < k; ++i) {
-      const uint32_t nd = nodes[(size_t)b * k + i];
+      const uint32_t nd = h.nodes[(size_t)b * k + i];
       ids[(size_t)b * k + i] = i < counts[b] ? ids_[nd] : FVDB_NO_ID;
     }
   }
@@ -665,7 +480,7 @@ int HNSWIndex::finish_failed(const float* q, bool q_on_device, uint32_t dim, uin
   n_fallback_ += failed.size();
   int rcg = ensure_host_graph();
   if (rcg) return rcg;
-  std::lock_guard<std::mutex> lk(walk_mu_);  // the host walk's lanes and scorer are one set per index
+  std::lock_guard<std::mutex> lk(walk_mu_);  // the host walk's scorer and heaps are one set per index
   std::vector<float> hq((size_t)failed.size() * dim);
   for (size_t i = 0; i < failed.size(); ++i) {
     if (q_on_device) {
@@ -707,11 +522,7 @@ int HNSWIndex::search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint
 
 int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef,
                            uint64_t* ids, float* dist, uint32_t* counts) {
-  for (uint32_t b = 0; b < B; ++b) counts[b] = 0;
-  for (size_t i = 0; i < (size_t)B * k; ++i) {
-    ids[i] = FVDB_NO_ID;
-    dist[i] = __builtin_huge_valf();
-  }
+  fill_empty(ids, dist, counts, B, k);
   if (!has_entry_) return FVDB_OK;  // empty index -> empty results (:404-407)
   if (has_dim_ && dim != dim_) return FVDB_E_DIM;
   if (entry_lost_) return FVDB_E_NOT_FOUND;  // "Entry point node not found in index" (:422-429)
@@ -728,16 +539,11 @@ int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_
   const float* qd = q;
   if (!q_on_device) {  // stage the batch in HBM
     const uint64_t bytes = (uint64_t)B * dim * 4;
-    if (bytes > d_q_cap_) {
-      if (d_q_) fvdb_dev_free(ctx_, d_q_);
-      d_q_ = nullptr;
-      d_q_cap_ = 0;
-      if (fvdb_dev_alloc(ctx_, bytes, &d_q_)) return FVDB_E_OOM;
-      d_q_cap_ = bytes;
-    }
-    int rc = fvdb_dev_upload(ctx_, d_q_, q, bytes);
+    int rc = d_q_.reserve(ctx_, bytes, false);
     if (rc) return rc;
-    qd = (const float*)d_q_;
+    rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes);
+    if (rc) return rc;
+    qd = (const float*)d_q_.dev;
   }
   int rc = device_launch(qd, B, k, ef, 0);
   if (rc) return rc;
@@ -747,66 +553,46 @@ int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_
   return finish_failed(q, q_on_device, dim, k, ef, ids, dist, counts, failed);
 }
 
+// The layered walk on the host (:398-467) for chunks of at most 16384 queries in lock step: one scorer launch per hop
+// for the whole chunk.  (Several smaller groups on a stream each, driven round-robin so that one group's hop is on the
+// GPU while another's host phase runs, were measured slower: launch + stream sync cost more than the overlap wins,
+// profiles/r01_hnsw_lanes.log.)  The caller holds walk_mu_ and has pulled nbrs_.
 int HNSWIndex::search_host_walk(const float* q, bool q_on_device, uint32_t B, uint32_t k, uint32_t ef, uint64_t* ids,
                                 float* dist, uint32_t* counts) {
-  for (uint32_t b = 0; b < B; ++b) counts[b] = 0;
-  for (size_t i = 0; i < (size_t)B * k; ++i) {
-    ids[i] = FVDB_NO_ID;
-    dist[i] = __builtin_huge_valf();
-  }
-  static const int auto_threads = usable_cpus();
-  const int nt = std::max(1, threads_ > 0 ? threads_ : auto_threads);
+  fill_empty(ids, dist, counts, B, k);
+  Walk& w = search_walk_;
   const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0) + 1;
-  // Lanes (one HIP stream each) can be driven round-robin by the calling thread so that one lane's hop
-  // is on the GPU while another's host phase runs.  Measured on MI355X (profiles/r01_hnsw_lanes.log):
-  // launch + stream sync cost more than the overlap wins — 1 lane 15.5 ms/step, 2 lanes 18.1, 3 lanes
-  // 27.2 (1024 queries, 300K nodes) — so the default is ONE lane = one launch per hop for the whole batch.
-  static const uint32_t max_lanes = getenv("FVDB_HNSW_LANES") ? std::max(1, atoi(getenv("FVDB_HNSW_LANES"))) : 1;
   const uint32_t step = 16384;
-  for (uint32_t o = 0; o < B; o += step) {
-    const uint32_t b = std::min(step, B - o);
-    uint32_t nl = std::min<uint32_t>(max_lanes, std::max<uint32_t>(1, b / 64));
-    const uint32_t per = (b + nl - 1) / nl;
-    nl = (b + per - 1) / per;
-    if (lanes_.size() < nl) lanes_.resize(nl);
-    for (uint32_t l = 0; l < nl; ++l) {
-      Lane& ln = lanes_[l];
-      int rc = lane_ensure(ln, per, maxdeg);
+  for (uint32_t lo = 0; lo < B; lo += step) {
+    const uint32_t n = std::min(step, B - lo);
+    int rc = walk_begin(w, n, maxdeg);
+    if (rc) return rc;
+    rc = q_on_device ? fvdb_scorer_set_queries_dev(w.sc, q + (size_t)lo * dim_, n)
+                     : fvdb_scorer_set_queries(w.sc, q + (size_t)lo * dim_, n);
+    if (rc) return rc;
+    uint32_t* cand = fvdb_scorer_cand_buffer(w.sc);  // distance to the entry point (:432-435)
+    for (uint32_t b = 0; b < n; ++b) cand[(size_t)b * w.cap_C] = entry_;
+    rc = fvdb_scorer_run(w.sc, n, 1);
+    if (rc) return rc;
+    n_dist_ += n;
+    n_hops_ += 1;
+    const float* dbuf = fvdb_scorer_dist_buffer(w.sc);
+    for (uint32_t b = 0; b < n; ++b) w.qs[b].cur.assign(1, Cand{entry_, dbuf[(size_t)b * w.cap_C]});
+    for (uint32_t layer = level_[entry_] + 1; layer-- > 0;) {  // :437-448: ef = 1 above layer 0
+      rc = search_layer(w, n, layer == 0 ? ef : 1, layer);
       if (rc) return rc;
-      ln.lo = o + l * per;
-      ln.n = std::min(per, o + b - ln.lo);
-      ln.k = k;
-      ln.stage = 0;
-      ln.done = false;
-      ln.rc = 0;
-      ln.dists = ln.hops = 0;
-      ln.threads = ln.n >= 32 ? nt : 1;
-      if (ln.qs.size() < ln.n) ln.qs.resize(ln.n);
-      if (ln.cur.size() < ln.n) ln.cur.resize(ln.n);
-      ln.prev_cnt.assign(ln.cap_B, ln.cap_C);  // rows start dirty: cleared on first use
     }
-    uint32_t remaining = 0;
-    for (uint32_t l = 0; l < nl; ++l) {
-      lane_advance(lanes_[l], q, q_on_device, ef, ids, dist, counts);
-      if (!lanes_[l].done) ++remaining;
-    }
-    while (remaining) {
-      for (uint32_t l = 0; l < nl; ++l) {
-        Lane& ln = lanes_[l];
-        if (ln.done) continue;
-        ln.rc = fvdb_scorer_wait(ln.sc);
-        if (ln.rc) {
-          ln.done = true;
-        } else {
-          lane_advance(ln, q, q_on_device, ef, ids, dist, counts);
-        }
-        if (ln.done) --remaining;
+    for (uint32_t b = 0; b < n; ++b) {  // :451-466 filter deleted, take k
+      uint32_t nw = 0;
+      const size_t o = (size_t)(lo + b) * k;
+      for (const Cand& c : w.qs[b].cur) {
+        if (!registered_[c.node] || deleted_[c.node]) continue;
+        if (nw >= k) break;
+        ids[o + nw] = ids_[c.node];
+        dist[o + nw] = c.distance;
+        ++nw;
       }
-    }
-    for (uint32_t l = 0; l < nl; ++l) {
-      n_dist_ += lanes_[l].dists;
-      n_hops_ += lanes_[l].hops;
-      if (lanes_[l].rc) return lanes_[l].rc;
+      counts[lo + b] = nw;
     }
   }
   return FVDB_OK;
@@ -814,15 +600,15 @@ int HNSWIndex::search_host_walk(const float* q, bool q_on_device, uint32_t B, ui
 
 // distances from stored row `base_row` to a list of candidate rows (prune: :588-624)
 int HNSWIndex::score_pairs_from_row(uint32_t base_row, const std::vector<uint32_t>& cands, std::vector<float>& out) {
-  int rc = fvdb_scorer_set_query_rows(scorer_, &base_row, 1);
+  int rc = fvdb_scorer_set_query_rows(insert_walk_.sc, &base_row, 1);
   if (rc) return rc;
-  uint32_t* cand = fvdb_scorer_cand_buffer(scorer_);
+  uint32_t* cand = fvdb_scorer_cand_buffer(insert_walk_.sc);
   for (size_t i = 0; i < cands.size(); ++i) cand[i] = cands[i];
-  rc = fvdb_scorer_run(scorer_, 1, (uint32_t)cands.size());
+  rc = fvdb_scorer_run(insert_walk_.sc, 1, (uint32_t)cands.size());
   if (rc) return rc;
   n_dist_ += cands.size();
   n_hops_ += 1;
-  const float* d = fvdb_scorer_dist_buffer(scorer_);
+  const float* d = fvdb_scorer_dist_buffer(insert_walk_.sc);
   out.assign(d, d + cands.size());
   for (size_t i = 0; i < cands.size(); ++i) cand[i] = FVDB_NO_ROW;
   return FVDB_OK;
@@ -854,10 +640,49 @@ int HNSWIndex::insert(uint64_t id, const float* v, uint32_t dim, int64_t forced_
   return rc ? rc : err;
 }
 
+int HNSWIndex::append_nodes(const uint64_t* ids, const uint32_t* levels, const float* v, uint32_t m, uint32_t* first) {
+  uint64_t first64 = 0;
+  int rc = fvdb_store_append(store_, v, m, &first64);  // the vectors are resident before the graph links to them
+  if (rc) return rc;
+  *first = (uint32_t)first64;
+  host_vecs_.insert(host_vecs_.end(), v, v + (size_t)m * dim_);
+  for (uint32_t j = 0; j < m; ++j) {
+    ids_.push_back(ids[j]);
+    level_.push_back(levels[j]);
+    deleted_.push_back(0);
+    registered_.push_back(0);  // "not yet in the nodes map" while its links are being made (:370)
+    nbrs_.emplace_back(levels[j] + 1);
+  }
+  return FVDB_OK;
+}
+
 void HNSWIndex::finalize_insert(uint32_t row) {  // "nodes.insert(id, node)" (:367-370)
   index_of_[ids_[row]] = row;
   registered_[row] = 1;
   n_registered_ += 1;
+}
+
+template <class L>
+int HNSWIndex::adopt_nodes(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const L* levels) {
+  dim_ = dim;
+  has_dim_ = true;
+  int rc = ensure_store(dim);
+  if (rc) return rc;
+  uint64_t first = 0;
+  rc = fvdb_store_append(store_, v, n, &first);
+  if (rc) return rc;
+  host_vecs_.assign(v, v + n * dim);
+  ids_.assign(ids, ids + n);
+  level_.resize(n);
+  for (uint64_t i = 0; i < n; ++i) level_[i] = levels ? (uint32_t)levels[i] : (uint32_t)assign_level();
+  deleted_.assign(n, 0);
+  registered_.assign(n, 1);
+  n_registered_ = n;
+  index_of_.reserve(n * 2);
+  for (uint64_t i = 0; i < n; ++i) index_of_[ids[i]] = (uint32_t)i;
+  nbrs_.assign(n, {});
+  for (uint64_t i = 0; i < n; ++i) nbrs_[i].resize(level_[i] + 1);
+  return FVDB_OK;
 }
 
 void HNSWIndex::add_insert_stats(const fvdb_graph_insert_stats& st) {
@@ -925,9 +750,11 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
     const auto t_b = now();
     const uint32_t m = (uint32_t)acc.size();
     std::vector<uint32_t> lv(m);
+    std::vector<uint64_t> run_ids(m);
     for (uint32_t j = 0; j < m; ++j) {
       const int64_t f = levels ? levels[acc[j]] : -1;
       lv[j] = f >= 0 ? (uint32_t)f : (uint32_t)assign_level();
+      run_ids[j] = ids[acc[j]];
     }
     // vectors: one upload
     const float* src = v + acc[0] * dim;
@@ -937,18 +764,9 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
       for (uint32_t j = 0; j < m; ++j) std::memcpy(&packed[(size_t)j * dim], v + acc[j] * dim, (size_t)dim * 4);
       src = packed.data();
     }
-    uint64_t first64 = 0;
-    rc = fvdb_store_append(store_, src, m, &first64);
+    uint32_t first = 0;
+    rc = append_nodes(run_ids.data(), lv.data(), src, m, &first);
     if (rc) return finish(rc);
-    const uint32_t first = (uint32_t)first64;
-    host_vecs_.insert(host_vecs_.end(), src, src + (size_t)m * dim);
-    for (uint32_t j = 0; j < m; ++j) {
-      ids_.push_back(ids[acc[j]]);
-      level_.push_back(lv[j]);
-      deleted_.push_back(0);
-      registered_.push_back(0);  // "not yet in the nodes map" while its links are being made (:370)
-      nbrs_.emplace_back(lv[j] + 1);
-    }
     const auto t_c = now();
     rc = fvdb_graph_append_nodes(graph_, first, m, lv.data());
     if (rc) return finish(rc);
@@ -980,18 +798,10 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
         has_entry_ = true;
       }
       if (done < m && st.needs_host) {  // level >= 16 or an on-chip heap outgrown: this node takes the host algorithm
-        const uint32_t row = first + done;
         rc = ensure_host_graph();
         if (rc) return finish(rc);
-        std::vector<std::pair<uint32_t, uint32_t>> touched;
-        rc = link_host(row, &touched);
+        rc = link_and_publish(first + done, true);
         if (rc) return finish(rc);
-        finalize_insert(row);
-        rc = push_lists(touched);
-        if (rc) return finish(rc);
-        rc = fvdb_graph_set_entry(graph_, entry_, row + 1);
-        if (rc) return finish(rc);
-        n_host_inserts_ += 1;
         done += 1;
       } else if (nd == 0 && done < m) {
         return finish(FVDB_E_HIP);  // no progress and no request for the host path: never expected
@@ -1005,8 +815,34 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
   return finish(FVDB_OK);
 }
 
-// rows `touched` (node, layer) -> the device graph
-int HNSWIndex::push_lists(const std::vector<std::pair<uint32_t, uint32_t>>& touched) {
+// one insert by the host algorithm (the other mode; also dims / degree caps the device insert does not take)
+int HNSWIndex::insert_host(uint64_t id, const float* v, uint32_t dim, int64_t forced_level) {
+  int rc = ensure_store(dim);
+  if (rc) return rc;
+  rc = ensure_host_graph();
+  if (rc) return rc;
+  const uint32_t level = forced_level >= 0 ? (uint32_t)forced_level : (uint32_t)assign_level();
+  uint32_t row = 0;
+  rc = append_nodes(&id, &level, v, 1, &row);
+  if (rc) return rc;
+  return link_and_publish(row, false);
+}
+
+int HNSWIndex::link_and_publish(uint32_t row, bool on_device) {
+  std::vector<std::pair<uint32_t, uint32_t>> touched;
+  int rc = link_host(row, &touched);
+  if (rc) return rc;
+  finalize_insert(row);
+  n_host_inserts_ += 1;
+  if (!graph_ || host_ahead_) {  // no device copy that agrees with nbrs_: the next device use installs the whole graph
+    host_ahead_ = true;
+    return FVDB_OK;
+  }
+  // the device copy agrees with nbrs_ up to this insert: patch the rows `touched` (node, layer) into it
+  if (!on_device) {
+    rc = fvdb_graph_append_nodes(graph_, row, 1, &level_[row]);
+    if (rc) return rc;
+  }
   std::vector<uint32_t> nodes, layers, off{0}, flat;
   for (const auto& t : touched) {
     nodes.push_back(t.first);
@@ -1016,40 +852,9 @@ int HNSWIndex::push_lists(const std::vector<std::pair<uint32_t, uint32_t>>& touc
     off.push_back((uint32_t)flat.size());
   }
   if (flat.empty()) flat.push_back(0);
-  return fvdb_graph_set_lists(graph_, (uint32_t)nodes.size(), nodes.data(), layers.data(), off.data(), flat.data());
-}
-
-// one insert by the host algorithm (the other mode; also dims / degree caps the device insert does not take)
-int HNSWIndex::insert_host(uint64_t id, const float* v, uint32_t dim, int64_t forced_level) {
-  int rc = ensure_store(dim);
+  rc = fvdb_graph_set_lists(graph_, (uint32_t)nodes.size(), nodes.data(), layers.data(), off.data(), flat.data());
   if (rc) return rc;
-  rc = ensure_host_graph();
-  if (rc) return rc;
-  const uint32_t level = forced_level >= 0 ? (uint32_t)forced_level : (uint32_t)assign_level();
-  uint32_t row = 0;
-  rc = append_row(v, &row);  // the vector is resident before the graph links to it
-  if (rc) return rc;
-  ids_.push_back(id);
-  level_.push_back(level);
-  deleted_.push_back(0);
-  registered_.push_back(0);  // "not yet in the nodes map" while its links are being made (:370)
-  nbrs_.emplace_back(level + 1);
-  std::vector<std::pair<uint32_t, uint32_t>> touched;
-  rc = link_host(row, &touched);
-  if (rc) return rc;
-  finalize_insert(row);
-  n_host_inserts_ += 1;
-  if (graph_ && !host_ahead_) {  // the device copy agrees with nbrs_ up to this insert: patch the rows it changed
-    rc = fvdb_graph_append_nodes(graph_, row, 1, &level);
-    if (rc) return rc;
-    rc = push_lists(touched);
-    if (rc) return rc;
-    rc = fvdb_graph_set_entry(graph_, entry_, row + 1);
-    if (rc) return rc;
-  } else {
-    host_ahead_ = true;
-  }
-  return FVDB_OK;
+  return fvdb_graph_set_entry(graph_, entry_, row + 1);
 }
 
 int HNSWIndex::link_host(uint32_t row, std::vector<std::pair<uint32_t, uint32_t>>* touched) {
@@ -1067,27 +872,28 @@ int HNSWIndex::link_host(uint32_t row, std::vector<std::pair<uint32_t, uint32_t>
     const uint32_t ep = entry_;
     entry_level = level_[ep];
     const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0) + 1;
-    rc = ensure_scorer(1, maxdeg);
+    Walk& w = insert_walk_;
+    rc = walk_begin(w, 1, maxdeg);
     if (rc) return rc;
     std::vector<float> d0;
     rc = score_pairs_from_row(row, {ep}, d0);  // also loads the new vector as the scorer's query
     if (rc) return rc;
-    std::vector<Cand> current_nearest{{ep, d0[0]}};
+    std::vector<Cand>& res = w.qs[0].cur;  // search_layer's entry going in, its result coming out
+    res.assign(1, Cand{ep, d0[0]});
     const uint32_t search_level = std::min(level, entry_level);
-    std::vector<uint8_t> has1(1, 1);
-    std::vector<std::vector<Cand>> res;
     for (uint32_t lc = search_level + 1; lc-- > 0;) {  // :284-290
-      rc = search_layer_batch(1, {current_nearest[0]}, has1, 1, lc, res);
+      rc = search_layer(w, 1, 1, lc);
       if (rc) return rc;
-      if (!res[0].empty()) current_nearest = res[0];
     }
+    const std::vector<Cand> current_nearest = res;
     for (uint32_t lc = 0; lc <= level; ++lc) {  // :293-362
       const uint32_t m = cap(lc);
       const Cand start = (lc <= search_level && !current_nearest.empty()) ? current_nearest[0] : Cand{ep, d0[0]};
-      rc = search_layer_batch(1, {start}, has1, cfg_.ef_construction, lc, res);
+      res.assign(1, start);
+      rc = search_layer(w, 1, cfg_.ef_construction, lc);
       if (rc) return rc;
       std::vector<uint32_t> chosen;  // select_neighbors :556-558
-      for (size_t i = 0; i < res[0].size() && i < m; ++i) chosen.push_back(res[0][i].node);
+      for (size_t i = 0; i < res.size() && i < m; ++i) chosen.push_back(res[i].node);
       for (uint32_t nbv : chosen) set_insert(nbrs_[row][lc], nbv);
       std::vector<uint32_t> to_prune;
       for (uint32_t nbv : chosen) {
@@ -1111,7 +917,7 @@ int HNSWIndex::link_host(uint32_t row, std::vector<std::pair<uint32_t, uint32_t>
         for (const Cand& c : cs) set_insert(nbrs_[nbv][lc], c.node);
       }
       if (!to_prune.empty()) {  // put the new vector back as the query for the next layer
-        rc = fvdb_scorer_set_query_rows(scorer_, &row, 1);
+        rc = fvdb_scorer_set_query_rows(insert_walk_.sc, &row, 1);
         if (rc) return rc;
       }
     }
@@ -1127,25 +933,10 @@ int HNSWIndex::restore(const uint64_t* ids, const float* v, uint64_t n, uint32_t
                        const uint64_t* nbr_offsets, const uint64_t* nbrs, uint64_t entry_id) {
   if (!ids_.empty()) return FVDB_E_INVALID;
   if (n == 0) return FVDB_OK;
-  dim_ = dim;
-  has_dim_ = true;
-  int rc = ensure_store(dim);
+  int rc = adopt_nodes(ids, v, n, dim, levels);
   if (rc) return rc;
-  uint64_t first = 0;
-  rc = fvdb_store_append(store_, v, n, &first);
-  if (rc) return rc;
-  host_vecs_.assign(v, v + n * dim);
-  ids_.assign(ids, ids + n);
-  level_.assign(levels, levels + n);
-  deleted_.assign(n, 0);
-  registered_.assign(n, 1);
-  n_registered_ = n;
-  index_of_.reserve(n * 2);
-  for (uint64_t i = 0; i < n; ++i) index_of_[ids[i]] = (uint32_t)i;
-  nbrs_.assign(n, {});
   uint64_t slot = 0;
   for (uint64_t i = 0; i < n; ++i) {
-    nbrs_[i].resize(levels[i] + 1);
     for (uint32_t l = 0; l <= levels[i]; ++l, ++slot) {
       auto& s = nbrs_[i][l];
       for (uint64_t e = nbr_offsets[slot]; e < nbr_offsets[slot + 1]; ++e) {
@@ -1231,28 +1022,9 @@ int HNSWIndex::bulk_build(const uint64_t* ids, const float* v, uint64_t n, uint3
     for (uint64_t i = 0; i < n; ++i)
       if (!seen.insert(ids[i]).second) return FVDB_E_DUPLICATE;
   }
-  dim_ = dim;
-  has_dim_ = true;
-  int rc = ensure_store(dim);
+  int rc = adopt_nodes(ids, v, n, dim, levels);
   if (rc) return rc;
-  uint64_t first = 0;
-  rc = fvdb_store_append(store_, v, n, &first);
-  if (rc) return rc;
-  host_vecs_.assign(v, v + n * dim);
-  ids_.assign(ids, ids + n);
-  level_.resize(n);
-  uint32_t maxlevel = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    level_[i] = levels ? (uint32_t)levels[i] : (uint32_t)assign_level();
-    maxlevel = std::max(maxlevel, level_[i]);
-  }
-  deleted_.assign(n, 0);
-  registered_.assign(n, 1);
-  n_registered_ = n;
-  index_of_.reserve(n * 2);
-  for (uint64_t i = 0; i < n; ++i) index_of_[ids[i]] = (uint32_t)i;
-  nbrs_.assign(n, {});
-  for (uint64_t i = 0; i < n; ++i) nbrs_[i].resize(level_[i] + 1);
+  const uint32_t maxlevel = *std::max_element(level_.begin(), level_.end());
   // entry = earliest node carrying the maximum level (what sequential insertion ends with, :372-375)
   for (uint64_t i = 0; i < n; ++i)
     if (level_[i] == maxlevel) {

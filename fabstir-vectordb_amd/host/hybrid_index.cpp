@@ -18,10 +18,9 @@ HybridIndex::HybridIndex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, const HybridConf
 
 HybridIndex::~HybridIndex() {
   for (Slot& sl : slots_) {
-    if (sl.d_hid) fvdb_dev_free(ctx_ivf_, sl.d_hid);  // the other pointers are carved out of these two blocks
-    if (sl.h_hid) fvdb_host_free(ctx_ivf_, sl.h_hid);
+    sl.ivf.release();
     if (sl.ivf_done) fvdb_event_destroy(sl.ivf_done);
-    if (sl.d_q) fvdb_dev_free(ctx_ivf_, sl.d_q);
+    sl.d_q.release();
     if (sl.ivf_ctx && sl.ivf_ctx != ctx_ivf_) fvdb_ctx_destroy(sl.ivf_ctx);
   }
   if (sharded_) fvdb_sharded_destroy(sharded_);
@@ -66,6 +65,35 @@ int HybridIndex::write_lock(std::unique_lock<std::shared_mutex>& w) {
   }
 }
 
+HybridIndex::Lease::Lease(HybridIndex* h_, uint32_t slot, How how) : h(h_) {
+  std::unique_lock<std::mutex> lk(h->slot_mu_);
+  if (slot == kAnyFree) {
+    h->slot_cv_.wait(lk, [&] {
+      for (const Slot& s : h->slots_)
+        if (!s.active) return true;
+      return false;
+    });
+    for (uint32_t i = kSlots; i-- > 0;)  // from the top: the low slots are the ones a pipelining caller names
+      if (!h->slots_[i].active) {
+        slot = i;
+        break;
+      }
+  }
+  Slot& s = h->slots_[slot];
+  if (s.active != (how == kAdopt)) return;
+  s.active = true;
+  sl = &s;
+}
+
+HybridIndex::Lease::~Lease() {
+  if (!sl) return;
+  {
+    std::lock_guard<std::mutex> lk(h->slot_mu_);
+    sl->active = false;
+  }
+  h->slot_cv_.notify_all();
+}
+
 // src/hybrid/core.rs:357-417
 int HybridIndex::insert_with_timestamp(uint64_t id, const float* v, uint32_t dim, double ts, double now,
                                        int64_t level) {
@@ -104,15 +132,11 @@ int HybridIndex::build_recent(const uint64_t* ids, const float* v, uint64_t n, u
   return rc ? rc : err;
 }
 
-// Scale loader: same routing as insert_with_timestamp, but the HNSW part is built in one call (build_recent) and the
-// IVF part is assigned/appended in one GPU pass.  Only valid on an index with no vectors yet.
-int HybridIndex::bulk_insert(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts,
-                             double now) {
-  if (!initialized_) return FVDB_E_NOT_INITIALIZED;
-  std::unique_lock<std::shared_mutex> w(rw_);
-  if (!ts_order_.empty() || busy()) return FVDB_E_INVALID;
-  std::vector<uint64_t> rid, hid;
-  std::vector<float> rv, hv;
+int HybridIndex::bulk_route(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts, double now,
+                            std::vector<uint64_t>& hid, std::vector<float>& hv) {
+  std::vector<uint64_t> rid;
+  std::vector<float> rv;
+  std::vector<Pending> queue;
   for (uint64_t i = 0; i < n; ++i) {
     if (timestamps_.count(ids[i])) return FVDB_E_DUPLICATE;
     timestamps_[ids[i]] = ts[i];
@@ -121,22 +145,35 @@ int HybridIndex::bulk_insert(const uint64_t* ids, const float* v, uint64_t n, ui
     auto& V = to_recent ? rv : hv;
     I.push_back(ids[i]);
     V.insert(V.end(), v + i * dim, v + (i + 1) * dim);
+    if (to_recent) queue.push_back({ids[i], ts[i]});
   }
   ts_order_.assign(ids, ids + n);
-  if (!rid.empty()) {
-    int rc = build_recent(rid.data(), rv.data(), rid.size(), dim);
-    if (rc) return rc;
-    recent_count_ = rid.size();
-    for (uint64_t i = 0; i < n; ++i)
-      if (!ivf_trained_ || age_of(now, ts[i]) < cfg_.recent_threshold_s) {
-        pending_migration_.push_back({ids[i], ts[i]});
-        pending_min_ts_ = std::min(pending_min_ts_, ts[i]);
-      }
+  if (rid.empty()) return FVDB_OK;
+  int rc = build_recent(rid.data(), rv.data(), rid.size(), dim);  // sharded: a replica, every rank builds the same graph
+  if (rc) return rc;
+  recent_count_ = rid.size();
+  for (const Pending& p : queue) {
+    pending_migration_.push_back(p);
+    pending_min_ts_ = std::min(pending_min_ts_, p.ts);
   }
+  return FVDB_OK;
+}
+
+// Scale loader: same routing as insert_with_timestamp, but the HNSW part is built in one call (build_recent) and the
+// IVF part is assigned/appended in one GPU pass.  Only valid on an index with no vectors yet.
+int HybridIndex::bulk_insert(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts,
+                             double now) {
+  if (!initialized_) return FVDB_E_NOT_INITIALIZED;
+  std::unique_lock<std::shared_mutex> w(rw_);
+  if (!ts_order_.empty() || busy()) return FVDB_E_INVALID;
+  std::vector<uint64_t> hid;
+  std::vector<float> hv;
+  int rc = bulk_route(ids, v, n, dim, ts, now, hid, hv);
+  if (rc) return rc;
   if (!hid.empty()) {
     uint64_t ok = 0;
     int err = 0;
-    int rc = historical_->batch_insert(hid.data(), hv.data(), hid.size(), dim, &ok, &err);
+    rc = historical_->batch_insert(hid.data(), hv.data(), hid.size(), dim, &ok, &err);
     if (rc) return rc;
     if (err) return err;
     historical_count_ = ok;
@@ -161,33 +198,35 @@ static void plan_list_owners(const std::vector<uint64_t>& sizes, uint32_t world,
   }
 }
 
+// of the rows (ids, v, cl = the list of each) those whose list `owner` gives to `rank`
+namespace {
+struct Rows {
+  std::vector<uint64_t> ids;
+  std::vector<float> v;
+  std::vector<uint32_t> cl;
+};
+Rows owned_rows(const std::vector<uint64_t>& ids, const std::vector<float>& v, const std::vector<uint32_t>& cl, uint32_t dim,
+                const std::vector<uint32_t>& owner, uint32_t rank) {
+  Rows r;
+  for (size_t i = 0; i < ids.size(); ++i)
+    if (owner[cl[i]] == rank) {
+      r.ids.push_back(ids[i]);
+      r.cl.push_back(cl[i]);
+      r.v.insert(r.v.end(), v.begin() + i * dim, v.begin() + (i + 1) * dim);
+    }
+  return r;
+}
+}  // namespace
+
 int HybridIndex::bulk_insert_sharded(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts,
                                      double now, uint32_t rank, uint32_t world, uint32_t* owner_out) {
   if (!initialized_) return FVDB_E_NOT_INITIALIZED;
   std::unique_lock<std::shared_mutex> w(rw_);
   if (!ts_order_.empty() || world == 0 || rank >= world || busy()) return FVDB_E_INVALID;
-  std::vector<uint64_t> rid, hid;
-  std::vector<float> rv, hv;
-  for (uint64_t i = 0; i < n; ++i) {
-    if (timestamps_.count(ids[i])) return FVDB_E_DUPLICATE;
-    timestamps_[ids[i]] = ts[i];
-    const bool to_recent = !ivf_trained_ || age_of(now, ts[i]) < cfg_.recent_threshold_s;
-    auto& I = to_recent ? rid : hid;
-    auto& V = to_recent ? rv : hv;
-    I.push_back(ids[i]);
-    V.insert(V.end(), v + i * dim, v + (i + 1) * dim);
-  }
-  ts_order_.assign(ids, ids + n);
-  if (!rid.empty()) {  // replicated graph: every rank builds the same one
-    int rc = build_recent(rid.data(), rv.data(), rid.size(), dim);
-    if (rc) return rc;
-    recent_count_ = rid.size();
-    for (uint64_t i = 0; i < n; ++i)
-      if (!ivf_trained_ || age_of(now, ts[i]) < cfg_.recent_threshold_s) {
-        pending_migration_.push_back({ids[i], ts[i]});
-        pending_min_ts_ = std::min(pending_min_ts_, ts[i]);
-      }
-  }
+  std::vector<uint64_t> hid;
+  std::vector<float> hv;
+  int rc = bulk_route(ids, v, n, dim, ts, now, hid, hv);
+  if (rc) return rc;
   shard_rank_ = rank;
   shard_world_ = world;
   if (ivf_trained_) {
@@ -198,7 +237,7 @@ int HybridIndex::bulk_insert_sharded(const uint64_t* ids, const float* v, uint64
   if (!hid.empty()) {
     const uint32_t nlist = historical_->config().n_clusters;
     std::vector<uint32_t> cl(hid.size());
-    int rc = historical_->assign(hv.data(), hid.size(), dim, cl.data());
+    rc = historical_->assign(hv.data(), hid.size(), dim, cl.data());
     if (rc) return rc;
     std::vector<uint64_t> sizes(nlist, 0);
     for (uint32_t c : cl) sizes[c]++;
@@ -207,18 +246,10 @@ int HybridIndex::bulk_insert_sharded(const uint64_t* ids, const float* v, uint64
     shard_owner_ = owner;
     shard_sizes_ = sizes;
     if (owner_out) std::memcpy(owner_out, owner.data(), nlist * sizeof(uint32_t));
-    std::vector<uint64_t> kid;
-    std::vector<float> kv;
-    std::vector<uint32_t> kc;
-    for (size_t i = 0; i < hid.size(); ++i)
-      if (owner[cl[i]] == rank) {
-        kid.push_back(hid[i]);
-        kc.push_back(cl[i]);
-        kv.insert(kv.end(), hv.begin() + i * dim, hv.begin() + (i + 1) * dim);
-      }
+    const Rows mine = owned_rows(hid, hv, cl, dim, owner, rank);
     uint64_t ok = 0;
     int err = 0;
-    rc = historical_->batch_insert_assigned(kid.data(), kv.data(), kid.size(), dim, kc.data(), &ok, &err);
+    rc = historical_->batch_insert_assigned(mine.ids.data(), mine.v.data(), mine.ids.size(), dim, mine.cl.data(), &ok, &err);
     if (rc) return rc;
     if (err) return err;
     rc = fvdb_ivf_set_global_list_sizes(historical_->device(), sizes.data());
@@ -315,20 +346,13 @@ uint64_t HybridIndex::migrate_locked(double threshold_s, double now) {
     // is already in a list of ANOTHER rank cannot be seen here; ids that are still pending were never copied.)
     std::vector<uint32_t> cl(xi.size());
     if (historical_->assign(xv.data(), xi.size(), dim, cl.data())) return 0;
-    std::vector<uint64_t> kid;
-    std::vector<float> kv;
-    std::vector<uint32_t> kc;
-    for (size_t i = 0; i < xi.size(); ++i) {
-      shard_sizes_[cl[i]] += 1;
-      if (shard_owner_[cl[i]] == shard_rank_) {
-        kid.push_back(xi[i]);
-        kc.push_back(cl[i]);
-        kv.insert(kv.end(), xv.begin() + i * dim, xv.begin() + (i + 1) * dim);
-      }
-    }
+    for (uint32_t c : cl) shard_sizes_[c] += 1;
+    const Rows mine = owned_rows(xi, xv, cl, dim, shard_owner_, shard_rank_);
     uint64_t ok = 0;
     int err = 0;
-    if (!kid.empty() && historical_->batch_insert_assigned(kid.data(), kv.data(), kid.size(), dim, kc.data(), &ok, &err)) return 0;
+    if (!mine.ids.empty() &&
+        historical_->batch_insert_assigned(mine.ids.data(), mine.v.data(), mine.ids.size(), dim, mine.cl.data(), &ok, &err))
+      return 0;
     if (fvdb_ivf_set_global_list_sizes(historical_->device(), shard_sizes_.data())) return 0;
     migrated = xi.size();
   } else if (!xi.empty()) {
@@ -385,42 +409,47 @@ static void merge_parts(uint32_t B, uint32_t k, uint32_t rk, uint32_t hk, bool h
 void merge_parts_host(uint32_t B, uint32_t k, uint32_t rk, uint32_t hk, const uint64_t* rid, const float* rd,
                       const uint32_t* rc, const uint64_t* hid, const float* hd, const uint32_t* hc, uint64_t* ids,
                       float* dist, uint32_t* counts) {
-  for (size_t i = 0; i < (size_t)B * k; ++i) {
-    ids[i] = FVDB_NO_ID;
-    dist[i] = __builtin_huge_valf();
-  }
+  fill_empty(ids, dist, counts, B, k);
   merge_parts(B, k, rk, hk, rid != nullptr, rid, rd, rc, hid != nullptr, hid, hd, hc, ids, dist, counts);
+}
+
+int HybridIndex::migrate_if_due(double now, bool in_flight_before) {
+  if (!cfg_.auto_migrate) return FVDB_OK;
+  {
+    std::shared_lock<std::shared_mutex> r(rw_);
+    if (!migration_due(cfg_.recent_threshold_s, now)) return FVDB_OK;
+  }
+  std::unique_lock<std::shared_mutex> w(rw_);  // the reference takes its write locks here too (:621-622)
+  if (!migration_due(cfg_.recent_threshold_s, now)) return FVDB_OK;
+  if (in_flight_before || busy()) return FVDB_E_INVALID;  // the caller collects its batches and searches again
+  migrate_locked(cfg_.recent_threshold_s, now);
+  return FVDB_OK;
 }
 
 // Explicit pair for ONE thread that keeps several batches in flight (bench, pipelined servers).
 int HybridIndex::search_dev_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                                   double now) {
   if (slot >= kSlots) return FVDB_E_INVALID;
-  Slot& sl = slots_[slot];
+  return begin_explicit(slot, q_dev, B, dim, cfg, -1, now);
+}
+
+int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
+                                int shard_mode, double now) {
   bool others = false;
   {
     std::lock_guard<std::mutex> lk(slot_mu_);
-    if (sl.active) return FVDB_E_INVALID;  // the previous batch of this slot was never collected
+    if (slots_[slot].active) return FVDB_E_INVALID;  // the previous batch of this slot was never collected
     others = busy_unlocked();
   }
-  // per-search auto-migration (src/hybrid/core.rs:437-439), before this batch counts as in flight.  A due migration
-  // moves rows between the two indexes (and may grow the list pool) under the batches still in flight: refuse, the
-  // caller collects them and begins again
-  if (initialized_ && B != 0 && cfg.k != 0 && cfg_.auto_migrate) {
-    std::unique_lock<std::shared_mutex> w(rw_);
-    if (migration_due(cfg_.recent_threshold_s, now)) {
-      if (others || busy()) return FVDB_E_INVALID;
-      migrate_locked(cfg_.recent_threshold_s, now);
-    }
-  }
+  // the migration check comes before this batch counts as in flight.  Sharded: `now` is the same on every rank, so every
+  // rank migrates the same rows at the same step — also a rank that has no query of its own in it
+  if (initialized_ && cfg.k != 0 && (B != 0 || shard_mode >= 0))
+    if (int rc = migrate_if_due(now, others)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);  // no mutation is under way while the batch is enqueued
-  {
-    std::lock_guard<std::mutex> lk(slot_mu_);
-    if (sl.active) return FVDB_E_INVALID;
-    sl.active = true;
-  }
-  const int rc = begin_impl(slot, q_dev, B, dim, cfg);
-  return rc;
+  Lease lease(this, slot, Lease::kTake);
+  if (!lease.sl) return FVDB_E_INVALID;
+  lease.hand_over();  // whatever begin_impl returns, the slot stays the caller's until search_dev_end
+  return begin_impl(slot, q_dev, B, dim, cfg, shard_mode);
 }
 
 int HybridIndex::attach_comm(fvdb_comm* comm) {
@@ -434,39 +463,41 @@ int HybridIndex::attach_comm(fvdb_comm* comm) {
   return fvdb_sharded_create(historical_->device(), comm, &sharded_);
 }
 
+HybridIndex::Slice HybridIndex::strong_slice(uint32_t B) const {
+  const uint32_t W = (uint32_t)fvdb_comm_world(comm_), r = (uint32_t)fvdb_comm_rank(comm_);
+  const uint32_t per = (B + W - 1) / W;
+  return {per, std::min(B, r * per), std::min(B, (r + 1) * per)};
+}
+
 uint32_t HybridIndex::sharded_rows(uint32_t B, int mode) const {
   if (!comm_ || mode != FVDB_SHARD_STRONG) return B;
-  const uint32_t W = (uint32_t)fvdb_comm_world(comm_), r = (uint32_t)fvdb_comm_rank(comm_);
-  const uint32_t per = (B + W - 1) / W, lo = std::min(B, r * per), hi = std::min(B, (r + 1) * per);
-  return hi - lo;
+  const Slice s = strong_slice(B);
+  return s.hi - s.lo;
 }
 
 int HybridIndex::search_sharded_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim,
                                       const HybridSearchConfig& cfg, int mode, double now) {
   if (slot >= kSlots || !sharded_ || (mode != FVDB_SHARD_WEAK && mode != FVDB_SHARD_STRONG)) return FVDB_E_INVALID;
-  // per-search auto-migration as in search_dev_begin; `now` is the same on every rank, so every rank migrates the same
-  // rows at the same step (a due migration while batches are in flight is refused: collect first)
-  if (initialized_ && cfg.k != 0 && cfg_.auto_migrate) {
-    bool others;
-    {
-      std::lock_guard<std::mutex> lk(slot_mu_);
-      if (slots_[slot].active) return FVDB_E_INVALID;
-      others = busy_unlocked();
-    }
-    std::unique_lock<std::shared_mutex> w(rw_);
-    if (migration_due(cfg_.recent_threshold_s, now)) {
-      if (others || busy()) return FVDB_E_INVALID;
-      migrate_locked(cfg_.recent_threshold_s, now);
-    }
-  }
-  std::shared_lock<std::shared_mutex> r(rw_);
-  {
-    std::lock_guard<std::mutex> lk(slot_mu_);
-    if (slots_[slot].active) return FVDB_E_INVALID;
-    slots_[slot].active = true;
-  }
-  return begin_impl(slot, q_dev, B, dim, cfg, mode);
+  return begin_explicit(slot, q_dev, B, dim, cfg, mode, now);
 }
+
+// one block per slot for the IVF part's results, [ids R*hk u64 | dist R*hk f32 | counts R u32] -> a single copy
+// (R = rows the IVF part writes: B, or the padded slice length in strong sharded mode)
+namespace {
+struct IvfBlock {
+  uint64_t* ids = nullptr;
+  float* dist = nullptr;
+  uint32_t* counts = nullptr;
+  static uint64_t bytes(uint32_t rows, uint32_t hk) { return (uint64_t)rows * hk * 12 + (uint64_t)rows * 4; }
+  IvfBlock() = default;
+  IvfBlock(void* base, uint32_t rows, uint32_t hk) {
+    const uint64_t need = (uint64_t)rows * hk;
+    ids = (uint64_t*)base;
+    dist = (float*)((char*)base + need * 8);
+    counts = (uint32_t*)((char*)base + need * 12);
+  }
+};
+}  // namespace
 
 // enqueue everything for the batch; the slot is already marked active by the caller
 int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
@@ -478,11 +509,10 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
   const float* q_own = q_dev;
   uint32_t Bown = B, ivf_rows = B;
   if (shard_mode == FVDB_SHARD_STRONG) {
-    const uint32_t W = (uint32_t)fvdb_comm_world(comm_), r = (uint32_t)fvdb_comm_rank(comm_);
-    const uint32_t per = (B + W - 1) / W, lo = std::min(B, r * per), hi = std::min(B, (r + 1) * per);
-    q_own = q_dev + (size_t)lo * dim;
-    Bown = hi - lo;
-    ivf_rows = per;
+    const Slice s = strong_slice(B);
+    q_own = q_dev + (size_t)s.lo * dim;
+    Bown = s.hi - s.lo;
+    ivf_rows = s.per;
   }
   const uint32_t B_ivf_in = B;
   B = Bown;
@@ -502,46 +532,30 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
     sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot);
   }
   if (cfg.search_historical && ivf_trained_) {
-    // one device block and one pinned block per slot: [ids R*hk u64 | dist R*hk f32 | counts R u32] -> a single copy
-    // (R = rows the IVF part writes: B, or the padded slice length in strong sharded mode)
-    const uint64_t need = (uint64_t)ivf_rows * sl.hk;
-    const uint64_t bytes = need * 12 + (uint64_t)ivf_rows * 4;
-    if (bytes > sl.cap) {
-      if (sl.d_hid) fvdb_dev_free(ctx_ivf_, sl.d_hid);
-      if (sl.h_hid) fvdb_host_free(ctx_ivf_, sl.h_hid);
-      sl.d_hid = sl.h_hid = nullptr;
-      sl.cap = 0;
-      if (fvdb_dev_alloc(ctx_ivf_, bytes, &sl.d_hid) || fvdb_host_alloc(ctx_ivf_, bytes, &sl.h_hid)) return FVDB_E_OOM;
-      sl.cap = bytes;
-    }
-    sl.d_hd = (char*)sl.d_hid + need * 8;
-    sl.d_hc = (char*)sl.d_hid + need * 12;
-    sl.h_hd = (char*)sl.h_hid + need * 8;
-    sl.h_hc = (char*)sl.h_hid + need * 12;
+    const uint64_t bytes = IvfBlock::bytes(ivf_rows, sl.hk);
+    if (int rc = sl.ivf.reserve(ctx_ivf_, bytes, true)) return rc;
+    sl.ivf_rows = ivf_rows;
+    const IvfBlock d(sl.ivf.dev, ivf_rows, sl.hk);
     // each slot's IVF chain runs on its own stream with its own scratch set, so the chains of consecutive batches
     // overlap (a chain is ~20 dependent launches with gaps between them)
     static const bool one_stream = getenv("FVDB_IVF_ONE_STREAM") != nullptr;  // tuning aid
-    if (!sl.ivf_ctx) {
-      if (slot == 0 || one_stream) sl.ivf_ctx = ctx_ivf_;
-      else if (fvdb_ctx_create(fvdb_ctx_device(ctx_ivf_), &sl.ivf_ctx)) return FVDB_E_HIP;
-    }
+    if (slot_ctx(ctx_ivf_, slot == 0 || one_stream, &sl.ivf_ctx)) return FVDB_E_HIP;
     fvdb_ctx* on = sl.ivf_ctx == ctx_ivf_ ? nullptr : sl.ivf_ctx;
     if (!sl.ivf_done && fvdb_event_create(sl.ivf_ctx, &sl.ivf_done)) return FVDB_E_HIP;
     if (shard_mode >= 0) {
       // every rank must take part in the step's collectives even when its own slice is empty
       if (dim != historical_->dimension()) return FVDB_E_DIM;
       const int rcs = fvdb_ivf_search_sharded_begin(sharded_, on, on ? slot : 0, q_dev, B_ivf_in, sl.hk,
-                                                    (uint32_t)cfg.ivf_n_probe, shard_mode, (uint64_t*)sl.d_hid,
-                                                    (float*)sl.d_hd, (uint32_t*)sl.d_hc);
+                                                    (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
       if (rcs) return rcs;
       sl.ivf_in_flight = true;
     } else {
-      sl.ivf_in_flight = historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, (uint64_t*)sl.d_hid,
-                                                 (float*)sl.d_hd, (uint32_t*)sl.d_hc, on, on ? slot : 0) == FVDB_OK;
+      sl.ivf_in_flight = historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids, d.dist, d.counts,
+                                                 on, on ? slot : 0) == FVDB_OK;
     }
     if (sl.ivf_in_flight) {
       // result copy rides the slot's stream right behind the chain, then the event
-      if (fvdb_dev_download_async(sl.ivf_ctx, sl.h_hid, sl.d_hid, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, sl.ivf_done))
+      if (fvdb_dev_download_async(sl.ivf_ctx, sl.ivf.host, sl.ivf.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, sl.ivf_done))
         return FVDB_E_HIP;
     }
   }
@@ -550,28 +564,11 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
 
 int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint32_t* counts) {
   if (slot >= kSlots) return FVDB_E_INVALID;
-  Slot& sl = slots_[slot];
-  {
-    std::lock_guard<std::mutex> lk(slot_mu_);
-    if (!sl.active) return FVDB_E_INVALID;
-  }
-  struct Release {  // the slot is free again only when its buffers have been read
-    HybridIndex* h;
-    Slot* sl;
-    ~Release() {
-      {
-        std::lock_guard<std::mutex> lk(h->slot_mu_);
-        sl->active = false;
-      }
-      h->slot_cv_.notify_all();
-    }
-  } release{this, &sl};
+  Lease lease(this, slot, Lease::kAdopt);  // released at return: the slot is free again only when its buffers have been read
+  if (!lease.sl) return FVDB_E_INVALID;
+  Slot& sl = *lease.sl;
   const uint32_t B = sl.B, k = sl.k;
-  for (uint32_t b = 0; b < B; ++b) counts[b] = 0;
-  for (size_t i = 0; i < (size_t)B * k; ++i) {
-    ids[i] = FVDB_NO_ID;
-    dist[i] = __builtin_huge_valf();
-  }
+  fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   std::vector<uint64_t> rid;
   std::vector<float> rd;
@@ -585,8 +582,10 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
                   : recent_->search_dev(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data());
     have_r = rc2 == FVDB_OK;
   }
+  IvfBlock h;
   if (sl.ivf_in_flight) {
     have_h = fvdb_event_wait(sl.ivf_ctx, sl.ivf_done) == FVDB_OK;
+    h = IvfBlock(sl.ivf.host, sl.ivf_rows, sl.hk);
     bool others = false;
     {
       std::lock_guard<std::mutex> lk(slot_mu_);
@@ -594,102 +593,42 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
     }
     if (!others) fvdb_ivf_profile_collect(historical_->device());  // stage timing only makes sense one batch at a time
   }
-  merge_parts(B, k, sl.rk, sl.hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, (const uint64_t*)sl.h_hid,
-              (const float*)sl.h_hd, (const uint32_t*)sl.h_hc, ids, dist, counts);
+  merge_parts(B, k, sl.rk, sl.hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, h.ids, h.dist, h.counts, ids, dist,
+              counts);
   return FVDB_OK;
 }
 
-// The blocking entry points: any number of host threads.  A call holds the read side of rw_ from its migration
+// The blocking entry points: any number of host threads.  A call holds the read side of rw_ from after its migration
 // check to its merge and works in a slot leased for its duration.
 int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                              double now, uint64_t* ids, float* dist, uint32_t* counts) {
   const uint32_t k = (uint32_t)cfg.k;
-  for (uint32_t b = 0; b < B; ++b) counts[b] = 0;
-  for (size_t i = 0; i < (size_t)B * k; ++i) {
-    ids[i] = FVDB_NO_ID;
-    dist[i] = __builtin_huge_valf();
-  }
+  fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
-  if (cfg_.auto_migrate) {  // src/hybrid/core.rs:437-439; the reference takes its write locks here too (:621-622)
-    bool due;
-    {
-      std::shared_lock<std::shared_mutex> r(rw_);
-      due = migration_due(cfg_.recent_threshold_s, now);
-    }
-    if (due) {
-      std::unique_lock<std::shared_mutex> w(rw_);
-      if (migration_due(cfg_.recent_threshold_s, now)) {
-        if (busy()) return FVDB_E_INVALID;  // batches begun with search_dev_begin are still uncollected
-        migrate_locked(cfg_.recent_threshold_s, now);
-      }
-    }
-  }
+  if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);
-  uint32_t slot = 0;
-  {
-    std::unique_lock<std::mutex> lk(slot_mu_);
-    slot_cv_.wait(lk, [&] {
-      for (const Slot& s : slots_)
-        if (!s.active) return true;
-      return false;
-    });
-    for (uint32_t i = kSlots; i-- > 0;)  // from the top: the low slots are the ones a pipelining caller names
-      if (!slots_[i].active) {
-        slot = i;
-        break;
-      }
-    slots_[slot].active = true;
-  }
-  Slot& sl = slots_[slot];
-  auto give_back = [&]() {
-    {
-      std::lock_guard<std::mutex> lk(slot_mu_);
-      sl.active = false;
-    }
-    slot_cv_.notify_all();
-  };
+  Lease lease(this, Lease::kAnyFree, Lease::kTake);  // given back at every return, until search_dev_end takes it over
+  Slot& sl = *lease.sl;
+  const uint32_t slot = lease.index();
   const float* qd = q;
   if (!q_on_device) {  // stage the batch in HBM once; both parts read it from there
     const uint64_t bytes = (uint64_t)B * dim * 4;
-    if (bytes > sl.d_q_cap) {
-      if (sl.d_q) fvdb_dev_free(ctx_ivf_, sl.d_q);
-      sl.d_q = nullptr;
-      sl.d_q_cap = 0;
-      if (fvdb_dev_alloc(ctx_ivf_, bytes, &sl.d_q)) {
-        give_back();
-        return FVDB_E_OOM;
-      }
-      sl.d_q_cap = bytes;
-    }
-    if (!sl.ivf_ctx) {
-      if (slot == 0) sl.ivf_ctx = ctx_ivf_;
-      else if (fvdb_ctx_create(fvdb_ctx_device(ctx_ivf_), &sl.ivf_ctx)) {
-        give_back();
-        return FVDB_E_HIP;
-      }
-    }
+    if (int rc = sl.d_q.reserve(ctx_ivf_, bytes, false)) return rc;
+    if (slot_ctx(ctx_ivf_, slot == 0, &sl.ivf_ctx)) return FVDB_E_HIP;
     for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
-      if (!(q[i] - q[i] == 0.0f)) {  // NaN / Inf: the reference panics in partial_cmp().unwrap()
-        give_back();
-        return FVDB_E_NONFINITE;
-      }
-    const int rcu = fvdb_dev_upload(sl.ivf_ctx, sl.d_q, q, bytes);  // waits on the slot's own stream only
-    if (rcu) {
-      give_back();
-      return rcu;
-    }
-    qd = (const float*)sl.d_q;
+      if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;  // NaN / Inf: the reference panics in partial_cmp().unwrap()
+    const int rcu = fvdb_dev_upload(sl.ivf_ctx, sl.d_q.dev, q, bytes);  // waits on the slot's own stream only
+    if (rcu) return rcu;
+    qd = (const float*)sl.d_q.dev;
   }
   const int rc0 = begin_impl(slot, qd, B, dim, cfg);
-  if (rc0) {
-    if (sl.hnsw_in_flight || sl.ivf_in_flight) {  // drain what was enqueued before the failure
-      std::vector<uint64_t> ti((size_t)B * k);
-      std::vector<float> td((size_t)B * k);
-      std::vector<uint32_t> tc(B);
-      (void)search_dev_end(slot, ti.data(), td.data(), tc.data());
-    } else {
-      give_back();
-    }
+  if (rc0 && !sl.hnsw_in_flight && !sl.ivf_in_flight) return rc0;
+  lease.hand_over();
+  if (rc0) {  // drain what was enqueued before the failure
+    std::vector<uint64_t> ti((size_t)B * k);
+    std::vector<float> td((size_t)B * k);
+    std::vector<uint32_t> tc(B);
+    (void)search_dev_end(slot, ti.data(), td.data(), tc.data());
     return rc0;
   }
   return search_dev_end(slot, ids, dist, counts);

@@ -187,6 +187,31 @@ def test_device_traversal_equals_host_walk_and_oracle(fv, ctx):
     assert gh.device_fallbacks() == 0
 
 
+def test_host_walk_of_more_queries_than_one_chunk(fv, ctx):
+    # the host walk takes a batch in chunks of 16384 queries: a batch that crosses the boundary, against the device
+    # traversal for every row and against the oracle for the rows around the boundary and the last ones
+    n, d, B = 700, 8, 16384 + 300
+    x = mixture(n, d, n_comp=4, sigma=1.0, seed=71)
+    ids = np.arange(n, dtype=np.uint64) * 3 + 1
+    gh = fv.HNSWIndex(ctx, 8, 16, 60, seed=3)
+    gh.bulk_build(ids, x)
+    gi, lv, off, nb = gh.export_graph()
+    oh = orc.HNSWIndex(8, 16, 60, seed=3)
+    oh.restore(gi, x, lv, off, nb, gh.entry_point())
+    q = mixture(B, d, n_comp=4, sigma=1.2, seed=72)
+    k, ef = 5, 20
+    dev = gh.search(q, k, ef)
+    gh.set_device_traversal(False)
+    host = gh.search(q, k, ef)
+    gh.set_device_traversal(True)
+    assert np.array_equal(dev.counts, host.counts) and np.array_equal(dev.ids, host.ids)
+    assert np.array_equal(bits(dev.distances), bits(host.distances))
+    rows = np.r_[0:4, 16380:16390, B - 4:B]
+    oi, od, oc = oh.batch_search(q[rows], k, ef)
+    assert np.array_equal(host.counts[rows], oc) and np.array_equal(host.ids[rows], oi)
+    assert np.array_equal(bits(host.distances[rows]), bits(od))
+
+
 def test_device_traversal_duplicate_vectors_tie_order(fv, ctx):
     # exact distance ties exercise the restated BinaryHeap order inside the kernel
     d = 6
