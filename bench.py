@@ -7,7 +7,11 @@ through HybridIndex's search (IVF coarse + list scan + top-k and the whole HNSW 
 stable merge on the host).  Query batches are resident in HBM before the timed region starts; every step's results are
 complete, in host memory, inside it (the reference API returns them to the caller).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does what the headline figure needs and no more: it builds the index, finds the operating point, warms up,
+times the K steps and prints the result line (25 s at the default size, 20 s of them the graph's sequential build).
+--full adds everything else the benchmark measures or checks (below), after the timed steps, whose figure it leaves
+as it is; the CPU oracle's share makes such a run 9 to 13 s longer.
 --dump-outputs writes the results of the last of the K timed steps to DIR/{ids,distances,counts}.npy.  Data and queries
 are functions of the arguments alone; the operating point is too once --nprobe and --ef are given (left at 0 it is chosen
 by the recall the build under test reaches), so pin both when the dumps of two builds are to be compared.
@@ -18,18 +22,22 @@ carries the 128-byte RCCL id to the ranks and implements the barrier / max-over-
 --scaling weak (default): every rank brings its own batch per step (global batch N x 1024); strong: the global batch
 stays 1024, every rank produces the results of its slice.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's config.
+With --full five more of its entries are measured, which are null otherwise.  Two in config, host_collect_merge_ms_per_step
+and other_traversal_mode, take a few more steps after the timed ones.  The others are objects of their own:
 "roofline" — the dominant kernel (the graph traversal) against the HBM roofline, with the list scan as a second entry,
-durations measured live with HIP events on the launch streams; and "cpu_baseline" — the CPU oracle (the reference
+durations measured live with HIP events on the launch streams; "cpu_baseline" — the CPU oracle (the reference
 algorithm restated) timed on this box's host cores on a bounded sample of the same queries (checker/baseline only,
-never the product path).  --supplementary adds the two side workloads described in DESIGN.md (isotropic-384 IVF,
-sequential-insert hybrid); their outputs are committed under profiles/.
+never the product path); and "insert_path" — fresh rows inserted into the benchmark's graph by the GPU and by that oracle.
+--config c2|c5 keep their roofline and cpu_baseline behind --full in the same way.  --supplementary adds the two side
+workloads described in DESIGN.md (isotropic-384 IVF, sequential-insert hybrid); their outputs are committed under profiles/.
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -68,6 +76,18 @@ class Generator:
         if self.ambient:
             x += np.float32(self.ambient) * r.standard_normal((n, self.d), dtype=np.float32)
         return np.ascontiguousarray(x, dtype=np.float32)
+
+    def chunks(self, n, chunk):
+        """The n x d data set: rows c .. c + chunk are rows(chunk, stream=c // chunk).  Every chunk has a stream of its
+        own, so the chunks are drawn on all the CPUs this process may use; the array does not depend on how many."""
+        x = np.empty((n, self.d), np.float32)
+
+        def fill(c):
+            x[c:c + chunk] = self.rows(min(chunk, n - c), stream=c // chunk)
+
+        with ThreadPoolExecutor(usable_cpus()) as pool:
+            list(pool.map(fill, range(0, n, chunk)))
+        return x
 
 
 class IsotropicGenerator:
@@ -162,6 +182,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the results of the last timed step to DIR/{ids,distances,counts}.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check the rest as well: host share of a step, per-kernel times and "
+                         "roofline, the other traversal mode, the CPU oracle's baseline and the insert path (module docstring)")
     ap.add_argument("--n-vectors", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=384)
     ap.add_argument("--batch", type=int, default=1024)
@@ -175,8 +198,8 @@ def main():
     ap.add_argument("--query-batches", type=int, default=16, help="distinct query batches cycled through the steps")
     ap.add_argument("--select-batches", type=int, default=4,
                     help="batches the operating point is chosen on; the rest are held out and must confirm it")
-    ap.add_argument("--cpu-sample", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="--full: queries the CPU oracle is timed and checked on")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle (cpu_baseline, insert_path)")
     ap.add_argument("--hnsw-traversal", choices=["device", "host"], default="device",
                     help="device: the layered walk runs on the GPU (one launch per batch); host: on the host with one "
                          "candidate-scoring launch per hop (the north_star's split).  Identical results.")
@@ -184,8 +207,8 @@ def main():
                     help="sequential: the reference's own build — HNSWIndex::insert in id order (src/hnsw/core.rs:226-378), "
                          "device-resident; bulk: exact nearest-M per layer (an extension: another graph)")
     ap.add_argument("--insert-sample", type=int, default=2048,
-                    help="inserts timed on GPU and CPU oracle at the full graph size for the insert_path object (0 = skip)")
-    ap.add_argument("--compare-host-walk", type=int, default=3, help="extra steps timed with the host walk (0 = skip)")
+                    help="--full: inserts timed on GPU and CPU oracle at the full graph size for the insert_path object (0 = skip)")
+    ap.add_argument("--compare-host-walk", type=int, default=3, help="--full: extra steps timed with the host walk (0 = skip)")
     ap.add_argument("--parts", choices=["both", "recent", "historical"], default="both",
                     help="development aid: time only the HNSW or only the IVF part of the hybrid search (recall is then meaningless)")
     ap.add_argument("--in-flight", type=int, default=8,
@@ -245,9 +268,7 @@ def main():
     t_setup = time.time()
     gen = Generator(d=d, latent=args.latent, spread=args.spread)
     chunk = 10_000  # the reference's storage chunk (src/hybrid/persistence.rs:189) = our generation/insert unit
-    x = np.empty((N, d), np.float32)
-    for c in range(0, N, chunk):
-        x[c:c + chunk] = gen.rows(min(chunk, N - c), stream=c // chunk)
+    x = gen.chunks(N, chunk)
     ids = np.arange(N, dtype=np.uint64)
     r = np.random.Generator(np.random.Philox(key=99))
     is_recent = r.random(N) < args.recent_frac
@@ -430,52 +451,52 @@ def main():
         elapsed = float(tt.item())
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, last.ids, last.distances, last.counts, rank, world)
-    # host share of a step: collect + translate + merge of batches whose GPU work is already complete
-    host_collect_ms = None
-    if depth > 1:
-        for i in range(depth):
-            begin(i, i)
-        sync_all()
-        th = time.perf_counter()
-        for i in range(depth):
-            end(i)
-        host_collect_ms = (time.perf_counter() - th) / depth * 1e3
-        log(f"host collect+merge with the GPU work already done: {host_collect_ms:.3f} ms per step")
-    hnsw.graph_kernel_times()  # launches of the timed region overlap each other: per-launch durations are taken below
-    # per-kernel / per-stage timing: a few more steps, ONE batch at a time (with several batches in flight the launches
-    # of different batches overlap and stretch each other, and one chain's events would be overwritten by the next)
-    hyb.ivf_device_stage_times()
-    n_solo = 8
-    for i in range(n_solo):
-        run(i, nprobe, ef)
-    graph_ms_sum, graph_launches, graph_rows, graph_hops = hnsw.graph_kernel_times()
-    # and the traversal with the card to itself (no list-scan chain beside it): the kernel's own latency-bound time
-    graph_alone_ms = None
-    if world == 1 and args.hnsw_traversal == "device":
+    host_collect_ms = other = None
+    if args.full:
+        # host share of a step: collect + translate + merge of batches whose GPU work is already complete
+        if depth > 1:
+            for i in range(depth):
+                begin(i, i)
+            sync_all()
+            th = time.perf_counter()
+            for i in range(depth):
+                end(i)
+            host_collect_ms = (time.perf_counter() - th) / depth * 1e3
+            log(f"host collect+merge with the GPU work already done: {host_collect_ms:.3f} ms per step")
+        hnsw.graph_kernel_times()  # launches of the timed region overlap each other: per-launch durations are taken below
+        # per-kernel / per-stage timing: a few more steps, ONE batch at a time (with several batches in flight the launches
+        # of different batches overlap and stretch each other, and one chain's events would be overwritten by the next)
+        hyb.ivf_device_stage_times()
+        n_solo = 8
         for i in range(n_solo):
-            hnsw.search_dev(qdev[i % nb], B, d, k, ef)
-        ms_a, n_a, _, _ = hnsw.graph_kernel_times()
-        graph_alone_ms = ms_a / max(n_a, 1)
+            run(i, nprobe, ef)
+        graph_ms_sum, graph_launches, graph_rows, graph_hops = hnsw.graph_kernel_times()
+        # and the traversal with the card to itself (no list-scan chain beside it): the kernel's own latency-bound time
+        graph_alone_ms = None
+        if world == 1 and args.hnsw_traversal == "device":
+            for i in range(n_solo):
+                hnsw.search_dev(qdev[i % nb], B, d, k, ef)
+            ms_a, n_a, _, _ = hnsw.graph_kernel_times()
+            graph_alone_ms = ms_a / max(n_a, 1)
     ctx_ivf.set_profiling(0)
     ctx_hnsw.set_profiling(0)
-    n_prof, stage = hyb.ivf_device_stage_times()
-    stats = hyb.ivf_device_last_stats()
-
-    # the same workload with the other traversal mode (reported next to the headline value)
-    other = None
-    if args.compare_host_walk > 0 and world == 1:
-        hnsw.set_device_traversal(args.hnsw_traversal != "device")
-        run(0, nprobe, ef)
-        ctx_ivf.device_synchronize()
-        t1 = time.perf_counter()
-        for i in range(args.compare_host_walk):
-            run(i, nprobe, ef)
-        ctx_ivf.device_synchronize()
-        dt = (time.perf_counter() - t1) / args.compare_host_walk
-        other = {"hnsw_traversal": "host" if args.hnsw_traversal == "device" else "device",
-                 "value": round(B / dt, 1), "ms_per_step": round(dt * 1e3, 4), "steps": args.compare_host_walk}
-        hnsw.set_device_traversal(args.hnsw_traversal == "device")
-        log(f"other traversal mode ({other['hnsw_traversal']}): {other['ms_per_step']} ms/step, {other['value']:.0f} QPS")
+    if args.full:
+        n_prof, stage = hyb.ivf_device_stage_times()
+        stats = hyb.ivf_device_last_stats()
+        # the same workload with the other traversal mode (reported next to the headline value)
+        if args.compare_host_walk > 0 and world == 1:
+            hnsw.set_device_traversal(args.hnsw_traversal != "device")
+            run(0, nprobe, ef)
+            ctx_ivf.device_synchronize()
+            t1 = time.perf_counter()
+            for i in range(args.compare_host_walk):
+                run(i, nprobe, ef)
+            ctx_ivf.device_synchronize()
+            dt = (time.perf_counter() - t1) / args.compare_host_walk
+            other = {"hnsw_traversal": "host" if args.hnsw_traversal == "device" else "device",
+                     "value": round(B / dt, 1), "ms_per_step": round(dt * 1e3, 4), "steps": args.compare_host_walk}
+            hnsw.set_device_traversal(args.hnsw_traversal == "device")
+            log(f"other traversal mode ({other['hnsw_traversal']}): {other['ms_per_step']} ms/step, {other['value']:.0f} QPS")
 
     recall = float(np.mean([recall_of(i, nprobe, ef) for i in range(nb)]))
     global_batch = B if strong else world * B
@@ -483,15 +504,16 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     log(f"{args.steps} steps: {ms_per_step:.3f} ms/step, {qps:.0f} QPS, recall@{k}={recall:.4f}")
 
-    roofline = build_roofline(args, d, B, hi - lo, world, stage, n_prof, stats, graph_ms_sum, graph_launches, graph_rows,
-                              graph_hops, ms_per_step)
-    if graph_alone_ms:
-        roofline["kernel_ms_alone"] = round(graph_alone_ms, 4)
-        roofline["frac_alone"] = round(roofline["bytes_per_launch"] / (graph_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+    roofline = cpu = ins = None
+    if args.full:
+        roofline = build_roofline(args, d, B, hi - lo, world, stage, n_prof, stats, graph_ms_sum, graph_launches, graph_rows,
+                                  graph_hops, ms_per_step)
+        if graph_alone_ms:
+            roofline["kernel_ms_alone"] = round(graph_alone_ms, 4)
+            roofline["frac_alone"] = round(roofline["bytes_per_launch"] / (graph_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
 
     # ---- CPU baseline: the oracle (reference algorithm restated) on the same structures ----
-    cpu = ins = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu, oracle_hyb = cpu_baseline(fv, hyb, x, ids, is_recent, now, queries[0], run(0, nprobe, ef), k, nprobe, ef, args)
         if args.insert_sample > 0:  # last: it grows the graph
             ins = insert_path(hyb, oracle_hyb, gen, N, args.insert_sample, graph_build_s, args)
@@ -667,9 +689,7 @@ def run_ivf_config(args):
     os.dup2(2, 1)
     t0 = time.time()
     gen = Generator(d=d, latent=args.latent, spread=args.spread)
-    x = np.empty((N, d), np.float32)
-    for c in range(0, N, 10_000):
-        x[c:c + 10_000] = gen.rows(min(10_000, N - c), stream=c // 10_000)
+    x = gen.chunks(N, 10_000)
     ids = np.arange(N, dtype=np.uint64)
     nb = max(1, min(args.query_batches, 8))
     queries = [gen.rows(B, stream=10_000_000 + i) for i in range(nb)]
@@ -721,36 +741,37 @@ def run_ivf_config(args):
     log(f"{args.steps} steps: {ms_per_step:.3f} ms/step, {qps:.0f} QPS, recall@{k}={recall:.4f}, rescans {ivf.scan_fallbacks() - f0}")
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, *result((args.steps - 1) % depth))
-    # per-stage / per-kernel durations, one batch at a time (HIP events on the launch stream)
-    ctx.set_profiling(1)
-    ivf.stage_times()
-    n_solo = 8
-    for i in range(n_solo):
-        ctx.check(lib.fvdb_ivf_search_dev(h, qdev[i % nb], B, k, nprobe, outs[0][0], outs[0][1], outs[0][2], None))
-    ctx.synchronize()
-    n_prof, stage = ivf.stage_times()
-    ctx.set_profiling(0)
-    st = ivf.last_stats()
-    esz = 2 if (cfg["dtype"] == "f16" or stage.get("mfma_filter_kernel", 0.0) > 0.0) else 4
-    mfma_path = stage.get("mfma_filter_kernel", 0.0) > 0.0
-    scan_ms = (stage["mfma_filter_kernel"] if mfma_path else stage["fine_scan"]) / max(n_prof, 1)
-    phys = st["list_rows_touched"] * d * esz
-    flops = 2.0 * st["rows_scanned"] * d
-    t_b, t_f = phys / (HBM_PEAK_GBPS * 1e9), (flops / (MFMA_F16_PEAK_TFLOPS * 1e12) if mfma_path else 0.0)
-    frac = max(t_b, t_f) / (scan_ms * 1e-3) if scan_ms > 0 else 0.0
-    roofline = {"bound": "hbm" if t_b >= t_f else "mfma", "achieved": round(phys / (scan_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s", "frac": round(frac, 4), "traffic": None,
-                "kernel": "fvdb::scan_mfma_wg_kernel (IVF list scan: fp16 MFMA filter over every probed row)" if mfma_path
-                          else "fvdb::scan_topk_kernel (IVF list scan, exact)",
-                "kernel_ms": round(scan_ms, 4), "physical_lower_bound_bytes": int(phys), "useful_flops": int(flops),
-                "algorithmic_bytes_per_launch_survey_8d": int(st["rows_scanned"] * d * (2 if cfg["dtype"] == "f16" else 4)),
-                "rows_scanned_per_query": round(st["rows_scanned"] / B, 1),
-                "stage_ms": {k_: round(v / max(n_prof, 1), 4) for k_, v in stage.items()},
-                "note": "achieved = every probed list streamed once per launch (fp16 rows / fp16 mirror) / the filter kernel's "
-                        "duration (HIP events, one batch at a time); SURVEY 8d's per-query bytes are shared by the queries probing a list"}
-    assert 0.0 <= roofline["frac"] <= 1.0
-    cpu = None
-    if not args.no_cpu_baseline:
+    roofline = cpu = None
+    if args.full:
+        # per-stage / per-kernel durations, one batch at a time (HIP events on the launch stream)
+        ctx.set_profiling(1)
+        ivf.stage_times()
+        n_solo = 8
+        for i in range(n_solo):
+            ctx.check(lib.fvdb_ivf_search_dev(h, qdev[i % nb], B, k, nprobe, outs[0][0], outs[0][1], outs[0][2], None))
+        ctx.synchronize()
+        n_prof, stage = ivf.stage_times()
+        ctx.set_profiling(0)
+        st = ivf.last_stats()
+        esz = 2 if (cfg["dtype"] == "f16" or stage.get("mfma_filter_kernel", 0.0) > 0.0) else 4
+        mfma_path = stage.get("mfma_filter_kernel", 0.0) > 0.0
+        scan_ms = (stage["mfma_filter_kernel"] if mfma_path else stage["fine_scan"]) / max(n_prof, 1)
+        phys = st["list_rows_touched"] * d * esz
+        flops = 2.0 * st["rows_scanned"] * d
+        t_b, t_f = phys / (HBM_PEAK_GBPS * 1e9), (flops / (MFMA_F16_PEAK_TFLOPS * 1e12) if mfma_path else 0.0)
+        frac = max(t_b, t_f) / (scan_ms * 1e-3) if scan_ms > 0 else 0.0
+        roofline = {"bound": "hbm" if t_b >= t_f else "mfma", "achieved": round(phys / (scan_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s", "frac": round(frac, 4), "traffic": None,
+                    "kernel": "fvdb::scan_mfma_wg_kernel (IVF list scan: fp16 MFMA filter over every probed row)" if mfma_path
+                              else "fvdb::scan_topk_kernel (IVF list scan, exact)",
+                    "kernel_ms": round(scan_ms, 4), "physical_lower_bound_bytes": int(phys), "useful_flops": int(flops),
+                    "algorithmic_bytes_per_launch_survey_8d": int(st["rows_scanned"] * d * (2 if cfg["dtype"] == "f16" else 4)),
+                    "rows_scanned_per_query": round(st["rows_scanned"] / B, 1),
+                    "stage_ms": {k_: round(v / max(n_prof, 1), 4) for k_, v in stage.items()},
+                    "note": "achieved = every probed list streamed once per launch (fp16 rows / fp16 mirror) / the filter kernel's "
+                            "duration (HIP events, one batch at a time); SURVEY 8d's per-query bytes are shared by the queries probing a list"}
+        assert 0.0 <= roofline["frac"] <= 1.0
+    if args.full and not args.no_cpu_baseline:
         import oracle as orc
         orc.build()
         t2 = time.time()

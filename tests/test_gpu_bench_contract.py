@@ -1,6 +1,7 @@
 """The driver-facing contract of bench.py, on a small workload: stdout carries exactly ONE JSON line with the agreed
-keys, `roofline` and `cpu_baseline` objects included, the roofline fraction is a fraction, and the GPU answers of the
-sample equal the oracle's; --dump-outputs leaves the results of the last timed step, whichever way the steps ran."""
+keys; with --full the `roofline` and `cpu_baseline` objects are included, the roofline fraction is a fraction, and the
+GPU answers of the sample equal the oracle's, while a plain run measures its steps and leaves those entries null;
+--dump-outputs leaves the results of the last timed step, whichever way the steps ran."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     shape = [sys.executable, os.path.join(ROOT, "bench.py"), "--n-vectors", "60000", "--nlist", "64", "--steps", "6",
              "--warmup", "1", "--query-batches", "4", "--train-sample", "20000", "--batch", "256"]
-    cmd = shape + ["--select-batches", "2", "--cpu-sample", "64", "--compare-host-walk", "1", "--insert-sample", "256",
+    cmd = shape + ["--full", "--select-batches", "2", "--cpu-sample", "64", "--compare-host-walk", "1", "--insert-sample", "256",
                    "--dump-outputs", str(tmp_path / "pipelined")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -69,13 +70,25 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     exact = np.argsort(d2, axis=1)[:, :10]
     assert bench.recall_at_k(ids.astype(np.int64), cnt.astype(np.int64), exact, 10) >= 0.9
     # the same step collected one batch at a time (search_dev instead of search_dev_begin / _end), at the operating
-    # point the first run chose: the same arrays
+    # point the first run chose, in a plain run: the same arrays
     one = shape + ["--in-flight", "1", "--nprobe", str(j["config"]["nprobe"]), "--ef", str(j["config"]["hnsw_ef"]),
-                   "--no-cpu-baseline", "--compare-host-walk", "0", "--insert-sample", "0", "--dump-outputs", str(tmp_path / "one")]
+                   "--dump-outputs", str(tmp_path / "one")]
     p = subprocess.run(one, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     for n, a in (("ids", ids), ("distances", dist), ("counts", cnt)):
         assert np.array_equal(np.load(tmp_path / "one" / f"{n}.npy"), a), n
+    # and the plain run's line: the headline entries of the first run, and nothing that takes steps or runs of its own
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[:2000]
+    plain = json.loads(lines[0])
+    for key in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert plain[key] == j[key], key
+    assert plain["value"] > 0 and abs(plain["value"] - 256 * 6 / (plain["ms_per_step"] * 6 / 1e3)) / plain["value"] < 0.02
+    assert plain["config"]["recall_at_10"] == j["config"]["recall_at_10"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["insert_path"] is None
+    assert plain["config"]["other_traversal_mode"] is None and j["config"]["other_traversal_mode"]["steps"] == 1
+    assert plain["config"]["host_collect_merge_ms_per_step"] is None
+    assert not [w for w in ("cpu baseline", "insert path", "other traversal mode") if w in p.stderr]
 
 
 def test_dump_outputs_takes_rows_with_fewer_than_k_hits(tmp_path):

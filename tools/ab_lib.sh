@@ -6,8 +6,8 @@ mkdir -p gpurun_out/ab
 for spec in "$@"; do
   name=${spec%%=*}; rest=${spec#*=}; envs=""
   [[ "$rest" == *@* ]] && envs=$(echo "${rest#*@}" | tr ',' ' ') && rest=${rest%%@*}
-  v=${rest%%:*}; flags=""
-  [[ "$rest" == *:* ]] && flags=${rest#*:}
+  v=${rest%%:*}; flags="--full"  # the stage times printed below
+  [[ "$rest" == *:* ]] && flags="--full ${rest#*:}"
   cp fabstir-vectordb_amd/lib_variants/libfvdb_hip_$v.so fabstir-vectordb_amd/lib/libfvdb_hip.so
   env $envs python bench.py --steps 100 --warmup 3 --nprobe 32 --ef 50 --no-cpu-baseline --compare-host-walk 0 --query-batches 8 $flags > gpurun_out/ab/$name.json 2> gpurun_out/ab/$name.log
   python - <<PY

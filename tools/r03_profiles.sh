@@ -3,9 +3,9 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03
 mkdir -p $O
-echo "== default bench (the driver's command)"; python3 bench.py > $O/bench_c3_default.json 2> $O/bench_c3_default.log; tail -n 4 $O/bench_c3_default.log | cut -c1-300
-echo "== c2 / c5"; python3 bench.py --config c2 > $O/bench_c2.json 2> $O/bench_c2.log; tail -n 2 $O/bench_c2.log | cut -c1-200
-python3 bench.py --config c5 > $O/bench_c5.json 2> $O/bench_c5.log; tail -n 2 $O/bench_c5.log | cut -c1-200
+echo "== default bench, everything measured"; python3 bench.py --full > $O/bench_c3_default.json 2> $O/bench_c3_default.log; tail -n 4 $O/bench_c3_default.log | cut -c1-300
+echo "== c2 / c5"; python3 bench.py --config c2 --full > $O/bench_c2.json 2> $O/bench_c2.log; tail -n 2 $O/bench_c2.log | cut -c1-200
+python3 bench.py --config c5 --full > $O/bench_c5.json 2> $O/bench_c5.log; tail -n 2 $O/bench_c5.log | cut -c1-200
 echo "== rocprofv3 kernel trace of the bench command, 8 batches in flight"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace8 -o bench -- python3 bench.py --no-cpu-baseline --compare-host-walk 0 --insert-sample 0 > $O/bench_in_flight_8_under_rocprof.json 2> $O/bench_in_flight_8_under_rocprof.log
 tail -n 1 $O/bench_in_flight_8_under_rocprof.log | cut -c1-200
