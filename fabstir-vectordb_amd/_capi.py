@@ -25,6 +25,12 @@ class SearchStats(C.Structure):
     _fields_ = [("rows_scanned", u64), ("work_items", u64), ("list_rows_touched", u64)]
 
 
+class MaintenanceInfo(C.Structure):
+    """fvdb_maintenance_info_t (include/fvdb.h)."""
+    _fields_ = [("rows_in", u64), ("rows_out", u64), ("host_bytes", u64), ("move_bytes", u64), ("ms_gather", f32),
+                ("ms_train", f32), ("ms_assign", f32), ("ms_ranks", f32), ("ms_move", f32), ("ms_total", f32)]
+
+
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
 # tests/test_cabi_symbols.py checks the built library exports each of them.
 SIGNATURES = {
@@ -60,6 +66,11 @@ SIGNATURES = {
     "fvdb_ivf_reserve": (i32, [vp, u64]),
     "fvdb_ivf_clear": (i32, [vp]),
     "fvdb_ivf_set_global_list_sizes": (i32, [vp, u64p]),
+    "fvdb_ivf_compact": (i32, [vp, u64p, u64p]),
+    "fvdb_ivf_train_from": (i32, [vp, vp, u32, u64, C.POINTER(TrainResult)]),
+    "fvdb_ivf_assign_from": (i32, [vp, vp, u32p, u64p]),
+    "fvdb_ivf_refill_from": (i32, [vp, vp, u64, u32p]),
+    "fvdb_ivf_maintenance_info": (i32, [vp, C.POINTER(MaintenanceInfo)]),
     "fvdb_ivf_search": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
     "fvdb_ivf_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_all": (i32, [vp, f32p, u32, u32, u64p, f32p, u32p]),

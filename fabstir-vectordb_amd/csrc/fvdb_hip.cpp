@@ -26,6 +26,7 @@
 #include "kernels_mfma.h"
 #include "kernels_mfma_wg.h"
 #include "kernels_util.h"
+#include "kernels_maint.h"
 
 using namespace fvdb;
 
@@ -244,6 +245,15 @@ struct fvdb_ivf : IvfScratch {
   DBuf t_off, t_blocks, t_glob, t_len;  // device list table, logical (global) block counts, rows per list
   std::vector<uint32_t> glob_blocks_host;  // empty => local sizes
   bool glob_set = false;
+
+  // resident maintenance (ivf_maint.h): the sequence map and the destinations of the source index whose rows
+  // fvdb_ivf_assign_from ranked against this index's centroids, kept for fvdb_ivf_refill_from; the figures of the
+  // last job
+  DBuf m_seq, m_dest, m_ids;
+  fvdb_ivf* m_src = nullptr;
+  uint64_t m_rows = 0;
+  bool m_assigned = false;  // m_dest holds fvdb_ivf_assign_from's ranking of m_src's m_rows rows
+  fvdb_maintenance_info_t m_info{};
 
   // per-search scratch
   fvdb_search_stats last_stats{};
@@ -1441,7 +1451,8 @@ void fvdb_ivf_destroy(fvdb_ivf* ivf) {
   ivf->pool.release();
   ivf->cpool.release();
   DBuf* bufs[] = {&ivf->d_xmax, &ivf->d_cent_pad, &ivf->d_cnorm, &ivf->d_cnmax, &ivf->s_fallbacks, &ivf->d_mfma_stamps, &ivf->d_centroids_rm,
-                  &ivf->c_off, &ivf->c_blocks, &ivf->c_glob, &ivf->t_off, &ivf->t_blocks, &ivf->t_glob, &ivf->t_len};
+                  &ivf->c_off, &ivf->c_blocks, &ivf->c_glob, &ivf->t_off, &ivf->t_blocks, &ivf->t_glob, &ivf->t_len,
+                  &ivf->m_seq, &ivf->m_dest, &ivf->m_ids};
   for (DBuf* b : bufs) b->release();
   ivf->release_all();
   for (auto& sp : ivf->spare) sp.release_all();
@@ -2126,19 +2137,16 @@ uint64_t fvdb_ivf_stage_times(fvdb_ivf* ivf, float* ms_out) {
 // =============================================================================================
 // k-means training on the GPU (src/ivf/core.rs:240-429)
 // =============================================================================================
-int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_iterations, uint64_t seed,
-                   fvdb_train_result* out) {
+// Everything after "the rows are in HBM": X is [n][d] f32 on the device.  fvdb_ivf_train uploads its rows there,
+// fvdb_ivf_train_from (ivf_maint.h) gathers them from another index's lists; the arithmetic is shared.
+static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t max_iterations, uint64_t seed,
+                          fvdb_train_result* out) {
   fvdb_ctx* ctx = ivf->ctx;
   const uint32_t nlist = ivf->nlist, d = ivf->d;
-  if (n == 0 || n < nlist) FAIL(ctx, FVDB_E_INSUFFICIENT, "insufficient training data");
-  if (max_iterations == 0) FAIL(ctx, FVDB_E_INVALID, "max_iterations must be > 0");
-  if (d > 2048) FAIL(ctx, FVDB_E_UNSUPPORTED, "training supports d <= 2048");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = check_finite(ctx, x, n * d);
-  if (rc) return rc;
-  DBuf dx, dmind, dassign, dnew, ddist, dsc;
+  int rc = FVDB_OK;
+  DBuf dmind, dassign, dnew, ddist, dsc;
   auto cleanup = [&]() {
-    dx.release(); dmind.release(); dassign.release(); dnew.release(); ddist.release(); dsc.release();
+    dmind.release(); dassign.release(); dnew.release(); ddist.release(); dsc.release();
   };
 #define TCHK(call)                                                        \
   do {                                                                    \
@@ -2149,14 +2157,12 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
       return e_ == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP;         \
     }                                                                     \
   } while (0)
-  TCHK(dx.ensure(n * d * 4));
   TCHK(dmind.ensure(n * 4));
   TCHK(dassign.ensure(n * 4));
   TCHK(dnew.ensure(n * 4));
   TCHK(ddist.ensure(n * 4));
   TCHK(dsc.ensure(64));
   TCHK(ivf->d_centroids_rm.ensure((size_t)nlist * d * 4));
-  TCHK(hipMemcpyAsync(dx.p, x, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
   float* cent = ivf->d_centroids_rm.as<float>();
   const uint32_t gn = cdiv(n, 256);
 
@@ -2171,12 +2177,12 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
     }
   } rng{seed};
   uint64_t pick = rng.next() % n;
-  TCHK(hipMemcpyAsync(cent, dx.as<float>() + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  TCHK(hipMemcpyAsync(cent, X + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream));
   hipLaunchKernelGGL(fill_f32_kernel, dim3(gn), dim3(256), 0, ctx->stream, dmind.as<float>(), n,
                      __builtin_huge_valf());
   uint32_t chosen = 1;
   for (uint32_t i = 1; i < nlist; ++i) {
-    hipLaunchKernelGGL(kpp_min_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, dx.as<float>(), d, n, pick,
+    hipLaunchKernelGGL(kpp_min_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, X, d, n, pick,
                        dmind.as<float>());
     const float u = (float)(rng.next() >> 40) * (1.0f / 16777216.0f);
     hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(256), 0, ctx->stream, dmind.as<float>(), n, u,
@@ -2186,7 +2192,7 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
     TCHK(hipStreamSynchronize(ctx->stream));
     if (p == ~0ull) continue;  // reference: the loop never fired, no centroid pushed this round
     pick = p;
-    TCHK(hipMemcpyAsync(cent + (size_t)chosen * d, dx.as<float>() + pick * d, (size_t)d * 4,
+    TCHK(hipMemcpyAsync(cent + (size_t)chosen * d, X + pick * d, (size_t)d * 4,
                         hipMemcpyDeviceToDevice, ctx->stream));
     chosen++;
   }
@@ -2196,7 +2202,7 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
   }
 
   auto error_of = [&](float* out_err) -> int {
-    hipLaunchKernelGGL(kmeans_point_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, dx.as<float>(), d, n,
+    hipLaunchKernelGGL(kmeans_point_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, X, d, n,
                        dassign.as<uint32_t>(), cent, ddist.as<float>());
     hipLaunchKernelGGL(seq_sqsum_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, ddist.as<float>(), n,
                        (float*)dsc.p + 4);
@@ -2217,14 +2223,14 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
     iterations = iter + 1;
     rc = install_centroids(ivf, cent);
     if (rc) { cleanup(); return rc; }
-    rc = assign_dev(ivf, dx.as<float>(), n, dnew.as<uint32_t>());
+    rc = assign_dev(ivf, X, n, dnew.as<uint32_t>());
     if (rc) { cleanup(); return rc; }
     TCHK(hipMemsetAsync(dsc.p, 0, 4, ctx->stream));
     hipLaunchKernelGGL(count_changed_kernel, dim3(gn), dim3(256), 0, ctx->stream, dnew.as<uint32_t>(),
                        dassign.as<uint32_t>(), n, (uint32_t*)dsc.p);
     uint32_t changed = 0;
     TCHK(hipMemcpyAsync(&changed, dsc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3(nlist), dim3(256), 0, ctx->stream, dx.as<float>(), d, n,
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3(nlist), dim3(256), 0, ctx->stream, X, d, n,
                        dassign.as<uint32_t>(), cent);
     TCHK(hipStreamSynchronize(ctx->stream));
     if (iterations >= max_iterations) break;
@@ -2261,6 +2267,34 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
   }
 #undef TCHK
   return FVDB_OK;
+}
+
+static int train_args_ok(fvdb_ivf* ivf, uint64_t n, uint32_t max_iterations) {
+  fvdb_ctx* ctx = ivf->ctx;
+  if (n == 0 || n < ivf->nlist) FAIL(ctx, FVDB_E_INSUFFICIENT, "insufficient training data");
+  if (max_iterations == 0) FAIL(ctx, FVDB_E_INVALID, "max_iterations must be > 0");
+  if (ivf->d > 2048) FAIL(ctx, FVDB_E_UNSUPPORTED, "training supports d <= 2048");
+  return FVDB_OK;
+}
+
+int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_iterations, uint64_t seed,
+                   fvdb_train_result* out) {
+  fvdb_ctx* ctx = ivf->ctx;
+  int rc = train_args_ok(ivf, n, max_iterations);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = check_finite(ctx, x, n * ivf->d);
+  if (rc) return rc;
+  DBuf dx;
+  HIPCHK(ctx, dx.ensure(n * ivf->d * 4));
+  hipError_t e = hipMemcpyAsync(dx.p, x, n * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) {
+    dx.release();
+    FAIL(ctx, FVDB_E_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  }
+  rc = train_resident(ivf, dx.as<float>(), n, max_iterations, seed, out);
+  dx.release();
+  return rc;
 }
 
 // =============================================================================================
@@ -2660,4 +2694,5 @@ int fvdb_scorer_run(fvdb_scorer* sc, uint32_t B, uint32_t C) {
 
 }  // extern "C"
 
+#include "ivf_maint.h"
 #include "comm_sharded.h"

@@ -331,6 +331,40 @@ class DeviceIVF:
     def clear(self):
         self.ctx.check(self.lib.fvdb_ivf_clear(self.h))
 
+    # --- maintenance that keeps the rows in HBM (include/fvdb.h: sequence order, fvdb_ivf_compact ...) ---
+    def compact(self):
+        """Drop the soft-deleted rows; returns (rows removed, surviving ids in sequence order)."""
+        ids = np.empty(max(self.total_rows(), 1), np.uint64)
+        removed = C.c_uint64(0)
+        self.ctx.check(self.lib.fvdb_ivf_compact(self.h, C.byref(removed), _ptr(ids, u64p)))
+        return removed.value, ids[:self.total_rows()]
+
+    def train_from(self, src, max_iterations=25, seed=0):
+        """fvdb_ivf_train on `src`'s rows in sequence order, taken from its lists on the device."""
+        res = _capi.TrainResult()
+        self.ctx.check(self.lib.fvdb_ivf_train_from(self.h, src.h, max_iterations, seed, C.byref(res)))
+        return dict(iterations=res.iterations, converged=bool(res.converged), initial_error=res.initial_error,
+                    final_error=res.final_error)
+
+    def assign_from(self, src):
+        """Nearest centroid of this index for each of `src`'s rows in sequence order: (clusters, ids)."""
+        n = src.total_rows()
+        cl, ids = np.empty(max(n, 1), np.uint32), np.empty(max(n, 1), np.uint64)
+        self.ctx.check(self.lib.fvdb_ivf_assign_from(self.h, src.h, _ptr(cl, u32p), _ptr(ids, u64p)))
+        return cl[:n], ids[:n]
+
+    def refill_from(self, src, n_rows=None):
+        """Move the first n_rows rows of `src`'s sequence into the lists assign_from chose; returns their positions."""
+        n = src.total_rows() if n_rows is None else int(n_rows)
+        pos = np.empty(max(n, 1), np.uint32)
+        self.ctx.check(self.lib.fvdb_ivf_refill_from(self.h, src.h, n, _ptr(pos, u32p)))
+        return pos[:n]
+
+    def maintenance_info(self):
+        m = _capi.MaintenanceInfo()
+        self.ctx.check(self.lib.fvdb_ivf_maintenance_info(self.h, C.byref(m)))
+        return {name: getattr(m, name) for name, _ in m._fields_}
+
     def set_global_list_sizes(self, sizes):
         s = np.ascontiguousarray(sizes, np.uint64)
         self.ctx.check(self.lib.fvdb_ivf_set_global_list_sizes(self.h, _ptr(s, u64p)))

@@ -49,6 +49,38 @@ int fvh_ivf_search(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, 
 int fvh_ivf_mark_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->mark_deleted(id); }
 int fvh_ivf_is_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->is_deleted(id); }
 void* fvh_ivf_device(void* p) { return ((IVFIndex*)p)->device(); }
+// retrain / add_clusters / optimize_clusters / get_cluster_stats (src/ivf/operations.rs:148-288).  out4 = old_clusters,
+// new_clusters, vectors_reassigned, converged.  An invalid config is refused here (IVFIndex::new would have panicked).
+static int retrain_config(uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iterations, uint64_t seed,
+                          IVFConfig* c) {
+  c->n_clusters = n_clusters;
+  c->n_probe = n_probe;
+  c->train_size = train_size;
+  c->max_iterations = max_iterations;
+  c->seed = seed;
+  return c->is_valid() ? FVDB_OK : FVDB_E_INVALID;
+}
+int fvh_ivf_retrain(void* p, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iterations,
+                    uint64_t seed, uint64_t* out4) {
+  IVFConfig c;
+  if (int rc = retrain_config(n_clusters, n_probe, train_size, max_iterations, seed, &c)) return rc;
+  IVFIndex::RetrainResult r{};
+  const int rc = ((IVFIndex*)p)->retrain(c, &r);
+  if (!rc && out4) std::memcpy(out4, &r, sizeof r);
+  return rc;
+}
+int fvh_ivf_add_clusters(void* p, uint32_t n_clusters_to_add, uint64_t* vectors_reassigned) {
+  return ((IVFIndex*)p)->add_clusters(n_clusters_to_add, vectors_reassigned);
+}
+int fvh_ivf_optimize_clusters(void* p, uint32_t* iterations, float* improvement) {
+  return ((IVFIndex*)p)->optimize_clusters(iterations, improvement);
+}
+int fvh_ivf_cluster_stats(void* p, IVFIndex::ClusterStats* out) {
+  *out = ((IVFIndex*)p)->get_cluster_stats();
+  return FVDB_OK;
+}
+uint32_t fvh_ivf_n_clusters(void* p) { return ((IVFIndex*)p)->config().n_clusters; }
+uint32_t fvh_ivf_n_probe(void* p) { return ((IVFIndex*)p)->config().n_probe; }
 
 // ---- HNSWIndex ----
 void* fvh_hnsw_new(fvdb_ctx* ctx, uint32_t M, uint32_t M0, uint32_t efc, uint64_t seed) {
@@ -265,6 +297,15 @@ int fvh_hybrid_from_parts(void* p, const uint64_t* ids, const double* ts, uint64
 }
 int fvh_hybrid_vacuum(void* p, uint64_t* hnsw_removed, uint64_t* ivf_removed) {
   return ((HybridIndex*)p)->vacuum(hnsw_removed, ivf_removed);
+}
+int fvh_hybrid_retrain_historical(void* p, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size,
+                                  uint32_t max_iterations, uint64_t seed, uint64_t* out4) {
+  IVFConfig c;
+  if (int rc = retrain_config(n_clusters, n_probe, train_size, max_iterations, seed, &c)) return rc;
+  IVFIndex::RetrainResult r{};
+  const int rc = ((HybridIndex*)p)->retrain_historical(c, &r);
+  if (!rc && out4) std::memcpy(out4, &r, sizeof r);
+  return rc;
 }
 int fvh_ivf_vacuum(void* p, uint64_t* removed) { return ((IVFIndex*)p)->vacuum(removed); }
 uint64_t fvh_hnsw_vacuum(void* p) { return ((HNSWIndex*)p)->vacuum(); }

@@ -141,6 +141,20 @@ class IVFIndex {
   uint64_t active_count() const { return total_ - deleted_.size(); }
   uint64_t deleted_count() const { return deleted_.size(); }
   int vacuum(uint64_t* removed);                                                  // operations.rs:625
+  // Re-partitioning (operations.rs:148-260).  The rows stay in HBM: a new device index is trained on the old one's
+  // rows in sequence order (lists ascending, list-position order inside: this project's outcome of the reference's
+  // walk over `inverted_lists.values()`), every row is re-inserted in that order, and the old device index is destroyed.
+  struct RetrainResult {  // operations.rs RetrainResult
+    uint64_t old_clusters, new_clusters, vectors_reassigned, converged;
+  };
+  struct ClusterStats {  // operations.rs:263-288
+    uint64_t n_clusters, total_vectors, empty_clusters;
+    float avg_cluster_size, size_variance;
+  };
+  int retrain(const IVFConfig& new_config, RetrainResult* out);                   // operations.rs:148-193
+  int add_clusters(uint32_t n_clusters_to_add, uint64_t* vectors_reassigned);     // operations.rs:195-220
+  int optimize_clusters(uint32_t* iterations, float* improvement);                // operations.rs:222-260
+  ClusterStats get_cluster_stats() const;                                         // operations.rs:263-288
   uint64_t cluster_size(uint32_t c) const;
   // list `c` in list-position order, copied back from HBM (save path, src/hybrid/persistence.rs:289-311)
   int export_list(uint32_t c, float* rows, uint64_t* ids, uint8_t* live) const;
@@ -152,12 +166,18 @@ class IVFIndex {
     uint32_t cluster, pos;
   };
   int ensure_device(uint32_t dim);
+  float size_variance() const;                                                    // operations.rs:552-563
+  // the shared body of retrain and optimize_clusters: train a new device index of `n_clusters` lists on the rows of
+  // the present one and re-insert them; `reinserted` counts the rows that went in (all, or those before a duplicate)
+  int rebuild(uint32_t n_clusters, uint32_t max_iterations, uint64_t seed, fvdb_train_result* tr, uint64_t* reinserted);
   int place(const uint64_t* ids, const float* v, uint64_t n, const uint32_t* clusters, uint64_t* n_ok, int* first_error);
   fvdb_ctx* ctx_;
   IVFConfig cfg_;
   fvdb_ivf* dev_ = nullptr;
+  uint32_t dev_clusters_ = 0;  // lists of dev_; differs from cfg_.n_clusters only after a retrain whose training failed
   uint32_t dim_ = 0;
   bool trained_ = false;
+  bool live_again_ = false;    // a row was inserted under an id that is in deleted_: its live bit is set (vacuum)
   uint64_t total_ = 0;
   std::unordered_multimap<uint64_t, Loc> where_;  // id -> every list position holding it
   std::unordered_set<uint64_t> deleted_;
@@ -460,6 +480,11 @@ class HybridIndex {
                  bool ivf_trained);
   // vacuum (src/hybrid/core.rs:989-1012): both indexes; refused while a batch is in flight
   int vacuum(uint64_t* hnsw_removed, uint64_t* ivf_removed);
+  // IVFIndex::retrain of the historical index, under vacuum's rule (refused while a batch begun with search_dev_begin
+  // is uncollected); FVDB_E_UNSUPPORTED once the index is sharded.  The reference has no real counterpart: its
+  // maintenance scheduler only simulates a retrain (src/hybrid/maintenance.rs:509-533).  This is the way out of the
+  // default configuration's 3 clusters (src/hybrid/core.rs:69).
+  int retrain_historical(const IVFConfig& new_ivf_config, IVFIndex::RetrainResult* out);
   uint64_t timestamp_count() const { return ts_order_.size(); }
   void export_timestamps(uint64_t* ids, double* ts) const;  // insertion order
   HNSWIndex& recent() { return *recent_; }

@@ -297,6 +297,17 @@ int HybridIndex::vacuum(uint64_t* hnsw_removed, uint64_t* ivf_removed) {
   return historical_->vacuum(ivf_removed);
 }
 
+int HybridIndex::retrain_historical(const IVFConfig& new_ivf_config, IVFIndex::RetrainResult* out) {
+  std::unique_lock<std::shared_mutex> w(rw_, std::defer_lock);
+  if (int rc = write_lock(w)) return rc;
+  if (sharded_ || comm_ || shard_world_ > 0) return FVDB_E_UNSUPPORTED;  // the ranks would have to agree on the new lists
+  if (!ivf_trained_) return FVDB_E_NOT_TRAINED;
+  const int rc = historical_->retrain(new_ivf_config, out);
+  ivf_trained_ = historical_->is_trained();
+  if (historical_->config().n_clusters == new_ivf_config.n_clusters) cfg_.ivf = new_ivf_config;
+  return rc;
+}
+
 void HybridIndex::export_timestamps(uint64_t* ids, double* ts) const {
   for (size_t i = 0; i < ts_order_.size(); ++i) {
     ids[i] = ts_order_[i];

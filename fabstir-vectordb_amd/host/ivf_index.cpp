@@ -13,7 +13,7 @@ IVFIndex::~IVFIndex() {
 }
 
 int IVFIndex::ensure_device(uint32_t dim) {
-  if (dev_ && dim_ == dim) return FVDB_OK;
+  if (dev_ && dim_ == dim && dev_clusters_ == cfg_.n_clusters) return FVDB_OK;
   if (dev_) {
     fvdb_ivf_destroy(dev_);
     dev_ = nullptr;
@@ -21,6 +21,7 @@ int IVFIndex::ensure_device(uint32_t dim) {
   int rc = fvdb_ivf_create(ctx_, dim, cfg_.n_clusters, &dev_);
   if (rc) return rc;
   dim_ = dim;
+  dev_clusters_ = cfg_.n_clusters;
   return FVDB_OK;
 }
 
@@ -64,59 +65,177 @@ void IVFIndex::clear_lists() {
 }
 
 // src/ivf/operations.rs:625-645: every row of a soft-deleted id leaves its list, the survivors keep their order.
-// The lists live in HBM as packed 64-row blocks: copy the survivors out, empty the lists, append them again.
+// The rows never leave HBM (fvdb_ivf_compact drops the rows whose live bit is clear); the ids of the survivors come
+// back in sequence order, and with the new list sizes that is every survivor's (list, position).
 int IVFIndex::vacuum(uint64_t* removed_out) {
   const uint64_t removed = deleted_.size();
   if (removed_out) *removed_out = removed;
   if (removed == 0) return FVDB_OK;
   if (dev_) {
-    std::vector<uint64_t> sizes(cfg_.n_clusters);
-    int rc = fvdb_ivf_list_sizes(dev_, sizes.data());
-    if (rc) return rc;
-    std::vector<float> xv, rows;
-    std::vector<uint64_t> xi, ids;
-    std::vector<uint32_t> xc;
-    for (uint32_t c = 0; c < cfg_.n_clusters; ++c) {
-      if (sizes[c] == 0) continue;
-      rows.resize(sizes[c] * (size_t)dim_);
-      ids.resize(sizes[c]);
-      rc = fvdb_ivf_list_export(dev_, c, rows.data(), ids.data(), nullptr);
-      if (rc) return rc;
-      for (uint64_t i = 0; i < sizes[c]; ++i) {
-        if (deleted_.count(ids[i])) continue;
-        xi.push_back(ids[i]);
-        xc.push_back(c);
-        xv.insert(xv.end(), rows.begin() + i * dim_, rows.begin() + (i + 1) * dim_);
+    if (live_again_) {  // rows inserted under an id deleted earlier carry a live bit: the reference drops them by id
+      std::vector<uint32_t> cl, ps;
+      for (uint64_t id : deleted_) {
+        auto r = where_.equal_range(id);
+        for (auto it = r.first; it != r.second; ++it) {
+          cl.push_back(it->second.cluster);
+          ps.push_back(it->second.pos);
+        }
       }
+      int rc = fvdb_ivf_set_deleted(dev_, cl.data(), ps.data(), cl.size(), 1);
+      if (rc) return rc;
     }
-    rc = fvdb_ivf_clear(dev_);
+    std::vector<uint64_t> ids(fvdb_ivf_total_rows(dev_)), sizes(dev_clusters_);
+    int rc = fvdb_ivf_compact(dev_, nullptr, ids.data());
+    if (rc) return rc;
+    rc = fvdb_ivf_list_sizes(dev_, sizes.data());
     if (rc) return rc;
     where_.clear();
-    const uint64_t total_before = total_;
-    total_ = 0;
-    if (!xi.empty()) {
-      uint64_t ok = 0;
-      int err = 0;
-      rc = place(xi.data(), xv.data(), xi.size(), xc.data(), &ok, &err);
-      if (rc) return rc;
-    }
-    total_ = total_before - removed;  // "total_vectors -= removed_count" (:638), counted in ids like the reference
-  } else {
-    total_ -= removed;
+    size_t i = 0;
+    for (uint32_t c = 0; c < dev_clusters_; ++c)
+      for (uint32_t p = 0; p < sizes[c]; ++p) where_.emplace(ids[i++], Loc{c, p});
   }
+  total_ -= removed;  // "total_vectors -= removed_count" (:638), counted in ids like the reference
   deleted_.clear();
+  live_again_ = false;
+  return FVDB_OK;
+}
+
+float IVFIndex::size_variance() const {  // operations.rs:552-563, f32 sums in cluster order
+  const uint32_t nc = cfg_.n_clusters;
+  std::vector<uint64_t> sizes(std::max(nc, dev_clusters_), 0);
+  if (dev_) fvdb_ivf_list_sizes(dev_, sizes.data());
+  float sum = 0.0f;
+  for (uint32_t c = 0; c < nc; ++c) sum += (float)sizes[c];
+  const float mean = sum / (float)nc;
+  float acc = 0.0f;
+  for (uint32_t c = 0; c < nc; ++c) {
+    const float t = (float)sizes[c] - mean;
+    acc += t * t;
+  }
+  return acc / (float)nc;
+}
+
+// src/ivf/operations.rs:263-288
+IVFIndex::ClusterStats IVFIndex::get_cluster_stats() const {
+  ClusterStats st{};
+  st.n_clusters = cfg_.n_clusters;
+  st.total_vectors = total_;
+  st.avg_cluster_size = cfg_.n_clusters ? (float)total_ / (float)cfg_.n_clusters : 0.0f;
+  st.size_variance = size_variance();
+  std::vector<uint64_t> sizes(std::max(cfg_.n_clusters, dev_clusters_), 0);
+  if (dev_) fvdb_ivf_list_sizes(dev_, sizes.data());
+  for (uint32_t c = 0; c < cfg_.n_clusters; ++c) st.empty_clusters += sizes[c] == 0;
+  return st;
+}
+
+// "Collect all existing vectors ... train ... clear ... reinsert" (operations.rs:158-186, :231-250) without the rows
+// leaving HBM.  The reference's re-insert loop stops at the first DuplicateVector (`?` at :185 / :249): an id stored in
+// two lists (the duplicate check is per list, src/ivf/core.rs:128-134) whose copies now meet in one list.  The rows
+// before that repeat are in place and the rest are gone; same here, and FVDB_E_DUPLICATE is returned after the swap.
+int IVFIndex::rebuild(uint32_t n_clusters, uint32_t max_iterations, uint64_t seed, fvdb_train_result* tr,
+                      uint64_t* reinserted) {
+  fvdb_ivf* nd = nullptr;
+  int rc = fvdb_ivf_create(ctx_, dim_, n_clusters, &nd);
+  if (rc) return rc;
+  rc = fvdb_ivf_train_from(nd, dev_, max_iterations, seed, tr);
+  const uint64_t n = fvdb_ivf_total_rows(dev_);
+  std::vector<uint32_t> cl(n), pos(n);
+  std::vector<uint64_t> ids(n);
+  if (!rc) rc = fvdb_ivf_assign_from(nd, dev_, cl.data(), ids.data());
+  uint64_t keep = n;
+  if (!rc) {
+    std::unordered_multimap<uint64_t, uint32_t> seen;  // only ids stored more than once can repeat
+    for (uint64_t i = 0; i < n && keep == n; ++i) {
+      if (where_.count(ids[i]) < 2) continue;
+      auto r = seen.equal_range(ids[i]);
+      for (auto it = r.first; it != r.second; ++it)
+        if (it->second == cl[i]) keep = i;
+      seen.emplace(ids[i], cl[i]);
+    }
+    rc = fvdb_ivf_refill_from(nd, dev_, keep, pos.data());
+  }
+  if (rc) {  // the old device index is untouched
+    fvdb_ivf_destroy(nd);
+    return rc;
+  }
+  fvdb_ivf_destroy(dev_);
+  dev_ = nd;
+  dev_clusters_ = n_clusters;
+  where_.clear();
+  for (uint64_t i = 0; i < keep; ++i) where_.emplace(ids[i], Loc{cl[i], pos[i]});
+  *reinserted = keep;
+  return keep == n ? FVDB_OK : FVDB_E_DUPLICATE;
+}
+
+// src/ivf/operations.rs:148-193.  deleted_ is keyed by id and not touched (:148-193 never mention it): a soft-deleted
+// row moves with its live bit clear.
+int IVFIndex::retrain(const IVFConfig& new_config, RetrainResult* out) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  const IVFConfig old_config = cfg_;
+  const uint64_t old_vectors = total_;
+  // :168-169 replace the config and clear `trained` BEFORE train can fail; when it fails for want of rows (or on
+  // degenerate data) the reference is left with the new config, untrained, its lists whole.  Mirrored: the old device
+  // index stays (dev_clusters_ lists) until a later train() builds one for the new config.
+  cfg_ = new_config;
+  trained_ = false;
+  const uint64_t n = dev_ ? fvdb_ivf_total_rows(dev_) : 0;
+  if (n == 0 || n < cfg_.n_clusters) return FVDB_E_INSUFFICIENT;
+  fvdb_train_result tr{};
+  uint64_t reinserted = 0;
+  const int rc = rebuild(cfg_.n_clusters, cfg_.max_iterations, cfg_.seed, &tr, &reinserted);
+  if (rc && rc != FVDB_E_DUPLICATE) {
+    if (rc != FVDB_E_INSUFFICIENT && rc != FVDB_E_INVALID) {  // the device's failure, not the reference's: nothing changed
+      cfg_ = old_config;
+      trained_ = true;
+    }
+    return rc;
+  }
+  trained_ = true;
+  total_ = reinserted;  // :176 resets the counter, each re-insert counts one
+  if (rc) return rc;
+  if (out) *out = RetrainResult{old_config.n_clusters, cfg_.n_clusters, old_vectors, tr.converged};
+  return FVDB_OK;
+}
+
+// src/ivf/operations.rs:195-220
+int IVFIndex::add_clusters(uint32_t n_clusters_to_add, uint64_t* vectors_reassigned) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (n_clusters_to_add == 0) return FVDB_E_INVALID;  // "Cannot add 0 clusters"
+  IVFConfig nc = cfg_;
+  nc.n_clusters += n_clusters_to_add;
+  RetrainResult r{};
+  const int rc = retrain(nc, &r);
+  if (rc) return rc;
+  if (vectors_reassigned) *vectors_reassigned = r.vectors_reassigned;
+  return FVDB_OK;
+}
+
+// src/ivf/operations.rs:222-260.  total_vectors is NOT reset before the re-inserts (:243-250), so it doubles: kept.
+int IVFIndex::optimize_clusters(uint32_t* iterations, float* improvement) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  const float initial_variance = size_variance();
+  const uint64_t n = dev_ ? fvdb_ivf_total_rows(dev_) : 0;
+  if (n == 0 || n < cfg_.n_clusters) return FVDB_E_INSUFFICIENT;  // train fails first (:240), nothing has changed
+  fvdb_train_result tr{};
+  uint64_t reinserted = 0;
+  const int rc = rebuild(cfg_.n_clusters, cfg_.max_iterations, cfg_.seed, &tr, &reinserted);
+  if (rc && rc != FVDB_E_DUPLICATE) return rc;
+  total_ += reinserted;
+  if (rc) return rc;
+  if (iterations) *iterations = tr.iterations;
+  if (improvement) *improvement = std::max(initial_variance - size_variance(), 0.0f);
   return FVDB_OK;
 }
 
 int IVFIndex::export_list(uint32_t c, float* rows, uint64_t* ids, uint8_t* live) const {
   if (c >= cfg_.n_clusters) return FVDB_E_INVALID;
-  if (!dev_) return FVDB_OK;  // nothing stored yet
+  if (!dev_ || c >= dev_clusters_) return FVDB_OK;  // nothing stored yet
   return fvdb_ivf_list_export(dev_, c, rows, ids, live);
 }
 
 uint64_t IVFIndex::cluster_size(uint32_t c) const {
-  if (!dev_ || c >= cfg_.n_clusters) return 0;
-  std::vector<uint64_t> sizes(cfg_.n_clusters);
+  if (!dev_ || c >= cfg_.n_clusters || c >= dev_clusters_) return 0;
+  std::vector<uint64_t> sizes(dev_clusters_);
   fvdb_ivf_list_sizes(dev_, sizes.data());
   return sizes[c];
 }
@@ -146,6 +265,7 @@ int IVFIndex::place(const uint64_t* ids, const float* v, uint64_t n, const uint3
     }
     batch_seen.emplace(ids[i], clusters[i]);
     keep.push_back(i);
+    if (!deleted_.empty() && deleted_.count(ids[i])) live_again_ = true;
   }
   if (n_ok) *n_ok = keep.size();
   if (keep.empty()) return FVDB_OK;

@@ -42,6 +42,13 @@ HOST_SIGNATURES = {
     "fvh_ivf_mark_deleted": (i32, [vp, u64]),
     "fvh_ivf_is_deleted": (i32, [vp, u64]),
     "fvh_ivf_device": (vp, [vp]),
+    "fvh_ivf_retrain": (i32, [vp, u32, u32, u32, u32, u64, u64p]),
+    "fvh_ivf_add_clusters": (i32, [vp, u32, u64p]),
+    "fvh_ivf_optimize_clusters": (i32, [vp, u32p, f32p]),
+    "fvh_ivf_cluster_stats": (i32, [vp, vp]),
+    "fvh_ivf_n_clusters": (u32, [vp]),
+    "fvh_ivf_n_probe": (u32, [vp]),
+    "fvh_hybrid_retrain_historical": (i32, [vp, u32, u32, u32, u32, u64, u64p]),
     "fvh_hnsw_new": (vp, [vp, u32, u32, u32, u64]),
     "fvh_hnsw_free": (None, [vp]),
     "fvh_hnsw_insert": (i32, [vp, u64, f32p, u32, i64]),
@@ -259,6 +266,51 @@ class IVFIndex(_Base):
         self._check(self.lib.fvh_ivf_vacuum(self.h, C.byref(out)))
         return out.value
 
+    # --- re-partitioning (src/ivf/operations.rs:148-288); the rows stay in HBM ---
+    def _sync_config(self):
+        # the mirror replaces its config before a retrain's training can fail (operations.rs:168-169): read it back
+        self._dev_clusters = max(getattr(self, "_dev_clusters", 0), self.n_clusters)  # list_sizes: room for the old lists
+        self.n_clusters = int(self.lib.fvh_ivf_n_clusters(self.h))
+        self.n_probe = int(self.lib.fvh_ivf_n_probe(self.h))
+
+    def retrain(self, n_clusters, n_probe=None, train_size=10000, max_iterations=25, seed=0):
+        """IVFIndex::retrain (operations.rs:148-193) with the new IVFConfig's fields; returns RetrainResult as a dict."""
+        out = np.zeros(4, np.uint64)
+        rc = self.lib.fvh_ivf_retrain(self.h, int(n_clusters), int(self.n_probe if n_probe is None else n_probe),
+                                      int(train_size), int(max_iterations), int(seed), _ptr(out, u64p))
+        self._sync_config()
+        self._check(rc)
+        return dict(old_clusters=int(out[0]), new_clusters=int(out[1]), vectors_reassigned=int(out[2]), converged=bool(out[3]))
+
+    def add_clusters(self, n_clusters_to_add):
+        """IVFIndex::add_clusters (operations.rs:195-220)."""
+        out = C.c_uint64(0)
+        rc = self.lib.fvh_ivf_add_clusters(self.h, int(n_clusters_to_add), C.byref(out))
+        self._sync_config()
+        if rc == 6 and int(n_clusters_to_add) == 0:
+            raise InvalidConfig("Invalid parameter: Cannot add 0 clusters")
+        self._check(rc)
+        return dict(clusters_added=int(n_clusters_to_add), vectors_reassigned=out.value)
+
+    def optimize_clusters(self):
+        """IVFIndex::optimize_clusters (operations.rs:222-260); total_vectors doubles like the reference's."""
+        it, imp = C.c_uint32(0), C.c_float(0)
+        self._check(self.lib.fvh_ivf_optimize_clusters(self.h, C.byref(it), C.byref(imp)))
+        return dict(iterations=it.value, improvement=imp.value)
+
+    def get_cluster_stats(self):
+        """ClusterStats (operations.rs:263-288)."""
+        st = _ClusterStats()
+        self._check(self.lib.fvh_ivf_cluster_stats(self.h, C.byref(st)))
+        return dict(n_clusters=st.n_clusters, total_vectors=st.total_vectors, avg_cluster_size=st.avg_cluster_size,
+                    size_variance=st.size_variance, empty_clusters=st.empty_clusters)
+
+    def maintenance_info(self):
+        """Figures of the last resident maintenance job (fvdb_ivf_maintenance_info)."""
+        m = _capi.MaintenanceInfo()
+        self._check(self.ctx.lib.fvdb_ivf_maintenance_info(self._dev(), C.byref(m)))
+        return {name: getattr(m, name) for name, _ in m._fields_}
+
     def export_list(self, c):
         """Rows (f32), ids and live flags of inverted list `c`, in list-position order (save path)."""
         n = self.get_cluster_size(c)
@@ -292,9 +344,10 @@ class IVFIndex(_Base):
         return out
 
     def list_sizes(self):
-        out = np.empty(self.n_clusters, np.uint64)
+        # after a retrain whose training failed the device index still has its old lists (see _sync_config)
+        out = np.zeros(max(self.n_clusters, getattr(self, "_dev_clusters", 0)), np.uint64)
         self._check(self.ctx.lib.fvdb_ivf_list_sizes(self._dev(), _ptr(out, u64p)))
-        return out
+        return out[:self.n_clusters]
 
     def stage_times(self):
         ms = np.zeros(8, np.float32)
@@ -305,6 +358,12 @@ class IVFIndex(_Base):
         st = _capi.SearchStats()
         self._check(self.ctx.lib.fvdb_ivf_last_stats(self._dev(), C.byref(st)))
         return dict(rows_scanned=st.rows_scanned, work_items=st.work_items, list_rows_touched=st.list_rows_touched)
+
+
+class _ClusterStats(C.Structure):
+    """IVFIndex::ClusterStats (host/fvdb_host.hpp)."""
+    _fields_ = [("n_clusters", u64), ("total_vectors", u64), ("empty_clusters", u64), ("avg_cluster_size", C.c_float),
+                ("size_variance", C.c_float)]
 
 
 class _InsertInfo(C.Structure):
@@ -711,6 +770,19 @@ class HybridIndex(_Base):
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.fvh_hybrid_vacuum(self.h, C.byref(a), C.byref(b)))
         return {"hnsw_removed": a.value, "ivf_removed": b.value, "total_removed": a.value + b.value}
+
+    def retrain_historical(self, n_clusters, n_probe=None, train_size=10000, max_iterations=25, seed=0):
+        """IVFIndex::retrain of the historical index (no counterpart in the reference, whose maintenance scheduler only
+        simulates one, src/hybrid/maintenance.rs:509-533): the way from the default 3 clusters to a partition that
+        suits the data.  Refused while a batch begun with search_dev_begin is uncollected, and once sharded."""
+        out = np.zeros(4, np.uint64)
+        n_probe = int(self.n_probe if n_probe is None else n_probe)
+        rc = self.lib.fvh_hybrid_retrain_historical(self.h, int(n_clusters), n_probe, int(train_size),
+                                                    int(max_iterations), int(seed), _ptr(out, u64p))
+        ivf = self.lib.fvh_hybrid_ivf(self.h)
+        self.n_clusters, self.n_probe = int(self.lib.fvh_ivf_n_clusters(ivf)), int(self.lib.fvh_ivf_n_probe(ivf))
+        self._check(rc)
+        return dict(old_clusters=int(out[0]), new_clusters=int(out[1]), vectors_reassigned=int(out[2]), converged=bool(out[3]))
 
     def from_parts(self, ids, timestamps, recent_count, historical_count, ivf_trained):
         """HybridIndex::from_parts (src/hybrid/core.rs:857-877): adopt hnsw() / ivf() as restored by the caller."""

@@ -164,6 +164,41 @@ uint64_t fvdb_ivf_total_rows(fvdb_ivf* ivf);
  * walk over `InvertedList.vectors` of the reference's save path (src/hybrid/persistence.rs:289-311). */
 int fvdb_ivf_list_export(fvdb_ivf* ivf, uint32_t list, float* rows, uint64_t* ids, uint8_t* live);
 int fvdb_ivf_reserve(fvdb_ivf* ivf, uint64_t n_rows);
+
+/* ---- Maintenance that re-partitions an index without its rows leaving HBM -------------------------------------------
+ * (src/ivf/operations.rs:148-260 retrain / add_clusters / optimize_clusters, :625-645 vacuum).  The SEQUENCE ORDER of
+ * an index is: lists in ascending cluster id, each list in list-position order (the order of fvdb_ivf_list_export).
+ * Every row keeps its place in that order inside the list it moves to, in every representation the pool keeps; norms
+ * and live bits travel with the row (a soft-deleted row stays soft-deleted).  The job builds a second pool beside the
+ * first and swaps: FVDB_E_OOM leaves the index as it was.  Destination lists are ranked with one LDS counter per list:
+ * up to 16384 lists, FVDB_E_UNSUPPORTED above.  An index with global list sizes set (a shard) is refused with
+ * FVDB_E_UNSUPPORTED.  Only ids, cluster numbers, positions and the list tables cross the host link. */
+typedef struct fvdb_maintenance_info_t {
+  uint64_t rows_in, rows_out;  /* rows of the source sequence; rows in the lists afterwards */
+  uint64_t host_bytes;         /* copied to or from the host by the job (ids, clusters, positions, list tables) */
+  uint64_t move_bytes;         /* read + written in HBM by the move stage */
+  float ms_gather, ms_train, ms_assign, ms_ranks, ms_move;  /* device time per stage, summed over the job's calls */
+  float ms_total;
+} fvdb_maintenance_info_t;
+/* Drop every row whose live bit is clear; survivors keep their order.  removed (optional) = rows dropped.  out_ids
+ * (optional, room for fvdb_ivf_total_rows() entries) receives the surviving ids in sequence order: with
+ * fvdb_ivf_list_sizes that is every survivor's (list, position). */
+int fvdb_ivf_compact(fvdb_ivf* ivf, uint64_t* removed, uint64_t* out_ids);
+/* fvdb_ivf_train of dst on src's rows in sequence order (soft-deleted rows included, fp16 rows widened exactly), with
+ * no host copy: the result is that of fvdb_ivf_train given the exported rows, bit for bit.  dst and src share d, row
+ * dtype and device and are different objects; src is not modified; dst's lists are emptied like fvdb_ivf_train does
+ * and dst takes over src's coarse and scan mode. */
+int fvdb_ivf_train_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t max_iterations, uint64_t seed, fvdb_train_result* out);
+/* Nearest centroid of dst for each of src's rows in sequence order.  out_cluster / out_ids (optional, host,
+ * fvdb_ivf_total_rows(src) entries each): the cluster and the id of every row.  The ranking stays on the device for
+ * fvdb_ivf_refill_from. */
+int fvdb_ivf_assign_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t* out_cluster, uint64_t* out_ids);
+/* Move the first n_rows rows of src's sequence into dst's lists (which must be empty), each into the list
+ * fvdb_ivf_assign_from chose; the rest are left out (the host mirror cuts the sequence where the reference's re-insert
+ * stops at a duplicate).  out_pos (optional, host, n_rows entries): each row's position in its list.  src is unchanged. */
+int fvdb_ivf_refill_from(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n_rows, uint32_t* out_pos);
+/* Figures of the last maintenance job on this index (compact; train_from + assign_from + refill_from as dst). */
+int fvdb_ivf_maintenance_info(fvdb_ivf* ivf, fvdb_maintenance_info_t* out);
 int fvdb_ivf_clear(fvdb_ivf* ivf);   /* empties the lists, keeps centroids (hybrid initialize :278-287) */
 /* Multi-GPU: sizes of ALL lists of the logical index (this rank may own a subset), so the
  * tie-break position `seq` is identical on every rank.  Default = local sizes. */
