@@ -25,6 +25,11 @@ class SearchStats(C.Structure):
     _fields_ = [("rows_scanned", u64), ("work_items", u64), ("list_rows_touched", u64)]
 
 
+class MaskInfo(C.Structure):
+    """fvdb_mask_info_t (include/fvdb.h)."""
+    _fields_ = [("kind", u32), ("stale", u32), ("units", u32), ("reserved", u32), ("allowed_live", u64)]
+
+
 class MaintenanceInfo(C.Structure):
     """fvdb_maintenance_info_t (include/fvdb.h)."""
     _fields_ = [("rows_in", u64), ("rows_out", u64), ("host_bytes", u64), ("move_bytes", u64), ("ms_gather", f32),
@@ -153,6 +158,15 @@ SIGNATURES = {
     "fvdb_sharded_out_rows": (u32, [vp, u32, i32]),
     "fvdb_ivf_search_sharded_begin": (i32, [vp, vp, u32, vp, u32, u32, u32, i32, vp, vp, vp]),
     "fvdb_ivf_search_sharded_end": (i32, [vp, vp, u32]),
+    # filtered search: allow-set masks
+    "fvdb_mask_create_ivf": (i32, [vp, u64p, u64, C.POINTER(vp)]),
+    "fvdb_mask_create_graph": (i32, [vp, u32p, u64, C.POINTER(vp)]),
+    "fvdb_mask_info": (i32, [vp, vp]),
+    "fvdb_mask_destroy": (None, [vp]),
+    "fvdb_ivf_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_ivf_search_probes_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_graph_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_graph_scan_allowed_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
 }
 
 _lib = None

@@ -45,12 +45,16 @@ struct fvdb_graph {
   DBuf s_q, d_counters;
   DBuf d_stamps, d_build_stamps;  // diagnostic builds only (-DFVDB_GRAPH_STAMPS, -DFVDB_BUILD_STAMPS)
   uint64_t tot_queries = 0, tot_again = 0;  // traversal counters [3], [2] folded in at every fvdb_graph_kernel_times
-  static constexpr uint32_t kSlots = 16;  // batches that may be in flight at once, each on its own stream
+  static constexpr uint32_t kSlots = kGraphSlots;  // batches that may be in flight at once, each on its own stream
   DBuf s_visited[kSlots], s_touched[kSlots], s_spill[kSlots];
   uint32_t vis_B[kSlots] = {}, vis_words = 0, vis_tcap = 0, vis_stride = 0;
   bool uploaded = false;
   std::vector<uint8_t> h_deleted;  // host copy of the flags: searches skip the per-neighbour flag load when none is set
   uint64_t n_deleted = 0;
+  // bumped by everything that changes the nodes, their links or their flags (upload, append_nodes, insert_linked,
+  // set_lists, set_entry, set_deleted): a mask (fvdb_mask) built before the bump is refused by the masked searches
+  uint64_t mutations = 0;
+  DBuf s_scan[kSlots];  // exact scan under a mask (allow_masks.h): padded queries and partial lists, one per slot
   // profiling: HIP events around the last launches of the traversal kernel (ring of 64)
   hipEvent_t kev[64][2] = {};
   uint32_t kev_n = 0;   // launches recorded since the last fvdb_graph_kernel_times call
@@ -611,6 +615,7 @@ void fvdb_graph_destroy(fvdb_graph* g) {
   for (auto& b : g->s_visited) b.release();
   for (auto& b : g->s_touched) b.release();
   for (auto& b : g->s_spill) b.release();
+  for (auto& b : g->s_scan) b.release();
   for (DBuf* b : bufs) b->release();
   g->h_state.release();
   g->h_patch.release();
@@ -629,6 +634,7 @@ int fvdb_graph_configure(fvdb_graph* g, uint32_t max_connections, uint32_t max_c
 
 int fvdb_graph_upload(fvdb_graph* g, uint32_t n, const uint32_t* levels, const uint8_t* deleted,
                       const uint32_t* slot_start, const uint32_t* adj, uint32_t entry_node) {
+  g->mutations += 1;
   fvdb_ctx* ctx = g->store->ctx;
   if (n == 0 || n > g->store->rows || entry_node >= n) FAIL(ctx, FVDB_E_INVALID, "graph does not match the store");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -706,6 +712,7 @@ int fvdb_graph_upload(fvdb_graph* g, uint32_t n, const uint32_t* levels, const u
 }
 
 int fvdb_graph_append_nodes(fvdb_graph* g, uint32_t first, uint32_t n_new, const uint32_t* levels) {
+  g->mutations += 1;
   fvdb_ctx* ctx = g->store->ctx;
   if (n_new == 0) return FVDB_OK;
   if (first != g->n || (uint64_t)first + n_new > g->store->rows) FAIL(ctx, FVDB_E_INVALID, "nodes are appended in store-row order");
@@ -756,6 +763,7 @@ int fvdb_graph_append_nodes(fvdb_graph* g, uint32_t first, uint32_t n_new, const
 int fvdb_graph_set_lists(fvdb_graph* g, uint32_t n_lists, const uint32_t* nodes, const uint32_t* layers, const uint32_t* offsets,
                          const uint32_t* nbrs) {
   fvdb_ctx* ctx = g->store->ctx;
+  g->mutations += 1;
   if (n_lists == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint32_t ps = 2 + 64;
@@ -794,6 +802,7 @@ int fvdb_graph_set_lists(fvdb_graph* g, uint32_t n_lists, const uint32_t* nodes,
 }
 
 int fvdb_graph_set_entry(fvdb_graph* g, uint32_t entry_node, uint32_t n_linked) {
+  g->mutations += 1;
   fvdb_ctx* ctx = g->store->ctx;
   if (entry_node >= g->n || n_linked > g->n) FAIL(ctx, FVDB_E_INVALID, "no such node");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -842,6 +851,7 @@ int fvdb_graph_download(fvdb_graph* g, uint32_t* slot_start, uint32_t* adj, uint
 }
 
 int fvdb_graph_set_deleted(fvdb_graph* g, uint32_t node, int deleted) {
+  g->mutations += 1;
   fvdb_ctx* ctx = g->store->ctx;
   if (!g->uploaded || node >= g->n) FAIL(ctx, FVDB_E_NOT_FOUND, "no such node");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -863,6 +873,7 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
                              fvdb_graph_insert_stats* stats) {
   fvdb_store* s = g->store;
   fvdb_ctx* ctx = s->ctx;
+  g->mutations += 1;
   if (n_done) *n_done = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (n == 0) return FVDB_OK;
@@ -953,12 +964,16 @@ int fvdb_graph_search_dev(fvdb_graph* g, const float* q_dev, uint32_t B, uint32_
                                     out_status_dev);
 }
 
-int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
-                               uint32_t ef, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev,
-                               uint32_t* out_status_dev) {
+// The traversal, unmasked (mask == nullptr: the graph's own flags) or under an allow-set mask, whose flags then stand
+// for `deleted` in the one GraphView the kernels are handed.
+static int graph_search_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const fvdb_mask* mask, const float* q_dev, uint32_t B,
+                             uint32_t k, uint32_t ef, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                             uint32_t* out_status_dev) {
   fvdb_store* s = g->store;
   fvdb_ctx* ctx = on ? on : s->ctx;
   if (slot >= fvdb_graph::kSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
+  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
+  if (mask && mask->stamp != g->mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
   if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
   if (s->d != s->dpad && slot != 0) FAIL(ctx, FVDB_E_UNSUPPORTED, "padded dimensions use slot 0 only");
   if (!g->uploaded || !g->has_entry) FAIL(ctx, FVDB_E_INVALID, "graph not uploaded");
@@ -982,8 +997,10 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
     HIPCHK(ctx, g->d_counters.ensure(32));
     HIPCHK(ctx, hipMemsetAsync(g->d_counters.p, 0, 32, ctx->stream));
   }
-  const GraphView gv{s->data, g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(), g->d_adj0.as<uint32_t>(), g->d_ubase.as<uint32_t>(),
-                     g->d_adjU.as<uint32_t>(), g->stride0, g->strideU, g->n, s->dpad, g->entry, g->top_level, g->n_deleted ? 1u : 0u,
+  const uint32_t* deleted = mask ? mask->flags.as<uint32_t>() : g->d_deleted.as<uint32_t>();
+  const uint32_t any_deleted = mask ? 1u : (g->n_deleted ? 1u : 0u);
+  const GraphView gv{s->data, g->d_level.as<uint32_t>(), deleted, g->d_adj0.as<uint32_t>(), g->d_ubase.as<uint32_t>(),
+                     g->d_adjU.as<uint32_t>(), g->stride0, g->strideU, g->n, s->dpad, g->entry, g->top_level, any_deleted,
                      g->d_counters.as<unsigned long long>(), graph_stamps_report(g)};
   hipEvent_t* ev = nullptr;
   if (s->ctx->profiling) {  // the store's context carries the switch, whichever stream the launch goes to
@@ -1008,6 +1025,20 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
   }
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
+}
+
+int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                               uint32_t ef, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                               uint32_t* out_status_dev) {
+  return graph_search_slot(g, on, slot, nullptr, q_dev, B, k, ef, out_nodes_dev, out_dist_dev, out_counts_dev, out_status_dev);
+}
+
+int fvdb_graph_search_dev_slot_masked(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                      uint32_t k, uint32_t ef, uint32_t* out_nodes_dev, float* out_dist_dev,
+                                      uint32_t* out_counts_dev, uint32_t* out_status_dev) {
+  if (!g) return FVDB_E_INVALID;
+  if (!mask) FAIL(on ? on : g->store->ctx, FVDB_E_INVALID, "null mask");
+  return graph_search_slot(g, on, slot, mask, q_dev, B, k, ef, out_nodes_dev, out_dist_dev, out_counts_dev, out_status_dev);
 }
 
 int fvdb_graph_tie_restarts(fvdb_graph* g, uint64_t* queries, uint64_t* searched_again) {
@@ -1052,3 +1083,27 @@ int fvdb_graph_kernel_times(fvdb_graph* g, float* ms_sum, uint32_t* launches, ui
 }
 
 }  // extern "C"
+
+// what allow_masks.h builds a graph mask from, and the inputs of its exact scan
+int graph_mask_source(fvdb_graph* g, GraphMaskSource* out) {
+  out->store = g->store;
+  out->deleted = g->d_deleted.as<uint32_t>();
+  out->n = g->uploaded ? g->n : 0;
+  out->mutations = g->mutations;
+  return FVDB_OK;
+}
+int graph_scan_inputs(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, const float* q_dev, uint32_t B, size_t part_bytes,
+                      const float** queries, uint64_t** part) {
+  const fvdb_store* s = g->store;
+  DBuf& scratch = g->s_scan[slot];
+  const size_t q_bytes = s->d != s->dpad ? (((size_t)B * s->dpad * 4 + 255) & ~(size_t)255) : 0;
+  HIPCHK(ctx, scratch.ensure(std::max<size_t>(q_bytes + part_bytes, 8)));
+  *queries = q_dev;
+  if (q_bytes) {
+    hipLaunchKernelGGL(graph_pad_rows_kernel, dim3(cdiv((uint64_t)B * s->dpad, 256)), dim3(256), 0, ctx->stream, q_dev, s->d,
+                       s->dpad, (uint64_t)B, scratch.as<float>());
+    *queries = scratch.as<float>();
+  }
+  *part = (uint64_t*)((char*)scratch.p + q_bytes);
+  return FVDB_OK;
+}

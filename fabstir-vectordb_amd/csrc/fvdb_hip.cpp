@@ -134,6 +134,10 @@ enum FbWord : uint32_t {
   FB_WORDS = 8,     // [7] unused
 };
 constexpr size_t kFbBytes = FB_WORDS * 4;
+// The index keeps the block twice, one after the other: the second copy takes the counts of the searches under an
+// allow-set mask, so that what AUTO's watches read (the first, through its pinned copy) is the unmasked traffic alone.
+// The public counters report the sum of both.
+constexpr size_t kFbAllBytes = 2 * kFbBytes;
 constexpr uint32_t kFbReasonWords = 5;  // fvdb_ivf_scan_fallback_reasons: words 2..6, the four reasons and the refine counter
 
 // Stage events of a search, recorded while profiling is on; finish_profile turns pairs of them into stage times.
@@ -213,7 +217,7 @@ struct fvdb_ivf : IvfScratch {
   DBuf d_cent_pad;       // [nlist][dpad] zero padded (only when d != dpad)
   DBuf d_cnorm, d_cnmax; // |c|^2 per centroid, max |c|^2 (matrix-core coarse stage)
   DBuf s_fallbacks;      // counter block (FbWord)
-  uint32_t* fb_word(FbWord w) const { return s_fallbacks.as<uint32_t>() + w; }
+  uint32_t* fb_word(FbWord w, bool masked = false) const { return s_fallbacks.as<uint32_t>() + (masked ? FB_WORDS : 0) + w; }
   int coarse_mode = 0;   // 0 = matrix cores + exact verification when applicable, 1 = exact scan only
   int scan_mode = 0;     // same choice for the inverted-list scan
   // AUTO scan mode watches its own hit rate: the rescan counter is copied to pinned host memory behind every
@@ -240,6 +244,9 @@ struct fvdb_ivf : IvfScratch {
   std::vector<std::vector<uint32_t>> list_blocks;  // per list: pool block indices
   std::vector<uint32_t> list_len;                  // rows per list (including soft-deleted)
   uint64_t total_rows = 0;
+  // bumped by everything that changes the rows a search sees or where they sit (add, set_deleted, clear, new centroids,
+  // compact, refill, reserve): a mask (fvdb_mask) built before the bump is refused by the masked searches
+  uint64_t mutations = 0;
   uint32_t max_list_blocks = 0;
   bool table_dirty = true;
   DBuf t_off, t_blocks, t_glob, t_len;  // device list table, logical (global) block counts, rows per list
@@ -268,8 +275,17 @@ struct Env {
   fvdb_ctx* ctx;
   IvfScratch* S;
   const float* given_thr = nullptr;  // sharded search: filter thresholds already agreed between the ranks ([B], device)
+  const uint64_t* live = nullptr;    // masked search: these words stand for pool.valid in every stage of the list scan
 };
 inline IvfScratch& slot_scratch(fvdb_ivf* ivf, uint32_t slot) { return slot == 0 ? *ivf : ivf->spare[slot - 1]; }
+// The liveness words of the inverted lists as this search sees them, and the pool with them in place: the one place
+// every argument block of the list scan takes them from.
+inline const uint64_t* live_words(const fvdb_ivf* ivf, const Env& E) { return E.live ? E.live : ivf->pool.valid; }
+inline PoolView list_pool(const fvdb_ivf* ivf, const Env& E) {
+  PoolView v = ivf->pool.view();
+  v.valid = live_words(ivf, E);
+  return v;
+}
 }  // namespace
 
 
@@ -581,13 +597,13 @@ int run_fine_exact(fvdb_ivf* ivf, const Env& E, const Batch& b, int role) {
   launch_plan(ivf, E, b.probes, b.B * b.np, b.np, segb, Q, scan_stats(S), /*rezero_cnt=*/nullptr);
   mark(ivf, E, EV_SCAN_BEGIN);
   const ListTable lists = list_table(ivf);
-  ScanLaunch s{ivf->pool.view(), lists.off, lists.blocks, nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(),
+  ScanLaunch s{list_pool(ivf, E), lists.off, lists.blocks, nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(),
                S.s_entries.as<uint2>(), S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.k, b.np,
                maxsegs, S.s_part.as<uint2>()};
   s.f16 = ivf->f16;
   launch_scan(ctx, s, role);
   mark(ivf, E, EV_SCAN_DONE);
-  launch_merge(ctx, merge_args(ivf->pool.view(), lists, ivf->t_glob.as<uint32_t>(), S.s_part, maxsegs, segb, b));
+  launch_merge(ctx, merge_args(list_pool(ivf, E), lists, ivf->t_glob.as<uint32_t>(), S.s_part, maxsegs, segb, b));
   mark(ivf, E, EV_FINE_DONE);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
@@ -682,11 +698,12 @@ void launch_prep_queries(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_
                      S.s_scnt.as<uint32_t>(), S.s_mslots.as<uint32_t>());
 }
 
-ThresholdArgs threshold_args(fvdb_ivf* ivf, const IvfScratch& S, const float* qpad, const uint32_t* probes, uint32_t B,
+ThresholdArgs threshold_args(fvdb_ivf* ivf, const Env& E, const float* qpad, const uint32_t* probes, uint32_t B,
                              uint32_t k, uint32_t np, float* thr_out) {
+  const IvfScratch& S = *E.S;
   ThresholdArgs t{};
   t.rows = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
-  t.pool_valid = ivf->pool.valid;
+  t.pool_valid = live_words(ivf, E);
   t.pool_norms = ivf->pool.norms;
   t.d4 = ivf->d4;
   t.lists = list_table(ivf);
@@ -715,7 +732,7 @@ MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, uint
   const IvfScratch& S = *E.S;
   MfmaScanArgs a{};
   a.pool_data = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
-  a.pool_valid = ivf->pool.valid;
+  a.pool_valid = live_words(ivf, E);
   a.pool_norms = ivf->pool.norms;
   a.d4 = ivf->d4;
   a.list_off = ivf->t_off.as<uint32_t>();
@@ -767,7 +784,7 @@ void mfma_threshold(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch&
   IvfScratch& S = *E.S;
   if (E.given_thr) return;
   if (!ivf_knobs().mfma_threshold_pass) {
-    launch_threshold_direct(ivf, ctx, threshold_args(ivf, S, b.qpad, b.probes, b.B, b.k, b.np, S.s_thr.as<float>()));
+    launch_threshold_direct(ivf, ctx, threshold_args(ivf, E, b.qpad, b.probes, b.B, b.k, b.np, S.s_thr.as<float>()));
     return;
   }
   hipLaunchKernelGGL(first_probe_kernel, dim3(cdiv(b.B, 256)), dim3(256), 0, ctx->stream, b.probes, b.B, b.np,
@@ -920,7 +937,7 @@ int mfma_refine(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, 
   HIPCHK(ctx, S.s_probes2.ensure((size_t)b.B * b.np * 4));
   hipLaunchKernelGGL(refine_threshold_kernel, dim3(cdiv(b.B, 4)), dim3(256), 0, ctx->stream, S.s_sdist.as<float>(),
                      S.s_scnt.as<uint32_t>(), b.probes, S.s_qn2.as<float>(), ivf->d_xmax.as<uint32_t>(), b.B, b.np, P.ka, P.cmax,
-                     ivf->dpad, P.x_rounded, S.s_thr.as<float>(), S.s_probes2.as<uint32_t>(), ivf->fb_word(FB_REFINED));
+                     ivf->dpad, P.x_rounded, S.s_thr.as<float>(), S.s_probes2.as<uint32_t>(), ivf->fb_word(FB_REFINED, E.live != nullptr));
   launch_plan(ivf, E, S.s_probes2.as<uint32_t>(), b.B * b.np, b.np, P.segb, P.Q, nullptr, S.s_cnt.as<uint32_t>(), P.lsplit,
               P.segb_tail);
   launch_filter(ctx, a, P);
@@ -931,7 +948,7 @@ int mfma_refine(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, 
 VerifyArgs verify_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b) {
   const IvfScratch& S = *E.S;
   VerifyArgs v{};
-  v.pool = ivf->pool.view();
+  v.pool = list_pool(ivf, E);
   v.lists = list_table(ivf);
   v.probes = b.probes;
   v.glob_blocks = ivf->t_glob.as<uint32_t>();
@@ -956,8 +973,8 @@ VerifyArgs verify_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Bat
   v.out_dist = b.out_dist;
   v.out_counts = b.out_counts;
   v.out_keys = b.out_keys;
-  v.fallbacks = ivf->fb_word(FB_SCAN);
-  v.reasons = ivf->fb_word(FB_REASONS);
+  v.fallbacks = ivf->fb_word(FB_SCAN, E.live != nullptr);
+  v.reasons = ivf->fb_word(FB_REASONS, E.live != nullptr);
   v.fail_list = S.s_fail.as<uint32_t>();
   v.nfail = S.s_scnt.as<uint32_t>() + b.B;
   return v;
@@ -970,7 +987,7 @@ void launch_select(fvdb_ivf* ivf, fvdb_ctx* ctx, const VerifyArgs& v) {
 FallbackArgs fallback_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const VerifyArgs& v) {
   const IvfScratch& S = *E.S;
   FallbackArgs fa{};
-  fa.pool = ivf->pool.view();
+  fa.pool = list_pool(ivf, E);
   fa.lists = v.lists;
   fa.probes = b.probes;
   fa.queries = b.qpad;
@@ -1036,8 +1053,10 @@ int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   launch_select(ivf, ctx, v);
   mfma_rescan(ivf, E, P, b, v);
   mark(ivf, E, EV_FINE_DONE);
-  rc = mfma_watch_counters(ivf, ctx, b.B);
-  if (rc) return rc;
+  if (!E.live) {  // a masked batch is none of the watches' business: it counts into the second block
+    rc = mfma_watch_counters(ivf, ctx, b.B);
+    if (rc) return rc;
+  }
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }
@@ -1049,6 +1068,9 @@ int run_fine(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_
   // beyond the shape: this index's own state (norms, lists rather than the one flat list), which thr_share_ok must not ask
   bool mfma = (ivf->scan_mode == FVDB_SCAN_AUTO || ivf->scan_mode == FVDB_SCAN_FILTER) && !ivf_knobs().scan_exact &&
               mfma_shape_ok(ivf, B, k, np) && role == ROLE_LIST && ivf->pool.norms != nullptr;
+  // a mask thins the lists the filter samples its threshold from: AUTO scans exactly under one and keeps its hit-rate
+  // watch for the unmasked traffic (FVDB_SCAN_FILTER still forces the filter)
+  if (mfma && E.live && ivf->scan_mode == FVDB_SCAN_AUTO) mfma = false;
   if (mfma && ivf->scan_mode == FVDB_SCAN_AUTO && auto_backs_off(ivf)) mfma = false;
   if (mfma) return run_fine_mfma(ivf, E, b);
   return run_fine_exact(ivf, E, b, role);
@@ -1146,7 +1168,7 @@ int ivf_shared_thresholds(fvdb_ivf* ivf, const Env& E, const float* q_dev, const
   HIPCHK(ctx, S.s_scnt.ensure((size_t)(B + 2) * 4));
   HIPCHK(ctx, S.s_mslots.ensure((size_t)B * 64 * 4));
   launch_prep_queries(ivf, E, qpad, B);
-  ThresholdArgs t = threshold_args(ivf, S, qpad, probes, B, k, np, u_out);
+  ThresholdArgs t = threshold_args(ivf, E, qpad, probes, B, k, np, u_out);
   t.glob_blocks = ivf->t_glob.as<uint32_t>();
   launch_threshold_direct(ivf, ctx, t);
   HIPCHK(ctx, hipGetLastError());
@@ -1464,6 +1486,7 @@ void fvdb_ivf_destroy(fvdb_ivf* ivf) {
 }
 
 static int install_centroids(fvdb_ivf* ivf, const float* d_rowmajor /* device [nlist][d] */) {
+  ivf->mutations += 1;
   fvdb_ctx* ctx = ivf->ctx;
   const uint32_t nlist = ivf->nlist, cblocks = cdiv(nlist, 64);
   int rc = ivf->cpool.reserve(ctx, cblocks);
@@ -1497,12 +1520,12 @@ static int install_centroids(fvdb_ivf* ivf, const float* d_rowmajor /* device [n
   }
   HIPCHK(ctx, ivf->d_cnorm.ensure((size_t)nlist * 4));
   HIPCHK(ctx, ivf->d_cnmax.ensure(4));
-  HIPCHK(ctx, ivf->s_fallbacks.ensure(kFbBytes));
+  HIPCHK(ctx, ivf->s_fallbacks.ensure(kFbAllBytes));
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(nlist, 256)), dim3(256), 0, ctx->stream, cpad, ivf->dpad, ivf->dpad,
                      nlist, ivf->d_cnorm.as<float>());
   hipLaunchKernelGGL(max_f32_kernel, dim3(1), dim3(64), 0, ctx->stream, ivf->d_cnorm.as<float>(), nlist,
                      ivf->d_cnmax.as<float>());
-  HIPCHK(ctx, hipMemsetAsync(ivf->s_fallbacks.p, 0, kFbBytes, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ivf->s_fallbacks.p, 0, kFbAllBytes, ctx->stream));
   if (ivf->h_fb.p) *(volatile uint32_t*)ivf->h_fb.p = 0;
   ivf->mfma_q = ivf->fb_seen = ivf->q_seen = 0;
   ivf->exact_batches_left = ivf->backoff_len = 0;
@@ -1548,6 +1571,7 @@ int fvdb_ivf_get_centroids(fvdb_ivf* ivf, float* out) {
 }
 
 int fvdb_ivf_clear(fvdb_ivf* ivf) {
+  ivf->mutations += 1;
   fvdb_ctx* ctx = ivf->ctx;
   reset_lists(ivf);
   if (ivf->pool.valid && ivf->pool.cap_blocks)
@@ -1556,6 +1580,7 @@ int fvdb_ivf_clear(fvdb_ivf* ivf) {
 }
 
 int fvdb_ivf_reserve(fvdb_ivf* ivf, uint64_t n_rows) {
+  ivf->mutations += 1;
   HIPCHK(ivf->ctx, hipSetDevice(ivf->ctx->device));
   // every list may end in a partly filled block
   return ivf->pool.reserve(ivf->ctx, cdiv(n_rows, 64) + ivf->nlist);
@@ -1650,6 +1675,7 @@ int fvdb_ivf_assign(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t* out_clu
 
 // rows already staged in s_in (device, row-major); clusters on host
 static int append_staged(fvdb_ivf* ivf, const uint64_t* ids, uint64_t n, const uint32_t* cluster, uint32_t* out_pos) {
+  ivf->mutations += 1;
   fvdb_ctx* ctx = ivf->ctx;
   // count new blocks first so the pool grows once
   std::vector<uint32_t> add_len(ivf->nlist, 0);
@@ -1737,6 +1763,7 @@ int fvdb_ivf_add(fvdb_ivf* ivf, const float* x, const uint64_t* ids, uint64_t n,
 int fvdb_ivf_set_deleted(fvdb_ivf* ivf, const uint32_t* cluster, const uint32_t* pos, uint64_t n, int deleted) {
   fvdb_ctx* ctx = ivf->ctx;
   if (n == 0) return FVDB_OK;
+  ivf->mutations += 1;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::vector<uint32_t> slots(n);
   for (uint64_t i = 0; i < n; ++i) {
@@ -1893,6 +1920,40 @@ int fvdb_ivf_search_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const f
   if (rc) return rc;
   return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
                                          out_keys_dev));
+}
+
+// The same two searches under an allow-set mask (fvdb_mask_create_ivf): the mask's words take the place of the pool's
+// live words in every stage that reads them.  A mask built before the index last changed is refused.
+static int mask_env(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, Env* E) {
+  if (!ivf) return FVDB_E_INVALID;
+  int rc = slot_env(ivf, on, slot, E);
+  if (rc) return rc;
+  if (!mask || mask->ivf != ivf) FAIL(ivf->ctx, FVDB_E_INVALID, "mask of another index");
+  if (mask->stamp != ivf->mutations) FAIL(ivf->ctx, FVDB_E_INVALID, "stale mask: the index changed after the mask was created");
+  E->live = mask->words.as<uint64_t>();
+  return FVDB_OK;
+}
+
+int fvdb_ivf_search_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                    uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  Env E{};
+  int rc = mask_env(ivf, on, slot, mask, &E);
+  if (rc) return rc;
+  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
+                                         out_keys_dev));
+}
+
+int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                           const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                           uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                                           uint64_t* out_keys_dev) {
+  Env E{};
+  int rc = mask_env(ivf, on, slot, mask, &E);
+  if (rc) return rc;
+  if (!probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null probes");
+  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
+                                         out_keys_dev, probes_dev));
 }
 
 int fvdb_ivf_search_all_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint64_t* out_ids_dev,
@@ -2083,11 +2144,11 @@ static int read_counters(fvdb_ivf* ivf, FbWord first, uint32_t n, uint64_t* out)
   fvdb_ctx* ctx = ivf->ctx;
   for (uint32_t i = 0; i < n; ++i) out[i] = 0;
   if (!ivf->s_fallbacks.p) return FVDB_OK;
-  uint32_t v[FB_WORDS] = {};
+  uint32_t v[2 * FB_WORDS] = {};  // the unmasked searches' block, then the masked searches'
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpyAsync(v, ivf->fb_word(first), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(v, ivf->s_fallbacks.p, kFbAllBytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (uint32_t i = 0; i < n; ++i) out[i] = v[i];
+  for (uint32_t i = 0; i < n; ++i) out[i] = (uint64_t)v[first + i] + v[FB_WORDS + first + i];
   return FVDB_OK;
 }
 int fvdb_ivf_scan_fallbacks(fvdb_ivf* ivf, uint64_t* out) { return read_counters(ivf, FB_SCAN, 1, out); }
@@ -2696,3 +2757,4 @@ int fvdb_scorer_run(fvdb_scorer* sc, uint32_t B, uint32_t C) {
 
 #include "ivf_maint.h"
 #include "comm_sharded.h"
+#include "allow_masks.h"

@@ -102,3 +102,35 @@ struct fvdb_scorer {
   float* d_dist = nullptr;
   DBuf s_rows, s_in;  // private scratch: scorers are driven from different host threads
 };
+
+// ---- allow-set masks (allow_masks.h) ---------------------------------------------------------
+// A mask is a second liveness view of one index: pool words for an IVF index, per-node flags and the ascending list
+// of allowed live nodes for a graph.  It is immutable once created and owns its buffers, so searches in any number of
+// slots may read it at once.  `stamp` is the index's mutation counter at creation: a masked search compares it first.
+struct fvdb_ivf;
+struct fvdb_graph;
+struct fvdb_mask {
+  fvdb_ctx* ctx = nullptr;
+  fvdb_ivf* ivf = nullptr;      // exactly one of ivf / graph is set
+  fvdb_graph* graph = nullptr;
+  uint64_t stamp = 0;
+  uint64_t allowed_live = 0;    // rows (nodes) that are live in the index and in the allow-set
+  uint32_t units = 0;           // pool blocks / graph nodes the buffers cover
+  DBuf words;                   // IVF: valid[blk] & allow[blk], one word per pool block
+  DBuf flags;                   // graph: deleted[node] | !allowed[node], one uint32_t per node
+  DBuf nodes;                   // graph: allowed live node indices, ascending
+};
+
+// what allow_masks.h needs of a graph to build a mask and to scan under one, filled in by fvdb_graph.cpp
+struct GraphMaskSource {
+  fvdb_store* store;
+  const uint32_t* deleted;  // [n]
+  uint32_t n;
+  uint64_t mutations;
+};
+int graph_mask_source(fvdb_graph* g, GraphMaskSource* out);
+// the exact scan's inputs from the slot's scratch, enqueued on ctx's stream: the B queries at the store's row stride
+// (q_dev itself when d == dpad, else a zero-padded copy) and room for part_bytes of partial lists
+int graph_scan_inputs(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, const float* q_dev, uint32_t B, size_t part_bytes,
+                      const float** queries, uint64_t** part);
+constexpr uint32_t kGraphSlots = 16;

@@ -133,6 +133,7 @@ int fresh_pool(fvdb_ctx* ctx, const Pool& like, uint32_t blocks, Pool* out) {
 int repartition(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n, uint32_t* out_pos, uint64_t* out_ids, DBufs& T,
                 fvdb_maintenance_info_t* info) {
   fvdb_ctx* ctx = dst->ctx;
+  dst->mutations += 1;  // rows move: masks of dst are stale from here on
   const uint32_t nlist = dst->nlist;
   if (nlist > kRankMaxLists)
     FAIL(ctx, FVDB_E_UNSUPPORTED, "re-partition ranks destinations with one LDS counter per list: at most 16384 lists");

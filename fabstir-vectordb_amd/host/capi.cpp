@@ -46,6 +46,12 @@ int fvh_ivf_search(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, 
                    float* dist, uint32_t* counts) {
   return ((IVFIndex*)p)->search(q, B, d, k, n_probe, ids, dist, counts);
 }
+// filtered search: the allow-set is applied inside the search
+int fvh_ivf_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t n_probe, const uint64_t* allowed,
+                           uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((IVFIndex*)p)->search_allowed(q, B, d, k, n_probe, allowed, n_allowed, ids, dist, counts);
+}
+uint64_t fvh_ivf_mask_builds(void* p) { return ((IVFIndex*)p)->mask_builds(); }
 int fvh_ivf_mark_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->mark_deleted(id); }
 int fvh_ivf_is_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->is_deleted(id); }
 void* fvh_ivf_device(void* p) { return ((IVFIndex*)p)->device(); }
@@ -114,6 +120,14 @@ int fvh_hnsw_search(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k,
                     float* dist, uint32_t* counts) {
   return ((HNSWIndex*)p)->search(q, B, d, k, ef, ids, dist, counts);
 }
+int fvh_hnsw_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, const uint64_t* allowed,
+                            uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_allowed(q, B, d, k, ef, allowed, n_allowed, ids, dist, counts);
+}
+void fvh_hnsw_set_scan_cutoff(void* p, uint64_t nodes) { ((HNSWIndex*)p)->set_scan_cutoff(nodes); }
+uint64_t fvh_hnsw_scan_cutoff(void* p) { return ((HNSWIndex*)p)->scan_cutoff(); }
+void* fvh_hnsw_device_graph(void* p) { return ((HNSWIndex*)p)->device_graph(); }
+uint64_t fvh_hnsw_mask_builds(void* p) { return ((HNSWIndex*)p)->mask_builds(); }
 uint64_t fvh_hnsw_node_count(void* p) { return ((HNSWIndex*)p)->node_count(); }
 uint64_t fvh_hnsw_active_count(void* p) { return ((HNSWIndex*)p)->active_count(); }
 int fvh_hnsw_entry_point(void* p, uint64_t* out) { return ((HNSWIndex*)p)->entry_point(out) ? 0 : FVDB_E_NOT_FOUND; }
@@ -206,6 +220,20 @@ int fvh_hybrid_search(void* p, const float* q, uint32_t B, uint32_t d, uint64_t 
   c.recent_k = recent_k;
   c.historical_k = historical_k;
   return ((HybridIndex*)p)->search(q, B, d, c, now, ids, dist, counts);
+}
+int fvh_hybrid_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
+                              int search_recent, int search_historical, uint64_t recent_k, uint64_t historical_k,
+                              const uint64_t* allowed, uint64_t n_allowed, double now, uint64_t* ids, float* dist,
+                              uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = ef;
+  c.ivf_n_probe = nprobe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  c.recent_k = recent_k;
+  c.historical_k = historical_k;
+  return ((HybridIndex*)p)->search_allowed(q, B, d, c, allowed, n_allowed, now, ids, dist, counts);
 }
 // search_with_filter (src/hybrid/core.rs:513-549): `matches(id, user)` is the host application's metadata lookup +
 // MetadataFilter::matches (0 = no metadata or no match); NULL = no filter.

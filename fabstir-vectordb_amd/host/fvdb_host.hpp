@@ -9,6 +9,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -94,6 +95,16 @@ struct DevBuf {
   }
 };
 
+// Filtered search (include/fvdb.h "allow-set masks"): a device mask shared by the searches that
+// use it.  An index keeps the last one it built, keyed by the id list; it is rebuilt when the list differs or the
+// device index has changed since (fvdb_mask_info stale).  A search holds its own reference while it runs.
+typedef std::shared_ptr<fvdb_mask> MaskRef;
+inline MaskRef adopt_mask(fvdb_mask* m) { return MaskRef(m, [](fvdb_mask* p) { fvdb_mask_destroy(p); }); }
+inline bool mask_fresh(const MaskRef& m) {
+  fvdb_mask_info_t info;
+  return m && fvdb_mask_info(m.get(), &info) == FVDB_OK && !info.stale;
+}
+
 // The context (stream) of one in-flight slot, made on first use: borrowed from the index (slot 0) or created.
 inline int slot_ctx(fvdb_ctx* base, bool borrow, fvdb_ctx** ctx) {
   if (*ctx) return FVDB_OK;
@@ -136,6 +147,14 @@ class IVFIndex {
   // `on` / `slot`: run on another context's stream with that slot's scratch set (several searches in flight)
   int search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, uint64_t* ids_dev,
                  float* dist_dev, uint32_t* counts_dev, fvdb_ctx* on = nullptr, uint32_t slot = 0);
+  // search under an allow-set: what search() returns after mark_deleted of every id outside allowed[n_allowed]
+  int search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const uint64_t* allowed,
+                     uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts);
+  // the device mask for that allow-set (cached); search_dev under it
+  int allowed_mask(const uint64_t* allowed, uint64_t n_allowed, MaskRef* out);
+  int search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe,
+                        uint64_t* ids_dev, float* dist_dev, uint32_t* counts_dev, fvdb_ctx* on = nullptr, uint32_t slot = 0);
+  uint64_t mask_builds() const { return mask_builds_; }
   int mark_deleted(uint64_t id);                                                  // operations.rs:569
   bool is_deleted(uint64_t id) const { return deleted_.count(id) > 0; }
   uint64_t active_count() const { return total_ - deleted_.size(); }
@@ -181,6 +200,16 @@ class IVFIndex {
   uint64_t total_ = 0;
   std::unordered_multimap<uint64_t, Loc> where_;  // id -> every list position holding it
   std::unordered_set<uint64_t> deleted_;
+  std::mutex mask_mu_;  // the cached mask: several search threads may ask at once
+  std::vector<uint64_t> mask_key_;
+  MaskRef mask_;
+  uint64_t mask_builds_ = 0;
+  std::mutex allowed_mu_;           // search_allowed's staging blocks
+  DevBuf allowed_q_, allowed_out_;  // search_allowed: staged queries, result block and its pinned copy
+  void drop_mask() {
+    mask_.reset();
+    mask_key_.clear();
+  }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -193,6 +222,14 @@ struct HNSWConfig {
 
 class HNSWIndex {
  public:
+  // Filtered search.  AllowView = the allow-set as this index sees it: the device mask over node indices and the host
+  // copy of the same flags (deleted | not allowed, per node) for the queries the traversal hands back to the host walk.
+  struct AllowView {
+    MaskRef mask;
+    std::vector<uint8_t> eff;
+    uint64_t allowed_live = 0;
+  };
+  typedef std::shared_ptr<const AllowView> ViewRef;
   HNSWIndex(fvdb_ctx* ctx, const HNSWConfig& cfg);
   ~HNSWIndex();
   const HNSWConfig& config() const { return cfg_; }
@@ -223,6 +260,8 @@ class HNSWIndex {
   const fvdb_graph_insert_stats& insert_stats() const { return insert_stats_; }  // sums since construction
   uint64_t host_path_inserts() const { return n_host_inserts_; }
   uint64_t graph_upload_bytes() const { return graph_ ? fvdb_graph_upload_bytes(graph_) : 0; }
+  // the device graph as the searches see it (brought up to date first), for callers that drive the C ABI themselves
+  fvdb_graph* device_graph() { return sync_graph() == FVDB_OK ? graph_ : nullptr; }
   int search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
              uint32_t* counts);                                                    // :398 (batched, lock-step hops)
   int search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
@@ -233,9 +272,24 @@ class HNSWIndex {
   // Device traversal split in two so that several batches can be in flight: begin enqueues the launch and the
   // result copies on the slot's own stream (slot < kSlots), end waits for that slot and finishes on the host.
   static constexpr uint32_t kSlots = 16;
-  bool search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc, uint32_t slot = 0);
+  // `view` (optional): the search runs under that allow-set — masked traversal, or the exact scan when scans(view, k)
+  bool search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc, uint32_t slot = 0,
+                        const AllowView* view = nullptr);
   int search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                     uint32_t* counts, uint32_t slot = 0);
+                     uint32_t* counts, uint32_t slot = 0, const AllowView* view = nullptr);
+  int allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out);  // cached like IVFIndex::allowed_mask
+  // search under an allow-set: what search() returns after mark_deleted of every id outside it — unless the allowed
+  // live nodes number at most scan_cutoff(): then they are scanned exactly (best k by distance bits, then node index)
+  int search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
+                     uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts);
+  // the same with the view at hand and the queries in HBM (HybridIndex, when its traversal was not enqueued)
+  int search_dev_view(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
+                      uint64_t* ids, float* dist, uint32_t* counts);
+  // 0 = never scan, UINT64_MAX = always.  The default is a guess nobody has measured.
+  void set_scan_cutoff(uint64_t nodes) { scan_cutoff_ = nodes; }
+  uint64_t scan_cutoff() const { return scan_cutoff_; }
+  bool scans(const AllowView& v, uint32_t k) const { return v.allowed_live <= scan_cutoff_ && k <= FVDB_MAX_K; }
+  uint64_t mask_builds() const { return mask_builds_; }
   int mark_deleted(uint64_t id);                                                   // operations.rs:127
   bool is_deleted(uint64_t id) const;
   uint64_t active_count() const;
@@ -293,6 +347,7 @@ class HNSWIndex {
     uint32_t cap_B = 0, cap_C = 0;
     std::vector<Query> qs;
     std::vector<uint32_t> prev_cnt;  // candidates each scorer row holds from the hop before: what the next hop blanks
+    const uint8_t* del = nullptr;    // the deleted flags this walk sees: nullptr = deleted_, else an AllowView's
   };
   Walk search_walk_, insert_walk_;
   uint32_t cap(uint32_t layer) const { return layer == 0 ? cfg_.max_connections_layer_0 : cfg_.max_connections; }
@@ -304,15 +359,18 @@ class HNSWIndex {
   int score_pairs_from_row(uint32_t base_row, const std::vector<uint32_t>& cands, std::vector<float>& out);
   int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
                   float* dist, uint32_t* counts);
+  int search_view_locked(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
+                         uint64_t* ids, float* dist, uint32_t* counts);  // the caller holds search_mu_
   int sync_graph();
   bool device_path_ok(uint32_t ef) const;
-  int device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot);
+  int device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot, const AllowView* view = nullptr);
+  // scanned: the block came from the exact scan, which writes no status words
   int device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts, std::vector<uint32_t>& failed,
-                     uint32_t slot);
+                     uint32_t slot, bool scanned = false);
   int finish_failed(const float* q, bool q_on_device, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                    uint32_t* counts, const std::vector<uint32_t>& failed);
+                    uint32_t* counts, const std::vector<uint32_t>& failed, const AllowView* view = nullptr);
   int search_host_walk(const float* q, bool q_on_device, uint32_t B, uint32_t k, uint32_t ef, uint64_t* ids,
-                       float* dist, uint32_t* counts);
+                       float* dist, uint32_t* counts, const AllowView* view = nullptr);
   // The adjacency lists exist twice: nbrs_ (host) and the fixed-stride rows in HBM (graph_).  host_ahead_: nbrs_ holds
   // changes the device has not seen (restore, bulk build, vacuum, inserts made before the device graph existed) — the
   // next device use installs the whole graph once.  dev_ahead_: device inserts have linked nodes whose lists nbrs_
@@ -357,6 +415,11 @@ class HNSWIndex {
   // Searches may come from several host threads (HybridIndex leases a slot per call): the graph mirror is synced by
   // one of them, the rare host-walk fallback and the standalone search()/search_dev() entry points are serialised.
   std::mutex sync_mu_, walk_mu_, search_mu_;
+  uint64_t scan_cutoff_ = 8192;
+  std::mutex view_mu_;  // the cached allow view
+  std::vector<uint64_t> view_key_;
+  ViewRef view_;
+  uint64_t mask_builds_ = 0;
 
   fvdb_ctx* ctx_;
   HNSWConfig cfg_;
@@ -449,6 +512,13 @@ class HybridIndex {
   typedef int (*FilterFn)(uint64_t id, void* user);
   int search_with_filter(const float* q, uint32_t B, uint32_t dim, uint64_t k, FilterFn matches, void* user, double now,
                          uint64_t* ids, float* dist, uint32_t* counts);
+  // Filtered search with the allow-set applied inside both parts (no counterpart in the reference): what search()
+  // returns after remove() of every id outside allowed[n_allowed]; the recent part is scanned exactly instead when
+  // its allowed live nodes number at most recent().scan_cutoff().  The masks are built after the auto-migration step
+  // and under the same read lock as the search, so they match the rows searched; the last pair is kept for a caller
+  // that repeats one filter.  FVDB_E_UNSUPPORTED once the index is sharded.
+  int search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,
+                     uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* counts);
   // Concurrency (reference: tokio RwLock, searches = readers, src/hybrid/core.rs:457,466): search() / search_dev() /
   // search_with_filter() may be called from any number of host threads; each call leases a free slot (stream,
   // traversal state, IVF scratch set, result blocks) and returns it.  Mutations wait for those calls to finish.
@@ -507,7 +577,8 @@ class HybridIndex {
  private:
   static double age_of(double now, double ts) { return now - ts < 0 ? 0.0 : now - ts; }
   int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                  double now, uint64_t* ids, float* dist, uint32_t* counts);
+                  double now, uint64_t* ids, float* dist, uint32_t* counts, const uint64_t* allowed = nullptr,
+                  uint64_t n_allowed = 0, bool masked = false);
   // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                      int shard_mode, double now);
@@ -556,6 +627,9 @@ class HybridIndex {
     DevBuf d_q;  // staging for host-resident query batches of the blocking entry points
     const float* q = nullptr;
     uint32_t B = 0, dim = 0, k = 0, rk = 0, hk = 0, ef = 0;
+    // a search under an allow-set holds its masks here from begin to end
+    MaskRef ivf_mask;
+    HNSWIndex::ViewRef view;
   };
   Slot slots_[kSlots];
   // Slot::active held for a scope: set under slot_mu_, cleared on release with the waiting writers and searches woken.

@@ -139,6 +139,7 @@ static inline bool set_insert(std::vector<uint32_t>& s, uint32_t v) {
 HNSWIndex::HNSWIndex(fvdb_ctx* ctx, const HNSWConfig& cfg) : ctx_(ctx), cfg_(cfg), rng_(cfg.seed) {}
 
 HNSWIndex::~HNSWIndex() {
+  view_.reset();  // the cached mask goes before the graph it points into
   if (graph_) fvdb_graph_destroy(graph_);
   for (uint32_t i = 0; i < kSlots; ++i) {
     slots_[i].buf.release();
@@ -233,6 +234,7 @@ int HNSWIndex::search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer) {
   const float* dist = fvdb_scorer_dist_buffer(w.sc);
   static const int auto_threads = usable_cpus();
   const int nt = B >= 32 ? std::max(1, threads_ > 0 ? threads_ : auto_threads) : 1;  // OpenMP threads of the host phases
+  const uint8_t* del = w.del ? w.del : deleted_.data();  // a filtered search sees the nodes outside its allow-set as deleted
 
 #pragma omp parallel for schedule(static) num_threads(nt) if (nt > 1)
   for (uint32_t b = 0; b < B; ++b) {
@@ -272,7 +274,7 @@ int HNSWIndex::search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer) {
             for (uint32_t nbv : nbrs_[node][layer]) {
               if (!s.visited.insert(nbv)) continue;  // :506-507
               if (!registered_[nbv]) continue;       // nodes.get() == None (:509)
-              if (deleted_[nbv]) continue;           // :511-513
+              if (del[nbv]) continue;                // :511-513
               s.pending.push_back(nbv);
             }
           }
@@ -433,7 +435,7 @@ struct WalkBlock {
 }  // namespace
 
 // whole batch in one launch, results copied to pinned host memory — all asynchronous on the slot's stream
-int HNSWIndex::device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot) {
+int HNSWIndex::device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot, const AllowView* view) {
   if (slot >= kSlots) return FVDB_E_INVALID;
   int rc = sync_graph();
   if (rc) return rc;
@@ -444,15 +446,21 @@ int HNSWIndex::device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_
   rc = sl.buf.reserve(sl.ctx, bytes, true);
   if (rc) return rc;
   const WalkBlock d(sl.buf.dev, B, k);
-  rc = fvdb_graph_search_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, q_dev, B, k, ef, d.nodes, d.dist, d.counts,
-                                  d.status);
+  fvdb_ctx* on = slot == 0 ? nullptr : sl.ctx;
+  if (!view)
+    rc = fvdb_graph_search_dev_slot(graph_, on, slot, q_dev, B, k, ef, d.nodes, d.dist, d.counts, d.status);
+  else if (scans(*view, k))
+    rc = fvdb_graph_scan_allowed_dev_slot(graph_, on, slot, view->mask.get(), q_dev, B, k, d.nodes, d.dist, d.counts);
+  else
+    rc = fvdb_graph_search_dev_slot_masked(graph_, on, slot, view->mask.get(), q_dev, B, k, ef, d.nodes, d.dist, d.counts,
+                                           d.status);
   if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
   return rc;
 }
 
 // wait + translate; queries the kernel could not finish on chip are listed in `failed`
 int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts,
-                              std::vector<uint32_t>& failed, uint32_t slot) {
+                              std::vector<uint32_t>& failed, uint32_t slot, bool scanned) {
   DevSlot& sl = slots_[slot];
   int rc = fvdb_ctx_synchronize(sl.ctx);
   if (rc) return rc;
@@ -460,7 +468,7 @@ int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist
   std::memcpy(dist, h.dist, (size_t)B * k * 4);
   std::memcpy(counts, h.counts, (size_t)B * 4);
   for (uint32_t b = 0; b < B; ++b) {
-    if (h.status[b]) {
+    if (!scanned && h.status[b]) {
       failed.push_back(b);
       counts[b] = 0;
       continue;
@@ -475,7 +483,7 @@ int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist
 
 // rare: on-chip heap / visited log overflow -> host walk for those queries
 int HNSWIndex::finish_failed(const float* q, bool q_on_device, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                             float* dist, uint32_t* counts, const std::vector<uint32_t>& failed) {
+                             float* dist, uint32_t* counts, const std::vector<uint32_t>& failed, const AllowView* view) {
   if (failed.empty()) return FVDB_OK;
   n_fallback_ += failed.size();
   int rcg = ensure_host_graph();
@@ -493,7 +501,7 @@ int HNSWIndex::finish_failed(const float* q, bool q_on_device, uint32_t dim, uin
   std::vector<uint64_t> fi(failed.size() * (size_t)k);
   std::vector<float> fd(failed.size() * (size_t)k);
   std::vector<uint32_t> fc(failed.size());
-  int rc = search_host_walk(hq.data(), false, (uint32_t)failed.size(), k, ef, fi.data(), fd.data(), fc.data());
+  int rc = search_host_walk(hq.data(), false, (uint32_t)failed.size(), k, ef, fi.data(), fd.data(), fc.data(), view);
   if (rc) return rc;
   for (size_t i = 0; i < failed.size(); ++i) {
     std::memcpy(ids + (size_t)failed[i] * k, &fi[i * k], (size_t)k * 8);
@@ -504,20 +512,103 @@ int HNSWIndex::finish_failed(const float* q, bool q_on_device, uint32_t dim, uin
 }
 
 bool HNSWIndex::search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc,
-                                 uint32_t slot) {
+                                 uint32_t slot, const AllowView* view) {
   *rc = FVDB_OK;
   if (entry_lost_) return false;  // the caller's search_dev fallback reports the error
-  if (!has_entry_ || B == 0 || k == 0 || (has_dim_ && dim != dim_) || !device_path_ok(ef)) return false;
-  *rc = device_launch(q_dev, B, k, ef, slot);
+  const bool scan = view && scans(*view, k);  // the exact scan is a device kernel whatever the traversal setting
+  if (!has_entry_ || B == 0 || k == 0 || (has_dim_ && dim != dim_) || (!scan && !device_path_ok(ef))) return false;
+  *rc = device_launch(q_dev, B, k, ef, slot, view);
   return *rc == FVDB_OK;
 }
 
 int HNSWIndex::search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                              float* dist, uint32_t* counts, uint32_t slot) {
+                              float* dist, uint32_t* counts, uint32_t slot, const AllowView* view) {
   std::vector<uint32_t> failed;
-  int rc = device_collect(B, k, ids, dist, counts, failed, slot);
+  int rc = device_collect(B, k, ids, dist, counts, failed, slot, view && scans(*view, k));
   if (rc) return rc;
-  return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed);
+  return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed, view);
+}
+
+// ---- filtered search ----
+int HNSWIndex::allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out) {
+  if (n_allowed && !allowed) return FVDB_E_INVALID;
+  if (!has_entry_ || !store_) {
+    // a graph that has never held a row (a hybrid index fed only historical rows): every search of it answers "nothing"
+    // before it reaches the device, a filtered one too — there is no store to build a device graph over, and no need
+    *out = std::make_shared<AllowView>();
+    return FVDB_OK;
+  }
+  int rc = sync_graph();  // the mask is built against the device graph as the next search will see it
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(view_mu_);
+  const bool same = view_ && view_key_.size() == n_allowed &&
+                    (n_allowed == 0 || std::memcmp(view_key_.data(), allowed, n_allowed * 8) == 0);
+  if (!same || !mask_fresh(view_->mask)) {
+    view_.reset();
+    view_key_.clear();
+    auto v = std::make_shared<AllowView>();
+    const size_t n = ids_.size();
+    v->eff.assign(n, 1);
+    std::vector<uint32_t> nodes;
+    nodes.reserve(n_allowed);
+    for (uint64_t i = 0; i < n_allowed; ++i) {
+      auto it = index_of_.find(allowed[i]);
+      if (it == index_of_.end()) continue;  // an id this index does not hold
+      nodes.push_back(it->second);
+      v->eff[it->second] = deleted_[it->second];
+    }
+    fvdb_mask* m = nullptr;
+    rc = fvdb_mask_create_graph(graph_, nodes.data(), nodes.size(), &m);
+    if (rc) return rc;
+    v->mask = adopt_mask(m);
+    fvdb_mask_info_t info;
+    if ((rc = fvdb_mask_info(m, &info))) return rc;
+    v->allowed_live = info.allowed_live;
+    view_ = v;
+    view_key_.assign(allowed, allowed + n_allowed);
+    mask_builds_ += 1;
+  }
+  *out = view_;
+  return FVDB_OK;
+}
+
+int HNSWIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
+                              uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  fill_empty(ids, dist, counts, B, k);
+  if (!has_entry_ || B == 0 || k == 0) return FVDB_OK;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  ViewRef view;
+  int rc = allowed_view(allowed, n_allowed, &view);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> serial(search_mu_);  // slot 0 and one staging buffer, like search()
+  const uint64_t bytes = (uint64_t)B * dim * 4;
+  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
+  return search_view_locked((const float*)d_q_.dev, B, dim, k, ef, *view, ids, dist, counts);
+}
+
+int HNSWIndex::search_dev_view(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
+                               uint64_t* ids, float* dist, uint32_t* counts) {
+  std::lock_guard<std::mutex> serial(search_mu_);
+  return search_view_locked(q_dev, B, dim, k, ef, view, ids, dist, counts);
+}
+
+int HNSWIndex::search_view_locked(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
+                                  uint64_t* ids, float* dist, uint32_t* counts) {
+  fill_empty(ids, dist, counts, B, k);
+  if (!has_entry_ || B == 0 || k == 0) return FVDB_OK;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  if (entry_lost_) return FVDB_E_NOT_FOUND;
+  const bool scan = scans(view, k);
+  int rc;
+  if (!scan && !device_path_ok(ef)) {
+    if ((rc = ensure_host_graph())) return rc;
+    std::lock_guard<std::mutex> lk(walk_mu_);
+    return search_host_walk(q_dev, true, B, k, ef, ids, dist, counts, &view);
+  }
+  if ((rc = device_launch(q_dev, B, k, ef, 0, &view))) return rc;
+  std::vector<uint32_t> failed;
+  if ((rc = device_collect(B, k, ids, dist, counts, failed, 0, scan))) return rc;
+  return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed, &view);
 }
 
 int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef,
@@ -558,9 +649,11 @@ int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_
 // GPU while another's host phase runs, were measured slower: launch + stream sync cost more than the overlap wins,
 // profiles/r01_hnsw_lanes.log.)  The caller holds walk_mu_ and has pulled nbrs_.
 int HNSWIndex::search_host_walk(const float* q, bool q_on_device, uint32_t B, uint32_t k, uint32_t ef, uint64_t* ids,
-                                float* dist, uint32_t* counts) {
+                                float* dist, uint32_t* counts, const AllowView* view) {
   fill_empty(ids, dist, counts, B, k);
   Walk& w = search_walk_;
+  w.del = view ? view->eff.data() : nullptr;
+  const uint8_t* del = view ? view->eff.data() : deleted_.data();
   const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0) + 1;
   const uint32_t step = 16384;
   for (uint32_t lo = 0; lo < B; lo += step) {
@@ -586,7 +679,7 @@ int HNSWIndex::search_host_walk(const float* q, bool q_on_device, uint32_t B, ui
       uint32_t nw = 0;
       const size_t o = (size_t)(lo + b) * k;
       for (const Cand& c : w.qs[b].cur) {
-        if (!registered_[c.node] || deleted_[c.node]) continue;
+        if (!registered_[c.node] || del[c.node]) continue;
         if (nw >= k) break;
         ids[o + nw] = ids_[c.node];
         dist[o + nw] = c.distance;

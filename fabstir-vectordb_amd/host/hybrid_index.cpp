@@ -460,6 +460,8 @@ int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, u
   Lease lease(this, slot, Lease::kTake);
   if (!lease.sl) return FVDB_E_INVALID;
   lease.hand_over();  // whatever begin_impl returns, the slot stays the caller's until search_dev_end
+  slots_[slot].ivf_mask.reset();  // the explicit pair is an unfiltered search
+  slots_[slot].view.reset();
   return begin_impl(slot, q_dev, B, dim, cfg, shard_mode);
 }
 
@@ -540,7 +542,7 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
     // the graph walk is latency-bound (one wave per query): enqueue it FIRST so that the list scan launched
     // next fills the rest of every SIMD and the two run concurrently
     int rcb = 0;
-    sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot);
+    sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot, sl.view.get());
   }
   if (cfg.search_historical && ivf_trained_) {
     const uint64_t bytes = IvfBlock::bytes(ivf_rows, sl.hk);
@@ -560,6 +562,9 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
                                                     (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
       if (rcs) return rcs;
       sl.ivf_in_flight = true;
+    } else if (sl.ivf_mask) {
+      sl.ivf_in_flight = historical_->search_dev_masked(sl.ivf_mask, q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids,
+                                                        d.dist, d.counts, on, on ? slot : 0) == FVDB_OK;
     } else {
       sl.ivf_in_flight = historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids, d.dist, d.counts,
                                                  on, on ? slot : 0) == FVDB_OK;
@@ -579,6 +584,14 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   if (!lease.sl) return FVDB_E_INVALID;
   Slot& sl = *lease.sl;
   const uint32_t B = sl.B, k = sl.k;
+  // a filtered search's masks stay referenced until its results are in, whichever way this returns
+  struct DropMasks {
+    Slot& sl;
+    ~DropMasks() {
+      sl.ivf_mask.reset();
+      sl.view.reset();
+    }
+  } drop_masks{sl};
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   std::vector<uint64_t> rid;
@@ -588,9 +601,14 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   if (sl.recent) {
     rid.resize((size_t)B * sl.rk);
     rd.resize((size_t)B * sl.rk);
-    int rc2 = sl.hnsw_in_flight
-                  ? recent_->search_dev_end(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data(), slot)
-                  : recent_->search_dev(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data());
+    int rc2;
+    if (sl.hnsw_in_flight) {
+      rc2 = recent_->search_dev_end(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data(), slot, sl.view.get());
+    } else if (sl.view) {  // nothing was enqueued (host-walk setting): the standalone filtered search
+      rc2 = recent_->search_dev_view(sl.q, B, sl.dim, sl.rk, sl.ef, *sl.view, rid.data(), rd.data(), rc_.data());
+    } else {
+      rc2 = recent_->search_dev(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data());
+    }
     have_r = rc2 == FVDB_OK;
   }
   IvfBlock h;
@@ -612,15 +630,38 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
 // The blocking entry points: any number of host threads.  A call holds the read side of rw_ from after its migration
 // check to its merge and works in a slot leased for its duration.
 int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                             double now, uint64_t* ids, float* dist, uint32_t* counts) {
+                             double now, uint64_t* ids, float* dist, uint32_t* counts, const uint64_t* allowed,
+                             uint64_t n_allowed, bool masked) {
   const uint32_t k = (uint32_t)cfg.k;
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);
+  // filtered search: the masks are built here — after the migration, under the lock that keeps the rows where they
+  // are until this search has its results
+  MaskRef ivf_mask;
+  HNSWIndex::ViewRef view;
+  if (masked) {
+    if (cfg.search_recent)
+      if (int rc = recent_->allowed_view(allowed, n_allowed, &view)) return rc;
+    if (cfg.search_historical && ivf_trained_)
+      if (int rc = historical_->allowed_mask(allowed, n_allowed, &ivf_mask)) return rc;
+  }
   Lease lease(this, Lease::kAnyFree, Lease::kTake);  // given back at every return, until search_dev_end takes it over
   Slot& sl = *lease.sl;
   const uint32_t slot = lease.index();
+  sl.ivf_mask = ivf_mask;
+  sl.view = view;
+  // the slot keeps them only while this search runs: search_dev_end drops them when it collects the batch, and every
+  // return before the slot is handed to it drops them here — the next user of the slot must find none
+  struct DropMasks {
+    Slot* sl;
+    ~DropMasks() {
+      if (!sl) return;
+      sl->ivf_mask.reset();
+      sl->view.reset();
+    }
+  } drop_masks{&sl};
   const float* qd = q;
   if (!q_on_device) {  // stage the batch in HBM once; both parts read it from there
     const uint64_t bytes = (uint64_t)B * dim * 4;
@@ -635,6 +676,7 @@ int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint3
   const int rc0 = begin_impl(slot, qd, B, dim, cfg);
   if (rc0 && !sl.hnsw_in_flight && !sl.ivf_in_flight) return rc0;
   lease.hand_over();
+  drop_masks.sl = nullptr;  // search_dev_end's turn
   if (rc0) {  // drain what was enqueued before the failure
     std::vector<uint64_t> ti((size_t)B * k);
     std::vector<float> td((size_t)B * k);
@@ -643,6 +685,13 @@ int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint3
     return rc0;
   }
   return search_dev_end(slot, ids, dist, counts);
+}
+
+int HybridIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,
+                                uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* counts) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // the sharded IVF step takes no mask
+  if (n_allowed && !allowed) return FVDB_E_INVALID;
+  return search_impl(q, false, B, dim, cfg, now, ids, dist, counts, allowed, n_allowed, true);
 }
 
 // src/hybrid/core.rs:513-549

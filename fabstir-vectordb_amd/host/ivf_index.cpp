@@ -9,12 +9,16 @@ namespace fvdbh {
 IVFIndex::IVFIndex(fvdb_ctx* ctx, const IVFConfig& cfg) : ctx_(ctx), cfg_(cfg) {}
 
 IVFIndex::~IVFIndex() {
+  drop_mask();  // before the device index it points into
+  allowed_q_.release();
+  allowed_out_.release();
   if (dev_) fvdb_ivf_destroy(dev_);
 }
 
 int IVFIndex::ensure_device(uint32_t dim) {
   if (dev_ && dim_ == dim && dev_clusters_ == cfg_.n_clusters) return FVDB_OK;
   if (dev_) {
+    drop_mask();
     fvdb_ivf_destroy(dev_);
     dev_ = nullptr;
   }
@@ -158,6 +162,7 @@ int IVFIndex::rebuild(uint32_t n_clusters, uint32_t max_iterations, uint64_t see
     fvdb_ivf_destroy(nd);
     return rc;
   }
+  drop_mask();
   fvdb_ivf_destroy(dev_);
   dev_ = nd;
   dev_clusters_ = n_clusters;
@@ -347,6 +352,61 @@ int IVFIndex::search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t 
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
   return fvdb_ivf_search_dev_slot(dev_, on, slot, q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
+}
+
+// ---- filtered search ----
+int IVFIndex::allowed_mask(const uint64_t* allowed, uint64_t n_allowed, MaskRef* out) {
+  if (!trained_ || !dev_) return FVDB_E_NOT_TRAINED;
+  if (n_allowed && !allowed) return FVDB_E_INVALID;
+  std::lock_guard<std::mutex> lk(mask_mu_);
+  const bool same = mask_ && mask_key_.size() == n_allowed &&
+                    (n_allowed == 0 || std::memcmp(mask_key_.data(), allowed, n_allowed * 8) == 0);
+  if (!same || !mask_fresh(mask_)) {
+    drop_mask();
+    fvdb_mask* m = nullptr;
+    const int rc = fvdb_mask_create_ivf(dev_, allowed, n_allowed, &m);
+    if (rc) return rc;
+    mask_ = adopt_mask(m);
+    mask_key_.assign(allowed, allowed + n_allowed);
+    mask_builds_ += 1;
+  }
+  *out = mask_;
+  return FVDB_OK;
+}
+
+int IVFIndex::search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe,
+                                uint64_t* ids_dev, float* dist_dev, uint32_t* counts_dev, fvdb_ctx* on, uint32_t slot) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  return fvdb_ivf_search_dev_slot_masked(dev_, on, slot, mask.get(), q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
+}
+
+int IVFIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const uint64_t* allowed,
+                             uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  if (B == 0) return FVDB_OK;
+  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  MaskRef mask;
+  int rc = allowed_mask(allowed, n_allowed, &mask);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(allowed_mu_);  // one staging block: calls take turns
+  const uint64_t need = (uint64_t)B * k, bytes = need * 12 + (uint64_t)B * 4;
+  if ((rc = allowed_q_.reserve(ctx_, (uint64_t)B * dim * 4, false)) || (rc = allowed_out_.reserve(ctx_, bytes, true))) return rc;
+  if ((rc = fvdb_dev_upload(ctx_, allowed_q_.dev, q, (size_t)B * dim * 4))) return rc;
+  char* d = (char*)allowed_out_.dev;
+  rc = search_dev_masked(mask, (const float*)allowed_q_.dev, B, dim, k, n_probe, (uint64_t*)d, (float*)(d + need * 8),
+                         (uint32_t*)(d + need * 12));
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx_, allowed_out_.host, allowed_out_.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(ctx_)))
+    return rc;
+  const char* h = (const char*)allowed_out_.host;
+  std::memcpy(ids, h, need * 8);
+  std::memcpy(dist, h + need * 8, need * 4);
+  std::memcpy(counts, h + need * 12, (size_t)B * 4);
+  return FVDB_OK;
 }
 
 // src/ivf/operations.rs:569-591

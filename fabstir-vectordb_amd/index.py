@@ -90,6 +90,16 @@ HOST_SIGNATURES = {
     "fvh_hybrid_bulk_insert_sharded": (i32, [vp, u64p, f32p, u64, u32, f64p, dbl, u32, u32, u32p]),
     "fvh_hybrid_search": (i32, [vp, f32p, u32, u32, u64, u64, u64, i32, i32, u64, u64, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_search_with_filter": (i32, [vp, f32p, u32, u32, u64, vp, vp, dbl, u64p, f32p, u32p]),
+    # filtered search with the allow-set applied on the device
+    "fvh_ivf_search_allowed": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvh_ivf_mask_builds": (u64, [vp]),
+    "fvh_hnsw_search_allowed": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvh_hnsw_set_scan_cutoff": (None, [vp, u64]),
+    "fvh_hnsw_scan_cutoff": (u64, [vp]),
+    "fvh_hnsw_mask_builds": (u64, [vp]),
+    "fvh_hnsw_device_graph": (vp, [vp]),
+    "fvh_hybrid_search_allowed": (i32, [vp, f32p, u32, u32, u64, u64, u64, i32, i32, u64, u64, u64p, u64, dbl, u64p, f32p,
+                                        u32p]),
     "fvh_hybrid_search_dev": (i32, [vp, vp, u32, u32, u64, u64, u64, i32, i32, u64, u64, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_search_dev_begin": (i32, [vp, u32, vp, u32, u32, u64, u64, u64, i32, i32, u64, u64, dbl]),
     "fvh_hybrid_search_dev_end": (i32, [vp, u32, u64p, f32p, u32p]),
@@ -165,6 +175,13 @@ def _rows(x, dim=None):
     if dim is not None and x.shape[1] != dim:
         raise DimensionMismatch(f"Dimension mismatch: expected {dim}, got {x.shape[1]}")
     return x
+
+
+def _allowed_ids(allowed):
+    """An allow-set as a contiguous 1-d u64 array; an empty one is a zero-length view of a real buffer, so that
+    ctypes has an address to pass."""
+    a = np.ascontiguousarray(np.fromiter(allowed, np.uint64) if not isinstance(allowed, np.ndarray) else allowed, np.uint64)
+    return a.reshape(-1) if a.size else np.zeros(1, np.uint64)[:0]
 
 
 class _Base:
@@ -322,6 +339,17 @@ class IVFIndex(_Base):
     def search(self, queries, k, n_probe=None):
         return self._search(self.lib.fvh_ivf_search, queries, k, self.n_probe if n_probe is None else n_probe)
 
+    def search_allowed(self, queries, k, allowed, n_probe=None):
+        """search() among the rows whose id is in `allowed`: exactly what search() returns once every other row has been
+        mark_deleted.  The allow-set is applied inside the list scan on the device; the last mask is kept for a caller
+        that repeats one filter."""
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_ivf_search_allowed, queries, k, self.n_probe if n_probe is None else n_probe,
+                            _ptr(a, u64p), a.size)
+
+    def mask_builds(self):
+        return int(self.lib.fvh_ivf_mask_builds(self.h))
+
     search_with_config = search
 
     batch_search = search
@@ -410,6 +438,31 @@ class HNSWIndex(_Base):
 
     def search(self, queries, k, ef):
         return self._search(self.lib.fvh_hnsw_search, queries, k, ef)
+
+    def search_allowed(self, queries, k, ef, allowed):
+        """search() among the nodes whose id is in `allowed`: what search() returns once every other node has been
+        mark_deleted — unless at most scan_cutoff allowed live nodes remain: those are scanned exactly (the k best by
+        distance bits, then node index)."""
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_hnsw_search_allowed, queries, k, ef, _ptr(a, u64p), a.size)
+
+    @property
+    def scan_cutoff(self):
+        return int(self.lib.fvh_hnsw_scan_cutoff(self.h))
+
+    @scan_cutoff.setter
+    def scan_cutoff(self, nodes):
+        """0 = never scan, SCAN_ALWAYS = always.  The default (8192) is a guess nobody has measured."""
+        self.lib.fvh_hnsw_set_scan_cutoff(self.h, int(nodes))
+
+    SCAN_ALWAYS = 2 ** 64 - 1
+
+    def mask_builds(self):
+        return int(self.lib.fvh_hnsw_mask_builds(self.h))
+
+    def _graph(self):
+        """fvdb_graph* of the device graph, up to date (raw C-ABI calls in tests and tools)."""
+        return C.c_void_p(self.lib.fvh_hnsw_device_graph(self.h))
 
     def search_dev(self, q_dev, B, dim, k, ef):
         ids = np.empty((B, max(k, 1)), np.uint64)
@@ -676,6 +729,15 @@ class HybridIndex(_Base):
                             int(search_historical), recent_k, historical_k, float(now))
 
     search_with_config = search
+
+    def search_allowed(self, queries, k, allowed, now=0.0, hnsw_ef=50, ivf_n_probe=10, search_recent=True,
+                       search_historical=True, recent_k=0, historical_k=0):
+        """search() with the allow-set applied inside both parts on the device: what search() returns once every id
+        outside `allowed` has been deleted (the recent part scanned exactly below recent().scan_cutoff).  Unlike
+        search_with_filter it returns k matches whenever the searched rows hold k."""
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_hybrid_search_allowed, queries, k, hnsw_ef, ivf_n_probe, int(search_recent),
+                            int(search_historical), recent_k, historical_k, _ptr(a, u64p), a.size, float(now))
 
     _FILTER_FN = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_void_p)
 

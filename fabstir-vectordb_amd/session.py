@@ -200,6 +200,12 @@ class VectorDbSession:
                 flt = MetadataFilter.from_json(options["filter"])
             except FilterError as e:
                 raise SessionError(f"Invalid filter: {e}") from e
+        # "filterMode" (not in the reference): absent or "oversample" = the reference's filter path below; "pushdown" = the
+        # filter is evaluated over the metadata map once and the matching ids go down as an allow-set that the device
+        # applies inside the search (HybridIndex::search_allowed), so up to k matches come back however selective it is
+        mode = options.get("filterMode", "oversample")
+        if mode not in ("oversample", "pushdown"):
+            raise SessionError(f'Invalid filterMode: {mode!r} (expected "oversample" or "pushdown")')
         # with a filter: 3 k candidates, keep those whose metadata match, truncate — HybridIndex::search_with_filter of
         # the host mirror (src/hybrid/core.rs:513-549); this side only answers "does this id's metadata match"
         matches = None
@@ -208,7 +214,11 @@ class VectorDbSession:
                 key = self._rows.get(rid)
                 return key in self.metadata and flt.matches(self.metadata[key])
         try:
-            res = self.index.search_with_filter(q.reshape(1, -1), int(k), matches, now=self.now)  # defaults: ef 50, nprobe 10
+            if flt is not None and mode == "pushdown":
+                allowed = np.fromiter((rid for rid in self._rows if matches(rid)), np.uint64)
+                res = self.index.search_allowed(q.reshape(1, -1), int(k), allowed, now=self.now)  # defaults: ef 50, nprobe 10
+            else:
+                res = self.index.search_with_filter(q.reshape(1, -1), int(k), matches, now=self.now)  # defaults: ef 50, nprobe 10
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
         out = []

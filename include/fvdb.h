@@ -462,6 +462,61 @@ int fvdb_graph_kernel_times(fvdb_graph* g, float* ms_sum, uint32_t* launches, ui
  * such a query is the slowest of its launch).  Synchronises. */
 int fvdb_graph_tie_restarts(fvdb_graph* g, uint64_t* queries, uint64_t* searched_again);
 
+/* ---- filtered search: allow-set masks on the device -------------------------------------------------------
+ *   The reference filters after the search: search_with_filter asks for
+ * 3 k neighbours and keeps those the metadata filter accepts (src/hybrid/core.rs:513-549), so a selective filter
+ * returns few results or none.  A masked search applies the allow-set INSIDE the search: it returns exactly what the
+ * same search returns on an index in which every row outside the allow-set has been soft-deleted (mark_deleted,
+ * src/ivf/operations.rs:569-591, src/hnsw/operations.rs:127-137) — ids and distance bits, in the same order.  Rows
+ * already deleted stay excluded; entries of the allow-set the index does not hold are ignored.
+ *
+ * A mask is immutable and owns its device buffers: any number of searches in different slots may share one.  It is
+ * built against the index as it stands; every mutation of the index (add*, set_deleted, clear, reserve, set_centroids,
+ * train*, compact, refill_from; graph: upload, append_nodes, insert_linked, set_lists, set_entry, set_deleted) makes it
+ * stale, and a masked search with a stale mask returns FVDB_E_INVALID (fvdb_last_error says so), never wrong rows.
+ * Creating a mask needs the same exclusion against mutations as a search.  One mask serves a whole batch call.  The
+ * sharded search (fvdb_ivf_search_sharded_begin) takes no mask.
+ *  - fvdb_mask_create_ivf: ids[n] = the allowed row ids (host; duplicates and unknown ids are harmless).
+ *  - fvdb_mask_create_graph: nodes[n] = the allowed NODE indices (host; the graph holds no ids: node index = store row).
+ *  - fvdb_mask_info: allowed_live = rows (nodes) that are live in the index and allowed; stale = 1 once the index changed.
+ *  - fvdb_mask_destroy waits for the device before it frees the buffers. */
+typedef struct fvdb_mask fvdb_mask;
+typedef struct fvdb_mask_info_t {
+  uint32_t kind;   /* 1 = IVF index, 2 = graph */
+  uint32_t stale;
+  uint32_t units;  /* pool blocks (IVF) / nodes (graph) covered */
+  uint32_t reserved;
+  uint64_t allowed_live;
+} fvdb_mask_info_t;
+int fvdb_mask_create_ivf(fvdb_ivf* ivf, const uint64_t* ids, uint64_t n, fvdb_mask** out);
+int fvdb_mask_create_graph(fvdb_graph* g, const uint32_t* nodes, uint64_t n, fvdb_mask** out);
+int fvdb_mask_info(fvdb_mask* mask, fvdb_mask_info_t* out);
+void fvdb_mask_destroy(fvdb_mask* mask);
+/* fvdb_ivf_search_dev_slot / fvdb_ivf_search_probes_dev_slot under a mask: the skip of deleted rows
+ * (src/ivf/core.rs:666-669) also skips the rows the mask does not allow, in every stage of the list scan (exact scan,
+ * matrix-core threshold / filter / select / refine, exact rescan).  Under a mask FVDB_SCAN_AUTO always scans exactly
+ * (the filter samples its threshold from lists the mask has thinned); FVDB_SCAN_FILTER still forces the filter.  Masked
+ * searches are kept out of AUTO's hit-rate watch; fvdb_ivf_scan_fallbacks and _reasons count their rescans too. */
+int fvdb_ivf_search_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                    uint32_t* out_counts_dev, uint64_t* out_keys_dev);
+int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                           const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                           uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                                           uint64_t* out_keys_dev);
+/* fvdb_graph_search_dev_slot under a mask: a node the mask does not allow is treated as deleted — never expanded into
+ * `candidates`, never returned (src/hnsw/core.rs:511-513, :451-466).  status 1 queries go to the host walk as before;
+ * the host must apply the same view there. */
+int fvdb_graph_search_dev_slot_masked(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                      uint32_t k, uint32_t ef, uint32_t* out_nodes_dev, float* out_dist_dev,
+                                      uint32_t* out_counts_dev, uint32_t* out_status_dev);
+/* Exact k-NN over the allowed live nodes of a graph mask (no counterpart in the reference: "as if deleted" thins the
+ * graph the traversal walks, so a small allow-set is scanned instead).  Every allowed node is scored with the
+ * reference's f32 fold (src/core/vector_ops.rs:51-57); the k best by (distance bits ascending, node index ascending).
+ * out_nodes/out_dist: B x k (unused tail = FVDB_NO_ROW / +inf), out_counts[B].  k <= FVDB_MAX_K. */
+int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                     uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
+
 /* ---- multi-GPU: inverted lists sharded across the GPUs of a node, RCCL over xGMI -------------------------
  * (BASELINE config C4; SURVEY §8e.  The reference has no distributed execution: what is preserved is the result —
  * the merged answer equals the single-index answer bit for bit, because the selection keys are global.)
