@@ -36,6 +36,15 @@ class MaintenanceInfo(C.Structure):
                 ("ms_train", f32), ("ms_assign", f32), ("ms_ranks", f32), ("ms_move", f32), ("ms_total", f32)]
 
 
+class GraphMaintenanceInfo(C.Structure):
+    """fvdb_graph_maintenance_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u64) for n in ("nodes_in", "nodes_out", "edges_in", "edges_out", "rows_reclaimed", "bytes_reclaimed",
+                                   "host_bytes", "move_bytes")] + \
+               [(n, f32) for n in ("ms_scan", "ms_prune", "ms_move", "ms_total")]
+
+
+VACUUM_KEEP_ROWS = 1  # FVDB_VACUUM_KEEP_ROWS
+
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
 # tests/test_cabi_symbols.py checks the built library exports each of them.
 SIGNATURES = {
@@ -120,6 +129,8 @@ SIGNATURES = {
     "fvdb_graph_upload_bytes": (u64, [vp]),
     "fvdb_graph_set_insert_visited": (i32, [vp, i32, u32]),
     "fvdb_graph_insert_info": (i32, [vp, u32, vp]),
+    "fvdb_graph_vacuum": (i32, [vp, u32, u64p]),
+    "fvdb_graph_maintenance_info": (i32, [vp, C.POINTER(GraphMaintenanceInfo)]),
     "fvdb_graph_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_graph_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ctx_device": (i32, [vp]),

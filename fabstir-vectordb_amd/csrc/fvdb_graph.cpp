@@ -5,6 +5,7 @@
 // the rows it touches: the device-side insert (kernels_graph_build.h) edits them in place, a host-side insert patches
 // them through fvdb_graph_set_lists.  Nothing re-flattens or re-uploads the whole graph after a mutation.
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include "kernels_graph.h"
 #include "kernels_graph_fast.h"
 #include "kernels_graph_build.h"
+#include "kernels_graph_maint.h"
 
 using namespace fvdb;
 
@@ -37,6 +39,7 @@ struct fvdb_graph {
   std::vector<uint32_t> h_level, h_ubase;
   uint64_t upload_bytes = 0;        // host -> device bytes of graph STRUCTURE (not vectors) since creation
   fvdb_graph_insert_stats last{};
+  fvdb_graph_maintenance_info_t m_info{};  // the last fvdb_graph_vacuum
   // form of the device insert's `visited` (fvdb_graph_set_insert_visited) and what the hashed form has seen since creation
   int ins_vis_mode = 0;
   uint32_t ins_vis_slots = 0;
@@ -735,7 +738,7 @@ int fvdb_graph_append_nodes(fvdb_graph* g, uint32_t first, uint32_t n_new, const
   std::memcpy(hp + n_new, ub.data(), (size_t)n_new * 4);
   HIPCHK(ctx, hipMemcpyAsync(g->d_level.as<uint32_t>() + first, hp, (size_t)n_new * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(g->d_ubase.as<uint32_t>() + first, hp + n_new, (size_t)n_new * 4, hipMemcpyHostToDevice, ctx->stream));
-  // empty lists, clean flags and stamps for the new rows (a vacuumed-and-reused range never occurs: rows only grow)
+  // empty lists, clean flags and stamps for the new rows (rows only grow; a reclaiming vacuum writes fresh arrays)
   HIPCHK(ctx, hipMemsetAsync(g->d_adj0.as<uint32_t>() + (size_t)first * g->stride0, 0, (size_t)n_new * g->stride0 * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(g->d_deleted.as<uint32_t>() + first, 0, (size_t)n_new * 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(g->d_stamp0.as<uint32_t>() + first, 0, (size_t)n_new * 4, ctx->stream));
@@ -1083,6 +1086,265 @@ int fvdb_graph_kernel_times(fvdb_graph* g, float* ms_sum, uint32_t* launches, ui
 }
 
 }  // extern "C"
+
+// =============================================================================================
+// device-resident graph: maintenance (HNSWIndex::vacuum, src/hnsw/operations.rs:176-200; kernels_graph_maint.h)
+// =============================================================================================
+namespace {
+
+// the fresh arrays of a reclaiming vacuum: all allocated before the first change, freed again if one cannot be had
+struct FreshGraph {
+  DBuf level, deleted, ubase, adj0, adjU, dist0, distU, stamp0, stampU, rows;
+  DBuf* all[10] = {&level, &deleted, &ubase, &adj0, &adjU, &dist0, &distU, &stamp0, &stampU, &rows};
+  void release() {
+    for (DBuf* b : all) b->release();
+  }
+  // exactly `bytes` (DBuf::ensure adds slack of its own; the capacities here already carry the growth slack)
+  static hipError_t exact(DBuf& b, size_t bytes) {
+    const hipError_t e = hipMalloc(&b.p, std::max<size_t>(bytes, 256));
+    if (e == hipSuccess) b.cap = std::max<size_t>(bytes, 256);
+    return e;
+  }
+};
+
+struct StageEvents {
+  hipEvent_t ev[6] = {};
+  bool make() {
+    for (auto& e : ev)
+      if (hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+  }
+  ~StageEvents() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  static float ms(hipEvent_t a, hipEvent_t b) {
+    float v = 0.0f;
+    return hipEventElapsedTime(&v, a, b) == hipSuccess ? v : 0.0f;
+  }
+};
+
+uint32_t prune_grid(const fvdb_ctx* ctx, uint32_t rows) { return std::max(1u, std::min<uint32_t>(cdiv(rows, 4), (uint32_t)ctx->num_cus * 8u)); }
+
+}  // namespace
+
+extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* removed) {
+  if (!g) return FVDB_E_INVALID;
+  fvdb_store* s = g->store;
+  fvdb_ctx* ctx = s->ctx;
+  if (removed) *removed = 0;
+  if (flags & ~FVDB_VACUUM_KEEP_ROWS) FAIL(ctx, FVDB_E_INVALID, "graph vacuum: unknown flag");
+  if (!g->uploaded || g->n == 0) FAIL(ctx, FVDB_E_INVALID, "graph vacuum: no device graph");
+  const bool keep_rows = (flags & FVDB_VACUUM_KEEP_ROWS) != 0;
+  if (!keep_rows && s->rows != g->n) FAIL(ctx, FVDB_E_INVALID, "graph vacuum: the graph does not cover the store");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipDeviceSynchronize());  // searches of other slots run on streams of their own
+  const auto t0 = std::chrono::steady_clock::now();
+  fvdb_graph_maintenance_info_t info{};
+  const uint32_t n = g->n, u_rows = g->u_rows;
+  info.nodes_in = info.nodes_out = n;
+  // the survivors by the host's copy of the flags: new index = undeleted nodes before it
+  uint32_t n_out = 0, u_out = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!g->h_deleted[i]) {
+      n_out += 1;
+      u_out += g->h_level[i];
+    }
+  if (n_out == n) {  // nothing is deleted: nothing to prune, nothing to move
+    g->m_info = info;
+    return FVDB_OK;
+  }
+  StageEvents ev;
+  if (!ev.make()) FAIL(ctx, FVDB_E_HIP, "graph vacuum: no events");
+  hipStream_t st = ctx->stream;
+  const uint32_t n_wg = cdiv(n, 256);
+  const uint32_t* d_deleted = g->d_deleted.as<uint32_t>();
+  // scratch: [new_index n | src_node n | u_src or owner u_rows | wg_nodes n_wg | wg_urows n_wg | totals 2] words, counters
+  DBuf scratch, counters;
+  HIPCHK(ctx, scratch.ensure(((size_t)2 * n + u_rows + 2 * (size_t)n_wg + 2) * 4));
+  hipError_t ce = counters.ensure(32);
+  if (ce != hipSuccess) {
+    scratch.release();
+    HIPCHK(ctx, ce);
+  }
+  uint32_t* new_index = scratch.as<uint32_t>();
+  uint32_t* src_node = new_index + n;
+  uint32_t* u_aux = src_node + n;
+  uint32_t* wg_nodes = u_aux + u_rows;
+  uint32_t* wg_urows = wg_nodes + n_wg;
+  uint32_t* totals = wg_urows + n_wg;
+  FreshGraph f;
+  auto fail = [&](int code, const char* msg) {
+    f.release();
+    scratch.release();
+    counters.release();
+    ctx->set_err(msg);
+    return code;
+  };
+#define GM_TRY(call)                                                                                             \
+  do {                                                                                                           \
+    const hipError_t e_ = (call);                                                                                \
+    if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, hipGetErrorString(e_)); \
+  } while (0)
+  GM_TRY(hipMemsetAsync(counters.p, 0, 32, st));
+  GmPrune p0{}, pU{};
+  uint32_t n_cap = g->n_cap, u_cap = g->u_cap;
+  uint64_t host_bytes = 0;
+  if (keep_rows) {
+    n_out = n;
+    u_out = u_rows;
+    GM_TRY(hipEventRecord(ev.ev[0], st));
+    if (u_rows)
+      hipLaunchKernelGGL(gm_owner_kernel, dim3(n_wg), dim3(256), 0, st, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, u_rows, u_aux);
+    GM_TRY(hipEventRecord(ev.ev[1], st));
+    GM_TRY(hipEventRecord(ev.ev[2], st));
+    p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->stride0, n, n,
+                 nullptr, nullptr, 1u, d_deleted, n, nullptr, nullptr, nullptr, (unsigned long long*)counters.p};
+    pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->strideU, u_rows, u_rows,
+                 nullptr, u_aux, 1u, d_deleted, n, nullptr, nullptr, nullptr, (unsigned long long*)counters.p};
+  } else {
+    // stage 1a: survivors and their upper rows, counted on the device and checked against the host's copy of the flags
+    GM_TRY(hipEventRecord(ev.ev[0], st));
+    hipLaunchKernelGGL(gm_count_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), n, wg_nodes, wg_urows);
+    hipLaunchKernelGGL(gm_scan_kernel, dim3(1), dim3(1024), 0, st, wg_nodes, n_wg, totals);
+    hipLaunchKernelGGL(gm_scan_kernel, dim3(1), dim3(1024), 0, st, wg_urows, n_wg, totals + 1);
+    GM_TRY(hipGetLastError());
+    GM_TRY(hipEventRecord(ev.ev[1], st));
+    uint32_t h_tot[2] = {0, 0};
+    GM_TRY(hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, st));
+    GM_TRY(hipStreamSynchronize(st));
+    host_bytes += 8;
+    if (h_tot[0] != n_out || h_tot[1] != u_out) return fail(FVDB_E_HIP, "graph vacuum: the device's deleted flags differ from the host's copy");
+    // every allocation precedes the first change
+    n_cap = n_out + n_out / 8 + 1024;
+    u_cap = u_out + u_out / 8 + 1024;
+    const size_t row_bytes = (size_t)s->dpad * 4;
+    const size_t sizes[10] = {(size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4,
+                              (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4, (size_t)n_cap * 4, (size_t)u_cap * 4,
+                              (size_t)n_cap * row_bytes};
+    for (int b = 0; b < 10; ++b) {
+      const hipError_t e = FreshGraph::exact(*f.all[b], sizes[b]);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, "graph vacuum: no memory for the compacted copy (graph unchanged)");
+      }
+    }
+    for (int b = 0; b < 9; ++b) GM_TRY(hipMemsetAsync(f.all[b]->p, 0, f.all[b]->cap, st));  // (the store's rows are written whole)
+    // stage 1b: the maps, and level / upper-row base of every survivor at its new index
+    GM_TRY(hipEventRecord(ev.ev[2], st));
+    hipLaunchKernelGGL(gm_map_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, wg_nodes,
+                       wg_urows, n_out, u_out, new_index, src_node, u_aux, f.level.as<uint32_t>(), f.ubase.as<uint32_t>());
+    GM_TRY(hipGetLastError());
+    p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), f.adj0.as<uint32_t>(), f.dist0.as<float>(), g->stride0, n_out, n,
+                 src_node, nullptr, 0u, d_deleted, n, new_index, g->d_stamp0.as<uint32_t>(), f.stamp0.as<uint32_t>(), (unsigned long long*)counters.p};
+    pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), f.adjU.as<uint32_t>(), f.distU.as<float>(), g->strideU, u_out, u_rows,
+                 u_aux, nullptr, 0u, d_deleted, n, new_index, g->d_stampU.as<uint32_t>(), f.stampU.as<uint32_t>(), (unsigned long long*)counters.p};
+  }
+  // stage 2: prune + remap, one wave per destination row
+  GM_TRY(hipEventRecord(ev.ev[3], st));
+  hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, g->d_adj0.as<uint32_t>(), g->stride0, n, (unsigned long long*)counters.p);
+  if (u_rows)
+    hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, u_rows)), dim3(256), 0, st, g->d_adjU.as<uint32_t>(), g->strideU, u_rows,
+                       (unsigned long long*)counters.p);
+  if (p0.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, p0.rows)), dim3(256), 0, st, p0);
+  if (pU.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, pU.rows)), dim3(256), 0, st, pU);
+  GM_TRY(hipGetLastError());
+  GM_TRY(hipEventRecord(ev.ev[4], st));
+  // stage 3: store rows, one wave per destination row
+  if (!keep_rows && n_out) {
+    hipLaunchKernelGGL(gm_move_kernel, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float4*)s->data, n, s->dpad / 4, n_out, (float4*)f.rows.p);
+    GM_TRY(hipGetLastError());
+  }
+  GM_TRY(hipEventRecord(ev.ev[5], st));
+  unsigned long long h_cnt[4] = {0, 0, 0, 0};
+  GM_TRY(hipMemcpyAsync(h_cnt, counters.p, 32, hipMemcpyDeviceToHost, st));
+  GM_TRY(hipStreamSynchronize(st));
+  host_bytes += 32;
+#undef GM_TRY
+  // stage 4: bookkeeping
+  g->mutations += 1;
+  info.edges_in = h_cnt[0];
+  info.edges_out = h_cnt[1];
+  if (keep_rows) {
+    if (removed) *removed = h_cnt[2];
+  } else {
+    info.nodes_out = n_out;
+    info.rows_reclaimed = n - n_out;
+    info.bytes_reclaimed = (uint64_t)(n - n_out) * ((uint64_t)s->dpad * 4 + (uint64_t)g->stride0 * 8 + 16) +
+                           (uint64_t)(u_rows - u_out) * ((uint64_t)g->strideU * 8 + 4);
+    info.move_bytes = 2ull * n_out * s->dpad * 4;
+    std::swap(g->d_level, f.level);
+    std::swap(g->d_deleted, f.deleted);
+    std::swap(g->d_ubase, f.ubase);
+    std::swap(g->d_adj0, f.adj0);
+    std::swap(g->d_adjU, f.adjU);
+    std::swap(g->d_dist0, f.dist0);
+    std::swap(g->d_distU, f.distU);
+    std::swap(g->d_stamp0, f.stamp0);
+    std::swap(g->d_stampU, f.stampU);
+    // the store adopts the compacted rows: scorers read store->data at every launch
+    float* old_rows = s->data;
+    s->data = (float*)f.rows.p;
+    s->cap = n_cap;
+    s->rows = n_out;
+    f.rows.p = old_rows;
+    f.release();  // the old arrays
+    std::vector<uint32_t> lv(n_out), ub(n_out);
+    uint32_t w = 0, u = 0, entry = 0;
+    bool entry_alive = false;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (g->h_deleted[i]) continue;
+      if (g->has_entry && i == g->entry) {
+        entry = w;
+        entry_alive = true;
+      }
+      lv[w] = g->h_level[i];
+      ub[w] = u;
+      u += lv[w];
+      w += 1;
+    }
+    g->h_level.swap(lv);
+    g->h_ubase.swap(ub);
+    g->h_deleted.assign(n_out, 0);
+    g->n_deleted = 0;
+    g->n = n_out;
+    g->n_cap = n_cap;
+    g->u_rows = u_out;
+    g->u_cap = u_cap;
+    g->has_entry = entry_alive;
+    g->entry = entry_alive ? entry : 0;
+    g->top_level = entry_alive ? g->h_level[entry] : 0;
+    for (auto& v : g->vis_B) v = 0;  // visited maps are sized by the node count
+    if (removed) *removed = n - n_out;
+    BuildState bs{};
+    bs.has_entry = entry_alive ? 1u : 0u;
+    bs.entry = g->entry;
+    bs.entry_level = g->top_level;
+    bs.n_linked = n_out;
+    int rc = push_state(g, bs);
+    host_bytes += sizeof(BuildState);
+    if (rc) {
+      scratch.release();
+      counters.release();
+      return rc;
+    }
+  }
+  scratch.release();
+  counters.release();
+  info.host_bytes = host_bytes;
+  info.ms_scan = StageEvents::ms(ev.ev[0], ev.ev[1]) + (keep_rows ? 0.0f : StageEvents::ms(ev.ev[2], ev.ev[3]));
+  info.ms_prune = StageEvents::ms(ev.ev[3], ev.ev[4]);
+  info.ms_move = StageEvents::ms(ev.ev[4], ev.ev[5]);
+  info.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g->m_info = info;
+  return FVDB_OK;
+}
+
+extern "C" int fvdb_graph_maintenance_info(fvdb_graph* g, fvdb_graph_maintenance_info_t* out) {
+  if (!g || !out) return FVDB_E_INVALID;
+  *out = g->m_info;
+  return FVDB_OK;
+}
 
 // what allow_masks.h builds a graph mask from, and the inputs of its exact scan
 int graph_mask_source(fvdb_graph* g, GraphMaskSource* out) {

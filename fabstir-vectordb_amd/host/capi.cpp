@@ -337,6 +337,13 @@ int fvh_hybrid_retrain_historical(void* p, uint32_t n_clusters, uint32_t n_probe
 }
 int fvh_ivf_vacuum(void* p, uint64_t* removed) { return ((IVFIndex*)p)->vacuum(removed); }
 uint64_t fvh_hnsw_vacuum(void* p) { return ((HNSWIndex*)p)->vacuum(); }
+int fvh_hnsw_vacuum_ex(void* p, uint64_t* removed) { return ((HNSWIndex*)p)->vacuum(removed); }
+void fvh_hnsw_set_resident_vacuum(void* p, int on) { ((HNSWIndex*)p)->set_resident_vacuum(on != 0); }
+int fvh_hnsw_resident_vacuum(void* p) { return ((HNSWIndex*)p)->resident_vacuum(); }
+void fvh_hnsw_set_vacuum_keep_rows(void* p, int on) { ((HNSWIndex*)p)->set_vacuum_keep_rows(on != 0); }
+// returns HNSWIndex::VacuumPath of the last vacuum that removed something
+int fvh_hnsw_vacuum_info(void* p, fvdb_graph_maintenance_info_t* out) { return ((HNSWIndex*)p)->vacuum_info(out); }
+uint64_t fvh_hnsw_store_rows(void* p) { return ((HNSWIndex*)p)->store_rows(); }
 uint64_t fvh_hybrid_timestamp_count(void* p) { return ((HybridIndex*)p)->timestamp_count(); }
 void fvh_hybrid_export_timestamps(void* p, uint64_t* ids, double* ts) { ((HybridIndex*)p)->export_timestamps(ids, ts); }
 uint64_t fvh_hybrid_recent_count(void* p) { return ((HybridIndex*)p)->recent_count(); }

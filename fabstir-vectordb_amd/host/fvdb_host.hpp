@@ -293,7 +293,29 @@ class HNSWIndex {
   int mark_deleted(uint64_t id);                                                   // operations.rs:127
   bool is_deleted(uint64_t id) const;
   uint64_t active_count() const;
-  uint64_t vacuum();                                                               // operations.rs:176
+  // vacuum (operations.rs:176): deleted nodes leave every neighbour list and the node map.  With a device graph the
+  // whole operation is one device job (fvdb_graph_vacuum) that also renumbers the survivors densely, in their old
+  // order, and gives the dropped nodes' store rows and adjacency back; this mirror compacts its own arrays by the same
+  // rule.  The host algorithm (pull the lists, filter, install the whole graph at the next device use; rows kept)
+  // serves an index that has no device graph yet, set_resident_vacuum(false), and a graph the device cannot hold
+  // (a list longer than 64).  If the compacted copy cannot be allocated, or the entry point is among the deleted (the
+  // index then stays in the reference's entry-lost state, entry_point() still naming the removed id), the job prunes in
+  // place and keeps the rows (FVDB_VACUUM_KEEP_ROWS); a later vacuum reclaims them.  *removed: the reference's count.
+  int vacuum(uint64_t* removed);
+  uint64_t vacuum() {  // the reference's signature; a failure reads as 0
+    uint64_t r = 0;
+    return vacuum(&r) == FVDB_OK ? r : 0;
+  }
+  void set_resident_vacuum(bool on) { resident_vacuum_ = on; }
+  bool resident_vacuum() const { return resident_vacuum_; }
+  void set_vacuum_keep_rows(bool on) { vacuum_keep_rows_ = on; }  // A/B and tests: the resident job without the reclaim
+  // the last vacuum that removed something: which path it took and, for a resident one, the job's figures
+  enum VacuumPath : int { VACUUM_NONE = 0, VACUUM_RESIDENT = 1, VACUUM_RESIDENT_KEEP_ROWS = 2, VACUUM_HOST = 3 };
+  int vacuum_info(fvdb_graph_maintenance_info_t* out) const {
+    *out = vacuum_info_;
+    return vacuum_path_;
+  }
+  uint64_t store_rows() const { return store_ ? fvdb_store_rows(store_) : 0; }  // rows the vectors occupy in HBM
   int64_t level_of(uint64_t id) const;
   int64_t neighbors(uint64_t id, uint32_t layer, uint64_t* out, uint64_t cap);
   const float* vector_of(uint64_t id) const;  // host copy (migration, get_vector_by_id)
@@ -374,7 +396,8 @@ class HNSWIndex {
   // The adjacency lists exist twice: nbrs_ (host) and the fixed-stride rows in HBM (graph_).  host_ahead_: nbrs_ holds
   // changes the device has not seen (restore, bulk build, vacuum, inserts made before the device graph existed) — the
   // next device use installs the whole graph once.  dev_ahead_: device inserts have linked nodes whose lists nbrs_
-  // does not hold yet — whoever needs nbrs_ (export, neighbours, host walk, vacuum, a host-path insert) pulls them.
+  // does not hold yet (a resident vacuum leaves it set too) — whoever needs nbrs_ (export, neighbours, host walk, the host
+  // form of vacuum, a host-path insert) pulls them.
   // A host-path insert made while the two agree patches the rows it changed (fvdb_graph_set_lists): no whole-graph
   // upload follows an insert or a delete.
   fvdb_graph* graph_ = nullptr;
@@ -382,6 +405,11 @@ class HNSWIndex {
   int insert_mode_ = 0;
   int visited_mode_ = 0;
   uint32_t visited_slots_ = 0;
+  bool resident_vacuum_ = true, vacuum_keep_rows_ = false;
+  int vacuum_path_ = VACUUM_NONE;
+  fvdb_graph_maintenance_info_t vacuum_info_{};
+  uint64_t vacuum_host(const std::vector<uint8_t>& dead, uint64_t removed);  // the host algorithm; the lists are pulled
+  void vacuum_adopt(bool reclaimed, const std::vector<uint8_t>& dead);        // bookkeeping after the device job
   bool host_link_reported_ = false;  // the stderr line "device insert refused, linking on the host" was written
   fvdb_graph_insert_stats insert_stats_{};
   uint64_t n_host_inserts_ = 0;

@@ -1047,11 +1047,12 @@ int HNSWIndex::restore(const uint64_t* ids, const float* v, uint64_t n, uint32_t
   return FVDB_OK;
 }
 
-// src/hnsw/operations.rs:176-200: deleted nodes leave the node map and every neighbour set.  Their rows stay in HBM
-// unreferenced (the row store is append-only); `registered_ == 0` is this mirror's "nodes.get() == None".  The
-// reference does not repair an entry point that was removed: its searches then fail and its insert panics.
-uint64_t HNSWIndex::vacuum() {
-  if (ensure_host_graph()) return 0;
+// src/hnsw/operations.rs:176-200: deleted nodes leave the node map and every neighbour set.  The reference does not
+// repair an entry point that was removed: its searches then fail and its insert panics.  `registered_ == 0` is this
+// mirror's "nodes.get() == None" for a node whose rows are still held (host form, keep-rows form); the resident job
+// drops such nodes for good, together with the ones it removes itself (fvdb_host.hpp).
+int HNSWIndex::vacuum(uint64_t* removed_out) {
+  if (removed_out) *removed_out = 0;
   std::vector<uint8_t> dead(ids_.size(), 0);
   uint64_t removed = 0;
   for (size_t i = 0; i < ids_.size(); ++i)
@@ -1059,7 +1060,39 @@ uint64_t HNSWIndex::vacuum() {
       dead[i] = 1;
       ++removed;
     }
-  if (removed == 0) return 0;
+  if (removed == 0) return FVDB_OK;
+  int rc;
+  bool resident = resident_vacuum_ && graph_ != nullptr;
+  if (resident && host_ahead_) {  // the device copy is brought up to date first; a graph it cannot hold takes the host form
+    rc = sync_graph();
+    if (rc == FVDB_E_UNSUPPORTED) resident = false;
+    else if (rc) return rc;
+  }
+  if (resident) {
+    const bool entry_dead = has_entry_ && deleted_[entry_];  // removed now, or by an earlier vacuum (entry_lost_): the numbering stays
+    uint32_t flags = (vacuum_keep_rows_ || entry_dead) ? FVDB_VACUUM_KEEP_ROWS : 0u;
+    rc = fvdb_graph_vacuum(graph_, flags, nullptr);
+    if (rc == FVDB_E_OOM && flags == 0) {  // no room for the second copy: a vacuum that worked before still works
+      flags = FVDB_VACUUM_KEEP_ROWS;
+      rc = fvdb_graph_vacuum(graph_, flags, nullptr);
+    }
+    if (rc && rc != FVDB_E_UNSUPPORTED) return rc;
+    if (rc == FVDB_OK) {
+      fvdb_graph_maintenance_info(graph_, &vacuum_info_);
+      vacuum_path_ = flags ? VACUUM_RESIDENT_KEEP_ROWS : VACUUM_RESIDENT;
+      vacuum_adopt(flags == 0, dead);
+      n_registered_ -= removed;
+      if (removed_out) *removed_out = removed;
+      return FVDB_OK;
+    }
+  }
+  if ((rc = ensure_host_graph())) return rc;
+  vacuum_host(dead, removed);
+  if (removed_out) *removed_out = removed;
+  return FVDB_OK;
+}
+
+uint64_t HNSWIndex::vacuum_host(const std::vector<uint8_t>& dead, uint64_t removed) {
   for (size_t i = 0; i < ids_.size(); ++i) {
     if (dead[i]) {
       registered_[i] = 0;
@@ -1074,7 +1107,56 @@ uint64_t HNSWIndex::vacuum() {
   n_registered_ -= removed;
   if (has_entry_ && dead[entry_]) entry_lost_ = true;
   host_ahead_ = true;
+  vacuum_path_ = VACUUM_HOST;
+  vacuum_info_ = fvdb_graph_maintenance_info_t{};
   return removed;
+}
+
+// The device job has pruned the lists (and, `reclaimed`, renumbered the nodes: new index = undeleted nodes before it).
+// The lists now exist on the device only: whoever needs nbrs_ pulls them, as after a device insert.
+void HNSWIndex::vacuum_adopt(bool reclaimed, const std::vector<uint8_t>& dead) {
+  {
+    std::lock_guard<std::mutex> lk(view_mu_);  // the cached allow view names node indices and a mask that is now stale
+    view_.reset();
+    view_key_.clear();
+  }
+  const size_t n = ids_.size();
+  if (!reclaimed) {
+    for (size_t i = 0; i < n; ++i)
+      if (dead[i]) {
+        registered_[i] = 0;
+        auto it = index_of_.find(ids_[i]);
+        if (it != index_of_.end() && it->second == i) index_of_.erase(it);
+      }
+    if (has_entry_ && dead[entry_]) entry_lost_ = true;
+  } else {
+    // every deleted node goes: the ones removed now and those an earlier host-form or keep-rows vacuum left behind
+    size_t w = 0;
+    uint32_t entry = entry_;
+    index_of_.clear();
+    for (size_t i = 0; i < n; ++i) {
+      if (deleted_[i]) continue;
+      if (has_entry_ && i == entry_) entry = (uint32_t)w;
+      if (w != i) {
+        ids_[w] = ids_[i];
+        level_[w] = level_[i];
+        registered_[w] = registered_[i];
+        std::memmove(&host_vecs_[w * dim_], &host_vecs_[i * dim_], (size_t)dim_ * 4);
+      }
+      if (registered_[w]) index_of_[ids_[w]] = (uint32_t)w;
+      ++w;
+    }
+    ids_.resize(w);
+    level_.resize(w);
+    registered_.resize(w);
+    deleted_.assign(w, 0);
+    host_vecs_.resize(w * dim_);
+    host_vecs_.shrink_to_fit();
+    entry_ = entry;
+  }
+  nbrs_.assign(ids_.size(), {});
+  for (size_t i = 0; i < ids_.size(); ++i) nbrs_[i].resize(level_[i] + 1);
+  dev_ahead_ = true;
 }
 
 uint64_t HNSWIndex::graph_slots() const {

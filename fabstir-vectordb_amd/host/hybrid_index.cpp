@@ -293,7 +293,7 @@ int HybridIndex::from_parts(const uint64_t* ids, const double* ts, uint64_t n, u
 int HybridIndex::vacuum(uint64_t* hnsw_removed, uint64_t* ivf_removed) {
   std::unique_lock<std::shared_mutex> w(rw_, std::defer_lock);
   if (int rc = write_lock(w)) return rc;
-  *hnsw_removed = recent_->vacuum();
+  if (int rc = recent_->vacuum(hnsw_removed)) return rc;
   return historical_->vacuum(ivf_removed);
 }
 

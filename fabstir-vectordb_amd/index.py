@@ -117,6 +117,13 @@ HOST_SIGNATURES = {
     "fvh_hybrid_vacuum": (i32, [vp, u64p, u64p]),
     "fvh_ivf_vacuum": (i32, [vp, u64p]),
     "fvh_hnsw_vacuum": (u64, [vp]),
+    # resident vacuum
+    "fvh_hnsw_vacuum_ex": (i32, [vp, u64p]),
+    "fvh_hnsw_set_resident_vacuum": (None, [vp, i32]),
+    "fvh_hnsw_resident_vacuum": (i32, [vp]),
+    "fvh_hnsw_set_vacuum_keep_rows": (None, [vp, i32]),
+    "fvh_hnsw_vacuum_info": (i32, [vp, vp]),
+    "fvh_hnsw_store_rows": (u64, [vp]),
     "fvh_hybrid_from_parts": (i32, [vp, u64p, f64p, u64, u64, u64, i32]),
     "fvh_hybrid_timestamp_count": (u64, [vp]),
     "fvh_hybrid_export_timestamps": (None, [vp, u64p, f64p]),
@@ -519,7 +526,37 @@ class HNSWIndex(_Base):
         return bool(self.lib.fvh_hnsw_is_deleted(self.h, int(id)))
 
     def vacuum(self):
-        return int(self.lib.fvh_hnsw_vacuum(self.h))
+        """Deleted nodes leave every neighbour list and the node map; returns how many.  With a device graph this is one
+        device job that also gives their rows back (set_resident_vacuum); a failure raises."""
+        out = C.c_uint64(0)
+        self._check(self.lib.fvh_hnsw_vacuum_ex(self.h, C.byref(out)))
+        return out.value
+
+    def set_resident_vacuum(self, on):
+        """True (default): vacuum() runs on the adjacency in HBM and compacts the row store (fvdb_graph_vacuum).  False:
+        the host algorithm — lists pulled, filtered and installed whole at the next device use, rows kept.  Same
+        graph and same answers either way."""
+        self.lib.fvh_hnsw_set_resident_vacuum(self.h, int(bool(on)))
+
+    def resident_vacuum(self):
+        return bool(self.lib.fvh_hnsw_resident_vacuum(self.h))
+
+    def _set_vacuum_keep_rows(self, on):
+        """A/B and tests: the resident job prunes in place and reclaims nothing (FVDB_VACUUM_KEEP_ROWS)."""
+        self.lib.fvh_hnsw_set_vacuum_keep_rows(self.h, int(bool(on)))
+
+    def vacuum_info(self):
+        """The last vacuum() that removed something: "path" (None before the first, "resident", "resident_keep_rows" or
+        "host") and, for a resident one, the device job's figures (fvdb_graph_maintenance_info_t; zeros otherwise)."""
+        m = _capi.GraphMaintenanceInfo()
+        path = self.lib.fvh_hnsw_vacuum_info(self.h, C.cast(C.pointer(m), C.c_void_p))
+        out = {name: getattr(m, name) for name, _ in m._fields_}
+        out["path"] = (None, "resident", "resident_keep_rows", "host")[path]
+        return out
+
+    def store_rows(self):
+        """Rows the index's vectors occupy in HBM (equals node_count() after a resident vacuum)."""
+        return int(self.lib.fvh_hnsw_store_rows(self.h))
 
     def get_vector_by_id(self, id):
         out = np.empty(int(self.lib.fvh_hnsw_dimension(self.h)), np.float32)

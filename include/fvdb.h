@@ -453,6 +453,41 @@ typedef struct fvdb_graph_insert_info_t {
 int fvdb_graph_set_insert_visited(fvdb_graph* g, int mode, uint32_t table_slots);
 int fvdb_graph_insert_info(fvdb_graph* g, uint32_t ef_construction, fvdb_graph_insert_info_t* out);
 
+/* ---- device-resident graph maintenance ---------------------------------------------------------
+ * HNSWIndex::vacuum (src/hnsw/operations.rs:176-200: deleted nodes leave every neighbour set, then the node map) on
+ * the adjacency in HBM, as one device job.  Every node whose deleted flag is set is dropped from every list; a list
+ * keeps its survivors in their old order, each with its stored edge distance (so the distances stay valid and no
+ * whole-graph recomputation follows).  Rows of any stride are served (a row longer than 64 entries is walked in chunks).
+ *
+ * flags = 0: the job also RECLAIMS.  The surviving nodes are renumbered densely in their old order (node index = store
+ *   row still holds), the row store, the adjacency and distance rows, the stamps and the per-node arrays are written into
+ *   fresh buffers sized for the survivors (plus the usual growth slack) and swapped in, and the old ones are freed.  The
+ *   job holds two copies for a moment.  Every allocation precedes the first change: FVDB_E_OOM leaves the graph and the
+ *   store exactly as they were.  The graph must cover the whole store (FVDB_E_INVALID otherwise).  The entry point is
+ *   renumbered; if it was deleted the graph has no entry afterwards and searches are refused (the reference does not
+ *   repair it either).  The caller renumbers by the same rule: new index = number of undeleted nodes before it.
+ * FVDB_VACUUM_KEEP_ROWS: the lists are pruned in place with the numbering unchanged and nothing allocated or freed; the
+ *   lists of the deleted nodes are emptied; the nodes stay (deleted, unreferenced) until a later job reclaims them.
+ *
+ * removed (optional): flags = 0: nodes dropped; KEEP_ROWS: deleted nodes whose layer-0 list this call emptied.
+ * Every mask created before the call is stale afterwards.  fvdb_graph_upload_bytes does not change.  The caller
+ * excludes searches and inserts for the duration; the job synchronises the device before it starts and its stream
+ * before it returns.  Only totals, counters and the 32-byte construction state cross the host link. */
+#define FVDB_VACUUM_KEEP_ROWS 1u
+typedef struct fvdb_graph_maintenance_info_t {
+  uint64_t nodes_in, nodes_out;   /* nodes before / after */
+  uint64_t edges_in, edges_out;   /* stored neighbours before / after, all layers */
+  uint64_t rows_reclaimed;        /* store rows given back (0 with KEEP_ROWS) */
+  uint64_t bytes_reclaimed;       /* what the dropped nodes held: store row, adjacency + distance rows, stamps, per-node words */
+  uint64_t host_bytes;            /* copied to or from the host by the job */
+  uint64_t move_bytes;            /* read + written in HBM by the store-row move */
+  float ms_scan, ms_prune, ms_move;  /* device time per stage (HIP events) */
+  float ms_total;                    /* wall clock of the call, allocations and the final synchronisation included */
+} fvdb_graph_maintenance_info_t;
+int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* removed);
+/* Figures of the last fvdb_graph_vacuum on this graph (zeros before the first). */
+int fvdb_graph_maintenance_info(fvdb_graph* g, fvdb_graph_maintenance_info_t* out);
+
 /* With profiling on (fvdb_ctx_set_profiling): summed duration (HIP events on the launch stream) of the last
  * <= 64 launches of the traversal kernel since the previous call, and how many were summed; and (always) the
  * rows scored and hops taken by all queries since the previous call (either may be NULL).  Synchronises. */
