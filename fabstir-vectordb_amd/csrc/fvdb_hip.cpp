@@ -22,6 +22,7 @@
 #include "common.h"
 #include "kernels_misc.h"
 #include "kernels_scan.h"
+#include "kernels_wide.h"
 #include "kernels_coarse.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma_wg.h"
@@ -182,6 +183,7 @@ struct IvfScratch {
   Buf s_sdist{this}, s_probes2{this};
   Buf s_q{this}, s_cpart{this}, s_probes{this}, s_cnt{this}, s_fill{this}, s_eoff{this}, s_ioff{this}, s_entries{this};
   Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
+  Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
   Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
   hipEvent_t sev[EV_COUNT] = {};
   uint32_t* scalar(ScalWord w) const { return s_scalars.as<uint32_t>() + w; }
@@ -1124,6 +1126,70 @@ uint32_t sub_batch(fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
   return (uint32_t)std::min<uint64_t>(fit, B);
 }
 
+// ---- the wide selection (kernels_wide.h): 1 <= k <= FVDB_MAX_K_WIDE ----
+static_assert(kWideMaxK == FVDB_MAX_K_WIDE && kWideMaxProbes == FVDB_MAX_K, "kernels_wide.h sizes its LDS by these");
+// Arena budget of one sub-batch: 1 GiB of distance words, the figure the partial lists of the register path are held to.
+constexpr uint64_t kWideArenaBytes = 1ull << 30;
+// Blocks a query's arena is sized for: its np probed lists are distinct, so they hold no more than np longest lists
+// and no more than every list together.
+uint32_t wide_arena_blocks(const fvdb_ivf* ivf, uint32_t np) {
+  const uint64_t all = ivf->pool.used_blocks;
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)np * ivf->max_list_blocks, all));
+}
+uint32_t wide_sub_batch(const fvdb_ivf* ivf, uint32_t B, uint32_t np) {
+  const uint64_t per_q = (uint64_t)wide_arena_blocks(ivf, np) * 256;
+  const uint64_t fit = std::min<uint64_t>(std::max<uint64_t>(kWideArenaBytes / per_q, 1), 16384);
+  return (uint32_t)std::min<uint64_t>(fit, B);
+}
+
+// Fine stage of the wide path: every row of the probed lists scored into the arena, then one workgroup per query
+// selects.  Same outputs as run_fine_exact.
+int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  const uint32_t nlist = ivf->nlist;
+  const uint32_t segb = pick_segb(ivf, b.B, b.np);
+  const uint32_t cap_blocks = wide_arena_blocks(ivf, b.np);
+  const uint64_t stride = (uint64_t)cap_blocks * 64;
+  int rc = plan_scratch(ivf, E, b.B, b.np);
+  if (rc) return rc;
+  HIPCHK(ctx, S.s_wbase.ensure((size_t)b.B * (b.np + 1) * 4));
+  HIPCHK(ctx, S.s_arena.ensure((size_t)b.B * stride * 4));
+  HIPCHK(ctx, S.s_scalars.ensure(kScalarsBytes));
+  HIPCHK(ctx, hipMemsetAsync(S.s_cnt.p, 0, (size_t)nlist * 4, ctx->stream));
+  launch_plan(ivf, E, b.probes, b.B * b.np, b.np, segb, /*Q=*/16, scan_stats(S), /*rezero_cnt=*/nullptr);
+  const ListTable lists = list_table(ivf);
+  hipLaunchKernelGGL(wide_base_kernel, dim3(cdiv(b.B, 256)), dim3(256), 0, ctx->stream, b.probes, lists.off, b.B, b.np,
+                     cap_blocks, S.s_wbase.as<uint32_t>());
+  mark(ivf, E, EV_SCAN_BEGIN);
+  const PoolView pool = list_pool(ivf, E);
+  const uint32_t grid = (uint32_t)ctx->num_cus * ivf_knobs().scan_wgs_per_cu;
+  auto score = ivf->f16 ? wide_score_kernel<1> : wide_score_kernel<0>;
+  hipLaunchKernelGGL(score, dim3(grid), dim3(256), 0, ctx->stream, pool.data, pool.valid, pool.d4, lists.off, lists.blocks,
+                     nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(), (const u32x2*)S.s_entries.as<uint2>(),
+                     S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.np,
+                     S.s_wbase.as<uint32_t>(), S.s_arena.as<uint32_t>(), stride);
+  mark(ivf, E, EV_SCAN_DONE);
+  WideArgs w{};
+  w.pool = pool;
+  w.lists = lists;
+  w.probes = b.probes;
+  w.base = S.s_wbase.as<uint32_t>();
+  w.arena = S.s_arena.as<uint32_t>();
+  w.stride = stride;
+  w.B = b.B;
+  w.k = b.k;
+  w.nprobe = b.np;
+  w.out_ids = b.out_ids;
+  w.out_dist = b.out_dist;
+  w.out_counts = b.out_counts;
+  w.out_keys = b.out_keys;
+  hipLaunchKernelGGL(wide_select_kernel, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
+  mark(ivf, E, EV_FINE_DONE);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
 // ---- sharded search: filter thresholds computed once per query across the ranks (comm_sharded.h) ----
 // Whether a sharded step of B scanned queries uses the shared thresholds.  Every rank must answer alike (the answer
 // decides whether a collective is issued), so only quantities that are the same on every rank enter: shapes, and the
@@ -1956,6 +2022,59 @@ int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t
                                          out_keys_dev, probes_dev));
 }
 
+// search_common for the wide selection: coarse stage as ever, then run_fine_wide, sub-batched under the arena budget.
+static int search_wide_common(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                              uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
+  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
+  if (ivf->glob_set) FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search does not serve a shard of a larger index");
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t np = std::min(nprobe, ivf->nlist);
+  if (np == 0) FAIL(ctx, FVDB_E_INVALID, "nprobe must be > 0");
+  if (np > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe above FVDB_MAX_K");
+  int rc = upload_table(ivf);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> enq(S.enq);
+  if (ivf->ctx->profiling)
+    for (auto& e : S.sev)
+      if (!e) (void)hipEventCreate(&e);
+  S.pend_filter = false;
+  const uint32_t step = wide_sub_batch(ivf, B, np);
+  for (uint32_t o = 0; o < B; o += step) {
+    const uint32_t b = std::min(step, B - o);
+    const float* qpad = nullptr;
+    rc = padded_queries(ivf, E, q_dev + (size_t)o * ivf->d, b, &qpad);
+    if (rc) return rc;
+    HIPCHK(ctx, S.s_probes.ensure((size_t)b * np * 4));
+    rc = run_coarse(ivf, E, qpad, b, np, S.s_probes.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    rc = run_fine_wide(ivf, E,
+                       Batch{qpad, S.s_probes.as<uint32_t>(), b, k, np, out_ids ? out_ids + (size_t)o * k : nullptr,
+                             out_dist ? out_dist + (size_t)o * k : nullptr, out_counts ? out_counts + o : nullptr,
+                             out_keys ? out_keys + (size_t)o * k : nullptr});
+    if (rc) return rc;
+    rc = finish_profile(ivf, E, true, true);
+    if (rc) return rc;
+  }
+  ivf->last_set.store(E.S);
+  ivf->last_ctx.store(E.ctx);
+  return FVDB_OK;
+}
+
+int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                  uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  Env E{};
+  int rc = mask ? mask_env(ivf, on, slot, mask, &E) : slot_env(ivf, on, slot, &E);
+  if (rc) return rc;
+  return slot_done(ivf, E, search_wide_common(ivf, E, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev,
+                                              out_keys_dev));
+}
+
 int fvdb_ivf_search_all_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint64_t* out_ids_dev,
                             float* out_dist_dev, uint32_t* out_counts_dev) {
   return search_common(ivf, Env{ivf->ctx, ivf}, q_dev, B, k, 0, true, out_ids_dev, out_dist_dev, out_counts_dev, nullptr);
@@ -2003,10 +2122,11 @@ struct Lease {
 }  // extern "C++"
 
 static int search_host(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, bool all,
-                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts) {
+                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts, bool wide = false) {
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
   if (B == 0) return FVDB_OK;
-  if (k == 0 || k > FVDB_MAX_K) FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
+  if (k == 0 || k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K))
+    FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, wide ? "k must be in 1..FVDB_MAX_K_WIDE" : "k must be in 1..FVDB_MAX_K");
   int rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
   if (rc) return rc;
   Lease L(ivf);
@@ -2020,8 +2140,10 @@ static int search_host(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, ui
     HIPCHK(ctx, S.s_out_dist.ensure((size_t)B * k * 4));
     HIPCHK(ctx, S.s_out_cnt.ensure((size_t)B * 4));
     HIPCHK(ctx, hipMemcpyAsync(S.s_in.p, q, (size_t)B * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = search_common(ivf, L.E, S.s_in.as<float>(), B, k, nprobe, all, S.s_out_ids.as<uint64_t>(),
-                          S.s_out_dist.as<float>(), S.s_out_cnt.as<uint32_t>(), nullptr);
+    int r = wide ? search_wide_common(ivf, L.E, S.s_in.as<float>(), B, k, nprobe, S.s_out_ids.as<uint64_t>(),
+                                      S.s_out_dist.as<float>(), S.s_out_cnt.as<uint32_t>(), nullptr)
+                 : search_common(ivf, L.E, S.s_in.as<float>(), B, k, nprobe, all, S.s_out_ids.as<uint64_t>(),
+                                 S.s_out_dist.as<float>(), S.s_out_cnt.as<uint32_t>(), nullptr);
     if (r) return r;
     HIPCHK(ctx, hipMemcpyAsync(out_ids, S.s_out_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_dist, S.s_out_dist.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2036,6 +2158,10 @@ static int search_host(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, ui
 int fvdb_ivf_search(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                     float* out_dist, uint32_t* out_counts) {
   return search_host(ivf, q, B, k, nprobe, false, out_ids, out_dist, out_counts);
+}
+int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
+                         float* out_dist, uint32_t* out_counts) {
+  return search_host(ivf, q, B, k, nprobe, false, out_ids, out_dist, out_counts, /*wide=*/true);
 }
 int fvdb_ivf_search_all(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_counts) {

@@ -1,0 +1,329 @@
+// kernels_wide.h — the list scan for 256 < k <= 4096 (and any smaller k): the same result as kernels_scan.h defines,
+// selected another way.  Replaces IVFIndex::search_with_config's list scan, sort and truncate(k)
+// (src/ivf/core.rs:626-681) where k outgrows the 64 x 4 register list of WaveTopK.
+//
+//   score   wide_score_kernel: the work items and the fold of scan_topk_kernel (lane = row, queries through the scalar
+//           path), but each row's distance bits go to a per-query arena at the row's scan position `seq` instead of a
+//           register list.  Dead rows, masked rows and block padding write kInf32.  The arena index IS the tie-break,
+//           so this stage has no atomics and no ordering concern.
+//   select  wide_select_kernel: one workgroup per query.  Radix select (8-bit digits, LDS histogram) of the k-th
+//           smallest distance word — non-negative f32 bits are monotone as u32 — then the rows below the cut and the
+//           first rows AT the cut in seq order are gathered as 64-bit keys into LDS, sorted there (bitonic; the keys
+//           are unique) and resolved seq -> (probe rank, position) -> pool slot -> id as merge_topk_kernel does.
+//
+// Arena of a query: 64 words per block of its probed lists, rank after rank; base[q][r] = blocks of the lists ranked
+// before r (wide_base_kernel), so arena index == seq.
+#pragma once
+#include "kernels_scan.h"
+
+#pragma clang fp contract(off)
+
+namespace fvdb {
+
+constexpr uint32_t kWideMaxK = 4096;       // FVDB_MAX_K_WIDE: the survivors' keys fill 32 KB of LDS
+constexpr uint32_t kWideSelThreads = 512;  // 8 waves share one query's arena
+constexpr uint32_t kWideMaxProbes = 256;   // FVDB_MAX_K: nprobe keeps its limit
+
+struct WideArgs {
+  PoolView pool;
+  ListTable lists;
+  const uint32_t* probes;  // [B][nprobe] list ids in probe order
+  const uint32_t* base;    // [B][nprobe + 1] blocks of earlier-ranked probed lists; [nprobe] = all of them
+  uint32_t* arena;         // [B][stride] distance bits by seq
+  uint64_t stride;         // words per query
+  uint32_t B, k, nprobe;
+  uint64_t* out_ids;       // any of the four may be null
+  float* out_dist;
+  uint32_t* out_counts;
+  uint64_t* out_keys;
+};
+
+// base[q][0..np]: exclusive prefix of the block counts of query q's probed lists.  A list that would not fit the
+// query's arena (cap_blocks) counts as empty here and is then skipped by the score stage: nothing writes past the end.
+__global__ void wide_base_kernel(const uint32_t* __restrict__ probes, const uint32_t* __restrict__ list_off, uint32_t B,
+                                 uint32_t np, uint32_t cap_blocks, uint32_t* __restrict__ base) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= B) return;
+  uint32_t acc = 0;
+  for (uint32_t r = 0; r < np; ++r) {
+    base[(size_t)q * (np + 1) + r] = acc;
+    const uint32_t L = probes[(size_t)q * np + r];
+    const uint32_t nb = L == kInf32 ? 0u : list_off[L + 1] - list_off[L];
+    if (nb <= cap_blocks - acc) acc += nb;
+  }
+  base[(size_t)q * (np + 1) + np] = acc;
+}
+
+// One work item: rows of blocks [b0, b1) of a list against the ne (<= QQ) queries of a group.  The fold is
+// scan_item's, statement for statement (kernels_scan.h): the two must round alike.
+template <int QQ, int ST>
+__device__ __forceinline__ void wide_score_item(const void* __restrict__ pool_data, const uint64_t* __restrict__ pool_valid,
+                                                const uint32_t d4, const uint32_t* __restrict__ list_blocks,
+                                                const u32x2* __restrict__ entries, const float* __restrict__ queries,
+                                                const uint32_t dpad, const uint32_t nprobe,
+                                                const uint32_t* __restrict__ base, uint32_t* __restrict__ arena,
+                                                const uint64_t stride, const uint32_t b_begin, const uint32_t b0,
+                                                const uint32_t b1, const uint32_t e0, const uint32_t ne, const int lane) {
+  uint32_t qoff[QQ];
+#pragma unroll
+  for (int j = 0; j < QQ; ++j) qoff[j] = cload(entries + e0 + ((uint32_t)j < ne ? j : 0)).x * dpad;
+  // where query j's distances go: lane j keeps (arena word of this list's first row, blocks owned there) and the store
+  // below reads them back lane by lane — sixteen wave-uniform 64-bit offsets would not fit the scalar registers
+  uint32_t room_l = 0;  // 0: no query j, or its list was left out of the arena
+  uint64_t aoff_l = 0;
+  if ((uint32_t)lane < ne) {
+    const u32x2 e = entries[e0 + lane];
+    const uint32_t* bp = base + (size_t)e.x * (nprobe + 1) + e.y;
+    room_l = bp[1] - bp[0];
+    aoff_l = (uint64_t)e.x * stride + (uint64_t)bp[0] * 64;
+  }
+
+  for (uint32_t b = b0; b < b1; ++b) {
+    const uint32_t blk = cload(list_blocks + b_begin + b);
+    float acc[QQ];
+#pragma unroll
+    for (int j = 0; j < QQ; ++j) acc[j] = 0.0f;
+    uint32_t c = 0;
+    for (; c + 4 <= d4; c += 4) {
+      float x[16];
+      load_rows16<ST>(pool_data, blk, d4, c, lane, x);
+      f32x16 qn = cload16(queries + qoff[0] + 4 * c);
+#pragma unroll
+      for (int j = 0; j < QQ; ++j) {
+        const f32x16 qv = qn;
+        if (j + 1 < QQ) qn = cload16(queries + qoff[j + 1] + 4 * c);
+        __builtin_amdgcn_sched_barrier(0);
+        float t, a = acc[j];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          t = x[i] - qv[i];
+          a = a + t * t;
+        }
+        acc[j] = a;
+      }
+    }
+    if (ST == 0) {
+      const float4* xp = (const float4*)pool_data + (size_t)blk * d4 * 64 + lane;
+      for (; c < d4; ++c) {
+        const float4 xv = xp[(size_t)c * 64];
+#pragma unroll
+        for (int j = 0; j < QQ; ++j) {
+          const f32x4 qv = cload((const f32x4*)(queries + qoff[j] + 4 * c));
+          float t;
+          t = xv.x - qv.x; acc[j] = acc[j] + t * t;
+          t = xv.y - qv.y; acc[j] = acc[j] + t * t;
+          t = xv.z - qv.z; acc[j] = acc[j] + t * t;
+          t = xv.w - qv.w; acc[j] = acc[j] + t * t;
+        }
+      }
+    }
+    const uint64_t vmask = cload(pool_valid + blk);
+    const bool live = (vmask >> lane) & 1ull;
+#pragma unroll
+    for (int j = 0; j < QQ; ++j) {
+      const float dist = sqrtf(acc[j]);
+      const uint32_t room = rlane(room_l, j);
+      const uint64_t aoff = ((uint64_t)rlane((uint32_t)(aoff_l >> 32), j) << 32) | rlane((uint32_t)aoff_l, j);
+      if (b < room) arena[aoff + (size_t)b * 64 + lane] = live ? __float_as_uint(dist) : kInf32;
+    }
+  }
+}
+
+// Persistent waves pull (list segment, query group) items from the plan's work queue, as scan_topk_kernel does.
+template <int ST>
+__global__ __launch_bounds__(256) void wide_score_kernel(
+    const void* __restrict__ pool_data, const uint64_t* __restrict__ pool_valid, const uint32_t d4,
+    const uint32_t* __restrict__ list_off, const uint32_t* __restrict__ list_blocks, const uint32_t nlist,
+    const uint32_t* __restrict__ entry_off, const uint32_t* __restrict__ item_off, const u32x2* __restrict__ entries,
+    const uint32_t* __restrict__ n_items_p, uint32_t* __restrict__ head, const float* __restrict__ queries,
+    const uint32_t dpad, const uint32_t segb, const uint32_t nprobe, const uint32_t* __restrict__ base,
+    uint32_t* __restrict__ arena, const uint64_t stride) {
+  constexpr uint32_t Q = 16;
+  const int lane = threadIdx.x & 63;
+  const uint32_t n_items = cload(n_items_p);
+  for (;;) {
+    uint32_t item = 0;
+    if (lane == 0) item = atomicAdd(head, 1u);
+    item = rfl(item);
+    if (item >= n_items) return;
+
+    uint32_t lo = 0, hi = nlist;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (cload(item_off + mid) <= item) lo = mid; else hi = mid;
+    }
+    const uint32_t L = lo;
+    const uint32_t e_begin = cload(entry_off + L);
+    const uint32_t cnt = cload(entry_off + L + 1) - e_begin;
+    const uint32_t ngroups = (cnt + Q - 1) / Q;
+    const uint32_t local = item - cload(item_off + L);
+    const uint32_t seg = local / ngroups, g = local - seg * ngroups;
+    const uint32_t b_begin = cload(list_off + L);
+    const uint32_t nblk = cload(list_off + L + 1) - b_begin;
+    const uint32_t b0 = seg * segb;
+    const uint32_t b1 = min(b0 + segb, nblk);
+    const uint32_t e0 = e_begin + g * Q;
+    const uint32_t ne = min(Q, cnt - g * Q);
+
+    if (ne <= 4)
+      wide_score_item<4, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
+                             b_begin, b0, b1, e0, ne, lane);
+    else if (ne <= 8)
+      wide_score_item<8, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
+                             b_begin, b0, b1, e0, ne, lane);
+    else
+      wide_score_item<16, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
+                              b_begin, b0, b1, e0, ne, lane);
+  }
+}
+
+// rank r with base[r] <= blk < base[r + 1] (lists of no blocks own no index): the last r with base[r] <= blk
+__device__ __forceinline__ uint32_t wide_rank_of(const uint32_t* s_base, uint32_t np, uint32_t blk) {
+  uint32_t lo = 0, hi = np;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_base[mid] <= blk) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const WideArgs a) {
+  constexpr uint32_t T = kWideSelThreads, W = T / 64;
+  __shared__ uint64_t s_keys[kWideMaxK];
+  __shared__ uint32_t s_hist[256];
+  __shared__ uint32_t s_base[kWideMaxProbes + 1];
+  __shared__ uint32_t s_wties[W];
+  __shared__ uint32_t s_prefix, s_below, s_want, s_taken;
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t q = blockIdx.x, np = a.nprobe, k = a.k;
+  for (uint32_t r = tid; r <= np; r += T) s_base[r] = a.base[(size_t)q * (np + 1) + r];
+  if (tid == 0) {
+    s_prefix = 0;
+    s_below = 0;
+    s_taken = 0;
+  }
+  __syncthreads();
+  const uint32_t n = s_base[np] * 64;  // arena words of this query (dead rows and padding hold kInf32)
+  const uint32_t* __restrict__ ar = a.arena + (size_t)q * a.stride;
+  // each wave owns a contiguous run of whole blocks, in seq order
+  const uint32_t per = ((n / 64 + W - 1) / W) * 64;
+  const uint32_t w0 = min(wave * per, n), w1 = min(w0 + per, n);
+
+  // ---- the k-th smallest word: cut = its value, below = words smaller than it ----
+  const uint32_t kk = min(k, n);  // n == 0: nothing to select
+  uint32_t cut = 0, below = 0, want = 0;
+  if (kk) {
+    if (tid == 0) s_want = kk;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      for (uint32_t b = tid; b < 256; b += T) s_hist[b] = 0;
+      __syncthreads();
+      const uint32_t prefix = s_prefix;
+      const uint32_t himask = shift == 24 ? 0u : ~0u << (shift + 8);
+      for (uint32_t i = w0 + lane; i < w1; i += 64) {  // whole blocks: all 64 lanes run every round
+        const uint32_t v = ar[i];
+        const bool in = (v & himask) == prefix;
+        const uint32_t dg = (v >> shift) & 255u;
+        // distances of one query share their leading bits: a wave whose words all fall in one bin adds once
+        const uint32_t dg0 = rfl(dg);
+        const uint64_t m_in = __ballot(in);
+        if (__ballot(in && dg != dg0) == 0) {
+          if (lane == 0 && m_in) atomicAdd(&s_hist[dg0], (uint32_t)__popcll(m_in));
+        } else if (in) {
+          atomicAdd(&s_hist[dg], 1u);
+        }
+      }
+      __syncthreads();
+      if (wave == 0) {  // the bin holding the s_want-th word of this round: 4 bins per lane, prefix across lanes
+        const uint32_t h0 = s_hist[4 * lane], h1 = s_hist[4 * lane + 1], h2 = s_hist[4 * lane + 2], h3 = s_hist[4 * lane + 3];
+        const uint32_t mine = h0 + h1 + h2 + h3;
+        uint32_t inc = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t up = __shfl_up(inc, o);
+          if ((int)lane >= o) inc += up;
+        }
+        const uint32_t wantr = s_want, exc = inc - mine;
+        if (exc < wantr && wantr <= inc) {  // exactly one lane
+          uint32_t bin = 4 * lane, acc = exc;
+          if (acc + h0 < wantr) { acc += h0; ++bin;
+            if (acc + h1 < wantr) { acc += h1; ++bin;
+              if (acc + h2 < wantr) { acc += h2; ++bin; } } }
+          s_prefix = prefix | (bin << shift);
+          s_below += acc;
+          s_want = wantr - acc;
+        }
+      }
+      __syncthreads();
+    }
+    cut = s_prefix;
+    below = s_below;
+    want = s_want;  // words equal to `cut` still wanted: the first `want` of them in seq order
+    if (cut == kInf32) want = 0;  // fewer than k live rows: "no row" words are never results
+  }
+
+  // ---- words at the cut ahead of each wave ----
+  uint32_t ties = 0;
+  if (want)
+    for (uint32_t i = w0 + lane; i < w1; i += 64) ties += (uint32_t)__popcll(__ballot(ar[i] == cut));
+  if (lane == 0) s_wties[wave] = ties;
+  __syncthreads();
+  uint32_t tie_rank = 0;  // of the first word at the cut in this wave's run
+  for (uint32_t w = 0; w < wave; ++w) tie_rank += s_wties[w];
+
+  // ---- gather the survivors as (distance bits << 32 | seq) ----
+  if (kk)
+    for (uint32_t i = w0 + lane; i < w1; i += 64) {
+      const uint32_t v = ar[i];
+      const uint64_t m_tie = __ballot(v == cut);
+      const uint32_t my_tie = tie_rank + (uint32_t)__popcll(m_tie & ((1ull << lane) - 1ull));
+      tie_rank += (uint32_t)__popcll(m_tie);
+      uint32_t at = kInf32;
+      if (v < cut) at = atomicAdd(&s_taken, 1u);       // slots [0, below): any order, the sort follows
+      else if (v == cut && my_tie < want) at = below + my_tie;
+      if (at < kWideMaxK) s_keys[at] = ((uint64_t)v << 32) | i;
+    }
+  const uint32_t count = below + want;  // the selection found at least `want` words at the cut
+  uint32_t P = 1;
+  while (P < count) P <<= 1;
+  __syncthreads();
+  for (uint32_t e = count + tid; e < P; e += T) s_keys[e] = ~0ull;
+  __syncthreads();
+
+  // ---- sort ascending ----
+  for (uint32_t kb = 2; kb <= P; kb <<= 1)
+    for (uint32_t j = kb >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = tid; t < P / 2; t += T) {
+        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const uint64_t x = s_keys[lo], y = s_keys[hi];
+        const bool up = (lo & kb) == 0;
+        if ((x > y) == up) {
+          s_keys[lo] = y;
+          s_keys[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+
+  // ---- seq -> (rank, position) -> pool slot -> id ----
+  for (uint32_t e = tid; e < k; e += T) {
+    const bool have = e < count;
+    uint64_t key = ~0ull, id = ~0ull;
+    if (have) {
+      key = s_keys[e];
+      const uint32_t seq = (uint32_t)key;
+      const uint32_t r = wide_rank_of(s_base, np, seq >> 6);
+      const uint32_t L = a.probes[(size_t)q * np + r];
+      const uint32_t pos = seq - s_base[r] * 64;
+      const uint32_t blk = a.lists.blocks[a.lists.off[L] + (pos >> 6)];
+      id = a.pool.ids[(size_t)blk * 64 + (pos & 63)];
+    }
+    const size_t o = (size_t)q * k + e;
+    if (a.out_ids) a.out_ids[o] = id;
+    if (a.out_dist) a.out_dist[o] = have ? __uint_as_float((uint32_t)(key >> 32)) : __uint_as_float(0x7F800000u);
+    if (a.out_keys) a.out_keys[o] = key;
+  }
+  if (tid == 0 && a.out_counts) a.out_counts[q] = count;
+}
+
+}  // namespace fvdb

@@ -379,6 +379,37 @@ class DeviceIVF:
                                                 _ptr(ds, f32p), _ptr(cnt, u32p)))
         return ids, ds, cnt
 
+    def search_wide(self, q, k, nprobe, mask=None):
+        """The search for 1 <= k <= FVDB_MAX_K_WIDE (fvdb_ivf_search_wide); mask: a handle from fvdb_mask_create_ivf."""
+        q = self._rows(q)
+        B = q.shape[0]
+        ids, ds, cnt = self._out(B, k)
+        if mask is None:
+            self.ctx.check(self.lib.fvdb_ivf_search_wide(self.h, _ptr(q, f32p), B, k, nprobe, _ptr(ids, u64p),
+                                                         _ptr(ds, f32p), _ptr(cnt, u32p)))
+            return ids, ds, cnt
+        # the masked form takes device pointers only: stage the batch and copy the block of results back.  The device
+        # entry trusts its input, so the check fvdb_ivf_search_wide runs on host rows is made here
+        if not np.isfinite(q).all():
+            raise NonFiniteInput("non-finite input value")
+        need = B * k
+        q_dev, out_dev = self.ctx.upload(q), self.ctx.alloc(need * 12 + B * 4)
+        try:
+            at = lambda off: C.c_void_p(out_dev.value + off)
+            self.search_wide_dev(q_dev, B, k, nprobe, at(0), at(need * 8), at(need * 12), mask=mask)
+            self.ctx.synchronize()
+            ids = self.ctx.download(at(0), (B, k), np.uint64)
+            ds = self.ctx.download(at(need * 8), (B, k), np.float32)
+            cnt = self.ctx.download(at(need * 12), B, np.uint32)
+        finally:
+            self.ctx.free(q_dev)
+            self.ctx.free(out_dev)
+        return ids, ds, cnt
+
+    def search_wide_dev(self, q_dev, B, k, nprobe, ids_dev, dist_dev, cnt_dev, keys_dev=None, mask=None, on=None, slot=0):
+        self.ctx.check(self.lib.fvdb_ivf_search_wide_dev_slot(self.h, on.h if on is not None else None, slot, mask, q_dev, B, k,
+                                                              nprobe, ids_dev, dist_dev, cnt_dev, keys_dev))
+
     def search_all(self, q, k):
         q = self._rows(q)
         ids, ds, cnt = self._out(q.shape[0], k)

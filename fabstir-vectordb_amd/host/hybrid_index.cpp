@@ -562,12 +562,15 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
                                                     (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
       if (rcs) return rcs;
       sl.ivf_in_flight = true;
-    } else if (sl.ivf_mask) {
-      sl.ivf_in_flight = historical_->search_dev_masked(sl.ivf_mask, q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids,
-                                                        d.dist, d.counts, on, on ? slot : 0) == FVDB_OK;
     } else {
-      sl.ivf_in_flight = historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids, d.dist, d.counts,
-                                                 on, on ? slot : 0) == FVDB_OK;
+      // a historical part the engine refuses (historical_k above FVDB_MAX_K_WIDE, say) fails the search: the result
+      // must never quietly be the recent rows alone
+      const int rch = sl.ivf_mask ? historical_->search_dev_masked(sl.ivf_mask, q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe,
+                                                                   d.ids, d.dist, d.counts, on, on ? slot : 0)
+                                  : historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids, d.dist,
+                                                            d.counts, on, on ? slot : 0);
+      if (rch) return rch;
+      sl.ivf_in_flight = true;
     }
     if (sl.ivf_in_flight) {
       // result copy rides the slot's stream right behind the chain, then the event

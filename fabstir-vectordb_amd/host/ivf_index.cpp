@@ -339,11 +339,13 @@ int IVFIndex::assign(const float* v, uint64_t n, uint32_t dim, uint32_t* out) {
   return fvdb_ivf_assign(dev_, v, n, out);
 }
 
-// src/ivf/core.rs:626-681 for a batch (src/ivf/operations.rs:132-145)
+// src/ivf/core.rs:626-681 for a batch (src/ivf/operations.rs:132-145).  k <= FVDB_MAX_K goes through the register
+// top-k, a larger k (up to FVDB_MAX_K_WIDE) through the wide selection; the engine refuses anything above that.
 int IVFIndex::search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, uint64_t* ids,
                      float* dist, uint32_t* counts) {
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
+  if (k > FVDB_MAX_K) return fvdb_ivf_search_wide(dev_, q, B, k, n_probe, ids, dist, counts);
   return fvdb_ivf_search(dev_, q, B, k, n_probe, ids, dist, counts);
 }
 
@@ -351,6 +353,8 @@ int IVFIndex::search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t 
                          float* dist_dev, uint32_t* counts_dev, fvdb_ctx* on, uint32_t slot) {
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
+  if (k > FVDB_MAX_K)
+    return fvdb_ivf_search_wide_dev_slot(dev_, on, slot, nullptr, q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
   return fvdb_ivf_search_dev_slot(dev_, on, slot, q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
 }
 
@@ -378,6 +382,8 @@ int IVFIndex::search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_
                                 uint64_t* ids_dev, float* dist_dev, uint32_t* counts_dev, fvdb_ctx* on, uint32_t slot) {
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
+  if (k > FVDB_MAX_K)
+    return fvdb_ivf_search_wide_dev_slot(dev_, on, slot, mask.get(), q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
   return fvdb_ivf_search_dev_slot_masked(dev_, on, slot, mask.get(), q_dev, B, k, n_probe, ids_dev, dist_dev, counts_dev, nullptr);
 }
 
@@ -386,7 +392,7 @@ int IVFIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t 
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
   if (B == 0) return FVDB_OK;
-  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
   for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
     if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
   MaskRef mask;

@@ -62,6 +62,9 @@ typedef enum fvdb_status {
 
 /* Largest k (and nprobe) served by the in-kernel wavefront top-k (64 lanes x 4 registers). */
 #define FVDB_MAX_K 256u
+/* Largest k served by the wide selection of the IVF list scan (fvdb_ivf_search_wide*): the distances of the probed
+ * rows go through an arena in HBM and the k best are selected and sorted in LDS.  Equal to the traversal's ef limit. */
+#define FVDB_MAX_K_WIDE 4096u
 /* Row id meaning "no row" in padded outputs / candidate lists. */
 #define FVDB_NO_ROW UINT32_MAX
 #define FVDB_NO_ID UINT64_MAX
@@ -539,6 +542,18 @@ int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t
                                            const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
                                            uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
                                            uint64_t* out_keys_dev);
+/* search_with_config (src/ivf/core.rs:626-681) with 1 <= k <= FVDB_MAX_K_WIDE.  Same result definition, outputs,
+ * padding and keys as fvdb_ivf_search_dev_slot; mask may be NULL (fvdb_mask_create_ivf otherwise; a stale mask is
+ * FVDB_E_INVALID).  Always the exact scan (the matrix-core filter serves k <= 26).  nprobe keeps its limit
+ * (min(nprobe, nlist) <= FVDB_MAX_K).  k = 0 or k > FVDB_MAX_K_WIDE is FVDB_E_UNSUPPORTED, and so is an index holding a
+ * shard of a larger one (fvdb_ivf_set_global_list_sizes).  Slot and stream rules are fvdb_ivf_search_dev_slot's. */
+int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                  uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev, uint64_t* out_keys_dev);
+/* The same search (src/ivf/core.rs:626-681), blocking, with host pointers and leased scratch like fvdb_ivf_search: any
+ * number of host threads may call it on one index. */
+int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
+                         float* out_dist, uint32_t* out_counts);
 /* fvdb_graph_search_dev_slot under a mask: a node the mask does not allow is treated as deleted — never expanded into
  * `candidates`, never returned (src/hnsw/core.rs:511-513, :451-466).  status 1 queries go to the host walk as before;
  * the host must apply the same view there. */
