@@ -85,6 +85,11 @@ SIGNATURES = {
     "fvdb_ivf_assign_from": (i32, [vp, vp, u32p, u64p]),
     "fvdb_ivf_refill_from": (i32, [vp, vp, u64, u32p]),
     "fvdb_ivf_maintenance_info": (i32, [vp, C.POINTER(MaintenanceInfo)]),
+    # rows by location: the device gather
+    "fvdb_ivf_get_rows": (i32, [vp, u32p, u32p, u64, f32p]),
+    "fvdb_ivf_get_rows_dev": (i32, [vp, vp, u32p, u32p, u64, vp]),
+    "fvdb_ivf_assign_from_store": (i32, [vp, vp, u32p, u64, u32p]),
+    "fvdb_ivf_add_assigned_from_store": (i32, [vp, vp, u32p, u64p, u64, u32p, u32p]),
     "fvdb_ivf_search": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
     "fvdb_ivf_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_all": (i32, [vp, f32p, u32, u32, u64p, f32p, u32p]),

@@ -28,6 +28,7 @@
 #include "kernels_mfma_wg.h"
 #include "kernels_util.h"
 #include "kernels_maint.h"
+#include "kernels_rows.h"
 
 using namespace fvdb;
 
@@ -185,10 +186,16 @@ struct IvfScratch {
   Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
   Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
   Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
+  // fvdb_ivf_get_rows (ivf_rows.h): slots and gathered rows of one fetch.  Not s_slots / s_in: in set 0 those are the
+  // insert staging.  fetch_done: the last fetch that read s_fslots on a stream other than the set's own
+  Buf s_fslots{this}, s_frows{this};
+  hipEvent_t fetch_done = nullptr;
   hipEvent_t sev[EV_COUNT] = {};
   uint32_t* scalar(ScalWord w) const { return s_scalars.as<uint32_t>() + w; }
   void release_all() {
     for (DBuf* b : bufs) b->release();
+    if (fetch_done) (void)hipEventDestroy(fetch_done);
+    fetch_done = nullptr;
     for (auto& e : sev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
@@ -262,6 +269,7 @@ struct fvdb_ivf : IvfScratch {
   fvdb_ivf* m_src = nullptr;
   uint64_t m_rows = 0;
   bool m_assigned = false;  // m_dest holds fvdb_ivf_assign_from's ranking of m_src's m_rows rows
+  bool m_store_job = false; // m_info holds fvdb_ivf_assign_from_store's figures: the add that follows continues them
   fvdb_maintenance_info_t m_info{};
 
   // per-search scratch
@@ -2882,5 +2890,6 @@ int fvdb_scorer_run(fvdb_scorer* sc, uint32_t B, uint32_t C) {
 }  // extern "C"
 
 #include "ivf_maint.h"
+#include "ivf_rows.h"
 #include "comm_sharded.h"
 #include "allow_masks.h"

@@ -303,6 +303,33 @@ class DeviceIVF:
                                                       _ptr(cl, u32p), _ptr(pos, u32p)))
         return pos
 
+    # --- rows by location: the device gather (include/fvdb.h "Rows by location") ---
+    def get_rows(self, clusters, pos, out=None):
+        """Rows at (list, position), f32 (fp16 rows widened exactly), read back with one device gather."""
+        cl = np.ascontiguousarray(clusters, np.uint32).reshape(-1)
+        ps = np.ascontiguousarray(pos, np.uint32).reshape(-1)
+        if out is None:
+            out = np.empty((cl.size, self.d), np.float32)
+        self.ctx.check(self.lib.fvdb_ivf_get_rows(self.h, _ptr(cl, u32p), _ptr(ps, u32p), cl.size, _ptr(out, f32p)))
+        return out
+
+    def assign_from_store(self, store, rows):
+        """assign() of the store's rows `rows`, gathered in HBM."""
+        r = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        out = np.empty(r.size, np.uint32)
+        self.ctx.check(self.lib.fvdb_ivf_assign_from_store(self.h, store.h, _ptr(r, u32p), r.size, _ptr(out, u32p)))
+        return out
+
+    def add_assigned_from_store(self, store, rows, ids, clusters):
+        """add_assigned() of the store's rows `rows`, gathered in HBM; returns each row's position in its list."""
+        r = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        ids = np.ascontiguousarray(ids, np.uint64)
+        cl = np.ascontiguousarray(clusters, np.uint32)
+        pos = np.empty(r.size, np.uint32)
+        self.ctx.check(self.lib.fvdb_ivf_add_assigned_from_store(self.h, store.h, _ptr(r, u32p), _ptr(ids, u64p), r.size,
+                                                                 _ptr(cl, u32p), _ptr(pos, u32p)))
+        return pos
+
     def set_deleted(self, clusters, pos, deleted=True):
         cl = np.ascontiguousarray(clusters, np.uint32)
         ps = np.ascontiguousarray(pos, np.uint32)

@@ -85,6 +85,10 @@ int fvh_ivf_cluster_stats(void* p, IVFIndex::ClusterStats* out) {
   *out = ((IVFIndex*)p)->get_cluster_stats();
   return FVDB_OK;
 }
+// rows by id, read back from HBM (src/ivf/core.rs:553-562); found[i] = 0 leaves row i of out untouched
+int fvh_ivf_get_vectors(void* p, const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
+  return ((IVFIndex*)p)->get_vectors(ids, n, out, found);
+}
 uint32_t fvh_ivf_n_clusters(void* p) { return ((IVFIndex*)p)->config().n_clusters; }
 uint32_t fvh_ivf_n_probe(void* p) { return ((IVFIndex*)p)->config().n_probe; }
 
@@ -344,6 +348,13 @@ void fvh_hnsw_set_vacuum_keep_rows(void* p, int on) { ((HNSWIndex*)p)->set_vacuu
 // returns HNSWIndex::VacuumPath of the last vacuum that removed something
 int fvh_hnsw_vacuum_info(void* p, fvdb_graph_maintenance_info_t* out) { return ((HNSWIndex*)p)->vacuum_info(out); }
 uint64_t fvh_hnsw_store_rows(void* p) { return ((HNSWIndex*)p)->store_rows(); }
+// vectors of search hits (includeVectors, bindings/node/src/session.rs:266-281): recent part first, then historical
+int fvh_hybrid_get_vectors(void* p, const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
+  return ((HybridIndex*)p)->get_vectors(ids, n, out, found);
+}
+void fvh_hybrid_set_resident_migration(void* p, int on) { ((HybridIndex*)p)->set_resident_migration(on != 0); }
+// returns HybridIndex::MigrationPath of the last migration that had rows to copy
+int fvh_hybrid_migration_info(void* p, fvdb_maintenance_info_t* out) { return ((HybridIndex*)p)->migration_info(out); }
 uint64_t fvh_hybrid_timestamp_count(void* p) { return ((HybridIndex*)p)->timestamp_count(); }
 void fvh_hybrid_export_timestamps(void* p, uint64_t* ids, double* ts) { ((HybridIndex*)p)->export_timestamps(ids, ts); }
 uint64_t fvh_hybrid_recent_count(void* p) { return ((HybridIndex*)p)->recent_count(); }

@@ -139,7 +139,19 @@ class IVFIndex {
   // rows whose list is already known (load path / shard placement)
   int batch_insert_assigned(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const uint32_t* clusters,
                             uint64_t* n_ok, int* first_error);
+  // batch_insert with the rows taken from a row store in HBM (rows[i] = store row of ids[i]) instead of the host: the
+  // same per-row outcome (the duplicate checks of place(), live_again_), the same lists.  Only the kept rows' indices,
+  // ids and clusters cross the host link (fvdb_ivf_assign_from_store / fvdb_ivf_add_assigned_from_store).
+  int batch_insert_from_store(const uint64_t* ids, fvdb_store* store, const uint32_t* rows, uint64_t n, uint64_t* n_ok,
+                              int* first_error);
   int assign(const float* v, uint64_t n, uint32_t dim, uint32_t* out);
+  // Rows by id (get_vector_by_id, src/ivf/core.rs:553-562), read back from HBM with one device gather for the whole
+  // batch (fvdb_ivf_get_rows).  An id may sit in several lists (the duplicate check is per list): the LOWEST (cluster,
+  // position) is taken.  The reference walks a HashMap of lists and returns the first copy it meets, so any of them
+  // is one of its outcomes.  A soft-deleted id still returns its row (:553-562 do not look at the deleted set).
+  int get_vector_by_id(uint64_t id, float* out);  // FVDB_E_NOT_FOUND when no list holds the id
+  // found[i] = 1 and out row i (dimension() floats) filled, or found[i] = 0 and the row untouched
+  int get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found);
   int find_cluster(const float* v, uint32_t dim, uint32_t* out);                  // :493
   int search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, uint64_t* ids, float* dist,
              uint32_t* counts);                                                   // :626, operations.rs:132
@@ -190,6 +202,8 @@ class IVFIndex {
   // the present one and re-insert them; `reinserted` counts the rows that went in (all, or those before a duplicate)
   int rebuild(uint32_t n_clusters, uint32_t max_iterations, uint64_t seed, fvdb_train_result* tr, uint64_t* reinserted);
   int place(const uint64_t* ids, const float* v, uint64_t n, const uint32_t* clusters, uint64_t* n_ok, int* first_error);
+  // the per-list duplicate check of place(): the indices of the rows that go in, in order (live_again_ noted)
+  std::vector<uint64_t> accept(const uint64_t* ids, uint64_t n, const uint32_t* clusters, int* first_error);
   fvdb_ctx* ctx_;
   IVFConfig cfg_;
   fvdb_ivf* dev_ = nullptr;
@@ -319,6 +333,12 @@ class HNSWIndex {
   int64_t level_of(uint64_t id) const;
   int64_t neighbors(uint64_t id, uint32_t layer, uint64_t* out, uint64_t cap);
   const float* vector_of(uint64_t id) const;  // host copy (migration, get_vector_by_id)
+  // batch form of vector_of: found[i] = 1 and out row i filled, or found[i] = 0 and the row untouched
+  void get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found) const;
+  // The row store behind the graph, and the row of a node in it: the node index (resident migration).  false when the
+  // id is not a node or the store does not hold its row.
+  fvdb_store* store() const { return store_; }
+  bool store_row_of(uint64_t id, uint32_t* row) const;
   bool contains(uint64_t id) const { return index_of_.count(id) > 0; }
   // Extension (not in the reference): build the graph for n vectors at once.  Levels from the PRNG
   // (or given); per layer every member links to its exact nearest M (M0 on layer 0) members, found
@@ -568,6 +588,23 @@ class HybridIndex {
     return !pending_migration_.empty() && age_of(now, pending_min_ts_) >= threshold_s;
   }
   uint64_t migrate_with_threshold(double threshold_s, double now);                                // :600
+  // Where a migration's rows come from (the non-sharded branch): true (default) = the graph's row store in HBM, the due
+  // ids go down as store row indices (IVFIndex::batch_insert_from_store); false = the host copy, uploaded by
+  // IVFIndex::batch_insert.  Same lists either way.  A due id whose row the store does not hold sends the whole job down
+  // the host path.
+  void set_resident_migration(bool on) { resident_migration_ = on; }
+  bool resident_migration() const { return resident_migration_; }
+  // the last migration that had rows to copy: which path it took and its figures (resident: fvdb_ivf_maintenance_info;
+  // host: rows and the bytes batch_insert copies, no stage times)
+  enum MigrationPath : int { MIGRATION_NONE = 0, MIGRATION_RESIDENT = 1, MIGRATION_HOST = 2 };
+  int migration_info(fvdb_maintenance_info_t* out) const {
+    *out = migration_info_;
+    return migration_path_;
+  }
+  // Vectors by id (includeVectors, bindings/node/src/session.rs:266-281): the recent part is asked first, then the
+  // historical part; found[i] = 0 and the row untouched when neither holds the id.  Runs under the read side of the
+  // lock, beside searches.
+  int get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found);
   int remove(uint64_t id, double now);                                                             // delete :904
   uint64_t recent_count() const { return recent_count_; }
   uint64_t historical_count() const { return historical_count_; }
@@ -626,6 +663,9 @@ class HybridIndex {
   int bulk_route(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts, double now,
                  std::vector<uint64_t>& hid, std::vector<float>& hv);
   bool sequential_graph_ = true;
+  bool resident_migration_ = true;
+  int migration_path_ = MIGRATION_NONE;
+  fvdb_maintenance_info_t migration_info_{};
   std::atomic<bool> writers_wait_{false};
   // exclusive access for a mutation: with no batch in flight, or FVDB_E_INVALID / after waiting (set_blocking_writers)
   int write_lock(std::unique_lock<std::shared_mutex>& w);

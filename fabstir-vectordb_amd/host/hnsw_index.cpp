@@ -188,6 +188,21 @@ const float* HNSWIndex::vector_of(uint64_t id) const {
   return it == index_of_.end() ? nullptr : &host_vecs_[(size_t)it->second * dim_];
 }
 
+void HNSWIndex::get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found) const {
+  for (uint64_t i = 0; i < n; ++i) {
+    const float* v = vector_of(ids[i]);
+    found[i] = v != nullptr;
+    if (v) std::memcpy(out + i * dim_, v, (size_t)dim_ * sizeof(float));
+  }
+}
+
+bool HNSWIndex::store_row_of(uint64_t id, uint32_t* row) const {
+  auto it = index_of_.find(id);
+  if (it == index_of_.end() || !store_ || it->second >= fvdb_store_rows(store_)) return false;
+  *row = it->second;
+  return true;
+}
+
 int64_t HNSWIndex::level_of(uint64_t id) const {
   auto it = index_of_.find(id);
   return it == index_of_.end() ? -1 : (int64_t)level_[it->second];

@@ -342,6 +342,40 @@ uint64_t HybridIndex::migrate_locked(double threshold_s, double now) {
   if (due.empty()) return 0;
   uint64_t migrated = 0;
   const uint32_t dim = recent_->dimension();
+  const bool sharded = shard_world_ > 0 && !shard_owner_.empty();
+  // Resident form (non-sharded): the rows already sit in HBM in the graph's row store, so the due ids go down as store
+  // row indices and nothing of the vectors crosses the host link.  A due id whose row the store does not hold (there is
+  // none today) sends the whole job down the host path: one job, one path.
+  if (resident_migration_ && !sharded && recent_->store()) {
+    std::vector<uint64_t> ri;
+    std::vector<uint32_t> rr;
+    bool all = true;
+    for (uint64_t id : due) {
+      if (!recent_->vector_of(id)) continue;  // get_node(id) == None
+      uint32_t row = 0;
+      if (!recent_->store_row_of(id, &row)) {
+        all = false;
+        break;
+      }
+      ri.push_back(id);
+      rr.push_back(row);
+    }
+    if (all) {
+      if (!ri.empty()) {
+        int err = 0;
+        if (historical_->batch_insert_from_store(ri.data(), recent_->store(), rr.data(), ri.size(), &migrated, &err)) return 0;
+        migration_path_ = MIGRATION_RESIDENT;
+        fvdb_ivf_maintenance_info(historical_->device(), &migration_info_);
+      }
+      pending_migration_.swap(keep);
+      pending_min_ts_ = min_ts;
+      if (migrated) {
+        recent_count_ = recent_count_ >= migrated ? recent_count_ - migrated : 0;
+        historical_count_ += migrated;
+      }
+      return migrated;
+    }
+  }
   std::vector<float> xv;
   std::vector<uint64_t> xi;
   for (uint64_t id : due) {
@@ -370,6 +404,12 @@ uint64_t HybridIndex::migrate_locked(double threshold_s, double now) {
     int err = 0;
     int rc = historical_->batch_insert(xi.data(), xv.data(), xi.size(), dim, &migrated, &err);
     if (rc) return 0;  // IVF untrained / dimension mismatch: every insert fails; ids stay pending
+    // what batch_insert copied: the rows up twice (assign, append), clusters down, ids and slots of the kept rows up
+    migration_path_ = MIGRATION_HOST;
+    migration_info_ = fvdb_maintenance_info_t{};
+    migration_info_.rows_in = xi.size();
+    migration_info_.rows_out = migrated;
+    migration_info_.host_bytes = (uint64_t)xi.size() * (dim * 4ull + 4) + migrated * (dim * 4ull + 12);
   }
   // A copy that failed as a duplicate fails the same way on every later search (the reference
   // retries it each time with no effect), so due ids leave the queue either way.
@@ -380,6 +420,31 @@ uint64_t HybridIndex::migrate_locked(double threshold_s, double now) {
     historical_count_ += migrated;
   }
   return migrated;
+}
+
+// bindings/node/src/session.rs:272-279: the recent index answers first, the historical one for the rest
+int HybridIndex::get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
+  if (n == 0) return FVDB_OK;
+  if (!ids || !out || !found) return FVDB_E_INVALID;
+  std::shared_lock<std::shared_mutex> r(rw_);
+  recent_->get_vectors(ids, n, out, found);
+  std::vector<uint64_t> rest, at;
+  for (uint64_t i = 0; i < n; ++i)
+    if (!found[i]) {
+      rest.push_back(ids[i]);
+      at.push_back(i);
+    }
+  if (rest.empty()) return FVDB_OK;
+  const uint32_t dim = historical_->dimension();
+  std::vector<float> rows(rest.size() * (size_t)dim);
+  std::vector<uint8_t> f(rest.size(), 0);
+  if (int rc = historical_->get_vectors(rest.data(), rest.size(), rows.data(), f.data())) return rc;
+  for (size_t j = 0; j < rest.size(); ++j)
+    if (f[j]) {
+      found[at[j]] = 1;
+      std::memcpy(out + at[j] * dim, &rows[j * dim], (size_t)dim * sizeof(float));
+    }
+  return FVDB_OK;
 }
 
 // src/hybrid/core.rs:425-486 for a batch of queries

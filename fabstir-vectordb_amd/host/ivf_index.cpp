@@ -252,9 +252,8 @@ int IVFIndex::find_cluster(const float* v, uint32_t dim, uint32_t* out) {
   return fvdb_ivf_assign(dev_, v, 1, out);
 }
 
-// rows whose cluster is known: per-list duplicate check (InvertedList::insert :128-134), then append
-int IVFIndex::place(const uint64_t* ids, const float* v, uint64_t n, const uint32_t* clusters, uint64_t* n_ok,
-                    int* first_error) {
+// the per-list duplicate check (InvertedList::insert :128-134) over a batch, in order
+std::vector<uint64_t> IVFIndex::accept(const uint64_t* ids, uint64_t n, const uint32_t* clusters, int* first_error) {
   std::vector<uint64_t> keep;
   keep.reserve(n);
   std::unordered_multimap<uint64_t, uint32_t> batch_seen;  // (id -> cluster) accepted earlier in this batch
@@ -272,6 +271,13 @@ int IVFIndex::place(const uint64_t* ids, const float* v, uint64_t n, const uint3
     keep.push_back(i);
     if (!deleted_.empty() && deleted_.count(ids[i])) live_again_ = true;
   }
+  return keep;
+}
+
+// rows whose cluster is known: per-list duplicate check, then append
+int IVFIndex::place(const uint64_t* ids, const float* v, uint64_t n, const uint32_t* clusters, uint64_t* n_ok,
+                    int* first_error) {
+  const std::vector<uint64_t> keep = accept(ids, n, clusters, first_error);
   if (n_ok) *n_ok = keep.size();
   if (keep.empty()) return FVDB_OK;
   std::vector<uint32_t> pos(keep.size());
@@ -293,6 +299,77 @@ int IVFIndex::place(const uint64_t* ids, const float* v, uint64_t n, const uint3
   for (size_t j = 0; j < keep.size(); ++j) where_.emplace(ids[keep[j]], Loc{clusters[keep[j]], pos[j]});
   total_ += keep.size();
   return FVDB_OK;
+}
+
+// batch_insert (operations.rs:107-130) with the rows read from a row store in HBM: the assignment pass and the append
+// gather them there (fvdb_ivf_assign_from_store, fvdb_ivf_add_assigned_from_store); place()'s checks run in between
+int IVFIndex::batch_insert_from_store(const uint64_t* ids, fvdb_store* store, const uint32_t* rows, uint64_t n,
+                                      uint64_t* n_ok, int* first_error) {
+  if (n_ok) *n_ok = 0;
+  if (first_error) *first_error = 0;
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (!store) return FVDB_E_INVALID;
+  if (n == 0) return FVDB_OK;
+  std::vector<uint32_t> clusters(n);
+  int rc = fvdb_ivf_assign_from_store(dev_, store, rows, n, clusters.data());
+  if (rc) return rc;
+  const std::vector<uint64_t> keep = accept(ids, n, clusters.data(), first_error);
+  if (n_ok) *n_ok = keep.size();
+  if (keep.empty()) return FVDB_OK;
+  std::vector<uint32_t> pos(keep.size());
+  if (keep.size() == n) {
+    rc = fvdb_ivf_add_assigned_from_store(dev_, store, rows, ids, n, clusters.data(), pos.data());
+  } else {  // only the kept rows' indices go down
+    std::vector<uint32_t> xr(keep.size()), xc(keep.size());
+    std::vector<uint64_t> xi(keep.size());
+    for (size_t j = 0; j < keep.size(); ++j) {
+      xr[j] = rows[keep[j]];
+      xi[j] = ids[keep[j]];
+      xc[j] = clusters[keep[j]];
+    }
+    rc = fvdb_ivf_add_assigned_from_store(dev_, store, xr.data(), xi.data(), keep.size(), xc.data(), pos.data());
+  }
+  if (rc) return rc;
+  for (size_t j = 0; j < keep.size(); ++j) where_.emplace(ids[keep[j]], Loc{clusters[keep[j]], pos[j]});
+  total_ += keep.size();
+  return FVDB_OK;
+}
+
+// src/ivf/core.rs:553-562.  Of the lists that hold the id, the lowest (cluster, position) answers (fvdb_host.hpp).
+int IVFIndex::get_vectors(const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
+  if (n == 0) return FVDB_OK;
+  if (!ids || !out || !found) return FVDB_E_INVALID;
+  std::vector<uint32_t> cl, ps;
+  std::vector<uint64_t> at;  // which of the n each location answers
+  for (uint64_t i = 0; i < n; ++i) {
+    found[i] = 0;
+    auto r = where_.equal_range(ids[i]);
+    if (r.first == r.second) continue;
+    Loc best = r.first->second;
+    for (auto it = r.first; it != r.second; ++it)
+      if (it->second.cluster < best.cluster || (it->second.cluster == best.cluster && it->second.pos < best.pos)) best = it->second;
+    found[i] = 1;
+    cl.push_back(best.cluster);
+    ps.push_back(best.pos);
+    at.push_back(i);
+  }
+  if (at.empty()) return FVDB_OK;
+  if (!dev_) return FVDB_E_NOT_TRAINED;
+  if (at.size() == n) return fvdb_ivf_get_rows(dev_, cl.data(), ps.data(), n, out);
+  std::vector<float> rows(at.size() * (size_t)dim_);
+  const int rc = fvdb_ivf_get_rows(dev_, cl.data(), ps.data(), at.size(), rows.data());
+  if (rc) {
+    for (uint64_t i : at) found[i] = 0;
+    return rc;
+  }
+  for (size_t j = 0; j < at.size(); ++j) std::memcpy(out + at[j] * dim_, &rows[j * dim_], dim_ * sizeof(float));
+  return FVDB_OK;
+}
+
+int IVFIndex::get_vector_by_id(uint64_t id, float* out) {
+  uint8_t found = 0;
+  const int rc = get_vectors(&id, 1, out, &found);
+  return rc ? rc : (found ? FVDB_OK : FVDB_E_NOT_FOUND);
 }
 
 // src/ivf/core.rs:431-455

@@ -138,6 +138,11 @@ HOST_SIGNATURES = {
     "fvh_hybrid_set_blocking_writers": (None, [vp, i32]),
     "fvh_hybrid_blocking_writers": (i32, [vp]),
     "fvh_hybrid_ivf": (vp, [vp]),
+    # rows by id and resident migration
+    "fvh_ivf_get_vectors": (i32, [vp, u64p, u64, f32p, C.POINTER(C.c_uint8)]),
+    "fvh_hybrid_get_vectors": (i32, [vp, u64p, u64, f32p, C.POINTER(C.c_uint8)]),
+    "fvh_hybrid_set_resident_migration": (None, [vp, i32]),
+    "fvh_hybrid_migration_info": (i32, [vp, vp]),
 }
 
 
@@ -189,6 +194,16 @@ def _allowed_ids(allowed):
     ctypes has an address to pass."""
     a = np.ascontiguousarray(np.fromiter(allowed, np.uint64) if not isinstance(allowed, np.ndarray) else allowed, np.uint64)
     return a.reshape(-1) if a.size else np.zeros(1, np.uint64)[:0]
+
+
+def _get_vectors(self, fn, ids, dim):
+    """(rows [n x dim] f32, found [n] bool) for `ids`; a row that was not found is zero."""
+    ids = np.ascontiguousarray(np.atleast_1d(ids), np.uint64).reshape(-1)
+    out = np.zeros((ids.size, max(int(dim or 0), 1)), np.float32)
+    found = np.zeros(max(ids.size, 1), np.uint8)
+    if ids.size:
+        self._check(fn(self.h, _ptr(ids, u64p), ids.size, _ptr(out, f32p), found.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out, found[:ids.size].astype(bool)
 
 
 class _Base:
@@ -342,6 +357,16 @@ class IVFIndex(_Base):
         self._check(self.lib.fvh_ivf_export_list(self.h, int(c), _ptr(rows, f32p), _ptr(ids, u64p),
                                                  live.ctypes.data_as(C.POINTER(C.c_uint8))))
         return rows, ids, live.astype(bool)
+
+    def get_vectors(self, ids):
+        """Rows of `ids` read back from HBM with one device gather: (rows [n x d] f32, found [n] bool).  A soft-deleted
+        id still has its row; of several lists holding one id the lowest (cluster, position) answers."""
+        return _get_vectors(self, self.lib.fvh_ivf_get_vectors, ids, self.dimension())
+
+    def get_vector_by_id(self, id):
+        """IVFIndex::get_vector_by_id (src/ivf/core.rs:553-562): the row as f32, or None."""
+        rows, found = self.get_vectors([int(id)])
+        return rows[0] if found[0] else None
 
     def search(self, queries, k, n_probe=None):
         return self._search(self.lib.fvh_ivf_search, queries, k, self.n_probe if n_probe is None else n_probe)
@@ -898,6 +923,28 @@ class HybridIndex(_Base):
 
     def migrate_with_threshold(self, threshold, now):
         return int(self.lib.fvh_hybrid_migrate(self.h, float(threshold), float(now)))
+
+    def set_resident_migration(self, on):
+        """Where a migration's rows come from: True (default) = the graph's row store in HBM (the due ids go down as
+        store row indices), False = the host copy, uploaded.  Same lists either way."""
+        self.lib.fvh_hybrid_set_resident_migration(self.h, int(bool(on)))
+
+    def migration_info(self):
+        """The last migration that had rows to copy: path ("resident" / "host" / None) and its figures
+        (fvdb_maintenance_info_t; the host path reports rows and host_bytes only)."""
+        m = _capi.MaintenanceInfo()
+        path = self.lib.fvh_hybrid_migration_info(self.h, C.byref(m))
+        out = {name: getattr(m, name) for name, _ in m._fields_}
+        out["path"] = {1: "resident", 2: "host"}.get(path)
+        out["resident"] = path == 1
+        return out
+
+    def get_vectors(self, ids):
+        """Vectors of `ids` (includeVectors, bindings/node/src/session.rs:266-281): the recent part answers first, the
+        historical part (one device gather) for the rest.  Returns (rows [n x d] f32, found [n] bool)."""
+        dim = int(self.lib.fvh_hnsw_dimension(self.lib.fvh_hybrid_hnsw(self.h))) or \
+            int(self.lib.fvh_ivf_dimension(self.lib.fvh_hybrid_ivf(self.h)))
+        return _get_vectors(self, self.lib.fvh_hybrid_get_vectors, ids, dim)
 
     def recent_count(self):
         return int(self.lib.fvh_hybrid_recent_count(self.h))

@@ -221,13 +221,25 @@ class VectorDbSession:
                 res = self.index.search_with_filter(q.reshape(1, -1), int(k), matches, now=self.now)  # defaults: ef 50, nprobe 10
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
+        include_vectors = bool(options.get("includeVectors", False))  # session.rs:229-231
         out = []
         ids, ds = res[0]
         pairs = list(zip(ids.tolist(), ds.tolist()))
+        kept = []
         for rid, d in pairs:
             score = np.float32(1.0) / (np.float32(1.0) + np.float32(d))
             if not score >= threshold:
                 continue
+            kept.append((rid, score))
+        vectors = {}
+        if include_vectors and kept:  # session.rs:266-281: the recent index first, then the historical one; one call
+            try:
+                rows, found = self.index.get_vectors(np.array([rid for rid, _ in kept], np.uint64))
+            except Exception as e:
+                raise SessionError(f"Search failed: {e}") from e
+            # the f32 values widened to doubles (utils.rs:12-14); an id neither part holds has no vector
+            vectors = {rid: [float(v) for v in rows[i]] for i, (rid, _) in enumerate(kept) if found[i]}
+        for rid, score in kept:
             key = self._rows.get(rid, f"row_{rid}")
             md = dict(self.metadata.get(key, {}))
             rid_out = key
@@ -235,7 +247,10 @@ class VectorDbSession:
                 rid_out = md.pop("_originalId")
                 if "_userMetadata" in md:
                     md = md.pop("_userMetadata")
-            out.append({"id": rid_out, "score": float(score), "metadata": md})
+            item = {"id": rid_out, "score": float(score), "metadata": md}
+            if include_vectors:
+                item["vector"] = vectors.get(rid)
+            out.append(item)
         return out
 
     def delete_vector(self, id):

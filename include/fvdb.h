@@ -202,6 +202,31 @@ int fvdb_ivf_assign_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t* out_cluster, ui
 int fvdb_ivf_refill_from(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n_rows, uint32_t* out_pos);
 /* Figures of the last maintenance job on this index (compact; train_from + assign_from + refill_from as dst). */
 int fvdb_ivf_maintenance_info(fvdb_ivf* ivf, fvdb_maintenance_info_t* out);
+
+/* ---- Rows by location ------------------------------------------------------------------------------------------------
+ * One device gather serves three things: reading a row back (IVFIndex::get_vector_by_id, src/ivf/core.rs:553-562),
+ * returning the hits' vectors (includeVectors, bindings/node/src/session.rs:266-281) and the migration of rows from
+ * the graph's row store into the lists without a trip through the host (src/hybrid/core.rs:600-649). */
+/* Rows of the inverted lists by location (list, position), as fvdb_ivf_set_deleted names them.  out: n x d f32
+ * (fp16 rows widened exactly).  A soft-deleted row is returned like any other (src/ivf/core.rs:553-562 does not look
+ * at the deleted set).  FVDB_E_NOT_FOUND if a location is not a row; nothing is written then.  Reads only: does not
+ * bump the mutation counter, leaves masks fresh.  Any number of host threads may call it, beside searches in any
+ * slot (each call leases a scratch set and its stream, like fvdb_ivf_search); not beside a mutation. */
+int fvdb_ivf_get_rows(fvdb_ivf* ivf, const uint32_t* cluster, const uint32_t* pos, uint64_t n, float* out_rows /*host*/);
+/* Same, enqueued on `on`'s stream (NULL = the index's) into device memory; no synchronisation. */
+int fvdb_ivf_get_rows_dev(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const uint32_t* pos, uint64_t n,
+                          float* out_rows_dev);
+/* fvdb_ivf_assign / fvdb_ivf_add_assigned with the rows taken from a row store in HBM instead of the host (the
+ * staging vector of HybridIndex::migrate, src/hybrid/core.rs:619-640, never exists): the result is, bit for bit and
+ * in every representation the pool keeps (blocked rows, fp16 mirror, row-major copy, norms, largest norm), that of
+ * the host form given fvdb_store_get() of those rows.  Store and index share d (FVDB_E_DIM) and the device
+ * (FVDB_E_INVALID); a row index >= fvdb_store_rows() is FVDB_E_NOT_FOUND before anything is changed.  The rows are
+ * not checked for NaN / Inf again: fvdb_store_append did.  fvdb_ivf_maintenance_info afterwards reports the pair as
+ * one job: rows_in = rows_out = n, host_bytes (row indices, clusters, ids, slots: at most 32 n), ms_gather,
+ * ms_assign, ms_move. */
+int fvdb_ivf_assign_from_store(fvdb_ivf* ivf, fvdb_store* store, const uint32_t* rows, uint64_t n, uint32_t* out_cluster);
+int fvdb_ivf_add_assigned_from_store(fvdb_ivf* ivf, fvdb_store* store, const uint32_t* rows, const uint64_t* ids,
+                                     uint64_t n, const uint32_t* cluster, uint32_t* out_pos);
 int fvdb_ivf_clear(fvdb_ivf* ivf);   /* empties the lists, keeps centroids (hybrid initialize :278-287) */
 /* Multi-GPU: sizes of ALL lists of the logical index (this rank may own a subset), so the
  * tie-break position `seq` is identical on every rank.  Default = local sizes. */
