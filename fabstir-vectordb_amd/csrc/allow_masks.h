@@ -80,7 +80,7 @@ int build_graph_mask(fvdb_mask* m, const GraphMaskSource& src, const uint32_t* n
                        m->flags.as<uint32_t>());
   hipLaunchKernelGGL(allow_graph_count_kernel, dim3(n_wg), dim3(256), 0, ctx->stream, m->flags.as<uint32_t>(), src.deleted, n,
                      (uint32_t*)d_wg.p);
-  hipLaunchKernelGGL(allow_graph_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (uint32_t*)d_wg.p, n_wg,
+  hipLaunchKernelGGL(block_excl_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, ctx->stream, (uint32_t*)d_wg.p, n_wg,
                      (unsigned long long*)d_total.p);
   hipLaunchKernelGGL(allow_graph_write_kernel, dim3(n_wg), dim3(256), 0, ctx->stream, m->flags.as<uint32_t>(), n,
                      (const uint32_t*)d_wg.p, m->nodes.as<uint32_t>());

@@ -239,7 +239,7 @@ BuildView build_view(fvdb_graph* g, uint32_t ef = 0, const InsertPlan& plan = In
 int edge_dist(fvdb_graph* g, const uint32_t* codes_dev, const uint32_t* owner_dev, uint32_t n_rows, bool upper_all) {
   fvdb_ctx* ctx = g->store->ctx;
   if (n_rows == 0) return FVDB_OK;
-  const size_t lds = 4 * (size_t)kTileRows * kFastStride * 4;
+  const size_t lds = 4 * (size_t)kTileRows * kScoreStride * 4;
   hipLaunchKernelGGL(build_kernels(g->store->dpad, false).edge_dist, dim3((n_rows + 3) / 4), dim3(256), lds, ctx->stream, build_view(g), codes_dev,
                      owner_dev, n_rows, upper_all ? 1u : 0u);
   HIPCHK(ctx, hipGetLastError());
@@ -1206,8 +1206,8 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
     // stage 1a: survivors and their upper rows, counted on the device and checked against the host's copy of the flags
     GM_TRY(hipEventRecord(ev.ev[0], st));
     hipLaunchKernelGGL(gm_count_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), n, wg_nodes, wg_urows);
-    hipLaunchKernelGGL(gm_scan_kernel, dim3(1), dim3(1024), 0, st, wg_nodes, n_wg, totals);
-    hipLaunchKernelGGL(gm_scan_kernel, dim3(1), dim3(1024), 0, st, wg_urows, n_wg, totals + 1);
+    hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_nodes, n_wg, totals);
+    hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_urows, n_wg, totals + 1);
     GM_TRY(hipGetLastError());
     GM_TRY(hipEventRecord(ev.ev[1], st));
     uint32_t h_tot[2] = {0, 0};

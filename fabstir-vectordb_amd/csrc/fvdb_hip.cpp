@@ -1230,7 +1230,7 @@ int ivf_shared_thresholds(fvdb_ivf* ivf, const Env& E, const float* q_dev, const
   HIPCHK(ctx, S.s_qn2.ensure((size_t)B * 4));
   if (!ivf->pool.norms || !ivf->d_xmax.p) {  // no rows on this rank yet: it owns nothing
     HIPCHK(ctx, hipMemsetAsync(S.s_qn2.p, 0, (size_t)B * 4, ctx->stream));
-    hipLaunchKernelGGL(fill_f32_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, u_out, B, __builtin_huge_valf());
+    hipLaunchKernelGGL(fill_f32_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, u_out, (uint64_t)B, __builtin_huge_valf());
     HIPCHK(ctx, hipGetLastError());
     return FVDB_OK;
   }

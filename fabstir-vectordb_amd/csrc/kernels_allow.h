@@ -17,6 +17,7 @@
 #include "common.h"
 #include "kernels_scan.h"
 #include "score_rows.h"
+#include "wave_ops.h"
 
 namespace fvdb {
 
@@ -102,34 +103,6 @@ __global__ __launch_bounds__(256) void allow_graph_count_kernel(uint32_t* __rest
   if (threadIdx.x == 0) wg_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// exclusive prefix sum of wg_count[0 .. n_wg) in place, the total into *total; one workgroup of 1024
-__global__ __launch_bounds__(1024) void allow_graph_scan_kernel(uint32_t* __restrict__ wg_count, uint32_t n_wg, unsigned long long* __restrict__ total) {
-  __shared__ uint32_t s_wave[16];
-  __shared__ uint32_t s_base;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < n_wg; c0 += 1024) {
-    const uint32_t i = c0 + threadIdx.x;
-    const uint32_t v = i < n_wg ? wg_count[i] : 0u;
-    uint32_t incl = v;  // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o);
-      if ((int)lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = s_base;
-    for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-    if (i < n_wg) wg_count[i] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_base = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_base;
-}
-
 // node i of workgroup b goes to out[wg_offset[b] + its rank among the workgroup's allowed live nodes]: ascending
 __global__ __launch_bounds__(256) void allow_graph_write_kernel(const uint32_t* __restrict__ flags, uint32_t n, const uint32_t* __restrict__ wg_offset,
                                                                 uint32_t* __restrict__ out_nodes) {
@@ -142,7 +115,7 @@ __global__ __launch_bounds__(256) void allow_graph_write_kernel(const uint32_t* 
   __syncthreads();
   uint32_t base = wg_offset[blockIdx.x];
   for (uint32_t w = 0; w < wave; ++w) base += s_cnt[w];
-  if (ok) out_nodes[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+  if (ok) out_nodes[base + ballot_rank(m, lane)] = i;
 }
 
 // ---- exact scan of the allowed live nodes -----------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 // first, and only queries in which two heap members met with equal distances (or ef > 64, or d > 1024) come here.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -103,10 +104,6 @@ __device__ __forceinline__ HItem h_pop(HItem* h, uint32_t& n) {
 // routine it replaces (the path of a sift is a sorted chain, so "shift every smaller ancestor down one level" can
 // be decided for all ancestors at once), hence the same heap layout and the same tie behaviour.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float rlane_f(float v, uint32_t l) {
-  return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), l));
-}
-
 // place (en, ed) at the hole `pos` and sift it up (h_sift_up with start 0)
 __device__ __forceinline__ void rh_sift_up(uint32_t& hn, float& hd, uint32_t pos, uint32_t en, float ed, int lane) {
   const uint32_t x = pos + 1, y = (uint32_t)lane + 1;

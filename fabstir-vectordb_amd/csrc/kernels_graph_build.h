@@ -8,8 +8,8 @@
 //
 // Why the results cannot differ from the serial algorithm although the work is reorganised:
 //
-//  * Distances are pure functions of two rows (the reference's left-to-right f32 fold, computed exactly as in
-//    kernels_graph_fast.h: coalesced loads, products transposed through LDS, a per-lane sequential add chain).
+//  * Distances are pure functions of two rows (the reference's left-to-right f32 fold, computed by the scorer of
+//    score_rows.h: coalesced loads, products transposed through LDS, a per-lane sequential add chain).
 //    A search round therefore scores the unvisited neighbours of SEVERAL candidates at once — the kSpec nearest
 //    unexpanded ones — on all eight waves, and wave 0 then REPLAYS the reference's loop (pop, visit the neighbours
 //    in list order, admission rule :517-531) out of that table, with no memory latency inside the loop.  The replay
@@ -41,6 +41,8 @@
 //    stops and the rest of the batch is speculated again.
 #pragma once
 #include "kernels_graph_fast.h"
+#include "score_rows.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -132,7 +134,7 @@ __host__ __device__ inline BuildLds build_lds_layout(uint32_t bitmap_words, uint
   L.dist = take(kSlots * 64 * 4);
   L.misc = take((64 + 2 * kSpec + kSlots) * 4);  // 64 control words, fetch list (nodes, slots), list counts
   L.slist = take(kSpec * 64 * 2);
-  L.tiles = take(kBuildWaves * tile_rows * kFastStride * 4);
+  L.tiles = take(kBuildWaves * tile_rows * kScoreStride * 4);
   L.total = o;
   return L;
 }
@@ -155,51 +157,8 @@ enum { MS_NSPEC = 0, MS_NSCORE = 1, MS_DONE = 2, MS_TIE = 3, MS_OVER = 4, MS_CUR
        MS_FNODE = 64, MS_FSLOT = 64 + kSpec, MS_CNT = 64 + 2 * kSpec };
 
 // ---------------------------------------------------------------------------------------------
-// scoring: RC rows by one wave, one product tile (see score_fixed, kernels_graph_fast.h, for the derivation)
+// scoring: score_fixed (score_rows.h) with one product tile per wave
 // ---------------------------------------------------------------------------------------------
-template <int NB, int RC, bool FULL>
-__device__ __forceinline__ float score_tile1(const float* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
-                                             uint32_t cnt, float* tile, int lane) {
-  float2 x[RC][NB];
-  const uint32_t last = cnt - 1;
-#pragma unroll
-  for (int r = 0; r < RC; ++r) {
-    const uint32_t rr = (uint32_t)r < last ? (uint32_t)r : last;  // wave-uniform
-    const uint32_t node = __builtin_amdgcn_readlane(pn, rr);
-    const float* row = rows + (size_t)node * dpad;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-      const uint32_t j = (uint32_t)c * 128u + 2u * (uint32_t)lane;
-      if (FULL) x[r][c] = *(const float2*)(row + j);
-      else x[r][c] = j < dpad ? *(const float2*)(row + j) : make_float2(0.0f, 0.0f);
-    }
-  }
-  const uint32_t lrow = (uint32_t)lane < (uint32_t)RC ? (uint32_t)lane : (uint32_t)(RC - 1);
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NB; ++c) {
-#pragma unroll
-    for (int r = 0; r < RC; ++r) {
-      const float t0 = q2[c].x - x[r][c].x, t1 = q2[c].y - x[r][c].y;
-      *(float2*)(tile + (uint32_t)r * kFastStride + 2u * (uint32_t)lane) = make_float2(t0 * t0, t1 * t1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const float4* p = (const float4*)(tile + lrow * kFastStride);
-#pragma unroll 16
-    for (int i = 0; i < 32; ++i) {
-      const float4 v = p[i];
-      acc = acc + v.x;
-      acc = acc + v.y;
-      acc = acc + v.z;
-      acc = acc + v.w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  return sqrtf(acc);
-}
-
 // rows one wave scores per pass: 16 x NB float2 registers of row data (8 rows beyond 512 dims)
 template <int NB>
 struct BuildRows {
@@ -210,52 +169,10 @@ struct BuildRows {
 template <int NB, bool FULL>
 __device__ __forceinline__ float score_upto16(const float* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
                                               uint32_t cnt, float* tile, int lane) {
-  if (NB <= 4 && cnt > 8) return score_tile1<NB, (NB <= 4 ? 16 : 8), FULL>(rows, dpad, q2, pn, cnt, tile, lane);
-  if (cnt > 4) return score_tile1<NB, 8, FULL>(rows, dpad, q2, pn, cnt, tile, lane);
-  return score_tile1<NB, 4, FULL>(rows, dpad, q2, pn, cnt, tile, lane);
+  if (NB <= 4 && cnt > 8) return score_fixed<NB, (NB <= 4 ? 16 : 8), FULL, 1>(rows, dpad, q2, pn, cnt, tile, 0, lane);
+  if (cnt > 4) return score_fixed<NB, 8, FULL, 1>(rows, dpad, q2, pn, cnt, tile, 0, lane);
+  return score_fixed<NB, 4, FULL, 1>(rows, dpad, q2, pn, cnt, tile, 0, lane);
 }
-
-// wave-wide max / min of a float, result in every lane (DPP row shifts + row broadcasts, no LDS)
-__device__ __forceinline__ float wave_max_f(float v) {
-  const int ninf = (int)0xFF800000u;
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x111, 0xf, 0xf, false)));  // row_shr:1
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x112, 0xf, 0xf, false)));  // row_shr:2
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x114, 0xf, 0xf, false)));  // row_shr:4
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x118, 0xf, 0xf, false)));  // row_shr:8
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x142, 0xa, 0xf, false)));  // row_bcast:15
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), 0x143, 0xc, 0xf, false)));  // row_bcast:31
-  return rlane_f(v, 63);
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-  const int pinf = (int)0x7F800000u;
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x111, 0xf, 0xf, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x112, 0xf, 0xf, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x114, 0xf, 0xf, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x118, 0xf, 0xf, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x142, 0xa, 0xf, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(pinf, __float_as_int(v), 0x143, 0xc, 0xf, false)));
-  return rlane_f(v, 63);
-}
-
-// lane `l` of `old` <- `value` (both wave-uniform): one compare and one select.  (v_writelane_b32 through inline asm cost
-// more: the lane select has to travel in M0, the wait states around it are spelled out by hand, and the tied operand made
-// the compiler copy the registers of the set around every call — ~100 instructions per admission in the replay loop.)
-__device__ __forceinline__ uint32_t writelane_u(uint32_t value, uint32_t l, uint32_t old) {
-  const uint32_t me = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  return me == l ? value : old;
-}
-
-// the same on unsigned values (zero fill: max's identity; min = ~max(~v))
-__device__ __forceinline__ uint32_t wave_max_u(uint32_t v) {
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ uint32_t wave_min_u(uint32_t v) { return ~wave_max_u(~v); }
 
 // ---------------------------------------------------------------------------------------------
 // per-workgroup context
@@ -286,7 +203,7 @@ __device__ __forceinline__ BuildCtx build_ctx(unsigned char* lds, const BuildLds
   c.dist = (float*)(lds + L.dist);
   c.misc = (uint32_t*)(lds + L.misc);
   c.slist = (uint16_t*)(lds + L.slist);
-  c.tile = (float*)(lds + L.tiles) + (size_t)c.wave * tile_rows * kFastStride;
+  c.tile = (float*)(lds + L.tiles) + (size_t)c.wave * tile_rows * kScoreStride;
   return c;
 }
 
@@ -410,7 +327,7 @@ __device__ __forceinline__ void fetch_lists(const BuildView& g, BuildCtx& c, uin
       if (nfresh) base = atomicAdd(&c.misc[MS_NSCORE], nfresh);
     }
     base = __builtin_amdgcn_readfirstlane(base);
-    if (fresh) c.slist[base + __popcll(fm & ((1ull << lane) - 1))] = (uint16_t)(p * 64 + lane);
+    if (fresh) c.slist[base + ballot_rank(fm, (uint32_t)lane)] = (uint16_t)(p * 64 + lane);
   }
 }
 
@@ -1012,7 +929,7 @@ __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c,
   }
   // d(q, entry) (:277-281)
   if (c.wave == 0) {
-    const float d0 = score_tile1<NB, 4, FULL>(g.rows, g.dpad, q2, entry, 1, c.tile, c.lane);
+    const float d0 = score_fixed<NB, 4, FULL, 1>(g.rows, g.dpad, q2, entry, 1, c.tile, 0, c.lane);
     if (c.lane == 0) c.misc[MS_CURD] = __float_as_uint(d0);
   }
   __syncthreads();
@@ -1630,7 +1547,7 @@ __global__ __launch_bounds__(256) void graph_edge_dist_kernel(const BuildView g,
   const uint32_t tile_rows = kTileRows;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_e[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* tile = (float*)lds_e + (size_t)wave * tile_rows * kFastStride;
+  float* tile = (float*)lds_e + (size_t)wave * tile_rows * kScoreStride;
   const uint32_t i = blockIdx.x * 4 + wave;
   if (i >= n_rows) return;
   uint32_t base_node;

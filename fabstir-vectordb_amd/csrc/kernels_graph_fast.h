@@ -18,111 +18,29 @@
 //    the reference.  (A second launch for those queries was tried first: one or two queries per thousand meet an
 //    accidental tie on real data, and a launch of their own behind the main one doubled the batch's latency.)
 //
-//  * Scoring keeps the reference's arithmetic — per row t = q_i - x_i; sum = sum + t*t, i ascending, f32, no FMA —
-//    but splits it where it is order-free: the products t*t are computed with the rows loaded COALESCED (a wave
-//    instruction reads 512 contiguous bytes of one row; all of the hop's loads are in flight together, in registers),
-//    each 128-dim block of products is transposed through a small LDS tile, and lane r then adds row r's products in
-//    dimension order.  The sum sees the same addends in the same order, so the bits are the reference's; the VALU
-//    work per hop drops from 3 ops per dim per lane-pass to ~1, and the 12 dependent L2 round trips of the old
-//    per-lane row stream become one HBM latency.
+//  * Scoring is the transposed-product scorer of score_rows.h (score_fixed: query and rows in registers, two product
+//    tiles): the reference's arithmetic, addend for addend, with coalesced row loads and one HBM latency per hop.
 //
 // The visited set stays the per-query bitmap in HBM (atomicOr, cleared from a log at the end of each layer).
 #pragma once
 #include "kernels_graph.h"
+#include "score_rows.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
 namespace fvdb {
 
-#ifndef FVDB_FAST_ADD_UNROLL
-#define FVDB_FAST_ADD_UNROLL 16  // LDS reads in flight ahead of the add chain (8: 1 % slower; 32: spills)
-#endif
-constexpr int kFastAddUnroll = FVDB_FAST_ADD_UNROLL;
 #ifndef FVDB_FAST_WAVES16
 #define FVDB_FAST_WAVES16 3      // waves per SIMD the 16-row form is compiled for (its LDS allows two workgroups per CU)
 #endif
-constexpr uint32_t kFastStride = 132;  // floats per staged row block: 128 products + 4 pad (lane r's reads hit 16 distinct bank quads)
 
-__device__ __forceinline__ uint32_t dpp_wave_shr1(uint32_t v) {
-  // lane i <- lane i-1 (lane 0 <- 0): one VALU op instead of an LDS-crossbar shuffle
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-
-// LDS per wave: pending [64 u32] | scalars [16 u32] | two product tiles [R][kFastStride] floats
+// LDS per wave: pending [64 u32] | scalars [16 u32] | two product tiles [R][kScoreStride] floats (score_rows.h)
 #ifndef FVDB_FAST_TILES
 #define FVDB_FAST_TILES 2  // product tiles per wave: 2 = the products of block c + 1 are written during the add chain of block c
 #endif
 __host__ __device__ inline size_t graph_fast_lds_bytes(uint32_t R) {
-  return (64 + 16) * 4 + FVDB_FAST_TILES * (size_t)R * kFastStride * 4;
-}
-
-// Distances of the wave's query to `cnt` rows (1 <= cnt <= RC; lane r of `pn` holds the r-th row's node): returns, in
-// lane r < cnt, sqrt of the reference's sum.  q2[c] = dims (128c + 2*lane, +1) of the query, held in registers for the
-// whole kernel.  Straight-line code for exactly RC rows — rows past cnt repeat the last one (an L2 hit) and their sums
-// are ignored — so the scheduler can fill the bubbles of the dependent add chain of block c with the products of block
-// c + 1, which go to the other tile.  FULL: dpad == NB * 128, no bounds checks.
-template <int NB, int RC, bool FULL>
-__device__ __forceinline__ float score_fixed(const float* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
-                                             uint32_t cnt, float* stage, uint32_t tile_floats, int lane
-#ifdef FVDB_GRAPH_STAMPS
-                                             , unsigned long long* t_acc
-#endif
-) {
-  STAMP(ta);
-  float2 x[RC][NB];
-  const uint32_t last = cnt - 1;
-#pragma unroll
-  for (int r = 0; r < RC; ++r) {
-    const uint32_t rr = (uint32_t)r < last ? (uint32_t)r : last;  // wave-uniform
-    const uint32_t node = __builtin_amdgcn_readlane(pn, rr);
-    const float* row = rows + (size_t)node * dpad;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) {
-      const uint32_t j = (uint32_t)c * 128u + 2u * (uint32_t)lane;
-      if (FULL) x[r][c] = *(const float2*)(row + j);
-      else x[r][c] = j < dpad ? *(const float2*)(row + j) : make_float2(0.0f, 0.0f);  // dpad % 4 == 0: pairs never straddle it
-    }
-  }
-  STAMP(tb);
-  STAMP_ADD(8, ta, tb);
-  const uint32_t lrow = (uint32_t)lane < (uint32_t)RC ? (uint32_t)lane : (uint32_t)(RC - 1);  // idle lanes add a valid row too: no branch
-  auto products = [&](int c, float* tile) {
-#pragma unroll
-    for (int r = 0; r < RC; ++r) {
-      const float t0 = q2[c].x - x[r][c].x, t1 = q2[c].y - x[r][c].y;
-      *(float2*)(tile + (uint32_t)r * kFastStride + 2u * (uint32_t)lane) = make_float2(t0 * t0, t1 * t1);
-    }
-  };
-  products(0, stage);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  STAMP(tc1);
-  STAMP_ADD(9, tb, tc1);
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NB; ++c) {
-    float* cur = FVDB_FAST_TILES == 2 ? stage + (uint32_t)(c & 1) * tile_floats : stage;
-    if (FVDB_FAST_TILES == 2 && c + 1 < NB) products(c + 1, stage + (uint32_t)((c + 1) & 1) * tile_floats);
-    const float4* p = (const float4*)(cur + lrow * kFastStride);
-#pragma unroll kFastAddUnroll
-    for (int i = 0; i < 32; ++i) {
-      const float4 v = p[i];
-      acc = acc + v.x;
-      acc = acc + v.y;
-      acc = acc + v.z;
-      acc = acc + v.w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();  // tile c is rewritten by block c + 2, tile c + 1 is complete
-    if (FVDB_FAST_TILES == 1 && c + 1 < NB) {  // one tile: the next block's products only now
-      products(c + 1, stage);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-  STAMP(tc2);
-  STAMP_ADD(11, tc1, tc2);
-  return sqrtf(acc);
+  return (64 + 16) * 4 + FVDB_FAST_TILES * (size_t)R * kScoreStride * 4;
 }
 
 // the smallest straight-line variant that holds the round
@@ -136,14 +54,14 @@ __device__ __forceinline__ float score_round(const GraphView& g, const float2 (&
 #define FVDB_TACC
 #endif
 ) {
-  const uint32_t dpad = g.dpad, tile = (uint32_t)R * kFastStride;
+  const uint32_t dpad = g.dpad, tile = (uint32_t)R * kScoreStride;
   if (dpad == (uint32_t)NB * 128u) {
-    if (R > 8 && cnt > 8) return score_fixed<NB, R, true>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-    if (R > 4 && cnt > 4) return score_fixed<NB, (R < 8 ? R : 8), true>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-    return score_fixed<NB, (R < 4 ? R : 4), true>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    if (R > 8 && cnt > 8) return score_fixed<NB, R, true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    if (R > 4 && cnt > 4) return score_fixed<NB, (R < 8 ? R : 8), true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    return score_fixed<NB, (R < 4 ? R : 4), true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
   }
-  if (R > 8 && cnt > 8) return score_fixed<NB, R, false>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-  return score_fixed<NB, (R < 8 ? R : 8), false>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+  if (R > 8 && cnt > 8) return score_fixed<NB, R, false, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+  return score_fixed<NB, (R < 8 ? R : 8), false, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
 }
 #undef FVDB_TACC
 

@@ -2,7 +2,7 @@
 // leave every neighbour list, and (unless the caller keeps the rows) the node map itself — the survivors are renumbered
 // densely IN THEIR OLD ORDER and the row store and every per-node array are compacted.
 //
-//   gm_count / gm_scan   survivors and the sum of their levels per 256 nodes, exclusive prefix over the workgroups
+//   gm_count / scan      survivors and the sum of their levels per 256 nodes, exclusive prefix over the workgroups
 //   gm_map               node -> new index (kGmNone = dropped), new index -> old node, new upper row -> old upper row,
 //                        level and upper-row base of every survivor at its new index
 //   gm_owner             (keep-rows form) upper row -> the node it belongs to
@@ -18,16 +18,11 @@
 //                        store a contiguous run; destination <= source, neighbouring waves share nothing
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 namespace fvdb {
 
 constexpr uint32_t kGmNone = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t gm_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void gm_count_kernel(const uint32_t* __restrict__ deleted, const uint32_t* __restrict__ level, uint32_t n,
                                                        uint32_t* __restrict__ wg_nodes, uint32_t* __restrict__ wg_urows) {
@@ -35,7 +30,7 @@ __global__ __launch_bounds__(256) void gm_count_kernel(const uint32_t* __restric
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const bool alive = i < n && deleted[i] == 0u;
   const uint32_t cnt = (uint32_t)__popcll(__ballot(alive));
-  const uint32_t lv = gm_wave_sum(alive ? level[i] : 0u);
+  const uint32_t lv = wave_sum_u(alive ? level[i] : 0u);
   if ((threadIdx.x & 63) == 0) {
     s_n[threadIdx.x >> 6] = cnt;
     s_u[threadIdx.x >> 6] = lv;
@@ -45,34 +40,6 @@ __global__ __launch_bounds__(256) void gm_count_kernel(const uint32_t* __restric
     wg_nodes[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
     wg_urows[blockIdx.x] = s_u[0] + s_u[1] + s_u[2] + s_u[3];
   }
-}
-
-// exclusive prefix sum of v[0 .. m) in place, the total into *total; one workgroup of 1024
-__global__ __launch_bounds__(1024) void gm_scan_kernel(uint32_t* __restrict__ v, uint32_t m, uint32_t* __restrict__ total) {
-  __shared__ uint32_t s_wave[16];
-  __shared__ uint32_t s_base;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < m; c0 += 1024) {
-    const uint32_t i = c0 + threadIdx.x;
-    const uint32_t x = i < m ? v[i] : 0u;
-    uint32_t incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o);
-      if ((int)lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = s_base;
-    for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-    if (i < m) v[i] = before + incl - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_base = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_base;
 }
 
 // wg_nodes / wg_urows: the exclusive prefixes.  n_out / u_out bound every write (they are the totals of the same scan).
@@ -88,18 +55,13 @@ __global__ __launch_bounds__(256) void gm_map_kernel(const uint32_t* __restrict_
   const bool alive = i < n && deleted[i] == 0u;
   const uint32_t lv = alive ? level[i] : 0u;
   const uint64_t m = __ballot(alive);
-  uint32_t incl = lv;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = __shfl_up(incl, o);
-    if ((int)lane >= o) incl += up;
-  }
+  const uint32_t incl = wave_incl_scan_u(lv, (int)lane);
   if (lane == 63) {
     s_n[wave] = (uint32_t)__popcll(m);
     s_u[wave] = incl;
   }
   __syncthreads();
-  uint32_t ni = wg_nodes[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  uint32_t ni = wg_nodes[blockIdx.x] + ballot_rank(m, lane);
   uint32_t nu = wg_urows[blockIdx.x] + incl - lv;
   for (uint32_t w = 0; w < wave; ++w) {
     ni += s_n[w];

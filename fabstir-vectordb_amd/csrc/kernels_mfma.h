@@ -744,10 +744,6 @@ __global__ __launch_bounds__(1024) void thr_loopback_fill_kernel(float* __restri
     if (!(thr[i] < __builtin_huge_valf())) thr[i] = typ - qn[i];
 }
 #endif
-__global__ void fill_f32_kernel(float* __restrict__ p, uint32_t n, float v) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // B'. refine: a query whose survivors outgrew the buffer had a loose threshold (the sampled list did not hold its near
@@ -852,12 +848,7 @@ __global__ __launch_bounds__(256) void select_kernel(const VerifyArgs m) {
       const uint32_t L = m.probes[(size_t)q * np + r];
       v = L != kInf32 ? m.glob_blocks[L] * 64u : 0u;
     }
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(inc, o);
-      if (lane >= o) inc += up;
-    }
+    const uint32_t inc = wave_incl_scan_u(v, lane);
     if (r < np) s_base[w][r] = carry + inc - v;
     carry += rlane(inc, 63);
   }
@@ -903,7 +894,7 @@ __global__ __launch_bounds__(256) void select_kernel(const VerifyArgs m) {
       const uint32_t s = s0 + lane;
       const bool c = s < cnt && !(m.sval[(size_t)q * m.cmax + s] > cut);
       const uint64_t mask = __ballot(c);
-      const uint32_t slot = ncand + __popcll(mask & ((1ull << lane) - 1ull));
+      const uint32_t slot = ncand + ballot_rank(mask, (uint32_t)lane);
       if (c && slot < kSelCand) s_cand[w][slot] = s;
       ncand += __popcll(mask);
     }

@@ -19,6 +19,7 @@
 // style shuffles only when a candidate beats the current k-th key.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -47,8 +48,6 @@ __device__ __forceinline__ f32x16_n cload16(const float* p) {
   return *(const FVDB_CONST_AS f32x16_a*)(uintptr_t)p;
 }
 
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint32_t rlane(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
 
 __device__ __forceinline__ bool key_lt(uint32_t ah, uint32_t al, uint32_t bh, uint32_t bl) {
   return ah < bh || (ah == bh && al < bl);

@@ -237,12 +237,7 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
       if (wave == 0) {  // the bin holding the s_want-th word of this round: 4 bins per lane, prefix across lanes
         const uint32_t h0 = s_hist[4 * lane], h1 = s_hist[4 * lane + 1], h2 = s_hist[4 * lane + 2], h3 = s_hist[4 * lane + 3];
         const uint32_t mine = h0 + h1 + h2 + h3;
-        uint32_t inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t up = __shfl_up(inc, o);
-          if ((int)lane >= o) inc += up;
-        }
+        const uint32_t inc = wave_incl_scan_u(mine, (int)lane);
         const uint32_t wantr = s_want, exc = inc - mine;
         if (exc < wantr && wantr <= inc) {  // exactly one lane
           uint32_t bin = 4 * lane, acc = exc;
@@ -276,7 +271,7 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
     for (uint32_t i = w0 + lane; i < w1; i += 64) {
       const uint32_t v = ar[i];
       const uint64_t m_tie = __ballot(v == cut);
-      const uint32_t my_tie = tie_rank + (uint32_t)__popcll(m_tie & ((1ull << lane) - 1ull));
+      const uint32_t my_tie = tie_rank + ballot_rank(m_tie, lane);
       tie_rank += (uint32_t)__popcll(m_tie);
       uint32_t at = kInf32;
       if (v < cut) at = atomicAdd(&s_taken, 1u);       // slots [0, below): any order, the sort follows
