@@ -364,10 +364,14 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
   //    threshold of a query comes from ONE list — by the logical index's sizes, the same choice on every rank — so only
   //    the rank owning that list computes it; an all-gather of the ranks' arrays (+inf = not mine) and a minimum give
   //    every rank every threshold.  Without this each rank would sample rows for all Bq queries: W times the work.
+  IvfSearch scan{IvfSearch::PROBED, q_scan, Bq, k, nprobe, sl.ids.as<uint64_t>(), sl.dist.as<float>(), sl.cnt.as<uint32_t>(),
+                 sl.keys.as<uint64_t>(), probes_scan};
   if (thr_share_ok(ivf, Bq, k, np)) {
     HIPCHK(ctx, sl.u_own.ensure((size_t)Bq * 4));
     HIPCHK(ctx, sl.thr.ensure((size_t)Bq * 4));
-    rc = shared_thresholds_slot(ivf, on, slot, q_scan, probes_scan, Bq, k, np, sl.u_own.as<float>());
+    rc = on_slot(ivf, on, slot, kNoMask, [&](const Env& E) {
+      return ivf_shared_thresholds(ivf, E, q_scan, probes_scan, Bq, k, np, sl.u_own.as<float>());
+    });
     if (rc) return rc;
     const float* u_all = sl.u_own.as<float>();
     if (W > 1) {
@@ -377,14 +381,13 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
       if (rc) return rc;
       u_all = sl.u_all.as<float>();
     }
-    rc = thr_combine_slot(ivf, on, slot, u_all, W, Bq, sl.thr.as<float>(), c->loopback);
+    rc = on_slot(ivf, on, slot, kNoMask, [&](const Env& E) {
+      return ivf_thr_combine(ivf, E, u_all, W, Bq, sl.thr.as<float>(), c->loopback);
+    });
     if (rc) return rc;
-    rc = search_probes_thr_slot(ivf, on, slot, q_scan, probes_scan, sl.thr.as<float>(), Bq, k, nprobe,
-                                sl.ids.as<uint64_t>(), sl.dist.as<float>(), sl.cnt.as<uint32_t>(), sl.keys.as<uint64_t>());
-  } else {
-    rc = fvdb_ivf_search_probes_dev_slot(ivf, on, slot, q_scan, probes_scan, Bq, k, nprobe, sl.ids.as<uint64_t>(),
-                                         sl.dist.as<float>(), sl.cnt.as<uint32_t>(), sl.keys.as<uint64_t>());
+    scan.given_thr = sl.thr.as<float>();
   }
+  rc = search_on_slot(ivf, on, slot, kNoMask, scan);
   if (rc) return rc;
   // 3. exchange 2: the partials of rank p's queries go to rank p
   const uint64_t* gk = sl.keys.as<uint64_t>();

@@ -284,8 +284,7 @@ namespace {
 struct Env {
   fvdb_ctx* ctx;
   IvfScratch* S;
-  const float* given_thr = nullptr;  // sharded search: filter thresholds already agreed between the ranks ([B], device)
-  const uint64_t* live = nullptr;    // masked search: these words stand for pool.valid in every stage of the list scan
+  const uint64_t* live = nullptr;  // masked search: these words stand for pool.valid in every stage of the list scan
 };
 inline IvfScratch& slot_scratch(fvdb_ivf* ivf, uint32_t slot) { return slot == 0 ? *ivf : ivf->spare[slot - 1]; }
 // The liveness words of the inverted lists as this search sees them, and the pool with them in place: the one place
@@ -458,6 +457,7 @@ struct Batch {
   float* out_dist;
   uint32_t* out_counts;
   uint64_t* out_keys;
+  const float* given_thr = nullptr;  // sharded search: filter thresholds already agreed between the ranks ([B], device)
 };
 
 inline ListTable list_table(const fvdb_ivf* ivf) {
@@ -738,7 +738,7 @@ void launch_threshold_direct(fvdb_ivf* ivf, fvdb_ctx* ctx, const ThresholdArgs& 
   else hipLaunchKernelGGL((threshold_direct_kernel<false>), dim3(cdiv(t.B, 4)), dim3(256), 0, ctx->stream, t);
 }
 
-MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, uint32_t B) {
+MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b) {
   const IvfScratch& S = *E.S;
   MfmaScanArgs a{};
   a.pool_data = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
@@ -754,12 +754,12 @@ MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, uint
   a.n_items = S.scalar(SC_FINE_ITEMS);
   a.head = S.scalar(SC_FINE_HEAD);
   a.qh = (const _Float16*)S.s_qh.p;
-  a.zero_row = B;
+  a.zero_row = b.B;
   a.dpad = ivf->dpad;
   a.segb = P.segb;
   // sharded search: the thresholds were computed once per query by the rank owning the list and combined across the
   // ranks before this call (ivf_shared_thresholds + the exchange in comm_sharded.h)
-  a.thr = E.given_thr ? E.given_thr : S.s_thr.as<float>();
+  a.thr = b.given_thr ? b.given_thr : S.s_thr.as<float>();
   a.cmax = P.cmax;
   a.surv = (u32x2*)S.s_surv.p;
   a.sval = S.s_sdist.as<float>();
@@ -792,7 +792,7 @@ void launch_mfma(fvdb_ctx* ctx, const MfmaScanArgs& a, const MfmaPlan& P) {
 void mfma_threshold(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b, const MfmaScanArgs& a) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
-  if (E.given_thr) return;
+  if (b.given_thr) return;
   if (!ivf_knobs().mfma_threshold_pass) {
     launch_threshold_direct(ivf, ctx, threshold_args(ivf, E, b.qpad, b.probes, b.B, b.k, b.np, S.s_thr.as<float>()));
     return;
@@ -965,8 +965,8 @@ VerifyArgs verify_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Bat
   v.queries = b.qpad;
   v.qn = S.s_qn2.as<float>();
   v.xmax_bits = ivf->d_xmax.as<uint32_t>();
-  v.thr = E.given_thr ? E.given_thr : S.s_thr.as<float>();
-  v.remote_thr = E.given_thr ? 1 : 0;
+  v.thr = b.given_thr ? b.given_thr : S.s_thr.as<float>();
+  v.remote_thr = b.given_thr ? 1 : 0;
   v.surv = (const u32x2*)S.s_surv.p;
   v.sval = S.s_sdist.as<float>();
   v.scnt = S.s_scnt.as<uint32_t>();
@@ -1048,12 +1048,12 @@ int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   if (rc) return rc;
   mark(ivf, E, EV_SCAN_BEGIN);
   launch_prep_queries(ivf, E, b.qpad, b.B);
-  MfmaScanArgs a = mfma_scan_args(ivf, E, P, b.B);
+  MfmaScanArgs a = mfma_scan_args(ivf, E, P, b);
   mfma_threshold(ivf, E, P, b, a);
   rc = mfma_filter(ivf, E, P, b, &a);
   if (rc) return rc;
   // thresholds agreed between the ranks are not refined; AUTO refines only while it has seen the need
-  if (!E.given_thr && !kn.mfma_no_refine && (ivf->scan_mode != FVDB_SCAN_AUTO || auto_refines(ivf))) {
+  if (!b.given_thr && !kn.mfma_no_refine && (ivf->scan_mode != FVDB_SCAN_AUTO || auto_refines(ivf))) {
     rc = mfma_refine(ivf, E, P, b, a);
     if (rc) return rc;
   }
@@ -1071,13 +1071,11 @@ int run_fine_mfma(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   return FVDB_OK;
 }
 
-int run_fine(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t k, uint32_t np, const uint32_t* probes,
-             uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys, int role) {
-  const Batch b{qpad, probes, B, k, np, out_ids, out_dist, out_counts, out_keys};
+int run_fine(fvdb_ivf* ivf, const Env& E, const Batch& b, int role) {
   E.S->pend_filter = false;
   // beyond the shape: this index's own state (norms, lists rather than the one flat list), which thr_share_ok must not ask
   bool mfma = (ivf->scan_mode == FVDB_SCAN_AUTO || ivf->scan_mode == FVDB_SCAN_FILTER) && !ivf_knobs().scan_exact &&
-              mfma_shape_ok(ivf, B, k, np) && role == ROLE_LIST && ivf->pool.norms != nullptr;
+              mfma_shape_ok(ivf, b.B, b.k, b.np) && role == ROLE_LIST && ivf->pool.norms != nullptr;
   // a mask thins the lists the filter samples its threshold from: AUTO scans exactly under one and keeps its hit-rate
   // watch for the unmasked traffic (FVDB_SCAN_FILTER still forces the filter)
   if (mfma && E.live && ivf->scan_mode == FVDB_SCAN_AUTO) mfma = false;
@@ -1155,6 +1153,7 @@ uint32_t wide_sub_batch(const fvdb_ivf* ivf, uint32_t B, uint32_t np) {
 int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
+  S.pend_filter = false;  // no filter kernel in this path: finish_profile has no interval of it to add
   const uint32_t nlist = ivf->nlist;
   const uint32_t segb = pick_segb(ivf, b.B, b.np);
   const uint32_t cap_blocks = wide_arena_blocks(ivf, b.np);
@@ -1853,55 +1852,110 @@ int fvdb_ivf_set_deleted(fvdb_ivf* ivf, const uint32_t* cluster, const uint32_t*
   return FVDB_OK;
 }
 
-// given_probes (device, [B][min(nprobe, nlist)] cluster ids in probe order): the coarse stage is skipped.
-// probes_only (device, same shape): only the coarse stage runs and its result is copied there.
-static int search_common(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe, bool all,
-                         uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys,
-                         const uint32_t* given_probes = nullptr, uint32_t* probes_only = nullptr) {
+// ---------------------------------------------------------------------------------------------
+// IVF search: one request, one sub-batch driver, one way onto a scratch set
+// ---------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// What an entry point asks for, stated once.  Everything per query — the queries, the optional inputs, every output —
+// lives here, so that slice() can cut all of it alike.
+struct IvfSearch {
+  enum Kind {
+    PROBED,       // the nprobe nearest lists, k <= FVDB_MAX_K
+    ALL,          // every list (ROLE_ALL), no coarse stage
+    WIDE,         // the nprobe nearest lists, k <= FVDB_MAX_K_WIDE (run_fine_wide)
+    COARSE_ONLY,  // the coarse stage alone: probes_out is the result
+  } kind;
+  const float* q_dev;  // [B][d]
+  uint32_t B, k, nprobe;
+  // results [B][k], counts [B]; any of them may be null
+  uint64_t* ids = nullptr;
+  float* dist = nullptr;
+  uint32_t* counts = nullptr;
+  uint64_t* keys = nullptr;
+  const uint32_t* given_probes = nullptr;  // [B][np] cluster ids in probe order: the coarse stage is skipped
+  const float* given_thr = nullptr;        // [B] filter thresholds agreed between the ranks (Batch::given_thr)
+  uint32_t* probes_out = nullptr;          // COARSE_ONLY: [B][np]
+
+  // Queries o .. o + b of the request; np = min(nprobe, nlist) as the driver clamped it.  The only place a stride is written.
+  IvfSearch slice(uint32_t o, uint32_t b, uint32_t d, uint32_t np) const {
+    auto at = [o](auto* p, size_t stride) { return p ? p + (size_t)o * stride : nullptr; };
+    IvfSearch s = *this;
+    s.B = b;
+    s.q_dev = at(q_dev, d);
+    s.ids = at(ids, k);
+    s.dist = at(dist, k);
+    s.counts = at(counts, 1);
+    s.keys = at(keys, k);
+    s.given_probes = at(given_probes, np);
+    s.given_thr = at(given_thr, 1);
+    s.probes_out = at(probes_out, np);
+    return s;
+  }
+};
+
+// The k a search serves.  The driver asks for every entry point; search_host asks first, before it stages anything.
+int check_k(fvdb_ctx* ctx, IvfSearch::Kind kind, uint32_t k) {
+  if (kind == IvfSearch::WIDE) {
+    if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
+  } else if (k == 0 || k > FVDB_MAX_K) {
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
+  }
+  return FVDB_OK;
+}
+
+// the stage events of a scratch set exist from the first profiled search on it
+void ensure_stage_events(const fvdb_ivf* ivf, IvfScratch& S) {
+  if (!ivf->ctx->profiling) return;
+  for (auto& e : S.sev)
+    if (!e) (void)hipEventCreate(&e);
+}
+
+// Every IVF search: validated, cut into sub-batches that fit the scratch budget, each through its coarse and fine stage.
+int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
+  const bool all = R.kind == IvfSearch::ALL, wide = R.kind == IvfSearch::WIDE;
   if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
-  if (k == 0 || k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
-  if (B == 0) return FVDB_OK;
+  int rc = check_k(ctx, R.kind, R.k);
+  if (rc) return rc;
+  if (wide && ivf->glob_set) FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search does not serve a shard of a larger index");
+  if (R.B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t np = all ? ivf->nlist : std::min(nprobe, ivf->nlist);
+  const uint32_t np = all ? ivf->nlist : std::min(R.nprobe, ivf->nlist);
   if (np == 0) FAIL(ctx, FVDB_E_INVALID, "nprobe must be > 0");
   if (!all && np > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe above FVDB_MAX_K");
-  int rc = upload_table(ivf);
+  rc = upload_table(ivf);
   if (rc) return rc;
   std::lock_guard<std::mutex> enq(S.enq);  // one search's launches go in as a block
-  if (ivf->ctx->profiling)
-    for (auto& e : S.sev)
-      if (!e) (void)hipEventCreate(&e);
-  const uint32_t step = sub_batch(ivf, B, k, np);
-  for (uint32_t o = 0; o < B; o += step) {
-    const uint32_t b = std::min(step, B - o);
+  ensure_stage_events(ivf, S);
+  const uint32_t step = wide ? wide_sub_batch(ivf, R.B, np) : sub_batch(ivf, R.B, R.k, np);
+  for (uint32_t o = 0; o < R.B; o += step) {
+    const IvfSearch r = R.slice(o, std::min(step, R.B - o), ivf->d, np);
     const float* qpad = nullptr;
-    rc = padded_queries(ivf, E, q_dev + (size_t)o * ivf->d, b, &qpad);
+    rc = padded_queries(ivf, E, r.q_dev, r.B, &qpad);
     if (rc) return rc;
-    HIPCHK(ctx, S.s_probes.ensure((size_t)b * np * 4));
+    HIPCHK(ctx, S.s_probes.ensure((size_t)r.B * np * 4));
     const uint32_t* probes = S.s_probes.as<uint32_t>();
     if (all) {
-      hipLaunchKernelGGL(probes_all_kernel, dim3(cdiv((uint64_t)b * np, 256)), dim3(256), 0, ctx->stream, b, np,
+      hipLaunchKernelGGL(probes_all_kernel, dim3(cdiv((uint64_t)r.B * np, 256)), dim3(256), 0, ctx->stream, r.B, np,
                          S.s_probes.as<uint32_t>());
       mark(ivf, E, EV_COARSE_DONE);
-    } else if (given_probes) {
-      probes = given_probes + (size_t)o * np;
+    } else if (r.given_probes) {
+      probes = r.given_probes;
       // no coarse stage in this call: zero-length stage intervals
       mark(ivf, E, EV_COARSE_BEGIN);
       mark(ivf, E, EV_COARSE_SCANNED);
       mark(ivf, E, EV_COARSE_DONE);
     } else {
-      rc = run_coarse(ivf, E, qpad, b, np, probes_only ? probes_only + (size_t)o * np : S.s_probes.as<uint32_t>(), nullptr);
+      rc = run_coarse(ivf, E, qpad, r.B, np, r.probes_out ? r.probes_out : S.s_probes.as<uint32_t>(), nullptr);
       if (rc) return rc;
     }
-    if (probes_only) continue;
-    Env Eo = E;
-    if (E.given_thr) Eo.given_thr = E.given_thr + o;  // agreed thresholds are indexed like the queries
-    rc = run_fine(ivf, Eo, qpad, b, k, np, probes, out_ids ? out_ids + (size_t)o * k : nullptr,
-                  out_dist ? out_dist + (size_t)o * k : nullptr, out_counts ? out_counts + o : nullptr,
-                  out_keys ? out_keys + (size_t)o * k : nullptr, all ? ROLE_ALL : ROLE_LIST);
+    if (R.kind == IvfSearch::COARSE_ONLY) continue;
+    const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr};
+    rc = wide ? run_fine_wide(ivf, E, b) : run_fine(ivf, E, b, all ? ROLE_ALL : ROLE_LIST);
     if (rc) return rc;
+    // per sub-batch: each one records the stage events anew, so their intervals are folded in before the next does
     rc = finish_profile(ivf, E, !all, true);
     if (rc) return rc;
   }
@@ -1910,22 +1964,27 @@ static int search_common(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32
   return FVDB_OK;
 }
 
-int fvdb_ivf_search_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
-                        uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
-  return search_common(ivf, Env{ivf->ctx, ivf}, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                       out_keys_dev);
-}
-
 // The explicit-slot entry points: the caller names the scratch set (slot) and the stream (`on`); nothing in the index
 // object changes, so calls on different slots may come from different host threads at the same time.
-static int slot_env(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, Env* E) {
+int slot_env(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, Env* E) {
   if (slot >= fvdb_ivf::kSlots) FAIL(ivf->ctx, FVDB_E_INVALID, "slot out of range");
   if (on && on->device != ivf->ctx->device) FAIL(ivf->ctx, FVDB_E_INVALID, "context of another device");
   E->ctx = on ? on : ivf->ctx;
   E->S = &slot_scratch(ivf, slot);
   return FVDB_OK;
 }
-static int slot_done(fvdb_ivf* ivf, const Env& E, int rc) {
+// The same under an allow-set mask (fvdb_mask_create_ivf): the mask's words take the place of the pool's live words in
+// every stage that reads them.  A mask built before the index last changed is refused.
+int mask_env(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, Env* E) {
+  if (!ivf) return FVDB_E_INVALID;
+  int rc = slot_env(ivf, on, slot, E);
+  if (rc) return rc;
+  if (!mask || mask->ivf != ivf) FAIL(ivf->ctx, FVDB_E_INVALID, "mask of another index");
+  if (mask->stamp != ivf->mutations) FAIL(ivf->ctx, FVDB_E_INVALID, "stale mask: the index changed after the mask was created");
+  E->live = mask->words.as<uint64_t>();
+  return FVDB_OK;
+}
+int slot_done(fvdb_ivf* ivf, const Env& E, int rc) {
   if (rc && E.ctx != ivf->ctx) {  // the failure text is read from the index's own context
     std::string m;
     {
@@ -1937,162 +1996,30 @@ static int slot_done(fvdb_ivf* ivf, const Env& E, int rc) {
   return rc;
 }
 
-int fvdb_ivf_coarse_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t nprobe,
-                             uint32_t* out_probes_dev) {
-  if (!out_probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null output");
+// How a call names its mask: none, or one that must be this index's and fresh (a null pointer is then refused).
+struct SlotMask {
+  bool required = false;
+  fvdb_mask* mask = nullptr;
+};
+constexpr SlotMask kNoMask{};
+inline SlotMask masked_by(fvdb_mask* mask) { return SlotMask{true, mask}; }
+
+// body(E) on slot `slot` and `on`'s stream: every launch goes to that stream and touches only that slot's scratch, so
+// slots can be in flight together.
+template <class Body>
+int on_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, SlotMask m, Body body) {
   Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
+  int rc = m.required ? mask_env(ivf, on, slot, m.mask, &E) : slot_env(ivf, on, slot, &E);
   if (rc) return rc;
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, 1, nprobe, false, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                         out_probes_dev));
+  return slot_done(ivf, E, body(E));
+}
+inline int search_on_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, SlotMask m, const IvfSearch& R) {
+  return on_slot(ivf, on, slot, m, [&](const Env& E) { return ivf_search(ivf, E, R); });
 }
 
-int fvdb_ivf_search_probes_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev,
-                                    const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
-                                    uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
-                                    uint64_t* out_keys_dev) {
-  if (!probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null probes");
-  Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                                         out_keys_dev, probes_dev));
-}
-
-// the sharded step's variants (comm_sharded.h): thresholds shared between the ranks
-static int shared_thresholds_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, const uint32_t* probes_dev,
-                                  uint32_t B, uint32_t k, uint32_t np, float* u_out) {
-  Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, ivf_shared_thresholds(ivf, E, q_dev, probes_dev, B, k, np, u_out));
-}
-static int thr_combine_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* u_all, uint32_t W, uint32_t B,
-                            float* thr_out, bool loopback_fill) {
-  Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, ivf_thr_combine(ivf, E, u_all, W, B, thr_out, loopback_fill));
-}
-static int search_probes_thr_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, const uint32_t* probes_dev,
-                                  const float* thr_dev, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev,
-                                  float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
-  Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  E.given_thr = thr_dev;
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                                         out_keys_dev, probes_dev));
-}
-
-int fvdb_ivf_search_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
-                             uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
-                             uint64_t* out_keys_dev) {
-  // every launch goes to `on`'s stream and touches only this slot's scratch, so slots can be in flight together
-  Env E{};
-  int rc = slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                                         out_keys_dev));
-}
-
-// The same two searches under an allow-set mask (fvdb_mask_create_ivf): the mask's words take the place of the pool's
-// live words in every stage that reads them.  A mask built before the index last changed is refused.
-static int mask_env(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, Env* E) {
-  if (!ivf) return FVDB_E_INVALID;
-  int rc = slot_env(ivf, on, slot, E);
-  if (rc) return rc;
-  if (!mask || mask->ivf != ivf) FAIL(ivf->ctx, FVDB_E_INVALID, "mask of another index");
-  if (mask->stamp != ivf->mutations) FAIL(ivf->ctx, FVDB_E_INVALID, "stale mask: the index changed after the mask was created");
-  E->live = mask->words.as<uint64_t>();
-  return FVDB_OK;
-}
-
-int fvdb_ivf_search_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
-                                    uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
-                                    uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
-  Env E{};
-  int rc = mask_env(ivf, on, slot, mask, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                                         out_keys_dev));
-}
-
-int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
-                                           const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
-                                           uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
-                                           uint64_t* out_keys_dev) {
-  Env E{};
-  int rc = mask_env(ivf, on, slot, mask, &E);
-  if (rc) return rc;
-  if (!probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null probes");
-  return slot_done(ivf, E, search_common(ivf, E, q_dev, B, k, nprobe, false, out_ids_dev, out_dist_dev, out_counts_dev,
-                                         out_keys_dev, probes_dev));
-}
-
-// search_common for the wide selection: coarse stage as ever, then run_fine_wide, sub-batched under the arena budget.
-static int search_wide_common(fvdb_ivf* ivf, const Env& E, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
-                              uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint64_t* out_keys) {
-  fvdb_ctx* ctx = E.ctx;
-  IvfScratch& S = *E.S;
-  if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
-  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
-  if (ivf->glob_set) FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search does not serve a shard of a larger index");
-  if (B == 0) return FVDB_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t np = std::min(nprobe, ivf->nlist);
-  if (np == 0) FAIL(ctx, FVDB_E_INVALID, "nprobe must be > 0");
-  if (np > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe above FVDB_MAX_K");
-  int rc = upload_table(ivf);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> enq(S.enq);
-  if (ivf->ctx->profiling)
-    for (auto& e : S.sev)
-      if (!e) (void)hipEventCreate(&e);
-  S.pend_filter = false;
-  const uint32_t step = wide_sub_batch(ivf, B, np);
-  for (uint32_t o = 0; o < B; o += step) {
-    const uint32_t b = std::min(step, B - o);
-    const float* qpad = nullptr;
-    rc = padded_queries(ivf, E, q_dev + (size_t)o * ivf->d, b, &qpad);
-    if (rc) return rc;
-    HIPCHK(ctx, S.s_probes.ensure((size_t)b * np * 4));
-    rc = run_coarse(ivf, E, qpad, b, np, S.s_probes.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    rc = run_fine_wide(ivf, E,
-                       Batch{qpad, S.s_probes.as<uint32_t>(), b, k, np, out_ids ? out_ids + (size_t)o * k : nullptr,
-                             out_dist ? out_dist + (size_t)o * k : nullptr, out_counts ? out_counts + o : nullptr,
-                             out_keys ? out_keys + (size_t)o * k : nullptr});
-    if (rc) return rc;
-    rc = finish_profile(ivf, E, true, true);
-    if (rc) return rc;
-  }
-  ivf->last_set.store(E.S);
-  ivf->last_ctx.store(E.ctx);
-  return FVDB_OK;
-}
-
-int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
-                                  uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
-                                  uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
-  if (!ivf) return FVDB_E_INVALID;
-  Env E{};
-  int rc = mask ? mask_env(ivf, on, slot, mask, &E) : slot_env(ivf, on, slot, &E);
-  if (rc) return rc;
-  return slot_done(ivf, E, search_wide_common(ivf, E, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev,
-                                              out_keys_dev));
-}
-
-int fvdb_ivf_search_all_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint64_t* out_ids_dev,
-                            float* out_dist_dev, uint32_t* out_counts_dev) {
-  return search_common(ivf, Env{ivf->ctx, ivf}, q_dev, B, k, 0, true, out_ids_dev, out_dist_dev, out_counts_dev, nullptr);
-}
-
-// A leased scratch set + stream for one blocking search: any number of host threads may call the host-pointer
+// A leased scratch set + stream for one blocking call: any number of host threads may call the host-pointer
 // entry points on one index; each call takes a free set (or waits for one) and gives it back when it returns.
 // With stage profiling on, the call runs on the index's own stream with set 0 instead (a measuring run is one thread).
-extern "C++" {
-namespace {
 struct Lease {
   fvdb_ivf* ivf;
   int idx = -1;
@@ -2126,32 +2053,102 @@ struct Lease {
     ivf->lease_cv.notify_one();
   }
 };
+// body(E) on a leased set, which goes back when the call returns
+template <class Body>
+int on_lease(fvdb_ivf* ivf, Body body) {
+  Lease L(ivf);
+  if (L.rc) return L.rc;
+  return slot_done(ivf, L.E, body(L.E));
+}
 }  // namespace
 }  // extern "C++"
 
-static int search_host(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, bool all,
-                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts, bool wide = false) {
+int fvdb_ivf_search_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                        uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  return ivf_search(ivf, Env{ivf->ctx, ivf},
+                    IvfSearch{IvfSearch::PROBED, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+int fvdb_ivf_search_all_dev(fvdb_ivf* ivf, const float* q_dev, uint32_t B, uint32_t k, uint64_t* out_ids_dev,
+                            float* out_dist_dev, uint32_t* out_counts_dev) {
+  return ivf_search(ivf, Env{ivf->ctx, ivf}, IvfSearch{IvfSearch::ALL, q_dev, B, k, 0, out_ids_dev, out_dist_dev, out_counts_dev});
+}
+
+int fvdb_ivf_coarse_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t nprobe,
+                             uint32_t* out_probes_dev) {
+  if (!out_probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null output");
+  IvfSearch R{IvfSearch::COARSE_ONLY, q_dev, B, 1, nprobe};
+  R.probes_out = out_probes_dev;
+  return search_on_slot(ivf, on, slot, kNoMask, R);
+}
+
+int fvdb_ivf_search_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                             uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                             uint64_t* out_keys_dev) {
+  return search_on_slot(ivf, on, slot, kNoMask,
+                        IvfSearch{IvfSearch::PROBED, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+int fvdb_ivf_search_probes_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev,
+                                    const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                    uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                                    uint64_t* out_keys_dev) {
+  if (!probes_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null probes");
+  return search_on_slot(ivf, on, slot, kNoMask,
+                        IvfSearch{IvfSearch::PROBED, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev,
+                                  probes_dev});
+}
+
+int fvdb_ivf_search_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                    uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  return search_on_slot(ivf, on, slot, masked_by(mask),
+                        IvfSearch{IvfSearch::PROBED, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                           const uint32_t* probes_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                           uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                                           uint64_t* out_keys_dev) {
+  return on_slot(ivf, on, slot, masked_by(mask), [&](const Env& E) -> int {
+    if (!probes_dev) FAIL(E.ctx, FVDB_E_INVALID, "null probes");  // after the slot and the mask, as ever
+    return ivf_search(ivf, E,
+                      IvfSearch{IvfSearch::PROBED, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev,
+                                probes_dev});
+  });
+}
+
+int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                  uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  return search_on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask,
+                        IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+// The blocking host-pointer searches: the batch is staged in a leased set, searched there, and the results copied back.
+static int search_host(fvdb_ivf* ivf, IvfSearch::Kind kind, const float* q, uint32_t B, uint32_t k, uint32_t nprobe,
+                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts) {
+  // ivf_search makes these refusals again, for every entry point; here they come before the input is read and a set is
+  // leased, in the order callers know: not trained, nothing to do, k, non-finite input
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
   if (B == 0) return FVDB_OK;
-  if (k == 0 || k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K))
-    FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, wide ? "k must be in 1..FVDB_MAX_K_WIDE" : "k must be in 1..FVDB_MAX_K");
-  int rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
+  int rc = check_k(ivf->ctx, kind, k);
   if (rc) return rc;
-  Lease L(ivf);
-  if (L.rc) return L.rc;
-  fvdb_ctx* ctx = L.E.ctx;
-  IvfScratch& S = *L.E.S;
-  auto run = [&]() -> int {
+  rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
+  if (rc) return rc;
+  return on_lease(ivf, [&](const Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    IvfScratch& S = *E.S;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, S.s_in.ensure((size_t)B * ivf->d * 4));
     HIPCHK(ctx, S.s_out_ids.ensure((size_t)B * k * 8));
     HIPCHK(ctx, S.s_out_dist.ensure((size_t)B * k * 4));
     HIPCHK(ctx, S.s_out_cnt.ensure((size_t)B * 4));
     HIPCHK(ctx, hipMemcpyAsync(S.s_in.p, q, (size_t)B * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = wide ? search_wide_common(ivf, L.E, S.s_in.as<float>(), B, k, nprobe, S.s_out_ids.as<uint64_t>(),
-                                      S.s_out_dist.as<float>(), S.s_out_cnt.as<uint32_t>(), nullptr)
-                 : search_common(ivf, L.E, S.s_in.as<float>(), B, k, nprobe, all, S.s_out_ids.as<uint64_t>(),
-                                 S.s_out_dist.as<float>(), S.s_out_cnt.as<uint32_t>(), nullptr);
+    int r = ivf_search(ivf, E,
+                       IvfSearch{kind, S.s_in.as<float>(), B, k, nprobe, S.s_out_ids.as<uint64_t>(), S.s_out_dist.as<float>(),
+                                 S.s_out_cnt.as<uint32_t>()});
     if (r) return r;
     HIPCHK(ctx, hipMemcpyAsync(out_ids, S.s_out_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_dist, S.s_out_dist.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2159,23 +2156,23 @@ static int search_host(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, ui
       HIPCHK(ctx, hipMemcpyAsync(out_counts, S.s_out_cnt.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return FVDB_OK;
-  };
-  return slot_done(ivf, L.E, run());
+  });
 }
 
 int fvdb_ivf_search(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                     float* out_dist, uint32_t* out_counts) {
-  return search_host(ivf, q, B, k, nprobe, false, out_ids, out_dist, out_counts);
+  return search_host(ivf, IvfSearch::PROBED, q, B, k, nprobe, out_ids, out_dist, out_counts);
 }
 int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                          float* out_dist, uint32_t* out_counts) {
-  return search_host(ivf, q, B, k, nprobe, false, out_ids, out_dist, out_counts, /*wide=*/true);
+  return search_host(ivf, IvfSearch::WIDE, q, B, k, nprobe, out_ids, out_dist, out_counts);
 }
 int fvdb_ivf_search_all(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_counts) {
-  return search_host(ivf, q, B, k, 0, true, out_ids, out_dist, out_counts);
+  return search_host(ivf, IvfSearch::ALL, q, B, k, 0, out_ids, out_dist, out_counts);
 }
 
+// The coarse stage with its centroid distances, for host rows: one batch, not sub-batched.
 int fvdb_ivf_coarse(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t nprobe, uint32_t* out_clusters,
                     float* out_dist) {
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
@@ -2184,11 +2181,9 @@ int fvdb_ivf_coarse(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t nprobe, 
   if (np == 0 || np > FVDB_MAX_K) FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, "nprobe must be in 1..FVDB_MAX_K");
   int rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
   if (rc) return rc;
-  Lease L(ivf);
-  if (L.rc) return L.rc;
-  fvdb_ctx* ctx = L.E.ctx;
-  IvfScratch& S = *L.E.S;
-  auto run = [&]() -> int {
+  return on_lease(ivf, [&](const Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    IvfScratch& S = *E.S;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> enq(S.enq);
     HIPCHK(ctx, S.s_in.ensure((size_t)B * ivf->d * 4));
@@ -2196,20 +2191,17 @@ int fvdb_ivf_coarse(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t nprobe, 
     HIPCHK(ctx, S.s_cdist.ensure((size_t)B * np * 4));
     HIPCHK(ctx, hipMemcpyAsync(S.s_in.p, q, (size_t)B * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream));
     const float* qpad = nullptr;
-    int r = padded_queries(ivf, L.E, S.s_in.as<float>(), B, &qpad);
+    int r = padded_queries(ivf, E, S.s_in.as<float>(), B, &qpad);
     if (r) return r;
-    if (ivf->ctx->profiling)
-      for (auto& e : S.sev)
-        if (!e) (void)hipEventCreate(&e);
-    r = run_coarse(ivf, L.E, qpad, B, np, S.s_probes.as<uint32_t>(), S.s_cdist.as<float>());
+    ensure_stage_events(ivf, S);
+    r = run_coarse(ivf, E, qpad, B, np, S.s_probes.as<uint32_t>(), S.s_cdist.as<float>());
     if (r) return r;
     HIPCHK(ctx, hipMemcpyAsync(out_clusters, S.s_probes.p, (size_t)B * np * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (out_dist)
       HIPCHK(ctx, hipMemcpyAsync(out_dist, S.s_cdist.p, (size_t)B * np * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return FVDB_OK;
-  };
-  return slot_done(ivf, L.E, run());
+  });
 }
 
 int fvdb_ivf_set_coarse_mode(fvdb_ivf* ivf, int mode) {

@@ -38,11 +38,9 @@ int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const 
     if (cluster[i] >= ivf->nlist || pos[i] >= ivf->list_len[cluster[i]]) FAIL(ivf->ctx, FVDB_E_NOT_FOUND, "no such row");
     slots[i] = ivf->list_blocks[cluster[i]][pos[i] >> 6] * 64 + (pos[i] & 63);
   }
-  Lease L(ivf);
-  if (L.rc) return L.rc;
-  fvdb_ctx* ctx = L.E.ctx;
-  IvfScratch& S = *L.E.S;
-  auto run = [&]() -> int {
+  return on_lease(ivf, [&](const Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    IvfScratch& S = *E.S;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, S.s_fslots.ensure(n * 4));
     if (to_host) HIPCHK(ctx, S.s_frows.ensure(n * ivf->d * 4));
@@ -67,8 +65,7 @@ int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const 
       HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, S.fetch_done, 0));
     }
     return FVDB_OK;
-  };
-  return slot_done(ivf, L.E, run());
+  });
 }
 
 int store_pair_ok(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_t n) {
