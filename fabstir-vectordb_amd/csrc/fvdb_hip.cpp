@@ -23,6 +23,7 @@
 #include "kernels_misc.h"
 #include "kernels_scan.h"
 #include "kernels_wide.h"
+#include "kernels_rank.h"
 #include "kernels_coarse.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma_wg.h"
@@ -185,6 +186,8 @@ struct IvfScratch {
   Buf s_q{this}, s_cpart{this}, s_probes{this}, s_cnt{this}, s_fill{this}, s_eoff{this}, s_ioff{this}, s_entries{this};
   Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
   Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
+  Buf s_rbase{this}, s_rarena{this};  // the full centroid ranking (kernels_rank.h): the same for the centroid table
+  Buf s_qual{this};                   // fvdb_ivf_search_quality_dev: the two result blocks
   Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
   // fvdb_ivf_get_rows (ivf_rows.h): slots and gathered rows of one fetch.  Not s_slots / s_in: in set 0 those are the
   // insert staging.  fetch_done: the last fetch that read s_fslots on a stream other than the set's own
@@ -485,12 +488,82 @@ MergeArgs merge_args(const PoolView& pool, const ListTable& lists, const uint32_
   return m;
 }
 
+// ---- the full centroid ranking (kernels_rank.h): kc above the register top-k ----
+// Arena of one chunk of queries: the ranking is cut so that its distance words stay under this.
+constexpr uint64_t kRankArenaBytes = 256ull << 20;
+// What a search of np = min(nprobe, nlist) lists needs beyond the register path, asked by every entry point before it
+// touches the device: the full ranking sorts the whole centroid table in one workgroup's LDS.
+int check_rank(fvdb_ctx* ctx, const fvdb_ivf* ivf, uint32_t np) {
+  if (np > FVDB_MAX_K && ivf->nlist > kRankSortMaxLists)
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe above FVDB_MAX_K needs an index of at most 16384 lists");
+  return FVDB_OK;
+}
+
+// Coarse stage for kc > FVDB_MAX_K: every centroid scored into a per-query arena with the exact fold, then one
+// workgroup per query sorts (distance bits, cluster position) and keeps the first kc.  Same outputs as run_coarse.
+int run_coarse_rank(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t kc, uint32_t* out_probes,
+                    float* out_dist) {
+  fvdb_ctx* ctx = E.ctx;
+  IvfScratch& S = *E.S;
+  int rc = check_rank(ctx, ivf, kc);
+  if (rc) return rc;
+  const uint32_t cblocks = ivf->cpool.used_blocks, n = cblocks * 64;
+  uint32_t P = 1;
+  while (P < n) P <<= 1;
+  const uint32_t lds = P * 8;
+  const uint32_t threads = std::min<uint32_t>(kRankThreads, std::max<uint32_t>(64, P / 2));
+  const uint32_t chunk = (uint32_t)std::min<uint64_t>(B, std::max<uint64_t>(1, kRankArenaBytes / ((uint64_t)n * 4)));
+  HIPCHK(ctx, S.s_rarena.ensure((size_t)chunk * n * 4));
+  HIPCHK(ctx, S.s_rbase.ensure((size_t)chunk * 2 * 4));
+  HIPCHK(ctx, S.s_entries.ensure((size_t)chunk * 8));
+  HIPCHK(ctx, S.s_ceoff.ensure(16));
+  HIPCHK(ctx, S.s_cioff.ensure(16));
+  HIPCHK(ctx, S.s_scalars.ensure(kScalarsBytes));
+  // the attribute belongs to the function (on this device), not to the launch: every call sets the same value, the
+  // largest sort served, so that searches of indexes of different sizes on different host threads never lower it
+  // under one another
+  HIPCHK(ctx, hipFuncSetAttribute((const void*)rank_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(kRankSortMaxLists * 8)));
+  const ListTable clist{ivf->c_off.as<uint32_t>(), ivf->c_blocks.as<uint32_t>(), 1};
+  const PoolView cpool = ivf->cpool.view();
+  const uint32_t grid = (uint32_t)ctx->num_cus * ivf_knobs().scan_wgs_per_cu;
+  mark(ivf, E, EV_COARSE_BEGIN);
+  for (uint32_t o = 0; o < B; o += chunk) {
+    const uint32_t b = std::min(chunk, B - o);
+    hipLaunchKernelGGL(plan_all_kernel, dim3(cdiv(b, 256)), dim3(256), 0, ctx->stream, b, cblocks, 1u, 16u,
+                       S.s_ceoff.as<uint32_t>(), S.s_cioff.as<uint32_t>(), S.s_entries.as<uint2>(),
+                       S.scalar(SC_COARSE_ITEMS), S.scalar(SC_COARSE_HEAD));
+    hipLaunchKernelGGL(rank_base_kernel, dim3(cdiv(b, 256)), dim3(256), 0, ctx->stream, b, cblocks, S.s_rbase.as<uint32_t>());
+    const uint32_t items = cblocks * cdiv(b, 16);
+    hipLaunchKernelGGL(wide_score_kernel<0>, dim3(std::min(grid, std::max<uint32_t>(1u, cdiv(items, 4)))), dim3(256), 0,
+                       ctx->stream, cpool.data, cpool.valid, cpool.d4, clist.off, clist.blocks, 1u, S.s_ceoff.as<uint32_t>(),
+                       S.s_cioff.as<uint32_t>(), (const u32x2*)S.s_entries.as<uint2>(), S.scalar(SC_COARSE_ITEMS),
+                       S.scalar(SC_COARSE_HEAD), qpad + (size_t)o * ivf->dpad, ivf->dpad, 1u, 1u, S.s_rbase.as<uint32_t>(),
+                       S.s_rarena.as<uint32_t>(), (uint64_t)n);
+    if (o + b == B) mark(ivf, E, EV_COARSE_SCANNED);
+    RankArgs r{};
+    r.pool = cpool;
+    r.lists = clist;
+    r.arena = S.s_rarena.as<uint32_t>();
+    r.n = n;
+    r.P = P;
+    r.np = kc;
+    r.out_probes = out_probes + (size_t)o * kc;
+    r.out_dist = out_dist ? out_dist + (size_t)o * kc : nullptr;
+    hipLaunchKernelGGL(rank_sort_kernel, dim3(b), dim3(threads), lds, ctx->stream, r);
+  }
+  mark(ivf, E, EV_COARSE_DONE);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
 // Coarse stage: rank the centroid table for B queries, keep kc nearest per query.
 // Writes u32 cluster ids to out_probes[B][kc] (probe order) and, optionally, their distances.
 int run_coarse(fvdb_ivf* ivf, const Env& E, const float* qpad, uint32_t B, uint32_t kc, uint32_t* out_probes,
                float* out_dist) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
+  if (kc > FVDB_MAX_K) return run_coarse_rank(ivf, E, qpad, B, kc, out_probes, out_dist);
   if (ivf->coarse_mode == 0 && !ivf_knobs().coarse_exact && ivf->dpad % 16 == 0 && kc <= 48 && ivf->nlist >= 64 && B > 0 &&
       (uint64_t)B * ivf->nlist < (1ull << 31)) {
     // matrix cores propose 64 candidates per query; the reference's arithmetic decides (kernels_coarse.h)
@@ -1191,7 +1264,10 @@ int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   w.out_dist = b.out_dist;
   w.out_counts = b.out_counts;
   w.out_keys = b.out_keys;
-  hipLaunchKernelGGL(wide_select_kernel, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
+  if (b.np <= kWideMaxProbes)
+    hipLaunchKernelGGL(wide_select_kernel<true>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
+  else
+    hipLaunchKernelGGL(wide_select_kernel<false>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
   mark(ivf, E, EV_FINE_DONE);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
@@ -1861,7 +1937,8 @@ namespace {
 // lives here, so that slice() can cut all of it alike.
 struct IvfSearch {
   enum Kind {
-    PROBED,       // the nprobe nearest lists, k <= FVDB_MAX_K
+    PROBED,       // the nprobe nearest lists: k <= FVDB_MAX_K up to 256 lists probed; above that it is served as WIDE
+                  // (k <= FVDB_MAX_K_WIDE)
     ALL,          // every list (ROLE_ALL), no coarse stage
     WIDE,         // the nprobe nearest lists, k <= FVDB_MAX_K_WIDE (run_fine_wide)
     COARSE_ONLY,  // the coarse stage alone: probes_out is the result
@@ -1894,9 +1971,18 @@ struct IvfSearch {
   }
 };
 
+// Whether a request takes the wide selection (run_fine_wide): asked for, or more lists probed (np = min(nprobe, nlist))
+// than the register path ranks and merges.
+inline bool wide_route(IvfSearch::Kind kind, uint32_t np) {
+  return kind == IvfSearch::WIDE || (kind == IvfSearch::PROBED && np > FVDB_MAX_K);
+}
+inline uint32_t probed_lists(const fvdb_ivf* ivf, IvfSearch::Kind kind, uint32_t nprobe) {
+  return kind == IvfSearch::ALL ? ivf->nlist : std::min(nprobe, ivf->nlist);
+}
+
 // The k a search serves.  The driver asks for every entry point; search_host asks first, before it stages anything.
-int check_k(fvdb_ctx* ctx, IvfSearch::Kind kind, uint32_t k) {
-  if (kind == IvfSearch::WIDE) {
+int check_k(fvdb_ctx* ctx, IvfSearch::Kind kind, uint32_t k, uint32_t np) {
+  if (wide_route(kind, np)) {
     if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
   } else if (k == 0 || k > FVDB_MAX_K) {
     FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
@@ -1915,16 +2001,17 @@ void ensure_stage_events(const fvdb_ivf* ivf, IvfScratch& S) {
 int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
-  const bool all = R.kind == IvfSearch::ALL, wide = R.kind == IvfSearch::WIDE;
+  const uint32_t np = probed_lists(ivf, R.kind, R.nprobe);
+  const bool all = R.kind == IvfSearch::ALL, wide = wide_route(R.kind, np);
   if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
-  int rc = check_k(ctx, R.kind, R.k);
+  int rc = check_k(ctx, R.kind, R.k, np);
   if (rc) return rc;
-  if (wide && ivf->glob_set) FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search does not serve a shard of a larger index");
+  if (wide && ivf->glob_set)
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search (k or nprobe above FVDB_MAX_K) does not serve a shard of a larger index");
   if (R.B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t np = all ? ivf->nlist : std::min(R.nprobe, ivf->nlist);
   if (np == 0) FAIL(ctx, FVDB_E_INVALID, "nprobe must be > 0");
-  if (!all && np > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe above FVDB_MAX_K");
+  if (!all && (rc = check_rank(ctx, ivf, np))) return rc;
   rc = upload_table(ivf);
   if (rc) return rc;
   std::lock_guard<std::mutex> enq(S.enq);  // one search's launches go in as a block
@@ -2126,6 +2213,40 @@ int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fv
                         IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
 }
 
+// evaluate_search_quality's two searches and their comparison (src/ivf/operations.rs:344-377), resident: the search at
+// nprobe and the search of every list in centroid-rank order run on the slot, their results stay in the slot's scratch,
+// and one wave per query counts the matches.
+int fvdb_ivf_search_quality_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                uint32_t nprobe, float* out_recall_dev, float* out_precision_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  if (!q_dev || !out_recall_dev || !out_precision_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null buffer");
+  return on_slot(ivf, on, slot, kNoMask, [&](const Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    IvfScratch& S = *E.S;
+    if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
+    const IvfSearch::Kind kind = k > FVDB_MAX_K ? IvfSearch::WIDE : IvfSearch::PROBED;
+    int rc = check_k(ctx, kind, k, probed_lists(ivf, kind, nprobe));
+    if (rc) return rc;
+    if (B == 0) return FVDB_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)B * k;
+    HIPCHK(ctx, S.s_qual.ensure(2 * (n * 12 + (size_t)B * 4)));
+    char* p = (char*)S.s_qual.p;
+    uint64_t* ids[2] = {(uint64_t*)p, (uint64_t*)p + n};
+    float* dist[2] = {(float*)(p + n * 16), (float*)(p + n * 16) + n};
+    uint32_t* cnt[2] = {(uint32_t*)(p + n * 24), (uint32_t*)(p + n * 24) + B};
+    const uint32_t probes[2] = {nprobe, ivf->nlist};  // the configured search, the ground truth
+    for (int i = 0; i < 2; ++i) {
+      rc = ivf_search(ivf, E, IvfSearch{kind, q_dev, B, k, probes[i], ids[i], dist[i], cnt[i]});
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(search_quality_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, ids[0], cnt[0], ids[1], cnt[1], B, k,
+                       out_recall_dev, out_precision_dev);
+    HIPCHK(ctx, hipGetLastError());
+    return FVDB_OK;
+  });
+}
+
 // The blocking host-pointer searches: the batch is staged in a leased set, searched there, and the results copied back.
 static int search_host(fvdb_ivf* ivf, IvfSearch::Kind kind, const float* q, uint32_t B, uint32_t k, uint32_t nprobe,
                        uint64_t* out_ids, float* out_dist, uint32_t* out_counts) {
@@ -2133,7 +2254,7 @@ static int search_host(fvdb_ivf* ivf, IvfSearch::Kind kind, const float* q, uint
   // leased, in the order callers know: not trained, nothing to do, k, non-finite input
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
   if (B == 0) return FVDB_OK;
-  int rc = check_k(ivf->ctx, kind, k);
+  int rc = check_k(ivf->ctx, kind, k, probed_lists(ivf, kind, nprobe));
   if (rc) return rc;
   rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
   if (rc) return rc;
@@ -2178,8 +2299,10 @@ int fvdb_ivf_coarse(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t nprobe, 
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
   if (B == 0) return FVDB_OK;
   const uint32_t np = std::min(nprobe, ivf->nlist);
-  if (np == 0 || np > FVDB_MAX_K) FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, "nprobe must be in 1..FVDB_MAX_K");
-  int rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
+  if (np == 0) FAIL(ivf->ctx, FVDB_E_UNSUPPORTED, "nprobe must be > 0");
+  int rc = check_rank(ivf->ctx, ivf, np);
+  if (rc) return rc;
+  rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
   if (rc) return rc;
   return on_lease(ivf, [&](const Env& E) -> int {
     fvdb_ctx* ctx = E.ctx;

@@ -22,7 +22,7 @@ namespace fvdb {
 
 constexpr uint32_t kWideMaxK = 4096;       // FVDB_MAX_K_WIDE: the survivors' keys fill 32 KB of LDS
 constexpr uint32_t kWideSelThreads = 512;  // 8 waves share one query's arena
-constexpr uint32_t kWideMaxProbes = 256;   // FVDB_MAX_K: nprobe keeps its limit
+constexpr uint32_t kWideMaxProbes = 256;   // FVDB_MAX_K: the rank bases of this many probes are staged in LDS
 
 struct WideArgs {
   PoolView pool;
@@ -187,17 +187,24 @@ __device__ __forceinline__ uint32_t wide_rank_of(const uint32_t* s_base, uint32_
   return lo;
 }
 
+// LDS_BASE: the query's rank bases are staged in LDS (nprobe <= kWideMaxProbes); otherwise they are read where
+// wide_base_kernel left them — only the binary searches of the <= k winners touch them.
+template <bool LDS_BASE>
 __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const WideArgs a) {
   constexpr uint32_t T = kWideSelThreads, W = T / 64;
   __shared__ uint64_t s_keys[kWideMaxK];
   __shared__ uint32_t s_hist[256];
-  __shared__ uint32_t s_base[kWideMaxProbes + 1];
+  __shared__ uint32_t s_base_lds[LDS_BASE ? kWideMaxProbes + 1 : 1];
   __shared__ uint32_t s_wties[W];
   __shared__ uint32_t s_prefix, s_below, s_want, s_taken;
 
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q = blockIdx.x, np = a.nprobe, k = a.k;
-  for (uint32_t r = tid; r <= np; r += T) s_base[r] = a.base[(size_t)q * (np + 1) + r];
+  const uint32_t* s_base = a.base + (size_t)q * (np + 1);
+  if (LDS_BASE) {
+    for (uint32_t r = tid; r <= np; r += T) s_base_lds[r] = a.base[(size_t)q * (np + 1) + r];
+    s_base = s_base_lds;
+  }
   if (tid == 0) {
     s_prefix = 0;
     s_below = 0;

@@ -85,6 +85,19 @@ int fvh_ivf_cluster_stats(void* p, IVFIndex::ClusterStats* out) {
   *out = ((IVFIndex*)p)->get_cluster_stats();
   return FVDB_OK;
 }
+// evaluate_search_quality (src/ivf/operations.rs:329-391) at the configured n_probe.  out3 = avg_recall, avg_precision,
+// avg_query_time_ms; B = 0 is FVDB_E_INVALID ("No test queries provided")
+int fvh_ivf_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, float* out3,
+                                    uint64_t* queries_evaluated) {
+  IVFIndex::SearchQuality s{};
+  const int rc = ((IVFIndex*)p)->evaluate_search_quality(q, B, d, k, &s);
+  if (rc) return rc;
+  out3[0] = s.avg_recall;
+  out3[1] = s.avg_precision;
+  out3[2] = s.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
+  return FVDB_OK;
+}
 // rows by id, read back from HBM (src/ivf/core.rs:553-562); found[i] = 0 leaves row i of out untouched
 int fvh_ivf_get_vectors(void* p, const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
   return ((IVFIndex*)p)->get_vectors(ids, n, out, found);

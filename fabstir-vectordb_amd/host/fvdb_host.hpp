@@ -186,6 +186,15 @@ class IVFIndex {
   int add_clusters(uint32_t n_clusters_to_add, uint64_t* vectors_reassigned);     // operations.rs:195-220
   int optimize_clusters(uint32_t* iterations, float* improvement);                // operations.rs:222-260
   ClusterStats get_cluster_stats() const;                                         // operations.rs:263-288
+  // evaluate_search_quality (operations.rs:329-391): the configured n_probe against the search of every list in
+  // centroid-rank order, per query on the device (fvdb_ivf_search_quality_dev); the per-query values are summed here
+  // in query order, in f32, as the reference's `total_recall += recall`.  avg_query_time_ms is the wall time of the
+  // call over B (the reference times each query by itself).  B == 0 is FVDB_E_INVALID (:334-338).
+  struct SearchQuality {  // operations.rs SearchQuality
+    float avg_recall, avg_precision, avg_query_time_ms;
+    uint64_t queries_evaluated;
+  };
+  int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, SearchQuality* out);
   uint64_t cluster_size(uint32_t c) const;
   // list `c` in list-position order, copied back from HBM (save path, src/hybrid/persistence.rs:289-311)
   int export_list(uint32_t c, float* rows, uint64_t* ids, uint8_t* live) const;
@@ -219,7 +228,9 @@ class IVFIndex {
   MaskRef mask_;
   uint64_t mask_builds_ = 0;
   std::mutex allowed_mu_;           // search_allowed's staging blocks
-  DevBuf allowed_q_, allowed_out_;  // search_allowed: staged queries, result block and its pinned copy
+  // search_allowed: staged queries, result block and its pinned copy; evaluate_search_quality stages its queries and
+  // its per-query figures in the same pair, under the same mutex
+  DevBuf allowed_q_, allowed_out_;
   void drop_mask() {
     mask_.reset();
     mask_key_.clear();

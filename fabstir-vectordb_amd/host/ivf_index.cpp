@@ -1,5 +1,6 @@
 // ivf_index.cpp — IVFIndex mirror (src/ivf/core.rs, src/ivf/operations.rs) over the C ABI.
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 
 #include "fvdb_host.hpp"
@@ -130,6 +131,40 @@ IVFIndex::ClusterStats IVFIndex::get_cluster_stats() const {
   if (dev_) fvdb_ivf_list_sizes(dev_, sizes.data());
   for (uint32_t c = 0; c < cfg_.n_clusters; ++c) st.empty_clusters += sizes[c] == 0;
   return st;
+}
+
+// src/ivf/operations.rs:329-391
+int IVFIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, SearchQuality* out) {
+  if (B == 0) return FVDB_E_INVALID;  // "No test queries provided"
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  if (!q || !out) return FVDB_E_INVALID;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  const auto start = std::chrono::steady_clock::now();
+  std::lock_guard<std::mutex> lk(allowed_mu_);  // search_allowed's staging blocks: calls take turns
+  const uint64_t bytes = (uint64_t)B * 8;  // recall[B], precision[B]
+  int rc;
+  if ((rc = allowed_q_.reserve(ctx_, (uint64_t)B * dim * 4, false)) || (rc = allowed_out_.reserve(ctx_, bytes, true))) return rc;
+  if ((rc = fvdb_dev_upload(ctx_, allowed_q_.dev, q, (size_t)B * dim * 4))) return rc;
+  float* d = (float*)allowed_out_.dev;
+  rc = fvdb_ivf_search_quality_dev(dev_, nullptr, 0, (const float*)allowed_q_.dev, B, k, cfg_.n_probe, d, d + B);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx_, allowed_out_.host, allowed_out_.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(ctx_)))
+    return rc;
+  const float* h = (const float*)allowed_out_.host;
+  float total_recall = 0.0f, total_precision = 0.0f;
+  for (uint32_t b = 0; b < B; ++b) {
+    total_recall += h[b];
+    total_precision += h[B + b];
+  }
+  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
+  out->avg_recall = total_recall / (float)B;
+  out->avg_precision = total_precision / (float)B;
+  out->avg_query_time_ms = elapsed.count() / (float)B;
+  out->queries_evaluated = B;
+  return FVDB_OK;
 }
 
 // "Collect all existing vectors ... train ... clear ... reinsert" (operations.rs:158-186, :231-250) without the rows
@@ -417,7 +452,8 @@ int IVFIndex::assign(const float* v, uint64_t n, uint32_t dim, uint32_t* out) {
 }
 
 // src/ivf/core.rs:626-681 for a batch (src/ivf/operations.rs:132-145).  k <= FVDB_MAX_K goes through the register
-// top-k, a larger k (up to FVDB_MAX_K_WIDE) through the wide selection; the engine refuses anything above that.
+// top-k, a larger k (up to FVDB_MAX_K_WIDE) through the wide selection; the engine refuses anything above that.  Any
+// n_probe is served: above FVDB_MAX_K probed lists the engine takes the wide selection by itself.
 int IVFIndex::search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, uint64_t* ids,
                      float* dist, uint32_t* counts) {
   if (!trained_) return FVDB_E_NOT_TRAINED;

@@ -143,6 +143,8 @@ HOST_SIGNATURES = {
     "fvh_hybrid_get_vectors": (i32, [vp, u64p, u64, f32p, C.POINTER(C.c_uint8)]),
     "fvh_hybrid_set_resident_migration": (None, [vp, i32]),
     "fvh_hybrid_migration_info": (i32, [vp, vp]),
+    # recall self-evaluation at any n_probe
+    "fvh_ivf_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, f32p, u64p]),
 }
 
 
@@ -343,6 +345,19 @@ class IVFIndex(_Base):
         self._check(self.lib.fvh_ivf_cluster_stats(self.h, C.byref(st)))
         return dict(n_clusters=st.n_clusters, total_vectors=st.total_vectors, avg_cluster_size=st.avg_cluster_size,
                     size_variance=st.size_variance, empty_clusters=st.empty_clusters)
+
+    def evaluate_search_quality(self, queries, k):
+        """IVFIndex::evaluate_search_quality (operations.rs:329-391): the configured n_probe against the search of every
+        list, both on the device.  Returns SearchQuality as a dict; avg_query_time_ms is the call's wall time over the
+        number of queries."""
+        q = np.asarray(queries, np.float32)
+        if q.size == 0:
+            raise InvalidConfig("Invalid parameter: No test queries provided")
+        q = _rows(q)
+        out, n = np.zeros(3, np.float32), C.c_uint64(0)
+        self._check(self.lib.fvh_ivf_evaluate_search_quality(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], int(k),
+                                                             _ptr(out, f32p), C.byref(n)))
+        return dict(avg_recall=out[0], avg_precision=out[1], avg_query_time_ms=float(out[2]), queries_evaluated=int(n.value))
 
     def maintenance_info(self):
         """Figures of the last resident maintenance job (fvdb_ivf_maintenance_info)."""

@@ -56,11 +56,13 @@ typedef enum fvdb_status {
   FVDB_E_NONFINITE = 9,     /* NaN/Inf input (reference panics: partial_cmp().unwrap()) */
   FVDB_E_HIP = 10,          /* HIP runtime error (message via fvdb_last_error) */
   FVDB_E_OOM = 11,          /* device or host allocation failed */
-  FVDB_E_UNSUPPORTED = 12,  /* k or nprobe above the compiled limit (FVDB_MAX_K) */
+  FVDB_E_UNSUPPORTED = 12,  /* k above the compiled limit of the entry point, or a shape it does not serve */
   FVDB_E_RCCL = 13          /* RCCL missing or a collective failed (message via fvdb_last_error) */
 } fvdb_status;
 
-/* Largest k (and nprobe) served by the in-kernel wavefront top-k (64 lanes x 4 registers). */
+/* Largest k (and nprobe) served by the in-kernel wavefront top-k (64 lanes x 4 registers).  It is the limit of that
+ * register path only: an IVF search with a larger k (fvdb_ivf_search_wide*) or with more than this many lists probed
+ * (any IVF search entry point) goes through the wide selection below, and its centroids are ranked by a full sort. */
 #define FVDB_MAX_K 256u
 /* Largest k served by the wide selection of the IVF list scan (fvdb_ivf_search_wide*): the distances of the probed
  * rows go through an arena in HBM and the k best are selected and sorted in LDS.  Equal to the traversal's ef limit. */
@@ -233,7 +235,11 @@ int fvdb_ivf_clear(fvdb_ivf* ivf);   /* empties the lists, keeps centroids (hybr
 int fvdb_ivf_set_global_list_sizes(fvdb_ivf* ivf, const uint64_t* sizes /* nlist */);
 
 /* search_with_config for B queries.  out_ids/out_dist are B x k (unused tail = FVDB_NO_ID /
- * +inf), out_counts[B] the number of hits.  nprobe > nlist probes every list. */
+ * +inf), out_counts[B] the number of hits.  nprobe > nlist probes every list.  Any nprobe >= 1 is served: with
+ * min(nprobe, nlist) > FVDB_MAX_K the centroid table is ranked whole (one sort per query, nlist <= 16384, otherwise
+ * FVDB_E_UNSUPPORTED) and the lists go through the wide selection, which then also takes any k <= FVDB_MAX_K_WIDE.  The
+ * same holds for every IVF search entry point below, the coarse step alone and the masked forms included; not for an
+ * index holding a shard of a larger one (fvdb_ivf_set_global_list_sizes) nor for the sharded search. */
 int fvdb_ivf_search(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                     float* out_dist, uint32_t* out_counts);
 /* Same with device pointers.  q is B x d row-major f32 in HBM.  out_keys (optional, B x k u64)
@@ -288,7 +294,8 @@ int fvdb_ivf_coarse_fallbacks(fvdb_ivf* ivf, uint64_t* out);
  * row scored with the reference's arithmetic) by construction.  AUTO also watches its own hit rate: when more than
  * one query in eight of the recent batches needed the exact rescan (data the filter cannot separate), the following
  * 64 batches (doubling up to 4096 while that stays so) use the exact scan.  AUTO applies when padded d % 16 == 0,
- * k <= 26, nprobe <= 256 and the batch has 32..16384 queries; other shapes use the exact scan. */
+ * k <= 26, nprobe <= 256 and the batch has 32..16384 queries; other shapes use the exact scan (more than 256 lists
+ * probed: the wide selection, whatever the mode). */
 #define FVDB_SCAN_AUTO 0
 #define FVDB_SCAN_EXACT 1
 #define FVDB_SCAN_FILTER 2 /* the matrix-core filter for every batch it can serve (AUTO without the hit-rate back-off) */
@@ -569,8 +576,8 @@ int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t
                                            uint64_t* out_keys_dev);
 /* search_with_config (src/ivf/core.rs:626-681) with 1 <= k <= FVDB_MAX_K_WIDE.  Same result definition, outputs,
  * padding and keys as fvdb_ivf_search_dev_slot; mask may be NULL (fvdb_mask_create_ivf otherwise; a stale mask is
- * FVDB_E_INVALID).  Always the exact scan (the matrix-core filter serves k <= 26).  nprobe keeps its limit
- * (min(nprobe, nlist) <= FVDB_MAX_K).  k = 0 or k > FVDB_MAX_K_WIDE is FVDB_E_UNSUPPORTED, and so is an index holding a
+ * FVDB_E_INVALID).  Always the exact scan (the matrix-core filter serves k <= 26).  Any nprobe >= 1, as for
+ * fvdb_ivf_search.  k = 0 or k > FVDB_MAX_K_WIDE is FVDB_E_UNSUPPORTED, and so is an index holding a
  * shard of a larger one (fvdb_ivf_set_global_list_sizes).  Slot and stream rules are fvdb_ivf_search_dev_slot's. */
 int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                   uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
@@ -579,6 +586,16 @@ int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fv
  * number of host threads may call it on one index. */
 int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                          float* out_dist, uint32_t* out_counts);
+/* evaluate_search_quality's per-query figures (src/ivf/operations.rs:344-377), resident: the search at `nprobe` and
+ * the search of every list in centroid-rank order (search_with_config(query, k, n_clusters): the ground truth) run on
+ * the slot, both results stay in HBM, and per query
+ *   matches   = result entries whose id occurs among the truth's ids,
+ *   recall    = truth empty ? 1 : matches / min(len(truth), k),
+ *   precision = result empty ? 0 : matches / len(result)        (f32 divisions of exactly representable integers)
+ * go to out_recall_dev[B] / out_precision_dev[B] (device memory).  1 <= k <= FVDB_MAX_K_WIDE; slot and stream rules are
+ * fvdb_ivf_search_dev_slot's. */
+int fvdb_ivf_search_quality_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                uint32_t nprobe, float* out_recall_dev, float* out_precision_dev);
 /* fvdb_graph_search_dev_slot under a mask: a node the mask does not allow is treated as deleted — never expanded into
  * `candidates`, never returned (src/hnsw/core.rs:511-513, :451-466).  status 1 queries go to the host walk as before;
  * the host must apply the same view there. */
