@@ -69,9 +69,11 @@ def build_pair(fv, ctx, x, ids, nlist, seed, max_iterations=25):
 
 
 # ---- 1. retrain parity ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("old,new,d", [(3, 16, 32), (64, 24, 20), (8, 12, 10)])
-def test_retrain_matches_restated_oracle(fv, ctx, old, new, d):
-    n = 5000
+# the last case gathers more rows from the lists than one 8192-element tile of the sequential training sums holds
+@pytest.mark.parametrize("old,new,d,n", [
+    pytest.param(3, 16, 32, 5000, id="3-16-32"), pytest.param(64, 24, 20, 5000, id="64-24-20"),
+    pytest.param(8, 12, 10, 5000, id="8-12-10"), pytest.param(5, 9, 12, 9000, id="5-9-12-9000")])
+def test_retrain_matches_restated_oracle(fv, ctx, old, new, d, n):
     x = mixture(n, d, n_comp=20, seed=old * 100 + new)
     ids = np.arange(n, dtype=np.uint64) * 3 + 11
     rows = {int(i): x[j] for j, i in enumerate(ids)}
@@ -188,7 +190,16 @@ def test_error_cases_and_the_state_they_leave(fv, ctx):
 
 # ---- 4. fp16 pool ---------------------------------------------------------------------------------------------------
 def test_fp16_pool_retrain(fv, ctx):
-    n, d, old, new = 4000, 32, 6, 14
+    fp16_pool_retrain(fv, ctx, 4000)
+
+
+def test_fp16_pool_train_from_across_a_tile(fv, ctx):
+    # train_from gathers more rows from the fp16 lists than one 8192-element tile of the sequential training sums holds
+    fp16_pool_retrain(fv, ctx, 9000)
+
+
+def fp16_pool_retrain(fv, ctx, n):
+    d, old, new = 32, 6, 14
     x = mixture(n, d, n_comp=10, seed=31)
     xh = x.astype(np.float16).astype(np.float32)  # what the pool stores, widened exactly
     ids = np.arange(n, dtype=np.uint64) + 5
