@@ -106,6 +106,7 @@ SIGNATURES = {
     "fvdb_ivf_stage_times": (u64, [vp, f32p]),
     "fvdb_ivf_profile_collect": (i32, [vp]),
     "fvdb_merge_keys_dev": (i32, [vp, vp, vp, u32, u32, u32, vp, vp, vp]),
+    "fvdb_merge_keys_wide_dev": (i32, [vp, vp, vp, u32, u32, u32, vp, vp, vp]),
     "fvdb_store_create": (i32, [vp, u32, u64, C.POINTER(vp)]),
     "fvdb_store_destroy": (None, [vp]),
     "fvdb_store_append": (i32, [vp, f32p, u64, u64p]),
@@ -173,6 +174,7 @@ SIGNATURES = {
     "fvdb_sharded_destroy": (None, [vp]),
     "fvdb_sharded_out_rows": (u32, [vp, u32, i32]),
     "fvdb_ivf_search_sharded_begin": (i32, [vp, vp, u32, vp, u32, u32, u32, i32, vp, vp, vp]),
+    "fvdb_ivf_search_sharded_wide_begin": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, i32, vp, vp, vp]),
     "fvdb_ivf_search_sharded_end": (i32, [vp, vp, u32]),
     # filtered search: allow-set masks
     "fvdb_mask_create_ivf": (i32, [vp, u64p, u64, C.POINTER(vp)]),
@@ -182,6 +184,7 @@ SIGNATURES = {
     "fvdb_ivf_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_probes_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_ivf_search_shard_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
     "fvdb_ivf_search_wide": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
     "fvdb_ivf_search_quality_dev": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
     "fvdb_graph_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),

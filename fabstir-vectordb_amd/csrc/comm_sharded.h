@@ -291,9 +291,16 @@ uint32_t fvdb_sharded_out_rows(fvdb_sharded* s, uint32_t B, int mode) {
   return mode == FVDB_SHARD_STRONG ? cdiv(B, (uint64_t)s->comm->world) : B;
 }
 
-int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
-                                  uint32_t nprobe, int mode, uint64_t* out_ids_dev, float* out_dist_dev,
-                                  uint32_t* out_counts_dev) {
+}  // extern "C"
+
+namespace {
+// One sharded step.  wide_api = false: fvdb_ivf_search_sharded_begin, the register path with its limits.  wide_api =
+// true: fvdb_ivf_search_sharded_wide_begin — any k <= FVDB_MAX_K_WIDE, any nprobe, an optional mask.  Every decision
+// that chooses a collective (route, threshold sharing) is taken from shapes, modes and whether a mask is present: the
+// same on every rank.
+int sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B, uint32_t k,
+                  uint32_t nprobe, int mode, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                  bool wide_api) {
   if (!s) return FVDB_E_INVALID;
   fvdb_ivf* ivf = s->ivf;
   fvdb_comm* c = s->comm;
@@ -302,12 +309,29 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
   if (mode != FVDB_SHARD_WEAK && mode != FVDB_SHARD_STRONG) FAIL(ctx, FVDB_E_INVALID, "unknown sharding mode");
   if (!q_dev || !out_ids_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null buffer");
   if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
-  if (k == 0 || k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
+  if (wide_api) {
+    if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
+  } else if (k == 0 || k > FVDB_MAX_K) {
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K");
+  }
   if (B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint32_t W = (uint32_t)c->world, d = ivf->d;
   const uint32_t np = std::min(nprobe, ivf->nlist);
-  if (np == 0 || np > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe must be in 1..FVDB_MAX_K");
+  if (wide_api) {
+    if (np == 0) FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe must be > 0");
+    int rcw = check_rank(ctx, ivf, np);
+    if (rcw) return rcw;
+    if (mask) {  // refused here, before the first collective, as every masked search refuses it
+      Env E{};
+      if ((rcw = mask_env(ivf, on, slot, mask, &E))) return rcw;
+    }
+  } else if (np == 0 || np > FVDB_MAX_K) {
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "nprobe must be in 1..FVDB_MAX_K");
+  }
+  // the wide selection (kernels_wide.h) serves what the register lists do not hold: no filter, so no thresholds
+  const bool wide = k > FVDB_MAX_K || np > FVDB_MAX_K;
+  const SlotMask smask = mask ? masked_by(mask) : kNoMask;
   const bool weak = mode == FVDB_SHARD_WEAK;
   const uint32_t Bo = weak ? B : cdiv(B, W);     // queries whose final result this rank produces
   const uint32_t Bq = weak ? W * B : B;          // queries scanned against the lists this rank owns
@@ -364,9 +388,11 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
   //    threshold of a query comes from ONE list — by the logical index's sizes, the same choice on every rank — so only
   //    the rank owning that list computes it; an all-gather of the ranks' arrays (+inf = not mine) and a minimum give
   //    every rank every threshold.  Without this each rank would sample rows for all Bq queries: W times the work.
-  IvfSearch scan{IvfSearch::PROBED, q_scan, Bq, k, nprobe, sl.ids.as<uint64_t>(), sl.dist.as<float>(), sl.cnt.as<uint32_t>(),
-                 sl.keys.as<uint64_t>(), probes_scan};
-  if (thr_share_ok(ivf, Bq, k, np)) {
+  //    Under a mask the thresholds stay rank-local (each a valid bound for its own rows): FVDB_SCAN_AUTO scans exactly
+  //    then, and whether a mask is present is the same on every rank.
+  IvfSearch scan{wide ? IvfSearch::SHARD_WIDE : IvfSearch::PROBED, q_scan, Bq, k, nprobe, sl.ids.as<uint64_t>(),
+                 sl.dist.as<float>(), sl.cnt.as<uint32_t>(), sl.keys.as<uint64_t>(), probes_scan};
+  if (!wide && !mask && thr_share_ok(ivf, Bq, k, np)) {
     HIPCHK(ctx, sl.u_own.ensure((size_t)Bq * 4));
     HIPCHK(ctx, sl.thr.ensure((size_t)Bq * 4));
     rc = on_slot(ivf, on, slot, kNoMask, [&](const Env& E) {
@@ -387,7 +413,7 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
     if (rc) return rc;
     scan.given_thr = sl.thr.as<float>();
   }
-  rc = search_on_slot(ivf, on, slot, kNoMask, scan);
+  rc = search_on_slot(ivf, on, slot, smask, scan);
   if (rc) return rc;
   // 3. exchange 2: the partials of rank p's queries go to rank p
   const uint64_t* gk = sl.keys.as<uint64_t>();
@@ -400,7 +426,23 @@ int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, 
     gi = sl.gi.as<uint64_t>();
   }
   // 4. world-way merge by key: exactly the single-index result for these Bo queries
+  if (wide) return fvdb_merge_keys_wide_dev(ctx, gk, gi, W, Bo, k, out_ids_dev, out_dist_dev, out_counts_dev);
   return fvdb_merge_keys_dev(ctx, gk, gi, W, Bo, k, out_ids_dev, out_dist_dev, out_counts_dev);
+}
+}  // namespace
+
+extern "C" {
+
+int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                  uint32_t nprobe, int mode, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev) {
+  return sharded_begin(s, on, slot, nullptr, q_dev, B, k, nprobe, mode, out_ids_dev, out_dist_dev, out_counts_dev, false);
+}
+
+int fvdb_ivf_search_sharded_wide_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                       uint32_t B, uint32_t k, uint32_t nprobe, int mode, uint64_t* out_ids_dev,
+                                       float* out_dist_dev, uint32_t* out_counts_dev) {
+  return sharded_begin(s, on, slot, mask, q_dev, B, k, nprobe, mode, out_ids_dev, out_dist_dev, out_counts_dev, true);
 }
 
 int fvdb_ivf_search_sharded_end(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot) {

@@ -186,6 +186,7 @@ struct IvfScratch {
   Buf s_q{this}, s_cpart{this}, s_probes{this}, s_cnt{this}, s_fill{this}, s_eoff{this}, s_ioff{this}, s_entries{this};
   Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
   Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
+  Buf s_wgbase{this};                // the same bases over the logical index, for the keys of a shard's wide search
   Buf s_rbase{this}, s_rarena{this};  // the full centroid ranking (kernels_rank.h): the same for the centroid table
   Buf s_qual{this};                   // fvdb_ivf_search_quality_dev: the two result blocks
   Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
@@ -461,6 +462,7 @@ struct Batch {
   uint32_t* out_counts;
   uint64_t* out_keys;
   const float* given_thr = nullptr;  // sharded search: filter thresholds already agreed between the ranks ([B], device)
+  bool glob_keys = false;            // wide selection: keys carry the logical index's seq (a shard of a larger index)
 };
 
 inline ListTable list_table(const fvdb_ivf* ivf) {
@@ -1264,7 +1266,16 @@ int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   w.out_dist = b.out_dist;
   w.out_counts = b.out_counts;
   w.out_keys = b.out_keys;
-  if (b.np <= kWideMaxProbes)
+  if (b.glob_keys) {
+    HIPCHK(ctx, S.s_wgbase.ensure((size_t)b.B * b.np * 4));
+    hipLaunchKernelGGL(wide_gbase_kernel, dim3(cdiv(b.B, 256)), dim3(256), 0, ctx->stream, b.probes, ivf->t_glob.as<uint32_t>(),
+                       b.B, b.np, S.s_wgbase.as<uint32_t>());
+    w.gbase = S.s_wgbase.as<uint32_t>();
+    if (b.np <= kWideMaxProbes)
+      hipLaunchKernelGGL((wide_select_kernel<true, true>), dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
+    else
+      hipLaunchKernelGGL((wide_select_kernel<false, true>), dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
+  } else if (b.np <= kWideMaxProbes)
     hipLaunchKernelGGL(wide_select_kernel<true>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
   else
     hipLaunchKernelGGL(wide_select_kernel<false>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, w);
@@ -1941,6 +1952,7 @@ struct IvfSearch {
                   // (k <= FVDB_MAX_K_WIDE)
     ALL,          // every list (ROLE_ALL), no coarse stage
     WIDE,         // the nprobe nearest lists, k <= FVDB_MAX_K_WIDE (run_fine_wide)
+    SHARD_WIDE,   // WIDE on an index that may hold a shard of a larger one: keys by the logical index's seq
     COARSE_ONLY,  // the coarse stage alone: probes_out is the result
   } kind;
   const float* q_dev;  // [B][d]
@@ -1974,7 +1986,20 @@ struct IvfSearch {
 // Whether a request takes the wide selection (run_fine_wide): asked for, or more lists probed (np = min(nprobe, nlist))
 // than the register path ranks and merges.
 inline bool wide_route(IvfSearch::Kind kind, uint32_t np) {
-  return kind == IvfSearch::WIDE || (kind == IvfSearch::PROBED && np > FVDB_MAX_K);
+  return kind == IvfSearch::WIDE || kind == IvfSearch::SHARD_WIDE || (kind == IvfSearch::PROBED && np > FVDB_MAX_K);
+}
+// The keys of a shard's wide search hold the logical index's seq in 32 bits, as the register path's do: 64 x the blocks
+// of np probed lists of the logical index must stay below 2^32.  Bounded by np longest lists and by all lists together.
+int check_shard_seq(fvdb_ctx* ctx, const fvdb_ivf* ivf, uint32_t np) {
+  uint64_t gmax = 0, gsum = 0;
+  for (uint32_t L = 0; L < ivf->nlist; ++L) {
+    const uint64_t nb = ivf->glob_set ? ivf->glob_blocks_host[L] : ivf->list_blocks[L].size();
+    gmax = std::max(gmax, nb);
+    gsum += nb;
+  }
+  if (std::min((uint64_t)np * gmax, gsum) * 64 >= (1ull << 32))
+    FAIL(ctx, FVDB_E_UNSUPPORTED, "the probed lists of the logical index hold more than 2^32 scan positions");
+  return FVDB_OK;
 }
 inline uint32_t probed_lists(const fvdb_ivf* ivf, IvfSearch::Kind kind, uint32_t nprobe) {
   return kind == IvfSearch::ALL ? ivf->nlist : std::min(nprobe, ivf->nlist);
@@ -2006,12 +2031,13 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
   if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
   int rc = check_k(ctx, R.kind, R.k, np);
   if (rc) return rc;
-  if (wide && ivf->glob_set)
+  if (wide && ivf->glob_set && R.kind != IvfSearch::SHARD_WIDE)
     FAIL(ctx, FVDB_E_UNSUPPORTED, "the wide search (k or nprobe above FVDB_MAX_K) does not serve a shard of a larger index");
   if (R.B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (np == 0) FAIL(ctx, FVDB_E_INVALID, "nprobe must be > 0");
   if (!all && (rc = check_rank(ctx, ivf, np))) return rc;
+  if (R.kind == IvfSearch::SHARD_WIDE && (rc = check_shard_seq(ctx, ivf, np))) return rc;
   rc = upload_table(ivf);
   if (rc) return rc;
   std::lock_guard<std::mutex> enq(S.enq);  // one search's launches go in as a block
@@ -2039,7 +2065,7 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
       if (rc) return rc;
     }
     if (R.kind == IvfSearch::COARSE_ONLY) continue;
-    const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr};
+    const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr, R.kind == IvfSearch::SHARD_WIDE};
     rc = wide ? run_fine_wide(ivf, E, b) : run_fine(ivf, E, b, all ? ROLE_ALL : ROLE_LIST);
     if (rc) return rc;
     // per sub-batch: each one records the stage events anew, so their intervals are folded in before the next does
@@ -2211,6 +2237,15 @@ int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fv
   if (!ivf) return FVDB_E_INVALID;
   return search_on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask,
                         IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+int fvdb_ivf_search_shard_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                        uint32_t k, uint32_t nprobe, const uint32_t* given_probes_dev, uint64_t* out_ids_dev,
+                                        float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  return search_on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask,
+                        IvfSearch{IvfSearch::SHARD_WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev,
+                                  out_keys_dev, given_probes_dev});
 }
 
 // evaluate_search_quality's two searches and their comparison (src/ivf/operations.rs:344-377), resident: the search at
@@ -2621,6 +2656,19 @@ int fvdb_merge_keys_dev(fvdb_ctx* ctx, const uint64_t* keys, const uint64_t* ids
     case 2: hipLaunchKernelGGL((merge_keys_kernel<2>), dim3(grid), dim3(256), 0, ctx->stream, keys, ids, G, B, k, out_ids, out_dist, out_counts); break;
     default: hipLaunchKernelGGL((merge_keys_kernel<4>), dim3(grid), dim3(256), 0, ctx->stream, keys, ids, G, B, k, out_ids, out_dist, out_counts); break;
   }
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+int fvdb_merge_keys_wide_dev(fvdb_ctx* ctx, const uint64_t* keys, const uint64_t* ids, uint32_t G, uint32_t B, uint32_t k,
+                             uint64_t* out_ids, float* out_dist, uint32_t* out_counts) {
+  if (!ctx) return FVDB_E_INVALID;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be in 1..FVDB_MAX_K_WIDE");
+  if (B == 0 || G == 0) return FVDB_OK;
+  if (!keys || !ids || !out_ids || !out_dist) FAIL(ctx, FVDB_E_INVALID, "null buffer");
+  if ((uint64_t)G * k >= (1ull << 31)) FAIL(ctx, FVDB_E_UNSUPPORTED, "too many partial lists for one merge");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(merge_keys_wide_kernel, dim3(B), dim3(256), 0, ctx->stream, keys, ids, G, B, k, out_ids, out_dist, out_counts);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }

@@ -11,6 +11,10 @@
 //           first rows AT the cut in seq order are gathered as 64-bit keys into LDS, sorted there (bitonic; the keys
 //           are unique) and resolved seq -> (probe rank, position) -> pool slot -> id as merge_topk_kernel does.
 //
+//   shards  on an index holding a shard of a larger one the selection is the same and only the keys written out change:
+//           their low word becomes the LOGICAL index's seq (wide_gbase_kernel, GLOB_KEYS), unique across ranks, and
+//           merge_keys_wide_kernel merges partial lists of up to kWideMaxK such keys.
+//
 // Arena of a query: 64 words per block of its probed lists, rank after rank; base[q][r] = blocks of the lists ranked
 // before r (wide_base_kernel), so arena index == seq.
 #pragma once
@@ -29,6 +33,7 @@ struct WideArgs {
   ListTable lists;
   const uint32_t* probes;  // [B][nprobe] list ids in probe order
   const uint32_t* base;    // [B][nprobe + 1] blocks of earlier-ranked probed lists; [nprobe] = all of them
+  const uint32_t* gbase;   // GLOB_KEYS only: [B][nprobe] the same count over the LOGICAL index (wide_gbase_kernel)
   uint32_t* arena;         // [B][stride] distance bits by seq
   uint64_t stride;         // words per query
   uint32_t B, k, nprobe;
@@ -52,6 +57,21 @@ __global__ void wide_base_kernel(const uint32_t* __restrict__ probes, const uint
     if (nb <= cap_blocks - acc) acc += nb;
   }
   base[(size_t)q * (np + 1) + np] = acc;
+}
+
+// gbase[q][0..np): exclusive prefix of the LOGICAL index's block counts of query q's probed lists — the base of
+// merge_topk_kernel's seq (kernels_scan.h), which is what makes a key unique across the ranks of a sharded index.
+// "No list" entries count as empty, as they do there.
+__global__ void wide_gbase_kernel(const uint32_t* __restrict__ probes, const uint32_t* __restrict__ glob_blocks, uint32_t B,
+                                  uint32_t np, uint32_t* __restrict__ gbase) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= B) return;
+  uint32_t acc = 0;
+  for (uint32_t r = 0; r < np; ++r) {
+    gbase[(size_t)q * np + r] = acc;
+    const uint32_t L = probes[(size_t)q * np + r];
+    acc += L == kInf32 ? 0u : glob_blocks[L];
+  }
 }
 
 // One work item: rows of blocks [b0, b1) of a list against the ne (<= QQ) queries of a group.  The fold is
@@ -189,7 +209,10 @@ __device__ __forceinline__ uint32_t wide_rank_of(const uint32_t* s_base, uint32_
 
 // LDS_BASE: the query's rank bases are staged in LDS (nprobe <= kWideMaxProbes); otherwise they are read where
 // wide_base_kernel left them — only the binary searches of the <= k winners touch them.
-template <bool LDS_BASE>
+// GLOB_KEYS: a shard of a larger index (fvdb_ivf_search_shard_wide_dev_slot).  Selection is unchanged — by (distance
+// bits, local arena index); the lists of other ranks are empty here, so that order restricted to this rank's rows is
+// the logical index's order — and only the key written out carries the logical index's seq (a.gbase) in its low word.
+template <bool LDS_BASE, bool GLOB_KEYS = false>
 __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const WideArgs a) {
   constexpr uint32_t T = kWideSelThreads, W = T / 64;
   __shared__ uint64_t s_keys[kWideMaxK];
@@ -319,6 +342,7 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
       const uint32_t pos = seq - s_base[r] * 64;
       const uint32_t blk = a.lists.blocks[a.lists.off[L] + (pos >> 6)];
       id = a.pool.ids[(size_t)blk * 64 + (pos & 63)];
+      if (GLOB_KEYS) key = (key & 0xFFFFFFFF00000000ull) | (a.gbase[(size_t)q * np + r] * 64u + pos);
     }
     const size_t o = (size_t)q * k + e;
     if (a.out_ids) a.out_ids[o] = id;
@@ -326,6 +350,54 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
     if (a.out_keys) a.out_keys[o] = key;
   }
   if (tid == 0 && a.out_counts) a.out_counts[q] = count;
+}
+
+// G-way merge of per-shard (key, id) partial lists of up to kWideMaxK entries each (fvdb_merge_keys_wide_dev): the
+// result merge_keys_kernel defines, found without a sort.  Every partial list is ascending with ~0 tails and the keys
+// are unique across the lists, so the place of an entry in the merged order is its own index plus, for every other
+// list, the number of that list's keys below it (a lower bound).  Entries whose place is below k write themselves
+// there; nothing is staged in LDS (G * k keys would be 256 KB at G = 8, k = 4096).  One workgroup per query.
+__global__ __launch_bounds__(256) void merge_keys_wide_kernel(const uint64_t* __restrict__ keys,
+                                                              const uint64_t* __restrict__ ids, uint32_t G, uint32_t B,
+                                                              uint32_t k, uint64_t* __restrict__ out_ids,
+                                                              float* __restrict__ out_dist,
+                                                              uint32_t* __restrict__ out_counts) {
+  __shared__ uint32_t s_valid;
+  const uint32_t tid = threadIdx.x, q = blockIdx.x;
+  if (tid == 0) s_valid = 0;
+  __syncthreads();
+  uint32_t valid = 0;
+  const uint32_t total = G * k;  // <= 2^31: the host checks
+  for (uint32_t t = tid; t < total; t += 256) {
+    const uint32_t g = t / k, e = t - g * k;
+    const size_t o = ((size_t)g * B + q) * k + e;
+    const uint64_t key = keys[o];
+    if ((uint32_t)(key >> 32) == kInf32) continue;  // "no result": the tail of a short list
+    ++valid;
+    uint32_t place = e;
+    for (uint32_t g2 = 0; g2 < G && place < k; ++g2) {
+      if (g2 == g) continue;
+      const uint64_t* __restrict__ other = keys + ((size_t)g2 * B + q) * k;
+      uint32_t lo = 0, hi = k;  // first index with other[i] >= key
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (other[mid] < key) lo = mid + 1; else hi = mid;
+      }
+      place += lo;
+    }
+    if (place < k) {
+      out_ids[(size_t)q * k + place] = ids[o];
+      out_dist[(size_t)q * k + place] = __uint_as_float((uint32_t)(key >> 32));
+    }
+  }
+  if (valid) atomicAdd(&s_valid, valid);
+  __syncthreads();
+  const uint32_t count = min(k, s_valid);
+  for (uint32_t e = count + tid; e < k; e += 256) {
+    out_ids[(size_t)q * k + e] = ~0ull;
+    out_dist[(size_t)q * k + e] = __uint_as_float(0x7F800000u);
+  }
+  if (tid == 0 && out_counts) out_counts[q] = count;
 }
 
 }  // namespace fvdb

@@ -437,6 +437,13 @@ class DeviceIVF:
         self.ctx.check(self.lib.fvdb_ivf_search_wide_dev_slot(self.h, on.h if on is not None else None, slot, mask, q_dev, B, k,
                                                               nprobe, ids_dev, dist_dev, cnt_dev, keys_dev))
 
+    def search_shard_wide_dev(self, q_dev, B, k, nprobe, ids_dev, dist_dev, cnt_dev, keys_dev=None, mask=None, probes_dev=None,
+                              on=None, slot=0):
+        """The wide search on an index that may hold a shard of a larger one (fvdb_ivf_search_shard_wide_dev_slot): keys
+        by the logical index's scan position, to be merged with merge_keys_wide_dev."""
+        self.ctx.check(self.lib.fvdb_ivf_search_shard_wide_dev_slot(self.h, on.h if on is not None else None, slot, mask, q_dev, B,
+                                                                    k, nprobe, probes_dev, ids_dev, dist_dev, cnt_dev, keys_dev))
+
     def search_all(self, q, k):
         q = self._rows(q)
         ids, ds, cnt = self._out(q.shape[0], k)
@@ -556,3 +563,8 @@ class RowStore:
 
 def merge_keys_dev(ctx, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev):
     ctx.check(ctx.lib.fvdb_merge_keys_dev(ctx.h, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev))
+
+
+def merge_keys_wide_dev(ctx, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev):
+    """fvdb_merge_keys_wide_dev: the same merge for 1 <= k <= FVDB_MAX_K_WIDE."""
+    ctx.check(ctx.lib.fvdb_merge_keys_wide_dev(ctx.h, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev))

@@ -300,6 +300,20 @@ int fvh_hybrid_search_sharded_begin(void* p, uint32_t slot, const float* q_dev, 
   c.historical_k = historical_k;
   return ((HybridIndex*)p)->search_sharded_begin(slot, q_dev, B, d, c, mode, now);
 }
+int fvh_hybrid_search_allowed_sharded_begin(void* p, uint32_t slot, const float* q_dev, uint32_t B, uint32_t d, uint64_t k,
+                                            uint64_t ef, uint64_t nprobe, int search_recent, int search_historical,
+                                            uint64_t recent_k, uint64_t historical_k, int mode, const uint64_t* allowed,
+                                            uint64_t n_allowed, double now) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = ef;
+  c.ivf_n_probe = nprobe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  c.recent_k = recent_k;
+  c.historical_k = historical_k;
+  return ((HybridIndex*)p)->search_allowed_sharded_begin(slot, q_dev, B, d, c, mode, allowed, n_allowed, now);
+}
 int fvh_hybrid_search_sharded_end(void* p, uint32_t slot, uint64_t* ids, float* dist, uint32_t* counts) {
   return ((HybridIndex*)p)->search_sharded_end(slot, ids, dist, counts);
 }

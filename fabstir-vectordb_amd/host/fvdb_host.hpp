@@ -564,6 +564,13 @@ class HybridIndex {
   int search_sharded_end(uint32_t slot, uint64_t* ids, float* dist, uint32_t* counts) {
     return search_dev_end(slot, ids, dist, counts);
   }
+  // A step whose historical_k or ivf_n_probe exceeds FVDB_MAX_K goes through fvdb_ivf_search_sharded_wide_begin.
+  // search_allowed_sharded_begin is the same step under an allow-set (search_allowed's semantics), collected by
+  // search_sharded_end: the masks are built after the migration step, under the read lock, and stay referenced until
+  // the slot is collected; the recent part is the masked traversal / allowed scan of this rank's own queries, the
+  // historical part the masked sharded step.  Every rank passes the SAME allow-set, as it passes the same `now`.
+  int search_allowed_sharded_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
+                                   int mode, const uint64_t* allowed, uint64_t n_allowed, double now = 0.0);
   uint32_t sharded_rows(uint32_t B, int mode) const;  // rows search_sharded_end writes on this rank
   // search_with_filter (src/hybrid/core.rs:513-549): ask for 3 k neighbours, keep the first k whose id the host
   // application's metadata filter accepts.  `matches(id, user)` stands for `metadata_map.get(id)` +
@@ -575,7 +582,7 @@ class HybridIndex {
   // returns after remove() of every id outside allowed[n_allowed]; the recent part is scanned exactly instead when
   // its allowed live nodes number at most recent().scan_cutoff().  The masks are built after the auto-migration step
   // and under the same read lock as the search, so they match the rows searched; the last pair is kept for a caller
-  // that repeats one filter.  FVDB_E_UNSUPPORTED once the index is sharded.
+  // that repeats one filter.  FVDB_E_UNSUPPORTED once the index is sharded (search_allowed_sharded_begin serves that).
   int search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,
                      uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* counts);
   // Concurrency (reference: tokio RwLock, searches = readers, src/hybrid/core.rs:457,466): search() / search_dev() /
@@ -657,7 +664,8 @@ class HybridIndex {
                   uint64_t n_allowed = 0, bool masked = false);
   // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                     int shard_mode, double now);
+                     int shard_mode, double now, const uint64_t* allowed = nullptr, uint64_t n_allowed = 0,
+                     bool masked = false);
   int begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                  int shard_mode = -1);
   // The per-search auto-migration (src/hybrid/core.rs:437-439).  A due migration moves rows between the two indexes (and

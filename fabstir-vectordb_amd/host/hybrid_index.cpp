@@ -510,7 +510,7 @@ int HybridIndex::search_dev_begin(uint32_t slot, const float* q_dev, uint32_t B,
 }
 
 int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                                int shard_mode, double now) {
+                                int shard_mode, double now, const uint64_t* allowed, uint64_t n_allowed, bool masked) {
   bool others = false;
   {
     std::lock_guard<std::mutex> lk(slot_mu_);
@@ -525,8 +525,15 @@ int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, u
   Lease lease(this, slot, Lease::kTake);
   if (!lease.sl) return FVDB_E_INVALID;
   lease.hand_over();  // whatever begin_impl returns, the slot stays the caller's until search_dev_end
-  slots_[slot].ivf_mask.reset();  // the explicit pair is an unfiltered search
+  slots_[slot].ivf_mask.reset();  // the explicit pair is an unfiltered search, unless it names an allow-set
   slots_[slot].view.reset();
+  if (masked && initialized_ && cfg.k != 0) {
+    // built as search_impl builds them: after the migration, under the read lock; search_dev_end drops them
+    if (cfg.search_recent)
+      if (int rc = recent_->allowed_view(allowed, n_allowed, &slots_[slot].view)) return rc;
+    if (cfg.search_historical && ivf_trained_)
+      if (int rc = historical_->allowed_mask(allowed, n_allowed, &slots_[slot].ivf_mask)) return rc;
+  }
   return begin_impl(slot, q_dev, B, dim, cfg, shard_mode);
 }
 
@@ -557,6 +564,14 @@ int HybridIndex::search_sharded_begin(uint32_t slot, const float* q_dev, uint32_
                                       const HybridSearchConfig& cfg, int mode, double now) {
   if (slot >= kSlots || !sharded_ || (mode != FVDB_SHARD_WEAK && mode != FVDB_SHARD_STRONG)) return FVDB_E_INVALID;
   return begin_explicit(slot, q_dev, B, dim, cfg, mode, now);
+}
+
+int HybridIndex::search_allowed_sharded_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim,
+                                              const HybridSearchConfig& cfg, int mode, const uint64_t* allowed,
+                                              uint64_t n_allowed, double now) {
+  if (slot >= kSlots || !sharded_ || (mode != FVDB_SHARD_WEAK && mode != FVDB_SHARD_STRONG)) return FVDB_E_INVALID;
+  if (n_allowed && !allowed) return FVDB_E_INVALID;
+  return begin_explicit(slot, q_dev, B, dim, cfg, mode, now, allowed, n_allowed, true);
 }
 
 // one block per slot for the IVF part's results, [ids R*hk u64 | dist R*hk f32 | counts R u32] -> a single copy
@@ -623,8 +638,13 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
     if (shard_mode >= 0) {
       // every rank must take part in the step's collectives even when its own slice is empty
       if (dim != historical_->dimension()) return FVDB_E_DIM;
-      const int rcs = fvdb_ivf_search_sharded_begin(sharded_, on, on ? slot : 0, q_dev, B_ivf_in, sl.hk,
-                                                    (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
+      // k or nprobe beyond the register path, or an allow-set: the wide sharded step; otherwise the call as ever
+      const bool beyond = sl.hk > FVDB_MAX_K || cfg.ivf_n_probe > FVDB_MAX_K || sl.ivf_mask;
+      const int rcs = beyond ? fvdb_ivf_search_sharded_wide_begin(sharded_, on, on ? slot : 0, sl.ivf_mask.get(), q_dev, B_ivf_in,
+                                                                  sl.hk, (uint32_t)std::min<uint64_t>(cfg.ivf_n_probe, 0xFFFFFFFFu),
+                                                                  shard_mode, d.ids, d.dist, d.counts)
+                             : fvdb_ivf_search_sharded_begin(sharded_, on, on ? slot : 0, q_dev, B_ivf_in, sl.hk,
+                                                             (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
       if (rcs) return rcs;
       sl.ivf_in_flight = true;
     } else {

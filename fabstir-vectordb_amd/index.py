@@ -105,6 +105,8 @@ HOST_SIGNATURES = {
     "fvh_hybrid_search_dev_end": (i32, [vp, u32, u64p, f32p, u32p]),
     "fvh_hybrid_attach_comm": (i32, [vp, vp]),
     "fvh_hybrid_search_sharded_begin": (i32, [vp, u32, vp, u32, u32, u64, u64, u64, i32, i32, u64, u64, i32, dbl]),
+    "fvh_hybrid_search_allowed_sharded_begin": (i32, [vp, u32, vp, u32, u32, u64, u64, u64, i32, i32, u64, u64, i32, u64p, u64,
+                                                      dbl]),
     "fvh_hybrid_search_sharded_end": (i32, [vp, u32, u64p, f32p, u32p]),
     "fvh_hybrid_sharded_rows": (u32, [vp, u32, i32]),
     "fvh_plan_list_owners": (None, [u64p, u32, u32, u32p]),
@@ -890,6 +892,17 @@ class HybridIndex(_Base):
         self._check(self.lib.fvh_hybrid_search_sharded_begin(self.h, slot, q_dev, B, dim, k, hnsw_ef, ivf_n_probe,
                                                              int(search_recent), int(search_historical), recent_k,
                                                              historical_k, mode, float(now)))
+        self._inflight = getattr(self, "_inflight", {})
+        self._inflight[slot] = (self.sharded_rows(B, mode), k)
+
+    def search_allowed_sharded_begin(self, slot, q_dev, B, k, mode, allowed, hnsw_ef=50, ivf_n_probe=10, search_recent=True,
+                                     search_historical=True, recent_k=0, historical_k=0, dim=None, now=0.0):
+        """search_sharded_begin under an allow-set (search_allowed's semantics): every rank passes the same `allowed`.
+        Collected by search_sharded_end."""
+        a = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+        self._check(self.lib.fvh_hybrid_search_allowed_sharded_begin(self.h, slot, q_dev, B, dim, k, hnsw_ef, ivf_n_probe,
+                                                                     int(search_recent), int(search_historical), recent_k,
+                                                                     historical_k, mode, _ptr(a, u64p), a.size, float(now)))
         self._inflight = getattr(self, "_inflight", {})
         self._inflight[slot] = (self.sharded_rows(B, mode), k)
 

@@ -1,6 +1,7 @@
 """Multi-GPU execution of the hybrid search: one process per GPU, inverted lists owned by ranks, RCCL over xGMI.
 
-All of the data path lives below Python, in the C ABI (include/fvdb.h: fvdb_comm_*, fvdb_ivf_search_sharded_begin/_end)
+All of the data path lives below Python, in the C ABI (include/fvdb.h: fvdb_comm_*, fvdb_ivf_search_sharded_begin/_end,
+fvdb_ivf_search_sharded_wide_begin for k or nprobe above FVDB_MAX_K and for an allow-set)
 and in the C++ host mirror (HybridIndex::attach_comm / search_sharded_begin / search_sharded_end): centroid ranking,
 exchange 1 (all-gather of queries + probe lists), the scan of the lists the rank owns, exchange 2 (all-to-all of the
 partial (key, id) lists), the world-way merge by key and the reference's hybrid merge with the replicated graph's
@@ -237,14 +238,20 @@ class ShardedHybrid:
         """Result rows this rank gets for a step of B queries."""
         return self.hyb.sharded_rows(B, mode)
 
-    def search_dev_begin(self, slot, q_dev, B, k, ef, nprobe, mode=WEAK, now=0.0):
+    def search_dev_begin(self, slot, q_dev, B, k, ef, nprobe, mode=WEAK, now=0.0, allowed=None):
         """Enqueue this rank's step in `slot` (q_dev: device pointer to B x d f32 — the rank's own batch in WEAK mode,
-        the global batch in STRONG mode).  Every rank must call begin/end in the same order, with the same `now`."""
-        self.hyb.search_sharded_begin(slot, q_dev, B, k, mode, hnsw_ef=ef, ivf_n_probe=nprobe, dim=self.d, now=now)
+        the global batch in STRONG mode).  Every rank must call begin/end in the same order, with the same `now` — and,
+        for a filtered search, the same `allowed` ids (None = no filter): each rank masks its own shard with them.
+        k and nprobe are not bound by FVDB_MAX_K (fvdb_ivf_search_sharded_wide_begin serves what lies above it)."""
+        if allowed is None:
+            self.hyb.search_sharded_begin(slot, q_dev, B, k, mode, hnsw_ef=ef, ivf_n_probe=nprobe, dim=self.d, now=now)
+        else:
+            self.hyb.search_allowed_sharded_begin(slot, q_dev, B, k, mode, allowed, hnsw_ef=ef, ivf_n_probe=nprobe, dim=self.d,
+                                                  now=now)
 
     def search_dev_end(self, slot):
         return self.hyb.search_sharded_end(slot)
 
-    def search_dev(self, q_dev, B, k, ef, nprobe, mode=WEAK, now=0.0):
-        self.search_dev_begin(0, q_dev, B, k, ef, nprobe, mode, now)
+    def search_dev(self, q_dev, B, k, ef, nprobe, mode=WEAK, now=0.0, allowed=None):
+        self.search_dev_begin(0, q_dev, B, k, ef, nprobe, mode, now, allowed)
         return self.search_dev_end(0)

@@ -241,7 +241,8 @@ int fvdb_ivf_set_global_list_sizes(fvdb_ivf* ivf, const uint64_t* sizes /* nlist
  * min(nprobe, nlist) > FVDB_MAX_K the centroid table is ranked whole (one sort per query, nlist <= 16384, otherwise
  * FVDB_E_UNSUPPORTED) and the lists go through the wide selection, which then also takes any k <= FVDB_MAX_K_WIDE.  The
  * same holds for every IVF search entry point below, the coarse step alone and the masked forms included; not for an
- * index holding a shard of a larger one (fvdb_ivf_set_global_list_sizes) nor for the sharded search. */
+ * index holding a shard of a larger one (fvdb_ivf_set_global_list_sizes) nor for fvdb_ivf_search_sharded_begin: a shard
+ * is served by fvdb_ivf_search_shard_wide_dev_slot and the sharded search by fvdb_ivf_search_sharded_wide_begin. */
 int fvdb_ivf_search(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                     float* out_dist, uint32_t* out_counts);
 /* Same with device pointers.  q is B x d row-major f32 in HBM.  out_keys (optional, B x k u64)
@@ -336,6 +337,14 @@ int fvdb_ivf_profile_collect(fvdb_ivf* ivf);  /* profiling mode 2: fold the last
  * keys/ids: G x B x k (device).  Exact because keys are unique. */
 int fvdb_merge_keys_dev(fvdb_ctx* ctx, const uint64_t* keys_dev, const uint64_t* ids_dev, uint32_t G, uint32_t B,
                         uint32_t k, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev);
+
+/* The same merge for 1 <= k <= FVDB_MAX_K_WIDE (same layout, same outputs: tails from the count up are FVDB_NO_ID /
+ * +inf, counts = min(k, valid entries)).  Needs what every search here writes: each partial list ascending by key with
+ * its "no result" (~0) entries last, and keys unique across the lists.  An entry's place in the result is then its own
+ * index plus the number of smaller keys in every other list, so nothing is sorted and nothing is staged on chip.  At
+ * k <= FVDB_MAX_K it returns exactly what fvdb_merge_keys_dev returns. */
+int fvdb_merge_keys_wide_dev(fvdb_ctx* ctx, const uint64_t* keys_dev, const uint64_t* ids_dev, uint32_t G, uint32_t B,
+                             uint32_t k, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev);
 
 /* ---- top-k / merge utilities -----------------------------------------------------------
  * The reference's public vector_ops helpers, batched: B independent rows per call, k <= FVDB_MAX_K.  Outputs are
@@ -547,7 +556,7 @@ int fvdb_graph_tie_restarts(fvdb_graph* g, uint64_t* queries, uint64_t* searched
  * train*, compact, refill_from; graph: upload, append_nodes, insert_linked, set_lists, set_entry, set_deleted) makes it
  * stale, and a masked search with a stale mask returns FVDB_E_INVALID (fvdb_last_error says so), never wrong rows.
  * Creating a mask needs the same exclusion against mutations as a search.  One mask serves a whole batch call.  The
- * sharded search (fvdb_ivf_search_sharded_begin) takes no mask.
+ * sharded search takes one through fvdb_ivf_search_sharded_wide_begin (fvdb_ivf_search_sharded_begin takes none).
  *  - fvdb_mask_create_ivf: ids[n] = the allowed row ids (host; duplicates and unknown ids are harmless).
  *  - fvdb_mask_create_graph: nodes[n] = the allowed NODE indices (host; the graph holds no ids: node index = store row).
  *  - fvdb_mask_info: allowed_live = rows (nodes) that are live in the index and allowed; stale = 1 once the index changed.
@@ -584,6 +593,21 @@ int fvdb_ivf_search_probes_dev_slot_masked(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t
 int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                   uint32_t k, uint32_t nprobe, uint64_t* out_ids_dev, float* out_dist_dev,
                                   uint32_t* out_counts_dev, uint64_t* out_keys_dev);
+/* The wide search for an index that may hold a shard of a larger one (fvdb_ivf_set_global_list_sizes; an index
+ * without global sizes is its own logical index).  1 <= k <= FVDB_MAX_K_WIDE, any nprobe >= 1 (nlist <= 16384 above
+ * FVDB_MAX_K probes), mask may be NULL, given_probes_dev may be NULL (otherwise [B][min(nprobe, nlist)] list ids in
+ * probe order, 0xFFFFFFFF = "no list", and the coarse stage is skipped).  The rows are selected as the wide search
+ * selects them — by (distance bits, scan position on this rank); lists this rank does not own are empty here, so that
+ * order over this rank's rows is the logical index's — and every key is
+ *   (distance bits << 32) | (64 x blocks of the earlier-ranked probed lists of the LOGICAL index + position),
+ * the key of fvdb_ivf_search_dev_slot: unique across the ranks, so the partial lists merge exactly
+ * (fvdb_merge_keys_wide_dev).  The low word is 32 bits wide, on this path as on the register path: a logical index
+ * whose probed lists could hold 2^32 scan positions or more (64 x min(nprobe x longest list, all lists) blocks) is
+ * refused with FVDB_E_UNSUPPORTED.  Slot and stream rules are fvdb_ivf_search_dev_slot's. */
+int fvdb_ivf_search_shard_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                        uint32_t B, uint32_t k, uint32_t nprobe, const uint32_t* given_probes_dev,
+                                        uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
+                                        uint64_t* out_keys_dev);
 /* The same search (src/ivf/core.rs:626-681), blocking, with host pointers and leased scratch like fvdb_ivf_search: any
  * number of host threads may call it on one index. */
 int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
@@ -654,6 +678,19 @@ uint32_t fvdb_sharded_out_rows(fvdb_sharded* s, uint32_t B, int mode);
 int fvdb_ivf_search_sharded_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
                                   uint32_t nprobe, int mode, uint64_t* out_ids_dev, float* out_dist_dev,
                                   uint32_t* out_counts_dev);
+/* The sharded search at any k <= FVDB_MAX_K_WIDE, any nprobe >= 1 (nlist <= 16384 above FVDB_MAX_K probes) and under
+ * an optional allow-set mask (NULL = none); collected by fvdb_ivf_search_sharded_end.  Same modes, exchanges, slot
+ * buffers and output shapes as fvdb_ivf_search_sharded_begin.  With k > FVDB_MAX_K or more than FVDB_MAX_K lists
+ * probed, the lists step is fvdb_ivf_search_shard_wide_dev_slot and the merge fvdb_merge_keys_wide_dev; that route has
+ * no matrix-core filter, so it exchanges no thresholds.  Otherwise the step is fvdb_ivf_search_sharded_begin's, under
+ * the mask if there is one; a masked step keeps its filter thresholds rank-local.  Which route and which collectives
+ * a call takes follows from shapes, mode and whether a mask is given alone, so every rank decides alike.
+ * Every rank must pass a mask built from the SAME allow-set (each over its own shard: fvdb_mask_create_ivf), as every
+ * rank of a hybrid index passes the same `now`.  A mask of another index, or one built before the index last changed,
+ * is FVDB_E_INVALID before anything is exchanged. */
+int fvdb_ivf_search_sharded_wide_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                       uint32_t B, uint32_t k, uint32_t nprobe, int mode, uint64_t* out_ids_dev,
+                                       float* out_dist_dev, uint32_t* out_counts_dev);
 int fvdb_ivf_search_sharded_end(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot);
 
 #ifdef __cplusplus
