@@ -108,6 +108,10 @@ SIGNATURES = {
     "fvdb_merge_keys_dev": (i32, [vp, vp, vp, u32, u32, u32, vp, vp, vp]),
     "fvdb_merge_keys_wide_dev": (i32, [vp, vp, vp, u32, u32, u32, vp, vp, vp]),
     "fvdb_store_create": (i32, [vp, u32, u64, C.POINTER(vp)]),
+    # fp16 rows in the row store
+    "fvdb_store_create_ex": (i32, [vp, u32, u64, i32, C.POINTER(vp)]),
+    "fvdb_store_dtype": (i32, [vp]),
+    "fvdb_store_bytes": (u64, [vp]),
     "fvdb_store_destroy": (None, [vp]),
     "fvdb_store_append": (i32, [vp, f32p, u64, u64p]),
     "fvdb_store_rows": (u64, [vp]),

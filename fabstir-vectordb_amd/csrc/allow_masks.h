@@ -93,8 +93,8 @@ int build_graph_mask(fvdb_mask* m, const GraphMaskSource& src, const uint32_t* n
 }
 
 template <int KR>
-void launch_allow_scan(fvdb_ctx* ctx, const AllowScanArgs& a, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
-  if (a.slices) hipLaunchKernelGGL((allow_scan_kernel<KR>), dim3(cdiv(a.B, 4), a.slices), dim3(256), 0, ctx->stream, a);
+void launch_allow_scan(fvdb_ctx* ctx, const AllowScanArgs& a, bool f16 /* the store's rows */, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
+  if (a.slices) hipLaunchKernelGGL((f16 ? allow_scan_kernel<KR, half_t> : allow_scan_kernel<KR, float>), dim3(cdiv(a.B, 4), a.slices), dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL((allow_merge_kernel<KR>), dim3(cdiv(a.B, 4)), dim3(256), 0, ctx->stream, a.part, a.nodes, a.slices, a.B, a.k,
                      out_nodes, out_dist, out_counts);
 }
@@ -206,9 +206,9 @@ int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot,
   rc = graph_scan_inputs(g, ctx, slot, q_dev, B, (size_t)a.slices * B * k * 8, &a.queries, &a.part);
   if (rc) return rc;
   switch (k <= 64 ? 1 : (k <= 128 ? 2 : 4)) {
-    case 1: launch_allow_scan<1>(ctx, a, out_nodes_dev, out_dist_dev, out_counts_dev); break;
-    case 2: launch_allow_scan<2>(ctx, a, out_nodes_dev, out_dist_dev, out_counts_dev); break;
-    default: launch_allow_scan<4>(ctx, a, out_nodes_dev, out_dist_dev, out_counts_dev); break;
+    case 1: launch_allow_scan<1>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
+    case 2: launch_allow_scan<2>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
+    default: launch_allow_scan<4>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
   }
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;

@@ -149,27 +149,32 @@ int pull_state(fvdb_graph* g, BuildState* st) {
 
 // The construction kernels are instantiated per 128-dim block count NB, FULL (no bounds checks) for the BASELINE
 // dimensions 384 and 768, and, the insert pair, per form of the insert's `visited` (HASH: kernels_graph_build.h,
-// Visited<>).  Every instantiation of one template has the same signature, so choosing one is a lookup.
+// Visited<>), and per row element (float, half_t).  Every instantiation of one template has the same signature, so
+// choosing one is a lookup.
 struct BuildKernels {
   decltype(&hnsw_insert_search_kernel<3, true, false>) search;
   decltype(&hnsw_insert_commit_kernel<3, true, false>) commit;
   decltype(&graph_edge_dist_kernel<3, true>) edge_dist;
 };
-template <int NB, bool FULL>
-BuildKernels build_kernels_of(bool hashed) {
-  if (hashed) return {hnsw_insert_search_kernel<NB, FULL, true>, hnsw_insert_commit_kernel<NB, FULL, true>, graph_edge_dist_kernel<NB, FULL>};
-  return {hnsw_insert_search_kernel<NB, FULL, false>, hnsw_insert_commit_kernel<NB, FULL, false>, graph_edge_dist_kernel<NB, FULL>};
+template <int NB, bool FULL, typename RT>
+BuildKernels build_kernels_rows(bool hashed) {
+  if (hashed) return {hnsw_insert_search_kernel<NB, FULL, true, RT>, hnsw_insert_commit_kernel<NB, FULL, true, RT>, graph_edge_dist_kernel<NB, FULL, RT>};
+  return {hnsw_insert_search_kernel<NB, FULL, false, RT>, hnsw_insert_commit_kernel<NB, FULL, false, RT>, graph_edge_dist_kernel<NB, FULL, RT>};
 }
-BuildKernels build_kernels(uint32_t dpad, bool hashed) {
-  const uint32_t nb128 = (dpad + 127) / 128;
-  if (dpad == 384) return build_kernels_of<3, true>(hashed);
-  if (dpad == 768) return build_kernels_of<6, true>(hashed);
-  if (nb128 == 1) return build_kernels_of<1, false>(hashed);
-  if (nb128 == 2) return build_kernels_of<2, false>(hashed);
-  if (nb128 == 3) return build_kernels_of<3, false>(hashed);
-  if (nb128 == 4) return build_kernels_of<4, false>(hashed);
-  if (nb128 <= 6) return build_kernels_of<6, false>(hashed);
-  return build_kernels_of<8, false>(hashed);
+template <int NB, bool FULL>
+BuildKernels build_kernels_of(const fvdb_store* s, bool hashed) {
+  return s->f16() ? build_kernels_rows<NB, FULL, half_t>(hashed) : build_kernels_rows<NB, FULL, float>(hashed);
+}
+BuildKernels build_kernels(const fvdb_store* s, bool hashed) {
+  const uint32_t dpad = s->dpad, nb128 = (dpad + 127) / 128;
+  if (dpad == 384) return build_kernels_of<3, true>(s, hashed);
+  if (dpad == 768) return build_kernels_of<6, true>(s, hashed);
+  if (nb128 == 1) return build_kernels_of<1, false>(s, hashed);
+  if (nb128 == 2) return build_kernels_of<2, false>(s, hashed);
+  if (nb128 == 3) return build_kernels_of<3, false>(s, hashed);
+  if (nb128 == 4) return build_kernels_of<4, false>(s, hashed);
+  if (nb128 <= 6) return build_kernels_of<6, false>(s, hashed);
+  return build_kernels_of<8, false>(s, hashed);
 }
 
 // What fvdb_graph_insert_linked would put in LDS for this graph now.  The fixed tables come first; `visited` and the
@@ -240,7 +245,7 @@ int edge_dist(fvdb_graph* g, const uint32_t* codes_dev, const uint32_t* owner_de
   fvdb_ctx* ctx = g->store->ctx;
   if (n_rows == 0) return FVDB_OK;
   const size_t lds = 4 * (size_t)kTileRows * kScoreStride * 4;
-  hipLaunchKernelGGL(build_kernels(g->store->dpad, false).edge_dist, dim3((n_rows + 3) / 4), dim3(256), lds, ctx->stream, build_view(g), codes_dev,
+  hipLaunchKernelGGL(build_kernels(g->store, false).edge_dist, dim3((n_rows + 3) / 4), dim3(256), lds, ctx->stream, build_view(g), codes_dev,
                      owner_dev, n_rows, upper_all ? 1u : 0u);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
@@ -426,22 +431,29 @@ void fold_insert(fvdb_graph* g, const InsertPlan& plan, const BuildState& st, ui
 }
 
 // The traversal kernels: the sorted-register kernel per (128-dim blocks NB, rows per scoring round R, byte map or bitmap
-// as `visited`), the exact-heap kernel per place of its `nearest` heap.
+// as `visited`, row element), the exact-heap kernel per place of its `nearest` heap and row element.  The rows per round
+// are the f32 table's for fp16 rows too: nothing has been measured that would justify another.
 using FastKernel = decltype(&hnsw_search_fast_kernel<3, 16, true>);
+using ExactKernel = decltype(&hnsw_search_kernel<true>);
 template <int NB, int R>
-FastKernel fast_kernel_of(bool bytemap) {
+FastKernel fast_kernel_of(bool bytemap, bool f16) {
+  if (f16) return bytemap ? hnsw_search_fast_kernel<NB, R, true, half_t> : hnsw_search_fast_kernel<NB, R, false, half_t>;
   return bytemap ? hnsw_search_fast_kernel<NB, R, true> : hnsw_search_fast_kernel<NB, R, false>;
 }
-FastKernel fast_kernel(uint32_t nb128, int R, bool bytemap) {
+FastKernel fast_kernel(uint32_t nb128, int R, bool bytemap, bool f16) {
   switch (nb128) {
-    case 1: return fast_kernel_of<1, 16>(bytemap);
-    case 2: return fast_kernel_of<2, 16>(bytemap);
-    case 3: return R == 8 ? fast_kernel_of<3, 8>(bytemap) : R == 12 ? fast_kernel_of<3, 12>(bytemap) : fast_kernel_of<3, 16>(bytemap);
-    case 4: return fast_kernel_of<4, 12>(bytemap);
+    case 1: return fast_kernel_of<1, 16>(bytemap, f16);
+    case 2: return fast_kernel_of<2, 16>(bytemap, f16);
+    case 3: return R == 8 ? fast_kernel_of<3, 8>(bytemap, f16) : R == 12 ? fast_kernel_of<3, 12>(bytemap, f16) : fast_kernel_of<3, 16>(bytemap, f16);
+    case 4: return fast_kernel_of<4, 12>(bytemap, f16);
     case 5:
-    case 6: return fast_kernel_of<6, 8>(bytemap);
-    default: return fast_kernel_of<8, 6>(bytemap);
+    case 6: return fast_kernel_of<6, 8>(bytemap, f16);
+    default: return fast_kernel_of<8, 6>(bytemap, f16);
   }
+}
+ExactKernel exact_kernel(bool rh, bool f16) {
+  if (f16) return rh ? hnsw_search_kernel<true, half_t> : hnsw_search_kernel<false, half_t>;
+  return rh ? hnsw_search_kernel<true> : hnsw_search_kernel<false>;
 }
 
 // What one traversal launch works with: the slot's scratch and its numbers (search_scratch), the kernel (search_kernel).
@@ -451,7 +463,7 @@ struct SearchPlan {
   size_t lds;         // dynamic LDS of a workgroup: of the exact-heap search first, then of the kernel chosen
   uint32_t wave_lds;  // the sorted-register kernel's share of it per query (4 queries to a workgroup)
   FastKernel fast;    // the sorted-register kernel, or
-  decltype(&hnsw_search_kernel<true>) exact;  // the exact-heap kernel, one query per workgroup;
+  ExactKernel exact;  // the exact-heap kernel, one query per workgroup;
   bool rh;            // its `nearest` in registers (ef <= 63): the candidates heap may continue in the HBM spill
 };
 
@@ -502,7 +514,7 @@ int search_kernel(fvdb_graph* g, fvdb_ctx* ctx, uint32_t ef, SearchPlan* sp) {
   static const int fast_r = getenv("FVDB_GRAPH_FAST_R") ? atoi(getenv("FVDB_GRAPH_FAST_R")) : 0;
   const uint32_t nb128 = (g->store->dpad + 127) / 128;
   if (no_fast || !sp->rh || nb128 > 8 || g->n >= 0x80000000u) {
-    sp->exact = sp->rh ? hnsw_search_kernel<true> : hnsw_search_kernel<false>;
+    sp->exact = exact_kernel(sp->rh, g->store->f16());
     return FVDB_OK;
   }
   int R = nb128 <= 3 ? 16 : (nb128 == 4 ? 12 : (nb128 <= 6 ? 8 : 6));  // rows per scoring round: registers R*NB*2
@@ -510,7 +522,7 @@ int search_kernel(fvdb_graph* g, fvdb_ctx* ctx, uint32_t ef, SearchPlan* sp) {
   sp->wave_lds = (uint32_t)((std::max(graph_fast_lds_bytes((uint32_t)R), sp->lds) + 15) & ~(size_t)15);
   sp->lds = 4 * (size_t)sp->wave_lds;
   if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
-  sp->fast = fast_kernel(nb128, R, sp->bytemap);
+  sp->fast = fast_kernel(nb128, R, sp->bytemap, g->store->f16());
   return FVDB_OK;
 }
 
@@ -903,7 +915,7 @@ int fvdb_graph_insert_linked(fvdb_graph* g, uint32_t first, uint32_t n, uint32_t
   HIPCHK(ctx, g->d_chg.ensure((size_t)kChgCap * 4 * 4));
   if (n >= 8)  // (a call that cannot speculate skips this)
     HIPCHK(ctx, hipMemsetAsync(g->d_spec.p, 0, (size_t)sched.Kmax * kSpecWords * 4, ctx->stream));  // no stale "usable" flags
-  const BuildKernels kernels = build_kernels(s->dpad, plan.repr == 2);
+  const BuildKernels kernels = build_kernels(s, plan.repr == 2);
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kernels.commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
   HIPCHK(ctx, hipFuncSetAttribute((const void*)kernels.search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
   BuildView v = build_view(g, ef_construction, plan);
@@ -1218,7 +1230,7 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
     // every allocation precedes the first change
     n_cap = n_out + n_out / 8 + 1024;
     u_cap = u_out + u_out / 8 + 1024;
-    const size_t row_bytes = (size_t)s->dpad * 4;
+    const size_t row_bytes = s->row_bytes();
     const size_t sizes[10] = {(size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4,
                               (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4, (size_t)n_cap * 4, (size_t)u_cap * 4,
                               (size_t)n_cap * row_bytes};
@@ -1252,7 +1264,10 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
   GM_TRY(hipEventRecord(ev.ev[4], st));
   // stage 3: store rows, one wave per destination row
   if (!keep_rows && n_out) {
-    hipLaunchKernelGGL(gm_move_kernel, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float4*)s->data, n, s->dpad / 4, n_out, (float4*)f.rows.p);
+    if (s->f16())  // a half row is dpad * 2 bytes: whole 8-byte chunks
+      hipLaunchKernelGGL(gm_move_kernel<float2>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float2*)s->data, n, s->dpad / 4, n_out, (float2*)f.rows.p);
+    else
+      hipLaunchKernelGGL(gm_move_kernel<float4>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float4*)s->data, n, s->dpad / 4, n_out, (float4*)f.rows.p);
     GM_TRY(hipGetLastError());
   }
   GM_TRY(hipEventRecord(ev.ev[5], st));
@@ -1270,9 +1285,9 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
   } else {
     info.nodes_out = n_out;
     info.rows_reclaimed = n - n_out;
-    info.bytes_reclaimed = (uint64_t)(n - n_out) * ((uint64_t)s->dpad * 4 + (uint64_t)g->stride0 * 8 + 16) +
+    info.bytes_reclaimed = (uint64_t)(n - n_out) * ((uint64_t)s->row_bytes() + (uint64_t)g->stride0 * 8 + 16) +
                            (uint64_t)(u_rows - u_out) * ((uint64_t)g->strideU * 8 + 4);
-    info.move_bytes = 2ull * n_out * s->dpad * 4;
+    info.move_bytes = 2ull * n_out * s->row_bytes();
     std::swap(g->d_level, f.level);
     std::swap(g->d_deleted, f.deleted);
     std::swap(g->d_ubase, f.ubase);
@@ -1283,8 +1298,8 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
     std::swap(g->d_stamp0, f.stamp0);
     std::swap(g->d_stampU, f.stampU);
     // the store adopts the compacted rows: scorers read store->data at every launch
-    float* old_rows = s->data;
-    s->data = (float*)f.rows.p;
+    void* old_rows = s->data;
+    s->data = f.rows.p;
     s->cap = n_cap;
     s->rows = n_out;
     f.rows.p = old_rows;

@@ -2828,17 +2828,23 @@ int fvdb_merge_search_results(fvdb_ctx* ctx, const uint64_t* ids, const float* d
 // row store + candidate scoring
 // =============================================================================================
 int fvdb_store_create(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, fvdb_store** out) {
+  return fvdb_store_create_ex(ctx, d, capacity_rows, FVDB_F32, out);
+}
+
+int fvdb_store_create_ex(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, int row_dtype, fvdb_store** out) {
   if (!ctx || !out) return FVDB_E_INVALID;
   *out = nullptr;
   if (d == 0) FAIL(ctx, FVDB_E_INVALID, "d must be > 0");
+  if (row_dtype != FVDB_F32 && row_dtype != FVDB_F16) FAIL(ctx, FVDB_E_INVALID, "row_dtype must be FVDB_F32 or FVDB_F16");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   fvdb_store* s = new (std::nothrow) fvdb_store();
   if (!s) return FVDB_E_OOM;
   s->ctx = ctx;
   s->d = d;
-  s->dpad = ((d + 3) / 4) * 4;
+  s->dpad = ((d + 3) / 4) * 4;  // either element: the row stride stays a multiple of 8 bytes
+  s->dtype = (uint32_t)row_dtype;
   s->cap = std::max<uint64_t>(capacity_rows, 64);
-  hipError_t e = hipMalloc(&s->data, s->cap * s->dpad * 4);
+  hipError_t e = hipMalloc(&s->data, s->cap * s->row_bytes());
   if (e != hipSuccess) {
     delete s;
     FAIL(ctx, FVDB_E_OOM, "store allocation failed");
@@ -2860,6 +2866,8 @@ void fvdb_store_destroy(fvdb_store* s) {
 }
 
 uint64_t fvdb_store_rows(fvdb_store* s) { return s->rows; }
+int fvdb_store_dtype(fvdb_store* s) { return (int)s->dtype; }
+uint64_t fvdb_store_bytes(fvdb_store* s) { return s->rows * (uint64_t)s->row_bytes(); }
 
 int fvdb_store_append(fvdb_store* s, const float* rows, uint64_t n, uint64_t* first_row) {
   fvdb_ctx* ctx = s->ctx;
@@ -2871,17 +2879,24 @@ int fvdb_store_append(fvdb_store* s, const float* rows, uint64_t n, uint64_t* fi
   if (s->rows + n >= 0xFFFFFFFFull) FAIL(ctx, FVDB_E_UNSUPPORTED, "store limited to 2^32-1 rows");
   if (s->rows + n > s->cap) {
     uint64_t ncap = std::max<uint64_t>(s->rows + n, s->cap + s->cap / 2);
-    float* nd = nullptr;
-    HIPCHK(ctx, hipMalloc(&nd, ncap * s->dpad * 4));
+    void* nd = nullptr;
+    HIPCHK(ctx, hipMalloc(&nd, ncap * s->row_bytes()));
     if (s->rows)
-      HIPCHK(ctx, hipMemcpyAsync(nd, s->data, s->rows * s->dpad * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(nd, s->data, s->rows * s->row_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(s->data);
     s->data = nd;
     s->cap = ncap;
   }
-  float* dst = s->data + s->rows * s->dpad;
-  if (s->d == s->dpad) {
+  void* dstv = (char*)s->data + s->rows * s->row_bytes();
+  float* dst = (float*)dstv;
+  if (s->f16()) {  // rounded to nearest even on the device, pads zero
+    HIPCHK(ctx, s->s_in.ensure(n * s->d * 4));
+    HIPCHK(ctx, hipMemcpyAsync(s->s_in.p, rows, n * s->d * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pad_rows_f16_kernel, dim3(cdiv(n * s->dpad, 256)), dim3(256), 0, ctx->stream, s->s_in.as<float>(),
+                       s->d, s->dpad, n, (half_t*)dstv);
+    HIPCHK(ctx, hipGetLastError());
+  } else if (s->d == s->dpad) {
     HIPCHK(ctx, hipMemcpyAsync(dst, rows, n * s->d * 4, hipMemcpyHostToDevice, ctx->stream));
   } else {
     HIPCHK(ctx, s->s_in.ensure(n * s->d * 4));
@@ -2897,7 +2912,14 @@ int fvdb_store_append(fvdb_store* s, const float* rows, uint64_t n, uint64_t* fi
 int fvdb_store_get(fvdb_store* s, uint64_t row, float* out) {
   fvdb_ctx* ctx = s->ctx;
   if (row >= s->rows) FAIL(ctx, FVDB_E_NOT_FOUND, "row out of range");
-  HIPCHK(ctx, hipMemcpyAsync(out, s->data + row * s->dpad, (size_t)s->d * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (s->f16()) {  // widened on the host: exact
+    std::vector<_Float16> h(s->d);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), (const char*)s->data + row * s->row_bytes(), (size_t)s->d * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t j = 0; j < s->d; ++j) out[j] = (float)h[j];
+    return FVDB_OK;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(out, (const float*)s->data + row * s->dpad, (size_t)s->d * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FVDB_OK;
 }
@@ -2924,8 +2946,12 @@ int fvdb_score_candidates(fvdb_store* s, const float* q, uint32_t B, const uint3
   }
   qd = s->s_q.as<float>();
   HIPCHK(ctx, hipMemcpyAsync(s->s_cand.p, cand, (size_t)B * C * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(score_candidates_kernel, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, ctx->stream, s->data,
-                     s->dpad, qd, s->s_cand.as<uint32_t>(), B, C, C, s->s_out.as<float>());
+  if (s->f16())
+    hipLaunchKernelGGL(score_candidates_kernel<half_t>, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, ctx->stream, (const half_t*)s->data,
+                       s->dpad, qd, s->s_cand.as<uint32_t>(), B, C, C, s->s_out.as<float>());
+  else
+    hipLaunchKernelGGL(score_candidates_kernel<float>, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, ctx->stream, (const float*)s->data,
+                       s->dpad, qd, s->s_cand.as<uint32_t>(), B, C, C, s->s_out.as<float>());
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, s->s_out.p, (size_t)B * C * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -3000,8 +3026,12 @@ int fvdb_scorer_set_query_rows(fvdb_scorer* sc, const uint32_t* rows, uint32_t B
     if (rows[i] >= s->rows) FAIL(ctx, FVDB_E_NOT_FOUND, "query row out of range");
   HIPCHK(ctx, sc->s_rows.ensure((size_t)B * 4));
   HIPCHK(ctx, hipMemcpyAsync(sc->s_rows.p, rows, (size_t)B * 4, hipMemcpyHostToDevice, sc->stream));
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv((uint64_t)B * s->dpad, 256)), dim3(256), 0, sc->stream, s->data,
-                     sc->s_rows.as<uint32_t>(), s->dpad, B, sc->d_q);
+  if (s->f16())
+    hipLaunchKernelGGL(gather_rows_kernel<half_t>, dim3(cdiv((uint64_t)B * s->dpad, 256)), dim3(256), 0, sc->stream, (const half_t*)s->data,
+                       sc->s_rows.as<uint32_t>(), s->dpad, B, sc->d_q);
+  else
+    hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(cdiv((uint64_t)B * s->dpad, 256)), dim3(256), 0, sc->stream, (const float*)s->data,
+                       sc->s_rows.as<uint32_t>(), s->dpad, B, sc->d_q);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(sc->stream));
   return FVDB_OK;
@@ -3032,8 +3062,12 @@ int fvdb_scorer_launch(fvdb_scorer* sc, uint32_t B, uint32_t C) {
   if (B > sc->max_B || C > sc->max_C) FAIL(ctx, FVDB_E_INVALID, "shape above scorer capacity");
   if (B == 0 || C == 0) return FVDB_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return FVDB_E_HIP;  // current device is per host thread
-  hipLaunchKernelGGL(score_candidates_kernel, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, sc->stream, s->data,
-                     s->dpad, sc->d_q, sc->d_cand, B, C, sc->max_C, sc->d_dist);
+  if (s->f16())
+    hipLaunchKernelGGL(score_candidates_kernel<half_t>, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, sc->stream, (const half_t*)s->data,
+                       s->dpad, sc->d_q, sc->d_cand, B, C, sc->max_C, sc->d_dist);
+  else
+    hipLaunchKernelGGL(score_candidates_kernel<float>, dim3(cdiv((uint64_t)B * C, 256)), dim3(256), 0, sc->stream, (const float*)s->data,
+                       s->dpad, sc->d_q, sc->d_cand, B, C, sc->max_C, sc->d_dist);
   if (hipGetLastError() != hipSuccess) return FVDB_E_HIP;
   return FVDB_OK;
 }

@@ -87,7 +87,10 @@ struct fvdb_store {
   fvdb_ctx* ctx = nullptr;
   uint32_t d = 0, dpad = 0;
   uint64_t rows = 0, cap = 0;
-  float* data = nullptr;  // [cap][dpad]
+  uint32_t dtype = FVDB_F32;  // element of a stored row: FVDB_F32, or FVDB_F16 (rounded to nearest even at append)
+  void* data = nullptr;       // [cap][dpad] of it
+  bool f16() const { return dtype == FVDB_F16; }
+  size_t row_bytes() const { return (size_t)dpad * (f16() ? 2 : 4); }
   DBuf s_q, s_cand, s_out, s_in;
 };
 

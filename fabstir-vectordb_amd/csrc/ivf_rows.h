@@ -90,8 +90,12 @@ int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_
   HIPCHK(ctx, hipMemcpyAsync(ivf->s_slots.p, rows, n * 4, hipMemcpyHostToDevice, ctx->stream));
   for (uint64_t o = 0; o < n; o += kGatherStep) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
-    hipLaunchKernelGGL(store_gather_rows_kernel, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, s->data, s->dpad,
-                       ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
+    if (s->f16())  // widened into the f32 staging: the lists round again, to the same values, if they are fp16 too
+      hipLaunchKernelGGL(store_gather_rows_kernel<half_t>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const half_t*)s->data, s->dpad,
+                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
+    else
+      hipLaunchKernelGGL(store_gather_rows_kernel<float>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const float*)s->data, s->dpad,
+                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
   }
   HIPCHK(ctx, hipGetLastError());
   ivf->m_info.ms_gather += clock.end();  // waits: `rows` is the caller's, and s_slots is written again by the append

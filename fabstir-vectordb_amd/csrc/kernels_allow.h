@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void allow_graph_write_kernel(const uint32_t* 
 // cache.  A wave scores 64 nodes per round with score_rows_wave (the traversal's arithmetic: sub, mul, sequential add,
 // sqrt) and keeps its k best by (distance bits, position in the node list): position order is node-index order.
 struct AllowScanArgs {
-  const float* rows;       // the store: [node][dpad]
+  const void* rows;        // the store: [node][dpad] of the kernel's RT (float or half_t)
   const float* queries;    // [B][dpad]
   const uint32_t* nodes;   // [n_nodes] ascending
   uint32_t dpad, n_nodes, B, k;
@@ -131,7 +131,7 @@ struct AllowScanArgs {
   uint64_t* part;              // [slices][B][k] keys, ~0 = none
 };
 
-template <int KR>
+template <int KR, typename RT = float>
 __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) {
   __shared__ __attribute__((aligned(16))) float s_tile[4][kScoreTileFloats];
   const int lane = threadIdx.x & 63;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) 
     const uint32_t pos = e0 + (uint32_t)lane;
     const bool have = (uint32_t)lane < cnt;
     const uint32_t node = have ? a.nodes[pos] : 0u;
-    const float d = score_rows_wave(a.rows, a.dpad, qrow, node, cnt, s_tile[w], lane);
+    const float d = score_rows_wave((const RT*)a.rows, a.dpad, qrow, node, cnt, s_tile[w], lane);
     offer<KR>(tk, a.k, have ? __float_as_uint(d) : kInf32, pos, th, tl, lane);
   }
   uint64_t* out = a.part + ((size_t)s * a.B + q) * a.k;

@@ -16,6 +16,7 @@
 // first, and only queries in which two heap members met with equal distances (or ef > 64, or d > 1024) come here.
 #pragma once
 #include "common.h"
+#include "row_types.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -23,7 +24,7 @@
 namespace fvdb {
 
 struct GraphView {
-  const float* rows;          // [n][dpad] row-major vectors (fvdb_store)
+  const void* rows;           // [n][dpad] row-major vectors (fvdb_store): float or half_t, the kernel's RT
   const uint32_t* level;      // [n]
   const uint32_t* deleted;    // [n] 0/1
   // Adjacency, fixed stride on every layer so that an insert rewrites only the rows it touches (kernels_graph_build.h,
@@ -264,23 +265,29 @@ __device__ __forceinline__ HItem lds_pop_parallel(HItem* h, uint32_t& n, int lan
 // by one `global_load_lds_dword` (data discarded into an LDS scratch word per lane, no VGPR held), np*12 loads in
 // flight together.  Each lane then streams its own row (row-major, 16 bytes per load, 32 dims per batch, two
 // batch ahead) out of L2; the query sits in LDS and is read with broadcast loads.
+// RT: the stored row's element.  fp16 rows are loaded four elements (8 bytes) at a time and widened exactly as the fold
+// reaches them; a 128-byte line then holds 64 dims, and everything else is the same.
+template <typename RT>
 __device__ __forceinline__ void score_pending(const GraphView& g, const float* q_lds, float* pf_scratch,
                                               const uint32_t* pending, float* pdist, uint32_t np, int lane) {
   const uint32_t dpad = g.dpad;
-  const uint32_t lpr = (dpad + 31) >> 5, nlines = np * lpr;  // 32 floats per line
+  using Quad = typename RowVec<RT>::Quad;
+  const RT* rows = (const RT*)g.rows;
+  constexpr uint32_t kPerLine = 128 / sizeof(RT);  // row elements per 128-byte line
+  const uint32_t lpr = (dpad + kPerLine - 1) / kPerLine, nlines = np * lpr;
   for (uint32_t l = lane; l < nlines; l += 64) {
     const uint32_t r = l / lpr, ln = l - r * lpr;
-    const float* src = g.rows + (size_t)pending[r] * dpad + ln * 32;
+    const RT* src = rows + (size_t)pending[r] * dpad + ln * kPerLine;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                      (__attribute__((address_space(3))) void*)pf_scratch, 4, 0, 0);
   }
   if ((uint32_t)lane < np) {
-    const float* row = g.rows + (size_t)pending[lane] * dpad;
-    const float4* xp = (const float4*)row;
+    const RT* row = rows + (size_t)pending[lane] * dpad;
+    const Quad* xp = (const Quad*)row;
     const float4* qp = (const float4*)q_lds;  // same address in every lane: LDS broadcast reads
     const uint32_t nb = dpad >> 5;            // whole 32-dim batches
     float acc = 0.0f;
-    auto issue = [&](uint32_t bi, float4 (&dst)[8]) {
+    auto issue = [&](uint32_t bi, Quad (&dst)[8]) {
       const uint32_t bb = bi < nb ? bi : nb - 1;  // past the end: re-request the last batch (keeps counts static)
 #pragma unroll
       for (int i = 0; i < 8; ++i) dst[i] = xp[bb * 8 + i];
@@ -290,14 +297,15 @@ __device__ __forceinline__ void score_pending(const GraphView& g, const float* q
 #pragma unroll
       for (int i = 0; i < 8; ++i) dst[i] = qp[bb * 8 + i];
     };
-    auto fold = [&](const float4 (&src)[8], const float4 (&qv)[8]) {
+    auto fold = [&](const Quad (&src)[8], const float4 (&qv)[8]) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
+        const float4 xv = row_widen(src[i]);
         float t;
-        t = qv[i].x - src[i].x; acc = acc + t * t;
-        t = qv[i].y - src[i].y; acc = acc + t * t;
-        t = qv[i].z - src[i].z; acc = acc + t * t;
-        t = qv[i].w - src[i].w; acc = acc + t * t;
+        t = qv[i].x - xv.x; acc = acc + t * t;
+        t = qv[i].y - xv.y; acc = acc + t * t;
+        t = qv[i].z - xv.z; acc = acc + t * t;
+        t = qv[i].w - xv.w; acc = acc + t * t;
       }
     };
     uint32_t done = 0;
@@ -306,7 +314,8 @@ __device__ __forceinline__ void score_pending(const GraphView& g, const float* q
       // two batches per trip so both buffer indices are static.  Kept this lean on purpose: at <= 152 VGPRs two
       // traversal waves AND a list-scan wave fit one SIMD, so the IVF chain of the same step (and the traversal of
       // the next batch in flight) run beside this kernel instead of queueing behind it.
-      float4 r0[8], r1[8], qa[8];
+      Quad r0[8], r1[8];
+      float4 qa[8];
       const uint32_t nb2 = nb - nb % 2;
       issue(0, r0);
       for (uint32_t bi = 0; bi < nb2; bi += 2) {
@@ -324,13 +333,14 @@ __device__ __forceinline__ void score_pending(const GraphView& g, const float* q
       done = nb2;
     }
     for (uint32_t bi = done; bi < nb; ++bi) {
-      float4 t8[8], q8[8];
+      Quad t8[8];
+      float4 q8[8];
       issue(bi, t8);
       issue_q(bi, q8);
       fold(t8, q8);
     }
     for (uint32_t j = nb << 5; j < dpad; j += 4) {
-      const float4 xv = *(const float4*)(row + j);
+      const float4 xv = row_widen(*(const Quad*)(row + j));
       const float4 qv = *(const float4*)(q_lds + j);
       float t;
       t = qv.x - xv.x; acc = acc + t * t;
@@ -356,7 +366,7 @@ __host__ __device__ inline size_t graph_lds_bytes(uint32_t dpad, uint32_t ef, ui
 // The whole search of query `b` by the calling wavefront, with the reference's heaps restated (exact on distance ties).
 // `lds`: graph_lds_bytes(dpad, ef, cand_cap) bytes private to the wave.
 // RH: `nearest` in registers + wave-parallel heap pushes (ef <= 63); otherwise both heaps in LDS, driven by lane 0.
-template <bool RH>
+template <bool RH, typename RT>
 __device__ __forceinline__ void hnsw_search_exact_body(const GraphView& g, const float* __restrict__ queries, uint32_t b, uint32_t k,
                                                        uint32_t ef_final, uint32_t cand_cap, uint32_t* __restrict__ vis /* this query's bitmap, zero on entry */,
                                                        uint32_t words, uint32_t* __restrict__ tch /* its visited log */, uint32_t tcap,
@@ -384,7 +394,7 @@ __device__ __forceinline__ void hnsw_search_exact_body(const GraphView& g, const
   if (lane == 0) pending[0] = g.entry;
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
-  score_pending(g, q_lds, pf_scratch, pending, pdist, 1, lane);
+  score_pending<RT>(g, q_lds, pf_scratch, pending, pdist, 1, lane);
   uint32_t n_res = 1;
   if (lane == 0) res[0] = HItem{g.entry, pdist[0]};
   __builtin_amdgcn_s_waitcnt(0);
@@ -486,7 +496,7 @@ __device__ __forceinline__ void hnsw_search_exact_body(const GraphView& g, const
       hops_done += 1;
       rows_scored += np;
       if (np) {
-        score_pending(g, q_lds, pf_scratch, pending, pdist, np, lane);
+        score_pending<RT>(g, q_lds, pf_scratch, pending, pdist, np, lane);
         STAMP(t3s);
         STAMP_ADD(2, t2s, t3s);
 #ifdef FVDB_GRAPH_STAMPS
@@ -633,7 +643,7 @@ __device__ __forceinline__ void hnsw_search_exact_body(const GraphView& g, const
   }
 }
 
-template <bool RH>
+template <bool RH, typename RT = float>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 3))) void hnsw_search_kernel(const GraphView g, const float* __restrict__ queries,
                                                          uint32_t B, uint32_t k, uint32_t ef_final, uint32_t cand_cap,
                                                          uint32_t* __restrict__ visited /* [B][words] zero on entry */,
@@ -645,7 +655,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 3))) void
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const uint32_t b = blockIdx.x;
   if (b >= B) return;
-  hnsw_search_exact_body<RH>(g, queries, b, k, ef_final, cand_cap, visited + (size_t)b * words, words, touched + (size_t)b * tcap, tcap, out_nodes, out_dist, out_counts,
+  hnsw_search_exact_body<RH, RT>(g, queries, b, k, ef_final, cand_cap, visited + (size_t)b * words, words, touched + (size_t)b * tcap, tcap, out_nodes, out_dist, out_counts,
                              out_status, lds, (int)threadIdx.x, spill ? spill + (size_t)b * spill_cap : nullptr, spill ? spill_cap : 0u);
 }
 

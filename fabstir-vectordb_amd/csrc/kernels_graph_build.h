@@ -91,7 +91,7 @@ struct BuildState {
 };
 
 struct BuildView {
-  const float* rows;  // [n][dpad]
+  const void* rows;  // [n][dpad]: float or half_t, the kernel's RT
   uint32_t dpad;
   const uint32_t* level;
   const uint32_t* deleted;
@@ -166,8 +166,8 @@ struct BuildRows {
 };
 
 // `cnt` (1..BuildRows<NB>::kMax) rows, the smallest straight-line form that holds them
-template <int NB, bool FULL>
-__device__ __forceinline__ float score_upto16(const float* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
+template <int NB, bool FULL, typename RT>
+__device__ __forceinline__ float score_upto16(const RT* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
                                               uint32_t cnt, float* tile, int lane) {
   if (NB <= 4 && cnt > 8) return score_fixed<NB, (NB <= 4 ? 16 : 8), FULL, 1>(rows, dpad, q2, pn, cnt, tile, 0, lane);
   if (cnt > 4) return score_fixed<NB, 8, FULL, 1>(rows, dpad, q2, pn, cnt, tile, 0, lane);
@@ -332,7 +332,7 @@ __device__ __forceinline__ void fetch_lists(const BuildView& g, BuildCtx& c, uin
 }
 
 // Score the listed rows on all waves; distances land in dist[slot][position].
-template <int NB, bool FULL>
+template <int NB, bool FULL, typename RT>
 __device__ __forceinline__ void score_lists(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t U) {
   if (U == 0) return;
   const uint32_t per = (U + kBuildWaves - 1) / kBuildWaves;
@@ -341,7 +341,7 @@ __device__ __forceinline__ void score_lists(const BuildView& g, BuildCtx& c, con
     const uint32_t cnt = min(rc, U - base);
     const uint32_t code = (uint32_t)c.lane < cnt ? (uint32_t)c.slist[base + c.lane] : 0u;
     const uint32_t pn = (uint32_t)c.lane < cnt ? (c.nbr[code] & 0x7FFFFFFFu) : 0u;
-    const float d = score_upto16<NB, FULL>(g.rows, g.dpad, q2, pn, cnt, c.tile, c.lane);
+    const float d = score_upto16<NB, FULL>((const RT*)g.rows, g.dpad, q2, pn, cnt, c.tile, c.lane);
     if ((uint32_t)c.lane < cnt) c.dist[code] = d;
   }
 }
@@ -353,7 +353,7 @@ __device__ __forceinline__ void score_lists(const BuildView& g, BuildCtx& c, con
 // smallest distance below the current one.  Returns (node, distance) in every thread.
 // false (hashed visited set only): the walk met more nodes than the set holds (MS_OVER = 2).
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT>
 __device__ __forceinline__ bool greedy_layer(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t& cur,
                                              float& cur_d, uint32_t* elog) {
   Visited<HASH>::clear(g, c);
@@ -373,7 +373,7 @@ __device__ __forceinline__ bool greedy_layer(const BuildView& g, BuildCtx& c, co
     fetch_lists<HASH>(g, c, 1, layer);
     __syncthreads();
     const uint32_t U = c.misc[MS_NSCORE];
-    score_lists<NB, FULL>(g, c, q2, U);
+    score_lists<NB, FULL, RT>(g, c, q2, U);
     __syncthreads();
     if (c.wave == 0) {
       const int lane = c.lane;
@@ -487,7 +487,7 @@ __device__ __forceinline__ void near_reg_max(const NearSet& h, int r, uint32_t e
 // goes on.  A list is fetched once: it stays in the table until its candidate is expanded or falls out of the kSpec
 // nearest.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL, bool EXACT, bool HASH>
+template <int NB, bool FULL, bool EXACT, bool HASH, typename RT>
 __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t start,
                                                 float start_d, uint32_t* elog, uint32_t* stat) {
   const int lane = c.lane;
@@ -821,7 +821,7 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
     __syncthreads();
     BSTAMP(t2);
     const uint32_t U = c.misc[MS_NSCORE];
-    score_lists<NB, FULL>(g, c, q2, U);
+    score_lists<NB, FULL, RT>(g, c, q2, U);
     __syncthreads();
     BSTAMP(t3);
     BSTAMP_ADD(g, 0, t0, t1);
@@ -889,12 +889,12 @@ __device__ __forceinline__ bool ef_search_layer(const BuildView& g, BuildCtx& c,
 
 // search_layer(ef) with the tie rule: sorted registers first, the restated heaps when two members tie.
 // false: the restated `candidates` heap outgrew its LDS slots, or the hashed visited set filled (host path for this node).
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT>
 __device__ __forceinline__ bool ef_search(const BuildView& g, BuildCtx& c, const float2 (&q2)[NB], uint32_t layer, uint32_t start,
                                           float start_d, uint32_t* elog, uint32_t* stat, bool exact_on_tie) {
   const uint32_t log0 = c.misc[MS_NLOG];
   if (g.ef <= (uint32_t)kNearRegs * 64u && !g.exact_first) {
-    if (ef_search_layer<NB, FULL, false, HASH>(g, c, q2, layer, start, start_d, elog, stat)) return true;
+    if (ef_search_layer<NB, FULL, false, HASH, RT>(g, c, q2, layer, start, start_d, elog, stat)) return true;
     if (HASH && c.misc[MS_OVER] == 2) return false;  // the restated heaps would meet the same nodes
     if (threadIdx.x == 0 && stat) stat[3] += 1;
     if (!exact_on_tie) return false;  // a speculation far down the batch: not worth twice the time of the others
@@ -902,7 +902,7 @@ __device__ __forceinline__ bool ef_search(const BuildView& g, BuildCtx& c, const
     __syncthreads();
   }
   if (threadIdx.x == 0) c.misc[MS_ORDER] = 1;  // heaps with equal keys: the outcome depends on the order of the lists
-  return ef_search_layer<NB, FULL, true, HASH>(g, c, q2, layer, start, start_d, elog, stat);
+  return ef_search_layer<NB, FULL, true, HASH, RT>(g, c, q2, layer, start, start_d, elog, stat);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -912,7 +912,7 @@ __device__ __forceinline__ bool ef_search(const BuildView& g, BuildCtx& c, const
 // l + 1 rows only, so all of an insert's searches can run before any of its links are made.
 // Results -> res[layer]; false = host path needed.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT>
 __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c, uint32_t node, uint32_t level, uint32_t entry,
                                                 uint32_t entry_level, uint32_t* elog, uint32_t* stat, bool exact_on_tie = true,
                                                 int only_layer = -1 /* >= 0: the descent + that layer's search only */) {
@@ -920,7 +920,7 @@ __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c,
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const uint32_t j = (uint32_t)b * 128u + 2u * (uint32_t)c.lane;
-    q2[b] = j < g.dpad ? *(const float2*)(g.rows + (size_t)node * g.dpad + j) : make_float2(0.0f, 0.0f);
+    q2[b] = j < g.dpad ? row_pair_f32((const RT*)g.rows + (size_t)node * g.dpad, j) : make_float2(0.0f, 0.0f);
   }
   if (threadIdx.x == 0) {
     c.misc[MS_NLOG] = 0;
@@ -929,7 +929,7 @@ __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c,
   }
   // d(q, entry) (:277-281)
   if (c.wave == 0) {
-    const float d0 = score_fixed<NB, 4, FULL, 1>(g.rows, g.dpad, q2, entry, 1, c.tile, 0, c.lane);
+    const float d0 = score_fixed<NB, 4, FULL, 1>((const RT*)g.rows, g.dpad, q2, entry, 1, c.tile, 0, c.lane);
     if (c.lane == 0) c.misc[MS_CURD] = __float_as_uint(d0);
   }
   __syncthreads();
@@ -942,13 +942,13 @@ __device__ __forceinline__ bool insert_searches(const BuildView& g, BuildCtx& c,
   // the descent's expansions are logged once per insert: by the whole-insert call, or by the layer-0 call
   if (only_layer < 0 || (uint32_t)only_layer <= search_level)
     for (uint32_t lc = search_level + 1; lc-- > 0;)
-      if (!greedy_layer<NB, FULL, HASH>(g, c, q2, lc, cur, cur_d, only_layer <= 0 ? elog : nullptr)) return false;
+      if (!greedy_layer<NB, FULL, HASH, RT>(g, c, q2, lc, cur, cur_d, only_layer <= 0 ? elog : nullptr)) return false;
   BSTAMP(tg1);
   BSTAMP_ADD(g, 3, tg0, tg1);
   for (uint32_t lc = 0; lc <= level; ++lc) {
     if (only_layer >= 0 && lc != (uint32_t)only_layer) continue;
     const bool low = lc <= search_level;
-    if (!ef_search<NB, FULL, HASH>(g, c, q2, lc, low ? cur : entry, low ? cur_d : entry_d, elog, stat, exact_on_tie)) return false;
+    if (!ef_search<NB, FULL, HASH, RT>(g, c, q2, lc, low ? cur : entry, low ? cur_d : entry_d, elog, stat, exact_on_tie)) return false;
   }
   return true;
 }
@@ -1117,7 +1117,7 @@ __device__ __forceinline__ void insert_links(const BuildView& g, BuildCtx& c, ui
 //
 // Returns 0 (adopt) or the cause.  Uses the searches' scratch (dist / nbr / slist / cand), idle between two inserts.
 // ---------------------------------------------------------------------------------------------
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT>
 __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, BuildCtx& c, uint32_t node, uint32_t level, uint32_t tag,
                                                          const uint32_t* __restrict__ sp, const uint32_t* __restrict__ elog, const uint32_t* chg,
                                                              uint32_t strict /* A/B and bisecting: 1 any change is a conflict, 2 no second
@@ -1196,9 +1196,9 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const uint32_t j = (uint32_t)b * 128u + 2u * (uint32_t)c.lane;
-    q2[b] = j < g.dpad ? *(const float2*)(g.rows + (size_t)node * g.dpad + j) : make_float2(0.0f, 0.0f);
+    q2[b] = j < g.dpad ? row_pair_f32((const RT*)g.rows + (size_t)node * g.dpad, j) : make_float2(0.0f, 0.0f);
   }
-  score_lists<NB, FULL>(g, c, q2, nchk);  // dist[i] overwrites the touched-row list, which is no longer needed
+  score_lists<NB, FULL, RT>(g, c, q2, nchk);  // dist[i] overwrites the touched-row list, which is no longer needed
   __syncthreads();
   // ---- stage 1, one thread per check: the rule above.  Outcome in k_res[i]: state << 22 | a << 11 | b with
   //      0 x never entered the set, 1 x was inside over the expansions (k, b], 2 second look needed (below), 3 conflict
@@ -1358,7 +1358,7 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
       __syncthreads();
       const uint32_t nf = c.misc[MS_NSCORE];
       // (slist is rewritten: the checks' entries are i -> i, restored below)
-      score_lists<NB, FULL>(g, c, q2, nf);
+      score_lists<NB, FULL, RT>(g, c, q2, nf);
       __syncthreads();
       const float w = __uint_as_float(el[kLogCap + ta - 1]);
       if (threadIdx.x < nf && c.dist[kChkCap + threadIdx.x] < w) {
@@ -1383,7 +1383,7 @@ __device__ __forceinline__ uint32_t validate_speculation(const BuildView& g, Bui
 // Speculation: workgroup (b, l) runs the layer-l search of node first + cursor + b against the graph as it stands (the
 // searches of an insert's layers only share the greedy descent, which every one of them repeats: a node with levels
 // would otherwise take several times as long as its batch mates, and the slowest workgroup sets the launch's duration).
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT = float>
 __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(const BuildView g, uint32_t first, uint32_t n, uint32_t exact_positions,
                                                                               uint32_t tag, uint32_t* __restrict__ spec /* [grid.x][kSpecWords] */,
                                                                               uint32_t* __restrict__ elogs /* [grid.x][kBuildLayers][kLogWords] */) {
@@ -1403,7 +1403,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(co
   // speculations of a batch, the ones most likely to be adopted, do that; the others are left to the next batch
   // (`exact_positions`: the host raises it to the whole batch on data where ties are the rule, e.g. duplicate vectors)
   uint32_t tstat[4] = {0, 0, 0, 0};
-  const bool ok = insert_searches<NB, FULL, HASH>(g, c, node, level, st.entry, st.entry_level, elog, tstat, blockIdx.x < exact_positions, (int)layer);
+  const bool ok = insert_searches<NB, FULL, HASH, RT>(g, c, node, level, st.entry, st.entry_level, elog, tstat, blockIdx.x < exact_positions, (int)layer);
   __syncthreads();
   const uint32_t nlog = c.misc[MS_NLOG];
   if (threadIdx.x == 0) {
@@ -1424,7 +1424,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(co
 // (at most max_rerun times per launch, then the kernel stops and leaves the rest to the next speculation).
 // spec == nullptr: no speculation, every search runs here (small graphs, where every insert touches what the next reads).
 // HASH: the form of `visited` (Visited<HASH>), chosen by the host for the whole call.
-template <int NB, bool FULL, bool HASH>
+template <int NB, bool FULL, bool HASH, typename RT = float>
 __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(const BuildView g, uint32_t first, uint32_t n, uint32_t count,
                                                                               uint32_t tag, uint32_t max_rerun,
                                                                               const uint32_t* __restrict__ spec,
@@ -1473,7 +1473,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
       for (uint32_t l = 0; l <= level; ++l) usable = usable && sp[8 + l] == tag;
       uint32_t why = sp[1] == node && sp[2] == st.entry ? 2u : 1u;
       if (usable) {
-        why = validate_speculation<NB, FULL, HASH>(g, c, node, level, tag, sp, elogs + (size_t)b * kBuildLayers * kLogWords, chg, strict);
+        why = validate_speculation<NB, FULL, HASH, RT>(g, c, node, level, tag, sp, elogs + (size_t)b * kBuildLayers * kLogWords, chg, strict);
         have = why == 0;
         n_chk += c.misc[MS_NCHK];
         n_touch += c.misc[MS_NT];
@@ -1495,7 +1495,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
       reruns += 1;
       n_rerun += 1;
       BSTAMP(ts0);
-      if (!insert_searches<NB, FULL, HASH>(g, c, node, level, st.entry, st.entry_level, nullptr, stat)) {
+      if (!insert_searches<NB, FULL, HASH, RT>(g, c, node, level, st.entry, st.entry_level, nullptr, stat)) {
         if (HASH && c.misc[MS_OVER] == 2) vis_host = 1;  // the hashed visited set filled: this node is the host's
         st.status = 1;
         break;
@@ -1541,7 +1541,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_commit_kernel(co
 // Distance of every stored edge of the listed rows (code: node for layer 0, 0x80000000 | upper row otherwise, with
 // `owner[i]` = the node the upper row belongs to), or of ALL layer-0 rows / upper rows when codes == nullptr: one wave
 // per row, base = the row's node.  Fills dist0 / distU for graphs whose rows came from the host.
-template <int NB, bool FULL>
+template <int NB, bool FULL, typename RT = float>
 __global__ __launch_bounds__(256) void graph_edge_dist_kernel(const BuildView g, const uint32_t* __restrict__ codes,
                                                              const uint32_t* __restrict__ owner, uint32_t n_rows, uint32_t upper_all) {
   const uint32_t tile_rows = kTileRows;
@@ -1571,12 +1571,12 @@ __global__ __launch_bounds__(256) void graph_edge_dist_kernel(const BuildView g,
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const uint32_t j = (uint32_t)b * 128u + 2u * (uint32_t)lane;
-    q2[b] = j < g.dpad ? *(const float2*)(g.rows + (size_t)base_node * g.dpad + j) : make_float2(0.0f, 0.0f);
+    q2[b] = j < g.dpad ? row_pair_f32((const RT*)g.rows + (size_t)base_node * g.dpad, j) : make_float2(0.0f, 0.0f);
   }
   for (uint32_t o = 0; o < k; o += BuildRows<NB>::kMax) {
     const uint32_t cnt = min(BuildRows<NB>::kMax, k - o);
     const uint32_t pn = (uint32_t)lane < cnt ? adj[at + 1 + o + lane] : 0u;
-    const float d = score_upto16<NB, FULL>(g.rows, g.dpad, q2, pn, cnt, tile, lane);
+    const float d = score_upto16<NB, FULL>((const RT*)g.rows, g.dpad, q2, pn, cnt, tile, lane);
     if ((uint32_t)lane < cnt) adjd[at + 1 + o + lane] = d;
   }
 }

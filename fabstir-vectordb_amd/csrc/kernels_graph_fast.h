@@ -44,7 +44,7 @@ __host__ __device__ inline size_t graph_fast_lds_bytes(uint32_t R) {
 }
 
 // the smallest straight-line variant that holds the round
-template <int NB, int R>
+template <int NB, int R, typename RT>
 __device__ __forceinline__ float score_round(const GraphView& g, const float2 (&q2)[NB], uint32_t pn, uint32_t cnt,
                                              float* stage, int lane
 #ifdef FVDB_GRAPH_STAMPS
@@ -55,13 +55,14 @@ __device__ __forceinline__ float score_round(const GraphView& g, const float2 (&
 #endif
 ) {
   const uint32_t dpad = g.dpad, tile = (uint32_t)R * kScoreStride;
+  const RT* rows = (const RT*)g.rows;
   if (dpad == (uint32_t)NB * 128u) {
-    if (R > 8 && cnt > 8) return score_fixed<NB, R, true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-    if (R > 4 && cnt > 4) return score_fixed<NB, (R < 8 ? R : 8), true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-    return score_fixed<NB, (R < 4 ? R : 4), true, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    if (R > 8 && cnt > 8) return score_fixed<NB, R, true, FVDB_FAST_TILES>(rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    if (R > 4 && cnt > 4) return score_fixed<NB, (R < 8 ? R : 8), true, FVDB_FAST_TILES>(rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+    return score_fixed<NB, (R < 4 ? R : 4), true, FVDB_FAST_TILES>(rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
   }
-  if (R > 8 && cnt > 8) return score_fixed<NB, R, false, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
-  return score_fixed<NB, (R < 8 ? R : 8), false, FVDB_FAST_TILES>(g.rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+  if (R > 8 && cnt > 8) return score_fixed<NB, R, false, FVDB_FAST_TILES>(rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
+  return score_fixed<NB, (R < 8 ? R : 8), false, FVDB_FAST_TILES>(rows, dpad, q2, pn, cnt, stage, tile, lane FVDB_TACC);
 }
 #undef FVDB_TACC
 
@@ -69,7 +70,7 @@ __device__ __forceinline__ float score_round(const GraphView& g, const float2 (&
 // nodes, so they never share a byte) instead of one bit per node with atomicOr — scattered integer atomics execute at
 // the memory side, one uncached request each, and 32 of them per hop were a chip-wide throughput limit.  The row of a
 // query is vstride bytes either way (the exact-heap restart uses its first `words` words as a bitmap).
-template <int NB, int R, bool BYTES>
+template <int NB, int R, bool BYTES, typename RT = float>
 __global__ __launch_bounds__(256, (R <= 8 ? 4 : (R <= 12 ? 3 : FVDB_FAST_WAVES16))) void hnsw_search_fast_kernel(const GraphView g, const float* __restrict__ queries, uint32_t B,
                                                               uint32_t k, uint32_t ef_final, uint32_t cand_cap, uint32_t wave_lds,
                                                               uint8_t* __restrict__ visited /* [B][vstride] zero on entry */,
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256, (R <= 8 ? 4 : (R <= 12 ? 3 : FVDB_FAST_WAVES16
   unsigned long long t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   // nearest = [(entry, dist(q, entry))]  (:432-435)
-  const float d_entry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(score_round<NB, R>(g, q2, g.entry, 1, stage, lane
+  const float d_entry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(score_round<NB, R, RT>(g, q2, g.entry, 1, stage, lane
 #ifdef FVDB_GRAPH_STAMPS
                                                                                                             , t_acc
 #endif
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(256, (R <= 8 ? 4 : (R <= 12 ? 3 : FVDB_FAST_WAVES16
         const uint32_t cnt = min((uint32_t)R, np - base);
         STAMP(t2s);
         const uint32_t pn = (uint32_t)lane < cnt ? pending[base + lane] : 0u;
-        const float pd = score_round<NB, R>(g, q2, pn, cnt, stage, lane
+        const float pd = score_round<NB, R, RT>(g, q2, pn, cnt, stage, lane
 #ifdef FVDB_GRAPH_STAMPS
                                             , t_acc
 #endif
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256, (R <= 8 ? 4 : (R <= 12 ? 3 : FVDB_FAST_WAVES16
   if (status == 2) {
     // equal distances met inside the heaps: this query is searched again, from the start, with the reference's heaps
     // restated (kernels_graph.h) — same wave, same launch; the visited bitmap was left clean above
-    hnsw_search_exact_body<true>(g, queries, b, k, ef_final, cand_cap, vis, words, tch, tcap, out_nodes, out_dist,
+    hnsw_search_exact_body<true, RT>(g, queries, b, k, ef_final, cand_cap, vis, words, tch, tcap, out_nodes, out_dist,
                                  out_counts, out_status, lds_f, lane, spill ? spill + (size_t)b * spill_cap : nullptr, spill ? spill_cap : 0u);
     return;
   }

@@ -14,7 +14,8 @@
 //                        walked in chunks of 64 with the count carried, so any stride is served.  The source row may be
 //                        the destination row (keep-rows form): a chunk is read whole before any of it is written, and
 //                        what is written never lies beyond what was read.
-//   gm_move              one wave per destination store row, 16 bytes per lane: whole dpad * 4-byte rows, every load and
+//   gm_move              one wave per destination store row, a chunk per lane (16 bytes of an f32 row, 8 of an fp16 row:
+//                        dpad / 4 chunks either way): whole rows, every load and
 //                        store a contiguous run; destination <= source, neighbouring waves share nothing
 #pragma once
 #include "common.h"
@@ -160,16 +161,17 @@ __global__ __launch_bounds__(256) void gm_prune_kernel(const GmPrune a) {
   }
 }
 
-// d4 = 16-byte chunks of a row (dpad / 4)
-__global__ __launch_bounds__(256) void gm_move_kernel(const uint32_t* __restrict__ src_node, const float4* __restrict__ src, uint32_t src_rows,
-                                                      uint32_t d4, uint32_t rows, float4* __restrict__ dst) {
+// d4 = chunks of a row (dpad / 4); Chunk = four row elements (float4: f32 rows, float2: fp16 rows)
+template <typename Chunk>
+__global__ __launch_bounds__(256) void gm_move_kernel(const uint32_t* __restrict__ src_node, const Chunk* __restrict__ src, uint32_t src_rows,
+                                                      uint32_t d4, uint32_t rows, Chunk* __restrict__ dst) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const uint32_t s = src_node[r];
   if (s >= src_rows) return;  // cannot happen; never read outside
-  const float4* in = src + (size_t)s * d4;
-  float4* out = dst + (size_t)r * d4;
+  const Chunk* in = src + (size_t)s * d4;
+  Chunk* out = dst + (size_t)r * d4;
   for (uint32_t c = lane; c < d4; c += 64) out[c] = in[c];
 }
 

@@ -1,6 +1,7 @@
 // kernels_misc.h — layout conversion, candidate scoring (HNSW hops) and k-means reductions.
 #pragma once
 #include "common.h"
+#include "row_types.h"
 
 #pragma clang fp contract(off)
 
@@ -84,18 +85,30 @@ __global__ void pad_rows_kernel(const float* __restrict__ src, uint32_t d, uint3
   dst[t] = j < d ? src[i * d + j] : 0.0f;
 }
 
-// queries[b] = rows[idx[b]] (both [.][dpad])
-__global__ void gather_rows_kernel(const float* __restrict__ rows, const uint32_t* __restrict__ idx, uint32_t dpad,
+// [n][d] f32 -> [n][dpad] fp16, rounded to nearest even (overflow: +-Inf), zero padded: the append of an fp16 store
+__global__ void pad_rows_f16_kernel(const float* __restrict__ src, uint32_t d, uint32_t dpad, uint64_t n,
+                                    half_t* __restrict__ dst) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * dpad) return;
+  const uint64_t i = t / dpad;
+  const uint32_t j = (uint32_t)(t % dpad);
+  dst[t] = (half_t)(j < d ? src[i * d + j] : 0.0f);
+}
+
+// queries[b] = rows[idx[b]] (both [.][dpad]; stored rows of either element, widened into the f32 query buffer)
+template <typename RT>
+__global__ void gather_rows_kernel(const RT* __restrict__ rows, const uint32_t* __restrict__ idx, uint32_t dpad,
                                    uint32_t B, float* __restrict__ dst) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (uint64_t)B * dpad) return;
   const uint32_t b = (uint32_t)(t / dpad), j = (uint32_t)(t % dpad);
-  dst[t] = rows[(size_t)idx[b] * dpad + j];
+  dst[t] = row_widen(rows[(size_t)idx[b] * dpad + j]);
 }
 
 // Candidate scoring for graph hops: lane = one (query, candidate) pair, sequential f32 fold like
 // src/hnsw/core.rs:691-697.  cand may live in pinned host memory mapped into the GPU.
-__global__ __launch_bounds__(256) void score_candidates_kernel(const float* __restrict__ rows, uint32_t dpad,
+template <typename RT>
+__global__ __launch_bounds__(256) void score_candidates_kernel(const RT* __restrict__ rows, uint32_t dpad,
                                                                const float* __restrict__ queries,
                                                                const uint32_t* __restrict__ cand, uint32_t B,
                                                                uint32_t C, uint32_t stride, float* __restrict__ out) {
@@ -105,11 +118,11 @@ __global__ __launch_bounds__(256) void score_candidates_kernel(const float* __re
   const uint32_t row = cand[(size_t)b * stride + c];
   float res = __uint_as_float(0x7F800000u);
   if (row != 0xFFFFFFFFu) {
-    const float4* xp = (const float4*)(rows + (size_t)row * dpad);
+    const typename RowVec<RT>::Quad* xp = (const typename RowVec<RT>::Quad*)(rows + (size_t)row * dpad);
     const float4* qp = (const float4*)(queries + (size_t)b * dpad);
     float acc = 0.0f;
     for (uint32_t i = 0; i < dpad / 4; ++i) {
-      const float4 x = xp[i], q = qp[i];
+      const float4 x = row_widen(xp[i]), q = qp[i];
       float u;
       u = q.x - x.x; acc = acc + u * u;
       u = q.y - x.y; acc = acc + u * u;

@@ -13,6 +13,7 @@
 //              row sit 1 KiB apart, so the read is strided by the layout itself
 #pragma once
 #include "common.h"
+#include "row_types.h"
 
 namespace fvdb {
 
@@ -51,15 +52,16 @@ __global__ __launch_bounds__(256) void pool_gather_rows_kernel(const void* __res
 }
 
 // store rows [row][dpad] (dpad = d rounded up to 4) and rows[n] -> out[n][d]
-__global__ __launch_bounds__(256) void store_gather_rows_kernel(const float* __restrict__ data, uint32_t dpad,
+template <typename RT>
+__global__ __launch_bounds__(256) void store_gather_rows_kernel(const RT* __restrict__ data, uint32_t dpad,
                                                                 const uint32_t* __restrict__ rows, uint32_t n, uint32_t d,
                                                                 float* __restrict__ out) {
   const uint32_t i = blockIdx.x * kRowsPerGroup + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= n) return;
-  const float4* src = (const float4*)(data + (size_t)rows[i] * dpad);
+  const typename RowVec<RT>::Quad* src = (const typename RowVec<RT>::Quad*)(data + (size_t)rows[i] * dpad);
   float* o = out + (size_t)i * d;
   for (uint32_t c = lane; c < dpad / 4; c += 64) {
-    const float4 v = src[c];
+    const float4 v = row_widen(src[c]);
     if (4 * c + 0 < d) o[4 * c + 0] = v.x;
     if (4 * c + 1 < d) o[4 * c + 1] = v.y;
     if (4 * c + 2 < d) o[4 * c + 2] = v.z;

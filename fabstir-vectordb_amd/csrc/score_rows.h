@@ -3,6 +3,9 @@
 // lane walking its own row.  This file is its only home; the traversal (kernels_graph_fast.h), the insert and the edge
 // distances (kernels_graph_build.h), the coarse select, the allow-set exact scan and the matrix-core select all call it.
 //
+// Rows are f32 or fp16 (row_types.h): the row element is a template parameter, the loads read pairs of it, and
+// score_products widens a pair exactly before it subtracts.  Everything after the load is the same code for both.
+//
 // Scoring keeps the reference's arithmetic — per row t = q_i - x_i; sum = sum + t*t, i ascending, f32, no FMA — but
 // splits it where it is order-free:
 //   * the products t*t are computed with the rows loaded COALESCED: a wave instruction reads 512 contiguous bytes of ONE
@@ -19,6 +22,7 @@
 //   score_rows_stream<RC>              dimension at run time, the next block's loads in flight while one is folded
 #pragma once
 #include "common.h"
+#include "row_types.h"
 
 #pragma clang fp contract(off)
 
@@ -50,11 +54,13 @@ constexpr uint32_t kScoreTileFloats = 16 * kScoreStride;  // one wave's tile (<=
 // the core
 // ---------------------------------------------------------------------------------------------
 // products of block c of RC rows into `tile`: x[r][c] = dims (128c + 2*lane, +1) of row r, q the same dims of the query
-template <int RC, int NB>
-__device__ __forceinline__ void score_products(const float2 (&x)[RC][NB], int c, const float2 q, float* tile, int lane) {
+// (x as loaded — float2, or a half pair kept packed until here and widened exactly)
+template <typename P, int RC, int NB>
+__device__ __forceinline__ void score_products(const P (&x)[RC][NB], int c, const float2 q, float* tile, int lane) {
 #pragma unroll
   for (int r = 0; r < RC; ++r) {
-    const float t0 = q.x - x[r][c].x, t1 = q.y - x[r][c].y;
+    const float2 xv = row_widen(x[r][c]);
+    const float t0 = q.x - xv.x, t1 = q.y - xv.y;
     *(float2*)(tile + (uint32_t)r * kScoreStride + 2u * (uint32_t)lane) = make_float2(t0 * t0, t1 * t1);
   }
 }
@@ -104,23 +110,24 @@ __device__ __forceinline__ float score_fold(const float* tile, uint32_t lrow, fl
 // TILES = 2: `stage` holds two tiles, tile_floats apart, and the products of block c + 1 go to the other tile, so the
 // scheduler can fill the bubbles of the dependent add chain of block c with them.  TILES = 1: one tile — products of
 // block c, fence, fold of block c, fence.
-template <int NB, int RC, bool FULL, int TILES>
-__device__ __forceinline__ float score_fixed(const float* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
+template <int NB, int RC, bool FULL, int TILES, typename RT>
+__device__ __forceinline__ float score_fixed(const RT* __restrict__ rows, uint32_t dpad, const float2 (&q2)[NB], uint32_t pn,
                                              uint32_t cnt, float* stage, uint32_t tile_floats, int lane SCORE_STAMP_PARAM) {
   static_assert(TILES == 1 || TILES == 2, "one or two product tiles");
   SCORE_STAMP(ta);
-  float2 x[RC][NB];
+  using P = typename RowVec<RT>::Pair;
+  P x[RC][NB];
   const uint32_t last = cnt - 1;
 #pragma unroll
   for (int r = 0; r < RC; ++r) {
     const uint32_t rr = (uint32_t)r < last ? (uint32_t)r : last;  // wave-uniform
     const uint32_t node = __builtin_amdgcn_readlane(pn, rr);
-    const float* row = rows + (size_t)node * dpad;
+    const RT* row = rows + (size_t)node * dpad;
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
       const uint32_t j = (uint32_t)c * 128u + 2u * (uint32_t)lane;
-      if (FULL) x[r][c] = *(const float2*)(row + j);
-      else x[r][c] = j < dpad ? *(const float2*)(row + j) : make_float2(0.0f, 0.0f);  // dpad % 4 == 0: pairs never straddle it
+      if (FULL) x[r][c] = *(const P*)(row + j);
+      else x[r][c] = j < dpad ? *(const P*)(row + j) : RowVec<RT>::zero_pair();  // dpad % 4 == 0: pairs never straddle it
     }
   }
   SCORE_STAMP(tb);
@@ -153,11 +160,12 @@ __device__ __forceinline__ float score_fixed(const float* __restrict__ rows, uin
 // Distances of query `q` (dpad floats, 8-byte aligned, dpad % 4 == 0) to RC rows: row r (< cnt) is
 // rows + readlane(pn, base + r) * dpad.  Returns, in lane r < cnt, sqrt of the reference's sum.  `tile`: kScoreTileFloats
 // floats of LDS private to the wave.  Rows past cnt repeat the last one (their sums are ignored).
-template <int RC>
-__device__ __forceinline__ float score_rows_stream(const float* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
+template <int RC, typename RT>
+__device__ __forceinline__ float score_rows_stream(const RT* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
                                                    uint32_t base, uint32_t cnt, float* tile, int lane) {
   const uint32_t nb = (dpad + 127) >> 7;
-  const float* rp[RC];
+  using P = typename RowVec<RT>::Pair;
+  const RT* rp[RC];
   const uint32_t last = cnt - 1;
 #pragma unroll
   for (int r = 0; r < RC; ++r) {
@@ -165,20 +173,21 @@ __device__ __forceinline__ float score_rows_stream(const float* __restrict__ row
     rp[r] = rows + (size_t)__builtin_amdgcn_readlane(pn, base + rr) * dpad;
   }
   const uint32_t j0 = 2u * (uint32_t)lane;
-  auto load = [&](uint32_t c, float2 (&x)[RC][1], float2& qv) {
+  auto load = [&](uint32_t c, P (&x)[RC][1], float2& qv) {
     const uint32_t j = c * 128u + j0;
     const bool in = j < dpad;  // dpad % 4 == 0: a pair never straddles the end
     qv = in ? *(const float2*)(q + j) : make_float2(0.0f, 0.0f);
 #pragma unroll
-    for (int r = 0; r < RC; ++r) x[r][0] = in ? *(const float2*)(rp[r] + j) : make_float2(0.0f, 0.0f);
+    for (int r = 0; r < RC; ++r) x[r][0] = in ? *(const P*)(rp[r] + j) : RowVec<RT>::zero_pair();
   };
   const uint32_t lrow = score_lane_row<RC>(lane);
   float acc = 0.0f;
-  auto fold = [&](const float2 (&x)[RC][1], const float2 qv) {
+  auto fold = [&](const P (&x)[RC][1], const float2 qv) {
     score_products(x, 0, qv, tile, lane);
     acc = score_fold(tile, lrow, acc);
   };
-  float2 xa[RC][1], xb[RC][1], qa, qb;
+  P xa[RC][1], xb[RC][1];
+  float2 qa, qb;
   load(0, xa, qa);
   for (uint32_t c = 0; c < nb; c += 2) {
     if (c + 1 < nb) load(c + 1, xb, qb);
@@ -192,7 +201,8 @@ __device__ __forceinline__ float score_rows_stream(const float* __restrict__ row
 }
 
 // up to 16 rows, the smallest straight-line form that holds them
-__device__ __forceinline__ float score_rows_upto16(const float* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
+template <typename RT>
+__device__ __forceinline__ float score_rows_upto16(const RT* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
                                                    uint32_t base, uint32_t cnt, float* tile, int lane) {
   if (cnt > 8) return score_rows_stream<16>(rows, dpad, q, pn, base, cnt, tile, lane);
   if (cnt > 4) return score_rows_stream<8>(rows, dpad, q, pn, base, cnt, tile, lane);
@@ -200,7 +210,8 @@ __device__ __forceinline__ float score_rows_upto16(const float* __restrict__ row
 }
 
 // lane i < n (n <= 64): distance to row rows + pn_i * dpad; chunks of 16 one after the other
-__device__ __forceinline__ float score_rows_wave(const float* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
+template <typename RT>
+__device__ __forceinline__ float score_rows_wave(const RT* __restrict__ rows, uint32_t dpad, const float* __restrict__ q, uint32_t pn,
                                                  uint32_t n, float* tile, int lane) {
   float out = 0.0f;
   for (uint32_t base = 0; base < n; base += 16) {

@@ -68,6 +68,17 @@ STATUS_TO_EXC = {1: NotTrained, 2: DuplicateVector, 3: DimensionMismatch, 4: Ins
                  9: NonFiniteInput, 10: HipError, 11: OutOfMemory, 12: Unsupported}
 
 
+ROW_DTYPES = {"f32": 0, "f16": 1}  # fvdb_dtype
+
+
+def row_dtype_code(row_dtype):
+    """fvdb_dtype of a row_dtype argument ("f32" / "f16")."""
+    try:
+        return ROW_DTYPES[row_dtype]
+    except (KeyError, TypeError):
+        raise InvalidConfig(f'row_dtype must be "f32" or "f16", got {row_dtype!r}') from None
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -239,7 +250,7 @@ class DeviceIVF:
         self.ctx, self.lib = ctx, ctx.lib
         self.d, self.nlist, self.dtype = int(d), int(nlist), dtype
         h = C.c_void_p()
-        ctx.check(self.lib.fvdb_ivf_create_ex(ctx.h, self.d, self.nlist, {"f32": 0, "f16": 1}[dtype], C.byref(h)))
+        ctx.check(self.lib.fvdb_ivf_create_ex(ctx.h, self.d, self.nlist, ROW_DTYPES[dtype], C.byref(h)))
         self.h = h
 
     def close(self):
@@ -517,11 +528,16 @@ class DeviceIVF:
 class RowStore:
     """Row-major vector store for gathered candidate scoring (fvdb_store)."""
 
-    def __init__(self, ctx, d, capacity_rows=1024):
-        self.ctx, self.lib, self.d = ctx, ctx.lib, int(d)
+    def __init__(self, ctx, d, capacity_rows=1024, dtype="f32"):
+        """dtype "f16": rows are rounded to IEEE fp16 (nearest even) at append and widened wherever they are read."""
+        self.ctx, self.lib, self.d, self.dtype = ctx, ctx.lib, int(d), dtype
         h = C.c_void_p()
-        ctx.check(self.lib.fvdb_store_create(ctx.h, self.d, capacity_rows, C.byref(h)))
+        ctx.check(self.lib.fvdb_store_create_ex(ctx.h, self.d, capacity_rows, ROW_DTYPES[dtype], C.byref(h)))
         self.h = h
+
+    def nbytes(self):
+        """HBM held by the stored rows (fvdb_store_bytes)."""
+        return int(self.lib.fvdb_store_bytes(self.h))
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):

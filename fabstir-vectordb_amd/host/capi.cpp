@@ -9,6 +9,26 @@ using namespace fvdbh;
 extern "C" {
 
 // ---- IVFIndex ----
+static bool row_dtype_ok(int row_dtype) { return row_dtype == FVDB_F32 || row_dtype == FVDB_F16; }
+
+// fp16 rows: bit-exact round-to-nearest-even f32 -> binary16 -> f32, the doors' routine
+void fvh_round_f16(const float* in, uint64_t n, float* out) { round_f16(in, n, out); }
+
+// the constructors with the rows' storage chosen (FVDB_F32 / FVDB_F16); anything else is an invalid config
+void* fvh_ivf_new_ex(fvdb_ctx* ctx, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iterations,
+                     uint64_t seed, int row_dtype) {
+  IVFConfig c;
+  c.n_clusters = n_clusters;
+  c.n_probe = n_probe;
+  c.train_size = train_size;
+  c.max_iterations = max_iterations;
+  c.seed = seed;
+  c.row_dtype = row_dtype;
+  if (!c.is_valid() || !row_dtype_ok(row_dtype)) return nullptr;
+  return new (std::nothrow) IVFIndex(ctx, c);
+}
+int fvh_ivf_row_dtype(void* p) { return ((IVFIndex*)p)->config().row_dtype; }
+
 void* fvh_ivf_new(fvdb_ctx* ctx, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iterations,
                   uint64_t seed) {
   IVFConfig c;
@@ -114,6 +134,18 @@ void* fvh_hnsw_new(fvdb_ctx* ctx, uint32_t M, uint32_t M0, uint32_t efc, uint64_
   c.seed = seed;
   return new (std::nothrow) HNSWIndex(ctx, c);
 }
+void* fvh_hnsw_new_ex(fvdb_ctx* ctx, uint32_t M, uint32_t M0, uint32_t efc, uint64_t seed, int row_dtype) {
+  if (!row_dtype_ok(row_dtype)) return nullptr;
+  HNSWConfig c;
+  c.max_connections = M;
+  c.max_connections_layer_0 = M0;
+  c.ef_construction = efc;
+  c.seed = seed;
+  c.row_dtype = row_dtype;
+  return new (std::nothrow) HNSWIndex(ctx, c);
+}
+int fvh_hnsw_row_dtype(void* p) { return ((HNSWIndex*)p)->config().row_dtype; }
+uint64_t fvh_hnsw_store_bytes(void* p) { return ((HNSWIndex*)p)->store_bytes(); }
 void fvh_hnsw_free(void* p) { delete (HNSWIndex*)p; }
 int fvh_hnsw_insert(void* p, uint64_t id, const float* v, uint32_t d, int64_t level) {
   return ((HNSWIndex*)p)->insert(id, v, d, level);
@@ -186,6 +218,30 @@ int fvh_hnsw_graph_kernel_times(void* p, float* ms_sum, uint32_t* launches, uint
 uint32_t fvh_hnsw_dimension(void* p) { return ((HNSWIndex*)p)->dimension(); }
 
 // ---- HybridIndex ----
+// one row_dtype for the graph and the lists
+void* fvh_hybrid_new_ex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, double recent_threshold_s, uint64_t migration_batch_size,
+                        int auto_migrate, uint64_t min_ivf_training_size, uint32_t M, uint32_t M0, uint32_t efc,
+                        uint64_t hseed, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iter,
+                        uint64_t iseed, int row_dtype) {
+  HybridConfig c;
+  c.recent_threshold_s = recent_threshold_s;
+  c.migration_batch_size = migration_batch_size;
+  c.auto_migrate = auto_migrate != 0;
+  c.min_ivf_training_size = min_ivf_training_size;
+  c.hnsw.max_connections = M;
+  c.hnsw.max_connections_layer_0 = M0;
+  c.hnsw.ef_construction = efc;
+  c.hnsw.seed = hseed;
+  c.ivf.n_clusters = n_clusters;
+  c.ivf.n_probe = n_probe;
+  c.ivf.train_size = train_size;
+  c.ivf.max_iterations = max_iter;
+  c.ivf.seed = iseed;
+  c.set_row_dtype(row_dtype);
+  if (!c.ivf.is_valid() || !(recent_threshold_s > 0) || migration_batch_size == 0 || !row_dtype_ok(row_dtype)) return nullptr;
+  return new (std::nothrow) HybridIndex(ctx_ivf, ctx_hnsw, c);
+}
+
 void* fvh_hybrid_new(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, double recent_threshold_s, uint64_t migration_batch_size,
                      int auto_migrate, uint64_t min_ivf_training_size, uint32_t M, uint32_t M0, uint32_t efc,
                      uint64_t hseed, uint32_t n_clusters, uint32_t n_probe, uint32_t train_size, uint32_t max_iter,

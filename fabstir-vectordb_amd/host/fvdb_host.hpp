@@ -113,12 +113,31 @@ inline int slot_ctx(fvdb_ctx* base, bool borrow, fvdb_ctx** ctx) {
   return FVDB_OK;
 }
 
+// Half-precision rows (row_dtype = FVDB_F16 in a config).  An index created with it rounds every
+// incoming row to IEEE binary16, to nearest even, ONCE, at the door — insert, batch_insert*, bulk_insert, bulk_build,
+// restore, insert_with_timestamp — and is from then on the reference algorithm given the rounded rows: the device
+// stores them as fp16 and widens exactly, the host copy holds the same values as f32.  Queries, training data and
+// centroids stay f32.  A value whose rounding overflows becomes +-Inf, which the entry point refuses as it refuses any
+// non-finite row (FVDB_E_NONFINITE).
+//
+// round_f16: out[i] = in[i] rounded to binary16 (nearest, ties to even) and widened back; integer arithmetic on the bit
+// patterns only.  The doors use it and nothing else does.
+void round_f16(const float* in, uint64_t n, float* out);
+// the rows as the index keeps them: v itself (FVDB_F32), or the rounded copy in `keep`
+inline const float* rows_at_the_door(int row_dtype, const float* v, uint64_t count, std::vector<float>& keep) {
+  if (row_dtype != FVDB_F16 || !v || count == 0) return v;
+  keep.resize(count);
+  round_f16(v, count, keep.data());
+  return keep.data();
+}
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
 struct IVFConfig {
   uint32_t n_clusters = 256, n_probe = 16, train_size = 10000, max_iterations = 25;  // :50-60
   uint64_t seed = 0;
+  int row_dtype = FVDB_F32;  // storage of the lists' rows (no counterpart in the reference)
   bool is_valid() const { return n_clusters > 0 && n_probe > 0 && n_probe <= n_clusters && train_size > 0 && max_iterations > 0; }
 };
 
@@ -243,6 +262,7 @@ class IVFIndex {
 struct HNSWConfig {
   uint32_t max_connections = 16, max_connections_layer_0 = 32, ef_construction = 200;  // :37-46
   uint64_t seed = 0;
+  int row_dtype = FVDB_F32;  // storage of the graph's rows (no counterpart in the reference)
 };
 
 class HNSWIndex {
@@ -341,6 +361,7 @@ class HNSWIndex {
     return vacuum_path_;
   }
   uint64_t store_rows() const { return store_ ? fvdb_store_rows(store_) : 0; }  // rows the vectors occupy in HBM
+  uint64_t store_bytes() const { return store_ ? fvdb_store_bytes(store_) : 0; }  // and their bytes
   int64_t level_of(uint64_t id) const;
   int64_t neighbors(uint64_t id, uint32_t layer, uint64_t* out, uint64_t cap);
   const float* vector_of(uint64_t id) const;  // host copy (migration, get_vector_by_id)
@@ -509,6 +530,9 @@ struct HybridConfig {
   uint64_t migration_batch_size = 100;
   bool auto_migrate = true;
   uint64_t min_ivf_training_size = 10;
+  // one knob for both parts: set_row_dtype writes hnsw.row_dtype and ivf.row_dtype together
+  void set_row_dtype(int dt) { hnsw.row_dtype = ivf.row_dtype = dt; }
+  int row_dtype() const { return hnsw.row_dtype; }
   static HybridConfig defaults() {
     HybridConfig c;
     c.ivf.train_size = 9;

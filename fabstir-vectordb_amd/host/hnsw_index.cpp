@@ -17,6 +17,41 @@
 
 namespace fvdbh {
 
+// ---- round_f16: the doors of an index with fp16 rows (fvdb_host.hpp) -------------------------
+// f32 -> binary16 (round to nearest, ties to even) -> f32, on the bit patterns.  binary16: 1 sign, 5 exponent (bias 15),
+// 10 mantissa bits; normal range 2^-14 .. 65504, subnormals k * 2^-24.  Rounding to nearest even of the value at the
+// target's spacing is: add half a unit in the last kept place, less one when the kept part is even, and cut.
+void round_f16(const float* in, uint64_t n, float* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    std::memcpy(&u, &in[i], 4);
+    const uint32_t sign = u & 0x80000000u;
+    uint32_t a = u & 0x7FFFFFFFu;
+    if (a >= 0x7F800000u) {
+      // Inf and NaN are themselves
+    } else if (a >= 0x477FF000u) {
+      a = 0x7F800000u;  // >= 65520 = 65504 + half a unit: rounds past the largest half, to infinity
+    } else if (a >= 0x38800000u) {
+      // normal half (>= 2^-14): keep 10 of the 23 mantissa bits; a carry into the exponent is the right answer
+      a += 0x00000FFFu + ((a >> 13) & 1u);
+      a &= 0xFFFFE000u;
+    } else if (a <= 0x33000000u) {
+      a = 0;  // <= 2^-25, half the smallest subnormal: the tie goes to the even neighbour, zero
+    } else {
+      // subnormal half: a multiple of 2^-24.  m = the 24-bit significand, to be cut by `shift` more bits than it has
+      const uint32_t e = a >> 23;  // 102 .. 112
+      const uint32_t m = (a & 0x007FFFFFu) | 0x00800000u;
+      const uint32_t shift = 126 - e;  // 14 .. 24: value = m * 2^(e - 150) = (m >> shift) * 2^-24 and a remainder
+      const uint32_t k = (m + ((1u << (shift - 1)) - 1u) + ((m >> shift) & 1u)) >> shift;  // 0 .. 1024 (2^-14)
+      // k * 2^-24 as f32: exact in float arithmetic, k < 2^11
+      const float f = (float)k * 5.9604644775390625e-8f;
+      std::memcpy(&a, &f, 4);
+    }
+    a |= sign;
+    std::memcpy(&out[i], &a, 4);
+  }
+}
+
 // ---- RustHeap ------------------------------------------------------------------------------
 void RustHeap::sift_up(size_t start, size_t pos) {
   Cand elt = data[pos];
@@ -166,7 +201,7 @@ size_t HNSWIndex::assign_level() {
 
 int HNSWIndex::ensure_store(uint32_t dim) {
   if (store_) return FVDB_OK;
-  return fvdb_store_create(ctx_, dim, 1024, &store_);
+  return fvdb_store_create_ex(ctx_, dim, 1024, cfg_.row_dtype, &store_);
 }
 
 int HNSWIndex::walk_begin(Walk& w, uint32_t B, uint32_t C) {
@@ -818,6 +853,8 @@ int HNSWIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uin
     if (first_error) *first_error = err;
     return rc;
   };
+  std::vector<float> rounded;  // fp16 rows: the checks, the store and host_vecs_ all see the rounded values
+  v = rows_at_the_door(cfg_.row_dtype, v, n * dim, rounded);
   for (uint64_t at = 0; at < n;) {
     // the next run of inserts that pass the reference's checks (a failed insert draws no level and changes nothing)
     std::vector<uint64_t> acc;
@@ -1041,6 +1078,8 @@ int HNSWIndex::restore(const uint64_t* ids, const float* v, uint64_t n, uint32_t
                        const uint64_t* nbr_offsets, const uint64_t* nbrs, uint64_t entry_id) {
   if (!ids_.empty()) return FVDB_E_INVALID;
   if (n == 0) return FVDB_OK;
+  std::vector<float> rounded;
+  v = rows_at_the_door(cfg_.row_dtype, v, n * dim, rounded);
   int rc = adopt_nodes(ids, v, n, dim, levels);
   if (rc) return rc;
   uint64_t slot = 0;
@@ -1206,6 +1245,8 @@ int HNSWIndex::bulk_build(const uint64_t* ids, const float* v, uint64_t n, uint3
   if (!ids_.empty()) return FVDB_E_INVALID;
   if (n == 0) return FVDB_OK;
   if (n >= 0xFFFFFFFFull) return FVDB_E_UNSUPPORTED;
+  std::vector<float> rounded;
+  v = rows_at_the_door(cfg_.row_dtype, v, n * dim, rounded);
   {
     std::unordered_set<uint64_t> seen;
     seen.reserve(n * 2);

@@ -220,6 +220,7 @@ Rows owned_rows(const std::vector<uint64_t>& ids, const std::vector<float>& v, c
 
 int HybridIndex::bulk_insert_sharded(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const double* ts,
                                      double now, uint32_t rank, uint32_t world, uint32_t* owner_out) {
+  if (cfg_.row_dtype() == FVDB_F16) return FVDB_E_UNSUPPORTED;  // a sharded fp16 hybrid is not served (attach_comm)
   if (!initialized_) return FVDB_E_NOT_INITIALIZED;
   std::unique_lock<std::shared_mutex> w(rw_);
   if (!ts_order_.empty() || world == 0 || rank >= world || busy()) return FVDB_E_INVALID;
@@ -304,7 +305,7 @@ int HybridIndex::retrain_historical(const IVFConfig& new_ivf_config, IVFIndex::R
   if (!ivf_trained_) return FVDB_E_NOT_TRAINED;
   const int rc = historical_->retrain(new_ivf_config, out);
   ivf_trained_ = historical_->is_trained();
-  if (historical_->config().n_clusters == new_ivf_config.n_clusters) cfg_.ivf = new_ivf_config;
+  if (historical_->config().n_clusters == new_ivf_config.n_clusters) cfg_.ivf = historical_->config();  // (row_dtype kept)
   return rc;
 }
 
@@ -538,6 +539,8 @@ int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, u
 }
 
 int HybridIndex::attach_comm(fvdb_comm* comm) {
+  // fp16 rows: the sharded step and the replicated graph have not been taken through half-width rows yet
+  if (comm && cfg_.row_dtype() == FVDB_F16) return FVDB_E_UNSUPPORTED;
   std::unique_lock<std::shared_mutex> w(rw_);
   if (busy()) return FVDB_E_INVALID;
   if (sharded_) fvdb_sharded_destroy(sharded_);

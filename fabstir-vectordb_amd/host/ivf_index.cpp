@@ -23,7 +23,7 @@ int IVFIndex::ensure_device(uint32_t dim) {
     fvdb_ivf_destroy(dev_);
     dev_ = nullptr;
   }
-  int rc = fvdb_ivf_create(ctx_, dim, cfg_.n_clusters, &dev_);
+  int rc = fvdb_ivf_create_ex(ctx_, dim, cfg_.n_clusters, cfg_.row_dtype, &dev_);
   if (rc) return rc;
   dim_ = dim;
   dev_clusters_ = cfg_.n_clusters;
@@ -174,7 +174,7 @@ int IVFIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, 
 int IVFIndex::rebuild(uint32_t n_clusters, uint32_t max_iterations, uint64_t seed, fvdb_train_result* tr,
                       uint64_t* reinserted) {
   fvdb_ivf* nd = nullptr;
-  int rc = fvdb_ivf_create(ctx_, dim_, n_clusters, &nd);
+  int rc = fvdb_ivf_create_ex(ctx_, dim_, n_clusters, cfg_.row_dtype, &nd);
   if (rc) return rc;
   rc = fvdb_ivf_train_from(nd, dev_, max_iterations, seed, tr);
   const uint64_t n = fvdb_ivf_total_rows(dev_);
@@ -217,6 +217,7 @@ int IVFIndex::retrain(const IVFConfig& new_config, RetrainResult* out) {
   // degenerate data) the reference is left with the new config, untrained, its lists whole.  Mirrored: the old device
   // index stays (dev_clusters_ lists) until a later train() builds one for the new config.
   cfg_ = new_config;
+  cfg_.row_dtype = old_config.row_dtype;  // the rows stay where and as they are: a retrain does not change their storage
   trained_ = false;
   const uint64_t n = dev_ ? fvdb_ivf_total_rows(dev_) : 0;
   if (n == 0 || n < cfg_.n_clusters) return FVDB_E_INSUFFICIENT;
@@ -411,6 +412,8 @@ int IVFIndex::get_vector_by_id(uint64_t id, float* out) {
 int IVFIndex::insert(uint64_t id, const float* v, uint32_t dim) {
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
+  std::vector<float> rounded;
+  v = rows_at_the_door(cfg_.row_dtype, v, dim, rounded);
   uint32_t c = 0;
   int rc = fvdb_ivf_assign(dev_, v, 1, &c);
   if (rc) return rc;
@@ -429,6 +432,8 @@ int IVFIndex::batch_insert(const uint64_t* ids, const float* v, uint64_t n, uint
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
   if (n == 0) return FVDB_OK;
+  std::vector<float> rounded;
+  v = rows_at_the_door(cfg_.row_dtype, v, n * dim, rounded);
   std::vector<uint32_t> clusters(n);
   int rc = fvdb_ivf_assign(dev_, v, n, clusters.data());
   if (rc) return rc;
@@ -442,6 +447,8 @@ int IVFIndex::batch_insert_assigned(const uint64_t* ids, const float* v, uint64_
   if (!trained_) return FVDB_E_NOT_TRAINED;
   if (dim != dim_) return FVDB_E_DIM;
   if (n == 0) return FVDB_OK;
+  std::vector<float> rounded;
+  v = rows_at_the_door(cfg_.row_dtype, v, n * dim, rounded);
   return place(ids, v, n, clusters, n_ok, first_error);
 }
 

@@ -14,7 +14,7 @@ import numpy as np
 from . import _capi
 from ._capi import f32p, u32p, u64p
 from .engine import (STATUS_TO_EXC, DimensionMismatch, FvdbError, InconsistentDimensions,
-                     InsufficientTrainingData, InvalidConfig, _f32, _ptr)
+                     InsufficientTrainingData, InvalidConfig, Unsupported, _f32, _ptr, row_dtype_code)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_capi.LIB_DIR, "libfvdb_host.so")
@@ -147,7 +147,17 @@ HOST_SIGNATURES = {
     "fvh_hybrid_migration_info": (i32, [vp, vp]),
     # recall self-evaluation at any n_probe
     "fvh_ivf_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, f32p, u64p]),
+    # half-precision rows: the constructors with a row_dtype, the doors' rounding routine
+    "fvh_ivf_new_ex": (vp, [vp, u32, u32, u32, u32, u64, i32]),
+    "fvh_hnsw_new_ex": (vp, [vp, u32, u32, u32, u64, i32]),
+    "fvh_hybrid_new_ex": (vp, [vp, vp, dbl, u64, i32, u64, u32, u32, u32, u64, u32, u32, u32, u32, u64, i32]),
+    "fvh_ivf_row_dtype": (i32, [vp]),
+    "fvh_hnsw_row_dtype": (i32, [vp]),
+    "fvh_hnsw_store_bytes": (u64, [vp]),
+    "fvh_round_f16": (None, [f32p, u64, f32p]),
 }
+
+_ROW_DTYPE_NAMES = ("f32", "f16")
 
 
 def load_host():
@@ -182,6 +192,15 @@ class SearchResults:
     def scores(self):
         """Node/REST surface score = 1/(1+distance) in f32 (bindings/node/src/session.rs:291, src/api/rest.rs:653)."""
         return (np.float32(1.0) / (np.float32(1.0) + self.distances)).astype(np.float32)
+
+
+def round_f16(x):
+    """The rounding an index with row_dtype="f16" applies at its door: f32 -> IEEE fp16 (nearest, ties to even) -> f32,
+    by the host mirror's own routine."""
+    x = _f32(x)
+    out = np.empty_like(x)
+    load_host().fvh_round_f16(_ptr(x, f32p), x.size, _ptr(out, f32p))
+    return out
 
 
 def _rows(x, dim=None):
@@ -231,15 +250,20 @@ class _Base:
 class IVFIndex(_Base):
     """src/ivf/core.rs IVFIndex (IVFConfig::default :50-60)."""
 
-    def __init__(self, ctx, n_clusters=256, n_probe=16, train_size=10000, max_iterations=25, seed=0, _handle=None):
+    def __init__(self, ctx, n_clusters=256, n_probe=16, train_size=10000, max_iterations=25, seed=0, row_dtype="f32",
+                 _handle=None):
+        """row_dtype "f16": the lists keep their rows as IEEE fp16.  Every inserted row is rounded once (nearest even) and
+        the index is the reference algorithm on the rounded rows; training data, centroids and queries stay f32."""
         self.ctx, self.lib = ctx, load_host()
         self.n_clusters, self.n_probe = n_clusters, n_probe
         self._own = _handle is None
         if _handle is None:
-            _handle = self.lib.fvh_ivf_new(ctx.h, n_clusters, n_probe, train_size, max_iterations, seed)
+            _handle = self.lib.fvh_ivf_new_ex(ctx.h, n_clusters, n_probe, train_size, max_iterations, seed,
+                                              row_dtype_code(row_dtype))
             if not _handle:
                 raise InvalidConfig("Invalid IVFConfig")
         self.h = _handle
+        self.row_dtype = _ROW_DTYPE_NAMES[self.lib.fvh_ivf_row_dtype(self.h)]
 
     def __del__(self):
         if getattr(self, "_own", False) and getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -453,12 +477,19 @@ class _InsertInfo(C.Structure):
 class HNSWIndex(_Base):
     """src/hnsw/core.rs HNSWIndex (HNSWConfig::default :37-46)."""
 
-    def __init__(self, ctx, max_connections=16, max_connections_layer_0=32, ef_construction=200, seed=0, _handle=None):
+    def __init__(self, ctx, max_connections=16, max_connections_layer_0=32, ef_construction=200, seed=0, row_dtype="f32",
+                 _handle=None):
+        """row_dtype "f16": the graph's row store keeps IEEE fp16.  Every inserted row is rounded once (nearest even) and
+        the index is the reference algorithm on the rounded rows (get_vector_by_id returns them); queries stay f32."""
         self.ctx, self.lib = ctx, load_host()
         self._own = _handle is None
         if _handle is None:
-            _handle = self.lib.fvh_hnsw_new(ctx.h, max_connections, max_connections_layer_0, ef_construction, seed)
+            _handle = self.lib.fvh_hnsw_new_ex(ctx.h, max_connections, max_connections_layer_0, ef_construction, seed,
+                                               row_dtype_code(row_dtype))
+            if not _handle:
+                raise InvalidConfig("Invalid HNSWConfig")
         self.h = _handle
+        self.row_dtype = _ROW_DTYPE_NAMES[self.lib.fvh_hnsw_row_dtype(self.h)]
 
     def __del__(self):
         if getattr(self, "_own", False) and getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -600,6 +631,10 @@ class HNSWIndex(_Base):
         """Rows the index's vectors occupy in HBM (equals node_count() after a resident vacuum)."""
         return int(self.lib.fvh_hnsw_store_rows(self.h))
 
+    def store_bytes(self):
+        """HBM the index's vectors occupy: store_rows() x the padded row's bytes (half as many with row_dtype "f16")."""
+        return int(self.lib.fvh_hnsw_store_bytes(self.h))
+
     def get_vector_by_id(self, id):
         out = np.empty(int(self.lib.fvh_hnsw_dimension(self.h)), np.float32)
         self._check(self.lib.fvh_hnsw_get_vector(self.h, int(id), _ptr(out, f32p)))
@@ -722,20 +757,24 @@ class HybridIndex(_Base):
 
     def __init__(self, ctx, recent_threshold=WEEK, migration_batch_size=100, auto_migrate=True,
                  min_ivf_training_size=10, max_connections=16, max_connections_layer_0=32, ef_construction=200,
-                 hnsw_seed=0, n_clusters=3, n_probe=2, train_size=9, max_iterations=25, ivf_seed=0, ctx_hnsw=None):
-        # defaults = HybridConfig::default (src/hybrid/core.rs:69-85)
+                 hnsw_seed=0, n_clusters=3, n_probe=2, train_size=9, max_iterations=25, ivf_seed=0, ctx_hnsw=None,
+                 row_dtype="f32"):
+        # defaults = HybridConfig::default (src/hybrid/core.rs:69-85); row_dtype "f16": the graph's rows and the lists'
+        # rows are IEEE fp16, rounded once at insert (one knob for both parts)
         self.ctx, self.lib = ctx, load_host()
+        self.row_dtype = _ROW_DTYPE_NAMES[row_dtype_code(row_dtype)]
         self.ctx_hnsw = ctx_hnsw or ctx
         self.n_clusters, self.n_probe = n_clusters, n_probe
         self.config = dict(recent_threshold=recent_threshold, migration_batch_size=migration_batch_size,
                            auto_migrate=auto_migrate, min_ivf_training_size=min_ivf_training_size,
                            max_connections=max_connections, max_connections_layer_0=max_connections_layer_0,
                            ef_construction=ef_construction, hnsw_seed=hnsw_seed, n_clusters=n_clusters, n_probe=n_probe,
-                           train_size=train_size, max_iterations=max_iterations, ivf_seed=ivf_seed)
-        self.h = self.lib.fvh_hybrid_new(ctx.h, self.ctx_hnsw.h, recent_threshold, migration_batch_size,
-                                         int(auto_migrate), min_ivf_training_size, max_connections,
-                                         max_connections_layer_0, ef_construction, hnsw_seed, n_clusters, n_probe,
-                                         train_size, max_iterations, ivf_seed)
+                           train_size=train_size, max_iterations=max_iterations, ivf_seed=ivf_seed,
+                           row_dtype=self.row_dtype)
+        self.h = self.lib.fvh_hybrid_new_ex(ctx.h, self.ctx_hnsw.h, recent_threshold, migration_batch_size,
+                                            int(auto_migrate), min_ivf_training_size, max_connections,
+                                            max_connections_layer_0, ef_construction, hnsw_seed, n_clusters, n_probe,
+                                            train_size, max_iterations, ivf_seed, row_dtype_code(self.row_dtype))
         if not self.h:
             raise InvalidConfig("Invalid HybridConfig")
 
@@ -792,6 +831,7 @@ class HybridIndex(_Base):
 
     def bulk_insert_sharded(self, ids, vectors, timestamps, now, rank, world):
         """Multi-GPU placement: HNSW replicated, IVF lists owned by `rank` only.  Returns owner[nlist]."""
+        self._refuse_sharded_f16("bulk_insert_sharded")
         v = _rows(vectors)
         ids = np.ascontiguousarray(ids, np.uint64)
         ts = np.ascontiguousarray(timestamps, np.float64)
@@ -881,7 +921,17 @@ class HybridIndex(_Base):
         return SearchResults(ids, ds, cnt)
 
     # ---- multi-GPU (sharded.py is the user-facing wrapper) ----
+    def _refuse_sharded_f16(self, what):
+        # the host mirror refuses the same call with FVDB_E_UNSUPPORTED; it has no message channel of its own
+        if self.row_dtype == "f16":
+            exc = Unsupported(f'{what}: a HybridIndex with row_dtype="f16" cannot be sharded: the sharded step and the '
+                              'replicated graph serve f32 rows only')
+            exc.status = 12
+            raise exc
+
     def attach_comm(self, comm_handle):
+        if comm_handle:
+            self._refuse_sharded_f16("attach_comm")
         self._check(self.lib.fvh_hybrid_attach_comm(self.h, comm_handle))
 
     def sharded_rows(self, B, mode):
@@ -982,6 +1032,10 @@ class HybridIndex(_Base):
 
     def hnsw(self):
         return HNSWIndex(self.ctx_hnsw, _handle=self.lib.fvh_hybrid_hnsw(self.h))
+
+    def store_bytes(self):
+        """HBM the recent part's vectors occupy (HNSWIndex.store_bytes)."""
+        return self.hnsw().store_bytes()
 
     def ivf_device_stage_times(self):
         return self.ivf().stage_times()

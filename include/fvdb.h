@@ -381,10 +381,22 @@ int fvdb_merge_search_results_dev(fvdb_ctx* ctx, const uint64_t* ids_dev, const 
  * Replaces euclidean_distance at src/hnsw/core.rs:279,434,487,515 (search_layer) and
  * :573,605,611 (prune): the host walks the graph, each hop's candidate batch is scored here.
  */
-int fvdb_store_create(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, fvdb_store** out);
+int fvdb_store_create(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, fvdb_store** out); /* FVDB_F32 rows */
+/* The same with the row element chosen.  An FVDB_F16 store keeps its rows as IEEE fp16, the rule of fvdb_ivf_create_ex:
+ * fvdb_store_append rounds each value to nearest even on the device (a value whose rounding overflows is stored as
+ * +-Inf; a caller that wants such rows refused checks before it appends) and pads the row with zeros to the same
+ * multiple of four elements as an f32 store, fvdb_store_get widens.  Every entry point that takes a store, or a graph
+ * built on one, serves either element: fvdb_score_candidates, fvdb_scorer_* (set_query_rows widens the stored rows
+ * into the f32 queries), fvdb_graph_* (search, masked search, scan_allowed, insert_linked, edge distances, vacuum),
+ * fvdb_ivf_assign_from_store and fvdb_ivf_add_assigned_from_store (the gather widens, so the lists may be of either
+ * dtype).  Queries are f32 everywhere.  Widening fp16 is exact and the f32 arithmetic is the f32 store's, so every
+ * distance is, bit for bit, what an f32 store holding the rounded values gives. */
+int fvdb_store_create_ex(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, int row_dtype, fvdb_store** out);
 void fvdb_store_destroy(fvdb_store* s);
 int fvdb_store_append(fvdb_store* s, const float* rows, uint64_t n, uint64_t* first_row);
 uint64_t fvdb_store_rows(fvdb_store* s);
+int fvdb_store_dtype(fvdb_store* s);      /* FVDB_F32 or FVDB_F16 */
+uint64_t fvdb_store_bytes(fvdb_store* s); /* HBM held by the stored rows: rows x padded row bytes */
 int fvdb_store_get(fvdb_store* s, uint64_t row, float* out /* d */);
 /* One-shot: B queries (host), C candidate row indices per query (FVDB_NO_ROW = pad) -> B x C
  * distances (+inf for pads). */
