@@ -193,6 +193,8 @@ SIGNATURES = {
     "fvdb_ivf_search_quality_dev": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
     "fvdb_graph_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_graph_scan_allowed_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    "fvdb_graph_search_flat_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    "fvdb_search_quality_lists_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
 }
 
 _lib = None

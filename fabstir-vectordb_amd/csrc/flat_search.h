@@ -1,0 +1,90 @@
+// flat_search.h — exact search of the C ABI (include/fvdb.h, "exact search"): the flat scan of a
+// graph's row store and the comparison of two resident id blocks.  Included at the end of fvdb_hip.cpp, after
+// allow_masks.h, for the same reason: the kernels lean on kernels_scan.h, which lives in this translation unit, and what
+// they need of the graph comes through graph_mask_source / graph_scan_inputs (fvdb_internal.h).
+#pragma once
+#include "kernels_flat.h"
+
+namespace {
+
+// queries of one launch pair: bounds the partial lists ((4096 Q + B) * k keys at the most, 84 MB at k = 256)
+constexpr uint32_t kFlatSubBatch = 8192;
+
+template <int Q, int KR>
+void launch_flat_scan(fvdb_ctx* ctx, const FlatScanArgs& a, bool f16 /* the store's rows */, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
+  if (a.slices)
+    hipLaunchKernelGGL((f16 ? flat_scan_kernel<Q, KR, half_t> : flat_scan_kernel<Q, KR, float>), dim3(cdiv(a.B, Q), cdiv(a.slices, 4)),
+                       dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL((flat_merge_kernel<KR>), dim3(cdiv(a.B, 4)), dim3(256), 0, ctx->stream, a.part, a.slices, a.B, a.k, out_nodes,
+                     out_dist, out_counts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
+  if (!g) return FVDB_E_INVALID;
+  GraphMaskSource src{};
+  int rc = graph_mask_source(g, &src);
+  if (rc) return rc;
+  fvdb_store* s = src.store;
+  fvdb_ctx* ctx = on ? on : s->ctx;
+  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
+  if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
+  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
+  if (mask && mask->stamp != src.mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
+  if (k == 0 || k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "exact scan: k must be in 1..FVDB_MAX_K");
+  if (!q_dev || !out_nodes_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null argument");
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = src.n;
+  const uint32_t tiles = cdiv(n, 64);
+  const int kr = k <= 64 ? 1 : (k <= 128 ? 2 : 4);
+  const uint32_t Q = kr == 4 ? 4 : 8;  // queries of a group: the wider lists leave registers for fewer
+  // sub-batches run one after the other on the stream and share the slot's scratch
+  for (uint32_t b0 = 0; b0 < B; b0 += kFlatSubBatch) {
+    const uint32_t Bs = std::min(kFlatSubBatch, B - b0);
+    FlatScanArgs a{};
+    a.rows = s->data;
+    a.dead = mask ? mask->flags.as<uint32_t>() : src.deleted;
+    a.dpad = s->dpad;
+    a.n = n;
+    a.B = Bs;
+    a.k = k;
+    // enough (group, slice) waves to fill the device at a small batch, a slice no shorter than four tiles
+    a.slices = n ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(tiles, 4), cdiv(4096, cdiv(Bs, Q)))) : 0;
+    a.slice_tiles = a.slices ? cdiv(tiles, a.slices) : 0;
+    if (a.slices) a.slices = cdiv(tiles, a.slice_tiles);
+    rc = graph_scan_inputs(g, ctx, slot, q_dev + (size_t)b0 * s->d, Bs, (size_t)a.slices * Bs * k * 8, &a.queries, &a.part);
+    if (rc) return rc;
+    uint32_t* on_ = out_nodes_dev + (size_t)b0 * k;
+    float* od_ = out_dist_dev + (size_t)b0 * k;
+    uint32_t* oc_ = out_counts_dev + b0;
+    switch (kr) {
+      case 1: launch_flat_scan<8, 1>(ctx, a, s->f16(), on_, od_, oc_); break;
+      case 2: launch_flat_scan<8, 2>(ctx, a, s->f16(), on_, od_, oc_); break;
+      default: launch_flat_scan<4, 4>(ctx, a, s->f16(), on_, od_, oc_); break;
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return FVDB_OK;
+}
+
+int fvdb_search_quality_lists_dev(fvdb_ctx* ctx, const uint64_t* res_ids_dev, const uint32_t* res_counts_dev,
+                                  const uint64_t* truth_ids_dev, const uint32_t* truth_counts_dev, uint32_t B, uint32_t k,
+                                  float* out_recall_dev, float* out_precision_dev) {
+  if (!ctx) return FVDB_E_INVALID;
+  if (!res_ids_dev || !res_counts_dev || !truth_ids_dev || !truth_counts_dev || !out_recall_dev || !out_precision_dev)
+    FAIL(ctx, FVDB_E_INVALID, "null buffer");
+  if (k == 0) FAIL(ctx, FVDB_E_UNSUPPORTED, "k must be > 0");
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(search_quality_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, res_ids_dev, res_counts_dev, truth_ids_dev,
+                     truth_counts_dev, B, k, out_recall_dev, out_precision_dev);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+}  // extern "C"

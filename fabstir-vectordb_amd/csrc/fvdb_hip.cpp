@@ -3090,3 +3090,4 @@ int fvdb_scorer_run(fvdb_scorer* sc, uint32_t B, uint32_t C) {
 #include "ivf_rows.h"
 #include "comm_sharded.h"
 #include "allow_masks.h"
+#include "flat_search.h"

@@ -173,6 +173,25 @@ int fvh_hnsw_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uin
                             uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
   return ((HNSWIndex*)p)->search_allowed(q, B, d, k, ef, allowed, n_allowed, ids, dist, counts);
 }
+// exact search and search quality.  out3 = avg_recall, avg_precision, avg_query_time_ms
+int fvh_hnsw_search_exact(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact(q, B, d, k, ids, dist, counts);
+}
+int fvh_hnsw_search_exact_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, const uint64_t* allowed,
+                                  uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact_allowed(q, B, d, k, allowed, n_allowed, ids, dist, counts);
+}
+int fvh_hnsw_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, float* out3,
+                                     uint64_t* queries_evaluated) {
+  SearchQuality s{};
+  const int rc = ((HNSWIndex*)p)->evaluate_search_quality(q, B, d, k, ef, &s);
+  if (rc) return rc;
+  out3[0] = s.avg_recall;
+  out3[1] = s.avg_precision;
+  out3[2] = s.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
+  return FVDB_OK;
+}
 void fvh_hnsw_set_scan_cutoff(void* p, uint64_t nodes) { ((HNSWIndex*)p)->set_scan_cutoff(nodes); }
 uint64_t fvh_hnsw_scan_cutoff(void* p) { return ((HNSWIndex*)p)->scan_cutoff(); }
 void* fvh_hnsw_device_graph(void* p) { return ((HNSWIndex*)p)->device_graph(); }
@@ -293,6 +312,29 @@ int fvh_hybrid_search(void* p, const float* q, uint32_t B, uint32_t d, uint64_t 
   c.recent_k = recent_k;
   c.historical_k = historical_k;
   return ((HybridIndex*)p)->search(q, B, d, c, now, ids, dist, counts);
+}
+int fvh_hybrid_search_exact(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, int search_recent, int search_historical,
+                            double now, uint64_t* ids, float* dist, uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_exact(q, B, d, c, now, ids, dist, counts);
+}
+int fvh_hybrid_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
+                                       double now, float* out3, uint64_t* queries_evaluated) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = ef;
+  c.ivf_n_probe = nprobe;
+  SearchQuality s{};
+  const int rc = ((HybridIndex*)p)->evaluate_search_quality(q, B, d, c, now, &s);
+  if (rc) return rc;
+  out3[0] = s.avg_recall;
+  out3[1] = s.avg_precision;
+  out3[2] = s.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
+  return FVDB_OK;
 }
 int fvh_hybrid_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
                               int search_recent, int search_historical, uint64_t recent_k, uint64_t historical_k,

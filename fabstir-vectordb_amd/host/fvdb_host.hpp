@@ -131,6 +131,18 @@ inline const float* rows_at_the_door(int row_dtype, const float* v, uint64_t cou
   return keep.data();
 }
 
+// Exact search and search quality.  SearchQuality: src/ivf/operations.rs SearchQuality.
+struct SearchQuality {
+  float avg_recall, avg_precision, avg_query_time_ms;
+  uint64_t queries_evaluated;
+};
+// Two B x k id blocks with their hit counts compared per query on the device (fvdb_search_quality_lists_dev: the
+// reference's matches / recall / precision, src/ivf/operations.rs:357-377); the per-query f32 values are summed here in
+// query order, as IVFIndex::evaluate_search_quality sums them.  The node -> id mapping and the hybrid merge live in
+// this mirror, so the two blocks go down to `stage` first (16 B k + 8 B bytes).
+int compare_id_blocks(fvdb_ctx* ctx, DevBuf& stage, uint32_t B, uint32_t k, const uint64_t* res_ids, const uint32_t* res_counts,
+                      const uint64_t* truth_ids, const uint32_t* truth_counts, float* total_recall, float* total_precision);
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
@@ -330,6 +342,19 @@ class HNSWIndex {
   // the same with the view at hand and the queries in HBM (HybridIndex, when its traversal was not enqueued)
   int search_dev_view(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
                       uint64_t* ids, float* dist, uint32_t* counts);
+  // Exact search (no counterpart in the reference): the k nearest live nodes by (distance bits,
+  // node index), every live row of the store scored by the flat scan (fvdb_graph_search_flat_dev_slot); node indices
+  // map to ids as search() maps them.  allowed != nullptr or masked: under that allow-set, through the cached view.
+  // k in 1..FVDB_MAX_K (FVDB_E_UNSUPPORTED otherwise).
+  int search_exact(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts);
+  int search_exact_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
+                           uint64_t* ids, float* dist, uint32_t* counts);
+  // the same with the queries in HBM and the slot chosen by the caller, who owns that slot for the call (HybridIndex)
+  int search_exact_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                       float* dist, uint32_t* counts, uint32_t slot);
+  // search(k, ef) against search_exact(k): the reference's recall / precision (src/ivf/operations.rs:329-391 applied
+  // to the graph).  B == 0 is FVDB_E_INVALID.
+  int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
   // 0 = never scan, UINT64_MAX = always.  The default is a guess nobody has measured.
   void set_scan_cutoff(uint64_t nodes) { scan_cutoff_ = nodes; }
   uint64_t scan_cutoff() const { return scan_cutoff_; }
@@ -491,6 +516,7 @@ class HNSWIndex {
   };
   DevSlot slots_[kSlots];
   DevBuf d_q_;  // staging for host-resident query batches of search()
+  DevBuf qual_;  // evaluate_search_quality: the two id blocks and the per-query figures
   std::atomic<uint64_t> n_fallback_{0};
   // Searches may come from several host threads (HybridIndex leases a slot per call): the graph mirror is synced by
   // one of them, the rare host-walk fallback and the standalone search()/search_dev() entry points are serialised.
@@ -609,6 +635,18 @@ class HybridIndex {
   // that repeats one filter.  FVDB_E_UNSUPPORTED once the index is sharded (search_allowed_sharded_begin serves that).
   int search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,
                      uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* counts);
+  // Exact search: search()'s migration step and read lock, then the recent part from the flat
+  // scan of the graph's rows and the historical part from the search of every list (search_with_config(q, k,
+  // n_clusters), src/ivf/core.rs:626-681), merged by the usual merge — no de-duplication: a migrated row that still
+  // sits in the graph appears twice, as in search().  cfg: k, search_recent, search_historical (recent_k /
+  // historical_k as in search()); k in 1..FVDB_MAX_K.  FVDB_E_UNSUPPORTED once the index is sharded: a rank holds
+  // only the lists it owns.
+  int search_exact(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                   float* dist, uint32_t* counts);
+  // search(cfg) against search_exact(cfg) under ONE hold of the read lock, after one migration step: both see the same
+  // rows.  B == 0 is FVDB_E_INVALID.
+  int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
+                              SearchQuality* out);
   // Concurrency (reference: tokio RwLock, searches = readers, src/hybrid/core.rs:457,466): search() / search_dev() /
   // search_with_filter() may be called from any number of host threads; each call leases a free slot (stream,
   // traversal state, IVF scratch set, result blocks) and returns it.  Mutations wait for those calls to finish.
@@ -686,6 +724,13 @@ class HybridIndex {
   int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                   double now, uint64_t* ids, float* dist, uint32_t* counts, const uint64_t* allowed = nullptr,
                   uint64_t n_allowed = 0, bool masked = false);
+  // search_impl / search_exact after the migration step, the caller holding the read side of rw_
+  int search_locked(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids,
+                    float* dist, uint32_t* counts, const uint64_t* allowed, uint64_t n_allowed, bool masked);
+  int exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
+                   uint32_t* counts);
+  std::mutex qual_mu_;  // evaluate_search_quality's staging block
+  DevBuf qual_;
   // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                      int shard_mode, double now, const uint64_t* allowed = nullptr, uint64_t n_allowed = 0,

@@ -181,6 +181,7 @@ HNSWIndex::~HNSWIndex() {
     if (i > 0 && slots_[i].ctx) fvdb_ctx_destroy(slots_[i].ctx);
   }
   d_q_.release();
+  qual_.release();
   for (Walk* w : {&search_walk_, &insert_walk_})
     if (w->sc) fvdb_scorer_destroy(w->sc);
   if (store_) fvdb_store_destroy(store_);
@@ -659,6 +660,115 @@ int HNSWIndex::search_view_locked(const float* q_dev, uint32_t B, uint32_t dim, 
   std::vector<uint32_t> failed;
   if ((rc = device_collect(B, k, ids, dist, counts, failed, 0, scan))) return rc;
   return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed, &view);
+}
+
+// ---- exact search and search quality ----
+int compare_id_blocks(fvdb_ctx* ctx, DevBuf& stage, uint32_t B, uint32_t k, const uint64_t* res_ids, const uint32_t* res_counts,
+                      const uint64_t* truth_ids, const uint32_t* truth_counts, float* total_recall, float* total_precision) {
+  const uint64_t n = (uint64_t)B * k;
+  const uint64_t o_tid = n * 8, o_rc = 2 * n * 8, o_tc = o_rc + (uint64_t)B * 4, o_out = o_tc + (uint64_t)B * 4;
+  const uint64_t bytes = o_out + (uint64_t)B * 8;
+  int rc = stage.reserve(ctx, bytes, true);
+  if (rc) return rc;
+  char* h = (char*)stage.host;
+  char* d = (char*)stage.dev;
+  std::memcpy(h, res_ids, n * 8);
+  std::memcpy(h + o_tid, truth_ids, n * 8);
+  std::memcpy(h + o_rc, res_counts, (size_t)B * 4);
+  std::memcpy(h + o_tc, truth_counts, (size_t)B * 4);
+  if ((rc = fvdb_dev_upload(ctx, d, h, o_out))) return rc;
+  float* out = (float*)(d + o_out);
+  rc = fvdb_search_quality_lists_dev(ctx, (const uint64_t*)d, (const uint32_t*)(d + o_rc), (const uint64_t*)(d + o_tid),
+                                     (const uint32_t*)(d + o_tc), B, k, out, out + B);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx, h + o_out, d + o_out, (size_t)B * 8)) || (rc = fvdb_ctx_synchronize(ctx))) return rc;
+  const float* r = (const float*)(h + o_out);
+  float tr = 0.0f, tp = 0.0f;
+  for (uint32_t b = 0; b < B; ++b) {  // `total_recall += recall` (operations.rs:374-375), in query order
+    tr += r[b];
+    tp += r[B + b];
+  }
+  *total_recall = tr;
+  *total_precision = tp;
+  return FVDB_OK;
+}
+
+int HNSWIndex::search_exact_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                                float* dist, uint32_t* counts, uint32_t slot) {
+  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (slot >= kSlots) return FVDB_E_INVALID;
+  fill_empty(ids, dist, counts, B, k);
+  if (!has_entry_ || !store_) return FVDB_OK;  // a graph that has never held a row
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  if (B == 0) return FVDB_OK;
+  int rc = sync_graph();
+  if (rc) return rc;
+  DevSlot& sl = slots_[slot];
+  if ((rc = slot_ctx(ctx_, slot == 0, &sl.ctx))) return rc;
+  const uint64_t bytes = WalkBlock(nullptr, B, k).bytes;
+  if ((rc = sl.buf.reserve(sl.ctx, bytes, true))) return rc;
+  const WalkBlock d(sl.buf.dev, B, k);
+  rc = fvdb_graph_search_flat_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, view ? view->mask.get() : nullptr, q_dev, B, k,
+                                       d.nodes, d.dist, d.counts);
+  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
+  if (rc) return rc;
+  std::vector<uint32_t> none;
+  return device_collect(B, k, ids, dist, counts, none, slot, true);
+}
+
+int HNSWIndex::search_exact(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  fill_empty(ids, dist, counts, B, k);
+  if (!has_entry_ || !store_) return FVDB_OK;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  if (B == 0) return FVDB_OK;
+  std::lock_guard<std::mutex> serial(search_mu_);  // slot 0 and one staging buffer, like search()
+  const uint64_t bytes = (uint64_t)B * dim * 4;
+  int rc;
+  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
+  return search_exact_dev((const float*)d_q_.dev, B, dim, k, nullptr, ids, dist, counts, 0);
+}
+
+int HNSWIndex::search_exact_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed,
+                                    uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  fill_empty(ids, dist, counts, B, k);
+  if (!has_entry_ || !store_) return FVDB_OK;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  if (B == 0) return FVDB_OK;
+  ViewRef view;
+  int rc = allowed_view(allowed, n_allowed, &view);
+  if (rc) return rc;
+  if (!view->mask) return FVDB_OK;
+  std::lock_guard<std::mutex> serial(search_mu_);
+  const uint64_t bytes = (uint64_t)B * dim * 4;
+  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
+  return search_exact_dev((const float*)d_q_.dev, B, dim, k, view.get(), ids, dist, counts, 0);
+}
+
+int HNSWIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out) {
+  if (B == 0 || !q || !out) return FVDB_E_INVALID;  // "No test queries provided" (operations.rs:334-338)
+  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  const auto start = std::chrono::steady_clock::now();
+  const size_t n = (size_t)B * k;
+  std::vector<uint64_t> rid(n), tid(n);
+  std::vector<float> rd(n), td(n);
+  std::vector<uint32_t> rcn(B), tcn(B);
+  int rc;
+  if ((rc = search(q, B, dim, k, ef, rid.data(), rd.data(), rcn.data()))) return rc;
+  if ((rc = search_exact(q, B, dim, k, tid.data(), td.data(), tcn.data()))) return rc;
+  float tr = 0.0f, tp = 0.0f;
+  {
+    std::lock_guard<std::mutex> serial(search_mu_);  // qual_ is one block: calls take turns
+    if ((rc = compare_id_blocks(ctx_, qual_, B, k, rid.data(), rcn.data(), tid.data(), tcn.data(), &tr, &tp))) return rc;
+  }
+  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
+  out->avg_recall = tr / (float)B;
+  out->avg_precision = tp / (float)B;
+  out->avg_query_time_ms = elapsed.count() / (float)B;
+  out->queries_evaluated = B;
+  return FVDB_OK;
 }
 
 int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef,

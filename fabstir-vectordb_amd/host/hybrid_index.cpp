@@ -17,6 +17,7 @@ HybridIndex::HybridIndex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, const HybridConf
 }
 
 HybridIndex::~HybridIndex() {
+  qual_.release();
   for (Slot& sl : slots_) {
     sl.ivf.release();
     if (sl.ivf_done) fvdb_event_destroy(sl.ivf_done);
@@ -728,6 +729,13 @@ int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint3
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);
+  return search_locked(q, q_on_device, B, dim, cfg, ids, dist, counts, allowed, n_allowed, masked);
+}
+
+int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
+                               uint64_t* ids, float* dist, uint32_t* counts, const uint64_t* allowed, uint64_t n_allowed,
+                               bool masked) {
+  const uint32_t k = (uint32_t)cfg.k;
   // filtered search: the masks are built here — after the migration, under the lock that keeps the rows where they
   // are until this search has its results
   MaskRef ivf_mask;
@@ -776,6 +784,88 @@ int HybridIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint3
     return rc0;
   }
   return search_dev_end(slot, ids, dist, counts);
+}
+
+// ---- exact search and search quality ----
+// The two exact parts and the usual merge; the caller holds the read side of rw_.  The graph's scan runs in a slot leased
+// for the call (its stream, its scratch, its result block), the every-list search in a scratch set the engine leases.
+int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
+                              uint32_t* counts) {
+  const uint32_t k = (uint32_t)cfg.k;
+  const uint32_t rk = (uint32_t)(cfg.recent_k > 0 ? cfg.recent_k : cfg.k), hk = (uint32_t)(cfg.historical_k > 0 ? cfg.historical_k : cfg.k);
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  std::vector<uint64_t> rid, hid;
+  std::vector<float> rd, hd;
+  std::vector<uint32_t> rc_(B, 0), hc(B, 0);
+  const bool have_r = cfg.search_recent, have_h = cfg.search_historical && ivf_trained_;
+  if (have_r) {
+    if (rk > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+    rid.resize((size_t)B * rk);
+    rd.resize((size_t)B * rk);
+    Lease lease(this, Lease::kAnyFree, Lease::kTake);
+    Slot& sl = *lease.sl;
+    const uint32_t slot = lease.index();
+    const uint64_t bytes = (uint64_t)B * dim * 4;
+    int rc;
+    if ((rc = sl.d_q.reserve(ctx_ivf_, bytes, false))) return rc;
+    if (slot_ctx(ctx_ivf_, slot == 0, &sl.ivf_ctx)) return FVDB_E_HIP;
+    if ((rc = fvdb_dev_upload(sl.ivf_ctx, sl.d_q.dev, q, bytes))) return rc;
+    if ((rc = recent_->search_exact_dev((const float*)sl.d_q.dev, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), slot)))
+      return rc;
+  }
+  if (have_h) {
+    hid.resize((size_t)B * hk);
+    hd.resize((size_t)B * hk);
+    // search_with_config(q, k, n_clusters): every list, in centroid-rank order (the any-nprobe route where it applies)
+    if (int rc = historical_->search(q, B, dim, hk, historical_->config().n_clusters, hid.data(), hd.data(), hc.data())) return rc;
+  }
+  merge_parts(B, k, rk, hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, hid.data(), hd.data(), hc.data(), ids, dist, counts);
+  return FVDB_OK;
+}
+
+int HybridIndex::search_exact(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                              float* dist, uint32_t* counts) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // a rank holds only the lists it owns
+  const uint32_t k = (uint32_t)cfg.k;
+  if (cfg.k == 0 || cfg.k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  fill_empty(ids, dist, counts, B, k);
+  if (!initialized_ || B == 0) return FVDB_OK;
+  if (int rc = migrate_if_due(now, false)) return rc;
+  std::shared_lock<std::shared_mutex> r(rw_);
+  return exact_locked(q, B, dim, cfg, ids, dist, counts);
+}
+
+int HybridIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
+                                         SearchQuality* out) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;
+  if (B == 0 || !q || !out) return FVDB_E_INVALID;  // "No test queries provided" (src/ivf/operations.rs:334-338)
+  if (cfg.k == 0 || cfg.k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (!initialized_) return FVDB_E_INVALID;
+  const uint32_t k = (uint32_t)cfg.k;
+  const auto start = std::chrono::steady_clock::now();
+  const size_t n = (size_t)B * k;
+  std::vector<uint64_t> rid(n), tid(n);
+  std::vector<float> rd(n), td(n);
+  std::vector<uint32_t> rcn(B), tcn(B);
+  if (int rc = migrate_if_due(now, false)) return rc;
+  float tr = 0.0f, tp = 0.0f;
+  {
+    std::shared_lock<std::shared_mutex> r(rw_);  // one hold for both searches: they see the same rows
+    fill_empty(rid.data(), rd.data(), rcn.data(), B, k);
+    fill_empty(tid.data(), td.data(), tcn.data(), B, k);
+    int rc;
+    if ((rc = search_locked(q, false, B, dim, cfg, rid.data(), rd.data(), rcn.data(), nullptr, 0, false))) return rc;
+    if ((rc = exact_locked(q, B, dim, cfg, tid.data(), td.data(), tcn.data()))) return rc;
+    std::lock_guard<std::mutex> lk(qual_mu_);
+    if ((rc = compare_id_blocks(ctx_ivf_, qual_, B, k, rid.data(), rcn.data(), tid.data(), tcn.data(), &tr, &tp))) return rc;
+  }
+  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
+  out->avg_recall = tr / (float)B;
+  out->avg_precision = tp / (float)B;
+  out->avg_query_time_ms = elapsed.count() / (float)B;
+  out->queries_evaluated = B;
+  return FVDB_OK;
 }
 
 int HybridIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,

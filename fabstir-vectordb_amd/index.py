@@ -155,6 +155,12 @@ HOST_SIGNATURES = {
     "fvh_hnsw_row_dtype": (i32, [vp]),
     "fvh_hnsw_store_bytes": (u64, [vp]),
     "fvh_round_f16": (None, [f32p, u64, f32p]),
+    # exact search and search quality
+    "fvh_hnsw_search_exact": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
+    "fvh_hnsw_search_exact_allowed": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvh_hnsw_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
+    "fvh_hybrid_search_exact": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
+    "fvh_hybrid_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
 }
 
 _ROW_DTYPE_NAMES = ("f32", "f16")
@@ -245,6 +251,17 @@ class _Base:
         cnt = np.zeros(B, np.uint32)
         self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], k, *mid, _ptr(ids, u64p), _ptr(ds, f32p), _ptr(cnt, u32p)))
         return SearchResults(ids, ds, cnt)
+
+
+    def _quality(self, fn, queries, *args):
+        """evaluate_search_quality of the graph and hybrid classes: SearchQuality as a dict, as IVFIndex returns it."""
+        q = np.asarray(queries, np.float32)
+        if q.size == 0:
+            raise InvalidConfig("Invalid parameter: No test queries provided")
+        q = _rows(q)
+        out, n = np.zeros(3, np.float32), C.c_uint64(0)
+        self._check(fn(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], *args, _ptr(out, f32p), C.byref(n)))
+        return dict(avg_recall=out[0], avg_precision=out[1], avg_query_time_ms=float(out[2]), queries_evaluated=int(n.value))
 
 
 class IVFIndex(_Base):
@@ -412,6 +429,11 @@ class IVFIndex(_Base):
     def search(self, queries, k, n_probe=None):
         return self._search(self.lib.fvh_ivf_search, queries, k, self.n_probe if n_probe is None else n_probe)
 
+    def search_exact(self, queries, k):
+        """The exact k nearest live rows: the search of every list, search_with_config(q, k, n_clusters) (src/ivf/core.rs
+        :626-681).  A spelling of search() that the three index classes share; it adds no engine code."""
+        return self.search(queries, k, n_probe=self.n_clusters)
+
     def search_allowed(self, queries, k, allowed, n_probe=None):
         """search() among the rows whose id is in `allowed`: exactly what search() returns once every other row has been
         mark_deleted.  The allow-set is applied inside the list scan on the device; the last mask is kept for a caller
@@ -525,6 +547,24 @@ class HNSWIndex(_Base):
         distance bits, then node index)."""
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hnsw_search_allowed, queries, k, ef, _ptr(a, u64p), a.size)
+
+    def search_exact(self, queries, k):
+        """The k nearest live nodes, exactly: every live row the graph holds is scored where it is stored (as it is
+        stored: the rounded rows of an "f16" index) with the reference's f32 distance; the best k by distance bits, then
+        node index.  k in 1..256.  No counterpart in the reference: the ground truth recall is measured against."""
+        return self._search(self.lib.fvh_hnsw_search_exact, queries, k)
+
+    def search_exact_allowed(self, queries, k, allowed):
+        """search_exact() among the nodes whose id is in `allowed` (the cached mask of search_allowed)."""
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_hnsw_search_exact_allowed, queries, k, _ptr(a, u64p), a.size)
+
+    def evaluate_search_quality(self, queries, k, ef):
+        """search(k, ef) against search_exact(k) with the reference's formulas (src/ivf/operations.rs:357-377): per query
+        matches = result entries whose id is among the truth's, recall = matches / min(len(truth), k) (1 if the truth
+        is empty), precision = matches / len(result) (0 if the result is empty); compared on the device, averaged in
+        f32 in query order."""
+        return self._quality(self.lib.fvh_hnsw_evaluate_search_quality, queries, int(k), int(ef))
 
     @property
     def scan_cutoff(self):
@@ -836,6 +876,7 @@ class HybridIndex(_Base):
         ids = np.ascontiguousarray(ids, np.uint64)
         ts = np.ascontiguousarray(timestamps, np.float64)
         owner = np.zeros(self.n_clusters, np.uint32)
+        self._sharded = True
         self._check(self.lib.fvh_hybrid_bulk_insert_sharded(self.h, _ptr(ids, u64p), _ptr(v, f32p), v.shape[0],
                                                             v.shape[1], _ptr(ts, f64p), float(now), rank, world,
                                                             _ptr(owner, u32p)))
@@ -857,6 +898,23 @@ class HybridIndex(_Base):
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hybrid_search_allowed, queries, k, hnsw_ef, ivf_n_probe, int(search_recent),
                             int(search_historical), recent_k, historical_k, _ptr(a, u64p), a.size, float(now))
+
+    def search_exact(self, queries, k, now=0.0, search_recent=True, search_historical=True):
+        """search() with both parts exact: the recent part from the flat scan of the graph's rows, the historical part
+        from the search of every list, merged as search() merges (no de-duplication: a migrated row that still sits in
+        the graph appears twice).  Takes the same auto-migration step and read lock.  k in 1..256.  Refused
+        (Unsupported) on a sharded index: each rank holds only the lists it owns, so no rank can answer alone."""
+        self._refuse_when_sharded("search_exact")
+        return self._search(self.lib.fvh_hybrid_search_exact, queries, k, int(search_recent), int(search_historical),
+                            float(now))
+
+    def evaluate_search_quality(self, queries, k, now=0.0, hnsw_ef=50, ivf_n_probe=10):
+        """search(k, hnsw_ef, ivf_n_probe) against search_exact(k), both under one hold of the read lock after one
+        migration step; the formulas of HNSWIndex.evaluate_search_quality (an id returned twice counts twice).  Refused
+        on a sharded index, as search_exact is."""
+        self._refuse_when_sharded("evaluate_search_quality")
+        return self._quality(self.lib.fvh_hybrid_evaluate_search_quality, queries, int(k), int(hnsw_ef), int(ivf_n_probe),
+                             float(now))
 
     _FILTER_FN = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_void_p)
 
@@ -921,6 +979,14 @@ class HybridIndex(_Base):
         return SearchResults(ids, ds, cnt)
 
     # ---- multi-GPU (sharded.py is the user-facing wrapper) ----
+    def _refuse_when_sharded(self, what):
+        # the host mirror refuses the same call with FVDB_E_UNSUPPORTED; it has no message channel of its own
+        if getattr(self, "_sharded", False):
+            exc = Unsupported(f"{what}: not served on a sharded HybridIndex: each rank holds only the inverted lists it "
+                              "owns, so no rank can give the exact answer alone")
+            exc.status = 12
+            raise exc
+
     def _refuse_sharded_f16(self, what):
         # the host mirror refuses the same call with FVDB_E_UNSUPPORTED; it has no message channel of its own
         if self.row_dtype == "f16":
@@ -933,6 +999,7 @@ class HybridIndex(_Base):
         if comm_handle:
             self._refuse_sharded_f16("attach_comm")
         self._check(self.lib.fvh_hybrid_attach_comm(self.h, comm_handle))
+        self._sharded = True
 
     def sharded_rows(self, B, mode):
         return int(self.lib.fvh_hybrid_sharded_rows(self.h, B, mode))

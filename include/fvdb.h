@@ -647,6 +647,26 @@ int fvdb_graph_search_dev_slot_masked(fvdb_graph* g, fvdb_ctx* on, uint32_t slot
 int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                      uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
 
+/* ---- exact search ------------------------------------------------
+ * Flat exact k-NN over the rows a graph holds, as they are stored, where they are stored (no counterpart in the
+ * reference: the ground truth its recall figures are measured against).  Every live node is scored with the
+ * reference's f32 fold (src/core/vector_ops.rs:51-57; an fp16 row widened exactly first) by a coalesced tile scan of
+ * the row store; the k best by (distance bits ascending, node index ascending) — the result rule of
+ * fvdb_graph_scan_allowed_dev_slot, whose slot, stream and staleness rules also hold here.  mask: NULL = the graph's
+ * own deleted flags; else a node the mask does not allow counts as deleted (a mask of another graph or a stale one:
+ * FVDB_E_INVALID).  out_nodes/out_dist: B x k (unused tail = FVDB_NO_ROW / +inf), out_counts[q] = min(k, live nodes);
+ * an empty graph gives counts of 0.  k == 0 or k > FVDB_MAX_K: FVDB_E_UNSUPPORTED.  Large batches are scanned in
+ * sub-batches on the stream so the partial lists in the slot's scratch stay bounded. */
+int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
+/* The comparison of fvdb_ivf_search_quality_dev on two id blocks the caller holds in HBM (B x k ids with their hit
+ * counts; entries at or beyond a count are not read): per query matches, recall and precision by the formulas stated
+ * there — an id the result holds twice counts twice — to out_recall_dev[B] / out_precision_dev[B], enqueued on ctx's
+ * stream.  k > 0. */
+int fvdb_search_quality_lists_dev(fvdb_ctx* ctx, const uint64_t* res_ids_dev, const uint32_t* res_counts_dev,
+                                  const uint64_t* truth_ids_dev, const uint32_t* truth_counts_dev, uint32_t B, uint32_t k,
+                                  float* out_recall_dev, float* out_precision_dev);
+
 /* ---- multi-GPU: inverted lists sharded across the GPUs of a node, RCCL over xGMI -------------------------
  * (BASELINE config C4; SURVEY §8e.  The reference has no distributed execution: what is preserved is the result —
  * the merged answer equals the single-index answer bit for bit, because the selection keys are global.)
