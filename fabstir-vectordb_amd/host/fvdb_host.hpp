@@ -7,6 +7,7 @@
 // from the GPU through the C ABI.  Nothing in here computes a vector distance on the CPU.
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
 #include <memory>
@@ -136,6 +137,11 @@ struct SearchQuality {
   float avg_recall, avg_precision, avg_query_time_ms;
   uint64_t queries_evaluated;
 };
+// from the sums over B queries; avg_query_time_ms is the wall time since `start` over B
+inline SearchQuality quality_of(float total_recall, float total_precision, uint32_t B, std::chrono::steady_clock::time_point start) {
+  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
+  return {total_recall / (float)B, total_precision / (float)B, elapsed.count() / (float)B, B};
+}
 // Two B x k id blocks with their hit counts compared per query on the device (fvdb_search_quality_lists_dev: the
 // reference's matches / recall / precision, src/ivf/operations.rs:357-377); the per-query f32 values are summed here in
 // query order, as IVFIndex::evaluate_search_quality sums them.  The node -> id mapping and the hybrid merge live in
@@ -221,10 +227,7 @@ class IVFIndex {
   // centroid-rank order, per query on the device (fvdb_ivf_search_quality_dev); the per-query values are summed here
   // in query order, in f32, as the reference's `total_recall += recall`.  avg_query_time_ms is the wall time of the
   // call over B (the reference times each query by itself).  B == 0 is FVDB_E_INVALID (:334-338).
-  struct SearchQuality {  // operations.rs SearchQuality
-    float avg_recall, avg_precision, avg_query_time_ms;
-    uint64_t queries_evaluated;
-  };
+  typedef fvdbh::SearchQuality SearchQuality;  // operations.rs SearchQuality
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, SearchQuality* out);
   uint64_t cluster_size(uint32_t c) const;
   // list `c` in list-position order, copied back from HBM (save path, src/hybrid/persistence.rs:289-311)
@@ -319,33 +322,55 @@ class HNSWIndex {
   uint64_t graph_upload_bytes() const { return graph_ ? fvdb_graph_upload_bytes(graph_) : 0; }
   // the device graph as the searches see it (brought up to date first), for callers that drive the C ABI themselves
   fvdb_graph* device_graph() { return sync_graph() == FVDB_OK ? graph_ : nullptr; }
+  // ---- search ----
+  // One graph search, stated once: every entry point below fills one in and hands it on.  Where two entry points
+  // differ, they differ in these fields.
+  struct Search {
+    enum Kind { kTraversal, kExact } kind;  // the layered walk (src/hnsw/core.rs:398-467) / the flat scan of every live row
+    const float* q;                         // B x dim queries, row-major ...
+    bool q_on_device;                       // ... in HBM, or in host memory
+    uint32_t B, dim, k, ef;
+    uint64_t* ids;                          // B x k results to host memory (null at a begin, which delivers nothing)
+    float* dist;
+    uint32_t* counts;
+    const AllowView* view = nullptr;        // under this allow-set, or (by_list) under allowed[n_allowed]: admit() gets the view
+    bool by_list = false;
+    const uint64_t* allowed = nullptr;
+    uint64_t n_allowed = 0;
+    uint32_t slot = 0;                      // stream, scratch set and result block
+    bool owns_slot = false;                 // the caller holds `slot` for the call (HybridIndex's lease): run() takes no lock
+    // filled in by admit() and stage()
+    ViewRef held = nullptr;                 // keeps a by_list view alive
+    enum Route { kAnswered, kHostWalk, kDevice } route = kAnswered;
+    bool scanned = false;                   // kDevice by a scan: the result block carries no status words
+    const float* q_dev = nullptr;           // the queries in HBM
+  };
+  // Blocking searches, results to host memory.  They run in slot 0 and take turns (search_mu_); what each answers
+  // before it reaches the device is the table in DESIGN.md section 9l.
   int search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
              uint32_t* counts);                                                    // :398 (batched, lock-step hops)
   int search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                 uint32_t* counts);  // queries resident in HBM, results to host
-  // Split form for callers that overlap other GPU work with the graph walk: begin enqueues the
-  // device-resident traversal (returns false when this search has to use the host walk instead, in which
-  // case nothing was enqueued), end waits for it and delivers the results.
-  // Device traversal split in two so that several batches can be in flight: begin enqueues the launch and the
-  // result copies on the slot's own stream (slot < kSlots), end waits for that slot and finishes on the host.
-  static constexpr uint32_t kSlots = 16;
-  // `view` (optional): the search runs under that allow-set — masked traversal, or the exact scan when scans(view, k)
-  bool search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc, uint32_t slot = 0,
-                        const AllowView* view = nullptr);
-  int search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                     uint32_t* counts, uint32_t slot = 0, const AllowView* view = nullptr);
-  int allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out);  // cached like IVFIndex::allowed_mask
+                 uint32_t* counts);  // the queries resident in HBM
   // search under an allow-set: what search() returns after mark_deleted of every id outside it — unless the allowed
   // live nodes number at most scan_cutoff(): then they are scanned exactly (best k by distance bits, then node index)
   int search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
                      uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts);
-  // the same with the view at hand and the queries in HBM (HybridIndex, when its traversal was not enqueued)
-  int search_dev_view(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
-                      uint64_t* ids, float* dist, uint32_t* counts);
+  int allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out);  // cached like IVFIndex::allowed_mask
+  // The split form, so that several batches can be in flight: begin enqueues the launch and the result copy on the
+  // slot's own stream (slot < kSlots) and returns whether it did; the slot remembers.  end, given the same arguments,
+  // waits for that slot and finishes on the host — or, when nothing was enqueued (the checks answered the search, it
+  // has to use the host walk, the launch failed: *rc), runs the blocking search now, in slot 0.  A caller that makes
+  // the blocking call itself after a begin that returned false gets the same.  `view` (optional): masked traversal, or
+  // the scan of the allowed nodes when scans(view, k) — a device kernel whatever set_device_traversal says.
+  static constexpr uint32_t kSlots = 16;
+  bool search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc, uint32_t slot = 0,
+                        const AllowView* view = nullptr);
+  int search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
+                     uint32_t* counts, uint32_t slot = 0, const AllowView* view = nullptr);
   // Exact search (no counterpart in the reference): the k nearest live nodes by (distance bits,
   // node index), every live row of the store scored by the flat scan (fvdb_graph_search_flat_dev_slot); node indices
-  // map to ids as search() maps them.  allowed != nullptr or masked: under that allow-set, through the cached view.
-  // k in 1..FVDB_MAX_K (FVDB_E_UNSUPPORTED otherwise).
+  // map to ids as search() maps them.  _allowed: under that allow-set, through the cached view.
+  // k in 1..FVDB_MAX_K (FVDB_E_UNSUPPORTED otherwise).  It still answers after the entry point was vacuumed away.
   int search_exact(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts);
   int search_exact_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
                            uint64_t* ids, float* dist, uint32_t* counts);
@@ -439,7 +464,7 @@ class HNSWIndex {
   };
   // Working state of one lock-step walk: the scorer (one HIP stream; candidate and distance rows in pinned memory) and
   // the per-query heaps.  There are two, never used by the same caller: search_walk_ serves the host walk of the
-  // searches (under walk_mu_ — finish_failed runs it from search threads that hold the index only for reading),
+  // searches (under walk_mu_ — finish() runs it from search threads that hold the index only for reading),
   // insert_walk_ the host algorithm of an insert (B = 1, under the caller's write exclusion).
   struct Walk {
     fvdb_scorer* sc = nullptr;
@@ -456,18 +481,15 @@ class HNSWIndex {
   // search_layer (:469-554) for the B queries loaded into w's scorer, in lock step; entries and results in Query::cur
   int search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer);
   int score_pairs_from_row(uint32_t base_row, const std::vector<uint32_t>& cands, std::vector<float>& out);
-  int search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                  float* dist, uint32_t* counts);
-  int search_view_locked(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
-                         uint64_t* ids, float* dist, uint32_t* counts);  // the caller holds search_mu_
   int sync_graph();
-  bool device_path_ok(uint32_t ef) const;
-  int device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot, const AllowView* view = nullptr);
-  // scanned: the block came from the exact scan, which writes no status words
-  int device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts, std::vector<uint32_t>& failed,
-                     uint32_t slot, bool scanned = false);
-  int finish_failed(const float* q, bool q_on_device, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                    uint32_t* counts, const std::vector<uint32_t>& failed, const AllowView* view = nullptr);
+  // The five steps of a search (hnsw_index.cpp).  admit: the checks made before the device is reached; stage: host
+  // queries to d_q_; launch: enqueue in the slot and mark it; finish: collect a marked slot, or run the search now;
+  // run: all of it, blocking — in slot 0 under search_mu_, or in a slot its caller owns.
+  int admit(Search& s);
+  int stage(Search& s);
+  int launch(Search& s);
+  int finish(Search& s);
+  int run(Search& s);
   int search_host_walk(const float* q, bool q_on_device, uint32_t B, uint32_t k, uint32_t ef, uint64_t* ids,
                        float* dist, uint32_t* counts, const AllowView* view = nullptr);
   // The adjacency lists exist twice: nbrs_ (host) and the fixed-stride rows in HBM (graph_).  host_ahead_: nbrs_ holds
@@ -513,9 +535,11 @@ class HNSWIndex {
   struct DevSlot {  // per in-flight batch: stream (context), device result block and its pinned host copy
     fvdb_ctx* ctx = nullptr;  // slot 0 borrows ctx_, the others own theirs
     DevBuf buf;               // WalkBlock layout
+    bool enqueued = false;    // launch() to finish(): a batch is in flight here ...
+    bool scanned = false;     // ... whose block came from a scan, which writes no status words
   };
   DevSlot slots_[kSlots];
-  DevBuf d_q_;  // staging for host-resident query batches of search()
+  DevBuf d_q_;  // stage(): host-resident query batches
   DevBuf qual_;  // evaluate_search_quality: the two id blocks and the per-query figures
   std::atomic<uint64_t> n_fallback_{0};
   // Searches may come from several host threads (HybridIndex leases a slot per call): the graph mirror is synced by
@@ -572,6 +596,9 @@ struct HybridSearchConfig {  // :172-197
   bool search_recent = true, search_historical = true;
   uint64_t recent_k = 0, historical_k = 0;
   uint64_t k = 10, hnsw_ef = 50, ivf_n_probe = 10;
+  // results asked of each part: its own k where one is given, k otherwise
+  uint32_t rk() const { return (uint32_t)(recent_k > 0 ? recent_k : k); }
+  uint32_t hk() const { return (uint32_t)(historical_k > 0 ? historical_k : k); }
 };
 
 class HybridIndex {
@@ -737,6 +764,8 @@ class HybridIndex {
                      bool masked = false);
   int begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                  int shard_mode = -1);
+  int build_masks(const HybridSearchConfig& cfg, const uint64_t* allowed, uint64_t n_allowed, HNSWIndex::ViewRef* view,
+                  MaskRef* ivf_mask);
   // The per-search auto-migration (src/hybrid/core.rs:437-439).  A due migration moves rows between the two indexes (and
   // may grow the list pool), so it is refused with FVDB_E_INVALID while batches begun with search_dev_begin are
   // uncollected — now, or (`in_flight_before`) when the caller looked before it came here.
@@ -788,6 +817,15 @@ class HybridIndex {
     HNSWIndex::ViewRef view;
   };
   Slot slots_[kSlots];
+  int stage_finite(Slot& sl, const float* q, uint32_t B, uint32_t dim);
+  // A slot keeps a filtered search's masks only while that search runs: dropped at scope exit, whichever way it
+  // returns, so that the next user of the slot finds none.  sl = nullptr: handed on to the search_dev_end that collects.
+  struct DropMasks {
+    Slot* sl;
+    ~DropMasks() {
+      if (sl) sl->ivf_mask.reset(), sl->view.reset();
+    }
+  };
   // Slot::active held for a scope: set under slot_mu_, cleared on release with the waiting writers and searches woken.
   // hand_over() leaves the mark in place for the search_dev_end that collects the batch, which adopts it.
   struct Lease {

@@ -374,18 +374,6 @@ int HNSWIndex::search_layer(Walk& w, uint32_t B, uint32_t ef, uint32_t layer) {
   return FVDB_OK;
 }
 
-// --------------------------------------------------------------------------------------------
-// search (src/hnsw/core.rs:398-467), batched
-// --------------------------------------------------------------------------------------------
-int HNSWIndex::search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
-                      uint32_t* counts) {
-  return search_impl(q, false, B, dim, k, ef, ids, dist, counts);
-}
-int HNSWIndex::search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                          float* dist, uint32_t* counts) {
-  return search_impl(q_dev, true, B, dim, k, ef, ids, dist, counts);
-}
-
 int HNSWIndex::ensure_graph_handle() {
   if (graph_) return FVDB_OK;
   int rc = fvdb_graph_create(store_, &graph_);
@@ -461,12 +449,6 @@ int HNSWIndex::ensure_host_graph() {
   return FVDB_OK;
 }
 
-bool HNSWIndex::device_path_ok(uint32_t ef) const {
-  static const bool env_off = getenv("FVDB_HNSW_DEVICE") && atoi(getenv("FVDB_HNSW_DEVICE")) == 0;
-  const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0);
-  return device_traversal_ && !env_off && maxdeg <= 64 && ef <= 4096;  // one lane per neighbour
-}
-
 // one device block and one pinned block per slot, [nodes B*k | dist B*k | counts B | status B] -> a single copy
 namespace {
 struct WalkBlock {
@@ -485,39 +467,100 @@ struct WalkBlock {
 };
 }  // namespace
 
-// whole batch in one launch, results copied to pinned host memory — all asynchronous on the slot's stream
-int HNSWIndex::device_launch(const float* q_dev, uint32_t B, uint32_t k, uint32_t ef, uint32_t slot, const AllowView* view) {
-  if (slot >= kSlots) return FVDB_E_INVALID;
-  int rc = sync_graph();
-  if (rc) return rc;
-  DevSlot& sl = slots_[slot];
-  rc = slot_ctx(ctx_, slot == 0, &sl.ctx);
-  if (rc) return rc;
-  const uint64_t bytes = WalkBlock(nullptr, B, k).bytes;
-  rc = sl.buf.reserve(sl.ctx, bytes, true);
-  if (rc) return rc;
-  const WalkBlock d(sl.buf.dev, B, k);
-  fvdb_ctx* on = slot == 0 ? nullptr : sl.ctx;
-  if (!view)
-    rc = fvdb_graph_search_dev_slot(graph_, on, slot, q_dev, B, k, ef, d.nodes, d.dist, d.counts, d.status);
-  else if (scans(*view, k))
-    rc = fvdb_graph_scan_allowed_dev_slot(graph_, on, slot, view->mask.get(), q_dev, B, k, d.nodes, d.dist, d.counts);
-  else
-    rc = fvdb_graph_search_dev_slot_masked(graph_, on, slot, view->mask.get(), q_dev, B, k, ef, d.nodes, d.dist, d.counts,
-                                           d.status);
-  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
+// --------------------------------------------------------------------------------------------
+// The five steps of a search (fvdb_host.hpp, HNSWIndex::Search)
+// --------------------------------------------------------------------------------------------
+// What an entry point answers before it reaches the device — DESIGN.md section 9l has the table.  The entry points
+// differ in WHERE the empty batch (B == 0 or k == 0) is answered, and a caller can tell: the filtered traversal
+// answers it before it looks at the dimension, the exact search after that, search() / search_dev() last of all.
+int HNSWIndex::admit(Search& s) {
+  s.route = Search::kAnswered;
+  const bool exact = s.kind == Search::kExact, filtered = s.by_list || s.view, nothing = s.B == 0 || s.k == 0;
+  if (exact && (s.k == 0 || s.k > FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
+  if (exact && s.slot >= kSlots) return FVDB_E_INVALID;  // a traversal's slot is launch()'s to refuse, after all of this
+  if (s.ids) fill_empty(s.ids, s.dist, s.counts, s.B, s.k);
+  // empty index -> empty results (:404-407); the exact scan needs the store too (a graph that has never held a row)
+  if (!has_entry_ || (exact && !store_)) return FVDB_OK;
+  if (!exact && filtered && nothing) return FVDB_OK;
+  if (has_dim_ && s.dim != dim_) return FVDB_E_DIM;
+  if (exact && nothing) return FVDB_OK;
+  if (s.by_list) {
+    if (int rc = allowed_view(s.allowed, s.n_allowed, &s.held)) return rc;
+    s.view = s.held.get();
+  }
+  // "Entry point node not found in index" (:422-429); the exact search does not start from it and still answers
+  if (!exact && entry_lost_) return FVDB_E_NOT_FOUND;
+  if (nothing) return FVDB_OK;
+  if (exact && s.view && !s.view->mask) return FVDB_OK;
+  // the scans are device kernels whatever the traversal setting; the traversal kernel has one lane per neighbour
+  static const bool env_off = getenv("FVDB_HNSW_DEVICE") && atoi(getenv("FVDB_HNSW_DEVICE")) == 0;
+  const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0);
+  s.scanned = exact || (s.view && scans(*s.view, s.k));
+  s.route = s.scanned || (device_traversal_ && !env_off && maxdeg <= 64 && s.ef <= 4096) ? Search::kDevice : Search::kHostWalk;
+  return FVDB_OK;
+}
+
+int HNSWIndex::stage(Search& s) {
+  s.q_dev = s.q;
+  if (s.q_on_device) return FVDB_OK;
+  const uint64_t bytes = (uint64_t)s.B * s.dim * 4;
+  int rc = d_q_.reserve(ctx_, bytes, false);
+  if (!rc) rc = fvdb_dev_upload(ctx_, d_q_.dev, s.q, bytes);
+  s.q_dev = (const float*)d_q_.dev;
   return rc;
 }
 
-// wait + translate; queries the kernel could not finish on chip are listed in `failed`
-int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts,
-                              std::vector<uint32_t>& failed, uint32_t slot, bool scanned) {
-  DevSlot& sl = slots_[slot];
+// whole batch in one launch, results copied to pinned host memory — all asynchronous on the slot's stream
+int HNSWIndex::launch(Search& s) {
+  if (s.slot >= kSlots) return FVDB_E_INVALID;
+  int rc = sync_graph();
+  if (rc) return rc;
+  DevSlot& sl = slots_[s.slot];
+  rc = slot_ctx(ctx_, s.slot == 0, &sl.ctx);
+  if (rc) return rc;
+  const uint64_t bytes = WalkBlock(nullptr, s.B, s.k).bytes;
+  rc = sl.buf.reserve(sl.ctx, bytes, true);
+  if (rc) return rc;
+  const WalkBlock d(sl.buf.dev, s.B, s.k);
+  fvdb_ctx* on = s.slot == 0 ? nullptr : sl.ctx;
+  fvdb_mask* mask = s.view ? s.view->mask.get() : nullptr;
+  if (s.kind == Search::kExact)
+    rc = fvdb_graph_search_flat_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, s.k, d.nodes, d.dist, d.counts);
+  else if (!s.view)
+    rc = fvdb_graph_search_dev_slot(graph_, on, s.slot, s.q_dev, s.B, s.k, s.ef, d.nodes, d.dist, d.counts, d.status);
+  else if (s.scanned)
+    rc = fvdb_graph_scan_allowed_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, s.k, d.nodes, d.dist, d.counts);
+  else
+    rc = fvdb_graph_search_dev_slot_masked(graph_, on, s.slot, mask, s.q_dev, s.B, s.k, s.ef, d.nodes, d.dist, d.counts, d.status);
+  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
+  sl.enqueued = rc == FVDB_OK;
+  sl.scanned = s.scanned;
+  return rc;
+}
+
+// wait + translate; then, rare, the queries the kernel could not finish on chip (heap / visited log overflow) walk on
+// the host.  A slot nothing was enqueued in: the search runs now, in slot 0.
+int HNSWIndex::finish(Search& s) {
+  if (s.slot >= kSlots) return FVDB_E_INVALID;
+  DevSlot& sl = slots_[s.slot];
+  // a request run() launched a moment ago (route kDevice) is collected whatever the mark says; one that arrives from
+  // search_dev_end has not been through admit() in this call
+  if (!sl.enqueued && s.route != Search::kDevice) {
+    s.slot = 0;
+    s.owns_slot = false;
+    return run(s);
+  }
+  sl.enqueued = false;
+  const uint32_t B = s.B, k = s.k;
+  uint64_t* const ids = s.ids;  // the loop below runs B x k times per batch: everything it reads is a local
+  uint32_t* const counts = s.counts;
+  const bool scanned = sl.scanned;
   int rc = fvdb_ctx_synchronize(sl.ctx);
   if (rc) return rc;
   const WalkBlock h(sl.buf.host, B, k);
-  std::memcpy(dist, h.dist, (size_t)B * k * 4);
+  std::memcpy(s.dist, h.dist, (size_t)B * k * 4);
   std::memcpy(counts, h.counts, (size_t)B * 4);
+  std::vector<uint32_t> failed;
   for (uint32_t b = 0; b < B; ++b) {
     if (!scanned && h.status[b]) {
       failed.push_back(b);
@@ -529,55 +572,87 @@ int HNSWIndex::device_collect(uint32_t B, uint32_t k, uint64_t* ids, float* dist
       ids[(size_t)b * k + i] = i < counts[b] ? ids_[nd] : FVDB_NO_ID;
     }
   }
-  return FVDB_OK;
-}
-
-// rare: on-chip heap / visited log overflow -> host walk for those queries
-int HNSWIndex::finish_failed(const float* q, bool q_on_device, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
-                             float* dist, uint32_t* counts, const std::vector<uint32_t>& failed, const AllowView* view) {
   if (failed.empty()) return FVDB_OK;
   n_fallback_ += failed.size();
-  int rcg = ensure_host_graph();
-  if (rcg) return rcg;
+  if ((rc = ensure_host_graph())) return rc;
   std::lock_guard<std::mutex> lk(walk_mu_);  // the host walk's scorer and heaps are one set per index
+  const uint32_t dim = s.dim;
   std::vector<float> hq((size_t)failed.size() * dim);
   for (size_t i = 0; i < failed.size(); ++i) {
-    if (q_on_device) {
-      int rc = fvdb_dev_download(ctx_, &hq[i * dim], q + (size_t)failed[i] * dim, (size_t)dim * 4);
-      if (rc) return rc;
+    if (s.q_on_device) {
+      if ((rc = fvdb_dev_download(ctx_, &hq[i * dim], s.q + (size_t)failed[i] * dim, (size_t)dim * 4))) return rc;
     } else {
-      std::memcpy(&hq[i * dim], q + (size_t)failed[i] * dim, (size_t)dim * 4);
+      std::memcpy(&hq[i * dim], s.q + (size_t)failed[i] * dim, (size_t)dim * 4);
     }
   }
   std::vector<uint64_t> fi(failed.size() * (size_t)k);
   std::vector<float> fd(failed.size() * (size_t)k);
   std::vector<uint32_t> fc(failed.size());
-  int rc = search_host_walk(hq.data(), false, (uint32_t)failed.size(), k, ef, fi.data(), fd.data(), fc.data(), view);
+  rc = search_host_walk(hq.data(), false, (uint32_t)failed.size(), k, s.ef, fi.data(), fd.data(), fc.data(), s.view);
   if (rc) return rc;
   for (size_t i = 0; i < failed.size(); ++i) {
-    std::memcpy(ids + (size_t)failed[i] * k, &fi[i * k], (size_t)k * 8);
-    std::memcpy(dist + (size_t)failed[i] * k, &fd[i * k], (size_t)k * 4);
-    counts[failed[i]] = fc[i];
+    std::memcpy(s.ids + (size_t)failed[i] * k, &fi[i * k], (size_t)k * 8);
+    std::memcpy(s.dist + (size_t)failed[i] * k, &fd[i * k], (size_t)k * 4);
+    s.counts[failed[i]] = fc[i];
   }
   return FVDB_OK;
 }
 
+// The standalone entry points work in slot 0 with one staging buffer, so calls from several host threads take turns
+// (HybridIndex gives each of its concurrent searches a slot of its own and says so: owns_slot).
+int HNSWIndex::run(Search& s) {
+  int rc = admit(s);
+  if (rc || s.route == Search::kAnswered) return rc;
+  std::unique_lock<std::mutex> serial(search_mu_, std::defer_lock);
+  if (!s.owns_slot) serial.lock();
+  if (s.route == Search::kHostWalk) {  // the queries go to the scorer from wherever they are
+    if ((rc = ensure_host_graph())) return rc;
+    std::lock_guard<std::mutex> lk(walk_mu_);
+    return search_host_walk(s.q, s.q_on_device, s.B, s.k, s.ef, s.ids, s.dist, s.counts, s.view);
+  }
+  if ((rc = stage(s)) || (rc = launch(s))) return rc;
+  return finish(s);
+}
+
+// --------------------------------------------------------------------------------------------
+// search (src/hnsw/core.rs:398-467), batched — the entry points
+// --------------------------------------------------------------------------------------------
+int HNSWIndex::search(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids, float* dist,
+                      uint32_t* counts) {
+  Search s{Search::kTraversal, q, false, B, dim, k, ef, ids, dist, counts};
+  return run(s);
+}
+
+int HNSWIndex::search_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
+                          float* dist, uint32_t* counts) {
+  Search s{Search::kTraversal, q_dev, true, B, dim, k, ef, ids, dist, counts};
+  return run(s);
+}
+
+int HNSWIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
+                              uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  Search s{Search::kTraversal, q, false, B, dim, k, ef, ids, dist, counts};
+  s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed;
+  return run(s);
+}
+
 bool HNSWIndex::search_dev_begin(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, int* rc,
                                  uint32_t slot, const AllowView* view) {
+  Search s{Search::kTraversal, q_dev, true, B, dim, k, ef, nullptr, nullptr, nullptr};
+  s.slot = slot, s.view = view;
   *rc = FVDB_OK;
-  if (entry_lost_) return false;  // the caller's search_dev fallback reports the error
-  const bool scan = view && scans(*view, k);  // the exact scan is a device kernel whatever the traversal setting
-  if (!has_entry_ || B == 0 || k == 0 || (has_dim_ && dim != dim_) || (!scan && !device_path_ok(ef))) return false;
-  *rc = device_launch(q_dev, B, k, ef, slot, view);
+  if (slot < kSlots) slots_[slot].enqueued = false;
+  // whatever the checks found, the end reports it: it runs them again with somewhere to put the answer
+  if (admit(s) != FVDB_OK || s.route != Search::kDevice) return false;
+  if ((*rc = stage(s)) == FVDB_OK) *rc = launch(s);
   return *rc == FVDB_OK;
 }
 
 int HNSWIndex::search_dev_end(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, uint64_t* ids,
                               float* dist, uint32_t* counts, uint32_t slot, const AllowView* view) {
-  std::vector<uint32_t> failed;
-  int rc = device_collect(B, k, ids, dist, counts, failed, slot, view && scans(*view, k));
-  if (rc) return rc;
-  return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed, view);
+  Search s{Search::kTraversal, q_dev, true, B, dim, k, ef, ids, dist, counts};
+  s.slot = slot, s.view = view;
+  return finish(s);
 }
 
 // ---- filtered search ----
@@ -623,45 +698,6 @@ int HNSWIndex::allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef
   return FVDB_OK;
 }
 
-int HNSWIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
-                              uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_ || B == 0 || k == 0) return FVDB_OK;
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  ViewRef view;
-  int rc = allowed_view(allowed, n_allowed, &view);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> serial(search_mu_);  // slot 0 and one staging buffer, like search()
-  const uint64_t bytes = (uint64_t)B * dim * 4;
-  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
-  return search_view_locked((const float*)d_q_.dev, B, dim, k, ef, *view, ids, dist, counts);
-}
-
-int HNSWIndex::search_dev_view(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
-                               uint64_t* ids, float* dist, uint32_t* counts) {
-  std::lock_guard<std::mutex> serial(search_mu_);
-  return search_view_locked(q_dev, B, dim, k, ef, view, ids, dist, counts);
-}
-
-int HNSWIndex::search_view_locked(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowView& view,
-                                  uint64_t* ids, float* dist, uint32_t* counts) {
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_ || B == 0 || k == 0) return FVDB_OK;
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  if (entry_lost_) return FVDB_E_NOT_FOUND;
-  const bool scan = scans(view, k);
-  int rc;
-  if (!scan && !device_path_ok(ef)) {
-    if ((rc = ensure_host_graph())) return rc;
-    std::lock_guard<std::mutex> lk(walk_mu_);
-    return search_host_walk(q_dev, true, B, k, ef, ids, dist, counts, &view);
-  }
-  if ((rc = device_launch(q_dev, B, k, ef, 0, &view))) return rc;
-  std::vector<uint32_t> failed;
-  if ((rc = device_collect(B, k, ids, dist, counts, failed, 0, scan))) return rc;
-  return finish_failed(q_dev, true, dim, k, ef, ids, dist, counts, failed, &view);
-}
-
 // ---- exact search and search quality ----
 int compare_id_blocks(fvdb_ctx* ctx, DevBuf& stage, uint32_t B, uint32_t k, const uint64_t* res_ids, const uint32_t* res_counts,
                       const uint64_t* truth_ids, const uint32_t* truth_counts, float* total_recall, float* total_precision) {
@@ -695,55 +731,21 @@ int compare_id_blocks(fvdb_ctx* ctx, DevBuf& stage, uint32_t B, uint32_t k, cons
 
 int HNSWIndex::search_exact_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
                                 float* dist, uint32_t* counts, uint32_t slot) {
-  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
-  if (slot >= kSlots) return FVDB_E_INVALID;
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_ || !store_) return FVDB_OK;  // a graph that has never held a row
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  if (B == 0) return FVDB_OK;
-  int rc = sync_graph();
-  if (rc) return rc;
-  DevSlot& sl = slots_[slot];
-  if ((rc = slot_ctx(ctx_, slot == 0, &sl.ctx))) return rc;
-  const uint64_t bytes = WalkBlock(nullptr, B, k).bytes;
-  if ((rc = sl.buf.reserve(sl.ctx, bytes, true))) return rc;
-  const WalkBlock d(sl.buf.dev, B, k);
-  rc = fvdb_graph_search_flat_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, view ? view->mask.get() : nullptr, q_dev, B, k,
-                                       d.nodes, d.dist, d.counts);
-  if (!rc) rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes);
-  if (rc) return rc;
-  std::vector<uint32_t> none;
-  return device_collect(B, k, ids, dist, counts, none, slot, true);
+  Search s{Search::kExact, q_dev, true, B, dim, k, 0, ids, dist, counts};
+  s.view = view, s.slot = slot, s.owns_slot = true;
+  return run(s);
 }
 
 int HNSWIndex::search_exact(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
-  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_ || !store_) return FVDB_OK;
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  if (B == 0) return FVDB_OK;
-  std::lock_guard<std::mutex> serial(search_mu_);  // slot 0 and one staging buffer, like search()
-  const uint64_t bytes = (uint64_t)B * dim * 4;
-  int rc;
-  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
-  return search_exact_dev((const float*)d_q_.dev, B, dim, k, nullptr, ids, dist, counts, 0);
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  return run(s);
 }
 
 int HNSWIndex::search_exact_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed,
                                     uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
-  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_ || !store_) return FVDB_OK;
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  if (B == 0) return FVDB_OK;
-  ViewRef view;
-  int rc = allowed_view(allowed, n_allowed, &view);
-  if (rc) return rc;
-  if (!view->mask) return FVDB_OK;
-  std::lock_guard<std::mutex> serial(search_mu_);
-  const uint64_t bytes = (uint64_t)B * dim * 4;
-  if ((rc = d_q_.reserve(ctx_, bytes, false)) || (rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes))) return rc;
-  return search_exact_dev((const float*)d_q_.dev, B, dim, k, view.get(), ids, dist, counts, 0);
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed;
+  return run(s);
 }
 
 int HNSWIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out) {
@@ -763,45 +765,8 @@ int HNSWIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim,
     std::lock_guard<std::mutex> serial(search_mu_);  // qual_ is one block: calls take turns
     if ((rc = compare_id_blocks(ctx_, qual_, B, k, rid.data(), rcn.data(), tid.data(), tcn.data(), &tr, &tp))) return rc;
   }
-  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
-  out->avg_recall = tr / (float)B;
-  out->avg_precision = tp / (float)B;
-  out->avg_query_time_ms = elapsed.count() / (float)B;
-  out->queries_evaluated = B;
+  *out = quality_of(tr, tp, B, start);
   return FVDB_OK;
-}
-
-int HNSWIndex::search_impl(const float* q, bool q_on_device, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef,
-                           uint64_t* ids, float* dist, uint32_t* counts) {
-  fill_empty(ids, dist, counts, B, k);
-  if (!has_entry_) return FVDB_OK;  // empty index -> empty results (:404-407)
-  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
-  if (entry_lost_) return FVDB_E_NOT_FOUND;  // "Entry point node not found in index" (:422-429)
-  if (B == 0 || k == 0) return FVDB_OK;
-  // standalone entry point: slot 0 and one staging buffer => calls from several host threads take turns here
-  // (HybridIndex gives each of its concurrent searches a slot of its own through search_dev_begin/_end)
-  std::lock_guard<std::mutex> serial(search_mu_);
-  if (!device_path_ok(ef)) {
-    int rcg = ensure_host_graph();
-    if (rcg) return rcg;
-    std::lock_guard<std::mutex> lk(walk_mu_);
-    return search_host_walk(q, q_on_device, B, k, ef, ids, dist, counts);
-  }
-  const float* qd = q;
-  if (!q_on_device) {  // stage the batch in HBM
-    const uint64_t bytes = (uint64_t)B * dim * 4;
-    int rc = d_q_.reserve(ctx_, bytes, false);
-    if (rc) return rc;
-    rc = fvdb_dev_upload(ctx_, d_q_.dev, q, bytes);
-    if (rc) return rc;
-    qd = (const float*)d_q_.dev;
-  }
-  int rc = device_launch(qd, B, k, ef, 0);
-  if (rc) return rc;
-  std::vector<uint32_t> failed;
-  rc = device_collect(B, k, ids, dist, counts, failed, 0);
-  if (rc) return rc;
-  return finish_failed(q, q_on_device, dim, k, ef, ids, dist, counts, failed);
 }
 
 // The layered walk on the host (:398-467) for chunks of at most 16384 queries in lock step: one scorer launch per hop

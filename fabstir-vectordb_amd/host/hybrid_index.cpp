@@ -529,14 +529,35 @@ int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, u
   lease.hand_over();  // whatever begin_impl returns, the slot stays the caller's until search_dev_end
   slots_[slot].ivf_mask.reset();  // the explicit pair is an unfiltered search, unless it names an allow-set
   slots_[slot].view.reset();
-  if (masked && initialized_ && cfg.k != 0) {
-    // built as search_impl builds them: after the migration, under the read lock; search_dev_end drops them
-    if (cfg.search_recent)
-      if (int rc = recent_->allowed_view(allowed, n_allowed, &slots_[slot].view)) return rc;
-    if (cfg.search_historical && ivf_trained_)
-      if (int rc = historical_->allowed_mask(allowed, n_allowed, &slots_[slot].ivf_mask)) return rc;
-  }
+  if (masked && initialized_ && cfg.k != 0)  // search_dev_end drops them
+    if (int rc = build_masks(cfg, allowed, n_allowed, &slots_[slot].view, &slots_[slot].ivf_mask)) return rc;
   return begin_impl(slot, q_dev, B, dim, cfg, shard_mode);
+}
+
+// The masks of a filtered search, one per part that is searched.  Every caller builds them after the migration step and
+// under the read lock that keeps the rows where they are until the search has its results.
+int HybridIndex::build_masks(const HybridSearchConfig& cfg, const uint64_t* allowed, uint64_t n_allowed, HNSWIndex::ViewRef* view,
+                             MaskRef* ivf_mask) {
+  if (cfg.search_recent)
+    if (int rc = recent_->allowed_view(allowed, n_allowed, view)) return rc;
+  if (cfg.search_historical && ivf_trained_)
+    if (int rc = historical_->allowed_mask(allowed, n_allowed, ivf_mask)) return rc;
+  return FVDB_OK;
+}
+
+// NaN / Inf in a query: the reference panics in partial_cmp().unwrap()
+static int check_finite(const float* q, uint64_t n) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  return FVDB_OK;
+}
+// host queries, checked, into the slot's staging block; both parts read them from there
+int HybridIndex::stage_finite(Slot& sl, const float* q, uint32_t B, uint32_t dim) {
+  const uint64_t bytes = (uint64_t)B * dim * 4;
+  if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;
+  if (int rc = sl.d_q.reserve(ctx_ivf_, bytes, false)) return rc;
+  if (slot_ctx(ctx_ivf_, &sl == slots_, &sl.ivf_ctx)) return FVDB_E_HIP;
+  return fvdb_dev_upload(sl.ivf_ctx, sl.d_q.dev, q, bytes);  // waits on the slot's own stream only
 }
 
 int HybridIndex::attach_comm(fvdb_comm* comm) {
@@ -617,8 +638,8 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
   sl.B = B;
   sl.dim = dim;
   sl.k = (uint32_t)cfg.k;
-  sl.rk = (uint32_t)(cfg.recent_k > 0 ? cfg.recent_k : cfg.k);
-  sl.hk = (uint32_t)(cfg.historical_k > 0 ? cfg.historical_k : cfg.k);
+  sl.rk = cfg.rk();
+  sl.hk = cfg.hk();
   sl.ef = (uint32_t)cfg.hnsw_ef;
   sl.recent = cfg.search_recent;
   if (!initialized_ || sl.k == 0 || (B == 0 && shard_mode < 0)) return FVDB_OK;
@@ -677,13 +698,7 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   Slot& sl = *lease.sl;
   const uint32_t B = sl.B, k = sl.k;
   // a filtered search's masks stay referenced until its results are in, whichever way this returns
-  struct DropMasks {
-    Slot& sl;
-    ~DropMasks() {
-      sl.ivf_mask.reset();
-      sl.view.reset();
-    }
-  } drop_masks{sl};
+  DropMasks drop_masks{&sl};
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   std::vector<uint64_t> rid;
@@ -693,15 +708,8 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   if (sl.recent) {
     rid.resize((size_t)B * sl.rk);
     rd.resize((size_t)B * sl.rk);
-    int rc2;
-    if (sl.hnsw_in_flight) {
-      rc2 = recent_->search_dev_end(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data(), slot, sl.view.get());
-    } else if (sl.view) {  // nothing was enqueued (host-walk setting): the standalone filtered search
-      rc2 = recent_->search_dev_view(sl.q, B, sl.dim, sl.rk, sl.ef, *sl.view, rid.data(), rd.data(), rc_.data());
-    } else {
-      rc2 = recent_->search_dev(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data());
-    }
-    have_r = rc2 == FVDB_OK;
+    // the graph's slot remembers whether the begin enqueued anything; if not, this is the blocking search
+    have_r = recent_->search_dev_end(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data(), slot, sl.view.get()) == FVDB_OK;
   }
   IvfBlock h;
   if (sl.ivf_in_flight) {
@@ -740,12 +748,8 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
   // are until this search has its results
   MaskRef ivf_mask;
   HNSWIndex::ViewRef view;
-  if (masked) {
-    if (cfg.search_recent)
-      if (int rc = recent_->allowed_view(allowed, n_allowed, &view)) return rc;
-    if (cfg.search_historical && ivf_trained_)
-      if (int rc = historical_->allowed_mask(allowed, n_allowed, &ivf_mask)) return rc;
-  }
+  if (masked)
+    if (int rc = build_masks(cfg, allowed, n_allowed, &view, &ivf_mask)) return rc;
   Lease lease(this, Lease::kAnyFree, Lease::kTake);  // given back at every return, until search_dev_end takes it over
   Slot& sl = *lease.sl;
   const uint32_t slot = lease.index();
@@ -753,23 +757,10 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
   sl.view = view;
   // the slot keeps them only while this search runs: search_dev_end drops them when it collects the batch, and every
   // return before the slot is handed to it drops them here — the next user of the slot must find none
-  struct DropMasks {
-    Slot* sl;
-    ~DropMasks() {
-      if (!sl) return;
-      sl->ivf_mask.reset();
-      sl->view.reset();
-    }
-  } drop_masks{&sl};
+  DropMasks drop_masks{&sl};
   const float* qd = q;
   if (!q_on_device) {  // stage the batch in HBM once; both parts read it from there
-    const uint64_t bytes = (uint64_t)B * dim * 4;
-    if (int rc = sl.d_q.reserve(ctx_ivf_, bytes, false)) return rc;
-    if (slot_ctx(ctx_ivf_, slot == 0, &sl.ivf_ctx)) return FVDB_E_HIP;
-    for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
-      if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;  // NaN / Inf: the reference panics in partial_cmp().unwrap()
-    const int rcu = fvdb_dev_upload(sl.ivf_ctx, sl.d_q.dev, q, bytes);  // waits on the slot's own stream only
-    if (rcu) return rcu;
+    if (int rc = stage_finite(sl, q, B, dim)) return rc;
     qd = (const float*)sl.d_q.dev;
   }
   const int rc0 = begin_impl(slot, qd, B, dim, cfg);
@@ -792,9 +783,8 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
 int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
                               uint32_t* counts) {
   const uint32_t k = (uint32_t)cfg.k;
-  const uint32_t rk = (uint32_t)(cfg.recent_k > 0 ? cfg.recent_k : cfg.k), hk = (uint32_t)(cfg.historical_k > 0 ? cfg.historical_k : cfg.k);
-  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
-    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  const uint32_t rk = cfg.rk(), hk = cfg.hk();
+  if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;  // whichever parts are searched, and before any other refusal
   std::vector<uint64_t> rid, hid;
   std::vector<float> rd, hd;
   std::vector<uint32_t> rc_(B, 0), hc(B, 0);
@@ -805,13 +795,9 @@ int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const Hy
     rd.resize((size_t)B * rk);
     Lease lease(this, Lease::kAnyFree, Lease::kTake);
     Slot& sl = *lease.sl;
-    const uint32_t slot = lease.index();
-    const uint64_t bytes = (uint64_t)B * dim * 4;
     int rc;
-    if ((rc = sl.d_q.reserve(ctx_ivf_, bytes, false))) return rc;
-    if (slot_ctx(ctx_ivf_, slot == 0, &sl.ivf_ctx)) return FVDB_E_HIP;
-    if ((rc = fvdb_dev_upload(sl.ivf_ctx, sl.d_q.dev, q, bytes))) return rc;
-    if ((rc = recent_->search_exact_dev((const float*)sl.d_q.dev, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), slot)))
+    if ((rc = stage_finite(sl, q, B, dim))) return rc;
+    if ((rc = recent_->search_exact_dev((const float*)sl.d_q.dev, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())))
       return rc;
   }
   if (have_h) {
@@ -860,11 +846,7 @@ int HybridIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t di
     std::lock_guard<std::mutex> lk(qual_mu_);
     if ((rc = compare_id_blocks(ctx_ivf_, qual_, B, k, rid.data(), rcn.data(), tid.data(), tcn.data(), &tr, &tp))) return rc;
   }
-  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
-  out->avg_recall = tr / (float)B;
-  out->avg_precision = tp / (float)B;
-  out->avg_query_time_ms = elapsed.count() / (float)B;
-  out->queries_evaluated = B;
+  *out = quality_of(tr, tp, B, start);
   return FVDB_OK;
 }
 

@@ -159,11 +159,7 @@ int IVFIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, 
     total_recall += h[b];
     total_precision += h[B + b];
   }
-  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
-  out->avg_recall = total_recall / (float)B;
-  out->avg_precision = total_precision / (float)B;
-  out->avg_query_time_ms = elapsed.count() / (float)B;
-  out->queries_evaluated = B;
+  *out = quality_of(total_recall, total_precision, B, start);
   return FVDB_OK;
 }
 
