@@ -43,6 +43,12 @@ class GraphMaintenanceInfo(C.Structure):
                [(n, f32) for n in ("ms_scan", "ms_prune", "ms_move", "ms_total")]
 
 
+class GraphSearchInfo(C.Structure):
+    """fvdb_graph_search_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("visited", "kernel", "nb128", "rows_per_round", "nearest_in_registers", "tcap",
+                                   "cand_cap", "spill_cap", "lds_bytes", "reserved")] + [("visited_bytes", u64)]
+
+
 VACUUM_KEEP_ROWS = 1  # FVDB_VACUUM_KEEP_ROWS
 
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
@@ -139,6 +145,7 @@ SIGNATURES = {
     "fvdb_graph_upload_bytes": (u64, [vp]),
     "fvdb_graph_set_insert_visited": (i32, [vp, i32, u32]),
     "fvdb_graph_insert_info": (i32, [vp, u32, vp]),
+    "fvdb_graph_search_info": (i32, [vp, u32, u32, C.POINTER(GraphSearchInfo)]),
     "fvdb_graph_vacuum": (i32, [vp, u32, u64p]),
     "fvdb_graph_maintenance_info": (i32, [vp, C.POINTER(GraphMaintenanceInfo)]),
     "fvdb_graph_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),

@@ -456,19 +456,22 @@ ExactKernel exact_kernel(bool rh, bool f16) {
   return rh ? hnsw_search_kernel<true> : hnsw_search_kernel<false>;
 }
 
-// What one traversal launch works with: the slot's scratch and its numbers (search_scratch), the kernel (search_kernel).
+// What one traversal launch works with.  search_plan decides all of it from (graph, B, ef) and touches nothing: the
+// launch path and fvdb_graph_search_info both ask it, so a report cannot drift from what runs.  search_scratch then sizes
+// the slot's buffers for the plan.
 struct SearchPlan {
   bool bytemap;  // `visited` of a query: one byte per node, else one bit
   uint32_t words, vstride, tcap, spill_cap, cand_cap;
-  size_t lds;         // dynamic LDS of a workgroup: of the exact-heap search first, then of the kernel chosen
+  uint32_t nb128;     // 128-dimension blocks of a padded row
+  int R;              // rows per scoring round of the sorted-register kernel (0: the exact-heap kernel runs)
+  size_t lds;         // dynamic LDS of a workgroup of the kernel chosen
   uint32_t wave_lds;  // the sorted-register kernel's share of it per query (4 queries to a workgroup)
   FastKernel fast;    // the sorted-register kernel, or
   ExactKernel exact;  // the exact-heap kernel, one query per workgroup;
   bool rh;            // its `nearest` in registers (ef <= 63): the candidates heap may continue in the HBM spill
 };
 
-// sizes and (re)zeroes the slot's visited maps, touched log and spill for (B, n)
-int search_scratch(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, uint32_t B, uint32_t ef, SearchPlan* sp) {
+int search_plan(const fvdb_graph* g, fvdb_ctx* ctx, uint32_t B, uint32_t ef, SearchPlan* sp) {
   // visited-log capacity per query: a query that outgrows it clears its whole map at the end of the layer instead of
   // entry by entry (FVDB_GRAPH_TCAP: test hook that forces that)
   sp->words = (g->n + 31) / 32;
@@ -479,6 +482,42 @@ int search_scratch(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, uint32_t B, uint
   const uint32_t vbytes = ((g->n + 63) / 64) * 64;
   sp->bytemap = !no_bytes && (uint64_t)vbytes * std::max<uint32_t>(B, 1024) <= (1ull << 30);
   sp->vstride = sp->bytemap ? vbytes : sp->words * 4;
+  // where the restated candidates heap continues when it outgrows its LDS slots (duplicate-heavy data): no node is
+  // admitted twice, so a query never needs more than n slots
+  sp->spill_cap = std::min<uint32_t>(((g->n + 63) / 64) * 64, 8192);
+  // candidate-heap slots of the exact-heap search: it holds every admitted node not yet expanded; a query that
+  // overflows it goes to the host walk (data with many duplicate vectors fills it quickly, so it stays generous:
+  // at the default tile size the sorted-register kernel's LDS need is larger anyway)
+  const int cand_env = getenv("FVDB_GRAPH_CAND_CAP") ? atoi(getenv("FVDB_GRAPH_CAND_CAP")) : 0;  // test hook: forces the host-walk fallback
+  sp->cand_cap = cand_env > 0 ? (uint32_t)cand_env : std::max<uint32_t>(1024, 8 * ef);
+  sp->lds = graph_lds_bytes(g->store->dpad, ef, sp->cand_cap);  // of the exact-heap search
+  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
+  static const bool lds_heaps = getenv("FVDB_GRAPH_LDS_HEAPS") != nullptr;  // tuning aid: lane-0 heaps for any ef
+  sp->rh = ef <= 63 && !lds_heaps;
+  // ef <= 63: the sorted-register kernel; a query in which two heap members meet with equal distances is re-run by
+  // the same wave with the reference's heaps restated (exact on ties)
+  static const bool no_fast = getenv("FVDB_GRAPH_NO_FAST") != nullptr;  // tuning aid / A-B
+  static const int fast_r = getenv("FVDB_GRAPH_FAST_R") ? atoi(getenv("FVDB_GRAPH_FAST_R")) : 0;
+  sp->nb128 = (g->store->dpad + 127) / 128;
+  sp->R = 0;
+  sp->wave_lds = 0;
+  sp->fast = nullptr;
+  sp->exact = nullptr;
+  if (no_fast || !sp->rh || sp->nb128 > 8 || g->n >= 0x80000000u) {
+    sp->exact = exact_kernel(sp->rh, g->store->f16());
+    return FVDB_OK;
+  }
+  sp->R = sp->nb128 <= 3 ? 16 : (sp->nb128 == 4 ? 12 : (sp->nb128 <= 6 ? 8 : 6));  // rows per scoring round: registers R*NB*2
+  if (sp->nb128 == 3 && (fast_r == 8 || fast_r == 12)) sp->R = fast_r;
+  sp->wave_lds = (uint32_t)((std::max(graph_fast_lds_bytes((uint32_t)sp->R), sp->lds) + 15) & ~(size_t)15);
+  sp->lds = 4 * (size_t)sp->wave_lds;
+  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
+  sp->fast = fast_kernel(sp->nb128, sp->R, sp->bytemap, g->store->f16());
+  return FVDB_OK;
+}
+
+// sizes and (re)zeroes the slot's visited maps, touched log and spill for the plan of (B, n)
+int search_scratch(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, uint32_t B, const SearchPlan* sp) {
   if (sp->words != g->vis_words || sp->tcap != g->vis_tcap || sp->vstride != g->vis_stride) {
     for (auto& v : g->vis_B) v = 0;
     g->vis_words = sp->words;
@@ -491,38 +530,7 @@ int search_scratch(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, uint32_t B, uint
     HIPCHK(ctx, g->s_touched[slot].ensure((size_t)B * sp->tcap * 4));
     g->vis_B[slot] = B;
   }
-  // where the restated candidates heap continues when it outgrows its LDS slots (duplicate-heavy data): no node is
-  // admitted twice, so a query never needs more than n slots
-  sp->spill_cap = std::min<uint32_t>(((g->n + 63) / 64) * 64, 8192);
   HIPCHK(ctx, g->s_spill[slot].ensure((size_t)B * sp->spill_cap * 8));
-  // candidate-heap slots of the exact-heap search: it holds every admitted node not yet expanded; a query that
-  // overflows it goes to the host walk (data with many duplicate vectors fills it quickly, so it stays generous:
-  // at the default tile size the sorted-register kernel's LDS need is larger anyway)
-  const int cand_env = getenv("FVDB_GRAPH_CAND_CAP") ? atoi(getenv("FVDB_GRAPH_CAND_CAP")) : 0;  // test hook: forces the host-walk fallback
-  sp->cand_cap = cand_env > 0 ? (uint32_t)cand_env : std::max<uint32_t>(1024, 8 * ef);
-  sp->lds = graph_lds_bytes(g->store->dpad, ef, sp->cand_cap);
-  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
-  return FVDB_OK;
-}
-
-int search_kernel(fvdb_graph* g, fvdb_ctx* ctx, uint32_t ef, SearchPlan* sp) {
-  static const bool lds_heaps = getenv("FVDB_GRAPH_LDS_HEAPS") != nullptr;  // tuning aid: lane-0 heaps for any ef
-  sp->rh = ef <= 63 && !lds_heaps;
-  // ef <= 63: the sorted-register kernel; a query in which two heap members meet with equal distances is re-run by
-  // the same wave with the reference's heaps restated (exact on ties)
-  static const bool no_fast = getenv("FVDB_GRAPH_NO_FAST") != nullptr;  // tuning aid / A-B
-  static const int fast_r = getenv("FVDB_GRAPH_FAST_R") ? atoi(getenv("FVDB_GRAPH_FAST_R")) : 0;
-  const uint32_t nb128 = (g->store->dpad + 127) / 128;
-  if (no_fast || !sp->rh || nb128 > 8 || g->n >= 0x80000000u) {
-    sp->exact = exact_kernel(sp->rh, g->store->f16());
-    return FVDB_OK;
-  }
-  int R = nb128 <= 3 ? 16 : (nb128 == 4 ? 12 : (nb128 <= 6 ? 8 : 6));  // rows per scoring round: registers R*NB*2
-  if (nb128 == 3 && (fast_r == 8 || fast_r == 12)) R = fast_r;
-  sp->wave_lds = (uint32_t)((std::max(graph_fast_lds_bytes((uint32_t)R), sp->lds) + 15) & ~(size_t)15);
-  sp->lds = 4 * (size_t)sp->wave_lds;
-  if (sp->lds > 160 * 1024) FAIL(ctx, FVDB_E_UNSUPPORTED, "dimension / ef too large for the on-chip traversal state");
-  sp->fast = fast_kernel(nb128, R, sp->bytemap, g->store->f16());
   return FVDB_OK;
 }
 
@@ -969,6 +977,29 @@ int fvdb_graph_insert_info(fvdb_graph* g, uint32_t ef_construction, fvdb_graph_i
   return FVDB_OK;
 }
 
+int fvdb_graph_search_info(fvdb_graph* g, uint32_t B, uint32_t ef, fvdb_graph_search_info_t* out) {
+  if (!g) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = g->store->ctx;
+  if (!out) FAIL(ctx, FVDB_E_INVALID, "search info: no output");
+  if (!g->uploaded || !g->has_entry) FAIL(ctx, FVDB_E_INVALID, "graph not uploaded");
+  if (ef == 0 || ef > 4096) FAIL(ctx, FVDB_E_UNSUPPORTED, "ef must be in 1..4096");
+  std::lock_guard<std::mutex> lk(g->mu);
+  SearchPlan sp{};
+  if (int rc = search_plan(g, ctx, B, ef, &sp)) return rc;
+  std::memset(out, 0, sizeof(*out));
+  out->visited = sp.bytemap ? FVDB_GRAPH_VISITED_BYTES : FVDB_GRAPH_VISITED_BITS;
+  out->kernel = sp.fast ? FVDB_GRAPH_KERNEL_SORTED : FVDB_GRAPH_KERNEL_HEAPS;
+  out->nb128 = sp.nb128;
+  out->rows_per_round = (uint32_t)sp.R;
+  out->nearest_in_registers = sp.rh ? 1u : 0u;
+  out->tcap = sp.tcap;
+  out->cand_cap = sp.cand_cap;
+  out->spill_cap = sp.spill_cap;
+  out->lds_bytes = (uint32_t)sp.lds;
+  out->visited_bytes = (uint64_t)B * sp.vstride;
+  return FVDB_OK;
+}
+
 // =============================================================================================
 // device-resident graph traversal
 // =============================================================================================
@@ -1005,7 +1036,7 @@ static int graph_search_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const f
   }
   SearchPlan sp{};
   int rc;
-  if ((rc = search_scratch(g, ctx, slot, B, ef, &sp)) || (rc = search_kernel(g, ctx, ef, &sp))) return rc;
+  if ((rc = search_plan(g, ctx, B, ef, &sp)) || (rc = search_scratch(g, ctx, slot, B, &sp))) return rc;
   if (sp.lds > 48 * 1024)
     HIPCHK(ctx, hipFuncSetAttribute(sp.fast ? (const void*)sp.fast : (const void*)sp.exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
   if (!g->d_counters.p) {

@@ -772,6 +772,22 @@ class HNSWIndex(_Base):
             "visited_mean": info.visited_entries / info.visited_searches if info.visited_searches else 0.0,
         }
 
+    def search_info(self, B, ef):
+        """What a device search of B queries at ef would run on the graph as it stands (fvdb_graph_search_info: the
+        launch's own plan, nothing allocated or launched): "visited" ("bytes" / "bits" per node), "kernel"
+        ("sorted_register" / "exact_heap"), "nb128", "rows_per_round" (0 for the exact-heap kernel),
+        "nearest_in_registers", "tcap", "cand_cap", "spill_cap", "lds_bytes", "visited_bytes" (the batch's maps)."""
+        g = self._graph()
+        if not g:
+            raise RuntimeError("search_info: the index has no device graph (empty, or a list longer than 64)")
+        info = _capi.GraphSearchInfo()
+        self._check(_capi.load().fvdb_graph_search_info(g, int(B), int(ef), C.byref(info)))
+        out = {name: int(getattr(info, name)) for name, _ in info._fields_ if name != "reserved"}
+        out["visited"] = (None, "bytes", "bits")[info.visited]
+        out["kernel"] = (None, "sorted_register", "exact_heap")[info.kernel]
+        out["nearest_in_registers"] = bool(info.nearest_in_registers)
+        return out
+
     def device_fallbacks(self):
         return int(self.lib.fvh_hnsw_device_fallbacks(self.h))
 

@@ -510,6 +510,28 @@ typedef struct fvdb_graph_insert_info_t {
 } fvdb_graph_insert_info_t;
 int fvdb_graph_set_insert_visited(fvdb_graph* g, int mode, uint32_t table_slots);
 int fvdb_graph_insert_info(fvdb_graph* g, uint32_t ef_construction, fvdb_graph_insert_info_t* out);
+/* search_info: what fvdb_graph_search_dev* would run for B queries at ef on the graph as it stands (node count, row
+ *   width and element), from the function the launch itself takes its plan from.  Allocates nothing, launches nothing;
+ *   the environment hooks the launch reads are read here too.  Same refusals as the search (graph not uploaded, ef
+ *   outside 1..4096, traversal state larger than LDS). */
+#define FVDB_GRAPH_VISITED_BYTES 1u   /* `visited` of a query: one byte per node */
+#define FVDB_GRAPH_VISITED_BITS 2u    /*                       one bit per node (atomicOr) */
+#define FVDB_GRAPH_KERNEL_SORTED 1u   /* hnsw_search_fast_kernel: `nearest` a sorted register array, four queries per workgroup */
+#define FVDB_GRAPH_KERNEL_HEAPS 2u    /* hnsw_search_kernel: the reference's heaps restated, one query per workgroup */
+typedef struct fvdb_graph_search_info_t {
+  uint32_t visited;               /* FVDB_GRAPH_VISITED_* */
+  uint32_t kernel;                /* FVDB_GRAPH_KERNEL_* */
+  uint32_t nb128;                 /* 128-dimension blocks of a padded row */
+  uint32_t rows_per_round;        /* rows one scoring round of the sorted-register kernel holds; 0 for the exact-heap kernel */
+  uint32_t nearest_in_registers;  /* exact-heap search (the kernel, or the restart after a tie): `nearest` in registers */
+  uint32_t tcap;                  /* entries of a query's visited log */
+  uint32_t cand_cap;              /* slots of the restated `candidates` heap in LDS */
+  uint32_t spill_cap;             /* slots of its continuation in HBM, per query */
+  uint32_t lds_bytes;             /* dynamic LDS of one workgroup */
+  uint32_t reserved;
+  uint64_t visited_bytes;         /* the batch's visited maps: B x the stride of one query's map */
+} fvdb_graph_search_info_t;
+int fvdb_graph_search_info(fvdb_graph* g, uint32_t B, uint32_t ef, fvdb_graph_search_info_t* out);
 
 /* ---- device-resident graph maintenance ---------------------------------------------------------
  * HNSWIndex::vacuum (src/hnsw/operations.rs:176-200: deleted nodes leave every neighbour set, then the node map) on

@@ -50,6 +50,8 @@ CASES = [  # n, d, M, M0, efc, seed
     (500, 384, 16, 32, 200, 3),   # BASELINE shape (C1 / C3 parameters)
     (300, 768, 16, 32, 200, 4),   # C5's dimension
     (350, 40, 4, 8, 300, 5),      # ef_construction above the sorted-register form: restated heaps only
+    (300, 512, 16, 32, 100, 6),   # f32 rows at four 128-dim blocks: 12 rows per traversal round
+    (250, 1024, 8, 16, 64, 7),    # f32 rows at eight blocks: 6 rows per round
 ]
 
 
