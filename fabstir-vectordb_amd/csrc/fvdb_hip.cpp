@@ -24,6 +24,7 @@
 #include "kernels_scan.h"
 #include "kernels_wide.h"
 #include "kernels_rank.h"
+#include "kernels_curve.h"
 #include "kernels_coarse.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma_wg.h"
@@ -189,6 +190,9 @@ struct IvfScratch {
   Buf s_wgbase{this};                // the same bases over the logical index, for the keys of a shard's wide search
   Buf s_rbase{this}, s_rarena{this};  // the full centroid ranking (kernels_rank.h): the same for the centroid table
   Buf s_qual{this};                   // fvdb_ivf_search_quality_dev: the two result blocks
+  // fvdb_ivf_quality_curve_dev (kernels_curve.h): live rows per list; per chunk the ranking, the truth's keys and hit
+  // counts, and the per-query recall and precision at every nprobe
+  Buf s_clive{this}, s_cprobes{this}, s_ckeys{this}, s_cval{this};
   Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
   // fvdb_ivf_get_rows (ivf_rows.h): slots and gathered rows of one fetch.  Not s_slots / s_in: in set 0 those are the
   // insert staging.  fetch_done: the last fetch that read s_fslots on a stream other than the set's own
@@ -1964,7 +1968,8 @@ struct IvfSearch {
   uint64_t* keys = nullptr;
   const uint32_t* given_probes = nullptr;  // [B][np] cluster ids in probe order: the coarse stage is skipped
   const float* given_thr = nullptr;        // [B] filter thresholds agreed between the ranks (Batch::given_thr)
-  uint32_t* probes_out = nullptr;          // COARSE_ONLY: [B][np]
+  uint32_t* probes_out = nullptr;          // [B][np] the ranking goes here: COARSE_ONLY's result; any other kind scans
+                                           // the lists from here instead of the set's own block, and the caller keeps it
 
   // Queries o .. o + b of the request; np = min(nprobe, nlist) as the driver clamped it.  The only place a stride is written.
   IvfSearch slice(uint32_t o, uint32_t b, uint32_t d, uint32_t np) const {
@@ -2061,8 +2066,10 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
       mark(ivf, E, EV_COARSE_SCANNED);
       mark(ivf, E, EV_COARSE_DONE);
     } else {
-      rc = run_coarse(ivf, E, qpad, r.B, np, r.probes_out ? r.probes_out : S.s_probes.as<uint32_t>(), nullptr);
+      uint32_t* ranked = r.probes_out ? r.probes_out : S.s_probes.as<uint32_t>();
+      rc = run_coarse(ivf, E, qpad, r.B, np, ranked, nullptr);
       if (rc) return rc;
+      probes = ranked;
     }
     if (R.kind == IvfSearch::COARSE_ONLY) continue;
     const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr, R.kind == IvfSearch::SHARD_WIDE};
@@ -2277,6 +2284,74 @@ int fvdb_ivf_search_quality_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, cons
     }
     hipLaunchKernelGGL(search_quality_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, ids[0], cnt[0], ids[1], cnt[1], B, k,
                        out_recall_dev, out_precision_dev);
+    HIPCHK(ctx, hipGetLastError());
+    return FVDB_OK;
+  });
+}
+
+// evaluate_search_quality at every nprobe from one search of every list (kernels_curve.h; src/ivf/operations.rs
+// :329-391 answers for one n_probe per call).  Per chunk of queries: the every-list search in centroid-rank order leaves
+// its ranking and its keys in blocks this call owns, one workgroup per query counts the truth rows of each rank, and one
+// thread per nprobe adds the chunk's values to the running sums in query order.
+// The chunk's ranking [chunk][nlist] and its two f32 matrices of that shape stay under this.
+constexpr uint64_t kCurveArenaBytes = 256ull << 20;
+static_assert(kCurveMaxLists == kRankSortMaxLists, "the curve's LDS tables and the ranking's sort serve the same indexes");
+int fvdb_ivf_quality_curve_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                               uint32_t k, uint32_t chunk_queries, float* out_recall_sum_dev, float* out_precision_sum_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  if (!q_dev || !out_recall_sum_dev || !out_precision_sum_dev) FAIL(ivf->ctx, FVDB_E_INVALID, "null buffer");
+  return on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask, [&](const Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    IvfScratch& S = *E.S;
+    if (!ivf->trained) FAIL(ctx, FVDB_E_NOT_TRAINED, "index not trained");
+    const uint32_t nlist = ivf->nlist;
+    const IvfSearch::Kind kind = k > FVDB_MAX_K ? IvfSearch::WIDE : IvfSearch::PROBED;
+    int rc = check_k(ctx, kind, k, nlist);
+    if (rc) return rc;
+    if ((rc = check_rank(ctx, ivf, nlist))) return rc;
+    if (ivf->glob_set) FAIL(ctx, FVDB_E_UNSUPPORTED, "the quality curve does not serve a shard of a larger index");
+    if (B == 0) return FVDB_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_table(ivf))) return rc;
+    uint32_t chunk = (uint32_t)std::max<uint64_t>(1, kCurveArenaBytes / ((uint64_t)nlist * 12));
+    if (chunk_queries) chunk = std::min(chunk, chunk_queries);
+    chunk = std::min(chunk, B);
+    const size_t mat = (size_t)chunk * nlist;
+    HIPCHK(ctx, S.s_clive.ensure((size_t)nlist * 4));
+    HIPCHK(ctx, S.s_cprobes.ensure(mat * 4));
+    HIPCHK(ctx, S.s_ckeys.ensure((size_t)chunk * k * 8 + (size_t)chunk * 4));
+    HIPCHK(ctx, S.s_cval.ensure(2 * mat * 4));
+    uint64_t* keys = S.s_ckeys.as<uint64_t>();
+    uint32_t* counts = (uint32_t*)(keys + (size_t)chunk * k);
+    float* recall = S.s_cval.as<float>();
+    float* precision = recall + mat;
+    // like rank_sort_kernel's: the attribute belongs to the function, so every call sets the same value, the largest served
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)curve_query_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(kCurveMaxLists * 8)));
+    const ListTable lists = list_table(ivf);
+    hipLaunchKernelGGL(list_live_kernel, dim3(cdiv(nlist, 4)), dim3(256), 0, ctx->stream, lists.off, lists.blocks,
+                       live_words(ivf, E), nlist, S.s_clive.as<uint32_t>());
+    HIPCHK(ctx, hipMemsetAsync(out_recall_sum_dev, 0, (size_t)nlist * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(out_precision_sum_dev, 0, (size_t)nlist * 4, ctx->stream));
+    for (uint32_t o = 0; o < B; o += chunk) {
+      const uint32_t b = std::min(chunk, B - o);
+      IvfSearch R{kind, q_dev + (size_t)o * ivf->d, b, k, nlist, nullptr, nullptr, counts, keys};
+      R.probes_out = S.s_cprobes.as<uint32_t>();
+      if ((rc = ivf_search(ivf, E, R))) return rc;
+      CurveArgs a{};
+      a.probes = S.s_cprobes.as<uint32_t>();
+      a.list_off = lists.off;
+      a.list_live = S.s_clive.as<uint32_t>();
+      a.keys = keys;
+      a.counts = counts;
+      a.np = nlist;
+      a.k = k;
+      a.recall = recall;
+      a.precision = precision;
+      hipLaunchKernelGGL(curve_query_kernel, dim3(b), dim3(kCurveThreads), (size_t)nlist * 8, ctx->stream, a);
+      hipLaunchKernelGGL(curve_sum_kernel, dim3(cdiv(nlist, 256)), dim3(256), 0, ctx->stream, recall, precision, b, nlist,
+                         out_recall_sum_dev, out_precision_sum_dev);
+    }
     HIPCHK(ctx, hipGetLastError());
     return FVDB_OK;
   });

@@ -118,6 +118,26 @@ int fvh_ivf_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32_
   if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
   return FVDB_OK;
 }
+// evaluate_search_quality at every n_probe = 1 .. n_clusters from one search of every list (IVFIndex::quality_curve).
+// out_recall / out_precision: n_out floats each, n_out = the index's lists (else FVDB_E_INVALID); out_ms: the wall time
+// per query.  use_allowed != 0: under the allow-set allowed[n_allowed] (an empty one allows nothing).
+int fvh_ivf_quality_curve(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, int use_allowed, const uint64_t* allowed,
+                          uint64_t n_allowed, uint32_t n_out, float* out_recall, float* out_precision, float* out_ms,
+                          uint64_t* queries_evaluated) {
+  static const uint64_t none = 0;
+  if (!out_recall || !out_precision) return FVDB_E_INVALID;
+  if (use_allowed && n_allowed && !allowed) return FVDB_E_INVALID;
+  IVFIndex::QualityCurve c;
+  const int rc = ((IVFIndex*)p)->quality_curve(q, B, d, k, use_allowed ? (n_allowed ? allowed : &none) : nullptr,
+                                               use_allowed ? n_allowed : 0, &c);
+  if (rc) return rc;
+  if (c.avg_recall.size() != n_out) return FVDB_E_INVALID;
+  std::memcpy(out_recall, c.avg_recall.data(), (size_t)n_out * 4);
+  std::memcpy(out_precision, c.avg_precision.data(), (size_t)n_out * 4);
+  if (out_ms) *out_ms = c.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = c.queries_evaluated;
+  return FVDB_OK;
+}
 // rows by id, read back from HBM (src/ivf/core.rs:553-562); found[i] = 0 leaves row i of out untouched
 int fvh_ivf_get_vectors(void* p, const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
   return ((IVFIndex*)p)->get_vectors(ids, n, out, found);

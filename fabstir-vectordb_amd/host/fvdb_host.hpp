@@ -229,6 +229,18 @@ class IVFIndex {
   // call over B (the reference times each query by itself).  B == 0 is FVDB_E_INVALID (:334-338).
   typedef fvdbh::SearchQuality SearchQuality;  // operations.rs SearchQuality
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, SearchQuality* out);
+  // The same figures at every n_probe = 1 .. n_clusters from ONE search of every list (fvdb_ivf_quality_curve_dev,
+  // DESIGN.md section 9m): avg_recall[p - 1] / avg_precision[p - 1] are what evaluate_search_quality would return with
+  // n_probe = p configured, bit for bit, provided no id is stored in two lists (otherwise rows are counted, not ids).
+  // allowed != nullptr: under that allow-set (the cached mask of search_allowed), "live" meaning allowed and live.
+  // evaluate_search_quality's refusals in its order.
+  struct QualityCurve {
+    std::vector<float> avg_recall, avg_precision;  // [n_clusters]
+    float avg_query_time_ms = 0.0f;                // wall time of the call over B
+    uint64_t queries_evaluated = 0;
+  };
+  int quality_curve(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
+                    QualityCurve* out);
   uint64_t cluster_size(uint32_t c) const;
   // list `c` in list-position order, copied back from HBM (save path, src/hybrid/persistence.rs:289-311)
   int export_list(uint32_t c, float* rows, uint64_t* ids, uint8_t* live) const;

@@ -163,6 +163,44 @@ int IVFIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, 
   return FVDB_OK;
 }
 
+// evaluate_search_quality (operations.rs:329-391) for every n_probe at once: the sums over the queries come from the
+// device in query order (fvdb_ivf_quality_curve_dev), the division by B is the reference's (:386-387).
+int IVFIndex::quality_curve(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
+                            QualityCurve* out) {
+  if (B == 0) return FVDB_E_INVALID;  // "No test queries provided"
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  if (!q || !out) return FVDB_E_INVALID;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  const auto start = std::chrono::steady_clock::now();
+  MaskRef mask;
+  int rc;
+  if (allowed && (rc = allowed_mask(allowed, n_allowed, &mask))) return rc;
+  std::lock_guard<std::mutex> lk(allowed_mu_);  // search_allowed's staging blocks: calls take turns
+  const uint32_t nlist = dev_clusters_;
+  const uint64_t bytes = (uint64_t)nlist * 8;  // recall sums [nlist], precision sums [nlist]
+  if ((rc = allowed_q_.reserve(ctx_, (uint64_t)B * dim * 4, false)) || (rc = allowed_out_.reserve(ctx_, bytes, true))) return rc;
+  if ((rc = fvdb_dev_upload(ctx_, allowed_q_.dev, q, (size_t)B * dim * 4))) return rc;
+  float* d = (float*)allowed_out_.dev;
+  rc = fvdb_ivf_quality_curve_dev(dev_, nullptr, 0, mask.get(), (const float*)allowed_q_.dev, B, k, 0, d, d + nlist);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx_, allowed_out_.host, allowed_out_.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(ctx_)))
+    return rc;
+  const float* h = (const float*)allowed_out_.host;
+  out->avg_recall.resize(nlist);
+  out->avg_precision.resize(nlist);
+  for (uint32_t p = 0; p < nlist; ++p) {
+    out->avg_recall[p] = h[p] / (float)B;
+    out->avg_precision[p] = h[nlist + p] / (float)B;
+  }
+  const std::chrono::duration<float, std::milli> elapsed = std::chrono::steady_clock::now() - start;
+  out->avg_query_time_ms = elapsed.count() / (float)B;
+  out->queries_evaluated = B;
+  return FVDB_OK;
+}
+
 // "Collect all existing vectors ... train ... clear ... reinsert" (operations.rs:158-186, :231-250) without the rows
 // leaving HBM.  The reference's re-insert loop stops at the first DuplicateVector (`?` at :185 / :249): an id stored in
 // two lists (the duplicate check is per list, src/ivf/core.rs:128-134) whose copies now meet in one list.  The rows

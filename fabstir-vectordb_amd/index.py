@@ -147,6 +147,8 @@ HOST_SIGNATURES = {
     "fvh_hybrid_migration_info": (i32, [vp, vp]),
     # recall self-evaluation at any n_probe
     "fvh_ivf_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, f32p, u64p]),
+    # recall and precision at every n_probe from one search of every list
+    "fvh_ivf_quality_curve": (i32, [vp, f32p, u32, u32, u32, i32, u64p, u64, u32, f32p, f32p, f32p, u64p]),
     # half-precision rows: the constructors with a row_dtype, the doors' rounding routine
     "fvh_ivf_new_ex": (vp, [vp, u32, u32, u32, u32, u64, i32]),
     "fvh_hnsw_new_ex": (vp, [vp, u32, u32, u32, u64, i32]),
@@ -401,6 +403,35 @@ class IVFIndex(_Base):
         self._check(self.lib.fvh_ivf_evaluate_search_quality(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], int(k),
                                                              _ptr(out, f32p), C.byref(n)))
         return dict(avg_recall=out[0], avg_precision=out[1], avg_query_time_ms=float(out[2]), queries_evaluated=int(n.value))
+
+    def recall_by_nprobe(self, queries, k, allowed=None):
+        """evaluate_search_quality (operations.rs:329-391) at EVERY n_probe from one search of every list (DESIGN.md
+        section 9m).  Returns a dict: avg_recall and avg_precision, f32 arrays of length n_clusters whose entry p - 1 is
+        what evaluate_search_quality returns with n_probe = p configured, bit for bit; queries_evaluated;
+        avg_query_time_ms (the call's wall time over the number of queries).  The figures are the reference's id-based
+        ones when no id is stored in two lists; otherwise they count rows, not ids.  allowed: an allow-set of ids, as
+        search_allowed takes it; the curve is then the one of the index with every other id deleted.
+        HybridIndex has no call of its own: h.ivf() is an IVFIndex view of the historical part, and this is its curve."""
+        q = np.asarray(queries, np.float32)
+        if q.size == 0:
+            raise InvalidConfig("Invalid parameter: No test queries provided")
+        q = _rows(q)
+        n = int(self.lib.fvh_ivf_n_clusters(self.h))
+        recall, precision = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        ms, done = C.c_float(0), C.c_uint64(0)
+        a = None if allowed is None else _allowed_ids(allowed)
+        self._check(self.lib.fvh_ivf_quality_curve(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], int(k), int(a is not None),
+                                                   None if a is None else _ptr(a, u64p), 0 if a is None else a.size, n,
+                                                   _ptr(recall, f32p), _ptr(precision, f32p), C.byref(ms), C.byref(done)))
+        return dict(avg_recall=recall, avg_precision=precision, avg_query_time_ms=float(ms.value),
+                    queries_evaluated=int(done.value))
+
+    def smallest_n_probe(self, queries, k, target_recall, allowed=None):
+        """(p, curve): the smallest n_probe whose avg_recall on these queries reaches target_recall (compared in f32), or
+        None when none does, and the curve of recall_by_nprobe it was read from."""
+        curve = self.recall_by_nprobe(queries, k, allowed)
+        hit = np.flatnonzero(curve["avg_recall"] >= np.float32(target_recall))
+        return (int(hit[0]) + 1 if hit.size else None), curve
 
     def maintenance_info(self):
         """Figures of the last resident maintenance job (fvdb_ivf_maintenance_info)."""

@@ -656,6 +656,26 @@ int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, 
  * fvdb_ivf_search_dev_slot's. */
 int fvdb_ivf_search_quality_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
                                 uint32_t nprobe, float* out_recall_dev, float* out_precision_dev);
+/* evaluate_search_quality (src/ivf/operations.rs:329-391) at EVERY nprobe from one search of every list.  The truth
+ * of a query is the top k of the search of every list in centroid-rank order, and a search at nprobe = p scans the
+ * first p ranked lists at the same scan positions: a truth row whose list ranks below p is in the p-probe result, and
+ * a p-probe result row that is in the truth is such a row.  Per query and p = 1 .. nlist
+ *   matches(p)   = truth entries whose list has centroid rank < p,
+ *   recall(p)    = truth empty ? 1 : matches(p) / min(len(truth), k),
+ *   precision(p) = len_result(p) == 0 ? 0 : matches(p) / len_result(p),  len_result(p) = min(k, live rows of the first
+ *                  p ranked lists)                                       (the f32 divisions of fvdb_ivf_search_quality_dev)
+ * and out_recall_sum_dev[p - 1] / out_precision_sum_dev[p - 1] (device memory, nlist floats each) receive their sums
+ * over the B queries, added in query order in f32 as the reference's `total_recall += recall` (:379-387): bit for bit
+ * the sums of fvdb_ivf_search_quality_dev's values at nprobe = p.  Uniqueness condition: these figures equal the
+ * reference's id-based ones when no id is stored in two lists; otherwise they count rows, not ids.
+ * mask: NULL, or an allow-set mask of this index ("live" then means allowed and live; a stale mask is FVDB_E_INVALID).
+ * chunk_queries: 0 = as many queries per pass as fit the call's scratch budget, else at most that many (the sums do not
+ * depend on it).  1 <= k <= FVDB_MAX_K_WIDE (the every-list search is fvdb_ivf_search_dev_slot's, or the wide one's for
+ * k > FVDB_MAX_K), else FVDB_E_UNSUPPORTED; so are an index of more than 16384 lists and one holding a shard of a larger
+ * one (fvdb_ivf_set_global_list_sizes).  B = 0 is FVDB_OK and writes nothing.  Slot and stream rules are
+ * fvdb_ivf_search_dev_slot's. */
+int fvdb_ivf_quality_curve_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                               uint32_t k, uint32_t chunk_queries, float* out_recall_sum_dev, float* out_precision_sum_dev);
 /* fvdb_graph_search_dev_slot under a mask: a node the mask does not allow is treated as deleted — never expanded into
  * `candidates`, never returned (src/hnsw/core.rs:511-513, :451-466).  status 1 queries go to the host walk as before;
  * the host must apply the same view there. */
