@@ -196,6 +196,9 @@ SIGNATURES = {
     "fvdb_ivf_search_probes_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivf_search_shard_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
+    # one allow-set per query
+    "fvdb_ivf_search_groups_dev_slot": (i32, [vp, vp, u32, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_graph_scan_allowed_groups_dev_slot": (i32, [vp, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_ivf_search_wide": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
     "fvdb_ivf_search_quality_dev": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp]),
     "fvdb_ivf_quality_curve_dev": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp]),

@@ -92,11 +92,21 @@ int build_graph_mask(fvdb_mask* m, const GraphMaskSource& src, const uint32_t* n
   return FVDB_OK;
 }
 
-template <int KR>
+template <int KR, bool GR = false>
 void launch_allow_scan(fvdb_ctx* ctx, const AllowScanArgs& a, bool f16 /* the store's rows */, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
-  if (a.slices) hipLaunchKernelGGL((f16 ? allow_scan_kernel<KR, half_t> : allow_scan_kernel<KR, float>), dim3(cdiv(a.B, 4), a.slices), dim3(256), 0, ctx->stream, a);
-  hipLaunchKernelGGL((allow_merge_kernel<KR>), dim3(cdiv(a.B, 4)), dim3(256), 0, ctx->stream, a.part, a.nodes, a.slices, a.B, a.k,
-                     out_nodes, out_dist, out_counts);
+  if (a.slices)
+    hipLaunchKernelGGL((f16 ? allow_scan_kernel<KR, half_t, GR> : allow_scan_kernel<KR, float, GR>), dim3(cdiv(a.B, 4), a.slices), dim3(256), 0,
+                       ctx->stream, a);
+  hipLaunchKernelGGL((allow_merge_kernel<KR, GR>), dim3(cdiv(a.B, 4)), dim3(256), 0, ctx->stream, a.part, a.nodes, a.slices, a.B, a.k,
+                     out_nodes, out_dist, out_counts, a.groups, a.group);
+}
+
+// the slices of a scan whose longest node list has n_nodes entries: enough (query, slice) waves to fill the device, a
+// slice no shorter than four rounds of 64
+void allow_scan_slices(AllowScanArgs& a, uint32_t n_nodes) {
+  a.slices = n_nodes ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(n_nodes, 256), cdiv(8192, a.B))) : 0;
+  a.slice_len = a.slices ? cdiv(n_nodes, a.slices) : 0;
+  if (a.slices) a.slices = cdiv(n_nodes, a.slice_len);
 }
 
 }  // namespace
@@ -198,10 +208,7 @@ int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot,
   a.n_nodes = n_nodes;
   a.B = B;
   a.k = k;
-  // enough (query, slice) waves to fill the device, a slice no shorter than four rounds of 64
-  a.slices = n_nodes ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(n_nodes, 256), cdiv(8192, B))) : 0;
-  a.slice_len = a.slices ? cdiv(n_nodes, a.slices) : 0;
-  if (a.slices) a.slices = cdiv(n_nodes, a.slice_len);
+  allow_scan_slices(a, n_nodes);
   // the slot's scratch: the queries padded to the store's row stride where d is not a multiple of 4, the partial lists
   rc = graph_scan_inputs(g, ctx, slot, q_dev, B, (size_t)a.slices * B * k * 8, &a.queries, &a.part);
   if (rc) return rc;
@@ -209,6 +216,63 @@ int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot,
     case 1: launch_allow_scan<1>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
     case 2: launch_allow_scan<2>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
     default: launch_allow_scan<4>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// The same scan, each query over the node list of its own mask.
+int fvdb_graph_scan_allowed_groups_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* const* masks, uint32_t G,
+                                            const uint32_t* group_of_query, const float* q_dev, uint32_t B, uint32_t k,
+                                            uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
+  if (!g) return FVDB_E_INVALID;
+  GraphMaskSource src{};
+  int rc = graph_mask_source(g, &src);
+  if (rc) return rc;
+  fvdb_store* s = src.store;
+  fvdb_ctx* ctx = on ? on : s->ctx;
+  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
+  if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
+  if (G && !masks) FAIL(ctx, FVDB_E_INVALID, "null mask table");
+  if (B && !group_of_query) FAIL(ctx, FVDB_E_INVALID, "null group array");
+  if (B && G == 0) FAIL(ctx, FVDB_E_INVALID, "queries but no group");
+  // every mask, named by a query or not, before anything is enqueued
+  std::vector<AllowGroup> groups(G);
+  uint32_t longest = 0;
+  for (uint32_t i = 0; i < G; ++i) {
+    const fvdb_mask* m = masks[i];
+    if (!m || m->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
+    if (m->stamp != src.mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
+    groups[i] = AllowGroup{m->nodes.as<uint32_t>(), (uint32_t)m->allowed_live, 0u};
+    longest = std::max(longest, groups[i].n_nodes);
+  }
+  for (uint32_t b = 0; b < B; ++b)
+    if (group_of_query[b] >= G) FAIL(ctx, FVDB_E_INVALID, "group index out of range");
+  if (k == 0 || k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "exact scan: k must be in 1..FVDB_MAX_K");
+  if (!q_dev || !out_nodes_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null argument");
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  AllowScanArgs a{};
+  a.rows = s->data;
+  a.dpad = s->dpad;
+  a.B = B;
+  a.k = k;
+  allow_scan_slices(a, longest);  // laid out for the longest list
+  // the slot's scratch: padded queries, the partial lists, then the group table and the group of each query
+  const size_t part_bytes = ((size_t)a.slices * B * k * 8 + 15) & ~(size_t)15;
+  const size_t table_bytes = (size_t)G * sizeof(AllowGroup);
+  rc = graph_scan_inputs(g, ctx, slot, q_dev, B, part_bytes + table_bytes + (size_t)B * 4, &a.queries, &a.part);
+  if (rc) return rc;
+  char* tail = (char*)a.part + part_bytes;
+  HIPCHK(ctx, hipMemcpyAsync(tail, groups.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(tail + table_bytes, group_of_query, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the table and the caller's array are host memory of this call
+  a.groups = (const AllowGroup*)tail;
+  a.group = (const uint32_t*)(tail + table_bytes);
+  switch (k <= 64 ? 1 : (k <= 128 ? 2 : 4)) {
+    case 1: launch_allow_scan<1, true>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
+    case 2: launch_allow_scan<2, true>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
+    default: launch_allow_scan<4, true>(ctx, a, s->f16(), out_nodes_dev, out_dist_dev, out_counts_dev); break;
   }
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;

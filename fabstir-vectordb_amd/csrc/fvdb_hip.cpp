@@ -188,6 +188,7 @@ struct IvfScratch {
   Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
   Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
   Buf s_wgbase{this};                // the same bases over the logical index, for the keys of a shard's wide search
+  Buf s_gwords{this}, s_group{this};  // a grouped search: the live-word pointer table [G + 1], the group of each query [B]
   Buf s_rbase{this}, s_rarena{this};  // the full centroid ranking (kernels_rank.h): the same for the centroid table
   Buf s_qual{this};                   // fvdb_ivf_search_quality_dev: the two result blocks
   // fvdb_ivf_quality_curve_dev (kernels_curve.h): live rows per list; per chunk the ranking, the truth's keys and hit
@@ -467,6 +468,9 @@ struct Batch {
   uint64_t* out_keys;
   const float* given_thr = nullptr;  // sharded search: filter thresholds already agreed between the ranks ([B], device)
   bool glob_keys = false;            // wide selection: keys carry the logical index's seq (a shard of a larger index)
+  // wide selection, one allow-set per query: the device table of live words and each query's entry in it (both null otherwise)
+  const uint64_t* const* words = nullptr;
+  const uint32_t* group = nullptr;
 };
 
 inline ListTable list_table(const fvdb_ivf* ivf) {
@@ -1250,11 +1254,19 @@ int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   mark(ivf, E, EV_SCAN_BEGIN);
   const PoolView pool = list_pool(ivf, E);
   const uint32_t grid = (uint32_t)ctx->num_cus * ivf_knobs().scan_wgs_per_cu;
-  auto score = ivf->f16 ? wide_score_kernel<1> : wide_score_kernel<0>;
-  hipLaunchKernelGGL(score, dim3(grid), dim3(256), 0, ctx->stream, pool.data, pool.valid, pool.d4, lists.off, lists.blocks,
-                     nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(), (const u32x2*)S.s_entries.as<uint2>(),
-                     S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.np,
-                     S.s_wbase.as<uint32_t>(), S.s_arena.as<uint32_t>(), stride);
+  if (b.group) {
+    auto score = ivf->f16 ? wide_score_kernel<1, WideGroups> : wide_score_kernel<0, WideGroups>;
+    hipLaunchKernelGGL(score, dim3(grid), dim3(256), 0, ctx->stream, pool.data, pool.valid, pool.d4, lists.off, lists.blocks,
+                       nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(), (const u32x2*)S.s_entries.as<uint2>(),
+                       S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.np,
+                       S.s_wbase.as<uint32_t>(), S.s_arena.as<uint32_t>(), stride, WideGroups{b.words, b.group});
+  } else {
+    auto score = ivf->f16 ? wide_score_kernel<1> : wide_score_kernel<0>;
+    hipLaunchKernelGGL(score, dim3(grid), dim3(256), 0, ctx->stream, pool.data, pool.valid, pool.d4, lists.off, lists.blocks,
+                       nlist, S.s_eoff.as<uint32_t>(), S.s_ioff.as<uint32_t>(), (const u32x2*)S.s_entries.as<uint2>(),
+                       S.scalar(SC_FINE_ITEMS), S.scalar(SC_FINE_HEAD), b.qpad, ivf->dpad, segb, b.np,
+                       S.s_wbase.as<uint32_t>(), S.s_arena.as<uint32_t>(), stride);
+  }
   mark(ivf, E, EV_SCAN_DONE);
   WideArgs w{};
   w.pool = pool;
@@ -1970,6 +1982,10 @@ struct IvfSearch {
   const float* given_thr = nullptr;        // [B] filter thresholds agreed between the ranks (Batch::given_thr)
   uint32_t* probes_out = nullptr;          // [B][np] the ranking goes here: COARSE_ONLY's result; any other kind scans
                                            // the lists from here instead of the set's own block, and the caller keeps it
+  // WIDE with one allow-set per query (fvdb_ivf_search_groups_dev_slot): the live words of each group, G masks and then
+  // the pool's own, and each query's index into them.  Device pointers; the driver fills them in from GroupSource.
+  const uint64_t* const* words = nullptr;  // [G + 1]
+  const uint32_t* group = nullptr;         // [B]
 
   // Queries o .. o + b of the request; np = min(nprobe, nlist) as the driver clamped it.  The only place a stride is written.
   IvfSearch slice(uint32_t o, uint32_t b, uint32_t d, uint32_t np) const {
@@ -1984,6 +2000,7 @@ struct IvfSearch {
     s.given_probes = at(given_probes, np);
     s.given_thr = at(given_thr, 1);
     s.probes_out = at(probes_out, np);
+    s.group = at(group, 1);
     return s;
   }
 };
@@ -2027,8 +2044,17 @@ void ensure_stage_events(const fvdb_ivf* ivf, IvfScratch& S) {
     if (!e) (void)hipEventCreate(&e);
 }
 
+// A grouped search's host side: the table of live-word pointers (device addresses, [n_words]) and the group of each
+// query ([B], every entry checked against the table by the entry point).  The driver copies both into the scratch set.
+struct GroupSource {
+  const uint64_t* const* words;
+  uint32_t n_words;
+  const uint32_t* group;
+};
+
 // Every IVF search: validated, cut into sub-batches that fit the scratch budget, each through its coarse and fine stage.
-int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
+int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R_in, const GroupSource* groups = nullptr) {
+  IvfSearch R = R_in;
   fvdb_ctx* ctx = E.ctx;
   IvfScratch& S = *E.S;
   const uint32_t np = probed_lists(ivf, R.kind, R.nprobe);
@@ -2047,6 +2073,17 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
   if (rc) return rc;
   std::lock_guard<std::mutex> enq(S.enq);  // one search's launches go in as a block
   ensure_stage_events(ivf, S);
+  if (groups) {
+    // in the set's own buffers, behind whatever the stream still runs from them; the caller's arrays are its own again
+    // when this returns
+    HIPCHK(ctx, S.s_gwords.ensure((size_t)groups->n_words * 8));
+    HIPCHK(ctx, S.s_group.ensure((size_t)R.B * 4));
+    HIPCHK(ctx, hipMemcpyAsync(S.s_gwords.p, groups->words, (size_t)groups->n_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(S.s_group.p, groups->group, (size_t)R.B * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    R.words = S.s_gwords.as<const uint64_t*>();
+    R.group = S.s_group.as<uint32_t>();
+  }
   const uint32_t step = wide ? wide_sub_batch(ivf, R.B, np) : sub_batch(ivf, R.B, R.k, np);
   for (uint32_t o = 0; o < R.B; o += step) {
     const IvfSearch r = R.slice(o, std::min(step, R.B - o), ivf->d, np);
@@ -2072,7 +2109,8 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R) {
       probes = ranked;
     }
     if (R.kind == IvfSearch::COARSE_ONLY) continue;
-    const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr, R.kind == IvfSearch::SHARD_WIDE};
+    const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr, R.kind == IvfSearch::SHARD_WIDE,
+                  r.words, r.group};
     rc = wide ? run_fine_wide(ivf, E, b) : run_fine(ivf, E, b, all ? ROLE_ALL : ROLE_LIST);
     if (rc) return rc;
     // per sub-batch: each one records the stage events anew, so their intervals are folded in before the next does
@@ -2131,7 +2169,8 @@ int on_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, SlotMask m, Body body) {
   Env E{};
   int rc = m.required ? mask_env(ivf, on, slot, m.mask, &E) : slot_env(ivf, on, slot, &E);
   if (rc) return rc;
-  return slot_done(ivf, E, body(E));
+  const int done = body(E);
+  return slot_done(ivf, E, done);
 }
 inline int search_on_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, SlotMask m, const IvfSearch& R) {
   return on_slot(ivf, on, slot, m, [&](const Env& E) { return ivf_search(ivf, E, R); });
@@ -2244,6 +2283,37 @@ int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fv
   if (!ivf) return FVDB_E_INVALID;
   return search_on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask,
                         IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
+}
+
+// The wide search with one allow-set per query.  Everything is checked before anything is enqueued:
+// every mask of the table, named by a query or not, and every group index.
+int fvdb_ivf_search_groups_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* const* masks, uint32_t G,
+                                    const uint32_t* group_of_query, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                    uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  return on_slot(ivf, on, slot, kNoMask, [&](Env& E) -> int {
+    fvdb_ctx* ctx = E.ctx;
+    if (G && !masks) FAIL(ctx, FVDB_E_INVALID, "null mask table");
+    if (B && !group_of_query) FAIL(ctx, FVDB_E_INVALID, "null group array");
+    if (B && G == 0) FAIL(ctx, FVDB_E_INVALID, "queries but no group");
+    // the last entry is the pool's own words: what a null mask ("no filter") maps to
+    std::vector<const uint64_t*> words((size_t)G + 1, ivf->pool.valid);
+    for (uint32_t g = 0; g < G; ++g) {
+      const fvdb_mask* m = masks[g];
+      if (!m) continue;
+      if (m->ivf != ivf) FAIL(ctx, FVDB_E_INVALID, "mask of another index");
+      if (m->stamp != ivf->mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the index changed after the mask was created");
+      words[g] = m->words.as<uint64_t>();
+    }
+    for (uint32_t b = 0; b < B; ++b)
+      if (group_of_query[b] >= G) FAIL(ctx, FVDB_E_INVALID, "group index out of range");
+    // a grouped search is a masked one to everything that asks (the counter blocks, AUTO's watch); the words a stage
+    // reads per batch are the pool's, the score stage reads each query's own
+    E.live = ivf->pool.valid;
+    const GroupSource src{words.data(), G + 1, group_of_query};
+    return ivf_search(ivf, E, IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev},
+                      &src);
+  });
 }
 
 int fvdb_ivf_search_shard_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,

@@ -9,6 +9,7 @@
 //   allow_scan_kernel         exact scan of the allowed live nodes: the reference's f32 fold (score_rows.h) over gathered
 //                             rows, per-(query, slice) top k by (distance bits, position in the node list)
 //   allow_merge_kernel        the slices of a query merged by the same key
+//                             both also in a grouped form (GR): every query scans the node list of its own group
 //
 // Membership: a hash set rather than a sorted array.  Both are exact.  The set is built by one pass of independent
 // inserts (a sort needs log^2 n passes or a radix sort this project does not otherwise have), and a lookup is one or two
@@ -122,6 +123,10 @@ __global__ __launch_bounds__(256) void allow_graph_write_kernel(const uint32_t* 
 // A workgroup = 4 waves = 4 consecutive queries over ONE slice of the node list, so the four gathers of a row meet in the
 // cache.  A wave scores 64 nodes per round with score_rows_wave (the traversal's arithmetic: sub, mul, sequential add,
 // sqrt) and keeps its k best by (distance bits, position in the node list): position order is node-index order.
+struct AllowGroup {  // the node list of one mask
+  const uint32_t* nodes;  // [n_nodes] ascending
+  uint32_t n_nodes, reserved;
+};
 struct AllowScanArgs {
   const void* rows;        // the store: [node][dpad] of the kernel's RT (float or half_t)
   const float* queries;    // [B][dpad]
@@ -129,9 +134,13 @@ struct AllowScanArgs {
   uint32_t dpad, n_nodes, B, k;
   uint32_t slices, slice_len;  // slice s = positions [s * slice_len, min(n_nodes, (s + 1) * slice_len))
   uint64_t* part;              // [slices][B][k] keys, ~0 = none
+  // grouped form: query q scans groups[group[q]] (the host has checked every group[] entry); nodes / n_nodes above are
+  // not read, and the slices are laid out for the longest list — a slice past the end of a shorter one scores nothing
+  const AllowGroup* groups;
+  const uint32_t* group;  // [B]
 };
 
-template <int KR, typename RT = float>
+template <int KR, typename RT = float, bool GR = false>
 __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) {
   __shared__ __attribute__((aligned(16))) float s_tile[4][kScoreTileFloats];
   const int lane = threadIdx.x & 63;
@@ -139,8 +148,15 @@ __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) 
   const uint32_t q = blockIdx.x * 4 + w, s = blockIdx.y;
   if (q >= a.B) return;  // whole waves leave; no workgroup barrier below
   const float* qrow = a.queries + (size_t)q * a.dpad;
+  const uint32_t* nodes = a.nodes;
+  uint32_t n_nodes = a.n_nodes;
+  if constexpr (GR) {
+    const AllowGroup g = a.groups[a.group[q]];
+    nodes = g.nodes;
+    n_nodes = g.n_nodes;
+  }
   const uint32_t lo = s * a.slice_len;
-  const uint32_t hi = min(a.n_nodes, lo + a.slice_len);
+  const uint32_t hi = min(n_nodes, lo + a.slice_len);  // below lo where the slice lies past the list: no round runs
   WaveTopK<KR> tk;
   tk.init();
   uint32_t th = kInf32, tl = kInf32;
@@ -148,7 +164,7 @@ __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) 
     const uint32_t cnt = min(64u, hi - e0);
     const uint32_t pos = e0 + (uint32_t)lane;
     const bool have = (uint32_t)lane < cnt;
-    const uint32_t node = have ? a.nodes[pos] : 0u;
+    const uint32_t node = have ? nodes[pos] : 0u;
     const float d = score_rows_wave((const RT*)a.rows, a.dpad, qrow, node, cnt, s_tile[w], lane);
     offer<KR>(tk, a.k, have ? __float_as_uint(d) : kInf32, pos, th, tl, lane);
   }
@@ -161,13 +177,16 @@ __global__ __launch_bounds__(256) void allow_scan_kernel(const AllowScanArgs a) 
 }
 
 // one wave per query: the slices' lists merged by key; positions become node indices.  slices == 0 writes empty rows.
-template <int KR>
+// GR: positions are those of the query's own group (groups / group as in AllowScanArgs; `nodes` is not read).
+template <int KR, bool GR = false>
 __global__ __launch_bounds__(256) void allow_merge_kernel(const uint64_t* __restrict__ part, const uint32_t* __restrict__ nodes, uint32_t slices,
                                                           uint32_t B, uint32_t k, uint32_t* __restrict__ out_nodes, float* __restrict__ out_dist,
-                                                          uint32_t* __restrict__ out_counts) {
+                                                          uint32_t* __restrict__ out_counts, const AllowGroup* __restrict__ groups,
+                                                          const uint32_t* __restrict__ group) {
   const int lane = threadIdx.x & 63;
   const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= B) return;
+  if constexpr (GR) nodes = groups[group[q]].nodes;
   WaveTopK<KR> tk;
   tk.init();
   uint32_t th = kInf32, tl = kInf32;

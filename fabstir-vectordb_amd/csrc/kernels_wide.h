@@ -5,7 +5,8 @@
 //   score   wide_score_kernel: the work items and the fold of scan_topk_kernel (lane = row, queries through the scalar
 //           path), but each row's distance bits go to a per-query arena at the row's scan position `seq` instead of a
 //           register list.  Dead rows, masked rows and block padding write kInf32.  The arena index IS the tie-break,
-//           so this stage has no atomics and no ordering concern.
+//           so this stage has no atomics and no ordering concern.  In the per-query form (PQ) the live word of a
+//           block is the word of the query's own allow-set: one batch, one mask per query.
 //   select  wide_select_kernel: one workgroup per query.  Radix select (8-bit digits, LDS histogram) of the k-th
 //           smallest distance word — non-negative f32 bits are monotone as u32 — then the rows below the cut and the
 //           first rows AT the cut in seq order are gathered as 64-bit keys into LDS, sorted there (bitonic; the keys
@@ -76,8 +77,11 @@ __global__ void wide_gbase_kernel(const uint32_t* __restrict__ probes, const uin
 
 // One work item: rows of blocks [b0, b1) of a list against the ne (<= QQ) queries of a group.  The fold is
 // scan_item's, statement for statement (kernels_scan.h): the two must round alike.
-template <int QQ, int ST>
+// PQ: liveness per query.  words[group[q]] are the live words query q sees (a mask's words are valid & allowed already;
+// the table's last entry is the pool's own), pool_valid is not read.  The host has checked every group[] entry.
+template <int QQ, int ST, bool PQ>
 __device__ __forceinline__ void wide_score_item(const void* __restrict__ pool_data, const uint64_t* __restrict__ pool_valid,
+                                                const uint64_t* const* __restrict__ words, const uint32_t* __restrict__ group,
                                                 const uint32_t d4, const uint32_t* __restrict__ list_blocks,
                                                 const u32x2* __restrict__ entries, const float* __restrict__ queries,
                                                 const uint32_t dpad, const uint32_t nprobe,
@@ -91,15 +95,20 @@ __device__ __forceinline__ void wide_score_item(const void* __restrict__ pool_da
   // below reads them back lane by lane — sixteen wave-uniform 64-bit offsets would not fit the scalar registers
   uint32_t room_l = 0;  // 0: no query j, or its list was left out of the arena
   uint64_t aoff_l = 0;
+  const uint64_t* words_l = nullptr;  // PQ: the live words of query j, kept the same way
   if ((uint32_t)lane < ne) {
     const u32x2 e = entries[e0 + lane];
     const uint32_t* bp = base + (size_t)e.x * (nprobe + 1) + e.y;
     room_l = bp[1] - bp[0];
     aoff_l = (uint64_t)e.x * stride + (uint64_t)bp[0] * 64;
+    if constexpr (PQ) words_l = words[group[e.x]];
   }
 
   for (uint32_t b = b0; b < b1; ++b) {
     const uint32_t blk = cload(list_blocks + b_begin + b);
+    uint64_t word_l = 0;  // PQ: lane j loads its query's word of this block now; the fold hides the latency
+    if constexpr (PQ)
+      if ((uint32_t)lane < ne) word_l = words_l[blk];
     float acc[QQ];
 #pragma unroll
     for (int j = 0; j < QQ; ++j) acc[j] = 0.0f;
@@ -137,27 +146,48 @@ __device__ __forceinline__ void wide_score_item(const void* __restrict__ pool_da
         }
       }
     }
-    const uint64_t vmask = cload(pool_valid + blk);
-    const bool live = (vmask >> lane) & 1ull;
+    uint64_t vmask = 0;
+    if constexpr (!PQ) vmask = cload(pool_valid + blk);
+    bool live = (vmask >> lane) & 1ull;
 #pragma unroll
     for (int j = 0; j < QQ; ++j) {
       const float dist = sqrtf(acc[j]);
       const uint32_t room = rlane(room_l, j);
       const uint64_t aoff = ((uint64_t)rlane((uint32_t)(aoff_l >> 32), j) << 32) | rlane((uint32_t)aoff_l, j);
+      if constexpr (PQ) {
+        const uint64_t word = ((uint64_t)rlane((uint32_t)(word_l >> 32), j) << 32) | rlane((uint32_t)word_l, j);
+        live = (word >> lane) & 1ull;
+      }
       if (b < room) arena[aoff + (size_t)b * 64 + lane] = live ? __float_as_uint(dist) : kInf32;
     }
   }
 }
 
 // Persistent waves pull (list segment, query group) items from the plan's work queue, as scan_topk_kernel does.
-template <int ST>
+// wide_score_kernel<ST>: one live word per block, the pool's or one mask's for the whole batch (pool_valid).
+// wide_score_kernel<ST, WideGroups>: one live word per (block, query) — the per-query form takes the table and the
+// group array as one further argument and does not read pool_valid.
+struct WideGroups {
+  const uint64_t* const* words;  // [G + 1] live words per group; a mask's, or the pool's own for "no filter"
+  const uint32_t* group;         // [B] of the sub-batch, every entry <= G (the host checks)
+};
+template <int ST, class... PerQuery>
 __global__ __launch_bounds__(256) void wide_score_kernel(
     const void* __restrict__ pool_data, const uint64_t* __restrict__ pool_valid, const uint32_t d4,
     const uint32_t* __restrict__ list_off, const uint32_t* __restrict__ list_blocks, const uint32_t nlist,
     const uint32_t* __restrict__ entry_off, const uint32_t* __restrict__ item_off, const u32x2* __restrict__ entries,
     const uint32_t* __restrict__ n_items_p, uint32_t* __restrict__ head, const float* __restrict__ queries,
     const uint32_t dpad, const uint32_t segb, const uint32_t nprobe, const uint32_t* __restrict__ base,
-    uint32_t* __restrict__ arena, const uint64_t stride) {
+    uint32_t* __restrict__ arena, const uint64_t stride, const PerQuery... per_query) {
+  static_assert(sizeof...(PerQuery) <= 1, "wide_score_kernel<ST> or wide_score_kernel<ST, WideGroups>");
+  constexpr bool PQ = sizeof...(PerQuery) != 0;
+  const uint64_t* const* words = nullptr;
+  const uint32_t* group = nullptr;
+  if constexpr (PQ) {
+    const WideGroups g = (per_query, ...);
+    words = g.words;
+    group = g.group;
+  }
   constexpr uint32_t Q = 16;
   const int lane = threadIdx.x & 63;
   const uint32_t n_items = cload(n_items_p);
@@ -186,14 +216,14 @@ __global__ __launch_bounds__(256) void wide_score_kernel(
     const uint32_t ne = min(Q, cnt - g * Q);
 
     if (ne <= 4)
-      wide_score_item<4, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
-                             b_begin, b0, b1, e0, ne, lane);
+      wide_score_item<4, ST, PQ>(pool_data, pool_valid, words, group, d4, list_blocks, entries, queries, dpad, nprobe, base,
+                                 arena, stride, b_begin, b0, b1, e0, ne, lane);
     else if (ne <= 8)
-      wide_score_item<8, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
-                             b_begin, b0, b1, e0, ne, lane);
+      wide_score_item<8, ST, PQ>(pool_data, pool_valid, words, group, d4, list_blocks, entries, queries, dpad, nprobe, base,
+                                 arena, stride, b_begin, b0, b1, e0, ne, lane);
     else
-      wide_score_item<16, ST>(pool_data, pool_valid, d4, list_blocks, entries, queries, dpad, nprobe, base, arena, stride,
-                              b_begin, b0, b1, e0, ne, lane);
+      wide_score_item<16, ST, PQ>(pool_data, pool_valid, words, group, d4, list_blocks, entries, queries, dpad, nprobe, base,
+                                  arena, stride, b_begin, b0, b1, e0, ne, lane);
   }
 }
 

@@ -71,6 +71,13 @@ int fvh_ivf_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint
                            uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
   return ((IVFIndex*)p)->search_allowed(q, B, d, k, n_probe, allowed, n_allowed, ids, dist, counts);
 }
+// one allow-set per query: set g = allowed[off[g] .. off[g + 1]), filtered[g] == 0 = "no filter"
+int fvh_ivf_search_allowed_groups(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t n_probe,
+                                  const uint64_t* allowed, const uint64_t* off, const uint8_t* filtered, uint32_t G,
+                                  const uint32_t* group_of_query, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((IVFIndex*)p)->search_allowed_groups(q, B, d, k, n_probe, AllowGroups{allowed, off, filtered, G, group_of_query}, ids, dist,
+                                               counts);
+}
 uint64_t fvh_ivf_mask_builds(void* p) { return ((IVFIndex*)p)->mask_builds(); }
 int fvh_ivf_mark_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->mark_deleted(id); }
 int fvh_ivf_is_deleted(void* p, uint64_t id) { return ((IVFIndex*)p)->is_deleted(id); }
@@ -215,6 +222,11 @@ int fvh_hnsw_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32
 void fvh_hnsw_set_scan_cutoff(void* p, uint64_t nodes) { ((HNSWIndex*)p)->set_scan_cutoff(nodes); }
 uint64_t fvh_hnsw_scan_cutoff(void* p) { return ((HNSWIndex*)p)->scan_cutoff(); }
 void* fvh_hnsw_device_graph(void* p) { return ((HNSWIndex*)p)->device_graph(); }
+int fvh_hnsw_search_allowed_groups(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, const uint64_t* allowed,
+                                   const uint64_t* off, const uint8_t* filtered, uint32_t G, const uint32_t* group_of_query,
+                                   uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_allowed_groups(q, B, d, k, ef, AllowGroups{allowed, off, filtered, G, group_of_query}, ids, dist, counts);
+}
 uint64_t fvh_hnsw_mask_builds(void* p) { return ((HNSWIndex*)p)->mask_builds(); }
 uint64_t fvh_hnsw_node_count(void* p) { return ((HNSWIndex*)p)->node_count(); }
 uint64_t fvh_hnsw_active_count(void* p) { return ((HNSWIndex*)p)->active_count(); }
@@ -369,6 +381,19 @@ int fvh_hybrid_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, u
   c.recent_k = recent_k;
   c.historical_k = historical_k;
   return ((HybridIndex*)p)->search_allowed(q, B, d, c, allowed, n_allowed, now, ids, dist, counts);
+}
+int fvh_hybrid_search_allowed_groups(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
+                                     int search_recent, int search_historical, const uint64_t* allowed, const uint64_t* off,
+                                     const uint8_t* filtered, uint32_t G, const uint32_t* group_of_query, double now,
+                                     uint64_t* ids, float* dist, uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = ef;
+  c.ivf_n_probe = nprobe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_allowed_groups(q, B, d, c, AllowGroups{allowed, off, filtered, G, group_of_query}, now, ids, dist,
+                                                  counts);
 }
 // search_with_filter (src/hybrid/core.rs:513-549): `matches(id, user)` is the host application's metadata lookup +
 // MetadataFilter::matches (0 = no metadata or no match); NULL = no filter.

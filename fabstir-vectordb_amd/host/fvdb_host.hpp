@@ -107,6 +107,28 @@ inline bool mask_fresh(const MaskRef& m) {
 }
 
 // The context (stream) of one in-flight slot, made on first use: borrowed from the index (slot 0) or created.
+// The allow-sets of one grouped search: G sets laid end to end, set g = ids[off[g] .. off[g + 1]);
+// filtered[g] == 0: group g is "no filter" (its range is not read).  group_of_query[B]: the set each query is searched
+// under; an entry >= G is FVDB_E_INVALID.
+struct AllowGroups {
+  const uint64_t* ids;
+  const uint64_t* off;      // [G + 1]
+  const uint8_t* filtered;  // [G]
+  uint32_t G;
+  const uint32_t* group_of_query;
+  const uint64_t* set(uint32_t g) const { return ids + off[g]; }
+  uint64_t size(uint32_t g) const { return off[g + 1] - off[g]; }
+  bool valid(uint32_t B) const {
+    if (B && !group_of_query) return false;
+    if (G && (!off || !filtered)) return false;
+    for (uint32_t g = 0; g < G; ++g)
+      if (off[g + 1] < off[g] || (filtered[g] && off[g + 1] > off[g] && !ids)) return false;
+    for (uint32_t b = 0; b < B; ++b)
+      if (group_of_query[b] >= G) return false;
+    return true;
+  }
+};
+
 inline int slot_ctx(fvdb_ctx* base, bool borrow, fvdb_ctx** ctx) {
   if (*ctx) return FVDB_OK;
   if (!borrow) return fvdb_ctx_create(fvdb_ctx_device(base), ctx);
@@ -199,6 +221,12 @@ class IVFIndex {
   // search under an allow-set: what search() returns after mark_deleted of every id outside allowed[n_allowed]
   int search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const uint64_t* allowed,
                      uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts);
+  // one allow-set per query: query b gets what search_allowed returns for it under the set of
+  // group_of_query[b], or what search returns where that group is "no filter".  One device call
+  // (fvdb_ivf_search_groups_dev_slot); the masks are built for this call, counted by mask_builds, and dropped when the
+  // results are in — the cached mask of search_allowed is left alone.
+  int search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const AllowGroups& groups,
+                            uint64_t* ids, float* dist, uint32_t* counts);
   // the device mask for that allow-set (cached); search_dev under it
   int allowed_mask(const uint64_t* allowed, uint64_t n_allowed, MaskRef* out);
   int search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe,
@@ -368,6 +396,13 @@ class HNSWIndex {
   int search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const uint64_t* allowed,
                      uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts);
   int allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out);  // cached like IVFIndex::allowed_mask
+  // One allow-set per query: query b gets what search_allowed returns for it under the set of
+  // group_of_query[b] (search, where that group is "no filter").  The views are built for this call and dropped after
+  // it; the cached one is left alone.  The queries of every group that scans(view, k) share ONE grouped scan
+  // (fvdb_graph_scan_allowed_groups_dev_slot); each other group is one masked traversal of its own queries, the
+  // unfiltered ones one plain traversal.  Blocking, in slot 0 under search_mu_ — or, owns_slot, in a slot the caller holds.
+  int search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowGroups& groups,
+                            uint64_t* ids, float* dist, uint32_t* counts, uint32_t slot = 0, bool owns_slot = false);
   // The split form, so that several batches can be in flight: begin enqueues the launch and the result copy on the
   // slot's own stream (slot < kSlots) and returns whether it did; the slot remembers.  end, given the same arguments,
   // waits for that slot and finishes on the host — or, when nothing was enqueued (the checks answered the search, it
@@ -502,6 +537,11 @@ class HNSWIndex {
   int launch(Search& s);
   int finish(Search& s);
   int run(Search& s);
+  // a view of the synced graph, not cached; scan_k > 0: without the host flags where scans(view, scan_k)
+  int make_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out, uint32_t scan_k = 0);
+  // queries [0, B) of q_dev, already in HBM and ordered so that local[b] indexes masks[]: one grouped scan in `slot`
+  int scan_groups(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const std::vector<fvdb_mask*>& masks,
+                  const std::vector<uint32_t>& local, uint32_t slot, uint64_t* ids, float* dist, uint32_t* counts);
   int search_host_walk(const float* q, bool q_on_device, uint32_t B, uint32_t k, uint32_t ef, uint64_t* ids,
                        float* dist, uint32_t* counts, const AllowView* view = nullptr);
   // The adjacency lists exist twice: nbrs_ (host) and the fixed-stride rows in HBM (graph_).  host_ahead_: nbrs_ holds
@@ -547,6 +587,7 @@ class HNSWIndex {
   struct DevSlot {  // per in-flight batch: stream (context), device result block and its pinned host copy
     fvdb_ctx* ctx = nullptr;  // slot 0 borrows ctx_, the others own theirs
     DevBuf buf;               // WalkBlock layout
+    DevBuf gq;                // search_allowed_groups: the queries in group order
     bool enqueued = false;    // launch() to finish(): a batch is in flight here ...
     bool scanned = false;     // ... whose block came from a scan, which writes no status words
   };
@@ -668,6 +709,11 @@ class HybridIndex {
   int search_with_filter(const float* q, uint32_t B, uint32_t dim, uint64_t k, FilterFn matches, void* user, double now,
                          uint64_t* ids, float* dist, uint32_t* counts);
   // Filtered search with the allow-set applied inside both parts (no counterpart in the reference): what search()
+  // search_allowed_groups: one allow-set per query — per query what search_allowed returns under
+  // the set of its group, or what search returns where the group is "no filter".  One migration step, every mask built
+  // after it under the read lock, the two parts by IVFIndex / HNSWIndex::search_allowed_groups, the usual merge.
+  int search_allowed_groups(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const AllowGroups& groups,
+                            double now, uint64_t* ids, float* dist, uint32_t* counts);
   // returns after remove() of every id outside allowed[n_allowed]; the recent part is scanned exactly instead when
   // its allowed live nodes number at most recent().scan_cutoff().  The masks are built after the auto-migration step
   // and under the same read lock as the search, so they match the rows searched; the last pair is kept for a caller

@@ -178,6 +178,7 @@ HNSWIndex::~HNSWIndex() {
   if (graph_) fvdb_graph_destroy(graph_);
   for (uint32_t i = 0; i < kSlots; ++i) {
     slots_[i].buf.release();
+    slots_[i].gq.release();
     if (i > 0 && slots_[i].ctx) fvdb_ctx_destroy(slots_[i].ctx);
   }
   d_q_.release();
@@ -672,29 +673,135 @@ int HNSWIndex::allowed_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef
   if (!same || !mask_fresh(view_->mask)) {
     view_.reset();
     view_key_.clear();
-    auto v = std::make_shared<AllowView>();
-    const size_t n = ids_.size();
-    v->eff.assign(n, 1);
-    std::vector<uint32_t> nodes;
-    nodes.reserve(n_allowed);
-    for (uint64_t i = 0; i < n_allowed; ++i) {
-      auto it = index_of_.find(allowed[i]);
-      if (it == index_of_.end()) continue;  // an id this index does not hold
-      nodes.push_back(it->second);
-      v->eff[it->second] = deleted_[it->second];
-    }
-    fvdb_mask* m = nullptr;
-    rc = fvdb_mask_create_graph(graph_, nodes.data(), nodes.size(), &m);
-    if (rc) return rc;
-    v->mask = adopt_mask(m);
-    fvdb_mask_info_t info;
-    if ((rc = fvdb_mask_info(m, &info))) return rc;
-    v->allowed_live = info.allowed_live;
+    ViewRef v;
+    if ((rc = make_view(allowed, n_allowed, &v))) return rc;
     view_ = v;
     view_key_.assign(allowed, allowed + n_allowed);
     mask_builds_ += 1;
   }
   *out = view_;
+  return FVDB_OK;
+}
+
+// the allow-set as the synced device graph sees it: ids -> node indices, the device mask, the host copy of its flags
+// scan_k > 0: the caller scans the view when scans(view, scan_k) and never hands such a view to the host walk, so the
+// host flags — one byte per node of the graph, per view — are then left out.
+int HNSWIndex::make_view(const uint64_t* allowed, uint64_t n_allowed, ViewRef* out, uint32_t scan_k) {
+  auto v = std::make_shared<AllowView>();
+  std::vector<uint32_t> nodes;
+  nodes.reserve(n_allowed);
+  for (uint64_t i = 0; i < n_allowed; ++i) {
+    auto it = index_of_.find(allowed[i]);
+    if (it == index_of_.end()) continue;  // an id this index does not hold
+    nodes.push_back(it->second);
+  }
+  fvdb_mask* m = nullptr;
+  int rc = fvdb_mask_create_graph(graph_, nodes.data(), nodes.size(), &m);
+  if (rc) return rc;
+  v->mask = adopt_mask(m);
+  fvdb_mask_info_t info;
+  if ((rc = fvdb_mask_info(m, &info))) return rc;
+  v->allowed_live = info.allowed_live;
+  if (!(scan_k && scans(*v, scan_k))) {
+    v->eff.assign(ids_.size(), 1);
+    for (uint32_t node : nodes) v->eff[node] = deleted_[node];
+  }
+  *out = v;
+  return FVDB_OK;
+}
+
+// ---- one allow-set per query ----
+int HNSWIndex::scan_groups(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const std::vector<fvdb_mask*>& masks,
+                           const std::vector<uint32_t>& local, uint32_t slot, uint64_t* ids, float* dist, uint32_t* counts) {
+  DevSlot& sl = slots_[slot];
+  int rc = slot_ctx(ctx_, slot == 0, &sl.ctx);
+  if (rc) return rc;
+  const uint64_t bytes = WalkBlock(nullptr, B, k).bytes;
+  if ((rc = sl.buf.reserve(sl.ctx, bytes, true))) return rc;
+  const WalkBlock d(sl.buf.dev, B, k);
+  rc = fvdb_graph_scan_allowed_groups_dev_slot(graph_, slot == 0 ? nullptr : sl.ctx, slot, masks.data(), (uint32_t)masks.size(),
+                                               local.data(), q_dev, B, k, d.nodes, d.dist, d.counts);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(sl.ctx, sl.buf.host, sl.buf.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(sl.ctx))) return rc;
+  const WalkBlock h(sl.buf.host, B, k);
+  std::memcpy(dist, h.dist, (size_t)B * k * 4);
+  std::memcpy(counts, h.counts, (size_t)B * 4);
+  for (uint32_t b = 0; b < B; ++b)
+    for (uint32_t i = 0; i < k; ++i) ids[(size_t)b * k + i] = i < counts[b] ? ids_[h.nodes[(size_t)b * k + i]] : FVDB_NO_ID;
+  return FVDB_OK;
+}
+
+int HNSWIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, const AllowGroups& groups,
+                                     uint64_t* ids, float* dist, uint32_t* counts, uint32_t slot, bool owns_slot) {
+  // what search_allowed answers before it reaches the device, in its order (admit)
+  fill_empty(ids, dist, counts, B, k);
+  if (!groups.valid(B)) return FVDB_E_INVALID;
+  if (!has_entry_ || B == 0 || k == 0) return FVDB_OK;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  if (slot >= kSlots) return FVDB_E_INVALID;
+  std::unique_lock<std::mutex> serial(search_mu_, std::defer_lock);
+  if (!owns_slot) serial.lock();  // the searches below run in the slot this call holds
+  int rc = sync_graph();  // the masks are built against the device graph as the searches will see it
+  if (rc) return rc;
+  const uint32_t G = groups.G;
+  std::vector<ViewRef> views(G);  // of this call: dropped at return
+  for (uint32_t g = 0; g < G; ++g) {
+    if (!groups.filtered[g]) continue;
+    if ((rc = make_view(groups.set(g), groups.size(g), &views[g], k))) return rc;
+    std::lock_guard<std::mutex> lk(view_mu_);
+    mask_builds_ += 1;
+  }
+  if (entry_lost_) return FVDB_E_NOT_FOUND;
+  // the queries in group order, the scanned groups first: every group is one run of rows, the scanned ones one block
+  std::vector<uint32_t> n_of(G, 0);
+  for (uint32_t b = 0; b < B; ++b) n_of[groups.group_of_query[b]] += 1;
+  std::vector<uint32_t> order, first(G, 0), local_of(G, 0);
+  std::vector<fvdb_mask*> scan_masks;
+  for (int scanned = 1; scanned >= 0; --scanned)
+    for (uint32_t g = 0; g < G; ++g) {
+      const bool sc = views[g] && views[g]->mask && scans(*views[g], k);
+      if (sc != (scanned == 1) || n_of[g] == 0) continue;
+      order.push_back(g);
+      if (sc) {
+        local_of[g] = (uint32_t)scan_masks.size();
+        scan_masks.push_back(views[g]->mask.get());
+      }
+    }
+  uint32_t at = 0, B_scan = 0;
+  for (uint32_t g : order) {
+    first[g] = at;
+    at += n_of[g];
+    if (views[g] && views[g]->mask && scans(*views[g], k)) B_scan = at;
+  }
+  std::vector<uint32_t> place(B), fill = first, local(B_scan);
+  for (uint32_t b = 0; b < B; ++b) place[b] = fill[groups.group_of_query[b]]++;
+  std::vector<float> gq((size_t)B * dim);
+  for (uint32_t b = 0; b < B; ++b) {
+    std::memcpy(&gq[(size_t)place[b] * dim], q + (size_t)b * dim, (size_t)dim * 4);
+    if (place[b] < B_scan) local[place[b]] = local_of[groups.group_of_query[b]];
+  }
+  DevSlot& sl = slots_[slot];
+  if ((rc = sl.gq.reserve(ctx_, (uint64_t)B * dim * 4, false)) || (rc = fvdb_dev_upload(ctx_, sl.gq.dev, gq.data(), (size_t)B * dim * 4)))
+    return rc;
+  const float* q_dev = (const float*)sl.gq.dev;
+  std::vector<uint64_t> gi((size_t)B * k);
+  std::vector<float> gd((size_t)B * k);
+  std::vector<uint32_t> gc(B, 0);
+  fill_empty(gi.data(), gd.data(), gc.data(), B, k);
+  if (B_scan && (rc = scan_groups(q_dev, B_scan, dim, k, scan_masks, local, slot, gi.data(), gd.data(), gc.data()))) return rc;
+  for (uint32_t g : order) {
+    if (first[g] < B_scan) continue;
+    // a group too large to scan: the masked traversal of its queries alone; "no filter": the plain one
+    const size_t o = first[g];
+    Search s{Search::kTraversal, q_dev + o * dim, true, n_of[g], dim, k, ef, &gi[o * k], &gd[o * k], &gc[o]};
+    s.view = views[g].get(), s.slot = slot, s.owns_slot = true;
+    if ((rc = run(s))) return rc;
+  }
+  for (uint32_t b = 0; b < B; ++b) {
+    std::memcpy(ids + (size_t)b * k, &gi[(size_t)place[b] * k], (size_t)k * 8);
+    std::memcpy(dist + (size_t)b * k, &gd[(size_t)place[b] * k], (size_t)k * 4);
+    counts[b] = gc[place[b]];
+  }
   return FVDB_OK;
 }
 

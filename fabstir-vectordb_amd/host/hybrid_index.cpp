@@ -857,6 +857,41 @@ int HybridIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, const 
   return search_impl(q, false, B, dim, cfg, now, ids, dist, counts, allowed, n_allowed, true);
 }
 
+// One allow-set per query.  The parts run one after the other, as exact_locked's do: the grouped
+// calls of the two index classes are blocking.
+int HybridIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
+                                       const AllowGroups& groups, double now, uint64_t* ids, float* dist, uint32_t* counts) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // the sharded IVF step takes no mask table
+  if (!groups.valid(B)) return FVDB_E_INVALID;
+  const uint32_t k = (uint32_t)cfg.k;
+  fill_empty(ids, dist, counts, B, k);
+  if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
+  if (int rc = migrate_if_due(now, false)) return rc;
+  std::shared_lock<std::shared_mutex> r(rw_);  // every mask below is built under it, after the migration
+  if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;
+  const uint32_t rk = cfg.rk(), hk = cfg.hk();
+  std::vector<uint64_t> rid, hid;
+  std::vector<float> rd, hd;
+  std::vector<uint32_t> rc_(B, 0), hc(B, 0);
+  const bool have_r = cfg.search_recent, have_h = cfg.search_historical && ivf_trained_;
+  if (have_r) {
+    rid.resize((size_t)B * rk);
+    rd.resize((size_t)B * rk);
+    Lease lease(this, Lease::kAnyFree, Lease::kTake);  // the graph's slot of the same index is this call's
+    if (int rc = recent_->search_allowed_groups(q, B, dim, rk, (uint32_t)cfg.hnsw_ef, groups, rid.data(), rd.data(), rc_.data(),
+                                                lease.index(), true))
+      return rc;
+  }
+  if (have_h) {
+    hid.resize((size_t)B * hk);
+    hd.resize((size_t)B * hk);
+    if (int rc = historical_->search_allowed_groups(q, B, dim, hk, (uint32_t)cfg.ivf_n_probe, groups, hid.data(), hd.data(), hc.data()))
+      return rc;
+  }
+  merge_parts(B, k, rk, hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, hid.data(), hd.data(), hc.data(), ids, dist, counts);
+  return FVDB_OK;
+}
+
 // src/hybrid/core.rs:513-549
 int HybridIndex::search_with_filter(const float* q, uint32_t B, uint32_t dim, uint64_t k, FilterFn matches, void* user,
                                     double now, uint64_t* ids, float* dist, uint32_t* counts) {

@@ -569,6 +569,46 @@ int IVFIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t 
   return FVDB_OK;
 }
 
+// ---- one allow-set per query ----
+int IVFIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const AllowGroups& groups,
+                                    uint64_t* ids, float* dist, uint32_t* counts) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  if (B == 0) return FVDB_OK;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  if (!groups.valid(B)) return FVDB_E_INVALID;
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  // the masks of this call: held until the results are in, dropped at return
+  std::vector<MaskRef> held(groups.G);
+  std::vector<fvdb_mask*> masks(groups.G, nullptr);
+  int rc;
+  for (uint32_t g = 0; g < groups.G; ++g) {
+    if (!groups.filtered[g]) continue;
+    fvdb_mask* m = nullptr;
+    if ((rc = fvdb_mask_create_ivf(dev_, groups.set(g), groups.size(g), &m))) return rc;
+    held[g] = adopt_mask(m);
+    masks[g] = m;
+    std::lock_guard<std::mutex> lk(mask_mu_);
+    mask_builds_ += 1;
+  }
+  std::lock_guard<std::mutex> lk(allowed_mu_);  // one staging block: calls take turns
+  const uint64_t need = (uint64_t)B * k, bytes = need * 12 + (uint64_t)B * 4;
+  if ((rc = allowed_q_.reserve(ctx_, (uint64_t)B * dim * 4, false)) || (rc = allowed_out_.reserve(ctx_, bytes, true))) return rc;
+  if ((rc = fvdb_dev_upload(ctx_, allowed_q_.dev, q, (size_t)B * dim * 4))) return rc;
+  char* d = (char*)allowed_out_.dev;
+  rc = fvdb_ivf_search_groups_dev_slot(dev_, nullptr, 0, masks.data(), groups.G, groups.group_of_query, (const float*)allowed_q_.dev, B,
+                                       k, n_probe, (uint64_t*)d, (float*)(d + need * 8), (uint32_t*)(d + need * 12), nullptr);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx_, allowed_out_.host, allowed_out_.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(ctx_)))
+    return rc;
+  const char* h = (const char*)allowed_out_.host;
+  std::memcpy(ids, h, need * 8);
+  std::memcpy(dist, h + need * 8, need * 4);
+  std::memcpy(counts, h + need * 12, (size_t)B * 4);
+  return FVDB_OK;
+}
+
 // src/ivf/operations.rs:569-591
 int IVFIndex::mark_deleted(uint64_t id) {
   auto r = where_.equal_range(id);

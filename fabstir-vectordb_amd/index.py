@@ -21,6 +21,7 @@ HOST_LIB_PATH = os.path.join(_capi.LIB_DIR, "libfvdb_host.so")
 _host = None
 i64p = C.POINTER(C.c_int64)
 f64p = C.POINTER(C.c_double)
+u8p = C.POINTER(C.c_uint8)
 vp, u64, u32, i32, i64, dbl = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int64, C.c_double
 
 HOST_SIGNATURES = {
@@ -163,6 +164,11 @@ HOST_SIGNATURES = {
     "fvh_hnsw_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
     "fvh_hybrid_search_exact": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
+    # one allow-set per query
+    "fvh_ivf_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
+    "fvh_hnsw_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
+    "fvh_hybrid_search_allowed_groups": (i32, [vp, f32p, u32, u32, u64, u64, u64, i32, i32, u64p, u64p, u8p, u32, u32p, dbl, u64p,
+                                               f32p, u32p]),
 }
 
 _ROW_DTYPE_NAMES = ("f32", "f16")
@@ -225,6 +231,29 @@ def _allowed_ids(allowed):
     ctypes has an address to pass."""
     a = np.ascontiguousarray(np.fromiter(allowed, np.uint64) if not isinstance(allowed, np.ndarray) else allowed, np.uint64)
     return a.reshape(-1) if a.size else np.zeros(1, np.uint64)[:0]
+
+
+def _allow_groups(allow_sets, group_of_query, B):
+    """The ctypes arguments of a grouped search: the allow-sets laid end to end with their offsets, a flag per set (0 where
+    the entry is None: "no filter") and the group of each query.  The arrays are returned too: the caller keeps them
+    alive for the call."""
+    sets = [None if a is None else _allowed_ids(a) for a in allow_sets]
+    off = np.zeros(len(sets) + 1, np.uint64)
+    off[1:] = np.cumsum([0 if a is None else a.size for a in sets], dtype=np.uint64)
+    flat = np.zeros(max(int(off[-1]), 1), np.uint64)
+    for g, a in enumerate(sets):
+        if a is not None:
+            flat[int(off[g]):int(off[g + 1])] = a
+    filtered = np.zeros(max(len(sets), 1), np.uint8)
+    filtered[:len(sets)] = [a is not None for a in sets]
+    group = np.asarray(group_of_query).reshape(-1)
+    if group.size != B:
+        raise InvalidConfig(f"group_of_query has {group.size} entries for {B} queries")
+    if group.size and (group.min() < 0 or group.max() >= len(sets)):
+        raise InvalidConfig(f"group_of_query names a group outside allow_sets (0..{len(sets) - 1})")
+    group = np.zeros(1, np.uint32)[:0] if not group.size else np.ascontiguousarray(group, np.uint32)
+    keep = (flat, off, filtered, group)
+    return (_ptr(flat, u64p), _ptr(off, u64p), filtered.ctypes.data_as(u8p), len(sets), _ptr(group, u32p)), keep
 
 
 def _get_vectors(self, fn, ids, dim):
@@ -473,6 +502,14 @@ class IVFIndex(_Base):
         return self._search(self.lib.fvh_ivf_search_allowed, queries, k, self.n_probe if n_probe is None else n_probe,
                             _ptr(a, u64p), a.size)
 
+    def search_allowed_groups(self, queries, k, allow_sets, group_of_query, n_probe=None):
+        """One allow-set per query in one call: query b gets what search_allowed(queries[b], k, allow_sets[g]) returns for
+        g = group_of_query[b], or what search() returns where allow_sets[g] is None.  The masks are built for this call
+        (mask_builds counts them) and dropped after it; the mask search_allowed keeps is left alone."""
+        q = _rows(queries)
+        args, keep = _allow_groups(allow_sets, group_of_query, q.shape[0])
+        return self._search(self.lib.fvh_ivf_search_allowed_groups, q, k, self.n_probe if n_probe is None else n_probe, *args)
+
     def mask_builds(self):
         return int(self.lib.fvh_ivf_mask_builds(self.h))
 
@@ -578,6 +615,14 @@ class HNSWIndex(_Base):
         distance bits, then node index)."""
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hnsw_search_allowed, queries, k, ef, _ptr(a, u64p), a.size)
+
+    def search_allowed_groups(self, queries, k, ef, allow_sets, group_of_query):
+        """One allow-set per query in one call: query b gets what search_allowed(queries[b], k, ef, allow_sets[g]) returns
+        for g = group_of_query[b] (search(), where allow_sets[g] is None).  The queries of every group small enough to be
+        scanned (scan_cutoff) share one launch; each larger group is one masked traversal of its own queries."""
+        q = _rows(queries)
+        args, keep = _allow_groups(allow_sets, group_of_query, q.shape[0])
+        return self._search(self.lib.fvh_hnsw_search_allowed_groups, q, k, ef, *args)
 
     def search_exact(self, queries, k):
         """The k nearest live nodes, exactly: every live row the graph holds is scored where it is stored (as it is
@@ -945,6 +990,16 @@ class HybridIndex(_Base):
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hybrid_search_allowed, queries, k, hnsw_ef, ivf_n_probe, int(search_recent),
                             int(search_historical), recent_k, historical_k, _ptr(a, u64p), a.size, float(now))
+
+    def search_allowed_groups(self, queries, k, allow_sets, group_of_query, now=0.0, hnsw_ef=50, ivf_n_probe=10,
+                              search_recent=True, search_historical=True):
+        """One allow-set per query in one call: query b gets what search_allowed(queries[b], k, allow_sets[g], ...) returns
+        for g = group_of_query[b] (search(), where allow_sets[g] is None).  One auto-migration step; every mask is built
+        after it.  Refused (Unsupported) on a sharded index, as search_allowed is."""
+        q = _rows(queries)
+        args, keep = _allow_groups(allow_sets, group_of_query, q.shape[0])
+        return self._search(self.lib.fvh_hybrid_search_allowed_groups, q, k, hnsw_ef, ivf_n_probe, int(search_recent),
+                            int(search_historical), *args, float(now))
 
     def search_exact(self, queries, k, now=0.0, search_recent=True, search_historical=True):
         """search() with both parts exact: the recent part from the flat scan of the graph's rows, the historical part

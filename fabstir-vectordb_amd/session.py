@@ -221,9 +221,12 @@ class VectorDbSession:
                 res = self.index.search_with_filter(q.reshape(1, -1), int(k), matches, now=self.now)  # defaults: ef 50, nprobe 10
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
-        include_vectors = bool(options.get("includeVectors", False))  # session.rs:229-231
+        return self._results_of(res[0], threshold, bool(options.get("includeVectors", False)))  # session.rs:229-231
+
+    def _results_of(self, hits, threshold, include_vectors):
+        """One query's (ids, distances) as the result list search() returns: score, threshold, metadata, vectors."""
         out = []
-        ids, ds = res[0]
+        ids, ds = hits
         pairs = list(zip(ids.tolist(), ds.tolist()))
         kept = []
         for rid, d in pairs:
@@ -252,6 +255,58 @@ class VectorDbSession:
                 item["vector"] = vectors.get(rid)
             out.append(item)
         return out
+
+    # -- search_many: a batch of requests, each with its own options (no counterpart in the reference) -----------
+    def search_many(self, query_vectors, k, options_list=None):
+        """search(query_vectors[i], k, options_list[i]) for every i, served by ONE index call
+        (HybridIndex.search_allowed_groups): each distinct filter is evaluated over the metadata map once and becomes one
+        allow-set, requests with equal filters (equal canonical JSON) share it, requests without a filter take the
+        "no filter" group.  A filtered request must say "filterMode": "pushdown" — the oversampling path keeps what is
+        left of 3 k candidates and cannot share a batch.  Returns one result list per query."""
+        import json
+        if self.destroyed:
+            raise SessionError("Session already destroyed")
+        n = len(query_vectors)
+        options_list = [{} for _ in range(n)] if options_list is None else [o or {} for o in options_list]
+        if len(options_list) != n:
+            raise SessionError(f"search_many: {n} queries but {len(options_list)} option sets")
+        qs, group_of_query, allow_sets, group_of_key = [], [], [], {}
+        for i, (qv, options) in enumerate(zip(query_vectors, options_list)):
+            q = js_array_to_vec_f32(qv)
+            if self.vector_dimension is not None and q.size != self.vector_dimension:
+                raise SessionError(
+                    f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+            qs.append(q)
+            key = None
+            if options.get("filter") is not None:
+                mode = options.get("filterMode", "oversample")
+                if mode != "pushdown":
+                    raise SessionError(f'search_many: request {i} has a filter with filterMode {mode!r}; a filtered request '
+                                       'in a batch needs "filterMode": "pushdown"')
+                key = json.dumps(options["filter"], sort_keys=True, separators=(",", ":"))
+            if key not in group_of_key:
+                allowed = None
+                if key is not None:
+                    try:
+                        flt = MetadataFilter.from_json(options["filter"])
+                    except FilterError as e:
+                        raise SessionError(f"Invalid filter: {e}") from e
+                    allowed = np.fromiter((rid for rid, name in self._rows.items()
+                                           if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                group_of_key[key] = len(allow_sets)
+                allow_sets.append(allowed)
+            group_of_query.append(group_of_key[key])
+        if n == 0:
+            return []
+        try:
+            res = self.index.search_allowed_groups(np.stack(qs), int(k), allow_sets, np.asarray(group_of_query, np.uint32),
+                                                   now=self.now)  # defaults: ef 50, nprobe 10
+        except Exception as e:
+            raise SessionError(f"Search failed: {e}") from e
+        return [self._results_of(res[i], np.float32(o.get("threshold", 0.0)), bool(o.get("includeVectors", False)))
+                for i, o in enumerate(options_list)]
+
+    searchMany = search_many
 
     def delete_vector(self, id):
         vid = VectorId(id)

@@ -589,7 +589,9 @@ int fvdb_graph_tie_restarts(fvdb_graph* g, uint64_t* queries, uint64_t* searched
  * built against the index as it stands; every mutation of the index (add*, set_deleted, clear, reserve, set_centroids,
  * train*, compact, refill_from; graph: upload, append_nodes, insert_linked, set_lists, set_entry, set_deleted) makes it
  * stale, and a masked search with a stale mask returns FVDB_E_INVALID (fvdb_last_error says so), never wrong rows.
- * Creating a mask needs the same exclusion against mutations as a search.  One mask serves a whole batch call.  The
+ * Creating a mask needs the same exclusion against mutations as a search.  One mask serves a whole batch call of the
+ * *_masked entry points; a batch in which every query has an allow-set of its own goes through the grouped entry points
+ * (fvdb_ivf_search_groups_dev_slot, fvdb_graph_scan_allowed_groups_dev_slot: a table of masks and one index per query).  The
  * sharded search takes one through fvdb_ivf_search_sharded_wide_begin (fvdb_ivf_search_sharded_begin takes none).
  *  - fvdb_mask_create_ivf: ids[n] = the allowed row ids (host; duplicates and unknown ids are harmless).
  *  - fvdb_mask_create_graph: nodes[n] = the allowed NODE indices (host; the graph holds no ids: node index = store row).
@@ -642,6 +644,18 @@ int fvdb_ivf_search_shard_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t sl
                                         uint32_t B, uint32_t k, uint32_t nprobe, const uint32_t* given_probes_dev,
                                         uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev,
                                         uint64_t* out_keys_dev);
+/* The wide search with one allow-set per query.  masks[G]: masks of this index, or NULL for "no
+ * filter"; group_of_query[B] (HOST memory, read before the call returns): the entry of masks[] query b is searched
+ * under.  The result of query b — ids, distance bits, count, order and key — is what fvdb_ivf_search_wide_dev_slot returns
+ * for that query alone under masks[group_of_query[b]] (for k <= FVDB_MAX_K also what fvdb_ivf_search_dev_slot_masked
+ * returns).  Always the wide route, 1 <= k <= FVDB_MAX_K_WIDE, any nprobe >= 1, with fvdb_ivf_search_wide_dev_slot's
+ * limits: an index holding a shard of a larger one is FVDB_E_UNSUPPORTED.  Checked before anything is enqueued, and for
+ * every entry of masks[] whether a query names it or not: a mask of another index or a stale one, a group index >= G, and
+ * G == 0 with B > 0 are FVDB_E_INVALID.  Counts as a masked search (AUTO's watch does not see it).  Slot and stream rules
+ * are fvdb_ivf_search_dev_slot's. */
+int fvdb_ivf_search_groups_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* const* masks, uint32_t G,
+                                    const uint32_t* group_of_query, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                    uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_counts_dev, uint64_t* out_keys_dev);
 /* The same search (src/ivf/core.rs:626-681), blocking, with host pointers and leased scratch like fvdb_ivf_search: any
  * number of host threads may call it on one index. */
 int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
@@ -688,6 +702,14 @@ int fvdb_graph_search_dev_slot_masked(fvdb_graph* g, fvdb_ctx* on, uint32_t slot
  * out_nodes/out_dist: B x k (unused tail = FVDB_NO_ROW / +inf), out_counts[B].  k <= FVDB_MAX_K. */
 int fvdb_graph_scan_allowed_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                      uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
+/* The same scan with one mask per query: masks[G] are masks of this graph, none NULL (the
+ * unfiltered exact scan is fvdb_graph_search_flat_dev_slot), group_of_query[B] is HOST memory, read before the call
+ * returns.  Query b gets what fvdb_graph_scan_allowed_dev_slot returns for it under masks[group_of_query[b]].
+ * k <= FVDB_MAX_K.  Checked before anything is enqueued, every mask whether named or not: a NULL, foreign or stale mask,
+ * a group index >= G, and G == 0 with B > 0 are FVDB_E_INVALID. */
+int fvdb_graph_scan_allowed_groups_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* const* masks, uint32_t G,
+                                            const uint32_t* group_of_query, const float* q_dev, uint32_t B, uint32_t k,
+                                            uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
 
 /* ---- exact search ------------------------------------------------
  * Flat exact k-NN over the rows a graph holds, as they are stored, where they are stored (no counterpart in the
