@@ -1408,6 +1408,7 @@ __global__ __launch_bounds__(kBuildThreads, 1) void hnsw_insert_search_kernel(co
   const uint32_t nlog = c.misc[MS_NLOG];
   if (threadIdx.x == 0) {
     if (tstat[3] || !ok) atomicAdd(&g.state->spec_ties, 1u);
+    if (tstat[3]) atomicAdd(&g.state->ties, tstat[3]);  // a restart is a restart, whether or not the commit adopts the search
     out[1] = node;
     out[2] = st.entry;
     out[8 + layer] = (ok && nlog <= kLogCap) ? tag : 0u;

@@ -469,7 +469,7 @@ int fvdb_graph_search_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const
 typedef struct fvdb_graph_insert_stats {
   uint32_t n_done, needs_host;
   uint32_t speculated_ok, searched_in_commit, commit_stops;  /* speculation: adopted / searched by the commit workgroup / early stops */
-  uint32_t rounds, expanded, rows_scored, tie_restarts;      /* of the searches run by the commit workgroup */
+  uint32_t rounds, expanded, rows_scored, tie_restarts;      /* of the searches run by the commit workgroup; tie_restarts: of the speculated ones too */
   uint32_t launches;
 } fvdb_graph_insert_stats;
 int fvdb_graph_configure(fvdb_graph* g, uint32_t max_connections, uint32_t max_connections_layer_0);
