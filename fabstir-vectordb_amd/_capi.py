@@ -158,6 +158,7 @@ SIGNATURES = {
     "fvdb_host_alloc": (i32, [vp, C.c_size_t, C.POINTER(vp)]),
     "fvdb_host_free": (None, [vp, vp]),
     "fvdb_dev_download_async": (i32, [vp, vp, vp, C.c_size_t]),
+    "fvdb_dev_copy_async": (i32, [vp, vp, vp, C.c_size_t]),
     "fvdb_event_create": (i32, [vp, C.POINTER(vp)]),
     "fvdb_event_destroy": (None, [vp]),
     "fvdb_event_record": (i32, [vp, vp]),

@@ -1527,6 +1527,10 @@ int fvdb_dev_download_async(fvdb_ctx* ctx, void* dst_pinned, const void* src, si
   HIPCHK(ctx, hipMemcpyAsync(dst_pinned, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   return FVDB_OK;
 }
+int fvdb_dev_copy_async(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes) {
+  HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return FVDB_OK;
+}
 struct fvdb_event {
   hipEvent_t ev = nullptr;
 };

@@ -674,6 +674,9 @@ class HybridIndex {
   // enqueues everything for the batch (traversal kernel on the slot's stream, IVF chain and its result copies on
   // the IVF stream) and returns; end waits for that slot only and merges on the host.  The query buffer must stay
   // valid and unchanged until end.  Mutations between a begin and its end are not allowed.
+  // Timing of the IVF part (unsharded, no allow-set; see Pair below): begin enqueues the graph walk at once, the IVF chain
+  // of the batch may start at the NEXT begin — one chain then serves both batches — or at its own end.  Results and
+  // error codes are unchanged; an error of a chain enqueued after begin returned comes back from that batch's end.
   static constexpr uint32_t kSlots = HNSWIndex::kSlots;
   int search_dev_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                        double now);
@@ -820,8 +823,9 @@ class HybridIndex {
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                      int shard_mode, double now, const uint64_t* allowed = nullptr, uint64_t n_allowed = 0,
                      bool masked = false);
+  // may_pair: the caller is the explicit pair's begin, whose IVF chain may wait for a partner (Pair below)
   int begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                 int shard_mode = -1);
+                 int shard_mode = -1, bool may_pair = false);
   int build_masks(const HybridSearchConfig& cfg, const uint64_t* allowed, uint64_t n_allowed, HNSWIndex::ViewRef* view,
                   MaskRef* ivf_mask);
   // The per-search auto-migration (src/hybrid/core.rs:437-439).  A due migration moves rows between the two indexes (and
@@ -861,6 +865,7 @@ class HybridIndex {
   mutable std::mutex slot_mu_;     // Slot::active
   std::condition_variable slot_cv_;
   fvdb_ctx* ctx_ivf_;
+  struct Pair;
   struct Slot {  // one batch in flight
     DevBuf ivf;             // results of the IVF part (IvfBlock layout): device block and its pinned host copy
     uint32_t ivf_rows = 0;  // rows the IVF part writes into it for this batch
@@ -873,8 +878,46 @@ class HybridIndex {
     // a search under an allow-set holds its masks here from begin to end
     MaskRef ivf_mask;
     HNSWIndex::ViewRef view;
+    // paired IVF chains (below): all four under pair_mu_
+    bool ivf_waiting = false;  // the IVF chain of this batch is not enqueued yet (q, B, dim, hk, n_probe say what it is)
+    uint32_t n_probe = 0;
+    int ivf_rc = FVDB_OK;      // status of an enqueue that happened after this batch's begin returned; search_dev_end's
+    Pair* pair = nullptr;      // the joint chain this batch's IVF rows come from, starting at row pair_off
+    uint32_t pair_off = 0;
   };
   Slot slots_[kSlots];
+  // One IVF chain for two batches in flight.  A batch begun with search_dev_begin on an unsharded
+  // index without an allow-set does not enqueue its IVF chain: it waits (waiting_) for the next such begin, which
+  // enqueues ONE chain for the queries of both on its own slot's stream and scratch set, or for its own end, a blocking
+  // search or a writer, which enqueue it alone (flush_waiting).
+  // Lifetime: the joint query block, the result blocks and the event belong to the Pair, never to a slot — the slot that
+  // launched may be collected and begun again (its event re-recorded, its block rewritten) before its partner is
+  // collected.  A Pair is held by the slots that read from it (refs) and free again after the second search_dev_end.
+  struct Pair {
+    DevBuf q;    // [B1 + B2][dim], the waiting batch first
+    DevBuf res;  // IvfBlock layout over rows = B1 + B2, with its pinned host copy
+    fvdb_event* done = nullptr;
+    fvdb_ctx* ctx = nullptr;  // the context whose stream carries the chain (the launching slot's)
+    uint32_t rows = 0, hk = 0, refs = 0;
+  };
+  static constexpr uint32_t kPairs = kSlots / 2;
+  static constexpr uint32_t kPairRowsMax = 16384;  // B1 + B2 of a joint chain: the largest batch the engine's parity tests run
+  // pairs can outnumber kPairs only when partners are collected far apart; a begin that finds none free does not pair
+  Pair pairs_[kPairs];
+  std::mutex pair_mu_;  // waiting_, the pool, the Slot fields above, and every enqueue of an IVF chain of the explicit pair
+  int waiting_ = -1;
+  static bool pairing_enabled();  // FVDB_HYBRID_PAIR=0 (read once) restores one chain per batch, enqueued at begin
+  // one batch alone: chain, result copy and event on the slot's own stream
+  int enqueue_ivf(uint32_t slot, const float* q_dev, uint32_t B_in, uint32_t ivf_rows, uint32_t dim, uint64_t n_probe,
+                  int shard_mode);
+  int enqueue_ivf_pair(Slot& first, uint32_t launcher, Pair& p);  // pair_mu_ held
+  int begin_ivf_paired(uint32_t slot);                            // takes pair_mu_
+  void flush_waiting_locked();                                    // pair_mu_ held: the waiting batch's chain, alone
+  void flush_waiting() {
+    std::lock_guard<std::mutex> lk(pair_mu_);
+    flush_waiting_locked();
+  }
+  void release_pair(Slot& sl);  // takes pair_mu_
   int stage_finite(Slot& sl, const float* q, uint32_t B, uint32_t dim);
   // A slot keeps a filtered search's masks only while that search runs: dropped at scope exit, whichever way it
   // returns, so that the next user of the slot finds none.  sl = nullptr: handed on to the search_dev_end that collects.

@@ -18,6 +18,13 @@ HybridIndex::HybridIndex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, const HybridConf
 
 HybridIndex::~HybridIndex() {
   qual_.release();
+  // a batch that still waits for a partner has nothing enqueued for its IVF part; joint chains in flight end with the
+  // release of their blocks, as the slots' own do
+  for (Pair& p : pairs_) {
+    p.q.release();
+    p.res.release();
+    if (p.done) fvdb_event_destroy(p.done);
+  }
   for (Slot& sl : slots_) {
     sl.ivf.release();
     if (sl.ivf_done) fvdb_event_destroy(sl.ivf_done);
@@ -58,6 +65,7 @@ int HybridIndex::set_ivf_centroids(const float* c, uint32_t dim) {
 int HybridIndex::write_lock(std::unique_lock<std::shared_mutex>& w) {
   for (;;) {
     w.lock();  // the blocking searches of other threads hold the read side for their whole duration: waited for here
+    flush_waiting();  // a batch whose IVF chain still waits for a partner: enqueued now, so that its collector only waits
     if (!busy()) return FVDB_OK;
     w.unlock();  // what is left in flight was begun with search_dev_begin and not collected yet
     if (!writers_wait_) return FVDB_E_INVALID;
@@ -531,7 +539,7 @@ int HybridIndex::begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, u
   slots_[slot].view.reset();
   if (masked && initialized_ && cfg.k != 0)  // search_dev_end drops them
     if (int rc = build_masks(cfg, allowed, n_allowed, &slots_[slot].view, &slots_[slot].ivf_mask)) return rc;
-  return begin_impl(slot, q_dev, B, dim, cfg, shard_mode);
+  return begin_impl(slot, q_dev, B, dim, cfg, shard_mode, shard_mode < 0 && !masked);
 }
 
 // The masks of a filtered search, one per part that is searched.  Every caller builds them after the migration step and
@@ -564,6 +572,7 @@ int HybridIndex::attach_comm(fvdb_comm* comm) {
   // fp16 rows: the sharded step and the replicated graph have not been taken through half-width rows yet
   if (comm && cfg_.row_dtype() == FVDB_F16) return FVDB_E_UNSUPPORTED;
   std::unique_lock<std::shared_mutex> w(rw_);
+  flush_waiting();  // no chain is left to be enqueued under another communicator
   if (busy()) return FVDB_E_INVALID;
   if (sharded_) fvdb_sharded_destroy(sharded_);
   sharded_ = nullptr;
@@ -617,11 +626,140 @@ struct IvfBlock {
 };
 }  // namespace
 
+static bool ivf_one_stream() {
+  static const bool on = getenv("FVDB_IVF_ONE_STREAM") != nullptr;  // tuning aid
+  return on;
+}
+
+bool HybridIndex::pairing_enabled() {
+  static const bool on = [] {
+    const char* v = getenv("FVDB_HYBRID_PAIR");  // A/B switch, read once
+    return !(v && std::strcmp(v, "0") == 0);
+  }();
+  return on;
+}
+
+// The IVF chain of one batch on the slot's own stream with its own scratch set, the result copy right behind it, then
+// the event.
+int HybridIndex::enqueue_ivf(uint32_t slot, const float* q_dev, uint32_t B_in, uint32_t ivf_rows, uint32_t dim, uint64_t n_probe,
+                             int shard_mode) {
+  Slot& sl = slots_[slot];
+  const uint64_t bytes = IvfBlock::bytes(ivf_rows, sl.hk);
+  if (int rc = sl.ivf.reserve(ctx_ivf_, bytes, true)) return rc;
+  sl.ivf_rows = ivf_rows;
+  const IvfBlock d(sl.ivf.dev, ivf_rows, sl.hk);
+  // each slot's IVF chain runs on its own stream with its own scratch set, so the chains of consecutive batches
+  // overlap (a chain is ~20 dependent launches with gaps between them)
+  if (slot_ctx(ctx_ivf_, slot == 0 || ivf_one_stream(), &sl.ivf_ctx)) return FVDB_E_HIP;
+  fvdb_ctx* on = sl.ivf_ctx == ctx_ivf_ ? nullptr : sl.ivf_ctx;
+  if (!sl.ivf_done && fvdb_event_create(sl.ivf_ctx, &sl.ivf_done)) return FVDB_E_HIP;
+  if (shard_mode >= 0) {
+    // every rank must take part in the step's collectives even when its own slice is empty
+    if (dim != historical_->dimension()) return FVDB_E_DIM;
+    // k or nprobe beyond the register path, or an allow-set: the wide sharded step; otherwise the call as ever
+    const bool beyond = sl.hk > FVDB_MAX_K || n_probe > FVDB_MAX_K || sl.ivf_mask;
+    const int rcs = beyond ? fvdb_ivf_search_sharded_wide_begin(sharded_, on, on ? slot : 0, sl.ivf_mask.get(), q_dev, B_in,
+                                                                sl.hk, (uint32_t)std::min<uint64_t>(n_probe, 0xFFFFFFFFu),
+                                                                shard_mode, d.ids, d.dist, d.counts)
+                           : fvdb_ivf_search_sharded_begin(sharded_, on, on ? slot : 0, q_dev, B_in, sl.hk, (uint32_t)n_probe,
+                                                           shard_mode, d.ids, d.dist, d.counts);
+    if (rcs) return rcs;
+  } else {
+    // a historical part the engine refuses (historical_k above FVDB_MAX_K_WIDE, say) fails the search: the result
+    // must never quietly be the recent rows alone
+    const int rch = sl.ivf_mask ? historical_->search_dev_masked(sl.ivf_mask, q_dev, B_in, dim, sl.hk, (uint32_t)n_probe, d.ids,
+                                                                 d.dist, d.counts, on, on ? slot : 0)
+                                : historical_->search_dev(q_dev, B_in, dim, sl.hk, (uint32_t)n_probe, d.ids, d.dist, d.counts, on,
+                                                          on ? slot : 0);
+    if (rch) return rch;
+  }
+  sl.ivf_in_flight = true;
+  // result copy rides the slot's stream right behind the chain, then the event
+  if (fvdb_dev_download_async(sl.ivf_ctx, sl.ivf.host, sl.ivf.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, sl.ivf_done))
+    return FVDB_E_HIP;
+  return FVDB_OK;
+}
+
+// One chain for the waiting batch `first` and the batch of slot `launcher`, on the launcher's stream with its scratch
+// set, into the Pair's own blocks.  pair_mu_ held.
+int HybridIndex::enqueue_ivf_pair(Slot& first, uint32_t launcher, Pair& p) {
+  Slot& sl = slots_[launcher];
+  const uint32_t rows = first.B + sl.B, dim = sl.dim;
+  const uint64_t bytes = IvfBlock::bytes(rows, sl.hk);
+  if (int rc = p.q.reserve(ctx_ivf_, (uint64_t)rows * dim * 4, false)) return rc;
+  if (int rc = p.res.reserve(ctx_ivf_, bytes, true)) return rc;
+  if (slot_ctx(ctx_ivf_, launcher == 0 || ivf_one_stream(), &sl.ivf_ctx)) return FVDB_E_HIP;
+  fvdb_ctx* on = sl.ivf_ctx == ctx_ivf_ ? nullptr : sl.ivf_ctx;
+  if (!p.done && fvdb_event_create(sl.ivf_ctx, &p.done)) return FVDB_E_HIP;
+  float* q = (float*)p.q.dev;
+  if (fvdb_dev_copy_async(sl.ivf_ctx, q, first.q, (size_t)first.B * dim * 4) ||
+      fvdb_dev_copy_async(sl.ivf_ctx, q + (size_t)first.B * dim, sl.q, (size_t)sl.B * dim * 4))
+    return FVDB_E_HIP;
+  const IvfBlock d(p.res.dev, rows, sl.hk);
+  if (int rc = historical_->search_dev(q, rows, dim, sl.hk, sl.n_probe, d.ids, d.dist, d.counts, on, on ? launcher : 0)) return rc;
+  if (fvdb_dev_download_async(sl.ivf_ctx, p.res.host, p.res.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, p.done))
+    return FVDB_E_HIP;
+  p.ctx = sl.ivf_ctx;
+  p.rows = rows;
+  p.hk = sl.hk;
+  p.refs = 2;
+  first.pair = sl.pair = &p;
+  first.pair_off = 0;
+  sl.pair_off = first.B;
+  first.ivf_in_flight = sl.ivf_in_flight = true;
+  return FVDB_OK;
+}
+
+// pair_mu_ held: the waiting batch goes alone, on its own slot's stream; what that returns is its search_dev_end's
+void HybridIndex::flush_waiting_locked() {
+  if (waiting_ < 0) return;
+  Slot& w = slots_[waiting_];
+  w.ivf_waiting = false;
+  w.ivf_rc = enqueue_ivf((uint32_t)waiting_, w.q, w.B, w.B, w.dim, w.n_probe, -1);
+  waiting_ = -1;
+}
+
+// The IVF part of an explicit begin that may share its chain: with the waiting batch if there is a compatible one (same
+// dim, historical k and n_probe; the index cannot have changed, both slots being in flight), else this batch waits.
+int HybridIndex::begin_ivf_paired(uint32_t slot) {
+  Slot& sl = slots_[slot];
+  std::lock_guard<std::mutex> lk(pair_mu_);
+  if (waiting_ >= 0) {
+    Slot& w = slots_[waiting_];
+    Pair* p = nullptr;
+    if (w.dim == sl.dim && w.hk == sl.hk && w.n_probe == sl.n_probe && (uint64_t)w.B + sl.B <= kPairRowsMax)
+      for (Pair& c : pairs_)
+        if (c.refs == 0) {
+          p = &c;
+          break;
+        }
+    if (p) {
+      w.ivf_waiting = false;
+      waiting_ = -1;
+      const int rc = enqueue_ivf_pair(w, slot, *p);
+      if (rc) w.ivf_rc = rc;  // nothing of a joint chain that failed is collected, and each batch reports the status
+      return rc;
+    }
+    flush_waiting_locked();
+  }
+  sl.ivf_waiting = true;
+  waiting_ = (int)slot;
+  return FVDB_OK;
+}
+
+void HybridIndex::release_pair(Slot& sl) {
+  std::lock_guard<std::mutex> lk(pair_mu_);
+  if (!sl.pair) return;
+  sl.pair->refs -= 1;
+  sl.pair = nullptr;
+}
+
 // enqueue everything for the batch; the slot is already marked active by the caller
 int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
-                            int shard_mode) {
+                            int shard_mode, bool may_pair) {
   Slot& sl = slots_[slot];
   sl.ivf_in_flight = sl.hnsw_in_flight = false;
+  sl.ivf_rc = FVDB_OK;
   // sharded: `q_own` / `Bown` are the queries whose final results this rank produces (the graph is replicated, so each
   // rank walks it for those only); the IVF part is handed the batch as the mode defines it
   const float* q_own = q_dev;
@@ -650,43 +788,23 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
     sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot, sl.view.get());
   }
   if (cfg.search_historical && ivf_trained_) {
-    const uint64_t bytes = IvfBlock::bytes(ivf_rows, sl.hk);
-    if (int rc = sl.ivf.reserve(ctx_ivf_, bytes, true)) return rc;
-    sl.ivf_rows = ivf_rows;
-    const IvfBlock d(sl.ivf.dev, ivf_rows, sl.hk);
-    // each slot's IVF chain runs on its own stream with its own scratch set, so the chains of consecutive batches
-    // overlap (a chain is ~20 dependent launches with gaps between them)
-    static const bool one_stream = getenv("FVDB_IVF_ONE_STREAM") != nullptr;  // tuning aid
-    if (slot_ctx(ctx_ivf_, slot == 0 || one_stream, &sl.ivf_ctx)) return FVDB_E_HIP;
-    fvdb_ctx* on = sl.ivf_ctx == ctx_ivf_ ? nullptr : sl.ivf_ctx;
-    if (!sl.ivf_done && fvdb_event_create(sl.ivf_ctx, &sl.ivf_done)) return FVDB_E_HIP;
-    if (shard_mode >= 0) {
-      // every rank must take part in the step's collectives even when its own slice is empty
+    sl.n_probe = (uint32_t)cfg.ivf_n_probe;
+    // The explicit pair on an unsharded index without an allow-set, inside the register path's k and n_probe (the route
+    // every batch size takes alike): the chain may be shared with the next batch begun.  A dimension the engine would
+    // refuse is refused now, as ever; what is left to fail later is the enqueue itself.
+    const bool pairable = may_pair && pairing_enabled() && shard_mode < 0 && !sharded_ && !sl.ivf_mask && B > 0 &&
+                          sl.hk <= FVDB_MAX_K && cfg.ivf_n_probe > 0 &&
+                          std::min<uint64_t>(cfg.ivf_n_probe, historical_->config().n_clusters) <= FVDB_MAX_K;
+    if (pairable) {
       if (dim != historical_->dimension()) return FVDB_E_DIM;
-      // k or nprobe beyond the register path, or an allow-set: the wide sharded step; otherwise the call as ever
-      const bool beyond = sl.hk > FVDB_MAX_K || cfg.ivf_n_probe > FVDB_MAX_K || sl.ivf_mask;
-      const int rcs = beyond ? fvdb_ivf_search_sharded_wide_begin(sharded_, on, on ? slot : 0, sl.ivf_mask.get(), q_dev, B_ivf_in,
-                                                                  sl.hk, (uint32_t)std::min<uint64_t>(cfg.ivf_n_probe, 0xFFFFFFFFu),
-                                                                  shard_mode, d.ids, d.dist, d.counts)
-                             : fvdb_ivf_search_sharded_begin(sharded_, on, on ? slot : 0, q_dev, B_ivf_in, sl.hk,
-                                                             (uint32_t)cfg.ivf_n_probe, shard_mode, d.ids, d.dist, d.counts);
-      if (rcs) return rcs;
-      sl.ivf_in_flight = true;
-    } else {
-      // a historical part the engine refuses (historical_k above FVDB_MAX_K_WIDE, say) fails the search: the result
-      // must never quietly be the recent rows alone
-      const int rch = sl.ivf_mask ? historical_->search_dev_masked(sl.ivf_mask, q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe,
-                                                                   d.ids, d.dist, d.counts, on, on ? slot : 0)
-                                  : historical_->search_dev(q_dev, B, dim, sl.hk, (uint32_t)cfg.ivf_n_probe, d.ids, d.dist,
-                                                            d.counts, on, on ? slot : 0);
-      if (rch) return rch;
-      sl.ivf_in_flight = true;
+      return begin_ivf_paired(slot);
     }
-    if (sl.ivf_in_flight) {
-      // result copy rides the slot's stream right behind the chain, then the event
-      if (fvdb_dev_download_async(sl.ivf_ctx, sl.ivf.host, sl.ivf.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, sl.ivf_done))
-        return FVDB_E_HIP;
+    std::unique_lock<std::mutex> lk(pair_mu_, std::defer_lock);
+    if (may_pair) {  // an explicit begin that cannot share: the chains still start in the order their batches were begun
+      lk.lock();
+      flush_waiting_locked();
     }
+    return enqueue_ivf(slot, q_dev, B_ivf_in, ivf_rows, dim, cfg.ivf_n_probe, shard_mode);
   }
   return FVDB_OK;
 }
@@ -701,6 +819,17 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   DropMasks drop_masks{&sl};
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
+  {
+    // still waiting for a partner: its chain goes alone now, on its own slot's stream
+    std::lock_guard<std::mutex> lk(pair_mu_);
+    if (sl.ivf_waiting) flush_waiting_locked();
+  }
+  // the joint chain's blocks are the Pair's: given up when this batch has read its rows, whichever way this returns
+  struct DropPair {
+    HybridIndex* h;
+    Slot* sl;
+    ~DropPair() { h->release_pair(*sl); }
+  } drop_pair{this, &sl};
   std::vector<uint64_t> rid;
   std::vector<float> rd;
   std::vector<uint32_t> rc_(B, 0);
@@ -713,8 +842,16 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   }
   IvfBlock h;
   if (sl.ivf_in_flight) {
-    have_h = fvdb_event_wait(sl.ivf_ctx, sl.ivf_done) == FVDB_OK;
-    h = IvfBlock(sl.ivf.host, sl.ivf_rows, sl.hk);
+    if (const Pair* p = sl.pair) {  // this batch's rows of the joint block
+      have_h = fvdb_event_wait(p->ctx, p->done) == FVDB_OK;
+      const IvfBlock all(p->res.host, p->rows, p->hk);
+      h.ids = all.ids + (size_t)sl.pair_off * p->hk;
+      h.dist = all.dist + (size_t)sl.pair_off * p->hk;
+      h.counts = all.counts + sl.pair_off;
+    } else {
+      have_h = fvdb_event_wait(sl.ivf_ctx, sl.ivf_done) == FVDB_OK;
+      h = IvfBlock(sl.ivf.host, sl.ivf_rows, sl.hk);
+    }
     bool others = false;
     {
       std::lock_guard<std::mutex> lk(slot_mu_);
@@ -724,7 +861,9 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   }
   merge_parts(B, k, sl.rk, sl.hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, h.ids, h.dist, h.counts, ids, dist,
               counts);
-  return FVDB_OK;
+  const int late = sl.ivf_rc;  // of a chain enqueued after this batch's begin had returned; FVDB_OK otherwise
+  sl.ivf_rc = FVDB_OK;
+  return late;
 }
 
 // The blocking entry points: any number of host threads.  A call holds the read side of rw_ from after its migration
@@ -763,6 +902,7 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
     if (int rc = stage_finite(sl, q, B, dim)) return rc;
     qd = (const float*)sl.d_q.dev;
   }
+  flush_waiting();  // a chain that waits for a partner starts before this search's, as it would have without pairing
   const int rc0 = begin_impl(slot, qd, B, dim, cfg);
   if (rc0 && !sl.hnsw_in_flight && !sl.ivf_in_flight) return rc0;
   lease.hand_over();

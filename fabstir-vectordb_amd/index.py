@@ -1064,7 +1064,10 @@ class HybridIndex(_Base):
         """Enqueue a batch search in `slot` (0..SLOTS-1) and return at once; several slots may be in flight together
         (the graph walk of one batch uses one wavefront per SIMD, so a second batch's walk runs beside it).  The
         query buffer must stay valid until search_dev_end(slot).  Inserts, deletes and migrations are refused (status
-        INVALID) while any slot is in flight, and so is a begin whose `now` makes an auto-migration due."""
+        INVALID) while any slot is in flight, and so is a begin whose `now` makes an auto-migration due.
+        Timing: the graph walk starts now; the IVF part of the batch may start at the NEXT search_dev_begin — one IVF
+        chain then serves both batches — or at this batch's own search_dev_end (unsharded index, no allow-set;
+        FVDB_HYBRID_PAIR=0 starts every chain at its begin).  Results and error codes are unchanged."""
         self._check(self.lib.fvh_hybrid_search_dev_begin(self.h, slot, q_dev, B, dim, k, hnsw_ef, ivf_n_probe,
                                                          int(search_recent), int(search_historical), recent_k,
                                                          historical_k, float(now)))

@@ -103,6 +103,13 @@ int fvdb_dev_download(fvdb_ctx* ctx, void* dst_host, const void* src_dev, size_t
 int fvdb_host_alloc(fvdb_ctx* ctx, size_t bytes, void** out);
 void fvdb_host_free(fvdb_ctx* ctx, void* p);
 int fvdb_dev_download_async(fvdb_ctx* ctx, void* dst_pinned, const void* src_dev, size_t bytes);
+/* device to device on ctx's stream, without waiting: the source must stay unchanged until the stream has passed it */
+int fvdb_dev_copy_async(fvdb_ctx* ctx, void* dst_dev, const void* src_dev, size_t bytes);
+/* The host mirror's hybrid begin/end pair (HybridIndex::search_dev_begin / search_dev_end, fvh_hybrid_search_dev_begin /
+ * _end) is built from these.  Timing rule of that pair: the graph walk of a batch is enqueued by its begin; its IVF part
+ * may be enqueued later — by the NEXT begin, which then runs one IVF chain for both batches (their queries copied side
+ * by side with fvdb_dev_copy_async), or by the batch's own end.  Results and error codes are what they would be had
+ * every chain been enqueued at once; the query buffer must stay valid and unchanged until end, as ever. */
 typedef struct fvdb_event fvdb_event;
 int fvdb_event_create(fvdb_ctx* ctx, fvdb_event** out);
 void fvdb_event_destroy(fvdb_event* e);
