@@ -49,7 +49,17 @@ class GraphSearchInfo(C.Structure):
                                    "cand_cap", "spill_cap", "lds_bytes", "reserved")] + [("visited_bytes", u64)]
 
 
+class GraphHealth(C.Structure):
+    """fvdb_graph_health_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("n_nodes", "n_live", "has_entry", "entry_live", "entry_level", "max_level_live")] + \
+               [(n, u64) for n in ("edge_slots_live", "dangling", "dangling0")] + [("degree0_hist", u32 * 65)] + \
+               [(n, u32) for n in ("reachable_live", "unreachable_live", "reach_rounds0", "components0", "largest_component0",
+                                   "isolated0", "launches", "reach_launches", "host_syncs")] + \
+               [("ms", f32), ("scratch_bytes", u64)]
+
+
 VACUUM_KEEP_ROWS = 1  # FVDB_VACUUM_KEEP_ROWS
+HEALTH_SKIP_REACH, HEALTH_SKIP_COMPONENTS = 1, 2  # FVDB_HEALTH_SKIP_*
 
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
 # tests/test_cabi_symbols.py checks the built library exports each of them.
@@ -148,6 +158,9 @@ SIGNATURES = {
     "fvdb_graph_search_info": (i32, [vp, u32, u32, C.POINTER(GraphSearchInfo)]),
     "fvdb_graph_vacuum": (i32, [vp, u32, u64p]),
     "fvdb_graph_maintenance_info": (i32, [vp, C.POINTER(GraphMaintenanceInfo)]),
+    # graph health
+    "fvdb_graph_health": (i32, [vp, u32, C.POINTER(GraphHealth)]),
+    "fvdb_graph_health_nodes": (i32, [vp, C.POINTER(C.c_uint8), u32p]),
     "fvdb_graph_search_dev": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_graph_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ctx_device": (i32, [vp]),

@@ -20,6 +20,7 @@
 #include "kernels_graph_fast.h"
 #include "kernels_graph_build.h"
 #include "kernels_graph_maint.h"
+#include "kernels_graph_health.h"
 
 using namespace fvdb;
 
@@ -40,6 +41,10 @@ struct fvdb_graph {
   uint64_t upload_bytes = 0;        // host -> device bytes of graph STRUCTURE (not vectors) since creation
   fvdb_graph_insert_stats last{};
   fvdb_graph_maintenance_info_t m_info{};  // the last fvdb_graph_vacuum
+  // per-node results of the last fvdb_graph_health: the reach bitmap, the layer-0 component labels, and `mutations` then
+  DBuf d_hreach, d_hlabel;
+  uint32_t health_has = 0, health_n = 0;  // bit 0: d_hreach is filled, bit 1: d_hlabel is; the node count then
+  uint64_t health_at = ~0ull;
   // form of the device insert's `visited` (fvdb_graph_set_insert_visited) and what the hashed form has seen since creation
   int ins_vis_mode = 0;
   uint32_t ins_vis_slots = 0;
@@ -634,7 +639,8 @@ void fvdb_graph_destroy(fvdb_graph* g) {
   (void)hipSetDevice(g->store->ctx->device);
   (void)hipStreamSynchronize(g->store->ctx->stream);
   DBuf* bufs[] = {&g->d_level, &g->d_deleted, &g->d_ubase, &g->d_adj0, &g->d_adjU, &g->d_dist0, &g->d_distU, &g->d_stamp0,
-                  &g->d_stampU, &g->d_state, &g->d_spec, &g->d_elog, &g->d_chg, &g->s_patch, &g->s_codes, &g->s_q, &g->d_counters, &g->d_stamps, &g->d_build_stamps};
+                  &g->d_stampU, &g->d_state, &g->d_spec, &g->d_elog, &g->d_chg, &g->s_patch, &g->s_codes, &g->s_q, &g->d_counters, &g->d_stamps, &g->d_build_stamps,
+                  &g->d_hreach, &g->d_hlabel};
   for (auto& b : g->s_visited) b.release();
   for (auto& b : g->s_touched) b.release();
   for (auto& b : g->s_spill) b.release();
@@ -1389,6 +1395,184 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
 extern "C" int fvdb_graph_maintenance_info(fvdb_graph* g, fvdb_graph_maintenance_info_t* out) {
   if (!g || !out) return FVDB_E_INVALID;
   *out = g->m_info;
+  return FVDB_OK;
+}
+
+// =============================================================================================
+// device-resident graph: health (kernels_graph_health.h).  Read-only: no flag, list, stamp, visited
+// map or counter of the graph is written, and `mutations` does not move.
+// =============================================================================================
+extern "C" int fvdb_graph_health(fvdb_graph* g, uint32_t flags, fvdb_graph_health_t* out) {
+  if (!g || !out) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = g->store->ctx;
+  std::memset(out, 0, sizeof *out);
+  if (flags & ~(FVDB_HEALTH_SKIP_REACH | FVDB_HEALTH_SKIP_COMPONENTS)) FAIL(ctx, FVDB_E_INVALID, "graph health: unknown flag");
+  if (!g->uploaded) FAIL(ctx, FVDB_E_INVALID, "graph health: no device graph");
+  const bool want_reach = !(flags & FVDB_HEALTH_SKIP_REACH), want_comp = !(flags & FVDB_HEALTH_SKIP_COMPONENTS);
+  const uint32_t n = g->n;
+  if (n >= 0x80000000u) FAIL(ctx, FVDB_E_UNSUPPORTED, "graph health: 2^31 nodes or more");
+  g->health_has = 0;
+  if (n == 0) {
+    g->health_has = (want_reach ? 1u : 0u) | (want_comp ? 2u : 0u);
+    g->health_n = 0;
+    g->health_at = g->mutations;
+    return FVDB_OK;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // every allocation precedes the first launch: [counters | state] words, then list, parent, size; bitmap and labels are kept
+  const size_t bitmap_bytes = (size_t)cdiv(n, 32) * 4, node_bytes = (size_t)n * 4;
+  const size_t head_bytes = (size_t)kGhCounters * 8 + kGhStateWords * 4;
+  DBuf head, list, parent, size, bitmap, label;
+  auto drop = [&]() {
+    for (DBuf* b : {&head, &list, &parent, &size, &bitmap, &label}) b->release();
+  };
+  {
+    hipError_t e = head.ensure(head_bytes);
+    if (e == hipSuccess && want_reach) e = list.ensure(node_bytes);
+    if (e == hipSuccess && want_reach) e = bitmap.ensure(bitmap_bytes);
+    if (e == hipSuccess && want_comp) e = parent.ensure(node_bytes);
+    if (e == hipSuccess && want_comp) e = size.ensure(node_bytes);
+    if (e == hipSuccess && want_comp) e = label.ensure(node_bytes);
+    if (e == hipSuccess) e = g->h_state.ensure(std::max(head_bytes, sizeof(BuildState)));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      drop();
+      FAIL(ctx, e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, "graph health: no memory for the scratch (graph unchanged)");
+    }
+  }
+  out->scratch_bytes = head.cap + list.cap + parent.cap + size.cap + bitmap.cap + label.cap;
+  StageEvents ev;
+  if (!ev.make()) {
+    drop();
+    FAIL(ctx, FVDB_E_HIP, "graph health: no events");
+  }
+  auto fail = [&](hipError_t e) {
+    drop();
+    ctx->set_err(std::string("graph health: ") + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP;
+  };
+#define GH_TRY(call)                      \
+  do {                                    \
+    const hipError_t e_ = (call);         \
+    if (e_ != hipSuccess) return fail(e_); \
+  } while (0)
+  unsigned long long* counters = head.as<unsigned long long>();
+  uint32_t* state = (uint32_t*)(counters + kGhCounters);
+  uint32_t* h_words = (uint32_t*)g->h_state.p;
+  const GhGraph gg{g->d_adj0.as<uint32_t>(), g->d_adjU.as<uint32_t>(), g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(),
+                   g->d_ubase.as<uint32_t>(), n, g->u_rows, g->stride0, g->strideU};
+  const bool has_entry = g->has_entry && g->entry < n;
+  const uint32_t entry = has_entry ? g->entry : kGhNone;
+  uint32_t launches = 0, reach_launches = 0, host_syncs = 0, rounds0 = 0, reached = 0;
+  GH_TRY(hipEventRecord(ev.ev[0], st));
+  GH_TRY(hipMemsetAsync(head.p, 0, head_bytes, st));
+  // census
+  hipLaunchKernelGGL(gh_census_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, gg, counters);
+  launches += 1;
+  GH_TRY(hipGetLastError());
+  // reach: layer by layer from the entry point's level, each layer closed step by step
+  if (want_reach) {
+    GH_TRY(hipMemsetAsync(bitmap.p, 0, bitmap_bytes, st));
+    if (has_entry) {
+      hipLaunchKernelGGL(gh_seed_kernel, dim3(1), dim3(64), 0, st, entry, n, bitmap.as<uint32_t>(), list.as<uint32_t>(), state);
+      launches += 1;
+      uint32_t tail = 1;
+      for (uint32_t layer = g->h_level[entry] + 1; layer-- > 0;) {
+        uint32_t lo = 0, hi = tail;  // the layer starts from everything reached so far
+        while (hi > lo) {
+          const bool narrow = hi - lo <= kGhQueue;
+          if (narrow)
+            hipLaunchKernelGGL(gh_reach_narrow_kernel, dim3(1), dim3(kGhNarrowThreads), 0, st, gg, layer, entry, lo, hi, bitmap.as<uint32_t>(),
+                               list.as<uint32_t>(), state);
+          else
+            hipLaunchKernelGGL(gh_reach_wide_kernel, dim3(prune_grid(ctx, hi - lo)), dim3(256), 0, st, gg, layer, entry, lo, hi,
+                               bitmap.as<uint32_t>(), list.as<uint32_t>(), state);
+          launches += 1;
+          reach_launches += 1;
+          GH_TRY(hipGetLastError());
+          GH_TRY(hipMemcpyAsync(h_words, state, kGhStateWords * 4, hipMemcpyDeviceToHost, st));
+          GH_TRY(hipStreamSynchronize(st));
+          host_syncs += 1;
+          tail = std::min(h_words[kGhTail], n);
+          if (tail < hi) return fail(hipErrorUnknown);  // cannot happen: the list only grows
+          if (layer == 0) rounds0 += narrow ? h_words[kGhSteps] : 1u;
+          lo = narrow ? std::min(std::max(h_words[kGhFrontier], hi), tail) : hi;
+          hi = tail;
+        }
+      }
+      reached = tail;
+    }
+  }
+  // weak components of the live layer-0 graph
+  if (want_comp) {
+    hipLaunchKernelGGL(uf_init_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, parent.as<uint32_t>(), size.as<uint32_t>());
+    hipLaunchKernelGGL(uf_union_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, gg, parent.as<uint32_t>());
+    hipLaunchKernelGGL(uf_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, gg.deleted, n, parent.as<uint32_t>(), label.as<uint32_t>(),
+                       size.as<uint32_t>());
+    hipLaunchKernelGGL(uf_summary_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, label.as<uint32_t>(), size.as<uint32_t>(), n, counters);
+    launches += 4;
+    GH_TRY(hipGetLastError());
+  }
+  GH_TRY(hipEventRecord(ev.ev[1], st));
+  GH_TRY(hipMemcpyAsync(g->h_state.p, counters, (size_t)kGhCounters * 8, hipMemcpyDeviceToHost, st));
+  GH_TRY(hipStreamSynchronize(st));
+  host_syncs += 1;
+#undef GH_TRY
+  const unsigned long long* c = (const unsigned long long*)g->h_state.p;
+  out->n_nodes = n;
+  out->n_live = (uint32_t)c[kGhLive];
+  out->has_entry = has_entry ? 1u : 0u;
+  out->entry_live = has_entry && !g->h_deleted[entry] ? 1u : 0u;
+  out->entry_level = has_entry ? g->h_level[entry] : 0u;
+  out->max_level_live = (uint32_t)c[kGhMaxLevel];
+  out->edge_slots_live = c[kGhSlots];
+  out->dangling = c[kGhDangling];
+  out->dangling0 = c[kGhDangling0];
+  for (uint32_t b = 0; b < 65; ++b) out->degree0_hist[b] = (uint32_t)c[kGhHist + b];
+  if (want_reach) {
+    // the entry point is in R whether it is live or not; everything else in R is live
+    out->reachable_live = reached - ((has_entry && !out->entry_live) ? 1u : 0u);
+    out->unreachable_live = out->n_live - out->reachable_live;
+    out->reach_rounds0 = rounds0;
+  }
+  if (want_comp) {
+    out->components0 = (uint32_t)c[kGhComponents];
+    out->largest_component0 = (uint32_t)c[kGhLargest];
+    out->isolated0 = (uint32_t)c[kGhIsolated];
+  }
+  out->launches = launches;
+  out->reach_launches = reach_launches;
+  out->host_syncs = host_syncs;
+  out->ms = StageEvents::ms(ev.ev[0], ev.ev[1]);
+  // the scratch goes back; the per-node results stay until the next job
+  std::swap(g->d_hreach, bitmap);
+  std::swap(g->d_hlabel, label);
+  drop();
+  g->health_has = (want_reach ? 1u : 0u) | (want_comp ? 2u : 0u);
+  g->health_n = n;
+  g->health_at = g->mutations;
+  return FVDB_OK;
+}
+
+extern "C" int fvdb_graph_health_nodes(fvdb_graph* g, uint8_t* reached, uint32_t* label0) {
+  if (!g) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = g->store->ctx;
+  if (g->health_at != g->mutations || g->health_n != g->n) FAIL(ctx, FVDB_E_INVALID, "graph health: the graph changed since the last job (or none ran)");
+  if ((reached && !(g->health_has & 1u)) || (label0 && !(g->health_has & 2u))) FAIL(ctx, FVDB_E_INVALID, "graph health: the last job skipped that part");
+  const uint32_t n = g->health_n;
+  if (n == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (reached) {
+    std::vector<uint32_t> words(cdiv(n, 32));
+    HIPCHK(ctx, hipMemcpyAsync(words.data(), g->d_hreach.p, words.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < n; ++i) reached[i] = (uint8_t)((words[i >> 5] >> (i & 31)) & 1u);
+  }
+  if (label0) {
+    HIPCHK(ctx, hipMemcpyAsync(label0, g->d_hlabel.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return FVDB_OK;
 }
 

@@ -518,6 +518,36 @@ void fvh_hnsw_set_vacuum_keep_rows(void* p, int on) { ((HNSWIndex*)p)->set_vacuu
 // returns HNSWIndex::VacuumPath of the last vacuum that removed something
 int fvh_hnsw_vacuum_info(void* p, fvdb_graph_maintenance_info_t* out) { return ((HNSWIndex*)p)->vacuum_info(out); }
 uint64_t fvh_hnsw_store_rows(void* p) { return ((HNSWIndex*)p)->store_rows(); }
+// graph stats and health.  out5: total_nodes, total_edges, max_layer, connected_components, and
+// avg_degree's f32 bits in the low half of the fifth word
+int fvh_hnsw_graph_stats(void* p, uint64_t* out5) {
+  HNSWIndex::GraphStats s;
+  const int rc = ((HNSWIndex*)p)->get_graph_stats(&s);
+  uint32_t bits;
+  std::memcpy(&bits, &s.avg_degree, 4);
+  out5[0] = s.total_nodes;
+  out5[1] = s.total_edges;
+  out5[2] = s.max_layer;
+  out5[3] = s.connected_components;
+  out5[4] = bits;
+  return rc;
+}
+uint32_t fvh_hnsw_max_level(void* p) { return ((HNSWIndex*)p)->get_max_level(); }
+void fvh_hnsw_level_distribution(void* p, uint64_t* out) { ((HNSWIndex*)p)->get_level_distribution(out); }
+// *path: HNSWIndex::HealthPath of the form that ran
+int fvh_hnsw_graph_health(void* p, uint32_t flags, fvdb_graph_health_t* out, int* path) {
+  return ((HNSWIndex*)p)->graph_health(out, flags, path);
+}
+// out: room for active_count() ids
+int fvh_hnsw_unreachable(void* p, uint64_t* out, uint64_t cap, uint64_t* n_out) {
+  std::vector<uint64_t> ids;
+  const int rc = ((HNSWIndex*)p)->unreachable(&ids);
+  *n_out = ids.size();
+  if (!rc && ids.size() <= cap && !ids.empty()) std::memcpy(out, ids.data(), ids.size() * 8);
+  return rc ? rc : (ids.size() <= cap ? FVDB_OK : FVDB_E_INVALID);
+}
+// labels: room for node_count() entries, in export_graph's node order
+int fvh_hnsw_component_labels(void* p, uint64_t* labels) { return ((HNSWIndex*)p)->component_labels(labels); }
 // vectors of search hits (includeVectors, bindings/node/src/session.rs:266-281): recent part first, then historical
 int fvh_hybrid_get_vectors(void* p, const uint64_t* ids, uint64_t n, float* out, uint8_t* found) {
   return ((HybridIndex*)p)->get_vectors(ids, n, out, found);

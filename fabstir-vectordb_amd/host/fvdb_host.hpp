@@ -457,6 +457,30 @@ class HNSWIndex {
     *out = vacuum_info_;
     return vacuum_path_;
   }
+  // ---- graph stats and health ----
+  // get_graph_stats (operations.rs:227-272) over the live nodes, its stub component count included ("assume 1
+  // component"); get_max_level / get_level_distribution (core.rs:667-684) over every node the map holds, deleted or not.
+  struct GraphStats {
+    uint64_t total_nodes = 0, total_edges = 0;
+    float avg_degree = 0.0f;
+    uint64_t max_layer = 0, connected_components = 0;
+  };
+  int get_graph_stats(GraphStats* out);
+  uint32_t get_max_level() const;
+  void get_level_distribution(uint64_t* out) const;  // get_max_level() + 1 entries
+  // What the stub does not say (definitions: include/fvdb.h, fvdb_graph_health): which live nodes a search can still
+  // reach, the weak components of the live layer-0 graph, degree and dangling-link figures.  One device job on the
+  // adjacency in HBM (brought up to date first); the same definitions restated on the host over nbrs_ when device
+  // traversal is off, the index is empty or the device cannot hold the graph (a list longer than 64).  flags:
+  // FVDB_HEALTH_SKIP_*.  A node the map no longer holds (a vacuum that kept its rows) is no node for any figure; an entry
+  // point lost to a vacuum leaves R empty.  Returns the job's or the pull's error; *path: which form ran.
+  enum HealthPath : int { HEALTH_NONE = 0, HEALTH_DEVICE = 1, HEALTH_HOST = 2 };
+  int graph_health(fvdb_graph_health_t* out, uint32_t flags = 0, int* path = nullptr);
+  // ids of the live nodes outside R, in node order; runs the reach part
+  int unreachable(std::vector<uint64_t>* ids_out);
+  // per node the map holds, in export_graph's order: the id of the smallest-index node of its layer-0 component
+  // (UINT64_MAX for a deleted node); runs the components part.  Room for node_count() entries.
+  int component_labels(uint64_t* labels_out);
   uint64_t store_rows() const { return store_ ? fvdb_store_rows(store_) : 0; }  // rows the vectors occupy in HBM
   uint64_t store_bytes() const { return store_ ? fvdb_store_bytes(store_) : 0; }  // and their bytes
   int64_t level_of(uint64_t id) const;
@@ -561,6 +585,9 @@ class HNSWIndex {
   fvdb_graph_maintenance_info_t vacuum_info_{};
   uint64_t vacuum_host(const std::vector<uint8_t>& dead, uint64_t removed);  // the host algorithm; the lists are pulled
   void vacuum_adopt(bool reclaimed, const std::vector<uint8_t>& dead);        // bookkeeping after the device job
+  // graph_health and the per-node results behind it: reached[node] (1 = in R), label[node] (0xFFFFFFFF: not live)
+  int health_run(uint32_t flags, fvdb_graph_health_t* out, int* path, std::vector<uint8_t>* reached, std::vector<uint32_t>* label);
+  void health_host(uint32_t flags, fvdb_graph_health_t* out, std::vector<uint8_t>* reached, std::vector<uint32_t>* label) const;
   bool host_link_reported_ = false;  // the stderr line "device insert refused, linking on the host" was written
   fvdb_graph_insert_stats insert_stats_{};
   uint64_t n_host_inserts_ = 0;

@@ -1423,6 +1423,185 @@ void HNSWIndex::export_graph(uint64_t* ids, uint32_t* levels, uint64_t* nbr_offs
   nbr_offsets[slot] = e;
 }
 
+// --------------------------------------------------------------------------------------------
+// graph stats and health (the definitions are stated in include/fvdb.h, fvdb_graph_health)
+// --------------------------------------------------------------------------------------------
+// src/hnsw/core.rs:667-670 and :673-684: every node the map holds, deleted ones included
+uint32_t HNSWIndex::get_max_level() const {
+  uint32_t m = 0;
+  for (size_t i = 0; i < ids_.size(); ++i)
+    if (registered_[i]) m = std::max(m, level_[i]);
+  return m;
+}
+void HNSWIndex::get_level_distribution(uint64_t* out) const {
+  const uint32_t m = get_max_level();
+  std::fill(out, out + m + 1, 0);
+  for (size_t i = 0; i < ids_.size(); ++i)
+    if (registered_[i])
+      for (uint32_t l = 0; l <= level_[i]; ++l) out[l] += 1;
+}
+
+// src/hnsw/operations.rs:227-272 from the census part of the health job
+int HNSWIndex::get_graph_stats(GraphStats* out) {
+  *out = GraphStats{};
+  fvdb_graph_health_t h;
+  int rc = graph_health(&h, FVDB_HEALTH_SKIP_REACH | FVDB_HEALTH_SKIP_COMPONENTS);
+  if (rc) return rc;
+  if (h.n_live == 0) return FVDB_OK;
+  out->total_nodes = h.n_live;
+  out->total_edges = h.edge_slots_live / 2;  // "Since edges are bidirectional, divide by 2"
+  out->avg_degree = (float)(out->total_edges * 2) / (float)out->total_nodes;
+  out->max_layer = h.max_level_live;
+  out->connected_components = 1;  // the reference's stub: "assume 1 component"
+  return FVDB_OK;
+}
+
+// the definitions once more, in plain host code over nbrs_ (pulled by the caller)
+void HNSWIndex::health_host(uint32_t flags, fvdb_graph_health_t* out, std::vector<uint8_t>* reached, std::vector<uint32_t>* label) const {
+  const uint32_t n = (uint32_t)ids_.size();
+  auto live = [&](uint32_t u) { return registered_[u] && !deleted_[u]; };
+  for (uint32_t u = 0; u < n; ++u) {
+    if (!live(u)) continue;
+    out->n_live += 1;
+    out->max_level_live = std::max(out->max_level_live, level_[u]);
+    for (uint32_t l = 0; l <= level_[u]; ++l) {
+      uint64_t dead = 0;
+      for (uint32_t v : nbrs_[u][l]) dead += live(v) ? 0 : 1;
+      out->edge_slots_live += nbrs_[u][l].size();
+      out->dangling += dead;
+      if (l == 0) {
+        out->dangling0 += dead;
+        out->degree0_hist[std::min<size_t>(nbrs_[u][0].size(), 64)] += 1;
+      }
+    }
+  }
+  const bool entry_ok = has_entry_ && !entry_lost_ && entry_ < n;
+  out->has_entry = entry_ok;
+  out->entry_live = entry_ok && live(entry_);
+  out->entry_level = entry_ok ? level_[entry_] : 0;
+  if (!(flags & FVDB_HEALTH_SKIP_REACH)) {
+    std::vector<uint8_t> in(n, 0);
+    std::vector<uint32_t> all, frontier, next;
+    if (entry_ok) {
+      in[entry_] = 1;
+      all.push_back(entry_);
+      for (uint32_t l = level_[entry_] + 1; l-- > 0;) {
+        frontier = all;  // what the layer above left seeds this one
+        while (!frontier.empty()) {
+          if (l == 0) out->reach_rounds0 += 1;
+          next.clear();
+          for (uint32_t u : frontier) {
+            if (level_[u] < l || !(live(u) || u == entry_)) continue;
+            for (uint32_t v : nbrs_[u][l])
+              if (live(v) && !in[v]) {
+                in[v] = 1;
+                next.push_back(v);
+              }
+          }
+          all.insert(all.end(), next.begin(), next.end());
+          frontier.swap(next);
+        }
+      }
+    }
+    for (uint32_t u : all) out->reachable_live += live(u) ? 1 : 0;
+    out->unreachable_live = out->n_live - out->reachable_live;
+    if (reached) reached->swap(in);
+  }
+  if (!(flags & FVDB_HEALTH_SKIP_COMPONENTS)) {
+    std::vector<uint32_t> parent(n), size(n, 0);
+    for (uint32_t u = 0; u < n; ++u) parent[u] = u;
+    auto find = [&](uint32_t x) {
+      while (parent[x] != x) x = parent[x] = parent[parent[x]];
+      return x;
+    };
+    for (uint32_t u = 0; u < n; ++u) {
+      if (!live(u)) continue;
+      for (uint32_t v : nbrs_[u][0]) {
+        if (!live(v)) continue;
+        const uint32_t a = find(u), b = find(v);
+        if (a != b) parent[std::max(a, b)] = std::min(a, b);  // a root is the smallest index of its tree
+      }
+    }
+    std::vector<uint32_t> lab(n, 0xFFFFFFFFu);
+    for (uint32_t u = 0; u < n; ++u)
+      if (live(u)) size[lab[u] = find(u)] += 1;
+    for (uint32_t u = 0; u < n; ++u)
+      if (lab[u] == u) {
+        out->components0 += 1;
+        out->isolated0 += size[u] == 1 ? 1 : 0;
+        out->largest_component0 = std::max(out->largest_component0, size[u]);
+      }
+    if (label) label->swap(lab);
+  }
+}
+
+int HNSWIndex::health_run(uint32_t flags, fvdb_graph_health_t* out, int* path, std::vector<uint8_t>* reached, std::vector<uint32_t>* label) {
+  std::memset(out, 0, sizeof *out);
+  if (path) *path = HEALTH_NONE;
+  if (flags & ~(FVDB_HEALTH_SKIP_REACH | FVDB_HEALTH_SKIP_COMPONENTS)) return FVDB_E_INVALID;
+  const uint32_t n = (uint32_t)ids_.size();
+  const bool want_reach = !(flags & FVDB_HEALTH_SKIP_REACH), want_comp = !(flags & FVDB_HEALTH_SKIP_COMPONENTS);
+  bool device = device_traversal_ && n > 0;
+  int rc;
+  if (device) {
+    rc = sync_graph();  // uploads when host_ahead_
+    if (rc == FVDB_E_UNSUPPORTED) device = false;
+    else if (rc) return rc;
+  }
+  if (device) {
+    // an entry point lost to a vacuum still has its (emptied, deleted) node on the device: no search starts there
+    const uint32_t dev_flags = flags | (entry_lost_ ? FVDB_HEALTH_SKIP_REACH : 0u);
+    if ((rc = fvdb_graph_health(graph_, dev_flags, out))) return rc;
+    if (entry_lost_) {
+      out->has_entry = out->entry_live = out->entry_level = 0;
+      if (want_reach) out->unreachable_live = out->n_live;
+    }
+    if (reached && want_reach) {
+      reached->assign(n, 0);
+      if (!entry_lost_ && (rc = fvdb_graph_health_nodes(graph_, reached->data(), nullptr))) return rc;
+    }
+    if (label && want_comp) {
+      label->assign(n, 0xFFFFFFFFu);
+      if ((rc = fvdb_graph_health_nodes(graph_, nullptr, label->data()))) return rc;
+    }
+    if (path) *path = HEALTH_DEVICE;
+  } else {
+    if ((rc = ensure_host_graph())) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    health_host(flags, out, reached, label);
+    out->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();  // wall clock: no device job ran
+    if (path) *path = HEALTH_HOST;
+  }
+  out->n_nodes = (uint32_t)n_registered_;
+  return FVDB_OK;
+}
+
+int HNSWIndex::graph_health(fvdb_graph_health_t* out, uint32_t flags, int* path) { return health_run(flags, out, path, nullptr, nullptr); }
+
+int HNSWIndex::unreachable(std::vector<uint64_t>* ids_out) {
+  ids_out->clear();
+  fvdb_graph_health_t h;
+  std::vector<uint8_t> reached;
+  int rc = health_run(FVDB_HEALTH_SKIP_COMPONENTS, &h, nullptr, &reached, nullptr);
+  if (rc) return rc;
+  for (size_t u = 0; u < ids_.size(); ++u)
+    if (registered_[u] && !deleted_[u] && !reached[u]) ids_out->push_back(ids_[u]);
+  return FVDB_OK;
+}
+
+int HNSWIndex::component_labels(uint64_t* labels_out) {
+  fvdb_graph_health_t h;
+  std::vector<uint32_t> label;
+  int rc = health_run(FVDB_HEALTH_SKIP_REACH, &h, nullptr, nullptr, &label);
+  if (rc) return rc;
+  uint64_t w = 0;
+  for (size_t u = 0; u < ids_.size(); ++u) {
+    if (!registered_[u]) continue;
+    labels_out[w++] = label[u] < ids_.size() ? ids_[label[u]] : UINT64_MAX;
+  }
+  return FVDB_OK;
+}
+
 int HNSWIndex::bulk_build(const uint64_t* ids, const float* v, uint64_t n, uint32_t dim, const int64_t* levels) {
   if (!ids_.empty()) return FVDB_E_INVALID;
   if (n == 0) return FVDB_OK;

@@ -169,6 +169,13 @@ HOST_SIGNATURES = {
     "fvh_hnsw_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
     "fvh_hybrid_search_allowed_groups": (i32, [vp, f32p, u32, u32, u64, u64, u64, i32, i32, u64p, u64p, u8p, u32, u32p, dbl, u64p,
                                                f32p, u32p]),
+    # graph stats and health
+    "fvh_hnsw_graph_stats": (i32, [vp, u64p]),
+    "fvh_hnsw_max_level": (u32, [vp]),
+    "fvh_hnsw_level_distribution": (None, [vp, u64p]),
+    "fvh_hnsw_graph_health": (i32, [vp, u32, C.POINTER(_capi.GraphHealth), C.POINTER(C.c_int)]),
+    "fvh_hnsw_unreachable": (i32, [vp, u64p, u64, u64p]),
+    "fvh_hnsw_component_labels": (i32, [vp, u64p]),
 }
 
 _ROW_DTYPE_NAMES = ("f32", "f16")
@@ -742,6 +749,56 @@ class HNSWIndex(_Base):
         out = {name: getattr(m, name) for name, _ in m._fields_}
         out["path"] = (None, "resident", "resident_keep_rows", "host")[path]
         return out
+
+    def get_graph_stats(self):
+        """The reference's GraphStats over the live nodes (src/hnsw/operations.rs:227-272), "connected_components" being
+        its stub: 1 whenever a node is live.  graph_health() has the real figures."""
+        out = np.zeros(5, np.uint64)
+        self._check(self.lib.fvh_hnsw_graph_stats(self.h, _ptr(out, u64p)))
+        return {"total_nodes": int(out[0]), "total_edges": int(out[1]),
+                "avg_degree": float(np.array([out[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+                "max_layer": int(out[2]), "connected_components": int(out[3])}
+
+    def get_max_level(self):
+        """The highest level among the nodes the index holds, deleted ones included (src/hnsw/core.rs:667-670)."""
+        return int(self.lib.fvh_hnsw_max_level(self.h))
+
+    def get_level_distribution(self):
+        """Nodes present on each layer, deleted ones included: get_max_level() + 1 entries (src/hnsw/core.rs:673-684)."""
+        out = np.zeros(self.get_max_level() + 1, np.uint64)
+        self.lib.fvh_hnsw_level_distribution(self.h, _ptr(out, u64p))
+        return [int(x) for x in out]
+
+    def graph_health(self, reach=True, components=True):
+        """What deletes and vacuums have done to the graph, computed exactly by one read-only device job on the adjacency in
+        HBM (fvdb_graph_health_t, include/fvdb.h): reachable_live / unreachable_live (live nodes any search can / no search
+        can admit, whatever the query, ef and k), the weak components of the live layer-0 graph, dangling links and the
+        layer-0 degree histogram.  "path": "device", or "host" where the mirror restated the same definitions itself
+        (device traversal off, an empty index, a graph the device cannot hold).  A part switched off reads as zeros."""
+        m, path = _capi.GraphHealth(), C.c_int(0)
+        flags = (0 if reach else _capi.HEALTH_SKIP_REACH) | (0 if components else _capi.HEALTH_SKIP_COMPONENTS)
+        self._check(self.lib.fvh_hnsw_graph_health(self.h, flags, C.byref(m), C.byref(path)))
+        out = {name: getattr(m, name) for name, _ in m._fields_}
+        out["degree0_hist"] = [int(x) for x in m.degree0_hist]
+        out["path"] = (None, "device", "host")[path.value]
+        return out
+
+    def unreachable_ids(self):
+        """Ids of the live nodes no search can return, in node order."""
+        buf = np.empty(max(self.active_count(), 1), np.uint64)
+        n = C.c_uint64(0)
+        self._check(self.lib.fvh_hnsw_unreachable(self.h, _ptr(buf, u64p), buf.size, C.byref(n)))
+        return buf[:n.value].copy()
+
+    def component_labels(self):
+        """(ids, labels) in export_graph()'s node order: labels[i] is the id of the smallest-index node of the layer-0
+        component ids[i] lies in, 2**64 - 1 for a deleted node."""
+        n = self.node_count()
+        if n == 0:
+            return np.empty(0, np.uint64), np.empty(0, np.uint64)
+        labels = np.empty(n, np.uint64)
+        self._check(self.lib.fvh_hnsw_component_labels(self.h, _ptr(labels, u64p)))
+        return self.export_graph()[0], labels
 
     def store_rows(self):
         """Rows the index's vectors occupy in HBM (equals node_count() after a resident vacuum)."""

@@ -464,6 +464,12 @@ class VectorDbSession:
                 "hnsw_deleted_count": hnsw_deleted, "ivf_deleted_count": ivf_deleted,
                 "total_deleted_count": hnsw_deleted + ivf_deleted}
 
+    def graph_health(self, reach=True, components=True):
+        """HNSWIndex.graph_health of the recent part (no counterpart in the reference's session)."""
+        if self.destroyed:
+            raise SessionError("Session already destroyed")
+        return self.index.hnsw().graph_health(reach=reach, components=components)
+
     def destroy(self):
         self.destroyed = True
         self.index = None

@@ -575,6 +575,47 @@ int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* removed);
 /* Figures of the last fvdb_graph_vacuum on this graph (zeros before the first). */
 int fvdb_graph_maintenance_info(fvdb_graph* g, fvdb_graph_maintenance_info_t* out);
 
+/* ---- device-resident graph health ---------------------------------------------------------------
+ * A read-only job over the adjacency in HBM, everything in integers.  live(u): the deleted flag of u is clear.  N_l(u):
+ * the stored list of u on layer l as stored (entries naming deleted nodes stay in it until a vacuum).
+ *   census   n_live; edge_slots_live = the list lengths of live nodes over all their layers and max_level_live — the
+ *            inputs of the reference's get_graph_stats (src/hnsw/operations.rs:227-272: total_edges = slots / 2,
+ *            avg_degree, max_layer; its connected_components is a stub that answers 1); dangling / dangling0 = entries of
+ *            live nodes' lists that name deleted nodes (all layers / layer 0: what fvdb_graph_vacuum would prune);
+ *            degree0_hist[b] = live nodes with |N_0(u)| = b, the last bin "64 or more".
+ *   reach    R = the nodes some search can admit, for every query, ef and k (src/hnsw/core.rs:398-554: a deleted
+ *            neighbour is marked visited and never expanded, :510-513; the entry point is seeded and expanded whether it
+ *            is deleted or not).  R = {entry} at l = level(entry); for l down to 0, R is closed under "u in R, live or
+ *            the entry, level(u) >= l: every live v in N_l(u) joins"; what a layer leaves seeds the next.  reachable_live
+ *            = |R and live|, unreachable_live = n_live - reachable_live, reach_rounds0 = the steps of layer 0's closure
+ *            (a step expands what the step before added, the first one all of R; the last one adds nothing).  No entry
+ *            point: R is empty.
+ *   components  weak components of layer 0 among live nodes (u ~ v when v in N_0(u), both live, direction ignored):
+ *            components0, largest_component0, isolated0 (components of one node).  The label of a live node is the
+ *            smallest node index of its component, that of a deleted node 0xFFFFFFFF.
+ * flags = 0 computes everything; a skipped part leaves its fields zero and its per-node result unavailable.  The job
+ * runs on the context's stream, allocates its scratch (about 17 bytes a node) before the first launch — FVDB_E_OOM
+ * leaves everything as it was — and gives it back, except the per-node results.  It changes nothing a search, an insert,
+ * a mask or a vacuum can see; searches may run beside it, the caller excludes inserts, deletes and vacuums for the
+ * duration.  n = 0: FVDB_OK and zeros; a graph that holds no device arrays yet: FVDB_E_INVALID;
+ * 2^31 nodes or more: FVDB_E_UNSUPPORTED.  Between launches the host reads 16 bytes of state. */
+#define FVDB_HEALTH_SKIP_REACH 1u
+#define FVDB_HEALTH_SKIP_COMPONENTS 2u
+typedef struct fvdb_graph_health_t {
+  uint32_t n_nodes, n_live, has_entry, entry_live, entry_level, max_level_live;
+  uint64_t edge_slots_live, dangling, dangling0;
+  uint32_t degree0_hist[65];
+  uint32_t reachable_live, unreachable_live, reach_rounds0;
+  uint32_t components0, largest_component0, isolated0;
+  uint32_t launches, reach_launches, host_syncs;   /* how the job ran: kernel launches (of them: reach steps), stream waits */
+  float    ms;                                     /* HIP events around the job */
+  uint64_t scratch_bytes;
+} fvdb_graph_health_t;
+int fvdb_graph_health(fvdb_graph* g, uint32_t flags, fvdb_graph_health_t* out);
+/* Per-node results of the last fvdb_graph_health: reached[n] (1 = in R), label0[n].  FVDB_E_INVALID if the graph changed
+ * since (or the job skipped what is asked for).  Either pointer may be NULL. */
+int fvdb_graph_health_nodes(fvdb_graph* g, uint8_t* reached, uint32_t* label0);
+
 /* With profiling on (fvdb_ctx_set_profiling): summed duration (HIP events on the launch stream) of the last
  * <= 64 launches of the traversal kernel since the previous call, and how many were summed; and (always) the
  * rows scored and hops taken by all queries since the previous call (either may be NULL).  Synchronises. */
