@@ -7,16 +7,9 @@
 
 namespace {
 
-// a device buffer of this call only
-struct Temp {
-  void* p = nullptr;
-  ~Temp() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-int upload_temp(fvdb_ctx* ctx, Temp& t, const void* host, size_t bytes) {
-  HIPCHK(ctx, hipMalloc(&t.p, std::max<size_t>(bytes, 8)));
+// a device buffer of this call only, filled from the host
+int upload_temp(fvdb_ctx* ctx, DBuf& t, const void* host, size_t bytes) {
+  HIPCHK(ctx, t.exact(std::max<size_t>(bytes, 8)));
   if (bytes) HIPCHK(ctx, hipMemcpyAsync(t.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   return FVDB_OK;
 }
@@ -41,11 +34,11 @@ int build_ivf_mask(fvdb_mask* m, const IvfMaskSource& src, const uint64_t* ids, 
   uint64_t slots = 1024;
   while (slots < 2 * n) slots <<= 1;
   if (slots > (1ull << 31)) FAIL(ctx, FVDB_E_UNSUPPORTED, "allow-set of more than 2^30 ids");
-  Temp d_ids, d_table, d_count;
+  DBuf d_ids, d_table, d_count;
   int rc = upload_temp(ctx, d_ids, ids, (size_t)n * 8);
   if (rc) return rc;
-  HIPCHK(ctx, hipMalloc(&d_table.p, (size_t)slots * 8));
-  HIPCHK(ctx, hipMalloc(&d_count.p, 8));
+  HIPCHK(ctx, d_table.exact((size_t)slots * 8));
+  HIPCHK(ctx, d_count.exact(8));
   HIPCHK(ctx, hipMemsetAsync(d_table.p, 0xFF, (size_t)slots * 8, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
   hipLaunchKernelGGL(allow_set_build_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)d_ids.p, n,
@@ -69,11 +62,11 @@ int build_graph_mask(fvdb_mask* m, const GraphMaskSource& src, const uint32_t* n
   HIPCHK(ctx, m->nodes.ensure(std::max<size_t>((size_t)std::min<uint64_t>(n, n_in) * 4, 4)));
   if (n == 0) return FVDB_OK;
   const uint32_t n_wg = cdiv(n, 256);
-  Temp d_in, d_wg, d_total;
+  DBuf d_in, d_wg, d_total;
   int rc = upload_temp(ctx, d_in, nodes, (size_t)n_in * 4);
   if (rc) return rc;
-  HIPCHK(ctx, hipMalloc(&d_wg.p, (size_t)n_wg * 4));
-  HIPCHK(ctx, hipMalloc(&d_total.p, 8));
+  HIPCHK(ctx, d_wg.exact((size_t)n_wg * 4));
+  HIPCHK(ctx, d_total.exact(8));
   HIPCHK(ctx, hipMemsetAsync(m->flags.p, 0x01, (size_t)n * 4, ctx->stream));  // every word non-zero: not allowed
   if (n_in)
     hipLaunchKernelGGL(allow_graph_mark_kernel, dim3(cdiv(n_in, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_in.p, n_in, n,
@@ -116,7 +109,7 @@ extern "C" {
 int fvdb_mask_create_ivf(fvdb_ivf* ivf, const uint64_t* ids, uint64_t n, fvdb_mask** out) {
   if (!ivf || !out) return FVDB_E_INVALID;
   *out = nullptr;
-  const IvfMaskSource src{ivf->ctx, ivf->pool.ids, ivf->pool.valid, ivf->pool.used_blocks};
+  const IvfMaskSource src{ivf->ctx, ivf->pool.ids(), ivf->pool.valid(), ivf->pool.used_blocks};
   int rc;
   if (n && !ids) FAIL(src.ctx, FVDB_E_INVALID, "allow-set: null ids");
   HIPCHK(src.ctx, hipSetDevice(src.ctx->device));
@@ -178,9 +171,6 @@ void fvdb_mask_destroy(fvdb_mask* m) {
   if (!m) return;
   (void)hipSetDevice(m->ctx->device);
   (void)hipDeviceSynchronize();  // searches in any slot may still be reading it
-  m->words.release();
-  m->flags.release();
-  m->nodes.release();
   delete m;
 }
 

@@ -85,7 +85,7 @@ struct fvdb_comm {
   static constexpr bool loopback = false;
 #endif
   std::mutex mu;                    // one collective at a time per communicator, same order on every rank
-  hipEvent_t last = nullptr;        // end of the previous collective of this communicator, on whichever stream it ran
+  DevEvent last;                   // end of the previous collective of this communicator, on whichever stream it ran
   bool have_last = false;
   HBuf h_send, h_recv;
 };
@@ -111,7 +111,7 @@ int comm_exchange(fvdb_comm* c, fvdb_ctx* on, int op, const Xfer* x, int n) {
   if (c->nccl) {
     // steps of different slots run on different streams; the collectives of ONE communicator must not overlap on the
     // device either, so each waits (on the device, not on the host) for the previous one to finish
-    if (!c->last) HIPCHK(on, hipEventCreateWithFlags(&c->last, hipEventDisableTiming));
+    HIPCHK(on, c->last.create(hipEventDisableTiming));
     if (c->have_last) HIPCHK(on, hipStreamWaitEvent(on->stream, c->last, 0));
     RCCLCHK(on, g_rccl.GroupStart());
     for (int i = 0; i < n; ++i) {
@@ -238,9 +238,6 @@ void fvdb_comm_destroy(fvdb_comm* c) {
   if (!c) return;
   (void)hipSetDevice(c->ctx->device);
   if (c->nccl) (void)g_rccl.CommDestroy(c->nccl);
-  if (c->last) (void)hipEventDestroy(c->last);
-  c->h_send.release();
-  c->h_recv.release();
   delete c;
 }
 int fvdb_comm_rank(fvdb_comm* c) { return c ? c->rank : -1; }
@@ -279,10 +276,6 @@ void fvdb_sharded_destroy(fvdb_sharded* s) {
   if (!s) return;
   (void)hipSetDevice(s->ivf->ctx->device);
   (void)hipDeviceSynchronize();
-  for (auto& sl : s->slot)
-    for (DBuf* b : {&sl.probes, &sl.q_all, &sl.probes_all, &sl.keys, &sl.ids, &sl.dist, &sl.cnt, &sl.gk, &sl.gi, &sl.u_own, &sl.u_all,
-                    &sl.thr})
-      b->release();
   delete s;
 }
 

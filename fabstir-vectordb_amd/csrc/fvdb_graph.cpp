@@ -64,7 +64,7 @@ struct fvdb_graph {
   uint64_t mutations = 0;
   DBuf s_scan[kSlots];  // exact scan under a mask (allow_masks.h): padded queries and partial lists, one per slot
   // profiling: HIP events around the last launches of the traversal kernel (ring of 64)
-  hipEvent_t kev[64][2] = {};
+  DevEvent kev[64][2];
   uint32_t kev_n = 0;   // launches recorded since the last fvdb_graph_kernel_times call
   std::mutex mu;        // launch bookkeeping: searches in different slots may come from different host threads
 };
@@ -95,14 +95,7 @@ __global__ __launch_bounds__(256) void graph_patch_kernel(const uint32_t* __rest
 // grow a device array to `new_bytes`, keeping the first `keep_bytes` and zeroing the rest
 int grow_keep(fvdb_ctx* ctx, DBuf& b, size_t keep_bytes, size_t new_bytes) {
   if (new_bytes <= b.cap) return FVDB_OK;
-  void* np = nullptr;
-  HIPCHK(ctx, hipMalloc(&np, new_bytes));
-  if (keep_bytes) HIPCHK(ctx, hipMemcpyAsync(np, b.p, keep_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync((char*)np + keep_bytes, 0, new_bytes - keep_bytes, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (b.p) (void)hipFree(b.p);
-  b.p = np;
-  b.cap = new_bytes;
+  HIPCHK(ctx, grow_keeping(b, new_bytes, keep_bytes, /*zero_rest=*/true, ctx->stream));
   return FVDB_OK;
 }
 
@@ -633,21 +626,8 @@ int fvdb_graph_create(fvdb_store* s, fvdb_graph** out) {
 
 void fvdb_graph_destroy(fvdb_graph* g) {
   if (!g) return;
-  for (auto& e : g->kev)
-    for (auto& x : e)
-      if (x) (void)hipEventDestroy(x);
   (void)hipSetDevice(g->store->ctx->device);
   (void)hipStreamSynchronize(g->store->ctx->stream);
-  DBuf* bufs[] = {&g->d_level, &g->d_deleted, &g->d_ubase, &g->d_adj0, &g->d_adjU, &g->d_dist0, &g->d_distU, &g->d_stamp0,
-                  &g->d_stampU, &g->d_state, &g->d_spec, &g->d_elog, &g->d_chg, &g->s_patch, &g->s_codes, &g->s_q, &g->d_counters, &g->d_stamps, &g->d_build_stamps,
-                  &g->d_hreach, &g->d_hlabel};
-  for (auto& b : g->s_visited) b.release();
-  for (auto& b : g->s_touched) b.release();
-  for (auto& b : g->s_spill) b.release();
-  for (auto& b : g->s_scan) b.release();
-  for (DBuf* b : bufs) b->release();
-  g->h_state.release();
-  g->h_patch.release();
   delete g;
 }
 
@@ -1054,13 +1034,11 @@ static int graph_search_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, const f
   const GraphView gv{s->data, g->d_level.as<uint32_t>(), deleted, g->d_adj0.as<uint32_t>(), g->d_ubase.as<uint32_t>(),
                      g->d_adjU.as<uint32_t>(), g->stride0, g->strideU, g->n, s->dpad, g->entry, g->top_level, any_deleted,
                      g->d_counters.as<unsigned long long>(), graph_stamps_report(g)};
-  hipEvent_t* ev = nullptr;
+  DevEvent* ev = nullptr;
   if (s->ctx->profiling) {  // the store's context carries the switch, whichever stream the launch goes to
     ev = g->kev[g->kev_n & 63];
-    if (!ev[0]) {
-      (void)hipEventCreate(&ev[0]);
-      (void)hipEventCreate(&ev[1]);
-    }
+    (void)ev[0].create();
+    (void)ev[1].create();
     (void)hipEventRecord(ev[0], ctx->stream);
   }
   if (sp.fast)
@@ -1123,7 +1101,7 @@ int fvdb_graph_kernel_times(fvdb_graph* g, float* ms_sum, uint32_t* launches, ui
   if (hops) *hops = c[1];
   const uint32_t n = std::min<uint32_t>(g->kev_n, 64);
   for (uint32_t i = 0; i < n; ++i) {
-    hipEvent_t* ev = g->kev[(g->kev_n - 1 - i) & 63];
+    const DevEvent* ev = g->kev[(g->kev_n - 1 - i) & 63];
     float ms = 0;
     if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
       *ms_sum += ms;
@@ -1141,39 +1119,193 @@ int fvdb_graph_kernel_times(fvdb_graph* g, float* ms_sum, uint32_t* launches, ui
 // =============================================================================================
 namespace {
 
-// the fresh arrays of a reclaiming vacuum: all allocated before the first change, freed again if one cannot be had
+uint32_t prune_grid(const fvdb_ctx* ctx, uint32_t rows) { return std::max(1u, std::min<uint32_t>(cdiv(rows, 4), (uint32_t)ctx->num_cus * 8u)); }
+
+// the fresh arrays of a reclaiming vacuum: all allocated before the first change, gone again if one cannot be had
 struct FreshGraph {
   DBuf level, deleted, ubase, adj0, adjU, dist0, distU, stamp0, stampU, rows;
-  DBuf* all[10] = {&level, &deleted, &ubase, &adj0, &adjU, &dist0, &distU, &stamp0, &stampU, &rows};
-  void release() {
-    for (DBuf* b : all) b->release();
-  }
-  // exactly `bytes` (DBuf::ensure adds slack of its own; the capacities here already carry the growth slack)
-  static hipError_t exact(DBuf& b, size_t bytes) {
-    const hipError_t e = hipMalloc(&b.p, std::max<size_t>(bytes, 256));
-    if (e == hipSuccess) b.cap = std::max<size_t>(bytes, 256);
-    return e;
-  }
 };
 
-struct StageEvents {
-  hipEvent_t ev[6] = {};
-  bool make() {
-    for (auto& e : ev)
-      if (hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-  }
-  ~StageEvents() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  static float ms(hipEvent_t a, hipEvent_t b) {
-    float v = 0.0f;
-    return hipEventElapsedTime(&v, a, b) == hipSuccess ? v : 0.0f;
-  }
+struct VacuumJob {
+  fvdb_graph* g;
+  fvdb_store* s;
+  fvdb_ctx* ctx;
+  hipStream_t st;
+  bool keep_rows;
+  uint32_t n, u_rows, n_wg;
+  uint32_t n_out, u_out;  // the survivors by the host's copy of the flags, and their upper rows
+  uint32_t n_cap, u_cap;
+  StageTimer<6> ev;
+  // scratch: [new_index n | src_node n | u_src or owner u_rows | wg_nodes n_wg | wg_urows n_wg | totals 2] words, counters
+  DBuf scratch, counters;
+  uint32_t *new_index = nullptr, *src_node = nullptr, *u_aux = nullptr, *wg_nodes = nullptr, *wg_urows = nullptr, *totals = nullptr;
+  FreshGraph f;
+  GmPrune p0{}, pU{};
+  uint64_t host_bytes = 0;
+  unsigned long long h_cnt[4] = {0, 0, 0, 0};
+  unsigned long long* cnt() const { return (unsigned long long*)counters.p; }
+  int alloc_scratch(), scan_in_place(), alloc_fresh(), scan_reclaim(), prune_move(), adopt();  // the stages, in this order
 };
 
-uint32_t prune_grid(const fvdb_ctx* ctx, uint32_t rows) { return std::max(1u, std::min<uint32_t>(cdiv(rows, 4), (uint32_t)ctx->num_cus * 8u)); }
+int VacuumJob::alloc_scratch() {
+  HIPCHK(ctx, ev.create());
+  HIPCHK(ctx, scratch.ensure(((size_t)2 * n + u_rows + 2 * (size_t)n_wg + 2) * 4));
+  HIPCHK(ctx, counters.ensure(32));
+  new_index = scratch.as<uint32_t>();
+  src_node = new_index + n;
+  u_aux = src_node + n;
+  wg_nodes = u_aux + u_rows;
+  wg_urows = wg_nodes + n_wg;
+  totals = wg_urows + n_wg;
+  HIPCHK(ctx, hipMemsetAsync(counters.p, 0, 32, st));
+  return FVDB_OK;
+}
+
+// keep_rows: nothing moves, the lists are pruned in place
+int VacuumJob::scan_in_place() {
+  const uint32_t* d_deleted = g->d_deleted.as<uint32_t>();
+  n_out = n;
+  u_out = u_rows;
+  HIPCHK(ctx, ev.mark(0, st));
+  if (u_rows)
+    hipLaunchKernelGGL(gm_owner_kernel, dim3(n_wg), dim3(256), 0, st, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, u_rows, u_aux);
+  HIPCHK(ctx, ev.mark(1, st));
+  HIPCHK(ctx, ev.mark(2, st));
+  p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->stride0, n, n,
+               nullptr, nullptr, 1u, d_deleted, n, nullptr, nullptr, nullptr, cnt()};
+  pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->strideU, u_rows, u_rows,
+               nullptr, u_aux, 1u, d_deleted, n, nullptr, nullptr, nullptr, cnt()};
+  return FVDB_OK;
+}
+
+// the fresh arrays, exactly sized (the capacities carry the growth slack already); every allocation precedes the first change
+int VacuumJob::alloc_fresh() {
+  n_cap = n_out + n_out / 8 + 1024;
+  u_cap = u_out + u_out / 8 + 1024;
+  const size_t nc = n_cap, uc = u_cap;
+  const struct {
+    DBuf* b;
+    size_t bytes;
+  } want[10] = {{&f.level, nc * 4},  {&f.deleted, nc * 4}, {&f.ubase, nc * 4},
+                {&f.adj0, nc * g->stride0 * 4}, {&f.adjU, uc * g->strideU * 4},
+                {&f.dist0, nc * g->stride0 * 4}, {&f.distU, uc * g->strideU * 4},
+                {&f.stamp0, nc * 4}, {&f.stampU, uc * 4},
+                {&f.rows, nc * s->row_bytes()}};
+  for (const auto& w : want) {
+    const hipError_t e = w.b->exact(std::max<size_t>(w.bytes, 256));
+    if (e != hipSuccess)
+      FAIL(ctx, e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, "graph vacuum: no memory for the compacted copy (graph unchanged)");
+  }
+  for (int b = 0; b < 9; ++b) HIPCHK(ctx, hipMemsetAsync(want[b].b->p, 0, want[b].b->cap, st));  // (the store's rows are written whole)
+  return FVDB_OK;
+}
+
+// reclaiming: the survivors are counted and mapped to their new indices, the lists pruned into the fresh arrays
+int VacuumJob::scan_reclaim() {
+  const uint32_t* d_deleted = g->d_deleted.as<uint32_t>();
+  // stage 1a: survivors and their upper rows, counted on the device and checked against the host's copy of the flags
+  HIPCHK(ctx, ev.mark(0, st));
+  hipLaunchKernelGGL(gm_count_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), n, wg_nodes, wg_urows);
+  hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_nodes, n_wg, totals);
+  hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_urows, n_wg, totals + 1);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, ev.mark(1, st));
+  uint32_t h_tot[2] = {0, 0};
+  HIPCHK(ctx, hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  host_bytes += 8;
+  if (h_tot[0] != n_out || h_tot[1] != u_out) FAIL(ctx, FVDB_E_HIP, "graph vacuum: the device's deleted flags differ from the host's copy");
+  int rc = alloc_fresh();
+  if (rc) return rc;
+  // stage 1b: the maps, and level / upper-row base of every survivor at its new index
+  HIPCHK(ctx, ev.mark(2, st));
+  hipLaunchKernelGGL(gm_map_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, wg_nodes,
+                     wg_urows, n_out, u_out, new_index, src_node, u_aux, f.level.as<uint32_t>(), f.ubase.as<uint32_t>());
+  HIPCHK(ctx, hipGetLastError());
+  p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), f.adj0.as<uint32_t>(), f.dist0.as<float>(), g->stride0, n_out, n,
+               src_node, nullptr, 0u, d_deleted, n, new_index, g->d_stamp0.as<uint32_t>(), f.stamp0.as<uint32_t>(), cnt()};
+  pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), f.adjU.as<uint32_t>(), f.distU.as<float>(), g->strideU, u_out, u_rows,
+               u_aux, nullptr, 0u, d_deleted, n, new_index, g->d_stampU.as<uint32_t>(), f.stampU.as<uint32_t>(), cnt()};
+  return FVDB_OK;
+}
+
+int VacuumJob::prune_move() {
+  // stage 2: prune + remap, one wave per destination row
+  HIPCHK(ctx, ev.mark(3, st));
+  hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, g->d_adj0.as<uint32_t>(), g->stride0, n, cnt());
+  if (u_rows)
+    hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, u_rows)), dim3(256), 0, st, g->d_adjU.as<uint32_t>(), g->strideU, u_rows,
+                       cnt());
+  if (p0.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, p0.rows)), dim3(256), 0, st, p0);
+  if (pU.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, pU.rows)), dim3(256), 0, st, pU);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, ev.mark(4, st));
+  // stage 3: store rows, one wave per destination row
+  if (!keep_rows && n_out) {
+    if (s->f16())  // a half row is dpad * 2 bytes: whole 8-byte chunks
+      hipLaunchKernelGGL(gm_move_kernel<float2>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float2*)s->data, n, s->dpad / 4, n_out, (float2*)f.rows.p);
+    else
+      hipLaunchKernelGGL(gm_move_kernel<float4>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float4*)s->data, n, s->dpad / 4, n_out, (float4*)f.rows.p);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, ev.mark(5, st));
+  HIPCHK(ctx, hipMemcpyAsync(h_cnt, counters.p, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  host_bytes += 32;
+  return FVDB_OK;
+}
+
+// the graph and the store take the compacted arrays; the host's bookkeeping follows them
+int VacuumJob::adopt() {
+  std::swap(g->d_level, f.level);
+  std::swap(g->d_deleted, f.deleted);
+  std::swap(g->d_ubase, f.ubase);
+  std::swap(g->d_adj0, f.adj0);
+  std::swap(g->d_adjU, f.adjU);
+  std::swap(g->d_dist0, f.dist0);
+  std::swap(g->d_distU, f.distU);
+  std::swap(g->d_stamp0, f.stamp0);
+  std::swap(g->d_stampU, f.stampU);
+  // the store adopts the compacted rows: scorers read store->data at every launch
+  std::swap(s->rows_buf, f.rows);
+  s->data = s->rows_buf.p;
+  s->cap = n_cap;
+  s->rows = n_out;
+  f = FreshGraph{};  // the old arrays go now, not when the job returns: the host bookkeeping below allocates
+  std::vector<uint32_t> lv(n_out), ub(n_out);
+  uint32_t w = 0, u = 0, entry = 0;
+  bool entry_alive = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (g->h_deleted[i]) continue;
+    if (g->has_entry && i == g->entry) {
+      entry = w;
+      entry_alive = true;
+    }
+    lv[w] = g->h_level[i];
+    ub[w] = u;
+    u += lv[w];
+    w += 1;
+  }
+  g->h_level.swap(lv);
+  g->h_ubase.swap(ub);
+  g->h_deleted.assign(n_out, 0);
+  g->n_deleted = 0;
+  g->n = n_out;
+  g->n_cap = n_cap;
+  g->u_rows = u_out;
+  g->u_cap = u_cap;
+  g->has_entry = entry_alive;
+  g->entry = entry_alive ? entry : 0;
+  g->top_level = entry_alive ? g->h_level[entry] : 0;
+  for (auto& v : g->vis_B) v = 0;  // visited maps are sized by the node count
+  BuildState bs{};
+  bs.has_entry = entry_alive ? 1u : 0u;
+  bs.entry = g->entry;
+  bs.entry_level = g->top_level;
+  bs.n_linked = n_out;
+  host_bytes += sizeof(BuildState);
+  return push_state(g, bs);
+}
 
 }  // namespace
 
@@ -1203,190 +1335,33 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
     g->m_info = info;
     return FVDB_OK;
   }
-  StageEvents ev;
-  if (!ev.make()) FAIL(ctx, FVDB_E_HIP, "graph vacuum: no events");
-  hipStream_t st = ctx->stream;
-  const uint32_t n_wg = cdiv(n, 256);
-  const uint32_t* d_deleted = g->d_deleted.as<uint32_t>();
-  // scratch: [new_index n | src_node n | u_src or owner u_rows | wg_nodes n_wg | wg_urows n_wg | totals 2] words, counters
-  DBuf scratch, counters;
-  HIPCHK(ctx, scratch.ensure(((size_t)2 * n + u_rows + 2 * (size_t)n_wg + 2) * 4));
-  hipError_t ce = counters.ensure(32);
-  if (ce != hipSuccess) {
-    scratch.release();
-    HIPCHK(ctx, ce);
-  }
-  uint32_t* new_index = scratch.as<uint32_t>();
-  uint32_t* src_node = new_index + n;
-  uint32_t* u_aux = src_node + n;
-  uint32_t* wg_nodes = u_aux + u_rows;
-  uint32_t* wg_urows = wg_nodes + n_wg;
-  uint32_t* totals = wg_urows + n_wg;
-  FreshGraph f;
-  auto fail = [&](int code, const char* msg) {
-    f.release();
-    scratch.release();
-    counters.release();
-    ctx->set_err(msg);
-    return code;
-  };
-#define GM_TRY(call)                                                                                             \
-  do {                                                                                                           \
-    const hipError_t e_ = (call);                                                                                \
-    if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, hipGetErrorString(e_)); \
-  } while (0)
-  GM_TRY(hipMemsetAsync(counters.p, 0, 32, st));
-  GmPrune p0{}, pU{};
-  uint32_t n_cap = g->n_cap, u_cap = g->u_cap;
-  uint64_t host_bytes = 0;
-  if (keep_rows) {
-    n_out = n;
-    u_out = u_rows;
-    GM_TRY(hipEventRecord(ev.ev[0], st));
-    if (u_rows)
-      hipLaunchKernelGGL(gm_owner_kernel, dim3(n_wg), dim3(256), 0, st, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, u_rows, u_aux);
-    GM_TRY(hipEventRecord(ev.ev[1], st));
-    GM_TRY(hipEventRecord(ev.ev[2], st));
-    p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), g->stride0, n, n,
-                 nullptr, nullptr, 1u, d_deleted, n, nullptr, nullptr, nullptr, (unsigned long long*)counters.p};
-    pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), g->strideU, u_rows, u_rows,
-                 nullptr, u_aux, 1u, d_deleted, n, nullptr, nullptr, nullptr, (unsigned long long*)counters.p};
-  } else {
-    // stage 1a: survivors and their upper rows, counted on the device and checked against the host's copy of the flags
-    GM_TRY(hipEventRecord(ev.ev[0], st));
-    hipLaunchKernelGGL(gm_count_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), n, wg_nodes, wg_urows);
-    hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_nodes, n_wg, totals);
-    hipLaunchKernelGGL(block_excl_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, wg_urows, n_wg, totals + 1);
-    GM_TRY(hipGetLastError());
-    GM_TRY(hipEventRecord(ev.ev[1], st));
-    uint32_t h_tot[2] = {0, 0};
-    GM_TRY(hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, st));
-    GM_TRY(hipStreamSynchronize(st));
-    host_bytes += 8;
-    if (h_tot[0] != n_out || h_tot[1] != u_out) return fail(FVDB_E_HIP, "graph vacuum: the device's deleted flags differ from the host's copy");
-    // every allocation precedes the first change
-    n_cap = n_out + n_out / 8 + 1024;
-    u_cap = u_out + u_out / 8 + 1024;
-    const size_t row_bytes = s->row_bytes();
-    const size_t sizes[10] = {(size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * 4, (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4,
-                              (size_t)n_cap * g->stride0 * 4, (size_t)u_cap * g->strideU * 4, (size_t)n_cap * 4, (size_t)u_cap * 4,
-                              (size_t)n_cap * row_bytes};
-    for (int b = 0; b < 10; ++b) {
-      const hipError_t e = FreshGraph::exact(*f.all[b], sizes[b]);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, "graph vacuum: no memory for the compacted copy (graph unchanged)");
-      }
-    }
-    for (int b = 0; b < 9; ++b) GM_TRY(hipMemsetAsync(f.all[b]->p, 0, f.all[b]->cap, st));  // (the store's rows are written whole)
-    // stage 1b: the maps, and level / upper-row base of every survivor at its new index
-    GM_TRY(hipEventRecord(ev.ev[2], st));
-    hipLaunchKernelGGL(gm_map_kernel, dim3(n_wg), dim3(256), 0, st, d_deleted, g->d_level.as<uint32_t>(), g->d_ubase.as<uint32_t>(), n, wg_nodes,
-                       wg_urows, n_out, u_out, new_index, src_node, u_aux, f.level.as<uint32_t>(), f.ubase.as<uint32_t>());
-    GM_TRY(hipGetLastError());
-    p0 = GmPrune{g->d_adj0.as<uint32_t>(), g->d_dist0.as<float>(), f.adj0.as<uint32_t>(), f.dist0.as<float>(), g->stride0, n_out, n,
-                 src_node, nullptr, 0u, d_deleted, n, new_index, g->d_stamp0.as<uint32_t>(), f.stamp0.as<uint32_t>(), (unsigned long long*)counters.p};
-    pU = GmPrune{g->d_adjU.as<uint32_t>(), g->d_distU.as<float>(), f.adjU.as<uint32_t>(), f.distU.as<float>(), g->strideU, u_out, u_rows,
-                 u_aux, nullptr, 0u, d_deleted, n, new_index, g->d_stampU.as<uint32_t>(), f.stampU.as<uint32_t>(), (unsigned long long*)counters.p};
-  }
-  // stage 2: prune + remap, one wave per destination row
-  GM_TRY(hipEventRecord(ev.ev[3], st));
-  hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, g->d_adj0.as<uint32_t>(), g->stride0, n, (unsigned long long*)counters.p);
-  if (u_rows)
-    hipLaunchKernelGGL(gm_edges_kernel, dim3(prune_grid(ctx, u_rows)), dim3(256), 0, st, g->d_adjU.as<uint32_t>(), g->strideU, u_rows,
-                       (unsigned long long*)counters.p);
-  if (p0.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, p0.rows)), dim3(256), 0, st, p0);
-  if (pU.rows) hipLaunchKernelGGL(gm_prune_kernel, dim3(prune_grid(ctx, pU.rows)), dim3(256), 0, st, pU);
-  GM_TRY(hipGetLastError());
-  GM_TRY(hipEventRecord(ev.ev[4], st));
-  // stage 3: store rows, one wave per destination row
-  if (!keep_rows && n_out) {
-    if (s->f16())  // a half row is dpad * 2 bytes: whole 8-byte chunks
-      hipLaunchKernelGGL(gm_move_kernel<float2>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float2*)s->data, n, s->dpad / 4, n_out, (float2*)f.rows.p);
-    else
-      hipLaunchKernelGGL(gm_move_kernel<float4>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, src_node, (const float4*)s->data, n, s->dpad / 4, n_out, (float4*)f.rows.p);
-    GM_TRY(hipGetLastError());
-  }
-  GM_TRY(hipEventRecord(ev.ev[5], st));
-  unsigned long long h_cnt[4] = {0, 0, 0, 0};
-  GM_TRY(hipMemcpyAsync(h_cnt, counters.p, 32, hipMemcpyDeviceToHost, st));
-  GM_TRY(hipStreamSynchronize(st));
-  host_bytes += 32;
-#undef GM_TRY
+  VacuumJob J{g, s, ctx, ctx->stream, keep_rows, n, u_rows, cdiv(n, 256), n_out, u_out, g->n_cap, g->u_cap};
+  int rc = J.alloc_scratch();
+  if (rc) return rc;
+  rc = keep_rows ? J.scan_in_place() : J.scan_reclaim();
+  if (rc) return rc;
+  rc = J.prune_move();
+  if (rc) return rc;
   // stage 4: bookkeeping
   g->mutations += 1;
-  info.edges_in = h_cnt[0];
-  info.edges_out = h_cnt[1];
+  info.edges_in = J.h_cnt[0];
+  info.edges_out = J.h_cnt[1];
   if (keep_rows) {
-    if (removed) *removed = h_cnt[2];
+    if (removed) *removed = J.h_cnt[2];
   } else {
     info.nodes_out = n_out;
     info.rows_reclaimed = n - n_out;
     info.bytes_reclaimed = (uint64_t)(n - n_out) * ((uint64_t)s->row_bytes() + (uint64_t)g->stride0 * 8 + 16) +
                            (uint64_t)(u_rows - u_out) * ((uint64_t)g->strideU * 8 + 4);
     info.move_bytes = 2ull * n_out * s->row_bytes();
-    std::swap(g->d_level, f.level);
-    std::swap(g->d_deleted, f.deleted);
-    std::swap(g->d_ubase, f.ubase);
-    std::swap(g->d_adj0, f.adj0);
-    std::swap(g->d_adjU, f.adjU);
-    std::swap(g->d_dist0, f.dist0);
-    std::swap(g->d_distU, f.distU);
-    std::swap(g->d_stamp0, f.stamp0);
-    std::swap(g->d_stampU, f.stampU);
-    // the store adopts the compacted rows: scorers read store->data at every launch
-    void* old_rows = s->data;
-    s->data = f.rows.p;
-    s->cap = n_cap;
-    s->rows = n_out;
-    f.rows.p = old_rows;
-    f.release();  // the old arrays
-    std::vector<uint32_t> lv(n_out), ub(n_out);
-    uint32_t w = 0, u = 0, entry = 0;
-    bool entry_alive = false;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (g->h_deleted[i]) continue;
-      if (g->has_entry && i == g->entry) {
-        entry = w;
-        entry_alive = true;
-      }
-      lv[w] = g->h_level[i];
-      ub[w] = u;
-      u += lv[w];
-      w += 1;
-    }
-    g->h_level.swap(lv);
-    g->h_ubase.swap(ub);
-    g->h_deleted.assign(n_out, 0);
-    g->n_deleted = 0;
-    g->n = n_out;
-    g->n_cap = n_cap;
-    g->u_rows = u_out;
-    g->u_cap = u_cap;
-    g->has_entry = entry_alive;
-    g->entry = entry_alive ? entry : 0;
-    g->top_level = entry_alive ? g->h_level[entry] : 0;
-    for (auto& v : g->vis_B) v = 0;  // visited maps are sized by the node count
+    rc = J.adopt();
     if (removed) *removed = n - n_out;
-    BuildState bs{};
-    bs.has_entry = entry_alive ? 1u : 0u;
-    bs.entry = g->entry;
-    bs.entry_level = g->top_level;
-    bs.n_linked = n_out;
-    int rc = push_state(g, bs);
-    host_bytes += sizeof(BuildState);
-    if (rc) {
-      scratch.release();
-      counters.release();
-      return rc;
-    }
+    if (rc) return rc;
   }
-  scratch.release();
-  counters.release();
-  info.host_bytes = host_bytes;
-  info.ms_scan = StageEvents::ms(ev.ev[0], ev.ev[1]) + (keep_rows ? 0.0f : StageEvents::ms(ev.ev[2], ev.ev[3]));
-  info.ms_prune = StageEvents::ms(ev.ev[3], ev.ev[4]);
-  info.ms_move = StageEvents::ms(ev.ev[4], ev.ev[5]);
+  info.host_bytes = J.host_bytes;
+  info.ms_scan = J.ev.ms(0, 1) + (keep_rows ? 0.0f : J.ev.ms(2, 3));
+  info.ms_prune = J.ev.ms(3, 4);
+  info.ms_move = J.ev.ms(4, 5);
   info.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   g->m_info = info;
   return FVDB_OK;
@@ -1402,123 +1377,115 @@ extern "C" int fvdb_graph_maintenance_info(fvdb_graph* g, fvdb_graph_maintenance
 // device-resident graph: health (kernels_graph_health.h).  Read-only: no flag, list, stamp, visited
 // map or counter of the graph is written, and `mutations` does not move.
 // =============================================================================================
-extern "C" int fvdb_graph_health(fvdb_graph* g, uint32_t flags, fvdb_graph_health_t* out) {
-  if (!g || !out) return FVDB_E_INVALID;
-  fvdb_ctx* ctx = g->store->ctx;
-  std::memset(out, 0, sizeof *out);
-  if (flags & ~(FVDB_HEALTH_SKIP_REACH | FVDB_HEALTH_SKIP_COMPONENTS)) FAIL(ctx, FVDB_E_INVALID, "graph health: unknown flag");
-  if (!g->uploaded) FAIL(ctx, FVDB_E_INVALID, "graph health: no device graph");
-  const bool want_reach = !(flags & FVDB_HEALTH_SKIP_REACH), want_comp = !(flags & FVDB_HEALTH_SKIP_COMPONENTS);
-  const uint32_t n = g->n;
-  if (n >= 0x80000000u) FAIL(ctx, FVDB_E_UNSUPPORTED, "graph health: 2^31 nodes or more");
-  g->health_has = 0;
-  if (n == 0) {
-    g->health_has = (want_reach ? 1u : 0u) | (want_comp ? 2u : 0u);
-    g->health_n = 0;
-    g->health_at = g->mutations;
-    return FVDB_OK;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // every allocation precedes the first launch: [counters | state] words, then list, parent, size; bitmap and labels are kept
-  const size_t bitmap_bytes = (size_t)cdiv(n, 32) * 4, node_bytes = (size_t)n * 4;
-  const size_t head_bytes = (size_t)kGhCounters * 8 + kGhStateWords * 4;
-  DBuf head, list, parent, size, bitmap, label;
-  auto drop = [&]() {
-    for (DBuf* b : {&head, &list, &parent, &size, &bitmap, &label}) b->release();
-  };
-  {
-    hipError_t e = head.ensure(head_bytes);
-    if (e == hipSuccess && want_reach) e = list.ensure(node_bytes);
-    if (e == hipSuccess && want_reach) e = bitmap.ensure(bitmap_bytes);
-    if (e == hipSuccess && want_comp) e = parent.ensure(node_bytes);
-    if (e == hipSuccess && want_comp) e = size.ensure(node_bytes);
-    if (e == hipSuccess && want_comp) e = label.ensure(node_bytes);
-    if (e == hipSuccess) e = g->h_state.ensure(std::max(head_bytes, sizeof(BuildState)));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      drop();
-      FAIL(ctx, e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP, "graph health: no memory for the scratch (graph unchanged)");
-    }
-  }
-  out->scratch_bytes = head.cap + list.cap + parent.cap + size.cap + bitmap.cap + label.cap;
-  StageEvents ev;
-  if (!ev.make()) {
-    drop();
-    FAIL(ctx, FVDB_E_HIP, "graph health: no events");
-  }
-  auto fail = [&](hipError_t e) {
-    drop();
-    ctx->set_err(std::string("graph health: ") + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP;
-  };
-#define GH_TRY(call)                      \
-  do {                                    \
-    const hipError_t e_ = (call);         \
-    if (e_ != hipSuccess) return fail(e_); \
-  } while (0)
-  unsigned long long* counters = head.as<unsigned long long>();
-  uint32_t* state = (uint32_t*)(counters + kGhCounters);
-  uint32_t* h_words = (uint32_t*)g->h_state.p;
-  const GhGraph gg{g->d_adj0.as<uint32_t>(), g->d_adjU.as<uint32_t>(), g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(),
-                   g->d_ubase.as<uint32_t>(), n, g->u_rows, g->stride0, g->strideU};
-  const bool has_entry = g->has_entry && g->entry < n;
-  const uint32_t entry = has_entry ? g->entry : kGhNone;
+namespace {
+
+struct HealthJob {
+  fvdb_graph* g;
+  fvdb_ctx* ctx;
+  hipStream_t st;
+  uint32_t n;
+  bool want_reach, want_comp;
+  size_t bitmap_bytes, node_bytes, head_bytes;
+  struct Scratch {  // head: [counters | state] words; bitmap and label become the graph's per-node results
+    DBuf head, list, parent, size, bitmap, label;
+  } sc;
+  StageTimer<2> ev;
+  unsigned long long* counters = nullptr;
+  uint32_t *state = nullptr, *h_words = nullptr;
+  GhGraph gg{};
+  bool has_entry = false;
+  uint32_t entry = kGhNone;
   uint32_t launches = 0, reach_launches = 0, host_syncs = 0, rounds0 = 0, reached = 0;
-  GH_TRY(hipEventRecord(ev.ev[0], st));
-  GH_TRY(hipMemsetAsync(head.p, 0, head_bytes, st));
-  // census
+  int alloc(fvdb_graph_health_t* out), census(), reach(), components(), report(fvdb_graph_health_t* out);  // the stages
+};
+
+// every allocation precedes the first launch
+int HealthJob::alloc(fvdb_graph_health_t* out) {
+  HIPCHK(ctx, sc.head.ensure(head_bytes));
+  if (want_reach) {
+    HIPCHK(ctx, sc.list.ensure(node_bytes));
+    HIPCHK(ctx, sc.bitmap.ensure(bitmap_bytes));
+  }
+  if (want_comp) {
+    HIPCHK(ctx, sc.parent.ensure(node_bytes));
+    HIPCHK(ctx, sc.size.ensure(node_bytes));
+    HIPCHK(ctx, sc.label.ensure(node_bytes));
+  }
+  HIPCHK(ctx, g->h_state.ensure(std::max(head_bytes, sizeof(BuildState))));
+  out->scratch_bytes = sc.head.cap + sc.list.cap + sc.parent.cap + sc.size.cap + sc.bitmap.cap + sc.label.cap;
+  HIPCHK(ctx, ev.create());
+  counters = sc.head.as<unsigned long long>();
+  state = (uint32_t*)(counters + kGhCounters);
+  h_words = (uint32_t*)g->h_state.p;
+  gg = GhGraph{g->d_adj0.as<uint32_t>(), g->d_adjU.as<uint32_t>(), g->d_level.as<uint32_t>(), g->d_deleted.as<uint32_t>(),
+               g->d_ubase.as<uint32_t>(), n, g->u_rows, g->stride0, g->strideU};
+  has_entry = g->has_entry && g->entry < n;
+  entry = has_entry ? g->entry : kGhNone;
+  return FVDB_OK;
+}
+
+int HealthJob::census() {
+  HIPCHK(ctx, ev.mark(0, st));
+  HIPCHK(ctx, hipMemsetAsync(sc.head.p, 0, head_bytes, st));
   hipLaunchKernelGGL(gh_census_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, gg, counters);
   launches += 1;
-  GH_TRY(hipGetLastError());
-  // reach: layer by layer from the entry point's level, each layer closed step by step
-  if (want_reach) {
-    GH_TRY(hipMemsetAsync(bitmap.p, 0, bitmap_bytes, st));
-    if (has_entry) {
-      hipLaunchKernelGGL(gh_seed_kernel, dim3(1), dim3(64), 0, st, entry, n, bitmap.as<uint32_t>(), list.as<uint32_t>(), state);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// reach: layer by layer from the entry point's level, each layer closed step by step
+int HealthJob::reach() {
+  uint32_t* bitmap = sc.bitmap.as<uint32_t>();
+  uint32_t* list = sc.list.as<uint32_t>();
+  HIPCHK(ctx, hipMemsetAsync(bitmap, 0, bitmap_bytes, st));
+  if (!has_entry) return FVDB_OK;
+  hipLaunchKernelGGL(gh_seed_kernel, dim3(1), dim3(64), 0, st, entry, n, bitmap, list, state);
+  launches += 1;
+  uint32_t tail = 1;
+  for (uint32_t layer = g->h_level[entry] + 1; layer-- > 0;) {
+    uint32_t lo = 0, hi = tail;  // the layer starts from everything reached so far
+    while (hi > lo) {
+      const bool narrow = hi - lo <= kGhQueue;
+      if (narrow)
+        hipLaunchKernelGGL(gh_reach_narrow_kernel, dim3(1), dim3(kGhNarrowThreads), 0, st, gg, layer, entry, lo, hi, bitmap, list, state);
+      else
+        hipLaunchKernelGGL(gh_reach_wide_kernel, dim3(prune_grid(ctx, hi - lo)), dim3(256), 0, st, gg, layer, entry, lo, hi, bitmap, list,
+                           state);
       launches += 1;
-      uint32_t tail = 1;
-      for (uint32_t layer = g->h_level[entry] + 1; layer-- > 0;) {
-        uint32_t lo = 0, hi = tail;  // the layer starts from everything reached so far
-        while (hi > lo) {
-          const bool narrow = hi - lo <= kGhQueue;
-          if (narrow)
-            hipLaunchKernelGGL(gh_reach_narrow_kernel, dim3(1), dim3(kGhNarrowThreads), 0, st, gg, layer, entry, lo, hi, bitmap.as<uint32_t>(),
-                               list.as<uint32_t>(), state);
-          else
-            hipLaunchKernelGGL(gh_reach_wide_kernel, dim3(prune_grid(ctx, hi - lo)), dim3(256), 0, st, gg, layer, entry, lo, hi,
-                               bitmap.as<uint32_t>(), list.as<uint32_t>(), state);
-          launches += 1;
-          reach_launches += 1;
-          GH_TRY(hipGetLastError());
-          GH_TRY(hipMemcpyAsync(h_words, state, kGhStateWords * 4, hipMemcpyDeviceToHost, st));
-          GH_TRY(hipStreamSynchronize(st));
-          host_syncs += 1;
-          tail = std::min(h_words[kGhTail], n);
-          if (tail < hi) return fail(hipErrorUnknown);  // cannot happen: the list only grows
-          if (layer == 0) rounds0 += narrow ? h_words[kGhSteps] : 1u;
-          lo = narrow ? std::min(std::max(h_words[kGhFrontier], hi), tail) : hi;
-          hi = tail;
-        }
-      }
-      reached = tail;
+      reach_launches += 1;
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipMemcpyAsync(h_words, state, kGhStateWords * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      host_syncs += 1;
+      tail = std::min(h_words[kGhTail], n);
+      if (tail < hi) FAIL(ctx, FVDB_E_HIP, "graph health: the reach list shrank");  // cannot happen: the list only grows
+      if (layer == 0) rounds0 += narrow ? h_words[kGhSteps] : 1u;
+      lo = narrow ? std::min(std::max(h_words[kGhFrontier], hi), tail) : hi;
+      hi = tail;
     }
   }
-  // weak components of the live layer-0 graph
-  if (want_comp) {
-    hipLaunchKernelGGL(uf_init_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, parent.as<uint32_t>(), size.as<uint32_t>());
-    hipLaunchKernelGGL(uf_union_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, gg, parent.as<uint32_t>());
-    hipLaunchKernelGGL(uf_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, gg.deleted, n, parent.as<uint32_t>(), label.as<uint32_t>(),
-                       size.as<uint32_t>());
-    hipLaunchKernelGGL(uf_summary_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, label.as<uint32_t>(), size.as<uint32_t>(), n, counters);
-    launches += 4;
-    GH_TRY(hipGetLastError());
-  }
-  GH_TRY(hipEventRecord(ev.ev[1], st));
-  GH_TRY(hipMemcpyAsync(g->h_state.p, counters, (size_t)kGhCounters * 8, hipMemcpyDeviceToHost, st));
-  GH_TRY(hipStreamSynchronize(st));
+  reached = tail;
+  return FVDB_OK;
+}
+
+// weak components of the live layer-0 graph
+int HealthJob::components() {
+  uint32_t *parent = sc.parent.as<uint32_t>(), *size = sc.size.as<uint32_t>(), *label = sc.label.as<uint32_t>();
+  hipLaunchKernelGGL(uf_init_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, parent, size);
+  hipLaunchKernelGGL(uf_union_kernel, dim3(prune_grid(ctx, n)), dim3(256), 0, st, gg, parent);
+  hipLaunchKernelGGL(uf_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, gg.deleted, n, parent, label, size);
+  hipLaunchKernelGGL(uf_summary_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, label, size, n, counters);
+  launches += 4;
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// the counters come back (the job's last sync) and become the report
+int HealthJob::report(fvdb_graph_health_t* out) {
+  HIPCHK(ctx, ev.mark(1, st));
+  HIPCHK(ctx, hipMemcpyAsync(g->h_state.p, counters, (size_t)kGhCounters * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   host_syncs += 1;
-#undef GH_TRY
   const unsigned long long* c = (const unsigned long long*)g->h_state.p;
   out->n_nodes = n;
   out->n_live = (uint32_t)c[kGhLive];
@@ -1544,11 +1511,40 @@ extern "C" int fvdb_graph_health(fvdb_graph* g, uint32_t flags, fvdb_graph_healt
   out->launches = launches;
   out->reach_launches = reach_launches;
   out->host_syncs = host_syncs;
-  out->ms = StageEvents::ms(ev.ev[0], ev.ev[1]);
-  // the scratch goes back; the per-node results stay until the next job
-  std::swap(g->d_hreach, bitmap);
-  std::swap(g->d_hlabel, label);
-  drop();
+  out->ms = ev.ms(0, 1);
+  return FVDB_OK;
+}
+
+}  // namespace
+
+extern "C" int fvdb_graph_health(fvdb_graph* g, uint32_t flags, fvdb_graph_health_t* out) {
+  if (!g || !out) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = g->store->ctx;
+  std::memset(out, 0, sizeof *out);
+  if (flags & ~(FVDB_HEALTH_SKIP_REACH | FVDB_HEALTH_SKIP_COMPONENTS)) FAIL(ctx, FVDB_E_INVALID, "graph health: unknown flag");
+  if (!g->uploaded) FAIL(ctx, FVDB_E_INVALID, "graph health: no device graph");
+  const bool want_reach = !(flags & FVDB_HEALTH_SKIP_REACH), want_comp = !(flags & FVDB_HEALTH_SKIP_COMPONENTS);
+  const uint32_t n = g->n;
+  if (n >= 0x80000000u) FAIL(ctx, FVDB_E_UNSUPPORTED, "graph health: 2^31 nodes or more");
+  g->health_has = 0;
+  if (n == 0) {
+    g->health_has = (want_reach ? 1u : 0u) | (want_comp ? 2u : 0u);
+    g->health_n = 0;
+    g->health_at = g->mutations;
+    return FVDB_OK;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HealthJob J{g, ctx, ctx->stream, n, want_reach, want_comp, (size_t)cdiv(n, 32) * 4, (size_t)n * 4,
+              (size_t)kGhCounters * 8 + kGhStateWords * 4};
+  int rc = J.alloc(out);
+  if (rc) return rc;
+  if ((rc = J.census())) return rc;
+  if (want_reach && (rc = J.reach())) return rc;
+  if (want_comp && (rc = J.components())) return rc;
+  if ((rc = J.report(out))) return rc;
+  std::swap(g->d_hreach, J.sc.bitmap);
+  std::swap(g->d_hlabel, J.sc.label);
+  J.sc = HealthJob::Scratch{};  // the scratch goes back (the last job's results with it); the per-node results stay until the next job
   g->health_has = (want_reach ? 1u : 0u) | (want_comp ? 2u : 0u);
   g->health_n = n;
   g->health_at = g->mutations;

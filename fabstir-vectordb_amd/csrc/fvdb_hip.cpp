@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pool.h"
 #include "kernels_misc.h"
 #include "kernels_scan.h"
 #include "kernels_wide.h"
@@ -34,96 +35,6 @@
 
 using namespace fvdb;
 
-
-// A pool of 64-row blocks in HBM (layout: common.h PoolView).
-struct Pool {
-  uint32_t d4 = 0;      // 4-dim chunks per row (of the padded dimension)
-  uint32_t esize = 4;   // bytes per stored element: 4 = f32, 2 = fp16
-  uint32_t cap_blocks = 0, used_blocks = 0;
-  void* data = nullptr;
-  uint64_t* ids = nullptr;
-  uint64_t* valid = nullptr;
-  float* norms = nullptr;  // |x|^2 per row (matrix-core filter, kernels_mfma.h)
-  bool mirror = false;     // f32 pools: keep an fp16 (round-to-nearest) copy of the rows for the matrix-core filter
-  void* half = nullptr;    // [blocks][d8][64] 8-half chunks, same lane = row layout
-  // f32 pools with the mirror also keep the rows ROW-MAJOR ([blocks * 64][dpad] f32, bit copies): the select stage
-  // scores some twenty single rows per query, and in the blocked layout every 16 bytes of a row sit in a different
-  // cache line (12 KB fetched per 1.5 KB row)
-  float* rm = nullptr;
-  size_t block_bytes() const { return (size_t)d4 * 4 * esize * 64; }
-  PoolView view() const { return PoolView{data, ids, valid, d4}; }
-  void release() {
-    if (norms) (void)hipFree(norms);
-    norms = nullptr;
-    if (half) (void)hipFree(half);
-    half = nullptr;
-    if (rm) (void)hipFree(rm);
-    rm = nullptr;
-    if (data) (void)hipFree(data);
-    if (ids) (void)hipFree(ids);
-    if (valid) (void)hipFree(valid);
-    data = nullptr;
-    ids = nullptr;
-    valid = nullptr;
-    cap_blocks = used_blocks = 0;
-  }
-  // grow to at least `blocks` capacity, preserving contents (stream-ordered copies)
-  int reserve(fvdb_ctx* ctx, uint32_t blocks) {
-    if (blocks <= cap_blocks) return FVDB_OK;
-    uint32_t ncap = std::max<uint32_t>(blocks, cap_blocks + cap_blocks / 2 + 16);
-    void* nd = nullptr;
-    uint64_t* ni = nullptr;
-    uint64_t* nv = nullptr;
-    float* nn = nullptr;
-    HIPCHK(ctx, hipMalloc(&nd, (size_t)ncap * block_bytes()));
-    // rows never written (the tail of each list's last block) must be finite: they share MFMA instructions with
-    // live rows, and 0 x NaN would poison those
-    HIPCHK(ctx, hipMemsetAsync(nd, 0, (size_t)ncap * block_bytes(), ctx->stream));
-    float* nr = nullptr;
-    if (mirror && esize == 4) {
-      HIPCHK(ctx, hipMalloc((void**)&nr, (size_t)ncap * block_bytes()));
-      HIPCHK(ctx, hipMemsetAsync(nr, 0, (size_t)ncap * block_bytes(), ctx->stream));
-      if (used_blocks && rm)
-        HIPCHK(ctx, hipMemcpyAsync(nr, rm, (size_t)used_blocks * block_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    void* nh = nullptr;
-    if (mirror) {
-      HIPCHK(ctx, hipMalloc(&nh, (size_t)ncap * block_bytes() / 2));
-      HIPCHK(ctx, hipMemsetAsync(nh, 0, (size_t)ncap * block_bytes() / 2, ctx->stream));
-      if (used_blocks && half)
-        HIPCHK(ctx, hipMemcpyAsync(nh, half, (size_t)used_blocks * block_bytes() / 2, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    HIPCHK(ctx, hipMalloc(&nn, (size_t)ncap * 64 * sizeof(float)));
-    HIPCHK(ctx, hipMemsetAsync(nn, 0, (size_t)ncap * 64 * sizeof(float), ctx->stream));
-    HIPCHK(ctx, hipMalloc(&ni, (size_t)ncap * 64 * sizeof(uint64_t)));
-    HIPCHK(ctx, hipMalloc(&nv, (size_t)ncap * sizeof(uint64_t)));
-    HIPCHK(ctx, hipMemsetAsync(nv, 0, (size_t)ncap * sizeof(uint64_t), ctx->stream));
-    if (used_blocks) {
-      HIPCHK(ctx, hipMemcpyAsync(nd, data, (size_t)used_blocks * block_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(ni, ids, (size_t)used_blocks * 64 * sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(nv, valid, (size_t)used_blocks * sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(nn, norms, (size_t)used_blocks * 64 * sizeof(float), hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (data) (void)hipFree(data);
-    if (ids) (void)hipFree(ids);
-    if (valid) (void)hipFree(valid);
-    if (norms) (void)hipFree(norms);
-    if (half) (void)hipFree(half);
-    half = nh;
-    if (rm) (void)hipFree(rm);
-    rm = nr;
-    norms = nn;
-    data = nd;
-    ids = ni;
-    valid = nv;
-    cap_blocks = ncap;
-    return FVDB_OK;
-  }
-};
 
 // Words of the counter block of an index (fvdb_ivf::s_fallbacks, 32 bytes, and its pinned copy h_fb): running totals
 // since the centroids were installed, added to by the kernels named.
@@ -176,40 +87,26 @@ struct IvfScratch {
   std::mutex enq;  // held while one search's launches are enqueued: searches sharing a set are ordered by the stream
   bool pend_filter = false;
   bool pending_profile = false, pend_coarse = false, pend_fine = false, collecting = false;
-  // a buffer of the set enrols itself on construction, so that release_all cannot miss one
-  std::vector<DBuf*> bufs;
-  struct Buf : DBuf {
-    explicit Buf(IvfScratch* set) { set->bufs.push_back(this); }
-  };
-  Buf s_qnorm{this}, s_A{this};
-  Buf s_qh{this}, s_qn2{this}, s_thr{this}, s_tA{this}, s_pa{this}, s_surv{this}, s_scnt{this}, s_fail{this}, s_mslots{this};
-  Buf s_sdist{this}, s_probes2{this};
-  Buf s_q{this}, s_cpart{this}, s_probes{this}, s_cnt{this}, s_fill{this}, s_eoff{this}, s_ioff{this}, s_entries{this};
-  Buf s_part{this}, s_scalars{this}, s_ceoff{this}, s_cioff{this};
-  Buf s_wbase{this}, s_arena{this};  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
-  Buf s_wgbase{this};                // the same bases over the logical index, for the keys of a shard's wide search
-  Buf s_gwords{this}, s_group{this};  // a grouped search: the live-word pointer table [G + 1], the group of each query [B]
-  Buf s_rbase{this}, s_rarena{this};  // the full centroid ranking (kernels_rank.h): the same for the centroid table
-  Buf s_qual{this};                   // fvdb_ivf_search_quality_dev: the two result blocks
+  DBuf s_qnorm, s_A;
+  DBuf s_qh, s_qn2, s_thr, s_tA, s_pa, s_surv, s_scnt, s_fail, s_mslots;
+  DBuf s_sdist, s_probes2;
+  DBuf s_q, s_cpart, s_probes, s_cnt, s_fill, s_eoff, s_ioff, s_entries;
+  DBuf s_part, s_scalars, s_ceoff, s_cioff;
+  DBuf s_wbase, s_arena;  // the wide selection (kernels_wide.h): per-query rank bases, distance arena
+  DBuf s_wgbase;          // the same bases over the logical index, for the keys of a shard's wide search
+  DBuf s_gwords, s_group;  // a grouped search: the live-word pointer table [G + 1], the group of each query [B]
+  DBuf s_rbase, s_rarena;  // the full centroid ranking (kernels_rank.h): the same for the centroid table
+  DBuf s_qual;            // fvdb_ivf_search_quality_dev: the two result blocks
   // fvdb_ivf_quality_curve_dev (kernels_curve.h): live rows per list; per chunk the ranking, the truth's keys and hit
   // counts, and the per-query recall and precision at every nprobe
-  Buf s_clive{this}, s_cprobes{this}, s_ckeys{this}, s_cval{this};
-  Buf s_in{this}, s_slots{this}, s_ids{this}, s_clusters{this}, s_out_ids{this}, s_out_dist{this}, s_out_cnt{this}, s_cdist{this};
+  DBuf s_clive, s_cprobes, s_ckeys, s_cval;
+  DBuf s_in, s_slots, s_ids, s_clusters, s_out_ids, s_out_dist, s_out_cnt, s_cdist;
   // fvdb_ivf_get_rows (ivf_rows.h): slots and gathered rows of one fetch.  Not s_slots / s_in: in set 0 those are the
   // insert staging.  fetch_done: the last fetch that read s_fslots on a stream other than the set's own
-  Buf s_fslots{this}, s_frows{this};
-  hipEvent_t fetch_done = nullptr;
-  hipEvent_t sev[EV_COUNT] = {};
+  DBuf s_fslots, s_frows;
+  DevEvent fetch_done;
+  DevEvent sev[EV_COUNT];
   uint32_t* scalar(ScalWord w) const { return s_scalars.as<uint32_t>() + w; }
-  void release_all() {
-    for (DBuf* b : bufs) b->release();
-    if (fetch_done) (void)hipEventDestroy(fetch_done);
-    fetch_done = nullptr;
-    for (auto& e : sev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
 };
 
 struct fvdb_ivf : IvfScratch {
@@ -298,7 +195,7 @@ struct Env {
 inline IvfScratch& slot_scratch(fvdb_ivf* ivf, uint32_t slot) { return slot == 0 ? *ivf : ivf->spare[slot - 1]; }
 // The liveness words of the inverted lists as this search sees them, and the pool with them in place: the one place
 // every argument block of the list scan takes them from.
-inline const uint64_t* live_words(const fvdb_ivf* ivf, const Env& E) { return E.live ? E.live : ivf->pool.valid; }
+inline const uint64_t* live_words(const fvdb_ivf* ivf, const Env& E) { return E.live ? E.live : ivf->pool.valid(); }
 inline PoolView list_pool(const fvdb_ivf* ivf, const Env& E) {
   PoolView v = ivf->pool.view();
   v.valid = live_words(ivf, E);
@@ -713,9 +610,9 @@ bool mfma_shape_ok(const fvdb_ivf* ivf, uint32_t B, uint32_t k, uint32_t np) {
   return ivf->dpad % 16 == 0 && k + kMfmaSlack <= 32 && np <= 256 && B >= 32 && B <= 16384;
 }
 // the filter reads fp16 rows (stored or mirrored)
-inline bool half_rows(const fvdb_ivf* ivf) { return ivf->f16 || ivf->pool.half != nullptr; }
+inline bool half_rows(const fvdb_ivf* ivf) { return ivf->f16 || ivf->pool.half() != nullptr; }
 // those rows against the rows the reference sees (mfma_error_bound): 0 the same, 1 rounded to nearest, 2 truncated
-inline int x_rounded(const fvdb_ivf* ivf) { return ivf->f16 ? 0 : (ivf->pool.half ? 1 : 2); }
+inline int x_rounded(const fvdb_ivf* ivf) { return ivf->f16 ? 0 : (ivf->pool.half() ? 1 : 2); }
 
 // What one matrix-core batch runs with, derived once from the index, the knobs and the batch shape.
 struct MfmaPlan {
@@ -795,9 +692,9 @@ ThresholdArgs threshold_args(fvdb_ivf* ivf, const Env& E, const float* qpad, con
                              uint32_t k, uint32_t np, float* thr_out) {
   const IvfScratch& S = *E.S;
   ThresholdArgs t{};
-  t.rows = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
+  t.rows = ivf->pool.half() ? ivf->pool.half() : ivf->pool.data();
   t.pool_valid = live_words(ivf, E);
-  t.pool_norms = ivf->pool.norms;
+  t.pool_norms = ivf->pool.norms();
   t.d4 = ivf->d4;
   t.lists = list_table(ivf);
   t.list_len = ivf->t_len.as<uint32_t>();
@@ -824,9 +721,9 @@ void launch_threshold_direct(fvdb_ivf* ivf, fvdb_ctx* ctx, const ThresholdArgs& 
 MfmaScanArgs mfma_scan_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Batch& b) {
   const IvfScratch& S = *E.S;
   MfmaScanArgs a{};
-  a.pool_data = ivf->pool.half ? ivf->pool.half : ivf->pool.data;
+  a.pool_data = ivf->pool.half() ? ivf->pool.half() : ivf->pool.data();
   a.pool_valid = live_words(ivf, E);
-  a.pool_norms = ivf->pool.norms;
+  a.pool_norms = ivf->pool.norms();
   a.d4 = ivf->d4;
   a.list_off = ivf->t_off.as<uint32_t>();
   a.list_blocks = ivf->t_blocks.as<uint32_t>();
@@ -1061,7 +958,7 @@ VerifyArgs verify_args(fvdb_ivf* ivf, const Env& E, const MfmaPlan& P, const Bat
   v.dpad = ivf->dpad;
   v.cmax = P.cmax;
   v.rows_f16 = P.x_rounded;
-  v.rows_rm = ivf->pool.rm;
+  v.rows_rm = ivf->pool.rm();
   v.out_ids = b.out_ids;
   v.out_dist = b.out_dist;
   v.out_counts = b.out_counts;
@@ -1158,7 +1055,7 @@ int run_fine(fvdb_ivf* ivf, const Env& E, const Batch& b, int role) {
   E.S->pend_filter = false;
   // beyond the shape: this index's own state (norms, lists rather than the one flat list), which thr_share_ok must not ask
   bool mfma = (ivf->scan_mode == FVDB_SCAN_AUTO || ivf->scan_mode == FVDB_SCAN_FILTER) && !ivf_knobs().scan_exact &&
-              mfma_shape_ok(ivf, b.B, b.k, b.np) && role == ROLE_LIST && ivf->pool.norms != nullptr;
+              mfma_shape_ok(ivf, b.B, b.k, b.np) && role == ROLE_LIST && ivf->pool.norms() != nullptr;
   // a mask thins the lists the filter samples its threshold from: AUTO scans exactly under one and keeps its hit-rate
   // watch for the unmasked traffic (FVDB_SCAN_FILTER still forces the filter)
   if (mfma && E.live && ivf->scan_mode == FVDB_SCAN_AUTO) mfma = false;
@@ -1330,7 +1227,7 @@ int ivf_shared_thresholds(fvdb_ivf* ivf, const Env& E, const float* q_dev, const
   if (rc) return rc;
   std::lock_guard<std::mutex> enq(S.enq);
   HIPCHK(ctx, S.s_qn2.ensure((size_t)B * 4));
-  if (!ivf->pool.norms || !ivf->d_xmax.p) {  // no rows on this rank yet: it owns nothing
+  if (!ivf->pool.norms() || !ivf->d_xmax.p) {  // no rows on this rank yet: it owns nothing
     HIPCHK(ctx, hipMemsetAsync(S.s_qn2.p, 0, (size_t)B * 4, ctx->stream));
     hipLaunchKernelGGL(fill_f32_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, u_out, (uint64_t)B, __builtin_huge_valf());
     HIPCHK(ctx, hipGetLastError());
@@ -1436,12 +1333,11 @@ int fvdb_ctx_create(int device, fvdb_ctx** out) {
   fvdb_ctx* ctx = new (std::nothrow) fvdb_ctx();
   if (!ctx) return FVDB_E_OOM;
   ctx->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || ctx->stream.create(hipStreamNonBlocking) != hipSuccess ||
+      ctx->ev0.create() != hipSuccess || ctx->ev1.create() != hipSuccess) {
     delete ctx;
     return FVDB_E_HIP;
   }
-  (void)hipEventCreate(&ctx->ev0);
-  (void)hipEventCreate(&ctx->ev1);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
   *out = ctx;
@@ -1464,10 +1360,6 @@ void fvdb_ctx_destroy(fvdb_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  ctx->h_stage.release();
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -1495,11 +1387,11 @@ int fvdb_ctx_set_profiling(fvdb_ctx* ctx, int on) {
 
 int fvdb_dev_alloc(fvdb_ctx* ctx, size_t bytes, void** out) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMalloc(out, std::max<size_t>(bytes, 16)));
+  HIPCHK(ctx, DeviceMem::alloc(out, std::max<size_t>(bytes, 16), 0));  // the caller's block from here on
   return FVDB_OK;
 }
 int fvdb_dev_free(fvdb_ctx* ctx, void* p) {
-  HIPCHK(ctx, hipFree(p));
+  HIPCHK(ctx, DeviceMem::free(p));
   return FVDB_OK;
 }
 int fvdb_dev_upload(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes) {
@@ -1516,12 +1408,12 @@ int fvdb_dev_download(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes) {
 int fvdb_host_alloc(fvdb_ctx* ctx, size_t bytes, void** out) {
   *out = nullptr;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipHostMalloc(out, std::max<size_t>(bytes, 16), hipHostMallocDefault));
+  HIPCHK(ctx, PinnedMem::alloc(out, std::max<size_t>(bytes, 16), hipHostMallocDefault));
   return FVDB_OK;
 }
 void fvdb_host_free(fvdb_ctx* ctx, void* p) {
   (void)ctx;
-  if (p) (void)hipHostFree(p);
+  if (p) (void)PinnedMem::free(p);
 }
 int fvdb_dev_download_async(fvdb_ctx* ctx, void* dst_pinned, const void* src, size_t bytes) {
   HIPCHK(ctx, hipMemcpyAsync(dst_pinned, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1532,23 +1424,21 @@ int fvdb_dev_copy_async(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes)
   return FVDB_OK;
 }
 struct fvdb_event {
-  hipEvent_t ev = nullptr;
+  DevEvent ev;
 };
 int fvdb_event_create(fvdb_ctx* ctx, fvdb_event** out) {
   *out = nullptr;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   fvdb_event* e = new (std::nothrow) fvdb_event();
   if (!e) return FVDB_E_OOM;
-  if (hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess) {
+  if (e->ev.create(hipEventDisableTiming) != hipSuccess) {
     delete e;
-    FAIL(ctx, FVDB_E_HIP, "hipEventCreate failed");
+    FAIL(ctx, FVDB_E_HIP, "event creation failed");
   }
   *out = e;
   return FVDB_OK;
 }
 void fvdb_event_destroy(fvdb_event* e) {
-  if (!e) return;
-  if (e->ev) (void)hipEventDestroy(e->ev);
   delete e;
 }
 int fvdb_event_record(fvdb_ctx* ctx, fvdb_event* e) {
@@ -1583,24 +1473,16 @@ static int dot_cosine(fvdb_ctx* ctx, const float* q, uint32_t B, const float* x,
   if (rc) return rc;
   rc = check_finite(ctx, x, n * d);
   if (rc) return rc;
-  float *dq = nullptr, *dx = nullptr, *dout = nullptr;
-  auto done = [&]() {
-    if (dq) (void)hipFree(dq);
-    if (dx) (void)hipFree(dx);
-    if (dout) (void)hipFree(dout);
-  };
-  if (hipMalloc(&dq, (size_t)B * d * 4) != hipSuccess || hipMalloc(&dx, n * d * 4) != hipSuccess ||
-      hipMalloc(&dout, (size_t)B * n * 4) != hipSuccess) {
-    done();
+  DBuf dq, dx, dout;
+  if (dq.exact((size_t)B * d * 4) != hipSuccess || dx.exact(n * d * 4) != hipSuccess ||
+      dout.exact((size_t)B * n * 4) != hipSuccess)
     FAIL(ctx, FVDB_E_OOM, "similarity scratch allocation failed");
-  }
-  (void)hipMemcpyAsync(dq, q, (size_t)B * d * 4, hipMemcpyHostToDevice, ctx->stream);
-  (void)hipMemcpyAsync(dx, x, n * d * 4, hipMemcpyHostToDevice, ctx->stream);
-  hipLaunchKernelGGL(dot_cosine_kernel, dim3(cdiv((uint64_t)B * n, 256)), dim3(256), 0, ctx->stream, dq, dx, B, n, d,
-                     cosine, dout);
-  hipError_t e = hipMemcpyAsync(out, dout, (size_t)B * n * 4, hipMemcpyDeviceToHost, ctx->stream);
+  (void)hipMemcpyAsync(dq.p, q, (size_t)B * d * 4, hipMemcpyHostToDevice, ctx->stream);
+  (void)hipMemcpyAsync(dx.p, x, n * d * 4, hipMemcpyHostToDevice, ctx->stream);
+  hipLaunchKernelGGL(dot_cosine_kernel, dim3(cdiv((uint64_t)B * n, 256)), dim3(256), 0, ctx->stream, dq.as<float>(),
+                     dx.as<float>(), B, n, d, cosine, dout.as<float>());
+  hipError_t e = hipMemcpyAsync(out, dout.p, (size_t)B * n * 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  done();
   if (e != hipSuccess) FAIL(ctx, FVDB_E_HIP, hipGetErrorString(e));
   return FVDB_OK;
 }
@@ -1641,7 +1523,7 @@ int fvdb_ivf_create_ex(fvdb_ctx* ctx, uint32_t d, uint32_t nlist, int row_dtype,
   static const bool no_mirror = getenv("FVDB_NO_FP16_MIRROR") != nullptr;  // tuning aid: filter from the f32 rows
   ivf->pool.mirror = !ivf->f16 && ivf->dpad % 16 == 0 && !no_mirror;
   ivf->cpool.d4 = ivf->d4;
-  for (auto& e : ivf->sev) (void)hipEventCreate(&e);
+  for (auto& e : ivf->sev) (void)e.create();
   *out = ivf;
   return FVDB_OK;
 }
@@ -1650,18 +1532,8 @@ void fvdb_ivf_destroy(fvdb_ivf* ivf) {
   if (!ivf) return;
   (void)hipSetDevice(ivf->ctx->device);
   (void)hipStreamSynchronize(ivf->ctx->stream);
-  ivf->pool.release();
-  ivf->cpool.release();
-  DBuf* bufs[] = {&ivf->d_xmax, &ivf->d_cent_pad, &ivf->d_cnorm, &ivf->d_cnmax, &ivf->s_fallbacks, &ivf->d_mfma_stamps, &ivf->d_centroids_rm,
-                  &ivf->c_off, &ivf->c_blocks, &ivf->c_glob, &ivf->t_off, &ivf->t_blocks, &ivf->t_glob, &ivf->t_len,
-                  &ivf->m_seq, &ivf->m_dest, &ivf->m_ids};
-  for (DBuf* b : bufs) b->release();
-  ivf->release_all();
-  for (auto& sp : ivf->spare) sp.release_all();
-  for (auto& sp : ivf->lease_set) sp.release_all();
   for (auto& c : ivf->lease_ctx)
     if (c) fvdb_ctx_destroy(c);
-  ivf->h_fb.release();
   delete ivf;
 }
 
@@ -1671,7 +1543,7 @@ static int install_centroids(fvdb_ivf* ivf, const float* d_rowmajor /* device [n
   const uint32_t nlist = ivf->nlist, cblocks = cdiv(nlist, 64);
   int rc = ivf->cpool.reserve(ctx, cblocks);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync(ivf->cpool.valid, 0, (size_t)ivf->cpool.cap_blocks * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ivf->cpool.valid(), 0, (size_t)ivf->cpool.cap_blocks * 8, ctx->stream));
   ivf->cpool.used_blocks = cblocks;
   std::vector<uint32_t> slots(nlist), off{0, cblocks}, blocks(cblocks), glob{cblocks};
   for (uint32_t i = 0; i < nlist; ++i) slots[i] = i;
@@ -1687,7 +1559,7 @@ static int install_centroids(fvdb_ivf* ivf, const float* d_rowmajor /* device [n
   const uint64_t threads = (uint64_t)nlist * ivf->d4;
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, ctx->stream, d_rowmajor, ivf->d,
                      ivf->d4, (uint64_t)nlist, ivf->s_slots.as<uint32_t>(), (const uint64_t*)nullptr,
-                     (float4*)ivf->cpool.data, ivf->cpool.ids, (unsigned long long*)ivf->cpool.valid, (void*)nullptr,
+                     (float4*)ivf->cpool.data(), ivf->cpool.ids(), (unsigned long long*)ivf->cpool.valid(), (void*)nullptr,
                      (float4*)nullptr);
   // matrix-core coarse stage: padded row-major table, |c|^2, max |c|^2
   const float* cpad = d_rowmajor;
@@ -1739,8 +1611,8 @@ int fvdb_ivf_set_centroids(fvdb_ivf* ivf, const float* centroids) {
   rc = install_centroids(ivf, ivf->d_centroids_rm.as<float>());
   if (rc) return rc;
   reset_lists(ivf);
-  if (ivf->pool.valid && ivf->pool.cap_blocks)
-    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid, 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
+  if (ivf->pool.valid() && ivf->pool.cap_blocks)
+    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid(), 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
   return FVDB_OK;
 }
 
@@ -1754,8 +1626,8 @@ int fvdb_ivf_clear(fvdb_ivf* ivf) {
   ivf->mutations += 1;
   fvdb_ctx* ctx = ivf->ctx;
   reset_lists(ivf);
-  if (ivf->pool.valid && ivf->pool.cap_blocks)
-    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid, 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
+  if (ivf->pool.valid() && ivf->pool.cap_blocks)
+    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid(), 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
   return FVDB_OK;
 }
 
@@ -1787,9 +1659,9 @@ int fvdb_ivf_list_export(fvdb_ivf* ivf, uint32_t list, float* rows, uint64_t* id
   const uint32_t d = ivf->d;
   for (uint32_t b = 0; b * 64 < len; ++b) {
     const uint32_t pb = ivf->list_blocks[list][b];
-    HIPCHK(ctx, hipMemcpyAsync(blk.data(), (const char*)P.data + (size_t)pb * bb, bb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(bid, P.ids + (size_t)pb * 64, sizeof bid, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&valid, P.valid + pb, sizeof valid, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(blk.data(), (const char*)P.data() + (size_t)pb * bb, bb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(bid, P.ids() + (size_t)pb * 64, sizeof bid, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&valid, P.valid() + pb, sizeof valid, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t rows_here = std::min<uint32_t>(64, len - b * 64);
     for (uint32_t lane = 0; lane < rows_here; ++lane) {
@@ -1887,21 +1759,21 @@ static int append_staged(fvdb_ivf* ivf, const uint64_t* ids, uint64_t n, const u
     const uint32_t d8 = ivf->dpad / 8;
     hipLaunchKernelGGL(scatter_rows_f16_kernel, dim3(cdiv(n * d8, 256)), dim3(256), 0, ctx->stream,
                        ivf->s_in.as<float>(), ivf->d, d8, n, ivf->s_slots.as<uint32_t>(),
-                       ids ? ivf->s_ids.as<uint64_t>() : nullptr, ivf->pool.data, ivf->pool.ids,
-                       (unsigned long long*)ivf->pool.valid);
+                       ids ? ivf->s_ids.as<uint64_t>() : nullptr, ivf->pool.data(), ivf->pool.ids(),
+                       (unsigned long long*)ivf->pool.valid());
   } else {
     const uint64_t threads = n * ivf->d4;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, ctx->stream, ivf->s_in.as<float>(),
                        ivf->d, ivf->d4, n, ivf->s_slots.as<uint32_t>(), ids ? ivf->s_ids.as<uint64_t>() : nullptr,
-                       (float4*)ivf->pool.data, ivf->pool.ids, (unsigned long long*)ivf->pool.valid, ivf->pool.half,
-                       (float4*)ivf->pool.rm);
+                       (float4*)ivf->pool.data(), ivf->pool.ids(), (unsigned long long*)ivf->pool.valid(), ivf->pool.half(),
+                       (float4*)ivf->pool.rm());
   }
   if (!ivf->d_xmax.p) {
     HIPCHK(ctx, ivf->d_xmax.ensure(4));
     HIPCHK(ctx, hipMemsetAsync(ivf->d_xmax.p, 0, 4, ctx->stream));
   }
   hipLaunchKernelGGL(pool_row_norms_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, ivf->s_in.as<float>(), ivf->d, n,
-                     ivf->f16 ? 1 : 0, ivf->s_slots.as<uint32_t>(), ivf->pool.norms, ivf->d_xmax.as<uint32_t>());
+                     ivf->f16 ? 1 : 0, ivf->s_slots.as<uint32_t>(), ivf->pool.norms(), ivf->d_xmax.as<uint32_t>());
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FVDB_OK;
@@ -1953,7 +1825,7 @@ int fvdb_ivf_set_deleted(fvdb_ivf* ivf, const uint32_t* cluster, const uint32_t*
   HIPCHK(ctx, ivf->s_slots.ensure(n * 4));
   HIPCHK(ctx, hipMemcpyAsync(ivf->s_slots.p, slots.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(set_valid_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, ivf->s_slots.as<uint32_t>(), n,
-                     deleted, (unsigned long long*)ivf->pool.valid);
+                     deleted, (unsigned long long*)ivf->pool.valid());
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FVDB_OK;
@@ -2044,8 +1916,7 @@ int check_k(fvdb_ctx* ctx, IvfSearch::Kind kind, uint32_t k, uint32_t np) {
 // the stage events of a scratch set exist from the first profiled search on it
 void ensure_stage_events(const fvdb_ivf* ivf, IvfScratch& S) {
   if (!ivf->ctx->profiling) return;
-  for (auto& e : S.sev)
-    if (!e) (void)hipEventCreate(&e);
+  for (auto& e : S.sev) (void)e.create();
 }
 
 // A grouped search's host side: the table of live-word pointers (device addresses, [n_words]) and the group of each
@@ -2301,7 +2172,7 @@ int fvdb_ivf_search_groups_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, 
     if (B && !group_of_query) FAIL(ctx, FVDB_E_INVALID, "null group array");
     if (B && G == 0) FAIL(ctx, FVDB_E_INVALID, "queries but no group");
     // the last entry is the pool's own words: what a null mask ("no filter") maps to
-    std::vector<const uint64_t*> words((size_t)G + 1, ivf->pool.valid);
+    std::vector<const uint64_t*> words((size_t)G + 1, ivf->pool.valid());
     for (uint32_t g = 0; g < G; ++g) {
       const fvdb_mask* m = masks[g];
       if (!m) continue;
@@ -2313,7 +2184,7 @@ int fvdb_ivf_search_groups_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, 
       if (group_of_query[b] >= G) FAIL(ctx, FVDB_E_INVALID, "group index out of range");
     // a grouped search is a masked one to everything that asks (the counter blocks, AUTO's watch); the words a stage
     // reads per batch are the pool's, the score stage reads each query's own
-    E.live = ivf->pool.valid;
+    E.live = ivf->pool.valid();
     const GroupSource src{words.data(), G + 1, group_of_query};
     return ivf_search(ivf, E, IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev},
                       &src);
@@ -2631,36 +2502,21 @@ uint64_t fvdb_ivf_stage_times(fvdb_ivf* ivf, float* ms_out) {
 // =============================================================================================
 // k-means training on the GPU (src/ivf/core.rs:240-429)
 // =============================================================================================
-// Everything after "the rows are in HBM": X is [n][d] f32 on the device.  fvdb_ivf_train uploads its rows there,
-// fvdb_ivf_train_from (ivf_maint.h) gathers them from another index's lists; the arithmetic is shared.
-static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t max_iterations, uint64_t seed,
-                          fvdb_train_result* out) {
+namespace {
+struct TrainJob {
+  fvdb_ivf* ivf;
+  const float* X;
+  uint64_t n;
+  DBuf dmind, dassign, dnew, ddist, dsc;  // freed when the job returns
+  float* cent = nullptr;                  // ivf->d_centroids_rm
+  uint32_t gn = 0;
+  int seed_centroids(uint64_t seed), error(float* out_err), iterate(uint32_t max_iterations, fvdb_train_result* res);
+};
+
+// k-means++ seeding (:336-371); draws from SplitMix64(seed)
+int TrainJob::seed_centroids(uint64_t seed) {
   fvdb_ctx* ctx = ivf->ctx;
   const uint32_t nlist = ivf->nlist, d = ivf->d;
-  int rc = FVDB_OK;
-  DBuf dmind, dassign, dnew, ddist, dsc;
-  auto cleanup = [&]() {
-    dmind.release(); dassign.release(); dnew.release(); ddist.release(); dsc.release();
-  };
-#define TCHK(call)                                                        \
-  do {                                                                    \
-    hipError_t e_ = (call);                                               \
-    if (e_ != hipSuccess) {                                               \
-      ctx->set_err(std::string(#call) + ": " + hipGetErrorString(e_));    \
-      cleanup();                                                          \
-      return e_ == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP;         \
-    }                                                                     \
-  } while (0)
-  TCHK(dmind.ensure(n * 4));
-  TCHK(dassign.ensure(n * 4));
-  TCHK(dnew.ensure(n * 4));
-  TCHK(ddist.ensure(n * 4));
-  TCHK(dsc.ensure(64));
-  TCHK(ivf->d_centroids_rm.ensure((size_t)nlist * d * 4));
-  float* cent = ivf->d_centroids_rm.as<float>();
-  const uint32_t gn = cdiv(n, 256);
-
-  // ---- k-means++ seeding (:336-371); draws from SplitMix64(seed) ----
   struct {
     uint64_t s;
     uint64_t next() {
@@ -2671,7 +2527,7 @@ static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t ma
     }
   } rng{seed};
   uint64_t pick = rng.next() % n;
-  TCHK(hipMemcpyAsync(cent, X + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cent, X + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream));
   hipLaunchKernelGGL(fill_f32_kernel, dim3(gn), dim3(256), 0, ctx->stream, dmind.as<float>(), n,
                      __builtin_huge_valf());
   uint32_t chosen = 1;
@@ -2682,55 +2538,58 @@ static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t ma
     hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(256), 0, ctx->stream, dmind.as<float>(), n, u,
                        (unsigned long long*)dsc.p);
     unsigned long long p = 0;
-    TCHK(hipMemcpyAsync(&p, dsc.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    TCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&p, dsc.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (p == ~0ull) continue;  // reference: the loop never fired, no centroid pushed this round
     pick = p;
-    TCHK(hipMemcpyAsync(cent + (size_t)chosen * d, X + pick * d, (size_t)d * 4,
-                        hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cent + (size_t)chosen * d, X + pick * d, (size_t)d * 4,
+                               hipMemcpyDeviceToDevice, ctx->stream));
     chosen++;
   }
-  if (chosen < nlist) {
-    cleanup();
-    FAIL(ctx, FVDB_E_INVALID, "k-means++ produced fewer centroids than n_clusters (degenerate data)");
-  }
+  if (chosen < nlist) FAIL(ctx, FVDB_E_INVALID, "k-means++ produced fewer centroids than n_clusters (degenerate data)");
+  return FVDB_OK;
+}
 
-  auto error_of = [&](float* out_err) -> int {
-    hipLaunchKernelGGL(kmeans_point_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, X, d, n,
-                       dassign.as<uint32_t>(), cent, ddist.as<float>());
-    hipLaunchKernelGGL(seq_sqsum_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, ddist.as<float>(), n,
-                       (float*)dsc.p + 4);
-    float r[2];
-    HIPCHK(ctx, hipMemcpyAsync(r, (float*)dsc.p + 4, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *out_err = r[0];
-    return FVDB_OK;
-  };
+int TrainJob::error(float* out_err) {
+  fvdb_ctx* ctx = ivf->ctx;
+  hipLaunchKernelGGL(kmeans_point_dist_kernel, dim3(gn), dim3(256), 0, ctx->stream, X, ivf->d, n,
+                     dassign.as<uint32_t>(), cent, ddist.as<float>());
+  hipLaunchKernelGGL(seq_sqsum_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, ddist.as<float>(), n,
+                     (float*)dsc.p + 4);
+  float r[2];
+  HIPCHK(ctx, hipMemcpyAsync(r, (float*)dsc.p + 4, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *out_err = r[0];
+  return FVDB_OK;
+}
 
-  TCHK(hipMemsetAsync(dassign.p, 0, n * 4, ctx->stream));  // assignments start at ClusterId(0) (:280)
-  float prev_error = __builtin_huge_valf(), initial_error = 0, final_error = 0;
-  rc = error_of(&initial_error);
-  if (rc) { cleanup(); return rc; }
+// Lloyd iterations from the seeded centroids; fills iterations, converged and the two errors of `res`
+int TrainJob::iterate(uint32_t max_iterations, fvdb_train_result* res) {
+  fvdb_ctx* ctx = ivf->ctx;
+  HIPCHK(ctx, hipMemsetAsync(dassign.p, 0, n * 4, ctx->stream));  // assignments start at ClusterId(0) (:280)
+  float prev_error = __builtin_huge_valf();
+  int rc = error(&res->initial_error);
+  if (rc) return rc;
   bool converged = false;
   uint32_t iterations = 0;
   for (uint32_t iter = 0; iter < max_iterations; ++iter) {
     iterations = iter + 1;
     rc = install_centroids(ivf, cent);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     rc = assign_dev(ivf, X, n, dnew.as<uint32_t>());
-    if (rc) { cleanup(); return rc; }
-    TCHK(hipMemsetAsync(dsc.p, 0, 4, ctx->stream));
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemsetAsync(dsc.p, 0, 4, ctx->stream));
     hipLaunchKernelGGL(count_changed_kernel, dim3(gn), dim3(256), 0, ctx->stream, dnew.as<uint32_t>(),
                        dassign.as<uint32_t>(), n, (uint32_t*)dsc.p);
     uint32_t changed = 0;
-    TCHK(hipMemcpyAsync(&changed, dsc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3(nlist), dim3(256), 0, ctx->stream, X, d, n,
+    HIPCHK(ctx, hipMemcpyAsync(&changed, dsc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3(ivf->nlist), dim3(256), 0, ctx->stream, X, ivf->d, n,
                        dassign.as<uint32_t>(), cent);
-    TCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (iterations >= max_iterations) break;
     float cur = 0;
-    rc = error_of(&cur);
-    if (rc) { cleanup(); return rc; }
+    rc = error(&cur);
+    if (rc) return rc;
     const float change = std::fabs(prev_error - cur) / prev_error;
     if (changed == 0 || change < 1e-4f) {
       converged = true;
@@ -2742,24 +2601,41 @@ static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t ma
     }
     prev_error = cur;
   }
-  rc = error_of(&final_error);
-  if (rc) { cleanup(); return rc; }
+  res->iterations = iterations;
+  res->converged = converged ? 1 : 0;
+  return error(&res->final_error);
+}
+}  // namespace
+
+// Everything after "the rows are in HBM": X is [n][d] f32 on the device.  fvdb_ivf_train uploads its rows there,
+// fvdb_ivf_train_from (ivf_maint.h) gathers them from another index's lists; the arithmetic is shared.
+static int train_resident(fvdb_ivf* ivf, const float* X, uint64_t n, uint32_t max_iterations, uint64_t seed,
+                          fvdb_train_result* out) {
+  fvdb_ctx* ctx = ivf->ctx;
+  const uint32_t nlist = ivf->nlist, d = ivf->d;
+  TrainJob J{ivf, X, n};
+  HIPCHK(ctx, J.dmind.ensure(n * 4));
+  HIPCHK(ctx, J.dassign.ensure(n * 4));
+  HIPCHK(ctx, J.dnew.ensure(n * 4));
+  HIPCHK(ctx, J.ddist.ensure(n * 4));
+  HIPCHK(ctx, J.dsc.ensure(64));
+  HIPCHK(ctx, ivf->d_centroids_rm.ensure((size_t)nlist * d * 4));
+  J.cent = ivf->d_centroids_rm.as<float>();
+  J.gn = cdiv(n, 256);
+  fvdb_train_result res{};
+  int rc = J.seed_centroids(seed);
+  if (rc) return rc;
+  rc = J.iterate(max_iterations, &res);
+  if (rc) return rc;
   ivf->h_centroids.resize((size_t)nlist * d);
-  TCHK(hipMemcpyAsync(ivf->h_centroids.data(), cent, (size_t)nlist * d * 4, hipMemcpyDeviceToHost, ctx->stream));
-  TCHK(hipStreamSynchronize(ctx->stream));
-  rc = install_centroids(ivf, cent);
-  cleanup();
+  HIPCHK(ctx, hipMemcpyAsync(ivf->h_centroids.data(), J.cent, (size_t)nlist * d * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  rc = install_centroids(ivf, J.cent);
   if (rc) return rc;
   reset_lists(ivf);
-  if (ivf->pool.valid && ivf->pool.cap_blocks)
-    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid, 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
-  if (out) {
-    out->iterations = iterations;
-    out->converged = converged ? 1 : 0;
-    out->initial_error = initial_error;
-    out->final_error = final_error;
-  }
-#undef TCHK
+  if (ivf->pool.valid() && ivf->pool.cap_blocks)
+    HIPCHK(ctx, hipMemsetAsync(ivf->pool.valid(), 0, (size_t)ivf->pool.cap_blocks * 8, ctx->stream));
+  if (out) *out = res;
   return FVDB_OK;
 }
 
@@ -2782,13 +2658,8 @@ int fvdb_ivf_train(fvdb_ivf* ivf, const float* x, uint64_t n, uint32_t max_itera
   DBuf dx;
   HIPCHK(ctx, dx.ensure(n * ivf->d * 4));
   hipError_t e = hipMemcpyAsync(dx.p, x, n * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) {
-    dx.release();
-    FAIL(ctx, FVDB_E_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-  }
-  rc = train_resident(ivf, dx.as<float>(), n, max_iterations, seed, out);
-  dx.release();
-  return rc;
+  if (e != hipSuccess) FAIL(ctx, FVDB_E_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  return train_resident(ivf, dx.as<float>(), n, max_iterations, seed, out);
 }
 
 // =============================================================================================
@@ -2898,16 +2769,6 @@ int fvdb_merge_search_results_dev(fvdb_ctx* ctx, const uint64_t* ids_dev, const 
 }
 
 // host-pointer forms: stage, run the device form, copy back
-namespace {
-struct UtilBufs {
-  void *a = nullptr, *b = nullptr, *o1 = nullptr, *o2 = nullptr, *oc = nullptr;
-  ~UtilBufs() {
-    for (void* p : {a, b, o1, o2, oc})
-      if (p) (void)hipFree(p);
-  }
-};
-}  // namespace
-
 static int top_k_host(fvdb_ctx* ctx, const float* scores, uint32_t B, uint64_t n, uint32_t k, int heap, uint64_t* out_idx,
                       uint32_t* out_counts) {
   if (!ctx || !scores || !out_counts || (!out_idx && k)) return FVDB_E_INVALID;
@@ -2915,15 +2776,15 @@ static int top_k_host(fvdb_ctx* ctx, const float* scores, uint32_t B, uint64_t n
   int rc = check_no_nan(ctx, scores, (uint64_t)B * n);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  UtilBufs u;
-  HIPCHK(ctx, hipMalloc(&u.a, std::max<size_t>((size_t)B * n * 4, 16)));
-  HIPCHK(ctx, hipMalloc(&u.o1, std::max<size_t>((size_t)B * k * 8, 16)));
-  HIPCHK(ctx, hipMalloc(&u.oc, (size_t)B * 4));
-  HIPCHK(ctx, hipMemcpyAsync(u.a, scores, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = fvdb_top_k_indices_dev(ctx, (const float*)u.a, B, n, k, heap, (uint64_t*)u.o1, (uint32_t*)u.oc);
+  DBuf a, o1, oc;
+  HIPCHK(ctx, a.exact(std::max<size_t>((size_t)B * n * 4, 16)));
+  HIPCHK(ctx, o1.exact(std::max<size_t>((size_t)B * k * 8, 16)));
+  HIPCHK(ctx, oc.exact((size_t)B * 4));
+  HIPCHK(ctx, hipMemcpyAsync(a.p, scores, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
+  rc = fvdb_top_k_indices_dev(ctx, a.as<const float>(), B, n, k, heap, o1.as<uint64_t>(), oc.as<uint32_t>());
   if (rc) return rc;
-  if (k) HIPCHK(ctx, hipMemcpyAsync(out_idx, u.o1, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(out_counts, u.oc, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (k) HIPCHK(ctx, hipMemcpyAsync(out_idx, o1.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out_counts, oc.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FVDB_OK;
 }
@@ -2943,24 +2804,24 @@ static int pairs_host(fvdb_ctx* ctx, const uint64_t* ids, const float* vals, uin
   int rc = check_no_nan(ctx, vals, (uint64_t)B * n);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  UtilBufs u;
-  HIPCHK(ctx, hipMalloc(&u.a, std::max<size_t>((size_t)B * n * 8, 16)));
-  HIPCHK(ctx, hipMalloc(&u.b, std::max<size_t>((size_t)B * n * 4, 16)));
-  HIPCHK(ctx, hipMalloc(&u.o1, std::max<size_t>((size_t)B * k * 8, 16)));
-  HIPCHK(ctx, hipMalloc(&u.o2, std::max<size_t>((size_t)B * k * 4, 16)));
-  HIPCHK(ctx, hipMalloc(&u.oc, (size_t)B * 4));
-  HIPCHK(ctx, hipMemcpyAsync(u.a, ids, (size_t)B * n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(u.b, vals, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = merge ? fvdb_merge_search_results_dev(ctx, (const uint64_t*)u.a, (const float*)u.b, B, n, k, (uint64_t*)u.o1,
-                                             (float*)u.o2, (uint32_t*)u.oc)
-             : fvdb_streaming_top_k_dev(ctx, (const uint64_t*)u.a, (const float*)u.b, B, n, k, (uint64_t*)u.o1,
-                                        (float*)u.o2, (uint32_t*)u.oc);
+  DBuf a, b, o1, o2, oc;
+  HIPCHK(ctx, a.exact(std::max<size_t>((size_t)B * n * 8, 16)));
+  HIPCHK(ctx, b.exact(std::max<size_t>((size_t)B * n * 4, 16)));
+  HIPCHK(ctx, o1.exact(std::max<size_t>((size_t)B * k * 8, 16)));
+  HIPCHK(ctx, o2.exact(std::max<size_t>((size_t)B * k * 4, 16)));
+  HIPCHK(ctx, oc.exact((size_t)B * 4));
+  HIPCHK(ctx, hipMemcpyAsync(a.p, ids, (size_t)B * n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(b.p, vals, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
+  rc = merge ? fvdb_merge_search_results_dev(ctx, a.as<const uint64_t>(), b.as<const float>(), B, n, k, o1.as<uint64_t>(),
+                                             o2.as<float>(), oc.as<uint32_t>())
+             : fvdb_streaming_top_k_dev(ctx, a.as<const uint64_t>(), b.as<const float>(), B, n, k, o1.as<uint64_t>(),
+                                        o2.as<float>(), oc.as<uint32_t>());
   if (rc) return rc;
   if (k) {
-    HIPCHK(ctx, hipMemcpyAsync(out_ids, u.o1, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(out_vals, u.o2, (size_t)B * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out_ids, o1.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out_vals, o2.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
-  HIPCHK(ctx, hipMemcpyAsync(out_counts, u.oc, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out_counts, oc.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return FVDB_OK;
 }
@@ -2993,11 +2854,11 @@ int fvdb_store_create_ex(fvdb_ctx* ctx, uint32_t d, uint64_t capacity_rows, int 
   s->dpad = ((d + 3) / 4) * 4;  // either element: the row stride stays a multiple of 8 bytes
   s->dtype = (uint32_t)row_dtype;
   s->cap = std::max<uint64_t>(capacity_rows, 64);
-  hipError_t e = hipMalloc(&s->data, s->cap * s->row_bytes());
-  if (e != hipSuccess) {
+  if (s->rows_buf.exact(s->cap * s->row_bytes()) != hipSuccess) {
     delete s;
     FAIL(ctx, FVDB_E_OOM, "store allocation failed");
   }
+  s->data = s->rows_buf.p;
   *out = s;
   return FVDB_OK;
 }
@@ -3006,11 +2867,6 @@ void fvdb_store_destroy(fvdb_store* s) {
   if (!s) return;
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->ctx->stream);
-  if (s->data) (void)hipFree(s->data);
-  s->s_q.release();
-  s->s_cand.release();
-  s->s_out.release();
-  s->s_in.release();
   delete s;
 }
 
@@ -3028,13 +2884,8 @@ int fvdb_store_append(fvdb_store* s, const float* rows, uint64_t n, uint64_t* fi
   if (s->rows + n >= 0xFFFFFFFFull) FAIL(ctx, FVDB_E_UNSUPPORTED, "store limited to 2^32-1 rows");
   if (s->rows + n > s->cap) {
     uint64_t ncap = std::max<uint64_t>(s->rows + n, s->cap + s->cap / 2);
-    void* nd = nullptr;
-    HIPCHK(ctx, hipMalloc(&nd, ncap * s->row_bytes()));
-    if (s->rows)
-      HIPCHK(ctx, hipMemcpyAsync(nd, s->data, s->rows * s->row_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(s->data);
-    s->data = nd;
+    HIPCHK(ctx, grow_keeping(s->rows_buf, ncap * s->row_bytes(), s->rows * s->row_bytes(), /*zero_rest=*/false, ctx->stream));
+    s->data = s->rows_buf.p;
     s->cap = ncap;
   }
   void* dstv = (char*)s->data + s->rows * s->row_bytes();
@@ -3118,15 +2969,18 @@ int fvdb_scorer_create(fvdb_store* s, uint32_t max_B, uint32_t max_C, fvdb_score
   sc->max_B = max_B;
   sc->max_C = max_C;
   const size_t nc = (size_t)max_B * max_C;
-  if (hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&sc->d_q, (size_t)max_B * s->dpad * 4) != hipSuccess ||
-      hipHostMalloc((void**)&sc->h_cand, nc * 4, hipHostMallocMapped) != hipSuccess ||
-      hipHostMalloc((void**)&sc->h_dist, nc * 4, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&sc->d_cand, sc->h_cand, 0) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&sc->d_dist, sc->h_dist, 0) != hipSuccess) {
-    fvdb_scorer_destroy(sc);
+  if (sc->stream.create(hipStreamNonBlocking) != hipSuccess ||
+      sc->q_buf.exact((size_t)max_B * s->dpad * 4) != hipSuccess ||
+      sc->cand_buf.exact(nc * 4, hipHostMallocMapped) != hipSuccess ||
+      sc->dist_buf.exact(nc * 4, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&sc->d_cand, sc->cand_buf.p, 0) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&sc->d_dist, sc->dist_buf.p, 0) != hipSuccess) {
+    delete sc;
     FAIL(ctx, FVDB_E_OOM, "scorer allocation failed");
   }
+  sc->d_q = sc->q_buf.as<float>();
+  sc->h_cand = sc->cand_buf.as<uint32_t>();
+  sc->h_dist = sc->dist_buf.as<float>();
   std::memset(sc->h_cand, 0xFF, nc * 4);
   *out = sc;
   return FVDB_OK;
@@ -3136,12 +2990,6 @@ void fvdb_scorer_destroy(fvdb_scorer* sc) {
   if (!sc) return;
   (void)hipSetDevice(sc->store->ctx->device);
   if (sc->stream) (void)hipStreamSynchronize(sc->stream);
-  if (sc->d_q) (void)hipFree(sc->d_q);
-  if (sc->h_cand) (void)hipHostFree(sc->h_cand);
-  if (sc->h_dist) (void)hipHostFree(sc->h_dist);
-  sc->s_rows.release();
-  sc->s_in.release();
-  if (sc->stream) (void)hipStreamDestroy(sc->stream);
   delete sc;
 }
 

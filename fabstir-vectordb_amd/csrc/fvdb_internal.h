@@ -4,57 +4,17 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dev_owned.h"
+
 #include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
 
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return (T*)p; }
-};
-
-struct HBuf {  // pinned host staging
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 struct fvdb_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevStream stream;  // declared before the buffers: it outlives them
+  DevEvent ev0, ev1;
   int num_cus = 256;
   std::string err;   // last failure; written under err_mu (searches may fail on several host threads)
   std::mutex err_mu;
@@ -88,7 +48,8 @@ struct fvdb_store {
   uint32_t d = 0, dpad = 0;
   uint64_t rows = 0, cap = 0;
   uint32_t dtype = FVDB_F32;  // element of a stored row: FVDB_F32, or FVDB_F16 (rounded to nearest even at append)
-  void* data = nullptr;       // [cap][dpad] of it
+  DBuf rows_buf;              // [cap][dpad] of it
+  void* data = nullptr;       // rows_buf.p, as the kernels' argument lists take it
   bool f16() const { return dtype == FVDB_F16; }
   size_t row_bytes() const { return (size_t)dpad * (f16() ? 2 : 4); }
   DBuf s_q, s_cand, s_out, s_in;
@@ -96,11 +57,13 @@ struct fvdb_store {
 
 struct fvdb_scorer {
   fvdb_store* store = nullptr;
-  hipStream_t stream = nullptr;  // private stream: scorers of different host threads run concurrently
+  DevStream stream;  // private stream: scorers of different host threads run concurrently
   uint32_t max_B = 0, max_C = 0;
-  float* d_q = nullptr;        // [max_B][dpad]
-  uint32_t* h_cand = nullptr;  // pinned, mapped
-  float* h_dist = nullptr;     // pinned, mapped
+  DBuf q_buf;                  // d_q: [max_B][dpad]
+  HBuf cand_buf, dist_buf;     // h_cand, h_dist: pinned, mapped
+  float* d_q = nullptr;        // raw views of the three
+  uint32_t* h_cand = nullptr;
+  float* h_dist = nullptr;
   uint32_t* d_cand = nullptr;  // device aliases of the mapped buffers
   float* d_dist = nullptr;
   DBuf s_rows, s_in;  // private scratch: scorers are driven from different host threads

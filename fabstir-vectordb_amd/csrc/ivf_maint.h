@@ -10,32 +10,8 @@
 
 namespace {
 
-// stream time of one stage: begin() .. end() (end waits for the stage)
-struct StageClock {
-  hipStream_t st;
-  hipEvent_t a = nullptr, b = nullptr;
-  explicit StageClock(hipStream_t s) : st(s) {
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-  }
-  ~StageClock() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void begin() { (void)hipEventRecord(a, st); }
-  float end() {
-    float ms = 0.0f;
-    if (hipEventRecord(b, st) != hipSuccess || hipEventSynchronize(b) != hipSuccess) return 0.0f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-  }
-};
-
 struct DBufs {  // temporaries of one job, freed when it returns
   DBuf tab, hist, total, rank, inv, pos, ids, dx;
-  ~DBufs() {
-    for (DBuf* b : {&tab, &hist, &total, &rank, &inv, &pos, &ids, &dx}) b->release();
-  }
 };
 
 int maint_index_ok(fvdb_ivf* ivf) {
@@ -85,7 +61,7 @@ int build_seq(fvdb_ivf* holder, fvdb_ivf* src, bool compact_dest, DBufs& T, uint
   *host_bytes += tab.size() * 4;
   const uint32_t* d = T.tab.as<uint32_t>();
   hipLaunchKernelGGL(seq_map_kernel, dim3(cdiv((uint64_t)nsb * 64, 256)), dim3(256), 0, ctx->stream, d, d + nsb,
-                     d + 2 * (size_t)nsb + 1, nsb, src->pool.valid, holder->m_seq.as<uint32_t>(),
+                     d + 2 * (size_t)nsb + 1, nsb, src->pool.valid(), holder->m_seq.as<uint32_t>(),
                      compact_dest ? holder->m_dest.as<uint32_t>() : (uint32_t*)nullptr);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // `tab` goes out of scope
@@ -95,36 +71,11 @@ int build_seq(fvdb_ivf* holder, fvdb_ivf* src, bool compact_dest, DBufs& T, uint
 // rows [o, o + B) of the sequence in holder->m_seq -> out[B][d]
 void launch_gather(fvdb_ivf* holder, fvdb_ivf* src, uint64_t o, uint32_t B, float* out) {
   const Pool& P = src->pool;
-  const int mode = P.rm ? GATHER_ROW_MAJOR : (P.esize == 4 ? GATHER_BLOCKED_F32 : GATHER_BLOCKED_F16);
+  const int mode = P.rm() ? GATHER_ROW_MAJOR : (P.esize == 4 ? GATHER_BLOCKED_F32 : GATHER_BLOCKED_F16);
   const uint32_t nch = (uint32_t)(P.block_bytes() / 1024);
-  const void* rows = P.rm ? (const void*)P.rm : (const void*)P.data;
+  const void* rows = P.rm() ? (const void*)P.rm() : (const void*)P.data();
   hipLaunchKernelGGL(gather_seq_rows_kernel, dim3(cdiv((uint64_t)B * nch, 256)), dim3(256), 0, holder->ctx->stream, rows,
                      holder->m_seq.as<uint32_t>() + o, B, src->d, nch, mode, out);
-}
-
-// an empty pool shaped like `like` with exactly `blocks` blocks, every buffer or none.  Nothing is cleared: the move
-// stage writes all 64 lanes of every block, tail lanes as zeros (Pool::reserve says why they must be finite).
-int fresh_pool(fvdb_ctx* ctx, const Pool& like, uint32_t blocks, Pool* out) {
-  Pool p;
-  p.d4 = like.d4;
-  p.esize = like.esize;
-  p.mirror = like.mirror;
-  const size_t bb = p.block_bytes();
-  hipError_t e = hipMalloc(&p.data, (size_t)blocks * bb);
-  if (e == hipSuccess && p.mirror && p.esize == 4) e = hipMalloc((void**)&p.rm, (size_t)blocks * bb);
-  if (e == hipSuccess && p.mirror) e = hipMalloc(&p.half, (size_t)blocks * bb / 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&p.norms, (size_t)blocks * 64 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&p.ids, (size_t)blocks * 64 * sizeof(uint64_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&p.valid, (size_t)blocks * sizeof(uint64_t));
-  if (e != hipSuccess) {
-    p.release();
-    (void)hipGetLastError();
-    ctx->set_err(std::string("second pool for the re-partition: ") + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? FVDB_E_OOM : FVDB_E_HIP;
-  }
-  p.cap_blocks = p.used_blocks = blocks;
-  *out = p;
-  return FVDB_OK;
 }
 
 // The job itself.  The first n rows of src's sequence (dst->m_seq) go to the lists named in dst->m_dest (kMaintNone
@@ -137,7 +88,8 @@ int repartition(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n, uint32_t* out_pos, uin
   const uint32_t nlist = dst->nlist;
   if (nlist > kRankMaxLists)
     FAIL(ctx, FVDB_E_UNSUPPORTED, "re-partition ranks destinations with one LDS counter per list: at most 16384 lists");
-  StageClock clock(ctx->stream);
+  StageTimer<2> clock;
+  HIPCHK(ctx, clock.create());
   std::vector<uint32_t> total(nlist, 0);
   if (n > 0) {
     // tiles of the sequence; the per-tile counts take tiles * nlist * 4 bytes, kept under 256 MiB
@@ -147,7 +99,7 @@ int repartition(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n, uint32_t* out_pos, uin
     HIPCHK(ctx, T.hist.ensure((size_t)tiles * nlist * 4));
     HIPCHK(ctx, T.total.ensure((size_t)nlist * 4));
     HIPCHK(ctx, T.rank.ensure(n * 4));
-    clock.begin();
+    clock.begin(ctx->stream);
     const uint32_t* dest = dst->m_dest.as<uint32_t>();
     hipLaunchKernelGGL(rank_hist_kernel, dim3(tiles), dim3(256), (size_t)nlist * 4, ctx->stream, dest, (uint32_t)n, tile,
                        nlist, T.hist.as<uint32_t>());
@@ -157,7 +109,7 @@ int repartition(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n, uint32_t* out_pos, uin
                        nlist, T.hist.as<uint32_t>(), T.rank.as<uint32_t>());
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(total.data(), T.total.p, (size_t)nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
-    info->ms_ranks += clock.end();
+    info->ms_ranks += clock.end(ctx->stream);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     info->host_bytes += (uint64_t)nlist * 4;
   }
@@ -181,60 +133,52 @@ int repartition(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n, uint32_t* out_pos, uin
       HIPCHK(ctx, dst->d_xmax.ensure(4));
       HIPCHK(ctx, hipMemsetAsync(dst->d_xmax.p, 0, 4, ctx->stream));
     }
-    int rc = fresh_pool(ctx, dst->pool, (uint32_t)blocks, &fresh);
-    if (rc) return rc;
-    // from here on a failure is a HIP error, not a shortage: release the fresh pool and report
-    auto run = [&]() -> int {
-      HIPCHK(ctx, hipMemcpyAsync(T.tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-      info->host_bytes += tab.size() * 4;
-      clock.begin();
-      HIPCHK(ctx, hipMemsetAsync(T.inv.p, 0xFF, blocks * 64 * 4, ctx->stream));
-      const Pool& S = src->pool;
-      hipLaunchKernelGGL(place_rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, dst->m_dest.as<uint32_t>(),
-                         T.rank.as<uint32_t>(), dst->m_seq.as<uint32_t>(), (uint32_t)n, nlist, T.tab.as<uint32_t>(),
-                         T.tab.as<uint32_t>() + nlist, S.ids, (uint32_t)(blocks * 64), (uint32_t)rows_out,
-                         T.inv.as<uint32_t>(), out_pos ? T.pos.as<uint32_t>() : (uint32_t*)nullptr,
-                         out_ids ? T.ids.as<uint64_t>() : (uint64_t*)nullptr);
-      const uint32_t nch = (uint32_t)(S.block_bytes() / 1024);
-      if (S.rm && fresh.rm)
-        hipLaunchKernelGGL(move_rows_rm_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, T.inv.as<uint32_t>(),
-                           (const float4*)S.rm, S.ids, S.norms, S.valid, S.d4, (float4*)fresh.data, (float4*)fresh.rm,
-                           fresh.half, fresh.ids, fresh.norms, fresh.valid);
-      else
-        hipLaunchKernelGGL(move_rows_blocked_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream,
-                           T.inv.as<uint32_t>(), (const uint4*)S.data, S.ids, S.norms, S.valid, nch, (uint4*)fresh.data,
-                           fresh.ids, fresh.norms, fresh.valid);
-      if (dst != src && src->d_xmax.p)
-        hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(64), 0, ctx->stream, src->d_xmax.as<uint32_t>(),
-                           dst->d_xmax.as<uint32_t>());
-      HIPCHK(ctx, hipGetLastError());
-      info->ms_move += clock.end();
-      if (out_pos) HIPCHK(ctx, hipMemcpyAsync(out_pos, T.pos.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-      if (out_ids) HIPCHK(ctx, hipMemcpyAsync(out_ids, T.ids.p, rows_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-      info->host_bytes += (out_pos ? n * 4 : 0) + (out_ids ? rows_out * 8 : 0);
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return FVDB_OK;
-    };
-    rc = run();
-    if (rc) {
-      fresh.release();
-      return rc;
-    }
+    // nothing is cleared: the move stage writes all 64 lanes of every block, tail lanes as zeros (pool_buffers says
+    // why they must be finite)
+    HIPCHK(ctx, pool_buffers(dst->pool, (uint32_t)blocks, /*carry=*/false, ctx->stream, &fresh));
+    // from here on a failure is a HIP error, not a shortage
+    HIPCHK(ctx, hipMemcpyAsync(T.tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    info->host_bytes += tab.size() * 4;
+    clock.begin(ctx->stream);
+    HIPCHK(ctx, hipMemsetAsync(T.inv.p, 0xFF, blocks * 64 * 4, ctx->stream));
+    const Pool& S = src->pool;
+    hipLaunchKernelGGL(place_rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, dst->m_dest.as<uint32_t>(),
+                       T.rank.as<uint32_t>(), dst->m_seq.as<uint32_t>(), (uint32_t)n, nlist, T.tab.as<uint32_t>(),
+                       T.tab.as<uint32_t>() + nlist, S.ids(), (uint32_t)(blocks * 64), (uint32_t)rows_out,
+                       T.inv.as<uint32_t>(), out_pos ? T.pos.as<uint32_t>() : (uint32_t*)nullptr,
+                       out_ids ? T.ids.as<uint64_t>() : (uint64_t*)nullptr);
+    const uint32_t nch = (uint32_t)(S.block_bytes() / 1024);
+    if (S.rm() && fresh.rm())
+      hipLaunchKernelGGL(move_rows_rm_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, T.inv.as<uint32_t>(),
+                         (const float4*)S.rm(), S.ids(), S.norms(), S.valid(), S.d4, (float4*)fresh.data(), (float4*)fresh.rm(),
+                         fresh.half(), fresh.ids(), fresh.norms(), fresh.valid());
+    else
+      hipLaunchKernelGGL(move_rows_blocked_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream,
+                         T.inv.as<uint32_t>(), (const uint4*)S.data(), S.ids(), S.norms(), S.valid(), nch, (uint4*)fresh.data(),
+                         fresh.ids(), fresh.norms(), fresh.valid());
+    if (dst != src && src->d_xmax.p)
+      hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(64), 0, ctx->stream, src->d_xmax.as<uint32_t>(),
+                         dst->d_xmax.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+    info->ms_move += clock.end(ctx->stream);
+    if (out_pos) HIPCHK(ctx, hipMemcpyAsync(out_pos, T.pos.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_ids) HIPCHK(ctx, hipMemcpyAsync(out_ids, T.ids.p, rows_out * 8, hipMemcpyDeviceToHost, ctx->stream));
+    info->host_bytes += (out_pos ? n * 4 : 0) + (out_ids ? rows_out * 8 : 0);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // bytes of the move: the source rows once (through `rm` where the pool keeps it), every representation written
     const size_t bb = fresh.block_bytes();
-    const uint64_t per_block_written = bb * (fresh.rm ? 2 : 1) + (fresh.half ? bb / 2 : 0) + 64 * 12 + 8;
+    const uint64_t per_block_written = bb * (fresh.rm() ? 2 : 1) + (fresh.half() ? bb / 2 : 0) + 64 * 12 + 8;
     info->move_bytes += blocks * per_block_written + rows_out * ((uint64_t)bb / 64 + 12) + blocks * 64 * 4;
   } else if (out_pos && n) {
     std::fill(out_pos, out_pos + n, kMaintNone);
   }
   // swap
   if (blocks > 0) {
-    dst->pool.release();
-    dst->pool = fresh;
+    dst->pool = std::move(fresh);
   } else {  // nothing survives: the lists are empty, the pool keeps its blocks for later appends
     dst->pool.used_blocks = 0;
-    if (dst->pool.valid && dst->pool.cap_blocks)
-      HIPCHK(ctx, hipMemsetAsync(dst->pool.valid, 0, (size_t)dst->pool.cap_blocks * 8, ctx->stream));
+    if (dst->pool.valid() && dst->pool.cap_blocks)
+      HIPCHK(ctx, hipMemsetAsync(dst->pool.valid(), 0, (size_t)dst->pool.cap_blocks * 8, ctx->stream));
   }
   uint32_t b = 0;
   for (uint32_t L = 0; L < nlist; ++L) {
@@ -273,7 +217,7 @@ int fvdb_ivf_compact(fvdb_ivf* ivf, uint64_t* removed, uint64_t* out_ids) {
   rc = build_seq(ivf, ivf, true, T, &ivf->m_info.host_bytes);
   if (rc) return rc;
   rc = repartition(ivf, ivf, n, nullptr, out_ids, T, &ivf->m_info);
-  ivf->m_seq.release();
+  ivf->m_seq.release();  // 8 bytes a row that nothing reads after the job
   ivf->m_dest.release();
   if (rc) return rc;
   finish_info(&ivf->m_info);
@@ -297,15 +241,16 @@ int fvdb_ivf_train_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t max_iterations, u
   rc = build_seq(dst, src, false, T, &dst->m_info.host_bytes);
   if (rc) return rc;
   HIPCHK(ctx, T.dx.ensure(n * dst->d * 4));
-  StageClock clock(ctx->stream);
-  clock.begin();
+  StageTimer<2> clock;
+  HIPCHK(ctx, clock.create());
+  clock.begin(ctx->stream);
   for (uint64_t o = 0; o < n; o += 1u << 20)  // a launch per 2^20 rows keeps the grid far below its limit
     launch_gather(dst, src, o, (uint32_t)std::min<uint64_t>(1u << 20, n - o), T.dx.as<float>() + o * dst->d);
   HIPCHK(ctx, hipGetLastError());
-  dst->m_info.ms_gather += clock.end();
-  clock.begin();
+  dst->m_info.ms_gather += clock.end(ctx->stream);
+  clock.begin(ctx->stream);
   rc = train_resident(dst, T.dx.as<float>(), n, max_iterations, seed, out);
-  dst->m_info.ms_train += clock.end();
+  dst->m_info.ms_train += clock.end(ctx->stream);
   if (rc) return rc;
   dst->coarse_mode = src->coarse_mode;
   dst->scan_mode = src->scan_mode;
@@ -329,17 +274,18 @@ int fvdb_ivf_assign_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t* out_cluster, ui
   rc = build_seq(dst, src, false, T, &dst->m_info.host_bytes);
   if (rc) return rc;
   HIPCHK(ctx, dst->m_dest.ensure(std::max<uint64_t>(n, 1) * 4));
-  StageClock clock(ctx->stream);
+  StageTimer<2> clock;
+  HIPCHK(ctx, clock.create());
   const uint32_t step = 65536;  // assign_dev's own batch: the dense rows of one batch at a time, not the whole matrix
   for (uint64_t o = 0; o < n; o += step) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(step, n - o);
     HIPCHK(ctx, dst->s_in.ensure((size_t)B * dst->d * 4));
-    clock.begin();
+    clock.begin(ctx->stream);
     launch_gather(dst, src, o, B, dst->s_in.as<float>());
-    dst->m_info.ms_gather += clock.end();
-    clock.begin();
+    dst->m_info.ms_gather += clock.end(ctx->stream);
+    clock.begin(ctx->stream);
     rc = assign_dev(dst, dst->s_in.as<float>(), B, dst->m_dest.as<uint32_t>() + o);
-    dst->m_info.ms_assign += clock.end();
+    dst->m_info.ms_assign += clock.end(ctx->stream);
     if (rc) return rc;
   }
   if (n && out_cluster) {
@@ -349,7 +295,7 @@ int fvdb_ivf_assign_from(fvdb_ivf* dst, fvdb_ivf* src, uint32_t* out_cluster, ui
   if (n && out_ids) {
     HIPCHK(ctx, T.ids.ensure(n * 8));
     hipLaunchKernelGGL(gather_ids_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, dst->m_seq.as<uint32_t>(),
-                       src->pool.ids, (uint32_t)n, T.ids.as<uint64_t>());
+                       src->pool.ids(), (uint32_t)n, T.ids.as<uint64_t>());
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out_ids, T.ids.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     dst->m_info.host_bytes += n * 8;
@@ -375,7 +321,7 @@ int fvdb_ivf_refill_from(fvdb_ivf* dst, fvdb_ivf* src, uint64_t n_rows, uint32_t
   HIPCHK(ctx, hipStreamSynchronize(src->ctx->stream));
   DBufs T;
   rc = repartition(dst, src, n_rows, out_pos, nullptr, T, &dst->m_info);
-  dst->m_seq.release();
+  dst->m_seq.release();  // as after a compact
   dst->m_dest.release();
   dst->m_src = nullptr;
   dst->m_rows = 0;

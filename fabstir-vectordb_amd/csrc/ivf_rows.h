@@ -1,7 +1,7 @@
 // ivf_rows.h — host side of the row gathers (kernels_rows.h): fvdb_ivf_get_rows, fvdb_ivf_get_rows_dev,
 // fvdb_ivf_assign_from_store, fvdb_ivf_add_assigned_from_store.  Included at the end of fvdb_hip.cpp, after
 // ivf_maint.h (same translation unit: it works on fvdb_ivf and fvdb_store, leases a scratch set like the blocking
-// searches, and reuses assign_dev, append_staged, StageClock and finish_info).
+// searches, and reuses assign_dev, append_staged and finish_info).
 //
 // A fetch only reads the index: it takes a leased scratch set (its own stream, s_fslots / s_frows), so any number of
 // host threads may fetch beside searches in any slot.  The _from_store pair is a mutation like fvdb_ivf_add: it runs
@@ -19,10 +19,10 @@ void launch_pool_gather(const fvdb_ivf* ivf, hipStream_t st, const uint32_t* slo
   for (uint64_t o = 0; o < n; o += kGatherStep) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
     if (P.esize == 4)
-      hipLaunchKernelGGL(pool_gather_rows_kernel<0>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data, P.rm,
+      hipLaunchKernelGGL(pool_gather_rows_kernel<0>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data(), P.rm(),
                          slots_dev + o, B, ivf->d, nch, out + o * ivf->d);
     else
-      hipLaunchKernelGGL(pool_gather_rows_kernel<1>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data,
+      hipLaunchKernelGGL(pool_gather_rows_kernel<1>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data(),
                          (const float*)nullptr, slots_dev + o, B, ivf->d, nch, out + o * ivf->d);
   }
 }
@@ -60,7 +60,7 @@ int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const 
     launch_pool_gather(ivf, st, S.s_fslots.as<uint32_t>(), n, out);
     HIPCHK(ctx, hipGetLastError());
     if (st != ctx->stream) {
-      if (!S.fetch_done) HIPCHK(ctx, hipEventCreateWithFlags(&S.fetch_done, hipEventDisableTiming));
+      HIPCHK(ctx, S.fetch_done.create(hipEventDisableTiming));
       HIPCHK(ctx, hipEventRecord(S.fetch_done, st));
       HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, S.fetch_done, 0));
     }
@@ -81,12 +81,12 @@ int store_pair_ok(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_t n
 }
 
 // store rows `rows[n]` -> ivf->s_in ([n][d], what fvdb_ivf_assign / _add_assigned upload there); waits for the gather
-int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_t n, StageClock& clock) {
+int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_t n, StageTimer<2>& clock) {
   fvdb_ctx* ctx = ivf->ctx;
   if (s->ctx != ctx) HIPCHK(ctx, hipStreamSynchronize(s->ctx->stream));  // rows written on the store's stream
   HIPCHK(ctx, ivf->s_in.ensure(n * ivf->d * 4));
   HIPCHK(ctx, ivf->s_slots.ensure(n * 4));
-  clock.begin();
+  clock.begin(ctx->stream);
   HIPCHK(ctx, hipMemcpyAsync(ivf->s_slots.p, rows, n * 4, hipMemcpyHostToDevice, ctx->stream));
   for (uint64_t o = 0; o < n; o += kGatherStep) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
@@ -98,7 +98,7 @@ int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_
                          ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
   }
   HIPCHK(ctx, hipGetLastError());
-  ivf->m_info.ms_gather += clock.end();  // waits: `rows` is the caller's, and s_slots is written again by the append
+  ivf->m_info.ms_gather += clock.end(ctx->stream);  // waits: `rows` is the caller's, and s_slots is written again by the append
   ivf->m_info.host_bytes += n * 4;
   return FVDB_OK;
 }
@@ -126,12 +126,13 @@ int fvdb_ivf_assign_from_store(fvdb_ivf* ivf, fvdb_store* store, const uint32_t*
   if (!out_cluster) FAIL(ctx, FVDB_E_INVALID, "null output");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, ivf->s_clusters.ensure(n * 4));
-  StageClock clock(ctx->stream);
+  StageTimer<2> clock;
+  HIPCHK(ctx, clock.create());
   rc = stage_from_store(ivf, store, rows, n, clock);
   if (rc) return rc;
-  clock.begin();
+  clock.begin(ctx->stream);
   rc = assign_dev(ivf, ivf->s_in.as<float>(), n, ivf->s_clusters.as<uint32_t>());
-  ivf->m_info.ms_assign += clock.end();
+  ivf->m_info.ms_assign += clock.end(ctx->stream);
   if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out_cluster, ivf->s_clusters.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -154,12 +155,13 @@ int fvdb_ivf_add_assigned_from_store(fvdb_ivf* ivf, fvdb_store* store, const uin
   for (uint64_t i = 0; i < n; ++i)
     if (cluster[i] >= ivf->nlist) FAIL(ctx, FVDB_E_INVALID, "cluster id out of range");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  StageClock clock(ctx->stream);
+  StageTimer<2> clock;
+  HIPCHK(ctx, clock.create());
   rc = stage_from_store(ivf, store, rows, n, clock);
   if (rc) return rc;
-  clock.begin();
+  clock.begin(ctx->stream);
   rc = append_staged(ivf, ids, n, cluster, out_pos);
-  ivf->m_info.ms_move += clock.end();
+  ivf->m_info.ms_move += clock.end(ctx->stream);
   if (rc) return rc;
   ivf->m_info.host_bytes += n * 4 + (ids ? n * 8 : 0);  // slots up, ids up; positions come from host bookkeeping
   ivf->m_info.rows_in = ivf->m_info.rows_out = n;
