@@ -219,6 +219,7 @@ SIGNATURES = {
     "fvdb_graph_search_dev_slot_masked": (i32, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_graph_scan_allowed_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    "fvdb_graph_search_flat_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_search_quality_lists_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
 }
 

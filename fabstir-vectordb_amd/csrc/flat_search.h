@@ -1,9 +1,11 @@
 // flat_search.h — exact search of the C ABI (include/fvdb.h, "exact search"): the flat scan of a
-// graph's row store and the comparison of two resident id blocks.  Included at the end of fvdb_hip.cpp, after
-// allow_masks.h, for the same reason: the kernels lean on kernels_scan.h, which lives in this translation unit, and what
-// they need of the graph comes through graph_mask_source / graph_scan_inputs (fvdb_internal.h).
+// graph's row store, its form for k up to FVDB_MAX_K_WIDE (section 9q) and the comparison of two resident id blocks.
+// Included at the end of fvdb_hip.cpp, after allow_masks.h, for the same reason: the kernels lean on kernels_scan.h,
+// which lives in this translation unit, and what they need of the graph comes through graph_mask_source /
+// graph_scan_inputs (fvdb_internal.h).
 #pragma once
 #include "kernels_flat.h"
+#include "kernels_flat_wide.h"
 
 namespace {
 
@@ -18,6 +20,15 @@ void launch_flat_scan(fvdb_ctx* ctx, const FlatScanArgs& a, bool f16 /* the stor
   hipLaunchKernelGGL((flat_merge_kernel<KR>), dim3(cdiv(a.B, 4)), dim3(256), 0, ctx->stream, a.part, a.slices, a.B, a.k, out_nodes,
                      out_dist, out_counts);
 }
+
+// the wide form's arena budget, kWideArenaBytes unless FVDB_FLAT_WIDE_ARENA_BYTES says otherwise (read at every call: a
+// test hook that forces several sub-batches on a small graph)
+uint64_t flat_wide_arena_bytes() {
+  const char* e = getenv("FVDB_FLAT_WIDE_ARENA_BYTES");
+  return e ? strtoull(e, nullptr, 10) : kWideArenaBytes;
+}
+
+constexpr int kFlatWideQ = 8;  // queries of a score group (DESIGN.md section 9q has the figures of 8 and 16)
 
 }  // namespace
 
@@ -67,6 +78,64 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
       case 2: launch_flat_scan<8, 2>(ctx, a, s->f16(), on_, od_, oc_); break;
       default: launch_flat_scan<4, 4>(ctx, a, s->f16(), on_, od_, oc_); break;
     }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return FVDB_OK;
+}
+
+int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                         uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
+  if (!g) return FVDB_E_INVALID;
+  GraphMaskSource src{};
+  int rc = graph_mask_source(g, &src);
+  if (rc) return rc;
+  fvdb_store* s = src.store;
+  fvdb_ctx* ctx = on ? on : s->ctx;
+  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
+  if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
+  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
+  if (mask && mask->stamp != src.mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
+  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "exact scan: k must be in 1..FVDB_MAX_K_WIDE");
+  if (!q_dev || !out_nodes_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null argument");
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  constexpr uint32_t Q = kFlatWideQ;
+  const uint32_t n = src.n;
+  const uint32_t tiles = cdiv(n, 64);
+  const uint64_t stride = (uint64_t)tiles * 64;  // arena words of a query; < 2^32 whatever n
+  // queries of a sub-batch: their arena fits the budget, at least one; sub-batches run one after the other on the
+  // stream and share the slot's scratch
+  const uint64_t fit = std::max<uint64_t>(flat_wide_arena_bytes() / std::max<uint64_t>(stride * 4, 1), 1);
+  const uint32_t step = (uint32_t)std::min<uint64_t>(fit, kFlatSubBatch);
+  for (uint32_t b0 = 0; b0 < B; b0 += step) {
+    const uint32_t Bs = std::min(step, B - b0);
+    FlatScoreArgs a{};
+    a.rows = s->data;
+    a.dead = mask ? mask->flags.as<uint32_t>() : src.deleted;
+    a.dpad = s->dpad;
+    a.n = n;
+    a.B = Bs;
+    // flat_scan_kernel's slices: enough (group, slice) waves to fill the device at a small batch
+    a.slices = n ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(tiles, 4), cdiv(4096, cdiv(Bs, Q)))) : 0;
+    a.slice_tiles = a.slices ? cdiv(tiles, a.slices) : 0;
+    if (a.slices) a.slices = cdiv(tiles, a.slice_tiles);
+    a.stride = stride;
+    uint64_t* part = nullptr;
+    rc = graph_scan_inputs(g, ctx, slot, q_dev + (size_t)b0 * s->d, Bs, (size_t)(Bs * stride * 4), &a.queries, &part);
+    if (rc) return rc;
+    a.arena = (uint32_t*)part;
+    if (a.slices)
+      hipLaunchKernelGGL((s->f16() ? flat_score_kernel<Q, half_t> : flat_score_kernel<Q, float>), dim3(cdiv(Bs, Q), cdiv(a.slices, 4)),
+                         dim3(256), 0, ctx->stream, a);
+    FlatSelectArgs sel{};
+    sel.arena = a.arena;
+    sel.stride = stride;
+    sel.n_words = (uint32_t)stride;  // n == 0: no word is read and every row comes out empty
+    sel.k = k;
+    sel.out_nodes = out_nodes_dev + (size_t)b0 * k;
+    sel.out_dist = out_dist_dev + (size_t)b0 * k;
+    sel.out_counts = out_counts_dev + b0;
+    hipLaunchKernelGGL(flat_select_kernel, dim3(Bs), dim3(kWideSelThreads), 0, ctx->stream, sel);
     HIPCHK(ctx, hipGetLastError());
   }
   return FVDB_OK;

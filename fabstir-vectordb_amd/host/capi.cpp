@@ -219,6 +219,25 @@ int fvh_hnsw_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32
   if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
   return FVDB_OK;
 }
+// the same three at k up to FVDB_MAX_K_WIDE
+int fvh_hnsw_search_exact_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact_wide(q, B, d, k, ids, dist, counts);
+}
+int fvh_hnsw_search_exact_wide_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, const uint64_t* allowed,
+                                       uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact_wide_allowed(q, B, d, k, allowed, n_allowed, ids, dist, counts);
+}
+int fvh_hnsw_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, float* out3,
+                                          uint64_t* queries_evaluated) {
+  SearchQuality s{};
+  const int rc = ((HNSWIndex*)p)->evaluate_search_quality_wide(q, B, d, k, ef, &s);
+  if (rc) return rc;
+  out3[0] = s.avg_recall;
+  out3[1] = s.avg_precision;
+  out3[2] = s.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
+  return FVDB_OK;
+}
 void fvh_hnsw_set_scan_cutoff(void* p, uint64_t nodes) { ((HNSWIndex*)p)->set_scan_cutoff(nodes); }
 uint64_t fvh_hnsw_scan_cutoff(void* p) { return ((HNSWIndex*)p)->scan_cutoff(); }
 void* fvh_hnsw_device_graph(void* p) { return ((HNSWIndex*)p)->device_graph(); }
@@ -361,6 +380,30 @@ int fvh_hybrid_evaluate_search_quality(void* p, const float* q, uint32_t B, uint
   c.ivf_n_probe = nprobe;
   SearchQuality s{};
   const int rc = ((HybridIndex*)p)->evaluate_search_quality(q, B, d, c, now, &s);
+  if (rc) return rc;
+  out3[0] = s.avg_recall;
+  out3[1] = s.avg_precision;
+  out3[2] = s.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
+  return FVDB_OK;
+}
+// the same two at k up to FVDB_MAX_K_WIDE
+int fvh_hybrid_search_exact_wide(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, int search_recent, int search_historical,
+                                 double now, uint64_t* ids, float* dist, uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_exact_wide(q, B, d, c, now, ids, dist, counts);
+}
+int fvh_hybrid_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
+                                            double now, float* out3, uint64_t* queries_evaluated) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = ef;
+  c.ivf_n_probe = nprobe;
+  SearchQuality s{};
+  const int rc = ((HybridIndex*)p)->evaluate_search_quality_wide(q, B, d, c, now, &s);
   if (rc) return rc;
   out3[0] = s.avg_recall;
   out3[1] = s.avg_precision;

@@ -378,7 +378,8 @@ class HNSWIndex {
     const uint64_t* allowed = nullptr;
     uint64_t n_allowed = 0;
     uint32_t slot = 0;                      // stream, scratch set and result block
-    bool owns_slot = false;                 // the caller holds `slot` for the call (HybridIndex's lease): run() takes no lock
+    bool wide = false;                      // kExact only: k up to FVDB_MAX_K_WIDE, fvdb_graph_search_flat_wide_dev_slot
+    bool owns_slot = false;                // the caller holds `slot` for the call (HybridIndex's lease): run() takes no lock
     // filled in by admit() and stage()
     ViewRef held = nullptr;                 // keeps a by_list view alive
     enum Route { kAnswered, kHostWalk, kDevice } route = kAnswered;
@@ -427,6 +428,17 @@ class HNSWIndex {
   // search(k, ef) against search_exact(k): the reference's recall / precision (src/ivf/operations.rs:329-391 applied
   // to the graph).  B == 0 is FVDB_E_INVALID.
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
+  // The same four with k in 1..FVDB_MAX_K_WIDE: the rows scored by the same fold, the k best
+  // chosen by the wide selection (fvdb_graph_search_flat_wide_dev_slot) — at k <= FVDB_MAX_K exactly what the calls
+  // above return.  They replace nothing above: search_exact and its kin keep their limit, as fvdb_ivf_search kept its
+  // own when fvdb_ivf_search_wide arrived.  evaluate_search_quality_wide: search(k, ef) returns at most ef rows.
+  int search_exact_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts);
+  int search_exact_wide_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
+                                uint64_t* ids, float* dist, uint32_t* counts);
+  int search_exact_wide_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                            float* dist, uint32_t* counts, uint32_t slot);
+  int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
+  int quality_impl(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out, bool wide);  // both forms
   // 0 = never scan, UINT64_MAX = always.  The default is a guess nobody has measured.
   void set_scan_cutoff(uint64_t nodes) { scan_cutoff_ = nodes; }
   uint64_t scan_cutoff() const { return scan_cutoff_; }
@@ -762,6 +774,13 @@ class HybridIndex {
   // rows.  B == 0 is FVDB_E_INVALID.
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
                               SearchQuality* out);
+  // The same two with k in 1..FVDB_MAX_K_WIDE: the recent part from the graph's wide exact scan
+  // (recent_k and historical_k up to FVDB_MAX_K_WIDE as well, else FVDB_E_UNSUPPORTED); migration step, read lock,
+  // merge and the sharded refusal are search_exact's.  At k <= FVDB_MAX_K they return what the two above return.
+  int search_exact_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                        float* dist, uint32_t* counts);
+  int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
+                                   SearchQuality* out);
   // Concurrency (reference: tokio RwLock, searches = readers, src/hybrid/core.rs:457,466): search() / search_dev() /
   // search_with_filter() may be called from any number of host threads; each call leases a free slot (stream,
   // traversal state, IVF scratch set, result blocks) and returns it.  Mutations wait for those calls to finish.
@@ -842,8 +861,14 @@ class HybridIndex {
   // search_impl / search_exact after the migration step, the caller holding the read side of rw_
   int search_locked(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids,
                     float* dist, uint32_t* counts, const uint64_t* allowed, uint64_t n_allowed, bool masked);
+  // wide: the graph's wide exact scan, part sizes up to FVDB_MAX_K_WIDE
   int exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
-                   uint32_t* counts);
+                   uint32_t* counts, bool wide = false);
+  // search_exact / search_exact_wide and evaluate_search_quality / _wide: one body each, `wide` choosing the limit of k
+  int exact_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids, float* dist,
+                 uint32_t* counts, bool wide);
+  int quality_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, SearchQuality* out,
+                   bool wide);
   std::mutex qual_mu_;  // evaluate_search_quality's staging block
   DevBuf qual_;
   // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl

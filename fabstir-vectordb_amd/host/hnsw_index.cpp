@@ -477,7 +477,7 @@ struct WalkBlock {
 int HNSWIndex::admit(Search& s) {
   s.route = Search::kAnswered;
   const bool exact = s.kind == Search::kExact, filtered = s.by_list || s.view, nothing = s.B == 0 || s.k == 0;
-  if (exact && (s.k == 0 || s.k > FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
+  if (exact && (s.k == 0 || s.k > (s.wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K))) return FVDB_E_UNSUPPORTED;
   if (exact && s.slot >= kSlots) return FVDB_E_INVALID;  // a traversal's slot is launch()'s to refuse, after all of this
   if (s.ids) fill_empty(s.ids, s.dist, s.counts, s.B, s.k);
   // empty index -> empty results (:404-407); the exact scan needs the store too (a graph that has never held a row)
@@ -526,7 +526,8 @@ int HNSWIndex::launch(Search& s) {
   fvdb_ctx* on = s.slot == 0 ? nullptr : sl.ctx;
   fvdb_mask* mask = s.view ? s.view->mask.get() : nullptr;
   if (s.kind == Search::kExact)
-    rc = fvdb_graph_search_flat_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, s.k, d.nodes, d.dist, d.counts);
+    rc = (s.wide ? fvdb_graph_search_flat_wide_dev_slot : fvdb_graph_search_flat_dev_slot)(graph_, on, s.slot, mask, s.q_dev, s.B, s.k,
+                                                                                          d.nodes, d.dist, d.counts);
   else if (!s.view)
     rc = fvdb_graph_search_dev_slot(graph_, on, s.slot, s.q_dev, s.B, s.k, s.ef, d.nodes, d.dist, d.counts, d.status);
   else if (s.scanned)
@@ -855,9 +856,38 @@ int HNSWIndex::search_exact_allowed(const float* q, uint32_t B, uint32_t dim, ui
   return run(s);
 }
 
+// ---- the same at k up to FVDB_MAX_K_WIDE: the request's `wide` flag and nothing else ----
+int HNSWIndex::search_exact_wide_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                                     float* dist, uint32_t* counts, uint32_t slot) {
+  Search s{Search::kExact, q_dev, true, B, dim, k, 0, ids, dist, counts};
+  s.view = view, s.slot = slot, s.owns_slot = true, s.wide = true;
+  return run(s);
+}
+
+int HNSWIndex::search_exact_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  s.wide = true;
+  return run(s);
+}
+
+int HNSWIndex::search_exact_wide_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed,
+                                         uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed, s.wide = true;
+  return run(s);
+}
+
 int HNSWIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out) {
+  return quality_impl(q, B, dim, k, ef, out, false);
+}
+
+int HNSWIndex::evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out) {
+  return quality_impl(q, B, dim, k, ef, out, true);
+}
+
+int HNSWIndex::quality_impl(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out, bool wide) {
   if (B == 0 || !q || !out) return FVDB_E_INVALID;  // "No test queries provided" (operations.rs:334-338)
-  if (k == 0 || k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (k == 0 || k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
   if (has_dim_ && dim != dim_) return FVDB_E_DIM;
   const auto start = std::chrono::steady_clock::now();
   const size_t n = (size_t)B * k;
@@ -866,7 +896,9 @@ int HNSWIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim,
   std::vector<uint32_t> rcn(B), tcn(B);
   int rc;
   if ((rc = search(q, B, dim, k, ef, rid.data(), rd.data(), rcn.data()))) return rc;
-  if ((rc = search_exact(q, B, dim, k, tid.data(), td.data(), tcn.data()))) return rc;
+  if ((rc = (wide ? search_exact_wide(q, B, dim, k, tid.data(), td.data(), tcn.data())
+                  : search_exact(q, B, dim, k, tid.data(), td.data(), tcn.data()))))
+    return rc;
   float tr = 0.0f, tp = 0.0f;
   {
     std::lock_guard<std::mutex> serial(search_mu_);  // qual_ is one block: calls take turns

@@ -921,7 +921,7 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
 // The two exact parts and the usual merge; the caller holds the read side of rw_.  The graph's scan runs in a slot leased
 // for the call (its stream, its scratch, its result block), the every-list search in a scratch set the engine leases.
 int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
-                              uint32_t* counts) {
+                              uint32_t* counts, bool wide) {
   const uint32_t k = (uint32_t)cfg.k;
   const uint32_t rk = cfg.rk(), hk = cfg.hk();
   if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;  // whichever parts are searched, and before any other refusal
@@ -930,17 +930,20 @@ int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const Hy
   std::vector<uint32_t> rc_(B, 0), hc(B, 0);
   const bool have_r = cfg.search_recent, have_h = cfg.search_historical && ivf_trained_;
   if (have_r) {
-    if (rk > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+    if (rk > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
     rid.resize((size_t)B * rk);
     rd.resize((size_t)B * rk);
     Lease lease(this, Lease::kAnyFree, Lease::kTake);
     Slot& sl = *lease.sl;
     int rc;
     if ((rc = stage_finite(sl, q, B, dim))) return rc;
-    if ((rc = recent_->search_exact_dev((const float*)sl.d_q.dev, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())))
+    const float* qd = (const float*)sl.d_q.dev;
+    if ((rc = wide ? recent_->search_exact_wide_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())
+                   : recent_->search_exact_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())))
       return rc;
   }
   if (have_h) {
+    if (wide && hk > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
     hid.resize((size_t)B * hk);
     hd.resize((size_t)B * hk);
     // search_with_config(q, k, n_clusters): every list, in centroid-rank order (the any-nprobe route where it applies)
@@ -952,21 +955,42 @@ int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const Hy
 
 int HybridIndex::search_exact(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
                               float* dist, uint32_t* counts) {
+  return exact_impl(q, B, dim, cfg, now, ids, dist, counts, false);
+}
+
+// the same search with the recent part from the graph's wide exact scan
+int HybridIndex::search_exact_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                                   float* dist, uint32_t* counts) {
+  return exact_impl(q, B, dim, cfg, now, ids, dist, counts, true);
+}
+
+int HybridIndex::exact_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                            float* dist, uint32_t* counts, bool wide) {
   if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // a rank holds only the lists it owns
   const uint32_t k = (uint32_t)cfg.k;
-  if (cfg.k == 0 || cfg.k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (cfg.k == 0 || cfg.k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0) return FVDB_OK;
   if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);
-  return exact_locked(q, B, dim, cfg, ids, dist, counts);
+  return exact_locked(q, B, dim, cfg, ids, dist, counts, wide);
 }
 
 int HybridIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
                                          SearchQuality* out) {
+  return quality_impl(q, B, dim, cfg, now, out, false);
+}
+
+int HybridIndex::evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
+                                              SearchQuality* out) {
+  return quality_impl(q, B, dim, cfg, now, out, true);
+}
+
+int HybridIndex::quality_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, SearchQuality* out,
+                              bool wide) {
   if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;
   if (B == 0 || !q || !out) return FVDB_E_INVALID;  // "No test queries provided" (src/ivf/operations.rs:334-338)
-  if (cfg.k == 0 || cfg.k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (cfg.k == 0 || cfg.k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
   if (!initialized_) return FVDB_E_INVALID;
   const uint32_t k = (uint32_t)cfg.k;
   const auto start = std::chrono::steady_clock::now();
@@ -982,7 +1006,7 @@ int HybridIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t di
     fill_empty(tid.data(), td.data(), tcn.data(), B, k);
     int rc;
     if ((rc = search_locked(q, false, B, dim, cfg, rid.data(), rd.data(), rcn.data(), nullptr, 0, false))) return rc;
-    if ((rc = exact_locked(q, B, dim, cfg, tid.data(), td.data(), tcn.data()))) return rc;
+    if ((rc = exact_locked(q, B, dim, cfg, tid.data(), td.data(), tcn.data(), wide))) return rc;
     std::lock_guard<std::mutex> lk(qual_mu_);
     if ((rc = compare_id_blocks(ctx_ivf_, qual_, B, k, rid.data(), rcn.data(), tid.data(), tcn.data(), &tr, &tp))) return rc;
   }

@@ -164,6 +164,12 @@ HOST_SIGNATURES = {
     "fvh_hnsw_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
     "fvh_hybrid_search_exact": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
+    # the same at k up to 4096
+    "fvh_hnsw_search_exact_wide": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
+    "fvh_hnsw_search_exact_wide_allowed": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvh_hnsw_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
+    "fvh_hybrid_search_exact_wide": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
+    "fvh_hybrid_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
     # one allow-set per query
     "fvh_ivf_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
     "fvh_hnsw_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
@@ -649,6 +655,22 @@ class HNSWIndex(_Base):
         f32 in query order."""
         return self._quality(self.lib.fvh_hnsw_evaluate_search_quality, queries, int(k), int(ef))
 
+    def search_exact_wide(self, queries, k):
+        """search_exact() with k in 1..4096: the same rows scored by the same fold, the k best
+        chosen by the wide selection.  For k <= 256 it returns exactly what search_exact() returns; that call keeps its
+        limit and its faster register list."""
+        return self._search(self.lib.fvh_hnsw_search_exact_wide, queries, k)
+
+    def search_exact_wide_allowed(self, queries, k, allowed):
+        """search_exact_wide() among the nodes whose id is in `allowed` (the cached mask of search_allowed)."""
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_hnsw_search_exact_wide_allowed, queries, k, _ptr(a, u64p), a.size)
+
+    def evaluate_search_quality_wide(self, queries, k, ef):
+        """evaluate_search_quality() with k in 1..4096: search(k, ef), which returns at most ef rows, against
+        search_exact_wide(k); the same formulas."""
+        return self._quality(self.lib.fvh_hnsw_evaluate_search_quality_wide, queries, int(k), int(ef))
+
     @property
     def scan_cutoff(self):
         return int(self.lib.fvh_hnsw_scan_cutoff(self.h))
@@ -1074,6 +1096,19 @@ class HybridIndex(_Base):
         self._refuse_when_sharded("evaluate_search_quality")
         return self._quality(self.lib.fvh_hybrid_evaluate_search_quality, queries, int(k), int(hnsw_ef), int(ivf_n_probe),
                              float(now))
+
+    def search_exact_wide(self, queries, k, now=0.0, search_recent=True, search_historical=True):
+        """search_exact() with k in 1..4096: the recent part from the graph's wide exact scan, the
+        rest — migration step, read lock, every-list search, merge, the sharded refusal — as there."""
+        self._refuse_when_sharded("search_exact_wide")
+        return self._search(self.lib.fvh_hybrid_search_exact_wide, queries, k, int(search_recent), int(search_historical),
+                            float(now))
+
+    def evaluate_search_quality_wide(self, queries, k, now=0.0, hnsw_ef=50, ivf_n_probe=10):
+        """evaluate_search_quality() with k in 1..4096: search() against search_exact_wide() under one hold of the lock."""
+        self._refuse_when_sharded("evaluate_search_quality_wide")
+        return self._quality(self.lib.fvh_hybrid_evaluate_search_quality_wide, queries, int(k), int(hnsw_ef),
+                             int(ivf_n_probe), float(now))
 
     _FILTER_FN = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_void_p)
 

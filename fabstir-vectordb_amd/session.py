@@ -194,6 +194,17 @@ class VectorDbSession:
             raise SessionError(
                 f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
         threshold = np.float32(options.get("threshold", 0.0))
+        # "exact" (not in the reference): the k nearest resident rows exactly — HybridIndex.search_exact, or its wide form
+        # above 256 — in place of the graph walk and the n_probe nearest lists
+        if options.get("exact"):
+            if options.get("filter") is not None:
+                raise SessionError('"exact" and "filter" cannot be combined: an exact filtered search is not available')
+            try:
+                exact = self.index.search_exact if int(k) <= 256 else self.index.search_exact_wide
+                res = exact(q.reshape(1, -1), int(k), now=self.now)
+            except Exception as e:
+                raise SessionError(f"Search failed: {e}") from e
+            return self._results_of(res[0], threshold, bool(options.get("includeVectors", False)))
         flt = None
         if options.get("filter") is not None:  # session.rs:233-247
             try:
@@ -307,6 +318,30 @@ class VectorDbSession:
                 for i, o in enumerate(options_list)]
 
     searchMany = search_many
+
+    def evaluate_search_quality(self, queries, k, options=None):
+        """Recall and precision of search() against the exact search over the same resident rows (no counterpart in the
+        reference's session): HybridIndex.evaluate_search_quality, or its wide form above k = 256, at search()'s
+        settings (ef 50, n_probe 10) unless options "hnswEf" / "ivfNProbe" say otherwise.  Returns avg_recall,
+        avg_precision, avg_query_time_ms, queries_evaluated."""
+        if self.destroyed:
+            raise SessionError("Session already destroyed")
+        options = options or {}
+        qs = [js_array_to_vec_f32(qv) for qv in queries]
+        for q in qs:
+            if self.vector_dimension is not None and q.size != self.vector_dimension:
+                raise SessionError(
+                    f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+        if not qs:
+            raise SessionError("Evaluation failed: No test queries provided")
+        try:
+            fn = self.index.evaluate_search_quality if int(k) <= 256 else self.index.evaluate_search_quality_wide
+            return fn(np.stack(qs), int(k), now=self.now, hnsw_ef=int(options.get("hnswEf", 50)),
+                      ivf_n_probe=int(options.get("ivfNProbe", 10)))
+        except Exception as e:
+            raise SessionError(f"Evaluation failed: {e}") from e
+
+    evaluateSearchQuality = evaluate_search_quality
 
     def delete_vector(self, id):
         vid = VectorId(id)

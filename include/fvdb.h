@@ -771,6 +771,18 @@ int fvdb_graph_scan_allowed_groups_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_
  * sub-batches on the stream so the partial lists in the slot's scratch stay bounded. */
 int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                     uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev);
+/* The same search with 1 <= k <= FVDB_MAX_K_WIDE.  Same result definition, arguments, outputs,
+ * mask, slot, stream and staleness rules, and the same refusals in the same order; k == 0 or k > FVDB_MAX_K_WIDE is
+ * FVDB_E_UNSUPPORTED.  Replaces nothing: fvdb_graph_search_flat_dev_slot keeps its limit and its register list, as
+ * fvdb_ivf_search kept its own beside fvdb_ivf_search_wide.  The rows are scored by the same fold; each distance word
+ * goes to a per-query arena in the slot's scratch (4 bytes per node, padded to whole 64-row tiles) and the k best are
+ * found by the wide selection of fvdb_ivf_search_wide — radix select of the k-th word, ties at the cut in node order —
+ * so for k <= FVDB_MAX_K it returns exactly what fvdb_graph_search_flat_dev_slot returns.  Always this route, whatever
+ * k.  Queries go in sub-batches whose arena fits 1 GiB (FVDB_FLAT_WIDE_ARENA_BYTES in the environment, read at every
+ * call, overrides the figure; a sub-batch holds at least one query), one after the other on the stream. */
+int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                         uint32_t B, uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev,
+                                         uint32_t* out_counts_dev);
 /* The comparison of fvdb_ivf_search_quality_dev on two id blocks the caller holds in HBM (B x k ids with their hit
  * counts; entries at or beyond a count are not read): per query matches, recall and precision by the formulas stated
  * there — an id the result holds twice counts twice — to out_recall_dev[B] / out_precision_dev[B], enqueued on ctx's

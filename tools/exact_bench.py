@@ -12,6 +12,14 @@ and whether the three answers are identical (ids and distance bits).
 The scan reads rows and liveness flags, never links, so the graph is installed with restore() as a ring: the rows get
 into the store the way a restored index's do, without a million sequential inserts.
 
+With --route (wide | register | copy, repeatable) the tool times just those routes of DESIGN.md section 9q instead, and
+--k may then exceed 256 on the wide and copy routes:
+  wide      HNSWIndex.search_exact_wide: the same tile scan writing a distance arena, then the wide selection
+  register  HNSWIndex.search_exact (k <= 256)
+  copy      the one-list copy, searched with search_all at k <= 256 and with search_wide above; its build time apart
+The routes named are warmed once each and then timed in turn, route after route within every repeat, so that a drift of
+the machine falls on all of them alike.
+
 Every path is warmed with one untimed call (graph upload, scratch, pinned buffers, the allowed route's mask build), then
 timed --repeat times; median, minimum and maximum are reported.  Each row element runs in a child process of its own
 under a time limit; the first failure stops the run.  A tree without search_exact (the parent commit) reports the two
@@ -59,6 +67,8 @@ def child(a):
     g = fv.HNSWIndex(ctx, 4, 8, 16, row_dtype=dtype)
     g.restore(ids, x, np.zeros(n, np.uint32), np.arange(n + 1, dtype=np.uint64), np.roll(ids, -1), 0)
     answers = {}
+    if a.route:
+        return routes(a, ctx, fv, g, x, ids, q, out)
     if hasattr(g, "search_exact"):
         r, t = timed(lambda: g.search_exact(q, k), a.repeat)
         t["rows_x_queries_per_s"] = n * B / (t["ms_median"] * 1e-3)
@@ -93,17 +103,69 @@ def child(a):
     print(json.dumps(out), flush=True)
 
 
+def routes(a, ctx, fv, g, x, ids, q, out):
+    """--route: the named routes of section 9q, timed in turn within every repeat"""
+    n, d, k, B = a.n, a.d, a.k, a.batch
+    fns, flat = {}, None
+    for name in a.route:
+        if name == "wide":
+            fns[name] = lambda: g.search_exact_wide(q, k)
+        elif name == "register":
+            fns[name] = lambda: g.search_exact(q, k)
+        else:
+            ctx.device_synchronize()
+            t0 = time.perf_counter()
+            flat = fv.DeviceIVF(ctx, d, 1, dtype=a.dtype)
+            flat.set_centroids(np.zeros((1, d), np.float32))
+            for c in range(0, n, 200_000):
+                flat.add_assigned(x[c:c + 200_000], ids[c:c + 200_000], np.zeros(min(200_000, n - c), np.uint32))
+            ctx.device_synchronize()
+            out["copy_build_ms"] = (time.perf_counter() - t0) * 1e3
+            out["copied_bytes"] = int(n) * d * 4
+            fns[name] = (lambda: flat.search_all(q, k)) if k <= 256 else (lambda: flat.search_wide(q, k, 1))
+    answers, ms = {}, {name: [] for name in fns}
+    for i in range(a.repeat + 1):  # the first round is the warm-up
+        for name, fn in fns.items():
+            ctx.device_synchronize()
+            t0 = time.perf_counter()
+            r = fn()
+            ctx.device_synchronize()
+            if i:
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+            answers[name] = (r.ids, r.distances, r.counts) if hasattr(r, "ids") else (r[0], r[1], r[2])
+    out["routes"] = {}
+    for name, v in ms.items():
+        v.sort()
+        out["routes"][name] = dict(ms_median=v[len(v) // 2], ms_min=v[0], ms_max=v[-1], runs=len(v),
+                                   rows_x_queries_per_s=n * B / (v[len(v) // 2] * 1e-3))
+    names = list(answers)
+    first = answers[names[0]]
+    out["identical"] = all(np.array_equal(first[0], answers[m][0]) and np.array_equal(first[2], answers[m][2]) and
+                           np.array_equal(np.ascontiguousarray(first[1]).view(np.uint32),
+                                          np.ascontiguousarray(answers[m][1]).view(np.uint32)) for m in names[1:])
+    out["compared"] = names
+    if flat is not None:
+        flat.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=200_000)
     ap.add_argument("--d", type=int, default=384)
-    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--k", type=int, default=10, help="may exceed 256 with --route wide / copy")
+    ap.add_argument("--route", action="append", choices=["wide", "register", "copy"], default=None,
+                    help="time only this route (repeatable): the routes of DESIGN.md section 9q")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--repeat", type=int, default=9, help="timed runs per path, after one warm-up")
     ap.add_argument("--repeat-allowed", type=int, default=3, help="timed runs of the gather scan (slow), after one warm-up")
     ap.add_argument("--step-timeout", type=int, default=600, help="seconds one row element may take")
     ap.add_argument("--dtype", default=None, help="(child) run this one row element in this process")
     a = ap.parse_args()
+    if a.route and "register" in a.route and a.k > 256:
+        ap.error("--route register takes k <= 256")
+    if not a.route and a.k > 256:
+        ap.error("k > 256 needs --route wide and / or --route copy")
     if a.dtype is not None:
         return child(a)
     for dtype in ("f32", "f16"):
@@ -111,6 +173,8 @@ def main():
         for name in ("n", "d", "k", "batch", "repeat"):
             cmd += [f"--{name}", str(getattr(a, name))]
         cmd += ["--repeat-allowed", str(a.repeat_allowed)]
+        for r in a.route or []:
+            cmd += ["--route", r]
         try:
             rc = subprocess.run(cmd, timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
