@@ -221,6 +221,8 @@ SIGNATURES = {
     "fvdb_graph_search_flat_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_search_quality_lists_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
+    # search quality over a grid of ef and n_probe
+    "fvdb_quality_grid_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]),
 }
 
 _lib = None

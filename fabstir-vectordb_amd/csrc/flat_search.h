@@ -1,11 +1,13 @@
 // flat_search.h — exact search of the C ABI (include/fvdb.h, "exact search"): the flat scan of a
-// graph's row store, its form for k up to FVDB_MAX_K_WIDE (section 9q) and the comparison of two resident id blocks.
+// graph's row store, its form for k up to FVDB_MAX_K_WIDE (section 9q), the comparison of two resident id blocks and
+// the quality grid over the parts of a hybrid search (section 9r).
 // Included at the end of fvdb_hip.cpp, after allow_masks.h, for the same reason: the kernels lean on kernels_scan.h,
 // which lives in this translation unit, and what they need of the graph comes through graph_mask_source /
 // graph_scan_inputs (fvdb_internal.h).
 #pragma once
 #include "kernels_flat.h"
 #include "kernels_flat_wide.h"
+#include "kernels_grid.h"
 
 namespace {
 
@@ -152,6 +154,49 @@ int fvdb_search_quality_lists_dev(fvdb_ctx* ctx, const uint64_t* res_ids_dev, co
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(search_quality_kernel, dim3(cdiv(B, 4)), dim3(256), 0, ctx->stream, res_ids_dev, res_counts_dev, truth_ids_dev,
                      truth_counts_dev, B, k, out_recall_dev, out_precision_dev);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// kernels_grid.h: the flags of every list against the truth, then one lane per (ef, n_probe, query).  The lists'
+// prefix counts live in the context's own scratch: calls on one context take turns here and run in stream order.
+int fvdb_quality_grid_dev(fvdb_ctx* ctx, const uint64_t* truth_ids_dev, const uint32_t* truth_counts_dev,
+                          const uint64_t* recent_ids_dev, const float* recent_dist_dev, const uint32_t* recent_counts_dev,
+                          const uint64_t* hist_ids_dev, const float* hist_dist_dev, const uint32_t* hist_counts_dev, uint32_t B,
+                          uint32_t k, uint32_t rk, uint32_t hk, uint32_t E, uint32_t P, float* out_recall_dev,
+                          float* out_precision_dev) {
+  if (!ctx) return FVDB_E_INVALID;
+  if (!truth_ids_dev || !truth_counts_dev || !out_recall_dev || !out_precision_dev) FAIL(ctx, FVDB_E_INVALID, "null buffer");
+  if (E == 0 && P == 0) FAIL(ctx, FVDB_E_INVALID, "quality grid: no recent and no historical lists");
+  if (E && (!recent_ids_dev || !recent_dist_dev || !recent_counts_dev)) FAIL(ctx, FVDB_E_INVALID, "null recent block");
+  if (P && (!hist_ids_dev || !hist_dist_dev || !hist_counts_dev)) FAIL(ctx, FVDB_E_INVALID, "null historical block");
+  if (E > kGridMaxPoints || P > kGridMaxPoints) FAIL(ctx, FVDB_E_UNSUPPORTED, "quality grid: at most 64 ef and 64 n_probe values");
+  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "quality grid: k must be in 1..FVDB_MAX_K_WIDE");
+  if (E && (rk == 0 || rk > FVDB_MAX_K_WIDE)) FAIL(ctx, FVDB_E_UNSUPPORTED, "quality grid: recent k must be in 1..FVDB_MAX_K_WIDE");
+  if (P && (hk == 0 || hk > FVDB_MAX_K_WIDE)) FAIL(ctx, FVDB_E_UNSUPPORTED, "quality grid: historical k must be in 1..FVDB_MAX_K_WIDE");
+  if (B == 0) return FVDB_OK;
+  const uint64_t pairs = (uint64_t)std::max(E, 1u) * std::max(P, 1u) * B;
+  if (B > 0x7FFFFFFFu || pairs > (1ull << 38)) FAIL(ctx, FVDB_E_UNSUPPORTED, "quality grid: batch too large for one call");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t g_words = (size_t)E * B * (rk + 1), h_words = (size_t)P * B * (hk + 1);
+  std::lock_guard<std::mutex> lk(ctx->grid_mu);  // both kernels are on the stream before another call may grow the block
+  HIPCHK(ctx, ctx->s_grid.ensure((g_words + h_words) * 4));
+  GridArgs a{};
+  a.t_ids = truth_ids_dev;
+  a.t_cnt = truth_counts_dev;
+  a.g_ids = E ? recent_ids_dev : nullptr;
+  a.g_dist = E ? recent_dist_dev : nullptr;
+  a.g_cnt = E ? recent_counts_dev : nullptr;
+  a.h_ids = P ? hist_ids_dev : nullptr;
+  a.h_dist = P ? hist_dist_dev : nullptr;
+  a.h_cnt = P ? hist_counts_dev : nullptr;
+  a.B = B, a.k = k, a.rk = rk, a.hk = hk, a.E = E, a.P = P;
+  a.g_pfx = ctx->s_grid.as<uint32_t>();
+  a.h_pfx = a.g_pfx + g_words;
+  a.recall = out_recall_dev;
+  a.precision = out_precision_dev;
+  hipLaunchKernelGGL(grid_flags_kernel, dim3(B), dim3(kGridThreads), 0, ctx->stream, a);
+  hipLaunchKernelGGL(grid_pairs_kernel, dim3(cdiv(pairs, 256)), dim3(256), 0, ctx->stream, a);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }

@@ -23,6 +23,8 @@ struct fvdb_ctx {
     err = std::move(m);
   }
   HBuf h_stage;     // host->device staging for host-pointer entry points
+  DBuf s_grid;      // fvdb_quality_grid_dev: the lists' prefix counts; grown and handed to the stream under grid_mu
+  std::mutex grid_mu;
   int profiling = 0;
 };
 

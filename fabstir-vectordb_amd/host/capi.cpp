@@ -238,6 +238,22 @@ int fvh_hnsw_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, u
   if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
   return FVDB_OK;
 }
+// search quality over a grid: the figures of `g` into the caller's arrays, rows x cols floats each
+static int grid_out(const QualityGrid& g, float* out_recall, float* out_precision, float* out_ms, uint64_t* queries_evaluated) {
+  std::memcpy(out_recall, g.avg_recall.data(), g.avg_recall.size() * 4);
+  std::memcpy(out_precision, g.avg_precision.data(), g.avg_precision.size() * 4);
+  if (out_ms) *out_ms = g.avg_query_time_ms;
+  if (queries_evaluated) *queries_evaluated = g.queries_evaluated;
+  return FVDB_OK;
+}
+// evaluate_search_quality (_wide above k = FVDB_MAX_K) at every listed ef from one exact search; out_recall /
+// out_precision: E floats each
+int fvh_hnsw_quality_by_ef(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, const uint32_t* efs, uint32_t E,
+                           float* out_recall, float* out_precision, float* out_ms, uint64_t* queries_evaluated) {
+  QualityGrid g;
+  const int rc = ((HNSWIndex*)p)->quality_by_ef(q, B, d, k, efs, E, out_recall && out_precision ? &g : nullptr);
+  return rc ? rc : grid_out(g, out_recall, out_precision, out_ms, queries_evaluated);
+}
 void fvh_hnsw_set_scan_cutoff(void* p, uint64_t nodes) { ((HNSWIndex*)p)->set_scan_cutoff(nodes); }
 uint64_t fvh_hnsw_scan_cutoff(void* p) { return ((HNSWIndex*)p)->scan_cutoff(); }
 void* fvh_hnsw_device_graph(void* p) { return ((HNSWIndex*)p)->device_graph(); }
@@ -410,6 +426,22 @@ int fvh_hybrid_evaluate_search_quality_wide(void* p, const float* q, uint32_t B,
   out3[2] = s.avg_query_time_ms;
   if (queries_evaluated) *queries_evaluated = s.queries_evaluated;
   return FVDB_OK;
+}
+// evaluate_search_quality (_wide above k = FVDB_MAX_K) at every pair (efs[i], n_probes[j]) in one call (DESIGN.md section
+// 9r); out_recall / out_precision: max(E, 1) x max(P, 1) floats each, row-major
+int fvh_hybrid_quality_grid(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, int search_recent, int search_historical,
+                            uint64_t recent_k, uint64_t historical_k, const uint32_t* efs, uint32_t E, const uint32_t* n_probes,
+                            uint32_t P, double now, float* out_recall, float* out_precision, float* out_ms,
+                            uint64_t* queries_evaluated) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  c.recent_k = recent_k;
+  c.historical_k = historical_k;
+  QualityGrid g;
+  const int rc = ((HybridIndex*)p)->quality_grid(q, B, d, c, efs, E, n_probes, P, now, out_recall && out_precision ? &g : nullptr);
+  return rc ? rc : grid_out(g, out_recall, out_precision, out_ms, queries_evaluated);
 }
 int fvh_hybrid_search_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
                               int search_recent, int search_historical, uint64_t recent_k, uint64_t historical_k,

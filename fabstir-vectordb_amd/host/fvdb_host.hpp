@@ -171,6 +171,51 @@ inline SearchQuality quality_of(float total_recall, float total_precision, uint3
 int compare_id_blocks(fvdb_ctx* ctx, DevBuf& stage, uint32_t B, uint32_t k, const uint64_t* res_ids, const uint32_t* res_counts,
                       const uint64_t* truth_ids, const uint32_t* truth_counts, float* total_recall, float* total_precision);
 
+// Search quality over a grid of (ef, n_probe) from one exact search.  avg_recall / avg_precision:
+// [rows][cols] row-major, entry (i, j) what evaluate_search_quality returns at (efs[i], n_probes[j]), bit for bit.
+struct QualityGrid {
+  uint32_t rows = 0, cols = 0;
+  std::vector<float> avg_recall, avg_precision;
+  float avg_query_time_ms = 0.0f;  // wall time of the call over B
+  uint64_t queries_evaluated = 0;
+};
+// The parts of a grid on the host, as the searches returned them: the truth's ids [B][k], the recent parts
+// [E][B][rk] and the historical parts [P][B][hk] (distances ascending), each with its hit counts.  E == 0 or P == 0:
+// that part is absent and its pointers are not read (not both).
+struct GridParts {
+  uint32_t B, k;
+  const uint64_t* tid;
+  const uint32_t* tcn;
+  uint32_t E, rk;
+  const uint64_t* rid;
+  const float* rd;
+  const uint32_t* rcn;
+  uint32_t P, hk;
+  const uint64_t* hid;
+  const float* hd;
+  const uint32_t* hcn;
+  uint32_t rows() const { return E ? E : 1; }
+  uint32_t cols() const { return P ? P : 1; }
+  // bytes one query adds to a sub-batch: its staged lists with their counts, its rows() x cols() pairs of figures, and
+  // the prefix counts the engine keeps per list entry (fvdb_quality_grid_dev)
+  uint64_t bytes_per_query() const {
+    return (uint64_t)k * 8 + 4 + (uint64_t)E * ((uint64_t)rk * 16 + 8) + (uint64_t)P * ((uint64_t)hk * 16 + 8) +
+           (uint64_t)rows() * cols() * 8;
+  }
+};
+constexpr uint64_t kQualityGridBytes = 256ull << 20;
+// the budget of a call: kQualityGridBytes unless FVDB_QUALITY_GRID_BYTES says otherwise (read at every call)
+uint64_t quality_grid_budget();
+// queries of a sub-batch: as many as fit the budget, at least one, at most B
+inline uint32_t quality_grid_step(uint64_t budget, const GridParts& p) {
+  const uint64_t fit = budget / p.bytes_per_query();
+  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(fit, 1), p.B);
+}
+// The parts go down to `stage` in sub-batches of quality_grid_step queries, one fvdb_quality_grid_dev call each; the
+// per-query figures come back and are added to total_recall / total_precision [rows() * cols()] in query order, in f32,
+// as compare_id_blocks adds them: the totals do not depend on the budget.
+int quality_grid_totals(fvdb_ctx* ctx, DevBuf& stage, const GridParts& p, float* total_recall, float* total_precision);
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
@@ -439,6 +484,12 @@ class HNSWIndex {
                             float* dist, uint32_t* counts, uint32_t slot);
   int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
   int quality_impl(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out, bool wide);  // both forms
+  // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every listed ef from ONE exact search (DESIGN.md
+  // section 9r): one search(k, efs[i]) each, one fvdb_quality_grid_dev call per sub-batch.  out: E x 1, entry i what
+  // the single call returns at efs[i], bit for bit; duplicates and any order are fine.  Refused before any search
+  // runs, in this order: B == 0, a null pointer or E == 0 FVDB_E_INVALID; k == 0, k > FVDB_MAX_K_WIDE or E > 64
+  // FVDB_E_UNSUPPORTED; a dimension mismatch FVDB_E_DIM.  An ef the search refuses: that search's code.
+  int quality_by_ef(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint32_t* efs, uint32_t E, QualityGrid* out);
   // 0 = never scan, UINT64_MAX = always.  The default is a guess nobody has measured.
   void set_scan_cutoff(uint64_t nodes) { scan_cutoff_ = nodes; }
   uint64_t scan_cutoff() const { return scan_cutoff_; }
@@ -781,6 +832,18 @@ class HybridIndex {
                         float* dist, uint32_t* counts);
   int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
                                    SearchQuality* out);
+  // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every pair (efs[i], n_probes[j]) in one call
+  // (DESIGN.md section 9r): one migration step; under ONE hold of the read lock one exact search, one traversal per
+  // listed ef and one list search per listed n_probe, the PARTS kept; then fvdb_quality_grid_dev merges and counts
+  // every pair.  cfg: k, recent_k, historical_k, search_recent, search_historical (hnsw_ef and ivf_n_probe are not
+  // read).  out: E x P (E or P counting as 1 when it is 0).  When the historical part is not searched or the lists are
+  // untrained every column holds the recent-only value, and every row the historical-only one when the recent part is
+  // not searched.  Duplicates and any order in efs / n_probes are fine.  Refused before any search runs, in this order:
+  // a sharded index FVDB_E_UNSUPPORTED; B == 0, a null pointer, E == 0 (P == 0) with the recent (historical) part
+  // searched FVDB_E_INVALID; k == 0, k > FVDB_MAX_K_WIDE, E or P > 64 FVDB_E_UNSUPPORTED; an index never initialised
+  // FVDB_E_INVALID; a dimension mismatch FVDB_E_DIM.  An ef or n_probe the underlying search refuses: that search's code.
+  int quality_grid(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint32_t* efs, uint32_t E,
+                   const uint32_t* n_probes, uint32_t P, double now, QualityGrid* out);
   // Concurrency (reference: tokio RwLock, searches = readers, src/hybrid/core.rs:457,466): search() / search_dev() /
   // search_with_filter() may be called from any number of host threads; each call leases a free slot (stream,
   // traversal state, IVF scratch set, result blocks) and returns it.  Mutations wait for those calls to finish.

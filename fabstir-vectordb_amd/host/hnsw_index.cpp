@@ -908,6 +908,100 @@ int HNSWIndex::quality_impl(const float* q, uint32_t B, uint32_t dim, uint32_t k
   return FVDB_OK;
 }
 
+// ---- search quality over a grid of ef and n_probe ----
+uint64_t quality_grid_budget() {
+  const char* e = getenv("FVDB_QUALITY_GRID_BYTES");
+  return e ? strtoull(e, nullptr, 10) : kQualityGridBytes;
+}
+
+int quality_grid_totals(fvdb_ctx* ctx, DevBuf& stage, const GridParts& p, float* total_recall, float* total_precision) {
+  const uint32_t B = p.B, k = p.k, E = p.E, P = p.P, rk = p.rk, hk = p.hk;
+  const uint32_t pairs = p.rows() * p.cols();
+  for (uint32_t i = 0; i < pairs; ++i) total_recall[i] = total_precision[i] = 0.0f;
+  const uint32_t step = quality_grid_step(quality_grid_budget(), p);
+  // one sub-batch of n queries: the 8-byte blocks first, then the 4-byte ones, the figures last
+  const uint64_t ns = step;
+  const uint64_t o_gid = ns * k * 8, o_hid = o_gid + ns * E * rk * 8, o_gd = o_hid + ns * P * hk * 8, o_hd = o_gd + ns * E * rk * 4,
+                 o_tc = o_hd + ns * P * hk * 4, o_gc = o_tc + ns * 4, o_hc = o_gc + ns * E * 4, o_out = o_hc + ns * P * 4;
+  const uint64_t bytes = o_out + ns * pairs * 8;
+  int rc = stage.reserve(ctx, bytes, true);
+  if (rc) return rc;
+  char* h = (char*)stage.host;
+  char* d = (char*)stage.dev;
+  for (uint32_t b0 = 0; b0 < B; b0 += step) {
+    const uint32_t n = std::min(step, B - b0);
+    // list e of a part is [B][width] on the host and [n][width] in the sub-batch: rows b0 .. b0 + n of it
+    std::memcpy(h, p.tid + (size_t)b0 * k, (size_t)n * k * 8);
+    std::memcpy(h + o_tc, p.tcn + b0, (size_t)n * 4);
+    for (uint32_t e = 0; e < E; ++e) {
+      const size_t src = (size_t)e * B + b0, dst = (size_t)e * n;
+      std::memcpy(h + o_gid + dst * rk * 8, p.rid + src * rk, (size_t)n * rk * 8);
+      std::memcpy(h + o_gd + dst * rk * 4, p.rd + src * rk, (size_t)n * rk * 4);
+      std::memcpy(h + o_gc + dst * 4, p.rcn + src, (size_t)n * 4);
+    }
+    for (uint32_t j = 0; j < P; ++j) {
+      const size_t src = (size_t)j * B + b0, dst = (size_t)j * n;
+      std::memcpy(h + o_hid + dst * hk * 8, p.hid + src * hk, (size_t)n * hk * 8);
+      std::memcpy(h + o_hd + dst * hk * 4, p.hd + src * hk, (size_t)n * hk * 4);
+      std::memcpy(h + o_hc + dst * 4, p.hcn + src, (size_t)n * 4);
+    }
+    if ((rc = fvdb_dev_upload(ctx, d, h, o_out))) return rc;
+    float* out = (float*)(d + o_out);
+    rc = fvdb_quality_grid_dev(ctx, (const uint64_t*)d, (const uint32_t*)(d + o_tc), (const uint64_t*)(d + o_gid),
+                               (const float*)(d + o_gd), (const uint32_t*)(d + o_gc), (const uint64_t*)(d + o_hid),
+                               (const float*)(d + o_hd), (const uint32_t*)(d + o_hc), n, k, rk, hk, E, P, out, out + (size_t)pairs * n);
+    if (rc) return rc;
+    if ((rc = fvdb_dev_download_async(ctx, h + o_out, d + o_out, (size_t)pairs * n * 8)) || (rc = fvdb_ctx_synchronize(ctx))) return rc;
+    const float* r = (const float*)(h + o_out);
+    const float* pr = r + (size_t)pairs * n;
+    for (uint32_t i = 0; i < pairs; ++i) {
+      float tr = total_recall[i], tp = total_precision[i];
+      for (uint32_t b = 0; b < n; ++b) {  // `total_recall += recall` (operations.rs:374-375), in query order
+        tr += r[(size_t)i * n + b];
+        tp += pr[(size_t)i * n + b];
+      }
+      total_recall[i] = tr;
+      total_precision[i] = tp;
+    }
+  }
+  return FVDB_OK;
+}
+
+int HNSWIndex::quality_by_ef(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint32_t* efs, uint32_t E, QualityGrid* out) {
+  if (B == 0 || !q || !out || !efs || E == 0) return FVDB_E_INVALID;  // "No test queries provided" (operations.rs:334-338)
+  if (k == 0 || k > FVDB_MAX_K_WIDE || E > 64) return FVDB_E_UNSUPPORTED;
+  if (has_dim_ && dim != dim_) return FVDB_E_DIM;
+  const auto start = std::chrono::steady_clock::now();
+  const size_t n = (size_t)B * k;
+  std::vector<uint64_t> tid(n), rid(n * E);
+  std::vector<float> td(n), rd(n * E);
+  std::vector<uint32_t> tcn(B), rcn((size_t)B * E);
+  int rc;
+  // the register form and the wide form agree for k <= FVDB_MAX_K (section 9q); each is what the single call uses there
+  if ((rc = (k > FVDB_MAX_K ? search_exact_wide(q, B, dim, k, tid.data(), td.data(), tcn.data())
+                            : search_exact(q, B, dim, k, tid.data(), td.data(), tcn.data()))))
+    return rc;
+  for (uint32_t e = 0; e < E; ++e)
+    if ((rc = search(q, B, dim, k, efs[e], &rid[e * n], &rd[e * n], &rcn[(size_t)e * B]))) return rc;
+  const GridParts p{B, k, tid.data(), tcn.data(), E, k, rid.data(), rd.data(), rcn.data(), 0, 0, nullptr, nullptr, nullptr};
+  std::vector<float> tr(E), tp(E);
+  {
+    std::lock_guard<std::mutex> serial(search_mu_);  // qual_ is one block: calls take turns
+    if ((rc = quality_grid_totals(ctx_, qual_, p, tr.data(), tp.data()))) return rc;
+  }
+  out->rows = E, out->cols = 1;
+  out->avg_recall.resize(E);
+  out->avg_precision.resize(E);
+  for (uint32_t e = 0; e < E; ++e) {
+    const SearchQuality s = quality_of(tr[e], tp[e], B, start);
+    out->avg_recall[e] = s.avg_recall;
+    out->avg_precision[e] = s.avg_precision;
+    out->avg_query_time_ms = s.avg_query_time_ms;
+  }
+  out->queries_evaluated = B;
+  return FVDB_OK;
+}
+
 // The layered walk on the host (:398-467) for chunks of at most 16384 queries in lock step: one scorer launch per hop
 // for the whole chunk.  (Several smaller groups on a stream each, driven round-robin so that one group's hop is on the
 // GPU while another's host phase runs, were measured slower: launch + stream sync cost more than the overlap wins,

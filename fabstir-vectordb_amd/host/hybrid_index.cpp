@@ -1014,6 +1014,83 @@ int HybridIndex::quality_impl(const float* q, uint32_t B, uint32_t dim, const Hy
   return FVDB_OK;
 }
 
+// quality_impl at every pair (efs[i], n_probes[j]).  The parts are the blocking searches of the
+// two index classes — what search_locked's begin / end pair returns for them — kept apart; the merge of every pair
+// happens on the device, inside the count.
+int HybridIndex::quality_grid(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint32_t* efs, uint32_t E,
+                              const uint32_t* n_probes, uint32_t P, double now, QualityGrid* out) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;
+  if (B == 0 || !q || !out) return FVDB_E_INVALID;  // "No test queries provided" (src/ivf/operations.rs:334-338)
+  if (cfg.search_recent && (E == 0 || !efs)) return FVDB_E_INVALID;
+  if (cfg.search_historical && (P == 0 || !n_probes)) return FVDB_E_INVALID;
+  if (cfg.k == 0 || cfg.k > FVDB_MAX_K_WIDE || E > 64 || P > 64) return FVDB_E_UNSUPPORTED;
+  if (!initialized_) return FVDB_E_INVALID;
+  if (cfg.search_recent && recent_->dimension() != 0 && dim != recent_->dimension()) return FVDB_E_DIM;
+  if (cfg.search_historical && ivf_trained_ && dim != historical_->dimension()) return FVDB_E_DIM;
+  const uint32_t k = (uint32_t)cfg.k, rk = cfg.rk(), hk = cfg.hk();
+  const bool wide = k > FVDB_MAX_K;  // the two exact forms agree for k <= FVDB_MAX_K (section 9q)
+  const auto start = std::chrono::steady_clock::now();
+  if (int rc = migrate_if_due(now, false)) return rc;
+  const bool have_r = cfg.search_recent, have_h = cfg.search_historical && ivf_trained_;
+  // a part that is not searched leaves the grid: one row (column) stands for all of them
+  const uint32_t Eg = have_r ? E : 0, Pg = have_h ? P : 0;
+  const size_t nt = (size_t)B * k, nr = (size_t)B * rk, nh = (size_t)B * hk;
+  std::vector<uint64_t> tid(nt), rid(nr * Eg), hid(nh * Pg);
+  std::vector<float> td(nt), rd(nr * Eg), hd(nh * Pg);
+  std::vector<uint32_t> tcn(B), rcn((size_t)B * Eg), hcn((size_t)B * Pg);
+  GridParts p{B, k, tid.data(), tcn.data(), Eg, rk, rid.data(), rd.data(), rcn.data(), Pg, hk, hid.data(), hd.data(), hcn.data()};
+  // neither part: every result is empty.  One historical list of no entries says so to the device.
+  const uint64_t no_id = FVDB_NO_ID;
+  const float no_dist = __builtin_huge_valf();
+  const std::vector<uint32_t> none(B, 0);
+  std::vector<uint64_t> none_ids;
+  std::vector<float> none_dist;
+  if (!Eg && !Pg) {
+    none_ids.assign(B, no_id);
+    none_dist.assign(B, no_dist);
+    p.P = 1, p.hk = 1, p.hid = none_ids.data(), p.hd = none_dist.data(), p.hcn = none.data();
+  }
+  std::vector<float> tr((size_t)p.rows() * p.cols()), tp(tr.size());
+  {
+    std::shared_lock<std::shared_mutex> r(rw_);  // one hold for every search: they see the same rows
+    fill_empty(tid.data(), td.data(), tcn.data(), B, k);
+    int rc;
+    if ((rc = exact_locked(q, B, dim, cfg, tid.data(), td.data(), tcn.data(), wide))) return rc;
+    if (Eg) {
+      // search_locked's recent part, one ef after the other: the batch staged once in a slot leased for the call, the
+      // traversal begun and collected there (a search the checks answer, or one for the host walk, runs in the end)
+      Lease lease(this, Lease::kAnyFree, Lease::kTake);
+      Slot& sl = *lease.sl;
+      if ((rc = stage_finite(sl, q, B, dim))) return rc;
+      const float* qd = (const float*)sl.d_q.dev;
+      for (uint32_t e = 0; e < Eg; ++e) {
+        int rcb = 0;
+        recent_->search_dev_begin(qd, B, dim, rk, efs[e], &rcb, lease.index(), nullptr);
+        if ((rc = recent_->search_dev_end(qd, B, dim, rk, efs[e], &rid[e * nr], &rd[e * nr], &rcn[(size_t)e * B], lease.index(), nullptr)))
+          return rc;
+      }
+    }
+    for (uint32_t j = 0; j < Pg; ++j)
+      if ((rc = historical_->search(q, B, dim, hk, n_probes[j], &hid[j * nh], &hd[j * nh], &hcn[(size_t)j * B]))) return rc;
+    std::lock_guard<std::mutex> lk(qual_mu_);
+    if ((rc = quality_grid_totals(ctx_ivf_, qual_, p, tr.data(), tp.data()))) return rc;
+  }
+  const uint32_t rows = E ? E : 1, cols = P ? P : 1;
+  out->rows = rows, out->cols = cols;
+  out->avg_recall.resize((size_t)rows * cols);
+  out->avg_precision.resize((size_t)rows * cols);
+  for (uint32_t i = 0; i < rows; ++i)
+    for (uint32_t j = 0; j < cols; ++j) {
+      const size_t at = (size_t)(Eg ? i : 0) * p.cols() + (Pg ? j : 0);
+      const SearchQuality s = quality_of(tr[at], tp[at], B, start);
+      out->avg_recall[(size_t)i * cols + j] = s.avg_recall;
+      out->avg_precision[(size_t)i * cols + j] = s.avg_precision;
+      out->avg_query_time_ms = s.avg_query_time_ms;
+    }
+  out->queries_evaluated = B;
+  return FVDB_OK;
+}
+
 int HybridIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const uint64_t* allowed,
                                 uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* counts) {
   if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // the sharded IVF step takes no mask

@@ -170,6 +170,10 @@ HOST_SIGNATURES = {
     "fvh_hnsw_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
     "fvh_hybrid_search_exact_wide": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
+    # search quality over a grid of ef and n_probe from one exact search
+    "fvh_hnsw_quality_by_ef": (i32, [vp, f32p, u32, u32, u32, u32p, u32, f32p, f32p, f32p, u64p]),
+    "fvh_hybrid_quality_grid": (i32, [vp, f32p, u32, u32, u64, i32, i32, u64, u64, u32p, u32, u32p, u32, dbl, f32p, f32p, f32p,
+                                      u64p]),
     # one allow-set per query
     "fvh_ivf_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
     "fvh_hnsw_search_allowed_groups": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64p, u8p, u32, u32p, u64p, f32p, u32p]),
@@ -306,6 +310,43 @@ class _Base:
         out, n = np.zeros(3, np.float32), C.c_uint64(0)
         self._check(fn(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], *args, _ptr(out, f32p), C.byref(n)))
         return dict(avg_recall=out[0], avg_precision=out[1], avg_query_time_ms=float(out[2]), queries_evaluated=int(n.value))
+
+    def _grid(self, call, queries, efs, n_probes):
+        """The grid calls of the graph and hybrid classes: call(q, B, dim, efs, E, n_probes, P, recall,
+        precision, ms, done) fills [max(E, 1)][max(P, 1)] f32 arrays."""
+        q = np.asarray(queries, np.float32)
+        if q.size == 0:
+            raise InvalidConfig("Invalid parameter: No test queries provided")
+        q = _rows(q)
+        e, p = _points(efs), _points(n_probes)
+        shape = (max(e.size, 1), max(p.size, 1))
+        recall, precision = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        ms, done = C.c_float(0), C.c_uint64(0)
+        self._check(call(_ptr(q, f32p), q.shape[0], q.shape[1], _ptr(e, u32p) if e.size else None, e.size,
+                         _ptr(p, u32p) if p.size else None, p.size, _ptr(recall, f32p), _ptr(precision, f32p), C.byref(ms),
+                         C.byref(done)))
+        return recall, precision, float(ms.value), int(done.value), e, p
+
+
+def pareto_points(grid, target_recall):
+    """HybridIndex.operating_points on a grid as quality_grid returns it: the (ef, n_probe) pairs whose avg_recall reaches
+    target_recall (compared in f32) and that no other reaching pair dominates (ef' <= ef and n_probe' <= n_probe), as
+    dicts sorted by ef.  A pair listed twice is reported once."""
+    reach = {}
+    for i, ef in enumerate(grid["efs"]):
+        for j, p in enumerate(grid["n_probes"]):
+            if grid["avg_recall"][i][j] >= np.float32(target_recall):
+                reach.setdefault((int(ef), int(p)), (grid["avg_recall"][i][j], grid["avg_precision"][i][j]))
+    keep = [pt for pt in reach if not any(o != pt and o[0] <= pt[0] and o[1] <= pt[1] for o in reach)]
+    return [dict(ef=ef, n_probe=p, avg_recall=reach[(ef, p)][0], avg_precision=reach[(ef, p)][1]) for ef, p in sorted(keep)]
+
+
+def _points(values):
+    """The listed ef or n_probe values of a grid call as a u32 array (None: no value)."""
+    v = np.asarray([] if values is None else values, np.int64).reshape(-1)
+    if v.size and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+        raise InvalidConfig("Invalid parameter: ef and n_probe values are 32-bit unsigned")
+    return np.ascontiguousarray(v, np.uint32)
 
 
 class IVFIndex(_Base):
@@ -670,6 +711,25 @@ class HNSWIndex(_Base):
         """evaluate_search_quality() with k in 1..4096: search(k, ef), which returns at most ef rows, against
         search_exact_wide(k); the same formulas."""
         return self._quality(self.lib.fvh_hnsw_evaluate_search_quality_wide, queries, int(k), int(ef))
+
+    def recall_by_ef(self, queries, k, efs):
+        """evaluate_search_quality (its wide form above k = 256) at every listed ef from ONE exact search (DESIGN.md section
+        9r): one traversal per listed ef, one device job that counts them all.  Returns a dict: efs (the list, as
+        given: duplicates and any order are fine), avg_recall and avg_precision (f32 arrays whose entry i is what the
+        single call returns at efs[i], bit for bit), queries_evaluated, avg_query_time_ms (the call's wall time over the
+        number of queries)."""
+        k = int(k)
+        recall, precision, ms, done, e, _ = self._grid(
+            lambda *a: self.lib.fvh_hnsw_quality_by_ef(self.h, a[0], a[1], a[2], k, a[3], a[4], *a[7:]), queries, efs, None)
+        return dict(efs=[int(x) for x in e], avg_recall=recall[:, 0], avg_precision=precision[:, 0], avg_query_time_ms=ms,
+                    queries_evaluated=done)
+
+    def smallest_ef(self, queries, k, target_recall, efs):
+        """The smallest listed ef whose avg_recall on these queries reaches target_recall (compared in f32), or None when
+        none does; read from recall_by_ef."""
+        curve = self.recall_by_ef(queries, k, efs)
+        reach = [ef for ef, r in zip(curve["efs"], curve["avg_recall"]) if r >= np.float32(target_recall)]
+        return min(reach) if reach else None
 
     @property
     def scan_cutoff(self):
@@ -1110,7 +1170,32 @@ class HybridIndex(_Base):
         return self._quality(self.lib.fvh_hybrid_evaluate_search_quality_wide, queries, int(k), int(hnsw_ef),
                              int(ivf_n_probe), float(now))
 
-    _FILTER_FN = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_void_p)
+    def quality_grid(self, queries, k, efs, n_probes, now=0.0, search_recent=True, search_historical=True):
+        """evaluate_search_quality (its wide form above k = 256) at EVERY pair (efs[i], n_probes[j]) in one call (DESIGN.md
+        section 9r): one migration step, one exact search, one traversal per listed ef, one list search per listed
+        n_probe, one device job that merges and counts every pair.  Returns a dict: efs and n_probes (the lists, as
+        given: duplicates and any order are fine), avg_recall and avg_precision (f32 arrays [E][P] whose entry (i, j) is
+        what evaluate_search_quality(queries, k, now, efs[i], n_probes[j]) returns, bit for bit), queries_evaluated,
+        avg_query_time_ms (the call's wall time over the number of queries).  A part that is not searched (or lists that
+        are untrained) leaves its axis constant; its list may then be empty and the axis has length 1.  Refused on a
+        sharded index, as evaluate_search_quality is."""
+        self._refuse_when_sharded("quality_grid")
+        k, sr, sh, now = int(k), int(bool(search_recent)), int(bool(search_historical)), float(now)
+        recall, precision, ms, done, e, p = self._grid(
+            lambda *a: self.lib.fvh_hybrid_quality_grid(self.h, a[0], a[1], a[2], k, sr, sh, 0, 0, a[3], a[4], a[5], a[6], now,
+                                                        *a[7:]), queries, efs, n_probes)
+        return dict(efs=[int(x) for x in e], n_probes=[int(x) for x in p], avg_recall=recall, avg_precision=precision,
+                    avg_query_time_ms=ms, queries_evaluated=done)
+
+    def operating_points(self, queries, k, target_recall, efs, n_probes, now=0.0):
+        """The cheapest pairs that reach target_recall on these queries (compared in f32), read from quality_grid: every
+        listed (ef, n_probe) whose avg_recall reaches the target and that no other reaching pair dominates — none with
+        ef' <= ef and n_probe' <= n_probe.  A list of dicts (ef, n_probe, avg_recall, avg_precision) sorted by ef; empty
+        when no pair reaches the target.  No timing is involved: which of them is fastest is for the caller to measure."""
+        grid = self.quality_grid(queries, k, efs, n_probes, now)
+        return pareto_points(grid, target_recall)
+
+    _FILTER_FN =C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_void_p)
 
     def search_with_filter(self, queries, k, matches=None, now=0.0):
         """HybridIndex::search_with_filter (src/hybrid/core.rs:513-549) in the host mirror: 3 k candidates with the

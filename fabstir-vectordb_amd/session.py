@@ -343,6 +343,26 @@ class VectorDbSession:
 
     evaluateSearchQuality = evaluate_search_quality
 
+    def quality_grid(self, queries, k, efs, n_probes):
+        """evaluate_search_quality at every pair of the listed "hnswEf" and "ivfNProbe" values in one call (no counterpart
+        in the reference's session): HybridIndex.quality_grid over the same resident rows, at the session's clock.
+        Returns efs, n_probes, avg_recall and avg_precision ([E][P]), avg_query_time_ms, queries_evaluated."""
+        if self.destroyed:
+            raise SessionError("Session already destroyed")
+        qs = [js_array_to_vec_f32(qv) for qv in queries]
+        for q in qs:
+            if self.vector_dimension is not None and q.size != self.vector_dimension:
+                raise SessionError(
+                    f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+        if not qs:
+            raise SessionError("Evaluation failed: No test queries provided")
+        try:
+            return self.index.quality_grid(np.stack(qs), int(k), efs, n_probes, now=self.now)
+        except Exception as e:
+            raise SessionError(f"Evaluation failed: {e}") from e
+
+    qualityGrid = quality_grid
+
     def delete_vector(self, id):
         vid = VectorId(id)
         if self.destroyed:

@@ -790,6 +790,30 @@ int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t s
 int fvdb_search_quality_lists_dev(fvdb_ctx* ctx, const uint64_t* res_ids_dev, const uint32_t* res_counts_dev,
                                   const uint64_t* truth_ids_dev, const uint32_t* truth_counts_dev, uint32_t B, uint32_t k,
                                   float* out_recall_dev, float* out_precision_dev);
+/* fvdb_search_quality_lists_dev's figures for the hybrid result at EVERY pair (efs[i], n_probes[j]) from the PARTS the
+ * caller holds in HBM, without forming any merged result.  Per query
+ *   truth    truth_ids_dev[B][k] with truth_counts_dev[B]: the ids of the exact result;
+ *   recent   recent_ids_dev / recent_dist_dev [E][B][rk] with recent_counts_dev[E][B]: the recent part at each listed
+ *            ef, distances ascending;
+ *   hist     hist_ids_dev / hist_dist_dev [P][B][hk] with hist_counts_dev[P][B]: the historical part at each listed
+ *            n_probe, distances ascending.
+ * Entries at or beyond a count are not read.  The result at (i, j) is the first L = min(k, |G| + |H|) entries of the
+ * stable merge of G = recent[i] and H = hist[j], recent first on equal distances (src/hybrid/core.rs:476-485): the
+ * first a entries of G and the first L - a of H, a found by a binary search (entry a of G is inside iff
+ * a + #{h in H : d_h < d_G[a]} < L).  matches = entries of that result whose id occurs in the truth (an id the
+ * result holds twice counts twice), recall = truth empty ? 1 : matches / min(len(truth), k), precision = L == 0 ? 0 :
+ * matches / L — bit for bit what fvdb_search_quality_lists_dev writes for the merged result.
+ * out_recall_dev / out_precision_dev: [max(E, 1)][max(P, 1)][B] floats, enqueued on ctx's stream.
+ * P == 0 (the hist pointers are not read, NULL is fine): the graph-only form, the result is recent[i] cut at k.
+ * E == 0 likewise: the list-only form.  E == 0 and P == 0, a NULL block of a part that is present: FVDB_E_INVALID.
+ * 1 <= k <= FVDB_MAX_K_WIDE, and so rk / hk of a part that is present; E, P <= 64; B < 2^31 and at most 2^38 (i, j,
+ * query) triples: FVDB_E_UNSUPPORTED otherwise.  B == 0 is FVDB_OK and writes nothing.  The lists' prefix counts go to
+ * scratch the context owns (4 bytes per list entry), shared by the calls on that context in stream order. */
+int fvdb_quality_grid_dev(fvdb_ctx* ctx, const uint64_t* truth_ids_dev, const uint32_t* truth_counts_dev,
+                          const uint64_t* recent_ids_dev, const float* recent_dist_dev, const uint32_t* recent_counts_dev,
+                          const uint64_t* hist_ids_dev, const float* hist_dist_dev, const uint32_t* hist_counts_dev, uint32_t B,
+                          uint32_t k, uint32_t rk, uint32_t hk, uint32_t E, uint32_t P, float* out_recall_dev,
+                          float* out_precision_dev);
 
 /* ---- multi-GPU: inverted lists sharded across the GPUs of a node, RCCL over xGMI -------------------------
  * (BASELINE config C4; SURVEY §8e.  The reference has no distributed execution: what is preserved is the result —
