@@ -32,28 +32,47 @@ uint64_t flat_wide_arena_bytes() {
 
 constexpr int kFlatWideQ = 8;  // queries of a score group (DESIGN.md section 9q has the figures of 8 and 16)
 
+// the argument checks of the two flat entry points, in the C ABI's order and with its messages; the k limit and its
+// message are the caller's.  FVDB_OK: *src and *ctx are set.
+int flat_check_args(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, uint32_t k, uint32_t k_max, const char* k_msg,
+                    bool have_buffers, GraphMaskSource* src, fvdb_ctx** ctx_out) {
+  if (!g) return FVDB_E_INVALID;
+  int rc = graph_mask_source(g, src);
+  if (rc) return rc;
+  fvdb_ctx* ctx = *ctx_out = on ? on : src->store->ctx;
+  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
+  if (on && on->device != src->store->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
+  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
+  if (mask && mask->stamp != src->mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
+  if (k == 0 || k > k_max) FAIL(ctx, FVDB_E_UNSUPPORTED, k_msg);
+  if (!have_buffers) FAIL(ctx, FVDB_E_INVALID, "null argument");
+  return FVDB_OK;
+}
+
+// the slices of n rows for a sub-batch of Bs queries in groups of Q: enough (group, slice) waves to fill the device at a
+// small batch, a slice no shorter than four tiles of 64 rows; n == 0: no slice
+void flat_slice_plan(uint32_t n, uint32_t Bs, uint32_t Q, uint32_t* slices, uint32_t* slice_tiles) {
+  const uint32_t tiles = cdiv(n, 64);
+  *slices = *slice_tiles = 0;
+  if (!n) return;
+  *slice_tiles = cdiv(tiles, std::max<uint32_t>(1, std::min<uint32_t>(cdiv(tiles, 4), cdiv(4096, cdiv(Bs, Q)))));
+  *slices = cdiv(tiles, *slice_tiles);
+}
+
 }  // namespace
 
 extern "C" {
 
 int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                     uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
-  if (!g) return FVDB_E_INVALID;
   GraphMaskSource src{};
-  int rc = graph_mask_source(g, &src);
+  fvdb_ctx* ctx = nullptr;
+  int rc = flat_check_args(g, on, slot, mask, k, FVDB_MAX_K, "exact scan: k must be in 1..FVDB_MAX_K",
+                           q_dev && out_nodes_dev && out_dist_dev && out_counts_dev, &src, &ctx);
   if (rc) return rc;
-  fvdb_store* s = src.store;
-  fvdb_ctx* ctx = on ? on : s->ctx;
-  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
-  if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
-  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
-  if (mask && mask->stamp != src.mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
-  if (k == 0 || k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "exact scan: k must be in 1..FVDB_MAX_K");
-  if (!q_dev || !out_nodes_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null argument");
   if (B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = src.n;
-  const uint32_t tiles = cdiv(n, 64);
+  fvdb_store* s = src.store;
   const int kr = k <= 64 ? 1 : (k <= 128 ? 2 : 4);
   const uint32_t Q = kr == 4 ? 4 : 8;  // queries of a group: the wider lists leave registers for fewer
   // sub-batches run one after the other on the stream and share the slot's scratch
@@ -63,13 +82,10 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
     a.rows = s->data;
     a.dead = mask ? mask->flags.as<uint32_t>() : src.deleted;
     a.dpad = s->dpad;
-    a.n = n;
+    a.n = src.n;
     a.B = Bs;
     a.k = k;
-    // enough (group, slice) waves to fill the device at a small batch, a slice no shorter than four tiles
-    a.slices = n ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(tiles, 4), cdiv(4096, cdiv(Bs, Q)))) : 0;
-    a.slice_tiles = a.slices ? cdiv(tiles, a.slices) : 0;
-    if (a.slices) a.slices = cdiv(tiles, a.slice_tiles);
+    flat_slice_plan(src.n, Bs, Q, &a.slices, &a.slice_tiles);
     rc = graph_scan_inputs(g, ctx, slot, q_dev + (size_t)b0 * s->d, Bs, (size_t)a.slices * Bs * k * 8, &a.queries, &a.part);
     if (rc) return rc;
     uint32_t* on_ = out_nodes_dev + (size_t)b0 * k;
@@ -87,24 +103,16 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
 
 int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
                                          uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
-  if (!g) return FVDB_E_INVALID;
   GraphMaskSource src{};
-  int rc = graph_mask_source(g, &src);
+  fvdb_ctx* ctx = nullptr;
+  int rc = flat_check_args(g, on, slot, mask, k, FVDB_MAX_K_WIDE, "exact scan: k must be in 1..FVDB_MAX_K_WIDE",
+                           q_dev && out_nodes_dev && out_dist_dev && out_counts_dev, &src, &ctx);
   if (rc) return rc;
-  fvdb_store* s = src.store;
-  fvdb_ctx* ctx = on ? on : s->ctx;
-  if (slot >= kGraphSlots) FAIL(ctx, FVDB_E_INVALID, "slot out of range");
-  if (on && on->device != s->ctx->device) FAIL(ctx, FVDB_E_INVALID, "context of another device");
-  if (mask && mask->graph != g) FAIL(ctx, FVDB_E_INVALID, "mask of another graph");
-  if (mask && mask->stamp != src.mutations) FAIL(ctx, FVDB_E_INVALID, "stale mask: the graph changed after the mask was created");
-  if (k == 0 || k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "exact scan: k must be in 1..FVDB_MAX_K_WIDE");
-  if (!q_dev || !out_nodes_dev || !out_dist_dev || !out_counts_dev) FAIL(ctx, FVDB_E_INVALID, "null argument");
   if (B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  fvdb_store* s = src.store;
   constexpr uint32_t Q = kFlatWideQ;
-  const uint32_t n = src.n;
-  const uint32_t tiles = cdiv(n, 64);
-  const uint64_t stride = (uint64_t)tiles * 64;  // arena words of a query; < 2^32 whatever n
+  const uint64_t stride = (uint64_t)cdiv(src.n, 64) * 64;  // arena words of a query: whole tiles; < 2^32 whatever n
   // queries of a sub-batch: their arena fits the budget, at least one; sub-batches run one after the other on the
   // stream and share the slot's scratch
   const uint64_t fit = std::max<uint64_t>(flat_wide_arena_bytes() / std::max<uint64_t>(stride * 4, 1), 1);
@@ -115,12 +123,9 @@ int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t s
     a.rows = s->data;
     a.dead = mask ? mask->flags.as<uint32_t>() : src.deleted;
     a.dpad = s->dpad;
-    a.n = n;
+    a.n = src.n;
     a.B = Bs;
-    // flat_scan_kernel's slices: enough (group, slice) waves to fill the device at a small batch
-    a.slices = n ? std::max<uint32_t>(1, std::min<uint32_t>(cdiv(tiles, 4), cdiv(4096, cdiv(Bs, Q)))) : 0;
-    a.slice_tiles = a.slices ? cdiv(tiles, a.slices) : 0;
-    if (a.slices) a.slices = cdiv(tiles, a.slice_tiles);
+    flat_slice_plan(src.n, Bs, Q, &a.slices, &a.slice_tiles);
     a.stride = stride;
     uint64_t* part = nullptr;
     rc = graph_scan_inputs(g, ctx, slot, q_dev + (size_t)b0 * s->d, Bs, (size_t)(Bs * stride * 4), &a.queries, &part);

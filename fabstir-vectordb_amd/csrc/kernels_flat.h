@@ -3,6 +3,8 @@
 // i ascending, f32, multiply and add separate, sqrt correctly rounded), the k best per query kept by the unique key
 // (distance bits << 32 | node index).  An fp16 row is widened exactly first (row_types.h).
 //
+//   flat_fold_slice     the work of one wave, shared with the wide form (kernels_flat_wide.h): the distances of the rows of
+//                       a slice of 64-row tiles to a group of Q queries, tile by tile, handed to the caller's sink
 //   flat_scan_kernel    one wave per (group of Q queries, slice of 64-row tiles): per-(query, slice) top k
 //   flat_merge_kernel   one wave per query: the slices' lists merged by the same key, the result block written
 //
@@ -39,45 +41,33 @@ struct FlatScanArgs {
   uint64_t* part;                // [slices][B][k] keys, ~0 = none
 };
 
-template <int Q, int KR, typename RT>
-__global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
-  __shared__ __attribute__((aligned(16))) float s_tile[4][kFlatTileFloats];
+// One wave's pass over the 64-row tiles [t0, t1) of the store against Q queries (queries + qoff[j], wave-uniform): the
+// prefetch, the staging of a chunk into the wave's LDS tile, the read-back as "lane = row" and the fold — the ONE text
+// of it, so flat_scan_kernel and flat_score_kernel (kernels_flat_wide.h) round alike.  At the end of tile t it calls
+// sink(t, row, live, acc): row = 64 t + lane, live = row < n && !dead[row], acc[j] = the squared distance to query j
+// (the sqrtf is the sink's).  No workgroup barrier: waves of a workgroup run slices of different lengths.
+template <int Q, typename RT, class Sink>
+__device__ __forceinline__ void flat_fold_slice(const RT* rows, const float* queries, const uint32_t* dead, const uint32_t dpad,
+                                                const uint32_t n, const uint32_t (&qoff)[Q], float* tile, const uint32_t t0,
+                                                const uint32_t t1, const int lane, Sink&& sink) {
   using Quad = typename RowVec<RT>::Quad;
-  const int lane = threadIdx.x & 63;
-  const uint32_t w = threadIdx.x >> 6;
-  const uint32_t s = blockIdx.y * 4 + w;
-  if (s >= a.slices) return;  // whole waves leave; no workgroup barrier below
-  const uint32_t q0 = blockIdx.x * Q;
-  const uint32_t ne = min((uint32_t)Q, a.B - q0);
-  uint32_t qoff[Q];
-#pragma unroll
-  for (int j = 0; j < Q; ++j) qoff[j] = (q0 + ((uint32_t)j < ne ? (uint32_t)j : 0u)) * a.dpad;  // a short group repeats its first query
-
-  float* tile = s_tile[w];
-  const uint32_t tiles = (a.n + 63) >> 6;
-  const uint32_t t0 = s * a.slice_tiles, t1 = min(tiles, t0 + a.slice_tiles);
-  const uint32_t nchunks = (a.dpad + kFlatChunk - 1) / kFlatChunk;
+  const uint32_t nchunks = (dpad + kFlatChunk - 1) / kFlatChunk;
   const uint32_t lr = (uint32_t)lane >> 3, lc = 4u * ((uint32_t)lane & 7u);  // the load role: row within 8, dims within the chunk
-  const RT* rows = (const RT*)a.rows;
 
   // chunk c of tile t: instruction i reads dims [32 c + lc, + 4) of row 64 t + 8 i + lr (rows at or beyond n repeat the
-  // last one: a valid address, never offered)
+  // last one: a valid address, never live)
   Quad x[8];
   auto load = [&](uint32_t t, uint32_t c) {
     const uint32_t j = c * kFlatChunk + lc;
-    const bool in = j < a.dpad;  // dpad % 4 == 0: a quad never straddles the end
+    const bool in = j < dpad;  // dpad % 4 == 0: a quad never straddles the end
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const uint32_t row = min(t * 64u + (uint32_t)i * 8u + lr, a.n - 1u);
+      const uint32_t row = min(t * 64u + (uint32_t)i * 8u + lr, n - 1u);
       Quad v = {};
-      if (in) v = *(const Quad*)(rows + (size_t)row * a.dpad + j);
+      if (in) v = *(const Quad*)(rows + (size_t)row * dpad + j);
       x[i] = v;
     }
   };
-
-  WaveTopK<KR> tk[Q];
-#pragma unroll
-  for (int j = 0; j < Q; ++j) tk[j].init();
 
   if (t0 < t1) load(t0, 0);
   for (uint32_t t = t0; t < t1; ++t) {
@@ -106,8 +96,8 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const uint32_t dbase = c * kFlatChunk + 16u * (uint32_t)h;  // wave-uniform
-        const float* qb = a.queries + dbase;
-        if (dbase + 16u <= a.dpad) {
+        const float* qb = queries + dbase;
+        if (dbase + 16u <= dpad) {
           f32x16 qn = cload16(qb + qoff[0]);
 #pragma unroll
           for (int j = 0; j < Q; ++j) {
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
         } else {  // the row's last dimensions: quads below dpad only, so no query is read past its end
 #pragma unroll
           for (int i4 = 0; i4 < 4; ++i4) {
-            if (dbase + 4u * (uint32_t)i4 < a.dpad) {
+            if (dbase + 4u * (uint32_t)i4 < dpad) {
 #pragma unroll
               for (int j = 0; j < Q; ++j) {
                 const f32x4 qv = cload((const f32x4*)(qb + qoff[j] + 4 * i4));
@@ -143,7 +133,31 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
       }
     }
     const uint32_t row = t * 64u + (uint32_t)lane;
-    const bool live = row < a.n && a.dead[row] == 0u;
+    const bool live = row < n && dead[row] == 0u;
+    sink(t, row, live, acc);
+  }
+}
+
+template <int Q, int KR, typename RT>
+__global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
+  __shared__ __attribute__((aligned(16))) float s_tile[4][kFlatTileFloats];
+  const int lane = threadIdx.x & 63;
+  const uint32_t w = threadIdx.x >> 6;
+  const uint32_t s = blockIdx.y * 4 + w;
+  if (s >= a.slices) return;  // whole waves leave; no workgroup barrier below
+  const uint32_t q0 = blockIdx.x * Q;
+  const uint32_t ne = min((uint32_t)Q, a.B - q0);
+  uint32_t qoff[Q];
+#pragma unroll
+  for (int j = 0; j < Q; ++j) qoff[j] = (q0 + ((uint32_t)j < ne ? (uint32_t)j : 0u)) * a.dpad;  // a short group repeats its first query
+  const uint32_t tiles = (a.n + 63) >> 6;
+  const uint32_t t0 = s * a.slice_tiles, t1 = min(tiles, t0 + a.slice_tiles);
+
+  WaveTopK<KR> tk[Q];
+#pragma unroll
+  for (int j = 0; j < Q; ++j) tk[j].init();
+
+  auto keep = [&](uint32_t t, uint32_t row, bool live, const float(&acc)[Q]) {
 #pragma unroll
     for (int j = 0; j < Q; ++j) {
       const float dist = sqrtf(acc[j]);
@@ -159,7 +173,8 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const FlatScanArgs a) {
         offer<KR>(tk[j], a.k, chi, row, th, tl, lane);
       }
     }
-  }
+  };
+  flat_fold_slice<Q>((const RT*)a.rows, a.queries, a.dead, a.dpad, a.n, qoff, s_tile[w], t0, t1, lane, keep);
 
 #pragma unroll
   for (int j = 0; j < Q; ++j) {

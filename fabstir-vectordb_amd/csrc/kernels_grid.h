@@ -13,9 +13,9 @@
 //   precision = L == 0  ? 0 : matches / L                         (search_quality_kernel's f32 divisions)
 // fG and fH depend on one list and T only, not on the pair: (E + P) k log k for the flags, E P log k for the pairs.
 //
-//   flags   grid_flags_kernel: one workgroup per query.  T goes into LDS and is sorted there (bitonic, as
-//           wide_select_kernel sorts its keys); then one wave per list: every entry finds its id by binary search and
-//           the wave's ballot gives the inclusive prefix counts, written to pfx[list][query][0 .. n].
+//   flags   grid_flags_kernel: one workgroup per query.  T goes into LDS and is sorted there (lds_bitonic_sort_u64,
+//           kernels_wide.h: the wide selection's sort); then one wave per list: every entry finds its id by binary search
+//           and the wave's ballot gives the inclusive prefix counts, written to pfx[list][query][0 .. n].
 //   pairs   grid_pairs_kernel: one lane per (i, j, query), the query fastest.  The binary search above, two prefix
 //           reads, two divisions.
 // The sums over the queries are the caller's, in query order (compare_id_blocks' loop).
@@ -65,19 +65,7 @@ __global__ __launch_bounds__(kGridThreads) void grid_flags_kernel(const GridArgs
   const uint64_t* __restrict__ truth = a.t_ids + (size_t)q * a.k;
   for (uint32_t e = tid; e < N; e += T) s_t[e] = e < nt ? truth[e] : ~0ull;
   __syncthreads();
-  for (uint32_t kb = 2; kb <= N; kb <<= 1)
-    for (uint32_t j = kb >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = tid; t < N / 2; t += T) {
-        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const uint64_t x = s_t[lo], y = s_t[hi];
-        const bool up = (lo & kb) == 0;
-        if ((x > y) == up) {
-          s_t[lo] = y;
-          s_t[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  lds_bitonic_sort_u64(s_t, N, tid, T);
   // the first nt keys are the truth's ids ascending (a pad is ~0, the largest key: it sorts behind or beside them)
 
   for (uint32_t l = wave; l < a.E + a.P; l += W) {  // wave-uniform: no barrier below

@@ -8,7 +8,8 @@
 //           {0, cblocks} rank bases that kernel reads for a single list.
 //   rank    rank_sort_kernel: one workgroup per query sorts the keys (distance bits << 32 | cluster position)
 //           ascending in dynamic LDS — the order of the reference's stable sort over `centroids` — and writes the
-//           first np cluster ids (and distances).  Bitonic over next_pow2(cblocks * 64) keys: at most 128 KiB.
+//           first np cluster ids (and distances).  lds_bitonic_sort_u64 (kernels_wide.h) over next_pow2(cblocks * 64)
+//           keys: at most 128 KiB.
 //
 // search_quality_kernel: matches / recall / precision of one result list against another (src/ivf/operations.rs
 // :357-377), one wave per query.
@@ -43,20 +44,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_sort_kernel(const RankArgs 
   const uint32_t* __restrict__ ar = a.arena + (size_t)q * a.n;
   for (uint32_t i = tid; i < a.P; i += T) s_rank[i] = i < a.n ? ((uint64_t)ar[i] << 32) | i : ~0ull;
   __syncthreads();
-
-  for (uint32_t kb = 2; kb <= a.P; kb <<= 1)
-    for (uint32_t j = kb >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = tid; t < a.P / 2; t += T) {
-        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const uint64_t x = s_rank[lo], y = s_rank[hi];
-        const bool up = (lo & kb) == 0;
-        if ((x > y) == up) {
-          s_rank[lo] = y;
-          s_rank[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  lds_bitonic_sort_u64(s_rank, a.P, tid, T);
 
   // cluster position -> pool slot -> cluster id, as merge_topk_kernel resolves a coarse result
   for (uint32_t e = tid; e < a.np; e += T) {

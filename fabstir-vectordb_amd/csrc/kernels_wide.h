@@ -11,6 +11,8 @@
 //           smallest distance word — non-negative f32 bits are monotone as u32 — then the rows below the cut and the
 //           first rows AT the cut in seq order are gathered as 64-bit keys into LDS, sorted there (bitonic; the keys
 //           are unique) and resolved seq -> (probe rank, position) -> pool slot -> id as merge_topk_kernel does.
+//           Everything up to the sorted keys is wide_select_keys, which flat_select_kernel (kernels_flat_wide.h) calls
+//           too; the sort is lds_bitonic_sort_u64, which also serves kernels_rank.h and kernels_grid.h.
 //
 //   shards  on an index holding a shard of a larger one the selection is the same and only the keys written out change:
 //           their low word becomes the LOGICAL index's seq (wide_gbase_kernel, GLOB_KEYS), unique across ranks, and
@@ -237,36 +239,44 @@ __device__ __forceinline__ uint32_t wide_rank_of(const uint32_t* s_base, uint32_
   return lo;
 }
 
-// LDS_BASE: the query's rank bases are staged in LDS (nprobe <= kWideMaxProbes); otherwise they are read where
-// wide_base_kernel left them — only the binary searches of the <= k winners touch them.
-// GLOB_KEYS: a shard of a larger index (fvdb_ivf_search_shard_wide_dev_slot).  Selection is unchanged — by (distance
-// bits, local arena index); the lists of other ranks are empty here, so that order restricted to this rank's rows is
-// the logical index's order — and only the key written out carries the logical index's seq (a.gbase) in its low word.
-template <bool LDS_BASE, bool GLOB_KEYS = false>
-__global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const WideArgs a) {
-  constexpr uint32_t T = kWideSelThreads, W = T / 64;
-  __shared__ uint64_t s_keys[kWideMaxK];
-  __shared__ uint32_t s_hist[256];
-  __shared__ uint32_t s_base_lds[LDS_BASE ? kWideMaxProbes + 1 : 1];
-  __shared__ uint32_t s_wties[W];
-  __shared__ uint32_t s_prefix, s_below, s_want, s_taken;
+// Bitonic sort, ascending, of the P (a power of two) 64-bit keys in LDS by the T threads of the workgroup, all of which
+// call it after a barrier behind the last write of a key; on return the keys are sorted and visible to every thread
+// (P == 1: no step and no barrier).  The one sort of the wide selection, rank_sort_kernel (kernels_rank.h) and
+// grid_flags_kernel (kernels_grid.h).
+__device__ __forceinline__ void lds_bitonic_sort_u64(uint64_t* keys, const uint32_t P, const uint32_t tid, const uint32_t T) {
+  for (uint32_t kb = 2; kb <= P; kb <<= 1)
+    for (uint32_t j = kb >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = tid; t < P / 2; t += T) {
+        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const uint64_t x = keys[lo], y = keys[hi];
+        const bool up = (lo & kb) == 0;
+        if ((x > y) == up) {
+          keys[lo] = y;
+          keys[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+}
 
+// The LDS of one selection: 33 840 bytes.  16-byte aligned: a lane reads its four histogram bins with one ds_read_b128.
+struct alignas(16) WideSelectLds {
+  uint64_t keys[kWideMaxK];
+  uint32_t hist[256];
+  uint32_t wties[kWideSelThreads / 64];
+  uint32_t prefix, below, want, taken;
+};
+
+// The selection itself, once: the k smallest of the n (a multiple of 64) distance words ar[0, n) as keys (word << 32 |
+// index), a word equal to the k-th taken in index order — the tie rule of wide_select_kernel and of flat_select_kernel
+// (kernels_flat_wide.h) is this text.  kInf32 words are never taken.  Every thread of a workgroup of kWideSelThreads
+// calls it; it owns `s` and asks nothing of its contents.  Returns the number of keys taken (<= k), s.keys[0, count)
+// ascending and visible to every thread.
+__device__ __forceinline__ uint32_t wide_select_keys(const uint32_t* __restrict__ ar, const uint32_t n, const uint32_t k,
+                                                     WideSelectLds& s) {
+  constexpr uint32_t T = kWideSelThreads, W = T / 64;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t q = blockIdx.x, np = a.nprobe, k = a.k;
-  const uint32_t* s_base = a.base + (size_t)q * (np + 1);
-  if (LDS_BASE) {
-    for (uint32_t r = tid; r <= np; r += T) s_base_lds[r] = a.base[(size_t)q * (np + 1) + r];
-    s_base = s_base_lds;
-  }
-  if (tid == 0) {
-    s_prefix = 0;
-    s_below = 0;
-    s_taken = 0;
-  }
-  __syncthreads();
-  const uint32_t n = s_base[np] * 64;  // arena words of this query (dead rows and padding hold kInf32)
-  const uint32_t* __restrict__ ar = a.arena + (size_t)q * a.stride;
-  // each wave owns a contiguous run of whole blocks, in seq order
+  // each wave owns a contiguous run of whole 64-word blocks, in index order
   const uint32_t per = ((n / 64 + W - 1) / W) * 64;
   const uint32_t w0 = min(wave * per, n), w1 = min(w0 + per, n);
 
@@ -274,11 +284,16 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
   const uint32_t kk = min(k, n);  // n == 0: nothing to select
   uint32_t cut = 0, below = 0, want = 0;
   if (kk) {
-    if (tid == 0) s_want = kk;
+    if (tid == 0) {  // read behind the first barrier of the first pass
+      s.prefix = 0;
+      s.below = 0;
+      s.taken = 0;
+      s.want = kk;
+    }
     for (int shift = 24; shift >= 0; shift -= 8) {
-      for (uint32_t b = tid; b < 256; b += T) s_hist[b] = 0;
+      for (uint32_t b = tid; b < 256; b += T) s.hist[b] = 0;
       __syncthreads();
-      const uint32_t prefix = s_prefix;
+      const uint32_t prefix = s.prefix;
       const uint32_t himask = shift == 24 ? 0u : ~0u << (shift + 8);
       for (uint32_t i = w0 + lane; i < w1; i += 64) {  // whole blocks: all 64 lanes run every round
         const uint32_t v = ar[i];
@@ -288,32 +303,32 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
         const uint32_t dg0 = rfl(dg);
         const uint64_t m_in = __ballot(in);
         if (__ballot(in && dg != dg0) == 0) {
-          if (lane == 0 && m_in) atomicAdd(&s_hist[dg0], (uint32_t)__popcll(m_in));
+          if (lane == 0 && m_in) atomicAdd(&s.hist[dg0], (uint32_t)__popcll(m_in));
         } else if (in) {
-          atomicAdd(&s_hist[dg], 1u);
+          atomicAdd(&s.hist[dg], 1u);
         }
       }
       __syncthreads();
-      if (wave == 0) {  // the bin holding the s_want-th word of this round: 4 bins per lane, prefix across lanes
-        const uint32_t h0 = s_hist[4 * lane], h1 = s_hist[4 * lane + 1], h2 = s_hist[4 * lane + 2], h3 = s_hist[4 * lane + 3];
+      if (wave == 0) {  // the bin holding the s.want-th word of this round: 4 bins per lane, prefix across lanes
+        const uint32_t h0 = s.hist[4 * lane], h1 = s.hist[4 * lane + 1], h2 = s.hist[4 * lane + 2], h3 = s.hist[4 * lane + 3];
         const uint32_t mine = h0 + h1 + h2 + h3;
         const uint32_t inc = wave_incl_scan_u(mine, (int)lane);
-        const uint32_t wantr = s_want, exc = inc - mine;
+        const uint32_t wantr = s.want, exc = inc - mine;
         if (exc < wantr && wantr <= inc) {  // exactly one lane
           uint32_t bin = 4 * lane, acc = exc;
           if (acc + h0 < wantr) { acc += h0; ++bin;
             if (acc + h1 < wantr) { acc += h1; ++bin;
               if (acc + h2 < wantr) { acc += h2; ++bin; } } }
-          s_prefix = prefix | (bin << shift);
-          s_below += acc;
-          s_want = wantr - acc;
+          s.prefix = prefix | (bin << shift);
+          s.below += acc;
+          s.want = wantr - acc;
         }
       }
       __syncthreads();
     }
-    cut = s_prefix;
-    below = s_below;
-    want = s_want;  // words equal to `cut` still wanted: the first `want` of them in seq order
+    cut = s.prefix;
+    below = s.below;
+    want = s.want;  // words equal to `cut` still wanted: the first `want` of them in index order
     if (cut == kInf32) want = 0;  // fewer than k live rows: "no row" words are never results
   }
 
@@ -321,12 +336,12 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
   uint32_t ties = 0;
   if (want)
     for (uint32_t i = w0 + lane; i < w1; i += 64) ties += (uint32_t)__popcll(__ballot(ar[i] == cut));
-  if (lane == 0) s_wties[wave] = ties;
+  if (lane == 0) s.wties[wave] = ties;
   __syncthreads();
   uint32_t tie_rank = 0;  // of the first word at the cut in this wave's run
-  for (uint32_t w = 0; w < wave; ++w) tie_rank += s_wties[w];
+  for (uint32_t w = 0; w < wave; ++w) tie_rank += s.wties[w];
 
-  // ---- gather the survivors as (distance bits << 32 | seq) ----
+  // ---- gather the survivors as (distance bits << 32 | index) ----
   if (kk)
     for (uint32_t i = w0 + lane; i < w1; i += 64) {
       const uint32_t v = ar[i];
@@ -334,31 +349,42 @@ __global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const Wide
       const uint32_t my_tie = tie_rank + ballot_rank(m_tie, lane);
       tie_rank += (uint32_t)__popcll(m_tie);
       uint32_t at = kInf32;
-      if (v < cut) at = atomicAdd(&s_taken, 1u);       // slots [0, below): any order, the sort follows
+      if (v < cut) at = atomicAdd(&s.taken, 1u);       // slots [0, below): any order, the sort follows
       else if (v == cut && my_tie < want) at = below + my_tie;
-      if (at < kWideMaxK) s_keys[at] = ((uint64_t)v << 32) | i;
+      if (at < kWideMaxK) s.keys[at] = ((uint64_t)v << 32) | i;
     }
   const uint32_t count = below + want;  // the selection found at least `want` words at the cut
   uint32_t P = 1;
   while (P < count) P <<= 1;
   __syncthreads();
-  for (uint32_t e = count + tid; e < P; e += T) s_keys[e] = ~0ull;
+  for (uint32_t e = count + tid; e < P; e += T) s.keys[e] = ~0ull;
   __syncthreads();
+  lds_bitonic_sort_u64(s.keys, P, tid, T);
+  return count;
+}
 
-  // ---- sort ascending ----
-  for (uint32_t kb = 2; kb <= P; kb <<= 1)
-    for (uint32_t j = kb >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = tid; t < P / 2; t += T) {
-        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const uint64_t x = s_keys[lo], y = s_keys[hi];
-        const bool up = (lo & kb) == 0;
-        if ((x > y) == up) {
-          s_keys[lo] = y;
-          s_keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+// LDS_BASE: the query's rank bases are staged in LDS (nprobe <= kWideMaxProbes); otherwise they are read where
+// wide_base_kernel left them — only the binary searches of the <= k winners touch them.
+// GLOB_KEYS: a shard of a larger index (fvdb_ivf_search_shard_wide_dev_slot).  Selection is unchanged — by (distance
+// bits, local arena index); the lists of other ranks are empty here, so that order restricted to this rank's rows is
+// the logical index's order — and only the key written out carries the logical index's seq (a.gbase) in its low word.
+template <bool LDS_BASE, bool GLOB_KEYS = false>
+__global__ __launch_bounds__(kWideSelThreads) void wide_select_kernel(const WideArgs a) {
+  constexpr uint32_t T = kWideSelThreads;
+  __shared__ WideSelectLds s_sel;
+  __shared__ uint32_t s_base_lds[LDS_BASE ? kWideMaxProbes + 1 : 1];
+
+  const uint32_t tid = threadIdx.x;
+  const uint32_t q = blockIdx.x, np = a.nprobe, k = a.k;
+  const uint32_t* s_base = a.base + (size_t)q * (np + 1);
+  if (LDS_BASE) {
+    for (uint32_t r = tid; r <= np; r += T) s_base_lds[r] = a.base[(size_t)q * (np + 1) + r];
+    s_base = s_base_lds;
+    __syncthreads();
+  }
+  // the arena words of this query, in seq order: s_base[np] * 64 (dead rows and padding hold kInf32)
+  const uint32_t count = wide_select_keys(a.arena + (size_t)q * a.stride, s_base[np] * 64, k, s_sel);
+  const uint64_t* s_keys = s_sel.keys;
 
   // ---- seq -> (rank, position) -> pool slot -> id ----
   for (uint32_t e = tid; e < k; e += T) {

@@ -99,6 +99,29 @@ def test_scan_equals_the_reference_fold_at_every_batch_and_k(fv, ctx, d, dtype):
     assert list(g.search_exact(q[29:33], 1).ids[:, 0]) == [1010, 1255, 1700, 1003]
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d", [10, 130])
+def test_scan_equals_the_reference_fold_on_both_sides_of_each_list_width(fv, ctx, d, dtype):
+    """k = 64 | 65 and 128 | 129: the widest list of one register per lane, both ends of the two-register list (the scan
+    and the merge of k in 65..128 run nowhere else) and the first k of the four-register one"""
+    x, ids, q, dist = big_case(d, dtype)
+    g = ring_graph(fv, ctx, ids, x, dtype)
+    for rows in (slice(27, 32), slice(0, 33)):  # B = 5, 33
+        for k in (64, 65, 128, 129):
+            got = g.search_exact(q[rows], k)
+            same(got, R.exact_topk(dist[rows], k, ids=ids), f"d={d} {dtype} B={rows.stop - rows.start} k={k}")
+    # under an allow-set the same kernels run with the mask's flags: 100 rows of every slice, duplicated ones among
+    # them, k below and above their number
+    nodes = np.concatenate([[10, 11, 12, 255, 256], np.arange(95) * 30 + 7])
+    allowed_nodes = np.zeros(BIG, bool)
+    allowed_nodes[nodes] = True
+    assert allowed_nodes.sum() == 100
+    for k in (65, 128):
+        got = g.search_exact_allowed(q, k, ids[nodes])
+        same(got, R.exact_topk(dist, k, live=allowed_nodes, ids=ids), f"d={d} {dtype} allowed, k={k}")
+        assert np.all(got.counts == min(k, 100))
+
+
 @pytest.mark.parametrize("d,dtype", [(130, "f32"), (10, "f16")])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_graphs_around_the_tile_size_and_k_above_the_live_count(fv, ctx, n, d, dtype):
