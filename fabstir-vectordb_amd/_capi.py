@@ -61,6 +61,14 @@ class GraphHealth(C.Structure):
 VACUUM_KEEP_ROWS = 1  # FVDB_VACUUM_KEEP_ROWS
 HEALTH_SKIP_REACH, HEALTH_SKIP_COMPONENTS = 1, 2  # FVDB_HEALTH_SKIP_*
 
+
+class MetaInfo(C.Structure):
+    """fvdb_meta_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u64) for n in ("slots", "present", "columns", "live_elements", "dead_elements", "hbm_bytes")]
+
+
+u8p = C.POINTER(C.c_uint8)
+
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
 # tests/test_cabi_symbols.py checks the built library exports each of them.
 SIGNATURES = {
@@ -223,6 +231,17 @@ SIGNATURES = {
     "fvdb_search_quality_lists_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     # search quality over a grid of ef and n_probe
     "fvdb_quality_grid_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]),
+    # metadata columns: filters evaluated on the device
+    "fvdb_meta_create": (i32, [vp, C.POINTER(vp)]),
+    "fvdb_meta_destroy": (None, [vp]),
+    "fvdb_meta_info": (i32, [vp, C.POINTER(MetaInfo)]),
+    "fvdb_meta_set_rows": (i32, [vp, u64, u64, u64p, u8p]),
+    "fvdb_meta_set_present": (i32, [vp, u32p, u8p, u64]),
+    "fvdb_meta_add_column": (i32, [vp, u32p]),
+    "fvdb_meta_set_cells": (i32, [vp, u32, u32p, u8p, u64p, u64, u8p, u64p, u64]),
+    "fvdb_meta_eval": (i32, [vp, u32p, u32, u32p, u64p, u32, u64p, u64p]),
+    "fvdb_meta_eval_fetch": (i32, [vp, u64p, u32p, u32p]),
+    "fvdb_meta_eval_dev": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u64p, u64p]),
 }
 
 _lib = None

@@ -3088,3 +3088,4 @@ int fvdb_scorer_run(fvdb_scorer* sc, uint32_t B, uint32_t C) {
 #include "comm_sharded.h"
 #include "allow_masks.h"
 #include "flat_search.h"
+#include "meta_table.h"

@@ -796,7 +796,17 @@ int HNSWIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim, u
     const size_t o = first[g];
     Search s{Search::kTraversal, q_dev + o * dim, true, n_of[g], dim, k, ef, &gi[o * k], &gd[o * k], &gc[o]};
     s.view = views[g].get(), s.slot = slot, s.owns_slot = true;
-    if ((rc = run(s))) return rc;
+    rc = run(s);
+    // A traversal the caller's slot cannot hold runs in slot 0 under search_mu_, the way finish() runs a search nothing was
+    // enqueued for.  The case in mind is padded dimensions (d not a multiple of 4: fvdb_graph_search_dev_slot pads the
+    // queries into one buffer, slot 0's); any other FVDB_E_UNSUPPORTED fails there the same way again.  Before, a
+    // grouped search of a HybridIndex at such a d with an unfiltered request was refused.  Like finish(), this does not
+    // exclude a HybridIndex call that holds the lease on slot 0 without search_mu_.
+    if (rc == FVDB_E_UNSUPPORTED && slot != 0) {
+      s.slot = 0, s.owns_slot = false;
+      rc = run(s);
+    }
+    if (rc) return rc;
   }
   for (uint32_t b = 0; b < B; ++b) {
     std::memcpy(ids + (size_t)b * k, &gi[(size_t)place[b] * k], (size_t)k * 8);

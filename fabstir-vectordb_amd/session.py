@@ -143,6 +143,8 @@ class VectorDbSession:
         self.now = now
         self.destroyed = False
         self.schema = None                                  # MetadataSchema or None (set_schema)
+        self._meta_columns = None                           # MetadataColumns, made by the first "resident" filter
+        self._filter_info = None                            # last_filter_info()
 
     # -- add_vectors: session.rs:340-432 -------------------------------------------------------
     def add_vectors(self, vectors):
@@ -159,28 +161,33 @@ class VectorDbSession:
         if not self.index.is_initialized() and vectors:
             training = np.stack([js_array_to_vec_f32(v["vector"]) for v in vectors[:10]])  # first 10 (:367-371)
             self.index.initialize(training)
-        for inp in vectors:
-            if self.schema is not None:  # :388-392, before anything of this vector is stored
+        stored = []  # row ids this call stored, for the resident metadata columns
+        try:
+            for inp in vectors:
+                if self.schema is not None:  # :388-392, before anything of this vector is stored
+                    try:
+                        self.schema.validate(inp.get("metadata", {}))
+                    except SchemaError as e:
+                        raise SessionError(f"Schema validation failed for vector '{inp['id']}': {e}") from e
+                vid = VectorId(inp["id"])
+                vec = js_array_to_vec_f32(inp["vector"])
+                if vec.size != self.vector_dimension:
+                    raise SessionError(f"Vector dimension mismatch: expected {self.vector_dimension}, got {vec.size}")
                 try:
-                    self.schema.validate(inp.get("metadata", {}))
-                except SchemaError as e:
-                    raise SessionError(f"Schema validation failed for vector '{inp['id']}': {e}") from e
-            vid = VectorId(inp["id"])
-            vec = js_array_to_vec_f32(inp["vector"])
-            if vec.size != self.vector_dimension:
-                raise SessionError(f"Vector dimension mismatch: expected {self.vector_dimension}, got {vec.size}")
-            try:
-                self.index.insert(vid.row_id(), vec, now=self.now)
-            except Exception as e:  # index errors surface as strings (bindings/node/src/error.rs:61-65)
-                raise SessionError(f"Failed to add vector: {e}") from e
-            md = inp.get("metadata", {})
-            if isinstance(md, dict):
-                md = dict(md)
-                md["_originalId"] = inp["id"]
-            else:
-                md = {"_originalId": inp["id"], "_userMetadata": md}
-            self.metadata[vid.to_string()] = md
-            self._rows[vid.row_id()] = vid.to_string()
+                    self.index.insert(vid.row_id(), vec, now=self.now)
+                except Exception as e:  # index errors surface as strings (bindings/node/src/error.rs:61-65)
+                    raise SessionError(f"Failed to add vector: {e}") from e
+                md = inp.get("metadata", {})
+                if isinstance(md, dict):
+                    md = dict(md)
+                    md["_originalId"] = inp["id"]
+                else:
+                    md = {"_originalId": inp["id"], "_userMetadata": md}
+                self.metadata[vid.to_string()] = md
+                self._rows[vid.row_id()] = vid.to_string()
+                stored.append(vid.row_id())
+        finally:  # whatever was stored before a failure is in the map, so it is in the columns too
+            self._columns_in_step(lambda cols: cols.sync_rows(stored, self._rows, self.metadata) if stored else None)
 
     addVectors = add_vectors
 
@@ -214,9 +221,11 @@ class VectorDbSession:
         # "filterMode" (not in the reference): absent or "oversample" = the reference's filter path below; "pushdown" = the
         # filter is evaluated over the metadata map once and the matching ids go down as an allow-set that the device
         # applies inside the search (HybridIndex::search_allowed), so up to k matches come back however selective it is
+        # "resident" = "pushdown" with the allow-set evaluated on the device over metadata columns kept in HBM
+        # (metadata_columns.py): the same ids in the same order, without the walk over the map
         mode = options.get("filterMode", "oversample")
-        if mode not in ("oversample", "pushdown"):
-            raise SessionError(f'Invalid filterMode: {mode!r} (expected "oversample" or "pushdown")')
+        if mode not in ("oversample", "pushdown", "resident"):
+            raise SessionError(f'Invalid filterMode: {mode!r} (expected "oversample", "pushdown" or "resident")')
         # with a filter: 3 k candidates, keep those whose metadata match, truncate — HybridIndex::search_with_filter of
         # the host mirror (src/hybrid/core.rs:513-549); this side only answers "does this id's metadata match"
         matches = None
@@ -225,7 +234,10 @@ class VectorDbSession:
                 key = self._rows.get(rid)
                 return key in self.metadata and flt.matches(self.metadata[key])
         try:
-            if flt is not None and mode == "pushdown":
+            if flt is not None and mode == "resident":
+                allowed = self._resident_allowed(flt)
+                res = self.index.search_allowed(q.reshape(1, -1), int(k), allowed, now=self.now)  # defaults: ef 50, nprobe 10
+            elif flt is not None and mode == "pushdown":
                 allowed = np.fromiter((rid for rid in self._rows if matches(rid)), np.uint64)
                 res = self.index.search_allowed(q.reshape(1, -1), int(k), allowed, now=self.now)  # defaults: ef 50, nprobe 10
             else:
@@ -233,6 +245,44 @@ class VectorDbSession:
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
         return self._results_of(res[0], threshold, bool(options.get("includeVectors", False)))  # session.rs:229-231
+
+    # -- "resident" filters: metadata columns in HBM (metadata_columns.py) -------------------------------------------
+    def _resident_allowed(self, flt):
+        """The allow-set of `flt` from the metadata columns: the ids "pushdown" computes, in the same order."""
+        from .metadata_columns import MetadataColumns
+        cols = getattr(self, "_meta_columns", None)
+        if cols is None:
+            cols = self._meta_columns = MetadataColumns(self.ctx, self._rows, self.metadata)
+        allowed, info = cols.evaluate(flt, self.metadata)
+        self._filter_info = info
+        return allowed
+
+    def _columns_in_step(self, update):
+        """update(columns) where a table exists.  The map is the truth: if the table cannot follow it (an engine error, no
+        memory), the table is dropped and the next "resident" filter rebuilds it from the map, so the caller's own
+        outcome — its result or the error it is raising — stands."""
+        cols = getattr(self, "_meta_columns", None)
+        if cols is None:
+            return
+        try:
+            update(cols)
+        except Exception:  # noqa: BLE001
+            self.refresh_metadata_columns()
+
+    def refresh_metadata_columns(self):
+        """For callers who changed `session.metadata` directly: the columns are dropped and rebuilt from the map by the
+        next "resident" filter."""
+        cols = getattr(self, "_meta_columns", None)
+        if cols is not None:
+            cols.close()
+        self._meta_columns = None
+
+    def last_filter_info(self):
+        """What the last "resident" filter did: route ("device", or "host" when the filter exceeds the engine's program
+        limits and the map was walked), slots, matches, unknown (slots the device left to the host), columns_created,
+        and the milliseconds of each step.  None before the first one."""
+        info = getattr(self, "_filter_info", None)
+        return None if info is None else dict(info)
 
     def _results_of(self, hits, threshold, include_vectors):
         """One query's (ids, distances) as the result list search() returns: score, threshold, metadata, vectors."""
@@ -272,8 +322,9 @@ class VectorDbSession:
         """search(query_vectors[i], k, options_list[i]) for every i, served by ONE index call
         (HybridIndex.search_allowed_groups): each distinct filter is evaluated over the metadata map once and becomes one
         allow-set, requests with equal filters (equal canonical JSON) share it, requests without a filter take the
-        "no filter" group.  A filtered request must say "filterMode": "pushdown" — the oversampling path keeps what is
-        left of 3 k candidates and cannot share a batch.  Returns one result list per query."""
+        "no filter" group.  A filtered request must say "filterMode": "pushdown" or "resident" (the allow-set evaluated on
+        the device; groups are keyed by mode and filter) — the oversampling path keeps what is left
+        of 3 k candidates and cannot share a batch.  Returns one result list per query."""
         import json
         if self.destroyed:
             raise SessionError("Session already destroyed")
@@ -291,10 +342,10 @@ class VectorDbSession:
             key = None
             if options.get("filter") is not None:
                 mode = options.get("filterMode", "oversample")
-                if mode != "pushdown":
+                if mode not in ("pushdown", "resident"):
                     raise SessionError(f'search_many: request {i} has a filter with filterMode {mode!r}; a filtered request '
-                                       'in a batch needs "filterMode": "pushdown"')
-                key = json.dumps(options["filter"], sort_keys=True, separators=(",", ":"))
+                                       'in a batch needs "filterMode": "pushdown" or "resident"')
+                key = (mode, json.dumps(options["filter"], sort_keys=True, separators=(",", ":")))
             if key not in group_of_key:
                 allowed = None
                 if key is not None:
@@ -302,8 +353,11 @@ class VectorDbSession:
                         flt = MetadataFilter.from_json(options["filter"])
                     except FilterError as e:
                         raise SessionError(f"Invalid filter: {e}") from e
-                    allowed = np.fromiter((rid for rid, name in self._rows.items()
-                                           if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                    if key[0] == "resident":
+                        allowed = self._resident_allowed(flt)
+                    else:
+                        allowed = np.fromiter((rid for rid, name in self._rows.items()
+                                               if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
                 group_of_key[key] = len(allow_sets)
                 allow_sets.append(allowed)
             group_of_query.append(group_of_key[key])
@@ -372,6 +426,7 @@ class VectorDbSession:
         except Exception as e:
             raise SessionError(f"Failed to delete vector: {e}") from e
         self.metadata.pop(vid.to_string(), None)  # :464-467
+        self._columns_in_step(lambda cols: cols.set_absent(vid.row_id()))
 
     deleteVector = delete_vector
 
@@ -396,6 +451,8 @@ class VectorDbSession:
         done = matching[:ok]  # the first `successful` entries, as the reference takes them (:553-558)
         for key, _ in done:
             self.metadata.pop(key, None)
+        # the entries are gone from the map, so their slots are not present any more
+        self._columns_in_step(lambda cols: cols.set_absent_many([VectorId(oid).row_id() for _, oid in done]))
         return {"deleted_count": ok, "deleted_ids": [oid for _, oid in done]}
 
     deleteByMetadata = delete_by_metadata
@@ -418,6 +475,12 @@ class VectorDbSession:
         else:
             md = {"_originalId": id, "_userMetadata": metadata}
         self.metadata[key] = md
+        def rewrite(cols):
+            rid = VectorId(id).row_id()
+            if rid in self._rows:
+                cols.sync_rows([rid], self._rows, self.metadata)
+
+        self._columns_in_step(rewrite)
 
     updateMetadata = update_metadata
 
@@ -483,6 +546,7 @@ class VectorDbSession:
                 raise SessionError(f"Incompatible index version: {e}") from e
             raise SessionError(f"Failed to load index: {e}") from e
         self.index = index
+        self.refresh_metadata_columns()  # another set of rows: the columns are rebuilt by the next "resident" filter
         self._rows = {rid: chunked.display_id(b) for rid, b in table.items()}
         data = self.storage.get(f"{cid}/metadata_map.cbor")
         if data is None:
@@ -526,6 +590,7 @@ class VectorDbSession:
         return self.index.hnsw().graph_health(reach=reach, components=components)
 
     def destroy(self):
+        self.refresh_metadata_columns()
         self.destroyed = True
         self.index = None
 

@@ -873,6 +873,107 @@ int fvdb_ivf_search_sharded_wide_begin(fvdb_sharded* s, fvdb_ctx* on, uint32_t s
                                        float* out_dist_dev, uint32_t* out_counts_dev);
 int fvdb_ivf_search_sharded_end(fvdb_sharded* s, fvdb_ctx* on, uint32_t slot);
 
+/* ---- metadata columns: filters evaluated on the device -------------------------------
+ * A table of typed metadata columns resident in HBM and one evaluation pass per filter.  Together they replace the
+ * walk of MetadataFilter::matches (src/core/metadata_filter.rs:265-338) over every entry of the session's metadata
+ * map (bindings/node/src/session.rs:233-247 hands the filter to the search; the allow-set form of that search is
+ * fvdb_mask_create_*).  The result is the list of row ids whose metadata match, in slot order, plus the slots the
+ * device could not decide.
+ *
+ * Slots.  A table has slots 0 .. slots-1, never reordered, never reused for another id: per slot a uint64 row id and a
+ * `present` byte (the row has an entry in the metadata map).  A slot that is not present matches no filter.
+ * Columns.  One per metadata path, as two arrays: tag[slot] (one byte, FVDB_META_*) and val[slot] (eight bytes):
+ *   MISSING, NULL, COMPLEX  no payload        BOOL    0 or 1            INT     the int64
+ *   FLOAT   the bits of the f64              STRING  the caller's dense code of the string (exact, assigned by the host)
+ *   ARRAY   its elements live in the column's element arrays; an element carries any tag but MISSING and ARRAY
+ * COMPLEX marks a value the device does not decide (an object compared whole, a nested list, an integer outside
+ * int64); a leaf that needs a comparison with one is "unknown" on that slot.  A new column is MISSING everywhere.
+ *
+ * Program.  Postfix, over three-valued results (true, false, unknown); n_instrs instructions of four uint32 each:
+ *   { FVDB_META_OP_EQUALS,               column, c, 0 }   cell (or any element of an ARRAY cell) equals constant c
+ *   { FVDB_META_OP_IN | flags << 8,      column, c, n }   a scalar cell equals one of the constants c .. c+n-1, which are
+ *                                                          sorted ascending by (tag, key), distinct, none COMPLEX or NEVER;
+ *                                                          flags: FVDB_META_IN_HAS_COMPLEX (the list also held a COMPLEX
+ *                                                          constant), FVDB_META_IN_HAS_ANY (the list was not empty)
+ *   { FVDB_META_OP_RANGE | flags << 8,   column, c, 0 }   constants c (lower) and c+1 (upper): FLOAT, key = the f64's bits;
+ *                                                          flags FVDB_META_RANGE_*; INT cells go to f64 to nearest even
+ *   { FVDB_META_OP_AND / _OR,            n, 0, 0 }        pops n results, pushes their Kleene AND / OR (n = 0: true / false)
+ * Constants are (tag, key) pairs.  key: NULL 0; BOOL 0 / 1; STRING the code; INT the int64 with its sign bit flipped;
+ * FLOAT the f64's bits with -0.0 folded onto 0.0, then all bits flipped if negative, else the sign bit set (so that key
+ * order is value order).  FVDB_META_NEVER is a constant that equals nothing (a NaN, a string without a code);
+ * FVDB_META_COMPLEX one that only the host can compare.  Equality needs equal tags (INT never equals FLOAT, BOOL is no
+ * number, NULL equals NULL, a NaN equals nothing, 0.0 equals -0.0).  The program must leave exactly one result.
+ *
+ * Limits (FVDB_E_UNSUPPORTED beyond them): FVDB_META_MAX_PROGRAM instructions, FVDB_META_MAX_STACK results on the stack
+ * at once (so also operands of one AND / OR), FVDB_META_MAX_CONSTS constants, fewer than 2^32 slots, fewer than 2^32
+ * elements in one column.  Malformed arguments (a column, constant or slot out of range, an unknown tag or op, unsorted
+ * IN constants, a stack underflow, more or less than one result left) are FVDB_E_INVALID before anything is enqueued.
+ * Every entry point locks the table: evaluations and mutations of one table are serialised. */
+#define FVDB_META_MISSING 0u
+#define FVDB_META_NULL 1u
+#define FVDB_META_BOOL 2u
+#define FVDB_META_INT 3u
+#define FVDB_META_FLOAT 4u
+#define FVDB_META_STRING 5u
+#define FVDB_META_ARRAY 6u
+#define FVDB_META_COMPLEX 7u
+#define FVDB_META_NEVER 15u
+#define FVDB_META_OP_EQUALS 1u
+#define FVDB_META_OP_IN 2u
+#define FVDB_META_OP_RANGE 3u
+#define FVDB_META_OP_AND 4u
+#define FVDB_META_OP_OR 5u
+#define FVDB_META_IN_HAS_COMPLEX 1u
+#define FVDB_META_IN_HAS_ANY 2u
+#define FVDB_META_RANGE_HAS_MIN 1u
+#define FVDB_META_RANGE_MIN_INCLUSIVE 2u
+#define FVDB_META_RANGE_HAS_MAX 4u
+#define FVDB_META_RANGE_MAX_INCLUSIVE 8u
+#define FVDB_META_MAX_PROGRAM 1024u
+#define FVDB_META_MAX_STACK 16u
+#define FVDB_META_MAX_CONSTS 65536u
+typedef struct fvdb_meta fvdb_meta;
+typedef struct fvdb_meta_info_t {
+  uint64_t slots, present, columns;
+  uint64_t live_elements, dead_elements; /* elements of ARRAY cells in use / left behind by rewritten cells, all columns */
+  uint64_t hbm_bytes;                    /* device memory the table holds, result buffers included */
+} fvdb_meta_info_t;
+/* The table itself: replaces the session's `metadata: HashMap<String, Value>` (bindings/node/src/session.rs:69) as
+ * what a filter is evaluated over. */
+int fvdb_meta_create(fvdb_ctx* ctx, fvdb_meta** out);
+void fvdb_meta_destroy(fvdb_meta* t);
+int fvdb_meta_info(fvdb_meta* t, fvdb_meta_info_t* out);
+/* Slots first .. first+n-1 get ids[i] and present[i] (session.rs:394-415: an entry of the metadata map per added
+ * vector).  first <= slots: a run may rewrite slots, extend the table, or both; new slots are MISSING in every column.
+ * A run over existing slots stores the ids it is given: that a slot is never reused for another id is the caller's
+ * rule to keep, the table does not check it. */
+int fvdb_meta_set_rows(fvdb_meta* t, uint64_t first, uint64_t n, const uint64_t* ids, const uint8_t* present);
+/* present[i] for the listed slots, strictly ascending (session.rs:464-467: delete_vector drops the entry). */
+int fvdb_meta_set_present(fvdb_meta* t, const uint32_t* slots, const uint8_t* present, uint64_t n);
+/* A new column, MISSING everywhere; its index to *out_column (metadata_filter.rs:360-375: one per dotted path). */
+int fvdb_meta_add_column(fvdb_meta* t, uint32_t* out_column);
+/* Cells of one column at the listed slots (strictly ascending): tags[i], vals[i] (session.rs:581-632 update_metadata;
+ * the value a path reaches, metadata_filter.rs:360-375).  For an ARRAY cell vals[i] is its LENGTH and its elements are
+ * the next vals[i] entries of elem_tags / elem_vals, taken in cell order; n_elems is their total.  A BOOL payload other
+ * than 0 or 1 (cell or element) is FVDB_E_INVALID.  Rewriting an ARRAY
+ * cell appends its elements and leaves the old ones dead (fvdb_meta_info counts them). */
+int fvdb_meta_set_cells(fvdb_meta* t, uint32_t column, const uint32_t* slots, const uint8_t* tags, const uint64_t* vals, uint64_t n,
+                        const uint8_t* elem_tags, const uint64_t* elem_vals, uint64_t n_elems);
+/* Runs a program over every slot (metadata_filter.rs:265-338 for every row at once).  The matching row ids and the
+ * unknown slots stay in buffers the table owns, both in ascending slot order, until the next evaluation;
+ * *out_matches / *out_unknown are their counts.  An unknown slot is in neither list of matches: the caller decides it
+ * and merges it in.  Returns after the pass has completed. */
+int fvdb_meta_eval(fvdb_meta* t, const uint32_t* instrs, uint32_t n_instrs, const uint32_t* const_tags, const uint64_t* const_keys,
+                   uint32_t n_consts, uint64_t* out_matches, uint64_t* out_unknown);
+/* The last evaluation's results to host memory: ids[matches], unknown_slots[unknown], and unknown_ranks[unknown] = the
+ * number of matching slots in front of each unknown slot, which is where a decided one is merged in.  A NULL pointer
+ * skips that array.  FVDB_E_INVALID when nothing has been evaluated. */
+int fvdb_meta_eval_fetch(fvdb_meta* t, uint64_t* ids, uint32_t* unknown_slots, uint32_t* unknown_ranks);
+/* The same three arrays where they are, in HBM, with their counts (any pointer may be NULL): for building a mask
+ * without the ids visiting the host.  Valid until the table's next evaluation, growth or destruction. */
+int fvdb_meta_eval_dev(fvdb_meta* t, const uint64_t** ids_dev, const uint32_t** unknown_slots_dev, const uint32_t** unknown_ranks_dev,
+                       uint64_t* out_matches, uint64_t* out_unknown);
+
 #ifdef __cplusplus
 }
 #endif
