@@ -228,6 +228,11 @@ SIGNATURES = {
     "fvdb_graph_scan_allowed_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    # radius search
+    "fvdb_graph_search_flat_radius_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp]),
+    "fvdb_graph_count_within_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, vp, vp]),
+    "fvdb_ivf_search_radius_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]),
+    "fvdb_ivf_search_radius": (i32, [vp, f32p, u32, f32p, u32, u32, u64p, f32p, u32p, u32p]),
     "fvdb_search_quality_lists_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     # search quality over a grid of ef and n_probe
     "fvdb_quality_grid_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]),

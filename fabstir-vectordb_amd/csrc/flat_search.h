@@ -1,5 +1,5 @@
 // flat_search.h — exact search of the C ABI (include/fvdb.h, "exact search"): the flat scan of a
-// graph's row store, its form for k up to FVDB_MAX_K_WIDE (section 9q), the comparison of two resident id blocks and
+// graph's row store, its form for k up to FVDB_MAX_K_WIDE (section 9q), radius search and count (section 9t), the comparison of two resident id blocks and
 // the quality grid over the parts of a hybrid search (section 9r).
 // Included at the end of fvdb_hip.cpp, after allow_masks.h, for the same reason: the kernels lean on kernels_scan.h,
 // which lives in this translation unit, and what they need of the graph comes through graph_mask_source /
@@ -8,6 +8,7 @@
 #include "kernels_flat.h"
 #include "kernels_flat_wide.h"
 #include "kernels_grid.h"
+#include "kernels_range.h"
 
 namespace {
 
@@ -101,13 +102,13 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
   return FVDB_OK;
 }
 
-int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
-                                         uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
-  GraphMaskSource src{};
-  fvdb_ctx* ctx = nullptr;
-  int rc = flat_check_args(g, on, slot, mask, k, FVDB_MAX_K_WIDE, "exact scan: k must be in 1..FVDB_MAX_K_WIDE",
-                           q_dev && out_nodes_dev && out_dist_dev && out_counts_dev, &src, &ctx);
-  if (rc) return rc;
+// The arena form of the flat scan, behind the checks of its two entry points: every (query, row) distance word to the
+// arena, then one workgroup per query selects — the k nearest (radius_dev null), or the ball of radius_dev[b] capped at k
+// with its size to out_totals_dev.
+static int flat_arena_search(fvdb_graph* g, fvdb_ctx* ctx, const GraphMaskSource& src, uint32_t slot, fvdb_mask* mask,
+                             const float* q_dev, uint32_t B, uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev,
+                             uint32_t* out_counts_dev, const float* radius_dev, uint32_t* out_totals_dev) {
+  int rc = FVDB_OK;
   if (B == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   fvdb_store* s = src.store;
@@ -142,7 +143,68 @@ int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t s
     sel.out_nodes = out_nodes_dev + (size_t)b0 * k;
     sel.out_dist = out_dist_dev + (size_t)b0 * k;
     sel.out_counts = out_counts_dev + b0;
-    hipLaunchKernelGGL(flat_select_kernel, dim3(Bs), dim3(kWideSelThreads), 0, ctx->stream, sel);
+    if (radius_dev)
+      hipLaunchKernelGGL(range_flat_select_kernel, dim3(Bs), dim3(kWideSelThreads), 0, ctx->stream,
+                         RangeFlatArgs{sel, radius_dev + b0, out_totals_dev + b0});
+    else
+      hipLaunchKernelGGL(flat_select_kernel, dim3(Bs), dim3(kWideSelThreads), 0, ctx->stream, sel);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return FVDB_OK;
+}
+
+int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                         uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev, uint32_t* out_counts_dev) {
+  GraphMaskSource src{};
+  fvdb_ctx* ctx = nullptr;
+  int rc = flat_check_args(g, on, slot, mask, k, FVDB_MAX_K_WIDE, "exact scan: k must be in 1..FVDB_MAX_K_WIDE",
+                           q_dev && out_nodes_dev && out_dist_dev && out_counts_dev, &src, &ctx);
+  if (rc) return rc;
+  return flat_arena_search(g, ctx, src, slot, mask, q_dev, B, k, out_nodes_dev, out_dist_dev, out_counts_dev, nullptr, nullptr);
+}
+
+// ---- radius search ----
+int fvdb_graph_search_flat_radius_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                           const float* radius_dev, uint32_t max_results, uint32_t* out_nodes_dev, float* out_dist_dev,
+                                           uint32_t* out_counts_dev, uint32_t* out_totals_dev) {
+  GraphMaskSource src{};
+  fvdb_ctx* ctx = nullptr;
+  int rc = flat_check_args(g, on, slot, mask, max_results, FVDB_MAX_K_WIDE, "radius search: max_results must be in 1..FVDB_MAX_K_WIDE",
+                           q_dev && radius_dev && out_nodes_dev && out_dist_dev && out_counts_dev && out_totals_dev, &src, &ctx);
+  if (rc) return rc;
+  return flat_arena_search(g, ctx, src, slot, mask, q_dev, B, max_results, out_nodes_dev, out_dist_dev, out_counts_dev, radius_dev,
+                           out_totals_dev);
+}
+
+// The size of every ball and nothing else: no arena.  Sub-batches only bound the grid and the padded queries' scratch.
+int fvdb_graph_count_within_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                     const float* radius_dev, uint32_t* out_totals_dev) {
+  GraphMaskSource src{};
+  fvdb_ctx* ctx = nullptr;
+  int rc = flat_check_args(g, on, slot, mask, 1, 1, "", q_dev && radius_dev && out_totals_dev, &src, &ctx);
+  if (rc) return rc;
+  if (B == 0) return FVDB_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  fvdb_store* s = src.store;
+  constexpr uint32_t Q = kFlatWideQ;
+  HIPCHK(ctx, hipMemsetAsync(out_totals_dev, 0, (size_t)B * 4, ctx->stream));
+  for (uint32_t b0 = 0; b0 < B; b0 += kFlatSubBatch) {
+    const uint32_t Bs = std::min(kFlatSubBatch, B - b0);
+    FlatCountArgs a{};
+    a.rows = s->data;
+    a.dead = mask ? mask->flags.as<uint32_t>() : src.deleted;
+    a.dpad = s->dpad;
+    a.n = src.n;
+    a.B = Bs;
+    flat_slice_plan(src.n, Bs, Q, &a.slices, &a.slice_tiles);
+    uint64_t* part = nullptr;
+    rc = graph_scan_inputs(g, ctx, slot, q_dev + (size_t)b0 * s->d, Bs, 0, &a.queries, &part);
+    if (rc) return rc;
+    a.radius = radius_dev + b0;
+    a.counts = out_totals_dev + b0;
+    if (a.slices)
+      hipLaunchKernelGGL((s->f16() ? flat_count_kernel<Q, half_t> : flat_count_kernel<Q, float>), dim3(cdiv(Bs, Q), cdiv(a.slices, 4)),
+                         dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
   }
   return FVDB_OK;

@@ -24,6 +24,7 @@
 #include "kernels_misc.h"
 #include "kernels_scan.h"
 #include "kernels_wide.h"
+#include "kernels_range.h"
 #include "kernels_rank.h"
 #include "kernels_curve.h"
 #include "kernels_coarse.h"
@@ -368,6 +369,9 @@ struct Batch {
   // wide selection, one allow-set per query: the device table of live words and each query's entry in it (both null otherwise)
   const uint64_t* const* words = nullptr;
   const uint32_t* group = nullptr;
+  // wide selection, radius search: the ball of radius[q] capped at k, its size to out_totals
+  const float* radius = nullptr;  // [B], device
+  uint32_t* out_totals = nullptr;
 };
 
 inline ListTable list_table(const fvdb_ivf* ivf) {
@@ -1179,7 +1183,13 @@ int run_fine_wide(fvdb_ivf* ivf, const Env& E, const Batch& b) {
   w.out_dist = b.out_dist;
   w.out_counts = b.out_counts;
   w.out_keys = b.out_keys;
-  if (b.glob_keys) {
+  if (b.radius) {
+    const RangeListArgs ra{w, b.radius, b.out_totals};
+    if (b.np <= kWideMaxProbes)
+      hipLaunchKernelGGL(range_list_select_kernel<true>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, ra);
+    else
+      hipLaunchKernelGGL(range_list_select_kernel<false>, dim3(b.B), dim3(kWideSelThreads), 0, ctx->stream, ra);
+  } else if (b.glob_keys) {
     HIPCHK(ctx, S.s_wgbase.ensure((size_t)b.B * b.np * 4));
     hipLaunchKernelGGL(wide_gbase_kernel, dim3(cdiv(b.B, 256)), dim3(256), 0, ctx->stream, b.probes, ivf->t_glob.as<uint32_t>(),
                        b.B, b.np, S.s_wgbase.as<uint32_t>());
@@ -1845,6 +1855,7 @@ struct IvfSearch {
     ALL,          // every list (ROLE_ALL), no coarse stage
     WIDE,         // the nprobe nearest lists, k <= FVDB_MAX_K_WIDE (run_fine_wide)
     SHARD_WIDE,   // WIDE on an index that may hold a shard of a larger one: keys by the logical index's seq
+    RADIUS,       // WIDE's lists and score stage; per query the rows within radius[b], at most k of them, and their number
     COARSE_ONLY,  // the coarse stage alone: probes_out is the result
   } kind;
   const float* q_dev;  // [B][d]
@@ -1862,6 +1873,9 @@ struct IvfSearch {
   // the pool's own, and each query's index into them.  Device pointers; the driver fills them in from GroupSource.
   const uint64_t* const* words = nullptr;  // [G + 1]
   const uint32_t* group = nullptr;         // [B]
+  // RADIUS: the radius of each query and where the size of its ball goes
+  const float* radius = nullptr;           // [B]
+  uint32_t* totals = nullptr;              // [B]
 
   // Queries o .. o + b of the request; np = min(nprobe, nlist) as the driver clamped it.  The only place a stride is written.
   IvfSearch slice(uint32_t o, uint32_t b, uint32_t d, uint32_t np) const {
@@ -1877,6 +1891,8 @@ struct IvfSearch {
     s.given_thr = at(given_thr, 1);
     s.probes_out = at(probes_out, np);
     s.group = at(group, 1);
+    s.radius = at(radius, 1);
+    s.totals = at(totals, 1);
     return s;
   }
 };
@@ -1884,7 +1900,8 @@ struct IvfSearch {
 // Whether a request takes the wide selection (run_fine_wide): asked for, or more lists probed (np = min(nprobe, nlist))
 // than the register path ranks and merges.
 inline bool wide_route(IvfSearch::Kind kind, uint32_t np) {
-  return kind == IvfSearch::WIDE || kind == IvfSearch::SHARD_WIDE || (kind == IvfSearch::PROBED && np > FVDB_MAX_K);
+  return kind == IvfSearch::WIDE || kind == IvfSearch::SHARD_WIDE || kind == IvfSearch::RADIUS ||
+         (kind == IvfSearch::PROBED && np > FVDB_MAX_K);
 }
 // The keys of a shard's wide search hold the logical index's seq in 32 bits, as the register path's do: 64 x the blocks
 // of np probed lists of the logical index must stay below 2^32.  Bounded by np longest lists and by all lists together.
@@ -1985,7 +2002,7 @@ int ivf_search(fvdb_ivf* ivf, const Env& E, const IvfSearch& R_in, const GroupSo
     }
     if (R.kind == IvfSearch::COARSE_ONLY) continue;
     const Batch b{qpad, probes, r.B, r.k, np, r.ids, r.dist, r.counts, r.keys, r.given_thr, R.kind == IvfSearch::SHARD_WIDE,
-                  r.words, r.group};
+                  r.words, r.group, r.radius, r.totals};
     rc = wide ? run_fine_wide(ivf, E, b) : run_fine(ivf, E, b, all ? ROLE_ALL : ROLE_LIST);
     if (rc) return rc;
     // per sub-batch: each one records the stage events anew, so their intervals are folded in before the next does
@@ -2160,6 +2177,21 @@ int fvdb_ivf_search_wide_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fv
                         IvfSearch{IvfSearch::WIDE, q_dev, B, k, nprobe, out_ids_dev, out_dist_dev, out_counts_dev, out_keys_dev});
 }
 
+// Radius search over the probed lists: fvdb_ivf_search_wide_dev_slot's lists, score stage and
+// rules; the selection keeps the rows within radius_dev[b], at most max_results of them, and counts them all.
+int fvdb_ivf_search_radius_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    const float* radius_dev, uint32_t max_results, uint32_t nprobe, uint64_t* out_ids_dev,
+                                    float* out_dist_dev, uint32_t* out_counts_dev, uint32_t* out_totals_dev) {
+  if (!ivf) return FVDB_E_INVALID;
+  return on_slot(ivf, on, slot, mask ? masked_by(mask) : kNoMask, [&](const Env& E) -> int {
+    if (!radius_dev || !out_totals_dev) FAIL(E.ctx, FVDB_E_INVALID, "null argument");  // after the slot and the mask, as ever
+    IvfSearch R{IvfSearch::RADIUS, q_dev, B, max_results, nprobe, out_ids_dev, out_dist_dev, out_counts_dev};
+    R.radius = radius_dev;
+    R.totals = out_totals_dev;
+    return ivf_search(ivf, E, R);
+  });
+}
+
 // The wide search with one allow-set per query.  Everything is checked before anything is enqueued:
 // every mask of the table, named by a query or not, and every group index.
 int fvdb_ivf_search_groups_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* const* masks, uint32_t G,
@@ -2303,8 +2335,10 @@ int fvdb_ivf_quality_curve_dev(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_
 }
 
 // The blocking host-pointer searches: the batch is staged in a leased set, searched there, and the results copied back.
+// RADIUS: radius[B] goes in behind the queries and out_totals[B] comes back behind the counts.
 static int search_host(fvdb_ivf* ivf, IvfSearch::Kind kind, const float* q, uint32_t B, uint32_t k, uint32_t nprobe,
-                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts) {
+                       uint64_t* out_ids, float* out_dist, uint32_t* out_counts, const float* radius = nullptr,
+                       uint32_t* out_totals = nullptr) {
   // ivf_search makes these refusals again, for every entry point; here they come before the input is read and a set is
   // leased, in the order callers know: not trained, nothing to do, k, non-finite input
   if (!ivf->trained) FAIL(ivf->ctx, FVDB_E_NOT_TRAINED, "index not trained");
@@ -2313,19 +2347,32 @@ static int search_host(fvdb_ivf* ivf, IvfSearch::Kind kind, const float* q, uint
   if (rc) return rc;
   rc = check_finite(ivf->ctx, q, (uint64_t)B * ivf->d);
   if (rc) return rc;
+  if (kind == IvfSearch::RADIUS) {
+    if (!radius || !out_totals) FAIL(ivf->ctx, FVDB_E_INVALID, "null argument");
+    for (uint32_t b = 0; b < B; ++b)
+      if (!(radius[b] >= 0.0f)) FAIL(ivf->ctx, FVDB_E_INVALID, "radius must be >= 0 (+inf allowed), not negative or NaN");
+  }
   return on_lease(ivf, [&](const Env& E) -> int {
     fvdb_ctx* ctx = E.ctx;
     IvfScratch& S = *E.S;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, S.s_in.ensure((size_t)B * ivf->d * 4));
+    const size_t q_bytes = (size_t)B * ivf->d * 4;
+    HIPCHK(ctx, S.s_in.ensure(q_bytes + (size_t)B * 4));
     HIPCHK(ctx, S.s_out_ids.ensure((size_t)B * k * 8));
     HIPCHK(ctx, S.s_out_dist.ensure((size_t)B * k * 4));
-    HIPCHK(ctx, S.s_out_cnt.ensure((size_t)B * 4));
-    HIPCHK(ctx, hipMemcpyAsync(S.s_in.p, q, (size_t)B * ivf->d * 4, hipMemcpyHostToDevice, ctx->stream));
-    int r = ivf_search(ivf, E,
-                       IvfSearch{kind, S.s_in.as<float>(), B, k, nprobe, S.s_out_ids.as<uint64_t>(), S.s_out_dist.as<float>(),
-                                 S.s_out_cnt.as<uint32_t>()});
+    HIPCHK(ctx, S.s_out_cnt.ensure((size_t)B * 8));
+    HIPCHK(ctx, hipMemcpyAsync(S.s_in.p, q, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    IvfSearch R{kind, S.s_in.as<float>(), B, k, nprobe, S.s_out_ids.as<uint64_t>(), S.s_out_dist.as<float>(),
+                S.s_out_cnt.as<uint32_t>()};
+    if (radius) {
+      HIPCHK(ctx, hipMemcpyAsync((char*)S.s_in.p + q_bytes, radius, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+      R.radius = (const float*)((char*)S.s_in.p + q_bytes);
+      R.totals = S.s_out_cnt.as<uint32_t>() + B;
+    }
+    int r = ivf_search(ivf, E, R);
     if (r) return r;
+    if (out_totals)
+      HIPCHK(ctx, hipMemcpyAsync(out_totals, S.s_out_cnt.as<uint32_t>() + B, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_ids, S.s_out_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_dist, S.s_out_dist.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (out_counts)
@@ -2342,6 +2389,10 @@ int fvdb_ivf_search(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint3
 int fvdb_ivf_search_wide(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                          float* out_dist, uint32_t* out_counts) {
   return search_host(ivf, IvfSearch::WIDE, q, B, k, nprobe, out_ids, out_dist, out_counts);
+}
+int fvdb_ivf_search_radius(fvdb_ivf* ivf, const float* q, uint32_t B, const float* radius, uint32_t max_results, uint32_t nprobe,
+                           uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint32_t* out_totals) {
+  return search_host(ivf, IvfSearch::RADIUS, q, B, max_results, nprobe, out_ids, out_dist, out_counts, radius, out_totals);
 }
 int fvdb_ivf_search_all(fvdb_ivf* ivf, const float* q, uint32_t B, uint32_t k, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_counts) {

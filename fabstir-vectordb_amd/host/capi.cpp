@@ -227,6 +227,34 @@ int fvh_hnsw_search_exact_wide_allowed(void* p, const float* q, uint32_t B, uint
                                        uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
   return ((HNSWIndex*)p)->search_exact_wide_allowed(q, B, d, k, allowed, n_allowed, ids, dist, counts);
 }
+// radius search: radius[B]; ids / dist [B][max_results], counts[B], totals[B].  allowed == NULL: no filter
+int fvh_hnsw_search_radius(void* p, const float* q, uint32_t B, uint32_t d, const float* radius, uint32_t max_results, uint64_t* ids,
+                           float* dist, uint32_t* counts, uint32_t* totals) {
+  return ((HNSWIndex*)p)->search_radius(q, B, d, radius, max_results, ids, dist, counts, totals);
+}
+int fvh_hnsw_search_radius_allowed(void* p, const float* q, uint32_t B, uint32_t d, const float* radius, uint32_t max_results,
+                                   const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts,
+                                   uint32_t* totals) {
+  return ((HNSWIndex*)p)->search_radius_allowed(q, B, d, radius, max_results, allowed, n_allowed, ids, dist, counts, totals);
+}
+int fvh_hnsw_count_within(void* p, const float* q, uint32_t B, uint32_t d, const float* radius, const uint64_t* allowed,
+                          uint64_t n_allowed, uint32_t* totals) {
+  return ((HNSWIndex*)p)->count_within(q, B, d, radius, allowed, n_allowed, totals);
+}
+int fvh_ivf_search_radius(void* p, const float* q, uint32_t B, uint32_t d, const float* radius, uint32_t max_results, uint32_t n_probe,
+                          const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals) {
+  return ((IVFIndex*)p)->search_radius(q, B, d, radius, max_results, n_probe, allowed, n_allowed, ids, dist, counts, totals);
+}
+int fvh_hybrid_search_radius(void* p, const float* q, uint32_t B, uint32_t d, const float* radius, uint64_t max_results,
+                             uint64_t ivf_n_probe, int search_recent, int search_historical, const uint64_t* allowed, uint64_t n_allowed,
+                             double now, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals) {
+  HybridSearchConfig c;
+  c.k = max_results;
+  c.ivf_n_probe = ivf_n_probe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_radius(q, B, d, radius, c, now, allowed, n_allowed, ids, dist, counts, totals);
+}
 int fvh_hnsw_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, float* out3,
                                           uint64_t* queries_evaluated) {
   SearchQuality s{};

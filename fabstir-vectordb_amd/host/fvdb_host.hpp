@@ -74,6 +74,14 @@ inline void fill_empty(uint64_t* ids, float* dist, uint32_t* counts, uint32_t B,
   }
 }
 
+// the radii of a radius search: each >= 0, +inf allowed; a negative or NaN one is FVDB_E_INVALID
+inline int check_radius(const float* radius, uint32_t B) {
+  if (B && !radius) return FVDB_E_INVALID;
+  for (uint32_t b = 0; b < B; ++b)
+    if (!(radius[b] >= 0.0f)) return FVDB_E_INVALID;
+  return FVDB_OK;
+}
+
 // Grow-only device block and, where the owner asks for one, its pinned host twin of the same size.  reserve() frees and
 // reallocates when the block is too small (contents are not kept); the owner's destructor calls release().
 struct DevBuf {
@@ -272,6 +280,14 @@ class IVFIndex {
   // results are in — the cached mask of search_allowed is left alone.
   int search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const AllowGroups& groups,
                             uint64_t* ids, float* dist, uint32_t* counts);
+  // Radius search (fvdb_ivf_search_radius): per query the live rows of the n_probe probed lists
+  // whose distance word is <= bits(radius[b]), the first min(total, max_results) of them in the wide search's order —
+  // search(k = max_results, n_probe) on the wide route, cut at the radius — and totals[b] = their exact number, over
+  // the probed lists only.  radius[B] in host memory, each >= 0 (+inf allowed), else FVDB_E_INVALID; max_results in
+  // 1..FVDB_MAX_K_WIDE.  allowed != nullptr: under that allow-set (the cached mask of search_allowed), rows outside it in
+  // neither results nor totals.
+  int search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, uint32_t n_probe,
+                    const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals);
   // the device mask for that allow-set (cached); search_dev under it
   int allowed_mask(const uint64_t* allowed, uint64_t n_allowed, MaskRef* out);
   int search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe,
@@ -425,6 +441,11 @@ class HNSWIndex {
     uint32_t slot = 0;                      // stream, scratch set and result block
     bool wide = false;                      // kExact only: k up to FVDB_MAX_K_WIDE, fvdb_graph_search_flat_wide_dev_slot
     bool owns_slot = false;                // the caller holds `slot` for the call (HybridIndex's lease): run() takes no lock
+    // kExact + wide, radius search: the rows within radius[b] (host memory, checked by the entry
+    // point), at most k of them, and the size of each ball to totals[B]; count_only: the sizes alone (k = 1, no ids)
+    const float* radius = nullptr;
+    uint32_t* totals = nullptr;
+    bool count_only = false;
     // filled in by admit() and stage()
     ViewRef held = nullptr;                 // keeps a by_list view alive
     enum Route { kAnswered, kHostWalk, kDevice } route = kAnswered;
@@ -484,6 +505,21 @@ class HNSWIndex {
                             float* dist, uint32_t* counts, uint32_t slot);
   int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
   int quality_impl(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out, bool wide);  // both forms
+  // Radius search (fvdb_graph_search_flat_radius_dev_slot): per query the live nodes whose distance
+  // word is <= bits(radius[b]) — radius[B] in host memory, each >= 0, +inf allowed; a negative or NaN one is
+  // FVDB_E_INVALID — the first min(total, max_results) of them by (distance bits, node index), which is
+  // search_exact_wide(k = max_results) cut at the radius, and totals[b] = their exact number.  Nodes map to ids as
+  // search_exact_wide maps them.  max_results in 1..FVDB_MAX_K_WIDE.  _allowed: under that allow-set (the cached view),
+  // rows outside it in neither results nor totals.  count_within: totals alone, by a scan that keeps no distances
+  // (fvdb_graph_count_within_dev_slot); allowed == nullptr: no filter.  _dev: queries in HBM, the caller's slot.
+  int search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, uint64_t* ids, float* dist,
+                    uint32_t* counts, uint32_t* totals);
+  int search_radius_allowed(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results,
+                            const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals);
+  int count_within(const float* q, uint32_t B, uint32_t dim, const float* radius, const uint64_t* allowed, uint64_t n_allowed,
+                   uint32_t* totals);
+  int search_radius_dev(const float* q_dev, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, const AllowView* view,
+                        uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals, uint32_t slot);
   // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every listed ef from ONE exact search (DESIGN.md
   // section 9r): one search(k, efs[i]) each, one fvdb_quality_grid_dev call per sub-batch.  out: E x 1, entry i what
   // the single call returns at efs[i], bit for bit; duplicates and any order are fine.  Refused before any search
@@ -832,6 +868,16 @@ class HybridIndex {
                         float* dist, uint32_t* counts);
   int evaluate_search_quality_wide(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
                                    SearchQuality* out);
+  // Radius search: search_exact_wide's migration step, read lock and sharded refusal; cfg.k is
+  // max_results (1..FVDB_MAX_K_WIDE) for each part and for the result.  The recent part is the graph's flat radius scan
+  // (HNSWIndex::search_radius_dev) and NOT a walk: a walk bounded by ef visits what its frontier reaches and cannot
+  // enumerate a ball, so the recent total is exact over every live node.  The historical part is
+  // IVFIndex::search_radius over the cfg.ivf_n_probe probed lists — every list when ivf_n_probe = n_clusters, the ball of
+  // the probed lists only below that.  The two capped lists go through the usual merge with k = max_results, and
+  // totals[b] = recent total + historical total: like that merge it does not de-duplicate, so an id that both parts hold
+  // within the radius counts twice.  allowed != nullptr: both parts under that allow-set (the cached view and mask).
+  int search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, const HybridSearchConfig& cfg, double now,
+                    const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals);
   // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every pair (efs[i], n_probes[j]) in one call
   // (DESIGN.md section 9r): one migration step; under ONE hold of the read lock one exact search, one traversal per
   // listed ef and one list search per listed n_probe, the PARTS kept; then fvdb_quality_grid_dev merges and counts

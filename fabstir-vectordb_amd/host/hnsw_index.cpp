@@ -480,6 +480,7 @@ int HNSWIndex::admit(Search& s) {
   if (exact && (s.k == 0 || s.k > (s.wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K))) return FVDB_E_UNSUPPORTED;
   if (exact && s.slot >= kSlots) return FVDB_E_INVALID;  // a traversal's slot is launch()'s to refuse, after all of this
   if (s.ids) fill_empty(s.ids, s.dist, s.counts, s.B, s.k);
+  if (s.totals) std::memset(s.totals, 0, (size_t)s.B * 4);
   // empty index -> empty results (:404-407); the exact scan needs the store too (a graph that has never held a row)
   if (!has_entry_ || (exact && !store_)) return FVDB_OK;
   if (!exact && filtered && nothing) return FVDB_OK;
@@ -520,12 +521,20 @@ int HNSWIndex::launch(Search& s) {
   rc = slot_ctx(ctx_, s.slot == 0, &sl.ctx);
   if (rc) return rc;
   const uint64_t bytes = WalkBlock(nullptr, s.B, s.k).bytes;
-  rc = sl.buf.reserve(sl.ctx, bytes, true);
+  // a radius search's radii ride behind the result block and the sizes of its balls come back in the status words
+  const uint64_t r_bytes = s.radius ? (uint64_t)s.B * 4 : 0;
+  rc = sl.buf.reserve(sl.ctx, bytes + r_bytes, true);
   if (rc) return rc;
   const WalkBlock d(sl.buf.dev, s.B, s.k);
   fvdb_ctx* on = s.slot == 0 ? nullptr : sl.ctx;
   fvdb_mask* mask = s.view ? s.view->mask.get() : nullptr;
-  if (s.kind == Search::kExact)
+  const float* r_dev = (const float*)((char*)sl.buf.dev + bytes);
+  if (s.radius && (rc = fvdb_dev_upload(sl.ctx, (char*)sl.buf.dev + bytes, s.radius, (size_t)r_bytes))) return rc;
+  if (s.kind == Search::kExact && s.radius)
+    rc = s.count_only ? fvdb_graph_count_within_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, r_dev, d.status)
+                      : fvdb_graph_search_flat_radius_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, r_dev, s.k, d.nodes, d.dist,
+                                                               d.counts, d.status);
+  else if (s.kind == Search::kExact)
     rc = (s.wide ? fvdb_graph_search_flat_wide_dev_slot : fvdb_graph_search_flat_dev_slot)(graph_, on, s.slot, mask, s.q_dev, s.B, s.k,
                                                                                           d.nodes, d.dist, d.counts);
   else if (!s.view)
@@ -560,6 +569,8 @@ int HNSWIndex::finish(Search& s) {
   int rc = fvdb_ctx_synchronize(sl.ctx);
   if (rc) return rc;
   const WalkBlock h(sl.buf.host, B, k);
+  if (s.totals) std::memcpy(s.totals, h.status, (size_t)B * 4);
+  if (s.count_only) return FVDB_OK;
   std::memcpy(s.dist, h.dist, (size_t)B * k * 4);
   std::memcpy(counts, h.counts, (size_t)B * 4);
   std::vector<uint32_t> failed;
@@ -884,6 +895,41 @@ int HNSWIndex::search_exact_wide_allowed(const float* q, uint32_t B, uint32_t di
                                          uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
   Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
   s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed, s.wide = true;
+  return run(s);
+}
+
+// ---- radius search: the wide request with a radius per query ----
+int HNSWIndex::search_radius_dev(const float* q_dev, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results,
+                                 const AllowView* view, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals, uint32_t slot) {
+  if (int rc = check_radius(radius, B)) return rc;
+  Search s{Search::kExact, q_dev, true, B, dim, max_results, 0, ids, dist, counts};
+  s.view = view, s.slot = slot, s.owns_slot = true, s.wide = true, s.radius = radius, s.totals = totals;
+  return run(s);
+}
+
+int HNSWIndex::search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, uint64_t* ids,
+                             float* dist, uint32_t* counts, uint32_t* totals) {
+  if (int rc = check_radius(radius, B)) return rc;
+  Search s{Search::kExact, q, false, B, dim, max_results, 0, ids, dist, counts};
+  s.wide = true, s.radius = radius, s.totals = totals;
+  return run(s);
+}
+
+int HNSWIndex::search_radius_allowed(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results,
+                                     const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts,
+                                     uint32_t* totals) {
+  if (int rc = check_radius(radius, B)) return rc;
+  Search s{Search::kExact, q, false, B, dim, max_results, 0, ids, dist, counts};
+  s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed, s.wide = true, s.radius = radius, s.totals = totals;
+  return run(s);
+}
+
+int HNSWIndex::count_within(const float* q, uint32_t B, uint32_t dim, const float* radius, const uint64_t* allowed, uint64_t n_allowed,
+                            uint32_t* totals) {
+  if (int rc = check_radius(radius, B)) return rc;
+  Search s{Search::kExact, q, false, B, dim, 1, 0, nullptr, nullptr, nullptr};
+  s.by_list = allowed != nullptr, s.allowed = allowed, s.n_allowed = n_allowed;
+  s.wide = true, s.radius = radius, s.totals = totals, s.count_only = true;
   return run(s);
 }
 

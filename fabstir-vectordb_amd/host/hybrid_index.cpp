@@ -976,6 +976,49 @@ int HybridIndex::exact_impl(const float* q, uint32_t B, uint32_t dim, const Hybr
   return exact_locked(q, B, dim, cfg, ids, dist, counts, wide);
 }
 
+// ---- radius search: two radius parts, the usual merge, the sum of the two totals ----
+int HybridIndex::search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, const HybridSearchConfig& cfg, double now,
+                               const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts,
+                               uint32_t* totals) {
+  if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // a rank holds only the lists it owns
+  const uint32_t k = (uint32_t)cfg.k;
+  if (cfg.k == 0 || cfg.k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  if (int rc = check_radius(radius, B)) return rc;
+  fill_empty(ids, dist, counts, B, k);
+  std::fill(totals, totals + B, 0u);
+  if (!initialized_ || B == 0) return FVDB_OK;
+  if (int rc = migrate_if_due(now, false)) return rc;
+  std::shared_lock<std::shared_mutex> r(rw_);
+  if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;
+  std::vector<uint64_t> rid, hid;
+  std::vector<float> rd, hd;
+  std::vector<uint32_t> rc_(B, 0), hc(B, 0), rt(B, 0), ht(B, 0);
+  const bool have_r = cfg.search_recent, have_h = cfg.search_historical && ivf_trained_;
+  if (have_r) {
+    rid.resize((size_t)B * k);
+    rd.resize((size_t)B * k);
+    HNSWIndex::ViewRef view;
+    int rc;
+    if (allowed && (rc = recent_->allowed_view(allowed, n_allowed, &view))) return rc;
+    Lease lease(this, Lease::kAnyFree, Lease::kTake);
+    Slot& sl = *lease.sl;
+    if ((rc = stage_finite(sl, q, B, dim))) return rc;
+    if ((rc = recent_->search_radius_dev((const float*)sl.d_q.dev, B, dim, radius, k, allowed ? view.get() : nullptr, rid.data(),
+                                         rd.data(), rc_.data(), rt.data(), lease.index())))
+      return rc;
+  }
+  if (have_h) {
+    hid.resize((size_t)B * k);
+    hd.resize((size_t)B * k);
+    if (int rc = historical_->search_radius(q, B, dim, radius, k, (uint32_t)std::min<uint64_t>(cfg.ivf_n_probe, 0xFFFFFFFFu), allowed,
+                                            n_allowed, hid.data(), hd.data(), hc.data(), ht.data()))
+      return rc;
+  }
+  merge_parts(B, k, k, k, have_r, rid.data(), rd.data(), rc_.data(), have_h, hid.data(), hd.data(), hc.data(), ids, dist, counts);
+  for (uint32_t b = 0; b < B; ++b) totals[b] = rt[b] + ht[b];
+  return FVDB_OK;
+}
+
 int HybridIndex::evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
                                          SearchQuality* out) {
   return quality_impl(q, B, dim, cfg, now, out, false);

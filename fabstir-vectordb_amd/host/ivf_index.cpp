@@ -569,6 +569,42 @@ int IVFIndex::search_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t 
   return FVDB_OK;
 }
 
+// ---- radius search ----
+int IVFIndex::search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, uint32_t n_probe,
+                            const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts,
+                            uint32_t* totals) {
+  if (!trained_) return FVDB_E_NOT_TRAINED;
+  if (dim != dim_) return FVDB_E_DIM;
+  if (!allowed) return fvdb_ivf_search_radius(dev_, q, B, radius, max_results, n_probe, ids, dist, counts, totals);
+  // under an allow-set: search_allowed's refusals, staging block and turn-taking
+  if (B == 0) return FVDB_OK;
+  const uint32_t k = max_results;
+  if (k == 0 || k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  for (uint64_t i = 0; i < (uint64_t)B * dim; ++i)
+    if (!(q[i] - q[i] == 0.0f)) return FVDB_E_NONFINITE;
+  int rc = check_radius(radius, B);
+  if (rc) return rc;
+  MaskRef mask;
+  if ((rc = allowed_mask(allowed, n_allowed, &mask))) return rc;
+  std::lock_guard<std::mutex> lk(allowed_mu_);
+  const uint64_t need = (uint64_t)B * k, bytes = need * 12 + (uint64_t)B * 8, q_bytes = (uint64_t)B * dim * 4;
+  if ((rc = allowed_q_.reserve(ctx_, q_bytes + (uint64_t)B * 4, false)) || (rc = allowed_out_.reserve(ctx_, bytes, true))) return rc;
+  char* dq = (char*)allowed_q_.dev;
+  if ((rc = fvdb_dev_upload(ctx_, dq, q, (size_t)q_bytes)) || (rc = fvdb_dev_upload(ctx_, dq + q_bytes, radius, (size_t)B * 4))) return rc;
+  char* d = (char*)allowed_out_.dev;
+  rc = fvdb_ivf_search_radius_dev_slot(dev_, nullptr, 0, mask.get(), (const float*)dq, B, (const float*)(dq + q_bytes), k, n_probe,
+                                       (uint64_t*)d, (float*)(d + need * 8), (uint32_t*)(d + need * 12), (uint32_t*)(d + need * 12) + B);
+  if (rc) return rc;
+  if ((rc = fvdb_dev_download_async(ctx_, allowed_out_.host, allowed_out_.dev, (size_t)bytes)) || (rc = fvdb_ctx_synchronize(ctx_)))
+    return rc;
+  const char* h = (const char*)allowed_out_.host;
+  std::memcpy(ids, h, need * 8);
+  std::memcpy(dist, h + need * 8, need * 4);
+  std::memcpy(counts, h + need * 12, (size_t)B * 4);
+  std::memcpy(totals, h + need * 12 + (size_t)B * 4, (size_t)B * 4);
+  return FVDB_OK;
+}
+
 // ---- one allow-set per query ----
 int IVFIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe, const AllowGroups& groups,
                                     uint64_t* ids, float* dist, uint32_t* counts) {

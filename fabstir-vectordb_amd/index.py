@@ -170,6 +170,12 @@ HOST_SIGNATURES = {
     "fvh_hnsw_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
     "fvh_hybrid_search_exact_wide": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
+    # radius search
+    "fvh_hnsw_search_radius": (i32, [vp, f32p, u32, u32, f32p, u32, u64p, f32p, u32p, u32p]),
+    "fvh_hnsw_search_radius_allowed": (i32, [vp, f32p, u32, u32, f32p, u32, u64p, u64, u64p, f32p, u32p, u32p]),
+    "fvh_hnsw_count_within": (i32, [vp, f32p, u32, u32, f32p, u64p, u64, u32p]),
+    "fvh_ivf_search_radius": (i32, [vp, f32p, u32, u32, f32p, u32, u32, u64p, u64, u64p, f32p, u32p, u32p]),
+    "fvh_hybrid_search_radius": (i32, [vp, f32p, u32, u32, f32p, u64, u64, i32, i32, u64p, u64, dbl, u64p, f32p, u32p, u32p]),
     # search quality over a grid of ef and n_probe from one exact search
     "fvh_hnsw_quality_by_ef": (i32, [vp, f32p, u32, u32, u32, u32p, u32, f32p, f32p, f32p, u64p]),
     "fvh_hybrid_quality_grid": (i32, [vp, f32p, u32, u32, u64, i32, i32, u64, u64, u32p, u32, u32p, u32, dbl, f32p, f32p, f32p,
@@ -250,6 +256,24 @@ def _allowed_ids(allowed):
     return a.reshape(-1) if a.size else np.zeros(1, np.uint64)[:0]
 
 
+def _allowed_args(allowed):
+    """(pointer, count, array) of an optional allow-set: a null pointer for None ("no filter")."""
+    if allowed is None:
+        return None, 0, None
+    a = _allowed_ids(allowed)
+    return _ptr(a, u64p), a.size, a
+
+
+def _radii(radius, B):
+    """The radii of a radius search as f32[B]: one value for every query, or one per query."""
+    r = np.asarray(radius, np.float32).reshape(-1)
+    if r.size == 1:
+        r = np.full(B, r[0], np.float32)
+    if r.size != B:
+        raise InvalidConfig(f"radius has {r.size} entries for {B} queries")
+    return np.ascontiguousarray(r) if B else np.zeros(1, np.float32)[:0]
+
+
 def _allow_groups(allow_sets, group_of_query, B):
     """The ctypes arguments of a grouped search: the allow-sets laid end to end with their offsets, a flag per set (0 where
     the entry is None: "no filter") and the group of each query.  The arrays are returned too: the caller keeps them
@@ -300,6 +324,17 @@ class _Base:
         self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], k, *mid, _ptr(ids, u64p), _ptr(ds, f32p), _ptr(cnt, u32p)))
         return SearchResults(ids, ds, cnt)
 
+    def _search_radius(self, fn, q, radius, max_results, *mid):
+        """The radius searches: (SearchResults of [B][max_results], totals uint32[B])."""
+        q = _rows(q)
+        B, m = q.shape[0], int(max_results)
+        r = _radii(radius, B)
+        ids = np.empty((B, max(m, 1)), np.uint64)
+        ds = np.empty((B, max(m, 1)), np.float32)
+        cnt, totals = np.zeros(B, np.uint32), np.zeros(B, np.uint32)
+        self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], _ptr(r, f32p), m, *mid, _ptr(ids, u64p), _ptr(ds, f32p),
+                       _ptr(cnt, u32p), _ptr(totals, u32p)))
+        return SearchResults(ids, ds, cnt), totals
 
     def _quality(self, fn, queries, *args):
         """evaluate_search_quality of the graph and hybrid classes: SearchQuality as a dict, as IVFIndex returns it."""
@@ -564,6 +599,16 @@ class IVFIndex(_Base):
         args, keep = _allow_groups(allow_sets, group_of_query, q.shape[0])
         return self._search(self.lib.fvh_ivf_search_allowed_groups, q, k, self.n_probe if n_probe is None else n_probe, *args)
 
+    def search_radius(self, queries, radius, max_results=4096, n_probe=None, allowed=None):
+        """Every live row of the n_probe probed lists within `radius` of its query (a scalar or one value per query; f32,
+        >= 0, inf allowed; the boundary is inclusive, on the f32 distance search() reports): (results, totals).
+        results[b] is what search(k=max_results) returns on the wide route, cut at the radius; totals[b] (uint32) is the
+        exact size of the ball over the probed lists, never capped.  max_results in 1..4096.  allowed: as in
+        search_allowed — rows outside it are in neither."""
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_radius(self.lib.fvh_ivf_search_radius, queries, radius, max_results,
+                                   self.n_probe if n_probe is None else n_probe, ap, an)
+
     def mask_builds(self):
         return int(self.lib.fvh_ivf_mask_builds(self.h))
 
@@ -706,6 +751,26 @@ class HNSWIndex(_Base):
         """search_exact_wide() among the nodes whose id is in `allowed` (the cached mask of search_allowed)."""
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hnsw_search_exact_wide_allowed, queries, k, _ptr(a, u64p), a.size)
+
+    def search_radius(self, queries, radius, max_results=4096, allowed=None):
+        """Every live node within `radius` of its query (a scalar or one value per query; f32, >= 0, inf allowed; the
+        boundary is inclusive, on the f32 distance search_exact_wide() reports): (results, totals).  results[b] is
+        search_exact_wide(k=max_results) cut at the radius; totals[b] (uint32) is the exact size of the ball, never
+        capped.  max_results in 1..4096.  allowed: as in search_exact_wide_allowed — nodes outside it are in neither."""
+        if allowed is None:
+            return self._search_radius(self.lib.fvh_hnsw_search_radius, queries, radius, max_results)
+        a = _allowed_ids(allowed)
+        return self._search_radius(self.lib.fvh_hnsw_search_radius_allowed, queries, radius, max_results, _ptr(a, u64p), a.size)
+
+    def count_within(self, queries, radius, allowed=None):
+        """search_radius()'s totals alone (uint32[B]), by a scan that keeps no distances and selects nothing."""
+        q = _rows(queries)
+        r = _radii(radius, q.shape[0])
+        ap, an, keep = _allowed_args(allowed)
+        totals = np.zeros(q.shape[0], np.uint32)
+        self._check(self.lib.fvh_hnsw_count_within(self.h, _ptr(q, f32p), q.shape[0], q.shape[1], _ptr(r, f32p), ap, an,
+                                                   _ptr(totals, u32p)))
+        return totals
 
     def evaluate_search_quality_wide(self, queries, k, ef):
         """evaluate_search_quality() with k in 1..4096: search(k, ef), which returns at most ef rows, against
@@ -1163,6 +1228,20 @@ class HybridIndex(_Base):
         self._refuse_when_sharded("search_exact_wide")
         return self._search(self.lib.fvh_hybrid_search_exact_wide, queries, k, int(search_recent), int(search_historical),
                             float(now))
+
+    def search_radius(self, queries, radius, max_results=4096, now=0.0, ivf_n_probe=10, search_recent=True, search_historical=True,
+                      allowed=None):
+        """Every resident row within `radius` of its query (a scalar or one value per query; f32, >= 0, inf allowed; the
+        boundary is inclusive): (results, totals).  The recent part is the graph's exact radius scan (a walk bounded by ef
+        cannot enumerate a ball), the historical part the ball of the ivf_n_probe probed lists (every list at
+        ivf_n_probe = n_clusters); each is capped at max_results (1..4096) and the two are merged as search() merges.
+        totals[b] (uint32) = recent total + historical total, exact and never capped; like the merge it does not
+        de-duplicate, so a migrated row that still sits in the graph counts twice.  One auto-migration step, the read
+        lock.  allowed: as in search_allowed.  Refused (Unsupported) on a sharded index."""
+        self._refuse_when_sharded("search_radius")
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_radius(self.lib.fvh_hybrid_search_radius, queries, radius, max_results, int(ivf_n_probe),
+                                   int(search_recent), int(search_historical), ap, an, float(now))
 
     def evaluate_search_quality_wide(self, queries, k, now=0.0, hnsw_ef=50, ivf_n_probe=10):
         """evaluate_search_quality() with k in 1..4096: search() against search_exact_wide() under one hold of the lock."""

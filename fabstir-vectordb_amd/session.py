@@ -129,6 +129,36 @@ class SessionError(Exception):
     pass
 
 
+def _score_f32(d):
+    """The session's score of a distance, in f32: 1 / (1 + d) (session.rs:291)."""
+    return np.float32(1.0) / (np.float32(1.0) + np.float32(d))
+
+
+def radius_of_threshold(threshold):
+    """The radius that stands for a score threshold: the largest f32 d >= 0 whose score
+    f32(1) / (f32(1) + d) is >= threshold, so that "distance bits <= bits(d)" IS the session's predicate and the device's
+    total is exact for it.  f32 add and divide are monotone, so the score never rises with d and a bisection over the
+    bit patterns of the non-negative f32 values (0 .. +inf, monotone as integers) finds d.  threshold <= 0: +inf (every
+    score is >= 0).  threshold > 1: None — no distance qualifies, d = 0 scores exactly 1.  The threshold is compared as
+    search() compares it, as an f32.  NaN: SessionError."""
+    t = np.float32(threshold)
+    if np.isnan(t):
+        raise SessionError("Invalid threshold: NaN")
+    if t <= np.float32(0.0):
+        return np.float32(np.inf)
+    if t > np.float32(1.0):
+        return None
+    at = lambda bits: np.array(bits, np.uint32).view(np.float32)[()]  # noqa: E731
+    lo, hi = 0, 0x7F800000  # score(lo) = 1 >= t; score(+inf) = 0 < t
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        if _score_f32(at(mid)) >= t:
+            lo = mid
+        else:
+            hi = mid
+    return at(lo)
+
+
 class VectorDbSession:
     """bindings/node/src/session.rs VectorDBSession — search()/addVectors()/deleteVector() on the GPU index."""
 
@@ -245,6 +275,54 @@ class VectorDbSession:
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
         return self._results_of(res[0], threshold, bool(options.get("includeVectors", False)))  # session.rs:229-231
+
+    # -- search_within: every row whose score clears a threshold (no counterpart in the reference) -------------------
+    def search_within(self, query_vector, threshold, options=None):
+        """Every resident row whose score 1/(1+distance) is >= threshold, where search(k, {"threshold": t}) returns at most
+        k of them and cannot say how many there are: HybridIndex.search_radius at radius_of_threshold(threshold), at
+        search()'s settings (n_probe 10; the recent part exact).  Returns {"results": the entries search() builds, nearest
+        first, at most options["maxResults"] (default 4096, 1..4096) of them; "total": how many rows clear the threshold,
+        never capped; "truncated": total > len(results)}.  options: "maxResults", "includeVectors", and "filter" with
+        "filterMode" "pushdown" (the default here) or "resident" — the matching ids go down as an allow-set as in
+        search(), and rows outside it are in neither the results nor the total.  "oversample" keeps what is left of 3 k
+        candidates: it has no meaning where nothing is asked for by count, and is refused."""
+        if self.destroyed:
+            raise SessionError("Session already destroyed")
+        options = options or {}
+        q = js_array_to_vec_f32(query_vector)
+        if self.vector_dimension is not None and q.size != self.vector_dimension:
+            raise SessionError(
+                f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+        radius = radius_of_threshold(threshold)
+        max_results = int(options.get("maxResults", 4096))
+        allowed = None
+        if options.get("filter") is not None:
+            mode = options.get("filterMode", "pushdown")
+            if mode not in ("pushdown", "resident"):
+                raise SessionError(f'Invalid filterMode for search_within: {mode!r} (expected "pushdown" or "resident"; '
+                                   '"oversample" applies to a search by count)')
+            try:
+                flt = MetadataFilter.from_json(options["filter"])
+            except FilterError as e:
+                raise SessionError(f"Invalid filter: {e}") from e
+            if mode == "resident":
+                allowed = self._resident_allowed(flt)
+            else:
+                allowed = np.fromiter((rid for rid, name in self._rows.items()
+                                       if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+        elif options.get("filterMode") == "oversample":
+            raise SessionError('Invalid filterMode for search_within: "oversample" applies to a search by count')
+        if radius is None:  # threshold > 1: no score reaches it
+            return {"results": [], "total": 0, "truncated": False}
+        try:
+            res, totals = self.index.search_radius(q.reshape(1, -1), radius, max_results, now=self.now, allowed=allowed)
+        except Exception as e:
+            raise SessionError(f"Search failed: {e}") from e
+        results = self._results_of(res[0], np.float32(threshold), bool(options.get("includeVectors", False)))
+        total = int(totals[0])
+        return {"results": results, "total": total, "truncated": total > len(results)}
+
+    searchWithin = search_within
 
     # -- "resident" filters: metadata columns in HBM (metadata_columns.py) -------------------------------------------
     def _resident_allowed(self, flt):

@@ -783,6 +783,36 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
 int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
                                          uint32_t B, uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev,
                                          uint32_t* out_counts_dev);
+/* ---- radius search -----------------------------------------------
+ * "Everything within r" where every search above answers "the k nearest".  For query b with radius r = radius[b]
+ * (f32, r >= 0, +inf allowed) the BALL is the set of candidate rows — the rows the corresponding k-search would score,
+ * under the same mask — whose distance word satisfies bits(dist) <= bits(r): inclusive, on the reference's own f32
+ * distance.  out_totals[b] = the size of the ball, exact and never capped.  The results are its first
+ * min(total, max_results) rows by the wide selection's key (distance bits << 32 | scan position): what the wide search
+ * at k = max_results returns, cut at the radius.  Outputs are [B][max_results] with the usual tails, out_counts[b] =
+ * min(total, max_results).  1 <= max_results <= FVDB_MAX_K_WIDE, else FVDB_E_UNSUPPORTED.  The _dev forms do not
+ * inspect device input: there a negative or NaN radius has an empty ball (-0.0 is 0.0).
+ *
+ * Over a graph's live nodes: fvdb_graph_search_flat_wide_dev_slot's scan, arguments, sub-batches, mask, slot, stream and
+ * staleness rules and its refusals in its order; the selection counts the ball in one pass over the arena and, when it
+ * fits max_results, gathers and sorts it with no radix pass. */
+int fvdb_graph_search_flat_radius_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                           uint32_t B, const float* radius_dev, uint32_t max_results, uint32_t* out_nodes_dev,
+                                           float* out_dist_dev, uint32_t* out_counts_dev, uint32_t* out_totals_dev);
+/* out_totals_dev[b] alone: the same scan with no arena and no selection, each wave counting the rows of its slice within
+ * each radius (integer adds: the result does not depend on their order).  out_totals_dev is zeroed on the stream first. */
+int fvdb_graph_count_within_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                     const float* radius_dev, uint32_t* out_totals_dev);
+/* Over the live rows of the nprobe probed lists in probe order: fvdb_ivf_search_wide_dev_slot's lists, score stage,
+ * mask, any-nprobe, slot, stream and staleness rules; an index holding a shard of a larger one is FVDB_E_UNSUPPORTED.
+ * Totals count the probed lists only. */
+int fvdb_ivf_search_radius_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev, uint32_t B,
+                                    const float* radius_dev, uint32_t max_results, uint32_t nprobe, uint64_t* out_ids_dev,
+                                    float* out_dist_dev, uint32_t* out_counts_dev, uint32_t* out_totals_dev);
+/* The same, blocking, with host pointers and leased scratch like fvdb_ivf_search_wide.  Non-finite queries are
+ * FVDB_E_NONFINITE as there; a negative or NaN radius is FVDB_E_INVALID. */
+int fvdb_ivf_search_radius(fvdb_ivf* ivf, const float* q, uint32_t B, const float* radius, uint32_t max_results, uint32_t nprobe,
+                           uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint32_t* out_totals);
 /* The comparison of fvdb_ivf_search_quality_dev on two id blocks the caller holds in HBM (B x k ids with their hit
  * counts; entries at or beyond a count are not read): per query matches, recall and precision by the formulas stated
  * there — an id the result holds twice counts twice — to out_recall_dev[B] / out_precision_dev[B], enqueued on ctx's
