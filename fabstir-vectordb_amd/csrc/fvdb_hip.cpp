@@ -33,6 +33,7 @@
 #include "kernels_util.h"
 #include "kernels_maint.h"
 #include "kernels_rows.h"
+#include "kernels_mmr.h"
 
 using namespace fvdb;
 
@@ -2740,6 +2741,27 @@ int fvdb_merge_keys_wide_dev(fvdb_ctx* ctx, const uint64_t* keys, const uint64_t
   if ((uint64_t)G * k >= (1ull << 31)) FAIL(ctx, FVDB_E_UNSUPPORTED, "too many partial lists for one merge");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(merge_keys_wide_kernel, dim3(B), dim3(256), 0, ctx->stream, keys, ids, G, B, k, out_ids, out_dist, out_counts);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// Diverse selection (kernels_mmr.h): one workgroup per query, everything in device memory
+int fvdb_mmr_select_dev(fvdb_ctx* ctx, const float* rows_dev, uint32_t row_stride, const uint64_t* ids_dev, const float* dist_dev,
+                        const uint32_t* counts_dev, uint32_t B, uint32_t fetch_k, uint32_t k, float lam, int distinct,
+                        uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_rank_dev, uint32_t* out_counts_dev) {
+  if (!ctx) return FVDB_E_INVALID;
+  if (fetch_k == 0 || fetch_k > FVDB_MAX_K) FAIL(ctx, FVDB_E_UNSUPPORTED, "fetch_k must be in 1..FVDB_MAX_K");
+  if (k == 0 || k > fetch_k) FAIL(ctx, FVDB_E_INVALID, "k must be in 1..fetch_k");
+  if (!(lam >= 0.0f && lam <= 1.0f)) FAIL(ctx, FVDB_E_INVALID, "lam must be in [0, 1]");
+  if (row_stride == 0 || row_stride % 4 != 0) FAIL(ctx, FVDB_E_INVALID, "row_stride must be a positive multiple of 4");
+  if (B == 0) return FVDB_OK;
+  if (!rows_dev || !ids_dev || !dist_dev || !counts_dev || !out_ids_dev || !out_dist_dev || !out_rank_dev || !out_counts_dev)
+    FAIL(ctx, FVDB_E_INVALID, "null buffer");
+  if ((uintptr_t)rows_dev % 16 != 0) FAIL(ctx, FVDB_E_INVALID, "rows_dev must be 16-byte aligned");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const float a = lam, b = 1.0f - a;
+  hipLaunchKernelGGL(mmr_select_kernel, dim3(B), dim3(256), 0, ctx->stream, rows_dev, row_stride, ids_dev, dist_dev, counts_dev,
+                     fetch_k, k, a, b, distinct ? 1u : 0u, out_ids_dev, out_dist_dev, out_rank_dev, out_counts_dev);
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }

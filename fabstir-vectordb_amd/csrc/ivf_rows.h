@@ -13,28 +13,34 @@ namespace {
 
 constexpr uint64_t kGatherStep = 1u << 20;  // rows per launch: the grid stays far below its limit
 
-void launch_pool_gather(const fvdb_ivf* ivf, hipStream_t st, const uint32_t* slots_dev, uint64_t n, float* out) {
+void launch_pool_gather(const fvdb_ivf* ivf, hipStream_t st, const uint32_t* slots_dev, uint64_t n, float* out, uint32_t ostride) {
   const Pool& P = ivf->pool;
   const uint32_t nch = (uint32_t)(P.block_bytes() / 1024);  // 16-byte chunks per row: d4 (f32), d8 (fp16)
   for (uint64_t o = 0; o < n; o += kGatherStep) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
     if (P.esize == 4)
       hipLaunchKernelGGL(pool_gather_rows_kernel<0>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data(), P.rm(),
-                         slots_dev + o, B, ivf->d, nch, out + o * ivf->d);
+                         slots_dev + o, B, ivf->d, nch, out + o * ostride, ostride);
     else
       hipLaunchKernelGGL(pool_gather_rows_kernel<1>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, st, P.data(),
-                         (const float*)nullptr, slots_dev + o, B, ivf->d, nch, out + o * ivf->d);
+                         (const float*)nullptr, slots_dev + o, B, ivf->d, nch, out + o * ostride, ostride);
   }
 }
 
+// ostride: floats between output rows (d: tightly packed).  skips: a cluster of FVDB_NO_ROW leaves its output row alone.
 int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const uint32_t* pos, uint64_t n, float* out,
-                    bool to_host) {
+                    bool to_host, uint32_t ostride, bool skips) {
   if (!ivf) return FVDB_E_INVALID;
+  if (ostride < ivf->d) FAIL(ivf->ctx, FVDB_E_INVALID, "output stride below the dimension");
   if (n == 0) return FVDB_OK;
   if (!cluster || !pos || !out) FAIL(ivf->ctx, FVDB_E_INVALID, "null argument");
   if (on && on->device != ivf->ctx->device) FAIL(ivf->ctx, FVDB_E_INVALID, "context of another device");
   std::vector<uint32_t> slots(n);
   for (uint64_t i = 0; i < n; ++i) {  // every location is checked before anything is enqueued
+    if (skips && cluster[i] == FVDB_NO_ROW) {
+      slots[i] = FVDB_NO_ROW;
+      continue;
+    }
     if (cluster[i] >= ivf->nlist || pos[i] >= ivf->list_len[cluster[i]]) FAIL(ivf->ctx, FVDB_E_NOT_FOUND, "no such row");
     slots[i] = ivf->list_blocks[cluster[i]][pos[i] >> 6] * 64 + (pos[i] & 63);
   }
@@ -46,7 +52,7 @@ int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const 
     if (to_host) HIPCHK(ctx, S.s_frows.ensure(n * ivf->d * 4));
     HIPCHK(ctx, hipMemcpyAsync(S.s_fslots.p, slots.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (to_host) {
-      launch_pool_gather(ivf, ctx->stream, S.s_fslots.as<uint32_t>(), n, S.s_frows.as<float>());
+      launch_pool_gather(ivf, ctx->stream, S.s_fslots.as<uint32_t>(), n, S.s_frows.as<float>(), ostride);
       HIPCHK(ctx, hipGetLastError());
       HIPCHK(ctx, hipMemcpyAsync(out, S.s_frows.p, n * ivf->d * 4, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -57,7 +63,7 @@ int get_rows_common(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const 
     // waits for it, so that the next holder of this set cannot overwrite s_fslots under the kernel.
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     hipStream_t st = on ? on->stream : ivf->ctx->stream;
-    launch_pool_gather(ivf, st, S.s_fslots.as<uint32_t>(), n, out);
+    launch_pool_gather(ivf, st, S.s_fslots.as<uint32_t>(), n, out, ostride);
     HIPCHK(ctx, hipGetLastError());
     if (st != ctx->stream) {
       HIPCHK(ctx, S.fetch_done.create(hipEventDisableTiming));
@@ -92,10 +98,10 @@ int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_
     const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
     if (s->f16())  // widened into the f32 staging: the lists round again, to the same values, if they are fp16 too
       hipLaunchKernelGGL(store_gather_rows_kernel<half_t>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const half_t*)s->data, s->dpad,
-                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
+                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d, ivf->d, (uint32_t)s->rows);
     else
       hipLaunchKernelGGL(store_gather_rows_kernel<float>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const float*)s->data, s->dpad,
-                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d);
+                         ivf->s_slots.as<uint32_t>() + o, B, ivf->d, ivf->s_in.as<float>() + o * ivf->d, ivf->d, (uint32_t)s->rows);
   }
   HIPCHK(ctx, hipGetLastError());
   ivf->m_info.ms_gather += clock.end(ctx->stream);  // waits: `rows` is the caller's, and s_slots is written again by the append
@@ -108,12 +114,38 @@ int stage_from_store(fvdb_ivf* ivf, fvdb_store* s, const uint32_t* rows, uint64_
 extern "C" {
 
 int fvdb_ivf_get_rows(fvdb_ivf* ivf, const uint32_t* cluster, const uint32_t* pos, uint64_t n, float* out_rows) {
-  return get_rows_common(ivf, nullptr, cluster, pos, n, out_rows, true);
+  return get_rows_common(ivf, nullptr, cluster, pos, n, out_rows, true, ivf ? ivf->d : 0, false);
 }
 
 int fvdb_ivf_get_rows_dev(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const uint32_t* pos, uint64_t n,
                           float* out_rows_dev) {
-  return get_rows_common(ivf, on, cluster, pos, n, out_rows_dev, false);
+  return get_rows_common(ivf, on, cluster, pos, n, out_rows_dev, false, ivf ? ivf->d : 0, false);
+}
+
+int fvdb_ivf_get_rows_dev_strided(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const uint32_t* pos, uint64_t n,
+                                  float* out_rows_dev, uint32_t out_stride) {
+  return get_rows_common(ivf, on, cluster, pos, n, out_rows_dev, false, out_stride, true);
+}
+
+int fvdb_store_get_rows_dev(fvdb_store* s, fvdb_ctx* on, const uint32_t* rows_dev, uint64_t n, float* out_rows_dev, uint32_t out_stride) {
+  if (!s) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = on ? on : s->ctx;
+  if (ctx->device != s->ctx->device) FAIL(s->ctx, FVDB_E_INVALID, "context of another device");
+  if (out_stride < s->d) FAIL(s->ctx, FVDB_E_INVALID, "output stride below the dimension");
+  if (n == 0) return FVDB_OK;
+  if (!rows_dev || !out_rows_dev) FAIL(s->ctx, FVDB_E_INVALID, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  for (uint64_t o = 0; o < n; o += kGatherStep) {
+    const uint32_t B = (uint32_t)std::min<uint64_t>(kGatherStep, n - o);
+    if (s->f16())
+      hipLaunchKernelGGL(store_gather_rows_kernel<half_t>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const half_t*)s->data, s->dpad,
+                         rows_dev + o, B, s->d, out_rows_dev + o * out_stride, out_stride, (uint32_t)s->rows);
+    else
+      hipLaunchKernelGGL(store_gather_rows_kernel<float>, dim3(cdiv(B, kRowsPerGroup)), dim3(256), 0, ctx->stream, (const float*)s->data, s->dpad,
+                         rows_dev + o, B, s->d, out_rows_dev + o * out_stride, out_stride, (uint32_t)s->rows);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
 }
 
 int fvdb_ivf_assign_from_store(fvdb_ivf* ivf, fvdb_store* store, const uint32_t* rows, uint64_t n, uint32_t* out_cluster) {

@@ -255,6 +255,44 @@ int fvh_hybrid_search_radius(void* p, const float* q, uint32_t B, uint32_t d, co
   c.search_historical = search_historical != 0;
   return ((HybridIndex*)p)->search_radius(q, B, d, radius, c, now, allowed, n_allowed, ids, dist, counts, totals);
 }
+// diverse search: ids / dist / ranks [B][k] in pick order, counts[B].  allowed == NULL: no filter
+void fvh_set_diverse_stage_bytes(uint64_t bytes) { set_diverse_stage_budget(bytes); }  // 0: the default again
+uint64_t fvh_diverse_stage_bytes() { return diverse_stage_budget(); }
+int fvh_ivf_search_diverse(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t fetch_k, float lam, int distinct,
+                           uint32_t n_probe, const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks,
+                           uint32_t* counts) {
+  return ((IVFIndex*)p)->search_diverse(q, B, d, k, fetch_k, lam, distinct != 0, n_probe, allowed, n_allowed, ids, dist, ranks, counts);
+}
+int fvh_hnsw_search_diverse(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t fetch_k, float lam, int distinct,
+                            uint32_t ef, const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks,
+                            uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_diverse(q, B, d, k, fetch_k, lam, distinct != 0, ef, allowed, n_allowed, ids, dist, ranks, counts);
+}
+int fvh_hybrid_search_diverse(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint32_t fetch_k, float lam, int distinct,
+                              uint64_t hnsw_ef, uint64_t ivf_n_probe, int search_recent, int search_historical, const uint64_t* allowed,
+                              uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = hnsw_ef;
+  c.ivf_n_probe = ivf_n_probe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_diverse(q, B, d, c, fetch_k, lam, distinct != 0, now, allowed, n_allowed, ids, dist, ranks, counts);
+}
+int fvh_hybrid_search_diverse_groups(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint32_t fetch_k, float lam,
+                                     int distinct, uint64_t hnsw_ef, uint64_t ivf_n_probe, int search_recent, int search_historical,
+                                     const uint64_t* allow_ids, const uint64_t* allow_off, const uint8_t* filtered, uint32_t G,
+                                     const uint32_t* group_of_query, double now, uint64_t* ids, float* dist, uint32_t* ranks,
+                                     uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = hnsw_ef;
+  c.ivf_n_probe = ivf_n_probe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  const AllowGroups groups{allow_ids, allow_off, filtered, G, group_of_query};
+  return ((HybridIndex*)p)->search_diverse_groups(q, B, d, c, fetch_k, lam, distinct != 0, groups, now, ids, dist, ranks, counts);
+}
 int fvh_hnsw_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, float* out3,
                                           uint64_t* queries_evaluated) {
   SearchQuality s{};

@@ -224,6 +224,47 @@ inline uint32_t quality_grid_step(uint64_t budget, const GridParts& p) {
 // as compare_id_blocks adds them: the totals do not depend on the budget.
 int quality_grid_totals(fvdb_ctx* ctx, DevBuf& stage, const GridParts& p, float* total_recall, float* total_precision);
 
+// Diverse search (fvdb_mmr_select_dev): the candidates of an ordinary search of fetch_k, their rows
+// gathered in HBM into a staging block, k of them selected per query by maximal marginal relevance.
+// check_diverse: the refusals every search_diverse makes first, in fvdb_mmr_select_dev's order.
+inline int check_diverse(uint32_t k, uint32_t fetch_k, float lam) {
+  if (fetch_k == 0 || fetch_k > FVDB_MAX_K) return FVDB_E_UNSUPPORTED;
+  if (k == 0 || k > fetch_k || !(lam >= 0.0f && lam <= 1.0f)) return FVDB_E_INVALID;
+  return FVDB_OK;
+}
+// "no result" rows of a diverse search: fill_empty and ranks of FVDB_NO_ROW
+inline void fill_empty_diverse(uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* counts, uint32_t B, uint32_t k) {
+  fill_empty(ids, dist, counts, B, k);
+  for (size_t i = 0; i < (size_t)B * k; ++i) ranks[i] = FVDB_NO_ROW;
+}
+// The staging block [queries][fetch_k][dim rounded up to 4] f32 is capped at kDiverseStageBytes (FVDB_DIVERSE_STAGE_BYTES,
+// read once, says otherwise): a batch is walked in sub-batches of as many queries as fit, at least one.
+// set_diverse_stage_budget(bytes) overrides both for the process (0: back to the environment's value or the default).
+constexpr uint64_t kDiverseStageBytes = 256ull << 20;
+uint64_t diverse_stage_budget();
+void set_diverse_stage_budget(uint64_t bytes);
+struct DiverseStage {
+  std::mutex mu;  // one block per index: selections take turns
+  DevBuf rows;    // the staging block
+  DevBuf io;      // per sub-batch: candidate ids, distances, counts and row locations in; picks out (pinned twin)
+  void release() {
+    rows.release();
+    io.release();
+  }
+};
+// Fills staging rows [0, n) of a sub-batch on ctx's stream: candidate i (ids[i], wanted where want[i] != 0) goes to
+// rows_dev + i * stride; `loc_dev` is room for n uint32_t in device memory, `want` is cleared where a row was found.
+struct RowSource {
+  virtual int gather(fvdb_ctx* ctx, const uint64_t* ids, uint8_t* want, uint64_t n, uint32_t* loc_dev, float* rows_dev,
+                     uint32_t stride) = 0;
+  virtual ~RowSource() {}
+};
+// cid / cd [B][fetch_k] and cc[B]: what the search of fetch_k returned (host memory).  Results [B][k] in pick order.
+// FVDB_E_NOT_FOUND when a candidate's row is in no source.
+int select_diverse(fvdb_ctx* ctx, DiverseStage& st, RowSource& src, uint32_t dim, uint32_t B, uint32_t fetch_k, uint32_t k,
+                   float lam, bool distinct, const uint64_t* cid, const float* cd, const uint32_t* cc, uint64_t* ids, float* dist,
+                   uint32_t* ranks, uint32_t* counts);
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
@@ -288,6 +329,14 @@ class IVFIndex {
   // neither results nor totals.
   int search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, uint32_t n_probe,
                     const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals);
+  // Diverse search: the candidates are exactly what search(fetch_k, n_probe) — search_allowed when
+  // allowed != nullptr — returns; k of them per query by fvdb_mmr_select_dev, in pick order, ranks[B][k] = each pick's
+  // position among the candidates.  1 <= k <= fetch_k <= FVDB_MAX_K, lam in [0, 1].
+  int search_diverse(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t fetch_k, float lam, bool distinct,
+                     uint32_t n_probe, const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks,
+                     uint32_t* counts);
+  // the rows of ids[n] (where want[i]) by the lowest location of each, gathered on ctx's stream (RowSource::gather)
+  int gather_rows_dev(fvdb_ctx* ctx, const uint64_t* ids, uint8_t* want, uint64_t n, float* rows_dev, uint32_t stride);
   // the device mask for that allow-set (cached); search_dev under it
   int allowed_mask(const uint64_t* allowed, uint64_t n_allowed, MaskRef* out);
   int search_dev_masked(const MaskRef& mask, const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, uint32_t n_probe,
@@ -366,6 +415,7 @@ class IVFIndex {
   // search_allowed: staged queries, result block and its pinned copy; evaluate_search_quality stages its queries and
   // its per-query figures in the same pair, under the same mutex
   DevBuf allowed_q_, allowed_out_;
+  DiverseStage diverse_;
   void drop_mask() {
     mask_.reset();
     mask_key_.clear();
@@ -520,6 +570,14 @@ class HNSWIndex {
                    uint32_t* totals);
   int search_radius_dev(const float* q_dev, uint32_t B, uint32_t dim, const float* radius, uint32_t max_results, const AllowView* view,
                         uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals, uint32_t slot);
+  // Diverse search: the candidates are exactly what search(fetch_k, ef) — search_allowed when
+  // allowed != nullptr — returns.  A graph walk returns at most ef rows, so fetch_k > ef just yields fewer candidates.
+  // k of them per query by fvdb_mmr_select_dev, in pick order; 1 <= k <= fetch_k <= FVDB_MAX_K, lam in [0, 1].
+  int search_diverse(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t fetch_k, float lam, bool distinct, uint32_t ef,
+                     const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* counts);
+  // the rows of ids[n] (where want[i]) from the row store, gathered on ctx's stream (RowSource::gather)
+  int gather_rows_dev(fvdb_ctx* ctx, const uint64_t* ids, uint8_t* want, uint64_t n, uint32_t* loc_dev, float* rows_dev,
+                      uint32_t stride);
   // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every listed ef from ONE exact search (DESIGN.md
   // section 9r): one search(k, efs[i]) each, one fvdb_quality_grid_dev call per sub-batch.  out: E x 1, entry i what
   // the single call returns at efs[i], bit for bit; duplicates and any order are fine.  Refused before any search
@@ -720,6 +778,7 @@ class HNSWIndex {
   DevSlot slots_[kSlots];
   DevBuf d_q_;  // stage(): host-resident query batches
   DevBuf qual_;  // evaluate_search_quality: the two id blocks and the per-query figures
+  DiverseStage diverse_;
   std::atomic<uint64_t> n_fallback_{0};
   // Searches may come from several host threads (HybridIndex leases a slot per call): the graph mirror is synced by
   // one of them, the rare host-walk fallback and the standalone search()/search_dev() entry points are serialised.
@@ -878,6 +937,21 @@ class HybridIndex {
   // within the radius counts twice.  allowed != nullptr: both parts under that allow-set (the cached view and mask).
   int search_radius(const float* q, uint32_t B, uint32_t dim, const float* radius, const HybridSearchConfig& cfg, double now,
                     const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts, uint32_t* totals);
+  // Diverse search: one auto-migration step; then, under ONE hold of the read lock, search(cfg with
+  // k = fetch_k) — search_allowed when allowed != nullptr — the id-to-location lookup (the recent part first, then the
+  // historical part, as get_vectors) and the gather.  cfg.k is k; recent_k / historical_k are not read (each part is asked
+  // for fetch_k).  With distinct a migrated row that still sits in the graph is returned once; lam = 1 and distinct is
+  // the de-duplicated search.  FVDB_E_UNSUPPORTED once the index is sharded.
+  int search_diverse(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint32_t fetch_k, float lam,
+                     bool distinct, double now, const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist,
+                     uint32_t* ranks, uint32_t* counts);
+  // the same with one allow-set per query: the candidates are what search_allowed_groups(cfg with k = fetch_k) returns
+  int search_diverse_groups(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint32_t fetch_k, float lam,
+                            bool distinct, const AllowGroups& groups, double now, uint64_t* ids, float* dist, uint32_t* ranks,
+                            uint32_t* counts);
+  int diverse_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint32_t fetch_k, float lam, bool distinct,
+                   double now, const uint64_t* allowed, uint64_t n_allowed, const AllowGroups* groups, uint64_t* ids, float* dist,
+                   uint32_t* ranks, uint32_t* counts);  // both forms
   // evaluate_search_quality (its wide form above k = FVDB_MAX_K) at every pair (efs[i], n_probes[j]) in one call
   // (DESIGN.md section 9r): one migration step; under ONE hold of the read lock one exact search, one traversal per
   // listed ef and one list search per listed n_probe, the PARTS kept; then fvdb_quality_grid_dev merges and counts
@@ -970,6 +1044,9 @@ class HybridIndex {
   // search_impl / search_exact after the migration step, the caller holding the read side of rw_
   int search_locked(const float* q, bool q_on_device, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids,
                     float* dist, uint32_t* counts, const uint64_t* allowed, uint64_t n_allowed, bool masked);
+  // search_allowed_groups after the migration step, the caller holding the read side of rw_
+  int groups_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const AllowGroups& groups, uint64_t* ids,
+                    float* dist, uint32_t* counts);
   // wide: the graph's wide exact scan, part sizes up to FVDB_MAX_K_WIDE
   int exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
                    uint32_t* counts, bool wide = false);
@@ -980,6 +1057,7 @@ class HybridIndex {
                    bool wide);
   std::mutex qual_mu_;  // evaluate_search_quality's staging block
   DevBuf qual_;
+  DiverseStage diverse_;
   // the explicit pair's begin, plain (shard_mode -1) or sharded: migration check, slot marked active, begin_impl
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                      int shard_mode, double now, const uint64_t* allowed = nullptr, uint64_t n_allowed = 0,

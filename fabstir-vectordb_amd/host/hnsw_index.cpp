@@ -183,6 +183,7 @@ HNSWIndex::~HNSWIndex() {
   }
   d_q_.release();
   qual_.release();
+  diverse_.release();
   for (Walk* w : {&search_walk_, &insert_walk_})
     if (w->sc) fvdb_scorer_destroy(w->sc);
   if (store_) fvdb_store_destroy(store_);

@@ -18,6 +18,7 @@ HybridIndex::HybridIndex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, const HybridConf
 
 HybridIndex::~HybridIndex() {
   qual_.release();
+  diverse_.release();
   // a batch that still waits for a partner has nothing enqueued for its IVF part; joint chains in flight end with the
   // release of their blocks, as the slots' own do
   for (Pair& p : pairs_) {
@@ -1152,6 +1153,12 @@ int HybridIndex::search_allowed_groups(const float* q, uint32_t B, uint32_t dim,
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);  // every mask below is built under it, after the migration
+  return groups_locked(q, B, dim, cfg, groups, ids, dist, counts);
+}
+
+int HybridIndex::groups_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const AllowGroups& groups,
+                               uint64_t* ids, float* dist, uint32_t* counts) {
+  const uint32_t k = (uint32_t)cfg.k;
   if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;
   const uint32_t rk = cfg.rk(), hk = cfg.hk();
   std::vector<uint64_t> rid, hid;

@@ -13,6 +13,7 @@ IVFIndex::~IVFIndex() {
   drop_mask();  // before the device index it points into
   allowed_q_.release();
   allowed_out_.release();
+  diverse_.release();
   if (dev_) fvdb_ivf_destroy(dev_);
 }
 

@@ -22,7 +22,7 @@ _host = None
 i64p = C.POINTER(C.c_int64)
 f64p = C.POINTER(C.c_double)
 u8p = C.POINTER(C.c_uint8)
-vp, u64, u32, i32, i64, dbl = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int64, C.c_double
+vp, u64, u32, i32, i64, dbl, f32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int64, C.c_double, C.c_float
 
 HOST_SIGNATURES = {
     "fvh_ivf_new": (vp, [vp, u32, u32, u32, u32, u64]),
@@ -176,6 +176,15 @@ HOST_SIGNATURES = {
     "fvh_hnsw_count_within": (i32, [vp, f32p, u32, u32, f32p, u64p, u64, u32p]),
     "fvh_ivf_search_radius": (i32, [vp, f32p, u32, u32, f32p, u32, u32, u64p, u64, u64p, f32p, u32p, u32p]),
     "fvh_hybrid_search_radius": (i32, [vp, f32p, u32, u32, f32p, u64, u64, i32, i32, u64p, u64, dbl, u64p, f32p, u32p, u32p]),
+    # diverse search
+    "fvh_set_diverse_stage_bytes": (None, [u64]),
+    "fvh_diverse_stage_bytes": (u64, []),
+    "fvh_ivf_search_diverse": (i32, [vp, f32p, u32, u32, u32, u32, f32, i32, u32, u64p, u64, u64p, f32p, u32p, u32p]),
+    "fvh_hnsw_search_diverse": (i32, [vp, f32p, u32, u32, u32, u32, f32, i32, u32, u64p, u64, u64p, f32p, u32p, u32p]),
+    "fvh_hybrid_search_diverse": (i32, [vp, f32p, u32, u32, u64, u32, f32, i32, u64, u64, i32, i32, u64p, u64, dbl, u64p, f32p, u32p,
+                                        u32p]),
+    "fvh_hybrid_search_diverse_groups": (i32, [vp, f32p, u32, u32, u64, u32, f32, i32, u64, u64, i32, i32, u64p, u64p, u8p, u32, u32p,
+                                               dbl, u64p, f32p, u32p, u32p]),
     # search quality over a grid of ef and n_probe from one exact search
     "fvh_hnsw_quality_by_ef": (i32, [vp, f32p, u32, u32, u32, u32p, u32, f32p, f32p, f32p, u64p]),
     "fvh_hybrid_quality_grid": (i32, [vp, f32p, u32, u32, u64, i32, i32, u64, u64, u32p, u32, u32p, u32, dbl, f32p, f32p, f32p,
@@ -229,6 +238,15 @@ class SearchResults:
     def scores(self):
         """Node/REST surface score = 1/(1+distance) in f32 (bindings/node/src/session.rs:291, src/api/rest.rs:653)."""
         return (np.float32(1.0) / (np.float32(1.0) + self.distances)).astype(np.float32)
+
+
+def set_diverse_stage_bytes(nbytes):
+    """The cap of search_diverse's staging block of candidate rows in HBM, for the process (default
+    256 MiB, or FVDB_DIVERSE_STAGE_BYTES read once): a batch is walked in sub-batches of the queries that fit, at least one.
+    0 restores the default.  The results do not depend on it.  Returns the cap now in force."""
+    lib = load_host()
+    lib.fvh_set_diverse_stage_bytes(int(nbytes))
+    return int(lib.fvh_diverse_stage_bytes())
 
 
 def round_f16(x):
@@ -335,6 +353,20 @@ class _Base:
         self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], _ptr(r, f32p), m, *mid, _ptr(ids, u64p), _ptr(ds, f32p),
                        _ptr(cnt, u32p), _ptr(totals, u32p)))
         return SearchResults(ids, ds, cnt), totals
+
+    def _search_diverse(self, fn, q, k, fetch_k, lam, distinct, *mid):
+        """The diverse searches: (SearchResults of [B][k] in pick order, ranks uint32[B][k])."""
+        q = _rows(q)
+        B, k, fetch_k, lam = q.shape[0], int(k), int(fetch_k), float(lam)
+        if not (k >= 0 and 0 <= fetch_k <= 0xFFFFFFFF):
+            raise InvalidConfig("Invalid parameter: k and fetch_k are unsigned")
+        ids = np.full((B, max(k, 1)), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        ds = np.full((B, max(k, 1)), np.inf, np.float32)
+        ranks = np.full((B, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        cnt = np.zeros(B, np.uint32)
+        self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], k, fetch_k, lam, int(bool(distinct)), *mid, _ptr(ids, u64p),
+                       _ptr(ds, f32p), _ptr(ranks, u32p), _ptr(cnt, u32p)))
+        return SearchResults(ids, ds, cnt), ranks
 
     def _quality(self, fn, queries, *args):
         """evaluate_search_quality of the graph and hybrid classes: SearchQuality as a dict, as IVFIndex returns it."""
@@ -609,6 +641,18 @@ class IVFIndex(_Base):
         return self._search_radius(self.lib.fvh_ivf_search_radius, queries, radius, max_results,
                                    self.n_probe if n_probe is None else n_probe, ap, an)
 
+    def search_diverse(self, queries, k, fetch_k, lam=0.5, distinct=True, n_probe=None, allowed=None):
+        """The k best rows that are not copies of each other: (results, ranks).  The candidates are
+        exactly what search(fetch_k, n_probe) — search_allowed with `allowed` — returns; on the device, k of them are
+        kept greedily by maximal marginal relevance, gain = (1 - lam) * (distance to the nearest pick) - lam * (distance
+        to the query) in f32, the first pick being the nearest row; distinct drops every later copy of an id first.
+        Results come in PICK order (not sorted by distance); ranks[b, i] (uint32) is the pick's position among the
+        candidates.  lam = 1 is the first k (distinct) candidates; lam = 0 a farthest-first traversal.
+        1 <= k <= fetch_k <= 256, lam in [0, 1]."""
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_diverse(self.lib.fvh_ivf_search_diverse, queries, k, fetch_k, lam, distinct,
+                                    self.n_probe if n_probe is None else n_probe, ap, an)
+
     def mask_builds(self):
         return int(self.lib.fvh_ivf_mask_builds(self.h))
 
@@ -761,6 +805,13 @@ class HNSWIndex(_Base):
             return self._search_radius(self.lib.fvh_hnsw_search_radius, queries, radius, max_results)
         a = _allowed_ids(allowed)
         return self._search_radius(self.lib.fvh_hnsw_search_radius_allowed, queries, radius, max_results, _ptr(a, u64p), a.size)
+
+    def search_diverse(self, queries, k, fetch_k, ef, lam=0.5, distinct=True, allowed=None):
+        """IVFIndex.search_diverse over the graph: the candidates are exactly what search(fetch_k, ef) — search_allowed
+        with `allowed` — returns.  A graph walk returns at most ef rows, so fetch_k > ef just yields fewer candidates.
+        (results, ranks) in pick order; 1 <= k <= fetch_k <= 256, lam in [0, 1]."""
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_diverse(self.lib.fvh_hnsw_search_diverse, queries, k, fetch_k, lam, distinct, int(ef), ap, an)
 
     def count_within(self, queries, radius, allowed=None):
         """search_radius()'s totals alone (uint32[B]), by a scan that keeps no distances and selects nothing."""
@@ -1242,6 +1293,29 @@ class HybridIndex(_Base):
         ap, an, keep = _allowed_args(allowed)
         return self._search_radius(self.lib.fvh_hybrid_search_radius, queries, radius, max_results, int(ivf_n_probe),
                                    int(search_recent), int(search_historical), ap, an, float(now))
+
+    def search_diverse(self, queries, k, fetch_k, lam=0.5, distinct=True, now=0.0, hnsw_ef=50, ivf_n_probe=10,
+                       search_recent=True, search_historical=True, allowed=None):
+        """IVFIndex.search_diverse over both parts: the candidates are exactly what search(fetch_k, ...) — search_allowed
+        with `allowed` — returns at these settings (the walk yields at most hnsw_ef recent rows), after one
+        auto-migration step; the search, the id-to-row lookup (the recent part first, as get_vectors) and the gather run
+        under one hold of the read lock.  search() returns a migrated row that still sits in the graph twice; with
+        distinct it comes once, and lam = 1 with distinct is the de-duplicated search().  (results, ranks) in pick order;
+        1 <= k <= fetch_k <= 256, lam in [0, 1].  Refused (Unsupported) on a sharded index."""
+        self._refuse_when_sharded("search_diverse")
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_diverse(self.lib.fvh_hybrid_search_diverse, queries, k, fetch_k, lam, distinct, int(hnsw_ef),
+                                    int(ivf_n_probe), int(search_recent), int(search_historical), ap, an, float(now))
+
+    def search_diverse_groups(self, queries, k, fetch_k, allow_sets, group_of_query, lam=0.5, distinct=True, now=0.0, hnsw_ef=50,
+                              ivf_n_probe=10, search_recent=True, search_historical=True):
+        """search_diverse() with one allow-set per query: the candidates of query b are what search_allowed_groups(fetch_k,
+        allow_sets, group_of_query) returns for it; one selection serves the batch."""
+        self._refuse_when_sharded("search_diverse_groups")
+        q = _rows(queries)
+        args, keep = _allow_groups(allow_sets, group_of_query, q.shape[0])
+        return self._search_diverse(self.lib.fvh_hybrid_search_diverse_groups, q, k, fetch_k, lam, distinct, int(hnsw_ef),
+                                    int(ivf_n_probe), int(search_recent), int(search_historical), *args, float(now))
 
     def evaluate_search_quality_wide(self, queries, k, now=0.0, hnsw_ef=50, ivf_n_probe=10):
         """evaluate_search_quality() with k in 1..4096: search() against search_exact_wide() under one hold of the lock."""

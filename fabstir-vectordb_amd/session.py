@@ -134,6 +134,25 @@ def _score_f32(d):
     return np.float32(1.0) / (np.float32(1.0) + np.float32(d))
 
 
+def diverse_options(options, k):
+    """The diverse-search options of one request: None when it names none of them, else
+    (fetch_k, lam, distinct).  "mmrLambda": float in [0, 1], absent = 1 (no re-ranking: "distinct" alone is the
+    de-duplicated search); "fetchK": integer in k..256, absent = min(256, 4 k); "distinct": absent = true."""
+    if not any(name in options for name in ("mmrLambda", "fetchK", "distinct")):
+        return None
+    k = int(k)
+    try:
+        lam = float(options.get("mmrLambda", 1.0))
+        fetch_k = int(options.get("fetchK", min(256, 4 * k)))
+    except (TypeError, ValueError) as e:
+        raise SessionError(f"Invalid mmrLambda or fetchK: {e}") from e
+    if not 0.0 <= lam <= 1.0:  # NaN included
+        raise SessionError(f"Invalid mmrLambda: {lam!r} (expected a number in [0, 1])")
+    if k < 1 or not k <= fetch_k <= 256:
+        raise SessionError(f"Invalid fetchK: {fetch_k} (expected k <= fetchK <= 256, with k = {k} >= 1)")
+    return fetch_k, float(np.float32(lam)), bool(options.get("distinct", True))
+
+
 def radius_of_threshold(threshold):
     """The radius that stands for a score threshold: the largest f32 d >= 0 whose score
     f32(1) / (f32(1) + d) is >= threshold, so that "distance bits <= bits(d)" IS the session's predicate and the device's
@@ -231,6 +250,9 @@ class VectorDbSession:
             raise SessionError(
                 f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
         threshold = np.float32(options.get("threshold", 0.0))
+        diverse = diverse_options(options, k)
+        if diverse is not None:
+            return self._search_diverse([q], k, [options], diverse)[0]
         # "exact" (not in the reference): the k nearest resident rows exactly — HybridIndex.search_exact, or its wide form
         # above 256 — in place of the graph walk and the n_probe nearest lists
         if options.get("exact"):
@@ -275,6 +297,53 @@ class VectorDbSession:
         except Exception as e:
             raise SessionError(f"Search failed: {e}") from e
         return self._results_of(res[0], threshold, bool(options.get("includeVectors", False)))  # session.rs:229-231
+
+    # -- diverse search: "mmrLambda" / "fetchK" / "distinct" (no counterpart in the reference) -----
+    def _search_diverse(self, qs, k, options_list, diverse):
+        """search() / search_many() with the diverse options, which every request of the batch shares: ONE
+        HybridIndex.search_diverse of fetchK candidates per query, grouped by filter as search_many groups, and one
+        selection on the device.  Results come in pick order; the threshold is applied to the picks afterwards."""
+        import json
+        fetch_k, lam, distinct = diverse
+        group_of_query, allow_sets, group_of_key = [], [], {}
+        for i, options in enumerate(options_list):
+            if options.get("exact"):
+                raise SessionError('"exact" cannot be combined with "mmrLambda" / "fetchK" / "distinct": the candidates of a '
+                                   'diverse search are those of the ordinary search of fetchK')
+            key = None
+            if options.get("filter") is not None:
+                mode = options.get("filterMode", "oversample")
+                if mode not in ("pushdown", "resident"):
+                    raise SessionError(f'a diverse search with a filter needs "filterMode": "pushdown" or "resident", not '
+                                       f'{mode!r}: "oversample" keeps what is left of 3 k candidates, while the selection '
+                                       'takes the fetchK candidates of a search under the allow-set')
+                key = (mode, json.dumps(options["filter"], sort_keys=True, separators=(",", ":")))
+            if key not in group_of_key:
+                allowed = None
+                if key is not None:
+                    try:
+                        flt = MetadataFilter.from_json(options["filter"])
+                    except FilterError as e:
+                        raise SessionError(f"Invalid filter: {e}") from e
+                    if key[0] == "resident":
+                        allowed = self._resident_allowed(flt)
+                    else:
+                        allowed = np.fromiter((rid for rid, name in self._rows.items()
+                                               if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                group_of_key[key] = len(allow_sets)
+                allow_sets.append(allowed)
+            group_of_query.append(group_of_key[key])
+        try:
+            if len(allow_sets) == 1:  # one filter, or none, for the whole batch
+                res, _ = self.index.search_diverse(np.stack(qs), int(k), fetch_k, lam, distinct, now=self.now,
+                                                   allowed=allow_sets[0])  # defaults: ef 50, nprobe 10
+            else:
+                res, _ = self.index.search_diverse_groups(np.stack(qs), int(k), fetch_k, allow_sets,
+                                                          np.asarray(group_of_query, np.uint32), lam, distinct, now=self.now)
+        except Exception as e:
+            raise SessionError(f"Search failed: {e}") from e
+        return [self._results_of(res[i], np.float32(o.get("threshold", 0.0)), bool(o.get("includeVectors", False)))
+                for i, o in enumerate(options_list)]
 
     # -- search_within: every row whose score clears a threshold (no counterpart in the reference) -------------------
     def search_within(self, query_vector, threshold, options=None):
@@ -410,6 +479,20 @@ class VectorDbSession:
         options_list = [{} for _ in range(n)] if options_list is None else [o or {} for o in options_list]
         if len(options_list) != n:
             raise SessionError(f"search_many: {n} queries but {len(options_list)} option sets")
+        # the diverse options ("mmrLambda", "fetchK", "distinct"): all requests or none, and the same values
+        diverse = [diverse_options(o, k) for o in options_list]
+        if any(d is not None for d in diverse):
+            if any(d != diverse[0] for d in diverse):
+                raise SessionError('search_many: "mmrLambda" / "fetchK" / "distinct" must have the same values in every request '
+                                   'of a batch (one search of fetchK and one selection serve it)')
+            qs = []
+            for qv in query_vectors:
+                q = js_array_to_vec_f32(qv)
+                if self.vector_dimension is not None and q.size != self.vector_dimension:
+                    raise SessionError(
+                        f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+                qs.append(q)
+            return self._search_diverse(qs, k, options_list, diverse[0])
         qs, group_of_query, allow_sets, group_of_key = [], [], [], {}
         for i, (qv, options) in enumerate(zip(query_vectors, options_list)):
             q = js_array_to_vec_f32(qv)

@@ -813,6 +813,38 @@ int fvdb_ivf_search_radius_dev_slot(fvdb_ivf* ivf, fvdb_ctx* on, uint32_t slot, 
  * FVDB_E_NONFINITE as there; a negative or NaN radius is FVDB_E_INVALID. */
 int fvdb_ivf_search_radius(fvdb_ivf* ivf, const float* q, uint32_t B, const float* radius, uint32_t max_results, uint32_t nprobe,
                            uint64_t* out_ids, float* out_dist, uint32_t* out_counts, uint32_t* out_totals);
+
+/* ---- diverse selection -------------------------------------------
+ * "The k best rows that are not copies of each other": of the candidates a search of fetch_k returned for a query,
+ * keep k by maximal marginal relevance, optionally after dropping every later copy of an id.  Per query, with
+ * candidates c = 0 .. n-1 (n = min(counts[b], fetch_k)) in the order given, a = (float)lam, b = 1.0f - a:
+ *   1. distinct: c is dropped when some c' < c has the same id;
+ *   2. the first pick is the first kept candidate;
+ *   3. after every pick s, for each kept unpicked c: t = the reference distance of row c to row s (f32, dimensions
+ *      ascending, no FMA, sqrtf), m[c] = min(m[c], t) from +inf, gain[c] = b * m[c] - a * dist[c] (two multiplies and
+ *      one subtract, each rounded once); the next pick has the largest gain, the smallest c among equal gains;
+ *   4. min(k, kept) picks.
+ * Outputs are [B][k] in PICK order: the id, the distance as given, and the rank (the candidate position c); tails are
+ * FVDB_NO_ID / +inf / FVDB_NO_ROW; out_counts[b] = the number of picks.  lam = 1 is the first k kept candidates.
+ * rows_dev: [B][fetch_k][row_stride] f32, 16-byte aligned, candidate c of query b at (b * fetch_k + c) * row_stride; the
+ * whole stride is folded, so every float past the dimension must be zero.  Rows of candidates at or beyond the count
+ * are not read.  Everything is device memory; the call is enqueued on ctx's stream and does not synchronise.
+ * fetch_k == 0 or > FVDB_MAX_K: FVDB_E_UNSUPPORTED; k == 0, k > fetch_k, lam NaN or outside [0, 1], row_stride == 0 or
+ * not a multiple of 4, a NULL buffer with B > 0: FVDB_E_INVALID; B == 0: FVDB_OK, nothing enqueued. */
+int fvdb_mmr_select_dev(fvdb_ctx* ctx, const float* rows_dev, uint32_t row_stride, const uint64_t* ids_dev, const float* dist_dev,
+                        const uint32_t* counts_dev, uint32_t B, uint32_t fetch_k, uint32_t k, float lam, int distinct,
+                        uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_rank_dev, uint32_t* out_counts_dev);
+/* The gathers that fill such a block.  fvdb_ivf_get_rows_dev with output row i at out_rows_dev + i * out_stride
+ * (out_stride >= d, else FVDB_E_INVALID); dimensions d .. min(out_stride, d rounded up to 4) are written as zeros, and a
+ * location whose cluster is FVDB_NO_ROW is skipped (its output row is left as it was).  out_stride == d is
+ * fvdb_ivf_get_rows_dev. */
+int fvdb_ivf_get_rows_dev_strided(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* cluster, const uint32_t* pos, uint64_t n,
+                                  float* out_rows_dev, uint32_t out_stride);
+/* Rows of a row store by row index, the same output form: rows_dev[n] in DEVICE memory, widened exactly when the store
+ * is fp16; an index at or beyond fvdb_store_rows() (FVDB_NO_ROW among them) is skipped.  Enqueued on `on`'s stream
+ * (NULL = the store's); no synchronisation.  Reads only. */
+int fvdb_store_get_rows_dev(fvdb_store* store, fvdb_ctx* on, const uint32_t* rows_dev, uint64_t n, float* out_rows_dev,
+                            uint32_t out_stride);
 /* The comparison of fvdb_ivf_search_quality_dev on two id blocks the caller holds in HBM (B x k ids with their hit
  * counts; entries at or beyond a count are not read): per query matches, recall and precision by the formulas stated
  * there — an id the result holds twice counts twice — to out_recall_dev[B] / out_precision_dev[B], enqueued on ctx's
