@@ -116,6 +116,10 @@ SIGNATURES = {
     "fvdb_mmr_select_dev": (i32, [vp, vp, u32, vp, vp, vp, u32, u32, u32, f32, i32, vp, vp, vp, vp]),
     "fvdb_ivf_get_rows_dev_strided": (i32, [vp, vp, u32p, u32p, u64, vp, u32]),
     "fvdb_store_get_rows_dev": (i32, [vp, vp, vp, u64, vp, u32]),
+    # grouped selection: the keys of candidate ids under a metadata column, and the selection
+    "fvdb_group_keys_of_ids_dev": (i32, [vp, u32, vp, u64, vp, vp]),
+    "fvdb_group_keys_ctx": (vp, [vp]),
+    "fvdb_group_select_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fvdb_ivf_assign_from_store": (i32, [vp, vp, u32p, u64, u32p]),
     "fvdb_ivf_add_assigned_from_store": (i32, [vp, vp, u32p, u64p, u64, u32p, u32p]),
     "fvdb_ivf_search": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),

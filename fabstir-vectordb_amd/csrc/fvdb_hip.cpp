@@ -34,6 +34,7 @@
 #include "kernels_maint.h"
 #include "kernels_rows.h"
 #include "kernels_mmr.h"
+#include "kernels_group.h"
 
 using namespace fvdb;
 
@@ -2762,6 +2763,56 @@ int fvdb_mmr_select_dev(fvdb_ctx* ctx, const float* rows_dev, uint32_t row_strid
   const float a = lam, b = 1.0f - a;
   hipLaunchKernelGGL(mmr_select_kernel, dim3(B), dim3(256), 0, ctx->stream, rows_dev, row_stride, ids_dev, dist_dev, counts_dev,
                      fetch_k, k, a, b, distinct ? 1u : 0u, out_ids_dev, out_dist_dev, out_rank_dev, out_counts_dev);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// Grouped selection (kernels_group.h): one workgroup per query, everything in device memory.  Up to
+// FVDB_MAX_K candidates the small instantiation (256 threads, 6.3 KiB of LDS), above it the full one (1024 threads,
+// 100 KiB).
+int fvdb_group_select_dev(fvdb_ctx* ctx, const uint64_t* ids_dev, const float* dist_dev, const uint32_t* counts_dev,
+                          const uint8_t* key_tag_dev, const uint64_t* key_val_dev, uint32_t B, uint32_t fetch_k, uint32_t k,
+                          uint32_t group_size, int distinct, int missing, uint64_t* out_ids_dev, float* out_dist_dev,
+                          uint32_t* out_rank_dev, uint32_t* out_members_dev, uint32_t* out_group_total_dev, uint8_t* out_key_tag_dev,
+                          uint64_t* out_key_val_dev, uint32_t* out_groups_dev, uint32_t* out_flags_dev) {
+  if (!ctx) return FVDB_E_INVALID;
+  if (fetch_k == 0 || fetch_k > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "fetch_k must be in 1..FVDB_MAX_K_WIDE");
+  if (k == 0 || group_size == 0) FAIL(ctx, FVDB_E_INVALID, "k and group_size must be at least 1");
+  if ((uint64_t)k * group_size > FVDB_MAX_K_WIDE) FAIL(ctx, FVDB_E_UNSUPPORTED, "k * group_size must be at most FVDB_MAX_K_WIDE");
+  if (missing != FVDB_GROUP_MISSING_DROP && missing != FVDB_GROUP_MISSING_OWN) FAIL(ctx, FVDB_E_INVALID, "missing must be DROP or OWN");
+  if (B == 0) return FVDB_OK;
+  if (!ids_dev || !dist_dev || !counts_dev || !key_tag_dev || !key_val_dev || !out_ids_dev || !out_dist_dev || !out_rank_dev ||
+      !out_members_dev || !out_group_total_dev || !out_key_tag_dev || !out_key_val_dev || !out_groups_dev || !out_flags_dev)
+    FAIL(ctx, FVDB_E_INVALID, "null buffer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  GroupArgs a{};
+  a.ids = ids_dev;
+  a.dist = dist_dev;
+  a.counts = counts_dev;
+  a.key_tag = key_tag_dev;
+  a.key_val = key_val_dev;
+  a.fetch_k = fetch_k;
+  a.k = k;
+  a.group_size = group_size;
+  a.distinct = distinct ? 1u : 0u;
+  a.missing = missing == FVDB_GROUP_MISSING_OWN ? kGroupMissingOwn : kGroupMissingDrop;
+  a.out_ids = out_ids_dev;
+  a.out_dist = out_dist_dev;
+  a.out_rank = out_rank_dev;
+  a.out_members = out_members_dev;
+  a.out_total = out_group_total_dev;
+  a.out_key_tag = out_key_tag_dev;
+  a.out_key_val = out_key_val_dev;
+  a.out_groups = out_groups_dev;
+  a.out_flags = out_flags_dev;
+  if (fetch_k <= kGroupSmallMax) {
+    hipLaunchKernelGGL((group_select_kernel<kGroupSmallMax, 256>), dim3(B), dim3(256), sizeof(GroupLds<kGroupSmallMax>), ctx->stream, a);
+  } else {
+    // like rank_sort_kernel's: the attribute belongs to the function, every call sets the same value
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)group_select_kernel<kGroupFullMax, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(GroupLds<kGroupFullMax>)));
+    hipLaunchKernelGGL((group_select_kernel<kGroupFullMax, 1024>), dim3(B), dim3(1024), sizeof(GroupLds<kGroupFullMax>), ctx->stream, a);
+  }
   HIPCHK(ctx, hipGetLastError());
   return FVDB_OK;
 }

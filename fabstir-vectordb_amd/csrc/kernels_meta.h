@@ -204,4 +204,76 @@ __global__ __launch_bounds__(256) void meta_scatter_bytes_kernel(const uint32_t*
   if (i < n) out[slots[i]] = bytes[i];
 }
 
+// ---- id -> slot: an open-addressing index in HBM, linear probing, `mask + 1` cells (a power of
+// two of at least twice the slots, so a probe always meets an empty cell).  A cell is an id word and a slot word.  The
+// empty id word is FVDB_NO_ID: a candidate with that id has no key by definition, so a slot that carries it is never
+// entered and never looked up, and every other id, 0 among them, is an ordinary id.
+constexpr uint64_t kMetaIndexEmpty = ~0ull;
+
+__device__ __forceinline__ uint32_t meta_index_hash(uint64_t id, uint32_t mask) {
+  id ^= id >> 33;
+  id *= 0xFF51AFD7ED558CCDull;
+  id ^= id >> 33;
+  return (uint32_t)id & mask;
+}
+
+// both arrays start as all ones.  A 64-bit compare-and-swap claims the id word; an atomic min settles the slot word, so
+// of the slots that carry one id the LOWEST wins whatever the order the threads arrive in.
+__global__ __launch_bounds__(256) void meta_index_build_kernel(const uint64_t* __restrict__ ids, uint32_t slots, uint64_t* __restrict__ hid,
+                                                               uint32_t* __restrict__ hslot, uint32_t mask) {
+  const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+  if (slot >= slots) return;
+  const uint64_t id = ids[slot];
+  if (id == kMetaIndexEmpty) return;
+  uint32_t h = meta_index_hash(id, mask);
+  for (uint32_t step = 0; step <= mask; ++step) {  // slots <= (mask + 1) / 2: ends at a cell of its own long before
+    const unsigned long long old = atomicCAS((unsigned long long*)&hid[h], (unsigned long long)kMetaIndexEmpty, (unsigned long long)id);
+    if (old == kMetaIndexEmpty || old == id) {
+      atomicMin(&hslot[h], slot);
+      return;
+    }
+    h = (h + 1) & mask;
+  }
+}
+
+// the key of one id by the rule of section 9v: (MISSING, 0) when the id is FVDB_NO_ID, is in no slot, its slot is not
+// present, or its cell is MISSING, ARRAY, COMPLEX or a FLOAT NaN; otherwise the cell's tag and its word as stored, a
+// FLOAT -0.0 folded onto 0.0, a NULL as 0.  Presence and the cell are read now: only set_rows asks for a rebuild.
+__global__ __launch_bounds__(256) void meta_keys_of_ids_kernel(const uint64_t* __restrict__ ids, uint64_t n, const uint64_t* __restrict__ hid,
+                                                               const uint32_t* __restrict__ hslot, uint32_t mask, uint32_t slots,
+                                                               const uint8_t* __restrict__ present, const uint8_t* __restrict__ ctag,
+                                                               const uint64_t* __restrict__ cval, uint8_t* __restrict__ out_tag,
+                                                               uint64_t* __restrict__ out_key) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t id = ids[i];
+  uint32_t slot = 0xFFFFFFFFu;
+  if (id != kMetaIndexEmpty && slots != 0) {
+    uint32_t h = meta_index_hash(id, mask);
+    for (uint32_t step = 0; step <= mask; ++step) {
+      const uint64_t e = hid[h];
+      if (e == kMetaIndexEmpty) break;
+      if (e == id) {
+        slot = hslot[h];
+        break;
+      }
+      h = (h + 1) & mask;
+    }
+  }
+  uint32_t tag = kMetaMissing;
+  uint64_t key = 0;
+  if (slot < slots && present[slot] != 0) {
+    const uint32_t t = ctag[slot];
+    uint64_t v = cval[slot];
+    if (t == kMetaFloat && (v << 1) == 0ull) v = 0ull;
+    const bool nan = t == kMetaFloat && (v & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
+    if (t >= kMetaNull && t <= kMetaString && !nan) {
+      tag = t;
+      key = t == kMetaNull ? 0ull : v;
+    }
+  }
+  out_tag[i] = (uint8_t)tag;
+  out_key[i] = key;
+}
+
 }  // namespace fvdb

@@ -21,6 +21,9 @@ struct fvdb_meta {
   std::vector<MetaCol> cols;
   DBuf coltab;                  // MetaColumn[cols], uploaded when a column appeared or moved
   bool coltab_dirty = true;
+  DBuf idx_id, idx_slot;        // id -> slot index (kernels_meta.h): [idx_cells] id words and slot words
+  uint64_t idx_cells = 0;       // a power of two >= 2 * slots once built
+  bool idx_dirty = true;        // set_rows has run since the last build
   DBuf prog;                    // constants' keys, instructions, constants' tags of the evaluation in flight
   DBuf ballots, counts, totals, out_ids, out_unknown, out_rank;
   uint64_t n_match = 0, n_unknown = 0;
@@ -129,7 +132,7 @@ int fvdb_meta_info(fvdb_meta* t, fvdb_meta_info_t* out) {
   out->present = t->present;
   out->columns = t->cols.size();
   out->live_elements = out->dead_elements = 0;
-  uint64_t bytes = t->ids.cap + t->pres.cap + t->coltab.cap + t->prog.cap + t->ballots.cap + t->counts.cap + t->totals.cap +
+  uint64_t bytes = t->ids.cap + t->pres.cap + t->idx_id.cap + t->idx_slot.cap + t->coltab.cap + t->prog.cap + t->ballots.cap + t->counts.cap + t->totals.cap +
                    t->out_ids.cap + t->out_unknown.cap + t->out_rank.cap;
   for (const MetaCol& c : t->cols) {
     out->live_elements += c.e_live;
@@ -150,6 +153,7 @@ int fvdb_meta_set_rows(fvdb_meta* t, uint64_t first, uint64_t n, const uint64_t*
   if (n == 0) return FVDB_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = meta_reserve(t, first + n)) return rc;
+  t->idx_dirty = true;  // the id index is rebuilt by the next key lookup
   HIPCHK(ctx, hipMemcpyAsync(t->ids.as<uint64_t>() + first, ids, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(t->pres.as<uint8_t>() + first, present, n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are its own again
@@ -372,5 +376,48 @@ int fvdb_meta_eval_dev(fvdb_meta* t, const uint64_t** ids_dev, const uint32_t** 
   if (out_unknown) *out_unknown = t->n_unknown;
   return FVDB_OK;
 }
+
+// The keys of n candidate ids under one column: the id index is built here when set_rows has run
+// since the last build, then one thread per id looks its slot up and reads presence and the cell as they are now.
+int fvdb_group_keys_of_ids_dev(fvdb_meta* t, uint32_t column, const uint64_t* ids_dev, uint64_t n, uint8_t* out_tag_dev, uint64_t* out_key_dev) {
+  if (!t) return FVDB_E_INVALID;
+  fvdb_ctx* ctx = t->ctx;
+  std::lock_guard<std::mutex> lk(t->mu);
+  if (column >= t->cols.size()) FAIL(ctx, FVDB_E_INVALID, "group keys: column out of range");
+  if (n >= (1ull << 31)) FAIL(ctx, FVDB_E_UNSUPPORTED, "group keys: 2^31 ids or more in one call");
+  if (n == 0) return FVDB_OK;
+  if (!ids_dev || !out_tag_dev || !out_key_dev) FAIL(ctx, FVDB_E_INVALID, "group keys: null buffer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const uint32_t slots = (uint32_t)t->slots;  // < 2^32: set_rows
+  if (t->idx_dirty && slots) {
+    uint64_t cells = 1024;
+    while (cells < 2 * t->slots) cells <<= 1;  // <= 2^33 > 2 * slots; the mask below needs cells <= 2^32
+    if (cells > (1ull << 32)) FAIL(ctx, FVDB_E_UNSUPPORTED, "group keys: a table of 2^31 slots or more");
+    if (cells != t->idx_cells) {
+      t->idx_cells = 0;
+      HIPCHK(ctx, hipStreamSynchronize(st));  // a lookup enqueued earlier may still read the old arrays
+      HIPCHK(ctx, t->idx_id.exact(cells * 8));
+      HIPCHK(ctx, t->idx_slot.exact(cells * 4));
+      t->idx_cells = cells;
+    }
+    HIPCHK(ctx, hipMemsetAsync(t->idx_id.p, 0xFF, cells * 8, st));
+    HIPCHK(ctx, hipMemsetAsync(t->idx_slot.p, 0xFF, cells * 4, st));
+    hipLaunchKernelGGL(meta_index_build_kernel, dim3(cdiv(slots, 256)), dim3(256), 0, st, (const uint64_t*)t->ids.as<uint64_t>(), slots,
+                       t->idx_id.as<uint64_t>(), t->idx_slot.as<uint32_t>(), (uint32_t)(cells - 1));
+    HIPCHK(ctx, hipGetLastError());
+    t->idx_dirty = false;
+  }
+  const MetaCol& c = t->cols[column];
+  hipLaunchKernelGGL(meta_keys_of_ids_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, st, ids_dev, n,
+                     (const uint64_t*)t->idx_id.as<uint64_t>(), (const uint32_t*)t->idx_slot.as<uint32_t>(),
+                     (uint32_t)(t->idx_cells ? t->idx_cells - 1 : 0), slots, (const uint8_t*)t->pres.as<uint8_t>(),
+                     (const uint8_t*)c.tag.as<uint8_t>(), (const uint64_t*)c.val.as<uint64_t>(), out_tag_dev, out_key_dev);
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// The context whose stream carries the lookup above: a caller that selects on another stream waits for this one first.
+fvdb_ctx* fvdb_group_keys_ctx(fvdb_meta* t) { return t ? t->ctx : nullptr; }
 
 }  // extern "C"

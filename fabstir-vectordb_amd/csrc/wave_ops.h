@@ -1,5 +1,5 @@
 // wave_ops.h — the cross-lane helpers of one wavefront (64 lanes), and the workgroup scan built on them.  Every kernel
-// header takes them from here; none of them touches LDS.
+// header takes them from here; the wave helpers touch no LDS, the workgroup scan uses 16 words its caller lends.
 #pragma once
 #include "common.h"
 
@@ -78,28 +78,40 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u(uint32_t v, int lane) {
 // set bits of a ballot below this lane: the lane's rank among the lanes that voted
 __device__ __forceinline__ uint32_t ballot_rank(uint64_t m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
 
+// The workgroup scan, once: the sum of the x of every thread before this one, and the workgroup's sum in `total`.  Every
+// thread of a workgroup of `waves` whole waves (at most 16) calls it; s_wave is 16 words of LDS the caller lends, free
+// again after the caller's next barrier.  One barrier inside.
+__device__ __forceinline__ uint32_t block_excl_scan_u(uint32_t x, uint32_t* s_wave, uint32_t lane, uint32_t wave, uint32_t waves,
+                                                      uint32_t& total) {
+  const uint32_t incl = wave_incl_scan_u(x, (int)lane);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+  for (uint32_t w = 0; w < waves; ++w) {
+    const uint32_t cw = s_wave[w];
+    before += w < wave ? cw : 0u;
+    all += cw;
+  }
+  total = all;
+  return before + incl - x;
+}
+
 // exclusive prefix sum of v[0 .. m) in place, the total into *total; one workgroup of 1024
 template <typename Total>
 __global__ __launch_bounds__(1024) void block_excl_scan_kernel(uint32_t* __restrict__ v, uint32_t m, Total* __restrict__ total) {
   __shared__ uint32_t s_wave[16];
-  __shared__ uint32_t s_base;
+  uint32_t base = 0;  // uniform: every thread adds the same chunk totals
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
   for (uint32_t c0 = 0; c0 < m; c0 += 1024) {
     const uint32_t i = c0 + threadIdx.x;
     const uint32_t x = i < m ? v[i] : 0u;
-    const uint32_t incl = wave_incl_scan_u(x, (int)lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = s_base;
-    for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-    if (i < m) v[i] = before + incl - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_base = before + incl;
-    __syncthreads();
+    uint32_t chunk;
+    const uint32_t before = block_excl_scan_u(x, s_wave, lane, wave, 16u, chunk);
+    if (i < m) v[i] = base + before;
+    base += chunk;
+    __syncthreads();  // s_wave is written again by the next chunk
   }
-  if (threadIdx.x == 0) *total = s_base;
+  if (threadIdx.x == 0) *total = base;
 }
 
 }  // namespace fvdb

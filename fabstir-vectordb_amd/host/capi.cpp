@@ -293,6 +293,37 @@ int fvh_hybrid_search_diverse_groups(void* p, const float* q, uint32_t B, uint32
   const AllowGroups groups{allow_ids, allow_off, filtered, G, group_of_query};
   return ((HybridIndex*)p)->search_diverse_groups(q, B, d, c, fetch_k, lam, distinct != 0, groups, now, ids, dist, ranks, counts);
 }
+// grouped search: k groups of up to group_size members by the cells of column `column` of the
+// metadata table `meta`; ctx = the context of the index.  ids / dist / ranks [B][k][group_size], members /
+// totals / key_tags / key_vals [B][k], groups / flags [B].  allowed == NULL: no filter
+int fvh_ivf_search_grouped(void* p, fvdb_ctx* ctx, fvdb_meta* meta, uint32_t column, const float* q, uint32_t B,
+                           uint32_t d, uint32_t k, uint32_t group_size, uint32_t fetch_k, int distinct, int missing, uint32_t n_probe,
+                           const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* members,
+                           uint32_t* totals, uint8_t* key_tags, uint64_t* key_vals, uint32_t* groups, uint32_t* flags) {
+  return search_grouped(*(IVFIndex*)p, ctx, GroupBy{meta, column}, q, B, d, k, group_size, fetch_k, distinct != 0, missing, n_probe,
+                        allowed, n_allowed, GroupedOut{ids, dist, ranks, members, totals, key_tags, key_vals, groups, flags});
+}
+int fvh_hnsw_search_grouped(void* p, fvdb_ctx* ctx, fvdb_meta* meta, uint32_t column, const float* q, uint32_t B,
+                            uint32_t d, uint32_t k, uint32_t group_size, uint32_t fetch_k, int distinct, int missing, uint32_t ef,
+                            const uint64_t* allowed, uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* members,
+                            uint32_t* totals, uint8_t* key_tags, uint64_t* key_vals, uint32_t* groups, uint32_t* flags) {
+  return search_grouped(*(HNSWIndex*)p, ctx, GroupBy{meta, column}, q, B, d, k, group_size, fetch_k, distinct != 0, missing, ef,
+                        allowed, n_allowed, GroupedOut{ids, dist, ranks, members, totals, key_tags, key_vals, groups, flags});
+}
+int fvh_hybrid_search_grouped(void* p, fvdb_ctx* ctx, fvdb_meta* meta, uint32_t column, const float* q, uint32_t B,
+                              uint32_t d, uint64_t k, uint32_t group_size, uint32_t fetch_k, int distinct, int missing, uint64_t hnsw_ef,
+                              uint64_t ivf_n_probe, int search_recent, int search_historical, const uint64_t* allowed,
+                              uint64_t n_allowed, double now, uint64_t* ids, float* dist, uint32_t* ranks, uint32_t* members,
+                              uint32_t* totals, uint8_t* key_tags, uint64_t* key_vals, uint32_t* groups, uint32_t* flags) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.hnsw_ef = hnsw_ef;
+  c.ivf_n_probe = ivf_n_probe;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return search_grouped(*(HybridIndex*)p, ctx, GroupBy{meta, column}, q, B, d, c, group_size, fetch_k, distinct != 0, missing, now,
+                        allowed, n_allowed, GroupedOut{ids, dist, ranks, members, totals, key_tags, key_vals, groups, flags});
+}
 int fvh_hnsw_evaluate_search_quality_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint32_t ef, float* out3,
                                           uint64_t* queries_evaluated) {
   SearchQuality s{};

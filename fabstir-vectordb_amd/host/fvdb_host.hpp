@@ -265,6 +265,39 @@ int select_diverse(fvdb_ctx* ctx, DiverseStage& st, RowSource& src, uint32_t dim
                    float lam, bool distinct, const uint64_t* cid, const float* cd, const uint32_t* cc, uint64_t* ids, float* dist,
                    uint32_t* ranks, uint32_t* counts);
 
+// Grouped search (fvdb_group_keys_of_ids_dev, fvdb_group_select_dev): the candidates of an ordinary
+// search of fetch_k, their keys under one column of a metadata table looked up in HBM, the first k groups with
+// group_size members each selected per query.  The class searches hand their candidates back in host memory, so one
+// upload of ids, distances and counts per sub-batch goes down; keys never visit the host.
+struct GroupBy {
+  fvdb_meta* table;      // the metadata table and the column whose cells are the keys
+  uint32_t column;
+};
+struct GroupedOut {      // host arrays, as fvdb_group_select_dev lays them out
+  uint64_t* ids;         // [B][k][group_size]
+  float* dist;
+  uint32_t* ranks;
+  uint32_t* members;     // [B][k]
+  uint32_t* totals;
+  uint8_t* key_tags;
+  uint64_t* key_vals;
+  uint32_t* groups;      // [B]
+  uint32_t* flags;
+};
+constexpr uint64_t kGroupedStageBytes = 64ull << 20;  // device block of one sub-batch: as many queries as fit, at least one
+// the refusals every search_grouped makes first, in fvdb_group_select_dev's order
+inline int check_grouped(uint32_t fetch_k, uint32_t k, uint32_t group_size, int missing) {
+  if (fetch_k == 0 || fetch_k > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  if (k == 0 || group_size == 0) return FVDB_E_INVALID;
+  if ((uint64_t)k * group_size > FVDB_MAX_K_WIDE) return FVDB_E_UNSUPPORTED;
+  if (missing != FVDB_GROUP_MISSING_DROP && missing != FVDB_GROUP_MISSING_OWN) return FVDB_E_INVALID;
+  return FVDB_OK;
+}
+void fill_empty_grouped(const GroupedOut& out, uint32_t B, uint32_t k, uint32_t group_size);
+// cid / cd [B][fetch_k] and cc[B]: what the search of fetch_k returned (host memory)
+int select_grouped(fvdb_ctx* ctx, const GroupBy& by, uint32_t B, uint32_t fetch_k, uint32_t k, uint32_t group_size, bool distinct,
+                   int missing, const uint64_t* cid, const float* cd, const uint32_t* cc, const GroupedOut& out);
+
 // ------------------------------------------------------------------------------------------
 // IVFIndex — src/ivf/core.rs, src/ivf/operations.rs
 // ------------------------------------------------------------------------------------------
@@ -1203,5 +1236,19 @@ void plan_list_owners_host(const uint64_t* sizes, uint32_t nlist, uint32_t world
 void merge_parts_host(uint32_t B, uint32_t k, uint32_t rk, uint32_t hk, const uint64_t* rid, const float* rd,
                       const uint32_t* rc, const uint64_t* hid, const float* hd, const uint32_t* hc, uint64_t* ids,
                       float* dist, uint32_t* counts);
+
+// Grouped search of the three classes: the candidates are exactly what the class's search(fetch_k)
+// — search_allowed when `allowed` is given — returns at these settings, so the register route up to FVDB_MAX_K and the
+// wide route above it; `ctx` carries the upload, the selection and the download.  For the hybrid index cfg.k counts
+// groups and the candidate search runs with k = fetch_k, recent_k = historical_k = 0; it takes search()'s migration step.
+int search_grouped(IVFIndex& ix, fvdb_ctx* ctx, const GroupBy& by, const float* q, uint32_t B, uint32_t dim, uint32_t k,
+                   uint32_t group_size, uint32_t fetch_k, bool distinct, int missing, uint32_t n_probe, const uint64_t* allowed,
+                   uint64_t n_allowed, const GroupedOut& out);
+int search_grouped(HNSWIndex& ix, fvdb_ctx* ctx, const GroupBy& by, const float* q, uint32_t B, uint32_t dim, uint32_t k,
+                   uint32_t group_size, uint32_t fetch_k, bool distinct, int missing, uint32_t ef, const uint64_t* allowed,
+                   uint64_t n_allowed, const GroupedOut& out);
+int search_grouped(HybridIndex& ix, fvdb_ctx* ctx, const GroupBy& by, const float* q, uint32_t B, uint32_t dim,
+                   const HybridSearchConfig& cfg, uint32_t group_size, uint32_t fetch_k, bool distinct, int missing, double now,
+                   const uint64_t* allowed, uint64_t n_allowed, const GroupedOut& out);
 
 }  // namespace fvdbh

@@ -185,6 +185,13 @@ HOST_SIGNATURES = {
                                         u32p]),
     "fvh_hybrid_search_diverse_groups": (i32, [vp, f32p, u32, u32, u64, u32, f32, i32, u64, u64, i32, i32, u64p, u64p, u8p, u32, u32p,
                                                dbl, u64p, f32p, u32p, u32p]),
+    # grouped search: index, its context, the metadata table, the column, ...
+    "fvh_ivf_search_grouped": (i32, [vp, vp, vp, u32, f32p, u32, u32, u32, u32, u32, i32, i32, u32, u64p, u64, u64p, f32p, u32p,
+                                     u32p, u32p, u8p, u64p, u32p, u32p]),
+    "fvh_hnsw_search_grouped": (i32, [vp, vp, vp, u32, f32p, u32, u32, u32, u32, u32, i32, i32, u32, u64p, u64, u64p, f32p, u32p,
+                                      u32p, u32p, u8p, u64p, u32p, u32p]),
+    "fvh_hybrid_search_grouped": (i32, [vp, vp, vp, u32, f32p, u32, u32, u64, u32, u32, i32, i32, u64, u64, i32, i32, u64p, u64,
+                                        dbl, u64p, f32p, u32p, u32p, u32p, u8p, u64p, u32p, u32p]),
     # search quality over a grid of ef and n_probe from one exact search
     "fvh_hnsw_quality_by_ef": (i32, [vp, f32p, u32, u32, u32, u32p, u32, f32p, f32p, f32p, u64p]),
     "fvh_hybrid_quality_grid": (i32, [vp, f32p, u32, u32, u64, i32, i32, u64, u64, u32p, u32, u32p, u32, dbl, f32p, f32p, f32p,
@@ -238,6 +245,45 @@ class SearchResults:
     def scores(self):
         """Node/REST surface score = 1/(1+distance) in f32 (bindings/node/src/session.rs:291, src/api/rest.rs:653)."""
         return (np.float32(1.0) / (np.float32(1.0) + self.distances)).astype(np.float32)
+
+
+GROUP_MISSING = {"drop": 0, "own": 1}  # FVDB_GROUP_MISSING_*
+
+
+class GroupedResults:
+    """What search_grouped returns, as fvdb_group_select_dev lays it out: ids / distances / ranks
+    [B][k][group_size] (tails FVDB_NO_ID / +inf / FVDB_NO_ROW), members / totals / key_tags / key_words [B][k], groups and
+    flags [B].  result[b] lists query b's groups as (key tag, key word, ids, distances, ranks, total) in group order."""
+
+    def __init__(self, ids, distances, ranks, members, totals, key_tags, key_words, groups, flags, k, group_size):
+        self.ids, self.distances, self.ranks, self.members, self.totals = ids, distances, ranks, members, totals
+        self.key_tags, self.key_words, self.groups, self.flags = key_tags, key_words, groups, flags
+        self.k, self.group_size = k, group_size
+
+    def __len__(self):
+        return self.groups.shape[0]
+
+    def __getitem__(self, b):
+        out = []
+        for g in range(int(self.groups[b])):
+            m = int(self.members[b, g])
+            out.append((int(self.key_tags[b, g]), int(self.key_words[b, g]), self.ids[b, g, :m], self.distances[b, g, :m],
+                        self.ranks[b, g, :m], int(self.totals[b, g])))
+        return out
+
+    def cut(self, b):
+        """True when query b's candidate list was full (flag bit 0): a nearer-than-returned row cannot be missing, but
+        rows beyond the fetch_k-th were not seen."""
+        return bool(int(self.flags[b]) & 1)
+
+    def groups_complete(self, b):
+        """The set of groups of query b is exact with respect to the underlying search: k groups were found, or the
+        candidate list was not cut."""
+        return int(self.groups[b]) == self.k or not self.cut(b)
+
+    def group_complete(self, b, g):
+        """Group g of query b holds its best members: it is full, or the candidate list was not cut."""
+        return int(self.members[b, g]) == self.group_size or not self.cut(b)
 
 
 def set_diverse_stage_bytes(nbytes):
@@ -367,6 +413,35 @@ class _Base:
         self._check(fn(self.h, _ptr(q, f32p), B, q.shape[1], k, fetch_k, lam, int(bool(distinct)), *mid, _ptr(ids, u64p),
                        _ptr(ds, f32p), _ptr(ranks, u32p), _ptr(cnt, u32p)))
         return SearchResults(ids, ds, cnt), ranks
+
+    def _search_grouped(self, fn, q, k, group_size, fetch_k, columns, path, distinct, missing, metadata, *mid):
+        """The grouped searches: GroupedResults.  `columns` is a MetadataColumns; the column of
+        `path` is built on first use, as a "resident" filter builds it, from `metadata` (None: the map of the columns'
+        last sync_rows) — after the limits have been checked, so a call that is refused builds nothing."""
+        q = _rows(q)
+        B, k, gs, fetch_k = q.shape[0], int(k), int(group_size), int(fetch_k)
+        if missing not in GROUP_MISSING:
+            raise InvalidConfig(f'Invalid parameter: missing must be "drop" or "own", got {missing!r}')
+        if not (0 <= k <= 0xFFFFFFFF and 0 <= gs <= 0xFFFFFFFF and 0 <= fetch_k <= 0xFFFFFFFF):
+            raise InvalidConfig("Invalid parameter: k, group_size and fetch_k are unsigned")
+        if fetch_k == 0 or fetch_k > 4096 or k * gs > 4096:  # the engine's refusals, in its order (check_grouped)
+            raise Unsupported("search_grouped: fetch_k must be in 1..4096 and k * group_size at most 4096")
+        if k == 0 or gs == 0:
+            raise InvalidConfig("Invalid parameter: k and group_size must be at least 1")
+        column = columns.group_column(path, metadata)
+        kk, gg = k, gs
+        ids = np.full((B, kk, gg), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        ds = np.full((B, kk, gg), np.inf, np.float32)
+        ranks = np.full((B, kk, gg), 0xFFFFFFFF, np.uint32)
+        members, totals = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.uint32)
+        tags, words = np.zeros((B, kk), np.uint8), np.zeros((B, kk), np.uint64)
+        groups, flags = np.zeros(B, np.uint32), np.zeros(B, np.uint32)
+        table = columns.table
+        self._check(fn(self.h, self.ctx.h, table.h, column, _ptr(q, f32p), B, q.shape[1], k, gs, fetch_k,
+                       int(bool(distinct)), GROUP_MISSING[missing], *mid, _ptr(ids, u64p), _ptr(ds, f32p), _ptr(ranks, u32p),
+                       _ptr(members, u32p), _ptr(totals, u32p), tags.ctypes.data_as(u8p), _ptr(words, u64p), _ptr(groups, u32p),
+                       _ptr(flags, u32p)))
+        return GroupedResults(ids, ds, ranks, members, totals, tags, words, groups, flags, k, gs)
 
     def _quality(self, fn, queries, *args):
         """evaluate_search_quality of the graph and hybrid classes: SearchQuality as a dict, as IVFIndex returns it."""
@@ -653,6 +728,20 @@ class IVFIndex(_Base):
         return self._search_diverse(self.lib.fvh_ivf_search_diverse, queries, k, fetch_k, lam, distinct,
                                     self.n_probe if n_probe is None else n_probe, ap, an)
 
+    def search_grouped(self, queries, k, group_size, fetch_k, columns, path, distinct=True, missing="drop", n_probe=None,
+                       allowed=None, metadata=None):
+        """The k best groups by a metadata field: GroupedResults.  The candidates are exactly what
+        search(fetch_k, n_probe) — search_allowed with `allowed` — returns; on the device each candidate id is looked up
+        in `columns` (a MetadataColumns) and gets the cell of `path` as its key, and walking the candidates in order the
+        first k distinct keys are the groups, each with its first group_size members.  Equality is the filters': 1, 1.0,
+        "1" and True are four keys, 0.0 and -0.0 one; a row without the field, with an array or an object there, or with
+        a NaN has no key and is dropped (missing="drop") or forms a group of its own ("own").  distinct drops every
+        later copy of an id first.  1 <= fetch_k <= 4096, k * group_size <= 4096.  metadata: the map the column of `path`
+        is built from on first use (None: the one `columns` was last synchronised with)."""
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_grouped(self.lib.fvh_ivf_search_grouped, queries, k, group_size, fetch_k, columns, path, distinct, missing,
+                                    metadata, self.n_probe if n_probe is None else n_probe, ap, an)
+
     def mask_builds(self):
         return int(self.lib.fvh_ivf_mask_builds(self.h))
 
@@ -812,6 +901,15 @@ class HNSWIndex(_Base):
         (results, ranks) in pick order; 1 <= k <= fetch_k <= 256, lam in [0, 1]."""
         ap, an, keep = _allowed_args(allowed)
         return self._search_diverse(self.lib.fvh_hnsw_search_diverse, queries, k, fetch_k, lam, distinct, int(ef), ap, an)
+
+    def search_grouped(self, queries, k, group_size, fetch_k, ef, columns, path, distinct=True, missing="drop", allowed=None,
+                       metadata=None):
+        """IVFIndex.search_grouped over the graph: the candidates are exactly what search(fetch_k, ef) — search_allowed
+        with `allowed` — returns.  A graph walk returns at most ef rows, so fetch_k > ef just yields fewer candidates (and
+        a list that was not cut)."""
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_grouped(self.lib.fvh_hnsw_search_grouped, queries, k, group_size, fetch_k, columns, path, distinct, missing,
+                                    metadata, int(ef), ap, an)
 
     def count_within(self, queries, radius, allowed=None):
         """search_radius()'s totals alone (uint32[B]), by a scan that keeps no distances and selects nothing."""
@@ -1306,6 +1404,17 @@ class HybridIndex(_Base):
         ap, an, keep = _allowed_args(allowed)
         return self._search_diverse(self.lib.fvh_hybrid_search_diverse, queries, k, fetch_k, lam, distinct, int(hnsw_ef),
                                     int(ivf_n_probe), int(search_recent), int(search_historical), ap, an, float(now))
+
+    def search_grouped(self, queries, k, group_size, fetch_k, columns, path, distinct=True, missing="drop", now=0.0, hnsw_ef=50,
+                       ivf_n_probe=10, search_recent=True, search_historical=True, allowed=None, metadata=None):
+        """IVFIndex.search_grouped over both parts: the candidates are exactly what search(fetch_k, ...) — search_allowed
+        with `allowed` — returns at these settings, after its auto-migration step.  search() returns a migrated row that
+        still sits in the graph twice; with distinct it takes one seat of its group.  Refused (Unsupported) on a sharded
+        index."""
+        self._refuse_when_sharded("search_grouped")
+        ap, an, keep = _allowed_args(allowed)
+        return self._search_grouped(self.lib.fvh_hybrid_search_grouped, queries, k, group_size, fetch_k, columns, path, distinct, missing,
+                                    metadata, int(hnsw_ef), int(ivf_n_probe), int(search_recent), int(search_historical), ap, an, float(now))
 
     def search_diverse_groups(self, queries, k, fetch_k, allow_sets, group_of_query, lam=0.5, distinct=True, now=0.0, hnsw_ef=50,
                               ivf_n_probe=10, search_recent=True, search_historical=True):

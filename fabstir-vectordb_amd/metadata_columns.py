@@ -271,6 +271,28 @@ class MetaTable:
         self.ctx.check(self.lib.fvdb_meta_eval_dev(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(m), C.byref(u)))
         return a.value, b.value, c.value, int(m.value), int(u.value)
 
+    def keys_of_ids_dev(self, column, ids_dev, n, out_tag_dev, out_key_dev):
+        """Enqueues the key lookup of n ids in device memory (fvdb_group_keys_of_ids_dev): one
+        (tag u8, canon word u64) per id into the two device arrays.  No synchronisation."""
+        self.ctx.check(self.lib.fvdb_group_keys_of_ids_dev(self.h, int(column), ids_dev, int(n), out_tag_dev, out_key_dev))
+
+    def keys_of_ids(self, column, ids):
+        """The same for a host array of ids: (tags u8 [n], words u64 [n])."""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        if ids.size == 0:
+            self.keys_of_ids_dev(column, None, 0, None, None)  # still refuses a column outside the table
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        bufs = []
+        try:
+            bufs.append(self.ctx.upload(ids))
+            bufs.append(self.ctx.alloc(ids.size))
+            bufs.append(self.ctx.alloc(ids.size * 8))
+            self.keys_of_ids_dev(column, bufs[0], ids.size, bufs[1], bufs[2])
+            return self.ctx.download(bufs[1], ids.shape, np.uint8), self.ctx.download(bufs[2], ids.shape, np.uint64)
+        finally:
+            for p in bufs:
+                self.ctx.free(p)
+
 
 def cells_arrays(cells):
     """(tags, vals, elem_tags, elem_vals) numpy arrays of a list of encode_value() results, as fvdb_meta_set_cells takes them."""
@@ -286,6 +308,8 @@ class MetadataColumns:
     """One fvdb_meta for a session: slot i = the i-th row id of `rows` (row id -> name in the metadata map), present
     where the name has an entry.  Columns appear the first time a filter names their path."""
 
+    _strings_by_code = None  # decode_key's list of the dictionary's strings by code, rebuilt when the dictionary has grown
+
     def __init__(self, ctx, rows, metadata):
         self.table = MetaTable(ctx)
         self.ids, self.names, self.slot_of = [], [], {}
@@ -299,6 +323,7 @@ class MetadataColumns:
     def sync_rows(self, rids, rows, metadata):
         """The listed row ids as they are now: new ones get the next slots, known ones keep theirs; presence and the
         cells of every existing column are rewritten."""
+        self.metadata = metadata  # the map the table mirrors: group_column builds a column from it
         slots = []
         first = len(self.ids)
         for rid in rids:
@@ -346,6 +371,33 @@ class MetadataColumns:
                 self._write_cells(path, col, range(len(self.ids)), metadata)
             self.columns[path] = col
         return col
+
+    # -- group keys ------------------------------------------------------------------------------
+    def group_column(self, path, metadata=None):
+        """The column whose cells are the group keys of `path`, built on first use as a "resident" filter builds it, from
+        `metadata` or else from the map of the last sync_rows."""
+        return self.ensure_column(path, self.metadata if metadata is None else metadata)
+
+    def decode_key(self, tag, word):
+        """The Python value of a group key (tag, canon word) as fvdb_group_keys_of_ids_dev writes it: a string by its
+        dictionary code, an int from its two's complement, a float from its bits, a bool, None for NULL.  MISSING (a
+        group made of one candidate without a key) decodes to `metadata_filter._MISSING`."""
+        tag, word = int(tag), int(word)
+        if tag == NULL:
+            return None
+        if tag == BOOL:
+            return bool(word)
+        if tag == INT:
+            return word - (1 << 64) if word >> 63 else word
+        if tag == FLOAT:
+            return struct.unpack("<d", struct.pack("<Q", word))[0]
+        if tag == STRING:
+            if self._strings_by_code is None or len(self._strings_by_code) != len(self.strings):
+                self._strings_by_code = list(self.strings)  # codes are dense and handed out in insertion order
+            return self._strings_by_code[word]
+        if tag == MISSING:
+            return _MISSING
+        raise ValueError(f"tag {tag} is no group key")
 
     # -- evaluation ----------------------------------------------------------------------------------------------------
     def evaluate(self, flt, metadata):

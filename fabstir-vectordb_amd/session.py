@@ -153,6 +153,42 @@ def diverse_options(options, k):
     return fetch_k, float(np.float32(lam)), bool(options.get("distinct", True))
 
 
+def grouped_options(options, k):
+    """The grouped-search options of one request: None when it has no "groupBy", else
+    (path, group_size, fetch_k, missing, fill, distinct).  "groupBy": a dotted path; "groupSize": integer >= 1, absent = 1,
+    with k * groupSize <= 4096 (k counts groups); "fetchK": integer in 1..4096, absent = min(4096, 4 k groupSize);
+    "groupMissing": "drop" (absent) or "own"; "fill": absent = false; "distinct": absent = true.  The combinations that are
+    out of scope are refused here: "mmrLambda", "exact", "threshold", and a filter on the oversampling route."""
+    if options.get("groupBy") is None:
+        return None
+    path = options["groupBy"]
+    if not isinstance(path, str) or not path:
+        raise SessionError(f'Invalid groupBy: {path!r} (expected a dotted path)')
+    for name, why in (("mmrLambda", "a diverse selection picks rows, a grouped one picks groups"),
+                      ("exact", "the candidates of a grouped search are those of the ordinary search of fetchK"),
+                      ("threshold", "a threshold cuts rows, not groups")):
+        if name in options and options[name] not in (None, False):
+            raise SessionError(f'"groupBy" cannot be combined with "{name}": {why}')
+    if options.get("filter") is not None and options.get("filterMode", "oversample") not in ("pushdown", "resident"):
+        raise SessionError(f'a grouped search with a filter needs "filterMode": "pushdown" or "resident", not '
+                           f'{options.get("filterMode", "oversample")!r}: "oversample" keeps what is left of 3 k candidates, '
+                           'while the groups are taken from the fetchK candidates of a search under the allow-set')
+    try:
+        k = int(k)
+        group_size = int(options.get("groupSize", 1))
+        fetch_k = int(options.get("fetchK", min(4096, 4 * k * group_size)))
+    except (TypeError, ValueError) as e:
+        raise SessionError(f"Invalid groupSize or fetchK: {e}") from e
+    if k < 1 or group_size < 1 or k * group_size > 4096:
+        raise SessionError(f"Invalid groupSize: {group_size} with k = {k} (expected k >= 1, groupSize >= 1, k * groupSize <= 4096)")
+    if not 1 <= fetch_k <= 4096:
+        raise SessionError(f"Invalid fetchK: {fetch_k} (expected 1 <= fetchK <= 4096)")
+    missing = options.get("groupMissing", "drop")
+    if missing not in ("drop", "own"):
+        raise SessionError(f'Invalid groupMissing: {missing!r} (expected "drop" or "own")')
+    return path, group_size, fetch_k, missing, bool(options.get("fill", False)), bool(options.get("distinct", True))
+
+
 def radius_of_threshold(threshold):
     """The radius that stands for a score threshold: the largest f32 d >= 0 whose score
     f32(1) / (f32(1) + d) is >= threshold, so that "distance bits <= bits(d)" IS the session's predicate and the device's
@@ -249,6 +285,9 @@ class VectorDbSession:
         if self.vector_dimension is not None and q.size != self.vector_dimension:
             raise SessionError(
                 f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+        grouped = grouped_options(options, k)
+        if grouped is not None:
+            return self._search_grouped([q], k, [options], grouped)[0]
         threshold = np.float32(options.get("threshold", 0.0))
         diverse = diverse_options(options, k)
         if diverse is not None:
@@ -290,7 +329,7 @@ class VectorDbSession:
                 allowed = self._resident_allowed(flt)
                 res = self.index.search_allowed(q.reshape(1, -1), int(k), allowed, now=self.now)  # defaults: ef 50, nprobe 10
             elif flt is not None and mode == "pushdown":
-                allowed = np.fromiter((rid for rid in self._rows if matches(rid)), np.uint64)
+                allowed = self._allowed_by(flt, "pushdown")
                 res = self.index.search_allowed(q.reshape(1, -1), int(k), allowed, now=self.now)  # defaults: ef 50, nprobe 10
             else:
                 res = self.index.search_with_filter(q.reshape(1, -1), int(k), matches, now=self.now)  # defaults: ef 50, nprobe 10
@@ -328,8 +367,7 @@ class VectorDbSession:
                     if key[0] == "resident":
                         allowed = self._resident_allowed(flt)
                     else:
-                        allowed = np.fromiter((rid for rid, name in self._rows.items()
-                                               if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                        allowed = self._allowed_by(flt, "pushdown")
                 group_of_key[key] = len(allow_sets)
                 allow_sets.append(allowed)
             group_of_query.append(group_of_key[key])
@@ -344,6 +382,83 @@ class VectorDbSession:
             raise SessionError(f"Search failed: {e}") from e
         return [self._results_of(res[i], np.float32(o.get("threshold", 0.0)), bool(o.get("includeVectors", False)))
                 for i, o in enumerate(options_list)]
+
+    # -- grouped search: "groupBy" / "groupSize" / "fetchK" / "groupMissing" / "fill"  ------------
+    def _allowed_by(self, flt, mode):
+        """The allow-set of a filter by the route a request chose: "resident" on the device, "pushdown" over the map."""
+        if mode == "resident":
+            return self._resident_allowed(flt)
+        return np.fromiter((rid for rid, name in self._rows.items() if name in self.metadata and flt.matches(self.metadata[name])),
+                           np.uint64)
+
+    def _search_grouped(self, qs, k, options_list, grouped):
+        """search() / search_many() with "groupBy", which every request of the batch shares: k counts groups.  The requests
+        are served filter by filter, one HybridIndex.search_grouped per distinct (mode, filter) — the search of fetchK
+        candidates, their keys looked up in the metadata columns in HBM and the selection all on the device.  With
+        "fill", every group that is not complete although the candidate list was cut is searched again, all of them in ONE
+        HybridIndex.search_allowed_groups call at k = groupSize, each under {"$and": [the request's filter, {path: key}]}
+        evaluated by the route the request chose ("resident" where it chose none); the answer replaces the group's hits
+        and the group is then complete in the sense "what search_allowed returns under that filter at the session's
+        settings".  The set of groups is never searched again: "groupsComplete" reports it."""
+        import json
+        from .metadata_columns import MetadataColumns
+        path, group_size, fetch_k, missing, fill, distinct = grouped
+        k = int(k)
+        cols = getattr(self, "_meta_columns", None)
+        if cols is None:
+            cols = self._meta_columns = MetadataColumns(self.ctx, self._rows, self.metadata)
+        batches = {}  # (mode, canonical filter) -> [request indices]
+        filters = {}
+        for i, options in enumerate(options_list):
+            key = None
+            if options.get("filter") is not None:
+                key = (options["filterMode"], json.dumps(options["filter"], sort_keys=True, separators=(",", ":")))
+                if key not in filters:
+                    try:
+                        filters[key] = MetadataFilter.from_json(options["filter"])
+                    except FilterError as e:
+                        raise SessionError(f"Invalid filter: {e}") from e
+            batches.setdefault(key, []).append(i)
+        out = [None] * len(qs)
+        refill = []  # (request, group position, filter key, key value)
+        try:
+            for key, members in batches.items():
+                allowed = None if key is None else self._allowed_by(filters[key], key[0])
+                res = self.index.search_grouped(np.stack([qs[i] for i in members]), k, group_size, fetch_k, cols, path,
+                                                distinct=distinct, missing=missing, now=self.now, allowed=allowed,
+                                                metadata=self.metadata)
+                for b, i in enumerate(members):
+                    include = bool(options_list[i].get("includeVectors", False))
+                    groups = []
+                    for g, (tag, word, ids, ds, _, total) in enumerate(res[b]):
+                        own = tag == 0  # FVDB_META_MISSING: one candidate without a key, a group of its own
+                        entry = {"key": None if own else cols.decode_key(tag, word),
+                                 "hits": self._results_of((ids, ds), np.float32(0.0), include), "total": total,
+                                 "complete": own or res.group_complete(b, g)}
+                        if own:
+                            entry["missing"] = True
+                        elif fill and not entry["complete"]:
+                            refill.append((i, g, key, entry["key"]))
+                        groups.append(entry)
+                    out[i] = {"groups": groups, "groupsComplete": res.groups_complete(b)}
+            if refill:
+                from .metadata_filter import MetadataFilter as F
+                sets = []
+                for i, g, key, value in refill:
+                    leaf = F("equals", field=path, value=value)
+                    flt = leaf if key is None else F("and", filters=[filters[key], leaf])
+                    sets.append(self._allowed_by(flt, "resident" if key is None else key[0]))
+                res = self.index.search_allowed_groups(np.stack([qs[i] for i, _, _, _ in refill]), group_size, sets,
+                                                       np.arange(len(refill), dtype=np.uint32), now=self.now)
+                for j, (i, g, _, _) in enumerate(refill):
+                    entry = out[i]["groups"][g]
+                    entry["hits"] = self._results_of(res[j], np.float32(0.0), bool(options_list[i].get("includeVectors", False)))
+                    entry["complete"] = True
+        except SessionError:
+            raise
+        except Exception as e:
+            raise SessionError(f"Search failed: {e}") from e
+        return out
 
     # -- search_within: every row whose score clears a threshold (no counterpart in the reference) -------------------
     def search_within(self, query_vector, threshold, options=None):
@@ -377,8 +492,7 @@ class VectorDbSession:
             if mode == "resident":
                 allowed = self._resident_allowed(flt)
             else:
-                allowed = np.fromiter((rid for rid, name in self._rows.items()
-                                       if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                allowed = self._allowed_by(flt, "pushdown")
         elif options.get("filterMode") == "oversample":
             raise SessionError('Invalid filterMode for search_within: "oversample" applies to a search by count')
         if radius is None:  # threshold > 1: no score reaches it
@@ -479,6 +593,19 @@ class VectorDbSession:
         options_list = [{} for _ in range(n)] if options_list is None else [o or {} for o in options_list]
         if len(options_list) != n:
             raise SessionError(f"search_many: {n} queries but {len(options_list)} option sets")
+        # "groupBy" (DESIGN.md section 9v): all requests or none, and the same grouping; each request keeps its own filter
+        grouped = [grouped_options(o, k) for o in options_list]
+        if any(g is not None for g in grouped):
+            if any(g != grouped[0] for g in grouped):
+                raise SessionError('search_many: "groupBy" and its options must have the same values in every request of a batch')
+            qs = []
+            for qv in query_vectors:
+                q = js_array_to_vec_f32(qv)
+                if self.vector_dimension is not None and q.size != self.vector_dimension:
+                    raise SessionError(
+                        f"Query vector dimension mismatch: expected {self.vector_dimension} dimensions, got {q.size}")
+                qs.append(q)
+            return self._search_grouped(qs, k, options_list, grouped[0])
         # the diverse options ("mmrLambda", "fetchK", "distinct"): all requests or none, and the same values
         diverse = [diverse_options(o, k) for o in options_list]
         if any(d is not None for d in diverse):
@@ -517,8 +644,7 @@ class VectorDbSession:
                     if key[0] == "resident":
                         allowed = self._resident_allowed(flt)
                     else:
-                        allowed = np.fromiter((rid for rid, name in self._rows.items()
-                                               if name in self.metadata and flt.matches(self.metadata[name])), np.uint64)
+                        allowed = self._allowed_by(flt, "pushdown")
                 group_of_key[key] = len(allow_sets)
                 allow_sets.append(allowed)
             group_of_query.append(group_of_key[key])

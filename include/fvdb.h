@@ -845,6 +845,58 @@ int fvdb_ivf_get_rows_dev_strided(fvdb_ivf* ivf, fvdb_ctx* on, const uint32_t* c
  * (NULL = the store's); no synchronisation.  Reads only. */
 int fvdb_store_get_rows_dev(fvdb_store* store, fvdb_ctx* on, const uint32_t* rows_dev, uint64_t n, float* out_rows_dev,
                             uint32_t out_stride);
+/* ---- grouped selection --------------------------------------------
+ * "The k best groups by a metadata field": of the candidates a search of fetch_k returned for a query, the first k
+ * groups by a key, each with its first group_size members.
+ *
+ * Key of a candidate, under a metadata table and one of its columns.  The key is NONE when the id is FVDB_NO_ID, the id
+ * is in no slot of the table, its slot is not present, its cell is MISSING, ARRAY or COMPLEX, or its cell is a FLOAT NaN.
+ * Otherwise it is (tag, canon): canon is the cell's word as stored, except that a FLOAT -0.0 is folded onto 0.0 and a NULL
+ * is 0.  Two candidates are in the same group iff their tags are equal and their canon words are equal (the equality of
+ * the metadata columns: 1, 1.0, "1" and true are four groups, 0.0 and -0.0 are one).
+ *
+ * Selection, per query, over candidates c = 0 .. n-1 (n = min(counts[b], fetch_k)) IN THE ORDER GIVEN; only positions
+ * are compared, never distances:
+ *   1. distinct: c is dropped when some c' < c has the same id;
+ *   2. a kept candidate whose key is none is dropped (missing = FVDB_GROUP_MISSING_DROP) or forms a group of its own
+ *      (FVDB_GROUP_MISSING_OWN);
+ *   3. the groups are ordered by the position of their first member;
+ *   4. the members of a group are its kept candidates in position order;
+ *   5. output is the first k groups, each with its first group_size members.
+ * Outputs, all device memory: out_ids / out_dist / out_rank [B][k][group_size] (the id, the distance as given, the
+ * candidate position c), out_members[B][k] (members written), out_group_total[B][k] (kept candidates of the n that carry
+ * the key, not capped by group_size), out_key_tag / out_key_val [B][k] (the group's tag and canon word; a group made by
+ * FVDB_GROUP_MISSING_OWN has tag FVDB_META_MISSING and word 0), out_groups[B] (groups written), out_flags[B] (bit 0 set
+ * iff n == fetch_k: the candidate list may have been cut).  Tails are FVDB_NO_ID / +inf / FVDB_NO_ROW / 0.
+ *
+ * What the flags let a caller conclude.  Walking candidates in ascending distance, the first k distinct keys ARE the k
+ * best groups by best member.  So the set of groups is exact with respect to the underlying search iff
+ * out_groups[b] == k or bit 0 is clear, and a group's members are its best members iff out_members == group_size or bit 0
+ * is clear.  Nothing else is claimed.
+ *
+ * fvdb_group_keys_of_ids_dev writes one (tag, canon) per id, a none key as (FVDB_META_MISSING, 0); enqueued on the
+ * stream of the table's context, no synchronisation.  (Its name carries the feature's prefix, not fvdb_meta_: the set of
+ * fvdb_meta_ entry points is the table's own.)  The lookup goes through an open-addressing index in HBM that the table
+ * owns: a power of two of cells, at least twice the slots, linear probing; built by a kernel from the slots' ids with a
+ * 64-bit compare-and-swap on the id word and an atomic min on the slot word, so of the slots that carry one id the LOWEST
+ * answers, whatever the scheduling.  The empty id word is FVDB_NO_ID, whose key is none by definition: such a slot is
+ * never entered, and every other id, 0 among them, is an ordinary id.  The index is rebuilt lazily, by the first lookup
+ * after fvdb_meta_set_rows has run; presence and cells are read at lookup time, so fvdb_meta_set_present and
+ * fvdb_meta_set_cells need no rebuild.  fvdb_meta_info's hbm_bytes counts it.  A column outside the table is
+ * FVDB_E_INVALID before anything is enqueued; n >= 2^31 is FVDB_E_UNSUPPORTED; n == 0 is FVDB_OK.  Locks the table.
+ *
+ * fvdb_group_select_dev takes key_tag_dev / key_val_dev [B][fetch_k] as that call writes them (a tag other than NULL,
+ * BOOL, INT, FLOAT or STRING, and any candidate whose id is FVDB_NO_ID, is a none key).  Enqueued on ctx's stream, no
+ * synchronisation; two runs over the same inputs write identical bytes.  fetch_k == 0 or > FVDB_MAX_K_WIDE, or
+ * k * group_size > FVDB_MAX_K_WIDE: FVDB_E_UNSUPPORTED; k == 0, group_size == 0, an unknown `missing`, a NULL buffer with
+ * B > 0: FVDB_E_INVALID; B == 0: FVDB_OK, nothing enqueued. */
+#define FVDB_GROUP_MISSING_DROP 0
+#define FVDB_GROUP_MISSING_OWN 1
+int fvdb_group_select_dev(fvdb_ctx* ctx, const uint64_t* ids_dev, const float* dist_dev, const uint32_t* counts_dev,
+                          const uint8_t* key_tag_dev, const uint64_t* key_val_dev, uint32_t B, uint32_t fetch_k, uint32_t k,
+                          uint32_t group_size, int distinct, int missing, uint64_t* out_ids_dev, float* out_dist_dev,
+                          uint32_t* out_rank_dev, uint32_t* out_members_dev, uint32_t* out_group_total_dev, uint8_t* out_key_tag_dev,
+                          uint64_t* out_key_val_dev, uint32_t* out_groups_dev, uint32_t* out_flags_dev);
 /* The comparison of fvdb_ivf_search_quality_dev on two id blocks the caller holds in HBM (B x k ids with their hit
  * counts; entries at or beyond a count are not read): per query matches, recall and precision by the formulas stated
  * there — an id the result holds twice counts twice — to out_recall_dev[B] / out_precision_dev[B], enqueued on ctx's
@@ -1035,6 +1087,13 @@ int fvdb_meta_eval_fetch(fvdb_meta* t, uint64_t* ids, uint32_t* unknown_slots, u
  * without the ids visiting the host.  Valid until the table's next evaluation, growth or destruction. */
 int fvdb_meta_eval_dev(fvdb_meta* t, const uint64_t** ids_dev, const uint32_t** unknown_slots_dev, const uint32_t** unknown_ranks_dev,
                        uint64_t* out_matches, uint64_t* out_unknown);
+/* The keys of n candidate ids under one column, for fvdb_group_select_dev ("grouped selection" above states the key
+ * rule, the id index and the refusals). */
+int fvdb_group_keys_of_ids_dev(fvdb_meta* t, uint32_t column, const uint64_t* ids_dev, uint64_t n, uint8_t* out_tag_dev,
+                               uint64_t* out_key_dev);
+/* The context whose stream carries that lookup (the one the table was made on; NULL for a NULL table): a caller that
+ * runs the selection on another stream waits for this one first. */
+fvdb_ctx* fvdb_group_keys_ctx(fvdb_meta* t);
 
 #ifdef __cplusplus
 }
