@@ -67,6 +67,15 @@ class MetaInfo(C.Structure):
     _fields_ = [(n, u64) for n in ("slots", "present", "columns", "live_elements", "dead_elements", "hbm_bytes")]
 
 
+class PQInfo(C.Structure):
+    """fvdb_pq_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("d", "m", "ksub", "ksub_actual", "trained", "dsub", "dsub_last", "m_padded", "table_stride",
+                                   "queries_per_workgroup", "lds_bytes", "lds_limit", "min_slice_rows", "max_d", "max_sub_dims",
+                                   "reserved")]
+
+
+PQ_NO_REFINE = -1  # FVDB_PQ_NO_REFINE
+
 u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
@@ -255,6 +264,26 @@ SIGNATURES = {
     "fvdb_meta_eval": (i32, [vp, u32p, u32, u32p, u64p, u32, u64p, u64p]),
     "fvdb_meta_eval_fetch": (i32, [vp, u64p, u32p, u32p]),
     "fvdb_meta_eval_dev": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u64p, u64p]),
+    # product quantization: the quantizer, the codes-only index, ADC and refined search
+    "fvdb_pq_create": (i32, [vp, u32, u32, u32, C.POINTER(vp)]),
+    "fvdb_pq_destroy": (None, [vp]),
+    "fvdb_pq_info": (i32, [vp, C.POINTER(PQInfo)]),
+    "fvdb_pq_set_codebooks": (i32, [vp, f32p, u32]),
+    "fvdb_pq_get_codebooks": (i32, [vp, f32p]),
+    "fvdb_pq_train": (i32, [vp, f32p, u64, u32, u32p, u64]),
+    "fvdb_pq_encode": (i32, [vp, f32p, u64, u8p]),
+    "fvdb_pq_decode": (i32, [vp, u8p, u64, f32p]),
+    "fvdb_pq_encode_dev": (i32, [vp, vp, vp, u64, vp]),
+    "fvdb_pq_decode_dev": (i32, [vp, vp, vp, u64, vp]),
+    "fvdb_pq_index_create": (i32, [vp, i32, C.POINTER(vp)]),
+    "fvdb_pq_index_destroy": (None, [vp]),
+    "fvdb_pq_index_add": (i32, [vp, u64p, f32p, u64]),
+    "fvdb_pq_index_set_deleted": (i32, [vp, u64p, u64, i32]),
+    "fvdb_pq_index_rows": (u64, [vp]),
+    "fvdb_pq_index_live": (u64, [vp]),
+    "fvdb_pq_index_bytes": (u64, [vp]),
+    "fvdb_pq_index_search": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvdb_pq_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp]),
 }
 
 _lib = None

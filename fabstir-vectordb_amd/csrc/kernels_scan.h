@@ -451,7 +451,7 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const uint64_t* __restr
 // -----------------------------------------------------------------------------------------
 // list_off (optional): lists with no blocks on this device are not planned at all — on a rank of a W-rank job that is
 // (W-1)/W of the probes of the W*B queries it scans
-__global__ void plan_count_kernel(const uint32_t* __restrict__ probes, uint32_t n, uint32_t* __restrict__ cnt,
+static __global__ void plan_count_kernel(const uint32_t* __restrict__ probes, uint32_t n, uint32_t* __restrict__ cnt,
                                   const uint32_t* __restrict__ list_off = nullptr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
@@ -461,7 +461,7 @@ __global__ void plan_count_kernel(const uint32_t* __restrict__ probes, uint32_t 
 }
 
 // single block of 1024 threads: exclusive scans over lists
-__global__ __launch_bounds__(1024) void plan_scan_kernel(const uint32_t* __restrict__ cnt,
+static __global__ __launch_bounds__(1024) void plan_scan_kernel(const uint32_t* __restrict__ cnt,
                                                          const uint32_t* __restrict__ list_off,
                                                          const uint32_t* __restrict__ list_len, uint32_t nlist,
                                                          uint32_t segb, uint32_t Q, uint32_t* __restrict__ entry_off,
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(const uint32_t* __restr
   }
 }
 
-__global__ void plan_fill_kernel(const uint32_t* __restrict__ probes, uint32_t n, uint32_t nprobe,
+static __global__ void plan_fill_kernel(const uint32_t* __restrict__ probes, uint32_t n, uint32_t nprobe,
                                  const uint32_t* __restrict__ entry_off, uint32_t* __restrict__ fill,
                                  uint2* __restrict__ entries, const uint32_t* __restrict__ list_off = nullptr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -548,7 +548,7 @@ __global__ void plan_fill_kernel(const uint32_t* __restrict__ probes, uint32_t n
 }
 
 // Plan for "every query scans list 0" (coarse ranking over the centroid table, flat scan).
-__global__ void plan_all_kernel(uint32_t B, uint32_t nblk, uint32_t segb, uint32_t Q, uint32_t* __restrict__ entry_off,
+static __global__ void plan_all_kernel(uint32_t B, uint32_t nblk, uint32_t segb, uint32_t Q, uint32_t* __restrict__ entry_off,
                                 uint32_t* __restrict__ item_off, uint2* __restrict__ entries,
                                 uint32_t* __restrict__ n_items, uint32_t* __restrict__ head) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -567,7 +567,7 @@ __global__ void plan_all_kernel(uint32_t B, uint32_t nblk, uint32_t segb, uint32
 
 // probes for "probe every list in id order" (exhaustive search / nprobe >= nlist is handled by
 // the coarse stage itself; this one serves fvdb_ivf_search_all).
-__global__ void probes_all_kernel(uint32_t B, uint32_t nlist, uint32_t* __restrict__ probes) {
+static __global__ void probes_all_kernel(uint32_t B, uint32_t nlist, uint32_t* __restrict__ probes) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * nlist) probes[i] = i % nlist;
 }

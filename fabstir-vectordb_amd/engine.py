@@ -577,6 +577,152 @@ class RowStore:
         return out
 
 
+class ProductQuantizer:
+    """ProductQuantizer (src/core/vector_ops.rs:390-578) on the device (fvdb_pq): d dims in
+    num_subspaces subspaces (the last one takes the remainder), num_centroids <= 256 centroids each, one byte a code."""
+
+    def __init__(self, ctx, d, num_subspaces, num_centroids):
+        self.ctx, self.lib, self.d, self.m, self.ksub = ctx, ctx.lib, int(d), int(num_subspaces), int(num_centroids)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_pq_create(ctx.h, self.d, self.m, self.ksub, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_pq_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """fvdb_pq_info_t as a dict: the subspace dims, ksub_actual, and what a search will use (table_stride,
+        queries_per_workgroup, lds_bytes of lds_limit, min_slice_rows)."""
+        v = _capi.PQInfo()
+        self.ctx.check(self.lib.fvdb_pq_info(self.h, C.byref(v)))
+        return {n: int(getattr(v, n)) for n, _ in v._fields_ if n != "reserved"}
+
+    def _rows(self, rows):
+        r = _f32(rows)
+        if r.ndim == 1:
+            r = r.reshape(1, -1)
+        if r.ndim != 2 or r.shape[1] != self.d:
+            raise DimensionMismatch(f"Dimension mismatch: expected {self.d}, got {r.shape[-1]}")
+        return r
+
+    def _book_floats(self):
+        return self.info()["ksub_actual"] * self.d
+
+    def train(self, rows, iterations, init_rows=None, seed=0):
+        """`iterations` Lloyd steps from the training rows init_rows[m][min(num_centroids, n)] names (None: drawn from
+        SplitMix64 on seed, distinct within a subspace); empty centroids are refilled by the rule of include/fvdb.h."""
+        r = self._rows(rows)
+        ip = None
+        if init_rows is not None:
+            init = np.ascontiguousarray(init_rows, np.uint32)
+            if init.shape != (self.m, min(self.ksub, r.shape[0])):
+                raise InvalidConfig(f"init_rows must be [{self.m}][{min(self.ksub, r.shape[0])}], got {init.shape}")
+            ip = _ptr(init, u32p)
+        self.ctx.check(self.lib.fvdb_pq_train(self.h, _ptr(r, f32p), r.shape[0], int(iterations), ip, int(seed)))
+
+    def set_codebooks(self, books, ksub_actual):
+        """books: the flat [m][ksub_actual][dims of j] f32 block."""
+        b = _f32(books).reshape(-1)
+        if b.size != int(ksub_actual) * self.d:
+            raise InvalidConfig(f"codebooks must hold {int(ksub_actual) * self.d} floats, got {b.size}")
+        self.ctx.check(self.lib.fvdb_pq_set_codebooks(self.h, _ptr(b, f32p), int(ksub_actual)))
+
+    def codebooks(self):
+        """The flat [m][ksub_actual][dims of j] f32 block (subspace j starts at ksub_actual * j * (d // m))."""
+        if not self.info()["trained"]:
+            raise NotTrained("Index not trained")
+        out = np.empty(self._book_floats(), np.float32)
+        self.ctx.check(self.lib.fvdb_pq_get_codebooks(self.h, _ptr(out, f32p)))
+        return out
+
+    def encode(self, rows):
+        r = self._rows(rows)
+        out = np.empty((r.shape[0], self.m), np.uint8)
+        self.ctx.check(self.lib.fvdb_pq_encode(self.h, _ptr(r, f32p), r.shape[0], _ptr(out, _capi.u8p)))
+        return out
+
+    def decode(self, codes):
+        c = np.ascontiguousarray(codes, np.uint8)
+        if c.ndim == 1:
+            c = c.reshape(1, -1)
+        if c.ndim != 2 or c.shape[1] != self.m:
+            raise DimensionMismatch(f"Dimension mismatch: expected {self.m} codes a row, got {c.shape[-1]}")
+        out = np.empty((c.shape[0], self.d), np.float32)
+        self.ctx.check(self.lib.fvdb_pq_decode(self.h, _ptr(c, _capi.u8p), c.shape[0], _ptr(out, f32p)))
+        return out
+
+
+class PQIndex:
+    """A codes-only index over a trained ProductQuantizer (fvdb_pq_index): ADC search over one-byte codes, and with
+    refine_rows "f32" / "f16" the rows too, for a re-scored (refined) search."""
+
+    def __init__(self, ctx, pq, refine_rows=None):
+        self.ctx, self.lib, self.pq, self.refine_rows = ctx, ctx.lib, pq, refine_rows
+        code = _capi.PQ_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_pq_index_create(pq.h, code, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_pq_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, ids, rows):
+        r = self.pq._rows(rows)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_pq_index_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_pq_index_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_pq_index_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_pq_index_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_pq_index_bytes(self.h))
+
+    def search(self, queries, k, fetch_k=None, allowed=None):
+        """The k nearest by ADC distance (ties to the earlier row); with fetch_k, the fetch_k nearest by ADC re-scored
+        against their stored rows and the k nearest of those.  allowed: only rows with these ids are candidates."""
+        from .index import SearchResults
+        if fetch_k is not None and self.refine_rows is None:
+            raise InvalidConfig("fetch_k needs an index created with refine_rows")
+        q = self.pq._rows(queries)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        dist = np.full((B, max(k, 0)), np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            al = al if al.size else np.zeros(1, np.uint64)[:0]
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_pq_index_search(self.h, _ptr(q, f32p), B, k, int(fetch_k or 0), ap, na, _ptr(ids, u64p),
+                                                     _ptr(dist, f32p), _ptr(counts, u32p)))
+        return SearchResults(ids, dist, counts)
+
+
 def merge_keys_dev(ctx, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev):
     ctx.check(ctx.lib.fvdb_merge_keys_dev(ctx.h, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev))
 

@@ -1095,6 +1095,100 @@ int fvdb_group_keys_of_ids_dev(fvdb_meta* t, uint32_t column, const uint64_t* id
  * runs the selection on another stream waits for this one first. */
 fvdb_ctx* fvdb_group_keys_ctx(fvdb_meta* t);
 
+/* ---- product quantization -----------------------------------------
+ * ProductQuantizer (src/core/vector_ops.rs:390-578: train, encode, decode) and a search over its codes.
+ *
+ * Geometry.  d dims, m = num_subspaces, ksub = num_centroids, 1 <= m <= d (m > d: FVDB_E_INVALID), 1 <= ksub <= 256
+ * (ksub > 256: FVDB_E_UNSUPPORTED, the reference's `closest as u8` would wrap).  dsub = d / m in integers; subspace j
+ * covers dims [j dsub, (j + 1) dsub), the last one runs to d (d = 10, m = 3: 3, 3, 4).  A codebook block is
+ * [m][ksub_actual][dims of j] f32, ksub_actual = min(ksub, training rows), the same in every subspace.  Limits of the
+ * kernels (FVDB_E_UNSUPPORTED at create, readable from fvdb_pq_info): d <= 2048, at most 128 dims in a subspace.
+ *
+ * The fold, wherever a distance is formed: t = a_i - b_i; s = s + t * t, i ascending, f32, multiply and add separate,
+ * sqrtf at the end (euclidean_distance_scalar).
+ *
+ * encode (:525-561): per subspace the centroid with the smallest distance, compared AFTER the root (two sums the root
+ * merges tie), ties to the lowest index, the code is that index as a byte; out_codes is [n][m].  A NaN or Inf in the
+ * rows is FVDB_E_NONFINITE before anything is written (host form; the _dev forms read rows already in HBM and do not
+ * check them, as fvdb_store's rows are not checked twice).
+ * decode (:563-577): the codes' centroids concatenated, d floats per row, bit copies.  A code >= ksub_actual is
+ * FVDB_E_INVALID (host form; the _dev form reads the last centroid instead).
+ * train (:405-444, :467-523): `iterations` Lloyd steps.  Assign: every training sub-vector to its nearest centroid by the
+ * encode rule.  Update: per centroid the sum of its members in data order from 0.0f, divided by (float)count; an empty
+ * centroid becomes a bit copy of one training sub-vector.  The reference draws the initial and the refill rows from
+ * thread_rng (unpinned); here init_rows[m][ksub_actual] names the initial training rows (an index >= n: FVDB_E_INVALID),
+ * and the refill row of (iteration it, subspace j, centroid c) is sm64(seed + ((it m + j) 256 + c)) mod n, where
+ * sm64(x) is one output of standard SplitMix64 from state x: z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  init_rows == NULL: the initial rows are
+ * drawn from the SplitMix64 stream of state `seed` (draw t of the call is sm64(seed + t 0x9E3779B97F4A7C15)), each
+ * reduced mod n, subspace after subspace; a row already drawn for the subspace is skipped and the next draw taken.
+ * iterations == 0 leaves the initial picks.  n == 0: FVDB_E_INSUFFICIENT.
+ * Every call but create / info / set_codebooks / train on an untrained quantizer is FVDB_E_NOT_TRAINED; rows of another
+ * dimension cannot be told apart through a pointer, so the Python surface raises FVDB_E_DIM's exception itself.
+ *
+ * ADC search.  For query q the table is T[j][c] = the fold over subspace j's dims of q against centroid c, WITHOUT the
+ * root.  A row with codes c_0 .. c_{m-1} has adc = sqrtf(((T[0][c_0] + T[1][c_1]) + ...) + T[m-1][c_{m-1}]), f32 adds,
+ * j ascending — in exact arithmetic the L2 distance from q to decode(codes).  A candidate's key is
+ * (bits(adc) << 32) | row, row = the append position; the result is the min(k, live rows) smallest keys, ascending, so
+ * ties go to the earlier row.  1 <= k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED.
+ * Refined search (fetch_k != 0; the index was created with refine rows, else FVDB_E_INVALID; k <= fetch_k, else
+ * FVDB_E_INVALID; fetch_k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED): the candidates are the ADC search of fetch_k, each
+ * is re-scored against its stored row with the fold above (an fp16 row widened exactly first), and the k smallest
+ * (bits(distance) << 32) | row are returned: the distances are the reference's own for those rows.
+ * Outputs: out_ids / out_dist are B x k (unused tail = FVDB_NO_ID / +inf), out_counts[B].  An empty index and
+ * k > live rows are not errors.  A quantizer whose tables do not fit the device's LDS for one query
+ * (m x table_stride x 4 bytes) is FVDB_E_UNSUPPORTED at search. */
+typedef struct fvdb_pq fvdb_pq;
+typedef struct fvdb_pq_index fvdb_pq_index;
+typedef struct fvdb_pq_info_t {
+  uint32_t d, m, ksub, ksub_actual;      /* ksub_actual: 0 until trained */
+  uint32_t trained, dsub, dsub_last;     /* dims of subspaces 0 .. m-2, and of the last one */
+  uint32_t m_padded;                     /* m rounded up to 16: the codes of a row in the index */
+  uint32_t table_stride;                 /* floats of one table row in LDS: ksub_actual, or + 1 (FVDB_PQ_TABLE_PAD=1) */
+  uint32_t queries_per_workgroup;        /* QT: the largest of 4, 2, 1 whose tables fit lds_limit; 0: none fits */
+  uint32_t lds_bytes;                    /* QT x m x table_stride x 4 */
+  uint32_t lds_limit;                    /* the device's LDS bytes per workgroup */
+  uint32_t min_slice_rows;               /* a scan slice is at least this many rows (the last one may be shorter) */
+  uint32_t max_d, max_sub_dims;          /* the limits above */
+  uint32_t reserved;
+} fvdb_pq_info_t;
+int fvdb_pq_create(fvdb_ctx* ctx, uint32_t d, uint32_t m, uint32_t ksub, fvdb_pq** out);
+void fvdb_pq_destroy(fvdb_pq* pq);
+int fvdb_pq_info(fvdb_pq* pq, fvdb_pq_info_t* out);
+/* books: [m][ksub_actual][dims of j] host floats, 1 <= ksub_actual <= ksub (else FVDB_E_INVALID).  Marks the
+ * quantizer trained.  Setting or training a quantizer invalidates the indexes made from it (their calls then return
+ * FVDB_E_INVALID). */
+int fvdb_pq_set_codebooks(fvdb_pq* pq, const float* books, uint32_t ksub_actual);
+int fvdb_pq_get_codebooks(fvdb_pq* pq, float* out_books);
+int fvdb_pq_train(fvdb_pq* pq, const float* rows, uint64_t n, uint32_t iterations, const uint32_t* init_rows, uint64_t seed);
+int fvdb_pq_encode(fvdb_pq* pq, const float* rows, uint64_t n, uint8_t* out_codes);
+int fvdb_pq_decode(fvdb_pq* pq, const uint8_t* codes, uint64_t n, float* out_rows);
+/* device pointers, enqueued on `on`'s stream (NULL: the quantizer's context); nothing is synchronised */
+int fvdb_pq_encode_dev(fvdb_pq* pq, fvdb_ctx* on, const float* rows_dev, uint64_t n, uint8_t* out_codes_dev);
+int fvdb_pq_decode_dev(fvdb_pq* pq, fvdb_ctx* on, const uint8_t* codes_dev, uint64_t n, float* out_rows_dev);
+/* A codes-only index.  refine_dtype: FVDB_PQ_NO_REFINE, or FVDB_F32 / FVDB_F16 to keep the rows too, in an fvdb_store the
+ * index owns (store row = code row).  add encodes on the device and appends codes, ids and a live flag; an id already
+ * present (or twice in the call) is FVDB_E_DUPLICATE, a NaN / Inf FVDB_E_NONFINITE, both before anything is written.
+ * set_deleted: flag != 0 deletes, 0 restores; an unknown id is FVDB_E_NOT_FOUND before anything is written. */
+#define FVDB_PQ_NO_REFINE (-1)
+int fvdb_pq_index_create(fvdb_pq* pq, int refine_dtype, fvdb_pq_index** out);
+void fvdb_pq_index_destroy(fvdb_pq_index* ix);
+int fvdb_pq_index_add(fvdb_pq_index* ix, const uint64_t* ids, const float* rows, uint64_t n);
+int fvdb_pq_index_set_deleted(fvdb_pq_index* ix, const uint64_t* ids, uint64_t n, int flag);
+uint64_t fvdb_pq_index_rows(fvdb_pq_index* ix);
+uint64_t fvdb_pq_index_live(fvdb_pq_index* ix);
+uint64_t fvdb_pq_index_bytes(fvdb_pq_index* ix); /* HBM held by the rows present: code blocks, ids, flags, refine rows */
+/* Host arrays.  allowed_ids (NULL: every live row): only live rows whose id is listed are candidates; ids the index
+ * does not hold are ignored.  The allow-set becomes the per-row "dead" words the scan reads.  Synchronises. */
+int fvdb_pq_index_search(fvdb_pq_index* ix, const float* q, uint32_t B, uint32_t k, uint32_t fetch_k, const uint64_t* allowed_ids,
+                         uint64_t n_allowed, uint64_t* out_ids, float* out_dist, uint32_t* out_counts);
+/* Device pointers, enqueued on `on`'s stream (NULL: the quantizer's context) with the scratch of `slot` (0..15): calls
+ * in different slots may be in flight at once, calls in one slot take turns in stream order.  dead_dev: NULL (the
+ * index's own flags), or [rows] words, non-zero = not a candidate.  Nothing is synchronised. */
+int fvdb_pq_index_search_dev_slot(fvdb_pq_index* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                  uint32_t fetch_k, const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
