@@ -21,6 +21,7 @@
 #pragma once
 #include "common.h"
 #include "kernels_flat.h"
+#include "kernels_refine.h"
 #include "score_rows.h"
 #include "wave_ops.h"
 
@@ -353,19 +354,9 @@ __global__ void pq_map_ids_kernel(const uint32_t* __restrict__ nodes, const uint
 }
 
 // ---- refine ----------------------------------------------------------------------------------------------------------
-struct PqRefineArgs {
-  const void* rows;          // the index's store: [row][dpad] of RT
-  const float* queries;      // [B][dpad], zero beyond d
-  const uint32_t* cand;      // [B][fk] rows, the ADC search's answer
-  const uint32_t* cand_cnt;  // [B]
-  const uint64_t* ids;       // [rows]
-  uint32_t dpad, B, fk, k;
-  uint64_t* out_ids;
-  float* out_dist;
-  uint32_t* out_counts;
-};
+// one wave per query over the ADC candidates (kernels_refine.h, shared with the SQ8 index)
+using PqRefineArgs = RefineArgs;
 
-// one wave per query, lane = candidate, 64 a pass (score_rows_wave: rounds of up to 16 rows through the shared scorer)
 template <int KR, typename RT>
 __global__ __launch_bounds__(256) void pq_refine_kernel(const PqRefineArgs a) {
   __shared__ __attribute__((aligned(16))) float s_tile[4][kScoreTileFloats];
@@ -373,38 +364,7 @@ __global__ __launch_bounds__(256) void pq_refine_kernel(const PqRefineArgs a) {
   const uint32_t w = threadIdx.x >> 6;
   const uint32_t q = blockIdx.x * 4 + w;
   if (q >= a.B) return;
-  const uint32_t cnt = min(rfl(a.cand_cnt[q]), a.fk);
-  WaveTopK<KR> tk;
-  tk.init();
-  for (uint32_t base = 0; base < cnt; base += 64) {
-    const uint32_t nn = min(64u, cnt - base);
-    const bool mine = (uint32_t)lane < nn;
-    const uint32_t row = mine ? a.cand[(size_t)q * a.fk + base + lane] : 0u;
-    const float dist = score_rows_wave((const RT*)a.rows, a.dpad, a.queries + (size_t)q * a.dpad, row, nn, s_tile[w], lane);
-    const uint32_t chi = mine ? __float_as_uint(dist) : kInf32;
-    if (base == 0) {
-      uint32_t shi = chi, slo = mine ? row : kInf32;
-      wave_sort64(shi, slo, lane);
-      tk.hi[0] = shi;
-      tk.lo[0] = slo;
-    } else {
-      uint32_t th, tl;
-      tk.kth(a.k, th, tl);
-      offer<KR>(tk, a.k, chi, row, th, tl, lane);
-    }
-  }
-  uint32_t count = 0;
-#pragma unroll
-  for (int rr = 0; rr < KR; ++rr) {
-    const uint32_t e = rr * 64 + lane;
-    const bool have = e < a.k && tk.hi[rr] != kInf32;
-    count += __popcll(__ballot(have));
-    if (e < a.k) {
-      a.out_ids[(size_t)q * a.k + e] = have ? a.ids[tk.lo[rr]] : ~0ull;
-      a.out_dist[(size_t)q * a.k + e] = have ? __uint_as_float(tk.hi[rr]) : __uint_as_float(0x7F800000u);
-    }
-  }
-  if (lane == 0) a.out_counts[q] = count;
+  refine_wave<KR, RT>(a, q, s_tile[w], lane);
 }
 
 // ---- small helpers ---------------------------------------------------------------------------------------------------

@@ -723,6 +723,110 @@ class PQIndex:
         return SearchResults(ids, dist, counts)
 
 
+def _rows_2d(rows, d=None):
+    r = _f32(rows)
+    if r.ndim == 1:
+        r = r.reshape(1, -1)
+    if r.ndim != 2 or (d is not None and r.shape[1] != d):
+        raise DimensionMismatch(f"Dimension mismatch: expected {d}, got {r.shape[-1]}")
+    return r
+
+
+def scalar_quantize_u8(ctx, rows):
+    """scalar_quantize_u8 (src/core/vector_ops.rs:369-387) on the device, row by row: (codes [n][d] u8, lo [n], hi [n])."""
+    r = _rows_2d(rows)
+    n, d = r.shape
+    codes, lo, hi = np.empty((n, d), np.uint8), np.empty(n, np.float32), np.empty(n, np.float32)
+    ctx.check(ctx.lib.fvdb_sq8_encode(ctx.h, _ptr(r, f32p), n, d, _ptr(codes, _capi.u8p), _ptr(lo, f32p), _ptr(hi, f32p)))
+    return codes, lo, hi
+
+
+def dequantize_u8(ctx, codes, lo, hi):
+    """ScalarQuantizedVector::dequantize (src/core/vector_ops.rs:357-366) on the device: f32 rows [n][d]."""
+    c = np.ascontiguousarray(codes, np.uint8)
+    if c.ndim == 1:
+        c = c.reshape(1, -1)
+    lo, hi = _f32(lo).reshape(-1), _f32(hi).reshape(-1)
+    if c.ndim != 2 or lo.size != c.shape[0] or hi.size != c.shape[0]:
+        raise InvalidConfig(f"codes [n][d] need n values of lo and hi, got {c.shape}, {lo.size}, {hi.size}")
+    out = np.empty(c.shape, np.float32)
+    ctx.check(ctx.lib.fvdb_sq8_decode(ctx.h, _ptr(c, _capi.u8p), _ptr(lo, f32p), _ptr(hi, f32p), c.shape[0], c.shape[1], _ptr(out, f32p)))
+    return out
+
+
+class SQ8Index:
+    """An index of u8 scalar-quantized rows (fvdb_sq8_index): a symmetric search over the codes on
+    the int8 matrix cores, re-scored on request against the decoded rows or, with refine_rows "f32" / "f16", the originals."""
+
+    def __init__(self, ctx, d, refine_rows=None):
+        self.ctx, self.lib, self.d, self.refine_rows = ctx, ctx.lib, int(d), refine_rows
+        code = _capi.SQ8_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_sq8_index_create(ctx.h, self.d, code, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_sq8_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, ids, rows):
+        r = _rows_2d(rows, self.d)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_sq8_index_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_sq8_index_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_sq8_index_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_sq8_index_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_sq8_index_bytes(self.h))
+
+    def info(self):
+        """fvdb_sq8_info_t as a dict: the layout, the tile sizes, the scan's LDS per k class (k <= 64, 128, 256), the limits."""
+        v = _capi.SQ8Info()
+        self.ctx.check(self.lib.fvdb_sq8_index_info(self.h, C.byref(v)))
+        return {n: (list(getattr(v, n)) if n in ("queries_in_lds", "lds_bytes") else int(getattr(v, n))) for n, _ in v._fields_}
+
+    def search(self, queries, k, fetch_k=None, refine="decoded", allowed=None):
+        """The k nearest by the symmetric code distance (ties to the earlier row); with fetch_k, the fetch_k nearest of
+        that search re-scored against the f32 query and the k nearest of those.  refine: "decoded" (the candidates'
+        decoded rows) or "f32" / "f16" (the stored originals: the index's refine_rows).  allowed: only rows with these
+        ids are candidates."""
+        from .index import SearchResults
+        mode = _capi.SQ8_REFINE_DECODED
+        if fetch_k is not None and refine != "decoded":
+            if refine not in ("f32", "f16") or refine != self.refine_rows:
+                raise InvalidConfig(f'refine must be "decoded" or the index\'s refine_rows ({self.refine_rows!r}), got {refine!r}')
+            mode = _capi.SQ8_REFINE_ROWS
+        q = _rows_2d(queries, self.d)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        dist = np.full((B, max(k, 0)), np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_sq8_index_search(self.h, _ptr(q, f32p), B, k, int(fetch_k or 0), mode, ap, na, _ptr(ids, u64p),
+                                                      _ptr(dist, f32p), _ptr(counts, u32p)))
+        return SearchResults(ids, dist, counts)
+
+
 def merge_keys_dev(ctx, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev):
     ctx.check(ctx.lib.fvdb_merge_keys_dev(ctx.h, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev))
 

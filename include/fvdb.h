@@ -1189,6 +1189,80 @@ int fvdb_pq_index_search_dev_slot(fvdb_pq_index* ix, fvdb_ctx* on, uint32_t slot
                                   uint32_t fetch_k, const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                   uint32_t* out_counts_dev);
 
+/* ---- scalar quantization to u8 -------------------------------------
+ * scalar_quantize_u8 and ScalarQuantizedVector::dequantize (src/core/vector_ops.rs:348-387) and a search over the codes.
+ * d is the row width, 1 <= d <= 2048 (0: FVDB_E_INVALID, more: FVDB_E_UNSUPPORTED).
+ *
+ * encode (:369-387), per row, all in f32, multiply and add separate: lo = the minimum and hi = the maximum of the row,
+ * range = hi - lo.  range == 0: every code is 0.  Otherwise code_i = round_half_away((v_i - lo) / range * 255) as a
+ * byte, the division before the multiplication.  Of equal extremes the earliest in dimension order is kept (it decides
+ * the sign of a zero lo or hi; compare them as values).  A NaN or Inf element, or a row whose range overflows to
+ * infinity, is FVDB_E_NONFINITE before anything is written (host forms, index add and host search; the _dev forms read
+ * rows already in HBM and do not check them).
+ * decode (:357-366): lo + ((float)code / 255.0f) * range with range = hi - lo, f32, that order, no FMA.
+ *
+ * Symmetric score (no reference counterpart; the approximate stage).  The query is encoded by the same rule into a_i,
+ * lo_q, range_q.  Exact integer sums A1 = sum a_i, A2 = sum a_i^2, C1 = sum c_i, C2 = sum c_i^2, P = sum a_i c_i over
+ * the unsigned codes.  In f64 with + - * / only and no contraction: sq = (double)range_q / 255.0,
+ * sr = (double)range_r / 255.0, D = (double)lo_q - (double)lo_r,
+ *   S = ((((double)d * D) * D + (2.0 * D) * (sq * (double)A1 - sr * (double)C1))
+ *        + ((sq * sq) * (double)A2 + (sr * sr) * (double)C2)) - ((2.0 * sq) * sr) * (double)P
+ * — in real arithmetic the squared distance between the two decoded vectors — and
+ * dist = sqrtf((float)(S > 0.0 ? S : 0.0)).  A candidate's key is (bits(dist) << 32) | row, row = the append position;
+ * the result is the min(k, live rows) smallest keys, ascending.  1 <= k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED.
+ * Refined search (fetch_k != 0; k <= fetch_k, else FVDB_E_INVALID; fetch_k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED): the
+ * candidates are the symmetric search of fetch_k, each is re-scored against the f32 query with the fold
+ * t = a - b; s = s + t * t, ascending, sqrtf last, and the k smallest (bits(distance) << 32) | row are returned.
+ * refine_mode names the re-score source: FVDB_SQ8_REFINE_DECODED, the candidate's decoded row (always available), or
+ * FVDB_SQ8_REFINE_ROWS, its stored original (an index created with refine rows, else FVDB_E_INVALID; an fp16 row is
+ * widened exactly first).  Outputs as for the product-quantization index: B x k, unused tail = FVDB_NO_ID / +inf. */
+typedef struct fvdb_sq8_index fvdb_sq8_index;
+typedef struct fvdb_sq8_info_t {
+  uint32_t d, d_padded;            /* d rounded up to 32: the code bytes of a row in the index */
+  uint32_t block_rows;             /* rows of one code block (the matrix instruction's N) */
+  uint32_t queries_per_workgroup;  /* queries of one scan workgroup (its M) */
+  uint32_t round_rows;             /* rows a workgroup scores between two looks at its survivor buffers */
+  uint32_t words_in_flight;        /* 1 KiB code words a scan wave keeps in flight */
+  uint32_t min_slice_rows;         /* a scan slice is at least this many rows (the last one may be shorter) */
+  uint32_t lds_limit;              /* the device's LDS bytes per workgroup */
+  uint32_t queries_in_lds[3];      /* per k class (k <= 64, <= 128, <= 256): the query operands are staged in LDS */
+  uint32_t lds_bytes[3];           /* per k class: dynamic LDS of a scan workgroup */
+  uint32_t max_d, max_k;           /* the limits above */
+} fvdb_sq8_info_t;
+/* vector_ops.rs:348-387.  out_codes [n][d], out_lo[n], out_hi[n]; host arrays, synchronises. */
+int fvdb_sq8_encode(fvdb_ctx* ctx, const float* rows, uint64_t n, uint32_t d, uint8_t* out_codes, float* out_lo, float* out_hi);
+/* vector_ops.rs:348-387 (dequantize, :357-366).  out_rows [n][d]. */
+int fvdb_sq8_decode(fvdb_ctx* ctx, const uint8_t* codes, const float* lo, const float* hi, uint64_t n, uint32_t d, float* out_rows);
+/* vector_ops.rs:348-387 with device pointers, enqueued on ctx's stream; nothing is synchronised */
+int fvdb_sq8_encode_dev(fvdb_ctx* ctx, const float* rows_dev, uint64_t n, uint32_t d, uint8_t* out_codes_dev, float* out_lo_dev,
+                        float* out_hi_dev);
+/* vector_ops.rs:348-387 (dequantize) with device pointers, enqueued on ctx's stream; nothing is synchronised */
+int fvdb_sq8_decode_dev(fvdb_ctx* ctx, const uint8_t* codes_dev, const float* lo_dev, const float* hi_dev, uint64_t n, uint32_t d,
+                        float* out_rows_dev);
+/* An index of vector_ops.rs:348-387 codes.  refine_dtype: FVDB_SQ8_NO_REFINE, or FVDB_F32 / FVDB_F16 to keep the rows
+ * too, in an fvdb_store the index owns (store row = code row).  add, set_deleted, rows, live and bytes have the
+ * semantics and error codes of their fvdb_pq_index_ counterparts. */
+#define FVDB_SQ8_NO_REFINE (-1)
+#define FVDB_SQ8_REFINE_DECODED 0
+#define FVDB_SQ8_REFINE_ROWS 1
+int fvdb_sq8_index_create(fvdb_ctx* ctx, uint32_t d, int refine_dtype, fvdb_sq8_index** out);
+void fvdb_sq8_index_destroy(fvdb_sq8_index* ix);                                                    /* vector_ops.rs:348-387 */
+int fvdb_sq8_index_add(fvdb_sq8_index* ix, const uint64_t* ids, const float* rows, uint64_t n);     /* vector_ops.rs:348-387 */
+int fvdb_sq8_index_set_deleted(fvdb_sq8_index* ix, const uint64_t* ids, uint64_t n, int flag);      /* vector_ops.rs:348-387 */
+uint64_t fvdb_sq8_index_rows(fvdb_sq8_index* ix);                                                   /* vector_ops.rs:348-387 */
+uint64_t fvdb_sq8_index_live(fvdb_sq8_index* ix);                                                   /* vector_ops.rs:348-387 */
+uint64_t fvdb_sq8_index_bytes(fvdb_sq8_index* ix); /* vector_ops.rs:348-387: HBM held by the rows present: code blocks, records, ids, flags, refine rows */
+int fvdb_sq8_index_info(fvdb_sq8_index* ix, fvdb_sq8_info_t* out);                                  /* vector_ops.rs:348-387 */
+/* Host arrays (vector_ops.rs:348-387 codes on both sides).  fetch_k == 0: the symmetric search alone (refine_mode is
+ * ignored).  allowed_ids as for fvdb_pq_index_search.  Synchronises. */
+int fvdb_sq8_index_search(fvdb_sq8_index* ix, const float* q, uint32_t B, uint32_t k, uint32_t fetch_k, int refine_mode,
+                          const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dist, uint32_t* out_counts);
+/* Device pointers (vector_ops.rs:348-387 codes on both sides), enqueued on `on`'s stream (NULL: the index's context)
+ * with the scratch of `slot` (0..15); dead_dev as for fvdb_pq_index_search_dev_slot.  Nothing is synchronised. */
+int fvdb_sq8_index_search_dev_slot(fvdb_sq8_index* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                   uint32_t fetch_k, int refine_mode, const uint32_t* dead_dev, uint64_t* out_ids_dev,
+                                   float* out_dist_dev, uint32_t* out_counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
