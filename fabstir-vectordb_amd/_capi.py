@@ -86,6 +86,18 @@ class SQ8Info(C.Structure):
 
 SQ8_NO_REFINE, SQ8_REFINE_DECODED, SQ8_REFINE_ROWS = -1, 0, 1  # FVDB_SQ8_*
 
+
+
+class CosInfo(C.Structure):
+    """fvdb_cos_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("d", "d_padded", "block_rows", "queries_per_workgroup", "round_rows", "words_in_flight",
+                                   "min_slice_rows", "lds_limit")] + \
+               [("queries_in_lds", u32 * 3), ("lds_bytes", u32 * 3), ("max_d", u32), ("max_k", u32), ("E", f32),
+                ("mag_min", f32), ("mag_max", f32), ("fallback_queries", u32), ("exact_pairs", u64)]
+
+
+COS_FILTER, COS_EXACT = 0, 1  # FVDB_COS_*
+
 u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
@@ -308,6 +320,18 @@ SIGNATURES = {
     "fvdb_sq8_index_info": (i32, [vp, C.POINTER(SQ8Info)]),
     "fvdb_sq8_index_search": (i32, [vp, f32p, u32, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
     "fvdb_sq8_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, i32, vp, vp, vp, vp]),
+    "fvdb_batch_normalize": (i32, [vp, f32p, u64, u32, f32p]),
+    "fvdb_batch_normalize_dev": (i32, [vp, vp, u64, u32, vp]),
+    "fvdb_cos_index_create": (i32, [vp, u32, C.POINTER(vp)]),
+    "fvdb_cos_index_destroy": (None, [vp]),
+    "fvdb_cos_index_add": (i32, [vp, u64p, f32p, u64]),
+    "fvdb_cos_index_set_deleted": (i32, [vp, u64p, u64, i32]),
+    "fvdb_cos_index_rows": (u64, [vp]),
+    "fvdb_cos_index_live": (u64, [vp]),
+    "fvdb_cos_index_bytes": (u64, [vp]),
+    "fvdb_cos_index_info": (i32, [vp, C.POINTER(CosInfo)]),
+    "fvdb_cos_index_search": (i32, [vp, f32p, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
+    "fvdb_cos_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

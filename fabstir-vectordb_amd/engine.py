@@ -827,6 +827,102 @@ class SQ8Index:
         return SearchResults(ids, dist, counts)
 
 
+def batch_normalize(ctx, rows):
+    """batch_normalize (src/core/vector_ops.rs:138-150) on the device: each row divided by its norm, a zero row unchanged."""
+    r = _rows_2d(rows)
+    out = np.empty(r.shape, np.float32)
+    ctx.check(ctx.lib.fvdb_batch_normalize(ctx.h, _ptr(r, f32p), r.shape[0], r.shape[1], _ptr(out, f32p)))
+    return out
+
+
+class CosineResults:
+    """B x k ids / similarities with per-query hit counts; the unused tail is FVDB_NO_ID / -inf."""
+
+    def __init__(self, ids, similarities, counts):
+        self.ids, self.similarities, self.counts = ids, similarities, counts
+
+    def __len__(self):
+        return self.ids.shape[0]
+
+    def __getitem__(self, b):
+        n = int(self.counts[b])
+        return self.ids[b, :n], self.similarities[b, :n]
+
+
+class CosineIndex:
+    """Cosine k-NN over rows in HBM (fvdb_cos_index): batch_search_parallel
+    (src/core/vector_ops.rs:310-346) with ties to the row added earlier.  The fp16 matrix cores filter, every row that
+    can reach the answer is scored with the reference's f32 arithmetic."""
+
+    def __init__(self, ctx, d):
+        self.ctx, self.lib, self.d = ctx, ctx.lib, int(d)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_cos_index_create(ctx.h, self.d, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_cos_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, ids, rows):
+        r = _rows_2d(rows, self.d)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_cos_index_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_cos_index_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_cos_index_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_cos_index_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_cos_index_bytes(self.h))
+
+    def info(self):
+        """fvdb_cos_info_t as a dict: the bound E and the magnitude window, the scan's geometry and LDS per k class
+        (k <= 64, 128, 256; queries_in_lds 0 = the query operands are read from HBM), and of the last search
+        exact_pairs and fallback_queries."""
+        v = _capi.CosInfo()
+        self.ctx.check(self.lib.fvdb_cos_index_info(self.h, C.byref(v)))
+        out = {}
+        for n, _ in v._fields_:
+            x = getattr(v, n)
+            out[n] = list(x) if n in ("queries_in_lds", "lds_bytes") else (float(x) if n in ("E", "mag_min", "mag_max") else int(x))
+        return out
+
+    def search(self, queries, k, allowed=None, mode="filter"):
+        """The k live rows of largest cosine similarity, descending, ties to the earlier row.  mode "filter": the
+        matrix-core filter and an exact re-score of its survivors; "exact": every live row scored exactly (the same
+        answer, bit for bit).  allowed: only rows with these ids are candidates."""
+        if mode not in ("filter", "exact"):
+            raise InvalidConfig(f'mode must be "filter" or "exact", got {mode!r}')
+        q = _rows_2d(queries, self.d)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        sim = np.full((B, max(k, 0)), -np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_cos_index_search(self.h, _ptr(q, f32p), B, k, _capi.COS_EXACT if mode == "exact" else _capi.COS_FILTER,
+                                                      ap, na, _ptr(ids, u64p), _ptr(sim, f32p), _ptr(counts, u32p)))
+        return CosineResults(ids, sim, counts)
+
+
 def merge_keys_dev(ctx, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev):
     ctx.check(ctx.lib.fvdb_merge_keys_dev(ctx.h, keys_dev, ids_dev, G, B, k, out_ids_dev, out_dist_dev, out_cnt_dev))
 

@@ -1263,6 +1263,76 @@ int fvdb_sq8_index_search_dev_slot(fvdb_sq8_index* ix, fvdb_ctx* on, uint32_t sl
                                    uint32_t fetch_k, int refine_mode, const uint32_t* dead_dev, uint64_t* out_ids_dev,
                                    float* out_dist_dev, uint32_t* out_counts_dev);
 
+/* ---- cosine search --------------------------------------------------
+ * batch_search_parallel (src/core/vector_ops.rs:310-346: batch_cosine_similarity, then a top-k; the browser index has
+ * the same search, bindings/wasm/src/index.rs:122) and batch_normalize (:138-150), for rows resident in HBM.
+ *
+ * The similarity is Embedding::cosine_similarity (src/core/types.rs:79-103), which cosine_similarity_scalar
+ * (vector_ops.rs:39-49) matches, all in f32 with multiply and add separate: dot = the left-to-right fold of the
+ * products a_i * b_i, each magnitude = sqrtf of the same fold of the squares, the result dot / (mag_a * mag_b), or 0.0
+ * when either magnitude is 0.  It is what fvdb_cosine_similarities returns.
+ * The answer for a query is the min(k, live rows) live rows of largest similarity, descending, ties to the row added
+ * earlier: the set and order top_k_indices (:12-22, a stable sort) gives on batch_cosine_similarity's output.
+ * batch_search_parallel itself calls top_k_indices_heap, whose choice and order among exactly equal scores come out of
+ * the heap's internal layout; fvdb_top_k_indices_heap remains for a caller who needs that order.
+ * Outputs per query: out_ids (caller-chosen u64) and out_sim are B x k, out_counts[B]; the unused tail is FVDB_NO_ID
+ * and -inf.  An empty index and an index with every row deleted give counts of 0.
+ *
+ * FVDB_COS_FILTER: the unit rows rounded to fp16 are scored on the matrix cores; the accumulator differs from the
+ * similarity above by at most E = 2^-9 (fvdb_cos_info_t.E; DESIGN 9y derives it), a running threshold drops only rows
+ * that provably cannot enter or tie, and every other row is scored by the definition above: ids, similarity bits and
+ * counts are those of FVDB_COS_EXACT, which scores every live row by the definition.  A query whose survivors outgrow
+ * their arena is answered the exact way and counted (fallback_queries).
+ * Limits: 1 <= d <= 2048 (0: FVDB_E_INVALID, more: FVDB_E_UNSUPPORTED), 1 <= k <= FVDB_MAX_K (else FVDB_E_UNSUPPORTED).
+ * The bound assumes magnitudes away from the ends of the f32 range: a row or query whose magnitude, by the fold above,
+ * is neither 0 nor within [2^-40, 2^40] is FVDB_E_UNSUPPORTED; a NaN or Inf element, or a sum of squares that
+ * overflows, is FVDB_E_NONFINITE; both before anything is written (add and the host search; the _dev forms read rows
+ * already in HBM and do not check them). */
+typedef struct fvdb_cos_index fvdb_cos_index;
+#define FVDB_COS_FILTER 0
+#define FVDB_COS_EXACT 1
+typedef struct fvdb_cos_info_t {
+  uint32_t d, d_padded;            /* d rounded up to 16: the halves of a row in the operand form */
+  uint32_t block_rows;             /* rows of one operand block (the matrix instruction's N) */
+  uint32_t queries_per_workgroup;  /* queries of one scan workgroup (its M) */
+  uint32_t round_rows;             /* rows a workgroup scores between two updates of its thresholds */
+  uint32_t words_in_flight;        /* 1 KiB operand words a scan wave keeps in flight */
+  uint32_t min_slice_rows;         /* a scan slice is at least this many rows (the last one may be shorter) */
+  uint32_t lds_limit;              /* the device's LDS bytes per workgroup */
+  uint32_t queries_in_lds[3];      /* per k class (k <= 64, <= 128, <= 256): 1 = the query operands are staged in LDS, 0 = read from HBM */
+  uint32_t lds_bytes[3];           /* per k class: dynamic LDS of a scan workgroup */
+  uint32_t max_d, max_k;           /* the limits above */
+  float E;                         /* the filter's bound on |accumulator - similarity| */
+  float mag_min, mag_max;          /* the magnitude window */
+  uint32_t fallback_queries;       /* last search: queries of a filter search whose arena overflowed */
+  uint64_t exact_pairs;            /* last search: (query, row) pairs the exact stage scored */
+} fvdb_cos_info_t;
+/* vector_ops.rs:138-150, bit for bit: norm = sqrtf of the fold of the squares, out = x / norm element by element, a
+ * zero-norm row copied unchanged.  rows and out are [n][d] host arrays, any d >= 1; synchronises. */
+int fvdb_batch_normalize(fvdb_ctx* ctx, const float* rows, uint64_t n, uint32_t d, float* out);
+/* vector_ops.rs:138-150 with device pointers, enqueued on ctx's stream; nothing is synchronised */
+int fvdb_batch_normalize_dev(fvdb_ctx* ctx, const float* rows_dev, uint64_t n, uint32_t d, float* out_dev);
+/* An index for vector_ops.rs:310-346.  Per row it keeps the f32 row as given, its magnitude, a deleted flag and the
+ * unit row in fp16 in the matrix instruction's operand form.  add, set_deleted, rows, live and bytes have the
+ * semantics and error codes of their fvdb_sq8_index_ counterparts. */
+int fvdb_cos_index_create(fvdb_ctx* ctx, uint32_t d, fvdb_cos_index** out);
+void fvdb_cos_index_destroy(fvdb_cos_index* ix);                                                    /* vector_ops.rs:310-346 */
+int fvdb_cos_index_add(fvdb_cos_index* ix, const uint64_t* ids, const float* rows, uint64_t n);     /* vector_ops.rs:310-346 */
+int fvdb_cos_index_set_deleted(fvdb_cos_index* ix, const uint64_t* ids, uint64_t n, int flag);      /* vector_ops.rs:310-346 */
+uint64_t fvdb_cos_index_rows(fvdb_cos_index* ix);                                                   /* vector_ops.rs:310-346 */
+uint64_t fvdb_cos_index_live(fvdb_cos_index* ix);                                                   /* vector_ops.rs:310-346 */
+uint64_t fvdb_cos_index_bytes(fvdb_cos_index* ix); /* vector_ops.rs:310-346: HBM held by the rows present: operand blocks, f32 rows, magnitudes, ids, flags */
+/* vector_ops.rs:310-346: the geometry, and the counters of the last search (waits for the device when there was one) */
+int fvdb_cos_index_info(fvdb_cos_index* ix, fvdb_cos_info_t* out);
+/* Host arrays (vector_ops.rs:310-346).  mode: FVDB_COS_FILTER or FVDB_COS_EXACT (else FVDB_E_INVALID).  allowed_ids as
+ * for fvdb_sq8_index_search.  Synchronises. */
+int fvdb_cos_index_search(fvdb_cos_index* ix, const float* q, uint32_t B, uint32_t k, int mode, const uint64_t* allowed_ids,
+                          uint64_t n_allowed, uint64_t* out_ids, float* out_sim, uint32_t* out_counts);
+/* Device pointers (vector_ops.rs:310-346), enqueued on `on`'s stream (NULL: the index's context) with the scratch of
+ * `slot` (0..15); dead_dev as for fvdb_sq8_index_search_dev_slot.  Nothing is synchronised. */
+int fvdb_cos_index_search_dev_slot(fvdb_cos_index* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k, int mode,
+                                   const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_sim_dev, uint32_t* out_counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
