@@ -98,6 +98,16 @@ class CosInfo(C.Structure):
 
 COS_FILTER, COS_EXACT = 0, 1  # FVDB_COS_*
 
+
+class FlatMfmaInfo(C.Structure):
+    """fvdb_flat_mfma_info (include/fvdb.h)."""
+    _fields_ = [(n, u64) for n in ("mirror_rows", "mirror_bytes", "rebuilds", "build_rows")] + [("build_ms", f32)] + \
+               [(n, u32) for n in ("block_rows", "queries_per_workgroup", "round_rows", "words_in_flight", "min_slice_rows",
+                                   "lds_limit")] + \
+               [("lds_bytes", u32 * 3), ("queries_in_lds", u32 * 3), ("max_d", u32), ("max_k", u32), ("exact_pairs", u64),
+                ("fallback_queries", u32), ("unbounded_queries", u32)]
+
+
 u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes).  Every symbol include/fvdb.h declares is listed here and
@@ -267,6 +277,9 @@ SIGNATURES = {
     "fvdb_graph_scan_allowed_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
     "fvdb_graph_search_flat_wide_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    # exact search, filtered
+    "fvdb_graph_search_flat_mfma_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]),
+    "fvdb_graph_flat_mfma_info": (i32, [vp, C.POINTER(FlatMfmaInfo)]),
     # radius search
     "fvdb_graph_search_flat_radius_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp]),
     "fvdb_graph_count_within_dev_slot": (i32, [vp, vp, u32, vp, vp, u32, vp, vp]),

@@ -63,6 +63,7 @@ struct fvdb_graph {
   // set_lists, set_entry, set_deleted): a mask (fvdb_mask) built before the bump is refused by the masked searches
   uint64_t mutations = 0;
   DBuf s_scan[kSlots];  // exact scan under a mask (allow_masks.h): padded queries and partial lists, one per slot
+  GraphFlatMirror flat_mirror;  // fp16 operand form of rows [0, built) for the filtered exact search (section 9z)
   // profiling: HIP events around the last launches of the traversal kernel (ring of 64)
   DevEvent kev[64][2];
   uint32_t kev_n = 0;   // launches recorded since the last fvdb_graph_kernel_times call
@@ -644,6 +645,7 @@ int fvdb_graph_configure(fvdb_graph* g, uint32_t max_connections, uint32_t max_c
 int fvdb_graph_upload(fvdb_graph* g, uint32_t n, const uint32_t* levels, const uint8_t* deleted,
                       const uint32_t* slot_start, const uint32_t* adj, uint32_t entry_node) {
   g->mutations += 1;
+  g->flat_mirror.reset();  // an installed graph may sit on other rows than the last one
   fvdb_ctx* ctx = g->store->ctx;
   if (n == 0 || n > g->store->rows || entry_node >= n) FAIL(ctx, FVDB_E_INVALID, "graph does not match the store");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1344,6 +1346,7 @@ extern "C" int fvdb_graph_vacuum(fvdb_graph* g, uint32_t flags, uint64_t* remove
   if (rc) return rc;
   // stage 4: bookkeeping
   g->mutations += 1;
+  g->flat_mirror.reset();  // a reclaiming vacuum renumbers the rows; the in-place one resets too: a rebuild is one pass
   info.edges_in = J.h_cnt[0];
   info.edges_out = J.h_cnt[1];
   if (keep_rows) {
@@ -1580,6 +1583,7 @@ int graph_mask_source(fvdb_graph* g, GraphMaskSource* out) {
   out->mutations = g->mutations;
   return FVDB_OK;
 }
+GraphFlatMirror* graph_flat_mirror(fvdb_graph* g) { return &g->flat_mirror; }
 int graph_scan_inputs(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, const float* q_dev, uint32_t B, size_t part_bytes,
                       const float** queries, uint64_t** part) {
   const fvdb_store* s = g->store;

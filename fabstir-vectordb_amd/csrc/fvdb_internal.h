@@ -102,3 +102,22 @@ int graph_mask_source(fvdb_graph* g, GraphMaskSource* out);
 int graph_scan_inputs(fvdb_graph* g, fvdb_ctx* ctx, uint32_t slot, const float* q_dev, uint32_t B, size_t part_bytes,
                       const float** queries, uint64_t** part);
 constexpr uint32_t kGraphSlots = 16;
+
+// ---- the operand mirror of a graph's rows (flat_mfma_search.h) --------------------------------
+// Owned by the graph, built and read by the filtered exact search.  Rows [0, built) of the store are mirrored; whatever
+// renumbers or replaces rows (upload, vacuum) calls reset() and the next filtered search builds the mirror whole.
+struct GraphFlatMirror {
+  std::mutex mu;           // builds take turns; a search holds it only while it looks at / extends the mirror
+  DBuf ops, xn, xmax;      // operand words [blocks][ksteps][64], |x|^2 [rows], the largest |x|^2 (one word)
+  DBuf ctr[kGraphSlots];   // a slot's counters of its last search: pairs (8 bytes), fallbacks, unbounded
+  uint64_t built = 0, cap_blocks = 0, builds = 0;
+  uint32_t last_slot = 0;
+  bool searched = false;
+  float build_ms = 0.0f;   // the last build or extension, and the rows it covered
+  uint64_t build_rows = 0;
+  void reset() {
+    std::lock_guard<std::mutex> lk(mu);
+    built = 0;
+  }
+};
+GraphFlatMirror* graph_flat_mirror(fvdb_graph* g);

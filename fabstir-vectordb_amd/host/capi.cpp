@@ -220,6 +220,14 @@ int fvh_hnsw_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32
   return FVDB_OK;
 }
 // the same three at k up to FVDB_MAX_K_WIDE
+int fvh_hnsw_search_exact_filtered(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact_filtered(q, B, d, k, ids, dist, counts);
+}
+int fvh_hnsw_search_exact_filtered_allowed(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, const uint64_t* allowed,
+                                           uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  return ((HNSWIndex*)p)->search_exact_filtered_allowed(q, B, d, k, allowed, n_allowed, ids, dist, counts);
+}
+int fvh_hnsw_exact_filter_info(void* p, fvdb_flat_mfma_info* out) { return ((HNSWIndex*)p)->exact_filter_info(out); }
 int fvh_hnsw_search_exact_wide(void* p, const float* q, uint32_t B, uint32_t d, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
   return ((HNSWIndex*)p)->search_exact_wide(q, B, d, k, ids, dist, counts);
 }
@@ -484,6 +492,14 @@ int fvh_hybrid_search_exact(void* p, const float* q, uint32_t B, uint32_t d, uin
   c.search_recent = search_recent != 0;
   c.search_historical = search_historical != 0;
   return ((HybridIndex*)p)->search_exact(q, B, d, c, now, ids, dist, counts);
+}
+int fvh_hybrid_search_exact_filtered(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, int search_recent,
+                                     int search_historical, double now, uint64_t* ids, float* dist, uint32_t* counts) {
+  HybridSearchConfig c;
+  c.k = k;
+  c.search_recent = search_recent != 0;
+  c.search_historical = search_historical != 0;
+  return ((HybridIndex*)p)->search_exact_filtered(q, B, d, c, now, ids, dist, counts);
 }
 int fvh_hybrid_evaluate_search_quality(void* p, const float* q, uint32_t B, uint32_t d, uint64_t k, uint64_t ef, uint64_t nprobe,
                                        double now, float* out3, uint64_t* queries_evaluated) {

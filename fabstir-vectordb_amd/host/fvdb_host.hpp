@@ -523,6 +523,7 @@ class HNSWIndex {
     uint64_t n_allowed = 0;
     uint32_t slot = 0;                      // stream, scratch set and result block
     bool wide = false;                      // kExact only: k up to FVDB_MAX_K_WIDE, fvdb_graph_search_flat_wide_dev_slot
+    bool filtered = false;                  // kExact only: the same answer by fvdb_graph_search_flat_mfma_dev_slot (section 9z)
     bool owns_slot = false;                // the caller holds `slot` for the call (HybridIndex's lease): run() takes no lock
     // kExact + wide, radius search: the rows within radius[b] (host memory, checked by the entry
     // point), at most k of them, and the size of each ball to totals[B]; count_only: the sizes alone (k = 1, no ids)
@@ -574,6 +575,16 @@ class HNSWIndex {
   // the same with the queries in HBM and the slot chosen by the caller, who owns that slot for the call (HybridIndex)
   int search_exact_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
                        float* dist, uint32_t* counts, uint32_t slot);
+  // The same three by the filtered route (fvdb_graph_search_flat_mfma_dev_slot): an fp16
+  // matrix-core filter over a mirror of the rows, the survivors scored by the same fold.  Same ids, distance bits and
+  // counts; also FVDB_E_UNSUPPORTED above 2048 dimensions.  exact_filter_info: fvdb_graph_flat_mfma_info
+  // (FVDB_E_NOT_FOUND before the device graph exists).
+  int search_exact_filtered(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts);
+  int search_exact_filtered_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed, uint64_t n_allowed,
+                                    uint64_t* ids, float* dist, uint32_t* counts);
+  int search_exact_filtered_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                                float* dist, uint32_t* counts, uint32_t slot);
+  int exact_filter_info(fvdb_flat_mfma_info* out);
   // search(k, ef) against search_exact(k): the reference's recall / precision (src/ivf/operations.rs:329-391 applied
   // to the graph).  B == 0 is FVDB_E_INVALID.
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint32_t ef, SearchQuality* out);
@@ -949,6 +960,9 @@ class HybridIndex {
   // only the lists it owns.
   int search_exact(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
                    float* dist, uint32_t* counts);
+  // search_exact with the recent part from the graph's filtered route: the same answer
+  int search_exact_filtered(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                            float* dist, uint32_t* counts);
   // search(cfg) against search_exact(cfg) under ONE hold of the read lock, after one migration step: both see the same
   // rows.  B == 0 is FVDB_E_INVALID.
   int evaluate_search_quality(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now,
@@ -1080,12 +1094,12 @@ class HybridIndex {
   // search_allowed_groups after the migration step, the caller holding the read side of rw_
   int groups_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, const AllowGroups& groups, uint64_t* ids,
                     float* dist, uint32_t* counts);
-  // wide: the graph's wide exact scan, part sizes up to FVDB_MAX_K_WIDE
+  // wide: the graph's wide exact scan, part sizes up to FVDB_MAX_K_WIDE; filtered: the graph's filtered route
   int exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
-                   uint32_t* counts, bool wide = false);
+                   uint32_t* counts, bool wide = false, bool filtered = false);
   // search_exact / search_exact_wide and evaluate_search_quality / _wide: one body each, `wide` choosing the limit of k
   int exact_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids, float* dist,
-                 uint32_t* counts, bool wide);
+                 uint32_t* counts, bool wide, bool filtered = false);
   int quality_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, SearchQuality* out,
                    bool wide);
   std::mutex qual_mu_;  // evaluate_search_quality's staging block

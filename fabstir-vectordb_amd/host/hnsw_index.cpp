@@ -536,8 +536,9 @@ int HNSWIndex::launch(Search& s) {
                       : fvdb_graph_search_flat_radius_dev_slot(graph_, on, s.slot, mask, s.q_dev, s.B, r_dev, s.k, d.nodes, d.dist,
                                                                d.counts, d.status);
   else if (s.kind == Search::kExact)
-    rc = (s.wide ? fvdb_graph_search_flat_wide_dev_slot : fvdb_graph_search_flat_dev_slot)(graph_, on, s.slot, mask, s.q_dev, s.B, s.k,
-                                                                                          d.nodes, d.dist, d.counts);
+    rc = (s.wide       ? fvdb_graph_search_flat_wide_dev_slot
+          : s.filtered ? fvdb_graph_search_flat_mfma_dev_slot
+                       : fvdb_graph_search_flat_dev_slot)(graph_, on, s.slot, mask, s.q_dev, s.B, s.k, d.nodes, d.dist, d.counts);
   else if (!s.view)
     rc = fvdb_graph_search_dev_slot(graph_, on, s.slot, s.q_dev, s.B, s.k, s.ef, d.nodes, d.dist, d.counts, d.status);
   else if (s.scanned)
@@ -876,6 +877,32 @@ int HNSWIndex::search_exact_allowed(const float* q, uint32_t B, uint32_t dim, ui
   Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
   s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed;
   return run(s);
+}
+
+// ---- the same by the filtered route: the request's `filtered` flag and nothing else ----
+int HNSWIndex::search_exact_filtered_dev(const float* q_dev, uint32_t B, uint32_t dim, uint32_t k, const AllowView* view, uint64_t* ids,
+                                         float* dist, uint32_t* counts, uint32_t slot) {
+  Search s{Search::kExact, q_dev, true, B, dim, k, 0, ids, dist, counts};
+  s.view = view, s.slot = slot, s.owns_slot = true, s.filtered = true;
+  return run(s);
+}
+
+int HNSWIndex::search_exact_filtered(const float* q, uint32_t B, uint32_t dim, uint32_t k, uint64_t* ids, float* dist, uint32_t* counts) {
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  s.filtered = true;
+  return run(s);
+}
+
+int HNSWIndex::search_exact_filtered_allowed(const float* q, uint32_t B, uint32_t dim, uint32_t k, const uint64_t* allowed,
+                                             uint64_t n_allowed, uint64_t* ids, float* dist, uint32_t* counts) {
+  Search s{Search::kExact, q, false, B, dim, k, 0, ids, dist, counts};
+  s.by_list = true, s.allowed = allowed, s.n_allowed = n_allowed, s.filtered = true;
+  return run(s);
+}
+
+int HNSWIndex::exact_filter_info(fvdb_flat_mfma_info* out) {
+  if (!graph_) return FVDB_E_NOT_FOUND;
+  return fvdb_graph_flat_mfma_info(graph_, out);
 }
 
 // ---- the same at k up to FVDB_MAX_K_WIDE: the request's `wide` flag and nothing else ----

@@ -922,7 +922,7 @@ int HybridIndex::search_locked(const float* q, bool q_on_device, uint32_t B, uin
 // The two exact parts and the usual merge; the caller holds the read side of rw_.  The graph's scan runs in a slot leased
 // for the call (its stream, its scratch, its result block), the every-list search in a scratch set the engine leases.
 int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, uint64_t* ids, float* dist,
-                              uint32_t* counts, bool wide) {
+                              uint32_t* counts, bool wide, bool filtered) {
   const uint32_t k = (uint32_t)cfg.k;
   const uint32_t rk = cfg.rk(), hk = cfg.hk();
   if (int rc = check_finite(q, (uint64_t)B * dim)) return rc;  // whichever parts are searched, and before any other refusal
@@ -939,8 +939,9 @@ int HybridIndex::exact_locked(const float* q, uint32_t B, uint32_t dim, const Hy
     int rc;
     if ((rc = stage_finite(sl, q, B, dim))) return rc;
     const float* qd = (const float*)sl.d_q.dev;
-    if ((rc = wide ? recent_->search_exact_wide_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())
-                   : recent_->search_exact_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())))
+    if ((rc = wide       ? recent_->search_exact_wide_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())
+              : filtered ? recent_->search_exact_filtered_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())
+                         : recent_->search_exact_dev(qd, B, dim, rk, nullptr, rid.data(), rd.data(), rc_.data(), lease.index())))
       return rc;
   }
   if (have_h) {
@@ -965,8 +966,14 @@ int HybridIndex::search_exact_wide(const float* q, uint32_t B, uint32_t dim, con
   return exact_impl(q, B, dim, cfg, now, ids, dist, counts, true);
 }
 
+// the same search with the recent part from the graph's filtered route
+int HybridIndex::search_exact_filtered(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
+                                       float* dist, uint32_t* counts) {
+  return exact_impl(q, B, dim, cfg, now, ids, dist, counts, false, true);
+}
+
 int HybridIndex::exact_impl(const float* q, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg, double now, uint64_t* ids,
-                            float* dist, uint32_t* counts, bool wide) {
+                            float* dist, uint32_t* counts, bool wide, bool filtered) {
   if (sharded_ || shard_world_) return FVDB_E_UNSUPPORTED;  // a rank holds only the lists it owns
   const uint32_t k = (uint32_t)cfg.k;
   if (cfg.k == 0 || cfg.k > (wide ? FVDB_MAX_K_WIDE : FVDB_MAX_K)) return FVDB_E_UNSUPPORTED;
@@ -974,7 +981,7 @@ int HybridIndex::exact_impl(const float* q, uint32_t B, uint32_t dim, const Hybr
   if (!initialized_ || B == 0) return FVDB_OK;
   if (int rc = migrate_if_due(now, false)) return rc;
   std::shared_lock<std::shared_mutex> r(rw_);
-  return exact_locked(q, B, dim, cfg, ids, dist, counts, wide);
+  return exact_locked(q, B, dim, cfg, ids, dist, counts, wide, filtered);
 }
 
 // ---- radius search: two radius parts, the usual merge, the sum of the two totals ----

@@ -165,6 +165,11 @@ HOST_SIGNATURES = {
     "fvh_hybrid_search_exact": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hybrid_evaluate_search_quality": (i32, [vp, f32p, u32, u32, u64, u64, u64, dbl, f32p, u64p]),
     # the same at k up to 4096
+    # exact search, filtered
+    "fvh_hnsw_search_exact_filtered": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
+    "fvh_hnsw_search_exact_filtered_allowed": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvh_hnsw_exact_filter_info": (i32, [vp, vp]),
+    "fvh_hybrid_search_exact_filtered": (i32, [vp, f32p, u32, u32, u64, i32, i32, dbl, u64p, f32p, u32p]),
     "fvh_hnsw_search_exact_wide": (i32, [vp, f32p, u32, u32, u32, u64p, f32p, u32p]),
     "fvh_hnsw_search_exact_wide_allowed": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
     "fvh_hnsw_evaluate_search_quality_wide": (i32, [vp, f32p, u32, u32, u32, u32, f32p, u64p]),
@@ -867,6 +872,24 @@ class HNSWIndex(_Base):
         a = _allowed_ids(allowed)
         return self._search(self.lib.fvh_hnsw_search_exact_allowed, queries, k, _ptr(a, u64p), a.size)
 
+    def search_exact_filtered(self, queries, k, allowed=None):
+        """search_exact() — search_exact_allowed() when `allowed` is given — by the filtered route (DESIGN.md section
+        9z): every pair scored on the matrix cores against an fp16 mirror of the rows, which the graph builds on the
+        first call and extends after appends, and only the rows that can reach the answer scored with the f32 fold.
+        The same ids, distance bits and counts.  k in 1..256, at most 2048 dimensions."""
+        if allowed is None:
+            return self._search(self.lib.fvh_hnsw_search_exact_filtered, queries, k)
+        a = _allowed_ids(allowed)
+        return self._search(self.lib.fvh_hnsw_search_exact_filtered_allowed, queries, k, _ptr(a, u64p), a.size)
+
+    def exact_filter_info(self):
+        """fvdb_flat_mfma_info as a dict: the mirror's rows, bytes and rebuilds, the last build's rows and milliseconds,
+        the scan's geometry and LDS per k class, and of the last search_exact_filtered() "exact_pairs",
+        "fallback_queries" (arena overflowed) and "unbounded_queries" (infinite bound), both answered over all rows."""
+        v = _capi.FlatMfmaInfo()
+        self._check(self.lib.fvh_hnsw_exact_filter_info(self.h, C.cast(C.pointer(v), C.c_void_p)))
+        return {n: (list(getattr(v, n)) if n in ("lds_bytes", "queries_in_lds") else getattr(v, n)) for n, _ in v._fields_}
+
     def evaluate_search_quality(self, queries, k, ef):
         """search(k, ef) against search_exact(k) with the reference's formulas (src/ivf/operations.rs:357-377): per query
         matches = result entries whose id is among the truth's, recall = matches / min(len(truth), k) (1 if the truth
@@ -1361,6 +1384,12 @@ class HybridIndex(_Base):
         (Unsupported) on a sharded index: each rank holds only the lists it owns, so no rank can answer alone."""
         self._refuse_when_sharded("search_exact")
         return self._search(self.lib.fvh_hybrid_search_exact, queries, k, int(search_recent), int(search_historical),
+                            float(now))
+
+    def search_exact_filtered(self, queries, k, now=0.0, search_recent=True, search_historical=True):
+        """search_exact() with the recent part from the graph's filtered route: the same answer."""
+        self._refuse_when_sharded("search_exact_filtered")
+        return self._search(self.lib.fvh_hybrid_search_exact_filtered, queries, k, int(search_recent), int(search_historical),
                             float(now))
 
     def evaluate_search_quality(self, queries, k, now=0.0, hnsw_ef=50, ivf_n_probe=10):

@@ -783,6 +783,36 @@ int fvdb_graph_search_flat_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, 
 int fvdb_graph_search_flat_wide_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
                                          uint32_t B, uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev,
                                          uint32_t* out_counts_dev);
+/* ---- exact search, filtered --------------------------------------
+ * fvdb_graph_search_flat_dev_slot's answer — the same nodes, distance bits and counts, ties to the lower node — by
+ * another route; arguments, outputs, mask, slot, stream and staleness rules, refusals and messages are that call's,
+ * with one more: a store wider than 2048 dimensions is FVDB_E_UNSUPPORTED (after the k check).  Every (query, row)
+ * pair is scored approximately by v_mfma_f32_32x32x16_f16 over an fp16 operand mirror of the rows; a per-query running
+ * threshold with the margin of the documented error bound keeps the rows that can reach the answer, and only those are
+ * scored with the reference's f32 fold, from the store.  The graph owns the mirror (1 KiB per 32 rows and 16
+ * dimensions, and 4 bytes a row): built on the first call, on the calling context's stream, which is waited for;
+ * extended by the rows appended since; reset by fvdb_graph_upload and fvdb_graph_vacuum and then rebuilt whole by the
+ * next call.  A query whose survivor arena fills up, or whose error bound is infinite (a magnitude could leave the fp16
+ * range), is answered by the exact fold over every live row, and counted. */
+int fvdb_graph_search_flat_mfma_dev_slot(fvdb_graph* g, fvdb_ctx* on, uint32_t slot, fvdb_mask* mask, const float* q_dev,
+                                         uint32_t B, uint32_t k, uint32_t* out_nodes_dev, float* out_dist_dev,
+                                         uint32_t* out_counts_dev);
+typedef struct fvdb_flat_mfma_info {
+  uint64_t mirror_rows, mirror_bytes; /* rows in the mirror now, and the HBM they take */
+  uint64_t rebuilds;                  /* whole builds after the first one (a reset came before each) */
+  uint64_t build_rows;                /* the last build or extension: rows covered, and its wall time with the wait */
+  float build_ms;
+  uint32_t block_rows, queries_per_workgroup, round_rows, words_in_flight, min_slice_rows;
+  uint32_t lds_limit;                 /* bytes of LDS a workgroup may take on this device */
+  uint32_t lds_bytes[3];              /* the scan's LDS for k <= 64, <= 128, <= 256 ... */
+  uint32_t queries_in_lds[3];         /* ... and whether the query operands are part of it (else read from HBM) */
+  uint32_t max_d, max_k;
+  /* of the last call (it is waited for): pairs scored by the exact fold, queries answered over all rows because
+   * their arena overflowed, queries answered over all rows because their bound is infinite */
+  uint64_t exact_pairs;
+  uint32_t fallback_queries, unbounded_queries;
+} fvdb_flat_mfma_info;
+int fvdb_graph_flat_mfma_info(fvdb_graph* g, fvdb_flat_mfma_info* out);
 /* ---- radius search -----------------------------------------------
  * "Everything within r" where every search above answers "the k nearest".  For query b with radius r = radius[b]
  * (f32, r >= 0, +inf allowed) the BALL is the set of candidate rows — the rows the corresponding k-search would score,

@@ -12,8 +12,11 @@ and whether the three answers are identical (ids and distance bits).
 The scan reads rows and liveness flags, never links, so the graph is installed with restore() as a ring: the rows get
 into the store the way a restored index's do, without a million sequential inserts.
 
-With --route (wide | register | copy, repeatable) the tool times just those routes of DESIGN.md section 9q instead, and
---k may then exceed 256 on the wide and copy routes:
+With --route (wide | register | copy | filtered, repeatable) the tool times just those routes of DESIGN.md sections 9q and
+9z instead, and --k may then exceed 256 on the wide and copy routes:
+  filtered  HNSWIndex.search_exact_filtered (k <= 256): the fp16 matrix-core filter and the exact re-score; the mirror
+            is built by the warm-up call, and its build rate, bytes per row and the last call's exact_pairs / (B n) and
+            fallback_queries are reported beside the times (--rows normal: standard-normal rows instead of the mixture)
   wide      HNSWIndex.search_exact_wide: the same tile scan writing a distance arena, then the wide selection
   register  HNSWIndex.search_exact (k <= 256)
   copy      the one-list copy, searched with search_all at k <= 256 and with search_wide above; its build time apart
@@ -49,6 +52,8 @@ def child(a):
     means = rng.standard_normal((64, d)).astype(np.float32)
     x = means[rng.integers(0, 64, n)] + np.float32(0.35) * rng.standard_normal((n, d)).astype(np.float32)
     q = means[rng.integers(0, 64, B)] + np.float32(0.35) * rng.standard_normal((B, d)).astype(np.float32)
+    if a.rows == "normal":
+        x, q = rng.standard_normal((n, d)).astype(np.float32), rng.standard_normal((B, d)).astype(np.float32)
     ids = np.arange(n, dtype=np.uint64)
 
     def timed(fn, repeat):
@@ -112,6 +117,8 @@ def routes(a, ctx, fv, g, x, ids, q, out):
             fns[name] = lambda: g.search_exact_wide(q, k)
         elif name == "register":
             fns[name] = lambda: g.search_exact(q, k)
+        elif name == "filtered":
+            fns[name] = lambda: g.search_exact_filtered(q, k)
         else:
             ctx.device_synchronize()
             t0 = time.perf_counter()
@@ -137,7 +144,15 @@ def routes(a, ctx, fv, g, x, ids, q, out):
     for name, v in ms.items():
         v.sort()
         out["routes"][name] = dict(ms_median=v[len(v) // 2], ms_min=v[0], ms_max=v[-1], runs=len(v),
+                                   queries_per_s=B / (v[len(v) // 2] * 1e-3),
                                    rows_x_queries_per_s=n * B / (v[len(v) // 2] * 1e-3))
+    if "filtered" in fns:  # the counters are those of the last filtered call
+        info = g.exact_filter_info()
+        out["filter"] = dict(exact_pairs=info["exact_pairs"], exact_pairs_per_pair=info["exact_pairs"] / (B * n),
+                             fallback_queries=info["fallback_queries"], unbounded_queries=info["unbounded_queries"],
+                             mirror_bytes_per_row=info["mirror_bytes"] / n, mirror_build_ms=info["build_ms"],
+                             mirror_build_rows_per_s=info["build_rows"] / (info["build_ms"] * 1e-3),
+                             lds_bytes=info["lds_bytes"], queries_in_lds=info["queries_in_lds"])
     names = list(answers)
     first = answers[names[0]]
     out["identical"] = all(np.array_equal(first[0], answers[m][0]) and np.array_equal(first[2], answers[m][2]) and
@@ -154,16 +169,17 @@ def main():
     ap.add_argument("--n", type=int, default=200_000)
     ap.add_argument("--d", type=int, default=384)
     ap.add_argument("--k", type=int, default=10, help="may exceed 256 with --route wide / copy")
-    ap.add_argument("--route", action="append", choices=["wide", "register", "copy"], default=None,
-                    help="time only this route (repeatable): the routes of DESIGN.md section 9q")
+    ap.add_argument("--route", action="append", choices=["wide", "register", "copy", "filtered"], default=None,
+                    help="time only this route (repeatable): the routes of DESIGN.md sections 9q and 9z")
+    ap.add_argument("--rows", choices=["mixture", "normal"], default="mixture", help="the rows and queries drawn")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--repeat", type=int, default=9, help="timed runs per path, after one warm-up")
     ap.add_argument("--repeat-allowed", type=int, default=3, help="timed runs of the gather scan (slow), after one warm-up")
     ap.add_argument("--step-timeout", type=int, default=600, help="seconds one row element may take")
     ap.add_argument("--dtype", default=None, help="(child) run this one row element in this process")
     a = ap.parse_args()
-    if a.route and "register" in a.route and a.k > 256:
-        ap.error("--route register takes k <= 256")
+    if a.route and a.k > 256 and ("register" in a.route or "filtered" in a.route):
+        ap.error("--route register and --route filtered take k <= 256")
     if not a.route and a.k > 256:
         ap.error("k > 256 needs --route wide and / or --route copy")
     if a.dtype is not None:
@@ -172,7 +188,7 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), "--dtype", dtype]
         for name in ("n", "d", "k", "batch", "repeat"):
             cmd += [f"--{name}", str(getattr(a, name))]
-        cmd += ["--repeat-allowed", str(a.repeat_allowed)]
+        cmd += ["--repeat-allowed", str(a.repeat_allowed), "--rows", a.rows]
         for r in a.route or []:
             cmd += ["--route", r]
         try:
