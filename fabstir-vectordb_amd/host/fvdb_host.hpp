@@ -712,6 +712,13 @@ class HNSWIndex {
   // graph mirrored in HBM.  Same results; inserts always use the host walk.
   void set_device_traversal(bool on) { device_traversal_ = on; }
   bool device_traversal() const { return device_traversal_; }
+  // whether admit() sends an unfiltered traversal at this ef to the device kernel (else the host walk runs it)
+  bool walks_on_device(uint32_t ef) const;
+  // the context whose stream carries the launches of `slot` (created at first use): for work a caller puts in front of
+  // a search_dev_begin in that slot
+  fvdb_ctx* slot_stream(uint32_t slot) {
+    return slot < kSlots && slot_ctx(ctx_, slot == 0, &slots_[slot].ctx) == FVDB_OK ? slots_[slot].ctx : nullptr;
+  }
   uint64_t device_fallbacks() const { return n_fallback_.load(); }
   // profiling on: summed HIP-event duration of the traversal kernel's launches since the last call
   int graph_kernel_times(float* ms_sum, uint32_t* launches, uint64_t* rows_scored, uint64_t* hops) {
@@ -903,9 +910,9 @@ class HybridIndex {
   // enqueues everything for the batch (traversal kernel on the slot's stream, IVF chain and its result copies on
   // the IVF stream) and returns; end waits for that slot only and merges on the host.  The query buffer must stay
   // valid and unchanged until end.  Mutations between a begin and its end are not allowed.
-  // Timing of the IVF part (unsharded, no allow-set; see Pair below): begin enqueues the graph walk at once, the IVF chain
-  // of the batch may start at the NEXT begin — one chain then serves both batches — or at its own end.  Results and
-  // error codes are unchanged; an error of a chain enqueued after begin returned comes back from that batch's end.
+  // Timing (unsharded, no allow-set; see Group below): the graph walk and the IVF chain of the batch may start at a LATER
+  // begin — one walk and one chain then serve a group of batches — or at its own end.  Results and error codes are
+  // unchanged; an error of a launch enqueued after begin returned comes back from that batch's end.
   static constexpr uint32_t kSlots = HNSWIndex::kSlots;
   int search_dev_begin(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                        double now);
@@ -1109,7 +1116,7 @@ class HybridIndex {
   int begin_explicit(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                      int shard_mode, double now, const uint64_t* allowed = nullptr, uint64_t n_allowed = 0,
                      bool masked = false);
-  // may_pair: the caller is the explicit pair's begin, whose IVF chain may wait for a partner (Pair below)
+  // may_pair: the caller is the explicit pair's begin, whose walk and IVF chain may wait for partners (Group below)
   int begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint32_t dim, const HybridSearchConfig& cfg,
                  int shard_mode = -1, bool may_pair = false);
   int build_masks(const HybridSearchConfig& cfg, const uint64_t* allowed, uint64_t n_allowed, HNSWIndex::ViewRef* view,
@@ -1151,7 +1158,7 @@ class HybridIndex {
   mutable std::mutex slot_mu_;     // Slot::active
   std::condition_variable slot_cv_;
   fvdb_ctx* ctx_ivf_;
-  struct Pair;
+  struct Group;
   struct Slot {  // one batch in flight
     DevBuf ivf;             // results of the IVF part (IvfBlock layout): device block and its pinned host copy
     uint32_t ivf_rows = 0;  // rows the IVF part writes into it for this batch
@@ -1164,46 +1171,86 @@ class HybridIndex {
     // a search under an allow-set holds its masks here from begin to end
     MaskRef ivf_mask;
     HNSWIndex::ViewRef view;
-    // paired IVF chains (below): all four under pair_mu_
+    // grouped launches (below): all of these under pair_mu_
     bool ivf_waiting = false;  // the IVF chain of this batch is not enqueued yet (q, B, dim, hk, n_probe say what it is)
+    bool walk_waiting = false;  // nor its graph walk (q, B, dim, rk, ef)
     uint32_t n_probe = 0;
     int ivf_rc = FVDB_OK;      // status of an enqueue that happened after this batch's begin returned; search_dev_end's
-    Pair* pair = nullptr;      // the joint chain this batch's IVF rows come from, starting at row pair_off
+    Group* pair = nullptr;     // the joint chain this batch's IVF rows come from, starting at row pair_off
     uint32_t pair_off = 0;
+    Group* walk = nullptr;     // the joint walk its graph rows come from, starting at row walk_off
+    uint32_t walk_off = 0;
   };
   Slot slots_[kSlots];
-  // One IVF chain for two batches in flight.  A batch begun with search_dev_begin on an unsharded
-  // index without an allow-set does not enqueue its IVF chain: it waits (waiting_) for the next such begin, which
-  // enqueues ONE chain for the queries of both on its own slot's stream and scratch set, or for its own end, a blocking
-  // search or a writer, which enqueue it alone (flush_waiting).
-  // Lifetime: the joint query block, the result blocks and the event belong to the Pair, never to a slot — the slot that
-  // launched may be collected and begun again (its event re-recorded, its block rewritten) before its partner is
-  // collected.  A Pair is held by the slots that read from it (refs) and free again after the second search_dev_end.
-  struct Pair {
-    DevBuf q;    // [B1 + B2][dim], the waiting batch first
-    DevBuf res;  // IvfBlock layout over rows = B1 + B2, with its pinned host copy
+  // One graph walk and one IVF chain for a group of batches in flight (DESIGN.md sections 9o and 9o.1).  A batch begun with
+  // search_dev_begin on an unsharded index without an allow-set does not enqueue its two halves: each waits, in a list of
+  // its own (walk_wait_, ivf_wait_), for the next such begins.  The begin that fills a list (FVDB_HYBRID_GROUP: how many
+  // batches that takes, per half) enqueues ONE launch for the queries of all its members, copied side by side: the walk
+  // on the graph's stream and traversal state of its own slot, the chain on its own slot's IVF stream and scratch set.
+  // A list is two lists because membership differs: a batch searched in one half only joins that half's list, and a
+  // walk joins only while the joint batch takes the kernel form a single batch takes (walks_join).
+  // Nothing waits for ever: a begin that cannot join, a member's own end, a blocking search, a writer and attach_comm
+  // enqueue what waits first, in begin order, as one launch if it is more than one batch (flush_waiting).
+  // Lifetime: the joint query block, the result blocks and the event belong to the Group, never to a slot — the slot that
+  // launched may be collected and begun again (its event re-recorded, its block rewritten, its traversal state reused)
+  // before its partners are collected.  The first end of a walk's members collects the whole joint walk into the
+  // Group's host blocks (HNSWIndex::search_dev_end: id translation, fallbacks), which frees the traversal slot; the others
+  // read their rows.  A Group is held by the slots that read from it (refs) and free again after the last one's end.
+  struct Group {
+    DevBuf q;    // [sum of B][dim], in begin order
+    uint32_t rows = 0, refs = 0;
+    // an IVF chain
+    DevBuf res;  // IvfBlock layout over `rows`, with its pinned host copy
     fvdb_event* done = nullptr;
     fvdb_ctx* ctx = nullptr;  // the context whose stream carries the chain (the launching slot's)
-    uint32_t rows = 0, hk = 0, refs = 0;
+    uint32_t hk = 0;
+    // a graph walk
+    // collected, rc and the blocks below.  Held across the wait for the walk and a possible host fallback walk: the
+    // explicit pair is one thread's, so nobody else stands at this mutex meanwhile
+    std::mutex mu;
+    uint32_t slot = 0, dim = 0, rk = 0, ef = 0;  // what the joint search_dev_begin was given: its end is given the same
+    fvdb_ctx* walk_ctx = nullptr;                // the stream the gather copies went to (the launching slot's)
+    bool enqueued = false;                       // whether that begin enqueued the walk; if not, its end searches now
+    bool collected = false;
+    int rc = FVDB_OK;
+    std::vector<uint64_t> ids;
+    std::vector<float> dist;
+    std::vector<uint32_t> counts;
   };
-  static constexpr uint32_t kPairs = kSlots / 2;
-  static constexpr uint32_t kPairRowsMax = 16384;  // B1 + B2 of a joint chain: the largest batch the engine's parity tests run
-  // pairs can outnumber kPairs only when partners are collected far apart; a begin that finds none free does not pair
-  Pair pairs_[kPairs];
-  std::mutex pair_mu_;  // waiting_, the pool, the Slot fields above, and every enqueue of an IVF chain of the explicit pair
-  int waiting_ = -1;
-  static bool pairing_enabled();  // FVDB_HYBRID_PAIR=0 (read once) restores one chain per batch, enqueued at begin
+  static constexpr uint32_t kGroupMax = 4;         // members of a group
+  static constexpr uint32_t kGroups = kSlots;      // walks and chains draw from one pool
+  static constexpr uint32_t kPairRowsMax = 16384;  // rows of a joint launch: the largest batch the engine's parity tests run
+  // a begin that finds no Group free does not group: what waits is enqueued batch by batch
+  Group groups_[kGroups];
+  std::mutex pair_mu_;  // the two lists, the pool, the Slot fields above, and every enqueue of the explicit pair's halves
+  uint32_t walk_wait_[kGroupMax], ivf_wait_[kGroupMax];  // slots, in begin order
+  uint32_t n_walk_wait_ = 0, n_ivf_wait_ = 0;
+  struct GroupSizes {
+    uint32_t walk, chain;
+  };
+  // batches per joint launch, read once: FVDB_HYBRID_GROUP=<walk>[,<chain>] (1, 2 or 4); FVDB_HYBRID_PAIR=0 means 1,1 —
+  // one walk and one chain per batch, enqueued at begin
+  static GroupSizes group_sizes();
   // one batch alone: chain, result copy and event on the slot's own stream
   int enqueue_ivf(uint32_t slot, const float* q_dev, uint32_t B_in, uint32_t ivf_rows, uint32_t dim, uint64_t n_probe,
                   int shard_mode);
-  int enqueue_ivf_pair(Slot& first, uint32_t launcher, Pair& p);  // pair_mu_ held
-  int begin_ivf_paired(uint32_t slot);                            // takes pair_mu_
-  void flush_waiting_locked();                                    // pair_mu_ held: the waiting batch's chain, alone
+  // pair_mu_ held, all of these.  The queries of `n` waiting slots side by side in g.q, copied on ctx's stream
+  int gather_queries(Group& g, fvdb_ctx* ctx, const uint32_t* slots, uint32_t n);
+  Group* free_group();
+  int enqueue_ivf_group(Group& g);   // the list's chain, launched from its last member's slot
+  void enqueue_walk_group(Group& g);  // the list's walk, likewise
+  bool walks_join(uint32_t slot);     // the batch may join the waiting walks: same shape, same kernel form jointly
+  void flush_chains_locked();
+  void flush_walks_locked();
+  int begin_ivf_grouped(uint32_t slot);    // takes pair_mu_
+  void begin_walk_grouped(uint32_t slot);  // takes pair_mu_
   void flush_waiting() {
     std::lock_guard<std::mutex> lk(pair_mu_);
-    flush_waiting_locked();
+    flush_walks_locked();
+    flush_chains_locked();
   }
-  void release_pair(Slot& sl);  // takes pair_mu_
+  int collect_walk(Group& g);     // takes g.mu: the joint walk's results, once
+  void release_groups(Slot& sl);  // takes pair_mu_
   int stage_finite(Slot& sl, const float* q, uint32_t B, uint32_t dim);
   // A slot keeps a filtered search's masks only while that search runs: dropped at scope exit, whichever way it
   // returns, so that the next user of the slot finds none.  sl = nullptr: handed on to the search_dev_end that collects.

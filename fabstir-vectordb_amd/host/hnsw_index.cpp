@@ -495,12 +495,17 @@ int HNSWIndex::admit(Search& s) {
   if (!exact && entry_lost_) return FVDB_E_NOT_FOUND;
   if (nothing) return FVDB_OK;
   if (exact && s.view && !s.view->mask) return FVDB_OK;
-  // the scans are device kernels whatever the traversal setting; the traversal kernel has one lane per neighbour
+  // the scans are device kernels whatever the traversal setting
+  s.scanned = exact || (s.view && scans(*s.view, s.k));
+  s.route = s.scanned || walks_on_device(s.ef) ? Search::kDevice : Search::kHostWalk;
+  return FVDB_OK;
+}
+
+// the traversal kernel has one lane per neighbour
+bool HNSWIndex::walks_on_device(uint32_t ef) const {
   static const bool env_off = getenv("FVDB_HNSW_DEVICE") && atoi(getenv("FVDB_HNSW_DEVICE")) == 0;
   const uint32_t maxdeg = std::max(cfg_.max_connections, cfg_.max_connections_layer_0);
-  s.scanned = exact || (s.view && scans(*s.view, s.k));
-  s.route = s.scanned || (device_traversal_ && !env_off && maxdeg <= 64 && s.ef <= 4096) ? Search::kDevice : Search::kHostWalk;
-  return FVDB_OK;
+  return device_traversal_ && !env_off && maxdeg <= 64 && ef <= 4096;
 }
 
 int HNSWIndex::stage(Search& s) {

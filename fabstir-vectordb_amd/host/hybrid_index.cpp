@@ -19,12 +19,12 @@ HybridIndex::HybridIndex(fvdb_ctx* ctx_ivf, fvdb_ctx* ctx_hnsw, const HybridConf
 HybridIndex::~HybridIndex() {
   qual_.release();
   diverse_.release();
-  // a batch that still waits for a partner has nothing enqueued for its IVF part; joint chains in flight end with the
+  // a batch that still waits for partners has nothing enqueued for that half; joint launches in flight end with the
   // release of their blocks, as the slots' own do
-  for (Pair& p : pairs_) {
-    p.q.release();
-    p.res.release();
-    if (p.done) fvdb_event_destroy(p.done);
+  for (Group& g : groups_) {
+    g.q.release();
+    g.res.release();
+    if (g.done) fvdb_event_destroy(g.done);
   }
   for (Slot& sl : slots_) {
     sl.ivf.release();
@@ -66,7 +66,7 @@ int HybridIndex::set_ivf_centroids(const float* c, uint32_t dim) {
 int HybridIndex::write_lock(std::unique_lock<std::shared_mutex>& w) {
   for (;;) {
     w.lock();  // the blocking searches of other threads hold the read side for their whole duration: waited for here
-    flush_waiting();  // a batch whose IVF chain still waits for a partner: enqueued now, so that its collector only waits
+    flush_waiting();  // batches whose walk or IVF chain still waits for partners: enqueued now, so that their collectors only wait
     if (!busy()) return FVDB_OK;
     w.unlock();  // what is left in flight was begun with search_dev_begin and not collected yet
     if (!writers_wait_) return FVDB_E_INVALID;
@@ -632,12 +632,21 @@ static bool ivf_one_stream() {
   return on;
 }
 
-bool HybridIndex::pairing_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("FVDB_HYBRID_PAIR");  // A/B switch, read once
-    return !(v && std::strcmp(v, "0") == 0);
+HybridIndex::GroupSizes HybridIndex::group_sizes() {
+  static const GroupSizes g = [] {
+    GroupSizes s{2, 2};  // what the measurements before the change supported
+    const char* v = getenv("FVDB_HYBRID_PAIR");  // A/B switches, read once
+    if (v && std::strcmp(v, "0") == 0) return GroupSizes{1, 1};
+    auto valid = [](unsigned x) { return x == 1 || x == 2 || x == kGroupMax; };
+    unsigned w = 0, c = 0;
+    if ((v = getenv("FVDB_HYBRID_GROUP"))) {
+      const int n = std::sscanf(v, "%u,%u", &w, &c);
+      if (n >= 1 && valid(w)) s.walk = w;  // the chain's size, left out, stays the default
+      if (n == 2 && valid(w) && valid(c)) s.chain = c;
+    }
+    return s;
   }();
-  return on;
+  return g;
 }
 
 // The IVF chain of one batch on the slot's own stream with its own scratch set, the result copy right behind it, then
@@ -681,78 +690,211 @@ int HybridIndex::enqueue_ivf(uint32_t slot, const float* q_dev, uint32_t B_in, u
   return FVDB_OK;
 }
 
-// One chain for the waiting batch `first` and the batch of slot `launcher`, on the launcher's stream with its scratch
-// set, into the Pair's own blocks.  pair_mu_ held.
-int HybridIndex::enqueue_ivf_pair(Slot& first, uint32_t launcher, Pair& p) {
+// ---- grouped launches (fvdb_host.hpp, Group; DESIGN.md sections 9o and 9o.1); pair_mu_ held unless said ----
+HybridIndex::Group* HybridIndex::free_group() {
+  for (Group& g : groups_)
+    if (g.refs == 0) return &g;
+  return nullptr;
+}
+
+int HybridIndex::gather_queries(Group& g, fvdb_ctx* ctx, const uint32_t* slots, uint32_t n) {
+  const uint32_t dim = slots_[slots[0]].dim;
+  uint32_t rows = 0;
+  for (uint32_t i = 0; i < n; ++i) rows += slots_[slots[i]].B;
+  if (int rc = g.q.reserve(ctx_ivf_, (uint64_t)rows * dim * 4, false)) return rc;
+  float* q = (float*)g.q.dev;
+  for (uint32_t i = 0; i < n; ++i) {
+    const Slot& m = slots_[slots[i]];
+    if (fvdb_dev_copy_async(ctx, q, m.q, (size_t)m.B * dim * 4)) return FVDB_E_HIP;
+    q += (size_t)m.B * dim;
+  }
+  g.rows = rows;
+  return FVDB_OK;
+}
+
+// One chain for the waiting batches, on the stream of the last one's slot with its scratch set, into the Group's own
+// blocks.
+int HybridIndex::enqueue_ivf_group(Group& g) {
+  const uint32_t n = n_ivf_wait_, launcher = ivf_wait_[n - 1];
   Slot& sl = slots_[launcher];
-  const uint32_t rows = first.B + sl.B, dim = sl.dim;
-  const uint64_t bytes = IvfBlock::bytes(rows, sl.hk);
-  if (int rc = p.q.reserve(ctx_ivf_, (uint64_t)rows * dim * 4, false)) return rc;
-  if (int rc = p.res.reserve(ctx_ivf_, bytes, true)) return rc;
   if (slot_ctx(ctx_ivf_, launcher == 0 || ivf_one_stream(), &sl.ivf_ctx)) return FVDB_E_HIP;
   fvdb_ctx* on = sl.ivf_ctx == ctx_ivf_ ? nullptr : sl.ivf_ctx;
-  if (!p.done && fvdb_event_create(sl.ivf_ctx, &p.done)) return FVDB_E_HIP;
-  float* q = (float*)p.q.dev;
-  if (fvdb_dev_copy_async(sl.ivf_ctx, q, first.q, (size_t)first.B * dim * 4) ||
-      fvdb_dev_copy_async(sl.ivf_ctx, q + (size_t)first.B * dim, sl.q, (size_t)sl.B * dim * 4))
+  if (int rc = gather_queries(g, sl.ivf_ctx, ivf_wait_, n)) return rc;
+  const uint64_t bytes = IvfBlock::bytes(g.rows, sl.hk);
+  if (int rc = g.res.reserve(ctx_ivf_, bytes, true)) return rc;
+  if (!g.done && fvdb_event_create(sl.ivf_ctx, &g.done)) return FVDB_E_HIP;
+  const IvfBlock d(g.res.dev, g.rows, sl.hk);
+  if (int rc = historical_->search_dev((const float*)g.q.dev, g.rows, sl.dim, sl.hk, sl.n_probe, d.ids, d.dist, d.counts, on,
+                                       on ? launcher : 0))
+    return rc;
+  if (fvdb_dev_download_async(sl.ivf_ctx, g.res.host, g.res.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, g.done))
     return FVDB_E_HIP;
-  const IvfBlock d(p.res.dev, rows, sl.hk);
-  if (int rc = historical_->search_dev(q, rows, dim, sl.hk, sl.n_probe, d.ids, d.dist, d.counts, on, on ? launcher : 0)) return rc;
-  if (fvdb_dev_download_async(sl.ivf_ctx, p.res.host, p.res.dev, (size_t)bytes) || fvdb_event_record(sl.ivf_ctx, p.done))
-    return FVDB_E_HIP;
-  p.ctx = sl.ivf_ctx;
-  p.rows = rows;
-  p.hk = sl.hk;
-  p.refs = 2;
-  first.pair = sl.pair = &p;
-  first.pair_off = 0;
-  sl.pair_off = first.B;
-  first.ivf_in_flight = sl.ivf_in_flight = true;
+  g.ctx = sl.ivf_ctx;
+  g.hk = sl.hk;
+  uint32_t off = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    Slot& m = slots_[ivf_wait_[i]];
+    m.pair = &g;
+    m.pair_off = off;
+    m.ivf_in_flight = true;
+    off += m.B;
+    g.refs += 1;
+  }
   return FVDB_OK;
 }
 
-// pair_mu_ held: the waiting batch goes alone, on its own slot's stream; what that returns is its search_dev_end's
-void HybridIndex::flush_waiting_locked() {
-  if (waiting_ < 0) return;
-  Slot& w = slots_[waiting_];
-  w.ivf_waiting = false;
-  w.ivf_rc = enqueue_ivf((uint32_t)waiting_, w.q, w.B, w.B, w.dim, w.n_probe, -1);
-  waiting_ = -1;
+// What waits goes now, in begin order: one batch alone on its own slot's stream, several as one chain.  What the enqueue
+// returns is every member's search_dev_end's to report, unless the caller is the begin of one of them.
+void HybridIndex::flush_chains_locked() {
+  const uint32_t n = n_ivf_wait_;
+  if (n == 0) return;
+  Group* g = n > 1 ? free_group() : nullptr;
+  if (g) {
+    const int rc = enqueue_ivf_group(*g);  // nothing of a joint chain that failed is collected
+    for (uint32_t i = 0; i < n; ++i) slots_[ivf_wait_[i]].ivf_rc = rc;
+  } else {
+    for (uint32_t i = 0; i < n; ++i) {
+      Slot& w = slots_[ivf_wait_[i]];
+      w.ivf_rc = enqueue_ivf(ivf_wait_[i], w.q, w.B, w.B, w.dim, w.n_probe, -1);
+    }
+  }
+  for (uint32_t i = 0; i < n; ++i) slots_[ivf_wait_[i]].ivf_waiting = false;
+  n_ivf_wait_ = 0;
 }
 
-// The IVF part of an explicit begin that may share its chain: with the waiting batch if there is a compatible one (same
-// dim, historical k and n_probe; the index cannot have changed, both slots being in flight), else this batch waits.
-int HybridIndex::begin_ivf_paired(uint32_t slot) {
+// The IVF part of an explicit begin that may share its chain: it joins the waiting batches if it is compatible with them
+// (same dim, historical k and n_probe; the index cannot have changed, all the slots being in flight), else they go first.
+// The batch that fills the group enqueues the chain and reports its status.
+int HybridIndex::begin_ivf_grouped(uint32_t slot) {
   Slot& sl = slots_[slot];
   std::lock_guard<std::mutex> lk(pair_mu_);
-  if (waiting_ >= 0) {
-    Slot& w = slots_[waiting_];
-    Pair* p = nullptr;
-    if (w.dim == sl.dim && w.hk == sl.hk && w.n_probe == sl.n_probe && (uint64_t)w.B + sl.B <= kPairRowsMax)
-      for (Pair& c : pairs_)
-        if (c.refs == 0) {
-          p = &c;
-          break;
-        }
-    if (p) {
-      w.ivf_waiting = false;
-      waiting_ = -1;
-      const int rc = enqueue_ivf_pair(w, slot, *p);
-      if (rc) w.ivf_rc = rc;  // nothing of a joint chain that failed is collected, and each batch reports the status
-      return rc;
-    }
-    flush_waiting_locked();
+  if (n_ivf_wait_) {
+    const Slot& w = slots_[ivf_wait_[0]];
+    uint64_t rows = sl.B;
+    for (uint32_t i = 0; i < n_ivf_wait_; ++i) rows += slots_[ivf_wait_[i]].B;
+    if (!(w.dim == sl.dim && w.hk == sl.hk && w.n_probe == sl.n_probe && rows <= kPairRowsMax && free_group()))
+      flush_chains_locked();
   }
   sl.ivf_waiting = true;
-  waiting_ = (int)slot;
-  return FVDB_OK;
+  ivf_wait_[n_ivf_wait_++] = slot;
+  if (n_ivf_wait_ < group_sizes().chain) return FVDB_OK;
+  flush_chains_locked();
+  const int rc = sl.ivf_rc;
+  sl.ivf_rc = FVDB_OK;
+  return rc;
 }
 
-void HybridIndex::release_pair(Slot& sl) {
+// One walk for the waiting batches, in the graph's slot of the last one: its stream, its traversal state, its result
+// block.  Whether the launch succeeded is the collection's to find out, as it is for a batch alone.
+void HybridIndex::enqueue_walk_group(Group& g) {
+  const uint32_t n = n_walk_wait_, launcher = walk_wait_[n - 1];
+  const Slot& sl = slots_[launcher];
+  g.slot = launcher, g.dim = sl.dim, g.rk = sl.rk, g.ef = sl.ef;
+  g.collected = false;
+  g.rc = FVDB_OK;
+  fvdb_ctx* stream = recent_->slot_stream(launcher);
+  int rc = stream ? gather_queries(g, stream, walk_wait_, n) : FVDB_E_HIP;
+  g.walk_ctx = stream;
+  g.enqueued = false;
+  if (!rc) {
+    int rcb = 0;
+    g.enqueued = recent_->search_dev_begin((const float*)g.q.dev, g.rows, g.dim, g.rk, g.ef, &rcb, launcher, nullptr);
+  } else {
+    g.collected = true;  // no joint block to walk: every member reports the failure
+    g.rc = rc;
+  }
+  uint32_t off = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    Slot& m = slots_[walk_wait_[i]];
+    m.walk = &g;
+    m.walk_off = off;
+    m.hnsw_in_flight = true;
+    off += m.B;
+    g.refs += 1;
+  }
+}
+
+void HybridIndex::flush_walks_locked() {
+  const uint32_t n = n_walk_wait_;
+  if (n == 0) return;
+  Group* g = n > 1 ? free_group() : nullptr;
+  if (g) {
+    enqueue_walk_group(*g);
+  } else {
+    for (uint32_t i = 0; i < n; ++i) {
+      Slot& w = slots_[walk_wait_[i]];
+      int rcb = 0;
+      w.hnsw_in_flight = recent_->search_dev_begin(w.q, w.B, w.dim, w.rk, w.ef, &rcb, walk_wait_[i], nullptr);
+    }
+  }
+  for (uint32_t i = 0; i < n; ++i) slots_[walk_wait_[i]].walk_waiting = false;
+  n_walk_wait_ = 0;
+}
+
+// A walk joins the waiting ones only if one launch can serve them all: the same dim, recent k and ef, and the joint batch
+// planned in the kernel form a batch alone is planned in (the byte-per-node visited map while the batch's maps fit its
+// limit: a launch in another form would re-size the traversal state of the walks in flight).  And only what the
+// launching slot of the graph runs as a device kernel: a search the host walk takes, or rows of a padded dimension
+// (the engine serves those in slot 0 alone), goes batch by batch from its own query buffer, as ever.
+bool HybridIndex::walks_join(uint32_t slot) {
+  const Slot& sl = slots_[slot];
+  if (sl.dim % 4 != 0 || !recent_->walks_on_device(sl.ef)) return false;
+  fvdb_graph* graph = recent_->device_graph();
+  if (!graph) return false;
+  uint64_t rows = sl.B;
+  for (uint32_t i = 0; i < n_walk_wait_; ++i) {
+    const Slot& w = slots_[walk_wait_[i]];
+    if (!(w.dim == sl.dim && w.rk == sl.rk && w.ef == sl.ef)) return false;
+    rows += w.B;
+  }
+  if (rows > kPairRowsMax || !free_group()) return false;
+  fvdb_graph_search_info_t one, all;
+  if (fvdb_graph_search_info(graph, sl.B, sl.ef, &one) || fvdb_graph_search_info(graph, (uint32_t)rows, sl.ef, &all)) return false;
+  return one.visited == all.visited && one.kernel == all.kernel && one.rows_per_round == all.rows_per_round &&
+         one.tcap == all.tcap;
+}
+
+// The graph walk of an explicit begin that may share its launch; the batch that fills the group enqueues it.
+void HybridIndex::begin_walk_grouped(uint32_t slot) {
+  Slot& sl = slots_[slot];
   std::lock_guard<std::mutex> lk(pair_mu_);
-  if (!sl.pair) return;
-  sl.pair->refs -= 1;
-  sl.pair = nullptr;
+  if (!walks_join(slot)) {
+    flush_walks_locked();
+    if (!walks_join(slot)) {  // not even alone in a group's form (host traversal, no device graph yet): at once, as ever
+      int rcb = 0;
+      sl.hnsw_in_flight = recent_->search_dev_begin(sl.q, sl.B, sl.dim, sl.rk, sl.ef, &rcb, slot, nullptr);
+      return;
+    }
+  }
+  sl.walk_waiting = true;
+  walk_wait_[n_walk_wait_++] = slot;
+  if (n_walk_wait_ >= group_sizes().walk) flush_walks_locked();
+}
+
+// The first of a joint walk's members to be collected waits for it and takes the whole of it to the host.
+int HybridIndex::collect_walk(Group& g) {
+  std::lock_guard<std::mutex> lk(g.mu);
+  if (g.collected) return g.rc;
+  g.ids.resize((size_t)g.rows * g.rk);
+  g.dist.resize((size_t)g.rows * g.rk);
+  g.counts.assign(g.rows, 0);
+  // a launch that was refused: the end searches the joint block again on another stream, or takes it to the host, so
+  // the copies that fill the block must have finished
+  if (!g.enqueued && fvdb_ctx_synchronize(g.walk_ctx)) {
+    g.collected = true;
+    return g.rc = FVDB_E_HIP;
+  }
+  g.rc = recent_->search_dev_end((const float*)g.q.dev, g.rows, g.dim, g.rk, g.ef, g.ids.data(), g.dist.data(), g.counts.data(),
+                                 g.slot, nullptr);
+  g.collected = true;
+  return g.rc;
+}
+
+void HybridIndex::release_groups(Slot& sl) {
+  std::lock_guard<std::mutex> lk(pair_mu_);
+  if (sl.pair) sl.pair->refs -= 1;
+  if (sl.walk) sl.walk->refs -= 1;
+  sl.pair = sl.walk = nullptr;
 }
 
 // enqueue everything for the batch; the slot is already marked active by the caller
@@ -785,25 +927,36 @@ int HybridIndex::begin_impl(uint32_t slot, const float* q_dev, uint32_t B, uint3
   if (cfg.search_recent && B > 0) {
     // the graph walk is latency-bound (one wave per query): enqueue it FIRST so that the list scan launched
     // next fills the rest of every SIMD and the two run concurrently
-    int rcb = 0;
-    sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot, sl.view.get());
+    // The explicit pair on an unsharded index without an allow-set: the walk may be shared with the next batches begun
+    // (begin_walk_grouped decides; the launch that serves the group still goes in front of the group's chain).
+    if (may_pair && group_sizes().walk > 1 && shard_mode < 0 && !sharded_ && !sl.view) {
+      begin_walk_grouped(slot);
+    } else {
+      std::unique_lock<std::mutex> lk(pair_mu_, std::defer_lock);
+      if (may_pair) {  // an explicit begin that cannot share: the walks still start in the order their batches were begun
+        lk.lock();
+        flush_walks_locked();
+      }
+      int rcb = 0;
+      sl.hnsw_in_flight = recent_->search_dev_begin(q_own, B, dim, sl.rk, sl.ef, &rcb, slot, sl.view.get());
+    }
   }
   if (cfg.search_historical && ivf_trained_) {
     sl.n_probe = (uint32_t)cfg.ivf_n_probe;
     // The explicit pair on an unsharded index without an allow-set, inside the register path's k and n_probe (the route
-    // every batch size takes alike): the chain may be shared with the next batch begun.  A dimension the engine would
+    // every batch size takes alike): the chain may be shared with the next batches begun.  A dimension the engine would
     // refuse is refused now, as ever; what is left to fail later is the enqueue itself.
-    const bool pairable = may_pair && pairing_enabled() && shard_mode < 0 && !sharded_ && !sl.ivf_mask && B > 0 &&
+    const bool pairable = may_pair && group_sizes().chain > 1 && shard_mode < 0 && !sharded_ && !sl.ivf_mask && B > 0 &&
                           sl.hk <= FVDB_MAX_K && cfg.ivf_n_probe > 0 &&
                           std::min<uint64_t>(cfg.ivf_n_probe, historical_->config().n_clusters) <= FVDB_MAX_K;
     if (pairable) {
       if (dim != historical_->dimension()) return FVDB_E_DIM;
-      return begin_ivf_paired(slot);
+      return begin_ivf_grouped(slot);
     }
     std::unique_lock<std::mutex> lk(pair_mu_, std::defer_lock);
     if (may_pair) {  // an explicit begin that cannot share: the chains still start in the order their batches were begun
       lk.lock();
-      flush_waiting_locked();
+      flush_chains_locked();
     }
     return enqueue_ivf(slot, q_dev, B_ivf_in, ivf_rows, dim, cfg.ivf_n_probe, shard_mode);
   }
@@ -821,29 +974,42 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
   fill_empty(ids, dist, counts, B, k);
   if (!initialized_ || B == 0 || k == 0) return FVDB_OK;
   {
-    // still waiting for a partner: its chain goes alone now, on its own slot's stream
+    // still waiting for partners: what waits goes now, in begin order, this batch's halves with it
     std::lock_guard<std::mutex> lk(pair_mu_);
-    if (sl.ivf_waiting) flush_waiting_locked();
+    if (sl.walk_waiting || sl.ivf_waiting) flush_walks_locked();  // a walk still goes in front of a chain begun before it
+    if (sl.ivf_waiting) flush_chains_locked();
   }
-  // the joint chain's blocks are the Pair's: given up when this batch has read its rows, whichever way this returns
-  struct DropPair {
+  // the joint launches' blocks are their Groups': given up when this batch has read its rows, whichever way this returns
+  struct DropGroups {
     HybridIndex* h;
     Slot* sl;
-    ~DropPair() { h->release_pair(*sl); }
-  } drop_pair{this, &sl};
+    ~DropGroups() { h->release_groups(*sl); }
+  } drop_groups{this, &sl};
   std::vector<uint64_t> rid;
   std::vector<float> rd;
-  std::vector<uint32_t> rc_(B, 0);
+  std::vector<uint32_t> rc_;
+  const uint64_t* r_ids = nullptr;
+  const float* r_dist = nullptr;
+  const uint32_t* r_counts = nullptr;
   bool have_r = false, have_h = false;
-  if (sl.recent) {
+  if (sl.recent && sl.walk) {  // this batch's rows of the joint walk
+    Group& g = *sl.walk;
+    if ((have_r = collect_walk(g) == FVDB_OK)) {
+      r_ids = g.ids.data() + (size_t)sl.walk_off * g.rk;
+      r_dist = g.dist.data() + (size_t)sl.walk_off * g.rk;
+      r_counts = g.counts.data() + sl.walk_off;
+    }
+  } else if (sl.recent) {
     rid.resize((size_t)B * sl.rk);
     rd.resize((size_t)B * sl.rk);
+    rc_.assign(B, 0);
     // the graph's slot remembers whether the begin enqueued anything; if not, this is the blocking search
     have_r = recent_->search_dev_end(sl.q, B, sl.dim, sl.rk, sl.ef, rid.data(), rd.data(), rc_.data(), slot, sl.view.get()) == FVDB_OK;
+    r_ids = rid.data(), r_dist = rd.data(), r_counts = rc_.data();
   }
   IvfBlock h;
   if (sl.ivf_in_flight) {
-    if (const Pair* p = sl.pair) {  // this batch's rows of the joint block
+    if (const Group* p = sl.pair) {  // this batch's rows of the joint block
       have_h = fvdb_event_wait(p->ctx, p->done) == FVDB_OK;
       const IvfBlock all(p->res.host, p->rows, p->hk);
       h.ids = all.ids + (size_t)sl.pair_off * p->hk;
@@ -860,8 +1026,7 @@ int HybridIndex::search_dev_end(uint32_t slot, uint64_t* ids, float* dist, uint3
     }
     if (!others) fvdb_ivf_profile_collect(historical_->device());  // stage timing only makes sense one batch at a time
   }
-  merge_parts(B, k, sl.rk, sl.hk, have_r, rid.data(), rd.data(), rc_.data(), have_h, h.ids, h.dist, h.counts, ids, dist,
-              counts);
+  merge_parts(B, k, sl.rk, sl.hk, have_r, r_ids, r_dist, r_counts, have_h, h.ids, h.dist, h.counts, ids, dist, counts);
   const int late = sl.ivf_rc;  // of a chain enqueued after this batch's begin had returned; FVDB_OK otherwise
   sl.ivf_rc = FVDB_OK;
   return late;
