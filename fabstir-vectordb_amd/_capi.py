@@ -87,6 +87,14 @@ class SQ8Info(C.Structure):
 SQ8_NO_REFINE, SQ8_REFINE_DECODED, SQ8_REFINE_ROWS = -1, 0, 1  # FVDB_SQ8_*
 
 
+class IVFSQ8Info(C.Structure):
+    """fvdb_ivfsq8_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("d", "d_padded", "nlist", "block_rows", "queries_per_item", "round_rows", "words_in_flight",
+                                   "max_segments", "segb", "segments", "max_list_blocks", "lds_limit")] + \
+               [("queries_in_lds", u32 * 3), ("lds_bytes", u32 * 3)] + \
+               [(n, u32) for n in ("max_d", "max_k", "max_nprobe", "max_nlist", "item_bound")] + \
+               [(n, u64) for n in ("pool_blocks", "rows_scored", "items")]
+
 
 class CosInfo(C.Structure):
     """fvdb_cos_info_t (include/fvdb.h)."""
@@ -345,6 +353,20 @@ SIGNATURES = {
     "fvdb_cos_index_info": (i32, [vp, C.POINTER(CosInfo)]),
     "fvdb_cos_index_search": (i32, [vp, f32p, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
     "fvdb_cos_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, i32, vp, vp, vp, vp]),
+    "fvdb_ivfsq8_create": (i32, [vp, u32, u32, i32, C.POINTER(vp)]),
+    "fvdb_ivfsq8_destroy": (None, [vp]),
+    "fvdb_ivfsq8_train": (i32, [vp, f32p, u64, u32, u64, C.POINTER(TrainResult)]),
+    "fvdb_ivfsq8_set_centroids": (i32, [vp, f32p]),
+    "fvdb_ivfsq8_get_centroids": (i32, [vp, f32p]),
+    "fvdb_ivfsq8_add": (i32, [vp, u64p, f32p, u64]),
+    "fvdb_ivfsq8_set_deleted": (i32, [vp, u64p, u64, i32]),
+    "fvdb_ivfsq8_rows": (u64, [vp]),
+    "fvdb_ivfsq8_live": (u64, [vp]),
+    "fvdb_ivfsq8_bytes": (u64, [vp]),
+    "fvdb_ivfsq8_list_sizes": (i32, [vp, u64p]),
+    "fvdb_ivfsq8_info": (i32, [vp, C.POINTER(IVFSQ8Info)]),
+    "fvdb_ivfsq8_search": (i32, [vp, f32p, u32, u32, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
+    "fvdb_ivfsq8_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

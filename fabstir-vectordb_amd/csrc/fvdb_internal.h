@@ -71,6 +71,10 @@ struct fvdb_scorer {
   DBuf s_rows, s_in;  // private scratch: scorers are driven from different host threads
 };
 
+// SQ8's refusal of rows and queries (fvdb_sq8.cpp): every element finite and every row's hi - lo finite in f32, else
+// FVDB_E_NONFINITE
+int sq8_check_rows(fvdb_ctx* ctx, const float* x, uint64_t n, uint32_t d);
+
 // ---- allow-set masks (allow_masks.h) ---------------------------------------------------------
 // A mask is a second liveness view of one index: pool words for an IVF index, per-node flags and the ascending list
 // of allowed live nodes for a graph.  It is immutable once created and owns its buffers, so searches in any number of

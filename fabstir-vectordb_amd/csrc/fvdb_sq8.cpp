@@ -16,14 +16,8 @@
 
 using namespace fvdb;
 
-namespace {
-
-constexpr uint32_t kSq8Slots = 16;
-constexpr uint32_t kSq8SubBatch = 8192;        // queries of one launch chain, a multiple of the 32-query tile
-constexpr uint32_t kSq8MinSliceBlocks = 16;    // 512 rows: a slice shorter than this does not pay for its partial list
-constexpr size_t kSq8DecodedBytes = 256u << 20;  // decoded candidate rows of one launch chain
-
 // every element finite and every row's hi - lo finite in f32: what encode refuses before anything is written
+// (declared in fvdb_internal.h: the probed index, fvdb_ivfsq8.cpp, refuses the same rows)
 int sq8_check_rows(fvdb_ctx* ctx, const float* x, uint64_t n, uint32_t d) {
   for (uint64_t r = 0; r < n; ++r) {
     const float* row = x + r * d;
@@ -37,6 +31,13 @@ int sq8_check_rows(fvdb_ctx* ctx, const float* x, uint64_t n, uint32_t d) {
   }
   return FVDB_OK;
 }
+
+namespace {
+
+constexpr uint32_t kSq8Slots = 16;
+constexpr uint32_t kSq8SubBatch = 8192;        // queries of one launch chain, a multiple of the 32-query tile
+constexpr uint32_t kSq8MinSliceBlocks = 16;    // 512 rows: a slice shorter than this does not pay for its partial list
+constexpr size_t kSq8DecodedBytes = 256u << 20;  // decoded candidate rows of one launch chain
 
 // host memory to the device on the stream, complete on return (the source may be pageable and short-lived)
 hipError_t upload(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes) {

@@ -51,12 +51,14 @@ struct Sq8EncodeArgs {
   float* flat_hi;
   uint4* blocks;      // the index form above, with info[row] = (lo, range, C1, C2); or null
   uint4* info;
+  const uint32_t* dest;  // [n] index row of every source row (kernels_ivfsq8.h: a row goes to its list's block); null: first + r
+  uint32_t per_row;      // non-zero: blocks is [row][2 ksteps] words, a row's words together (the probed scan's query form)
 };
 
 // A lane takes dims 16 c .. 16 c + 15 of chunk c = lane, lane + 64: its codes are one 16-byte word of the index form.
 // All in f32, no FMA: code = round_half_away((v - lo) / range * 255), the division first; range == 0: every code 0.
 // Of equal extremes the earliest dim is kept (it decides the sign of a zero lo).
-__global__ __launch_bounds__(256) void sq8_encode_kernel(const Sq8EncodeArgs a) {
+static __global__ __launch_bounds__(256) void sq8_encode_kernel(const Sq8EncodeArgs a) {
   const int lane = threadIdx.x & 63;
   const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= a.n) return;  // whole waves leave; no barrier below
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void sq8_encode_kernel(const Sq8EncodeArgs a) 
     }
   }
   const float range = mx - mn;
-  const uint64_t idx = a.first + r;
+  const uint64_t idx = a.dest ? (uint64_t)a.dest[r] : a.first + r;
   uint32_t s1 = 0, s2 = 0;
   const uint32_t words = a.blocks ? 2u * a.ksteps : chunks;  // the index form writes its pad word too
   for (uint32_t c = (uint32_t)lane; c < words; c += 64) {
@@ -117,7 +119,8 @@ __global__ __launch_bounds__(256) void sq8_encode_kernel(const Sq8EncodeArgs a) 
       }
     }
     if (a.blocks)
-      a.blocks[((size_t)(idx >> 5) * a.ksteps + (c >> 1)) * 64 + (c & 1u) * 32u + (uint32_t)(idx & 31u)] = make_uint4(w[0], w[1], w[2], w[3]);
+      a.blocks[a.per_row ? (size_t)idx * words + c : ((size_t)(idx >> 5) * a.ksteps + (c >> 1)) * 64 + (c & 1u) * 32u + (uint32_t)(idx & 31u)] =
+          make_uint4(w[0], w[1], w[2], w[3]);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -140,7 +143,7 @@ __device__ __forceinline__ float sq8_value(float lo, float range, uint32_t code)
 }
 
 // one thread per output float
-__global__ void sq8_decode_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lo, const float* __restrict__ hi, uint32_t d,
+static __global__ void sq8_decode_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ lo, const float* __restrict__ hi, uint32_t d,
                                   uint64_t n, float* __restrict__ out) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * d) return;
@@ -150,7 +153,7 @@ __global__ void sq8_decode_kernel(const uint8_t* __restrict__ codes, const float
 }
 
 // candidate slot (b, j) of a refined search -> out[b * fk + j][dpad], zero beyond d; slots beyond the count are skipped
-__global__ void sq8_decode_cand_kernel(const uint4* __restrict__ blocks, const uint4* __restrict__ info, uint32_t ksteps, uint32_t d,
+static __global__ void sq8_decode_cand_kernel(const uint4* __restrict__ blocks, const uint4* __restrict__ info, uint32_t ksteps, uint32_t d,
                                        uint32_t dpad, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ cand_cnt, uint32_t B,
                                        uint32_t fk, float* __restrict__ out) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -220,6 +223,65 @@ __device__ __forceinline__ void sq8_select(const uint64_t* buf, uint32_t cnt, ui
   }
 }
 
+// The symmetric score of include/fvdb.h, the one text of it for the flat scan below and the probed scan
+// (kernels_ivfsq8.h).  A row's record gives its terms once; a query's are qd[0..3] = lo_q, sq A1, (sq sq) A2, 2 sq and A1.
+struct Sq8RowTerms {
+  double lo, s, s1, s2;  // lo_r, sr, sr C1, (sr sr) C2
+  int32_t fix;           // 128 C1 - 16384 d: with 128 A1, what turns the signed product sum into the unsigned one; |.| < 2^26
+};
+__device__ __forceinline__ Sq8RowTerms sq8_row_terms(const uint4 inf, uint32_t d) {
+  Sq8RowTerms t;
+  t.lo = (double)__uint_as_float(inf.x);
+  t.s = (double)__uint_as_float(inf.y) / 255.0;
+  t.s1 = t.s * (double)inf.z;
+  t.s2 = (t.s * t.s) * (double)inf.w;
+  t.fix = 128 * (int32_t)inf.z - 16384 * (int32_t)d;
+  return t;
+}
+// bits of dist for one accumulator; dd = (double)d
+__device__ __forceinline__ uint32_t sq8_score_bits(int32_t acc, int32_t a1, const double* qd, const Sq8RowTerms& t, double dd) {
+  const int32_t P = acc + 128 * a1 + t.fix;  // the unsigned product sum, < 2^27
+  const double dl = qd[0] - t.lo;
+  const double S = (((dd * dl) * dl + (2.0 * dl) * (qd[1] - t.s1)) + (qd[2] + t.s2)) - (qd[3] * t.s) * (double)P;
+  return __float_as_uint(sqrtf((float)(S > 0.0 ? S : 0.0)));
+}
+// a query's scalars from its record (lo, range, A1, A2), by the thread that owns slot t
+__device__ __forceinline__ void sq8_query_terms(const uint4 qi, uint32_t t, double* s_qd, int32_t* s_a1) {
+  const double sq = (double)__uint_as_float(qi.y) / 255.0;
+  s_qd[4 * t + 0] = (double)__uint_as_float(qi.x);
+  s_qd[4 * t + 1] = sq * (double)qi.z;
+  s_qd[4 * t + 2] = (sq * sq) * (double)qi.w;
+  s_qd[4 * t + 3] = 2.0 * sq;
+  s_a1[t] = (int32_t)qi.z;
+}
+
+// Between a round's two barriers wave w looks at buffers 8 w .. 8 w + 7: one holding more than 64 KR keys is cut to
+// its k best (the buffer then starts with that sorted list, and a bound other than "none" says so) and the bound
+// becomes the k-th distance.
+template <int KR>
+__device__ __forceinline__ void sq8_cut_round(uint64_t* s_buf, uint32_t* s_cnt, uint32_t* s_bound, uint32_t w, uint32_t k, int lane) {
+  constexpr uint32_t CAP = KR * 64u + kSq8RoundRows;
+#pragma unroll 1
+  for (uint32_t j = 0; j < 8; ++j) {
+    const uint32_t qi = w * 8u + j;
+    const uint32_t cnt = rfl(s_cnt[qi]);
+    if (cnt > KR * 64u) {  // wave-uniform
+      WaveTopK<KR> tk;
+      uint32_t th;
+      sq8_select<KR>(s_buf + qi * CAP, cnt, rfl(s_bound[qi]) != kInf32 ? k : 0u, k, lane, tk, th);
+#pragma unroll
+      for (int rr = 0; rr < KR; ++rr) {
+        const uint32_t e = rr * 64 + lane;
+        if (e < k) s_buf[qi * CAP + e] = ((uint64_t)tk.hi[rr] << 32) | tk.lo[rr];
+      }
+      if (lane == 0) {
+        s_cnt[qi] = k;  // cnt > 64 KR >= k
+        s_bound[qi] = th;
+      }
+    }
+  }
+}
+
 // Workgroup = 4 waves, one tile of 32 queries (grid x) and one contiguous slice of row blocks (grid y), a quarter of it
 // per wave.  The A operand is the query tile (M = query), the B operand a row block (N = row), so a lane's 16
 // accumulators are 16 queries against ONE row: the row's record sits in registers, the queries' scalars are LDS
@@ -250,14 +312,9 @@ __global__ __launch_bounds__(256) void sq8_scan_kernel(const Sq8ScanArgs a) {
     const uint32_t t = threadIdx.x;
     uint4 qi = make_uint4(0u, 0u, 0u, 0u);
     if (t < nq) qi = a.qinfo[q0 + t];
-    const double sq = (double)__uint_as_float(qi.y) / 255.0;
-    s_qd[4 * t + 0] = (double)__uint_as_float(qi.x);
-    s_qd[4 * t + 1] = sq * (double)qi.z;
-    s_qd[4 * t + 2] = (sq * sq) * (double)qi.w;
-    s_qd[4 * t + 3] = 2.0 * sq;
+    sq8_query_terms(qi, t, s_qd, s_a1);
     s_cnt[t] = 0u;
     s_bound[t] = kInf32;
-    s_a1[t] = (int32_t)qi.z;
   }
   if (QLDS)
     for (uint32_t e = threadIdx.x; e < a.ksteps * 64u; e += 256) ((uint4*)s_q)[e] = qg[e];
@@ -305,22 +362,12 @@ __global__ __launch_bounds__(256) void sq8_scan_kernel(const Sq8ScanArgs a) {
 
       const uint32_t row = (wb0 + r) * 32u + ((uint32_t)lane & 31u);
       if (row < a.n && a.dead[row] == 0u) {
-        const uint4 inf = a.info[row];
-        const double lo_r = (double)__uint_as_float(inf.x);
-        const double sr = (double)__uint_as_float(inf.y) / 255.0;
-        const double src1 = sr * (double)inf.z;
-        const double sr2c2 = (sr * sr) * (double)inf.w;
-        const int32_t fix = 128 * (int32_t)inf.z - 16384 * (int32_t)a.d;  // |.| < 2^26
+        const Sq8RowTerms rt = sq8_row_terms(a.info[row], a.d);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const uint32_t qi = (uint32_t)(reg & 3) + 8u * (uint32_t)(reg >> 2) + 4u * h;
           if (qi < nq) {
-            const int32_t P = acc[reg] + 128 * s_a1[qi] + fix;  // the unsigned product sum, < 2^27
-            const double* qd = s_qd + 4 * qi;
-            const double dl = qd[0] - lo_r;
-            const double S = (((dd * dl) * dl + (2.0 * dl) * (qd[1] - src1)) + (qd[2] + sr2c2)) - (qd[3] * sr) * (double)P;
-            const float dist = sqrtf((float)(S > 0.0 ? S : 0.0));
-            const uint32_t chi = __float_as_uint(dist);
+            const uint32_t chi = sq8_score_bits(acc[reg], s_a1[qi], s_qd + 4 * qi, rt, dd);
             if (chi <= s_bound[qi]) {
               const uint32_t slot = atomicAdd(&s_cnt[qi], 1u);
               s_buf[qi * CAP + slot] = ((uint64_t)chi << 32) | row;
@@ -330,25 +377,7 @@ __global__ __launch_bounds__(256) void sq8_scan_kernel(const Sq8ScanArgs a) {
       }
     }
     __syncthreads();
-#pragma unroll 1
-    for (uint32_t j = 0; j < 8; ++j) {
-      const uint32_t qi = w * 8u + j;
-      const uint32_t cnt = rfl(s_cnt[qi]);
-      if (cnt > KR * 64u) {  // wave-uniform
-        WaveTopK<KR> tk;
-        uint32_t th;
-        sq8_select<KR>(s_buf + qi * CAP, cnt, rfl(s_bound[qi]) != kInf32 ? a.k : 0u, a.k, lane, tk, th);
-#pragma unroll
-        for (int rr = 0; rr < KR; ++rr) {
-          const uint32_t e = rr * 64 + lane;
-          if (e < a.k) s_buf[qi * CAP + e] = ((uint64_t)tk.hi[rr] << 32) | tk.lo[rr];
-        }
-        if (lane == 0) {
-          s_cnt[qi] = a.k;  // cnt > 64 KR >= k
-          s_bound[qi] = th;
-        }
-      }
-    }
+    sq8_cut_round<KR>(s_buf, s_cnt, s_bound, w, a.k, lane);
     __syncthreads();
   }
 
@@ -380,7 +409,7 @@ __global__ __launch_bounds__(256) void sq8_refine_kernel(const RefineArgs a) {
 }
 
 // rows of a merged result to the caller's ids
-__global__ void sq8_map_ids_kernel(const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ ids, uint64_t total,
+static __global__ void sq8_map_ids_kernel(const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ ids, uint64_t total,
                                    uint64_t* __restrict__ out_ids) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
@@ -389,7 +418,7 @@ __global__ void sq8_map_ids_kernel(const uint32_t* __restrict__ nodes, const uin
 }
 
 // [B][d] -> [B][dpad], zero beyond d
-__global__ void sq8_pad_queries_kernel(const float* __restrict__ src, uint32_t d, uint32_t dpad, uint64_t B, float* __restrict__ dst) {
+static __global__ void sq8_pad_queries_kernel(const float* __restrict__ src, uint32_t d, uint32_t dpad, uint64_t B, float* __restrict__ dst) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B * dpad) return;
   const uint64_t b = e / dpad;
@@ -397,7 +426,7 @@ __global__ void sq8_pad_queries_kernel(const float* __restrict__ src, uint32_t d
   dst[e] = i < d ? src[b * d + i] : 0.0f;
 }
 
-__global__ void sq8_set_flags_kernel(const uint32_t* __restrict__ rows, uint64_t n, uint32_t flag, uint32_t* __restrict__ dead) {
+static __global__ void sq8_set_flags_kernel(const uint32_t* __restrict__ rows, uint64_t n, uint32_t flag, uint32_t* __restrict__ dead) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) dead[rows[e]] = flag;
 }

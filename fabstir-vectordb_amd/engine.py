@@ -827,6 +827,103 @@ class SQ8Index:
         return SearchResults(ids, dist, counts)
 
 
+class IVFSQ8Index:
+    """An inverted file whose lists hold u8 scalar-quantized rows (fvdb_ivfsq8): centroids,
+    assignment and probe order are the IVF-flat index's, the score and the refine are SQ8Index's, and the probed lists
+    are scanned list by list on the int8 matrix cores.  Ties go to the row added earlier."""
+
+    def __init__(self, ctx, d, nlist, refine_rows=None):
+        self.ctx, self.lib, self.d, self.nlist, self.refine_rows = ctx, ctx.lib, int(d), int(nlist), refine_rows
+        code = _capi.SQ8_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_ivfsq8_create(ctx.h, self.d, self.nlist, code, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_ivfsq8_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def train(self, rows, max_iterations=25, seed=0):
+        """k-means on the device (DeviceIVF.train) for an index without rows."""
+        x = _rows_2d(rows, self.d)
+        res = _capi.TrainResult()
+        self.ctx.check(self.lib.fvdb_ivfsq8_train(self.h, _ptr(x, f32p), x.shape[0], max_iterations, seed, C.byref(res)))
+        return dict(iterations=res.iterations, converged=bool(res.converged), initial_error=res.initial_error,
+                    final_error=res.final_error)
+
+    def set_centroids(self, centroids):
+        c = _rows_2d(centroids, self.d)
+        if c.shape[0] != self.nlist:
+            raise InvalidConfig(f"expected {self.nlist} centroids, got {c.shape[0]}")
+        self.ctx.check(self.lib.fvdb_ivfsq8_set_centroids(self.h, _ptr(c, f32p)))
+
+    def centroids(self):
+        out = np.empty((self.nlist, self.d), np.float32)
+        self.ctx.check(self.lib.fvdb_ivfsq8_get_centroids(self.h, _ptr(out, f32p)))
+        return out
+
+    def add(self, ids, rows):
+        r = _rows_2d(rows, self.d)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_ivfsq8_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_ivfsq8_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_ivfsq8_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_ivfsq8_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_ivfsq8_bytes(self.h))
+
+    def list_sizes(self):
+        out = np.empty(self.nlist, np.uint64)
+        self.ctx.check(self.lib.fvdb_ivfsq8_list_sizes(self.h, _ptr(out, u64p)))
+        return out
+
+    def info(self):
+        """fvdb_ivfsq8_info_t as a dict: the layout, segb and the segments of the longest list, the scan's LDS per k class
+        (k <= 64, 128, 256), the limits, and of the last search item_bound, rows_scored and items."""
+        v = _capi.IVFSQ8Info()
+        self.ctx.check(self.lib.fvdb_ivfsq8_info(self.h, C.byref(v)))
+        return {n: (list(getattr(v, n)) if n in ("queries_in_lds", "lds_bytes") else int(getattr(v, n))) for n, _ in v._fields_}
+
+    def search(self, queries, k, nprobe, fetch_k=None, refine="decoded", allowed=None):
+        """The k nearest by the symmetric code distance among the live rows of each query's min(nprobe, nlist) nearest
+        lists; fetch_k, refine and allowed as in SQ8Index.search."""
+        from .index import SearchResults
+        mode = _capi.SQ8_REFINE_DECODED
+        if fetch_k is not None and refine != "decoded":
+            if refine not in ("f32", "f16") or refine != self.refine_rows:
+                raise InvalidConfig(f'refine must be "decoded" or the index\'s refine_rows ({self.refine_rows!r}), got {refine!r}')
+            mode = _capi.SQ8_REFINE_ROWS
+        q = _rows_2d(queries, self.d)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        dist = np.full((B, max(k, 0)), np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_ivfsq8_search(self.h, _ptr(q, f32p), B, k, int(nprobe), int(fetch_k or 0), mode, ap, na,
+                                                   _ptr(ids, u64p), _ptr(dist, f32p), _ptr(counts, u32p)))
+        return SearchResults(ids, dist, counts)
+
+
 def batch_normalize(ctx, rows):
     """batch_normalize (src/core/vector_ops.rs:138-150) on the device: each row divided by its norm, a zero row unchanged."""
     r = _rows_2d(rows)

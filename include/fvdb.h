@@ -1363,6 +1363,76 @@ int fvdb_cos_index_search(fvdb_cos_index* ix, const float* q, uint32_t B, uint32
 int fvdb_cos_index_search_dev_slot(fvdb_cos_index* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k, int mode,
                                    const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_sim_dev, uint32_t* out_counts_dev);
 
+/* ---- IVF over SQ8 codes ---------------------------------------------
+ * An inverted file whose lists hold the u8 codes of "scalar quantization to u8" above: nlist centroids; for every added
+ * row its codes (the encode rule above) in the list of its nearest centroid; with refine rows, the original row too.
+ *
+ * Centroids, assignment and probe order are the IVF-flat index's own: the index owns an fvdb_ivf that never receives
+ * rows and uses its fvdb_ivf_train / fvdb_ivf_set_centroids, its batched nearest-centroid assignment (fvdb_ivf_assign)
+ * and its coarse stage (fvdb_ivf_coarse_dev_slot).  A row's list and a query's probe list are bit for bit what
+ * fvdb_ivf_add and fvdb_ivf_search would choose.  train and set_centroids serve an index without rows; once rows have
+ * been added they are FVDB_E_UNSUPPORTED (no retrain here).
+ *
+ * Search.  The candidates of a query are the live (and allowed) rows of its min(nprobe, nlist) probed lists; their
+ * score is the symmetric score above (the same integer sums, the same f64 operations in the same order, sqrtf); the
+ * result is the min(k, candidates) smallest keys (bits(dist) << 32) | seq, ascending, where seq is the row's ordinal in
+ * add order (u32): ties go to the row added earlier, whichever lists the tied rows sit in.  With nprobe >= nlist the
+ * result is therefore bit for bit fvdb_sq8_index_search over the same rows added in the same order: ids, distance bits
+ * and counts.  fetch_k and refine_mode are fvdb_sq8_index_search's: the probed symmetric search of fetch_k, then the
+ * re-score over decoded rows or the stored originals (store row = seq), keys (bits(distance) << 32) | seq.
+ *
+ * Limits: 1 <= d <= 2048 (0: FVDB_E_INVALID, more: FVDB_E_UNSUPPORTED); 1 <= nlist <= 16384 (0: FVDB_E_INVALID, more:
+ * FVDB_E_UNSUPPORTED); k and fetch_k in 1..FVDB_MAX_K, else FVDB_E_UNSUPPORTED; nprobe == 0 is FVDB_E_INVALID and
+ * min(nprobe, nlist) > 256 FVDB_E_UNSUPPORTED; add or search before centroids exist is FVDB_E_NOT_TRAINED.  The
+ * non-finite checks are the SQ8 index's: host forms only, before anything is written.  add, set_deleted, rows, live
+ * and bytes have the semantics and error codes of their fvdb_sq8_index_ counterparts. */
+typedef struct fvdb_ivfsq8 fvdb_ivfsq8;
+typedef struct fvdb_ivfsq8_info_t {
+  uint32_t d, d_padded;            /* d rounded up to 32: the code bytes of a row in the pool */
+  uint32_t nlist;
+  uint32_t block_rows;             /* rows of one code block (the matrix instruction's N); a block belongs to one list */
+  uint32_t queries_per_item;       /* queries of one work item (its M) */
+  uint32_t round_rows;             /* rows a workgroup scores between two looks at its survivor buffers */
+  uint32_t words_in_flight;        /* 1 KiB code words a scan wave keeps in flight */
+  uint32_t max_segments;           /* S: a list is cut into at most this many segments */
+  uint32_t segb, segments;         /* as of the rows present: blocks of a segment, segments of the longest list */
+  uint32_t max_list_blocks;        /* blocks of the longest list */
+  uint32_t lds_limit;              /* the device's LDS bytes per workgroup */
+  uint32_t queries_in_lds[3];      /* per k class (k <= 64, <= 128, <= 256): the gathered query operands are staged in LDS */
+  uint32_t lds_bytes[3];           /* per k class: dynamic LDS of a scan workgroup */
+  uint32_t max_d, max_k, max_nprobe, max_nlist; /* the limits above */
+  uint32_t item_bound;             /* last search (its last sub-batch): workgroups launched, the host's bound on the items */
+  uint64_t pool_blocks;            /* code blocks in use */
+  uint64_t rows_scored, items;     /* last search (its last sub-batch): (query, row) pairs of the plan, and its work items */
+} fvdb_ivfsq8_info_t;
+#define FVDB_IVFSQ8_MAX_NPROBE 256
+#define FVDB_IVFSQ8_MAX_NLIST 16384
+/* refine_dtype: FVDB_SQ8_NO_REFINE, or FVDB_F32 / FVDB_F16 to keep the rows too, in an fvdb_store the index owns. */
+int fvdb_ivfsq8_create(fvdb_ctx* ctx, uint32_t d, uint32_t nlist, int refine_dtype, fvdb_ivfsq8** out);
+void fvdb_ivfsq8_destroy(fvdb_ivfsq8* ix);
+/* fvdb_ivf_train / fvdb_ivf_set_centroids / fvdb_ivf_get_centroids of the index's centroid table */
+int fvdb_ivfsq8_train(fvdb_ivfsq8* ix, const float* x, uint64_t n, uint32_t max_iterations, uint64_t seed, fvdb_train_result* out);
+int fvdb_ivfsq8_set_centroids(fvdb_ivfsq8* ix, const float* centroids);
+int fvdb_ivfsq8_get_centroids(fvdb_ivfsq8* ix, float* out /* nlist x d */);
+int fvdb_ivfsq8_add(fvdb_ivfsq8* ix, const uint64_t* ids, const float* rows, uint64_t n);
+int fvdb_ivfsq8_set_deleted(fvdb_ivfsq8* ix, const uint64_t* ids, uint64_t n, int flag);
+uint64_t fvdb_ivfsq8_rows(fvdb_ivfsq8* ix);
+uint64_t fvdb_ivfsq8_live(fvdb_ivfsq8* ix);
+uint64_t fvdb_ivfsq8_bytes(fvdb_ivfsq8* ix); /* HBM held by the blocks in use: codes, records, flags, the seq tables, ids, the list table, refine rows */
+int fvdb_ivfsq8_list_sizes(fvdb_ivfsq8* ix, uint64_t* out /* nlist */); /* rows of every list, deleted ones included */
+/* the geometry, and the plan's figures of the last search (waits for the device when there was one) */
+int fvdb_ivfsq8_info(fvdb_ivfsq8* ix, fvdb_ivfsq8_info_t* out);
+/* Host arrays.  fetch_k == 0: the symmetric search alone (refine_mode is ignored).  allowed_ids as for
+ * fvdb_pq_index_search.  Synchronises. */
+int fvdb_ivfsq8_search(fvdb_ivfsq8* ix, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint32_t fetch_k, int refine_mode,
+                       const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dist, uint32_t* out_counts);
+/* Device pointers, enqueued on `on`'s stream (NULL: the index's context) with the scratch of `slot` (0..15).  dead_dev:
+ * NULL (the index's own flags), or one word per POOL row (32 per block in use), non-zero = not a candidate; the
+ * unfilled rows of a block must be non-zero in it.  Nothing is synchronised. */
+int fvdb_ivfsq8_search_dev_slot(fvdb_ivfsq8* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                                uint32_t fetch_k, int refine_mode, const uint32_t* dead_dev, uint64_t* out_ids_dev,
+                                float* out_dist_dev, uint32_t* out_counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
