@@ -87,6 +87,16 @@ class SQ8Info(C.Structure):
 SQ8_NO_REFINE, SQ8_REFINE_DECODED, SQ8_REFINE_ROWS = -1, 0, 1  # FVDB_SQ8_*
 
 
+class BQInfo(C.Structure):
+    """fvdb_bq_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("d", "words", "chunks", "block_rows", "queries_per_workgroup", "round_rows", "min_slice_rows",
+                                   "max_slice_rows", "lds_limit")] + \
+               [("lds_bytes", u32 * 3), ("max_d", u32), ("max_k", u32), ("last_slices", u32), ("reserved", u32), ("last_pairs", u64)]
+
+
+BQ_NO_REFINE = -1  # FVDB_BQ_NO_REFINE
+
+
 class IVFSQ8Info(C.Structure):
     """fvdb_ivfsq8_info_t (include/fvdb.h)."""
     _fields_ = [(n, u32) for n in ("d", "d_padded", "nlist", "block_rows", "queries_per_item", "round_rows", "words_in_flight",
@@ -353,6 +363,18 @@ SIGNATURES = {
     "fvdb_cos_index_info": (i32, [vp, C.POINTER(CosInfo)]),
     "fvdb_cos_index_search": (i32, [vp, f32p, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
     "fvdb_cos_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, i32, vp, vp, vp, vp]),
+    "fvdb_bq_encode": (i32, [vp, f32p, u64, u32, f32p, u8p]),
+    "fvdb_bq_encode_dev": (i32, [vp, vp, u64, u32, vp, vp]),
+    "fvdb_bq_index_create": (i32, [vp, u32, i32, f32p, C.POINTER(vp)]),
+    "fvdb_bq_index_destroy": (None, [vp]),
+    "fvdb_bq_index_add": (i32, [vp, u64p, f32p, u64]),
+    "fvdb_bq_index_set_deleted": (i32, [vp, u64p, u64, i32]),
+    "fvdb_bq_index_rows": (u64, [vp]),
+    "fvdb_bq_index_live": (u64, [vp]),
+    "fvdb_bq_index_bytes": (u64, [vp]),
+    "fvdb_bq_index_info": (i32, [vp, C.POINTER(BQInfo)]),
+    "fvdb_bq_index_search": (i32, [vp, f32p, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvdb_bq_index_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp]),
     "fvdb_ivfsq8_create": (i32, [vp, u32, u32, i32, C.POINTER(vp)]),
     "fvdb_ivfsq8_destroy": (None, [vp]),
     "fvdb_ivfsq8_train": (i32, [vp, f32p, u64, u32, u64, C.POINTER(TrainResult)]),

@@ -827,6 +827,97 @@ class SQ8Index:
         return SearchResults(ids, dist, counts)
 
 
+def _center(center, d):
+    if center is None:
+        return None
+    c = _f32(center).reshape(-1)
+    if c.size != d:
+        raise DimensionMismatch(f"Dimension mismatch: expected {d}, got {c.size}")
+    return c
+
+
+def binary_quantize(ctx, rows, center=None):
+    """One sign bit a dimension (include/fvdb.h, "binary quantization"): bit i = (x_i - center_i) > 0, packed as
+    np.packbits(bitorder="little") packs it: codes [n][ceil(d / 8)] u8."""
+    r = _rows_2d(rows)
+    n, d = r.shape
+    c = _center(center, d)
+    codes = np.empty((n, (d + 7) // 8), np.uint8)
+    ctx.check(ctx.lib.fvdb_bq_encode(ctx.h, _ptr(r, f32p), n, d, None if c is None else _ptr(c, f32p), _ptr(codes, _capi.u8p)))
+    return codes
+
+
+class BQIndex:
+    """An index of sign codes (fvdb_bq_index): a Hamming search over one bit a dimension and, with
+    refine_rows "f32" / "f16", the exact re-score of its candidates against the kept rows.  Ties go to the row added earlier."""
+
+    def __init__(self, ctx, d, refine_rows=None, center=None):
+        self.ctx, self.lib, self.d, self.refine_rows = ctx, ctx.lib, int(d), refine_rows
+        code = _capi.BQ_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
+        c = _center(center, self.d)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_bq_index_create(ctx.h, self.d, code, None if c is None else _ptr(c, f32p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_bq_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, ids, rows):
+        r = _rows_2d(rows, self.d)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_bq_index_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_bq_index_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_bq_index_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_bq_index_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_bq_index_bytes(self.h))
+
+    def info(self):
+        """fvdb_bq_info_t as a dict: the layout, the query tile, the scan's LDS per k class (k <= 64, 128, 256), the
+        limits, and the slices and pairs of the last search."""
+        v = _capi.BQInfo()
+        self.ctx.check(self.lib.fvdb_bq_index_info(self.h, C.byref(v)))
+        return {n: (list(getattr(v, n)) if n == "lds_bytes" else int(getattr(v, n))) for n, _ in v._fields_}
+
+    def search(self, queries, k, fetch_k=None, allowed=None):
+        """The k nearest by Hamming distance between sign codes (the distance returned is that count); with fetch_k, the
+        fetch_k nearest of that search re-scored against the f32 query and the kept rows, and the k nearest of those.
+        allowed: only rows with these ids are candidates."""
+        from .index import SearchResults
+        if fetch_k is not None and int(fetch_k) < 1:  # 0 is the C ABI's "no refine", not a fetch_k
+            raise Unsupported("refined search: fetch_k must be in 1..256")
+        q = _rows_2d(queries, self.d)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        dist = np.full((B, max(k, 0)), np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_bq_index_search(self.h, _ptr(q, f32p), B, k, int(fetch_k or 0), ap, na, _ptr(ids, u64p),
+                                                     _ptr(dist, f32p), _ptr(counts, u32p)))
+        return SearchResults(ids, dist, counts)
+
+
 class IVFSQ8Index:
     """An inverted file whose lists hold u8 scalar-quantized rows (fvdb_ivfsq8): centroids,
     assignment and probe order are the IVF-flat index's, the score and the refine are SQ8Index's, and the probed lists

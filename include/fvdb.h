@@ -1293,6 +1293,66 @@ int fvdb_sq8_index_search_dev_slot(fvdb_sq8_index* ix, fvdb_ctx* on, uint32_t sl
                                    uint32_t fetch_k, int refine_mode, const uint32_t* dead_dev, uint64_t* out_ids_dev,
                                    float* out_dist_dev, uint32_t* out_counts_dev);
 
+/* ---- binary quantization -------------------------------------------
+ * One sign bit a dimension, a Hamming search over the codes and an exact re-score from kept rows.  No reference
+ * counterpart.  d is the row width, 1 <= d <= 2048 (0: FVDB_E_INVALID, more: FVDB_E_UNSUPPORTED); W = ceil(d / 32) code
+ * words a row.  An index has a centre c of d floats, fixed at creation; NULL means zeros.
+ *
+ * encode: bit_i = 1 iff (x_i - c_i) > 0, one f32 subtraction and no FMA, so -0 and +0 give 0; dims >= d are 0.  The
+ * flat form is [n][ceil(d / 8)] bytes, dim i = bit i & 7 of byte i >> 3 (numpy's packbits(bitorder="little")).  A NaN
+ * or Inf element of a row, a query or the centre is FVDB_E_NONFINITE before anything is written (host forms, index
+ * create, add and host search; the _dev forms read values already in HBM and do not check them).
+ *
+ * Hamming search.  The query is encoded by the same rule with the index's centre; ham = sum over the W words of
+ * popcount(x_w ^ q_w).  A candidate's key is (bits((float)ham) << 32) | row, row = the append position; candidates are
+ * the live rows (under an allow-set: the allowed ones of them); the result is the min(k, candidates) smallest keys,
+ * ascending, and the distance returned is (float)ham.  1 <= k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED.
+ * Refined search (fetch_k != 0; k <= fetch_k, else FVDB_E_INVALID; fetch_k <= FVDB_MAX_K, else FVDB_E_UNSUPPORTED; an
+ * index created with refine rows, else FVDB_E_INVALID): the candidates are the Hamming search of fetch_k, each is
+ * re-scored against the f32 query and its stored row (an fp16 row is widened exactly first) with the fold
+ * t = a - b; s = s + t * t, ascending, sqrtf last, and the k smallest (bits(distance) << 32) | row are returned.
+ * There is no decoded mode.  Outputs as for the product-quantization index: B x k, unused tail = FVDB_NO_ID / +inf. */
+typedef struct fvdb_bq_index fvdb_bq_index;
+typedef struct fvdb_bq_info_t {
+  uint32_t d, words;               /* W = ceil(d / 32) code words of a row */
+  uint32_t chunks;                 /* 16-byte words a row holds in the index: ceil(W / 4) rounded up to 1, 2, 3, 4, 8 or 16 */
+  uint32_t block_rows;             /* rows of one code block (a wave's lanes) */
+  uint32_t queries_per_workgroup;  /* the query tile of one scan workgroup */
+  uint32_t round_rows;             /* rows a workgroup scores between two looks at its survivor buffers */
+  uint32_t min_slice_rows;         /* a scan slice is at least this many rows (the last one may be shorter) */
+  uint32_t max_slice_rows;         /* and at most this many: what a 4-byte in-slice key can number */
+  uint32_t lds_limit;              /* the device's LDS bytes per workgroup */
+  uint32_t lds_bytes[3];           /* per k class (k <= 64, <= 128, <= 256): dynamic LDS of a scan workgroup */
+  uint32_t max_d, max_k;           /* the limits above */
+  uint32_t last_slices;            /* of the last search: slices of the scan */
+  uint32_t reserved;
+  uint64_t last_pairs;             /* of the last search: (query, row) pairs scored */
+} fvdb_bq_info_t;
+#define FVDB_BQ_NO_REFINE (-1)
+/* out_codes in the flat form; centre: d floats or NULL; host arrays, synchronises. */
+int fvdb_bq_encode(fvdb_ctx* ctx, const float* rows, uint64_t n, uint32_t d, const float* centre, uint8_t* out_codes);
+/* the same with device pointers, enqueued on ctx's stream; nothing is checked for NaN / Inf, nothing is synchronised */
+int fvdb_bq_encode_dev(fvdb_ctx* ctx, const float* rows_dev, uint64_t n, uint32_t d, const float* centre_dev, uint8_t* out_codes_dev);
+/* An index of sign codes.  refine_dtype: FVDB_BQ_NO_REFINE, or FVDB_F32 / FVDB_F16 to keep the rows too, in an
+ * fvdb_store the index owns (store row = code row).  centre: d host floats, copied, or NULL.  add, set_deleted, rows,
+ * live and bytes have the semantics and error codes of their fvdb_pq_index_ counterparts. */
+int fvdb_bq_index_create(fvdb_ctx* ctx, uint32_t d, int refine_dtype, const float* centre, fvdb_bq_index** out);
+void fvdb_bq_index_destroy(fvdb_bq_index* ix);
+int fvdb_bq_index_add(fvdb_bq_index* ix, const uint64_t* ids, const float* rows, uint64_t n);
+int fvdb_bq_index_set_deleted(fvdb_bq_index* ix, const uint64_t* ids, uint64_t n, int flag);
+uint64_t fvdb_bq_index_rows(fvdb_bq_index* ix);
+uint64_t fvdb_bq_index_live(fvdb_bq_index* ix);
+uint64_t fvdb_bq_index_bytes(fvdb_bq_index* ix); /* HBM held by the rows present: code blocks, ids, flags, refine rows */
+int fvdb_bq_index_info(fvdb_bq_index* ix, fvdb_bq_info_t* out);
+/* Host arrays.  fetch_k == 0: the Hamming search alone.  allowed_ids as for fvdb_pq_index_search.  Synchronises. */
+int fvdb_bq_index_search(fvdb_bq_index* ix, const float* q, uint32_t B, uint32_t k, uint32_t fetch_k, const uint64_t* allowed_ids,
+                         uint64_t n_allowed, uint64_t* out_ids, float* out_dist, uint32_t* out_counts);
+/* Device pointers, enqueued on `on`'s stream (NULL: the index's context) with the scratch of `slot` (0..15); dead_dev as
+ * for fvdb_pq_index_search_dev_slot.  Nothing is synchronised. */
+int fvdb_bq_index_search_dev_slot(fvdb_bq_index* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k,
+                                  uint32_t fetch_k, const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint32_t* out_counts_dev);
+
 /* ---- cosine search --------------------------------------------------
  * batch_search_parallel (src/core/vector_ops.rs:310-346: batch_cosine_similarity, then a top-k; the browser index has
  * the same search, bindings/wasm/src/index.rs:122) and batch_normalize (:138-150), for rows resident in HBM.
