@@ -106,6 +106,13 @@ class IVFSQ8Info(C.Structure):
                [(n, u64) for n in ("pool_blocks", "rows_scored", "items")]
 
 
+class IVFPQInfo(C.Structure):
+    """fvdb_ivfpq_info_t (include/fvdb.h)."""
+    _fields_ = [(n, u32) for n in ("d", "m", "ksub_actual", "nlist", "block_rows", "queries_per_workgroup", "lds_bytes", "lds_limit",
+                                   "words_in_flight", "max_k", "max_nlist", "last_slices")] + \
+               [(n, u64) for n in ("pool_blocks", "rows_scored", "pairs")]
+
+
 class CosInfo(C.Structure):
     """fvdb_cos_info_t (include/fvdb.h)."""
     _fields_ = [(n, u32) for n in ("d", "d_padded", "block_rows", "queries_per_workgroup", "round_rows", "words_in_flight",
@@ -389,6 +396,20 @@ SIGNATURES = {
     "fvdb_ivfsq8_info": (i32, [vp, C.POINTER(IVFSQ8Info)]),
     "fvdb_ivfsq8_search": (i32, [vp, f32p, u32, u32, u32, u32, i32, u64p, u64, u64p, f32p, u32p]),
     "fvdb_ivfsq8_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, i32, vp, vp, vp, vp]),
+    "fvdb_ivfpq_create": (i32, [vp, u32, i32, C.POINTER(vp)]),
+    "fvdb_ivfpq_destroy": (None, [vp]),
+    "fvdb_ivfpq_train": (i32, [vp, f32p, u64, u32, u64, C.POINTER(TrainResult)]),
+    "fvdb_ivfpq_set_centroids": (i32, [vp, f32p]),
+    "fvdb_ivfpq_get_centroids": (i32, [vp, f32p]),
+    "fvdb_ivfpq_add": (i32, [vp, u64p, f32p, u64]),
+    "fvdb_ivfpq_set_deleted": (i32, [vp, u64p, u64, i32]),
+    "fvdb_ivfpq_rows": (u64, [vp]),
+    "fvdb_ivfpq_live": (u64, [vp]),
+    "fvdb_ivfpq_bytes": (u64, [vp]),
+    "fvdb_ivfpq_list_sizes": (i32, [vp, u64p]),
+    "fvdb_ivfpq_info": (i32, [vp, C.POINTER(IVFPQInfo)]),
+    "fvdb_ivfpq_search": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
+    "fvdb_ivfpq_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -66,4 +66,13 @@ struct MergeArgs {
   const uint32_t* nq;
 };
 
+// Product quantization's subspace geometry (kernels_pq.h; the reference's, src/core/vector_ops.rs:411-421): dsub = d / m,
+// subspace j covers dims [j dsub, (j + 1) dsub), the last one runs to d.  ka = ksub_actual.
+struct PqGeom {
+  uint32_t d, m, dsub, ka;
+  __host__ __device__ uint32_t off(uint32_t j) const { return j * dsub; }
+  __host__ __device__ uint32_t dims(uint32_t j) const { return j + 1 == m ? d - j * dsub : dsub; }
+  __host__ __device__ size_t book(uint32_t j) const { return (size_t)ka * j * dsub; }  // every earlier subspace holds dsub dims
+};
+
 }  // namespace fvdb

@@ -51,27 +51,6 @@ hipError_t download(fvdb_ctx* ctx, void* dst, const void* src, size_t bytes) {
 
 }  // namespace
 
-struct fvdb_pq {
-  fvdb_ctx* ctx = nullptr;
-  PqGeom g{};              // g.ka = ksub_actual, 0 until trained
-  uint32_t ksub = 0;
-  uint32_t dmax = 0;       // pq_encode_kernel's instantiation: 8, 32 or 128
-  uint32_t pad = 0;        // table rows in LDS carry one float of padding
-  uint32_t lds_limit = 0;
-  uint64_t version = 0;    // bumped whenever the codebooks change
-  bool trained = false;
-  DBuf books;              // [m][ksub][dims]: room for ksub * d floats
-  DBuf s_rows, s_codes, s_refill;  // host-form scratch
-  uint32_t ts() const { return g.ka + pad; }
-  uint32_t m16() const { return (g.m + 15) / 16; }
-  uint32_t qt() const {  // queries of a scan workgroup: the largest of 4, 2, 1 whose tables fit
-    const uint64_t per = (uint64_t)g.m * ts() * 4;
-    for (uint32_t q = 4; q; q >>= 1)
-      if (per * q <= lds_limit) return q;
-    return 0;
-  }
-};
-
 struct PqSlot {
   DBuf q, qpad, tables, part, nodes, dist, counts, dead, out_ids;
 };

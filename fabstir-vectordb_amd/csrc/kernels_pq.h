@@ -34,13 +34,6 @@ constexpr uint32_t kPqMaxDims = 2048;
 constexpr uint32_t kPqBookFloats = 6144;  // staged centroids of one subspace: 24 KiB beside the four 9 KiB tiles
 constexpr int kPqAhead = 8;               // code words a scan wave keeps in flight: 8 KiB (half of it at four queries)
 
-struct PqGeom {
-  uint32_t d, m, dsub, ka;
-  __host__ __device__ uint32_t off(uint32_t j) const { return j * dsub; }
-  __host__ __device__ uint32_t dims(uint32_t j) const { return j + 1 == m ? d - j * dsub : dsub; }
-  __host__ __device__ size_t book(uint32_t j) const { return (size_t)ka * j * dsub; }  // every earlier subspace holds dsub dims
-};
-
 // ---- encode ---------------------------------------------------------------------------------------------------------
 struct PqEncodeArgs {
   const float* rows;   // [n][d], row-major, unpadded
@@ -170,7 +163,7 @@ struct PqUpdateArgs {
 
 // block (c, j), thread = dim: the members of centroid c of subspace j are found 128 rows at a time (two ballots) and
 // added in data order from 0.0f; the sum is divided by (float)count.
-__global__ __launch_bounds__(128) void pq_update_kernel(const PqUpdateArgs a) {
+static __global__ __launch_bounds__(128) void pq_update_kernel(const PqUpdateArgs a) {
   __shared__ uint64_t s_mask[2];
   const PqGeom g = a.g;
   const uint32_t c = blockIdx.x, j = blockIdx.y, i = threadIdx.x;
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(128) void pq_update_kernel(const PqUpdateArgs a) {
 
 // ---- decode (vector_ops.rs:563-577) ----------------------------------------------------------------------------------
 // one thread per output float, bit copies; a code at or above ka reads the last centroid (the host form refuses it first)
-__global__ void pq_decode_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ books, PqGeom g, uint64_t n,
+static __global__ void pq_decode_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ books, PqGeom g, uint64_t n,
                                  float* __restrict__ out) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * g.d) return;
@@ -215,7 +208,7 @@ __global__ void pq_decode_kernel(const uint8_t* __restrict__ codes, const float*
 
 // ---- the ADC tables --------------------------------------------------------------------------------------------------
 // block (j, b): T[b][j][c] for every c, one thread per entry; the query's sub-vector is wave-uniform (scalar loads)
-__global__ __launch_bounds__(256) void pq_table_kernel(const float* __restrict__ q /* [B][d] */, const float* __restrict__ books, PqGeom g,
+static __global__ __launch_bounds__(256) void pq_table_kernel(const float* __restrict__ q /* [B][d] */, const float* __restrict__ books, PqGeom g,
                                                        float* __restrict__ tables /* [B][m][ka] */) {
   const uint32_t j = blockIdx.x, b = blockIdx.y;
   const uint32_t off = g.off(j), dj = g.dims(j);
@@ -345,7 +338,7 @@ __global__ __launch_bounds__(256) void pq_adc_scan_kernel(const PqScanArgs a) {
 }
 
 // rows of a merged result to the caller's ids
-__global__ void pq_map_ids_kernel(const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ ids, uint64_t total,
+static __global__ void pq_map_ids_kernel(const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ ids, uint64_t total,
                                   uint64_t* __restrict__ out_ids) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
@@ -369,7 +362,7 @@ __global__ __launch_bounds__(256) void pq_refine_kernel(const PqRefineArgs a) {
 
 // ---- small helpers ---------------------------------------------------------------------------------------------------
 // [B][d] -> [B][dpad], zero beyond d
-__global__ void pq_pad_queries_kernel(const float* __restrict__ src, uint32_t d, uint32_t dpad, uint64_t B, float* __restrict__ dst) {
+static __global__ void pq_pad_queries_kernel(const float* __restrict__ src, uint32_t d, uint32_t dpad, uint64_t B, float* __restrict__ dst) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B * dpad) return;
   const uint64_t b = e / dpad;
@@ -377,7 +370,7 @@ __global__ void pq_pad_queries_kernel(const float* __restrict__ src, uint32_t d,
   dst[e] = i < d ? src[b * d + i] : 0.0f;
 }
 
-__global__ void pq_set_flags_kernel(const uint32_t* __restrict__ rows, uint64_t n, uint32_t flag, uint32_t* __restrict__ dead) {
+static __global__ void pq_set_flags_kernel(const uint32_t* __restrict__ rows, uint64_t n, uint32_t flag, uint32_t* __restrict__ dead) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) dead[rows[e]] = flag;
 }

@@ -1015,6 +1015,101 @@ class IVFSQ8Index:
         return SearchResults(ids, dist, counts)
 
 
+class IVFPQIndex:
+    """An inverted file whose lists hold product-quantized rows (fvdb_ivfpq) over a trained
+    ProductQuantizer: centroids, assignment and probe order are the IVF-flat index's, codes (not residual), ADC score and
+    refine are PQIndex's, and each query's probed lists are walked by waves that hold its table in LDS.  Ties go to the
+    row added earlier; with every list probed the result is PQIndex.search's."""
+
+    def __init__(self, ctx, pq, nlist, refine_rows=None):
+        self.ctx, self.lib, self.pq, self.d, self.nlist, self.refine_rows = ctx, ctx.lib, pq, pq.d, int(nlist), refine_rows
+        code = _capi.PQ_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
+        h = C.c_void_p()
+        ctx.check(self.lib.fvdb_ivfpq_create(pq.h, self.nlist, code, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.fvdb_ivfpq_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def train(self, rows, max_iterations=25, seed=0):
+        """k-means on the device (DeviceIVF.train) for an index without rows."""
+        x = _rows_2d(rows, self.d)
+        res = _capi.TrainResult()
+        self.ctx.check(self.lib.fvdb_ivfpq_train(self.h, _ptr(x, f32p), x.shape[0], max_iterations, seed, C.byref(res)))
+        return dict(iterations=res.iterations, converged=bool(res.converged), initial_error=res.initial_error,
+                    final_error=res.final_error)
+
+    def set_centroids(self, centroids):
+        c = _rows_2d(centroids, self.d)
+        if c.shape[0] != self.nlist:
+            raise InvalidConfig(f"expected {self.nlist} centroids, got {c.shape[0]}")
+        self.ctx.check(self.lib.fvdb_ivfpq_set_centroids(self.h, _ptr(c, f32p)))
+
+    def centroids(self):
+        out = np.empty((self.nlist, self.d), np.float32)
+        self.ctx.check(self.lib.fvdb_ivfpq_get_centroids(self.h, _ptr(out, f32p)))
+        return out
+
+    def add(self, ids, rows):
+        r = _rows_2d(rows, self.d)
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if i.size != r.shape[0]:
+            raise InvalidConfig(f"{i.size} ids for {r.shape[0]} rows")
+        self.ctx.check(self.lib.fvdb_ivfpq_add(self.h, _ptr(i, u64p), _ptr(r, f32p), r.shape[0]))
+
+    def mark_deleted(self, ids, deleted=True):
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        self.ctx.check(self.lib.fvdb_ivfpq_set_deleted(self.h, _ptr(i, u64p), i.size, int(bool(deleted))))
+
+    def rows(self):
+        return int(self.lib.fvdb_ivfpq_rows(self.h))
+
+    def live(self):
+        return int(self.lib.fvdb_ivfpq_live(self.h))
+
+    def bytes(self):
+        return int(self.lib.fvdb_ivfpq_bytes(self.h))
+
+    def list_sizes(self):
+        out = np.empty(self.nlist, np.uint64)
+        self.ctx.check(self.lib.fvdb_ivfpq_list_sizes(self.h, _ptr(out, u64p)))
+        return out
+
+    def info(self):
+        """fvdb_ivfpq_info_t as a dict: the geometry, QT and the scan's LDS, words in flight, the limits, and of the last
+        search its slices S, rows_scored and (query, list) pairs."""
+        v = _capi.IVFPQInfo()
+        self.ctx.check(self.lib.fvdb_ivfpq_info(self.h, C.byref(v)))
+        return {n: int(getattr(v, n)) for n, _ in v._fields_}
+
+    def search(self, queries, k, nprobe, fetch_k=None, allowed=None):
+        """The k nearest by ADC distance among the live rows of each query's min(nprobe, nlist) nearest lists; fetch_k
+        and allowed as in PQIndex.search."""
+        from .index import SearchResults
+        if fetch_k is not None and self.refine_rows is None:
+            raise InvalidConfig("fetch_k needs an index created with refine_rows")
+        q = _rows_2d(queries, self.d)
+        B, k = q.shape[0], int(k)
+        ids = np.full((B, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
+        dist = np.full((B, max(k, 0)), np.inf, np.float32)
+        counts = np.zeros(B, np.uint32)
+        ap, na = None, 0
+        if allowed is not None:
+            al = np.ascontiguousarray(allowed, np.uint64).reshape(-1)
+            ap, na = _ptr(np.concatenate([al, np.zeros(1, np.uint64)]), u64p), al.size  # never NULL: an empty set allows nothing
+        self.ctx.check(self.lib.fvdb_ivfpq_search(self.h, _ptr(q, f32p), B, k, int(nprobe), int(fetch_k or 0), ap, na,
+                                                  _ptr(ids, u64p), _ptr(dist, f32p), _ptr(counts, u32p)))
+        return SearchResults(ids, dist, counts)
+
+
 def batch_normalize(ctx, rows):
     """batch_normalize (src/core/vector_ops.rs:138-150) on the device: each row divided by its norm, a zero row unchanged."""
     r = _rows_2d(rows)

@@ -1493,6 +1493,78 @@ int fvdb_ivfsq8_search_dev_slot(fvdb_ivfsq8* ix, fvdb_ctx* on, uint32_t slot, co
                                 uint32_t fetch_k, int refine_mode, const uint32_t* dead_dev, uint64_t* out_ids_dev,
                                 float* out_dist_dev, uint32_t* out_counts_dev);
 
+/* ---- IVF over PQ codes -----------------------------------------------
+ * An inverted file whose lists hold the codes of "product quantization" above: nlist centroids; for every added row its
+ * m codes in the list of its nearest centroid; with refine rows, the original row too.  The index is created from a
+ * trained quantizer (d, m, ksub_actual and the codebooks are the quantizer's, which the caller keeps alive) and follows
+ * the quantizer's codebooks the way the codes-only index does: once they change, every call that reads codes is
+ * FVDB_E_INVALID.
+ *
+ * Codes are NOT residual: a row is encoded by the quantizer's own encode rule on the row itself, so the ADC table of a
+ * query is the per-query table of "product quantization", whatever list a row sits in.
+ *
+ * Centroids, assignment and probe order are the IVF-flat index's own, exactly as for "IVF over SQ8 codes": an fvdb_ivf
+ * that never receives rows, fvdb_ivf_train / fvdb_ivf_set_centroids, fvdb_ivf_assign and fvdb_ivf_coarse_dev_slot.
+ * train and set_centroids serve an index without rows; once rows have been added they are FVDB_E_UNSUPPORTED.
+ *
+ * Search.  The candidates of a query are the live (and allowed) rows of its min(nprobe, nlist) probed lists.  Their
+ * score is adc = sqrtf(((T[0][c_0] + T[1][c_1]) + ...) + T[m-1][c_{m-1}]), f32, j ascending, T the query's table; the
+ * key is (bits(adc) << 32) | seq with seq the row's ordinal in add order (u32) over the whole index; the result is the
+ * min(k, candidates) smallest keys, ascending: ties go to the row added earlier, whichever lists the tied rows sit in.
+ * With nprobe >= nlist the result is therefore bit for bit fvdb_pq_index_search over the same rows added in the same
+ * order: ids, distance bits and counts.  Refined search (fetch_k != 0, on an index created with refine rows, else
+ * FVDB_E_INVALID; k <= fetch_k, else FVDB_E_INVALID): the probed ADC search of fetch_k, then fvdb_pq_index_search's
+ * re-score against the stored rows (store row = seq), keys (bits(distance) << 32) | seq.
+ *
+ * A row is dead when its slot in a list's last block is unfilled, when it is deleted, or when it is not in the
+ * allow-set: one word per POOL row (64 per block in use).
+ *
+ * Refusals, all before anything is launched: creation from an untrained quantizer, add or search before centroids
+ * exist: FVDB_E_NOT_TRAINED; nlist == 0: FVDB_E_INVALID, nlist > 16384: FVDB_E_UNSUPPORTED; a query's table
+ * (m x table_stride x 4 bytes) above the device's LDS, k or fetch_k outside 1..FVDB_MAX_K: FVDB_E_UNSUPPORTED;
+ * nprobe == 0: FVDB_E_INVALID; an id already present or repeated in the call: FVDB_E_DUPLICATE; a non-finite row or
+ * query in the host forms: FVDB_E_NONFINITE.  nprobe has no limit of this index's own: min(nprobe, nlist) goes to
+ * fvdb_ivf_coarse_dev_slot, and what that refuses is returned as it is.  add, set_deleted, rows, live and bytes have the
+ * semantics and error codes of their fvdb_pq_index_ counterparts. */
+typedef struct fvdb_ivfpq fvdb_ivfpq;
+typedef struct fvdb_ivfpq_info_t {
+  uint32_t d, m, ksub_actual;      /* the quantizer's */
+  uint32_t nlist;
+  uint32_t block_rows;             /* rows of one code block; a block belongs to one list */
+  uint32_t queries_per_workgroup;  /* QT: 4, 2 or 1 tables in LDS; a wave of the workgroup scans for one of them */
+  uint32_t lds_bytes, lds_limit;   /* dynamic LDS of a scan workgroup; the device's LDS bytes per workgroup */
+  uint32_t words_in_flight;        /* 1 KiB code words a scan wave keeps in flight, across block and list boundaries */
+  uint32_t max_k, max_nlist;       /* the limits above */
+  uint32_t last_slices;            /* S of the last search (its last sub-batch): slices of a query's probe ranks */
+  uint64_t pool_blocks;            /* code blocks in use */
+  uint64_t rows_scored, pairs;     /* last search: rows of the lists walked (deleted ones included), (query, list) pairs */
+} fvdb_ivfpq_info_t;
+#define FVDB_IVFPQ_MAX_NLIST 16384
+/* refine_dtype: FVDB_PQ_NO_REFINE, or FVDB_F32 / FVDB_F16 to keep the rows too, in an fvdb_store the index owns. */
+int fvdb_ivfpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq** out);
+void fvdb_ivfpq_destroy(fvdb_ivfpq* ix);
+/* fvdb_ivf_train / fvdb_ivf_set_centroids / fvdb_ivf_get_centroids of the index's centroid table */
+int fvdb_ivfpq_train(fvdb_ivfpq* ix, const float* x, uint64_t n, uint32_t max_iterations, uint64_t seed, fvdb_train_result* out);
+int fvdb_ivfpq_set_centroids(fvdb_ivfpq* ix, const float* centroids);
+int fvdb_ivfpq_get_centroids(fvdb_ivfpq* ix, float* out /* nlist x d */);
+int fvdb_ivfpq_add(fvdb_ivfpq* ix, const uint64_t* ids, const float* rows, uint64_t n);
+int fvdb_ivfpq_set_deleted(fvdb_ivfpq* ix, const uint64_t* ids, uint64_t n, int flag);
+uint64_t fvdb_ivfpq_rows(fvdb_ivfpq* ix);
+uint64_t fvdb_ivfpq_live(fvdb_ivfpq* ix);
+uint64_t fvdb_ivfpq_bytes(fvdb_ivfpq* ix); /* HBM held by the blocks in use: codes, flags, the seq tables, ids, the list table, refine rows */
+int fvdb_ivfpq_list_sizes(fvdb_ivfpq* ix, uint64_t* out /* nlist */); /* rows of every list, deleted ones included */
+/* the geometry, and the counters of the last search (waits for the device when there was one) */
+int fvdb_ivfpq_info(fvdb_ivfpq* ix, fvdb_ivfpq_info_t* out);
+/* Host arrays.  fetch_k == 0: the ADC search alone.  allowed_ids as for fvdb_pq_index_search.  Synchronises. */
+int fvdb_ivfpq_search(fvdb_ivfpq* ix, const float* q, uint32_t B, uint32_t k, uint32_t nprobe, uint32_t fetch_k,
+                      const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dist, uint32_t* out_counts);
+/* Device pointers, enqueued on `on`'s stream (NULL: the index's context) with the scratch of `slot` (0..15).  dead_dev:
+ * NULL (the index's own flags), or one word per POOL row (64 per block in use), non-zero = not a candidate; the
+ * unfilled rows of a block must be non-zero in it.  Nothing is synchronised. */
+int fvdb_ivfpq_search_dev_slot(fvdb_ivfpq* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
+                               uint32_t fetch_k, const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                               uint32_t* out_counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
