@@ -11,7 +11,7 @@ The directory name carries a hyphen, so import it through `fvdb_import.py` at th
 from . import _capi  # noqa: F401
 from . import engine  # noqa: F401
 from .engine import *  # noqa: F401,F403
-from .engine import Context, DeviceIVF, RowStore, ProductQuantizer, PQIndex, SQ8Index, IVFSQ8Index, IVFPQIndex, scalar_quantize_u8, dequantize_u8, CosineIndex, batch_normalize, BQIndex, binary_quantize  # noqa: F401
+from .engine import Context, DeviceIVF, RowStore, ProductQuantizer, PQIndex, SQ8Index, IVFSQ8Index, IVFPQIndex, ivf_residuals, scalar_quantize_u8, dequantize_u8, CosineIndex, batch_normalize, BQIndex, binary_quantize  # noqa: F401
 from .index import IVFIndex, HNSWIndex, HybridIndex, SearchResults, load_host  # noqa: F401,E402
 from . import sharded  # noqa: F401,E402
 from . import metadata_filter  # noqa: F401,E402

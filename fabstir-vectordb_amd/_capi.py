@@ -410,6 +410,7 @@ SIGNATURES = {
     "fvdb_ivfpq_info": (i32, [vp, C.POINTER(IVFPQInfo)]),
     "fvdb_ivfpq_search": (i32, [vp, f32p, u32, u32, u32, u32, u64p, u64, u64p, f32p, u32p]),
     "fvdb_ivfpq_search_dev_slot": (i32, [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
+    "fvdb_ivfrpq_create": (i32, [vp, u32, i32, C.POINTER(vp)]),
 }
 
 _lib = None

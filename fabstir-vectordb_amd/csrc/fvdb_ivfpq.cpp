@@ -14,6 +14,7 @@
 #include "fvdb_internal.h"
 #include "common.h"
 #include "kernels_ivfpq.h"
+#include "kernels_ivfrpq.h"  // residual codes: the fused encode, the inner-product tables, the base
 
 using namespace fvdb;
 
@@ -50,6 +51,7 @@ int check_finite(fvdb_ctx* ctx, const float* x, uint64_t n) {
 
 struct IvfPqSlot {
   DBuf q, qpad, probes, tables, part, nodes, dist, counts, dead, out, stats;
+  DBuf base, qres;  // residual codes: base[Bs][np]; the queries at the centroid copy's row stride where it is not d
   uint32_t last_S = 0;
 };
 
@@ -65,6 +67,12 @@ struct fvdb_ivfpq {
   DBuf codes, dead, seq_of_row;  // per pool block / pool row
   DBuf row_of_seq, ids;          // per seq
   DBuf list_off, list_len, list_blocks, s_in, s_flat, s_rows;
+  // Residual codes (fvdb_ivfrpq_create; section 9zd): a row's codes encode row - centroid, and the pool carries one f32
+  // row term beside dead and seq_of_row.  The encode and the base kernel read the index's own copy of the centroids,
+  // [nlist][dpad] with dpad = d rounded up to 4 and zeros beyond d (the fvdb_ivf's table is behind the C ABI).
+  bool residual = false;
+  uint32_t dpad = 0;
+  DBuf term_of_row, cent, s_cluster, s_term;
   uint64_t n = 0, live = 0, blocks = 0, cap_blocks = 0, cap_seq = 0;
   std::vector<std::vector<uint32_t>> h_blocks;  // per list, in fill order
   std::vector<uint32_t> h_len, h_row_of_seq;
@@ -87,23 +95,73 @@ struct fvdb_ivfpq {
 
 namespace {
 
-template <int QT, int KR>
+template <int QT, int KR, bool RES>
 int launch_scan(fvdb_ctx* on, const IvfPqScanArgs& a, uint32_t lds, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
   // the attribute belongs to the function; every call sets what it needs
-  HIPCHK(on, hipFuncSetAttribute((const void*)ivfpq_scan_kernel<QT, KR, kIvfPqChains>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((ivfpq_scan_kernel<QT, KR, kIvfPqChains>), dim3(cdiv(a.B, QT), cdiv(a.S, 4 / QT)), dim3(256), lds, on->stream, a);
+  HIPCHK(on, hipFuncSetAttribute((const void*)ivfpq_scan_kernel<QT, KR, kIvfPqChains, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((ivfpq_scan_kernel<QT, KR, kIvfPqChains, RES>), dim3(cdiv(a.B, QT), cdiv(a.S, 4 / QT)), dim3(256), lds, on->stream, a);
   hipLaunchKernelGGL((flat_merge_kernel<KR>), dim3(cdiv(a.B, 4)), dim3(256), 0, on->stream, a.part, a.S, a.B, a.k, out_nodes, out_dist, out_counts);
   HIPCHK(on, hipGetLastError());
   return FVDB_OK;
 }
 
+// a.base set = residual codes: the RES instantiation
 template <int KR>
 int launch_scan_qt(uint32_t qt, fvdb_ctx* on, const IvfPqScanArgs& a, uint32_t lds, uint32_t* out_nodes, float* out_dist, uint32_t* out_counts) {
-  switch (qt) {
-    case 4: return launch_scan<4, KR>(on, a, lds, out_nodes, out_dist, out_counts);
-    case 2: return launch_scan<2, KR>(on, a, lds, out_nodes, out_dist, out_counts);
-    default: return launch_scan<1, KR>(on, a, lds, out_nodes, out_dist, out_counts);
+  if (a.base) {
+    switch (qt) {
+      case 4: return launch_scan<4, KR, true>(on, a, lds, out_nodes, out_dist, out_counts);
+      case 2: return launch_scan<2, KR, true>(on, a, lds, out_nodes, out_dist, out_counts);
+      default: return launch_scan<1, KR, true>(on, a, lds, out_nodes, out_dist, out_counts);
+    }
   }
+  switch (qt) {
+    case 4: return launch_scan<4, KR, false>(on, a, lds, out_nodes, out_dist, out_counts);
+    case 2: return launch_scan<2, KR, false>(on, a, lds, out_nodes, out_dist, out_counts);
+    default: return launch_scan<1, KR, false>(on, a, lds, out_nodes, out_dist, out_counts);
+  }
+}
+
+// add, residual codes: rows (in HBM) and their lists to flat codes and row terms
+void launch_residual_encode(fvdb_pq* pq, fvdb_ctx* on, const IvfRpqEncodeArgs& a) {
+  const dim3 grid(cdiv(cdiv(a.n, 64), 4)), block(256);
+  switch (pq->dmax) {
+    case 8: hipLaunchKernelGGL(ivfrpq_encode_kernel<8>, grid, block, 0, on->stream, a); break;
+    case 32: hipLaunchKernelGGL(ivfrpq_encode_kernel<32>, grid, block, 0, on->stream, a); break;
+    default: hipLaunchKernelGGL(ivfrpq_encode_kernel<128>, grid, block, 0, on->stream, a); break;
+  }
+}
+
+// search, residual codes: base[Bs][np] and the inner-product tables of a sub-batch (probes: the sub-batch's rows)
+int launch_residual_tables(fvdb_ivfpq* ix, fvdb_ctx* ctx, IvfPqSlot& S, const float* qs, uint32_t Bs, uint32_t np, const uint32_t* probes) {
+  const PqGeom g = ix->pq->g;
+  const float* qp = qs;
+  if (ix->dpad != g.d) {
+    HIPCHK(ctx, S.qres.ensure((size_t)Bs * ix->dpad * 4));
+    hipLaunchKernelGGL(pq_pad_queries_kernel, dim3(cdiv((uint64_t)Bs * ix->dpad, 256)), dim3(256), 0, ctx->stream, qs, g.d, ix->dpad, (uint64_t)Bs,
+                       S.qres.as<float>());
+    qp = S.qres.as<float>();
+  }
+  HIPCHK(ctx, S.base.ensure((size_t)Bs * np * 4));
+  hipLaunchKernelGGL(ivfrpq_base_kernel, dim3(cdiv(cdiv(np, 16), 4), Bs), dim3(256), 0, ctx->stream, qp, ix->cent.as<float>(), ix->dpad, probes, Bs,
+                     np, ix->nlist, S.base.as<float>());
+  hipLaunchKernelGGL(ivfrpq_table_kernel<(int)kIvfRpqTableQueries>, dim3(g.m, cdiv(Bs, kIvfRpqTableQueries)), dim3(256), 0, ctx->stream, qs,
+                     ix->pq->books.as<float>(), g, Bs, S.tables.as<float>());
+  HIPCHK(ctx, hipGetLastError());
+  return FVDB_OK;
+}
+
+// residual codes: the index's own padded copy of the centroids, after they were trained or set
+int copy_centroids(fvdb_ivfpq* ix) {
+  fvdb_ctx* ctx = ix->ctx;
+  const uint32_t d = ix->pq->g.d;
+  std::vector<float> c((size_t)ix->nlist * d), padded((size_t)ix->nlist * ix->dpad, 0.0f);
+  const int rc = fvdb_ivf_get_centroids(ix->ivf, c.data());
+  if (rc) return rc;
+  for (uint32_t L = 0; L < ix->nlist; ++L) memcpy(&padded[(size_t)L * ix->dpad], &c[(size_t)L * d], (size_t)d * 4);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, upload(ctx, ix->cent.p, padded.data(), padded.size() * 4));
+  return FVDB_OK;
 }
 
 template <typename RT>
@@ -159,11 +217,8 @@ int upload_lists(fvdb_ivfpq* ix) {
   return FVDB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fvdb_ivfpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq** out) {
+// both kinds of index: fvdb_ivfpq_create and fvdb_ivfrpq_create
+int create_index(fvdb_pq* pq, uint32_t nlist, int refine_dtype, bool residual, fvdb_ivfpq** out) {
   if (!pq || !out) return FVDB_E_INVALID;
   *out = nullptr;
   fvdb_ctx* ctx = pq->ctx;
@@ -185,6 +240,9 @@ int fvdb_ivfpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq*
   int rc = fvdb_ivf_create(ctx, pq->g.d, nlist, &ix->ivf);
   if (!rc && refine_dtype != FVDB_PQ_NO_REFINE) rc = fvdb_store_create_ex(ctx, pq->g.d, 1024, refine_dtype, &ix->store);
   if (!rc && (ix->list_off.exact((size_t)(nlist + 1) * 4) != hipSuccess || ix->list_len.exact((size_t)nlist * 4) != hipSuccess)) rc = FVDB_E_OOM;
+  ix->residual = residual;
+  ix->dpad = (pq->g.d + 3u) & ~3u;
+  if (!rc && residual && ix->cent.exact((size_t)nlist * ix->dpad * 4) != hipSuccess) rc = FVDB_E_OOM;
   if (!rc) rc = upload_lists(ix);
   if (rc) {
     fvdb_ivfpq_destroy(ix);
@@ -192,6 +250,18 @@ int fvdb_ivfpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq*
   }
   *out = ix;
   return FVDB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fvdb_ivfpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq** out) {
+  return create_index(pq, nlist, refine_dtype, /*residual=*/false, out);
+}
+
+int fvdb_ivfrpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq** out) {
+  return create_index(pq, nlist, refine_dtype, /*residual=*/true, out);
 }
 
 void fvdb_ivfpq_destroy(fvdb_ivfpq* ix) {
@@ -206,7 +276,8 @@ void fvdb_ivfpq_destroy(fvdb_ivfpq* ix) {
 int fvdb_ivfpq_train(fvdb_ivfpq* ix, const float* x, uint64_t n, uint32_t max_iterations, uint64_t seed, fvdb_train_result* out) {
   if (!ix) return FVDB_E_INVALID;
   if (ix->n) FAIL(ix->ctx, FVDB_E_UNSUPPORTED, "IVF-PQ: the centroids of an index with rows cannot be replaced");
-  const int rc = fvdb_ivf_train(ix->ivf, x, n, max_iterations, seed, out);
+  int rc = fvdb_ivf_train(ix->ivf, x, n, max_iterations, seed, out);
+  if (!rc && ix->residual) rc = copy_centroids(ix);
   if (!rc) ix->trained = true;
   return rc;
 }
@@ -214,7 +285,8 @@ int fvdb_ivfpq_train(fvdb_ivfpq* ix, const float* x, uint64_t n, uint32_t max_it
 int fvdb_ivfpq_set_centroids(fvdb_ivfpq* ix, const float* centroids) {
   if (!ix) return FVDB_E_INVALID;
   if (ix->n) FAIL(ix->ctx, FVDB_E_UNSUPPORTED, "IVF-PQ: the centroids of an index with rows cannot be replaced");
-  const int rc = fvdb_ivf_set_centroids(ix->ivf, centroids);
+  int rc = fvdb_ivf_set_centroids(ix->ivf, centroids);
+  if (!rc && ix->residual) rc = copy_centroids(ix);
   if (!rc) ix->trained = true;
   return rc;
 }
@@ -229,8 +301,8 @@ uint64_t fvdb_ivfpq_rows(fvdb_ivfpq* ix) { return ix ? ix->n : 0; }
 uint64_t fvdb_ivfpq_live(fvdb_ivfpq* ix) { return ix ? ix->live : 0; }
 uint64_t fvdb_ivfpq_bytes(fvdb_ivfpq* ix) {
   if (!ix) return 0;
-  return ix->blocks * ((uint64_t)ix->pq->m16() * 1024 + 64 * 8 + 4) + ix->n * 12 + (uint64_t)(2 * ix->nlist + 1) * 4 +
-         (ix->store ? fvdb_store_bytes(ix->store) : 0);
+  return ix->blocks * ((uint64_t)ix->pq->m16() * 1024 + 64 * 8 + 4 + (ix->residual ? 64 * 4 : 0)) + ix->n * 12 +
+         (uint64_t)(2 * ix->nlist + 1) * 4 + (ix->store ? fvdb_store_bytes(ix->store) : 0);
 }
 
 int fvdb_ivfpq_list_sizes(fvdb_ivfpq* ix, uint64_t* out) {
@@ -313,6 +385,7 @@ int fvdb_ivfpq_add(fvdb_ivfpq* ix, const uint64_t* ids, const float* rows, uint6
     HIPCHK(ctx, grow_keeping(ix->seq_of_row, nb * 64 * 4, ob * 64 * 4, /*zero_rest=*/true, ctx->stream));
     HIPCHK(ctx, grow_keeping(ix->dead, nb * 64 * 4, ob * 64 * 4, /*zero_rest=*/false, ctx->stream));
     launch_fill(ctx, ix->dead.as<uint32_t>() + ob * 64, (nb - ob) * 64, 1u);
+    if (ix->residual) HIPCHK(ctx, grow_keeping(ix->term_of_row, nb * 64 * 4, ob * 64 * 4, /*zero_rest=*/true, ctx->stream));
     ix->cap_blocks = nb;
   }
   if (ix->n + n > ix->cap_seq) {
@@ -326,11 +399,32 @@ int fvdb_ivfpq_add(fvdb_ivfpq* ix, const uint64_t* ids, const float* rows, uint6
   HIPCHK(ctx, ix->s_rows.ensure(n * 4));
   HIPCHK(ctx, upload(ctx, ix->s_in.p, rows, n * d * 4));
   HIPCHK(ctx, upload(ctx, ix->s_rows.p, dest.data(), n * 4));
-  // the quantizer's own encode to flat codes, then the place kernel packs them into the destination blocks
-  rc = fvdb_pq_encode_dev(pq, ctx, ix->s_in.as<float>(), n, ix->s_flat.as<uint8_t>());
-  if (rc) return rc;
+  // the quantizer's own encode to flat codes (residual codes: of row - centroid, with the row terms, in one kernel), then
+  // the place kernel packs them into the destination blocks
+  if (ix->residual) {
+    HIPCHK(ctx, ix->s_cluster.ensure(n * 4));
+    HIPCHK(ctx, ix->s_term.ensure(n * 4));
+    HIPCHK(ctx, upload(ctx, ix->s_cluster.p, cluster.data(), n * 4));
+    IvfRpqEncodeArgs e{};
+    e.rows = ix->s_in.as<float>();
+    e.cluster = ix->s_cluster.as<uint32_t>();
+    e.cent = ix->cent.as<float>();
+    e.books = pq->books.as<float>();
+    e.g = pq->g;
+    e.n = n;
+    e.nlist = ix->nlist;
+    e.dpad = ix->dpad;
+    e.flat = ix->s_flat.as<uint8_t>();
+    e.term = ix->s_term.as<float>();
+    launch_residual_encode(pq, ctx, e);
+    HIPCHK(ctx, hipGetLastError());
+  } else {
+    rc = fvdb_pq_encode_dev(pq, ctx, ix->s_in.as<float>(), n, ix->s_flat.as<uint8_t>());
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL(ivfpq_place_kernel, dim3(cdiv(n * m16, 256)), dim3(256), 0, ctx->stream, ix->s_flat.as<uint8_t>(), ix->s_rows.as<uint32_t>(),
-                     n, m, m16, (uint32_t)ix->n, ix->codes.as<uint4>(), ix->seq_of_row.as<uint32_t>(), ix->row_of_seq.as<uint32_t>());
+                     n, m, m16, (uint32_t)ix->n, ix->codes.as<uint4>(), ix->seq_of_row.as<uint32_t>(), ix->row_of_seq.as<uint32_t>(),
+                     ix->residual ? ix->s_term.as<float>() : (const float*)nullptr, ix->term_of_row.as<float>());
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, upload(ctx, ix->ids.as<uint64_t>() + ix->n, ids, n * 8));
   if (ix->store) {
@@ -417,7 +511,14 @@ int fvdb_ivfpq_search_dev_slot(fvdb_ivfpq* ix, fvdb_ctx* on, uint32_t slot, cons
     a.S = slices_for(cdiv(Bs, qt), qt, np, (uint32_t)ctx->num_cus);
     S.last_S = a.S;
     HIPCHK(ctx, S.tables.ensure((size_t)Bs * g.m * g.ka * 4));
-    hipLaunchKernelGGL(pq_table_kernel, dim3(g.m, Bs), dim3(256), 0, ctx->stream, qs, pq->books.as<float>(), g, S.tables.as<float>());
+    if (ix->residual) {
+      rc = launch_residual_tables(ix, ctx, S, qs, Bs, np, S.probes.as<uint32_t>() + (size_t)b0 * np);
+      if (rc) return rc;
+      a.term_of_row = ix->term_of_row.as<float>();
+      a.base = S.base.as<float>();
+    } else {
+      hipLaunchKernelGGL(pq_table_kernel, dim3(g.m, Bs), dim3(256), 0, ctx->stream, qs, pq->books.as<float>(), g, S.tables.as<float>());
+    }
     HIPCHK(ctx, S.part.ensure((size_t)a.S * Bs * kk * 8));
     a.codes = ix->codes.as<uint4>();
     a.dead = dead_dev ? dead_dev : ix->dead.as<uint32_t>();

@@ -39,19 +39,25 @@ struct IvfPqScanArgs {
   uint64_t* part;                // [S][B][k] keys (adc bits << 32 | seq), ~0 = none
   unsigned long long* stats;     // [2]: rows scored, (query, list) pairs; added to
   uint32_t nlist, np, m, m16, ka, ts /* floats of a table row in LDS: ka or ka + 1 */, B, k, S;
+  // residual codes (RES; kernels_ivfrpq.h), null otherwise: `tables` then holds inner products
+  const float* term_of_row;      // [pool rows] the row term r^.(r^ + 2c)
+  const float* base;             // [B][np] the squared fold of the query against the centroid of each probe rank
 };
 
 // The blocks of a wave's lists, in walk order: ranks r, r + S, ... of one query, every list's blocks in fill order.
-// Wave-uniform throughout.  next() past the last block returns 0 and is never dereferenced.
+// Wave-uniform throughout.  next() past the last block returns 0 and is never dereferenced.  `rank` is the probe rank of
+// the list that the block last returned belongs to (the residual scan's base is per rank).
 struct IvfPqWalk {
   const uint32_t* pr;  // the query's probe row
   const uint32_t* list_off;
   const uint32_t* list_blocks;
   uint32_t r, S, np, nlist, pos, end;
+  uint32_t rank = 0;
   __device__ __forceinline__ uint32_t next() {
     while (pos == end) {
       if (r >= np) return 0u;
       const uint32_t L = rfl(pr[r]);
+      if (L < nlist) rank = r;
       r += S;
       if (L < nlist) {
         pos = rfl(list_off[L]);
@@ -69,7 +75,11 @@ struct IvfPqWalk {
 // reads what the first brought in), so neither a block's nor a list's end drains the pipeline.  A block's dead words and
 // seqs are loaded when the fold reaches the block before it.  CH blocks are folded side by side in independent add
 // chains (their words alternate in the sequence); the index launches kIvfPqChains.
-template <int QT, int KR, int CH>
+//
+// RES (residual codes): the tables are inner products, the fold side also carries the probe rank
+// of each block, and with a block's dead words and seqs it loads the lane's row term and (one address a wave) the base
+// of the block's list; the block-end step is sqrt(max((base + term) - 2 ip, +0)).  Without RES none of this is compiled.
+template <int QT, int KR, int CH, bool RES = false>
 __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const IvfPqScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_tab[];  // [QT][m][ts]
   constexpr int AH = kIvfPqAhead;
@@ -121,14 +131,21 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const IvfPqScanArgs a) 
   // a group's blocks and the next group's; a block past the wave's last reads as pool block 0, whose words are loaded
   // (the pool is not empty when nblk > 0) and whose rows are dropped
   uint32_t fblk[CH], fnxt[CH], cblk[CH], cnxt[CH], fch = 0;
+  uint32_t crk[CH], cnrk[CH];  // RES: the probe ranks of cblk and cnxt
 #pragma unroll
   for (int c = 0; c < CH; ++c) fblk[c] = fw.next();
 #pragma unroll
   for (int c = 0; c < CH; ++c) fnxt[c] = fw.next();
 #pragma unroll
-  for (int c = 0; c < CH; ++c) cblk[c] = cw.next();
+  for (int c = 0; c < CH; ++c) {
+    cblk[c] = cw.next();
+    crk[c] = cw.rank;
+  }
 #pragma unroll
-  for (int c = 0; c < CH; ++c) cnxt[c] = cw.next();
+  for (int c = 0; c < CH; ++c) {
+    cnxt[c] = cw.next();
+    cnrk[c] = cw.rank;
+  }
   auto fetch = [&](const int sel) {  // sel = position in the unrolled body mod CH: a constant after unrolling
     const uint4 v = a.codes[((size_t)fblk[sel] * a.m16 + fch) * 64 + (uint32_t)lane];
     if (sel == CH - 1 && ++fch == a.m16) {
@@ -149,13 +166,22 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const IvfPqScanArgs a) 
     if ((uint64_t)u < nw) buf[u] = fetch(u % CH);
   }
   uint32_t dw[CH], sq[CH];  // of the lane's rows in the blocks being folded
+  // RES: the lane's row term, and the base of the block's list.  The base is one address a wave but stays in a VGPR:
+  // moving it to an SGPR where it is loaded waits for that load, and with it for every code word in flight (section 9zd)
+  float tm[CH], bs[CH];
+  const float* basew = a.base + (size_t)b * a.np;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     dw[c] = 1u;
     sq[c] = kInf32;
+    tm[c] = bs[c] = 0.0f;
     if ((uint32_t)c < nblk) {
       dw[c] = a.dead[(size_t)cblk[c] * 64 + (uint32_t)lane];
       sq[c] = a.seq_of_row[(size_t)cblk[c] * 64 + (uint32_t)lane];
+      if (RES) {
+        tm[c] = a.term_of_row[(size_t)cblk[c] * 64 + (uint32_t)lane];
+        bs[c] = basew[crk[c]];
+      }
     }
   }
 
@@ -181,19 +207,32 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const IvfPqScanArgs a) 
           uint32_t chi[CH], seq[CH];
 #pragma unroll
           for (int c = 0; c < CH; ++c) {
-            chi[c] = dw[c] == 0u ? __float_as_uint(sqrtf(acc[c][0])) : kInf32;
+            float sum = acc[c][0];
+            if (RES) {
+              const float v = (bs[c] + tm[c]) - (sum + sum);
+              sum = v > 0.0f ? v : 0.0f;
+            }
+            chi[c] = dw[c] == 0u ? __float_as_uint(sqrtf(sum)) : kInf32;
             acc[c][0] = 0.0f;
             seq[c] = sq[c];
             cblk[c] = cnxt[c];
+            crk[c] = cnrk[c];
           }
 #pragma unroll
-          for (int c = 0; c < CH; ++c) cnxt[c] = cw.next();
+          for (int c = 0; c < CH; ++c) {
+            cnxt[c] = cw.next();
+            cnrk[c] = cw.rank;
+          }
 #pragma unroll
           for (int c = 0; c < CH; ++c) {  // the next group's words, a group ahead of their use
             dw[c] = 1u;
             if (done + CH + (uint32_t)c < nblk) {
               dw[c] = a.dead[(size_t)cblk[c] * 64 + (uint32_t)lane];
               sq[c] = a.seq_of_row[(size_t)cblk[c] * 64 + (uint32_t)lane];
+              if (RES) {
+                tm[c] = a.term_of_row[(size_t)cblk[c] * 64 + (uint32_t)lane];
+                bs[c] = basew[crk[c]];
+              }
             }
           }
 #pragma unroll
@@ -227,7 +266,8 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const IvfPqScanArgs a) 
 // (code 0 beyond m) into the row's word of that chunk
 static __global__ void ivfpq_place_kernel(const uint8_t* __restrict__ flat /* [n][m] */, const uint32_t* __restrict__ dest, uint64_t n,
                                           uint32_t m, uint32_t m16, uint32_t seq0, uint4* __restrict__ codes,
-                                          uint32_t* __restrict__ seq_of_row, uint32_t* __restrict__ row_of_seq) {
+                                          uint32_t* __restrict__ seq_of_row, uint32_t* __restrict__ row_of_seq,
+                                          const float* __restrict__ term /* [n], or null */, float* __restrict__ term_of_row) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * m16) return;
   const uint64_t i = e / m16;
@@ -240,6 +280,7 @@ static __global__ void ivfpq_place_kernel(const uint8_t* __restrict__ flat /* [n
   if (chunk == 0) {
     seq_of_row[row] = seq0 + (uint32_t)i;
     row_of_seq[seq0 + i] = row;
+    if (term) term_of_row[row] = term[i];  // residual codes: the row term travels with the row
   }
 }
 

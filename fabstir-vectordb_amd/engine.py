@@ -1019,13 +1019,21 @@ class IVFPQIndex:
     """An inverted file whose lists hold product-quantized rows (fvdb_ivfpq) over a trained
     ProductQuantizer: centroids, assignment and probe order are the IVF-flat index's, codes (not residual), ADC score and
     refine are PQIndex's, and each query's probed lists are walked by waves that hold its table in LDS.  Ties go to the
-    row added earlier; with every list probed the result is PQIndex.search's."""
+    row added earlier; with every list probed the result is PQIndex.search's.
 
-    def __init__(self, ctx, pq, nlist, refine_rows=None):
+    residual=True (fvdb_ivfrpq_create): a row's codes are those of row - centroid of its list, and
+    the score is sqrt(max(|q - c|^2 + r^.(r^ + 2c) - 2 q.r^, 0)) from one inner-product table a query, one f32 a row and
+    one f32 a (query, list).  The quantizer must have been trained on residuals: train or choose the centroids,
+    pq.train(ivf_residuals(ctx, centroids, rows)[0], ...), IVFPQIndex(..., residual=True), set_centroids, add.  With
+    every list probed the result is then NOT PQIndex.search's."""
+
+    def __init__(self, ctx, pq, nlist, refine_rows=None, residual=False):
         self.ctx, self.lib, self.pq, self.d, self.nlist, self.refine_rows = ctx, ctx.lib, pq, pq.d, int(nlist), refine_rows
+        self.residual = bool(residual)
         code = _capi.PQ_NO_REFINE if refine_rows is None else row_dtype_code(refine_rows)
         h = C.c_void_p()
-        ctx.check(self.lib.fvdb_ivfpq_create(pq.h, self.nlist, code, C.byref(h)))
+        create = self.lib.fvdb_ivfrpq_create if self.residual else self.lib.fvdb_ivfpq_create
+        ctx.check(create(pq.h, self.nlist, code, C.byref(h)))
         self.h = h
 
     def close(self):
@@ -1108,6 +1116,19 @@ class IVFPQIndex:
         self.ctx.check(self.lib.fvdb_ivfpq_search(self.h, _ptr(q, f32p), B, k, int(nprobe), int(fetch_k or 0), ap, na,
                                                   _ptr(ids, u64p), _ptr(dist, f32p), _ptr(counts, u32p)))
         return SearchResults(ids, dist, counts)
+
+
+def ivf_residuals(ctx, centroids, rows):
+    """(residuals, lists): every row minus the centroid DeviceIVF.assign chooses for it (an f32 subtract, bit for bit what
+    IVFPQIndex(residual=True).add encodes), and those lists.  The training rows of a quantizer for residual codes."""
+    c, x = _rows_2d(centroids), _rows_2d(rows)
+    ivf = DeviceIVF(ctx, c.shape[1], c.shape[0])
+    try:
+        ivf.set_centroids(c)
+        lists = ivf.assign(x)
+    finally:
+        ivf.close()
+    return x - c[lists], lists
 
 
 def batch_normalize(ctx, rows):

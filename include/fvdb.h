@@ -1501,7 +1501,8 @@ int fvdb_ivfsq8_search_dev_slot(fvdb_ivfsq8* ix, fvdb_ctx* on, uint32_t slot, co
  * FVDB_E_INVALID.
  *
  * Codes are NOT residual: a row is encoded by the quantizer's own encode rule on the row itself, so the ADC table of a
- * query is the per-query table of "product quantization", whatever list a row sits in.
+ * query is the per-query table of "product quantization", whatever list a row sits in.  (An index created by
+ * fvdb_ivfrpq_create differs in exactly this: "IVF over residual PQ codes" below.)
  *
  * Centroids, assignment and probe order are the IVF-flat index's own, exactly as for "IVF over SQ8 codes": an fvdb_ivf
  * that never receives rows, fvdb_ivf_train / fvdb_ivf_set_centroids, fvdb_ivf_assign and fvdb_ivf_coarse_dev_slot.
@@ -1564,6 +1565,38 @@ int fvdb_ivfpq_search(fvdb_ivfpq* ix, const float* q, uint32_t B, uint32_t k, ui
 int fvdb_ivfpq_search_dev_slot(fvdb_ivfpq* ix, fvdb_ctx* on, uint32_t slot, const float* q_dev, uint32_t B, uint32_t k, uint32_t nprobe,
                                uint32_t fetch_k, const uint32_t* dead_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                uint32_t* out_counts_dev);
+
+/* ---- IVF over residual PQ codes --------------------------------------
+ * "IVF over PQ codes" with the codes of a row taken from its residual to its list's centroid ("IVFADC").  The object
+ * is an fvdb_ivfpq in residual mode: every fvdb_ivfpq_ call above serves it, with the semantics and refusals stated
+ * there, except for what a row's codes and a candidate's score are.  All arithmetic is f32, multiply and add separate.
+ *
+ * With r^ the decoded residual of a row and c its list's centroid,
+ *     |q - c - r^|^2 = |q - c|^2 + r^.(r^ + 2c) - 2 q.r^
+ * and the three parts are computed apart, so that the table a query keeps on chip does not depend on the list:
+ *   residual of a row   r_i = x_i - c_i, c the centroid fvdb_ivf_assign chooses; the codes are the quantizer's own encode
+ *                       rule on r (the fold t = r_i - cb_i; s = s + t*t, the root, strict <, first minimum).
+ *   row term            t_row = fold over i = 0..d-1 ascending of s = s + r^_i * (r^_i + (c_i + c_i)), from +0: one f32
+ *                       per pool row, kept beside the dead word and seq_of_row.
+ *   query table         P[b][j][code] = fold over the dims of subspace j ascending of s = s + q_i * cb_i, from +0: inner
+ *                       products, the same for every list.
+ *   base                base[b][r] = fold over all d of t = q_i - c_i; s = s + t*t for the centroid of probe rank r,
+ *                       without the root.
+ *   score               ip = ((P[0][c_0] + P[1][c_1]) + ...) + P[m-1][c_{m-1}], j ascending;
+ *                       v = (base + t_row) - (ip + ip); adc = sqrtf(v > 0 ? v : +0).
+ * The key is (bits(adc) << 32) | seq; selection, ties, dead rows, the allow-set and the fetch_k refine are those of
+ * "IVF over PQ codes".  The refine re-scores against the stored ORIGINAL rows (store row = seq).
+ *
+ * The quantizer must have been trained on residuals (rows minus their assigned centroids): that is the caller's job,
+ * and nothing checks it.  A quantizer trained on the rows themselves works and gains nothing.
+ *
+ * With nprobe >= nlist the result is NOT fvdb_pq_index_search's: the codes differ from the flat index's and the score is
+ * formed differently.  Rows with large norms lose bits: t_row and 2 ip grow with |c| |r^| and cancel in v, so adc carries
+ * an absolute error of the order of 2^-24 (base + |t_row| + 2 |ip|), which a row far from the origin but close to the
+ * query feels.  A v that rounds to or below zero gives adc = +0.
+ *
+ * fvdb_ivfpq_bytes counts the row terms (4 bytes a pool row); fvdb_ivfpq_info_t is unchanged. */
+int fvdb_ivfrpq_create(fvdb_pq* pq, uint32_t nlist, int refine_dtype, fvdb_ivfpq** out);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,12 @@ around calls that end in a synchronise; the runs alternate over two rounds, so a
 them.  Prints one JSON object and, with --out, writes it to a file.
 
     python tools/ivfpq_bench.py --n-vectors 1000000 --out profiles/ivfpq_bench.json
+
+--residual measures the residual index instead of the other index kinds: a second quantizer is
+trained on ivf_residuals of the same training rows, a residual IVFPQIndex is built over the same centroids and rows, and
+at each nprobe the plain and the residual ADC search alternate, again over two rounds.
+
+    python tools/ivfpq_bench.py --n-vectors 1000000 --residual --out profiles/ivfrpq_bench.json
 """
 import argparse
 import json
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--train-rows", type=int, default=50_000)
     ap.add_argument("--iterations", type=int, default=10)
+    ap.add_argument("--residual", action="store_true", help="plain against residual codes, nothing else")
     ap.add_argument("--out")
     a = ap.parse_args()
 
@@ -58,7 +65,8 @@ def main():
            "timing": "host clock around host-form calls, which synchronise; queries uploaded and results downloaded inside"}
 
     pq = fv.ProductQuantizer(ctx, d, a.subspaces, a.centroids)
-    pq.train(x[np.random.default_rng(0).choice(N, min(N, a.train_rows), replace=False)], a.iterations, seed=1)
+    pq_rows = x[np.random.default_rng(0).choice(N, min(N, a.train_rows), replace=False)]
+    pq.train(pq_rows, a.iterations, seed=1)
     ix = fv.IVFPQIndex(ctx, pq, a.nlist, refine_rows="f32")
     res["train"] = ix.train(x[np.random.default_rng(0).choice(N, min(N, 100_000), replace=False)], max_iterations=10, seed=1)
     t = time.perf_counter()
@@ -66,6 +74,8 @@ def main():
         ix.add(ids[c:c + 100_000], x[c:c + 100_000])
     res["add_rows_per_s"] = round(N / (time.perf_counter() - t))  # host check, assign, upload, encode, place, refine rows, tables
     note(f"IVFPQIndex built: {res['add_rows_per_s']} rows/s")
+    if a.residual:
+        return residual_runs(fv, ctx, a, res, ix, pq_rows, x, ids, queries)
     flat = fv.PQIndex(ctx, pq)
     sq8 = fv.IVFSQ8Index(ctx, d, a.nlist)
     sq8.set_centroids(ix.centroids())
@@ -110,11 +120,44 @@ def main():
     def hits(r):  # SearchResults, or DeviceIVF's (ids, distances, counts)
         return (r.ids, r.counts) if hasattr(r, "ids") else (r[0], r[2])
     res["recall"] = {n: round(float(np.mean([recall_at_k(*hits(fn(q)), t.ids, k) for q, t in zip(queries, truth)])), 4) for n, fn in runs.items()}
+    report(a, res)
 
+
+def report(a, res):
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
+
+
+def residual_runs(fv, ctx, a, res, ix, pq_rows, x, ids, queries):
+    """the plain index `ix` against a residual one over the same centroids and rows: ADC q/s alternating, recall, bytes"""
+    N, d, k = a.n, a.dim, a.k
+    rpq = fv.ProductQuantizer(ctx, d, a.subspaces, a.centroids)
+    rpq.train(fv.ivf_residuals(ctx, ix.centroids(), pq_rows)[0], a.iterations, seed=1)
+    rix = fv.IVFPQIndex(ctx, rpq, a.nlist, residual=True)
+    rix.set_centroids(ix.centroids())
+    t = time.perf_counter()
+    for c in range(0, N, 100_000):
+        rix.add(ids[c:c + 100_000], x[c:c + 100_000])
+    res["residual_add_rows_per_s"] = round(N / (time.perf_counter() - t))
+    note(f"residual IVFPQIndex built: {res['residual_add_rows_per_s']} rows/s")
+    res["bytes_per_row"] = {"ivfpq_codes_and_tables": (ix.bytes() - 4 * d * N) / N, "ivfrpq_codes_and_tables": rix.bytes() / N}
+    g = fv.HNSWIndex(ctx, max_connections=2, max_connections_layer_0=2, ef_construction=8)
+    g.bulk_build(ids, x, levels=np.zeros(N, np.int64))
+    truth = [g.search_exact(q, k) for q in queries]
+    runs = {}
+    for np_ in a.nprobe:
+        runs[f"ivfpq_adc_np{np_}"] = lambda q, p=np_: ix.search(q, k, p)
+        runs[f"ivfrpq_adc_np{np_}"] = lambda q, p=np_: rix.search(q, k, p)
+    res["info"], res["qps"] = rix.info(), {n: [] for n in runs}
+    for _ in range(2):
+        for n, fn in runs.items():
+            res["qps"][n].append(round(rate(fn, queries, a.reps), 1))
+            note(f"{n}: {res['qps'][n][-1]} q/s")
+    res["recall"] = {n: round(float(np.mean([recall_at_k(r.ids, r.counts, t.ids, k) for r, t in zip(map(fn, queries), truth)])), 4)
+                     for n, fn in runs.items()}
+    report(a, res)
 
 
 if __name__ == "__main__":
